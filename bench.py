@@ -9,8 +9,8 @@ entropy coding, bitstream packing on the GPU -> complete OBU bitstream on the ho
 
 The headline evaluates all 13 luma intra modes for every block (BASELINE config 2: "DCT/ADST + directional intra pred + CDEF").
 
-At N=1 with default flags the same JSON line carries a `configs` object with the other BASELINE
-configurations a single GPU can run (each with its own fps, roofline and stage times): config 2 with the cheapest
+A plain run measures the headline workload only.  With --full, at N=1 with default flags, the same JSON line also carries a
+`configs` object with the other BASELINE configurations a single GPU can run (each with its own fps, roofline and stage times): config 2 with the cheapest
 candidate set {DC, V, H}, at 8 bit, with 64x64 blocks and at the quantiser that matches libaom's quality; config 3 (1080p IPPP, 1 and
 4 chunks in flight); config 4's per-GPU unit (4K 10-bit IPPP chunk); config 5's (8K 10-bit HDR chunk with a film-grain table) and the
 reference's production operating point (av1an.rs:14).
@@ -20,9 +20,11 @@ when it is run without a launcher): scene-chunks are independent (SURVEY.md §8e
 no data-path collective; weak scaling.  `--workload cfg4` instead shards BASELINE config 4's job of 8 4K chunks over the ranks with the
 product's placement rule (strong scaling).  The only collectives are the timing barrier and the MAX over ranks.
 
-CPU baseline (reported only; rank 0, N=1): runs BEFORE anything touches the GPU, in SURVEY §8d's order -
+CPU baseline (--full only; reported only; rank 0, N=1): runs BEFORE anything touches the GPU, in SURVEY §8d's order -
 the reference's own av1an / SVT-AV1 if on PATH, else libaom 3.13.2 through the image's libavif (8-bit: this
 libaom has no high-bit-depth build), else the build's own C restatement ("port").
+
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0's bitstream, frame sizes and PSNR) as .npy files.
 
 Prints ONE JSON line on rank 0.
 """
@@ -387,8 +389,9 @@ def algorithmic_bytes(a, rep):
     return stage, step
 
 
-def run_workload(av1mi, torch, a, dev, local_rank, rank, world, steps, warmup, barrier, max_over_ranks):
-    """`steps` timed steps of workload `a` on this rank; returns (elapsed seconds (max over ranks), stage ms per step, last report)"""
+def run_workload(av1mi, torch, a, dev, local_rank, rank, world, steps, warmup, barrier, max_over_ranks, keep_outputs=False):
+    """`steps` timed steps of workload `a` on this rank; returns (elapsed seconds (max over ranks), stage ms per step, last report,
+    the last step's encode_chunk results: bitstreams included only with keep_outputs)"""
     w, h, bd, n = a["width"], a["height"], a["bit_depth"], a["frames"]
     # the job's scene-chunks over the ranks by the product's own placement rule (av1mi_chunk_owner): by default a job of `world` chunks, one
     # per GPU (weak scaling); job_chunks = J: a job of J chunks whatever the number of GPUs (strong scaling; BASELINE config 4: J = 8)
@@ -424,43 +427,46 @@ def run_workload(av1mi, torch, a, dev, local_rank, rank, world, steps, warmup, b
         rep.bytes = sum(r.bytes for r in res)
         return rep
 
-    def step():
+    def step(copy_out=False):
+        """one step: (merged report, the encode_chunk results - (bitstream or None, frame sizes, report, None) per chunk)"""
         import threading
         if job:   # this rank's chunks of the job, C_ of them in flight
             if not clips:
-                return None
+                return None, []
             res = [None] * len(clips)
 
             def work_job(i):
                 for k in range(i, len(clips), C_):
-                    res[k] = ctxs[i].encode_chunk(params, clips[k].data_ptr(), n, on_device=True, copy_out=False)[2]
+                    res[k] = ctxs[i].encode_chunk(params, clips[k].data_ptr(), n, on_device=True, copy_out=copy_out)
             th = [threading.Thread(target=work_job, args=(i,)) for i in range(min(C_, len(clips)))]
             for t in th:
                 t.start()
             for t in th:
                 t.join()
-            return merge(res)
+            return merge([r[2] for r in res]), res
         if C_ == 1:
-            return ctxs[0].encode_chunk(params, d_frames.data_ptr(), n, on_device=True, copy_out=False)[2]
+            r = ctxs[0].encode_chunk(params, d_frames.data_ptr(), n, on_device=True, copy_out=copy_out)
+            return r[2], [r]
         res = [None] * C_
 
         def work(i):   # every context encodes the whole chunk (its own copy of the work)
-            res[i] = ctxs[i].encode_chunk(params, d_frames.data_ptr(), n, on_device=True, copy_out=False)[2]
+            res[i] = ctxs[i].encode_chunk(params, d_frames.data_ptr(), n, on_device=True, copy_out=copy_out)
         th = [threading.Thread(target=work, args=(i,)) for i in range(C_)]
         for t in th:
             t.start()
         for t in th:
             t.join()
-        return merge(res)
+        return merge([r[2] for r in res]), res
     try:
         for _ in range(warmup):
             step()
         barrier()
         t0 = time.perf_counter()
         stage = {"recon": 0.0, "cdef": 0.0, "entropy": 0.0, "symbolize": 0.0, "pack": 0.0, "d2h": 0.0}
-        rep = None
-        for _ in range(steps):
-            rep = step()
+        rep, outs = None, []
+        for i in range(steps):
+            # keep_outputs: the last timed step also copies its bitstreams into Python objects (--dump-outputs)
+            rep, outs = step(copy_out=keep_outputs and i == steps - 1)
             if rep is None:   # a rank without a chunk of the job (more GPUs than chunks)
                 continue
             stage["recon"] += rep.ms_recon; stage["cdef"] += rep.ms_cdef; stage["entropy"] += rep.ms_entropy
@@ -474,7 +480,23 @@ def run_workload(av1mi, torch, a, dev, local_rank, rank, world, steps, warmup, b
     for s in stage:
         stage[s] /= steps
     stage["rangecode"] = stage["entropy"] - stage["symbolize"]
-    return elapsed, stage, rep
+    return elapsed, stage, rep, outs
+
+
+def dump_outputs(d, outs, max_bytes=64 << 20):
+    """What the last timed step handed its caller, per chunk k: chunk<k>_bitstream.npy (the bytes as float32), chunk<k>_frame_sizes.npy
+    and chunk<k>_psnr_db.npy (float64).  A bitstream too large for the budget is written as a fixed, seeded sample of its bytes,
+    in stream order."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    cap = (max_bytes - (1 << 20)) // 4 // max(1, len(outs))   # float32 bitstream entries per chunk; 1 MB left for the small arrays
+    for k, (data, sizes, rep, _) in enumerate(outs):
+        b = np.frombuffer(data, dtype=np.uint8)
+        if b.size > cap:
+            b = b[np.sort(np.random.default_rng(k).integers(0, b.size, cap))]
+        np.save(os.path.join(d, "chunk%d_bitstream.npy" % k), b.astype(np.float32))
+        np.save(os.path.join(d, "chunk%d_frame_sizes.npy" % k), np.asarray(sizes, dtype=np.float64))
+        np.save(os.path.join(d, "chunk%d_psnr_db.npy" % k), np.asarray([rep.psnr[i] for i in range(3)], dtype=np.float64))
 
 
 def result_of(av1mi, a, world, steps, elapsed, stage, rep, traffic_db):
@@ -624,7 +646,13 @@ def main():
                     help="intra mode candidate mask.  Default 0x1FFF: all 13 luma intra modes - BASELINE config 2 names \"directional intra pred\", so the "
                          "headline evaluates the directional, smooth and Paeth predictors for every block; 0x7 = {DC, V, H}, the library's own default")
     ap.add_argument("--configs", choices=["auto", "all", "none"], default="auto",
-                    help="the `configs` object with the other BASELINE configurations: auto = at N=1 when the workload flags are the defaults")
+                    help="with --full, the `configs` object with the other BASELINE configurations: auto = at N=1 when the workload flags are the defaults")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure what it does not need: the CPU baseline (unless --no-cpu-baseline) and the `configs` object")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (rank 0: bitstream bytes, frame sizes, PSNR per chunk) to DIR/<name>.npy.  "
+                         "That step then also copies its bitstream to the host inside the timed window, so ms_per_step is slightly higher "
+                         "than in a run without this option")
     ap.add_argument("--workload", choices=["cfg2", "cfg4"], default="cfg2",
                     help="cfg2 (default, the driver's line): every rank encodes its own 1080p chunk (weak scaling).  cfg4: BASELINE config 4 as "
                          "worded - a job of 8 scene-chunks of 4K 10-bit x 30 frames (IPPP), placed on the ranks by av1mi_chunk_owner (strong scaling)")
@@ -659,11 +687,11 @@ def main():
         "bit_depth", "block_log2", "static_cdf", "mode_mask", "partition_min"))
     if not default_flags:
         base["name"] = "custom"
-    with_configs = args.configs == "all" or (args.configs == "auto" and world == 1 and default_flags)
+    with_configs = args.full and (args.configs == "all" or (args.configs == "auto" and world == 1 and default_flags))
 
     # ---- CPU leg first: its worker pool forks, which must happen before this process (or torch) initialises HIP
     cpu = None
-    if world == 1 and rank == 0 and not args.no_cpu_baseline:
+    if args.full and world == 1 and rank == 0 and not args.no_cpu_baseline:
         cpu = cpu_baseline(base["width"], base["height"], base["bit_depth"], base["block_log2"], base["keyint"], base["mode_mask"])
 
     import torch
@@ -703,14 +731,17 @@ def main():
     except (OSError, KeyError, ValueError):
         pass
 
-    elapsed, stage, rep = run_workload(av1mi, torch, base, dev, local_rank, rank, world, args.steps, args.warmup, barrier, max_over_ranks)
+    elapsed, stage, rep, outs = run_workload(av1mi, torch, base, dev, local_rank, rank, world, args.steps, args.warmup, barrier, max_over_ranks,
+                                             keep_outputs=bool(args.dump_outputs) and rank == 0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs)
     head = result_of(av1mi, base, world, args.steps, elapsed, stage, rep, traffic_db)
     configs = {}
     if with_configs:
         for a in extra_configs(base):
             k, wu = max(2, min(args.steps, 6)), max(1, min(args.warmup, 2))
             try:
-                e2, s2, r2 = run_workload(av1mi, torch, a, dev, local_rank, rank, world, k, wu, barrier, max_over_ranks)
+                e2, s2, r2, _ = run_workload(av1mi, torch, a, dev, local_rank, rank, world, k, wu, barrier, max_over_ranks)
                 configs[a["name"]] = result_of(av1mi, a, world, k, e2, s2, r2, traffic_db)
             except Exception as e:   # a secondary configuration must not take the headline down; it is reported as failed
                 configs[a["name"]] = {"error": "%s: %s" % (type(e).__name__, e)}
