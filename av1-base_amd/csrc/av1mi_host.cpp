@@ -47,11 +47,10 @@ hipError_t av1mi_launch_lr(const Av1miDevParams *P, const void *pre, const void 
                            unsigned long long *unit_sse, int clear, hipStream_t s);
 hipError_t av1mi_launch_entropy(const Av1miDevParams *P, const uint16_t *cdf_init, const int16_t *levels, const Av1miBlkInfo *blk,
                                 uint32_t *streams, uint32_t *stream_len, uint32_t *tile_combos, uint8_t *slots, uint32_t *tile_bytes,
-                                const uint8_t *lr_choice, uint32_t *tile_order, int frame0, int count, int phase,
+                                const uint8_t *lr_choice, uint32_t *tile_order, int frame0, int count,
                                 hipStream_t s, hipEvent_t mid, hipStream_t aux, hipEvent_t fork, hipEvent_t join);
-hipError_t av1mi_launch_cdef(const Av1miDevParams *P, const void *rec, void *fin, const Av1miBlkInfo *blk, const uint16_t *dirtab, const void *src,
+hipError_t av1mi_launch_cdef(const Av1miDevParams *P, const void *rec, void *fin, const Av1miBlkInfo *blk, const void *src,
                              unsigned long long *sse, hipStream_t s);
-hipError_t av1mi_launch_cdef_dir(const Av1miDevParams *P, const void *rec, const Av1miBlkInfo *blk, uint16_t *dirtab, hipStream_t s);
 hipError_t av1mi_launch_sse(const Av1miDevParams *P, const void *a, const void *b, unsigned long long *sse, hipStream_t s);
 hipError_t av1mi_launch_pack(const Av1miDevParams *P, const uint8_t *slots, const uint32_t *tile_bytes, uint32_t *tile_off,
                              uint32_t *frame_size, uint32_t *payload_size, unsigned long long *frame_off, const uint8_t *hdr_blob,
@@ -421,12 +420,11 @@ std::vector<uint16_t> make_cdf_blob(int qidx) {
 // ------------------------------------------------------------------ context
 struct av1mi_ctx {
   int device = -1;
-  hipStream_t stream = nullptr;
-  bool pooled_streams = false;    // the streams go back to the process-wide pool (av1mi_ctx_create)
+  hipStream_t stream = nullptr;   // the four streams come from and go back to a process-wide pool (av1mi_ctx_create)
   hipStream_t stream2 = nullptr;  // CDEF + SSE run here, beside the entropy kernels on `stream`
   hipStream_t stream3 = nullptr;  // inter chunks: entropy coding of finished groups of frames, beside the frame-by-frame chain
-  hipStream_t stream4 = nullptr;  // all-key-frame chunks pipelined over groups: the groups' entropy coding alternates between stream3 and this one
-  hipEvent_t ev[14] = {};
+  hipStream_t stream4 = nullptr;  // the frame-edge tiles' symbolize variant, beside the regular one on `stream` (av1mi_launch_entropy)
+  hipEvent_t ev[13] = {};
   std::vector<hipEvent_t> me_ev;       // per frame: its motion search has finished (second stream -> main stream)
   std::vector<hipEvent_t> grp_ev;      // per group of frames of an inter chunk: reconstructed (main stream -> third stream)
   std::string err;
@@ -449,7 +447,6 @@ struct av1mi_ctx {
   void *d_stage = nullptr;             // sizes that are not multiples of 8: frames in the caller's tight layout (input / reconstruction out)
   void *d_cd = nullptr;                // loop restoration on: CDEF output (d_fin then holds the restored frames)
   unsigned long long *d_me_sub = nullptr;  // sub-sample refinement: refined [frame][8x8 unit] keys (me_kernel.hip)
-  uint16_t *d_cdefdir = nullptr;           // chunk-wide CDEF: {adjusted luma primary strength << 3 | direction} per 8x8 block (cdef_dir_kernel)
   uint16_t *d_quarter = nullptr;           // me_presearch: quarter-resolution luma of every frame of the chunk
   uint32_t *d_centre = nullptr;            // me_presearch: centre code of the full search per [frame][superblock]
   uint32_t *d_part = nullptr;              // content-driven partition: split mask per [frame][superblock] (partition_kernel)
@@ -489,11 +486,11 @@ void set_err(av1mi_ctx *c, const char *fmt, ...) {
 
 void free_workspace(av1mi_ctx *c) {
   void *ptrs[] = { c->d_src, c->d_rec, c->d_fin, c->d_levels, c->d_blk, c->d_slots, c->d_out, c->d_hdr, c->d_cdf, c->d_tile_bytes,
-                   c->d_tile_off, c->d_frame_size, c->d_payload, c->d_sym, c->d_frame_off, c->d_sse, c->d_overflow, c->d_streams, c->d_combos, c->d_me, c->d_cd, c->d_lrc, c->d_stage, c->d_qm, c->d_me_sub, c->d_lrsse, c->d_params, c->d_me64, c->d_cdefdir, c->d_part, c->d_quarter, c->d_centre };
+                   c->d_tile_off, c->d_frame_size, c->d_payload, c->d_sym, c->d_frame_off, c->d_sse, c->d_overflow, c->d_streams, c->d_combos, c->d_me, c->d_cd, c->d_lrc, c->d_stage, c->d_qm, c->d_me_sub, c->d_lrsse, c->d_params, c->d_me64, c->d_part, c->d_quarter, c->d_centre };
   for (void *p : ptrs) if (p) (void)hipFree(p);
   c->d_src = c->d_rec = c->d_fin = nullptr; c->d_levels = nullptr; c->d_blk = nullptr; c->d_slots = c->d_out = c->d_hdr = nullptr;
   c->d_cdf = nullptr; c->d_tile_bytes = c->d_tile_off = c->d_frame_size = c->d_payload = c->d_sym = nullptr;
-  c->d_frame_off = c->d_sse = nullptr; c->d_overflow = nullptr; c->d_streams = c->d_combos = nullptr; c->d_me = nullptr; c->d_cd = nullptr; c->d_lrc = nullptr; c->d_stage = nullptr; c->d_qm = nullptr; c->qm_key = -1; c->d_me_sub = nullptr; c->d_lrsse = nullptr; c->d_params = nullptr; c->d_me64 = nullptr; c->me64_bytes = 0; c->d_cdefdir = nullptr; c->d_part = nullptr; c->d_quarter = nullptr; c->d_centre = nullptr;
+  c->d_frame_off = c->d_sse = nullptr; c->d_overflow = nullptr; c->d_streams = c->d_combos = nullptr; c->d_me = nullptr; c->d_cd = nullptr; c->d_lrc = nullptr; c->d_stage = nullptr; c->d_qm = nullptr; c->qm_key = -1; c->d_me_sub = nullptr; c->d_lrsse = nullptr; c->d_params = nullptr; c->d_me64 = nullptr; c->me64_bytes = 0; c->d_part = nullptr; c->d_quarter = nullptr; c->d_centre = nullptr;
   if (c->h_out) (void)hipHostFree(c->h_out);
   c->h_out = nullptr; c->h_out_cap = 0;
   c->cap_frames = 0;
@@ -546,7 +543,6 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     HIPCHK(c, hipMalloc((void **)&c->d_sse, nf * 3 * 8));
     HIPCHK(c, hipMalloc((void **)&c->d_overflow, 4));
     HIPCHK(c, hipMalloc((void **)&c->d_me, nf * nb8 * 8));
-    HIPCHK(c, hipMalloc((void **)&c->d_cdefdir, nf * nsb * 64 * sizeof(uint16_t)));
     c->cap_frames = n_frames;
     c->ws_scale = c->cap_scale;
   }
@@ -717,38 +713,24 @@ int av1mi_ctx_create(int device_id, av1mi_ctx **out) {
   // taking its slots
   int prio_lo = 0, prio_hi = 0;
   if (hipSetDevice(device_id) == hipSuccess) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-  if (const char *fp = getenv("AV1MI_STREAM_PRIORITIES")) {   // experiment knob: "flat" = every stream at the default priority, "hi" = all high
-    if (!strcmp(fp, "flat")) prio_lo = prio_hi = 0;
-    else if (!strcmp(fp, "hi")) prio_lo = prio_hi;
-    else if (!strcmp(fp, "mid")) prio_lo = 0;   // chain high, the rest normal
-  }
-  // experiment knob: AV1MI_AUX_CU_MASK=<hex word> restricts the two auxiliary streams (bulk work beside the chain) to the CUs whose bit
-  // is set in the word, repeated over the chip's 256 CUs (0x55555555: every other CU)
-  bool aux_ok = true;
-  if (const char *m = getenv("AV1MI_AUX_CU_MASK")) {
-    uint32_t mask[8];
-    const uint32_t word = (uint32_t)strtoul(m, nullptr, 16);
-    for (auto &w : mask) w = word;
-    aux_ok = hipSetDevice(device_id) == hipSuccess && hipExtStreamCreateWithCUMask(&c->stream2, 8, mask) == hipSuccess &&
-             hipExtStreamCreateWithCUMask(&c->stream3, 8, mask) == hipSuccess;
-  }
-  if (aux_ok && !c->stream2) {   // a pooled set, if there is one for this device
+  bool pooled = false;   // a pooled set, if there is one for this device
+  {
     std::lock_guard<std::mutex> lk(g_stream_mu);
     for (size_t i = 0; i < g_stream_pool.size(); i++)
       if (g_stream_pool[i].first == device_id) {
         const StreamSet ss = g_stream_pool[i].second;
         g_stream_pool.erase(g_stream_pool.begin() + (long)i);
         c->stream = ss.s[0]; c->stream2 = ss.s[1]; c->stream3 = ss.s[2]; c->stream4 = ss.s[3];
-        c->pooled_streams = true;
+        pooled = true;
         break;
       }
   }
-  if (c->pooled_streams) {
+  if (pooled) {
     if (hipSetDevice(device_id) != hipSuccess) { delete c; return AV1MI_E_NO_DEVICE; }
   } else
-  if (!aux_ok || hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-      (!c->stream2 && hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio_lo) != hipSuccess) ||
-      (!c->stream3 && hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, prio_lo) != hipSuccess) ||
+  if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, prio_hi) != hipSuccess ||
+      hipStreamCreateWithPriority(&c->stream2, hipStreamNonBlocking, prio_lo) != hipSuccess ||
+      hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, prio_lo) != hipSuccess ||
       hipStreamCreateWithPriority(&c->stream4, hipStreamNonBlocking, prio_lo) != hipSuccess) {
     if (c->stream) (void)hipStreamDestroy(c->stream);
     if (c->stream2) (void)hipStreamDestroy(c->stream2);
@@ -757,7 +739,6 @@ int av1mi_ctx_create(int device_id, av1mi_ctx **out) {
     delete c;
     return AV1MI_E_NO_DEVICE;
   }
-  if (!getenv("AV1MI_AUX_CU_MASK")) c->pooled_streams = true;   // (the masked streams of the experiment knob are not pooled)
   for (auto &e : c->ev) (void)hipEventCreate(&e);
   *out = c;
   return AV1MI_OK;
@@ -771,15 +752,10 @@ void av1mi_ctx_destroy(av1mi_ctx *c) {
   for (auto &e : c->ev) if (e) (void)hipEventDestroy(e);
   for (auto &e : c->me_ev) (void)hipEventDestroy(e);
   for (auto &e : c->grp_ev) (void)hipEventDestroy(e);
-  if (c->pooled_streams && c->stream && c->stream2 && c->stream3 && c->stream4) {
-    (void)hipStreamSynchronize(c->stream2); (void)hipStreamSynchronize(c->stream3); (void)hipStreamSynchronize(c->stream4);
+  (void)hipStreamSynchronize(c->stream2); (void)hipStreamSynchronize(c->stream3); (void)hipStreamSynchronize(c->stream4);
+  {
     std::lock_guard<std::mutex> lk(g_stream_mu);
     g_stream_pool.push_back({ c->device, StreamSet{ { c->stream, c->stream2, c->stream3, c->stream4 } } });
-  } else {
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->stream2) (void)hipStreamDestroy(c->stream2);
-    if (c->stream3) (void)hipStreamDestroy(c->stream3);
-    if (c->stream4) (void)hipStreamDestroy(c->stream4);
   }
   delete c;
 }
@@ -1000,51 +976,19 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
                                          : (P.bit_depth == 8 ? av1mi_launch_recon_u8 : av1mi_launch_recon_u16);
   const bool lr = P.enable_lr != 0;
   uint32_t entropy_from = 0;      // inter chunks: frames before this one are entropy-coded on the third stream, beside the chain
-  bool sym_groups = false;        // ... or only symbolized there (AV1MI_SYM_GROUP)
-  bool entropy_joined = false;
   void *cdef_out = lr ? c->d_cd : c->d_fin;   // with loop restoration CDEF writes d_cd and the restored frame goes to d_fin
   if (!inter_chunk && lr) {
     // the unit decisions are part of the tile syntax: CDEF and restoration must precede entropy coding
     HIPCHK(c, launch_recon(&P, c->d_params, d_src, c->d_rec, c->d_levels, c->d_blk, nullptr, nullptr, P.part_map, s));
     if (P.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P, c->d_rec, c->d_blk, s));
-    HIPCHK(c, av1mi_launch_cdef(&P, c->d_rec, c->d_cd, c->d_blk, nullptr, nullptr, nullptr, s));
+    HIPCHK(c, av1mi_launch_cdef(&P, c->d_rec, c->d_cd, c->d_blk, nullptr, nullptr, s));
     HIPCHK(c, av1mi_launch_lr(&P, c->d_rec, c->d_cd, d_src, c->d_fin, c->d_lrc, c->d_lrsse, 1, s));
   } else if (!inter_chunk) {
-    // All-key-frame chunk: the frames are independent, so the chunk CAN run as a software pipeline over groups of frames
-    // (AV1MI_INTRA_GROUPS=k) - the main stream reconstructs group g + 1 while auxiliary streams symbolize and range-code group
-    // g.  Measured (1080p x 60, MI355X): 14.1 k frames/s as one group, 12.3 k as two, 10.7 k as three - the range coder holds
-    // 145 KB of LDS on every CU it sits on, which leaves the reconstruction (10 KB per wave) one wave there instead of sixteen.
-    // The default is therefore one group; the knob stays for the day the range coder's per-tile state leaves LDS.
-    uint32_t groups = 1;
-    if (const char *eg = getenv("AV1MI_INTRA_GROUPS")) { const int k = atoi(eg); if (k >= 1) groups = (uint32_t)k; }
-    if (groups > n_frames) groups = n_frames;
-    const uint32_t grp = (n_frames + groups - 1) / groups;
-    const size_t fbytes = (size_t)P.frame_samples * bps, nb8 = (size_t)P.b8_rows * P.b8_cols, nsb = (size_t)P.sb_rows * P.sb_cols;
-    uint32_t n_grp = 0;
-    for (uint32_t f0 = 0; f0 < n_frames; f0 += grp) {
-      const uint32_t cnt = f0 + grp < n_frames ? grp : n_frames - f0;
-      Av1miDevParams Pg = P;
-      Pg.n_frames = (int)cnt;
-      HIPCHK(c, launch_recon(&Pg, c->d_params, (const uint8_t *)d_src + f0 * fbytes, (uint8_t *)c->d_rec + f0 * fbytes,
-                             c->d_levels + f0 * nsb * AV1MI_SB_LEVELS, c->d_blk + f0 * nb8, nullptr, nullptr, P.part_map ? P.part_map + f0 * nsb : nullptr, s));
-      if (f0 + cnt < n_frames) {
-        if (c->grp_ev.size() <= n_grp) {
-          hipEvent_t e;
-          HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-          c->grp_ev.push_back(e);
-        }
-        hipStream_t sg = (n_grp & 1) ? c->stream4 : c->stream3;   // alternate: group g's range coder runs beside group g + 1's symbolize
-        HIPCHK(c, hipEventRecord(c->grp_ev[n_grp], s));
-        HIPCHK(c, hipStreamWaitEvent(sg, c->grp_ev[n_grp], 0));
-        HIPCHK(c, av1mi_launch_entropy(&P, c->d_cdf, c->d_levels, c->d_blk, c->d_streams, c->d_sym, c->d_combos, c->d_slots, c->d_tile_bytes, c->d_lrc,
-                                       c->d_tile_off, (int)f0, (int)cnt, 3, sg, nullptr, nullptr, nullptr, nullptr));
-        n_grp++;
-        entropy_from = f0 + cnt;
-      }
-    }
-    if (n_grp) HIPCHK(c, hipEventRecord(c->ev[10], c->stream3));
-    if (n_grp > 1) { HIPCHK(c, hipEventRecord(c->ev[11], c->stream4)); HIPCHK(c, hipStreamWaitEvent(s, c->ev[11], 0)); }
-    entropy_joined = n_grp != 0;
+    // All-key-frame chunk: one reconstruction launch over the chunk.  The frames are independent, so the chunk could run as a software
+    // pipeline over groups of frames - the main stream reconstructing group g + 1 while auxiliary streams symbolize and range-code group
+    // g.  Measured (1080p x 60, MI355X): 14.1 k frames/s as one group, 12.3 k as two, 10.7 k as three - the range coder holds 145 KB of
+    // LDS on every CU it sits on, which leaves the reconstruction (10 KB per wave) one wave there instead of sixteen.
+    HIPCHK(c, launch_recon(&P, c->d_params, d_src, c->d_rec, c->d_levels, c->d_blk, nullptr, nullptr, P.part_map, s));
   } else {
     // Inter chunk: a P frame needs the previous frame's final (post-CDEF) reconstruction, so motion search,
     // reconstruction and CDEF run frame by frame; entropy coding of ALL frames follows in one pass (every frame
@@ -1060,7 +1004,10 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
     if (acc64) HIPCHK(c, hipMemsetAsync(acc64, 0, (size_t)n_frames * nsb * (2 * P.me_range + 1) * (2 * P.me_range + 1) * sizeof(uint32_t), c->stream2));
     // one launch + one event per frame, enqueued from inside the frame loop below, behind the first frame's chain kernels: the chain's first
     // kernel (the key frame's reconstruction needs no vectors) no longer waits on the host for 120 - 180 API calls (under
-    // the profiler the chain started 6.4 ms after the chunk's first kernel; unprofiled the calls take ~ 8 us each and one chunk gains nothing)
+    // the profiler the chain started 6.4 ms after the chunk's first kernel; unprofiled the calls take ~ 8 us each and one chunk gains nothing).
+    // All of it behind the first frame rather than a few frames ahead of the chain - measured (1080p IPPP x 60, one chunk / four in flight,
+    // frames/s): all 5 420 / 7 560; 8 ahead 5 390 / 7 220; 4 ahead 5 410 / 6 970; 2 ahead 5 370 / 6 900 - with several chunks in flight a
+    // search that is enqueued late competes with the other chunks' chains instead of filling their gaps.
     while (c->me_ev.size() < n_frames) {
       hipEvent_t e;
       HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1072,23 +1019,6 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
       HIPCHK(c, av1mi_launch_quarter_luma(&P, d_src, c->d_quarter, c->stream2));
       centre = c->d_centre;
     }
-    uint32_t me_next = 0;
-    auto search_upto = [&](uint32_t upto) -> int {   // enqueue the search of the frames below `upto` that are not enqueued yet
-      for (; me_next < upto && me_next < n_frames; me_next++) {
-        const uint32_t f = me_next;
-        if (!av1mi_frame_is_inter(P, (int)f)) continue;
-        if (centre) HIPCHK(c, av1mi_launch_presearch(&P, c->d_quarter, c->d_centre, (int)f, 1, c->stream2));
-        HIPCHK(c, av1mi_launch_motion_search(&P, d_src, c->d_me, P.me_range, (int)f, 1, acc64, centre, c->stream2));
-        if (P.subpel) HIPCHK(c, av1mi_launch_subpel_refine(&P, d_src, c->d_me, c->d_me_sub, P.me_range, (int)f, 1, c->stream2));
-        HIPCHK(c, hipEventRecord(c->me_ev[f], c->stream2));
-      }
-      return AV1MI_OK;
-    };
-    // Frames the search is enqueued ahead of the chain.  Default: everything, right behind the FIRST frame's chain kernels - measured (1080p
-    // IPPP x 60, one chunk / four in flight, frames/s): all 5 420 / 7 560; 8 ahead 5 390 / 7 220; 4 ahead 5 410 / 6 970; 2 ahead 5 370 / 6 900 -
-    // with several chunks in flight a search that is enqueued late competes with the other chunks' chains instead of filling their gaps.
-    uint32_t me_ahead = n_frames;
-    if (const char *ea = getenv("AV1MI_ME_AHEAD")) { const int k = atoi(ea); me_ahead = k > 0 ? (uint32_t)k : n_frames; }
     // Entropy coding beside the chain: every frame starts from the default CDFs, so a group of frames can be symbolized and
     // range-coded (third stream) as soon as its last frame is reconstructed (and, with restoration on, its unit choices are
     // known) while the chain reconstructs the following frames; only the last group's entropy coding is left after the chain.
@@ -1099,8 +1029,6 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
     // chain and longer ones in groups of 32.
     uint32_t grp = n_frames <= 64 ? n_frames : 32;
     if (const char *eg = getenv("AV1MI_ENTROPY_GROUP")) { const int k = atoi(eg); grp = k > 0 ? (uint32_t)k : n_frames; }
-    // AV1MI_SYM_GROUP=k: groups of k frames are only SYMBOLIZED beside the chain; one range-coder launch for the whole chunk follows it
-    if (const char *eg = getenv("AV1MI_SYM_GROUP")) { const int k = atoi(eg); if (k > 0) { grp = (uint32_t)k; sym_groups = true; } }
     uint32_t n_grp = 0;
     if (lr) {   // the restoration units' candidate sums of the whole chunk, cleared once (not a fill per frame on the chain)
       const size_t upf = (size_t)((P.true_h + 32) / 64 > 0 ? (P.true_h + 32) / 64 : 1) * ((P.true_w + 32) / 64 > 0 ? (P.true_w + 32) / 64 : 1);
@@ -1116,19 +1044,25 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
       } else {
         const uint8_t *reff = (const uint8_t *)c->d_fin + (f - 1) * fbytes;
         unsigned long long *mef = (P.subpel ? c->d_me_sub : c->d_me) + f * nb8;
-        { const int mrc = search_upto(f + 1); if (mrc) return mrc; }
         HIPCHK(c, hipStreamWaitEvent(s, c->me_ev[f], 0));
         HIPCHK(c, launch_recon(&P1, c->d_params, srcf, recf, lvf, blkf, reff, mef, P.part_map ? P.part_map + f * nsb : nullptr, s));
       }
       if (!av1mi_frame_is_inter(P, (int)f)) { for (int i = 0; i < 4; i++) P1.lf_level[i] = P.lf_level[i]; }
       else { for (int i = 0; i < 4; i++) P1.lf_level[i] = P.lf_level_inter[i]; }
       if (P1.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P1, recf, blkf, s));
-      HIPCHK(c, av1mi_launch_cdef(&P1, recf, cdf_, blkf, nullptr, nullptr, nullptr, s));
+      HIPCHK(c, av1mi_launch_cdef(&P1, recf, cdf_, blkf, nullptr, nullptr, s));
       if (lr) {
         const int upf = ((P.true_h + 32) / 64 > 0 ? (P.true_h + 32) / 64 : 1) * ((P.true_w + 32) / 64 > 0 ? (P.true_w + 32) / 64 : 1);
         HIPCHK(c, av1mi_launch_lr(&P1, recf, cdf_, srcf, finf, c->d_lrc + (size_t)f * upf, c->d_lrsse + (size_t)f * upf * 8, 0, s));
       }
-      { const int mrc = search_upto(f + 1 + me_ahead); if (mrc) return mrc; }   // (after this frame's chain kernels are in the queue)
+      if (f == 0)   // (frame 0 of a chunk is a key frame: its chain kernels are in the queue)
+        for (uint32_t g = 1; g < n_frames; g++) {
+          if (!av1mi_frame_is_inter(P, (int)g)) continue;
+          if (centre) HIPCHK(c, av1mi_launch_presearch(&P, c->d_quarter, c->d_centre, (int)g, 1, c->stream2));
+          HIPCHK(c, av1mi_launch_motion_search(&P, d_src, c->d_me, P.me_range, (int)g, 1, acc64, centre, c->stream2));
+          if (P.subpel) HIPCHK(c, av1mi_launch_subpel_refine(&P, d_src, c->d_me, c->d_me_sub, P.me_range, (int)g, 1, c->stream2));
+          HIPCHK(c, hipEventRecord(c->me_ev[g], c->stream2));
+        }
       if ((f + 1) % grp == 0 && f + 1 < n_frames) {   // a full group that is not the last: hand it to the third stream
         if (c->grp_ev.size() <= n_grp) {
           hipEvent_t e;
@@ -1138,46 +1072,35 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
         HIPCHK(c, hipEventRecord(c->grp_ev[n_grp], s));
         HIPCHK(c, hipStreamWaitEvent(c->stream3, c->grp_ev[n_grp], 0));
         HIPCHK(c, av1mi_launch_entropy(&P, c->d_cdf, c->d_levels, c->d_blk, c->d_streams, c->d_sym, c->d_combos, c->d_slots, c->d_tile_bytes, c->d_lrc,
-                                       c->d_tile_off, (int)(f + 1 - grp), (int)grp, sym_groups ? 1 : 3, c->stream3, nullptr, nullptr, nullptr, nullptr));
+                                       c->d_tile_off, (int)(f + 1 - grp), (int)grp, c->stream3, nullptr, nullptr, nullptr, nullptr));
         n_grp++;
       }
     }
     entropy_from = n_grp * grp;
-    if (n_grp) {  // join: packing (main stream) needs every group's tile sizes and bytes
-      HIPCHK(c, hipEventRecord(c->ev[10], c->stream3));
-    }
-    entropy_joined = n_grp != 0;
+    if (n_grp) HIPCHK(c, hipEventRecord(c->ev[10], c->stream3));
   }
   HIPCHK(c, hipEventRecord(c->ev[2], s));
   // CDEF (+SSE) depends only on the reconstruction.  The range-coding kernel is a latency-bound
   // serial chain (one lane per tile: 480 waves, half the SIMDs idle), so CDEF runs beside IT on a
   // second stream; symbolize and CDEF are both throughput-bound and would only slow each other.
-  hipStream_t s2 = getenv("AV1MI_SERIAL") ? c->stream : c->stream2;  // AV1MI_SERIAL: single-stream timing experiments
+  hipStream_t s2 = c->stream2;
   HIPCHK(c, hipEventRecord(c->ev[3], s));
   HIPCHK(c, av1mi_launch_entropy(&P, c->d_cdf, c->d_levels, c->d_blk, c->d_streams, c->d_sym, c->d_combos, c->d_slots, c->d_tile_bytes, c->d_lrc,
                                  c->d_tile_off /* scratch until the packing kernels fill it */, (int)entropy_from, (int)(n_frames - entropy_from),
-                                 sym_groups && entropy_joined ? 1 : 3, s, c->ev[7],
-                                 c->stream4, c->ev[12], c->ev[13]));   // the frame-edge tiles' symbolize variant beside the regular one
-  if (entropy_joined) HIPCHK(c, hipStreamWaitEvent(s, c->ev[10], 0));
-  if (sym_groups && entropy_joined)   // every frame is symbolized: one range-coder launch for the whole chunk
-    HIPCHK(c, av1mi_launch_entropy(&P, c->d_cdf, c->d_levels, c->d_blk, c->d_streams, c->d_sym, c->d_combos, c->d_slots, c->d_tile_bytes, c->d_lrc,
-                                   c->d_tile_off, 0, (int)n_frames, 2, s, nullptr, nullptr, nullptr, nullptr));
+                                 s, c->ev[7], c->stream4, c->ev[11], c->ev[12]));   // the frame-edge tiles' symbolize variant beside the regular one
+  if (entropy_from) HIPCHK(c, hipStreamWaitEvent(s, c->ev[10], 0));   // join: packing needs the tile sizes and bytes of every group
   HIPCHK(c, hipEventRecord(c->ev[4], s));
-  // (AV1MI_CDEF_SPLIT: the direction search as a kernel of its own beside symbolize - measured slower overall: it takes symbolize's slots)
-  const bool split_cdef = !inter_chunk && !lr && P.enable_cdef && c->d_cdefdir && getenv("AV1MI_CDEF_SPLIT");
-  if (!inter_chunk && !lr) {  // deblocking and CDEF's direction search read only the reconstruction and block info: beside symbolize
+  if (!inter_chunk && !lr) {  // deblocking reads only the reconstruction and block info: beside symbolize
     HIPCHK(c, hipStreamWaitEvent(s2, c->ev[2], 0));
     if (P.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P, c->d_rec, c->d_blk, s2));
-    if (split_cdef) HIPCHK(c, av1mi_launch_cdef_dir(&P, c->d_rec, c->d_blk, c->d_cdefdir, s2));
   }
   HIPCHK(c, hipStreamWaitEvent(s2, c->ev[7], 0));  // ev[7]: recorded between symbolize and range-code (measured: starting CDEF
                                                    // right after the reconstruction, beside symbolize, costs 8 % overall)
   HIPCHK(c, hipEventRecord(c->ev[8], s2));
   // (an all-key chunk's CDEF is one launch over the chunk: it sums the squared error itself - a second pass over the frames, 0.19 ms at
   // 1080p x 60, would end after the range coder CDEF runs beside; a one-frame chunk's CDEF runs in strips without the sum)
-  const bool sse_in_cdef = !inter_chunk && !lr && n_frames > 1 && !getenv("AV1MI_CDEF_STRIPS");
-  if (!inter_chunk && !lr) HIPCHK(c, av1mi_launch_cdef(&P, c->d_rec, c->d_fin, c->d_blk, split_cdef ? c->d_cdefdir : nullptr, sse_in_cdef ? d_src : nullptr,
-                                                       sse_in_cdef ? c->d_sse : nullptr, s2));
+  const bool sse_in_cdef = !inter_chunk && !lr && n_frames > 1;
+  if (!inter_chunk && !lr) HIPCHK(c, av1mi_launch_cdef(&P, c->d_rec, c->d_fin, c->d_blk, sse_in_cdef ? d_src : nullptr, sse_in_cdef ? c->d_sse : nullptr, s2));
   if (!sse_in_cdef) HIPCHK(c, av1mi_launch_sse(&P, d_src, c->d_fin, c->d_sse, s2));
   HIPCHK(c, hipEventRecord(c->ev[9], s2));
   // packing and the download of the bitstream need nothing from the second stream: they run beside the tail of CDEF / SSE;

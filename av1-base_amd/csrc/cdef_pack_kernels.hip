@@ -11,7 +11,6 @@
 //     granularity: prefix sums over tile sizes, then every tile copies itself into the final
 //     Section-5 OBU stream (temporal delimiter, sequence header, OBU_FRAME with tile sizes).
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
 #include "av1mi_dev.h"
 
 namespace {
@@ -289,74 +288,13 @@ __device__ __forceinline__ int cdef_adjusted_pri(int pri_y, int var, int coeff_s
   return var ? (pri * (4 + var_str) + 8) >> 4 : 0;
 }
 
-// Chunk-wide launches: the direction search in a kernel of its own.  A wave per superblock stages the 64x64 luma samples in LDS
-// with row-contiguous 16-byte loads (lane = 8 samples of a row: 1 KB per instruction) and every lane then reads its own 8x8
-// block from there - as one kernel with the filter each lane loaded its block straight from HBM, 64 lanes touching 64 different
-// 16-byte segments per instruction (8192 cache-line requests per superblock against 640 for the whole filter pass), and the
-// filter kernel cannot hold an LDS tile beside the range coder (145 KB of LDS per CU).  This kernel runs beside symbolize; the
-// filter kernel (beside the range coder) reads {adjusted primary strength << 3 | direction} per 8x8 block.
-template <typename PIX>
-__global__ void __launch_bounds__(64) cdef_dir_kernel(Av1miDevParams P, const PIX *__restrict__ rec, const Av1miBlkInfo *__restrict__ blk,
-                                                     uint16_t *__restrict__ dirtab /* [frame][superblock][64] */) {
-  __shared__ __attribute__((aligned(16))) uint16_t tile[64][72];   // row pitch 144 B: 16-byte aligned, block rows land on different bank halves
-  const int sbs_per_frame = P.sb_rows * P.sb_cols;
-  const int f = blockIdx.x / sbs_per_frame, sb = blockIdx.x % sbs_per_frame;
-  const int sbr = sb / P.sb_cols, sbc = sb % P.sb_cols, lane = threadIdx.x;
-  const PIX *fr = rec + (size_t)f * P.frame_samples;
-  const int x0 = sbc * 64, y0 = sbr * 64, coeff_shift = P.bit_depth - 8;
-  const int b8r = lane >> 3, b8c = lane & 7;
-  const bool inside = (sbr * 8 + b8r) < P.b8_rows && (sbc * 8 + b8c) < P.b8_cols;
-  int skip = 1;
-  if (inside) skip = blk[(size_t)f * P.b8_rows * P.b8_cols + (size_t)(sbr * 8 + b8r) * P.b8_cols + sbc * 8 + b8c].skip;
-  const bool sb_on = __ballot(inside && !skip) != 0ull;
-  if (!P.enable_cdef || !sb_on) return;   // nothing of this superblock is filtered: the filter kernel does not read its entries
-  {
-    const int c8 = (lane & 7) * 8;
-    const bool col_in = x0 + c8 < P.width;   // (width is a multiple of 8: a group of 8 samples is inside or outside as a whole)
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      const int row = k * 8 + (lane >> 3);
-      if (col_in && y0 + row < P.height) {
-        const PIX *p = fr + (size_t)(y0 + row) * P.stride_y + x0 + c8;
-        uint4 w;
-        if (sizeof(PIX) == 2) {
-          w = *reinterpret_cast<const uint4 *>(p);
-        } else {
-          const uint2 q = *reinterpret_cast<const uint2 *>(p);
-          w.x = (q.x & 0xFF) | ((q.x & 0xFF00) << 8); w.y = ((q.x >> 16) & 0xFF) | ((q.x >> 24) << 16);
-          w.z = (q.y & 0xFF) | ((q.y & 0xFF00) << 8); w.w = ((q.y >> 16) & 0xFF) | ((q.y >> 24) << 16);
-        }
-        *reinterpret_cast<uint4 *>(&tile[row][c8]) = w;
-      }
-    }
-  }
-  __syncthreads();
-  int ydir = 0, var = 0;
-  if (inside && !skip) {
-    int px[8][8];
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const uint4 w = *reinterpret_cast<const uint4 *>(&tile[b8r * 8 + i][b8c * 8]);
-      const uint32_t d[4] = { w.x, w.y, w.z, w.w };
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        px[i][2 * j] = (int)((d[j] & 0xFFFF) >> coeff_shift) - 128;
-        px[i][2 * j + 1] = (int)((d[j] >> 16) >> coeff_shift) - 128;
-      }
-    }
-    cdef_direction_8x8(px, ydir, var);
-  }
-  dirtab[(size_t)blockIdx.x * 64 + lane] = (uint16_t)((cdef_adjusted_pri(P.cdef_y_pri, var, coeff_shift) << 3) | ydir);
-}
-
-// NS = 1: one wave per superblock (chunk-wide launches: throughput).  NS = 4 / 8: one wave per 16- / 8-row strip of a superblock
+// NS = 1: one wave per superblock (chunk-wide launches: throughput).  NS = 8: one wave per 8-row strip of a superblock
 // (one-frame launches of inter chunks: NS x the waves and 1 / NS of the filter work per wave: latency).
-// TAB: directions and adjusted strengths come from cdef_dir_kernel's table instead of being searched here.
 // SEC: some secondary strength is non-zero (the default strengths have none: the instantiation without carries no secondary-tap code).
 // SSEV: the squared error of the output against the source `src` is added to sse[frame][plane] (chunk-wide launches only).
-template <typename PIX, int NS, bool TAB, bool SEC, bool SSEV = false>
+template <typename PIX, int NS, bool SEC, bool SSEV = false>
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) cdef_sb_kernel(Av1miDevParams P, const PIX *__restrict__ rec, PIX *__restrict__ fin,
-                                                    const Av1miBlkInfo *__restrict__ blk, const uint16_t *__restrict__ dirtab,
+                                                    const Av1miBlkInfo *__restrict__ blk,
                                                     const PIX *__restrict__ src = nullptr, unsigned long long *__restrict__ sse = nullptr) {
   const int sbs_per_frame = P.sb_rows * P.sb_cols;
   const int strip = NS == 1 ? 0 : (int)(blockIdx.x % NS);
@@ -379,25 +317,20 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
   const bool do_filter = P.enable_cdef && sb_on && inside && !skip;
   const bool mine = NS == 1 || b8r / (8 / NS) == strip;   // this wave decides (and filters) only the blocks of its strip
   {
-    int ydir = 0, pri = 0;
-    if constexpr (TAB) {
-      if (do_filter && mine) { const int e = dirtab[(size_t)item * 64 + lane]; ydir = e & 7; pri = e >> 3; }
-    } else {
-      int var = 0;
-      if (do_filter && mine) {
-        // direction search §7.15.2 on the block's 8 rows of 8 samples (one-frame launches of inter chunks: the lane reads its block
-        // from L1/L2; the second group's reads hit L1)
-        const PIX *ty = fr + (size_t)(y0 + b8r * 8) * P.stride_y + x0 + b8c * 8;
-        int px[8][8];
+    int ydir = 0, var = 0;
+    if (do_filter && mine) {
+      // direction search §7.15.2 on the block's 8 rows of 8 samples (one-frame launches of inter chunks: the lane reads its block
+      // from L1/L2; the second group's reads hit L1)
+      const PIX *ty = fr + (size_t)(y0 + b8r * 8) * P.stride_y + x0 + b8c * 8;
+      int px[8][8];
 #pragma unroll
-        for (int i = 0; i < 8; i++) {
+      for (int i = 0; i < 8; i++) {
 #pragma unroll
-          for (int j = 0; j < 8; j++) px[i][j] = ((int)ty[(size_t)i * P.stride_y + j] >> coeff_shift) - 128;
-        }
-        cdef_direction_8x8(px, ydir, var);
+        for (int j = 0; j < 8; j++) px[i][j] = ((int)ty[(size_t)i * P.stride_y + j] >> coeff_shift) - 128;
       }
-      pri = cdef_adjusted_pri(P.cdef_y_pri, var, coeff_shift);
+      cdef_direction_8x8(px, ydir, var);
     }
+    const int pri = cdef_adjusted_pri(P.cdef_y_pri, var, coeff_shift);
     g_cdef.dir[lane] = (uint8_t)ydir;
     g_cdef.on[lane] = (uint8_t)do_filter;
     g_cdef.pri_y[lane] = (uint16_t)pri;
@@ -564,40 +497,26 @@ __global__ void __launch_bounds__(64) pack_tiles_kernel(Av1miDevParams P, const 
 
 }  // namespace
 
-// dirtab == nullptr: one kernel (direction search + filter); else the filter reads cdef_dir_kernel's table (av1mi_launch_cdef_dir before)
-extern "C" hipError_t av1mi_launch_cdef(const Av1miDevParams *P, const void *rec, void *fin, const Av1miBlkInfo *blk, const uint16_t *dirtab,
-                                        const void *src, unsigned long long *sse /* both or neither: the chunk-wide launch also sums the squared error */,
-                                        hipStream_t stream) {
+// src and sse: the squared error of the output against the source is added to sse[frame][plane] - chunk-wide launches only (the
+// host decides; a one-frame launch runs in strips and cannot sum it)
+extern "C" hipError_t av1mi_launch_cdef(const Av1miDevParams *P, const void *rec, void *fin, const Av1miBlkInfo *blk, const void *src,
+                                        unsigned long long *sse, hipStream_t stream) {
   const int grid = P->n_frames * P->sb_rows * P->sb_cols;
   const bool strips = P->n_frames == 1;  // a one-frame launch sits on an inter chunk's serial chain
-  static const bool exp_strips = getenv("AV1MI_CDEF_STRIPS") != nullptr;   // experiment: 16-row strips for chunk-wide launches too
   const bool sec = P->cdef_y_sec != 0 || P->cdef_uv_sec != 0;
-  const bool sse_here = src && sse && !strips && !exp_strips;
+  const bool sse_here = src || sse;
+  if (sse_here && (strips || !src || !sse)) return hipErrorInvalidValue;
   // one-frame launches: 8-row strips (4 080 waves at 1080p, still one round of the chip) - 16-row strips were 2.5 us per frame slower
-  // (AV1MI_CDEF_NS4 brings them back: same-box A/B of the chain)
-  static const bool ns8 = getenv("AV1MI_CDEF_NS4") == nullptr;
 #define CDEF_LAUNCH2(PIXT, SECV)                                                                                                           \
   do {                                                                                                                                     \
-    if (exp_strips && dirtab) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 4, true, SECV>), dim3(grid * 4), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, dirtab); \
-    else if (strips && ns8) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 8, false, SECV>), dim3(grid * 8), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, dirtab); \
-    else if (strips || exp_strips) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 4, false, SECV>), dim3(grid * 4), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, dirtab); \
-    else if (dirtab && sse_here) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 1, true, SECV, true>), dim3(grid), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, dirtab, (const PIXT *)src, sse); \
-    else if (dirtab) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 1, true, SECV>), dim3(grid), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, dirtab); \
-    else if (sse_here) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 1, false, SECV, true>), dim3(grid), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, dirtab, (const PIXT *)src, sse); \
-    else hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 1, false, SECV>), dim3(grid), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, dirtab); \
+    if (strips) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 8, SECV>), dim3(grid * 8), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk); \
+    else if (sse_here) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 1, SECV, true>), dim3(grid), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, (const PIXT *)src, sse); \
+    else hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 1, SECV>), dim3(grid), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk); \
   } while (0)
 #define CDEF_LAUNCH(PIXT) do { if (sec) CDEF_LAUNCH2(PIXT, true); else CDEF_LAUNCH2(PIXT, false); } while (0)
   if (P->bit_depth == 8) CDEF_LAUNCH(uint8_t); else CDEF_LAUNCH(uint16_t);
 #undef CDEF_LAUNCH2
 #undef CDEF_LAUNCH
-  return hipGetLastError();
-}
-
-// the direction search of a chunk-wide CDEF as a kernel of its own (see cdef_dir_kernel); dirtab: n_frames x superblocks x 64 entries
-extern "C" hipError_t av1mi_launch_cdef_dir(const Av1miDevParams *P, const void *rec, const Av1miBlkInfo *blk, uint16_t *dirtab, hipStream_t stream) {
-  const int grid = P->n_frames * P->sb_rows * P->sb_cols;
-  if (P->bit_depth == 8) hipLaunchKernelGGL((cdef_dir_kernel<uint8_t>), dim3(grid), dim3(64), 0, stream, *P, (const uint8_t *)rec, blk, dirtab);
-  else hipLaunchKernelGGL((cdef_dir_kernel<uint16_t>), dim3(grid), dim3(64), 0, stream, *P, (const uint16_t *)rec, blk, dirtab);
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 import sys, os, json
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/av1-base_amd")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "av1-base_amd"))
 import torch, av1mi, bench
 dev = torch.device("cuda", 0)
 w,h,bd,n = 1920,1080,10,60
