@@ -46,6 +46,17 @@ struct Av1miDevParams {
   int cfl;                  // chroma from luma is a candidate (key frames, blocks up to 32x32)
   int tx_search;            // identity transform for sparse intra luma residuals
   int enable_cdef, cdef_y_pri, cdef_y_sec, cdef_uv_pri, cdef_uv_sec, cdef_damping;
+  // CDEF strength search (av1mi_params.cdef_search): cdef_search = 0 - one fixed strength set per frame, the
+  // fields above (cdef_bits 0); k = 1..4 - cdef_bits = k - 1, 2^cdef_bits pairs per frame from the candidate pool, chosen on the device
+  // (the pointers below are null when it is off).  cdef_err: per [frame][superblock] the 16 luma
+  // and 8 chroma candidates' squared errors (cdef_search_kernel); cdef_idx: per [frame][superblock] the superblock's index into its frame's
+  // set, -1 where no block is coded (cdef_select_kernel; read by CDEF and coded by symbolize); cdef_sel: per frame 8 slots, the set's pair
+  // indices p = 8 l + c.  cdef_str_bit[0 / 1]: bit offset of the first strength field in a key / inter frame header
+  int cdef_search, cdef_bits;
+  int cdef_str_bit[2];
+  unsigned long long *cdef_err;
+  int8_t *cdef_idx;
+  uint8_t *cdef_sel;
   int disable_cdf_update;
   // plane geometry in samples
   int stride_y, stride_c;

@@ -52,6 +52,8 @@ hipError_t av1mi_launch_entropy(const Av1miDevParams *P, const uint16_t *cdf_ini
 hipError_t av1mi_launch_cdef(const Av1miDevParams *P, const void *rec, void *fin, const Av1miBlkInfo *blk, const void *src,
                              unsigned long long *sse, hipStream_t s);
 hipError_t av1mi_launch_sse(const Av1miDevParams *P, const void *a, const void *b, unsigned long long *sse, hipStream_t s);
+hipError_t av1mi_launch_cdef_search(const Av1miDevParams *P, const void *rec, const void *src, const Av1miBlkInfo *blk, uint8_t *hdr_blob,
+                                    int frame0, int count, hipStream_t s);
 hipError_t av1mi_launch_pack(const Av1miDevParams *P, const uint8_t *slots, const uint32_t *tile_bytes, uint32_t *tile_off,
                              uint32_t *frame_size, uint32_t *payload_size, unsigned long long *frame_off, const uint8_t *hdr_blob,
                              uint8_t *out, int *overflow, int stage, hipStream_t s);
@@ -114,6 +116,7 @@ int resolve(const av1mi_params *in, Resolved *r) {
   if (p.block_log2 < 3 || p.block_log2 > 6) return AV1MI_E_INVALID_ARG;
   if (p.cdef_damping == 0) { p.cdef_y_pri = 2; p.cdef_y_sec = 0; p.cdef_uv_pri = 1; p.cdef_uv_sec = 0; p.cdef_damping = 5; }
   if (p.cdef_damping < 3 || p.cdef_damping > 6 || p.cdef_y_pri > 15 || p.cdef_uv_pri > 15 || p.cdef_y_sec > 3 || p.cdef_uv_sec > 3) return AV1MI_E_INVALID_ARG;
+  if (p.cdef_search > 4 || (p.cdef_search && !p.enable_cdef)) return AV1MI_E_INVALID_ARG;
   r->qidx = kQuantizerToQindex[p.cq_level];
   if (p.subpel > 1 || p.enable_lr > 2 || p.color_range > 1 || p.intra_angle_delta > 1 || p.intra_edge_filter > 1 || p.cfl > 1 || p.tx_search > 1) return AV1MI_E_INVALID_ARG;
   if (p.partition_search > 1 || p.me_presearch > 1) return AV1MI_E_INVALID_ARG;
@@ -199,7 +202,9 @@ std::vector<uint8_t> make_sequence_header(const Resolved &r) {
 
 // OBU_FRAME payload up to the first tile: frame_header_obu (§5.9) + byte_alignment +
 // tile_group_obu's tile_start_and_end_present_flag + byte_alignment (§5.11.1)
-std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint32_t frame_number = 0, bool inter = false) {
+// cdef_str_bit (optional): bit offset of the first CDEF strength field - with the search on (cdef_bits > 0) the header carries the fixed
+// strengths as placeholders, 2^cdef_bits times, and cdef_select_kernel overwrites those 12 * 2^cdef_bits bits in the frame's slot
+std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint32_t frame_number = 0, bool inter = false, size_t *cdef_str_bit = nullptr) {
   const av1mi_params &p = r.p;
   BitWriter b;
   b.put(0, 1);  // show_existing_frame
@@ -268,9 +273,13 @@ std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint
   b.put(0, 1);  // loop_filter_delta_enabled
   if (p.enable_cdef) {
     b.put(p.cdef_damping - 3, 2);
-    b.put(0, 2);  // cdef_bits
-    b.put(p.cdef_y_pri, 4); b.put(p.cdef_y_sec, 2);
-    b.put(p.cdef_uv_pri, 4); b.put(p.cdef_uv_sec, 2);
+    const int cdef_bits = p.cdef_search ? (int)p.cdef_search - 1 : 0;
+    b.put((uint32_t)cdef_bits, 2);
+    if (cdef_str_bit) *cdef_str_bit = b.bits;
+    for (int i = 0; i < (1 << cdef_bits); i++) {
+      b.put(p.cdef_y_pri, 4); b.put(p.cdef_y_sec, 2);
+      b.put(p.cdef_uv_pri, 4); b.put(p.cdef_uv_sec, 2);
+    }
   }
   if (p.enable_lr) {  // lr_params (§5.9.20): luma RESTORE_WIENER (lr_type 2), chroma none, lr_unit_shift 0 = 64x64 units
     b.put(p.enable_lr == 2 ? 1 : 2, 2); b.put(0, 2); b.put(0, 2);  // luma lr_type: 1 = RESTORE_SWITCHABLE, 2 = RESTORE_WIENER
@@ -457,6 +466,9 @@ struct av1mi_ctx {
   int qm_key = -1;
   uint8_t *d_lrc = nullptr;            // per restoration unit: 0 = off, k = candidate k-1
   unsigned long long *d_lrsse = nullptr;  // per restoration unit: the candidates' SSE sums (scratch of lr_kernel.hip's two phases)
+  unsigned long long *d_cdef_err = nullptr;  // CDEF strength search: per [frame][superblock] the 24 candidates' squared errors
+  int8_t *d_cdef_idx = nullptr;              // ... per [frame][superblock] the index into the frame's set (-1: not coded)
+  uint8_t *d_cdef_sel = nullptr;             // ... per frame the set: 8 slots of pair indices
   size_t out_cap = 0;
   // host staging (pinned)
   uint8_t *h_out = nullptr;
@@ -486,11 +498,12 @@ void set_err(av1mi_ctx *c, const char *fmt, ...) {
 
 void free_workspace(av1mi_ctx *c) {
   void *ptrs[] = { c->d_src, c->d_rec, c->d_fin, c->d_levels, c->d_blk, c->d_slots, c->d_out, c->d_hdr, c->d_cdf, c->d_tile_bytes,
-                   c->d_tile_off, c->d_frame_size, c->d_payload, c->d_sym, c->d_frame_off, c->d_sse, c->d_overflow, c->d_streams, c->d_combos, c->d_me, c->d_cd, c->d_lrc, c->d_stage, c->d_qm, c->d_me_sub, c->d_lrsse, c->d_params, c->d_me64, c->d_part, c->d_quarter, c->d_centre };
+                   c->d_tile_off, c->d_frame_size, c->d_payload, c->d_sym, c->d_frame_off, c->d_sse, c->d_overflow, c->d_streams, c->d_combos, c->d_me, c->d_cd, c->d_lrc, c->d_stage, c->d_qm, c->d_me_sub, c->d_lrsse, c->d_params, c->d_me64, c->d_part, c->d_quarter, c->d_centre, c->d_cdef_err, c->d_cdef_idx, c->d_cdef_sel };
   for (void *p : ptrs) if (p) (void)hipFree(p);
   c->d_src = c->d_rec = c->d_fin = nullptr; c->d_levels = nullptr; c->d_blk = nullptr; c->d_slots = c->d_out = c->d_hdr = nullptr;
   c->d_cdf = nullptr; c->d_tile_bytes = c->d_tile_off = c->d_frame_size = c->d_payload = c->d_sym = nullptr;
   c->d_frame_off = c->d_sse = nullptr; c->d_overflow = nullptr; c->d_streams = c->d_combos = nullptr; c->d_me = nullptr; c->d_cd = nullptr; c->d_lrc = nullptr; c->d_stage = nullptr; c->d_qm = nullptr; c->qm_key = -1; c->d_me_sub = nullptr; c->d_lrsse = nullptr; c->d_params = nullptr; c->d_me64 = nullptr; c->me64_bytes = 0; c->d_part = nullptr; c->d_quarter = nullptr; c->d_centre = nullptr;
+  c->d_cdef_err = nullptr; c->d_cdef_idx = nullptr; c->d_cdef_sel = nullptr;
   if (c->h_out) (void)hipHostFree(c->h_out);
   c->h_out = nullptr; c->h_out_cap = 0;
   c->cap_frames = 0;
@@ -564,6 +577,11 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
       c->me64_bytes = need;
     }
   }
+  if (p.cdef_search && !c->d_cdef_err) {
+    HIPCHK(c, hipMalloc((void **)&c->d_cdef_err, c->cap_frames * nsb * 24 * sizeof(unsigned long long)));
+    HIPCHK(c, hipMalloc((void **)&c->d_cdef_idx, c->cap_frames * nsb));
+    HIPCHK(c, hipMalloc((void **)&c->d_cdef_sel, c->cap_frames * 8));
+  }
   if (p.enable_lr && !c->d_cd) {
     const size_t nf = c->cap_frames;
     HIPCHK(c, hipMalloc(&c->d_cd, nf * frame_samples * bps));
@@ -617,6 +635,11 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   P.enable_cdef = p.enable_cdef ? 1 : 0;
   P.cdef_y_pri = p.cdef_y_pri; P.cdef_y_sec = p.cdef_y_sec; P.cdef_uv_pri = p.cdef_uv_pri; P.cdef_uv_sec = p.cdef_uv_sec;
   P.cdef_damping = p.cdef_damping;
+  P.cdef_search = (int)p.cdef_search;
+  P.cdef_bits = p.cdef_search ? (int)p.cdef_search - 1 : 0;
+  P.cdef_err = p.cdef_search ? c->d_cdef_err : nullptr;
+  P.cdef_idx = p.cdef_search ? c->d_cdef_idx : nullptr;
+  P.cdef_sel = p.cdef_search ? c->d_cdef_sel : nullptr;
   P.disable_cdf_update = p.cdf_update ? 0 : 1;
   P.stride_y = r.cw; P.stride_c = r.cw / 2;
   P.plane_off_u = (long)r.cw * r.ch;
@@ -930,7 +953,9 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
   // headers + CDFs
   // header blob: sequence header OBU, then one fixed-size slot per frame with that frame's header (key and inter
   // frames have different lengths; frames of one kind differ only in grain_seed)
-  std::vector<uint8_t> seq = make_sequence_header(r), fh = make_frame_header(r, nullptr, 0, false), fhi = make_frame_header(r, nullptr, 0, true);
+  size_t str_key = 0, str_inter = 0;   // CDEF strength search: where cdef_select_kernel writes each frame's set
+  std::vector<uint8_t> seq = make_sequence_header(r), fh = make_frame_header(r, nullptr, 0, false, &str_key), fhi = make_frame_header(r, nullptr, 0, true, &str_inter);
+  P.cdef_str_bit[0] = (int)str_key; P.cdef_str_bit[1] = (int)str_inter;
   P.seq_hdr_bytes = (int)seq.size();
   P.frame_hdr_bytes = (int)fh.size();
   P.inter_hdr_bytes = (int)fhi.size();
@@ -949,6 +974,7 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
   HIPCHK(c, hipMemcpyAsync(c->d_params, &P, sizeof(P), hipMemcpyHostToDevice, s));  // the recon kernel reads its parameters from device memory
   HIPCHK(c, hipMemsetAsync(c->d_overflow, 0, 4, s));
   HIPCHK(c, hipMemsetAsync(c->d_sse, 0, (size_t)n_frames * 24, s));
+  if (P.cdef_search) HIPCHK(c, hipMemsetAsync(c->d_cdef_err, 0, (size_t)n_frames * P.sb_rows * P.sb_cols * 24 * sizeof(unsigned long long), s));
   HIPCHK(c, hipEventRecord(c->ev[0], s));
   const void *d_src = frames;
   if (!padded) {
@@ -981,6 +1007,7 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
     // the unit decisions are part of the tile syntax: CDEF and restoration must precede entropy coding
     HIPCHK(c, launch_recon(&P, c->d_params, d_src, c->d_rec, c->d_levels, c->d_blk, nullptr, nullptr, P.part_map, s));
     if (P.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P, c->d_rec, c->d_blk, s));
+    if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, c->d_rec, d_src, c->d_blk, c->d_hdr, 0, (int)n_frames, s));
     HIPCHK(c, av1mi_launch_cdef(&P, c->d_rec, c->d_cd, c->d_blk, nullptr, nullptr, s));
     HIPCHK(c, av1mi_launch_lr(&P, c->d_rec, c->d_cd, d_src, c->d_fin, c->d_lrc, c->d_lrsse, 1, s));
   } else if (!inter_chunk) {
@@ -989,6 +1016,12 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
     // g.  Measured (1080p x 60, MI355X): 14.1 k frames/s as one group, 12.3 k as two, 10.7 k as three - the range coder holds 145 KB of
     // LDS on every CU it sits on, which leaves the reconstruction (10 KB per wave) one wave there instead of sixteen.
     HIPCHK(c, launch_recon(&P, c->d_params, d_src, c->d_rec, c->d_levels, c->d_blk, nullptr, nullptr, P.part_map, s));
+    if (P.cdef_search) {
+      // the strength search reads the deblocked frames and symbolize codes its cdef_idx: deblocking, search and selection before entropy
+      // coding (CDEF itself still runs beside the range coder)
+      if (P.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P, c->d_rec, c->d_blk, s));
+      HIPCHK(c, av1mi_launch_cdef_search(&P, c->d_rec, d_src, c->d_blk, c->d_hdr, 0, (int)n_frames, s));
+    }
   } else {
     // Inter chunk: a P frame needs the previous frame's final (post-CDEF) reconstruction, so motion search,
     // reconstruction and CDEF run frame by frame; entropy coding of ALL frames follows in one pass (every frame
@@ -1050,6 +1083,11 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
       if (!av1mi_frame_is_inter(P, (int)f)) { for (int i = 0; i < 4; i++) P1.lf_level[i] = P.lf_level[i]; }
       else { for (int i = 0; i < 4; i++) P1.lf_level[i] = P.lf_level_inter[i]; }
       if (P1.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P1, recf, blkf, s));
+      if (P.cdef_search) {   // the frame's strength set before its CDEF (the next frame's reference is the output of the chosen strengths)
+        HIPCHK(c, av1mi_launch_cdef_search(&P, c->d_rec, d_src, c->d_blk, c->d_hdr, (int)f, 1, s));
+        P1.cdef_idx = P.cdef_idx + f * nsb;
+        P1.cdef_sel = P.cdef_sel + f * 8;
+      }
       HIPCHK(c, av1mi_launch_cdef(&P1, recf, cdf_, blkf, nullptr, nullptr, s));
       if (lr) {
         const int upf = ((P.true_h + 32) / 64 > 0 ? (P.true_h + 32) / 64 : 1) * ((P.true_w + 32) / 64 > 0 ? (P.true_w + 32) / 64 : 1);
@@ -1092,7 +1130,7 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
   HIPCHK(c, hipEventRecord(c->ev[4], s));
   if (!inter_chunk && !lr) {  // deblocking reads only the reconstruction and block info: beside symbolize
     HIPCHK(c, hipStreamWaitEvent(s2, c->ev[2], 0));
-    if (P.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P, c->d_rec, c->d_blk, s2));
+    if (P.lf_level[0] && !P.cdef_search) HIPCHK(c, av1mi_launch_deblock(&P, c->d_rec, c->d_blk, s2));
   }
   HIPCHK(c, hipStreamWaitEvent(s2, c->ev[7], 0));  // ev[7]: recorded between symbolize and range-code (measured: starting CDEF
                                                    // right after the reconstruction, beside symbolize, costs 8 % overall)

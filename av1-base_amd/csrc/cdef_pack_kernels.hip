@@ -3,7 +3,8 @@
 // (1) replaces the CDEF stage of the external SVT-AV1 worker behind `run_av1an`
 //     (/root/reference/crates/daemon/src/encode/av1an.rs:126-139):
 //     AV1 spec §7.15 - 8x8 direction search (§7.15.2) and the constrained primary/secondary
-//     filter (§7.15.3), 4:2:0, one strength set per frame (cdef_bits = 0).
+//     filter (§7.15.3), 4:2:0, one strength set per frame (cdef_bits = 0) - or, with the strength search on, a set of up to 8 per
+//     frame and an index per superblock, chosen by cdef_search_kernel + cdef_select_kernel below.
 //     MI355X mapping: one wave per 64x64 superblock; luma (68x68) and chroma (36x36 x2) tiles incl.
 //     the 2-pixel halo are staged once into LDS with coalesced row loads, unavailable (outside
 //     frame) samples carry a sentinel; each lane owns one 8x8 block (direction + filter).
@@ -292,14 +293,14 @@ __device__ __forceinline__ int cdef_adjusted_pri(int pri_y, int var, int coeff_s
 // (one-frame launches of inter chunks: NS x the waves and 1 / NS of the filter work per wave: latency).
 // SEC: some secondary strength is non-zero (the default strengths have none: the instantiation without carries no secondary-tap code).
 // SSEV: the squared error of the output against the source `src` is added to sse[frame][plane] (chunk-wide launches only).
-template <typename PIX, int NS, bool SEC, bool SSEV = false>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) cdef_sb_kernel(Av1miDevParams P, const PIX *__restrict__ rec, PIX *__restrict__ fin,
-                                                    const Av1miBlkInfo *__restrict__ blk,
-                                                    const PIX *__restrict__ src = nullptr, unsigned long long *__restrict__ sse = nullptr) {
-  const int sbs_per_frame = P.sb_rows * P.sb_cols;
-  const int strip = NS == 1 ? 0 : (int)(blockIdx.x % NS);
-  const int item = blockIdx.x / NS;
-  const int f = item / sbs_per_frame, sb = item % sbs_per_frame;
+// The candidate pool of the strength search: primary strength P8[i] = 0, 1, 2, 3, 4, 6, 8, 11 as nibbles.  Luma
+// candidate l = 0 .. 15 is (P8[l >> 1], secondary code 2 * (l & 1)), chroma candidate c = 0 .. 7 is (P8[c], 0); pair p = 8 l + c.
+__device__ __forceinline__ int cdef_pool_pri(int i) { return (int)((0xB8643210u >> (4 * i)) & 15u); }
+
+template <typename PIX, int NS, bool SEC, bool SSEV>
+__device__ __forceinline__ void cdef_sb_body(const Av1miDevParams &P, const PIX *__restrict__ rec, PIX *__restrict__ fin,
+                                             const Av1miBlkInfo *__restrict__ blk, const PIX *__restrict__ src, unsigned long long *__restrict__ sse,
+                                             int f, int sb, int strip) {
   const int sbr = sb / P.sb_cols, sbc = sb % P.sb_cols;
   const int lane = threadIdx.x;
   const PIX *fr = rec + (size_t)f * P.frame_samples;
@@ -343,6 +344,299 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
   unsigned long long *sse_f = SSEV ? sse + (size_t)f * 3 : nullptr;
   if (edge) cdef_filter_sb<PIX, true, SEC, SSEV>(P, fr, fo, x0, y0, w, h, lane, row0, row1, sf, sse_f);
   else cdef_filter_sb<PIX, false, SEC, SSEV>(P, fr, fo, x0, y0, w, h, lane, row0, row1, sf, sse_f);
+}
+
+// SEL: the strength search is on - each superblock filters with the pair its frame's set assigns it (P.cdef_idx / P.cdef_sel, frame-relative
+// like `rec`), loaded once per wave; the fixed-strength instantiations (SEL = false) are what they were before the search existed.
+template <typename PIX, int NS, bool SEC, bool SSEV = false, bool SEL = false>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) cdef_sb_kernel(Av1miDevParams P, const PIX *__restrict__ rec, PIX *__restrict__ fin,
+                                                    const Av1miBlkInfo *__restrict__ blk,
+                                                    const PIX *__restrict__ src = nullptr, unsigned long long *__restrict__ sse = nullptr) {
+  const int sbs_per_frame = P.sb_rows * P.sb_cols;
+  const int strip = NS == 1 ? 0 : (int)(blockIdx.x % NS);
+  const int item = blockIdx.x / NS;
+  const int f = item / sbs_per_frame, sb = item % sbs_per_frame;
+  if constexpr (SEL) {
+    Av1miDevParams Q = P;
+    const int ci = P.cdef_idx[(size_t)f * sbs_per_frame + sb];   // -1: no block of the superblock is coded, nothing is filtered
+    const int pr = ci >= 0 ? (int)P.cdef_sel[f * 8 + ci] : 0, l = pr >> 3, c = pr & 7;
+    Q.cdef_y_pri = cdef_pool_pri(l >> 1); Q.cdef_y_sec = (l & 1) * 2;
+    Q.cdef_uv_pri = cdef_pool_pri(c); Q.cdef_uv_sec = 0;
+    cdef_sb_body<PIX, NS, SEC, SSEV>(Q, rec, fin, blk, src, sse, f, sb, strip);
+  } else {
+    cdef_sb_body<PIX, NS, SEC, SSEV>(P, rec, fin, blk, src, sse, f, sb, strip);
+  }
+}
+
+// ------------------------------------------------------------------------------ CDEF strength search
+// Per superblock the squared error against the source of the CDEF output under every candidate of the pool: 16 luma candidates
+// (err[0 .. 15]) and 8 chroma candidates (err[16 .. 23], U + V), counted over the signalled frame size only.  The direction search is
+// cdef_sb_kernel's, once per 8x8 block; every sample's taps are loaded once and their differences to the centre formed once, only the
+// strength-dependent part of constrain() runs per candidate:
+//   luma  l = 0: the sample itself; l = 1 (primary 0, secondary 2): the secondary taps of direction 0 (a zero primary strength selects
+//         direction 0, spec §7.15.1), clamped to direction 0's taps; l = 2 j (primary P8[j], variance-adjusted per block): 4 primary taps;
+//         l = 2 j + 1: the same primary sum plus the secondary sum of the block's direction, which all seven share, clamped to its 12 taps.
+//   chroma c = 0: the sample itself; c = 1 .. 7: 4 primary taps (P8[c], not variance-adjusted).
+// A sum of primary taps alone never leaves the range of its taps (the weights total 12 < 16), so the primary-only candidates need no
+// clamp.  Unfiltered (skipped) blocks add the same error to every candidate.  Per lane in 32 bits (<= 64 samples of <= 1023^2), per
+// wave through LDS in 64 bits, into the table with 64-bit atomics (integer sums: the order does not matter).
+// NS: strips per superblock as cdef_sb_kernel (NS = 8 for one-frame launches on the P-frame chain).  Superblocks whose blocks are all
+// skipped code no cdef_idx: -1 is written for them (0 for the others, cdef_select_kernel fills in the index) and their errors stay 0.
+struct CdefSearchLds {
+  uint8_t dir[64];
+  uint8_t on[64];
+  int var[64];
+  uint32_t acc[24][65];
+};
+__shared__ CdefSearchLds g_cs;
+
+template <typename PIX, bool EDGE>
+__device__ __forceinline__ int cs_tap(const PIX *pl, int stride, int w, int h, int gx, int gy, int dy, int dx, int x) {
+  const int yy = gy + dy, xx = gx + dx;
+  if (EDGE && (yy < 0 || xx < 0 || yy >= h || xx >= w)) return x;   // not available: contributes nothing (cdef_rows' convention)
+  return ld_px(pl, yy * stride + xx);
+}
+// sum of the constrained differences of the 8 secondary taps of direction `dir` (weights 2, 2, 1, 1 per side direction) and their range
+template <typename PIX, bool EDGE>
+__device__ __forceinline__ int cs_secondary(const PIX *pl, int stride, int w, int h, int gx, int gy, int dir, int x, int sec, int sec_shift,
+                                            int &mx, int &mn) {
+  int sum = 0;
+#pragma unroll
+  for (int q = 0; q < 2; q++) {
+    int dy0, dx0, dy1, dx1;
+    cdef_dir_offsets((dir + (q ? 6 : 2)) & 7, dy0, dx0, dy1, dx1);
+    const int t0 = cs_tap<PIX, EDGE>(pl, stride, w, h, gx, gy, dy0, dx0, x), t1 = cs_tap<PIX, EDGE>(pl, stride, w, h, gx, gy, -dy0, -dx0, x);
+    const int t2 = cs_tap<PIX, EDGE>(pl, stride, w, h, gx, gy, dy1, dx1, x), t3 = cs_tap<PIX, EDGE>(pl, stride, w, h, gx, gy, -dy1, -dx1, x);
+    sum += 2 * (constrain(t0 - x, sec, sec_shift) + constrain(t1 - x, sec, sec_shift)) + constrain(t2 - x, sec, sec_shift) + constrain(t3 - x, sec, sec_shift);
+    mx = max(mx, max(max(t0, t1), max(t2, t3)));
+    mn = min(mn, min(min(t0, t1), min(t2, t3)));
+  }
+  return sum;
+}
+__device__ __forceinline__ int cs_round(int x, int sum) { return x + ((8 + sum - (sum < 0)) >> 4); }
+
+template <typename PIX, bool EDGE>
+__device__ __forceinline__ void cdef_search_sb(const Av1miDevParams &P, const PIX *fr, const PIX *sf, int x0, int y0, int w, int h, int lane,
+                                               int row0, int row1, uint32_t (&acc)[24]) {
+  const int coeff_shift = P.bit_depth - 8;
+  // ---- luma: lane = column
+  {
+    const int damping = P.cdef_damping + coeff_shift;
+    const int sec = 2 << coeff_shift, sec_shift = damp_shift(sec, damping);
+    const int tw = P.true_w - x0, th = P.true_h - y0;   // counted region (signalled size), superblock-relative
+    uint32_t base = 0;
+    if (lane < w && lane < tw) {
+      for (int r = row0; r < (row1 < h ? row1 : h) && r < th; r++) {
+        const int b = (r >> 3) * 8 + (lane >> 3);
+        const int gx = x0 + lane, gy = y0 + r;
+        const int x = ld_px(fr, gy * P.stride_y + gx), s = ld_px(sf, gy * P.stride_y + gx);
+        const int d0 = x - s;
+        if (!g_cs.on[b]) { base += (uint32_t)(d0 * d0); continue; }
+        const int dir = g_cs.dir[b], var = g_cs.var[b];
+        int dy0, dx0, dy1, dx1;
+        cdef_dir_offsets(dir, dy0, dx0, dy1, dx1);
+        const int p0 = cs_tap<PIX, EDGE>(fr, P.stride_y, P.width, P.height, gx, gy, dy0, dx0, x) - x;
+        const int p1 = cs_tap<PIX, EDGE>(fr, P.stride_y, P.width, P.height, gx, gy, -dy0, -dx0, x) - x;
+        const int p2 = cs_tap<PIX, EDGE>(fr, P.stride_y, P.width, P.height, gx, gy, dy1, dx1, x) - x;
+        const int p3 = cs_tap<PIX, EDGE>(fr, P.stride_y, P.width, P.height, gx, gy, -dy1, -dx1, x) - x;
+        int mx = max(x, max(max(p0, p1), max(p2, p3)) + x), mn = min(x, min(min(p0, p1), min(p2, p3)) + x);
+        const int ssum = cs_secondary<PIX, EDGE>(fr, P.stride_y, P.width, P.height, gx, gy, dir, x, sec, sec_shift, mx, mn);
+        acc[0] += (uint32_t)(d0 * d0);
+        {  // l = 1: direction 0
+          int mx0 = x, mn0 = x, ssum0 = ssum;
+          if (dir == 0) { mx0 = mx; mn0 = mn; }
+          else {
+            cdef_dir_offsets(0, dy0, dx0, dy1, dx1);
+            const int q0 = cs_tap<PIX, EDGE>(fr, P.stride_y, P.width, P.height, gx, gy, dy0, dx0, x), q1 = cs_tap<PIX, EDGE>(fr, P.stride_y, P.width, P.height, gx, gy, -dy0, -dx0, x);
+            const int q2 = cs_tap<PIX, EDGE>(fr, P.stride_y, P.width, P.height, gx, gy, dy1, dx1, x), q3 = cs_tap<PIX, EDGE>(fr, P.stride_y, P.width, P.height, gx, gy, -dy1, -dx1, x);
+            mx0 = max(mx0, max(max(q0, q1), max(q2, q3))); mn0 = min(mn0, min(min(q0, q1), min(q2, q3)));
+            ssum0 = cs_secondary<PIX, EDGE>(fr, P.stride_y, P.width, P.height, gx, gy, 0, x, sec, sec_shift, mx0, mn0);
+          }
+          int v = cs_round(x, ssum0);
+          v = v < mn0 ? mn0 : (v > mx0 ? mx0 : v);
+          acc[1] += (uint32_t)((v - s) * (v - s));
+        }
+#pragma unroll
+        for (int j = 1; j < 8; j++) {
+          const int pri = cdef_adjusted_pri(cdef_pool_pri(j), var, coeff_shift), psh = damp_shift(pri, damping);
+          const int odd = (pri >> coeff_shift) & 1, w0 = odd ? 3 : 4, w1 = odd ? 3 : 2;
+          const int psum = w0 * (constrain(p0, pri, psh) + constrain(p1, pri, psh)) + w1 * (constrain(p2, pri, psh) + constrain(p3, pri, psh));
+          const int v0 = cs_round(x, psum);
+          int v1 = cs_round(x, psum + ssum);
+          v1 = v1 < mn ? mn : (v1 > mx ? mx : v1);
+          acc[2 * j] += (uint32_t)((v0 - s) * (v0 - s));
+          acc[2 * j + 1] += (uint32_t)((v1 - s) * (v1 - s));
+        }
+      }
+    }
+#pragma unroll
+    for (int l = 0; l < 16; l++) acc[l] += base;
+  }
+  // ---- chroma: lanes 0-31 = columns of U, lanes 32-63 = columns of V
+  {
+    const int pl = lane >> 5, col = lane & 31;
+    const PIX *cp = fr + (pl ? P.plane_off_v : P.plane_off_u), *sp = sf + (pl ? P.plane_off_v : P.plane_off_u);
+    const int damping = P.cdef_damping + coeff_shift - 1;
+    const int wc = w >> 1, hc = h >> 1, cw = P.width >> 1, chh = P.height >> 1;
+    const int twc = (P.true_w >> 1) - (x0 >> 1), thc = (P.true_h >> 1) - (y0 >> 1);
+    uint32_t base = 0;
+    if (col < wc && col < twc) {
+      for (int r = row0 >> 1; r < ((row1 >> 1) < hc ? (row1 >> 1) : hc) && r < thc; r++) {
+        const int b = (r >> 2) * 8 + (col >> 2);
+        const int gx = (x0 >> 1) + col, gy = (y0 >> 1) + r;
+        const int x = ld_px(cp, gy * P.stride_c + gx), s = ld_px(sp, gy * P.stride_c + gx);
+        const int d0 = x - s;
+        if (!g_cs.on[b]) { base += (uint32_t)(d0 * d0); continue; }
+        int dy0, dx0, dy1, dx1;
+        cdef_dir_offsets(g_cs.dir[b], dy0, dx0, dy1, dx1);
+        const int p0 = cs_tap<PIX, EDGE>(cp, P.stride_c, cw, chh, gx, gy, dy0, dx0, x) - x;
+        const int p1 = cs_tap<PIX, EDGE>(cp, P.stride_c, cw, chh, gx, gy, -dy0, -dx0, x) - x;
+        const int p2 = cs_tap<PIX, EDGE>(cp, P.stride_c, cw, chh, gx, gy, dy1, dx1, x) - x;
+        const int p3 = cs_tap<PIX, EDGE>(cp, P.stride_c, cw, chh, gx, gy, -dy1, -dx1, x) - x;
+        acc[16] += (uint32_t)(d0 * d0);
+#pragma unroll
+        for (int c = 1; c < 8; c++) {
+          const int pri = cdef_pool_pri(c) << coeff_shift, psh = damp_shift(pri, damping);
+          const int odd = cdef_pool_pri(c) & 1, w0 = odd ? 3 : 4, w1 = odd ? 3 : 2;
+          const int psum = w0 * (constrain(p0, pri, psh) + constrain(p1, pri, psh)) + w1 * (constrain(p2, pri, psh) + constrain(p3, pri, psh));
+          const int v = cs_round(x, psum);
+          acc[16 + c] += (uint32_t)((v - s) * (v - s));
+        }
+      }
+    }
+#pragma unroll
+    for (int c = 16; c < 24; c++) acc[c] += base;
+  }
+}
+
+template <typename PIX, int NS>
+__global__ void __launch_bounds__(64) cdef_search_kernel(Av1miDevParams P, int frame0, const PIX *__restrict__ rec, const PIX *__restrict__ src,
+                                                         const Av1miBlkInfo *__restrict__ blk) {
+  const int sbs_per_frame = P.sb_rows * P.sb_cols;
+  const int strip = NS == 1 ? 0 : (int)(blockIdx.x % NS);
+  const int item = blockIdx.x / NS;
+  const int f = frame0 + item / sbs_per_frame, sb = item % sbs_per_frame;
+  const int sbr = sb / P.sb_cols, sbc = sb % P.sb_cols;
+  const int lane = threadIdx.x;
+  const PIX *fr = rec + (size_t)f * P.frame_samples, *sf = src + (size_t)f * P.frame_samples;
+  const int x0 = sbc * 64, y0 = sbr * 64;
+  const int coeff_shift = P.bit_depth - 8;
+  const int w = P.width - x0 < 64 ? P.width - x0 : 64, h = P.height - y0 < 64 ? P.height - y0 : 64;
+  const int b8r = lane >> 3, b8c = lane & 7;
+  const bool inside = (sbr * 8 + b8r) < P.b8_rows && (sbc * 8 + b8c) < P.b8_cols;
+  int skip = 1;
+  if (inside) skip = blk[(size_t)f * P.b8_rows * P.b8_cols + (size_t)(sbr * 8 + b8r) * P.b8_cols + sbc * 8 + b8c].skip;
+  const bool sb_on = __ballot(inside && !skip) != 0ull;
+  if (strip == 0 && lane == 0) P.cdef_idx[(size_t)f * sbs_per_frame + sb] = sb_on ? 0 : -1;
+  if (!sb_on) return;   // (wave-uniform)
+  const bool do_filter = inside && !skip;
+  const bool mine = NS == 1 || b8r / (8 / NS) == strip;
+  {
+    int ydir = 0, var = 0;
+    if (do_filter && mine) {
+      const PIX *ty = fr + (size_t)(y0 + b8r * 8) * P.stride_y + x0 + b8c * 8;
+      int px[8][8];
+#pragma unroll
+      for (int i = 0; i < 8; i++) {
+#pragma unroll
+        for (int j = 0; j < 8; j++) px[i][j] = ((int)ty[(size_t)i * P.stride_y + j] >> coeff_shift) - 128;
+      }
+      cdef_direction_8x8(px, ydir, var);
+    }
+    g_cs.dir[lane] = (uint8_t)ydir;
+    g_cs.on[lane] = (uint8_t)do_filter;
+    g_cs.var[lane] = var;
+  }
+  __syncthreads();
+  const bool edge = x0 < 2 || y0 < 2 || x0 + 66 > P.width || y0 + 66 > P.height;
+  const int row0 = NS == 1 ? 0 : strip * (64 / NS), row1 = NS == 1 ? 64 : (strip + 1) * (64 / NS);
+  uint32_t acc[24];
+#pragma unroll
+  for (int k = 0; k < 24; k++) acc[k] = 0;
+  if (edge) cdef_search_sb<PIX, true>(P, fr, sf, x0, y0, w, h, lane, row0, row1, acc);
+  else cdef_search_sb<PIX, false>(P, fr, sf, x0, y0, w, h, lane, row0, row1, acc);
+  // per wave: transpose through LDS, 24 lanes sum a candidate's 64 lane sums in 64 bits
+#pragma unroll
+  for (int k = 0; k < 24; k++) g_cs.acc[k][lane] = acc[k];
+  __syncthreads();
+  if (lane < 24) {
+    unsigned long long t = 0;
+    for (int i = 0; i < 64; i++) t += g_cs.acc[lane][i];
+    if (t) atomicAdd(&P.cdef_err[((size_t)f * sbs_per_frame + sb) * 24 + lane], t);
+  }
+}
+
+// The frame's strength set and every superblock's index into it, one workgroup per frame: E[sb][p] =
+// err[sb][l] + err[sb][16 + c] for pair p = 8 l + c.  n = 2^cdef_bits greedy picks (each minimising the sum over superblocks of the best
+// error so far), then two refinement passes that replace S[j] by the pair minimising the sum against the other n - 1 when that is strictly
+// lower; first minimum in p order on ties.  Then cdef_idx = the first j minimising E[sb][S[j]] on coded superblocks, the set into
+// cdef_sel, and the 12 n strength bits into the frame's header slot (the host wrote placeholders of that length at cdef_str_bit).
+// Threads: 128 pairs x 4 quarters of the superblocks.
+__global__ void __launch_bounds__(512) cdef_select_kernel(Av1miDevParams P, int frame0, uint8_t *__restrict__ hdr_blob) {
+  __shared__ unsigned long long part[512];
+  __shared__ int S[8];
+  __shared__ int best_p;
+  const int f = frame0 + (int)blockIdx.x, t = threadIdx.x, p = t & 127, q = t >> 7;
+  const int nsb = P.sb_rows * P.sb_cols, n = 1 << P.cdef_bits;
+  const unsigned long long *E = P.cdef_err + (size_t)f * nsb * 24;
+  const int8_t *idx = P.cdef_idx + (size_t)f * nsb;
+  const int pl = p >> 3, pc = 16 + (p & 7);
+  // cost of every pair against the set S[0 .. m) without entry `excl` (-1: none); leaves the argmin in best_p, the costs in part[0 .. 128)
+  auto pass = [&](int m, int excl) {
+    unsigned long long sum = 0;
+    for (int sb = q; sb < nsb; sb += 4) {
+      if (idx[sb] < 0) continue;   // no cdef_idx coded: the same error under every pair
+      const unsigned long long *e = E + (size_t)sb * 24;
+      unsigned long long o = ~0ull;
+      for (int i = 0; i < m; i++)
+        if (i != excl) { const int s = S[i]; const unsigned long long v = e[s >> 3] + e[16 + (s & 7)]; o = v < o ? v : o; }
+      const unsigned long long v = e[pl] + e[pc];
+      sum += v < o ? v : o;
+    }
+    part[t] = sum;
+    __syncthreads();
+    if (t < 128) part[t] = part[t] + part[t + 128] + part[t + 256] + part[t + 384];
+    __syncthreads();
+    if (t == 0) {
+      int b = 0;
+      for (int i = 1; i < 128; i++) if (part[i] < part[b]) b = i;
+      best_p = b;
+    }
+    __syncthreads();
+  };
+  for (int m = 0; m < n; m++) {
+    pass(m, -1);
+    if (t == 0) S[m] = best_p;
+    __syncthreads();
+  }
+  if (n > 1)
+    for (int it = 0; it < 2; it++)
+      for (int j = 0; j < n; j++) {
+        pass(n, j);
+        if (t == 0 && part[best_p] < part[S[j]]) S[j] = best_p;
+        __syncthreads();
+      }
+  for (int sb = t; sb < nsb; sb += 512) {
+    if (idx[sb] < 0) continue;
+    const unsigned long long *e = E + (size_t)sb * 24;
+    int bj = 0;
+    unsigned long long bv = ~0ull;
+    for (int j = 0; j < n; j++) { const int s = S[j]; const unsigned long long v = e[s >> 3] + e[16 + (s & 7)]; if (v < bv) { bv = v; bj = j; } }
+    P.cdef_idx[(size_t)f * nsb + sb] = (int8_t)bj;
+  }
+  if (t < n) P.cdef_sel[f * 8 + t] = (uint8_t)S[t];
+  if (t == 0) {   // cdef_y_pri_strength (4 bits), cdef_y_sec_strength (2), cdef_uv_pri_strength (4), cdef_uv_sec_strength (2) per pair, MSB first
+    uint8_t *h = hdr_blob + P.seq_hdr_bytes + (size_t)f * P.hdr_slot_bytes;
+    int bit = P.cdef_str_bit[av1mi_frame_is_inter(P, f)];
+    for (int j = 0; j < n; j++) {
+      const int l = S[j] >> 3, c = S[j] & 7;
+      const uint32_t v = ((uint32_t)cdef_pool_pri(l >> 1) << 8) | ((uint32_t)(l & 1) * 2 << 6) | ((uint32_t)cdef_pool_pri(c) << 2);
+      for (int k = 11; k >= 0; k--, bit++) {
+        const uint8_t m = (uint8_t)(0x80 >> (bit & 7));
+        h[bit >> 3] = ((v >> k) & 1) ? (uint8_t)(h[bit >> 3] | m) : (uint8_t)(h[bit >> 3] & ~m);
+      }
+    }
+  }
 }
 
 // ------------------------------------------------------------------------------ SSE (PSNR)
@@ -503,20 +797,37 @@ extern "C" hipError_t av1mi_launch_cdef(const Av1miDevParams *P, const void *rec
                                         unsigned long long *sse, hipStream_t stream) {
   const int grid = P->n_frames * P->sb_rows * P->sb_cols;
   const bool strips = P->n_frames == 1;  // a one-frame launch sits on an inter chunk's serial chain
-  const bool sec = P->cdef_y_sec != 0 || P->cdef_uv_sec != 0;
+  const bool sel = P->cdef_search != 0;   // the search's pairs: some may have a secondary strength (the SEC kernels branch per superblock)
+  const bool sec = sel || P->cdef_y_sec != 0 || P->cdef_uv_sec != 0;
   const bool sse_here = src || sse;
   if (sse_here && (strips || !src || !sse)) return hipErrorInvalidValue;
+  if (sel && (!P->cdef_idx || !P->cdef_sel)) return hipErrorInvalidValue;
   // one-frame launches: 8-row strips (4 080 waves at 1080p, still one round of the chip) - 16-row strips were 2.5 us per frame slower
-#define CDEF_LAUNCH2(PIXT, SECV)                                                                                                           \
+#define CDEF_LAUNCH2(PIXT, SECV, SELV)                                                                                                     \
   do {                                                                                                                                     \
-    if (strips) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 8, SECV>), dim3(grid * 8), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk); \
-    else if (sse_here) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 1, SECV, true>), dim3(grid), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, (const PIXT *)src, sse); \
-    else hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 1, SECV>), dim3(grid), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk); \
+    if (strips) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 8, SECV, false, SELV>), dim3(grid * 8), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, nullptr, nullptr); \
+    else if (sse_here) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 1, SECV, true, SELV>), dim3(grid), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, (const PIXT *)src, sse); \
+    else hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 1, SECV, false, SELV>), dim3(grid), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, nullptr, nullptr); \
   } while (0)
-#define CDEF_LAUNCH(PIXT) do { if (sec) CDEF_LAUNCH2(PIXT, true); else CDEF_LAUNCH2(PIXT, false); } while (0)
+#define CDEF_LAUNCH(PIXT) do { if (sel) CDEF_LAUNCH2(PIXT, true, true); else if (sec) CDEF_LAUNCH2(PIXT, true, false); else CDEF_LAUNCH2(PIXT, false, false); } while (0)
   if (P->bit_depth == 8) CDEF_LAUNCH(uint8_t); else CDEF_LAUNCH(uint16_t);
 #undef CDEF_LAUNCH2
 #undef CDEF_LAUNCH
+  return hipGetLastError();
+}
+
+// the strength search over frames [frame0, frame0 + count) of the chunk (P.cdef_err zeroed by the caller; rec / src chunk-wide), then the
+// selection; one-frame launches (the P-frame chain) in 8-row strips, as CDEF
+extern "C" hipError_t av1mi_launch_cdef_search(const Av1miDevParams *P, const void *rec, const void *src, const Av1miBlkInfo *blk, uint8_t *hdr_blob,
+                                               int frame0, int count, hipStream_t stream) {
+  if (!P->cdef_search || !P->cdef_err || !P->cdef_idx || !P->cdef_sel) return hipErrorInvalidValue;
+  const int grid = count * P->sb_rows * P->sb_cols;
+  const int ns = count == 1 ? 8 : 1;
+#define CS_LAUNCH(PIXT, NSV) hipLaunchKernelGGL((cdef_search_kernel<PIXT, NSV>), dim3(grid * NSV), dim3(64), 0, stream, *P, frame0, (const PIXT *)rec, (const PIXT *)src, blk)
+  if (P->bit_depth == 8) { if (ns == 8) CS_LAUNCH(uint8_t, 8); else CS_LAUNCH(uint8_t, 1); }
+  else { if (ns == 8) CS_LAUNCH(uint16_t, 8); else CS_LAUNCH(uint16_t, 1); }
+#undef CS_LAUNCH
+  hipLaunchKernelGGL(cdef_select_kernel, dim3(count), dim3(512), 0, stream, *P, frame0, hdr_blob);
   return hipGetLastError();
 }
 

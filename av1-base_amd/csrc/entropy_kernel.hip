@@ -731,6 +731,7 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
   const int tox = tg.tox, toy = tg.toy, tox8 = tox >> 3, toy8 = toy >> 3;
 #define INFO(ux_, uy_) TI.info[((uy_) + toy8) * TW + (ux_) + tox8]
   const int16_t *sb_levels = levels + ((size_t)f * sbs_per_frame + sb) * AV1MI_SB_LEVELS;
+  int cdef_todo = P.cdef_bits > 0;   // read_cdef: the superblock's cdef_idx is coded at its first block that is not skipped
   if (si % TSB == 0) {  // clear_left_context at the start of every superblock row of the tile
     __syncthreads();
     if (lane < 48) { (&S->left_lvl[0][0])[lane] = 0; (&S->left_dc[0][0])[lane] = 0; }
@@ -803,6 +804,11 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
         if (avail_u) sctx += uni(INFO(b8x, b8y - 1).skip);
         if (avail_l) sctx += uni(INFO(b8x - 1, b8y).skip);
         sym_wide(y, lane, adapt, skip, CL::SKIP + sctx * 3, 2);
+        if (cdef_todo && !skip) {   // read_cdef (§5.11.56): cdef_bits literal bits, MSB first
+          const int ci = uni(P.cdef_idx[(size_t)f * sbs_per_frame + sb]);
+          for (int i = P.cdef_bits - 1; i >= 0; i--) sym_bool(y, lane, (ci >> i) & 1, 16384);
+          cdef_todo = 0;
+        }
         const int is_inter = inter_frame ? uni(INFO(b8x, b8y).is_inter) : 0;
         if (inter_frame) {
           // inter_frame_mode_info (§5.11.18): is_inter, context from the neighbours' intra-ness

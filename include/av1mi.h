@@ -20,7 +20,7 @@
 extern "C" {
 #endif
 
-#define AV1MI_ABI_VERSION 7
+#define AV1MI_ABI_VERSION 8
 
 /* positive failure codes (-> Av1anFailed(code)) */
 enum {
@@ -100,6 +100,11 @@ typedef struct {
   uint32_t me_presearch;    /* inter frames: 1 = hierarchical motion search - a quarter-resolution search of +-64 luma samples per 32x32 cell finds the
                                centre the full-resolution search of +-me_range then runs around (row a13's "1/4-res ... full"); 0 (default): the
                                full-resolution search runs around the zero vector */
+  uint32_t cdef_search;     /* CDEF strengths chosen per frame and per 64x64 superblock by an exhaustive search on the device:
+                               0 (default) = off, the fixed strengths above for every frame; k = 1..4 = on, cdef_bits = k - 1, i.e. 1, 2, 4 or 8
+                               strength pairs per frame, each superblock picking one by the squared error of the filtered output against the
+                               source.  With the search on cdef_y_pri, cdef_y_sec, cdef_uv_pri and cdef_uv_sec are ignored; cdef_damping still
+                               applies (0: the default, 5).  Values above 4, or any value but 0 with enable_cdef = 0, are refused */
 } av1mi_params;
 
 typedef struct {

@@ -22,6 +22,7 @@ pub struct Av1miParams {            // include/av1mi.h: av1mi_params
     pub partition_search: u32,      // 1 = content-driven partition between min_block_log2 and block_log2
     pub min_block_log2: u32,        // smallest leaf under partition_search (0 = 3: 8x8)
     pub me_presearch: u32,          // 1 = quarter-resolution pre-search (+-64) before the full-resolution search
+    pub cdef_search: u32,           // 0 = fixed CDEF strengths; k = 1..4 = per-frame / per-superblock search over 2^(k-1) strength pairs
 }
 #[repr(C)]
 pub struct Av1miJob {               // include/av1mi.h: av1mi_job  <->  Av1anEncodeParams (av1an.rs:36-45)
@@ -51,12 +52,12 @@ extern "C" {
     fn av1mi_encode_file(job: *const Av1miJob, cb: ProgressCb, user: *mut c_void, total: *mut Av1miReport) -> c_int;
 }
 
-// Layout pin (include/av1mi.h: av1mi_struct_sizes).  Compile time: the sizes this file was written against (ABI version 7, LP64);
+// Layout pin (include/av1mi.h: av1mi_struct_sizes).  Compile time: the sizes this file was written against (ABI version 8, LP64);
 // run time, once: the library's own sizes and offsets - a libav1mi.so built from another revision of the header is refused
 // instead of being handed structures it would read past.
-pub const AV1MI_ABI_VERSION: u32 = 7;
-const _: () = assert!(std::mem::size_of::<Av1miParams>() == 35 * 4);
-const _: () = assert!(std::mem::size_of::<Av1miJob>() == 3 * 8 + 3 * 4 + 35 * 4);
+pub const AV1MI_ABI_VERSION: u32 = 8;
+const _: () = assert!(std::mem::size_of::<Av1miParams>() == 36 * 4);
+const _: () = assert!(std::mem::size_of::<Av1miJob>() == 3 * 8 + 3 * 4 + 36 * 4);
 const _: () = assert!(std::mem::size_of::<Av1miReport>() == 120);
 pub fn check_layout() -> Result<(), EncodeError> {
     static ONCE: std::sync::OnceLock<bool> = std::sync::OnceLock::new();
