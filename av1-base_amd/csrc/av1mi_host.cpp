@@ -14,6 +14,7 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstddef>
 #include <mutex>
@@ -90,7 +91,9 @@ int bits_for(unsigned v) { int n = 0; while (v) { n++; v >>= 1; } return n ? n :
 struct Resolved {
   av1mi_params p;
   int qidx;
+  int dc_q, ac_q;                     // quantiser steps of qidx at p.bit_depth
   int cw, ch;                         // coded size: p.width / p.height rounded up to multiples of 8
+  bool padded;                        // the coded size is not the signalled one: frames are edge-extended in and cropped out
   int sb_cols, sb_rows;
   int tile_sb, tile_cols, tile_rows;  // tiles of tile_sb x tile_sb superblocks (1, or 2 beyond 64 superblocks either way)
   int qm_level;                       // quantiser-matrix level of all planes (15 = flat); only meaningful with p.enable_qm
@@ -107,6 +110,7 @@ int resolve(const av1mi_params *in, Resolved *r) {
   av1mi_params &p = r->p;
   if (p.width < 8 || p.height < 8 || (p.width & 1) || (p.height & 1) || p.width > 65536 || p.height > 65536) return AV1MI_E_INVALID_ARG;
   r->cw = (int)((p.width + 7) & ~7u); r->ch = (int)((p.height + 7) & ~7u);
+  r->padded = r->cw != (int)p.width || r->ch != (int)p.height;
   if (p.bit_depth != 8 && p.bit_depth != 10) return AV1MI_E_INVALID_ARG;
   if (p.cq_level > 63 || p.film_grain > 50) return AV1MI_E_INVALID_ARG;
   if (p.keyint == 0) p.keyint = 1;
@@ -118,6 +122,8 @@ int resolve(const av1mi_params *in, Resolved *r) {
   if (p.cdef_damping < 3 || p.cdef_damping > 6 || p.cdef_y_pri > 15 || p.cdef_uv_pri > 15 || p.cdef_y_sec > 3 || p.cdef_uv_sec > 3) return AV1MI_E_INVALID_ARG;
   if (p.cdef_search > 4 || (p.cdef_search && !p.enable_cdef)) return AV1MI_E_INVALID_ARG;
   r->qidx = kQuantizerToQindex[p.cq_level];
+  r->dc_q = p.bit_depth == 8 ? av1_dc_q8[r->qidx] : av1_dc_q10[r->qidx];
+  r->ac_q = p.bit_depth == 8 ? av1_ac_q8[r->qidx] : av1_ac_q10[r->qidx];
   if (p.subpel > 1 || p.enable_lr > 2 || p.color_range > 1 || p.intra_angle_delta > 1 || p.intra_edge_filter > 1 || p.cfl > 1 || p.tx_search > 1) return AV1MI_E_INVALID_ARG;
   if (p.partition_search > 1 || p.me_presearch > 1) return AV1MI_E_INVALID_ARG;
   if (p.min_block_log2 == 0) p.min_block_log2 = 3;
@@ -142,8 +148,7 @@ int resolve(const av1mi_params *in, Resolved *r) {
 // deblocking level of a frame (the same for all four filters): libaom's "pick from q" rule; 0 = filter off
 int deblock_level(const Resolved &r, bool key) {
   if (!r.p.deblock) return 0;
-  const int q = r.p.bit_depth == 8 ? av1_ac_q8[r.qidx] : av1_ac_q10[r.qidx];
-  int g = r.p.bit_depth == 8 ? (q * 20723 + 1015158) >> 18 : (q * 20723 + 4060632) >> 20;
+  int g = r.p.bit_depth == 8 ? (r.ac_q * 20723 + 1015158) >> 18 : (r.ac_q * 20723 + 4060632) >> 20;
   if (key) g -= 4;
   return g < 0 ? 0 : (g > 63 ? 63 : g);
 }
@@ -424,27 +429,21 @@ std::vector<uint16_t> make_cdf_blob(int qidx) {
   return v;
 }
 
-}  // namespace
-
 // ------------------------------------------------------------------ context
-struct av1mi_ctx {
-  int device = -1;
-  hipStream_t stream = nullptr;   // the four streams come from and go back to a process-wide pool (av1mi_ctx_create)
-  hipStream_t stream2 = nullptr;  // CDEF + SSE run here, beside the entropy kernels on `stream`
-  hipStream_t stream3 = nullptr;  // inter chunks: entropy coding of finished groups of frames, beside the frame-by-frame chain
-  hipStream_t stream4 = nullptr;  // the frame-edge tiles' symbolize variant, beside the regular one on `stream` (av1mi_launch_entropy)
-  hipEvent_t ev[13] = {};
-  std::vector<hipEvent_t> me_ev;       // per frame: its motion search has finished (second stream -> main stream)
-  std::vector<hipEvent_t> grp_ev;      // per group of frames of an inter chunk: reconstructed (main stream -> third stream)
-  std::string err;
-  // workspace (device)
+// Points of one chunk on the context's streams; the report's stage times are the intervals between them.  Main stream: start, source
+// on the device, reconstruction (and the rest of the kind's work before entropy coding), symbolize, entropy coding (groups joined), packing
+// and download done.  Second stream: its work beside the range coder.  Third: an inter chunk's groups.  Fourth: the edge tiles' fork, join.
+enum ChunkEvent { EV_START, EV_SRC_READY, EV_RECON_DONE, EV_SYM_DONE, EV_ENTROPY_DONE, EV_PACK_DONE, EV_DOWNLOAD_DONE,
+                  EV_CDEF_START, EV_CDEF_DONE, EV_GROUPS_JOINED, EV_EDGE_FORK, EV_EDGE_JOIN, EV_COUNT };
+
+// A context's device workspace and host staging buffer.  Every buffer comes from ws_alloc, which records it; free_workspace frees
+// what was recorded and resets all of it to these defaults.
+struct Workspace {
   size_t cap_frames = 0;
-  int cap_scale = 1;   // per-tile symbol-stream / bitstream-slot capacity multiplier (1, 2, 4, ... 64)
-  int ws_scale = 0;    // the multiplier the workspace was allocated with
-  Resolved res = {};
+  int scale = 0;       // the capacity multiplier the workspace was allocated with
+  Resolved res = {};   // ... and the parameters of its last chunk
   void *d_src = nullptr, *d_rec = nullptr, *d_fin = nullptr;
-  int16_t *d_levels = nullptr;
-  Av1miBlkInfo *d_blk = nullptr;
+  int16_t *d_levels = nullptr; Av1miBlkInfo *d_blk = nullptr;
   uint8_t *d_slots = nullptr, *d_out = nullptr, *d_hdr = nullptr;
   uint16_t *d_cdf = nullptr;
   Av1miDevParams *d_params = nullptr;  // copy of P for the kernels that read their parameters through a pointer (recon)
@@ -460,19 +459,44 @@ struct av1mi_ctx {
   uint32_t *d_centre = nullptr;            // me_presearch: centre code of the full search per [frame][superblock]
   uint32_t *d_part = nullptr;              // content-driven partition: split mask per [frame][superblock] (partition_kernel)
   uint32_t *d_me64 = nullptr;              // 64x64 leaves: the search's [frame][superblock][candidate] SAD table
-  size_t me64_bytes = 0;
   Av1miQmEntry *d_qm = nullptr;        // quantiser-matrix steps (Av1miDevParams::qm_tab), valid for qm_key = (level, qidx, bit depth)
-  std::vector<Av1miQmEntry> h_qm;
-  int qm_key = -1;
+  std::vector<Av1miQmEntry> h_qm; int qm_key = -1;
   uint8_t *d_lrc = nullptr;            // per restoration unit: 0 = off, k = candidate k-1
   unsigned long long *d_lrsse = nullptr;  // per restoration unit: the candidates' SSE sums (scratch of lr_kernel.hip's two phases)
   unsigned long long *d_cdef_err = nullptr;  // CDEF strength search: per [frame][superblock] the 24 candidates' squared errors
   int8_t *d_cdef_idx = nullptr;              // ... per [frame][superblock] the index into the frame's set (-1: not coded)
   uint8_t *d_cdef_sel = nullptr;             // ... per frame the set: 8 slots of pair indices
-  size_t out_cap = 0;
-  // host staging (pinned)
-  uint8_t *h_out = nullptr;
-  size_t h_out_cap = 0;
+  uint8_t *h_out = nullptr;            // host staging (pinned), for when the caller's buffer cannot be page-locked
+  size_t out_cap = 0, me64_bytes = 0, h_out_cap = 0;   // bytes of d_out, d_me64, h_out
+  std::vector<std::pair<void *, bool>> owned;   // every buffer above: (address, page-locked host memory)
+};
+
+// (Re)allocates one buffer of the workspace - device memory, or page-locked host memory with `host` - and records it for free_workspace
+template <class T>
+hipError_t ws_alloc(Workspace &w, T *&p, size_t bytes, bool host = false) {
+  for (auto b = w.owned.begin(); p && b != w.owned.end(); ++b)   // a buffer that grows: the old one goes
+    if (b->first == (void *)p) { (void)(b->second ? hipHostFree(p) : hipFree(p)); w.owned.erase(b); break; }
+  void *v = nullptr;
+  const hipError_t e = host ? hipHostMalloc(&v, bytes, hipHostMallocDefault) : hipMalloc(&v, bytes);
+  if (e == hipSuccess) w.owned.emplace_back(v, host);
+  p = (T *)v;
+  return e;
+}
+
+}  // namespace
+
+struct av1mi_ctx {
+  int device = -1;
+  hipStream_t stream = nullptr;   // the four streams come from and go back to a process-wide pool (av1mi_ctx_create)
+  hipStream_t stream2 = nullptr;  // CDEF + SSE run here, beside the entropy kernels on `stream`
+  hipStream_t stream3 = nullptr;  // inter chunks: entropy coding of finished groups of frames, beside the frame-by-frame chain
+  hipStream_t stream4 = nullptr;  // the frame-edge tiles' symbolize variant, beside the regular one on `stream` (av1mi_launch_entropy)
+  hipEvent_t ev[EV_COUNT] = {};
+  std::vector<hipEvent_t> me_ev;       // per frame: its motion search has finished (second stream -> main stream)
+  std::vector<hipEvent_t> grp_ev;      // per group of frames of an inter chunk: reconstructed (main stream -> third stream)
+  std::string err;
+  int cap_scale = 1;   // per-tile symbol-stream / bitstream-slot capacity multiplier (1, 2, 4, ... 64)
+  Workspace ws;
   Av1miDevParams P = {};
 };
 
@@ -497,171 +521,138 @@ void set_err(av1mi_ctx *c, const char *fmt, ...) {
   } while (0)
 
 void free_workspace(av1mi_ctx *c) {
-  void *ptrs[] = { c->d_src, c->d_rec, c->d_fin, c->d_levels, c->d_blk, c->d_slots, c->d_out, c->d_hdr, c->d_cdf, c->d_tile_bytes,
-                   c->d_tile_off, c->d_frame_size, c->d_payload, c->d_sym, c->d_frame_off, c->d_sse, c->d_overflow, c->d_streams, c->d_combos, c->d_me, c->d_cd, c->d_lrc, c->d_stage, c->d_qm, c->d_me_sub, c->d_lrsse, c->d_params, c->d_me64, c->d_part, c->d_quarter, c->d_centre, c->d_cdef_err, c->d_cdef_idx, c->d_cdef_sel };
-  for (void *p : ptrs) if (p) (void)hipFree(p);
-  c->d_src = c->d_rec = c->d_fin = nullptr; c->d_levels = nullptr; c->d_blk = nullptr; c->d_slots = c->d_out = c->d_hdr = nullptr;
-  c->d_cdf = nullptr; c->d_tile_bytes = c->d_tile_off = c->d_frame_size = c->d_payload = c->d_sym = nullptr;
-  c->d_frame_off = c->d_sse = nullptr; c->d_overflow = nullptr; c->d_streams = c->d_combos = nullptr; c->d_me = nullptr; c->d_cd = nullptr; c->d_lrc = nullptr; c->d_stage = nullptr; c->d_qm = nullptr; c->qm_key = -1; c->d_me_sub = nullptr; c->d_lrsse = nullptr; c->d_params = nullptr; c->d_me64 = nullptr; c->me64_bytes = 0; c->d_part = nullptr; c->d_quarter = nullptr; c->d_centre = nullptr;
-  c->d_cdef_err = nullptr; c->d_cdef_idx = nullptr; c->d_cdef_sel = nullptr;
-  if (c->h_out) (void)hipHostFree(c->h_out);
-  c->h_out = nullptr; c->h_out_cap = 0;
-  c->cap_frames = 0;
+  for (auto &b : c->ws.owned) (void)(b.second ? hipHostFree(b.first) : hipFree(b.first));
+  c->ws = Workspace();
 }
+
+// Per-tile capacities (per superblock of the tile): 8192 symbol-stream entries and 4096 output bytes hold any tile of
+// ordinary content down to about CQ 20 (1080p clip at CQ 30: longest tile 4826 entries, ~1.2 KB); a tile that outgrows
+// them is detected on the device and the chunk is re-run at the next multiplier, which the context then keeps.
+// x32 / x64 reach the true worst case of a 64x64 4:2:0 tile (6144 coefficients x <= 37 stream entries: base + 4
+// range + sign + 31 Golomb bits; <= 10 output bytes per coefficient), so the retry ends.
+int tile_slot_bytes(const Resolved &r, int scale) { return 4096 * scale * r.tile_sb * r.tile_sb; }
+int tile_stream_cap(const Resolved &r, int scale) { return 8192 * scale * r.tile_sb * r.tile_sb; }
 
 int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   const av1mi_params &p = r.p;
+  Workspace &w = c->ws;
   // the per-tile buffers (symbol streams, bitstream slots, packed output) are sized by the tile grid and the per-tile
   // capacities, which follow tile_sb: a context that switches tile_sb at the same frame size must not reuse them
   // (648x360: 66 tiles x 4096 entries at tile_sb 1, but 18 x 16384 at tile_sb 2)
-  bool same = c->cap_frames >= n_frames && c->res.p.width == p.width && c->res.p.height == p.height && c->res.p.bit_depth == p.bit_depth &&
-              c->ws_scale == c->cap_scale && c->res.tile_sb == r.tile_sb;
+  const bool same = w.cap_frames >= n_frames && w.res.p.width == p.width && w.res.p.height == p.height && w.res.p.bit_depth == p.bit_depth &&
+                    w.scale == c->cap_scale && w.res.tile_sb == r.tile_sb;
   const int bps = p.bit_depth > 8 ? 2 : 1;
-  const size_t frame_samples = (size_t)r.cw * r.ch * 3 / 2;   // coded size
-  const size_t nsb = (size_t)r.sb_cols * r.sb_rows;
-  const size_t ntile = (size_t)r.tile_cols * r.tile_rows;
-  // Per-tile capacities (per superblock of the tile): 8192 symbol-stream entries and 4096 output bytes hold any tile of
-  // ordinary content down to about CQ 20 (1080p clip at CQ 30: longest tile 4826 entries, ~1.2 KB); a tile that outgrows
-  // them is detected on the device and the chunk is re-run at the next multiplier, which the context then keeps.
-  // x32 / x64 reach the true worst case of a 64x64 4:2:0 tile (6144 coefficients x <= 37 stream entries: base + 4
-  // range + sign + 31 Golomb bits; <= 10 output bytes per coefficient), so the retry ends.
-  const int slot = 4096 * c->cap_scale * r.tile_sb * r.tile_sb;
-  const int stream_cap = 8192 * c->cap_scale * r.tile_sb * r.tile_sb;
+  const size_t frame_bytes = (size_t)r.cw * r.ch * 3 / 2 * bps;   // coded size
+  const size_t nsb = (size_t)r.sb_cols * r.sb_rows, ntile = (size_t)r.tile_cols * r.tile_rows, nb8 = (size_t)(r.cw / 8) * (r.ch / 8);
   if (!same) {
     free_workspace(c);
-    const size_t nf = n_frames;
-    HIPCHK(c, hipMalloc(&c->d_src, nf * frame_samples * bps));
-    HIPCHK(c, hipMalloc(&c->d_rec, nf * frame_samples * bps));
-    HIPCHK(c, hipMalloc(&c->d_fin, nf * frame_samples * bps));
-    HIPCHK(c, hipMalloc((void **)&c->d_levels, nf * nsb * AV1MI_SB_LEVELS * sizeof(int16_t)));
-    const size_t nb8 = (size_t)(r.cw / 8) * (r.ch / 8);
-    HIPCHK(c, hipMalloc((void **)&c->d_blk, nf * nb8 * sizeof(Av1miBlkInfo)));
+    const size_t nf = n_frames, slot = (size_t)tile_slot_bytes(r, c->cap_scale);
+    for (void **b : { &w.d_src, &w.d_rec, &w.d_fin }) HIPCHK(c, ws_alloc(w, *b, nf * frame_bytes));
+    HIPCHK(c, ws_alloc(w, w.d_levels, nf * nsb * AV1MI_SB_LEVELS * sizeof(int16_t)));
+    HIPCHK(c, ws_alloc(w, w.d_blk, nf * nb8 * sizeof(Av1miBlkInfo)));
     // on the context's own stream: hipMemset would run on the null stream, which a non-blocking stream does not wait
     // for - the fill could land after the first reconstruction kernel had written its block info
-    HIPCHK(c, hipMemsetAsync(c->d_blk, 0, nf * nb8 * sizeof(Av1miBlkInfo), c->stream));
-    HIPCHK(c, hipMalloc((void **)&c->d_slots, nf * ntile * slot * 2));  // 16-bit pre-carry entries, one per output byte
-    c->out_cap = nf * (ntile * (size_t)(slot + 4) + 256);
-    HIPCHK(c, hipMalloc((void **)&c->d_out, c->out_cap));
-    HIPCHK(c, hipMalloc((void **)&c->d_hdr, 256 + nf * 512));
-    HIPCHK(c, hipMalloc((void **)&c->d_cdf, Av1miCdfLayout::TOTAL * sizeof(uint16_t)));
-    HIPCHK(c, hipMalloc((void **)&c->d_params, sizeof(Av1miDevParams)));
-    HIPCHK(c, hipMalloc((void **)&c->d_tile_bytes, nf * nsb * 4));
-    HIPCHK(c, hipMalloc((void **)&c->d_tile_off, nf * nsb * 4));
-    HIPCHK(c, hipMalloc((void **)&c->d_sym, nf * nsb * 4));
-    HIPCHK(c, hipMalloc((void **)&c->d_combos, nf * nsb * 4));
-    HIPCHK(c, hipMalloc((void **)&c->d_streams, nf * ntile * (size_t)stream_cap * 4));
-    HIPCHK(c, hipMalloc((void **)&c->d_frame_size, nf * 4));
-    HIPCHK(c, hipMalloc((void **)&c->d_payload, nf * 4));
-    HIPCHK(c, hipMalloc((void **)&c->d_frame_off, (nf + 1) * 8));
-    HIPCHK(c, hipMalloc((void **)&c->d_sse, nf * 3 * 8));
-    HIPCHK(c, hipMalloc((void **)&c->d_overflow, 4));
-    HIPCHK(c, hipMalloc((void **)&c->d_me, nf * nb8 * 8));
-    c->cap_frames = n_frames;
-    c->ws_scale = c->cap_scale;
+    HIPCHK(c, hipMemsetAsync(w.d_blk, 0, nf * nb8 * sizeof(Av1miBlkInfo), c->stream));
+    HIPCHK(c, ws_alloc(w, w.d_slots, nf * ntile * slot * 2));  // 16-bit pre-carry entries, one per output byte
+    w.out_cap = nf * (ntile * (slot + 4) + 256);
+    HIPCHK(c, ws_alloc(w, w.d_out, w.out_cap));
+    HIPCHK(c, ws_alloc(w, w.d_hdr, 256 + nf * 512));
+    HIPCHK(c, ws_alloc(w, w.d_cdf, Av1miCdfLayout::TOTAL * sizeof(uint16_t)));
+    HIPCHK(c, ws_alloc(w, w.d_params, sizeof(Av1miDevParams)));
+    for (uint32_t **b : { &w.d_tile_bytes, &w.d_tile_off, &w.d_sym, &w.d_combos }) HIPCHK(c, ws_alloc(w, *b, nf * nsb * 4));
+    HIPCHK(c, ws_alloc(w, w.d_streams, nf * ntile * (size_t)tile_stream_cap(r, c->cap_scale) * 4));
+    for (uint32_t **b : { &w.d_frame_size, &w.d_payload }) HIPCHK(c, ws_alloc(w, *b, nf * 4));
+    HIPCHK(c, ws_alloc(w, w.d_frame_off, (nf + 1) * 8));
+    HIPCHK(c, ws_alloc(w, w.d_sse, nf * 3 * 8));
+    HIPCHK(c, ws_alloc(w, w.d_overflow, 4));
+    HIPCHK(c, ws_alloc(w, w.d_me, nf * nb8 * 8));
+    w.cap_frames = n_frames; w.scale = c->cap_scale;
   }
-  if ((r.cw != (int)p.width || r.ch != (int)p.height) && !c->d_stage)
-    HIPCHK(c, hipMalloc(&c->d_stage, c->cap_frames * (size_t)p.width * p.height * 3 / 2 * bps));
-  if (p.partition_search && !c->d_part) HIPCHK(c, hipMalloc((void **)&c->d_part, c->cap_frames * nsb * sizeof(uint32_t)));
-  if (p.me_presearch && !c->d_quarter) {
-    HIPCHK(c, hipMalloc((void **)&c->d_quarter, c->cap_frames * (size_t)(r.cw / 4) * (r.ch / 4) * sizeof(uint16_t)));
-    HIPCHK(c, hipMalloc((void **)&c->d_centre, c->cap_frames * nsb * sizeof(uint32_t)));
+  const size_t nf = w.cap_frames;
+  if (r.padded && !w.d_stage) HIPCHK(c, ws_alloc(w, w.d_stage, nf * (size_t)p.width * p.height * 3 / 2 * bps));
+  if (p.partition_search && !w.d_part) HIPCHK(c, ws_alloc(w, w.d_part, nf * nsb * sizeof(uint32_t)));
+  if (p.me_presearch && !w.d_quarter) {
+    HIPCHK(c, ws_alloc(w, w.d_quarter, nf * (size_t)(r.cw / 4) * (r.ch / 4) * sizeof(uint16_t)));
+    HIPCHK(c, ws_alloc(w, w.d_centre, nf * nsb * sizeof(uint32_t)));
   }
-  if (p.subpel && !c->d_me_sub)   // output of the sub-sample refinement
-    HIPCHK(c, hipMalloc((void **)&c->d_me_sub, (size_t)c->cap_frames * (r.cw / 8) * (r.ch / 8) * 8));
+  if (p.subpel && !w.d_me_sub) HIPCHK(c, ws_alloc(w, w.d_me_sub, nf * nb8 * 8));  // output of the sub-sample refinement
   if (p.block_log2 >= 6 && p.keyint > 1) {   // candidate table of the 64x64 leaves' motion search
-    const size_t nc = 2 * (size_t)(p.me_range ? p.me_range : 8) + 1, need = c->cap_frames * nsb * nc * nc * sizeof(uint32_t);
-    if (c->me64_bytes < need) {
-      if (c->d_me64) (void)hipFree(c->d_me64);
-      c->d_me64 = nullptr; c->me64_bytes = 0;
-      HIPCHK(c, hipMalloc((void **)&c->d_me64, need));
-      c->me64_bytes = need;
-    }
+    const size_t nc = 2 * (size_t)(p.me_range ? p.me_range : 8) + 1, need = nf * nsb * nc * nc * sizeof(uint32_t);
+    if (w.me64_bytes < need) { w.me64_bytes = 0; HIPCHK(c, ws_alloc(w, w.d_me64, need)); w.me64_bytes = need; }
   }
-  if (p.cdef_search && !c->d_cdef_err) {
-    HIPCHK(c, hipMalloc((void **)&c->d_cdef_err, c->cap_frames * nsb * 24 * sizeof(unsigned long long)));
-    HIPCHK(c, hipMalloc((void **)&c->d_cdef_idx, c->cap_frames * nsb));
-    HIPCHK(c, hipMalloc((void **)&c->d_cdef_sel, c->cap_frames * 8));
+  if (p.cdef_search && !w.d_cdef_err) {
+    HIPCHK(c, ws_alloc(w, w.d_cdef_err, nf * nsb * 24 * sizeof(unsigned long long)));
+    HIPCHK(c, ws_alloc(w, w.d_cdef_idx, nf * nsb));
+    HIPCHK(c, ws_alloc(w, w.d_cdef_sel, nf * 8));
   }
-  if (p.enable_lr && !c->d_cd) {
-    const size_t nf = c->cap_frames;
-    HIPCHK(c, hipMalloc(&c->d_cd, nf * frame_samples * bps));
-    HIPCHK(c, hipMalloc((void **)&c->d_lrc, nf * nsb + 64));
-    HIPCHK(c, hipMalloc((void **)&c->d_lrsse, (nf * nsb + 64) * 8 * sizeof(unsigned long long)));
+  if (p.enable_lr && !w.d_cd) {
+    HIPCHK(c, ws_alloc(w, w.d_cd, nf * frame_bytes));
+    HIPCHK(c, ws_alloc(w, w.d_lrc, nf * nsb + 64));
+    HIPCHK(c, ws_alloc(w, w.d_lrsse, (nf * nsb + 64) * 8 * sizeof(unsigned long long)));
   }
-  c->res = r;
-  Av1miDevParams &P = c->P;
-  memset(&P, 0, sizeof(P));
-  P.width = r.cw; P.height = r.ch; P.bit_depth = p.bit_depth;
-  P.true_w = (int)p.width; P.true_h = (int)p.height;
-  P.mi_rows = r.ch / 4; P.mi_cols = r.cw / 4;
-  P.sb_rows = r.sb_rows; P.sb_cols = r.sb_cols;
-  P.tile_sb = r.tile_sb; P.tile_rows = r.tile_rows; P.tile_cols = r.tile_cols;
-  P.b8_rows = r.ch / 8; P.b8_cols = r.cw / 8;
-  P.n_frames = (int)n_frames;
-  P.base_q_idx = r.qidx;
-  P.qctx = r.qidx <= 20 ? 0 : (r.qidx <= 60 ? 1 : (r.qidx <= 120 ? 2 : 3));
-  P.dc_q = p.bit_depth == 8 ? av1_dc_q8[r.qidx] : av1_dc_q10[r.qidx];
-  P.ac_q = p.bit_depth == 8 ? av1_ac_q8[r.qidx] : av1_ac_q10[r.qidx];
-  P.dc_recip = (uint32_t)((((uint64_t)1 << 32) + P.dc_q - 1) / P.dc_q);
-  P.ac_recip = (uint32_t)((((uint64_t)1 << 32) + P.ac_q - 1) / P.ac_q);
-  P.using_qm = p.enable_qm ? 1 : 0; P.qm_y = P.qm_uv = r.qm_level;
-  P.qm_tab = nullptr;
+  w.res = r;
   if (p.enable_qm && r.qm_level < 15) {
     // dequantiser step per coefficient position (§7.12.3) and its reciprocal, for the square transform sizes 4..32
-    if (!c->d_qm) HIPCHK(c, hipMalloc((void **)&c->d_qm, 2 * AV1MI_QM_PLANE * sizeof(Av1miQmEntry)));
-    if (c->qm_key != ((r.qm_level << 16) | (r.qidx << 4) | (int)p.bit_depth)) {
+    if (!w.d_qm) HIPCHK(c, ws_alloc(w, w.d_qm, 2 * AV1MI_QM_PLANE * sizeof(Av1miQmEntry)));
+    const int key = (r.qm_level << 16) | (r.qidx << 4) | (int)p.bit_depth;
+    if (w.qm_key != key) {
       static const int off[4] = { AV1MI_QM_4X4, AV1MI_QM_8X8, AV1MI_QM_16X16, AV1MI_QM_32X32 };
-      c->h_qm.resize(2 * AV1MI_QM_PLANE);
+      w.h_qm.resize(2 * AV1MI_QM_PLANE);
       for (int pt = 0; pt < 2; pt++)
         for (int l2 = 2; l2 <= 5; l2++)
           for (int i = 0; i < (1 << (2 * l2)); i++) {
-            const uint32_t q = (uint32_t)(i ? P.ac_q : P.dc_q);
+            const uint32_t q = (uint32_t)(i ? r.ac_q : r.dc_q);
             const uint32_t q2 = (q * av1_qm_iwt[r.qm_level][pt][off[l2 - 2] + i] + 16) >> 5;
-            c->h_qm[pt * AV1MI_QM_PLANE + off[l2 - 2] + i] = { q2, (uint32_t)((((uint64_t)1 << 32) + q2 - 1) / q2) };
+            w.h_qm[pt * AV1MI_QM_PLANE + off[l2 - 2] + i] = { q2, (uint32_t)((((uint64_t)1 << 32) + q2 - 1) / q2) };
           }
-      HIPCHK(c, hipMemcpyAsync(c->d_qm, c->h_qm.data(), c->h_qm.size() * sizeof(Av1miQmEntry), hipMemcpyHostToDevice, c->stream));
-      c->qm_key = (r.qm_level << 16) | (r.qidx << 4) | (int)p.bit_depth;
+      HIPCHK(c, hipMemcpyAsync(w.d_qm, w.h_qm.data(), w.h_qm.size() * sizeof(Av1miQmEntry), hipMemcpyHostToDevice, c->stream));
+      w.qm_key = key;
     }
-    P.qm_tab = c->d_qm;
   }
+  return AV1MI_OK;
+}
+
+// The kernels' parameters of a chunk of `n_frames` frames: `r` at the coded size, the per-tile capacities of multiplier `scale` and the
+// workspace buffers the kernels find through them.  The header sizes follow with the headers (prepare_chunk).
+Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const uint32_t *part, const Av1miQmEntry *qm,
+                          unsigned long long *cdef_err, int8_t *cdef_idx, uint8_t *cdef_sel) {
+  const av1mi_params &p = r.p;
+  Av1miDevParams P;
+  memset(&P, 0, sizeof(P));
+  P.width = r.cw; P.height = r.ch; P.bit_depth = p.bit_depth; P.true_w = (int)p.width; P.true_h = (int)p.height;
+  P.mi_rows = r.ch / 4; P.mi_cols = r.cw / 4; P.b8_rows = r.ch / 8; P.b8_cols = r.cw / 8; P.sb_rows = r.sb_rows; P.sb_cols = r.sb_cols;
+  P.tile_sb = r.tile_sb; P.tile_rows = r.tile_rows; P.tile_cols = r.tile_cols;
+  P.n_frames = (int)n_frames;
+  P.base_q_idx = r.qidx;
+  P.qctx = r.qidx <= 20 ? 0 : (r.qidx <= 60 ? 1 : (r.qidx <= 120 ? 2 : 3));
+  P.dc_q = r.dc_q; P.ac_q = r.ac_q;
+  P.dc_recip = (uint32_t)((((uint64_t)1 << 32) + P.dc_q - 1) / P.dc_q);
+  P.ac_recip = (uint32_t)((((uint64_t)1 << 32) + P.ac_q - 1) / P.ac_q);
+  P.using_qm = p.enable_qm ? 1 : 0; P.qm_y = P.qm_uv = r.qm_level;
+  P.qm_tab = p.enable_qm && r.qm_level < 15 ? qm : nullptr;
   P.max_bs_log2 = (int)p.block_log2;
   P.min_bs_log2 = p.partition_search ? (int)p.min_block_log2 : (int)p.block_log2;
-  P.part_map = p.partition_search ? c->d_part : nullptr;
+  P.part_map = p.partition_search ? part : nullptr;
   P.mode_mask = p.intra_mode_mask ? (p.intra_mode_mask & 0x1FFF) : 0x0007;  // default candidates: DC, V, H
-  P.angle_delta = p.intra_angle_delta ? 1 : 0;
-  P.edge_filter = p.intra_edge_filter ? 1 : 0;
-  P.cfl = p.cfl ? 1 : 0;
-  P.tx_search = p.tx_search ? 1 : 0;
+  P.angle_delta = p.intra_angle_delta ? 1 : 0; P.edge_filter = p.intra_edge_filter ? 1 : 0; P.cfl = p.cfl ? 1 : 0; P.tx_search = p.tx_search ? 1 : 0;
   P.enable_cdef = p.enable_cdef ? 1 : 0;
   P.cdef_y_pri = p.cdef_y_pri; P.cdef_y_sec = p.cdef_y_sec; P.cdef_uv_pri = p.cdef_uv_pri; P.cdef_uv_sec = p.cdef_uv_sec;
-  P.cdef_damping = p.cdef_damping;
-  P.cdef_search = (int)p.cdef_search;
-  P.cdef_bits = p.cdef_search ? (int)p.cdef_search - 1 : 0;
-  P.cdef_err = p.cdef_search ? c->d_cdef_err : nullptr;
-  P.cdef_idx = p.cdef_search ? c->d_cdef_idx : nullptr;
-  P.cdef_sel = p.cdef_search ? c->d_cdef_sel : nullptr;
+  P.cdef_damping = p.cdef_damping; P.cdef_search = (int)p.cdef_search;
+  if (p.cdef_search) { P.cdef_bits = (int)p.cdef_search - 1; P.cdef_err = cdef_err; P.cdef_idx = cdef_idx; P.cdef_sel = cdef_sel; }
   P.disable_cdf_update = p.cdf_update ? 0 : 1;
-  P.stride_y = r.cw; P.stride_c = r.cw / 2;
-  P.plane_off_u = (long)r.cw * r.ch;
-  P.plane_off_v = P.plane_off_u + (long)(r.cw / 2) * (r.ch / 2);
-  P.frame_samples = (long)frame_samples;
-  P.tile_slot_bytes = slot;
-  P.stream_cap = stream_cap;
-  P.tile_size_bytes = 4;
-  P.keyint = (int)p.keyint;
-  P.me_range = (int)p.me_range;
-  P.subpel = p.subpel ? 1 : 0;
-  P.me_presearch = p.me_presearch ? 1 : 0;
+  P.stride_y = r.cw; P.stride_c = r.cw / 2; P.frame_samples = (long)r.cw * r.ch * 3 / 2;
+  P.plane_off_u = (long)r.cw * r.ch; P.plane_off_v = P.plane_off_u + (long)(r.cw / 2) * (r.ch / 2);
+  P.tile_slot_bytes = tile_slot_bytes(r, scale); P.stream_cap = tile_stream_cap(r, scale); P.tile_size_bytes = 4;
+  P.keyint = (int)p.keyint; P.me_range = (int)p.me_range; P.subpel = p.subpel ? 1 : 0; P.me_presearch = p.me_presearch ? 1 : 0;
   P.hdr_slot_bytes = 512;
   for (int i = 0; i < 4; i++) { P.lf_level[i] = deblock_level(r, true); P.lf_level_inter[i] = deblock_level(r, false); }
-  P.lf_sharpness = 0;
   P.enable_lr = (int)p.enable_lr;
   for (int rf = 0; rf < 4; rf++)
     for (int k = 0; k < 3; k++) {
       const BitString b = lr_code_of(rf, k); P.lr_code_len[rf][k] = b.len; P.lr_code_bits[rf][k] = b.bits;
       const BitString g = sgr_code_of(rf, k); P.sgr_code_len[rf][k] = g.len; P.sgr_code_bits[rf][k] = g.bits;
     }
-  return AV1MI_OK;
+  return P;
 }
 
 }  // namespace
@@ -935,30 +926,17 @@ int av1mi_encode_chunk(av1mi_ctx *c, const av1mi_params *params, const void *fra
   }
 }
 
-static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
-                             av1mi_buf *out, uint32_t *frame_sizes, void *recon, av1mi_report *report) {
-  out->data = nullptr; out->size = 0;
-  Resolved r;
-  int rc = resolve(params, &r);
-  if (rc) { set_err(c, "invalid parameters"); return rc; }
-  HIPCHK(c, hipSetDevice(c->device));
-  rc = ensure_workspace(c, r, n_frames);
-  if (rc) return rc;
-  Av1miDevParams &P = c->P;
-  const int bps = P.bit_depth > 8 ? 2 : 1;
-  const bool padded = r.cw != (int)r.p.width || r.ch != (int)r.p.height;
-  const size_t chunk_bytes = (size_t)n_frames * P.frame_samples * bps;                       // coded layout
-  const size_t user_bytes = (size_t)n_frames * r.p.width * r.p.height * 3 / 2 * bps;         // the caller's tight layout
-  hipStream_t s = c->stream;
-  // headers + CDFs
+// ---- one chunk: prepare_chunk, the schedule of its kind with entropy coding inside, packing, download_chunk
+// Header blob, CDFs, parameters and clears, then the source frames - uploaded, and edge-extended where the coded size is not the
+// signalled one - and their partition.  *d_src: the chunk's source frames on the device, at the coded size.
+static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, uint32_t n_frames, int frames_on_device, const void **d_src) {
+  Av1miDevParams &P = c->P; Workspace &w = c->ws; hipStream_t s = c->stream;
   // header blob: sequence header OBU, then one fixed-size slot per frame with that frame's header (key and inter
   // frames have different lengths; frames of one kind differ only in grain_seed)
   size_t str_key = 0, str_inter = 0;   // CDEF strength search: where cdef_select_kernel writes each frame's set
   std::vector<uint8_t> seq = make_sequence_header(r), fh = make_frame_header(r, nullptr, 0, false, &str_key), fhi = make_frame_header(r, nullptr, 0, true, &str_inter);
   P.cdef_str_bit[0] = (int)str_key; P.cdef_str_bit[1] = (int)str_inter;
-  P.seq_hdr_bytes = (int)seq.size();
-  P.frame_hdr_bytes = (int)fh.size();
-  P.inter_hdr_bytes = (int)fhi.size();
+  P.seq_hdr_bytes = (int)seq.size(); P.frame_hdr_bytes = (int)fh.size(); P.inter_hdr_bytes = (int)fhi.size();
   if (seq.size() > 256 || fh.size() > (size_t)P.hdr_slot_bytes || fhi.size() > (size_t)P.hdr_slot_bytes) { set_err(c, "internal: header larger than its slot"); return AV1MI_E_OVERFLOW; }
   std::vector<uint8_t> blob(seq.size() + (size_t)n_frames * P.hdr_slot_bytes, 0);
   memcpy(blob.data(), seq.data(), seq.size());
@@ -969,190 +947,185 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
     memcpy(blob.data() + seq.size() + (size_t)f * P.hdr_slot_bytes, h.data(), h.size());
   }
   std::vector<uint16_t> cdf = make_cdf_blob(r.qidx);
-  HIPCHK(c, hipMemcpyAsync(c->d_hdr, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->d_cdf, cdf.data(), cdf.size() * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(c->d_params, &P, sizeof(P), hipMemcpyHostToDevice, s));  // the recon kernel reads its parameters from device memory
-  HIPCHK(c, hipMemsetAsync(c->d_overflow, 0, 4, s));
-  HIPCHK(c, hipMemsetAsync(c->d_sse, 0, (size_t)n_frames * 24, s));
-  if (P.cdef_search) HIPCHK(c, hipMemsetAsync(c->d_cdef_err, 0, (size_t)n_frames * P.sb_rows * P.sb_cols * 24 * sizeof(unsigned long long), s));
-  HIPCHK(c, hipEventRecord(c->ev[0], s));
-  const void *d_src = frames;
-  if (!padded) {
-    if (!frames_on_device) {
-      HIPCHK(c, hipMemcpyAsync(c->d_src, frames, chunk_bytes, hipMemcpyHostToDevice, s));
-      d_src = c->d_src;
-    }
-  } else {
-    // not a multiple of 8: edge-extend every frame to the coded size (the signalled size stays exact)
-    const void *tight = frames;
-    if (!frames_on_device) {
-      HIPCHK(c, hipMemcpyAsync(c->d_stage, frames, user_bytes, hipMemcpyHostToDevice, s));
-      tight = c->d_stage;
-    }
-    HIPCHK(c, av1mi_launch_pad(tight, c->d_src, (int)r.p.width, (int)r.p.height, r.cw, r.ch, P.bit_depth, (int)n_frames, 0, s));
-    d_src = c->d_src;
-  }
+  HIPCHK(c, hipMemcpyAsync(w.d_hdr, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(w.d_cdf, cdf.data(), cdf.size() * 2, hipMemcpyHostToDevice, s));
+  HIPCHK(c, hipMemcpyAsync(w.d_params, &P, sizeof(P), hipMemcpyHostToDevice, s));  // the recon kernel reads its parameters from device memory
+  HIPCHK(c, hipMemsetAsync(w.d_overflow, 0, 4, s));
+  HIPCHK(c, hipMemsetAsync(w.d_sse, 0, (size_t)n_frames * 24, s));
+  if (P.cdef_search) HIPCHK(c, hipMemsetAsync(w.d_cdef_err, 0, (size_t)n_frames * P.sb_rows * P.sb_cols * 24 * sizeof(unsigned long long), s));
+  HIPCHK(c, hipEventRecord(c->ev[EV_START], s));
+  // the caller's frames are used in place if they are on the device at the coded size; a padded chunk arrives in the stage
+  const size_t bytes = (size_t)n_frames * (r.padded ? (size_t)r.p.width * r.p.height * 3 / 2 : (size_t)P.frame_samples) * (P.bit_depth > 8 ? 2 : 1);
+  if (!frames_on_device) HIPCHK(c, hipMemcpyAsync(r.padded ? w.d_stage : w.d_src, frames, bytes, hipMemcpyHostToDevice, s));
+  // not a multiple of 8: edge-extend every frame to the coded size (the signalled size stays exact)
+  if (r.padded) HIPCHK(c, av1mi_launch_pad(frames_on_device ? frames : w.d_stage, w.d_src, (int)r.p.width, (int)r.p.height, r.cw, r.ch, P.bit_depth, (int)n_frames, 0, s));
+  *d_src = frames_on_device && !r.padded ? frames : w.d_src;
   // content-driven partition: the split masks of every superblock of the chunk, from the source, before anything walks blocks (the second
-  // stream's motion search waits for ev[1] as well)
-  if (P.part_map) HIPCHK(c, av1mi_launch_partition(&P, d_src, c->d_part, s));
-  HIPCHK(c, hipEventRecord(c->ev[1], s));
-  const bool inter_chunk = P.keyint > 1 && n_frames > 1;
-  // 64x64 leaf blocks run the kernels of recon64_kernel.hip (64-point transforms, larger LDS tiles)
-  auto launch_recon = P.max_bs_log2 >= 6 ? (P.bit_depth == 8 ? av1mi_launch_recon64_u8 : av1mi_launch_recon64_u16)
-                                         : (P.bit_depth == 8 ? av1mi_launch_recon_u8 : av1mi_launch_recon_u16);
+  // stream's motion search waits for EV_SRC_READY as well)
+  if (P.part_map) HIPCHK(c, av1mi_launch_partition(&P, *d_src, w.d_part, s));
+  HIPCHK(c, hipEventRecord(c->ev[EV_SRC_READY], s));
+  return AV1MI_OK;
+}
+
+// 64x64 leaf blocks run the kernels of recon64_kernel.hip (64-point transforms, larger LDS tiles)
+static decltype(&av1mi_launch_recon_u8) recon_launcher(const Av1miDevParams &P) {
+  return P.max_bs_log2 >= 6 ? (P.bit_depth == 8 ? av1mi_launch_recon64_u8 : av1mi_launch_recon64_u16)
+                            : (P.bit_depth == 8 ? av1mi_launch_recon_u8 : av1mi_launch_recon_u16);
+}
+
+// Entropy coding of frames [from, n_frames) on the main stream (the frame-edge tiles' symbolize variant on the fourth), then the join
+// with the groups of frames before `from` coded on the third (schedule_inter): packing needs the tile sizes and bytes of every frame.
+static int entropy_code(av1mi_ctx *c, uint32_t from, uint32_t n_frames) {
+  Workspace &w = c->ws; hipStream_t s = c->stream;
+  HIPCHK(c, hipEventRecord(c->ev[EV_RECON_DONE], s));
+  HIPCHK(c, av1mi_launch_entropy(&c->P, w.d_cdf, w.d_levels, w.d_blk, w.d_streams, w.d_sym, w.d_combos, w.d_slots, w.d_tile_bytes, w.d_lrc,
+                                 w.d_tile_off /* scratch until the packing kernels fill it */, (int)from, (int)(n_frames - from),
+                                 s, c->ev[EV_SYM_DONE], c->stream4, c->ev[EV_EDGE_FORK], c->ev[EV_EDGE_JOIN]));
+  if (from) HIPCHK(c, hipStreamWaitEvent(s, c->ev[EV_GROUPS_JOINED], 0));
+  HIPCHK(c, hipEventRecord(c->ev[EV_ENTROPY_DONE], s));
+  return AV1MI_OK;
+}
+
+// The second stream beside the range coder, once symbolize is done: the squared error of the final frames
+static int sse_beside_range_coder(av1mi_ctx *c, const void *src) {
+  HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev[EV_SYM_DONE], 0));
+  HIPCHK(c, hipEventRecord(c->ev[EV_CDEF_START], c->stream2));
+  HIPCHK(c, av1mi_launch_sse(&c->P, src, c->ws.d_fin, c->ws.d_sse, c->stream2));
+  HIPCHK(c, hipEventRecord(c->ev[EV_CDEF_DONE], c->stream2));
+  return AV1MI_OK;
+}
+
+// All-key-frame chunk: one reconstruction launch over the chunk.  The frames are independent, so the chunk could run as a software
+// pipeline over groups of frames - the main stream reconstructing group g + 1 while auxiliary streams symbolize and range-code group
+// g.  Measured (1080p x 60, MI355X): 14.1 k frames/s as one group, 12.3 k as two, 10.7 k as three - the range coder holds 145 KB of
+// LDS on every CU it sits on, which leaves the reconstruction (10 KB per wave) one wave there instead of sixteen.
+// CDEF (+SSE) depends only on the reconstruction.  The range-coding kernel is a latency-bound serial chain (one lane per tile: 480
+// waves, half the SIMDs idle), so CDEF runs beside IT on the second stream; symbolize and CDEF are both throughput-bound and would
+// only slow each other.
+static int schedule_all_key(av1mi_ctx *c, const void *src, uint32_t n_frames) {
+  const Av1miDevParams &P = c->P; Workspace &w = c->ws; hipStream_t s = c->stream, s2 = c->stream2;
+  // Deblocking reads only the reconstruction and block info: beside symbolize on the second stream.  The strength search reads the
+  // deblocked frames and symbolize codes its cdef_idx: with the search on, deblocking and search run before entropy coding.
+  const hipStream_t deblock_s = P.cdef_search ? s : s2;
+  // CDEF's one launch over the chunk sums the squared error itself - a second pass over the frames, 0.19 ms at 1080p x 60, would end
+  // after the range coder CDEF runs beside; a one-frame chunk's CDEF runs in strips without the sum
+  const bool sse_in_cdef = n_frames > 1;
+  HIPCHK(c, recon_launcher(P)(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, nullptr, nullptr, P.part_map, s));
+  if (P.lf_level[0] && deblock_s == s) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, s));
+  if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, (int)n_frames, s));
+  if (const int rc = entropy_code(c, 0, n_frames)) return rc;
+  HIPCHK(c, hipStreamWaitEvent(s2, c->ev[EV_RECON_DONE], 0));
+  if (P.lf_level[0] && deblock_s == s2) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, s2));
+  // measured: starting CDEF right after the reconstruction, beside symbolize, costs 8 % overall
+  HIPCHK(c, hipStreamWaitEvent(s2, c->ev[EV_SYM_DONE], 0));
+  HIPCHK(c, hipEventRecord(c->ev[EV_CDEF_START], s2));
+  HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, w.d_fin, w.d_blk, sse_in_cdef ? src : nullptr, sse_in_cdef ? w.d_sse : nullptr, s2));
+  if (!sse_in_cdef) HIPCHK(c, av1mi_launch_sse(&P, src, w.d_fin, w.d_sse, s2));
+  HIPCHK(c, hipEventRecord(c->ev[EV_CDEF_DONE], s2));
+  return AV1MI_OK;
+}
+
+// All-key-frame chunk with loop restoration: the unit decisions are part of the tile syntax, so deblocking, CDEF (into d_cd) and
+// restoration (into d_fin) precede entropy coding on the main stream.
+static int schedule_all_key_lr(av1mi_ctx *c, const void *src, uint32_t n_frames) {
+  const Av1miDevParams &P = c->P; Workspace &w = c->ws; hipStream_t s = c->stream;
+  HIPCHK(c, recon_launcher(P)(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, nullptr, nullptr, P.part_map, s));
+  if (P.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, s));
+  if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, (int)n_frames, s));
+  HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, w.d_cd, w.d_blk, nullptr, nullptr, s));
+  HIPCHK(c, av1mi_launch_lr(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, 1, s));
+  const int rc = entropy_code(c, 0, n_frames);
+  return rc ? rc : sse_beside_range_coder(c, src);
+}
+
+// Inter chunk: a P frame needs the previous frame's final (post-CDEF) reconstruction, so reconstruction, deblocking, CDEF and
+// restoration run frame by frame on the main stream; the motion search runs beside that chain on the second stream, entropy coding of
+// finished groups of frames on the third (every frame starts from the default CDFs, so tiles of different frames stay independent).
+static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
+  const Av1miDevParams &P = c->P; Workspace &w = c->ws; hipStream_t s = c->stream, s2 = c->stream2;
+  Av1miDevParams P1 = P; P1.n_frames = 1;
+  const size_t fbytes = (size_t)P.frame_samples * (P.bit_depth > 8 ? 2 : 1), nb8 = (size_t)P.b8_rows * P.b8_cols, nsb = (size_t)P.sb_rows * P.sb_cols;
   const bool lr = P.enable_lr != 0;
-  uint32_t entropy_from = 0;      // inter chunks: frames before this one are entropy-coded on the third stream, beside the chain
-  void *cdef_out = lr ? c->d_cd : c->d_fin;   // with loop restoration CDEF writes d_cd and the restored frame goes to d_fin
-  if (!inter_chunk && lr) {
-    // the unit decisions are part of the tile syntax: CDEF and restoration must precede entropy coding
-    HIPCHK(c, launch_recon(&P, c->d_params, d_src, c->d_rec, c->d_levels, c->d_blk, nullptr, nullptr, P.part_map, s));
-    if (P.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P, c->d_rec, c->d_blk, s));
-    if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, c->d_rec, d_src, c->d_blk, c->d_hdr, 0, (int)n_frames, s));
-    HIPCHK(c, av1mi_launch_cdef(&P, c->d_rec, c->d_cd, c->d_blk, nullptr, nullptr, s));
-    HIPCHK(c, av1mi_launch_lr(&P, c->d_rec, c->d_cd, d_src, c->d_fin, c->d_lrc, c->d_lrsse, 1, s));
-  } else if (!inter_chunk) {
-    // All-key-frame chunk: one reconstruction launch over the chunk.  The frames are independent, so the chunk could run as a software
-    // pipeline over groups of frames - the main stream reconstructing group g + 1 while auxiliary streams symbolize and range-code group
-    // g.  Measured (1080p x 60, MI355X): 14.1 k frames/s as one group, 12.3 k as two, 10.7 k as three - the range coder holds 145 KB of
-    // LDS on every CU it sits on, which leaves the reconstruction (10 KB per wave) one wave there instead of sixteen.
-    HIPCHK(c, launch_recon(&P, c->d_params, d_src, c->d_rec, c->d_levels, c->d_blk, nullptr, nullptr, P.part_map, s));
-    if (P.cdef_search) {
-      // the strength search reads the deblocked frames and symbolize codes its cdef_idx: deblocking, search and selection before entropy
-      // coding (CDEF itself still runs beside the range coder)
-      if (P.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P, c->d_rec, c->d_blk, s));
-      HIPCHK(c, av1mi_launch_cdef_search(&P, c->d_rec, d_src, c->d_blk, c->d_hdr, 0, (int)n_frames, s));
+  uint8_t *cdef_out = (uint8_t *)(lr ? w.d_cd : w.d_fin);   // with loop restoration CDEF writes d_cd and the restored frame goes to d_fin
+  const size_t upf = (size_t)std::max(1, (P.true_h + 32) / 64) * std::max(1, (P.true_w + 32) / 64);   // restoration units per frame
+  // Motion search is open loop (source against previous source): all inter frames at once, on the second stream,
+  // beside the chain below; the first inter frame's reconstruction waits for it.
+  HIPCHK(c, hipStreamWaitEvent(s2, c->ev[EV_SRC_READY], 0));  // the source frames are in HBM
+  HIPCHK(c, hipMemsetAsync(w.d_me, 0xFF, (size_t)n_frames * nb8 * 8, s2));
+  uint32_t *acc64 = P.max_bs_log2 >= 6 ? w.d_me64 : nullptr;
+  if (acc64) HIPCHK(c, hipMemsetAsync(acc64, 0, (size_t)n_frames * nsb * (2 * P.me_range + 1) * (2 * P.me_range + 1) * sizeof(uint32_t), s2));
+  // one launch + one event per frame, enqueued from inside the frame loop below, behind the first frame's chain kernels: the chain's first
+  // kernel (the key frame's reconstruction needs no vectors) no longer waits on the host for 120 - 180 API calls (under
+  // the profiler the chain started 6.4 ms after the chunk's first kernel; unprofiled the calls take ~ 8 us each and one chunk gains nothing).
+  // All of it behind the first frame rather than a few frames ahead of the chain - measured (1080p IPPP x 60, one chunk / four in flight,
+  // frames/s): all 5 420 / 7 560; 8 ahead 5 390 / 7 220; 4 ahead 5 410 / 6 970; 2 ahead 5 370 / 6 900 - with several chunks in flight a
+  // search that is enqueued late competes with the other chunks' chains instead of filling their gaps.
+  while (c->me_ev.size() < n_frames) { hipEvent_t e; HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->me_ev.push_back(e); }
+  // hierarchical search: the chunk's luma at a quarter of the resolution (one launch), then per frame the superblocks' search centres
+  const uint32_t *centre = P.me_presearch ? w.d_centre : nullptr;
+  if (centre) HIPCHK(c, av1mi_launch_quarter_luma(&P, src, w.d_quarter, s2));
+  // Entropy coding beside the chain: every frame starts from the default CDFs, so a group of frames can be symbolized and
+  // range-coded (third stream) as soon as its last frame is reconstructed (and, with restoration on, its unit choices are
+  // known) while the chain reconstructs the following frames; only the last group's entropy coding is left after the chain.
+  // (AV1MI_ENTROPY_GROUP=k: groups of k frames - tests force small groups on short chunks; 0 = no overlap)
+  // Group size: since the chain's kernels got short (walk 76, inter pass 38 us per 1080p frame) a range-coder launch beside them costs
+  // more than it hides - 60-frame chunks, groups of 10 / 20 / none: 5 320 / 5 450 / 5 530 frames/s for one chunk, 7 670 / 8 050 / 7 970
+  // with four in flight, 2 440 / 2 460 / 2 540 at the production point - so chunks of up to 64 frames code everything after the
+  // chain and longer ones in groups of 32.
+  uint32_t grp = n_frames <= 64 ? n_frames : 32;
+  if (const char *eg = getenv("AV1MI_ENTROPY_GROUP")) { const int k = atoi(eg); grp = k > 0 ? (uint32_t)k : n_frames; }
+  uint32_t n_grp = 0;
+  // the restoration units' candidate sums of the whole chunk, cleared once (not a fill per frame on the chain)
+  if (lr) HIPCHK(c, hipMemsetAsync(w.d_lrsse, 0, (size_t)n_frames * upf * 8 * sizeof(unsigned long long), s));
+  for (uint32_t f = 0; f < n_frames; f++) {
+    const bool inter = av1mi_frame_is_inter(P, (int)f);
+    const uint8_t *srcf = (const uint8_t *)src + f * fbytes;
+    uint8_t *recf = (uint8_t *)w.d_rec + f * fbytes, *finf = (uint8_t *)w.d_fin + f * fbytes, *cdf_ = cdef_out + f * fbytes;
+    Av1miBlkInfo *blkf = w.d_blk + f * nb8;
+    int16_t *lvf = w.d_levels + f * nsb * AV1MI_SB_LEVELS;
+    const uint8_t *reff = inter ? (const uint8_t *)w.d_fin + (f - 1) * fbytes : nullptr;
+    const unsigned long long *mef = inter ? (P.subpel ? w.d_me_sub : w.d_me) + f * nb8 : nullptr;
+    if (inter) HIPCHK(c, hipStreamWaitEvent(s, c->me_ev[f], 0));
+    HIPCHK(c, recon_launcher(P)(&P1, w.d_params, srcf, recf, lvf, blkf, reff, mef, P.part_map ? P.part_map + f * nsb : nullptr, s));
+    for (int i = 0; i < 4; i++) P1.lf_level[i] = inter ? P.lf_level_inter[i] : P.lf_level[i];
+    if (P1.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P1, recf, blkf, s));
+    if (P.cdef_search) {   // the frame's strength set before its CDEF (the next frame's reference is the output of the chosen strengths)
+      HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, (int)f, 1, s));
+      P1.cdef_idx = P.cdef_idx + f * nsb; P1.cdef_sel = P.cdef_sel + f * 8;
     }
-  } else {
-    // Inter chunk: a P frame needs the previous frame's final (post-CDEF) reconstruction, so motion search,
-    // reconstruction and CDEF run frame by frame; entropy coding of ALL frames follows in one pass (every frame
-    // starts from the default CDFs, so tiles of different frames stay independent).
-    Av1miDevParams P1 = P;
-    P1.n_frames = 1;
-    const size_t fbytes = (size_t)P.frame_samples * bps, nb8 = (size_t)P.b8_rows * P.b8_cols, nsb = (size_t)P.sb_rows * P.sb_cols;
-    // Motion search is open loop (source against previous source): all inter frames at once, on the second stream,
-    // beside the chain below; the first inter frame's reconstruction waits for it.
-    HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev[1], 0));  // the source frames are in HBM
-    HIPCHK(c, hipMemsetAsync(c->d_me, 0xFF, (size_t)n_frames * nb8 * 8, c->stream2));
-    uint32_t *acc64 = P.max_bs_log2 >= 6 ? c->d_me64 : nullptr;
-    if (acc64) HIPCHK(c, hipMemsetAsync(acc64, 0, (size_t)n_frames * nsb * (2 * P.me_range + 1) * (2 * P.me_range + 1) * sizeof(uint32_t), c->stream2));
-    // one launch + one event per frame, enqueued from inside the frame loop below, behind the first frame's chain kernels: the chain's first
-    // kernel (the key frame's reconstruction needs no vectors) no longer waits on the host for 120 - 180 API calls (under
-    // the profiler the chain started 6.4 ms after the chunk's first kernel; unprofiled the calls take ~ 8 us each and one chunk gains nothing).
-    // All of it behind the first frame rather than a few frames ahead of the chain - measured (1080p IPPP x 60, one chunk / four in flight,
-    // frames/s): all 5 420 / 7 560; 8 ahead 5 390 / 7 220; 4 ahead 5 410 / 6 970; 2 ahead 5 370 / 6 900 - with several chunks in flight a
-    // search that is enqueued late competes with the other chunks' chains instead of filling their gaps.
-    while (c->me_ev.size() < n_frames) {
-      hipEvent_t e;
-      HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      c->me_ev.push_back(e);
-    }
-    // hierarchical search: the chunk's luma at a quarter of the resolution (one launch), then per frame the superblocks' search centres
-    const uint32_t *centre = nullptr;
-    if (P.me_presearch) {
-      HIPCHK(c, av1mi_launch_quarter_luma(&P, d_src, c->d_quarter, c->stream2));
-      centre = c->d_centre;
-    }
-    // Entropy coding beside the chain: every frame starts from the default CDFs, so a group of frames can be symbolized and
-    // range-coded (third stream) as soon as its last frame is reconstructed (and, with restoration on, its unit choices are
-    // known) while the chain reconstructs the following frames; only the last group's entropy coding is left after the chain.
-    // (AV1MI_ENTROPY_GROUP=k: groups of k frames - tests force small groups on short chunks; 0 = no overlap)
-    // Group size: since the chain's kernels got short (walk 76, inter pass 38 us per 1080p frame) a range-coder launch beside them costs
-    // more than it hides - 60-frame chunks, groups of 10 / 20 / none: 5 320 / 5 450 / 5 530 frames/s for one chunk, 7 670 / 8 050 / 7 970
-    // with four in flight, 2 440 / 2 460 / 2 540 at the production point - so chunks of up to 64 frames code everything after the
-    // chain and longer ones in groups of 32.
-    uint32_t grp = n_frames <= 64 ? n_frames : 32;
-    if (const char *eg = getenv("AV1MI_ENTROPY_GROUP")) { const int k = atoi(eg); grp = k > 0 ? (uint32_t)k : n_frames; }
-    uint32_t n_grp = 0;
-    if (lr) {   // the restoration units' candidate sums of the whole chunk, cleared once (not a fill per frame on the chain)
-      const size_t upf = (size_t)((P.true_h + 32) / 64 > 0 ? (P.true_h + 32) / 64 : 1) * ((P.true_w + 32) / 64 > 0 ? (P.true_w + 32) / 64 : 1);
-      HIPCHK(c, hipMemsetAsync(c->d_lrsse, 0, (size_t)n_frames * upf * 8 * sizeof(unsigned long long), s));
-    }
-    for (uint32_t f = 0; f < n_frames; f++) {
-      const uint8_t *srcf = (const uint8_t *)d_src + f * fbytes;
-      uint8_t *recf = (uint8_t *)c->d_rec + f * fbytes, *finf = (uint8_t *)c->d_fin + f * fbytes, *cdf_ = (uint8_t *)cdef_out + f * fbytes;
-      Av1miBlkInfo *blkf = c->d_blk + f * nb8;
-      int16_t *lvf = c->d_levels + f * nsb * AV1MI_SB_LEVELS;
-      if (!av1mi_frame_is_inter(P, (int)f)) {
-        HIPCHK(c, launch_recon(&P1, c->d_params, srcf, recf, lvf, blkf, nullptr, nullptr, P.part_map ? P.part_map + f * nsb : nullptr, s));
-      } else {
-        const uint8_t *reff = (const uint8_t *)c->d_fin + (f - 1) * fbytes;
-        unsigned long long *mef = (P.subpel ? c->d_me_sub : c->d_me) + f * nb8;
-        HIPCHK(c, hipStreamWaitEvent(s, c->me_ev[f], 0));
-        HIPCHK(c, launch_recon(&P1, c->d_params, srcf, recf, lvf, blkf, reff, mef, P.part_map ? P.part_map + f * nsb : nullptr, s));
+    HIPCHK(c, av1mi_launch_cdef(&P1, recf, cdf_, blkf, nullptr, nullptr, s));
+    if (lr) HIPCHK(c, av1mi_launch_lr(&P1, recf, cdf_, srcf, finf, w.d_lrc + f * upf, w.d_lrsse + f * upf * 8, 0, s));
+    if (f == 0)   // (frame 0 of a chunk is a key frame: its chain kernels are in the queue)
+      for (uint32_t g = 1; g < n_frames; g++) {
+        if (!av1mi_frame_is_inter(P, (int)g)) continue;
+        if (centre) HIPCHK(c, av1mi_launch_presearch(&P, w.d_quarter, w.d_centre, (int)g, 1, s2));
+        HIPCHK(c, av1mi_launch_motion_search(&P, src, w.d_me, P.me_range, (int)g, 1, acc64, centre, s2));
+        if (P.subpel) HIPCHK(c, av1mi_launch_subpel_refine(&P, src, w.d_me, w.d_me_sub, P.me_range, (int)g, 1, s2));
+        HIPCHK(c, hipEventRecord(c->me_ev[g], s2));
       }
-      if (!av1mi_frame_is_inter(P, (int)f)) { for (int i = 0; i < 4; i++) P1.lf_level[i] = P.lf_level[i]; }
-      else { for (int i = 0; i < 4; i++) P1.lf_level[i] = P.lf_level_inter[i]; }
-      if (P1.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P1, recf, blkf, s));
-      if (P.cdef_search) {   // the frame's strength set before its CDEF (the next frame's reference is the output of the chosen strengths)
-        HIPCHK(c, av1mi_launch_cdef_search(&P, c->d_rec, d_src, c->d_blk, c->d_hdr, (int)f, 1, s));
-        P1.cdef_idx = P.cdef_idx + f * nsb;
-        P1.cdef_sel = P.cdef_sel + f * 8;
-      }
-      HIPCHK(c, av1mi_launch_cdef(&P1, recf, cdf_, blkf, nullptr, nullptr, s));
-      if (lr) {
-        const int upf = ((P.true_h + 32) / 64 > 0 ? (P.true_h + 32) / 64 : 1) * ((P.true_w + 32) / 64 > 0 ? (P.true_w + 32) / 64 : 1);
-        HIPCHK(c, av1mi_launch_lr(&P1, recf, cdf_, srcf, finf, c->d_lrc + (size_t)f * upf, c->d_lrsse + (size_t)f * upf * 8, 0, s));
-      }
-      if (f == 0)   // (frame 0 of a chunk is a key frame: its chain kernels are in the queue)
-        for (uint32_t g = 1; g < n_frames; g++) {
-          if (!av1mi_frame_is_inter(P, (int)g)) continue;
-          if (centre) HIPCHK(c, av1mi_launch_presearch(&P, c->d_quarter, c->d_centre, (int)g, 1, c->stream2));
-          HIPCHK(c, av1mi_launch_motion_search(&P, d_src, c->d_me, P.me_range, (int)g, 1, acc64, centre, c->stream2));
-          if (P.subpel) HIPCHK(c, av1mi_launch_subpel_refine(&P, d_src, c->d_me, c->d_me_sub, P.me_range, (int)g, 1, c->stream2));
-          HIPCHK(c, hipEventRecord(c->me_ev[g], c->stream2));
-        }
-      if ((f + 1) % grp == 0 && f + 1 < n_frames) {   // a full group that is not the last: hand it to the third stream
-        if (c->grp_ev.size() <= n_grp) {
-          hipEvent_t e;
-          HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-          c->grp_ev.push_back(e);
-        }
-        HIPCHK(c, hipEventRecord(c->grp_ev[n_grp], s));
-        HIPCHK(c, hipStreamWaitEvent(c->stream3, c->grp_ev[n_grp], 0));
-        HIPCHK(c, av1mi_launch_entropy(&P, c->d_cdf, c->d_levels, c->d_blk, c->d_streams, c->d_sym, c->d_combos, c->d_slots, c->d_tile_bytes, c->d_lrc,
-                                       c->d_tile_off, (int)(f + 1 - grp), (int)grp, c->stream3, nullptr, nullptr, nullptr, nullptr));
-        n_grp++;
-      }
+    if ((f + 1) % grp == 0 && f + 1 < n_frames) {   // a full group that is not the last: hand it to the third stream
+      if (c->grp_ev.size() <= n_grp) { hipEvent_t e; HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->grp_ev.push_back(e); }
+      HIPCHK(c, hipEventRecord(c->grp_ev[n_grp], s));
+      HIPCHK(c, hipStreamWaitEvent(c->stream3, c->grp_ev[n_grp], 0));
+      HIPCHK(c, av1mi_launch_entropy(&P, w.d_cdf, w.d_levels, w.d_blk, w.d_streams, w.d_sym, w.d_combos, w.d_slots, w.d_tile_bytes, w.d_lrc,
+                                     w.d_tile_off, (int)(f + 1 - grp), (int)grp, c->stream3, nullptr, nullptr, nullptr, nullptr));
+      n_grp++;
     }
-    entropy_from = n_grp * grp;
-    if (n_grp) HIPCHK(c, hipEventRecord(c->ev[10], c->stream3));
   }
-  HIPCHK(c, hipEventRecord(c->ev[2], s));
-  // CDEF (+SSE) depends only on the reconstruction.  The range-coding kernel is a latency-bound
-  // serial chain (one lane per tile: 480 waves, half the SIMDs idle), so CDEF runs beside IT on a
-  // second stream; symbolize and CDEF are both throughput-bound and would only slow each other.
-  hipStream_t s2 = c->stream2;
-  HIPCHK(c, hipEventRecord(c->ev[3], s));
-  HIPCHK(c, av1mi_launch_entropy(&P, c->d_cdf, c->d_levels, c->d_blk, c->d_streams, c->d_sym, c->d_combos, c->d_slots, c->d_tile_bytes, c->d_lrc,
-                                 c->d_tile_off /* scratch until the packing kernels fill it */, (int)entropy_from, (int)(n_frames - entropy_from),
-                                 s, c->ev[7], c->stream4, c->ev[11], c->ev[12]));   // the frame-edge tiles' symbolize variant beside the regular one
-  if (entropy_from) HIPCHK(c, hipStreamWaitEvent(s, c->ev[10], 0));   // join: packing needs the tile sizes and bytes of every group
-  HIPCHK(c, hipEventRecord(c->ev[4], s));
-  if (!inter_chunk && !lr) {  // deblocking reads only the reconstruction and block info: beside symbolize
-    HIPCHK(c, hipStreamWaitEvent(s2, c->ev[2], 0));
-    if (P.lf_level[0] && !P.cdef_search) HIPCHK(c, av1mi_launch_deblock(&P, c->d_rec, c->d_blk, s2));
-  }
-  HIPCHK(c, hipStreamWaitEvent(s2, c->ev[7], 0));  // ev[7]: recorded between symbolize and range-code (measured: starting CDEF
-                                                   // right after the reconstruction, beside symbolize, costs 8 % overall)
-  HIPCHK(c, hipEventRecord(c->ev[8], s2));
-  // (an all-key chunk's CDEF is one launch over the chunk: it sums the squared error itself - a second pass over the frames, 0.19 ms at
-  // 1080p x 60, would end after the range coder CDEF runs beside; a one-frame chunk's CDEF runs in strips without the sum)
-  const bool sse_in_cdef = !inter_chunk && !lr && n_frames > 1;
-  if (!inter_chunk && !lr) HIPCHK(c, av1mi_launch_cdef(&P, c->d_rec, c->d_fin, c->d_blk, sse_in_cdef ? d_src : nullptr, sse_in_cdef ? c->d_sse : nullptr, s2));
-  if (!sse_in_cdef) HIPCHK(c, av1mi_launch_sse(&P, d_src, c->d_fin, c->d_sse, s2));
-  HIPCHK(c, hipEventRecord(c->ev[9], s2));
-  // packing and the download of the bitstream need nothing from the second stream: they run beside the tail of CDEF / SSE;
-  // the join comes before the reconstruction and the SSE are read (below)
-  HIPCHK(c, av1mi_launch_pack(&P, c->d_slots, c->d_tile_bytes, c->d_tile_off, c->d_frame_size, c->d_payload, c->d_frame_off, c->d_hdr,
-                              c->d_out, c->d_overflow, 0, s));
-  HIPCHK(c, av1mi_launch_pack(&P, c->d_slots, c->d_tile_bytes, c->d_tile_off, c->d_frame_size, c->d_payload, c->d_frame_off, c->d_hdr,
-                              c->d_out, c->d_overflow, 1, s));
-  HIPCHK(c, hipEventRecord(c->ev[5], s));
+  if (n_grp) HIPCHK(c, hipEventRecord(c->ev[EV_GROUPS_JOINED], c->stream3));
+  const int rc = entropy_code(c, n_grp * grp, n_frames);
+  return rc ? rc : sse_beside_range_coder(c, src);
+}
+
+// The packed bitstream into a buffer for the caller, the final frames into `recon` if asked for, and the report.
+static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, int frames_on_device, av1mi_buf *out, uint32_t *frame_sizes,
+                          void *recon, av1mi_report *report) {
+  const Av1miDevParams &P = c->P; Workspace &w = c->ws; hipStream_t s = c->stream, s2 = c->stream2;
   // sizes first, then exactly the bytes produced
   std::vector<unsigned long long> foff(n_frames + 1);
   int overflow = 0;
-  HIPCHK(c, hipMemcpyAsync(foff.data(), c->d_frame_off, (n_frames + 1) * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(&overflow, c->d_overflow, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(foff.data(), w.d_frame_off, (n_frames + 1) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(c, hipMemcpyAsync(&overflow, w.d_overflow, 4, hipMemcpyDeviceToHost, s));
   HIPCHK(c, hipStreamSynchronize(s));
   if (overflow) {
     (void)hipStreamSynchronize(s2);  // the retry reuses the buffers the second stream is still reading
@@ -1160,7 +1133,7 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
     return AV1MI_E_OVERFLOW;
   }
   const size_t total = (size_t)foff[n_frames];
-  if (total > c->out_cap) { (void)hipStreamSynchronize(s2); set_err(c, "internal: packed size exceeds buffer"); return AV1MI_E_OVERFLOW; }
+  if (total > w.out_cap) { (void)hipStreamSynchronize(s2); set_err(c, "internal: packed size exceeds buffer"); return AV1MI_E_OVERFLOW; }
   // the caller's buffer: a page-locked block of the pool (the copy lands in it directly); plain memory + this context's staging
   // buffer only if page-locked memory cannot be had
   uint8_t *host = (uint8_t *)pin_acquire(total ? total : 1);
@@ -1168,33 +1141,33 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
   if (!direct) {
     host = (uint8_t *)malloc(total ? total : 1);
     if (!host) { (void)hipStreamSynchronize(s2); return AV1MI_E_OOM; }
-    if (c->h_out_cap < total) {
-      if (c->h_out) (void)hipHostFree(c->h_out);
-      c->h_out = nullptr; c->h_out_cap = 0;
-      if (hipHostMalloc((void **)&c->h_out, total + (total >> 2) + 4096, hipHostMallocDefault) == hipSuccess) c->h_out_cap = total + (total >> 2) + 4096;
+    if (w.h_out_cap < total) {
+      w.h_out_cap = 0;
+      if (ws_alloc(w, w.h_out, total + (total >> 2) + 4096, true) == hipSuccess) w.h_out_cap = total + (total >> 2) + 4096;
     }
   }
-  uint8_t *dst = direct ? host : (c->h_out ? c->h_out : host);
-  hipError_t e1 = hipMemcpyAsync(dst, c->d_out, total, hipMemcpyDeviceToHost, s);
-  hipError_t e2 = hipEventRecord(c->ev[6], s);
-  if (e2 == hipSuccess) e2 = hipStreamWaitEvent(s, c->ev[9], 0);  // join: the final reconstruction and the SSE come from the second stream
+  uint8_t *dst = direct ? host : (w.h_out ? w.h_out : host);
+  hipError_t e1 = hipMemcpyAsync(dst, w.d_out, total, hipMemcpyDeviceToHost, s);
+  hipError_t e2 = hipEventRecord(c->ev[EV_DOWNLOAD_DONE], s);
+  if (e2 == hipSuccess) e2 = hipStreamWaitEvent(s, c->ev[EV_CDEF_DONE], 0);  // join: the final reconstruction and the SSE come from the second stream
   if (e1 == hipSuccess && e2 == hipSuccess && recon) {
-    const void *fin = c->d_fin;
-    if (padded) {  // crop to the signalled size, in the caller's tight layout
-      e1 = av1mi_launch_pad(c->d_fin, c->d_stage, (int)r.p.width, (int)r.p.height, r.cw, r.ch, P.bit_depth, (int)n_frames, 1, s);
-      fin = c->d_stage;
+    const void *fin = w.d_fin;
+    if (r.padded) {  // crop to the signalled size, in the caller's tight layout
+      e1 = av1mi_launch_pad(w.d_fin, w.d_stage, (int)r.p.width, (int)r.p.height, r.cw, r.ch, P.bit_depth, (int)n_frames, 1, s);
+      fin = w.d_stage;
     }
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(recon, fin, padded ? user_bytes : chunk_bytes, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s);
+    const size_t bytes = (size_t)n_frames * (r.padded ? (size_t)r.p.width * r.p.height * 3 / 2 : (size_t)P.frame_samples) * (P.bit_depth > 8 ? 2 : 1);
+    if (e1 == hipSuccess) e1 = hipMemcpyAsync(recon, fin, bytes, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s);
   }
   std::vector<unsigned long long> sse(n_frames * 3);
   std::vector<uint32_t> syms;
-  if (e1 == hipSuccess) e1 = hipMemcpyAsync(sse.data(), c->d_sse, (size_t)n_frames * 24, hipMemcpyDeviceToHost, s);
+  if (e1 == hipSuccess) e1 = hipMemcpyAsync(sse.data(), w.d_sse, (size_t)n_frames * 24, hipMemcpyDeviceToHost, s);
   if (e1 == hipSuccess && report) {
     syms.resize((size_t)n_frames * P.tile_rows * P.tile_cols);
-    e1 = hipMemcpyAsync(syms.data(), c->d_sym, syms.size() * 4, hipMemcpyDeviceToHost, s);
+    e1 = hipMemcpyAsync(syms.data(), w.d_sym, syms.size() * 4, hipMemcpyDeviceToHost, s);
   }
-  // the bitstream is on the host once ev[6] has passed: hand it over to the caller's buffer while the second stream finishes
-  if (e1 == hipSuccess && e2 == hipSuccess) e1 = hipEventSynchronize(c->ev[6]);
+  // the bitstream is on the host once EV_DOWNLOAD_DONE has passed: hand it over to the caller's buffer while the second stream finishes
+  if (e1 == hipSuccess && e2 == hipSuccess) e1 = hipEventSynchronize(c->ev[EV_DOWNLOAD_DONE]);
   if (e1 == hipSuccess && e2 == hipSuccess && dst != host) memcpy(host, dst, total);
   if (e1 == hipSuccess) e1 = hipStreamSynchronize(s);
   if (e1 != hipSuccess || e2 != hipSuccess) {
@@ -1207,11 +1180,8 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
   if (frame_sizes) for (uint32_t f = 0; f < n_frames; f++) frame_sizes[f] = (uint32_t)(foff[f + 1] - foff[f]);
   if (report) {
     memset(report, 0, sizeof(*report));
-    report->frames = n_frames;
-    report->bytes = total;
-    report->cap_scale = (uint32_t)c->cap_scale;
-    report->gpus_used = 1u << (c->device & 31);
-    report->chunks = 1;
+    report->frames = n_frames; report->bytes = total; report->chunks = 1;
+    report->cap_scale = (uint32_t)c->cap_scale; report->gpus_used = 1u << (c->device & 31);
     const double mx = (double)((1 << P.bit_depth) - 1);
     for (int pl = 0; pl < 3; pl++) {
       double t = 0;
@@ -1221,16 +1191,44 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
       report->psnr[pl] = t > 0 ? 10.0 * log10(mx * mx * npx / t) : 99.0;
     }
     for (uint32_t v : syms) { report->n_symbols += v; if (v > report->max_tile_symbols) report->max_tile_symbols = v; }
-    (void)hipEventElapsedTime(&report->ms_h2d, c->ev[0], c->ev[1]);
-    (void)hipEventElapsedTime(&report->ms_recon, c->ev[1], c->ev[2]);
-    (void)hipEventElapsedTime(&report->ms_cdef, c->ev[8], c->ev[9]);
-    (void)hipEventElapsedTime(&report->ms_entropy, c->ev[3], c->ev[4]);
-    (void)hipEventElapsedTime(&report->ms_symbolize, c->ev[3], c->ev[7]);
-    (void)hipEventElapsedTime(&report->ms_pack, c->ev[4], c->ev[5]);
-    (void)hipEventElapsedTime(&report->ms_d2h, c->ev[5], c->ev[6]);
-    (void)hipEventElapsedTime(&report->ms_total, c->ev[0], c->ev[6]);
+    (void)hipEventElapsedTime(&report->ms_h2d, c->ev[EV_START], c->ev[EV_SRC_READY]);
+    (void)hipEventElapsedTime(&report->ms_recon, c->ev[EV_SRC_READY], c->ev[EV_RECON_DONE]);
+    (void)hipEventElapsedTime(&report->ms_cdef, c->ev[EV_CDEF_START], c->ev[EV_CDEF_DONE]);
+    (void)hipEventElapsedTime(&report->ms_entropy, c->ev[EV_RECON_DONE], c->ev[EV_ENTROPY_DONE]);
+    (void)hipEventElapsedTime(&report->ms_symbolize, c->ev[EV_RECON_DONE], c->ev[EV_SYM_DONE]);
+    (void)hipEventElapsedTime(&report->ms_pack, c->ev[EV_ENTROPY_DONE], c->ev[EV_PACK_DONE]);
+    (void)hipEventElapsedTime(&report->ms_d2h, c->ev[EV_PACK_DONE], c->ev[EV_DOWNLOAD_DONE]);
+    (void)hipEventElapsedTime(&report->ms_total, c->ev[EV_START], c->ev[EV_DOWNLOAD_DONE]);
   }
   return AV1MI_OK;
+}
+
+static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
+                             av1mi_buf *out, uint32_t *frame_sizes, void *recon, av1mi_report *report) {
+  out->data = nullptr; out->size = 0;
+  Resolved r;
+  int rc = resolve(params, &r);
+  if (rc) { set_err(c, "invalid parameters"); return rc; }
+  HIPCHK(c, hipSetDevice(c->device));
+  rc = ensure_workspace(c, r, n_frames);
+  if (rc) return rc;
+  Workspace &w = c->ws;
+  c->P = dev_params(r, n_frames, c->cap_scale, w.d_part, w.d_qm, w.d_cdef_err, w.d_cdef_idx, w.d_cdef_sel);
+  const void *d_src = nullptr;
+  rc = prepare_chunk(c, r, frames, n_frames, frames_on_device, &d_src);
+  if (rc) return rc;
+  const Av1miDevParams &P = c->P;
+  if (P.keyint > 1 && n_frames > 1) rc = schedule_inter(c, d_src, n_frames);
+  else if (P.enable_lr) rc = schedule_all_key_lr(c, d_src, n_frames);
+  else rc = schedule_all_key(c, d_src, n_frames);
+  if (rc) return rc;
+  // packing and the download of the bitstream need nothing from the second stream: they run beside the tail of its work; the join
+  // comes before the reconstruction and the SSE are read (download_chunk)
+  for (int stage = 0; stage < 2; stage++)
+    HIPCHK(c, av1mi_launch_pack(&P, w.d_slots, w.d_tile_bytes, w.d_tile_off, w.d_frame_size, w.d_payload, w.d_frame_off, w.d_hdr,
+                                w.d_out, w.d_overflow, stage, c->stream));
+  HIPCHK(c, hipEventRecord(c->ev[EV_PACK_DONE], c->stream));
+  return download_chunk(c, r, n_frames, frames_on_device, out, frame_sizes, recon, report);
 }
 
 }  // extern "C"
