@@ -952,20 +952,237 @@ __global__ void __launch_bounds__(1024) tile_order_kernel(int n_tiles, const uin
 }
 
 // ================================================================================= K4
-// One lane per tile, 64 tiles per workgroup, FOUR waves per workgroup - one per SIMD of the CU - working as a pipeline over batches of
-// RC_BATCH entries (batch k is at stage j in trip k + j; double-buffered LDS rings between the stages, one barrier per trip):
-//   wave 0 (adapt):   walks the tile's stream and adapts the tile's narrow CDF rows (LDS, [slot][lane] x 8 bytes {c0, c1, c2, counter});
-//                     passes on every entry's row as it was BEFORE the entry;
+// Two forms of the range coder, one lane per tile and 64 tiles per workgroup (the launcher picks one).  Both run the per-entry core
+// below; they differ only in how its steps are split across waves and in the LDS rings between them.
+#define RC_BATCH 16
+#define RC_DUMMY (MAX_COMBOS * SLOTS_PER_COMBO)
+// a tile's narrow CDF rows, [slot][lane] x 8 bytes {c0, c1, c2, counter}, + one dummy row: entries that need no resolving go through
+// it, branch-free
+typedef uint64_t RcRows[RC_DUMMY + 1][64];
+typedef uint4 QBuf[RC_BATCH / 4];
+
+struct RcTile {
+  bool live, overflow;
+  int tile, count, nb;   // count: 0 on overflow; nb: batches of the wave's longest tile
+  const uint32_t *st;    // the tile's stream
+  int adapt;
+
+  // The stream reads are one 16-byte request per lane into 64 different streams (an HBM / L2 round trip each): the next batch is
+  // loaded while the current one is worked on.  Three register buffers (batch mod 3): a buffer is refilled with batch + 3 at the END
+  // of the trip that used it - when its registers are dead, so that the loaded registers ARE the loop-carried ones and nothing is
+  // copied (a copy waits for the load just issued) - which gives a load two whole trips to arrive.  The loads are unconditional (a
+  // load under `i < count` costs a select per register and makes the compiler wait for ALL loads in flight wherever one is used): a
+  // lane whose tile is shorter than the wave's longest reads what an earlier chunk left in its slot - batch kb < nb lies inside the
+  // slot, whose capacity is a multiple of the batch - and nothing uses it.
+  __device__ __forceinline__ void load_batch(QBuf &q, int kb) const {
+    kb = kb < nb ? kb : (nb > 0 ? nb - 1 : 0);
+#pragma unroll
+    for (int j = 0; j < RC_BATCH; j += 4) q[j / 4] = *reinterpret_cast<const uint4 *>(st + kb * RC_BATCH + j);
+  }
+};
+
+static __device__ __forceinline__ RcTile rc_tile(const Av1miDevParams &P, int n_tiles, const uint32_t *streams, const uint32_t *stream_len,
+                                                 const uint32_t *order, int tile0, int lane) {
+  RcTile t;
+  // order != nullptr (more workgroups than the chip holds at once): the 64 tiles of a workgroup are neighbours in the order of
+  // decreasing stream length (tile_order_kernel) - a wave lasts as long as its longest tile, so similar lengths waste the fewest
+  // lane-cycles, and the long ones start first
+  t.live = (int)(blockIdx.x * 64 + lane) < n_tiles;
+  t.tile = t.live ? tile0 + (order ? (int)order[blockIdx.x * 64 + lane] : (int)(blockIdx.x * 64 + lane)) : 0;
+  const int count_raw = t.live ? (int)stream_len[t.tile] : 0;
+  t.overflow = count_raw > P.stream_cap;
+  t.count = t.overflow ? 0 : count_raw;
+  int maxcount = t.count;
+  for (int o = 32; o > 0; o >>= 1) { const int m = __shfl_xor(maxcount, o, 64); maxcount = m > maxcount ? m : maxcount; }
+  t.nb = (maxcount + RC_BATCH - 1) / RC_BATCH;
+  t.st = streams + (size_t)(t.live ? t.tile : 0) * P.stream_cap;
+  t.adapt = !P.disable_cdf_update;
+  return t;
+}
+
+// per-lane CDF rows from the defaults of the tile's two (tx size, plane type) classes (one byte each in `combos`, 0xFF: none)
+static __device__ __forceinline__ void rc_init_rows(RcRows &row, const uint16_t *cdf_init, uint32_t combos, int lane) {
+  for (int k = 0; k < MAX_COMBOS; k++) {
+    const int combo = (combos >> (8 * k)) & 0xFF;
+    if (combo == 0xFF) continue;
+    const int txs = combo >> 1, ptype = combo & 1;
+    const uint16_t *b = cdf_init + CL::COEFF_BASE + (txs * 2 + ptype) * 42 * 5;
+    const uint16_t *r = cdf_init + CL::COEFF_BR + ((txs > 3 ? 3 : txs) * 2 + ptype) * 21 * 5;
+    uint64_t (*const rk)[64] = row + k * SLOTS_PER_COMBO;
+    for (int j = 0; j < 42; j++) rk[j][lane] = (uint64_t)b[j * 5] | ((uint64_t)b[j * 5 + 1] << 16) | ((uint64_t)b[j * 5 + 2] << 32);
+    for (int j = 0; j < 21; j++) rk[42 + j][lane] = (uint64_t)r[j * 5] | ((uint64_t)r[j * 5 + 1] << 16) | ((uint64_t)r[j * 5 + 2] << 32);
+  }
+  row[RC_DUMMY][lane] = 0;
+}
+
+// Every wave runs a loop of its own with the same number of barriers: in one loop with a branch per wave the compiler's wait-count
+// pass loses track of the loads in flight at the joins and waits for all of them.
+static __device__ __forceinline__ void rc_trip_end() {
+  // (the fences name the LDS address space only: the stream loads in flight and the output stores must not be waited for here)
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+static __device__ __forceinline__ void rc_entries(const QBuf &q, uint32_t (&ev)[RC_BATCH]) {
+#pragma unroll
+  for (int j = 0; j < RC_BATCH; j += 4) { ev[j] = q[j / 4].x; ev[j + 1] = q[j / 4].y; ev[j + 2] = q[j / 4].z; ev[j + 3] = q[j / 4].w; }
+}
+
+// the row after coding symbol s: the three values move towards 32768 (index < s) or 0 by their distance >> rate - packed 16-bit
+// arithmetic on {c0, c1} and on {c2, counter} (the counter half is replaced afterwards)
+static __device__ __forceinline__ uint64_t rc_adapt(uint64_t rw, int s) {
+  typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+  const uint32_t c01 = (uint32_t)rw, c2n = (uint32_t)(rw >> 32);  // {c0, c1}, {c2, counter}
+  const uint32_t cn = c2n >> 16;
+  const unsigned short rate = (unsigned short)(5 + (cn >> 4));   // counter <= 32: 5 + (cn > 15) + (cn > 31)
+  const us2 rv = { rate, rate }, top = { 0x8000, 0x8000 };
+  const us2 a = __builtin_bit_cast(us2, c01), b = __builtin_bit_cast(us2, c2n);
+  const uint32_t up01 = __builtin_bit_cast(uint32_t, (us2)(a + ((top - a) >> rv))), dn01 = __builtin_bit_cast(uint32_t, (us2)(a - (a >> rv)));
+  const uint32_t up2 = __builtin_bit_cast(uint32_t, (us2)(b + ((top - b) >> rv))), dn2 = __builtin_bit_cast(uint32_t, (us2)(b - (b >> rv)));
+  const uint32_t m01 = s >= 2 ? 0xFFFFFFFFu : (s ? 0xFFFFu : 0u);   // halves with index < s
+  const uint32_t n01 = (up01 & m01) | (dn01 & ~m01);
+  const uint32_t cn1 = cn + 1 < 32u ? cn + 1 : 32u;
+  const uint32_t n2 = ((s > 2 ? up2 : dn2) & 0xFFFFu) | (cn1 << 16);
+  return (uint64_t)n01 | ((uint64_t)n2 << 32);
+}
+
+// The batch's 16 entries, one after the other: `f(jj, entry, row)` sees each entry with its row as it was BEFORE the entry, then the
+// row is adapted.  An entry that is already resolved runs the same instructions against the dummy row: no divergent branch.  What
+// lies beyond a tile's count inside the last batch is whatever an earlier chunk left there: it may adapt rows (the tile is over) and
+// is replaced before it is coded.  The row of entry i + 1 is read BEFORE entry i's row is written back, and replaced by that new row
+// if both entries name the same slot - otherwise every entry waited for an LDS round trip behind the previous entry's write (read ->
+// adapt -> write -> read ...).
+template <class F>
+static __device__ __forceinline__ void rc_walk(RcRows &row, const QBuf &q, int lane, int adapt, F &&f) {
+  uint32_t ev[RC_BATCH];
+  rc_entries(q, ev);
+  auto slot_of = [&](uint32_t e) { const uint32_t t = e >> 2; return (int)(t < (uint32_t)RC_DUMMY ? t : (uint32_t)RC_DUMMY); };
+  int slot = slot_of(ev[0]);
+  uint64_t rw = row[slot][lane];
+#pragma unroll
+  for (int jj = 0; jj < RC_BATCH; jj++) {
+    const int s = ev[jj] & 3;
+    int slot_nx = 0;
+    uint64_t rw_nx = 0;
+    if (jj + 1 < RC_BATCH) { slot_nx = slot_of(ev[jj + 1]); rw_nx = row[slot_nx][lane]; }
+    f(jj, ev[jj], rw);
+    uint64_t nrow = rw;
+    if (adapt) {
+      nrow = rc_adapt(rw, s);
+      row[slot][lane] = nrow;
+    }
+    if (jj + 1 < RC_BATCH) { rw = slot_nx == slot ? nrow : rw_nx; slot = slot_nx; }
+  }
+}
+
+// a narrow entry resolved against its row: {fl, fh, N - s}; a resolved one as it is
+static __device__ __forceinline__ uint32_t rc_resolve(uint64_t rw, uint32_t ent) {
+  const int s = ent & 3;
+  const uint32_t c01 = (uint32_t)rw, c2 = (uint32_t)(rw >> 32) & 0xFFFFu;
+  // fl = icdf[s-1] (32768 for s == 0), fh = icdf[s] (0 for s == 3): one 64-bit shift each of {32768, c0, c1, c2} / {c0, c1, c2, 0}
+  const uint64_t vals = ((uint64_t)c2 << 32) | c01;
+  const uint32_t fh = (uint32_t)(vals >> (16 * s)) & 0xFFFFu;
+  const uint32_t fl = (uint32_t)(((vals << 16) | 0x8000u) >> (16 * s)) & 0xFFFFu;
+  return (ent & 0x80000000u) ? ent : ENT_RESOLVED(fl >> 6, fh >> 6, 3 - s);
+}
+
+// entry i of the tile, or beyond its count "the whole range" (fl = 32768, fh = 0 of a one-symbol alphabet): changes nothing, emits
+// nothing
+static __device__ __forceinline__ uint32_t rc_clip(uint32_t ent, int i, int count) { return i < count ? ent : ENT_RESOLVED(512, 0, 0); }
+
+struct RcStep {
+  uint32_t add;   // what the entry adds to `low`: below 2^16
+  int d;          // the normalisation shift
+};
+
+// range update (od_ec_encode_q15, the mirror of spec §8.2.6), branch-free: fl6 == 512 <=> s == 0
+static __device__ __forceinline__ RcStep rc_range(uint32_t &rng, uint32_t ent) {
+  const uint32_t fl6 = (ent >> 14) & 0x3FF, fh6 = (ent >> 4) & 0x3FF, ns = ent & 15;
+  const uint32_t r = rng, r8 = r >> 8;
+  // (r8 < 2^8, fl6 / fh6 <= 512: 24-bit multiplies, full rate)
+  const uint32_t v = (__umul24(r8, fh6) >> 1) + 4u * ns;
+  const uint32_t u = fl6 >= 512 ? r : (__umul24(r8, fl6) >> 1) + 4u * ns + 4u;
+  const uint32_t nr = u - v;
+  const int d = __builtin_clz(nr) - 16;
+  rng = nr << d;
+  return { r - u, d };
+}
+
+// Output: "pre-carry" entries, one 16-bit value per output byte holding the byte and, in bit 8, a carry that still has to be added to
+// the bytes before it (od_ec's precarry buffer).  Nothing already written is ever touched here; pack_tiles_kernel resolves the carries
+// of a whole tile with a wave-parallel carry-lookahead when it copies the tile to its final place.  This keeps the serial chain per
+// symbol short: the kernel lasts as long as its longest tile.
+struct RcOut {
+  uint16_t *tile;
+  int cap;   // entries
+  uint32_t low = 0;
+  int cnt = -9, pos = 0;
+
+  // (the tile's slot is a per-lane 64-bit base - chunks whose slots exceed 4 GB are legal: 4K x 140 frames at capacity scale 2 -
+  // and the entry's position inside it a 32-bit offset, one v_lshl_add_u64 per store; an entry beyond the slot's capacity goes to
+  // the last one: the overflow is reported through tile_bytes, what the slot then holds does not matter)
+  __device__ __forceinline__ RcOut(const Av1miDevParams &P, uint8_t *slots, const RcTile &t)
+      : tile(reinterpret_cast<uint16_t *>(slots) + (size_t)(t.live ? t.tile : 0) * (size_t)P.tile_slot_bytes), cap(P.tile_slot_bytes) {}
+
+  __device__ __forceinline__ void put(int p, uint32_t v) const { tile[(uint32_t)(p < cap ? p : cap - 1)] = (uint16_t)(v & 0x1FFu); }
+  __device__ __forceinline__ void emit(uint32_t v) { put(pos, v); pos++; }
+
+  // adds a range step to `low` and writes what is due (od_ec_enc_normalize)
+  __device__ __forceinline__ void code(uint32_t add, int d) {
+    uint32_t l = low + add;
+    int s2 = cnt + d;
+    if (s2 >= 0) {   // one byte, or two when at least 8 bits are ready
+      int c = cnt + 16;
+      const bool two = s2 >= 8;
+      // no inner branch: the first byte is stored in any case and, if it was not due, overwritten by the second at the same position
+      put(pos, l >> c);
+      pos += two;
+      l = two ? l & ((1u << c) - 1) : l;
+      c = two ? c - 8 : c;
+      emit(l >> c);
+      l &= (1u << c) - 1;
+      s2 = c + d - 24;
+    }
+    low = l << d;
+    cnt = s2;
+  }
+};
+
+// od_ec_enc_done, and the tile's length (all ones: overflow)
+static __device__ __forceinline__ void rc_finish(const RcTile &t, RcOut &o, uint32_t *tile_bytes) {
+  if (t.live && !t.overflow) {
+    uint32_t l = o.low;
+    int c = o.cnt, s = 10;
+    const uint32_t m = 0x3FFF;
+    uint32_t v = ((l + m) & ~m) | (m + 1);
+    s += c;
+    if (s > 0) {
+      uint32_t n = (1u << (c + 16)) - 1;
+      do {
+        o.emit(v >> (c + 16));
+        v &= n;
+        s -= 8;
+        c -= 8;
+        n >>= 8;
+      } while (s > 0);
+    }
+  }
+  if (t.live) tile_bytes[t.tile] = t.overflow ? 0xFFFFFFFFu : (uint32_t)o.pos;
+}
+
+// ---- K4, four-stage form
+// FOUR waves per workgroup - one per SIMD of the CU - working as a pipeline over batches of RC_BATCH entries (batch k is at stage j in
+// trip k + j; double-buffered LDS rings between the stages, one barrier per trip):
+//   wave 0 (adapt):   walks the tile's stream and adapts the tile's rows; passes on every entry's row as it was BEFORE the entry;
 //   wave 1 (resolve): turns (entry, row) into a RESOLVED entry {fl, fh, N - s};
 //   wave 2 (range):   the range recurrence alone: rng -> (what the entry adds to `low`, the normalisation shift);
 //   wave 3 (output):  accumulates `low` and writes the tile's bytes.
 // The kernel's duration is the serial chain of its longest tile (~4.8 k symbols at 1080p) times the instructions per entry of the
 // slowest stage: a wave alone on its SIMD issues one vector instruction per ~4.4 cycles, so the two-wave form (resolver 61, coder 45
 // instructions per entry) was bound at 61; the stages here are 34 / 25 / 20 / 34.
-#define RC_BATCH 16
-#define RC_DUMMY (MAX_COMBOS * SLOTS_PER_COMBO)
 struct RcLds {
-  uint64_t row[RC_DUMMY + 1][64];   // + one dummy row: entries that need no resolving go through it, branch-free
+  RcRows row;
   uint64_t ring_row[2][RC_BATCH][64];
   uint32_t ring_ent[2][RC_BATCH][64];
   uint32_t ring_upd[2][RC_BATCH][64];
@@ -978,208 +1195,58 @@ __global__ void __launch_bounds__(256) rangecode4_tiles_kernel(Av1miDevParams P,
                                                              uint32_t *__restrict__ tile_bytes, const uint32_t *__restrict__ order,
                                                              int tile0 /* chunk-wide index of the launch's first tile; n_tiles and `order` are launch-local */) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  // order != nullptr (more workgroups than the chip holds at once): a permutation of the launch's tiles, see the launcher
-  const bool live = (int)(blockIdx.x * 64 + lane) < n_tiles;
-  const int tile = live ? tile0 + (order ? (int)order[blockIdx.x * 64 + lane] : (int)(blockIdx.x * 64 + lane)) : 0;
-  const int count_raw = live ? (int)stream_len[tile] : 0;
-  const bool overflow = count_raw > P.stream_cap;
-  const int count = overflow ? 0 : count_raw;
-  int maxcount = count;
-  for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(maxcount, o, 64); maxcount = t > maxcount ? t : maxcount; }
-  const int nb = (maxcount + RC_BATCH - 1) / RC_BATCH;
-  const uint32_t *st = streams + (size_t)(live ? tile : 0) * P.stream_cap;
-  const int adapt = !P.disable_cdf_update;
-
-  // ---- adapt stage: per-lane CDF rows from the defaults of this tile's two (tx size, plane type) classes
-  if (wave == 0) {
-    const uint32_t cm = live ? tile_combos[tile] : 0xFFFFu;
-    for (int k = 0; k < MAX_COMBOS; k++) {
-      const int combo = (cm >> (8 * k)) & 0xFF;
-      if (combo == 0xFF) continue;
-      const int txs = combo >> 1, ptype = combo & 1;
-      const uint16_t *b = cdf_init + CL::COEFF_BASE + (txs * 2 + ptype) * 42 * 5;
-      const uint16_t *r = cdf_init + CL::COEFF_BR + ((txs > 3 ? 3 : txs) * 2 + ptype) * 21 * 5;
-      for (int j = 0; j < 42; j++) g_rc.row[k * SLOTS_PER_COMBO + j][lane] = (uint64_t)b[j * 5] | ((uint64_t)b[j * 5 + 1] << 16) | ((uint64_t)b[j * 5 + 2] << 32);
-      for (int j = 0; j < 21; j++) g_rc.row[k * SLOTS_PER_COMBO + 42 + j][lane] = (uint64_t)r[j * 5] | ((uint64_t)r[j * 5 + 1] << 16) | ((uint64_t)r[j * 5 + 2] << 32);
-    }
-    g_rc.row[RC_DUMMY][lane] = 0;
-  }
-  // ---- range stage / output stage state
-  uint32_t low = 0, rng = 0x8000;
-  int cnt = -9, out_pos = 0;
-  // Output: "pre-carry" entries, one 16-bit value per output byte holding the byte and, in bit 8, a carry that still
-  // has to be added to the bytes before it (od_ec's precarry buffer).  Nothing already written is ever touched here;
-  // pack_tiles_kernel resolves the carries of a whole tile with a wave-parallel carry-lookahead when it copies the
-  // tile to its final place.
-  // (the tile's slot is a per-lane 64-bit base - chunks whose slots exceed 4 GB are legal: 4K x 140 frames at capacity scale 2 -
-  // and the entry's position inside it a 32-bit offset, one v_lshl_add_u64 per store; an entry beyond the slot's capacity goes to
-  // the last one: the overflow is reported through tile_bytes, what the slot then holds does not matter)
-  uint16_t *const out_tile = reinterpret_cast<uint16_t *>(slots) + (size_t)(live ? tile : 0) * (size_t)P.tile_slot_bytes;
-  const int out_cap = P.tile_slot_bytes;  // entries
-#define PUT(pos_, v_)                                                                                                    \
-  do {                                                                                                                   \
-    out_tile[(uint32_t)((pos_) < out_cap ? (pos_) : out_cap - 1)] = (uint16_t)((v_) & 0x1FFu);                           \
-  } while (0)
-#define EMIT(v_) do { PUT(out_pos, v_); out_pos++; } while (0)
-
+  const RcTile T = rc_tile(P, n_tiles, streams, stream_len, order, tile0, lane);
+  if (wave == 0) rc_init_rows(g_rc.row, cdf_init, T.live ? tile_combos[T.tile] : 0xFFFFu, lane);
+  uint32_t rng = 0x8000;    // range stage
+  RcOut out(P, slots, T);   // output stage
   __syncthreads();
-  // The stream reads of waves 0 and 1 are one 16-byte request per lane into 64 different streams (an HBM / L2 round trip each):
-  // the next batch is loaded while the current one is worked on (handing the entries from wave 0 to wave 1 through LDS instead was
-  // measured: no faster).  What lies beyond a tile's count inside the last 16 bytes is whatever an earlier chunk left there: wave 0
-  // may adapt rows with it (the tile is over), wave 1 replaces it by an entry that codes nothing.
-  // Three register buffers (batch mod 3): a buffer is refilled with batch + 3 at the END of the trip that used it - when its registers
-  // are dead, so that the loaded registers ARE the loop-carried ones and nothing is copied (a copy waits for the load just issued) -
-  // which gives a load two whole trips to arrive.  The loads are unconditional (a load under `i < count` costs a select per register
-  // and makes the compiler wait for ALL loads in flight wherever one is used): a lane whose tile is shorter than the wave's longest
-  // reads what an earlier chunk left in its slot - batch kb < nb lies inside the slot, whose capacity is a multiple of the batch -
-  // and nothing uses it.
-  typedef uint4 QBuf[RC_BATCH / 4];
+  // waves 0 and 1 both read the stream (handing the entries from wave 0 to wave 1 through LDS instead was measured: no faster)
   QBuf qa, qb, qc;
-  auto load_batch = [&](QBuf &q, int kb) __attribute__((always_inline)) {
-    kb = kb < nb ? kb : (nb > 0 ? nb - 1 : 0);
-#pragma unroll
-    for (int j = 0; j < RC_BATCH; j += 4) q[j / 4] = *reinterpret_cast<const uint4 *>(st + kb * RC_BATCH + j);
-  };
-  if (wave <= 1) { load_batch(qa, 0); load_batch(qb, 1); load_batch(qc, 2); }
-  // Every wave runs a loop of its own with the same number of barriers (nb + 3): in one loop with a branch per wave the compiler's
-  // wait-count pass loses track of the loads in flight at the joins and waits for all of them.
-  auto trip_end = [&]() __attribute__((always_inline)) {
-    // (the fences name the LDS address space only: the stream loads in flight and the output stores must not be waited for here)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-  };
-  const int n_trips = (nb + 3 + 2) / 3 * 3;   // (a multiple of 3: the loops of waves 0 and 1 are unrolled by the three buffers)
+  if (wave <= 1) { T.load_batch(qa, 0); T.load_batch(qb, 1); T.load_batch(qc, 2); }
+  const int n_trips = (T.nb + 3 + 2) / 3 * 3;   // (a multiple of 3: the loops of waves 0 and 1 are unrolled by the three buffers)
   auto stage0 = [&](const int k, QBuf &q0) __attribute__((always_inline)) {
-    {
-      if (k < nb) {
-        uint32_t ev[RC_BATCH];
-#pragma unroll
-        for (int j = 0; j < RC_BATCH; j += 4) { ev[j] = q0[j / 4].x; ev[j + 1] = q0[j / 4].y; ev[j + 2] = q0[j / 4].z; ev[j + 3] = q0[j / 4].w; }
-        // The 16 entries of the batch, one after the other.  An entry that is already resolved runs the same instructions against the
-        // dummy row: no divergent branch.  The row of entry i + 1 is read BEFORE entry i's row is written back, and replaced by that
-        // new row if both entries name the same slot - otherwise every entry waited for an LDS round trip behind the previous
-        // entry's write (read -> adapt -> write -> read ...).
-        auto slot_of = [&](uint32_t e) { const uint32_t t = e >> 2; return (int)(t < (uint32_t)RC_DUMMY ? t : (uint32_t)RC_DUMMY); };
-        int slot = slot_of(ev[0]);
-        uint64_t rw = g_rc.row[slot][lane];
-#pragma unroll
-        for (int jj = 0; jj < RC_BATCH; jj++) {
-          const int s = ev[jj] & 3;
-          int slot_nx = 0;
-          uint64_t rw_nx = 0;
-          if (jj + 1 < RC_BATCH) { slot_nx = slot_of(ev[jj + 1]); rw_nx = g_rc.row[slot_nx][lane]; }
-          g_rc.ring_row[k & 1][jj][lane] = rw;
-          uint64_t nrow = rw;
-          if (adapt) {
-            // the three values move towards 32768 (index < s) or 0 by their distance >> rate: packed 16-bit arithmetic on {c0, c1}
-            // and on {c2, counter} (the counter half is replaced afterwards)
-            typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-            const uint32_t c01 = (uint32_t)rw, c2n = (uint32_t)(rw >> 32);  // {c0, c1}, {c2, counter}
-            const uint32_t cn = c2n >> 16;
-            const unsigned short rate = (unsigned short)(5 + (cn >> 4));   // counter <= 32: 5 + (cn > 15) + (cn > 31)
-            const us2 rv = { rate, rate }, top = { 0x8000, 0x8000 };
-            const us2 a = __builtin_bit_cast(us2, c01), b = __builtin_bit_cast(us2, c2n);
-            const uint32_t up01 = __builtin_bit_cast(uint32_t, (us2)(a + ((top - a) >> rv))), dn01 = __builtin_bit_cast(uint32_t, (us2)(a - (a >> rv)));
-            const uint32_t up2 = __builtin_bit_cast(uint32_t, (us2)(b + ((top - b) >> rv))), dn2 = __builtin_bit_cast(uint32_t, (us2)(b - (b >> rv)));
-            const uint32_t m01 = s >= 2 ? 0xFFFFFFFFu : (s ? 0xFFFFu : 0u);   // halves with index < s
-            const uint32_t n01 = (up01 & m01) | (dn01 & ~m01);
-            const uint32_t cn1 = cn + 1 < 32u ? cn + 1 : 32u;
-            const uint32_t n2 = ((s > 2 ? up2 : dn2) & 0xFFFFu) | (cn1 << 16);
-            nrow = (uint64_t)n01 | ((uint64_t)n2 << 32);
-            g_rc.row[slot][lane] = nrow;
-          }
-          if (jj + 1 < RC_BATCH) { rw = slot_nx == slot ? nrow : rw_nx; slot = slot_nx; }
-        }
-      }
-    }
-    load_batch(q0, k + 3);
-    trip_end();
+    if (k < T.nb) rc_walk(g_rc.row, q0, lane, T.adapt, [&](int jj, uint32_t, uint64_t rw) { g_rc.ring_row[k & 1][jj][lane] = rw; });
+    T.load_batch(q0, k + 3);
+    rc_trip_end();
   };
   auto stage1 = [&](const int k, QBuf &q1) __attribute__((always_inline)) {
-    {
-      if (k >= 1 && k - 1 < nb) {
-        const int kb = k - 1;
-        uint32_t ev[RC_BATCH];
+    if (k >= 1 && k - 1 < T.nb) {
+      const int kb = k - 1;
+      uint32_t ev[RC_BATCH];
+      rc_entries(q1, ev);
+      uint64_t rws[RC_BATCH];
 #pragma unroll
-        for (int j = 0; j < RC_BATCH; j += 4) { ev[j] = q1[j / 4].x; ev[j + 1] = q1[j / 4].y; ev[j + 2] = q1[j / 4].z; ev[j + 3] = q1[j / 4].w; }
-        uint64_t rws[RC_BATCH];
+      for (int j = 0; j < RC_BATCH; j++) rws[j] = g_rc.ring_row[kb & 1][j][lane];
 #pragma unroll
-        for (int j = 0; j < RC_BATCH; j++) rws[j] = g_rc.ring_row[kb & 1][j][lane];
-#pragma unroll
-        for (int jj = 0; jj < RC_BATCH; jj++) {
-          uint32_t ent = ev[jj];
-          const int s = ent & 3;
-          const uint32_t c01 = (uint32_t)rws[jj], c2 = (uint32_t)(rws[jj] >> 32) & 0xFFFFu;
-          // fl = icdf[s-1] (32768 for s == 0), fh = icdf[s] (0 for s == 3): one 64-bit shift each of {32768, c0, c1, c2} / {c0, c1, c2, 0}
-          const uint64_t vals = ((uint64_t)c2 << 32) | c01;
-          const uint32_t fh = (uint32_t)(vals >> (16 * s)) & 0xFFFFu;
-          const uint32_t fl = (uint32_t)(((vals << 16) | 0x8000u) >> (16 * s)) & 0xFFFFu;
-          ent = (ent & 0x80000000u) ? ent : ENT_RESOLVED(fl >> 6, fh >> 6, 3 - s);
-          // beyond this tile's count: "the whole range" (fl = 32768, fh = 0 of a one-symbol alphabet) changes nothing and emits nothing
-          ent = kb * RC_BATCH + jj < count ? ent : ENT_RESOLVED(512, 0, 0);
-          g_rc.ring_ent[kb & 1][jj][lane] = ent;
-        }
-      }
+      for (int j = 0; j < RC_BATCH; j++) g_rc.ring_ent[kb & 1][j][lane] = rc_clip(rc_resolve(rws[j], ev[j]), kb * RC_BATCH + j, T.count);
     }
-    if (k >= 1) load_batch(q1, k - 1 + 3);
-    trip_end();
+    if (k >= 1) T.load_batch(q1, k - 1 + 3);
+    rc_trip_end();
   };
   auto stage2 = [&](const int k) __attribute__((always_inline)) {
-    {
-      if (k >= 2 && k - 2 < nb) {
-        const int kb = k - 2;
-        uint32_t ce[RC_BATCH];
+    if (k >= 2 && k - 2 < T.nb) {
+      const int kb = k - 2;
+      uint32_t ce[RC_BATCH];
 #pragma unroll
-        for (int j = 0; j < RC_BATCH; j++) ce[j] = g_rc.ring_ent[kb & 1][j][lane];
+      for (int j = 0; j < RC_BATCH; j++) ce[j] = g_rc.ring_ent[kb & 1][j][lane];
 #pragma unroll
-        for (int j = 0; j < RC_BATCH; j++) {
-          const uint32_t ent = ce[j];
-          const uint32_t fl6 = (ent >> 14) & 0x3FF, fh6 = (ent >> 4) & 0x3FF, ns = ent & 15;
-          // range update (od_ec_encode_q15, the mirror of spec §8.2.6), branch-free: fl6 == 512 <=> s == 0
-          const uint32_t r = rng, r8 = r >> 8;
-          // (r8 < 2^8, fl6 / fh6 <= 512: 24-bit multiplies, full rate)
-          const uint32_t v = (__umul24(r8, fh6) >> 1) + 4u * ns;
-          const uint32_t u = fl6 >= 512 ? r : (__umul24(r8, fl6) >> 1) + 4u * ns + 4u;
-          const uint32_t nr = u - v;
-          const int d = __builtin_clz(nr) - 16;
-          rng = nr << d;
-          g_rc.ring_upd[kb & 1][j][lane] = (r - u) | ((uint32_t)d << 16);
-        }
+      for (int j = 0; j < RC_BATCH; j++) {
+        const RcStep e = rc_range(rng, ce[j]);
+        g_rc.ring_upd[kb & 1][j][lane] = e.add | ((uint32_t)e.d << 16);
       }
     }
-    trip_end();
+    rc_trip_end();
   };
   auto stage3 = [&](const int k) __attribute__((always_inline)) {
-    {
-      if (k >= 3 && k - 3 < nb) {
-        const int kb = k - 3;
-        uint32_t cu[RC_BATCH];
+    if (k >= 3 && k - 3 < T.nb) {
+      const int kb = k - 3;
+      uint32_t cu[RC_BATCH];
 #pragma unroll
-        for (int j = 0; j < RC_BATCH; j++) cu[j] = g_rc.ring_upd[kb & 1][j][lane];
+      for (int j = 0; j < RC_BATCH; j++) cu[j] = g_rc.ring_upd[kb & 1][j][lane];
 #pragma unroll
-        for (int j = 0; j < RC_BATCH; j++) {
-          const int d = (int)(cu[j] >> 16);
-          uint32_t l = low + (cu[j] & 0xFFFFu);
-          int s2 = cnt + d;
-          if (s2 >= 0) {   // one byte, or two when at least 8 bits are ready (od_ec_enc_normalize)
-            int c = cnt + 16;
-            const bool two = s2 >= 8;
-            // no inner branch: the first byte is stored in any case and, if it was not due, overwritten by the second at the same position
-            PUT(out_pos, l >> c);
-            out_pos += two;
-            l = two ? l & ((1u << c) - 1) : l;
-            c = two ? c - 8 : c;
-            EMIT(l >> c);
-            l &= (1u << c) - 1;
-            s2 = c + d - 24;
-          }
-          low = l << d;
-          cnt = s2;
-        }
-      }
+      for (int j = 0; j < RC_BATCH; j++) out.code(cu[j] & 0xFFFFu, (int)(cu[j] >> 16));
     }
-    trip_end();
+    rc_trip_end();
   };
   if (wave == 0) {
     for (int k = 0; k < n_trips; k += 3) { stage0(k, qa); stage0(k + 1, qb); stage0(k + 2, qc); }
@@ -1190,40 +1257,17 @@ __global__ void __launch_bounds__(256) rangecode4_tiles_kernel(Av1miDevParams P,
   } else {
     for (int k = 0; k < n_trips; k++) stage3(k);
   }
-  // ---- finish (od_ec_enc_done), output wave
-  if (wave == 3) {
-    if (live && !overflow) {
-      uint32_t l = low;
-      int c = cnt, s = 10;
-      const uint32_t m = 0x3FFF;
-      uint32_t v = ((l + m) & ~m) | (m + 1);
-      s += c;
-      if (s > 0) {
-        uint32_t n = (1u << (c + 16)) - 1;
-        do {
-          EMIT(v >> (c + 16));
-          v &= n;
-          s -= 8;
-          c -= 8;
-          n >>= 8;
-        } while (s > 0);
-      }
-    }
-    if (live) tile_bytes[tile] = overflow ? 0xFFFFFFFFu : (uint32_t)out_pos;
-  }
+  if (wave == 3) rc_finish(T, out, tile_bytes);
 }
-#undef EMIT
-#undef PUT
 
 // ---- K4, two-stage form (more than 256 workgroups: see the launcher)
-// One lane per tile, 64 tiles per workgroup, TWO waves per workgroup working as a pipeline:
-//   wave 0 (resolver): walks the tile's stream, adapts the tile's narrow CDF rows (LDS, [slot][lane] x
-//           8 bytes {c0, c1, c2, counter}) and turns every entry into a RESOLVED one in an LDS ring;
+// TWO waves per workgroup working as a pipeline:
+//   wave 0 (resolver): walks the tile's stream, adapts the tile's rows and turns every entry into a RESOLVED one in an LDS ring;
 //   wave 1 (coder):    runs the range coder over the ring and writes the tile's bytes.
 // The kernel's duration is the serial chain of its longest tile (~4.8 k symbols at 1080p), so halving
 // the instructions per link of that chain matters more than anything else here.
 struct Rc2Lds {
-  uint64_t row[MAX_COMBOS * SLOTS_PER_COMBO + 1][64];   // + one dummy row: entries that need no resolving go through it, branch-free
+  RcRows row;
   uint32_t ring[2][RC_BATCH][64];
 };
 __shared__ Rc2Lds g_rc2;
@@ -1234,203 +1278,42 @@ __global__ void __launch_bounds__(128) rangecode2_tiles_kernel(Av1miDevParams P,
                                                              uint32_t *__restrict__ tile_bytes, const uint32_t *__restrict__ order,
                                                              int tile0 /* chunk-wide index of the launch's first tile; n_tiles and `order` are launch-local */) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-  // order != nullptr (more tiles than the chip holds workgroups for at once): the 64 tiles of a workgroup are neighbours in
-  // the order of decreasing stream length (tile_order_kernel) - a wave lasts as long as its longest tile, so similar lengths
-  // waste the fewest lane-cycles, and the long ones start first
-  const bool live = (int)(blockIdx.x * 64 + lane) < n_tiles;
-  const int tile = live ? tile0 + (order ? (int)order[blockIdx.x * 64 + lane] : (int)(blockIdx.x * 64 + lane)) : 0;
-  const int count_raw = live ? (int)stream_len[tile] : 0;
-  const bool overflow = count_raw > P.stream_cap;
-  const int count = overflow ? 0 : count_raw;
-  int maxcount = count;
-  for (int o = 32; o > 0; o >>= 1) { const int t = __shfl_xor(maxcount, o, 64); maxcount = t > maxcount ? t : maxcount; }
-  const int nb = (maxcount + RC_BATCH - 1) / RC_BATCH;
-  const uint32_t *st = streams + (size_t)(live ? tile : 0) * P.stream_cap;
-  const int adapt = !P.disable_cdf_update;
-
-  // ---- resolver state
-  if (wave == 0) {
-    // per-lane CDF rows from the defaults of this tile's two (tx size, plane type) classes
-    const uint32_t cm = live ? tile_combos[tile] : 0xFFFFu;
-    for (int k = 0; k < MAX_COMBOS; k++) {
-      const int combo = (cm >> (8 * k)) & 0xFF;
-      if (combo == 0xFF) continue;
-      const int txs = combo >> 1, ptype = combo & 1;
-      const uint16_t *b = cdf_init + CL::COEFF_BASE + (txs * 2 + ptype) * 42 * 5;
-      const uint16_t *r = cdf_init + CL::COEFF_BR + ((txs > 3 ? 3 : txs) * 2 + ptype) * 21 * 5;
-      for (int j = 0; j < 42; j++) g_rc2.row[k * SLOTS_PER_COMBO + j][lane] = (uint64_t)b[j * 5] | ((uint64_t)b[j * 5 + 1] << 16) | ((uint64_t)b[j * 5 + 2] << 32);
-      for (int j = 0; j < 21; j++) g_rc2.row[k * SLOTS_PER_COMBO + 42 + j][lane] = (uint64_t)r[j * 5] | ((uint64_t)r[j * 5 + 1] << 16) | ((uint64_t)r[j * 5 + 2] << 32);
-    }
-    g_rc2.row[RC_DUMMY][lane] = 0;
-  }
-  // ---- coder state
-  uint32_t low = 0, rng = 0x8000;
-  int cnt = -9, out_pos = 0;
-  // Output: "pre-carry" entries, one 16-bit value per output byte holding the byte and, in bit 8, a carry that still
-  // has to be added to the bytes before it (od_ec's precarry buffer).  Nothing already written is ever touched here;
-  // pack_tiles_kernel resolves the carries of a whole tile with a wave-parallel carry-lookahead when it copies the
-  // tile to its final place.  This keeps the serial chain per symbol short: the kernel lasts as long as its longest tile.
-  // (the tile's slot is a per-lane 64-bit base - chunks whose slots exceed 4 GB are legal: 4K x 140 frames at capacity scale 2 -
-  // and the entry's position inside it a 32-bit offset, one v_lshl_add_u64 per store; an entry beyond the slot's capacity goes to
-  // the last one: the overflow is reported through tile_bytes, what the slot then holds does not matter)
-  uint16_t *const out_tile = reinterpret_cast<uint16_t *>(slots) + (size_t)(live ? tile : 0) * (size_t)P.tile_slot_bytes;
-  const int out_cap = P.tile_slot_bytes;  // entries
-#define PUT(pos_, v_)                                                                                                    \
-  do {                                                                                                                   \
-    out_tile[(uint32_t)((pos_) < out_cap ? (pos_) : out_cap - 1)] = (uint16_t)((v_) & 0x1FFu);                           \
-  } while (0)
-#define EMIT(v_) do { PUT(out_pos, v_); out_pos++; } while (0)
-
+  const RcTile T = rc_tile(P, n_tiles, streams, stream_len, order, tile0, lane);
+  if (wave == 0) rc_init_rows(g_rc2.row, cdf_init, T.live ? tile_combos[T.tile] : 0xFFFFu, lane);
+  uint32_t rng = 0x8000;    // coder
+  RcOut out(P, slots, T);
   __syncthreads();
-  // batch k is resolved by wave 0 in trip k and coded by wave 1 in trip k + 1.  The resolver's stream reads are one
-  // 16-byte request per lane into 64 different streams (an HBM round trip each): batch k + 1 is loaded while batch k is
-  // being resolved, otherwise every trip would start with that latency.
-  // (three register buffers refilled with batch + 3 at the end of the trip that used them, unconditional loads, a loop per wave with the
-  // same number of barriers: see the four-stage form)
-  typedef uint4 QBuf[RC_BATCH / 4];
+  // batch k is resolved by wave 0 in trip k and coded by wave 1 in trip k + 1
   QBuf qa, qb, qd;
-  auto load_batch = [&](QBuf &q, int kb) __attribute__((always_inline)) {
-    kb = kb < nb ? kb : (nb > 0 ? nb - 1 : 0);
-#pragma unroll
-    for (int j = 0; j < RC_BATCH; j += 4) q[j / 4] = *reinterpret_cast<const uint4 *>(st + kb * RC_BATCH + j);
-  };
-  if (wave == 0) { load_batch(qa, 0); load_batch(qb, 1); load_batch(qd, 2); }
-  auto trip_end = [&]() __attribute__((always_inline)) {
-    // (the fences name the LDS address space only: the stream loads in flight and the output stores must not be waited for here)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-  };
-  const int n_trips = (nb + 1 + 2) / 3 * 3;
+  if (wave == 0) { T.load_batch(qa, 0); T.load_batch(qb, 1); T.load_batch(qd, 2); }
+  const int n_trips = (T.nb + 1 + 2) / 3 * 3;
   auto resolve_trip = [&](const int k, QBuf &q0) __attribute__((always_inline)) {
-    {
-      if (k < nb) {
-        uint4 qc[RC_BATCH / 4];
-#pragma unroll
-        for (int j = 0; j < RC_BATCH / 4; j++) qc[j] = q0[j];
-        // The 16 entries of the batch, one after the other.  An entry that is already resolved (or lies beyond this tile's count) runs
-        // the same instructions against a dummy row and keeps its value: no divergent branch.  The row of entry i + 1 is read BEFORE
-        // entry i's row is written back, and replaced by that new row if both entries name the same slot - otherwise every entry
-        // waited for an LDS round trip behind the previous entry's write (read -> adapt -> write -> read ...).
-        uint32_t ev[RC_BATCH];
-#pragma unroll
-        for (int j = 0; j < RC_BATCH; j += 4) { ev[j] = qc[j / 4].x; ev[j + 1] = qc[j / 4].y; ev[j + 2] = qc[j / 4].z; ev[j + 3] = qc[j / 4].w; }
-        // (no test against the tile's count here: what lies beyond it may adapt rows - the tile is over - and the coder replaces it)
-        auto slot_of = [&](uint32_t e) { const uint32_t t = e >> 2; return (int)(t < (uint32_t)RC_DUMMY ? t : (uint32_t)RC_DUMMY); };
-        int slot = slot_of(ev[0]);
-        uint64_t rw = g_rc2.row[slot][lane];
-#pragma unroll
-        for (int jj = 0; jj < RC_BATCH; jj++) {
-          uint32_t ent = ev[jj];
-          const bool nar = !(ent & 0x80000000u);
-          const int s = ent & 3;
-          int slot_nx = 0;
-          uint64_t rw_nx = 0;
-          if (jj + 1 < RC_BATCH) { slot_nx = slot_of(ev[jj + 1]); rw_nx = g_rc2.row[slot_nx][lane]; }
-          const uint32_t c01 = (uint32_t)rw, c2n = (uint32_t)(rw >> 32);  // {c0, c1}, {c2, counter}
-          // fl = icdf[s-1] (32768 for s == 0), fh = icdf[s] (0 for s == 3): one 64-bit shift each of {32768, c0, c1, c2} / {c0, c1, c2, 0}
-          const uint64_t vals = ((uint64_t)(c2n & 0xFFFFu) << 32) | c01;
-          const uint32_t fh = (uint32_t)(vals >> (16 * s)) & 0xFFFFu;
-          const uint32_t fl = (uint32_t)(((vals << 16) | 0x8000u) >> (16 * s)) & 0xFFFFu;
-          ent = nar ? ENT_RESOLVED(fl >> 6, fh >> 6, 3 - s) : ent;
-          uint64_t nrow = rw;
-          if (adapt) {
-            // the three values move towards 32768 (index < s) or 0 by their distance >> rate: packed 16-bit arithmetic on {c0, c1}
-            // and on {c2, counter} (the counter half is replaced afterwards)
-            typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-            const uint32_t cn = c2n >> 16;
-            const unsigned short rate = (unsigned short)(5 + (cn >> 4));   // counter <= 32: 5 + (cn > 15) + (cn > 31)
-            const us2 rv = { rate, rate }, top = { 0x8000, 0x8000 };
-            const us2 a = __builtin_bit_cast(us2, c01), b = __builtin_bit_cast(us2, c2n);
-            const uint32_t up01 = __builtin_bit_cast(uint32_t, (us2)(a + ((top - a) >> rv))), dn01 = __builtin_bit_cast(uint32_t, (us2)(a - (a >> rv)));
-            const uint32_t up2 = __builtin_bit_cast(uint32_t, (us2)(b + ((top - b) >> rv))), dn2 = __builtin_bit_cast(uint32_t, (us2)(b - (b >> rv)));
-            const uint32_t m01 = s >= 2 ? 0xFFFFFFFFu : (s ? 0xFFFFu : 0u);   // halves with index < s
-            const uint32_t n01 = (up01 & m01) | (dn01 & ~m01);
-            const uint32_t cn1 = cn + 1 < 32u ? cn + 1 : 32u;
-            const uint32_t n2 = ((s > 2 ? up2 : dn2) & 0xFFFFu) | (cn1 << 16);
-            nrow = (uint64_t)n01 | ((uint64_t)n2 << 32);
-            g_rc2.row[slot][lane] = nrow;
-          }
-          g_rc2.ring[k & 1][jj][lane] = ent;
-          if (jj + 1 < RC_BATCH) { rw = slot_nx == slot ? nrow : rw_nx; slot = slot_nx; }
-        }
-      }
-    }
-    load_batch(q0, k + 3);
-    trip_end();
+    if (k < T.nb) rc_walk(g_rc2.row, q0, lane, T.adapt, [&](int jj, uint32_t ent, uint64_t rw) { g_rc2.ring[k & 1][jj][lane] = rc_resolve(rw, ent); });
+    T.load_batch(q0, k + 3);
+    rc_trip_end();
   };
   auto code_trip = [&](const int k) __attribute__((always_inline)) {
-    if (k > 0 && k <= nb) {
+    if (k > 0 && k <= T.nb) {
       const int base = (k - 1) * RC_BATCH;
-      // the batch's 16 entries into registers at once (the reads are independent of the coder's state); an entry beyond this tile's
-      // count is coded as "the whole range" (fl = 32768, fh = 0 of a one-symbol alphabet): it changes nothing and emits nothing
+      // the batch's 16 entries into registers at once (the reads are independent of the coder's state)
       uint32_t ce[RC_BATCH];
 #pragma unroll
       for (int j = 0; j < RC_BATCH; j++) ce[j] = g_rc2.ring[(k - 1) & 1][j][lane];
 #pragma unroll
       for (int j = 0; j < RC_BATCH; j++) {
-        {
-          const uint32_t ent = base + j < count ? ce[j] : ENT_RESOLVED(512, 0, 0);
-          const uint32_t fl6 = (ent >> 14) & 0x3FF, fh6 = (ent >> 4) & 0x3FF, ns = ent & 15;
-          // range update (od_ec_encode_q15, the mirror of spec §8.2.6), branch-free: fl6 == 512 <=> s == 0
-          uint32_t l = low, r = rng;
-          const uint32_t r8 = r >> 8;
-          // (r8 < 2^8, fl6 / fh6 <= 512: 24-bit multiplies, full rate)
-          const uint32_t v = (__umul24(r8, fh6) >> 1) + 4u * ns;
-          const uint32_t u = fl6 >= 512 ? r : (__umul24(r8, fl6) >> 1) + 4u * ns + 4u;
-          l += r - u;
-          r = u - v;
-          const int d = __builtin_clz(r) - 16;
-          int s2 = cnt + d;
-          if (s2 >= 0) {   // one byte, or two when at least 8 bits are ready (od_ec_enc_normalize)
-            int c = cnt + 16;
-            const bool two = s2 >= 8;
-            // no inner branch: the first byte is stored in any case and, if it was not due, overwritten by the second at the same position
-            PUT(out_pos, l >> c);
-            out_pos += two;
-            l = two ? l & ((1u << c) - 1) : l;
-            c = two ? c - 8 : c;
-            EMIT(l >> c);
-            l &= (1u << c) - 1;
-            s2 = c + d - 24;
-          }
-          low = l << d;
-          rng = r << d;
-          cnt = s2;
-        }
+        const RcStep e = rc_range(rng, rc_clip(ce[j], base + j, T.count));
+        out.code(e.add, e.d);
       }
     }
-    trip_end();
+    rc_trip_end();
   };
   if (wave == 0) {
     for (int k = 0; k < n_trips; k += 3) { resolve_trip(k, qa); resolve_trip(k + 1, qb); resolve_trip(k + 2, qd); }
   } else {
     for (int k = 0; k < n_trips; k++) code_trip(k);
   }
-  // ---- finish (od_ec_enc_done), coder wave
-  if (wave == 1) {
-    if (live && !overflow) {
-      uint32_t l = low;
-      int c = cnt, s = 10;
-      const uint32_t m = 0x3FFF;
-      uint32_t v = ((l + m) & ~m) | (m + 1);
-      s += c;
-      if (s > 0) {
-        uint32_t n = (1u << (c + 16)) - 1;
-        do {
-          EMIT(v >> (c + 16));
-          v &= n;
-          s -= 8;
-          c -= 8;
-          n >>= 8;
-        } while (s > 0);
-      }
-    }
-    if (live) tile_bytes[tile] = overflow ? 0xFFFFFFFFu : (uint32_t)out_pos;
-  }
+  if (wave == 1) rc_finish(T, out, tile_bytes);
 }
-#undef EMIT
-#undef PUT
 
 }  // namespace
 
