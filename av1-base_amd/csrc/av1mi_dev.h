@@ -64,7 +64,7 @@ struct Av1miDevParams {
   long frame_samples;             // samples per frame
   // per-tile bitstream slot
   int tile_slot_bytes;
-  int stream_cap;                 // 32-bit symbol-stream entries per tile (multiple of 4)
+  int stream_cap;                 // 32-bit symbol-stream entries per tile (a multiple of RC_BATCH = 16: the range coder reads whole batches)
   // header blob: sequence header OBU, then one slot of `hdr_slot_bytes` per frame holding that frame's OBU_FRAME
   // payload prefix (frame header + alignment); frame_hdr_bytes = its length on key frames, inter_hdr_bytes on
   // inter frames (frames differ only in type and grain_seed)

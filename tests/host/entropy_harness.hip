@@ -1,0 +1,193 @@
+// Launch harness of the entropy back end for tests/test_entropy_kernels.py: the range coder's two forms and the tile order
+// (entropy_kernel.hip), the frame / chunk layout and the tile packing (cdef_pack_kernels.hip), each driven with buffers the
+// test fills itself, so that every path can be checked against an exact reference.  Test infrastructure only.
+//
+// The kernels sit in anonymous namespaces, so only a translation unit that includes their source can launch them.  This file is
+// compiled twice: as is (the range coder) and with -DEH_PACK (the packing); the two sources do not share one translation unit.
+//
+// Every entry point allocates, copies in, launches, synchronises, copies out, frees and returns the hipError_t.  Arguments that
+// would take a launch outside its buffers are refused with hipErrorInvalidValue before that launch.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#ifndef EH_PACK
+#include "../../av1-base_amd/csrc/entropy_kernel.hip"
+#else
+#include "../../av1-base_amd/csrc/cdef_pack_kernels.hip"
+#endif
+
+namespace {
+
+// device buffers of one call, freed on every return path
+struct DevBufs {
+  std::vector<void *> p;
+  template <class T>
+  hipError_t alloc(T **d, size_t n, const void *src = nullptr) {
+    *d = nullptr;
+    void *v = nullptr;
+    hipError_t e = hipMalloc(&v, n * sizeof(T) > 0 ? n * sizeof(T) : 1);
+    if (e != hipSuccess) return e;
+    p.push_back(v);
+    *d = static_cast<T *>(v);
+    return src ? hipMemcpy(v, src, n * sizeof(T), hipMemcpyHostToDevice) : hipMemset(v, 0, n * sizeof(T));
+  }
+  ~DevBufs() {
+    for (void *v : p) (void)hipFree(v);
+  }
+};
+
+#define EH_TRY(x)                        \
+  do {                                   \
+    const hipError_t e_ = (x);           \
+    if (e_ != hipSuccess) return e_;     \
+  } while (0)
+
+}  // namespace
+
+#ifndef EH_PACK
+
+extern "C" int eh_coeff_base() { return CL::COEFF_BASE; }
+extern "C" int eh_coeff_br() { return CL::COEFF_BR; }
+extern "C" int eh_cdf_total() { return CL::TOTAL; }
+extern "C" int eh_rc_batch() { return RC_BATCH; }
+extern "C" int eh_slots_per_combo() { return SLOTS_PER_COMBO; }
+extern "C" int eh_max_combos() { return MAX_COMBOS; }
+extern "C" int eh_rc_dummy() { return RC_DUMMY; }
+
+// tile_order_kernel over n_tiles lengths: order[] receives the tiles in the order of decreasing length
+extern "C" hipError_t eh_tile_order(int n_tiles, const uint32_t *stream_len, uint32_t *order) {
+  if (n_tiles < 1) return hipErrorInvalidValue;
+  DevBufs b;
+  uint32_t *d_len, *d_order;
+  EH_TRY(b.alloc(&d_len, (size_t)n_tiles, stream_len));
+  EH_TRY(b.alloc(&d_order, (size_t)n_tiles));
+  hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, 0, n_tiles, d_len, d_order);
+  EH_TRY(hipGetLastError());
+  EH_TRY(hipDeviceSynchronize());
+  return hipMemcpy(order, d_order, (size_t)n_tiles * 4, hipMemcpyDeviceToHost);
+}
+
+// One launch of rangecode{2,4}_tiles_kernel over tiles [tile0, tile0 + n_tiles) of arrays that hold tile0 + n_tiles tiles:
+//   streams     (tile0 + n_tiles) x stream_cap entries     stream_len, tile_combos, tile_bytes: tile0 + n_tiles each
+//   slots       (tile0 + n_tiles) x tile_slot_bytes 16-bit pre-carry entries (in / out: what the kernel does not write stays)
+//   order       null, or the launch-local permutation of 0 .. n_tiles - 1 the workgroups take their tiles in
+//   cdf_init    CL::TOTAL entries
+extern "C" hipError_t eh_rangecode(int stages, int n_tiles, int tile0, int stream_cap, int tile_slot_bytes, int disable_cdf_update,
+                                   const uint16_t *cdf_init, const uint32_t *streams, const uint32_t *stream_len, const uint32_t *tile_combos,
+                                   const uint32_t *order, uint16_t *slots, uint32_t *tile_bytes) {
+  // the stream is read in whole batches up to the wave's longest tile: its capacity must be a multiple of the batch
+  if ((stages != 2 && stages != 4) || n_tiles < 1 || tile0 < 0 || stream_cap < RC_BATCH || stream_cap % RC_BATCH || tile_slot_bytes < 1)
+    return hipErrorInvalidValue;
+  const size_t total = (size_t)tile0 + (size_t)n_tiles;
+  for (size_t t = (size_t)tile0; t < total; t++)
+    for (int k = 0; k < MAX_COMBOS; k++) {
+      const uint32_t c = (tile_combos[t] >> (8 * k)) & 0xFFu;
+      if (c != 0xFFu && c >= 10u) return hipErrorInvalidValue;   // (tx size 0..4) x 2 plane types
+    }
+  if (order) {
+    std::vector<char> seen((size_t)n_tiles, 0);
+    for (int i = 0; i < n_tiles; i++) {
+      if (order[i] >= (uint32_t)n_tiles || seen[order[i]]) return hipErrorInvalidValue;
+      seen[order[i]] = 1;
+    }
+  }
+  Av1miDevParams P;
+  memset(&P, 0, sizeof(P));
+  P.stream_cap = stream_cap;
+  P.tile_slot_bytes = tile_slot_bytes;
+  P.disable_cdf_update = disable_cdf_update;
+  DevBufs b;
+  uint16_t *d_cdf, *d_slots;
+  uint32_t *d_streams, *d_len, *d_combos, *d_bytes, *d_order = nullptr;
+  EH_TRY(b.alloc(&d_cdf, (size_t)CL::TOTAL, cdf_init));
+  EH_TRY(b.alloc(&d_streams, total * (size_t)stream_cap, streams));
+  EH_TRY(b.alloc(&d_len, total, stream_len));
+  EH_TRY(b.alloc(&d_combos, total, tile_combos));
+  EH_TRY(b.alloc(&d_slots, total * (size_t)tile_slot_bytes, slots));
+  EH_TRY(b.alloc(&d_bytes, total, tile_bytes));
+  if (order) EH_TRY(b.alloc(&d_order, (size_t)n_tiles, order));
+  const int n_groups = (n_tiles + 63) / 64;
+  if (stages == 4)
+    hipLaunchKernelGGL(rangecode4_tiles_kernel, dim3(n_groups), dim3(256), 0, 0, P, n_tiles, d_cdf, d_streams, d_len, d_combos,
+                       reinterpret_cast<uint8_t *>(d_slots), d_bytes, d_order, tile0);
+  else
+    hipLaunchKernelGGL(rangecode2_tiles_kernel, dim3(n_groups), dim3(128), 0, 0, P, n_tiles, d_cdf, d_streams, d_len, d_combos,
+                       reinterpret_cast<uint8_t *>(d_slots), d_bytes, d_order, tile0);
+  EH_TRY(hipGetLastError());
+  EH_TRY(hipDeviceSynchronize());
+  EH_TRY(hipMemcpy(slots, d_slots, total * (size_t)tile_slot_bytes * 2, hipMemcpyDeviceToHost));
+  return hipMemcpy(tile_bytes, d_bytes, total * 4, hipMemcpyDeviceToHost);
+}
+
+#else
+
+// frame_layout_kernel + chunk_layout_kernel, then pack_tiles_kernel, over n_frames frames of tile_rows x tile_cols tiles:
+//   slots        n_frames x tiles x tile_slot_bytes 16-bit pre-carry entries     tile_bytes: n_frames x tiles
+//   hdr_blob     seq_hdr_bytes + n_frames x hdr_slot_bytes
+//   out          out_cap bytes (in / out: what the packing does not write stays)
+//   tile_off, frame_size, payload_size: outputs of n_frames x tiles, n_frames, n_frames; frame_off: n_frames + 1; overflow: the flag
+// The packing is launched whatever the flag says (it must then write nothing), as long as no tile is more than one entry past its
+// slot and the layout fits `out`.
+extern "C" hipError_t eh_pack(int n_frames, int tile_rows, int tile_cols, int tile_slot_bytes, int tile_size_bytes, int keyint,
+                              int seq_hdr_bytes, int frame_hdr_bytes, int inter_hdr_bytes, int hdr_slot_bytes, const uint16_t *slots,
+                              const uint32_t *tile_bytes, const uint8_t *hdr_blob, uint8_t *out, size_t out_cap, uint32_t *tile_off,
+                              uint32_t *frame_size, uint32_t *payload_size, unsigned long long *frame_off, int *overflow) {
+  if (n_frames < 1 || tile_rows < 1 || tile_cols < 1 || tile_slot_bytes < 1 || tile_size_bytes < 1 || tile_size_bytes > 4 || keyint < 1 ||
+      seq_hdr_bytes < 0 || frame_hdr_bytes < 0 || inter_hdr_bytes < 0 || frame_hdr_bytes > hdr_slot_bytes || inter_hdr_bytes > hdr_slot_bytes)
+    return hipErrorInvalidValue;
+  const size_t nt = (size_t)tile_rows * (size_t)tile_cols, ntot = (size_t)n_frames * nt;
+  Av1miDevParams P;
+  memset(&P, 0, sizeof(P));
+  P.n_frames = n_frames;
+  P.tile_rows = tile_rows;
+  P.tile_cols = tile_cols;
+  P.tile_slot_bytes = tile_slot_bytes;
+  P.tile_size_bytes = tile_size_bytes;
+  P.keyint = keyint;
+  P.seq_hdr_bytes = seq_hdr_bytes;
+  P.frame_hdr_bytes = frame_hdr_bytes;
+  P.inter_hdr_bytes = inter_hdr_bytes;
+  P.hdr_slot_bytes = hdr_slot_bytes;
+  DevBufs b;
+  uint16_t *d_slots;
+  uint32_t *d_bytes, *d_toff, *d_fsize, *d_pay;
+  unsigned long long *d_foff;
+  uint8_t *d_hdr, *d_out;
+  int *d_ovf;
+  // (+ one entry: a tile one entry past its slot - the overflow case - reads no further than that)
+  EH_TRY(b.alloc(&d_slots, ntot * (size_t)tile_slot_bytes + 1));
+  EH_TRY(hipMemcpy(d_slots, slots, ntot * (size_t)tile_slot_bytes * 2, hipMemcpyHostToDevice));
+  EH_TRY(b.alloc(&d_bytes, ntot, tile_bytes));
+  EH_TRY(b.alloc(&d_toff, ntot));
+  EH_TRY(b.alloc(&d_fsize, (size_t)n_frames));
+  EH_TRY(b.alloc(&d_pay, (size_t)n_frames));
+  EH_TRY(b.alloc(&d_foff, (size_t)n_frames + 1));
+  EH_TRY(b.alloc(&d_hdr, (size_t)seq_hdr_bytes + (size_t)n_frames * (size_t)hdr_slot_bytes, hdr_blob));
+  EH_TRY(b.alloc(&d_out, out_cap + 4096));   // (+ 4 KB the caller never sees: slack behind the buffer)
+  EH_TRY(hipMemcpy(d_out, out, out_cap, hipMemcpyHostToDevice));
+  EH_TRY(b.alloc(&d_ovf, 1));
+  hipLaunchKernelGGL(frame_layout_kernel, dim3(n_frames), dim3(256), 0, 0, P, d_bytes, d_toff, d_fsize, d_pay, d_ovf);
+  hipLaunchKernelGGL(chunk_layout_kernel, dim3(1), dim3(64), 0, 0, n_frames, d_fsize, d_foff);
+  EH_TRY(hipGetLastError());
+  EH_TRY(hipDeviceSynchronize());
+  EH_TRY(hipMemcpy(tile_off, d_toff, ntot * 4, hipMemcpyDeviceToHost));
+  EH_TRY(hipMemcpy(frame_size, d_fsize, (size_t)n_frames * 4, hipMemcpyDeviceToHost));
+  EH_TRY(hipMemcpy(payload_size, d_pay, (size_t)n_frames * 4, hipMemcpyDeviceToHost));
+  EH_TRY(hipMemcpy(frame_off, d_foff, ((size_t)n_frames + 1) * 8, hipMemcpyDeviceToHost));
+  EH_TRY(hipMemcpy(overflow, d_ovf, sizeof(int), hipMemcpyDeviceToHost));
+  // a tile more than one entry past its slot (the sentinel of a stream that outgrew its capacity) leaves sizes and offsets
+  // meaningless: the packing is then not launched at all
+  bool bounded = true;
+  for (size_t i = 0; i < ntot; i++) bounded = bounded && tile_bytes[i] <= (uint32_t)tile_slot_bytes + 1u;
+  if (!bounded) return *overflow ? hipSuccess : hipErrorInvalidValue;
+  if (frame_off[n_frames] > out_cap) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(pack_tiles_kernel, dim3((unsigned)ntot), dim3(64), 0, 0, P, reinterpret_cast<const uint8_t *>(d_slots), d_bytes, d_toff,
+                     d_pay, d_foff, d_hdr, d_out, d_ovf);
+  EH_TRY(hipGetLastError());
+  EH_TRY(hipDeviceSynchronize());
+  return hipMemcpy(out, d_out, out_cap, hipMemcpyDeviceToHost);
+}
+
+#endif

@@ -475,6 +475,113 @@ def test_alternative_schedules_give_the_same_bytes(av1mi, oracle, monkeypatch):
     assert outs[0][0] == b"".join(tus) and outs[0][2] == b"".join(raw_of(r, bd) for r in recs)
 
 
+def _set_rc_env(monkeypatch, env):
+    for k in ("AV1MI_RC_STAGES", "AV1MI_RC_SORT", "AV1MI_ENTROPY_GROUP"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+def _oracle_tus(oracle, frames, w, h, bd, keyint, fg=0, **kw):
+    """the oracle's temporal units of a chunk whose first frame is frame 0 of the clip; fg = N: the film-grain table of --film-grain N
+    with the ABI's grain_seed per frame"""
+    tus, ref, prev = [], None, None
+    for t, f in enumerate(frames):
+        key = t % keyint == 0
+        if fg:
+            kw.update(film_grain=1, fg_y_scaling=2 * fg, fg_c_scaling=fg, fg_seed=(7391 + 173 * t) & 0xFFFF)
+        tu, rec, _ = oracle.encode_frame(oracle.default_config(w, h, bd, **kw), f, with_seq_hdr=key, ref=None if key else ref,
+                                         prev_src=None if key else prev)
+        tus.append(tu)
+        ref, prev = rec, f
+    return tus
+
+
+def test_stress_carries_and_long_tiles_under_both_range_coder_forms(av1mi, oracle, monkeypatch):
+    """The noise content of test_stress_carries_and_long_tiles through each form of the range coder, forced, with the tiles in the
+    order of decreasing length: every frame equals the oracle, and each fresh context takes the capacity re-run path at CQ 4"""
+    rng = np.random.default_rng(99)
+    w, h, n = 328, 248, 6
+    frames = [[rng.integers(0, 256, (h, w)).astype(np.uint16), rng.integers(0, 256, (h // 2, w // 2)).astype(np.uint16),
+               rng.integers(0, 256, (h // 2, w // 2)).astype(np.uint16)] for _ in range(n)]
+    raw = b"".join(raw_of(f, 8) for f in frames)
+    confs = ((4, 5), (12, 4), (20, 3))
+    refs = {}
+    for cq, bs in confs:
+        cfg = oracle.default_config(w, h, 8, min_bs_log2=bs, max_bs_log2=bs, base_q_idx=av1mi.cq_to_qindex(cq))
+        refs[cq] = [oracle.encode_frame(cfg, f)[0] for f in frames]
+    for form in ("2", "4"):
+        _set_rc_env(monkeypatch, {"AV1MI_RC_STAGES": form, "AV1MI_RC_SORT": "1"})
+        with av1mi.Context(0) as c:
+            for cq, bs in confs:
+                data, sizes, rep, _ = c.encode_chunk(av1mi.default_params(w, h, 8, cq_level=cq, block_log2=bs), raw, n)
+                assert list(sizes) == [len(t) for t in refs[cq]], (form, cq)
+                assert data == b"".join(refs[cq]), (form, cq)
+                if cq == 4:
+                    assert rep.max_tile_symbols > 16384 and rep.cap_scale > 1, form
+    _set_rc_env(monkeypatch, {})
+
+
+@pytest.mark.parametrize("conf", ["ippp_static_cdfs", "tiles_2x2_lr_qm_grain", "entropy_groups"])
+def test_range_coder_forms_and_orders_on_inter_chunks(av1mi, oracle, monkeypatch, conf):
+    """Both forms of the range coder (AV1MI_RC_STAGES 2 / 4), each in the natural and the length-sorted tile order (AV1MI_RC_SORT 0 / 1),
+    on what the all-key tests do not reach: inter syntax with static CDFs; 2 x 2-superblock tiles with switchable restoration,
+    quantiser matrices and film grain; an inter chunk entropy-coded in groups of two frames (launches whose first tile is not the
+    chunk's first, with a tile order).  Every run equals the oracle."""
+    if conf == "ippp_static_cdfs":
+        w, h, bd, n, keyint, fg = 200, 120, 8, 5, 240, 0
+        pkw, okw, env = dict(block_log2=5, cdf_update=0), dict(min_bs_log2=5, max_bs_log2=5, disable_cdf_update=1), {}
+    elif conf == "tiles_2x2_lr_qm_grain":
+        w, h, bd, n, keyint, fg, cq = 328, 248, 10, 4, 2, 20, 30
+        qidx = av1mi.cq_to_qindex(cq)
+        lvl = oracle.qm_level(qidx, 1, 15)
+        pkw = dict(block_log2=4, tile_sb=2, enable_lr=2, enable_qm=1, qm_min=1, qm_max=15, film_grain=fg, cq_level=cq)
+        okw = dict(min_bs_log2=4, max_bs_log2=4, tile_w_sb=2, tile_h_sb=2, enable_lr=2, enable_qm=1, qm_y=lvl, qm_uv=lvl, base_q_idx=qidx)
+        env = {}
+    else:
+        w, h, bd, n, keyint, fg = 200, 120, 8, 7, 240, 0
+        pkw, okw, env = dict(block_log2=5, subpel=1), dict(min_bs_log2=5, max_bs_log2=5, subpel=1), {"AV1MI_ENTROPY_GROUP": "2"}
+    frames = [oracle.synthclip_frame(w, h, bd, seed=620 + w, t=t) for t in range(n)]
+    raw = b"".join(raw_of(f, bd) for f in frames)
+    tus = _oracle_tus(oracle, frames, w, h, bd, keyint, fg, **okw)
+    p = av1mi.default_params(w, h, bd, keyint=keyint, **pkw)
+    for stages in ("2", "4"):
+        for sort in ("0", "1"):
+            _set_rc_env(monkeypatch, dict(env, AV1MI_RC_STAGES=stages, AV1MI_RC_SORT=sort))
+            with av1mi.Context(0) as c:
+                data, sizes, _, _ = c.encode_chunk(p, raw, n)
+            assert list(sizes) == [len(t) for t in tus], (stages, sort)
+            assert data == b"".join(tus), (stages, sort)
+    _set_rc_env(monkeypatch, {})
+
+
+def test_production_point_where_the_default_is_the_two_stage_form(av1mi, oracle, monkeypatch):
+    """The reference's production point on a 1080p chunk of 40 frames (10-bit, keyint 240, CQ 8 -> base_q_idx 32, the reference's
+    tools): 40 x 510 tiles are 319 workgroups and the quantiser index is below 64, so the launcher's default is the two-stage form.
+    The default's bytes equal forced form 4 and forced form 2 in the sorted order; the first two temporal units equal the oracle
+    (frame i depends only on the frames before it)."""
+    w, h, bd, n, cq = 1920, 1080, 10, 40, 8
+    qidx = av1mi.cq_to_qindex(cq)
+    assert qidx < 64 and (n * 30 * 17 + 63) // 64 == 319
+    frames = [oracle.synthclip_frame(w, h, bd, seed=1080, t=t) for t in range(n)]
+    raw = b"".join(raw_of(f, bd) for f in frames)
+    p = av1mi.default_params(w, h, bd, keyint=240, cq_level=cq, film_grain=20, enable_qm=1, qm_min=1, qm_max=15, subpel=1, deblock=1, enable_lr=2)
+    outs = []
+    for env in ({}, {"AV1MI_RC_STAGES": "4"}, {"AV1MI_RC_STAGES": "2", "AV1MI_RC_SORT": "1"}):
+        _set_rc_env(monkeypatch, env)
+        with av1mi.Context(0) as c:
+            data, sizes, _, _ = c.encode_chunk(p, raw, n)
+        outs.append((data, list(sizes)))
+    _set_rc_env(monkeypatch, {})
+    assert outs[1] == outs[0] and outs[2] == outs[0]
+    lvl = oracle.qm_level(qidx, 1, 15)
+    tus = _oracle_tus(oracle, frames[:2], w, h, bd, 240, 20, min_bs_log2=5, max_bs_log2=5, base_q_idx=qidx, subpel=1,
+                      deblock=1, enable_lr=2, enable_qm=1, qm_y=lvl, qm_uv=lvl)
+    data, sizes = outs[0]
+    assert sizes[:2] == [len(t) for t in tus]
+    assert data[:sizes[0] + sizes[1]] == b"".join(tus)
+
+
 def test_golden_inter_sequences_through_the_c_abi(av1mi, ctx, oracle, golden_sequences):
     """The dav1d-pinned inter sequences the GPU path can express (decision-driven, one-superblock tiles)."""
     n = 0

@@ -2,10 +2,11 @@
 tests of the building blocks, size-independent properties.  None of this needs a GPU."""
 import ctypes as C
 import hashlib
-import math
 
 import numpy as np
 import pytest
+
+from ec_ref import SpecDecoder
 
 
 def sha(planes):
@@ -101,55 +102,8 @@ def test_range_coder_roundtrip_against_spec_decoder(oracle):
     nbytes = L.av1o_ec_finish(C.byref(e))
     data = buf.raw[:nbytes]
 
-    # ---- spec decoder
-    class Dec:
-        def __init__(self, data):
-            self.bits = "".join("{:08b}".format(b) for b in data)
-            self.pos = 0
-            sz = len(data)
-            nb = min(sz * 8, 15)
-            v = self.f(nb)
-            self.value = ((1 << 15) - 1) ^ (v << (15 - nb))
-            self.range = 1 << 15
-            self.maxbits = 8 * sz - 15
-
-        def f(self, n):
-            v = int(self.bits[self.pos:self.pos + n], 2) if n else 0
-            self.pos += n
-            return v
-
-        def read(self, cdf, adapt=True):
-            N = len(cdf) - 1
-            cur = self.range
-            sym = -1
-            while True:
-                sym += 1
-                prev = cur
-                f = (1 << 15) - cdf[sym]
-                cur = ((self.range >> 8) * (f >> 6) >> 1) + 4 * (N - sym - 1)
-                if not self.value < cur:
-                    break
-            self.range = prev - cur
-            self.value -= cur
-            bits = 15 - (self.range.bit_length() - 1)
-            self.range <<= bits
-            nb = min(bits, max(0, self.maxbits))
-            new = self.f(nb)
-            self.value = (new << (bits - nb)) ^ (((self.value + 1) << bits) - 1)
-            self.maxbits -= bits
-            if adapt:
-                rate = 3 + (cdf[N] > 15) + (cdf[N] > 31) + min(int(math.log2(N)), 2)
-                tmp = 0
-                for i in range(N - 1):
-                    tmp = (1 << 15) if i == sym else tmp
-                    if tmp < cdf[i]:
-                        cdf[i] -= (cdf[i] - tmp) >> rate
-                    else:
-                        cdf[i] += (tmp - cdf[i]) >> rate
-                cdf[N] += cdf[N] < 32
-            return sym
-
-    d = Dec(data)
+    # ---- spec decoder (tests/ec_ref.py)
+    d = SpecDecoder(data)
     for k, s in seq:
         if k < 0:
             assert d.read([1 << 14, 1 << 15, 0], adapt=False) == s
