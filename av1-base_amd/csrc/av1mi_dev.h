@@ -78,12 +78,18 @@ struct Av1miDevParams {
   int lf_level[4], lf_level_inter[4], lf_sharpness;
   // loop restoration (luma Wiener, 64x64 units): literal bits that code candidate k's coefficients against the
   // reference RefLrWiener (both passes), MSB first in the low `lr_code_len[r][k]` bits
-  int enable_lr;
+  int enable_lr;                         // the frames' restoration type: 1 = RESTORE_WIENER, 2 = RESTORE_SWITCHABLE (any plane)
   int lr_code_len[4][3];                 // [reference: 0 = Wiener_Taps_Mid, r = candidate r-1][candidate]
   unsigned long long lr_code_bits[4][3];
   // enable_lr = 2: the same for a self-guided unit (lr_sgr_set + both weights against RefSgrXqd; reference 0 = Sgrproj_Xqd_Mid)
   int sgr_code_len[4][3];
   unsigned long long sgr_code_bits[4][3];
+  // av1mi_params.enable_lr 3 / 4: U and V are restored as well, with enable_lr's type, in 32x32 units
+  // (lr_uv_shift 1); unit choices and sums are then [frame][plane][unit], else [frame][unit].  A chroma Wiener unit codes taps 1
+  // and 2 of each pass only (tap 0 is 0): its bit strings, against the plane's RefLrWiener; self-guided units share luma's.
+  int lr_chroma;
+  int lr_code_len_uv[4][3];
+  unsigned long long lr_code_bits_uv[4][3];
 };
 
 // ---- partition: does the node of size 2^bsl at superblock-local (ox, oy) split?  One rule for every kernel that

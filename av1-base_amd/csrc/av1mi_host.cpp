@@ -97,6 +97,7 @@ struct Resolved {
   int sb_cols, sb_rows;
   int tile_sb, tile_cols, tile_rows;  // tiles of tile_sb x tile_sb superblocks (1, or 2 beyond 64 superblocks either way)
   int qm_level;                       // quantiser-matrix level of all planes (15 = flat); only meaningful with p.enable_qm
+  int lr_chroma;                      // enable_lr 3 / 4: U and V restored as well (p.enable_lr then holds the type: 1 / 2)
 };
 
 // aom's quantizer_to_qindex[] (CQ level -> base_q_idx); 30 -> 120
@@ -124,8 +125,11 @@ int resolve(const av1mi_params *in, Resolved *r) {
   r->qidx = kQuantizerToQindex[p.cq_level];
   r->dc_q = p.bit_depth == 8 ? av1_dc_q8[r->qidx] : av1_dc_q10[r->qidx];
   r->ac_q = p.bit_depth == 8 ? av1_ac_q8[r->qidx] : av1_ac_q10[r->qidx];
-  if (p.subpel > 1 || p.enable_lr > 2 || p.color_range > 1 || p.intra_angle_delta > 1 || p.intra_edge_filter > 1 || p.cfl > 1 || p.tx_search > 1) return AV1MI_E_INVALID_ARG;
+  if (p.subpel > 1 || p.enable_lr > 4 || p.color_range > 1 || p.intra_angle_delta > 1 || p.intra_edge_filter > 1 || p.cfl > 1 || p.tx_search > 1) return AV1MI_E_INVALID_ARG;
   if (p.partition_search > 1 || p.me_presearch > 1) return AV1MI_E_INVALID_ARG;
+  // enable_lr 3 / 4 = 1 / 2 on all three planes: the frames' restoration type plus the chroma flag
+  r->lr_chroma = p.enable_lr >= 3;
+  if (r->lr_chroma) p.enable_lr -= 2;
   if (p.min_block_log2 == 0) p.min_block_log2 = 3;
   if (p.min_block_log2 < 3 || p.min_block_log2 > p.block_log2) return AV1MI_E_INVALID_ARG;
   if (p.color_primaries > 255 || p.transfer_characteristics > 255 || p.matrix_coefficients > 255) return AV1MI_E_INVALID_ARG;
@@ -286,9 +290,11 @@ std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint
       b.put(p.cdef_uv_pri, 4); b.put(p.cdef_uv_sec, 2);
     }
   }
-  if (p.enable_lr) {  // lr_params (§5.9.20): luma RESTORE_WIENER (lr_type 2), chroma none, lr_unit_shift 0 = 64x64 units
-    b.put(p.enable_lr == 2 ? 1 : 2, 2); b.put(0, 2); b.put(0, 2);  // luma lr_type: 1 = RESTORE_SWITCHABLE, 2 = RESTORE_WIENER
+  if (p.enable_lr) {  // lr_params (§5.9.20): lr_type per plane, lr_unit_shift 0 = 64x64 luma units
+    const uint32_t t = p.enable_lr == 2 ? 1 : 2;  // lr_type: 1 = RESTORE_SWITCHABLE, 2 = RESTORE_WIENER
+    b.put(t, 2); b.put(r.lr_chroma ? t : 0, 2); b.put(r.lr_chroma ? t : 0, 2);  // Y, U, V: chroma the luma type with enable_lr 3 / 4
     b.put(0, 1);
+    if (r.lr_chroma) b.put(1, 1);  // lr_uv_shift: 32x32 chroma units, the picture area of a luma unit
   }
   b.put(0, 1);  // tx_mode_select = 0: TX_MODE_LARGEST
   if (inter) b.put(0, 1);  // reference_select = 0
@@ -344,6 +350,8 @@ void lr_put_signed_ref(BitString &b, int low, int high, int k, int r, int v) {
   else lr_put_subexp(b, mx, k, lr_recenter(mx - 1 - rr, mx - 1 - x));
 }
 const int8_t kWienerCand[3][3] = { { 0, 0, -4 }, { 1, -3, -6 }, { 3, -7, 15 } };  // == lr_kernel.hip, oracle/av1o_lr.c
+// chroma (enable_lr 3 / 4; tap 0 is 0 and not coded, §5.11.58)
+const int8_t kWienerCandUV[3][3] = { { 0, 0, -4 }, { 0, 0, 16 }, { 0, 6, 20 } };  // == lr_kernel.hip
 const int8_t kSgrCand[3][3] = { { 9, 31, 31 }, { 9, 0, 31 }, { 9, 31, 95 } };     // { lr_sgr_set, xqd0, xqd1 }: == lr_kernel.hip, oracle/av1o_lr.c
 // self-guided unit (§5.11.58): lr_sgr_set L(4), then the two weights against RefSgrXqd (ref 0 = Sgrproj_Xqd_Mid at the tile
 // start, r = candidate r-1: the previous self-guided unit of the tile).  Every candidate uses set 9, whose radii are both
@@ -361,6 +369,14 @@ BitString lr_code_of(int ref, int cand) {
   BitString b;
   for (int pass = 0; pass < 2; pass++)
     for (int j = 0; j < 3; j++) lr_put_signed_ref(b, tmin[j], tmax[j] + 1, tk[j], ref ? kWienerCand[ref - 1][j] : mid[j], kWienerCand[cand][j]);
+  return b;
+}
+// the same for a chroma unit: taps 1 and 2 of each pass, against the plane's RefLrWiener
+BitString lr_code_of_uv(int ref, int cand) {
+  static const int tmin[3] = { -5, -23, -17 }, tmax[3] = { 10, 8, 46 }, tk[3] = { 1, 2, 3 }, mid[3] = { 3, -7, 15 };
+  BitString b;
+  for (int pass = 0; pass < 2; pass++)
+    for (int j = 1; j < 3; j++) lr_put_signed_ref(b, tmin[j], tmax[j] + 1, tk[j], ref ? kWienerCandUV[ref - 1][j] : mid[j], kWienerCandUV[cand][j]);
   return b;
 }
 
@@ -585,10 +601,11 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     HIPCHK(c, ws_alloc(w, w.d_cdef_idx, nf * nsb));
     HIPCHK(c, ws_alloc(w, w.d_cdef_sel, nf * 8));
   }
-  if (p.enable_lr && !w.d_cd) {
+  if (p.enable_lr && !w.d_cd) {   // unit choices and sums for three planes (enable_lr 3 / 4), whichever value this chunk has: the
+                                  // buffers stay with the geometry while enable_lr changes
     HIPCHK(c, ws_alloc(w, w.d_cd, nf * frame_bytes));
-    HIPCHK(c, ws_alloc(w, w.d_lrc, nf * nsb + 64));
-    HIPCHK(c, ws_alloc(w, w.d_lrsse, (nf * nsb + 64) * 8 * sizeof(unsigned long long)));
+    HIPCHK(c, ws_alloc(w, w.d_lrc, 3 * nf * nsb + 64));
+    HIPCHK(c, ws_alloc(w, w.d_lrsse, (3 * nf * nsb + 64) * 8 * sizeof(unsigned long long)));
   }
   w.res = r;
   if (p.enable_qm && r.qm_level < 15) {
@@ -647,10 +664,12 @@ Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const
   P.hdr_slot_bytes = 512;
   for (int i = 0; i < 4; i++) { P.lf_level[i] = deblock_level(r, true); P.lf_level_inter[i] = deblock_level(r, false); }
   P.enable_lr = (int)p.enable_lr;
+  P.lr_chroma = r.lr_chroma;
   for (int rf = 0; rf < 4; rf++)
     for (int k = 0; k < 3; k++) {
       const BitString b = lr_code_of(rf, k); P.lr_code_len[rf][k] = b.len; P.lr_code_bits[rf][k] = b.bits;
       const BitString g = sgr_code_of(rf, k); P.sgr_code_len[rf][k] = g.len; P.sgr_code_bits[rf][k] = g.bits;
+      const BitString u = lr_code_of_uv(rf, k); P.lr_code_len_uv[rf][k] = u.len; P.lr_code_bits_uv[rf][k] = u.bits;
     }
   return P;
 }
@@ -1047,7 +1066,8 @@ static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
   const size_t fbytes = (size_t)P.frame_samples * (P.bit_depth > 8 ? 2 : 1), nb8 = (size_t)P.b8_rows * P.b8_cols, nsb = (size_t)P.sb_rows * P.sb_cols;
   const bool lr = P.enable_lr != 0;
   uint8_t *cdef_out = (uint8_t *)(lr ? w.d_cd : w.d_fin);   // with loop restoration CDEF writes d_cd and the restored frame goes to d_fin
-  const size_t upf = (size_t)std::max(1, (P.true_h + 32) / 64) * std::max(1, (P.true_w + 32) / 64);   // restoration units per frame
+  // restoration units per frame, of all restored planes (choices and sums are [frame][plane][unit])
+  const size_t upf = (size_t)(P.lr_chroma ? 3 : 1) * std::max(1, (P.true_h + 32) / 64) * std::max(1, (P.true_w + 32) / 64);
   // Motion search is open loop (source against previous source): all inter frames at once, on the second stream,
   // beside the chain below; the first inter frame's reconstruction waits for it.
   HIPCHK(c, hipStreamWaitEvent(s2, c->ev[EV_SRC_READY], 0));  // the source frames are in HBM

@@ -716,8 +716,9 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
   // instantiation skips the other's frames.
   const int inter_frame = INTER;
   if (av1mi_frame_is_inter(P, f) != (int)INTER) return;
-  int lr_prev = 0;  // RefLrWiener of the tile: 0 = Wiener_Taps_Mid, k = candidate k-1 (the last unit coded with a Wiener filter)
-  int sgr_prev = 0; // RefSgrXqd of the tile: 0 = Sgrproj_Xqd_Mid, k = self-guided candidate k-1 (the last self-guided unit)
+  // 2 bits per plane (bits 2 p .. 2 p + 1: plane p):
+  int lr_prev = 0;  // RefLrWiener of the tile: 0 = Wiener_Taps_Mid, k = candidate k-1 (the plane's last unit coded with a Wiener filter)
+  int sgr_prev = 0; // RefSgrXqd of the tile: 0 = Sgrproj_Xqd_Mid, k = self-guided candidate k-1 (the plane's last self-guided unit)
 #pragma nounroll
   for (int si = 0; si < TSB * TSB; si++) {
   const int sbr = tr * TSB + si / TSB, sbc = tc * TSB + si % TSB;
@@ -739,25 +740,34 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
   }
 
   if (P.enable_lr) {
-    // read_lr (§5.11.57): the luma restoration unit whose origin lies in this superblock (units = 64x64, offset by 8
-    // rows, so unit (r, c) starts in superblock (r, c)); its coefficients are coded against RefLrWiener, which starts
-    // every tile at Wiener_Taps_Mid and follows the units coded with a filter
+    // read_lr (§5.11.57): the restoration units whose origin lies in this superblock, Y and (enable_lr 3 / 4) U, V.  Luma units are
+    // 64x64 offset by 8 rows, chroma units 32x32 offset by 4 (lr_uv_shift 1), so unit (r, c) of every plane starts in superblock
+    // (r, c), and the signalled size being even every plane has the same unit grid.  The coefficients are coded against the plane's
+    // RefLrWiener / RefSgrXqd, which start every tile at their mid values and follow the plane's units coded with a filter; the
+    // three CDFs are shared by the planes
     const int urows = imax((P.true_h + 32) / 64, 1), ucols = imax((P.true_w + 32) / 64, 1);  // from the signalled size
     if (sbr < urows && sbc < ucols) {
-      const int ch = uni(lr_choice[(size_t)f * urows * ucols + sbr * ucols + sbc]);
-      // choice: 0 = off, 1..3 = Wiener candidate, 4..6 = self-guided candidate (RESTORE_SWITCHABLE frames only)
-      if (P.enable_lr == 2) sym_wide(y, lane, adapt, ch == 0 ? 0 : (ch <= 3 ? 1 : 2), FULL ? CL::RESTORE_SW : CC::RESTORE_SW, 3);
-      else sym_wide(y, lane, adapt, ch != 0, FULL ? CL::USE_WIENER : CC::USE_WIENER, 2);
-      if (ch > 3) {
-        const int len = P.sgr_code_len[sgr_prev][ch - 4];
-        const unsigned long long bits = P.sgr_code_bits[sgr_prev][ch - 4];
-        for (int i = len - 1; i >= 0; i--) emit1(y, lane, ENT_LITERAL((int)((bits >> i) & 1)));
-        sgr_prev = ch - 3;
-      } else if (ch) {
-        const int len = P.lr_code_len[lr_prev][ch - 1];
-        const unsigned long long bits = P.lr_code_bits[lr_prev][ch - 1];
-        for (int i = len - 1; i >= 0; i--) emit1(y, lane, ENT_LITERAL((int)((bits >> i) & 1)));
-        lr_prev = ch;
+      const int nplanes = P.lr_chroma ? 3 : 1;
+#pragma nounroll
+      for (int pl = 0; pl < nplanes; pl++) {
+        // choice [frame][plane][unit]: 0 = off, 1..3 = Wiener candidate, 4..6 = self-guided candidate (RESTORE_SWITCHABLE frames only)
+        const int ch = uni(lr_choice[((size_t)f * nplanes + pl) * urows * ucols + sbr * ucols + sbc]);
+        if (P.enable_lr == 2) sym_wide(y, lane, adapt, ch == 0 ? 0 : (ch <= 3 ? 1 : 2), FULL ? CL::RESTORE_SW : CC::RESTORE_SW, 3);
+        else sym_wide(y, lane, adapt, ch != 0, FULL ? CL::USE_WIENER : CC::USE_WIENER, 2);
+        const int sh = 2 * pl;
+        if (ch > 3) {
+          const int rf = (sgr_prev >> sh) & 3;
+          const int len = P.sgr_code_len[rf][ch - 4];
+          const unsigned long long bits = P.sgr_code_bits[rf][ch - 4];
+          for (int i = len - 1; i >= 0; i--) emit1(y, lane, ENT_LITERAL((int)((bits >> i) & 1)));
+          sgr_prev = (sgr_prev & ~(3 << sh)) | ((ch - 3) << sh);
+        } else if (ch) {
+          const int rf = (lr_prev >> sh) & 3;
+          const int len = pl ? P.lr_code_len_uv[rf][ch - 1] : P.lr_code_len[rf][ch - 1];
+          const unsigned long long bits = pl ? P.lr_code_bits_uv[rf][ch - 1] : P.lr_code_bits[rf][ch - 1];
+          for (int i = len - 1; i >= 0; i--) emit1(y, lane, ENT_LITERAL((int)((bits >> i) & 1)));
+          lr_prev = (lr_prev & ~(3 << sh)) | (ch << sh);
+        }
       }
     }
   }

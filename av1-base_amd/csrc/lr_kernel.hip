@@ -1,4 +1,5 @@
-// lr_kernel.hip - loop restoration: per-unit Wiener decision and filter on luma.
+// lr_kernel.hip - loop restoration: per-unit Wiener decision and filter on luma, and on chroma with
+// enable_lr = 3 / 4.
 //
 // Replaces the restoration-filter search and application inside the SVT-AV1 worker behind `run_av1an`
 // (/root/reference/crates/daemon/src/encode/av1an.rs:126-139).  Normative part: AV1 spec §7.17.3 (units offset by 8 luma
@@ -10,14 +11,17 @@
 // LDS as int16 (the spec's clamp keeps it in 16 bits for 8/10 bit), the vertical pass reads 7 LDS rows per sample.  The
 // three candidates are evaluated for their SSE only (with enable_lr = 2 also three self-guided candidates: the A/B grids of
 // both box-filter passes go to LDS per stripe section, see sgr_grid); the winner is applied in a last pass that writes the final
-// reconstruction (chroma is copied: FrameRestorationType = NONE).  Algorithmic HBM bytes: CDEF frame read + pre-CDEF rows
-// at stripe edges + source read + final write = ~3*L*b + N*b per frame.
+// reconstruction (with enable_lr = 1 / 2 chroma is copied: FrameRestorationType = NONE; with 3 / 4 the chroma units are decided
+// and filtered in the same two launches, see lr_chroma).  Algorithmic HBM bytes: CDEF frame read + pre-CDEF rows at stripe edges
+// + source read + final write = ~3*L*b + N*b per frame (~3*N*b with the chroma units).
 #include <hip/hip_runtime.h>
 #include "av1mi_dev.h"
 
 namespace {
 
 __constant__ int8_t c_wiener_cand[3][3] = { { 0, 0, -4 }, { 1, -3, -6 }, { 3, -7, 15 } };
+// chroma (enable_lr = 3 / 4): §5.11.58 codes taps 1 and 2 of a chroma filter, tap 0 is 0
+__constant__ int8_t c_wiener_cand_uv[3][3] = { { 0, 0, -4 }, { 0, 0, 16 }, { 0, 6, 20 } };  // == av1mi_host.cpp kWienerCandUV
 
 // a wave works on at most 16 rows (LR_SLICES): the source window of those rows (3 more above, 2..3 below, 3 columns either
 // side; get_source_sample's stripe rule applied per row) is staged once and both filters read it from LDS
@@ -46,8 +50,17 @@ __device__ __forceinline__ void taps_of(int k, int *f) {
   const int c0 = c_wiener_cand[k][0], c1 = c_wiener_cand[k][1], c2 = c_wiener_cand[k][2];
   f[0] = f[6] = c0; f[1] = f[5] = c1; f[2] = f[4] = c2; f[3] = 128 - 2 * (c0 + c1 + c2);
 }
+__device__ __forceinline__ void taps_of_uv(int k, int *f) {
+  const int c1 = c_wiener_cand_uv[k][1], c2 = c_wiener_cand_uv[k][2];
+  f[0] = f[6] = 0; f[1] = f[5] = c1; f[2] = f[4] = c2; f[3] = 128 - 2 * (c1 + c2);
+}
 __device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// lanes 0-31 get the sum of lanes 0-31, lanes 32-63 that of lanes 32-63 (two chroma units side by side)
+__device__ __forceinline__ unsigned long long half_sum64(unsigned long long v) {
+  for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
 
@@ -66,14 +79,14 @@ __constant__ int8_t c_sgr_cand[3][3] = { { 9, 31, 31 }, { 9, 0, 31 }, { 9, 31, 9
 __shared__ uint16_t g_sgrA0[(SGR_ROWS + 2) / 2][66], g_sgrA1[SGR_ROWS + 2][66];
 __shared__ int32_t g_sgrB0[(SGR_ROWS + 2) / 2][66], g_sgrB1[SGR_ROWS + 2][66];
 
-// get_source_sample (§7.17.6): the row of the frame that supplies restoration input row y of the stripe [s0, s1]
+// get_source_sample (§7.17.6): the row of a plane of H rows that supplies restoration input row y of the stripe [s0, s1]
 template <typename PIX>
-__device__ __forceinline__ const PIX *lr_row(const Av1miDevParams &P, const PIX *cdef, const PIX *pre, int y, int s0, int s1) {
-  int yy = clampi(y, 0, P.true_h - 1);
+__device__ __forceinline__ const PIX *lr_row(const PIX *cdef, const PIX *pre, int y, int s0, int s1, int H, int stride) {
+  int yy = clampi(y, 0, H - 1);
   const PIX *fr = cdef;
   if (yy < s0) { yy = yy > s0 - 2 ? yy : s0 - 2; fr = pre; }
   else if (yy > s1) { yy = yy < s1 + 2 ? yy : s1 + 2; fr = pre; }
-  return fr + (size_t)yy * P.stride_y;
+  return fr + (size_t)yy * stride;
 }
 
 // A and B from the box sums (sum of samples b, of squares a) of a (2r+1)^2 window
@@ -91,15 +104,17 @@ __device__ __forceinline__ void sgr_ab(uint32_t a, uint32_t b, int bd, uint32_t 
 }
 
 // Source window of a unit section for the box sums: restoration input rows ya - 3 .. yb + 2 (get_source_sample's stripe rule
-// per row), columns xs - 3 .. xs + 66 (clamped to the frame) -> win[row - (ya - 3)][col - (xs - 3)], all loads independent.
+// per row), columns xs - 3 .. xs + 66 (clamped to the plane of W x H samples) -> win[row - (ya - 3)][col - (xs - 3)], all loads
+// independent.
 template <typename PIX>
-__device__ __forceinline__ void lr_stage(const Av1miDevParams &P, const PIX *cdef, const PIX *pre, int xs, int ya, int yb, int s0, int s1, int lane) {
+__device__ __forceinline__ void lr_stage(const PIX *cdef, const PIX *pre, int xs, int ya, int yb, int s0, int s1, int W, int H, int stride,
+                                         int lane) {
   uint16_t (*win)[72] = g_win;
-  const int rows = yb - ya + 6, W = P.true_w;
+  const int rows = yb - ya + 6;
 #pragma unroll 8
   for (int p = lane; p < rows * 70; p += 64) {
     const int i = p / 70, j = p - i * 70;
-    win[i][j] = (uint16_t)lr_row<PIX>(P, cdef, pre, ya - 3 + i, s0, s1)[clampi(xs - 3 + j, 0, W - 1)];
+    win[i][j] = (uint16_t)lr_row<PIX>(cdef, pre, ya - 3 + i, s0, s1, H, stride)[clampi(xs - 3 + j, 0, W - 1)];
   }
 }
 
@@ -188,20 +203,166 @@ __device__ __forceinline__ int sgr_blend(int cur, int flt0, int flt1, int w0, in
   return clampi((v + (1 << 10)) >> 11, 0, maxv);
 }
 
+// the decision of a unit from its sums: the first minimum in the order off, Wiener 1..3, self-guided 1..3
+template <bool SGR>
+__device__ __forceinline__ int lr_decide(const unsigned long long *usse) {
+  int best = 0;
+  unsigned long long bs = usse[0];
+  for (int k = 0; k < (SGR ? 6 : 3); k++) {
+    const unsigned long long s = usse[k + 1];
+    if (s < bs) { bs = s; best = k + 1; }
+  }
+  return best;
+}
+
+// ---- chroma units (enable_lr = 3 / 4) ---------------------------------------------------------------------
+// 32x32 units of the plane (lr_uv_shift 1), offset by 4 rows; stripes of 32 rows from 32 s - 4 (§7.17: StripeStartY = (64 s - 8) >> 1);
+// the plane ends at Round2(signalled size, 1) - 1.  A wave takes up to 16 rows of two neighbouring units of one plane, lane = column:
+// 64 lanes = 2 x 32 columns, so the window, the Wiener tile and the self-guided grids keep the luma layout (no LDS beyond luma's), and
+// the sums and the decision stay per unit (lanes 0-31 / 32-63 of a pass).  The last unit of a row (up to 47 columns) is processed
+// alone, or after its neighbour in a second pass of the wave.  Choices and sums are [frame][plane][unit].
+#define LR_SLICES_C 4   /* 16-row slices of a chroma unit: up to 51 rows */
+template <typename PIX, bool SGR, int PHASE>
+__device__ __forceinline__ void lr_chroma(const Av1miDevParams &P, int item, const PIX *pre, const PIX *cdef, const PIX *src, PIX *out,
+                                          uint8_t *choice, unsigned long long *unit_sse, int urows, int ucols) {
+  const int pairs = (ucols + 1) >> 1, slice = item % LR_SLICES_C, rest = item / LR_SLICES_C;
+  const int pc = rest % pairs, ur = rest / pairs % urows, pl = rest / (pairs * urows) % 2, f = rest / (pairs * urows * 2);
+  const int lane = threadIdx.x;
+  const size_t fo = (size_t)f * P.frame_samples + (pl ? P.plane_off_v : P.plane_off_u);
+  pre += fo; cdef += fo; src += fo; out += fo;
+  const int W = (P.true_w + 1) >> 1, H = (P.true_h + 1) >> 1, stride = P.stride_c;
+  const int uy0 = ur ? ur * 32 - 4 : 0, uy1 = ur == urows - 1 ? H : ur * 32 + 28;   // the unit row's rows
+  const int y0 = uy0 + slice * 16, y1 = y0 + 16 < uy1 ? y0 + 16 : uy1;              // this wave's rows
+  if (y0 >= uy1) return;
+  const int x0 = pc * 64, x1 = pc == pairs - 1 ? W : x0 + 64;
+  const int maxv = (1 << P.bit_depth) - 1;
+  const size_t ubase = ((size_t)f * 3 + 1 + pl) * urows * ucols + (size_t)ur * ucols;   // unit (ur, 0) of the plane
+  for (int xs = x0; xs < x1; xs += 64) {
+    const int x = xs + lane;
+    const bool active = x < x1;
+    const int uc_lo = min(ucols - 1, xs >> 5), uc_hi = min(ucols - 1, (xs >> 5) + 1), uc = lane < 32 ? uc_lo : uc_hi;
+    if constexpr (PHASE == 0) {
+      unsigned long long sse[7] = { 0, 0, 0, 0, 0, 0, 0 };
+      for (int st = (y0 + 4) / 32; st * 32 - 4 < y1; st++) {
+        const int s0 = st * 32 - 4, s1 = s0 + 31;
+        const int ya = y0 > s0 ? y0 : s0, yb = y1 < s1 + 1 ? y1 : s1 + 1;
+        __syncthreads();
+        lr_stage<PIX>(cdef, pre, xs, ya, yb, s0, s1, W, H, stride, lane);
+        __syncthreads();
+        int cur[16], sv[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++) {
+          const int y = ya + i < yb ? ya + i : yb - 1;
+          cur[i] = (int)g_win[y - ya + 3][lane + 3];
+          sv[i] = active ? (int)src[(size_t)y * stride + x] : cur[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 16; i++)
+          if (ya + i < yb) { const int d = cur[i] - sv[i]; sse[0] += (unsigned long long)(d * d); }
+        for (int k = 0; k < 3; k++) {
+          int tf[7];
+          taps_of_uv(k, tf);
+          wiener_h(P.bit_depth, ya, yb, tf, lane);
+#pragma unroll
+          for (int i = 0; i < 16; i++)
+            if (active && ya + i < yb) { const int d = wiener_v(i, lane, tf, maxv) - sv[i]; sse[k + 1] += (unsigned long long)(d * d); }
+        }
+        if constexpr (SGR) {
+          sgr_grid<0>(P.bit_depth, ya, yb, lane);
+          sgr_grid<1>(P.bit_depth, ya, yb, lane);
+          __syncthreads();
+#pragma unroll
+          for (int i = 0; i < 16; i++)
+            if (active && ya + i < yb) {
+              int f0, f1;
+              sgr_flt(lane, ya + i, ya, cur[i], f0, f1);
+#pragma unroll
+              for (int k = 0; k < 3; k++) {
+                const int d = sgr_blend(cur[i], f0, f1, c_sgr_cand[k][1], c_sgr_cand[k][2], maxv) - sv[i];
+                sse[4 + k] += (unsigned long long)(d * d);
+              }
+            }
+        }
+      }
+      for (int k = 0; k < (SGR ? 7 : 4); k++) {
+        const unsigned long long v = half_sum64(sse[k]);
+        if ((lane & 31) == 0 && v) atomicAdd(&unit_sse[(ubase + uc) * 8 + k], v);
+      }
+    } else {
+      // both units' decisions in every lane (the stripe loop below stays uniform); each lane applies its own unit's
+      const int best_lo = lr_decide<SGR>(unit_sse + (ubase + uc_lo) * 8), best_hi = lr_decide<SGR>(unit_sse + (ubase + uc_hi) * 8);
+      const int best = lane < 32 ? best_lo : best_hi;
+      if (slice == 0 && x == uc * 32) choice[ubase + uc] = (uint8_t)best;
+      const bool any_wiener = (best_lo && best_lo <= 3) || (best_hi && best_hi <= 3), any_sgr = best_lo > 3 || best_hi > 3;
+      int tf[7];
+      taps_of_uv(best && best <= 3 ? best - 1 : 0, tf);
+      for (int st = (y0 + 4) / 32; st * 32 - 4 < y1; st++) {
+        const int s0 = st * 32 - 4, s1 = s0 + 31;
+        const int ya = y0 > s0 ? y0 : s0, yb = y1 < s1 + 1 ? y1 : s1 + 1;
+        if (any_wiener || any_sgr) {
+          __syncthreads();
+          lr_stage<PIX>(cdef, pre, xs, ya, yb, s0, s1, W, H, stride, lane);
+          __syncthreads();
+        }
+        if constexpr (SGR) {
+          if (any_sgr) {
+            sgr_grid<0>(P.bit_depth, ya, yb, lane);
+            sgr_grid<1>(P.bit_depth, ya, yb, lane);
+            __syncthreads();
+          }
+        }
+        if (any_wiener) wiener_h(P.bit_depth, ya, yb, tf, lane);   // per-lane taps; g_mid is private to the lane's column
+        if (active)
+          for (int y = ya; y < yb; y++) {
+            int v;
+            if (best > 3) {
+              const int cur = (int)g_win[y - ya + 3][lane + 3];
+              int f0, f1;
+              sgr_flt(lane, y, ya, cur, f0, f1);
+              v = sgr_blend(cur, f0, f1, c_sgr_cand[best - 4][1], c_sgr_cand[best - 4][2], maxv);
+            } else if (best) {
+              v = wiener_v(y - ya, lane, tf, maxv);
+            } else {
+              v = cdef[(size_t)y * stride + x];
+            }
+            out[(size_t)y * stride + x] = (PIX)v;
+          }
+      }
+    }
+  }
+  if constexpr (PHASE == 1) {
+    // padding between the signalled and the coded size: copied with the last unit of the row / column (its last slice)
+    const int py1 = (ur == urows - 1 && y1 == uy1) ? P.height >> 1 : y1, px1 = pc == pairs - 1 ? P.width >> 1 : x1;
+    for (int y = y0; y < py1; y++)
+      for (int x = x0 + lane; x < px1; x += 64)
+        if (y >= y1 || x >= x1) out[(size_t)y * stride + x] = cdef[(size_t)y * stride + x];
+  }
+}
+
 // A unit is LR_SLICES waves, one per 16 of its rows (the last unit of a column has up to 103), in two launches: PHASE 0 adds
 // the slice's SSE of every candidate to the unit's sums (atomics), PHASE 1 reads the sums, takes the same decision in every
 // slice and applies it to its rows.  (As one wave per unit the kernel took 221 us of an inter frame's serial chain.)
+// CHROMA (enable_lr = 3 / 4): the grid's luma blocks are followed by the chroma units' (lr_chroma), and choices and sums are
+// [frame][plane][unit]; without it they are [frame][unit] and the luma blocks copy the co-located chroma.
 #define LR_SLICES 7
-template <typename PIX, bool SGR, int PHASE>
+template <typename PIX, bool SGR, bool CHROMA, int PHASE>
 __global__ void __launch_bounds__(64) lr_unit_kernel(Av1miDevParams P, const PIX *__restrict__ pre, const PIX *__restrict__ cdef,
                                                     const PIX *__restrict__ src, PIX *__restrict__ out, uint8_t *__restrict__ choice,
-                                                    unsigned long long *__restrict__ unit_sse /* [frame][unit][8] */) {
+                                                    unsigned long long *__restrict__ unit_sse /* [frame][(plane)][unit][8] */) {
   // units and stripes follow the signalled size; the last unit of a row/column also carries the padding up to the coded
   // size (copied, never filtered), so the whole frame buffer is defined
   const int urows = (P.true_h + 32) / 64 > 0 ? (P.true_h + 32) / 64 : 1, ucols = (P.true_w + 32) / 64 > 0 ? (P.true_w + 32) / 64 : 1;
   const int per_frame = urows * ucols;
+  if constexpr (CHROMA) {
+    const int luma_blocks = P.n_frames * per_frame * LR_SLICES;
+    if ((int)blockIdx.x >= luma_blocks) {
+      lr_chroma<PIX, SGR, PHASE>(P, (int)blockIdx.x - luma_blocks, pre, cdef, src, out, choice, unit_sse, urows, ucols);
+      return;
+    }
+  }
   const int item = blockIdx.x / LR_SLICES, slice = blockIdx.x % LR_SLICES;
   const int f = item / per_frame, u = item % per_frame, ur = u / ucols, uc = u % ucols;
+  const int uidx = CHROMA ? f * 3 * per_frame + u : item;   // the unit's choice and sums
   const int lane = threadIdx.x;
   const size_t fo = (size_t)f * P.frame_samples;
   pre += fo; cdef += fo; src += fo; out += fo;
@@ -210,7 +371,7 @@ __global__ void __launch_bounds__(64) lr_unit_kernel(Av1miDevParams P, const PIX
   if (y0 >= uy1) return;
   const int x0 = uc * 64, x1 = uc == ucols - 1 ? P.true_w : x0 + 64;
   const int maxv = (1 << P.bit_depth) - 1;
-  unsigned long long *usse = unit_sse + (size_t)item * 8;
+  unsigned long long *usse = unit_sse + (size_t)uidx * 8;
   if constexpr (PHASE == 0) {
   // ---- SSE without restoration and with each candidate
   unsigned long long sse[7] = { 0, 0, 0, 0, 0, 0, 0 };
@@ -221,7 +382,7 @@ __global__ void __launch_bounds__(64) lr_unit_kernel(Av1miDevParams P, const PIX
       const int s0 = st * 64 - 8, s1 = s0 + 63;
       const int ya = y0 > s0 ? y0 : s0, yb = y1 < s1 + 1 ? y1 : s1 + 1;
       __syncthreads();
-      lr_stage<PIX>(P, cdef, pre, xs, ya, yb, s0, s1, lane);   // the section's source window, once, for every candidate
+      lr_stage<PIX>(cdef, pre, xs, ya, yb, s0, s1, P.true_w, P.true_h, P.stride_y, lane);   // the section's source window, once, for every candidate
       __syncthreads();
       int cur[16], sv[16];   // this lane's CDEF and source samples of the section (<= 16 rows)
 #pragma unroll
@@ -273,8 +434,8 @@ __global__ void __launch_bounds__(64) lr_unit_kernel(Av1miDevParams P, const PIX
       if (s < bs) { bs = s; best = k + 1; }
     }
   }
-  if (lane == 0 && slice == 0) choice[item] = (uint8_t)best;
-  // ---- apply: luma of the slice, and the co-located chroma (copied)
+  if (lane == 0 && slice == 0) choice[uidx] = (uint8_t)best;
+  // ---- apply: luma of the slice, and (without CHROMA) the co-located chroma (copied)
   for (int xs = x0; xs < x1; xs += 64) {
     const int x = xs + lane;
     const bool active = x < x1;
@@ -283,7 +444,7 @@ __global__ void __launch_bounds__(64) lr_unit_kernel(Av1miDevParams P, const PIX
       const int ya = y0 > s0 ? y0 : s0, yb = y1 < s1 + 1 ? y1 : s1 + 1;
       if (best) {
         __syncthreads();
-        lr_stage<PIX>(P, cdef, pre, xs, ya, yb, s0, s1, lane);
+        lr_stage<PIX>(cdef, pre, xs, ya, yb, s0, s1, P.true_w, P.true_h, P.stride_y, lane);
         __syncthreads();
       }
       if (best > 3) {
@@ -316,42 +477,57 @@ __global__ void __launch_bounds__(64) lr_unit_kernel(Av1miDevParams P, const PIX
     for (int y = y0; y < py1; y++)
       for (int x = x0 + lane; x < px1; x += 64)
         if (y >= y1 || x >= x1) out[(size_t)y * P.stride_y + x] = cdef[(size_t)y * P.stride_y + x];
-    const int cy0 = y0 >> 1, cy1 = py1 >> 1, cx0 = x0 >> 1, cx1 = px1 >> 1;
-    for (int pl = 0; pl < 2; pl++) {
-      const size_t po = pl ? P.plane_off_v : P.plane_off_u;
-      for (int y = cy0; y < cy1; y++)
-        for (int x = cx0 + lane; x < cx1; x += 64) out[po + (size_t)y * P.stride_c + x] = cdef[po + (size_t)y * P.stride_c + x];
+    if constexpr (!CHROMA) {
+      const int cy0 = y0 >> 1, cy1 = py1 >> 1, cx0 = x0 >> 1, cx1 = px1 >> 1;
+      for (int pl = 0; pl < 2; pl++) {
+        const size_t po = pl ? P.plane_off_v : P.plane_off_u;
+        for (int y = cy0; y < cy1; y++)
+          for (int x = cx0 + lane; x < cx1; x += 64) out[po + (size_t)y * P.stride_c + x] = cdef[po + (size_t)y * P.stride_c + x];
+      }
     }
   }
   }  // PHASE 1
 }
 
-template <typename PIX, bool SGR>
+template <typename PIX, bool SGR, bool CHROMA>
 void launch_lr_phases(const Av1miDevParams *P, int grid, const PIX *pre, const PIX *cdef, const PIX *src, PIX *out, uint8_t *choice,
                       unsigned long long *unit_sse, hipStream_t stream) {
-  hipLaunchKernelGGL((lr_unit_kernel<PIX, SGR, 0>), dim3(grid), dim3(64), 0, stream, *P, pre, cdef, src, out, choice, unit_sse);
-  hipLaunchKernelGGL((lr_unit_kernel<PIX, SGR, 1>), dim3(grid), dim3(64), 0, stream, *P, pre, cdef, src, out, choice, unit_sse);
+  hipLaunchKernelGGL((lr_unit_kernel<PIX, SGR, CHROMA, 0>), dim3(grid), dim3(64), 0, stream, *P, pre, cdef, src, out, choice, unit_sse);
+  hipLaunchKernelGGL((lr_unit_kernel<PIX, SGR, CHROMA, 1>), dim3(grid), dim3(64), 0, stream, *P, pre, cdef, src, out, choice, unit_sse);
+}
+
+// enable_lr = 2 (RESTORE_SWITCHABLE): the instantiations with the self-guided candidates (17 KB of LDS per wave, 6.2 KB without)
+template <typename PIX>
+void launch_lr_typed(const Av1miDevParams *P, int grid, const void *pre, const void *cdef, const void *src, void *out, uint8_t *choice,
+                     unsigned long long *unit_sse, hipStream_t stream) {
+  const PIX *a = (const PIX *)pre, *b = (const PIX *)cdef, *s = (const PIX *)src;
+  PIX *o = (PIX *)out;
+  if (P->enable_lr == 2) {
+    if (P->lr_chroma) launch_lr_phases<PIX, true, true>(P, grid, a, b, s, o, choice, unit_sse, stream);
+    else launch_lr_phases<PIX, true, false>(P, grid, a, b, s, o, choice, unit_sse, stream);
+  } else {
+    if (P->lr_chroma) launch_lr_phases<PIX, false, true>(P, grid, a, b, s, o, choice, unit_sse, stream);
+    else launch_lr_phases<PIX, false, false>(P, grid, a, b, s, o, choice, unit_sse, stream);
+  }
 }
 
 }  // namespace
 
-// unit_sse: P->n_frames x units x 8 sums (scratch of the two phases; cleared here unless the caller did - the frame loop of a P chunk
-// clears the whole chunk's once instead of putting a fill between every frame's kernels on the chain).
+// unit_sse: P->n_frames x planes x units x 8 sums, planes = 3 with P->lr_chroma, else 1 (scratch of the two phases; cleared here
+// unless the caller did - the frame loop of a P chunk clears the whole chunk's once instead of putting a fill between every frame's
+// kernels on the chain).
 extern "C" hipError_t av1mi_launch_lr(const Av1miDevParams *P, const void *pre, const void *cdef, const void *src, void *out, uint8_t *choice,
                                       unsigned long long *unit_sse, int clear, hipStream_t stream) {
   const int urows = (P->true_h + 32) / 64 > 0 ? (P->true_h + 32) / 64 : 1, ucols = (P->true_w + 32) / 64 > 0 ? (P->true_w + 32) / 64 : 1;
-  const int units = P->n_frames * urows * ucols, grid = units * LR_SLICES;
+  const int units = P->n_frames * urows * ucols, planes = P->lr_chroma ? 3 : 1;
+  // chroma: per frame and plane, unit rows x pairs of unit columns, LR_SLICES_C waves each (the signalled size is even, so the chroma
+  // unit grid is the luma one)
+  const int grid = units * LR_SLICES + (P->lr_chroma ? P->n_frames * 2 * urows * ((ucols + 1) / 2) * LR_SLICES_C : 0);
   if (clear) {
-    hipError_t e = hipMemsetAsync(unit_sse, 0, (size_t)units * 8 * sizeof(unsigned long long), stream);
+    hipError_t e = hipMemsetAsync(unit_sse, 0, (size_t)units * planes * 8 * sizeof(unsigned long long), stream);
     if (e != hipSuccess) return e;
   }
-  // enable_lr = 2 (RESTORE_SWITCHABLE): the instantiation with the self-guided candidates (24 KB of LDS per wave)
-  if (P->bit_depth == 8) {
-    if (P->enable_lr == 2) launch_lr_phases<uint8_t, true>(P, grid, (const uint8_t *)pre, (const uint8_t *)cdef, (const uint8_t *)src, (uint8_t *)out, choice, unit_sse, stream);
-    else launch_lr_phases<uint8_t, false>(P, grid, (const uint8_t *)pre, (const uint8_t *)cdef, (const uint8_t *)src, (uint8_t *)out, choice, unit_sse, stream);
-  } else {
-    if (P->enable_lr == 2) launch_lr_phases<uint16_t, true>(P, grid, (const uint16_t *)pre, (const uint16_t *)cdef, (const uint16_t *)src, (uint16_t *)out, choice, unit_sse, stream);
-    else launch_lr_phases<uint16_t, false>(P, grid, (const uint16_t *)pre, (const uint16_t *)cdef, (const uint16_t *)src, (uint16_t *)out, choice, unit_sse, stream);
-  }
+  if (P->bit_depth == 8) launch_lr_typed<uint8_t>(P, grid, pre, cdef, src, out, choice, unit_sse, stream);
+  else launch_lr_typed<uint16_t>(P, grid, pre, cdef, src, out, choice, unit_sse, stream);
   return hipGetLastError();
 }

@@ -61,6 +61,10 @@ typedef struct {
   uint32_t enable_lr;       /* 1 = loop restoration on luma (Wiener, 64x64 units, each unit off or one of 3 filters by SSE);
                                2 = RESTORE_SWITCHABLE: each unit off, one of the 3 Wiener filters or one of 3 self-guided
                                filters (parameter set 9, three weightings);
+                               3 / 4 = 1 / 2 on all three planes: U and V in 32x32 units (the picture area of a luma
+                               unit), each unit decided on its own; chroma Wiener filters (0, 0, -4), (0, 0, 16), (0, 6, 20).
+                               A library without chroma restoration refuses 3 and 4 with AV1MI_E_INVALID_ARG, as every
+                               library refuses values above 4;
                                default 0: the decision needs the CDEF output, which serialises CDEF before entropy coding */
   uint32_t tile_sb;         /* tile size in 64x64 superblocks, both ways: 0 = automatic (1; 2 when the frame has more than 64
                                superblock rows or columns, e.g. 8K - AV1 allows at most 64 x 64 tiles), or force 1 / 2 */

@@ -11,7 +11,11 @@ pub struct Av1miParams {            // include/av1mi.h: av1mi_params
     pub width: u32, pub height: u32, pub bit_depth: u32,
     pub cq_level: u32, pub keyint: u32, pub block_log2: u32, pub cdf_update: u32, pub enable_cdef: u32,
     pub cdef_y_pri: u32, pub cdef_y_sec: u32, pub cdef_uv_pri: u32, pub cdef_uv_sec: u32, pub cdef_damping: u32,
-    pub intra_mode_mask: u32, pub film_grain: u32, pub first_frame: u32, pub me_range: u32, pub enable_lr: u32, pub tile_sb: u32, pub deblock: u32,
+    pub intra_mode_mask: u32, pub film_grain: u32, pub first_frame: u32, pub me_range: u32,
+    /// Loop restoration: 0 = off, 1 = Wiener on luma, 2 = off / Wiener / self-guided per luma unit; 3 / 4 = 1 / 2 on all three
+    /// planes (a library without chroma restoration refuses 3 and 4 with AV1MI_E_INVALID_ARG).
+    pub enable_lr: u32,
+    pub tile_sb: u32, pub deblock: u32,
     pub enable_qm: u32, pub qm_min: u32, pub qm_max: u32, pub subpel: u32,
     pub color_range: u32,           // 0 = studio (default; a Y4M XCOLORRANGE tag wins), 1 = full
     pub intra_angle_delta: u32,     // 1 = directional intra winners refined over the angle deltas -3..+3
