@@ -113,7 +113,8 @@ int resolve(const av1mi_params *in, Resolved *r) {
   r->cw = (int)((p.width + 7) & ~7u); r->ch = (int)((p.height + 7) & ~7u);
   r->padded = r->cw != (int)p.width || r->ch != (int)p.height;
   if (p.bit_depth != 8 && p.bit_depth != 10) return AV1MI_E_INVALID_ARG;
-  if (p.cq_level > 63 || p.film_grain > 50) return AV1MI_E_INVALID_ARG;
+  // cq_level 0 is base_q_idx 0: CodedLossless frames (spec 5.9.2), whose syntax this encoder does not write (no WHT, no lossless header)
+  if (p.cq_level == 0 || p.cq_level > 63 || p.film_grain > 50) return AV1MI_E_INVALID_ARG;
   if (p.keyint == 0) p.keyint = 1;
   if (p.me_range == 0) p.me_range = 8;
   if (p.me_range != 8 && p.me_range != 16) return AV1MI_E_INVALID_ARG;
@@ -195,7 +196,10 @@ std::vector<uint8_t> make_sequence_header(const Resolved &r) {
   {
     const bool desc = p.color_primaries || p.transfer_characteristics || p.matrix_coefficients;
     b.put(desc, 1);           // color_description_present_flag (absent: CP / TC / MC = 2 "unspecified")
-    if (desc) { b.put(p.color_primaries, 8); b.put(p.transfer_characteristics, 8); b.put(p.matrix_coefficients, 8); }
+    // a partial triple: each field left at 0 is written as 2 "unspecified" (0 is a reserved primaries / transfer code, and MC 0 =
+    // MC_IDENTITY is not allowed with 4:2:0, spec 5.5.2); the Matroska Colour element maps 0 the same way
+    auto code = [](uint32_t v) { return v ? v : 2u; };
+    if (desc) { b.put(code(p.color_primaries), 8); b.put(code(p.transfer_characteristics), 8); b.put(code(p.matrix_coefficients), 8); }
   }
   b.put(p.color_range ? 1 : 0, 1);  // color_range: 0 = studio (limited) range, 1 = full range
   b.put(0, 2);                // chroma_sample_position

@@ -43,7 +43,8 @@ typedef struct {
   uint32_t width, height;   /* luma size, even, >= 8, yuv 4:2:0.  Sizes that are not multiples of 8 are coded at the next
                                multiple of 8 (source edge-extended on the device) and signalled exactly, as any AV1 encoder does */
   uint32_t bit_depth;       /* 8 or 10 (samples: uint8_t / little-endian uint16_t) */
-  uint32_t cq_level;        /* "--crf N": 0..63, mapped to base_q_idx like aom (30 -> 120) */
+  uint32_t cq_level;        /* "--crf N": 1..63, mapped to base_q_idx like aom (30 -> 120).  0 (base_q_idx 0: lossless
+                               coding, which this encoder does not do) is refused with AV1MI_E_INVALID_ARG */
   uint32_t keyint;          /* "--keyint": 1 = every frame a key frame; N > 1 = a key frame every N frames of a chunk, the
                                frames between are INTER frames predicted from the previous reconstruction (one
                                reference, integer-pel full search; chunks always start with a key frame) */

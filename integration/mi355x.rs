@@ -83,7 +83,8 @@ pub fn run_mi355x(params: &Av1anEncodeParams, cq_level: u32) -> Result<(), Encod
     let mut p = Av1miParams::default();
     unsafe { av1mi_default_params(&mut p, 8, 8, 8) };   // geometry comes from the Y4M header
     // the reference's operating point, SVT_PARAMS (av1an.rs:14): "--crf 8 ... --film-grain 20 ... --keyint 240"
-    p.cq_level = cq_level;                               // "--crf" (8 in production; 30 is the benchmark's operating point)
+    p.cq_level = cq_level;                               // "--crf" (8 in production; 30 is the benchmark's operating point);
+                                                         // 1..63: 0 (lossless) fails with AV1MI_E_INVALID_ARG
     p.keyint = 240;                                      // "--keyint 240": IPPP inside a chunk, chunks start at scene cuts
     p.film_grain = 20;                                   // "--film-grain 20": film-grain table in every frame header
     p.enable_qm = 1; p.qm_min = 1; p.qm_max = 15;        // "--enable-qm 1 --qm-min 1 --qm-max 15": quantiser matrices

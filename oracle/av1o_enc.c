@@ -136,10 +136,10 @@ static void write_color_config(BitW *b, const Av1oConfig *cfg) {
   {
     const int desc = cfg->color_primaries || cfg->transfer_characteristics || cfg->matrix_coefficients;
     bw_put(b, desc, 1);             /* color_description_present_flag */
-    if (desc) {
-      bw_put(b, (unsigned)cfg->color_primaries, 8);
-      bw_put(b, (unsigned)cfg->transfer_characteristics, 8);
-      bw_put(b, (unsigned)cfg->matrix_coefficients, 8);
+    if (desc) { /* a field left at 0 is written as 2 "unspecified": MC 0 (identity) is not allowed with 4:2:0 (spec 5.5.2) */
+      bw_put(b, (unsigned)(cfg->color_primaries ? cfg->color_primaries : 2), 8);
+      bw_put(b, (unsigned)(cfg->transfer_characteristics ? cfg->transfer_characteristics : 2), 8);
+      bw_put(b, (unsigned)(cfg->matrix_coefficients ? cfg->matrix_coefficients : 2), 8);
     }
     /* (CP 1 / TC 13 / MC 0 - sRGB with the identity matrix - would imply 4:4:4 and no color_range bit: not a 4:2:0 description,
      * refused by the product's parameter check, never written here) */
@@ -1889,6 +1889,9 @@ long av1o_encode_frame2(const Av1oConfig *cfg, const Av1oFrame *src, const Av1oF
   long ret = -1;
   if (cfg->width % 8 || cfg->height % 8 || cfg->width < 8 || cfg->height < 8) return -2;
   if (bd != 8 && bd != 10) return -2;
+  /* base_q_idx 0 (no delta-q, no segmentation) makes the frame CodedLossless (spec 5.9.2): a different header and 4x4 WHT blocks,
+   * which this reference does not write - refused like the product's cq_level 0 */
+  if (cfg->base_q_idx < 1 || cfg->base_q_idx > 255) return -2;
   if (cfg->still_picture && ref) return -2;
   if (ref && !prev_src) return -2;
   make_geom(cfg, &g);

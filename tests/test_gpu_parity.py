@@ -828,6 +828,31 @@ def test_encode_file_matroska_and_obu_outputs(av1mi, oracle, tmp_path):
     assert [b[2] for b in blocks] == [t[2:] for t in tus]
 
 
+@pytest.mark.parametrize("triple", [(9, 16, 0), (0, 0, 1), (1, 0, 0), (9, 16, 9)])
+def test_encode_file_matroska_colour_equals_the_sequence_header(av1mi, oracle, tmp_path, triple):
+    """The Matroska track's Colour element says what the sequence header's color_config says, also for a partial colour triple (a field
+    left at 0 is 2 "unspecified" in both; MC 0 would be MC_IDENTITY, which 4:2:0 forbids)."""
+    from edge_content import color_config
+    w, h = 72, 56
+    y4m = tmp_path / "clip.y4m"
+    y4m.write_bytes(b"YUV4MPEG2 W%d H%d F25:1 Ip A1:1 C420jpeg\n" % (w, h) + b"FRAME\n" + raw_of(oracle.synthclip_frame(w, h, 8, seed=81, t=0), 8))
+    out = tmp_path / "clip.mkv"
+    hdr = dict(zip(("color_primaries", "transfer_characteristics", "matrix_coefficients"), triple))
+    rep = av1mi.run_mi355x(av1mi.EncodeParams(y4m, out, tmp_path, av1mi.derive_plan(8), chunk_frames=1, **hdr))
+    assert rep.frames == 1
+    mkv = out.read_bytes()
+    top = list(_ebml(mkv, 0, len(mkv)))
+    seg = list(_ebml(mkv, top[1][1], top[1][2]))
+    entry = next(_ebml(mkv, seg[1][1], seg[1][2]))
+    te = {e[0]: (e[1], e[2]) for e in _ebml(mkv, entry[1], entry[2])}
+    vid = {e[0]: (e[1], e[2]) for e in _ebml(mkv, te[0xE0][0], te[0xE0][1])}
+    col = {e[0]: int.from_bytes(mkv[e[1]:e[2]], "big") for e in _ebml(mkv, vid[0x55B0][0], vid[0x55B0][1])}
+    desc, cp, tc, mc, cr = color_config(mkv[te[0x63A2][0]:te[0x63A2][1]][4:])
+    assert desc == 1 and 0 not in (cp, tc, mc)
+    assert (col[0x55BB], col[0x55BA], col[0x55B1], col[0x55B9]) == (cp, tc, mc, 2 if cr else 1)
+    assert (cp, tc, mc) == tuple(v or 2 for v in triple)
+
+
 def test_encode_file_hdr_colour_frame_parameters_and_gpu_mask(av1mi, oracle, tmp_path):
     """BASELINE config 5's "HDR": the job's colour description (BT.2020 / PQ / BT.2020 NCL) reaches the sequence header - the same bytes
     as the oracle's, which dav1d / libavif read back (tests/golden/k200x120_hdr_bt2020_pq_10b) - and the Matroska track's Colour element.

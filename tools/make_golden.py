@@ -224,7 +224,33 @@ def make_sequences():
     json.dump(index, open(os.path.join(OUT, "index_seq.json"), "w"), indent=1)
 
 
+def make_edges():
+    """The patterned inputs and quantiser edges of tests/edge_content.py (FIXTURES): one chunk each, every frame checked against dav1d
+    before anything is written; tests/golden/index_edges.json lists them with the case (generator and its arguments, parameters)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import edge_content as E
+    index = []
+    for name in E.FIXTURES:
+        c = E.case(name)
+        frames = E.source(av1o, c)
+        tus, recs, sse = E.oracle_encode(av1o, c, frames)
+        dec = E.dav1d_decode(tus, c["w"], c["h"], c["bd"], c["params"].get("keyint", 1))
+        bad = E.decodes_to(dec, recs, c["bd"], False)
+        if bad is not None:
+            raise SystemExit("%s: dav1d output differs from the oracle reconstruction at %s" % (name, bad))
+        open(os.path.join(OUT, "edge_" + name + ".obu"), "wb").write(b"".join(tus))
+        meta = dict(name=name, case=c, frame_bytes=[len(x) for x in tus], src_sha256=[sha(f) for f in frames],
+                    dav1d_sha256=[sha(d) for d in dec], sse=sse, decoder="dav1d 1.5.3 via libavif 1.4.1 (Pillow 12.2.0)")
+        json.dump(meta, open(os.path.join(OUT, "edge_" + name + ".json"), "w"), indent=1, sort_keys=True)
+        index.append("edge_" + name)
+        print("%-32s %s B  dav1d == oracle recon on %d frames" % (name, meta["frame_bytes"], len(tus)))
+    json.dump(index, open(os.path.join(OUT, "index_edges.json"), "w"), indent=1)
+
+
 def main():
+    if "--edges" in sys.argv:
+        make_edges()
+        return
     os.makedirs(OUT, exist_ok=True)
     index = []
     for name, w, h, bd, seed, t, kw in CASES:
