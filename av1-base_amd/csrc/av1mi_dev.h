@@ -19,6 +19,17 @@
 
 struct Av1miQmEntry { uint32_t q, recip; };
 
+// What the host needs of a packed chunk before (and beside) its bytes, in one device record the packing kernels fill (its head cleared
+// at the start of the chunk) and one copy fetches: this head, then frame_off[n_frames + 1] - the frames' byte offsets in the packed
+// output and, last, its total (the packing kernels get `&overflow` and the offsets as the separate arrays they are to them).
+struct Av1miChunkRecord {
+  unsigned long long n_symbols;   // symbol-stream entries of all tiles of the chunk
+  uint32_t max_tile_symbols;      // ... of its longest tile
+  int overflow;                   // a tile outgrew its bitstream slot or its symbol stream: nothing was packed
+};
+static_assert(sizeof(Av1miChunkRecord) == 16, "the frame offsets follow the head, 8-byte aligned");
+
+
 struct Av1miDevParams {
   int width, height, bit_depth;   // CODED size: the signalled size rounded up to multiples of 8 (the source is edge-extended)
   int true_w, true_h;             // signalled size: what the decoder crops to, clamps references to and restores within
@@ -90,6 +101,9 @@ struct Av1miDevParams {
   int lr_chroma;
   int lr_code_len_uv[4][3];
   unsigned long long lr_code_bits_uv[4][3];
+  // packing: null (no counts wanted), or the chunk's record and the [frame][tile] symbol-stream lengths frame_layout_kernel reduces into it
+  Av1miChunkRecord *chunk_record;
+  const uint32_t *tile_symbols;
 };
 
 // ---- partition: does the node of size 2^bsl at superblock-local (ox, oy) split?  One rule for every kernel that
@@ -135,6 +149,46 @@ AV1MI_HD inline void av1mi_me_key_decode(unsigned long long key, int R, int *dy,
 
 // frame f of a chunk is a key frame iff f % keyint == 0
 AV1MI_HD inline int av1mi_frame_is_inter(const Av1miDevParams &P, int f) { return P.keyint > 1 && (f % P.keyint) != 0; }
+
+// ---- which symbolize variant owns a tile (entropy_kernel.hip: the kernels decide per tile, the launcher sizes its grids by it)
+// Under a content-driven partition (P.part_map, device memory: device code only): does the superblock keep one block size throughout -
+// no node between min_bs_log2 and max_bs_log2 splits by its mask?  (Only then does a tile hold exactly two (transform size, plane type)
+// classes.)
+AV1MI_HD inline bool av1mi_sb_unsplit(const Av1miDevParams &P, int f, int sbr, int sbc) {
+  if (!P.part_map || P.min_bs_log2 >= P.max_bs_log2) return true;
+  const uint32_t m = P.part_map[((size_t)f * P.sb_rows + sbr) * P.sb_cols + sbc];
+  return P.max_bs_log2 >= 6 ? !(m & 1u) : (P.max_bs_log2 == 5 ? !(m & 0x1Eu) : !(m & 0x1FFFE0u));
+}
+// ... and does the frame edge leave it alone?  A node of the leaf size whose origin lies inside the frame must not be forced to split
+// (has_rows / has_cols of av1mi_node_split: a leaf may overhang the edge by less than half its size - the bottom superblock row of a
+// 1080-row frame, 56 rows, keeps its four 32x32 leaves; a row of 40 would not).
+AV1MI_HD inline bool av1mi_sb_uniform(const Av1miDevParams &P, int f, int sbr, int sbc) {
+  if (!av1mi_sb_unsplit(P, f, sbr, sbc)) return false;
+  const int L = P.max_bs_log2, n = 1 << L;
+  if (L <= 3) return true;
+  for (int oy = 0; oy < 64; oy += n)
+    for (int ox = 0; ox < 64; ox += n) {
+      const int x = sbc * 64 + ox, yy = sbr * 64 + oy;
+      if (x < P.width && yy < P.height && (yy + (n >> 1) >= P.height || x + (n >> 1) >= P.width)) return false;
+    }
+  return true;
+}
+// The regular variant's tiles: adaptive CDFs and every superblock of the tile (tsb x tsb of them) uniform; all others are the full variant's.
+AV1MI_HD inline bool av1mi_tile_is_regular(const Av1miDevParams &P, int f, int tr, int tc, int tsb) {
+  if (P.disable_cdf_update) return false;
+  for (int si = 0; si < tsb * tsb; si++) {
+    const int sbr = tr * tsb + si / tsb, sbc = tc * tsb + si % tsb;
+    if (sbr < P.sb_rows && sbc < P.sb_cols && !av1mi_sb_uniform(P, f, sbr, sbc)) return false;
+  }
+  return true;
+}
+// Without a partition map ownership is geometry, the same in every frame, and a superblock that is not uniform lies in the last
+// superblock row or column: the full variant's tiles are among a frame's edge tiles - its last tile row, then the last tile column
+// above it, tile_cols + tile_rows - 1 in all.  Edge tile e of a frame:
+AV1MI_HD inline int av1mi_edge_tiles(const Av1miDevParams &P) { return P.tile_cols + P.tile_rows - 1; }
+AV1MI_HD inline int av1mi_edge_tile(const Av1miDevParams &P, int e) {
+  return e < P.tile_cols ? (P.tile_rows - 1) * P.tile_cols + e : (e - P.tile_cols) * P.tile_cols + P.tile_cols - 1;
+}
 
 // Per 8x8-unit block info written by the recon kernel, read by entropy + CDEF kernels.
 // Only the entry at a block's top-left 8x8 unit carries eobs; mode/skip are replicated over the

@@ -469,8 +469,8 @@ struct Workspace {
   Av1miDevParams *d_params = nullptr;  // copy of P for the kernels that read their parameters through a pointer (recon)
   uint32_t *d_tile_bytes = nullptr, *d_tile_off = nullptr, *d_frame_size = nullptr, *d_payload = nullptr, *d_sym = nullptr;
   uint32_t *d_streams = nullptr, *d_combos = nullptr;
-  unsigned long long *d_frame_off = nullptr, *d_sse = nullptr;
-  int *d_overflow = nullptr;
+  unsigned long long *d_sse = nullptr;
+  Av1miChunkRecord *d_record = nullptr;   // symbol counts, overflow flag, then frame_off[cap_frames + 1] (av1mi_launch_pack)
   unsigned long long *d_me = nullptr;  // motion search results per 8x8 unit per frame
   void *d_stage = nullptr;             // sizes that are not multiples of 8: frames in the caller's tight layout (input / reconstruction out)
   void *d_cd = nullptr;                // loop restoration on: CDEF output (d_fin then holds the restored frames)
@@ -487,6 +487,13 @@ struct Workspace {
   int8_t *d_cdef_idx = nullptr;              // ... per [frame][superblock] the index into the frame's set (-1: not coded)
   uint8_t *d_cdef_sel = nullptr;             // ... per frame the set: 8 slots of pair indices
   uint8_t *h_out = nullptr;            // host staging (pinned), for when the caller's buffer cannot be page-locked
+  // Page-locked host side of the small transfers.  The chunk constants - header blob, default CDFs, parameters - are the same for
+  // every chunk of a job: h_hdr / h_cdf / h_params hold what d_hdr / d_cdf / d_params hold, and prepare_chunk uploads only what differs.
+  uint8_t *h_hdr = nullptr; uint16_t *h_cdf = nullptr; Av1miDevParams *h_params = nullptr;
+  size_t hdr_bytes = 0;                // bytes of h_hdr that d_hdr is known to hold; 0: unknown (the strength search writes into d_hdr)
+  int cdf_qidx = -1;                   // the quantiser index d_cdf was made for (the blob depends on nothing else); -1: none
+  bool params_on_device = false;       // d_params holds *h_params
+  Av1miChunkRecord *h_record = nullptr; unsigned long long *h_sse = nullptr;   // d_record and d_sse land here
   size_t out_cap = 0, me64_bytes = 0, h_out_cap = 0;   // bytes of d_out, d_me64, h_out
   std::vector<std::pair<void *, bool>> owned;   // every buffer above: (address, page-locked host memory)
 };
@@ -582,9 +589,20 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     for (uint32_t **b : { &w.d_tile_bytes, &w.d_tile_off, &w.d_sym, &w.d_combos }) HIPCHK(c, ws_alloc(w, *b, nf * nsb * 4));
     HIPCHK(c, ws_alloc(w, w.d_streams, nf * ntile * (size_t)tile_stream_cap(r, c->cap_scale) * 4));
     for (uint32_t **b : { &w.d_frame_size, &w.d_payload }) HIPCHK(c, ws_alloc(w, *b, nf * 4));
-    HIPCHK(c, ws_alloc(w, w.d_frame_off, (nf + 1) * 8));
+    HIPCHK(c, ws_alloc(w, w.d_record, sizeof(Av1miChunkRecord) + (nf + 1) * 8));
     HIPCHK(c, ws_alloc(w, w.d_sse, nf * 3 * 8));
-    HIPCHK(c, ws_alloc(w, w.d_overflow, 4));
+    {  // the five small host mirrors share one page-locked block: an allocation of page-locked memory costs far more than they hold
+      auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+      const size_t b_hdr = up(256 + nf * 512), b_cdf = up(Av1miCdfLayout::TOTAL * sizeof(uint16_t)), b_par = up(sizeof(Av1miDevParams)),
+                   b_rec = up(sizeof(Av1miChunkRecord) + (nf + 1) * 8), b_sse = up(nf * 3 * 8);
+      uint8_t *h = nullptr;
+      HIPCHK(c, ws_alloc(w, h, b_hdr + b_cdf + b_par + b_rec + b_sse, true));
+      w.h_hdr = h; h += b_hdr;
+      w.h_cdf = reinterpret_cast<uint16_t *>(h); h += b_cdf;
+      w.h_params = reinterpret_cast<Av1miDevParams *>(h); h += b_par;
+      w.h_record = reinterpret_cast<Av1miChunkRecord *>(h); h += b_rec;
+      w.h_sse = reinterpret_cast<unsigned long long *>(h);
+    }
     HIPCHK(c, ws_alloc(w, w.d_me, nf * nb8 * 8));
     w.cap_frames = n_frames; w.scale = c->cap_scale;
   }
@@ -636,7 +654,7 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
 // The kernels' parameters of a chunk of `n_frames` frames: `r` at the coded size, the per-tile capacities of multiplier `scale` and the
 // workspace buffers the kernels find through them.  The header sizes follow with the headers (prepare_chunk).
 Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const uint32_t *part, const Av1miQmEntry *qm,
-                          unsigned long long *cdef_err, int8_t *cdef_idx, uint8_t *cdef_sel) {
+                          unsigned long long *cdef_err, int8_t *cdef_idx, uint8_t *cdef_sel, Av1miChunkRecord *record, const uint32_t *tile_symbols) {
   const av1mi_params &p = r.p;
   Av1miDevParams P;
   memset(&P, 0, sizeof(P));
@@ -669,6 +687,7 @@ Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const
   for (int i = 0; i < 4; i++) { P.lf_level[i] = deblock_level(r, true); P.lf_level_inter[i] = deblock_level(r, false); }
   P.enable_lr = (int)p.enable_lr;
   P.lr_chroma = r.lr_chroma;
+  P.chunk_record = record; P.tile_symbols = tile_symbols;
   for (int rf = 0; rf < 4; rf++)
     for (int k = 0; k < 3; k++) {
       const BitString b = lr_code_of(rf, k); P.lr_code_len[rf][k] = b.len; P.lr_code_bits[rf][k] = b.bits;
@@ -969,11 +988,29 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
     if (r.p.film_grain && f) h = make_frame_header(r, nullptr, f, inter);
     memcpy(blob.data() + seq.size() + (size_t)f * P.hdr_slot_bytes, h.data(), h.size());
   }
-  std::vector<uint16_t> cdf = make_cdf_blob(r.qidx);
-  HIPCHK(c, hipMemcpyAsync(w.d_hdr, blob.data(), blob.size(), hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(w.d_cdf, cdf.data(), cdf.size() * 2, hipMemcpyHostToDevice, s));
-  HIPCHK(c, hipMemcpyAsync(w.d_params, &P, sizeof(P), hipMemcpyHostToDevice, s));  // the recon kernel reads its parameters from device memory
-  HIPCHK(c, hipMemsetAsync(w.d_overflow, 0, 4, s));
+  // Upload what the device does not hold already (consecutive chunks of a job: nothing), from page-locked memory - the copies are
+  // asynchronous, and the previous chunk's have completed (download_chunk waits for the main stream).  With the strength search on,
+  // cdef_select_kernel writes the strengths into the frame headers on the device: the blob goes up every chunk.
+  if (w.hdr_bytes != blob.size() || memcmp(w.h_hdr, blob.data(), blob.size())) {
+    w.hdr_bytes = 0;
+    memcpy(w.h_hdr, blob.data(), blob.size());
+    HIPCHK(c, hipMemcpyAsync(w.d_hdr, w.h_hdr, blob.size(), hipMemcpyHostToDevice, s));
+  }
+  w.hdr_bytes = P.cdef_search ? 0 : blob.size();
+  if (w.cdf_qidx != r.qidx) {
+    w.cdf_qidx = -1;
+    const std::vector<uint16_t> cdf = make_cdf_blob(r.qidx);
+    memcpy(w.h_cdf, cdf.data(), cdf.size() * 2);
+    HIPCHK(c, hipMemcpyAsync(w.d_cdf, w.h_cdf, cdf.size() * 2, hipMemcpyHostToDevice, s));
+    w.cdf_qidx = r.qidx;
+  }
+  if (!w.params_on_device || memcmp(w.h_params, &P, sizeof(P))) {   // (dev_params clears the padding; a cap_scale change shows in P)
+    w.params_on_device = false;
+    memcpy(w.h_params, &P, sizeof(P));
+    HIPCHK(c, hipMemcpyAsync(w.d_params, w.h_params, sizeof(P), hipMemcpyHostToDevice, s));  // the recon kernel reads its parameters from device memory
+    w.params_on_device = true;
+  }
+  HIPCHK(c, hipMemsetAsync(w.d_record, 0, sizeof(Av1miChunkRecord), s));
   HIPCHK(c, hipMemsetAsync(w.d_sse, 0, (size_t)n_frames * 24, s));
   if (P.cdef_search) HIPCHK(c, hipMemsetAsync(w.d_cdef_err, 0, (size_t)n_frames * P.sb_rows * P.sb_cols * 24 * sizeof(unsigned long long), s));
   HIPCHK(c, hipEventRecord(c->ev[EV_START], s));
@@ -1142,36 +1179,43 @@ static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
 }
 
 // The packed bitstream into a buffer for the caller, the final frames into `recon` if asked for, and the report.
+// One copy brings the chunk record (frame offsets, symbol counts, overflow flag) to page-locked memory; the host waits for it, then
+// fetches exactly the bytes produced.  (Copying a guessed size behind packing without that wait was measured and left out: DESIGN 5d.)
 static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, int frames_on_device, av1mi_buf *out, uint32_t *frame_sizes,
                           void *recon, av1mi_report *report) {
   const Av1miDevParams &P = c->P; Workspace &w = c->ws; hipStream_t s = c->stream, s2 = c->stream2;
-  // sizes first, then exactly the bytes produced
-  std::vector<unsigned long long> foff(n_frames + 1);
-  int overflow = 0;
-  HIPCHK(c, hipMemcpyAsync(foff.data(), w.d_frame_off, (n_frames + 1) * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipMemcpyAsync(&overflow, w.d_overflow, 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(c, hipStreamSynchronize(s));
-  if (overflow) {
-    (void)hipStreamSynchronize(s2);  // the retry reuses the buffers the second stream is still reading
-    set_err(c, "a tile outgrew its %d-byte bitstream slot or its %d-entry symbol stream", P.tile_slot_bytes, P.stream_cap);
+  const Av1miChunkRecord &rec = *w.h_record;
+  const unsigned long long *foff = reinterpret_cast<const unsigned long long *>(w.h_record + 1);
+  hipError_t e1 = hipMemcpyAsync(w.h_record, w.d_record, sizeof(Av1miChunkRecord) + (n_frames + 1) * 8, hipMemcpyDeviceToHost, s);
+  if (e1 == hipSuccess) e1 = hipStreamSynchronize(s);
+  if (e1 != hipSuccess) {
+    (void)hipStreamSynchronize(s2);
+    set_err(c, "fetching the chunk record failed: %s", hipGetErrorString(e1));
+    return AV1MI_E_HIP;
+  }
+  // overflow or a size beyond the buffer end the chunk (the retry reuses the buffers the second stream is still reading, and `recon`
+  // may be the caller's memory: it drains first)
+  if (rec.overflow || foff[n_frames] > w.out_cap) {
+    (void)hipStreamSynchronize(s2);
+    if (rec.overflow) set_err(c, "a tile outgrew its %d-byte bitstream slot or its %d-entry symbol stream", P.tile_slot_bytes, P.stream_cap);
+    else set_err(c, "internal: packed size exceeds buffer");
     return AV1MI_E_OVERFLOW;
   }
   const size_t total = (size_t)foff[n_frames];
-  if (total > w.out_cap) { (void)hipStreamSynchronize(s2); set_err(c, "internal: packed size exceeds buffer"); return AV1MI_E_OVERFLOW; }
   // the caller's buffer: a page-locked block of the pool (the copy lands in it directly); plain memory + this context's staging
   // buffer only if page-locked memory cannot be had
-  uint8_t *host = (uint8_t *)pin_acquire(total ? total : 1);
-  const bool direct = host != nullptr;
-  if (!direct) {
+  uint8_t *host = (uint8_t *)pin_acquire(total ? total : 1), *dst = host;
+  if (!host) {
     host = (uint8_t *)malloc(total ? total : 1);
     if (!host) { (void)hipStreamSynchronize(s2); return AV1MI_E_OOM; }
     if (w.h_out_cap < total) {
       w.h_out_cap = 0;
       if (ws_alloc(w, w.h_out, total + (total >> 2) + 4096, true) == hipSuccess) w.h_out_cap = total + (total >> 2) + 4096;
     }
+    if (w.h_out && w.h_out_cap >= total) dst = w.h_out;   // (else: straight into the plain block, a staged copy)
+    else dst = host;
   }
-  uint8_t *dst = direct ? host : (w.h_out ? w.h_out : host);
-  hipError_t e1 = hipMemcpyAsync(dst, w.d_out, total, hipMemcpyDeviceToHost, s);
+  e1 = hipMemcpyAsync(dst, w.d_out, total, hipMemcpyDeviceToHost, s);
   hipError_t e2 = hipEventRecord(c->ev[EV_DOWNLOAD_DONE], s);
   if (e2 == hipSuccess) e2 = hipStreamWaitEvent(s, c->ev[EV_CDEF_DONE], 0);  // join: the final reconstruction and the SSE come from the second stream
   if (e1 == hipSuccess && e2 == hipSuccess && recon) {
@@ -1183,16 +1227,13 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
     const size_t bytes = (size_t)n_frames * (r.padded ? (size_t)r.p.width * r.p.height * 3 / 2 : (size_t)P.frame_samples) * (P.bit_depth > 8 ? 2 : 1);
     if (e1 == hipSuccess) e1 = hipMemcpyAsync(recon, fin, bytes, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s);
   }
-  std::vector<unsigned long long> sse(n_frames * 3);
-  std::vector<uint32_t> syms;
-  if (e1 == hipSuccess) e1 = hipMemcpyAsync(sse.data(), w.d_sse, (size_t)n_frames * 24, hipMemcpyDeviceToHost, s);
-  if (e1 == hipSuccess && report) {
-    syms.resize((size_t)n_frames * P.tile_rows * P.tile_cols);
-    e1 = hipMemcpyAsync(syms.data(), w.d_sym, syms.size() * 4, hipMemcpyDeviceToHost, s);
-  }
+  const unsigned long long *sse = w.h_sse;
+  if (e1 == hipSuccess) e1 = hipMemcpyAsync(w.h_sse, w.d_sse, (size_t)n_frames * 24, hipMemcpyDeviceToHost, s);
   // the bitstream is on the host once EV_DOWNLOAD_DONE has passed: hand it over to the caller's buffer while the second stream finishes
-  if (e1 == hipSuccess && e2 == hipSuccess) e1 = hipEventSynchronize(c->ev[EV_DOWNLOAD_DONE]);
-  if (e1 == hipSuccess && e2 == hipSuccess && dst != host) memcpy(host, dst, total);
+  if (e1 == hipSuccess && e2 == hipSuccess && dst != host) {
+    e1 = hipEventSynchronize(c->ev[EV_DOWNLOAD_DONE]);
+    if (e1 == hipSuccess) memcpy(host, dst, total);
+  }
   if (e1 == hipSuccess) e1 = hipStreamSynchronize(s);
   if (e1 != hipSuccess || e2 != hipSuccess) {
     (void)hipStreamSynchronize(s2);
@@ -1214,7 +1255,7 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
       const double npx = (double)n_frames * P.width * P.height / (pl ? 4 : 1);
       report->psnr[pl] = t > 0 ? 10.0 * log10(mx * mx * npx / t) : 99.0;
     }
-    for (uint32_t v : syms) { report->n_symbols += v; if (v > report->max_tile_symbols) report->max_tile_symbols = v; }
+    report->n_symbols = rec.n_symbols; report->max_tile_symbols = rec.max_tile_symbols;
     (void)hipEventElapsedTime(&report->ms_h2d, c->ev[EV_START], c->ev[EV_SRC_READY]);
     (void)hipEventElapsedTime(&report->ms_recon, c->ev[EV_SRC_READY], c->ev[EV_RECON_DONE]);
     (void)hipEventElapsedTime(&report->ms_cdef, c->ev[EV_CDEF_START], c->ev[EV_CDEF_DONE]);
@@ -1227,8 +1268,22 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
   return AV1MI_OK;
 }
 
+static int run_chunk(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
+                     av1mi_buf *out, uint32_t *frame_sizes, void *recon, av1mi_report *report);
+
 static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
                              av1mi_buf *out, uint32_t *frame_sizes, void *recon, av1mi_report *report) {
+  const int rc = run_chunk(c, params, frames, n_frames, frames_on_device, out, frame_sizes, recon, report);
+  if (rc != AV1MI_OK && rc != AV1MI_E_OVERFLOW) {
+    // a chunk that broke off may have left uploads from the page-locked copies in flight or undone: let them end, trust none of them
+    (void)hipStreamSynchronize(c->stream);
+    c->ws.hdr_bytes = 0; c->ws.cdf_qidx = -1; c->ws.params_on_device = false;
+  }
+  return rc;
+}
+
+static int run_chunk(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
+                     av1mi_buf *out, uint32_t *frame_sizes, void *recon, av1mi_report *report) {
   out->data = nullptr; out->size = 0;
   Resolved r;
   int rc = resolve(params, &r);
@@ -1237,7 +1292,7 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
   rc = ensure_workspace(c, r, n_frames);
   if (rc) return rc;
   Workspace &w = c->ws;
-  c->P = dev_params(r, n_frames, c->cap_scale, w.d_part, w.d_qm, w.d_cdef_err, w.d_cdef_idx, w.d_cdef_sel);
+  c->P = dev_params(r, n_frames, c->cap_scale, w.d_part, w.d_qm, w.d_cdef_err, w.d_cdef_idx, w.d_cdef_sel, w.d_record, w.d_sym);
   const void *d_src = nullptr;
   rc = prepare_chunk(c, r, frames, n_frames, frames_on_device, &d_src);
   if (rc) return rc;
@@ -1249,8 +1304,8 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
   // packing and the download of the bitstream need nothing from the second stream: they run beside the tail of its work; the join
   // comes before the reconstruction and the SSE are read (download_chunk)
   for (int stage = 0; stage < 2; stage++)
-    HIPCHK(c, av1mi_launch_pack(&P, w.d_slots, w.d_tile_bytes, w.d_tile_off, w.d_frame_size, w.d_payload, w.d_frame_off, w.d_hdr,
-                                w.d_out, w.d_overflow, stage, c->stream));
+    HIPCHK(c, av1mi_launch_pack(&P, w.d_slots, w.d_tile_bytes, w.d_tile_off, w.d_frame_size, w.d_payload,
+                                reinterpret_cast<unsigned long long *>(w.d_record + 1), w.d_hdr, w.d_out, &w.d_record->overflow, stage, c->stream));
   HIPCHK(c, hipEventRecord(c->ev[EV_PACK_DONE], c->stream));
   return download_chunk(c, r, n_frames, frames_on_device, out, frame_sizes, recon, report);
 }

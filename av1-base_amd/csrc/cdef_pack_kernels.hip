@@ -692,15 +692,25 @@ __device__ __forceinline__ int leb128_len(uint32_t v) {
   return n;
 }
 
-// one workgroup per frame: tile offsets inside the OBU_FRAME payload, frame (temporal unit) size
+// one workgroup per frame: tile offsets inside the OBU_FRAME payload, frame (temporal unit) size; with a chunk record (P.chunk_record)
+// the frame's tiles' symbol counts go into it (integer sum and maximum: the order of the frames' additions does not show)
 __global__ void __launch_bounds__(256) frame_layout_kernel(Av1miDevParams P, const uint32_t *__restrict__ tile_bytes,
                                                           uint32_t *__restrict__ tile_off, uint32_t *__restrict__ frame_size,
                                                           uint32_t *__restrict__ payload_size, int *__restrict__ overflow) {
   __shared__ uint32_t part[256];
+  __shared__ unsigned long long sym_sum[256];
+  __shared__ uint32_t sym_max[256];
   const int f = blockIdx.x, nt = P.tile_rows * P.tile_cols, t = threadIdx.x;
   const uint32_t *tb = tile_bytes + (size_t)f * nt;
   const int per = (nt + 255) / 256;
   uint32_t s = 0;
+  if (P.chunk_record) {
+    const uint32_t *sl = P.tile_symbols + (size_t)f * nt;
+    unsigned long long ssum = 0;
+    uint32_t smax = 0;
+    for (int i = t * per; i < (t + 1) * per && i < nt; i++) { ssum += sl[i]; smax = sl[i] > smax ? sl[i] : smax; }
+    sym_sum[t] = ssum; sym_max[t] = smax;
+  }
   for (int i = t * per; i < (t + 1) * per && i < nt; i++) {
     // a tile that outgrew its slot or its symbol stream (0xFFFFFFFF): flag it; the host re-runs the
     // chunk with larger capacities and pack_tiles_kernel does nothing in this pass
@@ -716,6 +726,13 @@ __global__ void __launch_bounds__(256) frame_layout_kernel(Av1miDevParams P, con
     for (int i = 0; i < 256; i++) { uint32_t v = part[i]; part[i] = run; run += v; }
     payload_size[f] = run;
     frame_size[f] = 2u + (inter ? 0u : (uint32_t)P.seq_hdr_bytes) + 1u + (uint32_t)leb128_len(run) + run;
+    if (P.chunk_record) {
+      unsigned long long ssum = 0;
+      uint32_t smax = 0;
+      for (int i = 0; i < 256; i++) { ssum += sym_sum[i]; smax = sym_max[i] > smax ? sym_max[i] : smax; }
+      atomicAdd(&P.chunk_record->n_symbols, ssum);
+      atomicMax(&P.chunk_record->max_tile_symbols, smax);
+    }
   }
   __syncthreads();
   uint32_t run = part[t];

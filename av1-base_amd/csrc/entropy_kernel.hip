@@ -615,29 +615,6 @@ __device__ __forceinline__ void sym_mv_component(Sym &y, int lane, int adapt, in
 
 __device__ __forceinline__ int icdf_prob(const Sym &y, int off, int el) { return (el > 0 ? y.cdf[off + el - 1] : 32768) - y.cdf[off + el]; }
 
-// Under a content-driven partition (P.part_map): does the superblock keep one block size throughout - no node between min_bs_log2
-// and max_bs_log2 splits by its mask?  (Only then does a tile hold exactly two (transform size, plane type) classes.)
-__device__ __forceinline__ bool sb_unsplit(const Av1miDevParams &P, int f, int sbr, int sbc) {
-  if (!P.part_map || P.min_bs_log2 >= P.max_bs_log2) return true;
-  const uint32_t m = P.part_map[((size_t)f * P.sb_rows + sbr) * P.sb_cols + sbc];
-  return P.max_bs_log2 >= 6 ? !(m & 1u) : (P.max_bs_log2 == 5 ? !(m & 0x1Eu) : !(m & 0x1FFFE0u));
-}
-
-// ... and does the frame edge leave it alone?  A node of the leaf size whose origin lies inside the frame must not be forced to split
-// (has_rows / has_cols of av1mi_node_split: a leaf may overhang the edge by less than half its size - the bottom superblock row of a
-// 1080-row frame, 56 rows, keeps its four 32x32 leaves; a row of 40 would not).
-__device__ __forceinline__ bool sb_uniform(const Av1miDevParams &P, int f, int sbr, int sbc) {
-  if (!sb_unsplit(P, f, sbr, sbc)) return false;
-  const int L = P.max_bs_log2, n = 1 << L;
-  if (L <= 3) return true;
-  for (int oy = 0; oy < 64; oy += n)
-    for (int ox = 0; ox < 64; ox += n) {
-      const int x = sbc * 64 + ox, yy = sbr * 64 + oy;
-      if (x < P.width && yy < P.height && (yy + (n >> 1) >= P.height || x + (n >> 1) >= P.width)) return false;
-    }
-  return true;
-}
-
 // FULL = false: regular tiles in adaptive mode - every leaf of the tile has one size, i.e. exactly two (tx size, plane type)
 // classes, no narrow rows in LDS (10.4 KB -> ~4 waves per SIMD).
 // FULL = true: tiles that mix sizes (content-driven partition, forced splits at the frame edge) and static-CDF mode.  Each variant
@@ -647,22 +624,18 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
                                                            const int16_t *__restrict__ levels, const Av1miBlkInfo *__restrict__ blk,
                                                            uint32_t *__restrict__ streams, uint32_t *__restrict__ stream_len,
                                                            uint32_t *__restrict__ tile_combos, const uint8_t *__restrict__ lr_choice,
-                                                           int tile0 /* chunk-wide index of this launch's first tile: launches cover whole frames */) {
+                                                           int tile0 /* chunk-wide index of this launch's first tile: launches cover whole frames */,
+                                                           int edge_grid /* 0: one workgroup per tile of the launch's frames; 1: per EDGE tile of them (av1mi_edge_tile) */) {
   // one wave per TILE of TSB x TSB superblocks (raster order inside the tile)
   const int tiles_per_frame = P.tile_rows * P.tile_cols, sbs_per_frame = P.sb_rows * P.sb_cols;
-  const int gt = (int)blockIdx.x + tile0;
+  int gt = (int)blockIdx.x + tile0;
+  if (edge_grid) { const int ne = av1mi_edge_tiles(P); gt = (tile0 / tiles_per_frame + (int)blockIdx.x / ne) * tiles_per_frame + av1mi_edge_tile(P, (int)blockIdx.x % ne); }
   const int f = gt / tiles_per_frame, tile = gt % tiles_per_frame;
   const int tr = tile / P.tile_cols, tc = tile % P.tile_cols;
   const int lane = threadIdx.x;
-  {
-    bool regular = !P.disable_cdf_update;
-    if (regular)   // (a tile whose superblocks mix block sizes holds more than two classes: the full variant's)
-      for (int si = 0; si < TSB * TSB; si++) {
-        const int sbr = tr * TSB + si / TSB, sbc = tc * TSB + si % TSB;
-        if (sbr < P.sb_rows && sbc < P.sb_cols) regular = regular && sb_uniform(P, f, sbr, sbc);
-      }
-    if (regular == FULL) return;
-  }
+  // (a tile whose superblocks mix block sizes holds more than two classes: the full variant's.  The launcher's grids are supersets
+  // of a variant's tiles; this test decides)
+  if (av1mi_tile_is_regular(P, f, tr, tc, TSB) == FULL) return;
   if constexpr (FULL) {
     for (int i = lane; i < CL::COEFF_BASE; i += 64) g_cdfw_full[i] = cdf_init[i];
     if (lane < 18) g_cdfw_full[CL::COEFF_BASE + lane] = 0;
@@ -1337,18 +1310,46 @@ extern "C" hipError_t av1mi_launch_entropy(const Av1miDevParams *P, const uint16
   const int n_tiles = count * tpf, tile0 = frame0 * tpf;
   bool has_inter = false, has_key = false;
   for (int f = frame0; f < frame0 + count; f++) { if (av1mi_frame_is_inter(*P, f)) has_inter = true; else has_key = true; }
-  // The two variants touch disjoint tiles.  The FULL one has few working waves (frame-edge tiles whose leaves the edge forces smaller)
-  // with a long serial chain each - 0.14 ms per 60-frame chunk when it ran after the regular one; on a stream of its own it runs
-  // beside it.
+  // The two variants touch disjoint tiles, and each is launched only over tiles that can be its own.  Under a content-driven partition
+  // the split masks are on the device: both take the whole grid.  Otherwise ownership is geometry (av1mi_tile_is_regular without a
+  // map): with static CDFs every tile is the full variant's; with adaptive ones only the frames' edge tiles can be, and the full
+  // variant runs over those alone - or not at all where the edge forces no split (1080p with 32x32 leaves: 30 600 waves of a 60-frame
+  // chunk that did nothing but find that out, beside the regular variant and taking wave slots from it).
+  bool regular_any = true, full_any = true, edge_grid = false;
+  if (!P->part_map) {
+    regular_any = !P->disable_cdf_update;
+    if (regular_any) {
+      full_any = false;
+      for (int e = 0; e < av1mi_edge_tiles(*P); e++) {
+        const int t = av1mi_edge_tile(*P, e);
+        if (!av1mi_tile_is_regular(*P, 0, t / P->tile_cols, t % P->tile_cols, P->tile_sb)) full_any = true;
+      }
+      edge_grid = full_any;
+    }
+  }
+  // The FULL variant has few working waves beside the regular one's (frame-edge tiles whose leaves the edge forces smaller) with a
+  // long serial chain each - 0.14 ms per 60-frame chunk when it ran after the regular one; on a stream of its own it runs beside it.
   hipStream_t fs = stream;
-  if (aux) {
+  const bool forked = aux && regular_any && full_any;
+  // Where the edge stream gets no kernel, the two events around it still go out.  They are not needed for ordering; they are kept
+  // because measured, four 1080p chunks in flight on one GPU (the product's default) lose 3.5 % without them - the contexts' kernels
+  // then run in step instead of one context's range coder beside another's reconstruction.  They cost a chunk 0.03 ms.
+  if (!forked && aux) {
+    (void)hipEventRecord(fork, stream); (void)hipStreamWaitEvent(aux, fork, 0);
+    (void)hipEventRecord(join, aux); (void)hipStreamWaitEvent(stream, join, 0);
+  }
+  if (forked) {
     (void)hipEventRecord(fork, stream);
     (void)hipStreamWaitEvent(aux, fork, 0);
     fs = aux;
   }
+  const int full_grid = edge_grid ? count * av1mi_edge_tiles(*P) : n_tiles;
 #define SYM_LAUNCH(FULLV, INTERV, TSBV)                                                                                                   \
-  hipLaunchKernelGGL((symbolize_tile_kernel<FULLV, INTERV, TSBV>), dim3(n_tiles), dim3(64), 0, (FULLV) ? fs : stream, *P, cdf_init, levels, blk, streams, \
-                     stream_len, tile_combos, lr_choice, tile0)
+  do {                                                                                                                                    \
+    if ((FULLV) ? full_any : regular_any)                                                                                                 \
+      hipLaunchKernelGGL((symbolize_tile_kernel<FULLV, INTERV, TSBV>), dim3((FULLV) ? full_grid : n_tiles), dim3(64), 0, (FULLV) ? fs : stream, *P, cdf_init, \
+                         levels, blk, streams, stream_len, tile_combos, lr_choice, tile0, (FULLV) && edge_grid ? 1 : 0);                  \
+  } while (0)
   if (P->tile_sb == 1) {
     if (has_key) { SYM_LAUNCH(false, false, 1); SYM_LAUNCH(true, false, 1); }
     if (has_inter) { SYM_LAUNCH(false, true, 1); SYM_LAUNCH(true, true, 1); }
@@ -1357,7 +1358,7 @@ extern "C" hipError_t av1mi_launch_entropy(const Av1miDevParams *P, const uint16
     if (has_inter) { SYM_LAUNCH(false, true, 2); SYM_LAUNCH(true, true, 2); }
   }
 #undef SYM_LAUNCH
-  if (aux) {
+  if (forked) {
     (void)hipEventRecord(join, aux);
     (void)hipStreamWaitEvent(stream, join, 0);
   }
