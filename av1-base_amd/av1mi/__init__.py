@@ -36,7 +36,7 @@ E_INVALID_ARG, E_NO_DEVICE, E_HIP, E_OOM, E_OVERFLOW, E_FORMAT, E_UNSUPPORTED = 
 
 # every symbol include/av1mi.h declares
 ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", "av1mi_last_error", "av1mi_encode_chunk",
-               "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes"]
+               "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex"]
 
 
 class Params(C.Structure):
@@ -112,6 +112,7 @@ _lib.av1mi_abi_version.restype = C.c_uint32
 _lib.av1mi_struct_sizes.argtypes = [C.POINTER(C.c_uint32), C.c_uint32]
 _lib.av1mi_struct_sizes.restype = C.c_uint32
 ABI_VERSION = 8   # include/av1mi.h: AV1MI_ABI_VERSION this mirror was written against
+_lib.av1mi_aq_qindex.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8)]
 _lib.av1mi_write_headers.argtypes = [C.POINTER(Params), C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_size_t)]
 
 
@@ -144,9 +145,30 @@ def _raise_for(rc, detail=""):
     raise EncodeFailed(rc, detail)
 
 
-def default_params(width, height, bit_depth=8, **kw):
+AQ_MAX_STRENGTH = 4
+
+
+def cq_aq(cq, strength):
+    """include/av1mi.h: AV1MI_CQ_AQ - the cq_level field with the strength of the adaptive quantisation in bits 8-10"""
+    return (cq & 0xFF) | ((strength & 7) << 8)
+
+
+def cq_level_of(v):
+    """include/av1mi.h: AV1MI_CQ_LEVEL"""
+    return v & 0xFF
+
+
+def aq_strength_of(v):
+    """include/av1mi.h: AV1MI_AQ_STRENGTH"""
+    return (v >> 8) & 7
+
+
+def default_params(width, height, bit_depth=8, aq_strength=None, **kw):
+    """aq_strength: packed into cq_level beside the CQ level (cq_aq); every other keyword sets the structure field of its name"""
     p = Params()
     _lib.av1mi_default_params(C.byref(p), width, height, bit_depth)
+    if aq_strength is not None:
+        kw["cq_level"] = cq_aq(kw.get("cq_level", p.cq_level), aq_strength)
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)
@@ -250,6 +272,22 @@ class Context:
                                    min_scene_len, sad, cut)
         _raise_for(rc, self.last_error())
         return list(sad), list(cut), state
+
+    def aq_qindex(self, params, frames, n_frames, on_device=False):
+        """The quantiser index of every superblock of every frame (include/av1mi.h: av1mi_aq_qindex) as a numpy array
+        [frame][superblock row][superblock column]; frames as for scene_cuts."""
+        import numpy as np
+        cw, ch = (params.width + 7) & ~7, (params.height + 7) & ~7
+        sbc, sbr = (cw + 63) // 64, (ch + 63) // 64
+        out = np.zeros((n_frames, sbr, sbc), dtype=np.uint8)
+        if on_device:
+            fptr = C.c_void_p(int(frames))
+        else:
+            keep = bytes(frames)
+            fptr = C.cast(C.c_char_p(keep), C.c_void_p)
+        rc = _lib.av1mi_aq_qindex(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0, out.ctypes.data_as(C.POINTER(C.c_uint8)))
+        _raise_for(rc, self.last_error())
+        return out
 
     def encode_chunk(self, params, frames, n_frames, on_device=False, want_recon=False, recon_ptr=None, copy_out=True):
         """frames: bytes-like/numpy (host) or an int device pointer (on_device=True).

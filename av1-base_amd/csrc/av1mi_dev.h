@@ -51,6 +51,12 @@ struct Av1miDevParams {
   // content-driven partition (av1mi_params.partition_search): null, or per frame of the chunk and superblock the split mask
   // partition_kernel wrote (av1mi_node_split below); a node larger than min_bs_log2 and not larger than max_bs_log2 follows it
   const uint32_t *part_map;
+  // activity-adaptive quantisation (av1mi_params.cq_level bits 8-10, aq_rule.h): null, or per frame of the chunk and superblock the
+  // quantiser index the superblock is coded with, base_q_idx + 4 d (aq_map_kernel).  The reconstruction takes the steps of the index's
+  // slot (av1mi_aq_slot below) once per superblock, symbolize codes the index against the tile's CurrentQIndex (read_delta_qindex);
+  // everything else a kernel derives from the quantiser - deblocking level, partition threshold, quantiser-matrix level, coefficient
+  // q context, range-coder stages - stays with base_q_idx
+  const uint8_t *aq_map;
   uint32_t mode_mask;
   int angle_delta;          // 1: directional winners of the luma mode decision are refined over the angle deltas -3 .. +3
   int edge_filter;          // enable_intra_edge_filter
@@ -105,6 +111,16 @@ struct Av1miDevParams {
   Av1miChunkRecord *chunk_record;
   const uint32_t *tile_symbols;
 };
+
+// ---- adaptive quantisation: the parameter block in device memory is followed by one copy per quantiser slot, equal to it except for
+// dc_q, ac_q, their reciprocals and the quantiser-matrix slice.  Slot 0 is the block itself (base_q_idx); slot 1 + 6 + d holds
+// base_q_idx + 4 d, d = -6 .. 6 (an index outside 1 .. 255 never occurs in a map: its slot repeats the base).
+#define AV1MI_AQ_SLOTS 14
+AV1MI_HD inline int av1mi_aq_slot(int qindex, int base_q_idx) { return 7 + (qindex - base_q_idx) / 4; }
+AV1MI_HD inline int av1mi_aq_slot_qindex(int slot, int base_q_idx) {
+  const int q = slot ? base_q_idx + 4 * (slot - 7) : base_q_idx;
+  return q >= 1 && q <= 255 ? q : base_q_idx;
+}
 
 // ---- partition: does the node of size 2^bsl at superblock-local (ox, oy) split?  One rule for every kernel that
 // walks blocks (reconstruction, motion search, symbolize).  The syntax forces a split where the node's half point is outside the
@@ -244,7 +260,8 @@ struct Av1miCdfLayout {
     RESTORE_SW = USE_WIENER + 3,           // [4] restoration_type of RESTORE_SWITCHABLE frames: NONE, WIENER, SGRPROJ
     CFL_SIGN = RESTORE_SW + 4,             // [9]
     CFL_ALPHA = CFL_SIGN + 9,              // [6][17]
-    COEFF_BASE = CFL_ALPHA + 6 * 17,       // [5][2][42][5]
+    DELTA_Q = CFL_ALPHA + 6 * 17,          // [5] delta_q_abs (adaptive quantisation)
+    COEFF_BASE = DELTA_Q + 5,              // [5][2][42][5]
     COEFF_BR = COEFF_BASE + 420 * 5,       // [5][2][21][5]
     INTRA_TOTAL = COEFF_BR + 210 * 5,      // everything a key frame needs
     // inter frames

@@ -75,7 +75,7 @@ extern "C" int av1mi_job_execute(const av1mi_exec_job *job, av1mi_state_cb state
   if (!job || !job->id || !job->input_path || !job->output_path || !job->temp_base_dir) return AV1MI_E_INVALID_ARG;
   ExecState st = {};
   st.cb = state_cb; st.user = user;
-  st.m.crf = job->params.cq_level; st.m.workers = job->workers;
+  st.m.crf = AV1MI_CQ_LEVEL(job->params.cq_level); st.m.workers = job->workers;
   auto fail = [&](int code, const std::string &msg) {
     if (error && error_cap) snprintf(error, error_cap, "%s", msg.c_str());
     set_stage(st, "failed");                         // JobState::Failed(msg)

@@ -25,9 +25,11 @@
 #include "../../include/av1mi.h"
 #include "av1_tables.h"
 #include "av1mi_dev.h"
+#include "aq_rule.h"
 
 extern "C" {
 hipError_t av1mi_launch_partition(const Av1miDevParams *P, const void *frames, uint32_t *part, hipStream_t stream);
+hipError_t av1mi_launch_aq(const Av1miDevParams *P, const void *frames, uint16_t *act, uint8_t *qmap, int strength, hipStream_t stream);
 // one translation unit per (largest leaf, sample type): recon_kernel.hip, recon8_kernel.hip, recon64_kernel.hip, recon64_8_kernel.hip
 #define AV1MI_RECON_PROTO(name) hipError_t name(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels, \
                                                Av1miBlkInfo *blk, const void *ref, const unsigned long long *me_best, const uint32_t *part, hipStream_t s)
@@ -98,6 +100,7 @@ struct Resolved {
   int tile_sb, tile_cols, tile_rows;  // tiles of tile_sb x tile_sb superblocks (1, or 2 beyond 64 superblocks either way)
   int qm_level;                       // quantiser-matrix level of all planes (15 = flat); only meaningful with p.enable_qm
   int lr_chroma;                      // enable_lr 3 / 4: U and V restored as well (p.enable_lr then holds the type: 1 / 2)
+  int aq;                             // strength of the adaptive quantisation, 0 = off (p.cq_level then holds the CQ level alone)
 };
 
 // aom's quantizer_to_qindex[] (CQ level -> base_q_idx); 30 -> 120
@@ -114,6 +117,10 @@ int resolve(const av1mi_params *in, Resolved *r) {
   r->padded = r->cw != (int)p.width || r->ch != (int)p.height;
   if (p.bit_depth != 8 && p.bit_depth != 10) return AV1MI_E_INVALID_ARG;
   // cq_level 0 is base_q_idx 0: CodedLossless frames (spec 5.9.2), whose syntax this encoder does not write (no WHT, no lossless header)
+  // ... and bits 8-10 of the field are the strength of the adaptive quantisation, 0 .. 4; nothing above them
+  r->aq = (int)AV1MI_AQ_STRENGTH(p.cq_level);
+  if ((p.cq_level >> 11) || r->aq > AV1MI_AQ_MAX_STRENGTH) return AV1MI_E_INVALID_ARG;
+  p.cq_level = AV1MI_CQ_LEVEL(p.cq_level);
   if (p.cq_level == 0 || p.cq_level > 63 || p.film_grain > 50) return AV1MI_E_INVALID_ARG;
   if (p.keyint == 0) p.keyint = 1;
   if (p.me_range == 0) p.me_range = 8;
@@ -276,7 +283,11 @@ std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint
   b.put(r.p.enable_qm ? 1 : 0, 1);  // using_qmatrix
   if (r.p.enable_qm) { b.put((uint32_t)r.qm_level, 4); b.put((uint32_t)r.qm_level, 4); }  // qm_y, qm_u (= qm_v: separate_uv_delta_q = 0)
   b.put(0, 1);  // segmentation_enabled
-  if (r.qidx > 0) b.put(0, 1);  // delta_q_present
+  if (r.qidx > 0) b.put(r.aq ? 1 : 0, 1);  // delta_q_present
+  if (r.aq) {
+    b.put(2, 2);  // delta_q_res: deltas in steps of 4
+    b.put(0, 1);  // delta_lf_present
+  }
   {  // loop_filter_params (§5.9.11): level 0 = deblocking off
     const uint32_t lv = (uint32_t)deblock_level(r, !inter);
     b.put(lv, 6); b.put(lv, 6);          // loop_filter_level[0..1]
@@ -421,6 +432,7 @@ std::vector<uint16_t> make_cdf_blob(int qidx) {
   emit_rows(v, CL::RESTORE_SW, av1_default_switchable_restore_cdf, 1, 4, nullptr, 3);
   emit_rows(v, CL::CFL_SIGN, av1_default_cfl_sign_cdf, 1, 9, nullptr, 8);
   emit_rows(v, CL::CFL_ALPHA, av1_default_cfl_alpha_cdf, 6, 17, nullptr, 16);
+  emit_rows(v, CL::DELTA_Q, av1_default_delta_q_cdf, 1, 5, nullptr, 4);
   // inter frames
   emit_rows(v, CL::IF_Y_MODE, av1_default_if_y_mode_cdf, 4, 14, nullptr, 13);
   emit_rows(v, CL::IS_INTER, av1_default_is_inter_cdf, 4, 3, nullptr, 2);
@@ -479,7 +491,9 @@ struct Workspace {
   uint32_t *d_centre = nullptr;            // me_presearch: centre code of the full search per [frame][superblock]
   uint32_t *d_part = nullptr;              // content-driven partition: split mask per [frame][superblock] (partition_kernel)
   uint32_t *d_me64 = nullptr;              // 64x64 leaves: the search's [frame][superblock][candidate] SAD table
-  Av1miQmEntry *d_qm = nullptr;        // quantiser-matrix steps (Av1miDevParams::qm_tab), valid for qm_key = (level, qidx, bit depth)
+  uint16_t *d_aq_act = nullptr;            // adaptive quantisation: E per [frame][superblock] (aq_activity_kernel)
+  uint8_t *d_aq_map = nullptr;             // ... the quantiser index per [frame][superblock] (aq_map_kernel)
+  Av1miQmEntry *d_qm = nullptr;        // quantiser-matrix steps (Av1miDevParams::qm_tab), one slice per quantiser slot, valid for qm_key = (slices, level, qidx, bit depth)
   std::vector<Av1miQmEntry> h_qm; int qm_key = -1;
   uint8_t *d_lrc = nullptr;            // per restoration unit: 0 = off, k = candidate k-1
   unsigned long long *d_lrsse = nullptr;  // per restoration unit: the candidates' SSE sums (scratch of lr_kernel.hip's two phases)
@@ -492,7 +506,7 @@ struct Workspace {
   uint8_t *h_hdr = nullptr; uint16_t *h_cdf = nullptr; Av1miDevParams *h_params = nullptr;
   size_t hdr_bytes = 0;                // bytes of h_hdr that d_hdr is known to hold; 0: unknown (the strength search writes into d_hdr)
   int cdf_qidx = -1;                   // the quantiser index d_cdf was made for (the blob depends on nothing else); -1: none
-  bool params_on_device = false;       // d_params holds *h_params
+  int params_on_device = 0;            // d_params holds the first so many blocks of h_params (1, or AV1MI_AQ_SLOTS with adaptive quantisation)
   Av1miChunkRecord *h_record = nullptr; unsigned long long *h_sse = nullptr;   // d_record and d_sse land here
   size_t out_cap = 0, me64_bytes = 0, h_out_cap = 0;   // bytes of d_out, d_me64, h_out
   std::vector<std::pair<void *, bool>> owned;   // every buffer above: (address, page-locked host memory)
@@ -585,7 +599,7 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     HIPCHK(c, ws_alloc(w, w.d_out, w.out_cap));
     HIPCHK(c, ws_alloc(w, w.d_hdr, 256 + nf * 512));
     HIPCHK(c, ws_alloc(w, w.d_cdf, Av1miCdfLayout::TOTAL * sizeof(uint16_t)));
-    HIPCHK(c, ws_alloc(w, w.d_params, sizeof(Av1miDevParams)));
+    HIPCHK(c, ws_alloc(w, w.d_params, AV1MI_AQ_SLOTS * sizeof(Av1miDevParams)));
     for (uint32_t **b : { &w.d_tile_bytes, &w.d_tile_off, &w.d_sym, &w.d_combos }) HIPCHK(c, ws_alloc(w, *b, nf * nsb * 4));
     HIPCHK(c, ws_alloc(w, w.d_streams, nf * ntile * (size_t)tile_stream_cap(r, c->cap_scale) * 4));
     for (uint32_t **b : { &w.d_frame_size, &w.d_payload }) HIPCHK(c, ws_alloc(w, *b, nf * 4));
@@ -593,7 +607,7 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     HIPCHK(c, ws_alloc(w, w.d_sse, nf * 3 * 8));
     {  // the five small host mirrors share one page-locked block: an allocation of page-locked memory costs far more than they hold
       auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-      const size_t b_hdr = up(256 + nf * 512), b_cdf = up(Av1miCdfLayout::TOTAL * sizeof(uint16_t)), b_par = up(sizeof(Av1miDevParams)),
+      const size_t b_hdr = up(256 + nf * 512), b_cdf = up(Av1miCdfLayout::TOTAL * sizeof(uint16_t)), b_par = up(AV1MI_AQ_SLOTS * sizeof(Av1miDevParams)),
                    b_rec = up(sizeof(Av1miChunkRecord) + (nf + 1) * 8), b_sse = up(nf * 3 * 8);
       uint8_t *h = nullptr;
       HIPCHK(c, ws_alloc(w, h, b_hdr + b_cdf + b_par + b_rec + b_sse, true));
@@ -618,6 +632,10 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     const size_t nc = 2 * (size_t)(p.me_range ? p.me_range : 8) + 1, need = nf * nsb * nc * nc * sizeof(uint32_t);
     if (w.me64_bytes < need) { w.me64_bytes = 0; HIPCHK(c, ws_alloc(w, w.d_me64, need)); w.me64_bytes = need; }
   }
+  if (r.aq && !w.d_aq_map) {
+    HIPCHK(c, ws_alloc(w, w.d_aq_act, nf * nsb * sizeof(uint16_t)));
+    HIPCHK(c, ws_alloc(w, w.d_aq_map, nf * nsb));
+  }
   if (p.cdef_search && !w.d_cdef_err) {
     HIPCHK(c, ws_alloc(w, w.d_cdef_err, nf * nsb * 24 * sizeof(unsigned long long)));
     HIPCHK(c, ws_alloc(w, w.d_cdef_idx, nf * nsb));
@@ -632,18 +650,24 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   w.res = r;
   if (p.enable_qm && r.qm_level < 15) {
     // dequantiser step per coefficient position (§7.12.3) and its reciprocal, for the square transform sizes 4..32
-    if (!w.d_qm) HIPCHK(c, ws_alloc(w, w.d_qm, 2 * AV1MI_QM_PLANE * sizeof(Av1miQmEntry)));
-    const int key = (r.qm_level << 16) | (r.qidx << 4) | (int)p.bit_depth;
+    // with adaptive quantisation one slice per quantiser slot (av1mi_aq_slot): the superblock's steps through the frame's matrix
+    if (!w.d_qm) HIPCHK(c, ws_alloc(w, w.d_qm, AV1MI_AQ_SLOTS * 2 * AV1MI_QM_PLANE * sizeof(Av1miQmEntry)));
+    const int slices = r.aq ? AV1MI_AQ_SLOTS : 1;
+    const int key = (slices << 24) | (r.qm_level << 16) | (r.qidx << 4) | (int)p.bit_depth;
     if (w.qm_key != key) {
       static const int off[4] = { AV1MI_QM_4X4, AV1MI_QM_8X8, AV1MI_QM_16X16, AV1MI_QM_32X32 };
-      w.h_qm.resize(2 * AV1MI_QM_PLANE);
-      for (int pt = 0; pt < 2; pt++)
-        for (int l2 = 2; l2 <= 5; l2++)
-          for (int i = 0; i < (1 << (2 * l2)); i++) {
-            const uint32_t q = (uint32_t)(i ? r.ac_q : r.dc_q);
-            const uint32_t q2 = (q * av1_qm_iwt[r.qm_level][pt][off[l2 - 2] + i] + 16) >> 5;
-            w.h_qm[pt * AV1MI_QM_PLANE + off[l2 - 2] + i] = { q2, (uint32_t)((((uint64_t)1 << 32) + q2 - 1) / q2) };
-          }
+      w.h_qm.resize((size_t)slices * 2 * AV1MI_QM_PLANE);
+      for (int sl = 0; sl < slices; sl++) {
+        const int qi = av1mi_aq_slot_qindex(sl, r.qidx);
+        const int dcq = p.bit_depth == 8 ? av1_dc_q8[qi] : av1_dc_q10[qi], acq = p.bit_depth == 8 ? av1_ac_q8[qi] : av1_ac_q10[qi];
+        for (int pt = 0; pt < 2; pt++)
+          for (int l2 = 2; l2 <= 5; l2++)
+            for (int i = 0; i < (1 << (2 * l2)); i++) {
+              const uint32_t q = (uint32_t)(i ? acq : dcq);
+              const uint32_t q2 = (q * av1_qm_iwt[r.qm_level][pt][off[l2 - 2] + i] + 16) >> 5;
+              w.h_qm[(size_t)(sl * 2 + pt) * AV1MI_QM_PLANE + off[l2 - 2] + i] = { q2, (uint32_t)((((uint64_t)1 << 32) + q2 - 1) / q2) };
+            }
+      }
       HIPCHK(c, hipMemcpyAsync(w.d_qm, w.h_qm.data(), w.h_qm.size() * sizeof(Av1miQmEntry), hipMemcpyHostToDevice, c->stream));
       w.qm_key = key;
     }
@@ -653,7 +677,7 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
 
 // The kernels' parameters of a chunk of `n_frames` frames: `r` at the coded size, the per-tile capacities of multiplier `scale` and the
 // workspace buffers the kernels find through them.  The header sizes follow with the headers (prepare_chunk).
-Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const uint32_t *part, const Av1miQmEntry *qm,
+Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const uint32_t *part, const Av1miQmEntry *qm, const uint8_t *aq_map,
                           unsigned long long *cdef_err, int8_t *cdef_idx, uint8_t *cdef_sel, Av1miChunkRecord *record, const uint32_t *tile_symbols) {
   const av1mi_params &p = r.p;
   Av1miDevParams P;
@@ -672,6 +696,7 @@ Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const
   P.max_bs_log2 = (int)p.block_log2;
   P.min_bs_log2 = p.partition_search ? (int)p.min_block_log2 : (int)p.block_log2;
   P.part_map = p.partition_search ? part : nullptr;
+  P.aq_map = r.aq ? aq_map : nullptr;
   P.mode_mask = p.intra_mode_mask ? (p.intra_mode_mask & 0x1FFF) : 0x0007;  // default candidates: DC, V, H
   P.angle_delta = p.intra_angle_delta ? 1 : 0; P.edge_filter = p.intra_edge_filter ? 1 : 0; P.cfl = p.cfl ? 1 : 0; P.tx_search = p.tx_search ? 1 : 0;
   P.enable_cdef = p.enable_cdef ? 1 : 0;
@@ -955,6 +980,47 @@ int av1mi_scene_cuts(av1mi_ctx *c, const av1mi_params *params, const void *frame
   return AV1MI_OK;
 }
 
+// The adaptive quantisation's decision alone: the same two launches the encoder runs on a chunk's source (av1mi_launch_aq), on buffers of
+// the call's own.
+int av1mi_aq_qindex(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, uint8_t *qindex) {
+  if (!c || !frames || !qindex || n_frames == 0) return AV1MI_E_INVALID_ARG;
+  Resolved r;
+  int rc = resolve(params, &r);
+  if (rc) { set_err(c, "invalid parameters"); return rc; }
+  const size_t nsb = (size_t)r.sb_cols * r.sb_rows, n_map = (size_t)n_frames * nsb;
+  if (!r.aq) { memset(qindex, r.qidx, n_map); return AV1MI_OK; }
+  if (frames_on_device && ((uintptr_t)frames & 15)) { set_err(c, "device frames must be 16-byte aligned"); return AV1MI_E_INVALID_ARG; }
+  HIPCHK(c, hipSetDevice(c->device));
+  const int bps = r.p.bit_depth > 8 ? 2 : 1;
+  const size_t in_bytes = (size_t)n_frames * r.p.width * r.p.height * 3 / 2 * bps, coded_bytes = (size_t)n_frames * r.cw * r.ch * 3 / 2 * bps;
+  const Av1miDevParams P = dev_params(r, n_frames, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  hipStream_t s = c->stream;
+  void *d_in = nullptr, *d_coded = nullptr;
+  uint16_t *d_act = nullptr;
+  uint8_t *d_map = nullptr;
+  auto cleanup = [&] { for (void *b : { d_in, d_coded, (void *)d_act, (void *)d_map }) if (b) (void)hipFree(b); };
+  hipError_t e = hipMalloc((void **)&d_act, n_map * sizeof(uint16_t));
+  if (e == hipSuccess) e = hipMalloc((void **)&d_map, n_map);
+  const void *src = frames;
+  if (e == hipSuccess && !frames_on_device) {
+    e = hipMalloc(&d_in, in_bytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in, frames, in_bytes, hipMemcpyHostToDevice, s);
+    src = d_in;
+  }
+  if (e == hipSuccess && r.padded) {   // the rule reads the coded size: edge-extended as the encoder's source is
+    e = hipMalloc(&d_coded, coded_bytes);
+    if (e == hipSuccess) e = av1mi_launch_pad(src, d_coded, (int)r.p.width, (int)r.p.height, r.cw, r.ch, (int)r.p.bit_depth, (int)n_frames, 0, s);
+    src = d_coded;
+  }
+  if (e == hipSuccess) e = av1mi_launch_aq(&P, src, d_act, d_map, r.aq, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(qindex, d_map, n_map, hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);   // (also after a failure: nothing may still read the buffers freed below)
+  cleanup();
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) { set_err(c, "adaptive-quantisation pass failed: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? AV1MI_E_OOM : AV1MI_E_HIP; }
+  return AV1MI_OK;
+}
+
 static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
                              av1mi_buf *out, uint32_t *frame_sizes, void *recon, av1mi_report *report);
 
@@ -1004,11 +1070,28 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
     HIPCHK(c, hipMemcpyAsync(w.d_cdf, w.h_cdf, cdf.size() * 2, hipMemcpyHostToDevice, s));
     w.cdf_qidx = r.qidx;
   }
-  if (!w.params_on_device || memcmp(w.h_params, &P, sizeof(P))) {   // (dev_params clears the padding; a cap_scale change shows in P)
-    w.params_on_device = false;
-    memcpy(w.h_params, &P, sizeof(P));
-    HIPCHK(c, hipMemcpyAsync(w.d_params, w.h_params, sizeof(P), hipMemcpyHostToDevice, s));  // the recon kernel reads its parameters from device memory
-    w.params_on_device = true;
+  {
+    // The recon kernel reads its parameters from device memory.  With adaptive quantisation the block is followed by one copy per
+    // quantiser slot (av1mi_aq_slot) that differs in the quantiser steps, their reciprocals and the quantiser-matrix slice alone: the
+    // walk takes its superblock's copy, and everything else it reads there is what the first block holds.
+    const int n_par = P.aq_map ? AV1MI_AQ_SLOTS : 1;
+    std::vector<Av1miDevParams> par((size_t)n_par, P);
+    for (int sl = 1; sl < n_par; sl++) {
+      const int qi = av1mi_aq_slot_qindex(sl, r.qidx);
+      Av1miDevParams &Q = par[(size_t)sl];
+      Q.dc_q = P.bit_depth == 8 ? av1_dc_q8[qi] : av1_dc_q10[qi];
+      Q.ac_q = P.bit_depth == 8 ? av1_ac_q8[qi] : av1_ac_q10[qi];
+      Q.dc_recip = (uint32_t)((((uint64_t)1 << 32) + Q.dc_q - 1) / Q.dc_q);
+      Q.ac_recip = (uint32_t)((((uint64_t)1 << 32) + Q.ac_q - 1) / Q.ac_q);
+      if (P.qm_tab) Q.qm_tab = P.qm_tab + (size_t)sl * 2 * AV1MI_QM_PLANE;
+    }
+    const size_t bytes = (size_t)n_par * sizeof(P);
+    if (w.params_on_device < n_par || memcmp(w.h_params, par.data(), bytes)) {   // (dev_params clears the padding; a cap_scale change shows in P)
+      w.params_on_device = 0;
+      memcpy(w.h_params, par.data(), bytes);
+      HIPCHK(c, hipMemcpyAsync(w.d_params, w.h_params, bytes, hipMemcpyHostToDevice, s));
+      w.params_on_device = n_par;
+    }
   }
   HIPCHK(c, hipMemsetAsync(w.d_record, 0, sizeof(Av1miChunkRecord), s));
   HIPCHK(c, hipMemsetAsync(w.d_sse, 0, (size_t)n_frames * 24, s));
@@ -1023,6 +1106,8 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   // content-driven partition: the split masks of every superblock of the chunk, from the source, before anything walks blocks (the second
   // stream's motion search waits for EV_SRC_READY as well)
   if (P.part_map) HIPCHK(c, av1mi_launch_partition(&P, *d_src, w.d_part, s));
+  // adaptive quantisation: every superblock's quantiser index, likewise from the source and on the device - the walks and symbolize read the map
+  if (P.aq_map) HIPCHK(c, av1mi_launch_aq(&P, *d_src, w.d_aq_act, w.d_aq_map, r.aq, s));
   HIPCHK(c, hipEventRecord(c->ev[EV_SRC_READY], s));
   return AV1MI_OK;
 }
@@ -1147,6 +1232,7 @@ static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
     const uint8_t *reff = inter ? (const uint8_t *)w.d_fin + (f - 1) * fbytes : nullptr;
     const unsigned long long *mef = inter ? (P.subpel ? w.d_me_sub : w.d_me) + f * nb8 : nullptr;
     if (inter) HIPCHK(c, hipStreamWaitEvent(s, c->me_ev[f], 0));
+    if (P.aq_map) P1.aq_map = P.aq_map + f * nsb;   // (the launch's first frame on, like the split masks)
     HIPCHK(c, recon_launcher(P)(&P1, w.d_params, srcf, recf, lvf, blkf, reff, mef, P.part_map ? P.part_map + f * nsb : nullptr, s));
     for (int i = 0; i < 4; i++) P1.lf_level[i] = inter ? P.lf_level_inter[i] : P.lf_level[i];
     if (P1.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P1, recf, blkf, s));
@@ -1277,7 +1363,7 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
   if (rc != AV1MI_OK && rc != AV1MI_E_OVERFLOW) {
     // a chunk that broke off may have left uploads from the page-locked copies in flight or undone: let them end, trust none of them
     (void)hipStreamSynchronize(c->stream);
-    c->ws.hdr_bytes = 0; c->ws.cdf_qidx = -1; c->ws.params_on_device = false;
+    c->ws.hdr_bytes = 0; c->ws.cdf_qidx = -1; c->ws.params_on_device = 0;
   }
   return rc;
 }
@@ -1292,7 +1378,7 @@ static int run_chunk(av1mi_ctx *c, const av1mi_params *params, const void *frame
   rc = ensure_workspace(c, r, n_frames);
   if (rc) return rc;
   Workspace &w = c->ws;
-  c->P = dev_params(r, n_frames, c->cap_scale, w.d_part, w.d_qm, w.d_cdef_err, w.d_cdef_idx, w.d_cdef_sel, w.d_record, w.d_sym);
+  c->P = dev_params(r, n_frames, c->cap_scale, w.d_part, w.d_qm, w.d_aq_map, w.d_cdef_err, w.d_cdef_idx, w.d_cdef_sel, w.d_record, w.d_sym);
   const void *d_src = nullptr;
   rc = prepare_chunk(c, r, frames, n_frames, frames_on_device, &d_src);
   if (rc) return rc;

@@ -61,7 +61,8 @@ struct CC {
     DC_SIGN = EOB_EXTRA + 2 * 9 * 3,     // [2][3][3] as in the full layout
     COEFF_BASE_EOB = DC_SIGN + 18,       // [2][4][4]
     USE_WIENER = COEFF_BASE_EOB + 2 * 16, RESTORE_SW = USE_WIENER + 3, CFL_SIGN = RESTORE_SW + 4, CFL_ALPHA = CFL_SIGN + 9,
-    TOTAL = CFL_ALPHA + 6 * 17
+    DELTA_Q = CFL_ALPHA + 6 * 17,
+    TOTAL = DELTA_Q + 5
   };
 };
 static_assert(CL::COEFF_BASE - CL::USE_WIENER == CC::TOTAL - CC::USE_WIENER, "the trailing tables are copied as one piece");
@@ -692,6 +693,7 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
   // 2 bits per plane (bits 2 p .. 2 p + 1: plane p):
   int lr_prev = 0;  // RefLrWiener of the tile: 0 = Wiener_Taps_Mid, k = candidate k-1 (the plane's last unit coded with a Wiener filter)
   int sgr_prev = 0; // RefSgrXqd of the tile: 0 = Sgrproj_Xqd_Mid, k = self-guided candidate k-1 (the plane's last self-guided unit)
+  int cur_q = P.base_q_idx;   // CurrentQIndex (adaptive quantisation): base_q_idx at the tile start, then the last index a delta was coded for
 #pragma nounroll
   for (int si = 0; si < TSB * TSB; si++) {
   const int sbr = tr * TSB + si / TSB, sbc = tc * TSB + si % TSB;
@@ -706,6 +708,7 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
 #define INFO(ux_, uy_) TI.info[((uy_) + toy8) * TW + (ux_) + tox8]
   const int16_t *sb_levels = levels + ((size_t)f * sbs_per_frame + sb) * AV1MI_SB_LEVELS;
   int cdef_todo = P.cdef_bits > 0;   // read_cdef: the superblock's cdef_idx is coded at its first block that is not skipped
+  int dq_todo = P.aq_map != nullptr;   // read_delta_qindex: at the superblock's first block
   if (si % TSB == 0) {  // clear_left_context at the start of every superblock row of the tile
     __syncthreads();
     if (lane < 48) { (&S->left_lvl[0][0])[lane] = 0; (&S->left_dc[0][0])[lane] = 0; }
@@ -791,6 +794,21 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
           const int ci = uni(P.cdef_idx[(size_t)f * sbs_per_frame + sb]);
           for (int i = P.cdef_bits - 1; i >= 0; i--) sym_bool(y, lane, (ci >> i) & 1, 16384);
           cdef_todo = 0;
+        }
+        if (dq_todo) {   // read_delta_qindex (§5.11.46): delta_q_present = 1, delta_q_res = 2, i.e. steps of 4
+          dq_todo = 0;
+          if (!(bsl == 6 && skip)) {   // a skipped 64x64 block codes none: CurrentQIndex stays (its levels are all zero - no step is used)
+            const int qsb = uni(P.aq_map[(size_t)f * sbs_per_frame + sb]);
+            const int r = (qsb - cur_q) / 4, a = iabs(r);
+            sym_wide(y, lane, adapt, imin(a, 3), FULL ? CL::DELTA_Q : CC::DELTA_Q, 4);   // delta_q_abs
+            if (a >= 3) {   // delta_q_rem_bits L(3), delta_q_abs_bits L(rem_bits + 1)
+              const int nb = floor_log2((unsigned)(a - 1)), rest = a - 1 - (1 << nb);
+              for (int i = 2; i >= 0; i--) sym_bool(y, lane, ((nb - 1) >> i) & 1, 16384);
+              for (int i = nb - 1; i >= 0; i--) sym_bool(y, lane, (rest >> i) & 1, 16384);
+            }
+            if (a) sym_bool(y, lane, r < 0, 16384);   // delta_q_sign_bit
+            cur_q = qsb;
+          }
         }
         const int is_inter = inter_frame ? uni(INFO(b8x, b8y).is_inter) : 0;
         if (inter_frame) {

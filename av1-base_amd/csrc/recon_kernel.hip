@@ -1593,7 +1593,8 @@ __global__ void __launch_bounds__(WalkSplit<INTER>::value ? 128 : 64) __attribut
                                                      int16_t *__restrict__ levels, Av1miBlkInfo *__restrict__ blk,
                                                      const PIX *__restrict__ ref /* inter frame: previous final reconstruction, one frame */,
                                                      const unsigned long long *__restrict__ me_best,
-                                                     const uint32_t *__restrict__ part /* split masks of the launch's first frame on (null: partition by geometry) */) {
+                                                     const uint32_t *__restrict__ part /* split masks of the launch's first frame on (null: partition by geometry) */,
+                                                     const uint8_t *__restrict__ aq /* adaptive quantisation: quantiser indices of the launch's first frame on (null: base_q_idx) */) {
   // The parameters come through a pointer to device memory, not by value: the transform items are `noinline` and take the
   // address of the block, and the address of a by-value kernel argument is a private copy - every lane wrote the whole
   // structure (0.6 KB) to scratch at the start of the kernel and read its fields back from there.  Loads through a
@@ -1616,13 +1617,25 @@ __global__ void __launch_bounds__(WalkSplit<INTER>::value ? 128 : 64) __attribut
   const int tile_mi_r1 = (tile_mi_r0 + TSB * 16 < P.mi_rows) ? tile_mi_r0 + TSB * 16 : P.mi_rows;
   const int tile_mi_c1 = (tile_mi_c0 + TSB * 16 < P.mi_cols) ? tile_mi_c0 + TSB * 16 : P.mi_cols;
   const PIX *frame = src + (size_t)f * P.frame_samples;
+  // adaptive quantisation: the quantiser slots (av1mi_aq_slot) of the tile's superblocks, four bits each - one scalar across the walk
+  uint32_t aq_slots = 0;
+  if (aq) {
+    for (int si = 0; si < TSB * TSB; si++) {
+      const int sbr = tr * TSB + si / TSB, sbc = tc * TSB + si % TSB;
+      if (sbr < P.sb_rows && sbc < P.sb_cols)
+        aq_slots |= (uint32_t)uniform_i(av1mi_aq_slot((int)aq[(size_t)f * sbs_per_frame + sbr * P.sb_cols + sbc], P.base_q_idx)) << (4 * si);
+    }
+  }
 #pragma nounroll
   for (int si = 0; si < TSB * TSB; si++) {
     const int sbr = tr * TSB + si / TSB, sbc = tc * TSB + si % TSB;
     if (sbr >= P.sb_rows || sbc >= P.sb_cols) continue;
     const int sb = sbr * P.sb_cols + sbc;
     SbCtx cx;
-    cx.P = Pd; cx.lane = threadIdx.x & 63; cx.sb_x = sbc * 64; cx.sb_y = sbr * 64;
+    // adaptive quantisation: the superblock's steps, reciprocals and matrix slice - its slot's copy of the parameters (slot 0, the
+    // block itself, without; a wave-uniform pointer: the fields stay scalar loads)
+    cx.P = Pd + ((aq_slots >> (4 * si)) & 15u);
+    cx.lane = threadIdx.x & 63; cx.sb_x = sbc * 64; cx.sb_y = sbr * 64;
     cx.tox = (si % TSB) * 64; cx.toy = (si / TSB) * 64;
     SbLds *const sbl = (SPLIT && threadIdx.x >= 64) ? SbSel<2>::get() : SbSel<0>::get();   // each wave of a split walk keeps a map of its own
     // decoded-block map (clear_block_decoded_flags, spec §5.11.3): the row above and the column left of the superblock
@@ -1716,7 +1729,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AV1MI_R
                                                      const PIX *__restrict__ src, PIX *__restrict__ rec, int16_t *__restrict__ levels,
                                                      Av1miBlkInfo *__restrict__ blk, const PIX *__restrict__ ref,
                                                      const unsigned long long *__restrict__ me_best, int cell_log2,
-                                                     const uint32_t *__restrict__ part) {
+                                                     const uint32_t *__restrict__ part, const uint8_t *__restrict__ aq) {
   const Av1miDevParams &P = *Pd;
   const int u = 1 << (cell_log2 - 3);
   for (int uy = blockIdx.y * u; uy < (int)(blockIdx.y + 1) * u; uy++)
@@ -1724,7 +1737,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AV1MI_R
       const int x = ux * 8, y = uy * 8;
       if (x >= P.width || y >= P.height) continue;
       SbCtx cx;
-      cx.P = Pd; cx.lane = threadIdx.x; cx.sb_x = x & ~63; cx.sb_y = y & ~63; cx.tox = 0; cx.toy = 0;
+      cx.lane = threadIdx.x; cx.sb_x = x & ~63; cx.sb_y = y & ~63; cx.tox = 0; cx.toy = 0;
+      cx.P = aq ? Pd + uniform_i(av1mi_aq_slot((int)aq[(cx.sb_y >> 6) * P.sb_cols + (cx.sb_x >> 6)], P.base_q_idx)) : Pd;
       const int bx = x - cx.sb_x, by = y - cx.sb_y;
       const int bsl = leaf_bsl_at(P, part != nullptr, part ? part[(cx.sb_y >> 6) * P.sb_cols + (cx.sb_x >> 6)] : 0u, cx.sb_x, cx.sb_y, bx, by);
       if (bsl == 0) continue;
@@ -1787,7 +1801,8 @@ extern "C" int av1mi_debug_stamps(unsigned long long *out, int reset) {
 
 // ref == nullptr: P->n_frames key frames in one launch.  ref != nullptr: ONE inter frame (P->n_frames must be 1),
 // predicted from `ref` with the motion search results `me_best` of that frame.
-// dP: the same parameters in device memory (what the kernel reads; n_frames and the loop-filter levels are not used by it).
+// dP: the same parameters in device memory (what the kernel reads; n_frames and the loop-filter levels are not used by it), followed
+// with adaptive quantisation (P->aq_map: the quantiser indices of the launch's first frame on) by the quantiser slots' copies.
 #if AV1MI_RECON_BIG && AV1MI_RECON_PIX8
 #define AV1MI_LAUNCH_RECON av1mi_launch_recon64_u8   /* leaf blocks up to 64x64 (P->max_bs_log2 == 6), 8-bit samples */
 #elif AV1MI_RECON_BIG
@@ -1812,9 +1827,9 @@ extern "C" hipError_t AV1MI_LAUNCH_RECON(const Av1miDevParams *P, const Av1miDev
 #define PRE_LAUNCH2(PIXT, SPV)                                                                                                               \
     do {                                                                                                                                     \
       if (P->qm_tab) hipLaunchKernelGGL((recon_inter_pre_kernel<PIXT, true, SPV>), pgrid, dim3(64), 0, stream, dP, (const PIXT *)src, (PIXT *)rec, \
-                                        levels, blk, (const PIXT *)ref, me_best, g, part);                                                   \
+                                        levels, blk, (const PIXT *)ref, me_best, g, part, P->aq_map);                                                   \
       else hipLaunchKernelGGL((recon_inter_pre_kernel<PIXT, false, SPV>), pgrid, dim3(64), 0, stream, dP, (const PIXT *)src, (PIXT *)rec,          \
-                              levels, blk, (const PIXT *)ref, me_best, g, part);                                                             \
+                              levels, blk, (const PIXT *)ref, me_best, g, part, P->aq_map);                                                             \
     } while (0)
 #define PRE_LAUNCH(PIXT) do { if (P->subpel) PRE_LAUNCH2(PIXT, true); else PRE_LAUNCH2(PIXT, false); } while (0)
     PRE_LAUNCH(ReconPix);
@@ -1825,9 +1840,9 @@ extern "C" hipError_t AV1MI_LAUNCH_RECON(const Av1miDevParams *P, const Av1miDev
 #define RECON_LAUNCH2(PIXT, INTERV, TSBV, EXTV)                                                                                             \
   do {                                                                                                                                      \
     if (P->qm_tab) hipLaunchKernelGGL((recon_sb_kernel<PIXT, INTERV, TSBV, true, EXTV>), dim3(grid), dim3(WalkSplit<INTERV>::value ? 128 : 64), 0, stream, dP, (const PIXT *)src,  \
-                                      (PIXT *)rec, levels, blk, (const PIXT *)ref, me_best, part);                                          \
+                                      (PIXT *)rec, levels, blk, (const PIXT *)ref, me_best, part, P->aq_map);                                          \
     else hipLaunchKernelGGL((recon_sb_kernel<PIXT, INTERV, TSBV, false, EXTV>), dim3(grid), dim3(WalkSplit<INTERV>::value ? 128 : 64), 0, stream, dP, (const PIXT *)src,           \
-                            (PIXT *)rec, levels, blk, (const PIXT *)ref, me_best, part);                                                    \
+                            (PIXT *)rec, levels, blk, (const PIXT *)ref, me_best, part, P->aq_map);                                                    \
   } while (0)
   // the optional intra tools (edge filter, chroma from luma) live in instantiations of their own (EXT)
 #define RECON_LAUNCH(PIXT, INTERV, TSBV)                                                                                                    \

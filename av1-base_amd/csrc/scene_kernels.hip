@@ -9,6 +9,7 @@
 // t-1) with 16-byte loads per lane; algorithmic bytes 2*L*b per frame pair (L luma samples).
 #include <hip/hip_runtime.h>
 #include "av1mi_dev.h"
+#include "aq_rule.h"
 
 namespace {
 
@@ -86,6 +87,35 @@ __global__ void __launch_bounds__(256) crop_frames_kernel(const PIX *__restrict_
   }
 }
 
+// sum and sum of squares of the 64 source luma samples of the 8x8 unit at (x0, y0), coordinates beyond the frame repeating the last
+// column / row (what the block's transform will see): the statistics of the partition pass and of the activity pass
+template <typename PIX>
+__device__ __forceinline__ void unit_stats(const Av1miDevParams &P, const PIX *__restrict__ luma, int x0, int y0, uint32_t &S, uint32_t &Q) {
+  S = 0; Q = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    const int yy = y0 + i < P.height ? y0 + i : P.height - 1;
+    const PIX *row = luma + (size_t)yy * P.stride_y;
+    if (x0 + 8 <= P.width) {   // eight samples of the row in one load (the coded width is a multiple of 8)
+      if (sizeof(PIX) == 2) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(row + x0);
+        const uint32_t w[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+        for (int k = 0; k < 4; k++) { const uint32_t a = w[k] & 0xFFFF, b = w[k] >> 16; S += a + b; Q += a * a + b * b; }
+      } else {
+        const uint2 v = *reinterpret_cast<const uint2 *>(row + x0);
+        const uint32_t w[2] = { v.x, v.y };
+#pragma unroll
+        for (int k = 0; k < 2; k++)
+#pragma unroll
+          for (int b8 = 0; b8 < 4; b8++) { const uint32_t a = (w[k] >> (8 * b8)) & 0xFF; S += a; Q += a * a; }
+      }
+    } else {
+      for (int j = 0; j < 8; j++) { const int xx = x0 + j < P.width ? x0 + j : P.width - 1; const uint32_t a = row[xx]; S += a; Q += a * a; }
+    }
+  }
+}
+
 // ---- content-driven partition (av1mi_params.partition_search; SURVEY.md §8a row a10: the block-size decision SVT-AV1
 // spends most of `--preset 3` on, /root/reference/crates/daemon/src/encode/av1an.rs:14).  Open loop, from the SOURCE luma: a node of the
 // partition tree splits when its four quadrants differ in activity - the largest quadrant variance exceeds four times the smallest plus
@@ -102,30 +132,8 @@ __global__ void __launch_bounds__(64) partition_kernel(Av1miDevParams P, const P
   const PIX *luma = frames + (size_t)f * P.frame_samples;
   {
     const int ux = (lane & 1) | ((lane >> 1) & 2) | ((lane >> 2) & 4), uy = ((lane >> 1) & 1) | ((lane >> 2) & 2) | ((lane >> 3) & 4);
-    const int x0 = sb_x + 8 * ux, y0 = sb_y + 8 * uy;
-    uint32_t S = 0, Q = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-      const int yy = y0 + i < P.height ? y0 + i : P.height - 1;
-      const PIX *row = luma + (size_t)yy * P.stride_y;
-      if (x0 + 8 <= P.width) {   // eight samples of the row in one load (the coded width is a multiple of 8)
-        if (sizeof(PIX) == 2) {
-          const uint4 v = *reinterpret_cast<const uint4 *>(row + x0);
-          const uint32_t w[4] = { v.x, v.y, v.z, v.w };
-#pragma unroll
-          for (int k = 0; k < 4; k++) { const uint32_t a = w[k] & 0xFFFF, b = w[k] >> 16; S += a + b; Q += a * a + b * b; }
-        } else {
-          const uint2 v = *reinterpret_cast<const uint2 *>(row + x0);
-          const uint32_t w[2] = { v.x, v.y };
-#pragma unroll
-          for (int k = 0; k < 2; k++)
-#pragma unroll
-            for (int b8 = 0; b8 < 4; b8++) { const uint32_t a = (w[k] >> (8 * b8)) & 0xFF; S += a; Q += a * a; }
-        }
-      } else {
-        for (int j = 0; j < 8; j++) { const int xx = x0 + j < P.width ? x0 + j : P.width - 1; const uint32_t a = row[xx]; S += a; Q += a * a; }
-      }
-    }
+    uint32_t S, Q;
+    unit_stats(P, luma, sb_x + 8 * ux, sb_y + 8 * uy, S, Q);
     uS[lane] = S; uQ[lane] = Q;
   }
   __syncthreads();
@@ -154,6 +162,40 @@ __global__ void __launch_bounds__(64) partition_kernel(Av1miDevParams P, const P
   }
 }
 
+// ---- activity-adaptive quantisation (av1mi_params.cq_level bits 8-10; aq_rule.h is the rule).  Open loop, from
+// the SOURCE luma, for all frames of a chunk before any tile walk.  First launch: one wave per superblock, lane = 8x8 unit (the
+// partition pass's statistics), e per unit, E = the rounded mean over the units inside the coded frame -> act[frame][superblock].
+// Second launch: one workgroup per frame sums E (integers: any order gives the same M) and writes the superblocks' quantiser indices.
+// Algorithmic bytes L b per frame (L luma samples) + 3 per superblock.
+template <typename PIX>
+__global__ void __launch_bounds__(64) aq_activity_kernel(Av1miDevParams P, const PIX *__restrict__ frames, uint16_t *__restrict__ act) {
+  const int f = blockIdx.y, sb = blockIdx.x, lane = threadIdx.x;
+  const int x0 = (sb % P.sb_cols) * 64 + 8 * (lane & 7), y0 = (sb / P.sb_cols) * 64 + 8 * (lane >> 3);
+  const bool inside = x0 < P.width && y0 < P.height;
+  uint32_t e = 0;
+  if (inside) {
+    uint32_t S, Q;
+    unit_stats(P, frames + (size_t)f * P.frame_samples, x0, y0, S, Q);
+    e = (uint32_t)av1mi_aq_unit_energy(S, Q, P.bit_depth);
+  }
+  uint32_t n = inside ? 1u : 0u;
+  for (int o = 32; o > 0; o >>= 1) { e += __shfl_xor(e, o, 64); n += __shfl_xor(n, o, 64); }
+  if (lane == 0) act[(size_t)f * P.sb_rows * P.sb_cols + sb] = (uint16_t)av1mi_aq_mean(e, n);
+}
+
+__global__ void __launch_bounds__(256) aq_map_kernel(Av1miDevParams P, const uint16_t *__restrict__ act, uint8_t *__restrict__ qmap, int strength) {
+  __shared__ uint32_t part[4];
+  const int f = blockIdx.x, t = threadIdx.x, nsb = P.sb_rows * P.sb_cols;
+  const uint16_t *E = act + (size_t)f * nsb;
+  uint32_t sum = 0;
+  for (int i = t; i < nsb; i += 256) sum += E[i];
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  if ((t & 63) == 0) part[t >> 6] = sum;
+  __syncthreads();
+  const int M = av1mi_aq_mean(part[0] + part[1] + part[2] + part[3], (uint32_t)nsb);
+  for (int i = t; i < nsb; i += 256) qmap[(size_t)f * nsb + i] = (uint8_t)av1mi_aq_qindex_of(strength, (int)E[i], M, P.base_q_idx);
+}
+
 }  // namespace
 
 // split masks of every superblock of P->n_frames frames (partition_kernel)
@@ -161,6 +203,15 @@ extern "C" hipError_t av1mi_launch_partition(const Av1miDevParams *P, const void
   dim3 grid(P->sb_rows * P->sb_cols, P->n_frames);
   if (P->bit_depth == 8) hipLaunchKernelGGL(partition_kernel<uint8_t>, grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, part);
   else hipLaunchKernelGGL(partition_kernel<uint16_t>, grid, dim3(64), 0, stream, *P, (const uint16_t *)frames, part);
+  return hipGetLastError();
+}
+
+// quantiser index of every superblock of P->n_frames frames (aq_activity_kernel, aq_map_kernel): act and qmap are [frame][superblock]
+extern "C" hipError_t av1mi_launch_aq(const Av1miDevParams *P, const void *frames, uint16_t *act, uint8_t *qmap, int strength, hipStream_t stream) {
+  dim3 grid(P->sb_rows * P->sb_cols, P->n_frames);
+  if (P->bit_depth == 8) hipLaunchKernelGGL(aq_activity_kernel<uint8_t>, grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, act);
+  else hipLaunchKernelGGL(aq_activity_kernel<uint16_t>, grid, dim3(64), 0, stream, *P, (const uint16_t *)frames, act);
+  hipLaunchKernelGGL(aq_map_kernel, dim3(P->n_frames), dim3(256), 0, stream, *P, (const uint16_t *)act, qmap, strength);
   return hipGetLastError();
 }
 

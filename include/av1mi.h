@@ -36,6 +36,11 @@ enum {
 
 typedef struct av1mi_ctx av1mi_ctx;
 
+/* av1mi_params.cq_level carries two values: the CQ level and the strength of the adaptive quantisation */
+#define AV1MI_CQ_AQ(cq, strength) (((uint32_t)(cq) & 0xFFu) | (((uint32_t)(strength) & 7u) << 8))
+#define AV1MI_CQ_LEVEL(v) ((uint32_t)(v) & 0xFFu)
+#define AV1MI_AQ_STRENGTH(v) (((uint32_t)(v) >> 8) & 7u)
+
 /* Operating point.  Replaces the reference's single constant
  *   SVT_PARAMS = "--crf 8 --preset 3 --film-grain 20 ... --keyint 240 --lookahead 40"
  * (crates/daemon/src/encode/av1an.rs:14) and `--pix-format yuv420p10le` (av1an.rs:90). */
@@ -43,8 +48,15 @@ typedef struct {
   uint32_t width, height;   /* luma size, even, >= 8, yuv 4:2:0.  Sizes that are not multiples of 8 are coded at the next
                                multiple of 8 (source edge-extended on the device) and signalled exactly, as any AV1 encoder does */
   uint32_t bit_depth;       /* 8 or 10 (samples: uint8_t / little-endian uint16_t) */
-  uint32_t cq_level;        /* "--crf N": 1..63, mapped to base_q_idx like aom (30 -> 120).  0 (base_q_idx 0: lossless
-                               coding, which this encoder does not do) is refused with AV1MI_E_INVALID_ARG */
+  uint32_t cq_level;        /* bits 0-7: "--crf N": 1..63, mapped to base_q_idx like aom (30 -> 120).  0 (base_q_idx 0: lossless
+                               coding, which this encoder does not do) is refused with AV1MI_E_INVALID_ARG.
+                               bits 8-10: aq_strength 0..4, activity-adaptive quantisation (AV1MI_CQ_AQ packs the field; DESIGN.md §3
+                               item 1c): 0 (default) = one quantiser index per frame; s = 1..4: every 64x64 superblock gets
+                               base_q_idx + 4 d, d in -6..6 from s times the difference between the log2 variance of its source luma
+                               (mean over its 8x8 units) and the frame's mean, s = 2 being one step per doubling - flat superblocks a
+                               finer quantiser, busy ones a coarser (delta_q_present = 1, delta_q_res = 2; deblocking level, partition
+                               threshold and quantiser-matrix level stay with base_q_idx).  Strengths 5..7 and any higher bit are
+                               refused with AV1MI_E_INVALID_ARG */
   uint32_t keyint;          /* "--keyint": 1 = every frame a key frame; N > 1 = a key frame every N frames of a chunk, the
                                frames between are INTER frames predicted from the previous reconstruction (one
                                reference, integer-pel full search; chunks always start with a key frame) */
@@ -178,6 +190,13 @@ typedef struct {
 int av1mi_scene_cuts(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames,
                      int frames_on_device, const void *prev_frame, av1mi_scene_state *state,
                      uint32_t min_scene_len, uint64_t *sad, uint8_t *is_cut);
+
+/* ---- adaptive quantisation: the decision on its own (what an analysis tool wants) ------------
+ * The quantiser index every 64x64 superblock of every frame is coded with: qindex[(f * sb_rows + r) * sb_cols + c],
+ * sb_cols = (ceil8(width) + 63) / 64, likewise rows; all base_q_idx when the strength is 0.  Same frame arguments as
+ * av1mi_scene_cuts (tight planar frames, host or 16-byte aligned device memory). */
+int av1mi_aq_qindex(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames,
+                    int frames_on_device, uint8_t *qindex);
 
 /* ---- the drop-in for `run_av1an` ---------------------------------------------------------
  * Replaces  pub fn run_av1an(params: &Av1anEncodeParams) -> Result<(), EncodeError>

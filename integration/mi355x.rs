@@ -9,7 +9,9 @@ use std::os::raw::{c_char, c_int, c_void};
 #[derive(Default, Clone, Copy)]
 pub struct Av1miParams {            // include/av1mi.h: av1mi_params
     pub width: u32, pub height: u32, pub bit_depth: u32,
-    pub cq_level: u32, pub keyint: u32, pub block_log2: u32, pub cdf_update: u32, pub enable_cdef: u32,
+    /// Bits 0-7: the CQ level 1..63; bits 8-10: aq_strength 0..4, activity-adaptive quantisation (`cq_aq` packs the field; 0 = off).
+    pub cq_level: u32,
+    pub keyint: u32, pub block_log2: u32, pub cdf_update: u32, pub enable_cdef: u32,
     pub cdef_y_pri: u32, pub cdef_y_sec: u32, pub cdef_uv_pri: u32, pub cdef_uv_sec: u32, pub cdef_damping: u32,
     pub intra_mode_mask: u32, pub film_grain: u32, pub first_frame: u32, pub me_range: u32,
     /// Loop restoration: 0 = off, 1 = Wiener on luma, 2 = off / Wiener / self-guided per luma unit; 3 / 4 = 1 / 2 on all three
@@ -46,6 +48,11 @@ pub struct Av1miReport {            // fills JobMetrics.{fps, frames_encoded, ps
     pub ms_d2h: f32, pub ms_total: f32, pub ms_symbolize: f32, pub n_symbols: u64,
     pub max_tile_symbols: u32, pub cap_scale: u32, pub chunks: u32, pub gpus_used: u32,
 }
+// include/av1mi.h: AV1MI_CQ_AQ / AV1MI_CQ_LEVEL / AV1MI_AQ_STRENGTH - cq_level carries the CQ level and the adaptive quantisation's strength
+pub const AV1MI_AQ_MAX_STRENGTH: u32 = 4;
+pub const fn cq_aq(cq: u32, strength: u32) -> u32 { (cq & 0xFF) | ((strength & 7) << 8) }
+pub const fn cq_level_of(v: u32) -> u32 { v & 0xFF }
+pub const fn aq_strength_of(v: u32) -> u32 { (v >> 8) & 7 }
 type ProgressCb = Option<extern "C" fn(user: *mut c_void, done: u32, total: u32, fps: f64, bytes: u64)>;
 
 #[link(name = "av1mi")]

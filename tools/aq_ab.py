@@ -1,0 +1,72 @@
+#!/usr/bin/env python3
+"""Adaptive quantisation A/B: bench.py's synthclip encoded with aq_strength 0, 1, 2 and 4 at the headline workload (1080p x 60, 10-bit,
+all 13 intra candidates, CQ 30), cfg3_1080p_ippp and the production point.  One JSON line per point and strength: frames/s (best of
+--steps after --warmup, the clip in HBM), bytes per frame, PSNR Y / U / V of the reconstruction, the report's stage times (the activity
+pass runs between the chunk's start and "source ready": ms_h2d), the time of the decision alone (av1mi_aq_qindex, with its
+allocations) and the histogram of the superblocks' quantiser indices.  The rule trades PSNR for flat-area quality: at equal bytes PSNR
+is expected to fall, and this tool reports what it measures, nothing more."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "av1-base_amd"))
+import bench  # noqa: E402
+
+
+POINTS = [
+    ("headline_cq30", dict(keyint=1, cq_level=30, intra_mode_mask=0x1FFF)),
+    ("cfg3_1080p_ippp", dict(keyint=240, cq_level=30, intra_mode_mask=0x7)),
+    ("production_1080p", dict(keyint=240, cq_level=8, intra_mode_mask=0x7, film_grain=20, subpel=1, deblock=1, enable_lr=2,
+                              enable_qm=1, qm_min=1, qm_max=15)),
+]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--frames", type=int, default=60)
+    ap.add_argument("--points", default="", help="comma-separated subset of the point names")
+    ap.add_argument("--strengths", default="0,1,2,4")
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    import av1mi
+    w, h, bd, n = 1920, 1080, 10, args.frames
+    dev = torch.device("cuda:0")
+    clip = bench.make_clip_torch(w, h, bd, n, 1080, dev)
+    torch.cuda.synchronize(dev)
+    want = set(args.points.split(",")) if args.points else None
+    with av1mi.Context(0) as ctx:
+        for name, kw in POINTS:
+            if want and name not in want:
+                continue
+            for s in [int(x) for x in args.strengths.split(",")]:
+                p = av1mi.default_params(w, h, bd, aq_strength=s, **kw)
+                for _ in range(args.warmup):
+                    ctx.encode_chunk(p, clip.data_ptr(), n, on_device=True, copy_out=False)
+                best, rep = None, None
+                for _ in range(args.steps):
+                    t0 = time.perf_counter()
+                    _, _, r, _ = ctx.encode_chunk(p, clip.data_ptr(), n, on_device=True, copy_out=False)
+                    dt = time.perf_counter() - t0
+                    if best is None or dt < best:
+                        best, rep = dt, r
+                ctx.aq_qindex(p, clip.data_ptr(), n, on_device=True)
+                t0 = time.perf_counter()
+                qmap = ctx.aq_qindex(p, clip.data_ptr(), n, on_device=True)
+                ms_map = (time.perf_counter() - t0) * 1e3
+                q, cnt = np.unique(qmap, return_counts=True)
+                print(json.dumps({"point": name, "aq_strength": s, "fps": round(n / best, 1), "ms": round(best * 1e3, 2),
+                                  "bytes_per_frame": round(rep.bytes / n, 1), "psnr": [round(x, 3) for x in rep.psnr],
+                                  "ms_h2d": round(rep.ms_h2d, 3), "ms_recon": round(rep.ms_recon, 3), "ms_entropy": round(rep.ms_entropy, 3),
+                                  "ms_symbolize": round(rep.ms_symbolize, 3), "ms_aq_qindex_call": round(ms_map, 3),
+                                  "qindex_hist": {int(a): int(b) for a, b in zip(q, cnt)}}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -202,6 +202,8 @@ def main():
     T["use_wiener"] = ([[int(32768 - raw[4])]], (1,), 2)
     T["use_sgrproj"] = ([[int(32768 - raw[6])]], (1,), 2)
     assert T["use_wiener"][0] == [[11570]] and T["use_sgrproj"][0] == [[16855]]
+    o = dav([28160, 32120, 32677], "delta_q")   # delta_q_abs (adaptive quantisation): libaom's AOM_CDF4(28160, 32120, 32677)
+    T["delta_q"] = ([[int(32768 - x) for x in blob.u16(o, 3)]], (1,), 4)
     o = dav([1418, 2123, 13340, 18405, 26972, 28343, 32294], "cfl_sign")
     T["cfl_sign"] = ([[int(32768 - x) for x in blob.u16(o, 7)]], (1,), 8)
 
