@@ -166,6 +166,12 @@ AV1MI_HD inline void av1mi_me_key_decode(unsigned long long key, int R, int *dy,
 // frame f of a chunk is a key frame iff f % keyint == 0
 AV1MI_HD inline int av1mi_frame_is_inter(const Av1miDevParams &P, int f) { return P.keyint > 1 && (f % P.keyint) != 0; }
 
+// ---- loop restoration: a plane's grid of units, from the signalled size (64x64 luma samples each; the last row / column takes a remainder of
+// less than half a unit), and the units of one frame over its restored planes - the frame stride of the [frame][plane][unit] choices and sums
+AV1MI_HD inline int av1mi_lr_unit_rows(const Av1miDevParams &P) { return (P.true_h + 32) / 64 > 0 ? (P.true_h + 32) / 64 : 1; }
+AV1MI_HD inline int av1mi_lr_unit_cols(const Av1miDevParams &P) { return (P.true_w + 32) / 64 > 0 ? (P.true_w + 32) / 64 : 1; }
+AV1MI_HD inline int av1mi_lr_frame_units(const Av1miDevParams &P) { return (P.lr_chroma ? 3 : 1) * av1mi_lr_unit_rows(P) * av1mi_lr_unit_cols(P); }
+
 // ---- which symbolize variant owns a tile (entropy_kernel.hip: the kernels decide per tile, the launcher sizes its grids by it)
 // Under a content-driven partition (P.part_map, device memory: device code only): does the superblock keep one block size throughout -
 // no node between min_bs_log2 and max_bs_log2 splits by its mask?  (Only then does a tile hold exactly two (transform size, plane type)

@@ -25,42 +25,8 @@
 #include "../../include/av1mi.h"
 #include "av1_tables.h"
 #include "av1mi_dev.h"
+#include "av1mi_launch.h"
 #include "aq_rule.h"
-
-extern "C" {
-hipError_t av1mi_launch_partition(const Av1miDevParams *P, const void *frames, uint32_t *part, hipStream_t stream);
-hipError_t av1mi_launch_aq(const Av1miDevParams *P, const void *frames, uint16_t *act, uint8_t *qmap, int strength, hipStream_t stream);
-// one translation unit per (largest leaf, sample type): recon_kernel.hip, recon8_kernel.hip, recon64_kernel.hip, recon64_8_kernel.hip
-#define AV1MI_RECON_PROTO(name) hipError_t name(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels, \
-                                               Av1miBlkInfo *blk, const void *ref, const unsigned long long *me_best, const uint32_t *part, hipStream_t s)
-AV1MI_RECON_PROTO(av1mi_launch_recon_u16);
-AV1MI_RECON_PROTO(av1mi_launch_recon_u8);
-AV1MI_RECON_PROTO(av1mi_launch_recon64_u16);
-AV1MI_RECON_PROTO(av1mi_launch_recon64_u8);
-hipError_t av1mi_launch_subpel_refine(const Av1miDevParams *P, const void *frames, const unsigned long long *best, unsigned long long *refined,
-                                      int me_range, int frame0, int count, hipStream_t stream);
-hipError_t av1mi_launch_motion_search(const Av1miDevParams *P, const void *frames, unsigned long long *best, int me_range, int frame0,
-                                      int count, uint32_t *acc64, const uint32_t *centre, hipStream_t stream);
-hipError_t av1mi_launch_quarter_luma(const Av1miDevParams *P, const void *frames, uint16_t *quarter, hipStream_t stream);
-hipError_t av1mi_launch_presearch(const Av1miDevParams *P, const uint16_t *quarter, uint32_t *centre, int frame0, int count, hipStream_t stream);
-hipError_t av1mi_launch_luma_sad(const Av1miDevParams *P, const void *frames, const void *prev0, unsigned long long *sad, hipStream_t s);
-hipError_t av1mi_launch_pad(const void *in, void *out, int w, int h, int cw, int ch, int bit_depth, int n_frames, int crop, hipStream_t s);
-hipError_t av1mi_launch_deblock(const Av1miDevParams *P, void *rec, const Av1miBlkInfo *blk, hipStream_t s);
-hipError_t av1mi_launch_lr(const Av1miDevParams *P, const void *pre, const void *cdef, const void *src, void *out, uint8_t *choice,
-                           unsigned long long *unit_sse, int clear, hipStream_t s);
-hipError_t av1mi_launch_entropy(const Av1miDevParams *P, const uint16_t *cdf_init, const int16_t *levels, const Av1miBlkInfo *blk,
-                                uint32_t *streams, uint32_t *stream_len, uint32_t *tile_combos, uint8_t *slots, uint32_t *tile_bytes,
-                                const uint8_t *lr_choice, uint32_t *tile_order, int frame0, int count,
-                                hipStream_t s, hipEvent_t mid, hipStream_t aux, hipEvent_t fork, hipEvent_t join);
-hipError_t av1mi_launch_cdef(const Av1miDevParams *P, const void *rec, void *fin, const Av1miBlkInfo *blk, const void *src,
-                             unsigned long long *sse, hipStream_t s);
-hipError_t av1mi_launch_sse(const Av1miDevParams *P, const void *a, const void *b, unsigned long long *sse, hipStream_t s);
-hipError_t av1mi_launch_cdef_search(const Av1miDevParams *P, const void *rec, const void *src, const Av1miBlkInfo *blk, uint8_t *hdr_blob,
-                                    int frame0, int count, hipStream_t s);
-hipError_t av1mi_launch_pack(const Av1miDevParams *P, const uint8_t *slots, const uint32_t *tile_bytes, uint32_t *tile_off,
-                             uint32_t *frame_size, uint32_t *payload_size, unsigned long long *frame_off, const uint8_t *hdr_blob,
-                             uint8_t *out, int *overflow, int stage, hipStream_t s);
-}
 
 namespace {
 
@@ -90,10 +56,21 @@ struct BitWriter {
 int tile_log2(int blk, int target) { int k = 0; while ((blk << k) < target) k++; return k; }
 int bits_for(unsigned v) { int n = 0; while (v) { n++; v >>= 1; } return n ? n : 1; }
 
+// quantiser steps of a quantiser index, and their reciprocals ceil(2^32 / q)
+struct QuantSteps { int dc_q, ac_q; uint32_t dc_recip, ac_recip; };
+uint32_t recip32(uint32_t q) { return (uint32_t)((((uint64_t)1 << 32) + q - 1) / q); }
+QuantSteps quant_steps(int qindex, int bit_depth) {
+  const int dc = bit_depth == 8 ? av1_dc_q8[qindex] : av1_dc_q10[qindex], ac = bit_depth == 8 ? av1_ac_q8[qindex] : av1_ac_q10[qindex];
+  return { dc, ac, recip32((uint32_t)dc), recip32((uint32_t)ac) };
+}
+void set_quant_steps(Av1miDevParams &P, const QuantSteps &q) { P.dc_q = q.dc_q; P.ac_q = q.ac_q; P.dc_recip = q.dc_recip; P.ac_recip = q.ac_recip; }
+// coefficient q context: which of the four sets of default coefficient CDFs the frames start from
+int q_context(int qidx) { return qidx <= 20 ? 0 : (qidx <= 60 ? 1 : (qidx <= 120 ? 2 : 3)); }
+
 struct Resolved {
   av1mi_params p;
   int qidx;
-  int dc_q, ac_q;                     // quantiser steps of qidx at p.bit_depth
+  QuantSteps q;                       // quantiser steps of qidx at p.bit_depth
   int cw, ch;                         // coded size: p.width / p.height rounded up to multiples of 8
   bool padded;                        // the coded size is not the signalled one: frames are edge-extended in and cropped out
   int sb_cols, sb_rows;
@@ -131,8 +108,7 @@ int resolve(const av1mi_params *in, Resolved *r) {
   if (p.cdef_damping < 3 || p.cdef_damping > 6 || p.cdef_y_pri > 15 || p.cdef_uv_pri > 15 || p.cdef_y_sec > 3 || p.cdef_uv_sec > 3) return AV1MI_E_INVALID_ARG;
   if (p.cdef_search > 4 || (p.cdef_search && !p.enable_cdef)) return AV1MI_E_INVALID_ARG;
   r->qidx = kQuantizerToQindex[p.cq_level];
-  r->dc_q = p.bit_depth == 8 ? av1_dc_q8[r->qidx] : av1_dc_q10[r->qidx];
-  r->ac_q = p.bit_depth == 8 ? av1_ac_q8[r->qidx] : av1_ac_q10[r->qidx];
+  r->q = quant_steps(r->qidx, (int)p.bit_depth);
   if (p.subpel > 1 || p.enable_lr > 4 || p.color_range > 1 || p.intra_angle_delta > 1 || p.intra_edge_filter > 1 || p.cfl > 1 || p.tx_search > 1) return AV1MI_E_INVALID_ARG;
   if (p.partition_search > 1 || p.me_presearch > 1) return AV1MI_E_INVALID_ARG;
   // enable_lr 3 / 4 = 1 / 2 on all three planes: the frames' restoration type plus the chroma flag
@@ -160,10 +136,14 @@ int resolve(const av1mi_params *in, Resolved *r) {
 // deblocking level of a frame (the same for all four filters): libaom's "pick from q" rule; 0 = filter off
 int deblock_level(const Resolved &r, bool key) {
   if (!r.p.deblock) return 0;
-  int g = r.p.bit_depth == 8 ? (r.ac_q * 20723 + 1015158) >> 18 : (r.ac_q * 20723 + 4060632) >> 20;
+  int g = r.p.bit_depth == 8 ? (r.q.ac_q * 20723 + 1015158) >> 18 : (r.q.ac_q * 20723 + 4060632) >> 20;
   if (key) g -= 4;
   return g < 0 ? 0 : (g > 63 ? 63 : g);
 }
+
+// bytes of n frames in the caller's layout: tight at the signalled size (the coded size, where that is a multiple of 8 both ways).
+// Width and height are even (resolve), so a frame's 3 / 2 is exact and multiplying by n first changes nothing.
+size_t caller_bytes(const Resolved &r, size_t n) { return n * r.p.width * r.p.height * 3 / 2 * (r.p.bit_depth > 8 ? 2 : 1); }
 
 // sequence_header_obu (AV1 spec §5.5), complete OBU incl. header and size
 std::vector<uint8_t> make_sequence_header(const Resolved &r) {
@@ -405,7 +385,7 @@ void emit_rows(std::vector<uint16_t> &v, size_t off, const uint16_t (*rows)[W], 
 }
 std::vector<uint16_t> make_cdf_blob(int qidx) {
   typedef Av1miCdfLayout CL;
-  const int q = qidx <= 20 ? 0 : (qidx <= 60 ? 1 : (qidx <= 120 ? 2 : 3));
+  const int q = q_context(qidx);
   std::vector<uint16_t> v(CL::TOTAL, 0);
   int pn[20];
   for (int i = 0; i < 20; i++) pn[i] = i < 4 ? 4 : (i < 16 ? 10 : 8);
@@ -621,7 +601,7 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     w.cap_frames = n_frames; w.scale = c->cap_scale;
   }
   const size_t nf = w.cap_frames;
-  if (r.padded && !w.d_stage) HIPCHK(c, ws_alloc(w, w.d_stage, nf * (size_t)p.width * p.height * 3 / 2 * bps));
+  if (r.padded && !w.d_stage) HIPCHK(c, ws_alloc(w, w.d_stage, caller_bytes(r, nf)));
   if (p.partition_search && !w.d_part) HIPCHK(c, ws_alloc(w, w.d_part, nf * nsb * sizeof(uint32_t)));
   if (p.me_presearch && !w.d_quarter) {
     HIPCHK(c, ws_alloc(w, w.d_quarter, nf * (size_t)(r.cw / 4) * (r.ch / 4) * sizeof(uint16_t)));
@@ -658,14 +638,13 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
       static const int off[4] = { AV1MI_QM_4X4, AV1MI_QM_8X8, AV1MI_QM_16X16, AV1MI_QM_32X32 };
       w.h_qm.resize((size_t)slices * 2 * AV1MI_QM_PLANE);
       for (int sl = 0; sl < slices; sl++) {
-        const int qi = av1mi_aq_slot_qindex(sl, r.qidx);
-        const int dcq = p.bit_depth == 8 ? av1_dc_q8[qi] : av1_dc_q10[qi], acq = p.bit_depth == 8 ? av1_ac_q8[qi] : av1_ac_q10[qi];
+        const QuantSteps qs = quant_steps(av1mi_aq_slot_qindex(sl, r.qidx), (int)p.bit_depth);
         for (int pt = 0; pt < 2; pt++)
           for (int l2 = 2; l2 <= 5; l2++)
             for (int i = 0; i < (1 << (2 * l2)); i++) {
-              const uint32_t q = (uint32_t)(i ? acq : dcq);
+              const uint32_t q = (uint32_t)(i ? qs.ac_q : qs.dc_q);
               const uint32_t q2 = (q * av1_qm_iwt[r.qm_level][pt][off[l2 - 2] + i] + 16) >> 5;
-              w.h_qm[(size_t)(sl * 2 + pt) * AV1MI_QM_PLANE + off[l2 - 2] + i] = { q2, (uint32_t)((((uint64_t)1 << 32) + q2 - 1) / q2) };
+              w.h_qm[(size_t)(sl * 2 + pt) * AV1MI_QM_PLANE + off[l2 - 2] + i] = { q2, recip32(q2) };
             }
       }
       HIPCHK(c, hipMemcpyAsync(w.d_qm, w.h_qm.data(), w.h_qm.size() * sizeof(Av1miQmEntry), hipMemcpyHostToDevice, c->stream));
@@ -687,10 +666,8 @@ Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const
   P.tile_sb = r.tile_sb; P.tile_rows = r.tile_rows; P.tile_cols = r.tile_cols;
   P.n_frames = (int)n_frames;
   P.base_q_idx = r.qidx;
-  P.qctx = r.qidx <= 20 ? 0 : (r.qidx <= 60 ? 1 : (r.qidx <= 120 ? 2 : 3));
-  P.dc_q = r.dc_q; P.ac_q = r.ac_q;
-  P.dc_recip = (uint32_t)((((uint64_t)1 << 32) + P.dc_q - 1) / P.dc_q);
-  P.ac_recip = (uint32_t)((((uint64_t)1 << 32) + P.ac_q - 1) / P.ac_q);
+  P.qctx = q_context(r.qidx);
+  set_quant_steps(P, r.q);
   P.using_qm = p.enable_qm ? 1 : 0; P.qm_y = P.qm_uv = r.qm_level;
   P.qm_tab = p.enable_qm && r.qm_level < 15 ? qm : nullptr;
   P.max_bs_log2 = (int)p.block_log2;
@@ -939,7 +916,7 @@ int av1mi_scene_cuts(av1mi_ctx *c, const av1mi_params *params, const void *frame
   if (rc) { set_err(c, "invalid parameters"); return rc; }
   HIPCHK(c, hipSetDevice(c->device));
   const int bps = r.p.bit_depth > 8 ? 2 : 1;
-  const size_t frame_bytes = (size_t)r.p.width * r.p.height * 3 / 2 * bps;
+  const size_t frame_bytes = caller_bytes(r, 1);
   Av1miDevParams P;
   memset(&P, 0, sizeof(P));
   P.width = r.p.width; P.height = r.p.height; P.bit_depth = r.p.bit_depth; P.n_frames = (int)n_frames;  // tight input layout
@@ -992,7 +969,7 @@ int av1mi_aq_qindex(av1mi_ctx *c, const av1mi_params *params, const void *frames
   if (frames_on_device && ((uintptr_t)frames & 15)) { set_err(c, "device frames must be 16-byte aligned"); return AV1MI_E_INVALID_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   const int bps = r.p.bit_depth > 8 ? 2 : 1;
-  const size_t in_bytes = (size_t)n_frames * r.p.width * r.p.height * 3 / 2 * bps, coded_bytes = (size_t)n_frames * r.cw * r.ch * 3 / 2 * bps;
+  const size_t in_bytes = caller_bytes(r, n_frames), coded_bytes = (size_t)n_frames * r.cw * r.ch * 3 / 2 * bps;
   const Av1miDevParams P = dev_params(r, n_frames, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   hipStream_t s = c->stream;
   void *d_in = nullptr, *d_coded = nullptr;
@@ -1077,12 +1054,8 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
     const int n_par = P.aq_map ? AV1MI_AQ_SLOTS : 1;
     std::vector<Av1miDevParams> par((size_t)n_par, P);
     for (int sl = 1; sl < n_par; sl++) {
-      const int qi = av1mi_aq_slot_qindex(sl, r.qidx);
       Av1miDevParams &Q = par[(size_t)sl];
-      Q.dc_q = P.bit_depth == 8 ? av1_dc_q8[qi] : av1_dc_q10[qi];
-      Q.ac_q = P.bit_depth == 8 ? av1_ac_q8[qi] : av1_ac_q10[qi];
-      Q.dc_recip = (uint32_t)((((uint64_t)1 << 32) + Q.dc_q - 1) / Q.dc_q);
-      Q.ac_recip = (uint32_t)((((uint64_t)1 << 32) + Q.ac_q - 1) / Q.ac_q);
+      set_quant_steps(Q, quant_steps(av1mi_aq_slot_qindex(sl, r.qidx), P.bit_depth));
       if (P.qm_tab) Q.qm_tab = P.qm_tab + (size_t)sl * 2 * AV1MI_QM_PLANE;
     }
     const size_t bytes = (size_t)n_par * sizeof(P);
@@ -1098,8 +1071,7 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   if (P.cdef_search) HIPCHK(c, hipMemsetAsync(w.d_cdef_err, 0, (size_t)n_frames * P.sb_rows * P.sb_cols * 24 * sizeof(unsigned long long), s));
   HIPCHK(c, hipEventRecord(c->ev[EV_START], s));
   // the caller's frames are used in place if they are on the device at the coded size; a padded chunk arrives in the stage
-  const size_t bytes = (size_t)n_frames * (r.padded ? (size_t)r.p.width * r.p.height * 3 / 2 : (size_t)P.frame_samples) * (P.bit_depth > 8 ? 2 : 1);
-  if (!frames_on_device) HIPCHK(c, hipMemcpyAsync(r.padded ? w.d_stage : w.d_src, frames, bytes, hipMemcpyHostToDevice, s));
+  if (!frames_on_device) HIPCHK(c, hipMemcpyAsync(r.padded ? w.d_stage : w.d_src, frames, caller_bytes(r, n_frames), hipMemcpyHostToDevice, s));
   // not a multiple of 8: edge-extend every frame to the coded size (the signalled size stays exact)
   if (r.padded) HIPCHK(c, av1mi_launch_pad(frames_on_device ? frames : w.d_stage, w.d_src, (int)r.p.width, (int)r.p.height, r.cw, r.ch, P.bit_depth, (int)n_frames, 0, s));
   *d_src = frames_on_device && !r.padded ? frames : w.d_src;
@@ -1110,12 +1082,6 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   if (P.aq_map) HIPCHK(c, av1mi_launch_aq(&P, *d_src, w.d_aq_act, w.d_aq_map, r.aq, s));
   HIPCHK(c, hipEventRecord(c->ev[EV_SRC_READY], s));
   return AV1MI_OK;
-}
-
-// 64x64 leaf blocks run the kernels of recon64_kernel.hip (64-point transforms, larger LDS tiles)
-static decltype(&av1mi_launch_recon_u8) recon_launcher(const Av1miDevParams &P) {
-  return P.max_bs_log2 >= 6 ? (P.bit_depth == 8 ? av1mi_launch_recon64_u8 : av1mi_launch_recon64_u16)
-                            : (P.bit_depth == 8 ? av1mi_launch_recon_u8 : av1mi_launch_recon_u16);
 }
 
 // Entropy coding of frames [from, n_frames) on the main stream (the frame-edge tiles' symbolize variant on the fourth), then the join
@@ -1155,16 +1121,18 @@ static int schedule_all_key(av1mi_ctx *c, const void *src, uint32_t n_frames) {
   // CDEF's one launch over the chunk sums the squared error itself - a second pass over the frames, 0.19 ms at 1080p x 60, would end
   // after the range coder CDEF runs beside; a one-frame chunk's CDEF runs in strips without the sum
   const bool sse_in_cdef = n_frames > 1;
-  HIPCHK(c, recon_launcher(P)(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, nullptr, nullptr, P.part_map, s));
-  if (P.lf_level[0] && deblock_s == s) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, s));
-  if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, (int)n_frames, s));
+  const bool deblock = av1mi_frame_lf_levels(P, 0)[0] != 0;
+  const int n = (int)n_frames;
+  HIPCHK(c, av1mi_launch_recon(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, nullptr, nullptr, 0, n, s));
+  if (deblock && deblock_s == s) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, 0, n, s));
+  if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, n, s));
   if (const int rc = entropy_code(c, 0, n_frames)) return rc;
   HIPCHK(c, hipStreamWaitEvent(s2, c->ev[EV_RECON_DONE], 0));
-  if (P.lf_level[0] && deblock_s == s2) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, s2));
+  if (deblock && deblock_s == s2) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, 0, n, s2));
   // measured: starting CDEF right after the reconstruction, beside symbolize, costs 8 % overall
   HIPCHK(c, hipStreamWaitEvent(s2, c->ev[EV_SYM_DONE], 0));
   HIPCHK(c, hipEventRecord(c->ev[EV_CDEF_START], s2));
-  HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, w.d_fin, w.d_blk, sse_in_cdef ? src : nullptr, sse_in_cdef ? w.d_sse : nullptr, s2));
+  HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, w.d_fin, w.d_blk, sse_in_cdef ? src : nullptr, sse_in_cdef ? w.d_sse : nullptr, 0, n, s2));
   if (!sse_in_cdef) HIPCHK(c, av1mi_launch_sse(&P, src, w.d_fin, w.d_sse, s2));
   HIPCHK(c, hipEventRecord(c->ev[EV_CDEF_DONE], s2));
   return AV1MI_OK;
@@ -1174,11 +1142,12 @@ static int schedule_all_key(av1mi_ctx *c, const void *src, uint32_t n_frames) {
 // restoration (into d_fin) precede entropy coding on the main stream.
 static int schedule_all_key_lr(av1mi_ctx *c, const void *src, uint32_t n_frames) {
   const Av1miDevParams &P = c->P; Workspace &w = c->ws; hipStream_t s = c->stream;
-  HIPCHK(c, recon_launcher(P)(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, nullptr, nullptr, P.part_map, s));
-  if (P.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, s));
-  if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, (int)n_frames, s));
-  HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, w.d_cd, w.d_blk, nullptr, nullptr, s));
-  HIPCHK(c, av1mi_launch_lr(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, 1, s));
+  const int n = (int)n_frames;
+  HIPCHK(c, av1mi_launch_recon(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, nullptr, nullptr, 0, n, s));
+  if (av1mi_frame_lf_levels(P, 0)[0]) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, 0, n, s));
+  if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, n, s));
+  HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, w.d_cd, w.d_blk, nullptr, nullptr, 0, n, s));
+  HIPCHK(c, av1mi_launch_lr(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, 1, 0, n, s));
   const int rc = entropy_code(c, 0, n_frames);
   return rc ? rc : sse_beside_range_coder(c, src);
 }
@@ -1188,12 +1157,10 @@ static int schedule_all_key_lr(av1mi_ctx *c, const void *src, uint32_t n_frames)
 // finished groups of frames on the third (every frame starts from the default CDFs, so tiles of different frames stay independent).
 static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
   const Av1miDevParams &P = c->P; Workspace &w = c->ws; hipStream_t s = c->stream, s2 = c->stream2;
-  Av1miDevParams P1 = P; P1.n_frames = 1;
-  const size_t fbytes = (size_t)P.frame_samples * (P.bit_depth > 8 ? 2 : 1), nb8 = (size_t)P.b8_rows * P.b8_cols, nsb = (size_t)P.sb_rows * P.sb_cols;
+  const size_t nb8 = (size_t)P.b8_rows * P.b8_cols, nsb = (size_t)P.sb_rows * P.sb_cols;
   const bool lr = P.enable_lr != 0;
-  uint8_t *cdef_out = (uint8_t *)(lr ? w.d_cd : w.d_fin);   // with loop restoration CDEF writes d_cd and the restored frame goes to d_fin
-  // restoration units per frame, of all restored planes (choices and sums are [frame][plane][unit])
-  const size_t upf = (size_t)(P.lr_chroma ? 3 : 1) * std::max(1, (P.true_h + 32) / 64) * std::max(1, (P.true_w + 32) / 64);
+  void *cdef_out = lr ? w.d_cd : w.d_fin;   // with loop restoration CDEF writes d_cd and the restored frame goes to d_fin
+  const unsigned long long *me_best = P.subpel ? w.d_me_sub : w.d_me;   // the keys the reconstruction reads
   // Motion search is open loop (source against previous source): all inter frames at once, on the second stream,
   // beside the chain below; the first inter frame's reconstruction waits for it.
   HIPCHK(c, hipStreamWaitEvent(s2, c->ev[EV_SRC_READY], 0));  // the source frames are in HBM
@@ -1222,26 +1189,16 @@ static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
   if (const char *eg = getenv("AV1MI_ENTROPY_GROUP")) { const int k = atoi(eg); grp = k > 0 ? (uint32_t)k : n_frames; }
   uint32_t n_grp = 0;
   // the restoration units' candidate sums of the whole chunk, cleared once (not a fill per frame on the chain)
-  if (lr) HIPCHK(c, hipMemsetAsync(w.d_lrsse, 0, (size_t)n_frames * upf * 8 * sizeof(unsigned long long), s));
+  if (lr) HIPCHK(c, hipMemsetAsync(w.d_lrsse, 0, (size_t)n_frames * av1mi_lr_frame_units(P) * 8 * sizeof(unsigned long long), s));
   for (uint32_t f = 0; f < n_frames; f++) {
-    const bool inter = av1mi_frame_is_inter(P, (int)f);
-    const uint8_t *srcf = (const uint8_t *)src + f * fbytes;
-    uint8_t *recf = (uint8_t *)w.d_rec + f * fbytes, *finf = (uint8_t *)w.d_fin + f * fbytes, *cdf_ = cdef_out + f * fbytes;
-    Av1miBlkInfo *blkf = w.d_blk + f * nb8;
-    int16_t *lvf = w.d_levels + f * nsb * AV1MI_SB_LEVELS;
-    const uint8_t *reff = inter ? (const uint8_t *)w.d_fin + (f - 1) * fbytes : nullptr;
-    const unsigned long long *mef = inter ? (P.subpel ? w.d_me_sub : w.d_me) + f * nb8 : nullptr;
-    if (inter) HIPCHK(c, hipStreamWaitEvent(s, c->me_ev[f], 0));
-    if (P.aq_map) P1.aq_map = P.aq_map + f * nsb;   // (the launch's first frame on, like the split masks)
-    HIPCHK(c, recon_launcher(P)(&P1, w.d_params, srcf, recf, lvf, blkf, reff, mef, P.part_map ? P.part_map + f * nsb : nullptr, s));
-    for (int i = 0; i < 4; i++) P1.lf_level[i] = inter ? P.lf_level_inter[i] : P.lf_level[i];
-    if (P1.lf_level[0]) HIPCHK(c, av1mi_launch_deblock(&P1, recf, blkf, s));
-    if (P.cdef_search) {   // the frame's strength set before its CDEF (the next frame's reference is the output of the chosen strengths)
-      HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, (int)f, 1, s));
-      P1.cdef_idx = P.cdef_idx + f * nsb; P1.cdef_sel = P.cdef_sel + f * 8;
-    }
-    HIPCHK(c, av1mi_launch_cdef(&P1, recf, cdf_, blkf, nullptr, nullptr, s));
-    if (lr) HIPCHK(c, av1mi_launch_lr(&P1, recf, cdf_, srcf, finf, w.d_lrc + f * upf, w.d_lrsse + f * upf * 8, 0, s));
+    const int fi = (int)f;
+    if (av1mi_frame_is_inter(P, fi)) HIPCHK(c, hipStreamWaitEvent(s, c->me_ev[f], 0));
+    HIPCHK(c, av1mi_launch_recon(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, w.d_fin, me_best, fi, 1, s));
+    if (av1mi_frame_lf_levels(P, fi)[0]) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, fi, 1, s));
+    // the frame's strength set before its CDEF (the next frame's reference is the output of the chosen strengths)
+    if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, fi, 1, s));
+    HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, cdef_out, w.d_blk, nullptr, nullptr, fi, 1, s));
+    if (lr) HIPCHK(c, av1mi_launch_lr(&P, w.d_rec, cdef_out, src, w.d_fin, w.d_lrc, w.d_lrsse, 0, fi, 1, s));
     if (f == 0)   // (frame 0 of a chunk is a key frame: its chain kernels are in the queue)
       for (uint32_t g = 1; g < n_frames; g++) {
         if (!av1mi_frame_is_inter(P, (int)g)) continue;
@@ -1310,8 +1267,7 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
       e1 = av1mi_launch_pad(w.d_fin, w.d_stage, (int)r.p.width, (int)r.p.height, r.cw, r.ch, P.bit_depth, (int)n_frames, 1, s);
       fin = w.d_stage;
     }
-    const size_t bytes = (size_t)n_frames * (r.padded ? (size_t)r.p.width * r.p.height * 3 / 2 : (size_t)P.frame_samples) * (P.bit_depth > 8 ? 2 : 1);
-    if (e1 == hipSuccess) e1 = hipMemcpyAsync(recon, fin, bytes, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s);
+    if (e1 == hipSuccess) e1 = hipMemcpyAsync(recon, fin, caller_bytes(r, n_frames), frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s);
   }
   const unsigned long long *sse = w.h_sse;
   if (e1 == hipSuccess) e1 = hipMemcpyAsync(w.h_sse, w.d_sse, (size_t)n_frames * 24, hipMemcpyDeviceToHost, s);

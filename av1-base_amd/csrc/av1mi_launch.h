@@ -1,0 +1,112 @@
+// av1mi_launch.h - the kernel launchers: the one declaration of every `av1mi_launch_*`.
+// av1mi_host.cpp calls them through this header, and every file that defines one includes it (the four reconstruction translation units
+// through recon_kernel.hip): the launchers have C linkage, which carries no types, so only the compiler seeing declaration and
+// definition together ("conflicting types") keeps a caller and a definition from drifting apart.
+//
+// Frames of a chunk.  A launcher that can run on part of a chunk takes the chunk-wide arrays and `(frame0, count)` - frames
+// [frame0, frame0 + count) of the chunk P describes.  The search kernels and the entropy coder index the chunk themselves; reconstruction,
+// deblocking, CDEF and restoration kernels see a launch's frames only: their launchers (and no one else) advance the arrays to frame0 and
+// hand the kernels av1mi_frame_range's parameters.  Every other launcher runs on all P->n_frames frames.
+#ifndef AV1MI_LAUNCH_H
+#define AV1MI_LAUNCH_H
+#include <hip/hip_runtime.h>
+#include "av1mi_dev.h"
+
+// The parameters of a launch over frames [frame0, frame0 + count): n_frames is the launch's, and every per-frame map the kernels index
+// from the launch's first frame on starts there - a kernel that is given a range indexes these maps relative to the launch, whether
+// or not it reads them.  (A new per-frame map gets its line here.)
+inline Av1miDevParams av1mi_frame_range(const Av1miDevParams &P, int frame0, int count) {
+  Av1miDevParams R = P;
+  const size_t sb0 = (size_t)frame0 * P.sb_rows * P.sb_cols;
+  R.n_frames = count;
+  if (R.part_map) R.part_map += sb0;
+  if (R.aq_map) R.aq_map += sb0;
+  if (R.cdef_idx) R.cdef_idx += sb0;
+  if (R.cdef_sel) R.cdef_sel += (size_t)frame0 * 8;
+  return R;
+}
+// frame f of a chunk-wide array of frames at the coded size (8- or 16-bit samples)
+inline const void *av1mi_frame_at(const Av1miDevParams &P, const void *frames, int f) {
+  return (const uint8_t *)frames + (size_t)f * P.frame_samples * (P.bit_depth > 8 ? 2 : 1);
+}
+inline void *av1mi_frame_at(const Av1miDevParams &P, void *frames, int f) { return const_cast<void *>(av1mi_frame_at(P, (const void *)frames, f)); }
+// deblocking levels of frame f, by its kind (level [0] zero: the frame is not deblocked - the launcher's and its caller's one rule)
+inline const int *av1mi_frame_lf_levels(const Av1miDevParams &P, int f) { return av1mi_frame_is_inter(P, f) ? P.lf_level_inter : P.lf_level; }
+
+extern "C" {
+// ---- whole chunk (or call): all P->n_frames frames
+// split masks of every superblock (partition_kernel)
+hipError_t av1mi_launch_partition(const Av1miDevParams *P, const void *frames, uint32_t *part, hipStream_t stream);
+// quantiser index of every superblock (aq_activity_kernel, aq_map_kernel): act and qmap are [frame][superblock]
+hipError_t av1mi_launch_aq(const Av1miDevParams *P, const void *frames, uint16_t *act, uint8_t *qmap, int strength, hipStream_t stream);
+// quarter-resolution luma of all frames
+hipError_t av1mi_launch_quarter_luma(const Av1miDevParams *P, const void *frames, uint16_t *quarter, hipStream_t stream);
+// `frames` / `prev0` must be 16-byte aligned device pointers (checked by the caller); sad[] zeroed by the caller
+hipError_t av1mi_launch_luma_sad(const Av1miDevParams *P, const void *frames, const void *prev0, unsigned long long *sad, hipStream_t stream);
+// n_frames frames of w x h edge-extended to cw x ch, or with `crop` frames of cw x ch cut back to w x h
+hipError_t av1mi_launch_pad(const void *in, void *out, int w, int h, int cw, int ch, int bit_depth, int n_frames, int crop, hipStream_t stream);
+// squared error of a against b into sse[frame][plane] (added)
+hipError_t av1mi_launch_sse(const Av1miDevParams *P, const void *a, const void *b, unsigned long long *sse, hipStream_t stream);
+// stage 0: the frames' layout, sizes and the chunk record; stage 1: headers and tiles into `out`
+hipError_t av1mi_launch_pack(const Av1miDevParams *P, const uint8_t *slots, const uint32_t *tile_bytes, uint32_t *tile_off,
+                             uint32_t *frame_size, uint32_t *payload_size, unsigned long long *frame_off, const uint8_t *hdr_blob,
+                             uint8_t *out, int *overflow, int stage, hipStream_t stream);
+
+// ---- frames [frame0, frame0 + count) of the chunk; every array is chunk-wide
+// search centres of the frames (key frames are skipped)
+hipError_t av1mi_launch_presearch(const Av1miDevParams *P, const uint16_t *quarter, uint32_t *centre, int frame0, int count, hipStream_t stream);
+// best[] (n_frames x 8x8 units) must be filled with 0xFF bytes before the launch.  Every inter frame is searched against the source frame
+// before it.  me_range must be 8 or 16.  acc64: block_log2 = 6 - the zeroed [frame][superblock][candidate] table, else null.
+// centre: pre-search centre codes [frame][superblock], or null.
+hipError_t av1mi_launch_motion_search(const Av1miDevParams *P, const void *frames, unsigned long long *best, int me_range, int frame0,
+                                      int count, uint32_t *acc64, const uint32_t *centre, hipStream_t stream);
+// Refines the frames' vectors: `best` = the full search's keys (av1mi_launch_motion_search on the same stream before), `refined` = same
+// layout, what the reconstruction reads with subpel = 1.
+hipError_t av1mi_launch_subpel_refine(const Av1miDevParams *P, const void *frames, const unsigned long long *best, unsigned long long *refined,
+                                      int me_range, int frame0, int count, hipStream_t stream);
+// One translation unit per (largest leaf, sample type): recon_kernel.hip, recon8_kernel.hip, recon64_kernel.hip, recon64_8_kernel.hip;
+// callers go through av1mi_launch_recon below.
+// frame0 a key frame: `count` key frames in one launch (fin and me_best are not read).  frame0 an inter frame: that ONE frame (count
+// must be 1), predicted from frame frame0 - 1 of `fin`, the final frames, with its keys in `me_best`, the chunk's motion search results.
+// dP: the chunk's parameters in device memory (what the kernels read; n_frames and the loop-filter levels are not used by them),
+// followed with adaptive quantisation by the quantiser slots' copies.  The kernels get P's split masks and quantiser indices from the
+// launch's first frame on.
+hipError_t av1mi_launch_recon_u16(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels, Av1miBlkInfo *blk,
+                                  const void *fin, const unsigned long long *me_best, int frame0, int count, hipStream_t stream);
+hipError_t av1mi_launch_recon_u8(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels, Av1miBlkInfo *blk,
+                                 const void *fin, const unsigned long long *me_best, int frame0, int count, hipStream_t stream);
+hipError_t av1mi_launch_recon64_u16(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels, Av1miBlkInfo *blk,
+                                    const void *fin, const unsigned long long *me_best, int frame0, int count, hipStream_t stream);
+hipError_t av1mi_launch_recon64_u8(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels, Av1miBlkInfo *blk,
+                                   const void *fin, const unsigned long long *me_best, int frame0, int count, hipStream_t stream);
+// both passes over the frames of `rec`, in place, with the levels of frame0's kind (av1mi_frame_lf_levels)
+hipError_t av1mi_launch_deblock(const Av1miDevParams *P, void *rec, const Av1miBlkInfo *blk, int frame0, int count, hipStream_t stream);
+// the strength search (P->cdef_err zeroed by the caller), then the selection; one-frame launches (the P-frame chain) in 8-row strips, as CDEF
+hipError_t av1mi_launch_cdef_search(const Av1miDevParams *P, const void *rec, const void *src, const Av1miBlkInfo *blk, uint8_t *hdr_blob,
+                                    int frame0, int count, hipStream_t stream);
+// `rec` filtered into `fin` (the caller's choice of output array).  src and sse, both or neither: the squared error of the output against
+// the source is added to sse[frame][plane] - launches of several frames only (a one-frame launch sits on an inter chunk's serial chain:
+// it runs in strips and cannot sum it)
+hipError_t av1mi_launch_cdef(const Av1miDevParams *P, const void *rec, void *fin, const Av1miBlkInfo *blk, const void *src,
+                             unsigned long long *sse, int frame0, int count, hipStream_t stream);
+// choice and unit_sse: [frame][plane][unit] (av1mi_lr_frame_units per frame), unit_sse with 8 sums per unit - scratch of the two phases,
+// cleared here for the launch's frames with `clear`, else by the caller (the frame loop of a P chunk clears the whole chunk's once
+// instead of putting a fill between every frame's kernels on the chain)
+hipError_t av1mi_launch_lr(const Av1miDevParams *P, const void *pre, const void *cdef, const void *src, void *out, uint8_t *choice,
+                           unsigned long long *unit_sse, int clear, int frame0, int count, hipStream_t stream);
+// tile_order: n_tiles entries of scratch.  mid: recorded on `stream` after symbolize, or null.  aux != null: the frame-edge tiles'
+// symbolize variant runs there, beside the regular one, between `fork` and `join`
+hipError_t av1mi_launch_entropy(const Av1miDevParams *P, const uint16_t *cdf_init, const int16_t *levels, const Av1miBlkInfo *blk,
+                                uint32_t *streams, uint32_t *stream_len, uint32_t *tile_combos, uint8_t *slots, uint32_t *tile_bytes,
+                                const uint8_t *lr_choice, uint32_t *tile_order, int frame0, int count,
+                                hipStream_t stream, hipEvent_t mid, hipStream_t aux, hipEvent_t fork, hipEvent_t join);
+}
+
+// 64x64 leaf blocks run the kernels of recon64_kernel.hip (64-point transforms, larger LDS tiles)
+inline hipError_t av1mi_launch_recon(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels, Av1miBlkInfo *blk,
+                                     const void *fin, const unsigned long long *me_best, int frame0, int count, hipStream_t stream) {
+  return (P->max_bs_log2 >= 6 ? (P->bit_depth == 8 ? av1mi_launch_recon64_u8 : av1mi_launch_recon64_u16)
+                              : (P->bit_depth == 8 ? av1mi_launch_recon_u8 : av1mi_launch_recon_u16))(P, dP, src, rec, levels, blk, fin, me_best, frame0, count, stream);
+}
+
+#endif

@@ -13,6 +13,7 @@
 //     Section-5 OBU stream (temporal delimiter, sequence header, OBU_FRAME with tile sizes).
 #include <hip/hip_runtime.h>
 #include "av1mi_dev.h"
+#include "av1mi_launch.h"
 
 namespace {
 
@@ -808,33 +809,33 @@ __global__ void __launch_bounds__(64) pack_tiles_kernel(Av1miDevParams P, const 
 
 }  // namespace
 
-// src and sse: the squared error of the output against the source is added to sse[frame][plane] - chunk-wide launches only (the
-// host decides; a one-frame launch runs in strips and cannot sum it)
 extern "C" hipError_t av1mi_launch_cdef(const Av1miDevParams *P, const void *rec, void *fin, const Av1miBlkInfo *blk, const void *src,
-                                        unsigned long long *sse, hipStream_t stream) {
-  const int grid = P->n_frames * P->sb_rows * P->sb_cols;
-  const bool strips = P->n_frames == 1;  // a one-frame launch sits on an inter chunk's serial chain
-  const bool sel = P->cdef_search != 0;   // the search's pairs: some may have a secondary strength (the SEC kernels branch per superblock)
-  const bool sec = sel || P->cdef_y_sec != 0 || P->cdef_uv_sec != 0;
+                                        unsigned long long *sse, int frame0, int count, hipStream_t stream) {
+  const Av1miDevParams R = av1mi_frame_range(*P, frame0, count);
+  rec = av1mi_frame_at(R, rec, frame0); fin = av1mi_frame_at(R, fin, frame0); blk += (size_t)frame0 * R.b8_rows * R.b8_cols;
+  if (src) src = av1mi_frame_at(R, src, frame0);
+  if (sse) sse += (size_t)frame0 * 3;
+  const int grid = count * R.sb_rows * R.sb_cols;
+  const bool strips = count == 1;  // a one-frame launch sits on an inter chunk's serial chain
+  const bool sel = R.cdef_search != 0;   // the search's pairs: some may have a secondary strength (the SEC kernels branch per superblock)
+  const bool sec = sel || R.cdef_y_sec != 0 || R.cdef_uv_sec != 0;
   const bool sse_here = src || sse;
   if (sse_here && (strips || !src || !sse)) return hipErrorInvalidValue;
-  if (sel && (!P->cdef_idx || !P->cdef_sel)) return hipErrorInvalidValue;
+  if (sel && (!R.cdef_idx || !R.cdef_sel)) return hipErrorInvalidValue;
   // one-frame launches: 8-row strips (4 080 waves at 1080p, still one round of the chip) - 16-row strips were 2.5 us per frame slower
 #define CDEF_LAUNCH2(PIXT, SECV, SELV)                                                                                                     \
   do {                                                                                                                                     \
-    if (strips) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 8, SECV, false, SELV>), dim3(grid * 8), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, nullptr, nullptr); \
-    else if (sse_here) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 1, SECV, true, SELV>), dim3(grid), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, (const PIXT *)src, sse); \
-    else hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 1, SECV, false, SELV>), dim3(grid), dim3(64), 0, stream, *P, (const PIXT *)rec, (PIXT *)fin, blk, nullptr, nullptr); \
+    if (strips) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 8, SECV, false, SELV>), dim3(grid * 8), dim3(64), 0, stream, R, (const PIXT *)rec, (PIXT *)fin, blk, nullptr, nullptr);  \
+    else if (sse_here) hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 1, SECV, true, SELV>), dim3(grid), dim3(64), 0, stream, R, (const PIXT *)rec, (PIXT *)fin, blk, (const PIXT *)src, sse);  \
+    else hipLaunchKernelGGL((cdef_sb_kernel<PIXT, 1, SECV, false, SELV>), dim3(grid), dim3(64), 0, stream, R, (const PIXT *)rec, (PIXT *)fin, blk, nullptr, nullptr);  \
   } while (0)
 #define CDEF_LAUNCH(PIXT) do { if (sel) CDEF_LAUNCH2(PIXT, true, true); else if (sec) CDEF_LAUNCH2(PIXT, true, false); else CDEF_LAUNCH2(PIXT, false, false); } while (0)
-  if (P->bit_depth == 8) CDEF_LAUNCH(uint8_t); else CDEF_LAUNCH(uint16_t);
+  if (R.bit_depth == 8) CDEF_LAUNCH(uint8_t); else CDEF_LAUNCH(uint16_t);
 #undef CDEF_LAUNCH2
 #undef CDEF_LAUNCH
   return hipGetLastError();
 }
 
-// the strength search over frames [frame0, frame0 + count) of the chunk (P.cdef_err zeroed by the caller; rec / src chunk-wide), then the
-// selection; one-frame launches (the P-frame chain) in 8-row strips, as CDEF
 extern "C" hipError_t av1mi_launch_cdef_search(const Av1miDevParams *P, const void *rec, const void *src, const Av1miBlkInfo *blk, uint8_t *hdr_blob,
                                                int frame0, int count, hipStream_t stream) {
   if (!P->cdef_search || !P->cdef_err || !P->cdef_idx || !P->cdef_sel) return hipErrorInvalidValue;

@@ -10,6 +10,7 @@
 // edges; algorithmic bytes <= 2 * 2 * N * b per frame (both passes, read + write).
 #include <hip/hip_runtime.h>
 #include "av1mi_dev.h"
+#include "av1mi_launch.h"
 
 namespace {
 
@@ -122,16 +123,18 @@ __global__ void __launch_bounds__(256) deblock_kernel(Av1miDevParams P, PIX *__r
 
 }  // namespace
 
-// both passes over P->n_frames frames of `rec`, in place
-extern "C" hipError_t av1mi_launch_deblock(const Av1miDevParams *P, void *rec, const Av1miBlkInfo *blk, hipStream_t stream) {
-  const long n = (long)P->mi_rows * P->mi_cols * 3 / 2;
-  dim3 grid((unsigned)((n + 255) / 256), P->n_frames);
-  if (P->bit_depth == 8) {
-    hipLaunchKernelGGL((deblock_kernel<uint8_t, 0>), grid, dim3(256), 0, stream, *P, (uint8_t *)rec, blk);
-    hipLaunchKernelGGL((deblock_kernel<uint8_t, 1>), grid, dim3(256), 0, stream, *P, (uint8_t *)rec, blk);
+extern "C" hipError_t av1mi_launch_deblock(const Av1miDevParams *P, void *rec, const Av1miBlkInfo *blk, int frame0, int count, hipStream_t stream) {
+  Av1miDevParams R = av1mi_frame_range(*P, frame0, count);
+  for (int i = 0; i < 4; i++) R.lf_level[i] = av1mi_frame_lf_levels(*P, frame0)[i];
+  rec = av1mi_frame_at(R, rec, frame0); blk += (size_t)frame0 * R.b8_rows * R.b8_cols;
+  const long n = (long)R.mi_rows * R.mi_cols * 3 / 2;
+  dim3 grid((unsigned)((n + 255) / 256), count);
+  if (R.bit_depth == 8) {
+    hipLaunchKernelGGL((deblock_kernel<uint8_t, 0>), grid, dim3(256), 0, stream, R, (uint8_t *)rec, blk);
+    hipLaunchKernelGGL((deblock_kernel<uint8_t, 1>), grid, dim3(256), 0, stream, R, (uint8_t *)rec, blk);
   } else {
-    hipLaunchKernelGGL((deblock_kernel<uint16_t, 0>), grid, dim3(256), 0, stream, *P, (uint16_t *)rec, blk);
-    hipLaunchKernelGGL((deblock_kernel<uint16_t, 1>), grid, dim3(256), 0, stream, *P, (uint16_t *)rec, blk);
+    hipLaunchKernelGGL((deblock_kernel<uint16_t, 0>), grid, dim3(256), 0, stream, R, (uint16_t *)rec, blk);
+    hipLaunchKernelGGL((deblock_kernel<uint16_t, 1>), grid, dim3(256), 0, stream, R, (uint16_t *)rec, blk);
   }
   return hipGetLastError();
 }

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdlib>
 #include "av1mi_dev.h"
+#include "av1mi_launch.h"
 
 namespace {
 
@@ -1320,10 +1321,8 @@ __global__ void __launch_bounds__(128) rangecode2_tiles_kernel(Av1miDevParams P,
 
 extern "C" hipError_t av1mi_launch_entropy(const Av1miDevParams *P, const uint16_t *cdf_init, const int16_t *levels,
                                            const Av1miBlkInfo *blk, uint32_t *streams, uint32_t *stream_len, uint32_t *tile_combos,
-                                           uint8_t *slots, uint32_t *tile_bytes, const uint8_t *lr_choice, uint32_t *tile_order /* n_tiles entries of scratch */,
-                                           int frame0, int count /* frames [frame0, frame0 + count) of the chunk: all arrays are chunk-wide */,
-                                           hipStream_t stream, hipEvent_t mid,
-                                           hipStream_t aux, hipEvent_t fork, hipEvent_t join /* aux != nullptr: the frame-edge tiles' variant runs there, beside the regular one */) {
+                                           uint8_t *slots, uint32_t *tile_bytes, const uint8_t *lr_choice, uint32_t *tile_order, int frame0, int count,
+                                           hipStream_t stream, hipEvent_t mid, hipStream_t aux, hipEvent_t fork, hipEvent_t join) {
   const int tpf = P->tile_rows * P->tile_cols;
   const int n_tiles = count * tpf, tile0 = frame0 * tpf;
   bool has_inter = false, has_key = false;

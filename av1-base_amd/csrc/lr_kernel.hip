@@ -16,6 +16,7 @@
 // + source read + final write = ~3*L*b + N*b per frame (~3*N*b with the chroma units).
 #include <hip/hip_runtime.h>
 #include "av1mi_dev.h"
+#include "av1mi_launch.h"
 
 namespace {
 
@@ -513,21 +514,21 @@ void launch_lr_typed(const Av1miDevParams *P, int grid, const void *pre, const v
 
 }  // namespace
 
-// unit_sse: P->n_frames x planes x units x 8 sums, planes = 3 with P->lr_chroma, else 1 (scratch of the two phases; cleared here
-// unless the caller did - the frame loop of a P chunk clears the whole chunk's once instead of putting a fill between every frame's
-// kernels on the chain).
 extern "C" hipError_t av1mi_launch_lr(const Av1miDevParams *P, const void *pre, const void *cdef, const void *src, void *out, uint8_t *choice,
-                                      unsigned long long *unit_sse, int clear, hipStream_t stream) {
-  const int urows = (P->true_h + 32) / 64 > 0 ? (P->true_h + 32) / 64 : 1, ucols = (P->true_w + 32) / 64 > 0 ? (P->true_w + 32) / 64 : 1;
-  const int units = P->n_frames * urows * ucols, planes = P->lr_chroma ? 3 : 1;
-  // chroma: per frame and plane, unit rows x pairs of unit columns, LR_SLICES_C waves each (the signalled size is even, so the chroma
-  // unit grid is the luma one)
-  const int grid = units * LR_SLICES + (P->lr_chroma ? P->n_frames * 2 * urows * ((ucols + 1) / 2) * LR_SLICES_C : 0);
+                                      unsigned long long *unit_sse, int clear, int frame0, int count, hipStream_t stream) {
+  const Av1miDevParams R = av1mi_frame_range(*P, frame0, count);
+  const int urows = av1mi_lr_unit_rows(R), ucols = av1mi_lr_unit_cols(R);
+  const size_t upf = (size_t)av1mi_lr_frame_units(R);
+  pre = av1mi_frame_at(R, pre, frame0); cdef = av1mi_frame_at(R, cdef, frame0); src = av1mi_frame_at(R, src, frame0); out = av1mi_frame_at(R, out, frame0);
+  choice += frame0 * upf; unit_sse += frame0 * upf * 8;
+  // luma: LR_SLICES waves per unit; chroma: per frame and plane, unit rows x pairs of unit columns, LR_SLICES_C waves each (the signalled
+  // size is even, so the chroma unit grid is the luma one)
+  const int grid = count * urows * ucols * LR_SLICES + (R.lr_chroma ? count * 2 * urows * ((ucols + 1) / 2) * LR_SLICES_C : 0);
   if (clear) {
-    hipError_t e = hipMemsetAsync(unit_sse, 0, (size_t)units * planes * 8 * sizeof(unsigned long long), stream);
+    hipError_t e = hipMemsetAsync(unit_sse, 0, count * upf * 8 * sizeof(unsigned long long), stream);
     if (e != hipSuccess) return e;
   }
-  if (P->bit_depth == 8) launch_lr_typed<uint8_t>(P, grid, pre, cdef, src, out, choice, unit_sse, stream);
-  else launch_lr_typed<uint16_t>(P, grid, pre, cdef, src, out, choice, unit_sse, stream);
+  if (R.bit_depth == 8) launch_lr_typed<uint8_t>(&R, grid, pre, cdef, src, out, choice, unit_sse, stream);
+  else launch_lr_typed<uint16_t>(&R, grid, pre, cdef, src, out, choice, unit_sse, stream);
   return hipGetLastError();
 }

@@ -22,6 +22,7 @@
 // the (2R+1)-fold re-reads of the reference by the dy waves of a cell are L2 hits.
 #include <hip/hip_runtime.h>
 #include "av1mi_dev.h"
+#include "av1mi_launch.h"
 #include "av1_tables.h"
 
 namespace {
@@ -617,21 +618,17 @@ __global__ void __launch_bounds__(128) presearch_kernel(Av1miDevParams P, const 
 
 }  // namespace
 
-// quarter-resolution luma of all P->n_frames frames of the chunk
 extern "C" hipError_t av1mi_launch_quarter_luma(const Av1miDevParams *P, const void *frames, uint16_t *quarter, hipStream_t stream) {
   dim3 grid(128, P->n_frames);
   if (P->bit_depth == 8) hipLaunchKernelGGL(quarter_luma_kernel<uint8_t>, grid, dim3(256), 0, stream, *P, (const uint8_t *)frames, quarter);
   else hipLaunchKernelGGL(quarter_luma_kernel<uint16_t>, grid, dim3(256), 0, stream, *P, (const uint16_t *)frames, quarter);
   return hipGetLastError();
 }
-// search centres of frames [frame0, frame0 + count) (key frames are skipped)
 extern "C" hipError_t av1mi_launch_presearch(const Av1miDevParams *P, const uint16_t *quarter, uint32_t *centre, int frame0, int count, hipStream_t stream) {
   hipLaunchKernelGGL(presearch_kernel, dim3(P->sb_rows * P->sb_cols, count), dim3(128), 0, stream, *P, quarter, centre, frame0);
   return hipGetLastError();
 }
 
-// Refines the vectors of frames [frame0, frame0 + count): `best` = the full search's keys (av1mi_launch_motion_search on the
-// same stream before), `refined` = same layout, what the recon kernel reads with subpel = 1.
 extern "C" hipError_t av1mi_launch_subpel_refine(const Av1miDevParams *P, const void *frames, const unsigned long long *best,
                                                  unsigned long long *refined, int me_range, int frame0, int count, hipStream_t stream) {
   // one wave per cell of the largest block size (every wave has work, and consecutive workgroups - which the dispatcher deals
@@ -643,12 +640,8 @@ extern "C" hipError_t av1mi_launch_subpel_refine(const Av1miDevParams *P, const 
   return hipGetLastError();
 }
 
-// best[] (n_frames x 8x8 units) must be filled with 0xFF bytes before the launch.  `frames`: the chunk's source frames
-// (P->n_frames of them); every inter frame is searched against the source frame before it.  R must be 8 or 16.
-// Searches frames [frame0, frame0 + count) of the chunk.
 extern "C" hipError_t av1mi_launch_motion_search(const Av1miDevParams *P, const void *frames, unsigned long long *best, int me_range,
-                                                 int frame0, int count, uint32_t *acc64 /* block_log2 = 6: zeroed [frame][superblock][candidate] table, else null */,
-                                                 const uint32_t *centre /* pre-search centre codes [frame][superblock], or null */, hipStream_t stream) {
+                                                 int frame0, int count, uint32_t *acc64, const uint32_t *centre, hipStream_t stream) {
   const int cells = ((P->width + 31) >> 5) * ((P->height + 31) >> 5);
   dim3 grid(cells, 2 * me_range + 1, count);
   const int vec_ok = ((uintptr_t)frames & 15) == 0;  // frame size in bytes is a multiple of 32

@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "av1mi_dev.h"
+#include "av1mi_launch.h"
 #include "av1_tables.h"
 // This file is compiled twice: as is (leaf blocks up to 32x32: the kernels keep their 10 KB of LDS and 4 waves per SIMD), and
 // through recon64_kernel.hip with AV1MI_RECON_BIG = 1 (block_log2 = 6: 64x64 luma blocks with the 64-point transform, 32x32
@@ -1799,10 +1800,6 @@ extern "C" int av1mi_debug_stamps(unsigned long long *out, int reset) {
 }
 #endif
 
-// ref == nullptr: P->n_frames key frames in one launch.  ref != nullptr: ONE inter frame (P->n_frames must be 1),
-// predicted from `ref` with the motion search results `me_best` of that frame.
-// dP: the same parameters in device memory (what the kernel reads; n_frames and the loop-filter levels are not used by it), followed
-// with adaptive quantisation (P->aq_map: the quantiser indices of the launch's first frame on) by the quantiser slots' copies.
 #if AV1MI_RECON_BIG && AV1MI_RECON_PIX8
 #define AV1MI_LAUNCH_RECON av1mi_launch_recon64_u8   /* leaf blocks up to 64x64 (P->max_bs_log2 == 6), 8-bit samples */
 #elif AV1MI_RECON_BIG
@@ -1818,18 +1815,26 @@ typedef uint8_t ReconPix;
 typedef uint16_t ReconPix;
 #endif
 extern "C" hipError_t AV1MI_LAUNCH_RECON(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels,
-                                         Av1miBlkInfo *blk, const void *ref, const unsigned long long *me_best, const uint32_t *part, hipStream_t stream) {
-  const int grid = P->n_frames * P->tile_rows * P->tile_cols;
-  const bool inter = ref != nullptr;
+                                         Av1miBlkInfo *blk, const void *fin, const unsigned long long *me_best, int frame0, int count, hipStream_t stream) {
+  const bool inter = av1mi_frame_is_inter(*P, frame0);
+  if (inter && (count != 1 || !fin || !me_best)) return hipErrorInvalidValue;
+  const Av1miDevParams R = av1mi_frame_range(*P, frame0, count);
+  const size_t nb8 = (size_t)P->b8_rows * P->b8_cols;
+  const void *ref = inter ? av1mi_frame_at(R, fin, frame0 - 1) : nullptr;
+  me_best = inter ? me_best + frame0 * nb8 : nullptr;
+  src = av1mi_frame_at(R, src, frame0); rec = av1mi_frame_at(R, rec, frame0);
+  levels += (size_t)frame0 * P->sb_rows * P->sb_cols * AV1MI_SB_LEVELS; blk += frame0 * nb8;
+  const uint32_t *part = R.part_map;
+  const int grid = count * P->tile_rows * P->tile_cols;
   if (inter) {  // first launch of an inter frame: every block as an inter block, all at once (see recon_inter_pre_kernel)
     const int g = P->max_bs_log2 > (AV1MI_RECON_BIG ? 6 : 5) ? (AV1MI_RECON_BIG ? 6 : 5) : P->max_bs_log2, cell = 1 << g;
     dim3 pgrid((P->width + cell - 1) / cell, (P->height + cell - 1) / cell, 2);   // z: luma | chroma
 #define PRE_LAUNCH2(PIXT, SPV)                                                                                                               \
     do {                                                                                                                                     \
       if (P->qm_tab) hipLaunchKernelGGL((recon_inter_pre_kernel<PIXT, true, SPV>), pgrid, dim3(64), 0, stream, dP, (const PIXT *)src, (PIXT *)rec, \
-                                        levels, blk, (const PIXT *)ref, me_best, g, part, P->aq_map);                                                   \
+                                        levels, blk, (const PIXT *)ref, me_best, g, part, R.aq_map);                                                    \
       else hipLaunchKernelGGL((recon_inter_pre_kernel<PIXT, false, SPV>), pgrid, dim3(64), 0, stream, dP, (const PIXT *)src, (PIXT *)rec,          \
-                              levels, blk, (const PIXT *)ref, me_best, g, part, P->aq_map);                                                             \
+                              levels, blk, (const PIXT *)ref, me_best, g, part, R.aq_map);                                                              \
     } while (0)
 #define PRE_LAUNCH(PIXT) do { if (P->subpel) PRE_LAUNCH2(PIXT, true); else PRE_LAUNCH2(PIXT, false); } while (0)
     PRE_LAUNCH(ReconPix);
@@ -1840,9 +1845,9 @@ extern "C" hipError_t AV1MI_LAUNCH_RECON(const Av1miDevParams *P, const Av1miDev
 #define RECON_LAUNCH2(PIXT, INTERV, TSBV, EXTV)                                                                                             \
   do {                                                                                                                                      \
     if (P->qm_tab) hipLaunchKernelGGL((recon_sb_kernel<PIXT, INTERV, TSBV, true, EXTV>), dim3(grid), dim3(WalkSplit<INTERV>::value ? 128 : 64), 0, stream, dP, (const PIXT *)src,  \
-                                      (PIXT *)rec, levels, blk, (const PIXT *)ref, me_best, part, P->aq_map);                                          \
+                                      (PIXT *)rec, levels, blk, (const PIXT *)ref, me_best, part, R.aq_map);                                           \
     else hipLaunchKernelGGL((recon_sb_kernel<PIXT, INTERV, TSBV, false, EXTV>), dim3(grid), dim3(WalkSplit<INTERV>::value ? 128 : 64), 0, stream, dP, (const PIXT *)src,           \
-                            (PIXT *)rec, levels, blk, (const PIXT *)ref, me_best, part, P->aq_map);                                                    \
+                            (PIXT *)rec, levels, blk, (const PIXT *)ref, me_best, part, R.aq_map);                                                     \
   } while (0)
   // the optional intra tools (edge filter, chroma from luma) live in instantiations of their own (EXT)
 #define RECON_LAUNCH(PIXT, INTERV, TSBV)                                                                                                    \

@@ -9,6 +9,7 @@
 // t-1) with 16-byte loads per lane; algorithmic bytes 2*L*b per frame pair (L luma samples).
 #include <hip/hip_runtime.h>
 #include "av1mi_dev.h"
+#include "av1mi_launch.h"
 #include "aq_rule.h"
 
 namespace {
@@ -198,7 +199,6 @@ __global__ void __launch_bounds__(256) aq_map_kernel(Av1miDevParams P, const uin
 
 }  // namespace
 
-// split masks of every superblock of P->n_frames frames (partition_kernel)
 extern "C" hipError_t av1mi_launch_partition(const Av1miDevParams *P, const void *frames, uint32_t *part, hipStream_t stream) {
   dim3 grid(P->sb_rows * P->sb_cols, P->n_frames);
   if (P->bit_depth == 8) hipLaunchKernelGGL(partition_kernel<uint8_t>, grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, part);
@@ -206,7 +206,6 @@ extern "C" hipError_t av1mi_launch_partition(const Av1miDevParams *P, const void
   return hipGetLastError();
 }
 
-// quantiser index of every superblock of P->n_frames frames (aq_activity_kernel, aq_map_kernel): act and qmap are [frame][superblock]
 extern "C" hipError_t av1mi_launch_aq(const Av1miDevParams *P, const void *frames, uint16_t *act, uint8_t *qmap, int strength, hipStream_t stream) {
   dim3 grid(P->sb_rows * P->sb_cols, P->n_frames);
   if (P->bit_depth == 8) hipLaunchKernelGGL(aq_activity_kernel<uint8_t>, grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, act);
@@ -228,7 +227,6 @@ extern "C" hipError_t av1mi_launch_pad(const void *in, void *out, int w, int h, 
   return hipGetLastError();
 }
 
-// `frames`/`prev0` must be 16-byte aligned device pointers (checked by the caller); sad[] zeroed by the caller.
 extern "C" hipError_t av1mi_launch_luma_sad(const Av1miDevParams *P, const void *frames, const void *prev0, unsigned long long *sad,
                                             hipStream_t stream) {
   const int bps = P->bit_depth > 8 ? 2 : 1;

@@ -1,10 +1,12 @@
 """GPU tests of the chunk's host path: what a context keeps from one chunk to the next (header blob, default CDFs and kernel
-parameters on the device), the chunk record the packing kernels fill, and the
-compact grid of the frame-edge tiles' symbolize variant.  Every expectation is the oracle's bytes, or a fresh context's."""
+parameters on the device), the chunk record the packing kernels fill, the
+compact grid of the frame-edge tiles' symbolize variant, and the launches over part of a chunk (frames [frame0, frame0 + count):
+av1-base_amd/csrc/av1mi_launch.h).  Every expectation is the oracle's bytes, or a fresh context's."""
 import numpy as np
 import pytest
 
 import edge_content as E
+from test_lr_chroma import clip
 
 pytestmark = pytest.mark.gpu
 
@@ -41,9 +43,10 @@ def run_oracle(oracle, case, frames):
     return tus, recs, sse, nsym
 
 
-def assert_equals_oracle(av1mi, ctx, oracle, case, frames, report=True, what=""):
+def assert_equals_oracle(av1mi, ctx, oracle, case, frames, report=True, what="", expect=None):
+    """`expect`: run_oracle's result for the chunk, where several tests share it"""
     data, sizes, rep, recon = run_gpu(av1mi, ctx, case, frames)
-    tus, recs, sse, nsym = run_oracle(oracle, case, frames)
+    tus, recs, sse, nsym = expect if expect is not None else run_oracle(oracle, case, frames)
     assert sizes == [len(t) for t in tus], what
     assert data == b"".join(tus), what
     assert recon == recs, what
@@ -187,3 +190,49 @@ def test_report_symbol_counts_come_from_the_chunk_record(av1mi, ctx, oracle):
     nsym = run_oracle(oracle, case, frames)[3]
     assert len(set(nsym)) > 1
     assert rep.max_tile_symbols == max(nsym) and rep.n_symbols == sum(nsym)
+
+
+# Launches over part of a chunk, at the smallest frame with more than one superblock each way and a partial last row and column
+# (136 x 72: 3 x 2 superblocks); content whose restoration units choose off, Wiener and self-guided filters.
+RANGE_CASES = {
+    # frames 1, 2, 3 are inter launches at frame0 = 1, 2, 3: split masks, sub-sample keys, the inter frames' deblocking levels,
+    # restoration choices and sums per frame
+    "inter_10bit": case_of(136, 72, 10, 4, keyint=240, deblock=1, subpel=1, me_presearch=1, partition_search=1, min_block_log2=3, enable_lr=2,
+                           enable_qm=1, qm_min=1),
+    # key-frame launches at frame0 = 2 and 4 inside an inter chunk; the 64x64 reconstruction units, tiles of two superblocks
+    "keys_8bit": case_of(136, 72, 8, 5, keyint=2, block_log2=6, deblock=1, enable_lr=1, tile_sb=2),
+}
+
+
+@pytest.fixture(scope="module")
+def range_cases(oracle):
+    """name -> (case, frames, the oracle's chunk)"""
+    out = {}
+    for name, case in RANGE_CASES.items():
+        frames = clip(oracle, case["w"], case["h"], case["bd"], case["n"], seed=61)
+        out[name] = (case, frames, run_oracle(oracle, case, frames))
+    return out
+
+
+@pytest.mark.parametrize("group", [None, "2"], ids=["one_group", "groups_of_2"])
+def test_inter_launches_at_every_frame_of_a_chunk(av1mi, ctx, oracle, range_cases, monkeypatch, group):
+    """... and with AV1MI_ENTROPY_GROUP = 2 the entropy coder's ranges: frames [0, 2) on the third stream, [2, 4) after the chain"""
+    if group is not None:
+        monkeypatch.setenv("AV1MI_ENTROPY_GROUP", group)
+    case, frames, expect = range_cases["inter_10bit"]
+    assert_equals_oracle(av1mi, ctx, oracle, case, frames, expect=expect)
+
+
+def test_key_frame_launches_inside_an_inter_chunk(av1mi, ctx, oracle, range_cases):
+    case, frames, expect = range_cases["keys_8bit"]
+    assert_equals_oracle(av1mi, ctx, oracle, case, frames, expect=expect)
+
+
+def test_frame_ranges_on_a_reused_context(av1mi, oracle, range_cases):
+    """both chunks in turn, twice, on one context: the parameters a context keeps (and the block cached on the device) are the chunk's,
+    never a launch's range of it"""
+    with av1mi.Context(0) as c:
+        for turn in range(2):
+            for name in ("inter_10bit", "keys_8bit"):
+                case, frames, expect = range_cases[name]
+                assert_equals_oracle(av1mi, c, oracle, case, frames, what="turn %d: %s" % (turn, name), expect=expect)
