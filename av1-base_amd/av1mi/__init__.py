@@ -36,7 +36,7 @@ E_INVALID_ARG, E_NO_DEVICE, E_HIP, E_OOM, E_OVERFLOW, E_FORMAT, E_UNSUPPORTED = 
 
 # every symbol include/av1mi.h declares
 ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", "av1mi_last_error", "av1mi_encode_chunk",
-               "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex"]
+               "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result"]
 
 
 class Params(C.Structure):
@@ -113,6 +113,7 @@ _lib.av1mi_struct_sizes.argtypes = [C.POINTER(C.c_uint32), C.c_uint32]
 _lib.av1mi_struct_sizes.restype = C.c_uint32
 ABI_VERSION = 8   # include/av1mi.h: AV1MI_ABI_VERSION this mirror was written against
 _lib.av1mi_aq_qindex.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8)]
+_lib.av1mi_lf_search_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
 _lib.av1mi_write_headers.argtypes = [C.POINTER(Params), C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_size_t)]
 
 
@@ -288,6 +289,16 @@ class Context:
         rc = _lib.av1mi_aq_qindex(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0, out.ctypes.data_as(C.POINTER(C.c_uint8)))
         _raise_for(rc, self.last_error())
         return out
+
+    def lf_search_result(self, n_frames):
+        """The deblocking levels of the last encoded chunk and the level search's error table (include/av1mi.h:
+        av1mi_lf_search_result): numpy arrays levels[frame][4] (uint8) and err[frame][plane][16] (uint64, zeros unless deblock = 2)."""
+        import numpy as np
+        levels = np.zeros((n_frames, 4), dtype=np.uint8)
+        err = np.zeros((n_frames, 3, 16), dtype=np.uint64)
+        rc = _lib.av1mi_lf_search_result(self._h, n_frames, levels.ctypes.data_as(C.POINTER(C.c_uint8)), err.ctypes.data_as(C.POINTER(C.c_uint64)))
+        _raise_for(rc, "av1mi_lf_search_result: the context's last successfully encoded chunk does not have %d frames (or there is none)" % n_frames)
+        return levels, err
 
     def encode_chunk(self, params, frames, n_frames, on_device=False, want_recon=False, recon_ptr=None, copy_out=True):
         """frames: bytes-like/numpy (host) or an int device pointer (on_device=True).

@@ -93,6 +93,14 @@ struct Av1miDevParams {
   int me_presearch;               // inter frames: 1 = the full search runs around the centre a quarter-resolution pre-search found per superblock
   // deblocking filter: loop_filter_level[0..3] (luma vertical edges, luma horizontal, U, V) of key / inter frames and sharpness
   int lf_level[4], lf_level_inter[4], lf_sharpness;
+  // level search (av1mi_params.deblock = 2): lf_search = 1 - the levels above are the header's placeholders and
+  // decide only whether a frame is deblocked (level [0] is at least 1); the frames' levels are chosen on the device (the pointers are
+  // null when it is off).  lf_search_g[0 / 1]: the level the quantiser formula gives key / inter frames, the centre of the candidate
+  // pool; lf_err: per [frame][plane] the 16 candidates' squared errors (deblock_search_kernel); lf_sel: per frame the four levels
+  // (deblock_decide_kernel; read by deblock_kernel); lf_bit[0 / 1]: bit offset of loop_filter_level[0] in a key / inter frame header
+  int lf_search, lf_search_g[2], lf_bit[2];
+  unsigned long long *lf_err;
+  uint8_t *lf_sel;
   // loop restoration (luma Wiener, 64x64 units): literal bits that code candidate k's coefficients against the
   // reference RefLrWiener (both passes), MSB first in the low `lr_code_len[r][k]` bits
   int enable_lr;                         // the frames' restoration type: 1 = RESTORE_WIENER, 2 = RESTORE_SWITCHABLE (any plane)

@@ -26,6 +26,7 @@
 #include "av1_tables.h"
 #include "av1mi_dev.h"
 #include "av1mi_launch.h"
+#include "deblock_pieces.h"
 #include "aq_rule.h"
 
 namespace {
@@ -107,6 +108,7 @@ int resolve(const av1mi_params *in, Resolved *r) {
   if (p.cdef_damping == 0) { p.cdef_y_pri = 2; p.cdef_y_sec = 0; p.cdef_uv_pri = 1; p.cdef_uv_sec = 0; p.cdef_damping = 5; }
   if (p.cdef_damping < 3 || p.cdef_damping > 6 || p.cdef_y_pri > 15 || p.cdef_uv_pri > 15 || p.cdef_y_sec > 3 || p.cdef_uv_sec > 3) return AV1MI_E_INVALID_ARG;
   if (p.cdef_search > 4 || (p.cdef_search && !p.enable_cdef)) return AV1MI_E_INVALID_ARG;
+  if (p.deblock > 2) return AV1MI_E_INVALID_ARG;
   r->qidx = kQuantizerToQindex[p.cq_level];
   r->q = quant_steps(r->qidx, (int)p.bit_depth);
   if (p.subpel > 1 || p.enable_lr > 4 || p.color_range > 1 || p.intra_angle_delta > 1 || p.intra_edge_filter > 1 || p.cfl > 1 || p.tx_search > 1) return AV1MI_E_INVALID_ARG;
@@ -204,7 +206,11 @@ std::vector<uint8_t> make_sequence_header(const Resolved &r) {
 // tile_group_obu's tile_start_and_end_present_flag + byte_alignment (§5.11.1)
 // cdef_str_bit (optional): bit offset of the first CDEF strength field - with the search on (cdef_bits > 0) the header carries the fixed
 // strengths as placeholders, 2^cdef_bits times, and cdef_select_kernel overwrites those 12 * 2^cdef_bits bits in the frame's slot
-std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint32_t frame_number = 0, bool inter = false, size_t *cdef_str_bit = nullptr) {
+// lf_bit (optional): bit offset of loop_filter_level[0] - with the level search on (deblock = 2) the header carries the pool's D = 0
+// entries as placeholders, max(g, 1), max(g, 1), g, g, and deblock_decide_kernel overwrites those 24 bits in the frame's slot (luma
+// never picks 0, so all four fields are coded whatever is chosen)
+std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint32_t frame_number = 0, bool inter = false, size_t *cdef_str_bit = nullptr,
+                                       size_t *lf_bit = nullptr) {
   const av1mi_params &p = r.p;
   BitWriter b;
   b.put(0, 1);  // show_existing_frame
@@ -269,9 +275,10 @@ std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint
     b.put(0, 1);  // delta_lf_present
   }
   {  // loop_filter_params (§5.9.11): level 0 = deblocking off
-    const uint32_t lv = (uint32_t)deblock_level(r, !inter);
-    b.put(lv, 6); b.put(lv, 6);          // loop_filter_level[0..1]
-    if (lv) { b.put(lv, 6); b.put(lv, 6); }  // [2..3] (U, V)
+    const uint32_t lv = (uint32_t)deblock_level(r, !inter), ly = p.deblock == 2 ? (uint32_t)av1mi_lf_pool((int)lv, 7, 0) : lv;
+    if (lf_bit) *lf_bit = b.bits;
+    b.put(ly, 6); b.put(ly, 6);          // loop_filter_level[0..1]
+    if (ly) { b.put(lv, 6); b.put(lv, 6); }  // [2..3] (U, V)
   }
   b.put(0, 3);  // loop_filter_sharpness
   b.put(0, 1);  // loop_filter_delta_enabled
@@ -480,6 +487,9 @@ struct Workspace {
   unsigned long long *d_cdef_err = nullptr;  // CDEF strength search: per [frame][superblock] the 24 candidates' squared errors
   int8_t *d_cdef_idx = nullptr;              // ... per [frame][superblock] the index into the frame's set (-1: not coded)
   uint8_t *d_cdef_sel = nullptr;             // ... per frame the set: 8 slots of pair indices
+  unsigned long long *d_lf_err = nullptr;    // deblocking level search: per [frame][plane] the 16 candidates' squared errors, and behind
+  uint8_t *d_lf_sel = nullptr;               // them, in the same block, per frame the four levels; h_lf: where one copy lands both
+  uint8_t *h_lf = nullptr;
   uint8_t *h_out = nullptr;            // host staging (pinned), for when the caller's buffer cannot be page-locked
   // Page-locked host side of the small transfers.  The chunk constants - header blob, default CDFs, parameters - are the same for
   // every chunk of a job: h_hdr / h_cdf / h_params hold what d_hdr / d_cdf / d_params hold, and prepare_chunk uploads only what differs.
@@ -519,6 +529,10 @@ struct av1mi_ctx {
   int cap_scale = 1;   // per-tile symbol-stream / bitstream-slot capacity multiplier (1, 2, 4, ... 64)
   Workspace ws;
   Av1miDevParams P = {};
+  // the last encoded chunk's deblocking levels (4 per frame) and level-search errors (48 per frame; zeros without the search):
+  // av1mi_lf_search_result.  Empty: no chunk, or the last one failed
+  std::vector<uint8_t> lf_levels;
+  std::vector<unsigned long long> lf_errs;
 };
 
 namespace {
@@ -616,10 +630,15 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     HIPCHK(c, ws_alloc(w, w.d_aq_act, nf * nsb * sizeof(uint16_t)));
     HIPCHK(c, ws_alloc(w, w.d_aq_map, nf * nsb));
   }
-  if (p.cdef_search && !w.d_cdef_err) {
+  if (p.cdef_search && (!w.d_cdef_err || !w.d_cdef_idx || !w.d_cdef_sel)) {
     HIPCHK(c, ws_alloc(w, w.d_cdef_err, nf * nsb * 24 * sizeof(unsigned long long)));
     HIPCHK(c, ws_alloc(w, w.d_cdef_idx, nf * nsb));
     HIPCHK(c, ws_alloc(w, w.d_cdef_sel, nf * 8));
+  }
+  if (p.deblock == 2 && (!w.d_lf_err || !w.h_lf)) {   // (both: the second allocation may have failed on an earlier chunk)
+    HIPCHK(c, ws_alloc(w, w.d_lf_err, nf * (3 * AV1MI_LF_CANDS * sizeof(unsigned long long) + 4)));
+    w.d_lf_sel = reinterpret_cast<uint8_t *>(w.d_lf_err + nf * 3 * AV1MI_LF_CANDS);
+    HIPCHK(c, ws_alloc(w, w.h_lf, nf * (3 * AV1MI_LF_CANDS * sizeof(unsigned long long) + 4), true));
   }
   if (p.enable_lr && !w.d_cd) {   // unit choices and sums for three planes (enable_lr 3 / 4), whichever value this chunk has: the
                                   // buffers stay with the geometry while enable_lr changes
@@ -657,7 +676,8 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
 // The kernels' parameters of a chunk of `n_frames` frames: `r` at the coded size, the per-tile capacities of multiplier `scale` and the
 // workspace buffers the kernels find through them.  The header sizes follow with the headers (prepare_chunk).
 Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const uint32_t *part, const Av1miQmEntry *qm, const uint8_t *aq_map,
-                          unsigned long long *cdef_err, int8_t *cdef_idx, uint8_t *cdef_sel, Av1miChunkRecord *record, const uint32_t *tile_symbols) {
+                          unsigned long long *cdef_err, int8_t *cdef_idx, uint8_t *cdef_sel, unsigned long long *lf_err, uint8_t *lf_sel,
+                          Av1miChunkRecord *record, const uint32_t *tile_symbols) {
   const av1mi_params &p = r.p;
   Av1miDevParams P;
   memset(&P, 0, sizeof(P));
@@ -687,6 +707,11 @@ Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const
   P.keyint = (int)p.keyint; P.me_range = (int)p.me_range; P.subpel = p.subpel ? 1 : 0; P.me_presearch = p.me_presearch ? 1 : 0;
   P.hdr_slot_bytes = 512;
   for (int i = 0; i < 4; i++) { P.lf_level[i] = deblock_level(r, true); P.lf_level_inter[i] = deblock_level(r, false); }
+  if (p.deblock == 2) {   // the level search: the header's placeholders (luma at least 1: every frame is deblocked)
+    P.lf_search = 1; P.lf_err = lf_err; P.lf_sel = lf_sel;
+    P.lf_search_g[0] = P.lf_level[0]; P.lf_search_g[1] = P.lf_level_inter[0];
+    for (int i = 0; i < 2; i++) { P.lf_level[i] = av1mi_lf_pool(P.lf_search_g[0], 7, 0); P.lf_level_inter[i] = av1mi_lf_pool(P.lf_search_g[1], 7, 0); }
+  }
   P.enable_lr = (int)p.enable_lr;
   P.lr_chroma = r.lr_chroma;
   P.chunk_record = record; P.tile_symbols = tile_symbols;
@@ -970,7 +995,7 @@ int av1mi_aq_qindex(av1mi_ctx *c, const av1mi_params *params, const void *frames
   HIPCHK(c, hipSetDevice(c->device));
   const int bps = r.p.bit_depth > 8 ? 2 : 1;
   const size_t in_bytes = caller_bytes(r, n_frames), coded_bytes = (size_t)n_frames * r.cw * r.ch * 3 / 2 * bps;
-  const Av1miDevParams P = dev_params(r, n_frames, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  const Av1miDevParams P = dev_params(r, n_frames, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   hipStream_t s = c->stream;
   void *d_in = nullptr, *d_coded = nullptr;
   uint16_t *d_act = nullptr;
@@ -998,6 +1023,14 @@ int av1mi_aq_qindex(av1mi_ctx *c, const av1mi_params *params, const void *frames
   return AV1MI_OK;
 }
 
+// The levels the context's last chunk was deblocked with and, with the level search, the candidates' errors: what download_chunk kept.
+int av1mi_lf_search_result(const av1mi_ctx *c, uint32_t n_frames, uint8_t *levels, uint64_t *err) {
+  if (!c || !levels || n_frames == 0 || c->lf_levels.size() != (size_t)n_frames * 4) return AV1MI_E_INVALID_ARG;
+  memcpy(levels, c->lf_levels.data(), c->lf_levels.size());
+  if (err) memcpy(err, c->lf_errs.data(), c->lf_errs.size() * sizeof(unsigned long long));
+  return AV1MI_OK;
+}
+
 static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
                              av1mi_buf *out, uint32_t *frame_sizes, void *recon, av1mi_report *report);
 
@@ -1019,8 +1052,11 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   // header blob: sequence header OBU, then one fixed-size slot per frame with that frame's header (key and inter
   // frames have different lengths; frames of one kind differ only in grain_seed)
   size_t str_key = 0, str_inter = 0;   // CDEF strength search: where cdef_select_kernel writes each frame's set
-  std::vector<uint8_t> seq = make_sequence_header(r), fh = make_frame_header(r, nullptr, 0, false, &str_key), fhi = make_frame_header(r, nullptr, 0, true, &str_inter);
+  size_t lf_key = 0, lf_inter = 0;     // deblocking level search: where deblock_decide_kernel writes each frame's levels
+  std::vector<uint8_t> seq = make_sequence_header(r), fh = make_frame_header(r, nullptr, 0, false, &str_key, &lf_key),
+                       fhi = make_frame_header(r, nullptr, 0, true, &str_inter, &lf_inter);
   P.cdef_str_bit[0] = (int)str_key; P.cdef_str_bit[1] = (int)str_inter;
+  P.lf_bit[0] = (int)lf_key; P.lf_bit[1] = (int)lf_inter;
   P.seq_hdr_bytes = (int)seq.size(); P.frame_hdr_bytes = (int)fh.size(); P.inter_hdr_bytes = (int)fhi.size();
   if (seq.size() > 256 || fh.size() > (size_t)P.hdr_slot_bytes || fhi.size() > (size_t)P.hdr_slot_bytes) { set_err(c, "internal: header larger than its slot"); return AV1MI_E_OVERFLOW; }
   std::vector<uint8_t> blob(seq.size() + (size_t)n_frames * P.hdr_slot_bytes, 0);
@@ -1033,13 +1069,14 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   }
   // Upload what the device does not hold already (consecutive chunks of a job: nothing), from page-locked memory - the copies are
   // asynchronous, and the previous chunk's have completed (download_chunk waits for the main stream).  With the strength search on,
-  // cdef_select_kernel writes the strengths into the frame headers on the device: the blob goes up every chunk.
+  // cdef_select_kernel writes the strengths into the frame headers on the device: the blob goes up every chunk.  Likewise with the
+  // deblocking level search (deblock_decide_kernel writes the levels).
   if (w.hdr_bytes != blob.size() || memcmp(w.h_hdr, blob.data(), blob.size())) {
     w.hdr_bytes = 0;
     memcpy(w.h_hdr, blob.data(), blob.size());
     HIPCHK(c, hipMemcpyAsync(w.d_hdr, w.h_hdr, blob.size(), hipMemcpyHostToDevice, s));
   }
-  w.hdr_bytes = P.cdef_search ? 0 : blob.size();
+  w.hdr_bytes = P.cdef_search || P.lf_search ? 0 : blob.size();
   if (w.cdf_qidx != r.qidx) {
     w.cdf_qidx = -1;
     const std::vector<uint16_t> cdf = make_cdf_blob(r.qidx);
@@ -1069,6 +1106,8 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   HIPCHK(c, hipMemsetAsync(w.d_record, 0, sizeof(Av1miChunkRecord), s));
   HIPCHK(c, hipMemsetAsync(w.d_sse, 0, (size_t)n_frames * 24, s));
   if (P.cdef_search) HIPCHK(c, hipMemsetAsync(w.d_cdef_err, 0, (size_t)n_frames * P.sb_rows * P.sb_cols * 24 * sizeof(unsigned long long), s));
+  // the level search's sums, once per attempt at the chunk (not a fill per frame on a P chain)
+  if (P.lf_search) HIPCHK(c, hipMemsetAsync(w.d_lf_err, 0, (size_t)n_frames * 3 * AV1MI_LF_CANDS * sizeof(unsigned long long), s));
   HIPCHK(c, hipEventRecord(c->ev[EV_START], s));
   // the caller's frames are used in place if they are on the device at the coded size; a padded chunk arrives in the stage
   if (!frames_on_device) HIPCHK(c, hipMemcpyAsync(r.padded ? w.d_stage : w.d_src, frames, caller_bytes(r, n_frames), hipMemcpyHostToDevice, s));
@@ -1116,14 +1155,16 @@ static int sse_beside_range_coder(av1mi_ctx *c, const void *src) {
 static int schedule_all_key(av1mi_ctx *c, const void *src, uint32_t n_frames) {
   const Av1miDevParams &P = c->P; Workspace &w = c->ws; hipStream_t s = c->stream, s2 = c->stream2;
   // Deblocking reads only the reconstruction and block info: beside symbolize on the second stream.  The strength search reads the
-  // deblocked frames and symbolize codes its cdef_idx: with the search on, deblocking and search run before entropy coding.
-  const hipStream_t deblock_s = P.cdef_search ? s : s2;
+  // deblocked frames and symbolize codes its cdef_idx: with the search on, deblocking and search run before entropy coding.  So they do
+  // with the deblocking level search, whose decision writes into the headers the main stream packs.
+  const hipStream_t deblock_s = P.cdef_search || P.lf_search ? s : s2;
   // CDEF's one launch over the chunk sums the squared error itself - a second pass over the frames, 0.19 ms at 1080p x 60, would end
   // after the range coder CDEF runs beside; a one-frame chunk's CDEF runs in strips without the sum
   const bool sse_in_cdef = n_frames > 1;
   const bool deblock = av1mi_frame_lf_levels(P, 0)[0] != 0;
   const int n = (int)n_frames;
   HIPCHK(c, av1mi_launch_recon(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, nullptr, nullptr, 0, n, s));
+  if (P.lf_search) HIPCHK(c, av1mi_launch_deblock_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, n, s));
   if (deblock && deblock_s == s) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, 0, n, s));
   if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, n, s));
   if (const int rc = entropy_code(c, 0, n_frames)) return rc;
@@ -1144,6 +1185,7 @@ static int schedule_all_key_lr(av1mi_ctx *c, const void *src, uint32_t n_frames)
   const Av1miDevParams &P = c->P; Workspace &w = c->ws; hipStream_t s = c->stream;
   const int n = (int)n_frames;
   HIPCHK(c, av1mi_launch_recon(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, nullptr, nullptr, 0, n, s));
+  if (P.lf_search) HIPCHK(c, av1mi_launch_deblock_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, n, s));
   if (av1mi_frame_lf_levels(P, 0)[0]) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, 0, n, s));
   if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, n, s));
   HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, w.d_cd, w.d_blk, nullptr, nullptr, 0, n, s));
@@ -1194,6 +1236,8 @@ static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
     const int fi = (int)f;
     if (av1mi_frame_is_inter(P, fi)) HIPCHK(c, hipStreamWaitEvent(s, c->me_ev[f], 0));
     HIPCHK(c, av1mi_launch_recon(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, w.d_fin, me_best, fi, 1, s));
+    // the frame's levels before its deblocking (its reconstruction does not depend on them; everything after sees the chosen levels)
+    if (P.lf_search) HIPCHK(c, av1mi_launch_deblock_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, fi, 1, s));
     if (av1mi_frame_lf_levels(P, fi)[0]) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, fi, 1, s));
     // the frame's strength set before its CDEF (the next frame's reference is the output of the chosen strengths)
     if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, fi, 1, s));
@@ -1271,6 +1315,11 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
   }
   const unsigned long long *sse = w.h_sse;
   if (e1 == hipSuccess) e1 = hipMemcpyAsync(w.h_sse, w.d_sse, (size_t)n_frames * 24, hipMemcpyDeviceToHost, s);
+  // the level search's tables and levels (av1mi_lf_search_result): one more small copy before the wait below.  The levels sit behind the
+  // whole workspace's tables, not behind this chunk's: two copies when the chunk is shorter
+  const size_t lf_err_bytes = (size_t)n_frames * 3 * AV1MI_LF_CANDS * sizeof(unsigned long long);
+  if (e1 == hipSuccess && P.lf_search) e1 = hipMemcpyAsync(w.h_lf, w.d_lf_err, lf_err_bytes, hipMemcpyDeviceToHost, s);
+  if (e1 == hipSuccess && P.lf_search) e1 = hipMemcpyAsync(w.h_lf + lf_err_bytes, w.d_lf_sel, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s);
   // the bitstream is on the host once EV_DOWNLOAD_DONE has passed: hand it over to the caller's buffer while the second stream finishes
   if (e1 == hipSuccess && e2 == hipSuccess && dst != host) {
     e1 = hipEventSynchronize(c->ev[EV_DOWNLOAD_DONE]);
@@ -1284,6 +1333,14 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
     return AV1MI_E_HIP;
   }
   out->data = host; out->size = total;
+  c->lf_levels.resize((size_t)n_frames * 4);
+  c->lf_errs.assign((size_t)n_frames * 3 * AV1MI_LF_CANDS, 0);
+  if (P.lf_search) {
+    memcpy(c->lf_errs.data(), w.h_lf, lf_err_bytes);
+    memcpy(c->lf_levels.data(), w.h_lf + lf_err_bytes, (size_t)n_frames * 4);
+  } else {
+    for (uint32_t f = 0; f < n_frames; f++) for (int i = 0; i < 4; i++) c->lf_levels[(size_t)f * 4 + i] = (uint8_t)av1mi_frame_lf_levels(P, (int)f)[i];
+  }
   if (frame_sizes) for (uint32_t f = 0; f < n_frames; f++) frame_sizes[f] = (uint32_t)(foff[f + 1] - foff[f]);
   if (report) {
     memset(report, 0, sizeof(*report));
@@ -1327,6 +1384,7 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
 static int run_chunk(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
                      av1mi_buf *out, uint32_t *frame_sizes, void *recon, av1mi_report *report) {
   out->data = nullptr; out->size = 0;
+  c->lf_levels.clear(); c->lf_errs.clear();
   Resolved r;
   int rc = resolve(params, &r);
   if (rc) { set_err(c, "invalid parameters"); return rc; }
@@ -1334,7 +1392,8 @@ static int run_chunk(av1mi_ctx *c, const av1mi_params *params, const void *frame
   rc = ensure_workspace(c, r, n_frames);
   if (rc) return rc;
   Workspace &w = c->ws;
-  c->P = dev_params(r, n_frames, c->cap_scale, w.d_part, w.d_qm, w.d_aq_map, w.d_cdef_err, w.d_cdef_idx, w.d_cdef_sel, w.d_record, w.d_sym);
+  c->P = dev_params(r, n_frames, c->cap_scale, w.d_part, w.d_qm, w.d_aq_map, w.d_cdef_err, w.d_cdef_idx, w.d_cdef_sel, w.d_lf_err, w.d_lf_sel,
+                     w.d_record, w.d_sym);
   const void *d_src = nullptr;
   rc = prepare_chunk(c, r, frames, n_frames, frames_on_device, &d_src);
   if (rc) return rc;

@@ -23,6 +23,8 @@ inline Av1miDevParams av1mi_frame_range(const Av1miDevParams &P, int frame0, int
   if (R.aq_map) R.aq_map += sb0;
   if (R.cdef_idx) R.cdef_idx += sb0;
   if (R.cdef_sel) R.cdef_sel += (size_t)frame0 * 8;
+  if (R.lf_err) R.lf_err += (size_t)frame0 * 48;
+  if (R.lf_sel) R.lf_sel += (size_t)frame0 * 4;
   return R;
 }
 // frame f of a chunk-wide array of frames at the coded size (8- or 16-bit samples)
@@ -79,8 +81,13 @@ hipError_t av1mi_launch_recon64_u16(const Av1miDevParams *P, const Av1miDevParam
                                     const void *fin, const unsigned long long *me_best, int frame0, int count, hipStream_t stream);
 hipError_t av1mi_launch_recon64_u8(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels, Av1miBlkInfo *blk,
                                    const void *fin, const unsigned long long *me_best, int frame0, int count, hipStream_t stream);
-// both passes over the frames of `rec`, in place, with the levels of frame0's kind (av1mi_frame_lf_levels)
+// both passes over the frames of `rec`, in place, with the levels of frame0's kind (av1mi_frame_lf_levels) or, with the level search
+// on, each frame's own (P->lf_sel: av1mi_launch_deblock_search on the same stream before)
 hipError_t av1mi_launch_deblock(const Av1miDevParams *P, void *rec, const Av1miBlkInfo *blk, int frame0, int count, hipStream_t stream);
+// the level search on the frames of `rec` before deblocking (P->lf_err zeroed by the caller), then the decision: the frames' levels into
+// P->lf_sel and into their headers
+hipError_t av1mi_launch_deblock_search(const Av1miDevParams *P, const void *rec, const void *src, const Av1miBlkInfo *blk, uint8_t *hdr_blob,
+                                       int frame0, int count, hipStream_t stream);
 // the strength search (P->cdef_err zeroed by the caller), then the selection; one-frame launches (the P-frame chain) in 8-row strips, as CDEF
 hipError_t av1mi_launch_cdef_search(const Av1miDevParams *P, const void *rec, const void *src, const Av1miBlkInfo *blk, uint8_t *hdr_blob,
                                     int frame0, int count, hipStream_t stream);

@@ -8,82 +8,20 @@
 // side, and reaches that far only when both neighbouring transforms are >= 16 wide), so one pass is one launch:
 // one thread per 4-sample edge segment of any plane.  HBM bound: each pass reads and writes the samples next to the
 // edges; algorithmic bytes <= 2 * 2 * N * b per frame (both passes, read + write).
+// The level is the quantiser's (deblock = 1) or, per frame and plane, the one deblock_search_kernel + deblock_decide_kernel below chose
+// by squared error against the source (deblock = 2); filter, edge predicate and limits are deblock_pieces.h's for all of them.
 #include <hip/hip_runtime.h>
 #include "av1mi_dev.h"
 #include "av1mi_launch.h"
+#include "deblock_pieces.h"
 
 namespace {
 
-__device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// one sample position across an edge: px[-k*step] = p(k-1), px[k*step] = q(k).  len: 4, 6 (chroma), 8 or 16 = filterLen
-template <typename PIX>
-__device__ __forceinline__ void filter_sample(PIX *px, long step, int plane, int lim, int blim, int thr, int len, int bd) {
-  const int one = 1 << (bd - 8);
-  int t[16];  // t[8 + i] = sample i (i < 0: p(-i-1), i >= 0: q(i)) for i in -8..7
-  const int reach = len == 16 ? 7 : (len == 8 ? 4 : (len == 6 ? 3 : 2));
-#pragma unroll
-  for (int i = -7; i < 7; i++) t[8 + i] = (i >= -reach && i < reach) ? (int)px[i * step] : 0;
-#define P(k) t[7 - (k)]
-#define Q(k) t[8 + (k)]
-  const int p0 = P(0), p1 = P(1), q0 = Q(0), q1 = Q(1);
-  const bool hev = iabs(p1 - p0) > thr || iabs(q1 - q0) > thr;
-  bool mask = iabs(p1 - p0) > lim || iabs(q1 - q0) > lim || iabs(p0 - q0) * 2 + iabs(p1 - q1) / 2 > blim;
-  if (len >= 6) mask = mask || iabs(P(2) - p1) > lim || iabs(Q(2) - q1) > lim;
-  if (len >= 8) mask = mask || iabs(P(3) - P(2)) > lim || iabs(Q(3) - Q(2)) > lim;
-  if (mask) return;
-  bool flat = false, flat2 = false;
-  if (len >= 6) {
-    flat = iabs(p1 - p0) <= one && iabs(q1 - q0) <= one && iabs(P(2) - p0) <= one && iabs(Q(2) - q0) <= one;
-    if (len >= 8) flat = flat && iabs(P(3) - p0) <= one && iabs(Q(3) - q0) <= one;
-  }
-  if (len >= 16) flat2 = iabs(P(4) - p0) <= one && iabs(Q(4) - q0) <= one && iabs(P(5) - p0) <= one && iabs(Q(5) - q0) <= one &&
-                         iabs(P(6) - p0) <= one && iabs(Q(6) - q0) <= one;
-  if (len == 4 || !flat) {
-    // narrow filter §7.14.6.3
-    const int lo = -(1 << (bd - 1)), hi = (1 << (bd - 1)) - 1, half = 0x80 << (bd - 8);
-    const int ps1 = p1 - half, ps0 = p0 - half, qs0 = q0 - half, qs1 = q1 - half;
-    int f = hev ? clampi(ps1 - qs1, lo, hi) : 0;
-    f = clampi(f + 3 * (qs0 - ps0), lo, hi);
-    const int f1 = clampi(f + 4, lo, hi) >> 3, f2 = clampi(f + 3, lo, hi) >> 3;
-    px[0] = (PIX)(clampi(qs0 - f1, lo, hi) + half);
-    px[-step] = (PIX)(clampi(ps0 + f2, lo, hi) + half);
-    if (!hev) {
-      const int g = (f1 + 1) >> 1;
-      px[step] = (PIX)(clampi(qs1 - g, lo, hi) + half);
-      px[-2 * step] = (PIX)(clampi(ps1 + g, lo, hi) + half);
-    }
-  } else {
-    // wide filter §7.14.6.4: 2n + 1 taps (n = 6 / 3 / 2) whose weights sum to 1 << log2size
-    const int log2size = (len == 16 && flat2) ? 4 : 3;
-    const int n = log2size == 4 ? 6 : (plane == 0 ? 3 : 2), n2 = (log2size == 3 && plane == 0) ? 0 : 1;
-    int out[12];
-#pragma unroll
-    for (int i = -6; i < 6; i++) {
-      int s = 0;
-      if (i >= -n && i < n) {
-#pragma unroll
-        for (int j = -6; j <= 6; j++) {
-          if (j < -n || j > n) continue;
-          const int p = clampi(i + j, -(n + 1), n);
-          s += t[8 + p] * (iabs(j) <= n2 ? 2 : 1);
-        }
-        s = (s + (1 << (log2size - 1))) >> log2size;
-      }
-      out[i + 6] = s;
-    }
-#pragma unroll
-    for (int i = -6; i < 6; i++)
-      if (i >= -n && i < n) px[i * step] = (PIX)out[i + 6];
-  }
-#undef P
-#undef Q
-}
-
 // PASS 0: vertical edges, 1: horizontal edges.  grid.x covers the 4x4 positions of all three planes, grid.y = frame.
+// lf_sel: null - the levels of the parameter block; else the level search's four levels per frame of the launch
 template <typename PIX, int PASS>
-__global__ void __launch_bounds__(256) deblock_kernel(Av1miDevParams P, PIX *__restrict__ rec, const Av1miBlkInfo *__restrict__ blk) {
+__global__ void __launch_bounds__(256) deblock_kernel(Av1miDevParams P, PIX *__restrict__ rec, const Av1miBlkInfo *__restrict__ blk,
+                                                     const uint8_t *__restrict__ lf_sel) {
   const int f = blockIdx.y;
   const long n_luma = (long)P.mi_rows * P.mi_cols, n_chroma = n_luma >> 2;
   const long id = (long)blockIdx.x * 256 + threadIdx.x;
@@ -93,31 +31,129 @@ __global__ void __launch_bounds__(256) deblock_kernel(Av1miDevParams P, PIX *__r
   const int ss = plane > 0;
   const int pcols = P.mi_cols >> ss;
   const int r4 = (int)(local / pcols), c4 = (int)(local % pcols);   // 4x4 position in the plane
-  const int row = r4 << ss, col = c4 << ss;                         // the same in luma 4x4 units
-  const int lvl = plane == 0 ? P.lf_level[PASS] : P.lf_level[plane + 1];
+  const int li = plane == 0 ? PASS : plane + 1;
+  const int lvl = lf_sel ? (int)lf_sel[f * 4 + li] : P.lf_level[li];
   if (!lvl) return;
-  if (col * 4 >= P.true_w || row * 4 >= P.true_h) return;           // onScreen (§7.14.2)
-  if (PASS == 0 ? c4 == 0 : r4 == 0) return;
   const Av1miBlkInfo *info = blk + (size_t)f * P.b8_rows * P.b8_cols;
-  const int prow = row - (PASS ? 1 << ss : 0), pcol = col - (PASS ? 0 : 1 << ss);
-  const int bsl = info[(size_t)(row >> 1) * P.b8_cols + (col >> 1)].bsl, pbsl = info[(size_t)(prow >> 1) * P.b8_cols + (pcol >> 1)].bsl;
-  int txw = (1 << bsl) >> ss, ptxw = (1 << pbsl) >> ss;
-  txw = txw < 4 ? 4 : txw; ptxw = ptxw < 4 ? 4 : ptxw;
+  const int len = av1mi_lf_edge_len(plane, PASS, r4, c4, info, P.b8_cols, P.true_w, P.true_h);
+  if (!len) return;
+  int lim, blim, thr;
+  av1mi_lf_limits(lvl, P.lf_sharpness, P.bit_depth, &lim, &blim, &thr);
   const int x = c4 * 4, y = r4 * 4;
-  if (((PASS == 0 ? x : y) & (txw - 1)) != 0) return;                // not a transform (= block) edge
-  const int base = txw < ptxw ? txw : ptxw;
-  const int len = plane == 0 ? (base >= 16 ? 16 : base) : (base >= 8 ? 6 : 4);
-  const int sharp = P.lf_sharpness;
-  const int shift = sharp > 4 ? 2 : (sharp > 0 ? 1 : 0);
-  const int limit = sharp > 0 ? clampi(lvl >> shift, 1, 9 - sharp) : ((lvl >> shift) > 1 ? (lvl >> shift) : 1);
-  const int sh = P.bit_depth - 8;
-  const int lim = limit << sh, blim = (2 * (lvl + 2) + limit) << sh, thr = (lvl >> 4) << sh;
   const long stride = plane ? P.stride_c : P.stride_y;
   PIX *pl = rec + (size_t)f * P.frame_samples + (plane == 0 ? 0 : (plane == 1 ? P.plane_off_u : P.plane_off_v));
 #pragma unroll
   for (int i = 0; i < 4; i++) {
     PIX *px = pl + (size_t)(y + (PASS ? 0 : i)) * stride + x + (PASS ? i : 0);
-    filter_sample<PIX>(px, PASS ? stride : 1, plane, lim, blim, thr, len, P.bit_depth);
+    av1mi_lf_filter_sample<PIX, long>(px, PASS ? stride : 1, plane, lim, blim, thr, len, P.bit_depth);
+  }
+}
+
+// ---- the level search (av1mi_params.deblock = 2).  One workgroup per (frame, plane, 64x64 superblock):
+// blockIdx.x < sb_rows * sb_cols - luma, then U, then V; blockIdx.y - frame frame0 + y of the chunk.  The superblock's tile of the
+// frame's reconstruction before deblocking (deblock_pieces.h: interior + halo, positions outside the plane clamped) goes into LDS once;
+// per candidate level the working copy is restored, filtered - vertical pass on every tile row, then horizontal pass on the interior's
+// columns, the lines of a pass spread over the lanes - and the interior's squared error against the source, within the signalled size,
+// is summed: 32 bits per lane (16 samples of at most 1023^2), 64 across the workgroup, one atomicAdd per candidate into
+// lf_err[frame][plane][candidate].  Levels, limits and loop bounds are wave-uniform.  Neighbouring candidates that clamp to the same
+// level are filtered once.
+template <typename PIX>
+__global__ void __launch_bounds__(256) deblock_search_kernel(Av1miDevParams P, int frame0, const PIX *__restrict__ rec, const PIX *__restrict__ src,
+                                                            const Av1miBlkInfo *__restrict__ blk) {
+  __shared__ __attribute__((aligned(16))) uint16_t pristine[AV1MI_LF_TILE_SAMPLES], work[AV1MI_LF_TILE_SAMPLES];
+  __shared__ uint8_t seg[2][AV1MI_LF_EDGES][AV1MI_LF_SEGS];
+  __shared__ unsigned long long wave_sum[4];
+  const int t = threadIdx.x, f = frame0 + (int)blockIdx.y;
+  const int nsb = P.sb_rows * P.sb_cols;
+  const int plane = (int)blockIdx.x / nsb, sb = (int)blockIdx.x % nsb;
+  const Av1miLfTile T = av1mi_lf_tile(plane, sb / P.sb_cols, sb % P.sb_cols, P.width, P.height);
+  const long stride = plane ? P.stride_c : P.stride_y;
+  const size_t plane_off = (size_t)f * P.frame_samples + (plane == 0 ? 0 : (plane == 1 ? P.plane_off_u : P.plane_off_v));
+  const PIX *rp = rec + plane_off, *sp = src + plane_off;
+  const Av1miBlkInfo *info = blk + (size_t)f * P.b8_rows * P.b8_cols;
+  for (int i = t; i < T.T * T.T; i += 256) {
+    int py, px;
+    av1mi_lf_tile_source(T, i / T.T, i % T.T, &py, &px);
+    pristine[(i / T.T) * AV1MI_LF_PITCH + i % T.T] = (uint16_t)rp[(size_t)py * stride + px];
+  }
+  for (int i = t; i < 2 * AV1MI_LF_EDGES * AV1MI_LF_SEGS; i += 256) {
+    const int pass = i / (AV1MI_LF_EDGES * AV1MI_LF_SEGS), e = i / AV1MI_LF_SEGS % AV1MI_LF_EDGES, k = i % AV1MI_LF_SEGS;
+    seg[pass][e][k] = k * 4 < (pass ? T.S : T.T) ? (uint8_t)av1mi_lf_tile_seg_len(T, pass, e, k, info, P.b8_cols, P.true_w, P.true_h) : 0;
+  }
+  // this lane's interior samples: sample i = k * 256 + t, row i / S; the source where the sample counts, -1 where it lies beyond the signalled size
+  const int per_lane = T.S * T.S / 256;   // 16 / 4
+  const int tw = plane ? (P.true_w + 1) >> 1 : P.true_w, th = plane ? (P.true_h + 1) >> 1 : P.true_h;
+  int want[16];
+#pragma unroll
+  for (int k = 0; k < 16; k++) {
+    if (k >= per_lane) break;   // (wave-uniform: a chroma item has 4 samples per lane)
+    const int i = k * 256 + t, iy = i / T.S, ix = i % T.S;
+    want[k] = (T.x0 + ix < tw && T.y0 + iy < th) ? (int)sp[(size_t)(T.y0 + iy) * stride + T.x0 + ix] : -1;
+  }
+  const int g = P.lf_search_g[av1mi_frame_is_inter(P, f)];
+  unsigned long long *err = P.lf_err + ((size_t)f * 3 + plane) * AV1MI_LF_CANDS;
+  unsigned long long total = 0;   // (thread 0) the last filtered candidate's sum
+  int last = -1;
+  const int n0 = av1mi_lf_tile_lines(T, 0), n1 = av1mi_lf_tile_lines(T, 1);
+  for (int c = 0; c < AV1MI_LF_CANDS; c++) {
+    const int lvl = av1mi_lf_pool(g, c, plane > 0);
+    if (lvl != last) {
+      last = lvl;
+      __syncthreads();   // the tile and the tables are written / the error pass before has read the working copy
+      // whole rows, 32 bits at a time: the two pad columns behind each row come along, never written and never read
+      for (int i = t; i < T.T * AV1MI_LF_PITCH / 2; i += 256) ((uint32_t *)work)[i] = ((const uint32_t *)pristine)[i];
+      __syncthreads();
+      if (lvl) {
+        int lim, blim, thr;
+        av1mi_lf_limits(lvl, P.lf_sharpness, P.bit_depth, &lim, &blim, &thr);
+        for (int L = t; L < n0; L += 256) {
+          int e, k;
+          const int off = av1mi_lf_tile_line(T, 0, L, &e, &k), len = seg[0][e][k];
+          if (len) av1mi_lf_filter_sample<uint16_t, int>(work + off, 1, plane, lim, blim, thr, len, P.bit_depth);
+        }
+        __syncthreads();
+        for (int L = t; L < n1; L += 256) {
+          int e, k;
+          const int off = av1mi_lf_tile_line(T, 1, L, &e, &k), len = seg[1][e][k];
+          if (len) av1mi_lf_filter_sample<uint16_t, int>(work + off, AV1MI_LF_PITCH, plane, lim, blim, thr, len, P.bit_depth);
+        }
+        __syncthreads();
+      }
+      uint32_t acc = 0;
+#pragma unroll
+      for (int k = 0; k < 16; k++) {
+        if (k >= per_lane) break;
+        const int i = k * 256 + t, iy = i / T.S, ix = i % T.S;
+        if (want[k] >= 0) { const int d = (int)work[(T.H + iy) * AV1MI_LF_PITCH + T.H + ix] - want[k]; acc += (uint32_t)(d * d); }
+      }
+      unsigned long long v = acc;
+      for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+      if ((t & 63) == 0) wave_sum[t >> 6] = v;
+      __syncthreads();
+      if (t == 0) total = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+    }
+    if (t == 0 && total) atomicAdd(err + c, total);
+  }
+}
+
+// The frame's levels from its error table (one workgroup per frame of the launch): per plane the first minimum, into lf_sel[frame][4] -
+// luma's level for both of its passes - and into the 24 bits of loop_filter_level[0..3] in the frame's header slot, where the host wrote
+// placeholders (lf_bit[key / inter]).
+__global__ void __launch_bounds__(64) deblock_decide_kernel(Av1miDevParams P, int frame0, uint8_t *__restrict__ hdr_blob) {
+  __shared__ int lv[3];
+  const int f = frame0 + (int)blockIdx.x, t = threadIdx.x;
+  const int inter = av1mi_frame_is_inter(P, f);
+  if (t < 3) lv[t] = av1mi_lf_pool(P.lf_search_g[inter], av1mi_lf_first_min(P.lf_err + ((size_t)f * 3 + t) * AV1MI_LF_CANDS), t > 0);
+  __syncthreads();
+  if (t < 4) P.lf_sel[f * 4 + t] = (uint8_t)lv[t < 2 ? 0 : t - 1];
+  if (t == 0) {
+    uint8_t *h = hdr_blob + P.seq_hdr_bytes + (size_t)f * P.hdr_slot_bytes;
+    int bit = P.lf_bit[inter];
+    const uint32_t v = ((uint32_t)lv[0] << 18) | ((uint32_t)lv[0] << 12) | ((uint32_t)lv[1] << 6) | (uint32_t)lv[2];
+    for (int k = 23; k >= 0; k--, bit++) {
+      const uint8_t m = (uint8_t)(0x80 >> (bit & 7));
+      h[bit >> 3] = ((v >> k) & 1) ? (uint8_t)(h[bit >> 3] | m) : (uint8_t)(h[bit >> 3] & ~m);
+    }
   }
 }
 
@@ -129,12 +165,23 @@ extern "C" hipError_t av1mi_launch_deblock(const Av1miDevParams *P, void *rec, c
   rec = av1mi_frame_at(R, rec, frame0); blk += (size_t)frame0 * R.b8_rows * R.b8_cols;
   const long n = (long)R.mi_rows * R.mi_cols * 3 / 2;
   dim3 grid((unsigned)((n + 255) / 256), count);
+  const uint8_t *sel = R.lf_search ? R.lf_sel : nullptr;
   if (R.bit_depth == 8) {
-    hipLaunchKernelGGL((deblock_kernel<uint8_t, 0>), grid, dim3(256), 0, stream, R, (uint8_t *)rec, blk);
-    hipLaunchKernelGGL((deblock_kernel<uint8_t, 1>), grid, dim3(256), 0, stream, R, (uint8_t *)rec, blk);
+    hipLaunchKernelGGL((deblock_kernel<uint8_t, 0>), grid, dim3(256), 0, stream, R, (uint8_t *)rec, blk, sel);
+    hipLaunchKernelGGL((deblock_kernel<uint8_t, 1>), grid, dim3(256), 0, stream, R, (uint8_t *)rec, blk, sel);
   } else {
-    hipLaunchKernelGGL((deblock_kernel<uint16_t, 0>), grid, dim3(256), 0, stream, R, (uint16_t *)rec, blk);
-    hipLaunchKernelGGL((deblock_kernel<uint16_t, 1>), grid, dim3(256), 0, stream, R, (uint16_t *)rec, blk);
+    hipLaunchKernelGGL((deblock_kernel<uint16_t, 0>), grid, dim3(256), 0, stream, R, (uint16_t *)rec, blk, sel);
+    hipLaunchKernelGGL((deblock_kernel<uint16_t, 1>), grid, dim3(256), 0, stream, R, (uint16_t *)rec, blk, sel);
   }
+  return hipGetLastError();
+}
+
+extern "C" hipError_t av1mi_launch_deblock_search(const Av1miDevParams *P, const void *rec, const void *src, const Av1miBlkInfo *blk, uint8_t *hdr_blob,
+                                                  int frame0, int count, hipStream_t stream) {
+  if (!P->lf_search || !P->lf_err || !P->lf_sel) return hipErrorInvalidValue;
+  dim3 grid((unsigned)(3 * P->sb_rows * P->sb_cols), count);
+  if (P->bit_depth == 8) hipLaunchKernelGGL((deblock_search_kernel<uint8_t>), grid, dim3(256), 0, stream, *P, frame0, (const uint8_t *)rec, (const uint8_t *)src, blk);
+  else hipLaunchKernelGGL((deblock_search_kernel<uint16_t>), grid, dim3(256), 0, stream, *P, frame0, (const uint16_t *)rec, (const uint16_t *)src, blk);
+  hipLaunchKernelGGL(deblock_decide_kernel, dim3(count), dim3(64), 0, stream, *P, frame0, hdr_blob);
   return hipGetLastError();
 }

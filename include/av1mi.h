@@ -82,7 +82,13 @@ typedef struct {
   uint32_t tile_sb;         /* tile size in 64x64 superblocks, both ways: 0 = automatic (1; 2 when the frame has more than 64
                                superblock rows or columns, e.g. 8K - AV1 allows at most 64 x 64 tiles), or force 1 / 2 */
   uint32_t deblock;         /* 1 = deblocking filter on (default 0: `loop_filter_level` = 0); the level follows the quantiser:
-                               (ac_q * 20723 + 1015158) >> 18 at 8-bit scale, 4 less on key frames, all four filters alike */
+                               g = (ac_q * 20723 + 1015158) >> 18 at 8-bit scale, 4 less on key frames, all four filters alike.
+                               2 = the level is searched on the GPU per frame and per plane: 16
+                               candidates g + {-12, -8, -6, -4, -3, -2, -1, 0, 1, 2, 3, 4, 6, 8, 12, 16} clamped to 1..63 (luma)
+                               / 0..63 (U, V); each plane takes the first candidate with the least squared error of the deblocked
+                               plane against the source, luma one level for both edge directions.  Sharpness stays 0, no
+                               loop-filter deltas.  av1mi_lf_search_result reports the levels.  Values above 2 are refused
+                               with AV1MI_E_INVALID_ARG (before the search existed every nonzero value meant 1) */
   uint32_t enable_qm;       /* "--enable-qm 1" (av1an.rs:14): quantiser matrices (using_qmatrix).  The level of all three planes
                                follows the quantiser as in SVT-AV1/libaom: qm_min + base_q_idx * (qm_max + 1 - qm_min) / 256
                                (0 = steepest matrix ... 14; 15 = flat).  Default 0 */
@@ -197,6 +203,14 @@ int av1mi_scene_cuts(av1mi_ctx *ctx, const av1mi_params *params, const void *fra
  * av1mi_scene_cuts (tight planar frames, host or 16-byte aligned device memory). */
 int av1mi_aq_qindex(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames,
                     int frames_on_device, uint8_t *qindex);
+
+/* ---- deblocking levels of the last chunk ---------------------------------------------------
+ * loop_filter_level[0..3] (luma vertical edges, luma horizontal, U, V) every frame of the context's last successfully encoded
+ * chunk was deblocked with: levels[4 * f + i], whatever `deblock` was (all 0 without the filter).  err (optional): with
+ * deblock = 2 the level search's table, err[(f * 3 + plane) * 16 + i] = squared error of the plane deblocked at candidate i
+ * against the source over the signalled size; zeros without the search.  The values arrive with the chunk's other small
+ * results: the call only copies them.  AV1MI_E_INVALID_ARG if n_frames is not the last chunk's frame count. */
+int av1mi_lf_search_result(const av1mi_ctx *ctx, uint32_t n_frames, uint8_t *levels, uint64_t *err);
 
 /* ---- the drop-in for `run_av1an` ---------------------------------------------------------
  * Replaces  pub fn run_av1an(params: &Av1anEncodeParams) -> Result<(), EncodeError>

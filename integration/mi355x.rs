@@ -17,7 +17,10 @@ pub struct Av1miParams {            // include/av1mi.h: av1mi_params
     /// Loop restoration: 0 = off, 1 = Wiener on luma, 2 = off / Wiener / self-guided per luma unit; 3 / 4 = 1 / 2 on all three
     /// planes (a library without chroma restoration refuses 3 and 4 with AV1MI_E_INVALID_ARG).
     pub enable_lr: u32,
-    pub tile_sb: u32, pub deblock: u32,
+    pub tile_sb: u32,
+    /// Deblocking: 0 = off, 1 = one level from the quantiser for all four filters, 2 = the level searched per frame and per plane on
+    /// the GPU (a library without the search treats 2 as 1; this one refuses values above 2 with AV1MI_E_INVALID_ARG).
+    pub deblock: u32,
     pub enable_qm: u32, pub qm_min: u32, pub qm_max: u32, pub subpel: u32,
     pub color_range: u32,           // 0 = studio (default; a Y4M XCOLORRANGE tag wins), 1 = full
     pub intra_angle_delta: u32,     // 1 = directional intra winners refined over the angle deltas -3..+3

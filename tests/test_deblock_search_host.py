@@ -1,0 +1,246 @@
+"""CPU tests of the deblocking level search (include/av1mi.h: av1mi_params.deblock = 2, av1mi_lf_search_result):
+the shared pieces (av1-base_amd/csrc/deblock_pieces.h) compiled for the host against oracle/av1o_deblock.c, the search's superblock
+tile with its halo against the whole-frame result, the candidate pool and first-minimum rule against tests/deblock_ref.py, and the
+headers, parameter checks and ABI."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import deblock_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "host", "deblock_pieces_host.cpp")
+U16P = C.POINTER(C.c_uint16)
+
+
+@pytest.fixture(scope="module")
+def av1mi():
+    lib = os.path.join(ROOT, "av1-base_amd", "libav1mi.so")
+    if not os.path.exists(lib):
+        import importlib.util
+        spec = importlib.util.spec_from_file_location("av1mi_build", os.path.join(ROOT, "av1-base_amd", "build.py"))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        mod.build()
+    import av1mi as m
+    return m
+
+
+@pytest.fixture(scope="module")
+def cxx():
+    c = next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++") or "") if c and os.path.exists(c)), None)
+    if not c:
+        pytest.skip("no clang++")
+    return c
+
+
+@pytest.fixture(scope="module")
+def pieces(cxx, tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("lf") / "liblfpieces.so")
+    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", SRC, "-o", so])
+    lib = C.CDLL(so)
+    lib.lf_frame.argtypes = [U16P, U16P, U16P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+    lib.lf_frame.restype = None
+    lib.lf_tiles_against_frame.argtypes = [U16P, U16P, U16P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.lf_tiles_against_frame.restype = C.c_long
+    lib.lf_pool.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.lf_first_min.argtypes = [C.POINTER(C.c_uint64)]
+    return lib
+
+
+# ---------------------------------------------------------------- frames and partitions
+def partition(rng, w, h, min_bsl, max_bsl):
+    """log2 block size per 8x8 unit of a random aligned quad-tree, blocks of 2^min_bsl .. 2^max_bsl samples (a block whose half
+    point is outside the frame splits, as the syntax forces)"""
+    out = np.full((h // 8, w // 8), 3, dtype=np.uint8)
+
+    def node(x, y, bsl):
+        n = 1 << bsl
+        if x >= w or y >= h:
+            return
+        must = bsl > max_bsl or x + n // 2 >= w or y + n // 2 >= h
+        if bsl > 3 and (must or (bsl > min_bsl and rng.integers(2))):
+            for q in range(4):
+                node(x + (q & 1) * n // 2, y + (q >> 1) * n // 2, bsl - 1)
+            return
+        out[y // 8:(y + n) // 8, x // 8:(x + n) // 8] = bsl
+    for y in range(0, h, 64):
+        for x in range(0, w, 64):
+            node(x, y, 6)
+    return out
+
+
+def content(rng, w, h, bd):
+    """noise of a few levels on a blocky base: narrow and wide filters both fire"""
+    amp = 6 << (bd - 8)
+    out = []
+    for pw, ph in ((w, h), (w // 2, h // 2), (w // 2, h // 2)):
+        base = (1 << (bd - 1)) + np.kron(rng.integers(-amp, amp + 1, ((ph + 7) // 8, (pw + 7) // 8)), np.ones((8, 8), dtype=np.int64))[:ph, :pw] // 2
+        out.append(np.ascontiguousarray(np.clip(base + rng.integers(-amp // 2, amp // 2 + 1, (ph, pw)), 0, (1 << bd) - 1).astype(np.uint16)))
+    return out
+
+
+# signalled size, coded size
+SIZES = [((8, 8), (8, 8)), ((72, 56), (72, 56)), ((200, 136), (200, 136)), ((202, 122), (208, 128))]
+RANGES = [(3, 6), (6, 6), (3, 3), (4, 5)]   # mixed sizes; all 64x64 (16-wide filters across superblock edges); all 8x8; 16 and 32
+LEVELS = [(24, 24, 24, 24), (9, 40, 0, 17), (63, 1, 5, 0), (17, 17, 63, 40)]
+
+
+def cases():
+    for (tw, th), (w, h) in SIZES:
+        for bd in (8, 10):
+            for ri, (lo, hi) in enumerate(RANGES):
+                yield tw, th, w, h, bd, lo, hi, LEVELS[(ri + (bd == 10)) % len(LEVELS)]
+
+
+def oracle_deblock(oracle, planes, w, h, tw, th, bd, bsl8, levels):
+    L = oracle.lib()
+    L.av1o_deblock_frame.argtypes = [C.POINTER(oracle.Config), C.POINTER(oracle.Frame), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.POINTER(C.c_int), C.c_int]
+    L.av1o_deblock_frame.restype = None
+    cfg = oracle.default_config(w, h, bd, true_width=tw, true_height=th)
+    fp = oracle._planes_to_frame(planes)
+    mi = np.ascontiguousarray(np.kron(bsl8, np.ones((2, 2), dtype=np.uint8)))
+    zeros = np.zeros_like(mi)
+    L.av1o_deblock_frame(C.byref(cfg), fp, mi.ctypes.data, zeros.ctypes.data, zeros.ctypes.data, w // 4, (C.c_int * 4)(*levels), 0)
+    out = oracle._frame_to_planes(fp)
+    L.av1o_frame_free(fp)
+    return out
+
+
+@pytest.mark.parametrize("tw,th,w,h,bd,lo,hi,levels", list(cases()))
+def test_pieces_equal_the_oracle_and_tiles_equal_the_frame(pieces, oracle, tw, th, w, h, bd, lo, hi, levels):
+    """tests 1 and 2: the whole-frame loop over the pieces is av1o_deblock_frame; every superblock's tile, filtered with its halo alone,
+    is the whole-frame result on its interior"""
+    rng = np.random.default_rng(w * 131 + h * 7 + bd + lo * 3 + hi)
+    bsl8 = np.ascontiguousarray(partition(rng, w, h, lo, hi))
+    if (lo, hi) == (3, 6) and w >= 200:
+        assert len(set(bsl8.ravel())) >= 3   # the partition mixes sizes
+    planes = content(rng, w, h, bd)
+    want = oracle_deblock(oracle, planes, w, h, tw, th, bd, bsl8, levels)
+    got = [p.copy() for p in planes]
+    pieces.lf_frame(*(p.ctypes.data_as(U16P) for p in got), w, h, tw, th, bd, bsl8.ctypes.data, (C.c_int * 4)(*levels))
+    moved = 0
+    for pl in range(3):
+        assert np.array_equal(got[pl], want[pl]), "plane %d" % pl
+        moved += int((want[pl] != planes[pl]).sum())
+    if w > 8:
+        assert moved > 0   # (8x8: no edge is filtered)
+    else:
+        assert moved == 0
+    ptrs = [p.ctypes.data_as(U16P) for p in planes]
+    for lvl in sorted(set(levels) | {24}):
+        assert pieces.lf_tiles_against_frame(*ptrs, w, h, tw, th, bd, bsl8.ctypes.data, lvl) == 0, "level %d" % lvl
+
+
+def _build_main(cxx, exe, extra):
+    return subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-DDEBLOCK_PIECES_MAIN"] + extra + [SRC, "-o", exe], capture_output=True, text=True)
+
+
+def test_standalone_program(cxx, tmp_path):
+    """test 2, the same source as a program with its own main: it builds and finds no mismatch"""
+    exe = str(tmp_path / "lf_main")
+    r = _build_main(cxx, exe, [])
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and " 0 mismatches" in out.stdout, out.stdout + out.stderr
+
+
+def test_standalone_program_under_sanitizers(cxx, tmp_path):
+    """... and under AddressSanitizer and UndefinedBehaviorSanitizer (host code only).  Skipped only where an empty program does not
+    build and run under the sanitizers - their runtimes are not installed; a failure of the project's source is a failure"""
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    probe_src, probe = str(tmp_path / "probe.cpp"), str(tmp_path / "probe")
+    open(probe_src, "w").write("int main() { return 0; }\n")
+    p = subprocess.run([cxx] + san + [probe_src, "-o", probe], capture_output=True, text=True)
+    if p.returncode or subprocess.run([probe], capture_output=True).returncode:
+        pytest.skip("the sanitizer runtimes are not installed")
+    exe = str(tmp_path / "lf_main_san")
+    r = _build_main(cxx, exe, san)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert " 0 mismatches" in out.stdout
+
+
+# ---------------------------------------------------------------- 3. pool and first minimum
+@pytest.mark.parametrize("g", [0, 1, 11, 15, 59, 63])
+def test_pool(pieces, g):
+    for chroma in (0, 1):
+        want = deblock_ref.pool(g, chroma)
+        assert [pieces.lf_pool(g, i, chroma) for i in range(16)] == want
+        assert min(want) >= (0 if chroma else 1) and max(want) <= 63 and want == sorted(want)
+    assert deblock_ref.pool(g, False)[7] == max(g, 1) and deblock_ref.pool(g, True)[7] == g   # the header's placeholders
+    if g == 0:
+        assert deblock_ref.pool(0, False)[:8] == [1] * 8 and deblock_ref.pool(0, True)[:8] == [0] * 8
+    if g == 63:
+        assert deblock_ref.pool(63, False)[7:] == [63] * 9
+
+
+def test_first_minimum(pieces):
+    rng = np.random.default_rng(3)
+    tables = [np.full(16, 7), np.zeros(16), np.arange(16)[::-1].copy(), np.array([5] * 8 + [4] * 8), np.array([9, 3, 3, 3] * 4),
+              np.array([2 ** 40 + 1] * 15 + [2 ** 40]), np.array([2 ** 63] * 16)]
+    tables += [rng.integers(0, 4, 16) for _ in range(50)] + [rng.integers(0, 2 ** 62, 16) for _ in range(50)]
+    for e in tables:
+        e = np.ascontiguousarray(e.astype(np.uint64))
+        assert pieces.lf_first_min(e.ctypes.data_as(C.POINTER(C.c_uint64))) == deblock_ref.first_min(e), e
+    assert deblock_ref.first_min([7] * 16) == 0 and deblock_ref.first_min([9, 3, 3, 3]) == 1
+
+
+# ---------------------------------------------------------------- 4. headers, parameters, ABI
+def _bits(data, n):
+    return [(data[i >> 3] >> (7 - (i & 7))) & 1 for i in range(n)]
+
+
+@pytest.mark.parametrize("cq", [30, 63])
+@pytest.mark.parametrize("kw", [{}, dict(enable_lr=2, cdef_search=3), dict(w=328, h=200, bd=8, film_grain=10)])
+def test_header_is_the_formulas_where_g_is_positive(av1mi, cq, kw):
+    kw = dict(kw)
+    args = (kw.pop("w", 1920), kw.pop("h", 1080), kw.pop("bd", 10))
+    assert av1mi.write_headers(av1mi.default_params(*args, cq_level=cq, deblock=2, **kw)) == \
+        av1mi.write_headers(av1mi.default_params(*args, cq_level=cq, deblock=1, **kw))
+
+
+@pytest.mark.parametrize("bd", [8, 10])
+def test_header_at_g_zero(av1mi, bd):
+    """CQ 1, key frame: the formula gives level 0 - two fields; the search's placeholder codes all four: 1, 1, 0, 0"""
+    seq1, fh1, n1 = av1mi.write_headers(av1mi.default_params(640, 360, bd, cq_level=1, deblock=1))
+    seq0, fh0, n0 = av1mi.write_headers(av1mi.default_params(640, 360, bd, cq_level=1, deblock=0))
+    seq2, fh2, n2 = av1mi.write_headers(av1mi.default_params(640, 360, bd, cq_level=1, deblock=2))
+    assert (seq1, fh1, n1) == (seq0, fh0, n0)   # g = 0: the formula's filter is off
+    assert seq2 == seq1 and n2 == n1 + 12
+    b1, b2 = _bits(fh1, n1), _bits(fh2, n2)
+    d = next(i for i in range(n1) if b1[i] != b2[i])   # the low bit of loop_filter_level[0]
+    at = d - 5
+    fields = [sum(b << (5 - i) for i, b in enumerate(b2[at + 6 * k:at + 6 * k + 6])) for k in range(4)]
+    assert fields == [1, 1, 0, 0]
+    assert b1[at:at + 12] == [0] * 12 and b2[:at] == b1[:at] and b2[at + 24:] == b1[at + 12:]
+
+
+def test_values_above_two_are_refused(av1mi):
+    for v in (3, 4, 255, 1 << 31):
+        with pytest.raises(av1mi.EncodeFailed) as e:
+            av1mi.write_headers(av1mi.default_params(640, 360, 8, deblock=v))
+        assert e.value.code == 1   # AV1MI_E_INVALID_ARG
+    for v in (0, 1, 2):
+        av1mi.write_headers(av1mi.default_params(640, 360, 8, deblock=v))
+
+
+def test_abi_unchanged_and_symbol_exported(av1mi):
+    assert C.sizeof(av1mi.Params) == 36 * 4 == 144 and av1mi.struct_sizes() == av1mi.mirror_sizes()
+    assert av1mi.ABI_VERSION == int(av1mi._lib.av1mi_abi_version()) == 8
+    assert "av1mi_lf_search_result" in av1mi.ABI_SYMBOLS
+    assert getattr(av1mi._lib, "av1mi_lf_search_result") is not None   # exported
+    hdr = open(os.path.join(ROOT, "include", "av1mi.h")).read()
+    assert re.search(r"\bint\s+av1mi_lf_search_result\s*\(", hdr)
+    assert "#define AV1MI_ABI_VERSION 8" in hdr
+    assert hasattr(av1mi.Context, "lf_search_result")
+    # without a chunk there is nothing to report
+    lv = (C.c_uint8 * 4)()
+    assert av1mi._lib.av1mi_lf_search_result(None, 1, lv, None) == 1
