@@ -115,6 +115,9 @@ struct Av1miDevParams {
   int lr_chroma;
   int lr_code_len_uv[4][3];
   unsigned long long lr_code_bits_uv[4][3];
+  // the self-guided fit (av1mi_params.enable_lr bit 8): null, or per [frame][plane 0..2][unit] the bit string
+  // { bits, length } of a self-guided unit, fixed candidates included (lr_fit_kernel.hip); unit choices are then 0 .. 22, 7 + t = set t
+  const uint32_t *lr_fit_code;
   // packing: null (no counts wanted), or the chunk's record and the [frame][tile] symbol-stream lengths frame_layout_kernel reduces into it
   Av1miChunkRecord *chunk_record;
   const uint32_t *tile_symbols;
@@ -179,6 +182,15 @@ AV1MI_HD inline int av1mi_frame_is_inter(const Av1miDevParams &P, int f) { retur
 AV1MI_HD inline int av1mi_lr_unit_rows(const Av1miDevParams &P) { return (P.true_h + 32) / 64 > 0 ? (P.true_h + 32) / 64 : 1; }
 AV1MI_HD inline int av1mi_lr_unit_cols(const Av1miDevParams &P) { return (P.true_w + 32) / 64 > 0 ? (P.true_w + 32) / 64 : 1; }
 AV1MI_HD inline int av1mi_lr_frame_units(const Av1miDevParams &P) { return (P.lr_chroma ? 3 : 1) * av1mi_lr_unit_rows(P) * av1mi_lr_unit_cols(P); }
+
+// the self-guided fit's buffers, all [frame][plane 0..2][unit] whichever planes are restored (lr_fit_kernel.hip)
+struct Av1miLrFit {
+  long long *sums;            // [16 sets][5]: H00, H01, H11, C0, C1 (lr_fit_rule.h)
+  unsigned long long *err;    // [23 candidates]: the exact SSE; ~0 for an absent candidate
+  int8_t *rec;                // [4]: choice, set, xqd0, xqd1
+  uint32_t *code;             // [2]: bits, length of a self-guided unit's syntax
+  uint32_t mask;              // the sets searched (never 0)
+};
 
 // ---- which symbolize variant owns a tile (entropy_kernel.hip: the kernels decide per tile, the launcher sizes its grids by it)
 // Under a content-driven partition (P.part_map, device memory: device code only): does the superblock keep one block size throughout -

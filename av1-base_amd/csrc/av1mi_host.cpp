@@ -26,6 +26,7 @@
 #include "av1_tables.h"
 #include "av1mi_dev.h"
 #include "av1mi_launch.h"
+#include "lr_fit_rule.h"
 #include "deblock_pieces.h"
 #include "aq_rule.h"
 
@@ -79,6 +80,7 @@ struct Resolved {
   int qm_level;                       // quantiser-matrix level of all planes (15 = flat); only meaningful with p.enable_qm
   int lr_chroma;                      // enable_lr 3 / 4: U and V restored as well (p.enable_lr then holds the type: 1 / 2)
   int aq;                             // strength of the adaptive quantisation, 0 = off (p.cq_level then holds the CQ level alone)
+  uint32_t lr_fit_mask;               // enable_lr bit 8: the parameter sets the self-guided fit searches, 0 = no fit (p.enable_lr holds the type)
 };
 
 // aom's quantizer_to_qindex[] (CQ level -> base_q_idx); 30 -> 120
@@ -111,6 +113,14 @@ int resolve(const av1mi_params *in, Resolved *r) {
   if (p.deblock > 2) return AV1MI_E_INVALID_ARG;
   r->qidx = kQuantizerToQindex[p.cq_level];
   r->q = quant_steps(r->qidx, (int)p.bit_depth);
+  // enable_lr bit 8 (AV1MI_LR_FIT): the self-guided fit on switchable units, bits 16-31 the sets searched (0 = all); nothing in bits 9-15
+  r->lr_fit_mask = 0;
+  if (p.enable_lr & 0x100u) {
+    const uint32_t low = p.enable_lr & 0xFFu;
+    if ((p.enable_lr & 0xFE00u) || (low != 2 && low != 4)) return AV1MI_E_INVALID_ARG;
+    r->lr_fit_mask = (p.enable_lr >> 16) ? (p.enable_lr >> 16) : 0xFFFFu;
+    p.enable_lr = low;
+  }
   if (p.subpel > 1 || p.enable_lr > 4 || p.color_range > 1 || p.intra_angle_delta > 1 || p.intra_edge_filter > 1 || p.cfl > 1 || p.tx_search > 1) return AV1MI_E_INVALID_ARG;
   if (p.partition_search > 1 || p.me_presearch > 1) return AV1MI_E_INVALID_ARG;
   // enable_lr 3 / 4 = 1 / 2 on all three planes: the frames' restoration type plus the chroma flag
@@ -327,43 +337,19 @@ std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint
 
 // ---- loop restoration unit syntax (§5.11.58): the literal bits that code a Wiener coefficient set against the
 // tile-start reference Wiener_Taps_Mid = {3, -7, 15} (tiles are one superblock = one unit, so that is always the
-// reference).  Mirrors decode_signed_subexp_with_ref_bool / decode_subexp_bool / NS / inverse_recenter.
-struct BitString { unsigned long long bits = 0; int len = 0; void put(unsigned v, int n) { for (int i = n - 1; i >= 0; i--) { bits = (bits << 1) | ((v >> i) & 1); len++; } } };
-void lr_put_ns(BitString &b, int n, int v) {
-  int w = 0, x = n;
-  while (x) { w++; x >>= 1; }
-  const int m = (1 << w) - n;
-  if (v < m) b.put((unsigned)v, w - 1);
-  else { const int extra = v + m; b.put((unsigned)(extra >> 1), w - 1); b.put((unsigned)(extra & 1), 1); }
-}
-void lr_put_subexp(BitString &b, int num_syms, int k, int v) {
-  int i = 0, mk = 0;
-  for (;;) {
-    const int b2 = i ? k + i - 1 : k, a = 1 << b2;
-    if (num_syms <= mk + 3 * a) { lr_put_ns(b, num_syms - mk, v - mk); return; }
-    if (v >= mk + a) { b.put(1, 1); i++; mk += a; }
-    else { b.put(0, 1); b.put((unsigned)(v - mk), b2); return; }
-  }
-}
-int lr_recenter(int r, int v) { return v > 2 * r ? v : (v >= r ? (v - r) << 1 : ((r - v) << 1) - 1); }
-void lr_put_signed_ref(BitString &b, int low, int high, int k, int r, int v) {
-  const int mx = high - low, x = v - low, rr = r - low;
-  if ((rr << 1) <= mx) lr_put_subexp(b, mx, k, lr_recenter(rr, x));
-  else lr_put_subexp(b, mx, k, lr_recenter(mx - 1 - rr, mx - 1 - x));
-}
-const int8_t kWienerCand[3][3] = { { 0, 0, -4 }, { 1, -3, -6 }, { 3, -7, 15 } };  // == lr_kernel.hip, oracle/av1o_lr.c
+// reference).  The writers (lr_put_signed_ref and what it calls, av1mi_lr_sgr_code) are lr_fit_rule.h's: the self-guided
+// fit runs them on the device, and the fixed candidates' constant strings below come from the same functions.
+using BitString = Av1miBitString;
+const int8_t kWienerCand[3][3] = { { 0, 0, -4 }, { 1, -3, -6 }, { 3, -7, 15 } };  // == lr_pieces.h, oracle/av1o_lr.c
 // chroma (enable_lr 3 / 4; tap 0 is 0 and not coded, §5.11.58)
-const int8_t kWienerCandUV[3][3] = { { 0, 0, -4 }, { 0, 0, 16 }, { 0, 6, 20 } };  // == lr_kernel.hip
-const int8_t kSgrCand[3][3] = { { 9, 31, 31 }, { 9, 0, 31 }, { 9, 31, 95 } };     // { lr_sgr_set, xqd0, xqd1 }: == lr_kernel.hip, oracle/av1o_lr.c
+const int8_t kWienerCandUV[3][3] = { { 0, 0, -4 }, { 0, 0, 16 }, { 0, 6, 20 } };  // == lr_pieces.h
+const int8_t kSgrCand[3][3] = { { 9, 31, 31 }, { 9, 0, 31 }, { 9, 31, 95 } };     // { lr_sgr_set, xqd0, xqd1 }: == lr_pieces.h, oracle/av1o_lr.c
 // self-guided unit (§5.11.58): lr_sgr_set L(4), then the two weights against RefSgrXqd (ref 0 = Sgrproj_Xqd_Mid at the tile
 // start, r = candidate r-1: the previous self-guided unit of the tile).  Every candidate uses set 9, whose radii are both
 // non-zero, so both weights are always coded.
 BitString sgr_code_of(int ref, int cand) {
-  static const int xmin[2] = { -96, -32 }, xmax[2] = { 31, 95 }, mid[2] = { -32, 31 };
-  BitString b;
-  b.put((unsigned)kSgrCand[cand][0], 4);
-  for (int i = 0; i < 2; i++) lr_put_signed_ref(b, xmin[i], xmax[i] + 1, 4, ref ? kSgrCand[ref - 1][1 + i] : mid[i], kSgrCand[cand][1 + i]);
-  return b;
+  static const int mid[2] = { -32, 31 };
+  return av1mi_lr_sgr_code(kSgrCand[cand][0], kSgrCand[cand][1], kSgrCand[cand][2], ref ? kSgrCand[ref - 1][1] : mid[0], ref ? kSgrCand[ref - 1][2] : mid[1]);
 }
 // ref: 0 = Wiener_Taps_Mid (tile start), r = candidate r-1 (the previous unit of the tile that was coded with a filter)
 BitString lr_code_of(int ref, int cand) {
@@ -484,6 +470,10 @@ struct Workspace {
   std::vector<Av1miQmEntry> h_qm; int qm_key = -1;
   uint8_t *d_lrc = nullptr;            // per restoration unit: 0 = off, k = candidate k-1
   unsigned long long *d_lrsse = nullptr;  // per restoration unit: the candidates' SSE sums (scratch of lr_kernel.hip's two phases)
+  // the self-guided fit: one block, laid out for the chunk's units (ensure_workspace) - errors and records, which the host fetches
+  // into h_fit with one copy, then sums and codes - so that one fill clears a chunk's part
+  Av1miLrFit fit = {};
+  uint8_t *d_fit = nullptr, *h_fit = nullptr;
   unsigned long long *d_cdef_err = nullptr;  // CDEF strength search: per [frame][superblock] the 24 candidates' squared errors
   int8_t *d_cdef_idx = nullptr;              // ... per [frame][superblock] the index into the frame's set (-1: not coded)
   uint8_t *d_cdef_sel = nullptr;             // ... per frame the set: 8 slots of pair indices
@@ -533,6 +523,11 @@ struct av1mi_ctx {
   // av1mi_lf_search_result.  Empty: no chunk, or the last one failed
   std::vector<uint8_t> lf_levels;
   std::vector<unsigned long long> lf_errs;
+  // ... and its self-guided fit (av1mi_lr_fit_result): the units of its frames over three planes, and whether the fit ran - the errors
+  // and records are then the head of ws.h_fit
+  size_t fit_units = 0;
+  uint32_t fit_plane_units = 0;   // the units of one plane of one frame (av1mi_lr_fit_units)
+  bool fit_on = false;
 };
 
 namespace {
@@ -567,6 +562,13 @@ void free_workspace(av1mi_ctx *c) {
 // range + sign + 31 Golomb bits; <= 10 output bytes per coefficient), so the retry ends.
 int tile_slot_bytes(const Resolved &r, int scale) { return 4096 * scale * r.tile_sb * r.tile_sb; }
 int tile_stream_cap(const Resolved &r, int scale) { return 8192 * scale * r.tile_sb * r.tile_sb; }
+
+// the self-guided fit's units of a chunk - its frames' restoration units over three planes - and the bytes of their block
+size_t fit_chunk_units(const Resolved &r, size_t n_frames) {
+  const size_t ur = (r.p.height + 32) / 64 > 0 ? (r.p.height + 32) / 64 : 1, uc = (r.p.width + 32) / 64 > 0 ? (r.p.width + 32) / 64 : 1;
+  return n_frames * 3 * ur * uc;
+}
+size_t fit_bytes(size_t units) { return units * (AV1MI_LR_FIT_CANDS * 8 + 4 + AV1MI_LR_FIT_SETS * 5 * 8 + 8) + 8; }
 
 int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   const av1mi_params &p = r.p;
@@ -646,6 +648,19 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     HIPCHK(c, ws_alloc(w, w.d_lrc, 3 * nf * nsb + 64));
     HIPCHK(c, ws_alloc(w, w.d_lrsse, (3 * nf * nsb + 64) * 8 * sizeof(unsigned long long)));
   }
+  if (r.lr_fit_mask && (!w.d_fit || !w.h_fit)) {   // for three planes, like the unit sums: the buffers stay while enable_lr changes
+    const size_t units = 3 * nf * nsb + 64;
+    HIPCHK(c, ws_alloc(w, w.d_fit, fit_bytes(units)));
+    HIPCHK(c, ws_alloc(w, w.h_fit, units * (AV1MI_LR_FIT_CANDS * 8 + 4), true));
+  }
+  if (r.lr_fit_mask) {   // this chunk's units, contiguous from the head of the block: errors, records (to a multiple of 8 bytes), sums, codes
+    const size_t n = fit_chunk_units(r, n_frames);
+    w.fit.err = reinterpret_cast<unsigned long long *>(w.d_fit);
+    w.fit.rec = reinterpret_cast<int8_t *>(w.fit.err + n * AV1MI_LR_FIT_CANDS);
+    w.fit.sums = reinterpret_cast<long long *>(w.fit.rec + ((n * 4 + 7) & ~(size_t)7));
+    w.fit.code = reinterpret_cast<uint32_t *>(w.fit.sums + n * AV1MI_LR_FIT_SETS * 5);
+  }
+  w.fit.mask = r.lr_fit_mask;
   w.res = r;
   if (p.enable_qm && r.qm_level < 15) {
     // dequantiser step per coefficient position (§7.12.3) and its reciprocal, for the square transform sizes 4..32
@@ -677,7 +692,7 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
 // workspace buffers the kernels find through them.  The header sizes follow with the headers (prepare_chunk).
 Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const uint32_t *part, const Av1miQmEntry *qm, const uint8_t *aq_map,
                           unsigned long long *cdef_err, int8_t *cdef_idx, uint8_t *cdef_sel, unsigned long long *lf_err, uint8_t *lf_sel,
-                          Av1miChunkRecord *record, const uint32_t *tile_symbols) {
+                          Av1miChunkRecord *record, const uint32_t *tile_symbols, const uint32_t *lr_fit_code) {
   const av1mi_params &p = r.p;
   Av1miDevParams P;
   memset(&P, 0, sizeof(P));
@@ -714,6 +729,7 @@ Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const
   }
   P.enable_lr = (int)p.enable_lr;
   P.lr_chroma = r.lr_chroma;
+  P.lr_fit_code = r.lr_fit_mask ? lr_fit_code : nullptr;
   P.chunk_record = record; P.tile_symbols = tile_symbols;
   for (int rf = 0; rf < 4; rf++)
     for (int k = 0; k < 3; k++) {
@@ -995,7 +1011,7 @@ int av1mi_aq_qindex(av1mi_ctx *c, const av1mi_params *params, const void *frames
   HIPCHK(c, hipSetDevice(c->device));
   const int bps = r.p.bit_depth > 8 ? 2 : 1;
   const size_t in_bytes = caller_bytes(r, n_frames), coded_bytes = (size_t)n_frames * r.cw * r.ch * 3 / 2 * bps;
-  const Av1miDevParams P = dev_params(r, n_frames, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  const Av1miDevParams P = dev_params(r, n_frames, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   hipStream_t s = c->stream;
   void *d_in = nullptr, *d_coded = nullptr;
   uint16_t *d_act = nullptr;
@@ -1042,6 +1058,21 @@ int av1mi_encode_chunk(av1mi_ctx *c, const av1mi_params *params, const void *fra
     if (rc != AV1MI_E_OVERFLOW || c->cap_scale >= 64) return rc;
     c->cap_scale *= 2;  // stays raised for the following chunks of this context (same content)
   }
+}
+
+uint32_t av1mi_lr_fit_units(const av1mi_ctx *c) { return c ? c->fit_plane_units : 0; }
+// The self-guided fit of the context's last chunk: what download_chunk fetched, zeros for a chunk without the fit.
+int av1mi_lr_fit_result(const av1mi_ctx *c, uint32_t n_frames, int8_t *units, uint64_t *err) {
+  if (!c || !units || n_frames == 0 || c->lf_levels.size() != (size_t)n_frames * 4) return AV1MI_E_INVALID_ARG;
+  const size_t n = c->fit_units;
+  if (c->fit_on) {
+    memcpy(units, c->ws.h_fit + n * AV1MI_LR_FIT_CANDS * 8, n * 4);
+    if (err) memcpy(err, c->ws.h_fit, n * AV1MI_LR_FIT_CANDS * 8);
+  } else {
+    memset(units, 0, n * 4);
+    if (err) memset(err, 0, n * AV1MI_LR_FIT_CANDS * 8);
+  }
+  return AV1MI_OK;
 }
 
 // ---- one chunk: prepare_chunk, the schedule of its kind with entropy coding inside, packing, download_chunk
@@ -1108,6 +1139,8 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   if (P.cdef_search) HIPCHK(c, hipMemsetAsync(w.d_cdef_err, 0, (size_t)n_frames * P.sb_rows * P.sb_cols * 24 * sizeof(unsigned long long), s));
   // the level search's sums, once per attempt at the chunk (not a fill per frame on a P chain)
   if (P.lf_search) HIPCHK(c, hipMemsetAsync(w.d_lf_err, 0, (size_t)n_frames * 3 * AV1MI_LF_CANDS * sizeof(unsigned long long), s));
+  // the self-guided fit's sums, errors, records and codes, once per attempt at the chunk
+  if (P.lr_fit_code) HIPCHK(c, hipMemsetAsync(w.d_fit, 0, fit_bytes(fit_chunk_units(r, n_frames)), s));
   HIPCHK(c, hipEventRecord(c->ev[EV_START], s));
   // the caller's frames are used in place if they are on the device at the coded size; a padded chunk arrives in the stage
   if (!frames_on_device) HIPCHK(c, hipMemcpyAsync(r.padded ? w.d_stage : w.d_src, frames, caller_bytes(r, n_frames), hipMemcpyHostToDevice, s));
@@ -1189,7 +1222,8 @@ static int schedule_all_key_lr(av1mi_ctx *c, const void *src, uint32_t n_frames)
   if (av1mi_frame_lf_levels(P, 0)[0]) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, 0, n, s));
   if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, n, s));
   HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, w.d_cd, w.d_blk, nullptr, nullptr, 0, n, s));
-  HIPCHK(c, av1mi_launch_lr(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, 1, 0, n, s));
+  HIPCHK(c, av1mi_launch_lr(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, 1, P.lr_fit_code == nullptr, 0, n, s));
+  if (P.lr_fit_code) HIPCHK(c, av1mi_launch_lr_fit(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, &w.fit, 0, n, s));
   const int rc = entropy_code(c, 0, n_frames);
   return rc ? rc : sse_beside_range_coder(c, src);
 }
@@ -1242,7 +1276,8 @@ static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
     // the frame's strength set before its CDEF (the next frame's reference is the output of the chosen strengths)
     if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, fi, 1, s));
     HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, cdef_out, w.d_blk, nullptr, nullptr, fi, 1, s));
-    if (lr) HIPCHK(c, av1mi_launch_lr(&P, w.d_rec, cdef_out, src, w.d_fin, w.d_lrc, w.d_lrsse, 0, fi, 1, s));
+    if (lr) HIPCHK(c, av1mi_launch_lr(&P, w.d_rec, cdef_out, src, w.d_fin, w.d_lrc, w.d_lrsse, 0, P.lr_fit_code == nullptr, fi, 1, s));
+    if (lr && P.lr_fit_code) HIPCHK(c, av1mi_launch_lr_fit(&P, w.d_rec, cdef_out, src, w.d_fin, w.d_lrc, w.d_lrsse, &w.fit, fi, 1, s));
     if (f == 0)   // (frame 0 of a chunk is a key frame: its chain kernels are in the queue)
       for (uint32_t g = 1; g < n_frames; g++) {
         if (!av1mi_frame_is_inter(P, (int)g)) continue;
@@ -1320,6 +1355,9 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
   const size_t lf_err_bytes = (size_t)n_frames * 3 * AV1MI_LF_CANDS * sizeof(unsigned long long);
   if (e1 == hipSuccess && P.lf_search) e1 = hipMemcpyAsync(w.h_lf, w.d_lf_err, lf_err_bytes, hipMemcpyDeviceToHost, s);
   if (e1 == hipSuccess && P.lf_search) e1 = hipMemcpyAsync(w.h_lf + lf_err_bytes, w.d_lf_sel, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s);
+  // the self-guided fit's errors and records (av1mi_lr_fit_result), likewise
+  const size_t fit_n = (size_t)n_frames * 3 * av1mi_lr_unit_rows(P) * av1mi_lr_unit_cols(P);
+  if (e1 == hipSuccess && P.lr_fit_code) e1 = hipMemcpyAsync(w.h_fit, w.d_fit, fit_n * (AV1MI_LR_FIT_CANDS * 8 + 4), hipMemcpyDeviceToHost, s);
   // the bitstream is on the host once EV_DOWNLOAD_DONE has passed: hand it over to the caller's buffer while the second stream finishes
   if (e1 == hipSuccess && e2 == hipSuccess && dst != host) {
     e1 = hipEventSynchronize(c->ev[EV_DOWNLOAD_DONE]);
@@ -1341,6 +1379,8 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
   } else {
     for (uint32_t f = 0; f < n_frames; f++) for (int i = 0; i < 4; i++) c->lf_levels[(size_t)f * 4 + i] = (uint8_t)av1mi_frame_lf_levels(P, (int)f)[i];
   }
+  c->fit_units = fit_n; c->fit_plane_units = (uint32_t)(av1mi_lr_unit_rows(P) * av1mi_lr_unit_cols(P));
+  c->fit_on = P.lr_fit_code != nullptr;   // (the values stay in h_fit until the context's next chunk)
   if (frame_sizes) for (uint32_t f = 0; f < n_frames; f++) frame_sizes[f] = (uint32_t)(foff[f + 1] - foff[f]);
   if (report) {
     memset(report, 0, sizeof(*report));
@@ -1384,7 +1424,7 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
 static int run_chunk(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
                      av1mi_buf *out, uint32_t *frame_sizes, void *recon, av1mi_report *report) {
   out->data = nullptr; out->size = 0;
-  c->lf_levels.clear(); c->lf_errs.clear();
+  c->lf_levels.clear(); c->lf_errs.clear(); c->fit_units = 0; c->fit_plane_units = 0; c->fit_on = false;
   Resolved r;
   int rc = resolve(params, &r);
   if (rc) { set_err(c, "invalid parameters"); return rc; }
@@ -1393,7 +1433,7 @@ static int run_chunk(av1mi_ctx *c, const av1mi_params *params, const void *frame
   if (rc) return rc;
   Workspace &w = c->ws;
   c->P = dev_params(r, n_frames, c->cap_scale, w.d_part, w.d_qm, w.d_aq_map, w.d_cdef_err, w.d_cdef_idx, w.d_cdef_sel, w.d_lf_err, w.d_lf_sel,
-                     w.d_record, w.d_sym);
+                     w.d_record, w.d_sym, w.fit.code);
   const void *d_src = nullptr;
   rc = prepare_chunk(c, r, frames, n_frames, frames_on_device, &d_src);
   if (rc) return rc;

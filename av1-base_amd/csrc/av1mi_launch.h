@@ -99,8 +99,13 @@ hipError_t av1mi_launch_cdef(const Av1miDevParams *P, const void *rec, void *fin
 // choice and unit_sse: [frame][plane][unit] (av1mi_lr_frame_units per frame), unit_sse with 8 sums per unit - scratch of the two phases,
 // cleared here for the launch's frames with `clear`, else by the caller (the frame loop of a P chunk clears the whole chunk's once
 // instead of putting a fill between every frame's kernels on the chain)
+// decide = 0: phase 0 alone - the fixed candidates' sums, for av1mi_launch_lr_fit on the same stream to decide with
 hipError_t av1mi_launch_lr(const Av1miDevParams *P, const void *pre, const void *cdef, const void *src, void *out, uint8_t *choice,
-                           unsigned long long *unit_sse, int clear, int frame0, int count, hipStream_t stream);
+                           unsigned long long *unit_sse, int clear, int decide, int frame0, int count, hipStream_t stream);
+// the self-guided fit (lr_fit_kernel.hip), after av1mi_launch_lr with decide = 0: sums, exact SSE, decision and filter, unit codes.
+// fit: the chunk-wide buffers, cleared by the caller once per attempt at the chunk; choice gets 0 .. 22
+hipError_t av1mi_launch_lr_fit(const Av1miDevParams *P, const void *pre, const void *cdef, const void *src, void *out, uint8_t *choice,
+                               const unsigned long long *unit_sse, const Av1miLrFit *fit, int frame0, int count, hipStream_t stream);
 // tile_order: n_tiles entries of scratch.  mid: recorded on `stream` after symbolize, or null.  aux != null: the frame-edge tiles'
 // symbolize variant runs there, beside the regular one, between `fork` and `join`
 hipError_t av1mi_launch_entropy(const Av1miDevParams *P, const uint16_t *cdf_init, const int16_t *levels, const Av1miBlkInfo *blk,

@@ -733,11 +733,14 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
         else sym_wide(y, lane, adapt, ch != 0, FULL ? CL::USE_WIENER : CC::USE_WIENER, 2);
         const int sh = 2 * pl;
         if (ch > 3) {
+          // with the self-guided fit (choices 4 .. 22) the unit's bits are its own, written against the carried RefSgrXqd by
+          // lr_fit_kernel.hip: [frame][plane 0..2][unit] { bits, length }
+          const uint32_t *fc = P.lr_fit_code ? P.lr_fit_code + (((size_t)f * 3 + pl) * urows * ucols + sbr * ucols + sbc) * 2 : nullptr;
           const int rf = (sgr_prev >> sh) & 3;
-          const int len = P.sgr_code_len[rf][ch - 4];
-          const unsigned long long bits = P.sgr_code_bits[rf][ch - 4];
+          const int len = fc ? uni((int)fc[1]) : P.sgr_code_len[rf][ch - 4];
+          const unsigned long long bits = fc ? (unsigned long long)(uint32_t)uni((int)fc[0]) : P.sgr_code_bits[rf][ch - 4];
           for (int i = len - 1; i >= 0; i--) emit1(y, lane, ENT_LITERAL((int)((bits >> i) & 1)));
-          sgr_prev = (sgr_prev & ~(3 << sh)) | ((ch - 3) << sh);
+          if (!fc) sgr_prev = (sgr_prev & ~(3 << sh)) | ((ch - 3) << sh);
         } else if (ch) {
           const int rf = (lr_prev >> sh) & 3;
           const int len = pl ? P.lr_code_len_uv[rf][ch - 1] : P.lr_code_len[rf][ch - 1];

@@ -40,6 +40,8 @@ typedef struct av1mi_ctx av1mi_ctx;
 #define AV1MI_CQ_AQ(cq, strength) (((uint32_t)(cq) & 0xFFu) | (((uint32_t)(strength) & 7u) << 8))
 #define AV1MI_CQ_LEVEL(v) ((uint32_t)(v) & 0xFFu)
 #define AV1MI_AQ_STRENGTH(v) (((uint32_t)(v) >> 8) & 7u)
+/* av1mi_params.enable_lr with the self-guided fit: lr = 2 or 4, sets = a mask over the 16 parameter sets searched (0 = all) */
+#define AV1MI_LR_FIT(lr, sets) ((uint32_t)(lr) | 0x100u | ((uint32_t)(sets) << 16))
 
 /* Operating point.  Replaces the reference's single constant
  *   SVT_PARAMS = "--crf 8 --preset 3 --film-grain 20 ... --keyint 240 --lookahead 40"
@@ -77,7 +79,13 @@ typedef struct {
                                3 / 4 = 1 / 2 on all three planes: U and V in 32x32 units (the picture area of a luma
                                unit), each unit decided on its own; chroma Wiener filters (0, 0, -4), (0, 0, 16), (0, 6, 20).
                                A library without chroma restoration refuses 3 and 4 with AV1MI_E_INVALID_ARG, as every
-                               library refuses values above 4;
+                               library refuses values above 4 in the low byte;
+                               bit 8 with a low byte of 2 or 4 (AV1MI_LR_FIT packs the field): the
+                               self-guided filter is fitted per unit - beside the seven candidates above a unit may take any of
+                               the 16 parameter sets (bits 16-31: a mask over the sets searched, 0 = all) with the two weights
+                               that least squares gives for the unit, the smallest exact SSE winning as before.  Headers are
+                               those of 2 / 4.  Bit 8 with any other low byte, and bits 9-15, are refused with
+                               AV1MI_E_INVALID_ARG.  av1mi_lr_fit_result reports the units' choices;
                                default 0: the decision needs the CDEF output, which serialises CDEF before entropy coding */
   uint32_t tile_sb;         /* tile size in 64x64 superblocks, both ways: 0 = automatic (1; 2 when the frame has more than 64
                                superblock rows or columns, e.g. 8K - AV1 allows at most 64 x 64 tiles), or force 1 / 2 */
@@ -211,6 +219,20 @@ int av1mi_aq_qindex(av1mi_ctx *ctx, const av1mi_params *params, const void *fram
  * against the source over the signalled size; zeros without the search.  The values arrive with the chunk's other small
  * results: the call only copies them.  AV1MI_E_INVALID_ARG if n_frames is not the last chunk's frame count. */
 int av1mi_lf_search_result(const av1mi_ctx *ctx, uint32_t n_frames, uint8_t *levels, uint64_t *err);
+
+/* ---- self-guided fit of the last chunk ------------------------------------------------------
+ * With enable_lr bit 8 (AV1MI_LR_FIT): per restoration unit of the context's last successfully encoded chunk
+ * units[((f * 3 + plane) * n_units + u) * 4 + 0..3] = { choice, lr_sgr_set, xqd0, xqd1 } - choice 0 = off, 1..3 = Wiener filter,
+ * 4..6 = fixed self-guided candidate, 7 + t = parameter set t with fitted weights (set and weights 0 unless choice >= 4) - and
+ * (optional) err[((f * 3 + plane) * n_units + u) * 23 + choice] = the candidates' squared error against the source, UINT64_MAX for
+ * an absent candidate (a set outside the mask, or a singular fit).  n_units = unit rows x unit columns of a plane,
+ * max(1, (size + 32) / 64) each way from the signalled size; units in raster order.  Entries are zero for planes that are not restored
+ * and for a chunk without the fit.  The values arrive with the chunk's other small results: the call only copies them.
+ * AV1MI_E_INVALID_ARG if n_frames is not the last chunk's frame count. */
+int av1mi_lr_fit_result(const av1mi_ctx *ctx, uint32_t n_frames, int8_t *units, uint64_t *err);
+/* n_units of the context's last successfully encoded chunk (0: none): what a caller sizes the two arrays above by -
+ * units holds n_frames * 3 * n_units * 4 entries, err n_frames * 3 * n_units * 23 */
+uint32_t av1mi_lr_fit_units(const av1mi_ctx *ctx);
 
 /* ---- the drop-in for `run_av1an` ---------------------------------------------------------
  * Replaces  pub fn run_av1an(params: &Av1anEncodeParams) -> Result<(), EncodeError>

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Self-guided fit A/B: bench.py's synthclip (1080p x 60, 10-bit) encoded with enable_lr 0 (off), 4 (switchable units on all planes, fixed
+candidates), fit | 4 (the self-guided filter fitted per unit over all 16 parameter sets) and fit | 4 with
+the mask 1 << 9 (set 9 alone: the fixed candidates' set with fitted weights) at the headline point (all key frames, CQ 30), IPPP at
+CQ 30 and the production point (CQ 8).  One JSON line per point and value: frames/s (best of --steps after --warmup, the clip in HBM),
+milliseconds per frame, bytes per frame, PSNR Y / U / V of the reconstruction, the report's stage times and, with the fit, the
+histogram of the units' choices (off / Wiener / fixed / fitted), of the fitted sets and of the fitted weights at their clamps
+(av1mi_lr_fit_result).  It reports what it measures, nothing more."""
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "av1-base_amd"))
+import bench  # noqa: E402
+
+
+POINTS = [
+    ("headline_cq30", dict(keyint=1, cq_level=30, intra_mode_mask=0x1FFF)),
+    ("cfg3_1080p_ippp", dict(keyint=240, cq_level=30, intra_mode_mask=0x7)),
+    ("production_1080p", dict(keyint=240, cq_level=8, intra_mode_mask=0x7, film_grain=20, subpel=1, enable_qm=1, qm_min=1, qm_max=15)),
+]
+VALUES = {"0": 0, "4": 4, "fit4": 0x104, "fit4_set9": 0x104 | ((1 << 9) << 16)}
+
+
+def fit_hist(units):
+    """choices, fitted sets and clamped weights of units[frame][plane][row][column][4] over the restored planes"""
+    u = units.reshape(-1, 4)
+    k = u[:, 0]
+    fitted = u[k >= 7]
+    sets = {int(t): int((fitted[:, 1] == t).sum()) for t in sorted(set(fitted[:, 1].tolist()))}
+    both = fitted[(fitted[:, 1] < 10)]
+    return {"units": int(len(u)), "off": int((k == 0).sum()), "wiener": int(((k >= 1) & (k <= 3)).sum()),
+            "fixed": int(((k >= 4) & (k <= 6)).sum()), "fitted": int(len(fitted)), "sets": sets,
+            "xqd0_at_clamp": int(((both[:, 2] == -96) | (both[:, 2] == 31)).sum()),
+            "xqd1_at_clamp": int(((both[:, 3] == -32) | (both[:, 3] == 95)).sum())}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--frames", type=int, default=60)
+    ap.add_argument("--points", default="", help="comma-separated subset of the point names")
+    ap.add_argument("--values", default="0,4,fit4,fit4_set9")
+    args = ap.parse_args()
+    import torch
+    import av1mi
+    w, h, bd, n = 1920, 1080, 10, args.frames
+    dev = torch.device("cuda:0")
+    clip = bench.make_clip_torch(w, h, bd, n, 1080, dev)
+    torch.cuda.synchronize(dev)
+    want = set(args.points.split(",")) if args.points else None
+    with av1mi.Context(0) as ctx:
+        for name, kw in POINTS:
+            if want and name not in want:
+                continue
+            for v in args.values.split(","):
+                p = av1mi.default_params(w, h, bd, enable_lr=VALUES[v], **kw)
+                for _ in range(args.warmup):
+                    ctx.encode_chunk(p, clip.data_ptr(), n, on_device=True, copy_out=False)
+                best, rep = None, None
+                for _ in range(args.steps):
+                    t0 = time.perf_counter()
+                    _, _, r, _ = ctx.encode_chunk(p, clip.data_ptr(), n, on_device=True, copy_out=False)
+                    dt = time.perf_counter() - t0
+                    if best is None or dt < best:
+                        best, rep = dt, r
+                line = {"point": name, "enable_lr": v, "fps": round(n / best, 1), "ms": round(best * 1e3, 2), "ms_per_frame": round(best * 1e3 / n, 3),
+                        "bytes_per_frame": round(rep.bytes / n, 1), "psnr": [round(x, 3) for x in rep.psnr], "sse": [int(x) for x in rep.sse],
+                        "ms_recon": round(rep.ms_recon, 3), "ms_entropy": round(rep.ms_entropy, 3)}
+                if VALUES[v] & 0x100:
+                    line["fit"] = fit_hist(ctx.lr_fit_result(n)[0])
+                print(json.dumps(line), flush=True)
+
+
+if __name__ == "__main__":
+    main()
