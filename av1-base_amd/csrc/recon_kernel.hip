@@ -55,6 +55,10 @@ static __device__ __forceinline__ int32_t av1_half_btf1(int32_t w, int32_t a) { 
 #include "txfm_gen.h"
 #include "fdct32_matrix.h"
 #include "intra_pieces.h"
+#include "quant_pieces.h"
+#ifndef AV1MI_CHROMA_HANDOVER
+#define AV1MI_CHROMA_HANDOVER 1
+#endif
 
 namespace {
 
@@ -1129,6 +1133,7 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
   int my_key = -1;  // (anti-diagonal << 6 | position inside it) of the last nonzero level in scan order
   uint32_t my_ext = 0;   // {last nonzero row + 1, last nonzero column + 1} of this lane's levels as packed 16-bit values (0: none)
   int16_t *lvl = reinterpret_cast<int16_t *>(S->srcblk) + po;  // source block is dead: reuse for the levels
+  namespace qp = av1mi_quant;
   if constexpr (MM) {
     // ---- forward 32x32 DCT as Y = Cm * X * Cm^T on the matrix cores (v_mfma_i32_32x32x32_i8; tools/mfma_fwd32_ab.hip is the
     // measured A/B against the butterflies).  Values are split into signed bytes, v = 256 * hi + lo: four products per stage, the two
@@ -1173,31 +1178,39 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
     ll2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(s2_lo, b_lo, ll2, 0, 0, 0);
     STAMP(3);   // forward transform
     // ---- dead-zone quantiser of the lane's 16 coefficients (k, m): levels to LDS, the key of the last nonzero one in scan order
+    // (quant_pieces.h).  The row k grows with the register, so of the scan key and the extent only the last nonzero register is
+    // tracked; registers 8 .. 15 (k >= 16) are all in dead-zone class 2, 4 .. 7 (k >= 8) never in class 0, and the rest compare the
+    // register's constant row offset against per-lane thresholds.
     {
       const int col = mr;
       const uint32_t acq = (uint32_t)P->ac_q, acr = P->ac_recip;
       const QmTab tab = QM ? qm_table(P) + (pc ? AV1MI_QM_PLANE : 0) + AV1MI_QM_32X32 + col : (QmTab)0;
+      const uint32_t r0 = qp::dz_round(acq, 0), r1 = qp::dz_round(acq, 1), r2 = qp::dz_round(acq, 2);
+      const int ta = qp::dz_ta(col + 4 * mh, 32), tb = qp::dz_tb(col + 4 * mh, 32);   // thresholds on (reg & 3) + 8 * (reg >> 2)
+      const bool dc = lane == 0;   // (row | col) == 0: register 0 of lane 0
+      int last = -1;
 #pragma unroll
       for (int reg = 0; reg < 16; reg++) {
-        const int row = (reg & 3) + 8 * (reg >> 2) + 4 * mh;
-        const int v = ((hh2[reg] << 16) + (mid2[reg] << 8) + ll2[reg] + 2048) >> 12;
-        uint32_t q, recip;
-        if constexpr (QM) { q = tab[row * 32].q; recip = tab[row * 32].recip; }
-        else if (reg == 0) { const bool dc = (row | col) == 0; q = dc ? (uint32_t)P->dc_q : acq; recip = dc ? P->dc_recip : acr; }
-        else { q = acq; recip = acr; }
-        const int d0 = row + col;
-        const uint32_t rnd = d0 < 8 ? (3 * q) >> 3 : (d0 < 16 ? (q >> 2) : (q >> 3));
-        const int sgn = v >> 31;
-        const uint32_t a = ((uint32_t)((v ^ sgn) - sgn) << TSH) + rnd;
-        uint32_t lv = __umulhi(a, recip);
-        lv = lv > 0x7FFF ? 0x7FFF : lv;
-        lvl[row * 32 + col] = (int16_t)(((int)lv ^ sgn) - sgn);
-        if (lv) {
-          const int key = (d0 << 6) | ((d0 & 1) ? row : col);
-          my_key = key > my_key ? key : my_key;
-          my_ext = ((uint32_t)(row + 1) << 16) | (uint32_t)(col + 1);   // (rows grow with reg)
+        const int row = qp::mm_row(reg, mh);
+        const int v = ((hh2[reg] << 16) + ((mid2[reg] << 8) + (ll2[reg] + 2048))) >> 12;
+        uint32_t q, recip, rnd;
+        if constexpr (QM) {
+          q = tab[row * 32].q; recip = tab[row * 32].recip;
+          rnd = qp::dz_round(q, qp::dz_class(row, col, 32));
+        } else {
+          q = acq; recip = acr;
+          rnd = qp::dz_round_mm(reg, ta, tb, r0, r1, r2);
+          if (reg == 0) {   // (the DC position is in class 0)
+            q = dc ? (uint32_t)P->dc_q : acq; recip = dc ? P->dc_recip : acr;
+            rnd = dc ? qp::dz_round(q, 0) : rnd;
+          }
         }
+        const int sgn = qp::sign_mask(v);
+        const uint32_t lv = qp::level_abs<TSH>(qp::magnitude(v, sgn), rnd, recip);
+        lvl[row * 32 + col] = (int16_t)qp::with_sign(lv, sgn);
+        last = lv ? reg : last;
       }
+      if (last >= 0) { const int row = qp::mm_row(last, mh); my_key = qp::scan_key(row, col); my_ext = qp::extent(row, col); }
     }
     wave_sync();
   } else {
@@ -1214,6 +1227,49 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
     // dead-zone quantiser + normative dequantiser (§7.12.3) of this lane's coefficient row.  QM: the step of every position
     // comes from the context's quantiser-matrix table {Round2(q * Quantizer_Matrix, 5), ceil(2^32 / that)}; the matrices are
     // symmetric, so lanes read entry [j][row] (consecutive addresses across the wave).
+    // HO: a chroma 16x16 pair keeps lanes 16 .. 31 of either half idle in this phase.  After the forward row pass the lane of row r hands
+    // columns 8 .. 15 to lane r + 16 (ds_bpermute: the crossbar, no memory), both quantise and dequantise eight coefficients, and the
+    // dequantised values come back for the inverse row pass.  Columns 8 .. 15 are in dead-zone class 2 in every row.
+    constexpr bool HO = AV1MI_CHROMA_HANDOVER && !QM && NPL == 2 && LOG2N == 4;
+    if constexpr (HO) {
+      if (row_lane) {
+  #pragma unroll
+        for (int j = 0; j < N; j++) x[j] = S->scratch[so + sl * ST + j];
+        Tx1d<LOG2N>::fwd(x, ht);
+      }
+      const int hi = (sl >> 4) & 1, row = sl & 15, jb = 8 * hi;
+      const int from_lo = (lane & ~16) << 2, from_hi = (lane | 16) << 2;
+      int c[8];
+  #pragma unroll
+      for (int j = 0; j < 8; j++) { const int up = __builtin_amdgcn_ds_bpermute(from_lo, x[8 + j]); c[j] = hi ? up : x[j]; }
+      const uint32_t acq = (uint32_t)P->ac_q, acr = P->ac_recip;
+      const uint32_t r0 = qp::dz_round(acq, 0), r1 = qp::dz_round(acq, 1), r2 = qp::dz_round(acq, 2);
+      const int ta = hi ? -1 : qp::dz_ta(row, CW), tb = hi ? -1 : qp::dz_tb(row, CW);
+      const int lim = 1 << (7 + bd);
+      int lastj = -1;
+  #pragma unroll
+      for (int j = 0; j < 8; j++) {
+        const int v = rshift_round(c[j], SH2);
+        uint32_t q = acq, recip = acr, rnd = qp::dz_round_row<CW>(j, ta, tb, r0, r1, r2);
+        if (j == 0) {
+          const bool dc = sl == 0;
+          q = dc ? (uint32_t)P->dc_q : acq; recip = dc ? P->dc_recip : acr;
+          rnd = qp::dz_pick(0, ta, tb, qp::dz_round(q, 0), qp::dz_round(q, 1), qp::dz_round(q, 2));
+        }
+        const int sgn = qp::sign_mask(v);
+        const uint32_t lv = qp::level_abs<TSH>(qp::magnitude(v, sgn), rnd, recip);
+        lvl[row * CW + jb + j] = (int16_t)qp::with_sign(lv, sgn);
+        int d = 0;
+        if (lv) {
+          lastj = jb + j;
+          d = qp::dequant<TSH>(lv, q, sgn, lim);
+        }
+        c[j] = d;
+      }
+      if (lastj >= 0) { my_key = qp::scan_key(row, lastj); my_ext = qp::extent(row, lastj); }
+  #pragma unroll
+      for (int j = 0; j < 8; j++) { x[8 + j] = __builtin_amdgcn_ds_bpermute(from_hi, c[j]); x[j] = c[j]; }
+    } else
     if (row_lane) {
   #pragma unroll
       for (int j = 0; j < N; j++) x[j] = S->scratch[so + sl * ST + j];
@@ -1225,34 +1281,30 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
         // multiply (level < 2^15, step < 2^15), and of the scan key only the last nonzero column is tracked (the key grows with the
         // column inside a row).  The dequantiser stays behind `if (lv)`: a column with no level in any row costs the wave nothing.
         const uint32_t acq = (uint32_t)P->ac_q, acr = P->ac_recip;
-        const uint32_t r0 = (3 * acq) >> 3, r1 = acq >> 2, r2 = acq >> 3;
-        const int ta = (CW >> 2) - row, tb = (CW >> 1) - row;   // column j is in dead-zone class 0 below ta, 1 below tb, else 2
+        const uint32_t r0 = qp::dz_round(acq, 0), r1 = qp::dz_round(acq, 1), r2 = qp::dz_round(acq, 2);
+        const int ta = qp::dz_ta(row, CW), tb = qp::dz_tb(row, CW);   // column j is in dead-zone class 0 below ta, 1 below tb, else 2
         const int lim = 1 << (7 + bd);
         int lastj = -1;
   #pragma unroll
         for (int j = 0; j < CW; j++) {
           const int v = rshift_round(x[j], SH2);
-          uint32_t q = acq, recip = acr, rnd = j < ta ? r0 : (j < tb ? r1 : r2);
+          uint32_t q = acq, recip = acr, rnd = qp::dz_round_row<CW>(j, ta, tb, r0, r1, r2);
           if (j == 0) {
             const bool dc = row == 0;
             q = dc ? (uint32_t)P->dc_q : acq; recip = dc ? P->dc_recip : acr;
-            rnd = 0 < ta ? (3 * q) >> 3 : (0 < tb ? (q >> 2) : (q >> 3));
+            rnd = qp::dz_pick(0, ta, tb, qp::dz_round(q, 0), qp::dz_round(q, 1), qp::dz_round(q, 2));
           }
-          const int sgn = v >> 31;
-          const uint32_t a = ((uint32_t)((v ^ sgn) - sgn) << TSH) + rnd;
-          uint32_t lv = __umulhi(a, recip);
-          lv = lv > 0x7FFF ? 0x7FFF : lv;
-          lvl[row * CW + j] = (int16_t)(((int)lv ^ sgn) - sgn);
+          const int sgn = qp::sign_mask(v);
+          const uint32_t lv = qp::level_abs<TSH>(qp::magnitude(v, sgn), rnd, recip);
+          lvl[row * CW + j] = (int16_t)qp::with_sign(lv, sgn);
           int d = 0;
           if (lv) {   // (most columns beyond the first few hold no level in any row: the wave skips the block)
             lastj = j;
-            d = (int)((__umul24(lv, q) & 0xFFFFFF) >> TSH);
-            d = (d ^ sgn) - sgn;
-            d = d < -lim ? -lim : (d > lim - 1 ? lim - 1 : d);
+            d = qp::dequant<TSH>(lv, q, sgn, lim);
           }
           x[j] = d;
         }
-        if (lastj >= 0) { const int d0 = row + lastj; my_key = (d0 << 6) | ((d0 & 1) ? row : lastj); my_ext = ((uint32_t)(row + 1) << 16) | (uint32_t)(lastj + 1); }
+        if (lastj >= 0) { my_key = qp::scan_key(row, lastj); my_ext = qp::extent(row, lastj); }
       } else {
       constexpr int QM_OFF = LOG2N == 2 ? AV1MI_QM_4X4 : (LOG2N == 3 ? AV1MI_QM_8X8 : (LOG2N == 4 ? AV1MI_QM_16X16 : AV1MI_QM_32X32));
       const QmTab tab = qm_table(P) + (pc ? AV1MI_QM_PLANE : 0) + QM_OFF + row;

@@ -1,0 +1,136 @@
+// Host build of the reconstruction kernel's quantiser rule (av1-base_amd/csrc/quant_pieces.h) for tests/test_quant_pieces_host.py: the same
+// source the kernel compiles, against the oracle's quantiser - the loop over a block's coefficients in oracle/av1o_enc.c
+// (code_tx_block), restated here per coefficient in 64-bit arithmetic because the oracle has it inside the block coder.  Test
+// infrastructure only.  The restatement is tied to the oracle itself by tests/test_recon_trim.py, which compares what the kernel codes
+// with this header against the oracle's bitstream and reconstruction.  With -DQUANT_PIECES_MAIN the file is a program of its own that runs every check and prints the mismatches.
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include "../../av1-base_amd/csrc/quant_pieces.h"
+#include "../../av1-base_amd/csrc/av1_tables.h"
+
+namespace qp = av1mi_quant;
+
+// ---- the oracle's rule (oracle/av1o_enc.c, code_tx_block: "dead-zone quantise" and "normative dequant §7.12.3")
+static int ref_tsh(int log2n) { return log2n >= 6 ? 2 : (log2n == 5 ? 1 : 0); }
+static uint32_t ref_rnd(uint32_t q, int i, int j, int cw) { return (i + j) < (cw >> 2) ? (3 * q) >> 3 : ((i + j) < (cw >> 1) ? (q >> 2) : (q >> 3)); }
+static int32_t ref_level(int32_t v, uint32_t q, uint32_t rnd, int sh) {
+  const uint32_t recip = (uint32_t)((((uint64_t)1 << 32) + q - 1) / q);
+  const uint32_t a = ((uint32_t)llabs((long long)v) << sh) + rnd;
+  uint32_t lv = (uint32_t)(((uint64_t)a * recip) >> 32);
+  if (lv > 0x7FFF) lv = 0x7FFF;
+  return v < 0 ? -(int32_t)lv : (int32_t)lv;
+}
+static int32_t ref_dequant(int32_t lv, uint32_t q, int sh, int bd) {
+  int64_t d = ((int64_t)llabs((long long)lv) * q) & 0xFFFFFF;
+  const int64_t lim = (int64_t)1 << (7 + bd);
+  d >>= sh;
+  if (lv < 0) d = -d;
+  if (d < -lim) d = -lim;
+  if (d > lim - 1) d = lim - 1;
+  return (int32_t)d;
+}
+
+template <int TSH>
+static long sweep_t(int bd, uint32_t q, int cls, long *capped) {
+  const uint32_t recip = (uint32_t)((((uint64_t)1 << 32) + q - 1) / q);
+  const int lim = 1 << (7 + bd);
+  // a position of the class in a 32-wide area, for the reference's own class rule
+  const int i = cls == 0 ? 0 : (cls == 1 ? 8 : 16), j = 0;
+  const uint32_t rnd = qp::dz_round(q, cls);
+  long bad = rnd != ref_rnd(q, i, j, 32);
+  static const int32_t extremes[] = { 1 << 17, (1 << 17) + 1, 1 << 18, (1 << 19) - 1, 1 << 20, (1 << 22) + 12345, 1 << 23, (1 << 24) - 1, 1 << 26, 1 << 28, (1 << 29) - 1 };
+  const int NE = (int)(sizeof(extremes) / sizeof(extremes[0]));
+  for (long k = -65536 - 2 * NE; k <= 65536; k++) {
+    int32_t v = (int32_t)k;
+    if (k < -65536) { const long e = -65537 - k; v = (e & 1) ? -extremes[e >> 1] : extremes[e >> 1]; }
+    const int sgn = qp::sign_mask(v);
+    const uint32_t lv = qp::level_abs<TSH>(qp::magnitude(v, sgn), rnd, recip);
+    const int32_t level = qp::with_sign(lv, sgn), want = ref_level(v, q, rnd, TSH);
+    bad += level != want || (int16_t)level != want;
+    bad += (lv ? qp::dequant<TSH>(lv, q, sgn, lim) : 0) != ref_dequant(want, q, TSH, bd);
+    *capped += lv == qp::LEVEL_CAP;
+  }
+  return bad;
+}
+
+// every coefficient value in +-2^16 and the extremes, both steps of the quantiser index, the three dead-zone classes: mismatches
+extern "C" long qp_sweep(int log2n, int bd, int qidx, long *capped) {
+  const uint32_t qs[2] = { (uint32_t)(bd == 8 ? av1_dc_q8[qidx] : av1_dc_q10[qidx]), (uint32_t)(bd == 8 ? av1_ac_q8[qidx] : av1_ac_q10[qidx]) };
+  long bad = 0;
+  *capped = 0;
+  for (int s = 0; s < 2; s++)
+    for (int cls = 0; cls < 3; cls++) {
+      const int sh = ref_tsh(log2n);
+      bad += sh == 0 ? sweep_t<0>(bd, qs[s], cls, capped) : (sh == 1 ? sweep_t<1>(bd, qs[s], cls, capped) : sweep_t<2>(bd, qs[s], cls, capped));
+    }
+  return bad;
+}
+
+template <int CW>
+static long rows_t() {
+  const uint32_t q = 1000, r0 = qp::dz_round(q, 0), r1 = qp::dz_round(q, 1), r2 = qp::dz_round(q, 2);
+  long bad = 0;
+  for (int row = 0; row < CW; row++) {
+    const int ta = qp::dz_ta(row, CW), tb = qp::dz_tb(row, CW);
+    for (int j = 0; j < CW; j++) {
+      const uint32_t want = ref_rnd(q, row, j, CW);
+      bad += qp::dz_round(q, qp::dz_class(row, j, CW)) != want;
+      bad += qp::dz_pick(j, ta, tb, r0, r1, r2) != want;
+      bad += qp::dz_round_row<CW>(j, ta, tb, r0, r1, r2) != want;
+    }
+  }
+  return bad;
+}
+
+// every (row, column): the class and its per-lane forms (a row per lane at every coded width; the matrix-core layout at 32x32), the key
+// and the extent of a lane from its last nonzero position
+extern "C" long qp_positions(void) {
+  long bad = rows_t<4>() + rows_t<8>() + rows_t<16>() + rows_t<32>();
+  const uint32_t q = 1000, r0 = qp::dz_round(q, 0), r1 = qp::dz_round(q, 1), r2 = qp::dz_round(q, 2);
+  bool seen[32][32] = {};
+  for (int lane = 0; lane < 64; lane++) {
+    const int col = lane & 31, mh = lane >> 5;
+    const int ta = qp::dz_ta(col + 4 * mh, 32), tb = qp::dz_tb(col + 4 * mh, 32);
+    int prev_row = -1, prev_key = -1;
+    for (int reg = 0; reg < 16; reg++) {
+      const int row = qp::mm_row(reg, mh);
+      bad += row <= prev_row || row > 31 || seen[row][col];   // rows grow with the register; every position once
+      seen[row][col] = true;
+      bad += qp::dz_round_mm(reg, ta, tb, r0, r1, r2) != ref_rnd(q, row, col, 32);
+      bad += qp::scan_key(row, col) <= prev_key;              // ... and so does the key: the last nonzero register decides it
+      prev_row = row; prev_key = qp::scan_key(row, col);
+    }
+  }
+  for (int r = 0; r < 32; r++)
+    for (int c = 0; c < 32; c++) {
+      bad += !seen[r][c];
+      bad += qp::extent(r, c) != (((uint32_t)(r + 1) << 16) | (uint32_t)(c + 1));
+      if (c) bad += qp::scan_key(r, c) <= qp::scan_key(r, c - 1);   // a row per lane: the key grows with the column
+      if (r) bad += qp::scan_key(r, c) <= qp::scan_key(r - 1, c);
+    }
+  return bad;
+}
+
+// scan keys of a cw x cw area, row-major
+extern "C" void qp_keys(int cw, int *out) {
+  for (int r = 0; r < cw; r++)
+    for (int c = 0; c < cw; c++) out[r * cw + c] = qp::scan_key(r, c);
+}
+
+#ifdef QUANT_PIECES_MAIN
+int main() {
+  long bad = qp_positions(), capped_all = 0;
+  static const int qidx[] = { 1, 120, 255 };
+  for (int log2n = 2; log2n <= 6; log2n++)
+    for (int bd = 8; bd <= 10; bd += 2)
+      for (int k = 0; k < 3; k++) {
+        long capped = 0;
+        bad += qp_sweep(log2n, bd, qidx[k], &capped);
+        capped_all += capped;
+      }
+  if (!capped_all) bad++;
+  printf("quant_pieces: %ld mismatches\n", bad);
+  return bad != 0;
+}
+#endif

@@ -1,0 +1,91 @@
+"""The reconstruction kernel's quantiser rule (av1-base_amd/csrc/quant_pieces.h: what both quantiser loops of recon_kernel.hip call)
+compiled for the host and checked, without a GPU, against the oracle's quantiser (oracle/av1o_enc.c, code_tx_block, restated per
+coefficient in tests/host/quant_pieces_host.cpp) and the oracle's scan tables: level, dequantised value, dead-zone class, scan key and
+extent - transform sizes 4 .. 64, 8 and 10 bit, the lowest quantiser index, 120 (CQ 30) and the highest, every coefficient value in
++-2^16 plus the extremes that reach the 0x7FFF cap, every (row, column) at every coded width."""
+import ctypes as C
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "tests", "host", "quant_pieces_host.cpp")
+QIDX = (1, 120, 255)
+
+
+@pytest.fixture(scope="module")
+def cxx():
+    c = next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++") or "") if c and os.path.exists(c)), None)
+    if not c:
+        pytest.skip("no clang++")
+    return c
+
+
+@pytest.fixture(scope="module")
+def quant(cxx, tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("quant") / "libquantpieces.so")
+    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", SRC, "-o", so])
+    lib = C.CDLL(so)
+    lib.qp_sweep.restype = C.c_long
+    lib.qp_sweep.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_long)]
+    lib.qp_positions.restype = C.c_long
+    lib.qp_keys.argtypes = [C.c_int, C.c_void_p]
+    return lib
+
+
+@pytest.mark.parametrize("log2n", [2, 3, 4, 5, 6])
+@pytest.mark.parametrize("bd", [8, 10])
+def test_levels_and_dequantised_values_equal_the_oracle(quant, log2n, bd):
+    for qidx in QIDX:
+        capped = C.c_long(0)
+        assert quant.qp_sweep(log2n, bd, qidx, C.byref(capped)) == 0, qidx
+        assert capped.value > 0, qidx   # the extremes reach the cap at every step
+
+
+def test_class_key_and_extent_at_every_position(quant):
+    assert quant.qp_positions() == 0
+
+
+@pytest.mark.parametrize("cw", [4, 8, 16, 32])
+def test_scan_key_orders_positions_as_the_oracle_scan(quant, oracle, cw):
+    """positions sorted by key are the oracle's default scan: the largest key among the nonzero levels is the one eob comes from"""
+    keys = np.zeros(cw * cw, np.int32)
+    quant.qp_keys(cw, keys.ctypes.data)
+    L = oracle.lib()
+    L.av1o_default_scan.restype = C.POINTER(C.c_int16)
+    L.av1o_default_scan.argtypes = [C.c_int]
+    scan = np.ctypeslib.as_array(L.av1o_default_scan({4: 2, 8: 3, 16: 4, 32: 5}[cw]), shape=(cw * cw,)).astype(np.int64)
+    assert len(set(keys.tolist())) == cw * cw
+    assert np.array_equal(np.argsort(keys, kind="stable"), scan)
+
+
+def _build_main(cxx, exe, extra):
+    return subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-DQUANT_PIECES_MAIN"] + extra + [SRC, "-o", exe], capture_output=True, text=True)
+
+
+def test_standalone_program(cxx, tmp_path):
+    exe = str(tmp_path / "quant_main")
+    r = _build_main(cxx, exe, [])
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and " 0 mismatches" in out.stdout, out.stdout + out.stderr
+
+
+def test_standalone_program_under_sanitizers(cxx, tmp_path):
+    """... and under AddressSanitizer and UndefinedBehaviorSanitizer (host code only).  Skipped only where an empty program does not
+    build and run under the sanitizers - their runtimes are not installed; a failure of the project's source is a failure"""
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    probe_src, probe = str(tmp_path / "probe.cpp"), str(tmp_path / "probe")
+    open(probe_src, "w").write("int main() { return 0; }\n")
+    p = subprocess.run([cxx] + san + [probe_src, "-o", probe], capture_output=True, text=True)
+    if p.returncode or subprocess.run([probe], capture_output=True).returncode:
+        pytest.skip("the sanitizer runtimes are not installed")
+    exe = str(tmp_path / "quant_main_san")
+    r = _build_main(cxx, exe, san)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert " 0 mismatches" in out.stdout
