@@ -36,7 +36,7 @@ E_INVALID_ARG, E_NO_DEVICE, E_HIP, E_OOM, E_OVERFLOW, E_FORMAT, E_UNSUPPORTED = 
 
 # every symbol include/av1mi.h declares
 ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", "av1mi_last_error", "av1mi_encode_chunk",
-               "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units"]
+               "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units"]
 
 
 class Params(C.Structure):
@@ -117,6 +117,9 @@ _lib.av1mi_lf_search_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_ui
 _lib.av1mi_lr_fit_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint64)]
 _lib.av1mi_lr_fit_units.argtypes = [C.c_void_p]
 _lib.av1mi_lr_fit_units.restype = C.c_uint32
+_lib.av1mi_lr_wiener_fit_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint64)]
+_lib.av1mi_lr_wiener_fit_units.argtypes = [C.c_void_p]
+_lib.av1mi_lr_wiener_fit_units.restype = C.c_uint32
 _lib.av1mi_write_headers.argtypes = [C.POINTER(Params), C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_size_t)]
 
 
@@ -172,13 +175,18 @@ def lr_fit_field(lr, sets=0):
     return (lr & 0xFF) | 0x100 | ((sets & 0xFFFF) << 16)
 
 
-def default_params(width, height, bit_depth=8, aq_strength=None, lr_fit=None, **kw):
+LR_WIENER_FIT = 0x400   # include/av1mi.h: AV1MI_LR_WIENER_FIT
+
+
+def default_params(width, height, bit_depth=8, aq_strength=None, lr_fit=None, lr_wiener_fit=False, **kw):
     """aq_strength: packed into cq_level beside the CQ level (cq_aq); lr_fit: True or a mask of parameter sets, packed into enable_lr
-    (lr_fit_field); every other keyword sets the structure field of its name"""
+    (lr_fit_field); lr_wiener_fit: True sets enable_lr's bit 10 (LR_WIENER_FIT); every other keyword sets the structure field of its name"""
     p = Params()
     _lib.av1mi_default_params(C.byref(p), width, height, bit_depth)
     if lr_fit is not None and lr_fit is not False:
         kw["enable_lr"] = lr_fit_field(kw.get("enable_lr", p.enable_lr), 0 if lr_fit is True else int(lr_fit))
+    if lr_wiener_fit:
+        kw["enable_lr"] = kw.get("enable_lr", p.enable_lr) | LR_WIENER_FIT
     if aq_strength is not None:
         kw["cq_level"] = cq_aq(kw.get("cq_level", p.cq_level), aq_strength)
     for k, v in kw.items():
@@ -329,6 +337,24 @@ class Context:
         err = np.zeros((n_frames, 3, ur, uc, 23), dtype=np.uint64)
         rc = _lib.av1mi_lr_fit_result(self._h, n_frames, units.ctypes.data_as(C.POINTER(C.c_int8)), err.ctypes.data_as(C.POINTER(C.c_uint64)))
         _raise_for(rc, "av1mi_lr_fit_result: the context's last successfully encoded chunk does not have %d frames (or there is none)" % n_frames)
+        return units, err
+
+    def lr_wiener_fit_result(self, n_frames, width=None, height=None):
+        """The Wiener fit of the last encoded chunk (include/av1mi.h: av1mi_lr_wiener_fit_result): numpy arrays
+        units[frame][plane][unit row][unit column][8] (int8: final choice, present, cv0 .. cv2, ch0 .. ch2) and
+        err[frame][plane][unit row][unit column] (uint64); zeros for planes that are not restored and for a chunk without the fit.
+        Sized and shaped as lr_fit_result's."""
+        import numpy as np
+        n_units = int(_lib.av1mi_lr_wiener_fit_units(self._h))
+        if width is None or height is None:
+            width, height = self._last_size if self._last_size is not None else (0, 0)
+        ur, uc = max((height + 32) // 64, 1), max((width + 32) // 64, 1)
+        if n_units == 0 or ur * uc != n_units:
+            _raise_for(E_INVALID_ARG, "av1mi_lr_wiener_fit_result: the last chunk has %d units per plane, not the %d x %d of %d x %d frames" % (n_units, ur, uc, width, height))
+        units = np.zeros((n_frames, 3, ur, uc, 8), dtype=np.int8)
+        err = np.zeros((n_frames, 3, ur, uc), dtype=np.uint64)
+        rc = _lib.av1mi_lr_wiener_fit_result(self._h, n_frames, units.ctypes.data_as(C.POINTER(C.c_int8)), err.ctypes.data_as(C.POINTER(C.c_uint64)))
+        _raise_for(rc, "av1mi_lr_wiener_fit_result: the context's last successfully encoded chunk does not have %d frames (or there is none)" % n_frames)
         return units, err
 
     def encode_chunk(self, params, frames, n_frames, on_device=False, want_recon=False, recon_ptr=None, copy_out=True):

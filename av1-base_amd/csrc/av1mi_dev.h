@@ -118,6 +118,9 @@ struct Av1miDevParams {
   // the self-guided fit (av1mi_params.enable_lr bit 8): null, or per [frame][plane 0..2][unit] the bit string
   // { bits, length } of a self-guided unit, fixed candidates included (lr_fit_kernel.hip); unit choices are then 0 .. 22, 7 + t = set t
   const uint32_t *lr_fit_code;
+  // the Wiener fit (av1mi_params.enable_lr bit 10): null, or per [frame][plane 0..2][unit] the bit string
+  // { bits 0-31, bits 32-63, length } of a Wiener unit, fixed filters included (lr_wfit_kernel.hip); choice 23 is then the fitted filter
+  const uint32_t *lr_wfit_code;
   // packing: null (no counts wanted), or the chunk's record and the [frame][tile] symbol-stream lengths frame_layout_kernel reduces into it
   Av1miChunkRecord *chunk_record;
   const uint32_t *tile_symbols;
@@ -190,6 +193,14 @@ struct Av1miLrFit {
   int8_t *rec;                // [4]: choice, set, xqd0, xqd1
   uint32_t *code;             // [2]: bits, length of a self-guided unit's syntax
   uint32_t mask;              // the sets searched (never 0)
+};
+
+// the Wiener fit's buffers, likewise [frame][plane 0..2][unit] (lr_wfit_kernel.hip)
+struct Av1miLrWfit {
+  unsigned long long *err;    // the fitted filter's exact SSE; ~0 if the candidate is absent
+  int8_t *rec;                // [8]: final choice 0 .. 23, candidate present, cv0, cv1, cv2, ch0, ch1, ch2
+  long long *sums;            // [27] (wiener_fit_rule.h)
+  uint32_t *code;             // [3]: bits 0-31, bits 32-63, length of a Wiener unit's syntax
 };
 
 // ---- which symbolize variant owns a tile (entropy_kernel.hip: the kernels decide per tile, the launcher sizes its grids by it)

@@ -27,6 +27,7 @@
 #include "av1mi_dev.h"
 #include "av1mi_launch.h"
 #include "lr_fit_rule.h"
+#include "wiener_fit_rule.h"
 #include "deblock_pieces.h"
 #include "aq_rule.h"
 
@@ -81,6 +82,7 @@ struct Resolved {
   int lr_chroma;                      // enable_lr 3 / 4: U and V restored as well (p.enable_lr then holds the type: 1 / 2)
   int aq;                             // strength of the adaptive quantisation, 0 = off (p.cq_level then holds the CQ level alone)
   uint32_t lr_fit_mask;               // enable_lr bit 8: the parameter sets the self-guided fit searches, 0 = no fit (p.enable_lr holds the type)
+  int lr_wfit;                        // enable_lr bit 10: the Wiener fit (p.enable_lr holds the type)
 };
 
 // aom's quantizer_to_qindex[] (CQ level -> base_q_idx); 30 -> 120
@@ -114,7 +116,15 @@ int resolve(const av1mi_params *in, Resolved *r) {
   r->qidx = kQuantizerToQindex[p.cq_level];
   r->q = quant_steps(r->qidx, (int)p.bit_depth);
   // enable_lr bit 8 (AV1MI_LR_FIT): the self-guided fit on switchable units, bits 16-31 the sets searched (0 = all); nothing in bits 9-15
+  // bit 10 (AV1MI_LR_WIENER_FIT): the Wiener fit, with any low byte 1 .. 4, alone or with bit 8
   r->lr_fit_mask = 0;
+  r->lr_wfit = 0;
+  if (p.enable_lr & 0x400u) {
+    const uint32_t low = p.enable_lr & 0xFFu;
+    if (low < 1 || low > 4 || (p.enable_lr & 0xFA00u) || (!(p.enable_lr & 0x100u) && (p.enable_lr >> 16))) return AV1MI_E_INVALID_ARG;
+    r->lr_wfit = 1;
+    p.enable_lr &= ~0x400u;
+  }
   if (p.enable_lr & 0x100u) {
     const uint32_t low = p.enable_lr & 0xFFu;
     if ((p.enable_lr & 0xFE00u) || (low != 2 && low != 4)) return AV1MI_E_INVALID_ARG;
@@ -474,6 +484,9 @@ struct Workspace {
   // into h_fit with one copy, then sums and codes - so that one fill clears a chunk's part
   Av1miLrFit fit = {};
   uint8_t *d_fit = nullptr, *h_fit = nullptr;
+  // the Wiener fit, likewise: errors and records at the head (h_wfit), then sums and codes
+  Av1miLrWfit wfit = {};
+  uint8_t *d_wfit = nullptr, *h_wfit = nullptr;
   unsigned long long *d_cdef_err = nullptr;  // CDEF strength search: per [frame][superblock] the 24 candidates' squared errors
   int8_t *d_cdef_idx = nullptr;              // ... per [frame][superblock] the index into the frame's set (-1: not coded)
   uint8_t *d_cdef_sel = nullptr;             // ... per frame the set: 8 slots of pair indices
@@ -528,6 +541,7 @@ struct av1mi_ctx {
   size_t fit_units = 0;
   uint32_t fit_plane_units = 0;   // the units of one plane of one frame (av1mi_lr_fit_units)
   bool fit_on = false;
+  bool wfit_on = false;           // ... and its Wiener fit (av1mi_lr_wiener_fit_result): the head of ws.h_wfit
 };
 
 namespace {
@@ -569,6 +583,7 @@ size_t fit_chunk_units(const Resolved &r, size_t n_frames) {
   return n_frames * 3 * ur * uc;
 }
 size_t fit_bytes(size_t units) { return units * (AV1MI_LR_FIT_CANDS * 8 + 4 + AV1MI_LR_FIT_SETS * 5 * 8 + 8) + 8; }
+size_t wfit_bytes(size_t units) { return units * (8 + 8 + AV1MI_LR_WFIT_SUMS * 8 + 12); }   // error, record, sums, code
 
 int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   const av1mi_params &p = r.p;
@@ -661,6 +676,18 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     w.fit.code = reinterpret_cast<uint32_t *>(w.fit.sums + n * AV1MI_LR_FIT_SETS * 5);
   }
   w.fit.mask = r.lr_fit_mask;
+  if (r.lr_wfit && (!w.d_wfit || !w.h_wfit)) {
+    const size_t units = 3 * nf * nsb + 64;
+    HIPCHK(c, ws_alloc(w, w.d_wfit, wfit_bytes(units)));
+    HIPCHK(c, ws_alloc(w, w.h_wfit, units * 16, true));
+  }
+  if (r.lr_wfit) {   // this chunk's units, contiguous from the head of the block
+    const size_t n = fit_chunk_units(r, n_frames);
+    w.wfit.err = reinterpret_cast<unsigned long long *>(w.d_wfit);
+    w.wfit.rec = reinterpret_cast<int8_t *>(w.wfit.err + n);
+    w.wfit.sums = reinterpret_cast<long long *>(w.wfit.rec + n * 8);
+    w.wfit.code = reinterpret_cast<uint32_t *>(w.wfit.sums + n * AV1MI_LR_WFIT_SUMS);
+  }
   w.res = r;
   if (p.enable_qm && r.qm_level < 15) {
     // dequantiser step per coefficient position (§7.12.3) and its reciprocal, for the square transform sizes 4..32
@@ -692,7 +719,7 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
 // workspace buffers the kernels find through them.  The header sizes follow with the headers (prepare_chunk).
 Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const uint32_t *part, const Av1miQmEntry *qm, const uint8_t *aq_map,
                           unsigned long long *cdef_err, int8_t *cdef_idx, uint8_t *cdef_sel, unsigned long long *lf_err, uint8_t *lf_sel,
-                          Av1miChunkRecord *record, const uint32_t *tile_symbols, const uint32_t *lr_fit_code) {
+                          Av1miChunkRecord *record, const uint32_t *tile_symbols, const uint32_t *lr_fit_code, const uint32_t *lr_wfit_code) {
   const av1mi_params &p = r.p;
   Av1miDevParams P;
   memset(&P, 0, sizeof(P));
@@ -730,6 +757,7 @@ Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const
   P.enable_lr = (int)p.enable_lr;
   P.lr_chroma = r.lr_chroma;
   P.lr_fit_code = r.lr_fit_mask ? lr_fit_code : nullptr;
+  P.lr_wfit_code = r.lr_wfit ? lr_wfit_code : nullptr;
   P.chunk_record = record; P.tile_symbols = tile_symbols;
   for (int rf = 0; rf < 4; rf++)
     for (int k = 0; k < 3; k++) {
@@ -1011,7 +1039,7 @@ int av1mi_aq_qindex(av1mi_ctx *c, const av1mi_params *params, const void *frames
   HIPCHK(c, hipSetDevice(c->device));
   const int bps = r.p.bit_depth > 8 ? 2 : 1;
   const size_t in_bytes = caller_bytes(r, n_frames), coded_bytes = (size_t)n_frames * r.cw * r.ch * 3 / 2 * bps;
-  const Av1miDevParams P = dev_params(r, n_frames, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  const Av1miDevParams P = dev_params(r, n_frames, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
   hipStream_t s = c->stream;
   void *d_in = nullptr, *d_coded = nullptr;
   uint16_t *d_act = nullptr;
@@ -1071,6 +1099,21 @@ int av1mi_lr_fit_result(const av1mi_ctx *c, uint32_t n_frames, int8_t *units, ui
   } else {
     memset(units, 0, n * 4);
     if (err) memset(err, 0, n * AV1MI_LR_FIT_CANDS * 8);
+  }
+  return AV1MI_OK;
+}
+
+uint32_t av1mi_lr_wiener_fit_units(const av1mi_ctx *c) { return c ? c->fit_plane_units : 0; }
+// The Wiener fit of the context's last chunk, likewise.
+int av1mi_lr_wiener_fit_result(const av1mi_ctx *c, uint32_t n_frames, int8_t *units, uint64_t *err) {
+  if (!c || !units || n_frames == 0 || c->lf_levels.size() != (size_t)n_frames * 4) return AV1MI_E_INVALID_ARG;
+  const size_t n = c->fit_units;
+  if (c->wfit_on) {
+    memcpy(units, c->ws.h_wfit + n * 8, n * 8);
+    if (err) memcpy(err, c->ws.h_wfit, n * 8);
+  } else {
+    memset(units, 0, n * 8);
+    if (err) memset(err, 0, n * 8);
   }
   return AV1MI_OK;
 }
@@ -1141,6 +1184,7 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   if (P.lf_search) HIPCHK(c, hipMemsetAsync(w.d_lf_err, 0, (size_t)n_frames * 3 * AV1MI_LF_CANDS * sizeof(unsigned long long), s));
   // the self-guided fit's sums, errors, records and codes, once per attempt at the chunk
   if (P.lr_fit_code) HIPCHK(c, hipMemsetAsync(w.d_fit, 0, fit_bytes(fit_chunk_units(r, n_frames)), s));
+  if (P.lr_wfit_code) HIPCHK(c, hipMemsetAsync(w.d_wfit, 0, wfit_bytes(fit_chunk_units(r, n_frames)), s));
   HIPCHK(c, hipEventRecord(c->ev[EV_START], s));
   // the caller's frames are used in place if they are on the device at the coded size; a padded chunk arrives in the stage
   if (!frames_on_device) HIPCHK(c, hipMemcpyAsync(r.padded ? w.d_stage : w.d_src, frames, caller_bytes(r, n_frames), hipMemcpyHostToDevice, s));
@@ -1224,6 +1268,7 @@ static int schedule_all_key_lr(av1mi_ctx *c, const void *src, uint32_t n_frames)
   HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, w.d_cd, w.d_blk, nullptr, nullptr, 0, n, s));
   HIPCHK(c, av1mi_launch_lr(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, 1, P.lr_fit_code == nullptr, 0, n, s));
   if (P.lr_fit_code) HIPCHK(c, av1mi_launch_lr_fit(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, &w.fit, 0, n, s));
+  if (P.lr_wfit_code) HIPCHK(c, av1mi_launch_lr_wfit(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, P.lr_fit_code ? &w.fit : nullptr, &w.wfit, 0, n, s));
   const int rc = entropy_code(c, 0, n_frames);
   return rc ? rc : sse_beside_range_coder(c, src);
 }
@@ -1278,6 +1323,7 @@ static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
     HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, cdef_out, w.d_blk, nullptr, nullptr, fi, 1, s));
     if (lr) HIPCHK(c, av1mi_launch_lr(&P, w.d_rec, cdef_out, src, w.d_fin, w.d_lrc, w.d_lrsse, 0, P.lr_fit_code == nullptr, fi, 1, s));
     if (lr && P.lr_fit_code) HIPCHK(c, av1mi_launch_lr_fit(&P, w.d_rec, cdef_out, src, w.d_fin, w.d_lrc, w.d_lrsse, &w.fit, fi, 1, s));
+    if (lr && P.lr_wfit_code) HIPCHK(c, av1mi_launch_lr_wfit(&P, w.d_rec, cdef_out, src, w.d_fin, w.d_lrc, w.d_lrsse, P.lr_fit_code ? &w.fit : nullptr, &w.wfit, fi, 1, s));
     if (f == 0)   // (frame 0 of a chunk is a key frame: its chain kernels are in the queue)
       for (uint32_t g = 1; g < n_frames; g++) {
         if (!av1mi_frame_is_inter(P, (int)g)) continue;
@@ -1358,6 +1404,7 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
   // the self-guided fit's errors and records (av1mi_lr_fit_result), likewise
   const size_t fit_n = (size_t)n_frames * 3 * av1mi_lr_unit_rows(P) * av1mi_lr_unit_cols(P);
   if (e1 == hipSuccess && P.lr_fit_code) e1 = hipMemcpyAsync(w.h_fit, w.d_fit, fit_n * (AV1MI_LR_FIT_CANDS * 8 + 4), hipMemcpyDeviceToHost, s);
+  if (e1 == hipSuccess && P.lr_wfit_code) e1 = hipMemcpyAsync(w.h_wfit, w.d_wfit, fit_n * 16, hipMemcpyDeviceToHost, s);   // (av1mi_lr_wiener_fit_result)
   // the bitstream is on the host once EV_DOWNLOAD_DONE has passed: hand it over to the caller's buffer while the second stream finishes
   if (e1 == hipSuccess && e2 == hipSuccess && dst != host) {
     e1 = hipEventSynchronize(c->ev[EV_DOWNLOAD_DONE]);
@@ -1381,6 +1428,7 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
   }
   c->fit_units = fit_n; c->fit_plane_units = (uint32_t)(av1mi_lr_unit_rows(P) * av1mi_lr_unit_cols(P));
   c->fit_on = P.lr_fit_code != nullptr;   // (the values stay in h_fit until the context's next chunk)
+  c->wfit_on = P.lr_wfit_code != nullptr;
   if (frame_sizes) for (uint32_t f = 0; f < n_frames; f++) frame_sizes[f] = (uint32_t)(foff[f + 1] - foff[f]);
   if (report) {
     memset(report, 0, sizeof(*report));
@@ -1424,7 +1472,7 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
 static int run_chunk(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
                      av1mi_buf *out, uint32_t *frame_sizes, void *recon, av1mi_report *report) {
   out->data = nullptr; out->size = 0;
-  c->lf_levels.clear(); c->lf_errs.clear(); c->fit_units = 0; c->fit_plane_units = 0; c->fit_on = false;
+  c->lf_levels.clear(); c->lf_errs.clear(); c->fit_units = 0; c->fit_plane_units = 0; c->fit_on = false; c->wfit_on = false;
   Resolved r;
   int rc = resolve(params, &r);
   if (rc) { set_err(c, "invalid parameters"); return rc; }
@@ -1433,7 +1481,7 @@ static int run_chunk(av1mi_ctx *c, const av1mi_params *params, const void *frame
   if (rc) return rc;
   Workspace &w = c->ws;
   c->P = dev_params(r, n_frames, c->cap_scale, w.d_part, w.d_qm, w.d_aq_map, w.d_cdef_err, w.d_cdef_idx, w.d_cdef_sel, w.d_lf_err, w.d_lf_sel,
-                     w.d_record, w.d_sym, w.fit.code);
+                     w.d_record, w.d_sym, w.fit.code, w.wfit.code);
   const void *d_src = nullptr;
   rc = prepare_chunk(c, r, frames, n_frames, frames_on_device, &d_src);
   if (rc) return rc;

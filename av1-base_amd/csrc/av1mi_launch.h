@@ -106,6 +106,13 @@ hipError_t av1mi_launch_lr(const Av1miDevParams *P, const void *pre, const void 
 // fit: the chunk-wide buffers, cleared by the caller once per attempt at the chunk; choice gets 0 .. 22
 hipError_t av1mi_launch_lr_fit(const Av1miDevParams *P, const void *pre, const void *cdef, const void *src, void *out, uint8_t *choice,
                                const unsigned long long *unit_sse, const Av1miLrFit *fit, int frame0, int count, hipStream_t stream);
+// the Wiener fit (lr_wfit_kernel.hip), after the decision and application above (av1mi_launch_lr with decide = 1, or av1mi_launch_lr_fit):
+// sums, solve and exact SSE, the override of units the fitted filter improves, and every Wiener unit's code.  sgr_fit: the self-guided
+// fit's buffers when it ran (the winner's error is then its err[choice]), else null (unit_sse[choice]).  wfit: the chunk-wide buffers,
+// cleared by the caller once per attempt at the chunk; choice gets 23 where the fitted filter won
+hipError_t av1mi_launch_lr_wfit(const Av1miDevParams *P, const void *pre, const void *cdef, const void *src, void *out, uint8_t *choice,
+                                const unsigned long long *unit_sse, const Av1miLrFit *sgr_fit, const Av1miLrWfit *wfit, int frame0, int count,
+                                hipStream_t stream);
 // tile_order: n_tiles entries of scratch.  mid: recorded on `stream` after symbolize, or null.  aux != null: the frame-edge tiles'
 // symbolize variant runs there, beside the regular one, between `fork` and `join`
 hipError_t av1mi_launch_entropy(const Av1miDevParams *P, const uint16_t *cdf_init, const int16_t *levels, const Av1miBlkInfo *blk,

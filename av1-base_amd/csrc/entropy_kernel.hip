@@ -728,11 +728,13 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
 #pragma nounroll
       for (int pl = 0; pl < nplanes; pl++) {
         // choice [frame][plane][unit]: 0 = off, 1..3 = Wiener candidate, 4..6 = self-guided candidate (RESTORE_SWITCHABLE frames only)
+        // with the Wiener fit (P.lr_wfit_code) 23 = the unit's fitted Wiener filter
         const int ch = uni(lr_choice[((size_t)f * nplanes + pl) * urows * ucols + sbr * ucols + sbc]);
-        if (P.enable_lr == 2) sym_wide(y, lane, adapt, ch == 0 ? 0 : (ch <= 3 ? 1 : 2), FULL ? CL::RESTORE_SW : CC::RESTORE_SW, 3);
+        const bool wiener = ch <= 3 || (P.lr_wfit_code && ch == 23);
+        if (P.enable_lr == 2) sym_wide(y, lane, adapt, ch == 0 ? 0 : (wiener ? 1 : 2), FULL ? CL::RESTORE_SW : CC::RESTORE_SW, 3);
         else sym_wide(y, lane, adapt, ch != 0, FULL ? CL::USE_WIENER : CC::USE_WIENER, 2);
         const int sh = 2 * pl;
-        if (ch > 3) {
+        if (!wiener) {
           // with the self-guided fit (choices 4 .. 22) the unit's bits are its own, written against the carried RefSgrXqd by
           // lr_fit_kernel.hip: [frame][plane 0..2][unit] { bits, length }
           const uint32_t *fc = P.lr_fit_code ? P.lr_fit_code + (((size_t)f * 3 + pl) * urows * ucols + sbr * ucols + sbc) * 2 : nullptr;
@@ -741,6 +743,13 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
           const unsigned long long bits = fc ? (unsigned long long)(uint32_t)uni((int)fc[0]) : P.sgr_code_bits[rf][ch - 4];
           for (int i = len - 1; i >= 0; i--) emit1(y, lane, ENT_LITERAL((int)((bits >> i) & 1)));
           if (!fc) sgr_prev = (sgr_prev & ~(3 << sh)) | ((ch - 3) << sh);
+        } else if (ch && P.lr_wfit_code) {
+          // every Wiener unit's bits are its own, written against the carried RefLrWiener by lr_wfit_kernel.hip:
+          // [frame][plane 0..2][unit] { bits 0-31, bits 32-63, length }
+          const uint32_t *wc = P.lr_wfit_code + (((size_t)f * 3 + pl) * urows * ucols + sbr * ucols + sbc) * 3;
+          const int len = uni((int)wc[2]);
+          const unsigned long long bits = (unsigned long long)(uint32_t)uni((int)wc[0]) | ((unsigned long long)(uint32_t)uni((int)wc[1]) << 32);
+          for (int i = len - 1; i >= 0; i--) emit1(y, lane, ENT_LITERAL((int)((bits >> i) & 1)));
         } else if (ch) {
           const int rf = (lr_prev >> sh) & 3;
           const int len = pl ? P.lr_code_len_uv[rf][ch - 1] : P.lr_code_len[rf][ch - 1];

@@ -42,6 +42,8 @@ typedef struct av1mi_ctx av1mi_ctx;
 #define AV1MI_AQ_STRENGTH(v) (((uint32_t)(v) >> 8) & 7u)
 /* av1mi_params.enable_lr with the self-guided fit: lr = 2 or 4, sets = a mask over the 16 parameter sets searched (0 = all) */
 #define AV1MI_LR_FIT(lr, sets) ((uint32_t)(lr) | 0x100u | ((uint32_t)(sets) << 16))
+/* av1mi_params.enable_lr bit 10: the Wiener fit, or-ed into a value with a low byte of 1 .. 4 (with or without AV1MI_LR_FIT) */
+#define AV1MI_LR_WIENER_FIT 0x400u
 
 /* Operating point.  Replaces the reference's single constant
  *   SVT_PARAMS = "--crf 8 --preset 3 --film-grain 20 ... --keyint 240 --lookahead 40"
@@ -84,8 +86,13 @@ typedef struct {
                                self-guided filter is fitted per unit - beside the seven candidates above a unit may take any of
                                the 16 parameter sets (bits 16-31: a mask over the sets searched, 0 = all) with the two weights
                                that least squares gives for the unit, the smallest exact SSE winning as before.  Headers are
-                               those of 2 / 4.  Bit 8 with any other low byte, and bits 9-15, are refused with
+                               those of 2 / 4.  Bit 8 with any other low byte, and bits 9 and 11-15, are refused with
                                AV1MI_E_INVALID_ARG.  av1mi_lr_fit_result reports the units' choices;
+                               bit 10 (AV1MI_LR_WIENER_FIT) with a low byte of 1 .. 4, alone or with
+                               bit 8: after the decision above a unit's Wiener filter is fitted by least squares - three vertical
+                               and three horizontal taps (chroma: two and two) - and replaces the unit's winner where its exact
+                               SSE is strictly smaller.  Headers are those of the low byte.  Bit 10 with any other low byte is
+                               refused with AV1MI_E_INVALID_ARG.  av1mi_lr_wiener_fit_result reports the units' final choices;
                                default 0: the decision needs the CDEF output, which serialises CDEF before entropy coding */
   uint32_t tile_sb;         /* tile size in 64x64 superblocks, both ways: 0 = automatic (1; 2 when the frame has more than 64
                                superblock rows or columns, e.g. 8K - AV1 allows at most 64 x 64 tiles), or force 1 / 2 */
@@ -233,6 +240,20 @@ int av1mi_lr_fit_result(const av1mi_ctx *ctx, uint32_t n_frames, int8_t *units, 
 /* n_units of the context's last successfully encoded chunk (0: none): what a caller sizes the two arrays above by -
  * units holds n_frames * 3 * n_units * 4 entries, err n_frames * 3 * n_units * 23 */
 uint32_t av1mi_lr_fit_units(const av1mi_ctx *ctx);
+
+/* ---- Wiener fit of the last chunk ------------------------------------------------------------
+ * With enable_lr bit 10 (AV1MI_LR_WIENER_FIT): per restoration unit of the context's last successfully encoded chunk
+ * units[((f * 3 + plane) * n_units + u) * 8 + 0..7] = { final choice 0..23, fitted candidate present, cv0, cv1, cv2, ch0, ch1, ch2 } -
+ * choice 23 = the fitted Wiener filter with the vertical taps cv and the horizontal taps ch (tap 0 of a chroma filter is 0), any
+ * other value the choice of the decision before the fit (av1mi_lr_fit_result keeps reporting that decision) - and (optional)
+ * err[(f * 3 + plane) * n_units + u] = the fitted candidate's squared error against the source, UINT64_MAX if it is absent (a
+ * singular fit).  n_units and the unit order are av1mi_lr_fit_result's.  Entries are zero for planes that are not restored and for a
+ * chunk without the fit.  The values arrive with the chunk's other small results: the call only copies them.
+ * AV1MI_E_INVALID_ARG if n_frames is not the last chunk's frame count. */
+int av1mi_lr_wiener_fit_result(const av1mi_ctx *ctx, uint32_t n_frames, int8_t *units, uint64_t *err);
+/* n_units of the context's last successfully encoded chunk (0: none): units holds n_frames * 3 * n_units * 8 entries, err
+ * n_frames * 3 * n_units */
+uint32_t av1mi_lr_wiener_fit_units(const av1mi_ctx *ctx);
 
 /* ---- the drop-in for `run_av1an` ---------------------------------------------------------
  * Replaces  pub fn run_av1an(params: &Av1anEncodeParams) -> Result<(), EncodeError>

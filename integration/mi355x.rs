@@ -16,6 +16,8 @@ pub struct Av1miParams {            // include/av1mi.h: av1mi_params
     pub intra_mode_mask: u32, pub film_grain: u32, pub first_frame: u32, pub me_range: u32,
     /// Loop restoration: 0 = off, 1 = Wiener on luma, 2 = off / Wiener / self-guided per luma unit; 3 / 4 = 1 / 2 on all three
     /// planes (a library without chroma restoration refuses 3 and 4 with AV1MI_E_INVALID_ARG).
+    /// Bit 8 with 2 / 4: the self-guided filter fitted per unit (bits 16-31 a mask over the parameter sets, 0 = all); bit 10
+    /// (`AV1MI_LR_WIENER_FIT`) with 1..4, alone or with bit 8: the Wiener taps fitted per unit.  A library without a fit refuses its bit.
     pub enable_lr: u32,
     pub tile_sb: u32,
     /// Deblocking: 0 = off, 1 = one level from the quantiser for all four filters, 2 = the level searched per frame and per plane on
@@ -53,6 +55,8 @@ pub struct Av1miReport {            // fills JobMetrics.{fps, frames_encoded, ps
 }
 // include/av1mi.h: AV1MI_CQ_AQ / AV1MI_CQ_LEVEL / AV1MI_AQ_STRENGTH - cq_level carries the CQ level and the adaptive quantisation's strength
 pub const AV1MI_AQ_MAX_STRENGTH: u32 = 4;
+// include/av1mi.h: AV1MI_LR_WIENER_FIT - or-ed into enable_lr
+pub const AV1MI_LR_WIENER_FIT: u32 = 0x400;
 pub const fn cq_aq(cq: u32, strength: u32) -> u32 { (cq & 0xFF) | ((strength & 7) << 8) }
 pub const fn cq_level_of(v: u32) -> u32 { v & 0xFF }
 pub const fn aq_strength_of(v: u32) -> u32 { (v >> 8) & 7 }

@@ -1,11 +1,13 @@
 #!/usr/bin/env python3
 """Self-guided fit A/B: bench.py's synthclip (1080p x 60, 10-bit) encoded with enable_lr 0 (off), 4 (switchable units on all planes, fixed
 candidates), fit | 4 (the self-guided filter fitted per unit over all 16 parameter sets) and fit | 4 with
-the mask 1 << 9 (set 9 alone: the fixed candidates' set with fitted weights) at the headline point (all key frames, CQ 30), IPPP at
+the mask 1 << 9 (set 9 alone: the fixed candidates' set with fitted weights), and with the Wiener fit (bit 10, item 9e) on 3, on 4 and on
+fit | 4, at the headline point (all key frames, CQ 30), IPPP at
 CQ 30 and the production point (CQ 8).  One JSON line per point and value: frames/s (best of --steps after --warmup, the clip in HBM),
 milliseconds per frame, bytes per frame, PSNR Y / U / V of the reconstruction, the report's stage times and, with the fit, the
 histogram of the units' choices (off / Wiener / fixed / fitted), of the fitted sets and of the fitted weights at their clamps
-(av1mi_lr_fit_result).  It reports what it measures, nothing more."""
+(av1mi_lr_fit_result) and, with the Wiener fit, the units choosing the fitted filter, those of them with a tap at a clamp and with
+different vertical and horizontal taps (av1mi_lr_wiener_fit_result).  It reports what it measures, nothing more."""
 import argparse
 import json
 import os
@@ -23,7 +25,8 @@ POINTS = [
     ("cfg3_1080p_ippp", dict(keyint=240, cq_level=30, intra_mode_mask=0x7)),
     ("production_1080p", dict(keyint=240, cq_level=8, intra_mode_mask=0x7, film_grain=20, subpel=1, enable_qm=1, qm_min=1, qm_max=15)),
 ]
-VALUES = {"0": 0, "4": 4, "fit4": 0x104, "fit4_set9": 0x104 | ((1 << 9) << 16)}
+VALUES = {"0": 0, "3": 3, "4": 4, "fit4": 0x104, "fit4_set9": 0x104 | ((1 << 9) << 16), "wfit3": 0x403, "wfit4": 0x404, "wfit_fit4": 0x504}
+TAPS_MIN, TAPS_MAX = (-5, -23, -17), (10, 8, 46)
 
 
 def fit_hist(units):
@@ -39,13 +42,25 @@ def fit_hist(units):
             "xqd1_at_clamp": int(((both[:, 3] == -32) | (both[:, 3] == 95)).sum())}
 
 
+def wfit_hist(units):
+    """of units[frame][plane][row][column][8] over the restored planes: present candidates, units choosing the fitted Wiener filter,
+    those with a tap at a clamp and those whose vertical and horizontal taps differ"""
+    import numpy as np
+    u = units.reshape(-1, 8).astype(np.int64)
+    won = u[u[:, 0] == 23]
+    lo, hi = np.array(TAPS_MIN * 2), np.array(TAPS_MAX * 2)
+    return {"present": int((u[:, 1] != 0).sum()), "fitted_wiener": int(len(won)),
+            "tap_at_clamp": int(((won[:, 2:] == lo) | (won[:, 2:] == hi)).any(axis=1).sum()),
+            "cv_ne_ch": int((won[:, 2:5] != won[:, 5:8]).any(axis=1).sum())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--frames", type=int, default=60)
     ap.add_argument("--points", default="", help="comma-separated subset of the point names")
-    ap.add_argument("--values", default="0,4,fit4,fit4_set9")
+    ap.add_argument("--values", default="0,4,fit4,fit4_set9,3,wfit3,wfit4,wfit_fit4")
     args = ap.parse_args()
     import torch
     import av1mi
@@ -74,6 +89,8 @@ def main():
                         "ms_recon": round(rep.ms_recon, 3), "ms_entropy": round(rep.ms_entropy, 3)}
                 if VALUES[v] & 0x100:
                     line["fit"] = fit_hist(ctx.lr_fit_result(n)[0])
+                if VALUES[v] & 0x400:
+                    line["wiener_fit"] = wfit_hist(ctx.lr_wiener_fit_result(n)[0])
                 print(json.dumps(line), flush=True)
 
 
