@@ -321,4 +321,48 @@ struct Av1miCdfLayout {
   };
 };
 
+// The wide rows as the regular symbolize variants keep them (entropy_kernel.hip): a regular tile has one luma and one chroma transform
+// size, so the tables the full layout keeps per size - a third of the wide rows - shrink to one slice per plane type: 3.2 instead of
+// 4.9 KB.  PARTITION .. SKIP keep their offsets.  The image depends on the blob and the leaf size alone, so the host builds it once
+// where it makes the blob (av1mi_cdf_compact_build) and uploads it behind the blob, at AT; a tile's wave copies it in 16-byte pieces.
+struct Av1miCdfCompact {
+  typedef Av1miCdfLayout CL;
+  enum {
+    LEAD = CL::TX_SET1,
+    TXSET = LEAD,                        // the luma size's slice of TX_SET1 ([13][8]) or TX_SET2 ([13][6]), if it has one
+    TXB_SKIP = TXSET + 13 * 8,           // [2 plane types][13][3]
+    EOB = TXB_SKIP + 2 * 13 * 3,         // [2][12]: the row (context 0) of the plane type's size
+    EOB_EXTRA = EOB + 2 * 12,            // [2][9][3]
+    DC_SIGN = EOB_EXTRA + 2 * 9 * 3,     // [2][3][3] as in the full layout
+    COEFF_BASE_EOB = DC_SIGN + 18,       // [2][4][4]
+    USE_WIENER = COEFF_BASE_EOB + 2 * 16, RESTORE_SW = USE_WIENER + 3, CFL_SIGN = RESTORE_SW + 4, CFL_ALPHA = CFL_SIGN + 9,
+    DELTA_Q = CFL_ALPHA + 6 * 17,
+    TOTAL = DELTA_Q + 5,
+    WORDS = (TOTAL + 18 + 7) & ~7,       // + 18: whole-row reads by 17 lanes may run past the last row; whole 16-byte pieces
+    AT = (CL::TOTAL + 7) & ~7,           // offset of the image in the uploaded blob (16-byte aligned)
+    BLOB_WORDS = AT + WORDS
+  };
+};
+static_assert(Av1miCdfLayout::COEFF_BASE - Av1miCdfLayout::USE_WIENER == Av1miCdfCompact::TOTAL - Av1miCdfCompact::USE_WIENER, "the trailing tables are copied as one piece");
+// the image (WORDS entries) of the blob `cdf` for leaves of 2^max_bs_log2 samples
+AV1MI_HD inline void av1mi_cdf_compact_build(const uint16_t *cdf, int max_bs_log2, uint16_t *w) {
+  typedef Av1miCdfLayout CL;
+  typedef Av1miCdfCompact CC;
+  const int l2y = max_bs_log2 > 6 ? 6 : max_bs_log2, l2c = l2y - 1 > 5 ? 5 : l2y - 1;
+  for (int i = 0; i < CC::WORDS; i++) w[i] = 0;
+  for (int i = 0; i < CC::LEAD; i++) w[i] = cdf[i];
+  if (l2y <= 3) for (int i = 0; i < 13 * 8; i++) w[CC::TXSET + i] = cdf[CL::TX_SET1 + (l2y - 2) * 13 * 8 + i];
+  else if (l2y == 4) for (int i = 0; i < 13 * 6; i++) w[CC::TXSET + i] = cdf[CL::TX_SET2 + (l2y - 2) * 13 * 6 + i];
+  for (int p = 0; p < 2; p++) {
+    const int l2 = p ? l2c : l2y, txs = l2 - 2, bwl = l2 > 5 ? 5 : l2, msz = 2 * bwl - 4, nsy = 5 + msz;
+    const int eoff = CL::EOB16 + 4 * (msz * 6 + (msz * (msz - 1)) / 2) + (p * 2 + 0) * (nsy + 1);
+    for (int k = 0; k < 39; k++) w[CC::TXB_SKIP + p * 39 + k] = cdf[CL::TXB_SKIP + txs * 39 + k];
+    for (int k = 0; k <= nsy; k++) w[CC::EOB + p * 12 + k] = cdf[eoff + k];
+    for (int k = 0; k < 27; k++) w[CC::EOB_EXTRA + p * 27 + k] = cdf[CL::EOB_EXTRA + (txs * 2 + p) * 27 + k];
+    for (int k = 0; k < 16; k++) w[CC::COEFF_BASE_EOB + p * 16 + k] = cdf[CL::COEFF_BASE_EOB + (txs * 2 + p) * 16 + k];
+  }
+  for (int i = 0; i < 18; i++) w[CC::DC_SIGN + i] = cdf[CL::DC_SIGN + i];
+  for (int i = 0; i < CC::TOTAL - CC::USE_WIENER; i++) w[CC::USE_WIENER + i] = cdf[CL::USE_WIENER + i];
+}
+
 #endif

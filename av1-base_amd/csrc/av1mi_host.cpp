@@ -499,6 +499,7 @@ struct Workspace {
   uint8_t *h_hdr = nullptr; uint16_t *h_cdf = nullptr; Av1miDevParams *h_params = nullptr;
   size_t hdr_bytes = 0;                // bytes of h_hdr that d_hdr is known to hold; 0: unknown (the strength search writes into d_hdr)
   int cdf_qidx = -1;                   // the quantiser index d_cdf was made for (the blob depends on nothing else); -1: none
+  int cdf_bs_log2 = -1;                // ... and the leaf size its compact image behind the blob was made for
   int params_on_device = 0;            // d_params holds the first so many blocks of h_params (1, or AV1MI_AQ_SLOTS with adaptive quantisation)
   Av1miChunkRecord *h_record = nullptr; unsigned long long *h_sse = nullptr;   // d_record and d_sse land here
   size_t out_cap = 0, me64_bytes = 0, h_out_cap = 0;   // bytes of d_out, d_me64, h_out
@@ -609,7 +610,7 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     w.out_cap = nf * (ntile * (slot + 4) + 256);
     HIPCHK(c, ws_alloc(w, w.d_out, w.out_cap));
     HIPCHK(c, ws_alloc(w, w.d_hdr, 256 + nf * 512));
-    HIPCHK(c, ws_alloc(w, w.d_cdf, Av1miCdfLayout::TOTAL * sizeof(uint16_t)));
+    HIPCHK(c, ws_alloc(w, w.d_cdf, Av1miCdfCompact::BLOB_WORDS * sizeof(uint16_t)));   // the blob and its compact image
     HIPCHK(c, ws_alloc(w, w.d_params, AV1MI_AQ_SLOTS * sizeof(Av1miDevParams)));
     for (uint32_t **b : { &w.d_tile_bytes, &w.d_tile_off, &w.d_sym, &w.d_combos }) HIPCHK(c, ws_alloc(w, *b, nf * nsb * 4));
     HIPCHK(c, ws_alloc(w, w.d_streams, nf * ntile * (size_t)tile_stream_cap(r, c->cap_scale) * 4));
@@ -618,7 +619,7 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     HIPCHK(c, ws_alloc(w, w.d_sse, nf * 3 * 8));
     {  // the five small host mirrors share one page-locked block: an allocation of page-locked memory costs far more than they hold
       auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-      const size_t b_hdr = up(256 + nf * 512), b_cdf = up(Av1miCdfLayout::TOTAL * sizeof(uint16_t)), b_par = up(AV1MI_AQ_SLOTS * sizeof(Av1miDevParams)),
+      const size_t b_hdr = up(256 + nf * 512), b_cdf = up(Av1miCdfCompact::BLOB_WORDS * sizeof(uint16_t)), b_par = up(AV1MI_AQ_SLOTS * sizeof(Av1miDevParams)),
                    b_rec = up(sizeof(Av1miChunkRecord) + (nf + 1) * 8), b_sse = up(nf * 3 * 8);
       uint8_t *h = nullptr;
       HIPCHK(c, ws_alloc(w, h, b_hdr + b_cdf + b_par + b_rec + b_sse, true));
@@ -1151,12 +1152,15 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
     HIPCHK(c, hipMemcpyAsync(w.d_hdr, w.h_hdr, blob.size(), hipMemcpyHostToDevice, s));
   }
   w.hdr_bytes = P.cdef_search || P.lf_search ? 0 : blob.size();
-  if (w.cdf_qidx != r.qidx) {
+  if (w.cdf_qidx != r.qidx || w.cdf_bs_log2 != P.max_bs_log2) {
     w.cdf_qidx = -1;
-    const std::vector<uint16_t> cdf = make_cdf_blob(r.qidx);
+    // the blob, and behind it the regular symbolize variants' compact image of it for this leaf size (av1mi_dev.h: Av1miCdfCompact)
+    std::vector<uint16_t> cdf = make_cdf_blob(r.qidx);
+    cdf.resize(Av1miCdfCompact::BLOB_WORDS, 0);
+    av1mi_cdf_compact_build(cdf.data(), P.max_bs_log2, cdf.data() + Av1miCdfCompact::AT);
     memcpy(w.h_cdf, cdf.data(), cdf.size() * 2);
     HIPCHK(c, hipMemcpyAsync(w.d_cdf, w.h_cdf, cdf.size() * 2, hipMemcpyHostToDevice, s));
-    w.cdf_qidx = r.qidx;
+    w.cdf_qidx = r.qidx; w.cdf_bs_log2 = P.max_bs_log2;
   }
   {
     // The recon kernel reads its parameters from device memory.  With adaptive quantisation the block is followed by one copy per

@@ -114,7 +114,8 @@ hipError_t av1mi_launch_lr_wfit(const Av1miDevParams *P, const void *pre, const 
                                 const unsigned long long *unit_sse, const Av1miLrFit *sgr_fit, const Av1miLrWfit *wfit, int frame0, int count,
                                 hipStream_t stream);
 // tile_order: n_tiles entries of scratch.  mid: recorded on `stream` after symbolize, or null.  aux != null: the frame-edge tiles'
-// symbolize variant runs there, beside the regular one, between `fork` and `join`
+// symbolize variant runs there, beside the regular one, between `fork` and `join`.  cdf_init: Av1miCdfCompact::BLOB_WORDS entries, 16-byte
+// aligned - the blob (Av1miCdfLayout) and behind it its compact image for P->max_bs_log2 (av1mi_cdf_compact_build)
 hipError_t av1mi_launch_entropy(const Av1miDevParams *P, const uint16_t *cdf_init, const int16_t *levels, const Av1miBlkInfo *blk,
                                 uint32_t *streams, uint32_t *stream_len, uint32_t *tile_combos, uint8_t *slots, uint32_t *tile_bytes,
                                 const uint8_t *lr_choice, uint32_t *tile_order, int frame0, int count,

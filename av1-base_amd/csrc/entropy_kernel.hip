@@ -28,6 +28,7 @@
 namespace {
 
 typedef Av1miCdfLayout CL;
+typedef unsigned int u4 __attribute__((ext_vector_type(4)));   // a 16-byte piece
 
 // ---- stream entry encoding ------------------------------------------------------------------
 // narrow  : bit31 = 0 | slot (bits 2..10) | symbol (bits 0..1)
@@ -52,23 +53,12 @@ __shared__ InterLds g_inter;
 // The wide rows' layout of the REGULAR variants: a regular tile has one luma and one chroma transform size, so the tables the full
 // layout (Av1miCdfLayout) keeps per size - a third of the wide rows - shrink to one slice per plane type: 3.2 instead of 4.9 KB, which
 // takes the key-frame variant from 5 to 6 waves per SIMD and the inter-frame variant from 4 to 5.  PARTITION .. SKIP keep their offsets.
-struct CC {
-  enum {
-    LEAD = CL::TX_SET1,
-    TXSET = LEAD,                        // the luma size's slice of TX_SET1 ([13][8]) or TX_SET2 ([13][6]), if it has one
-    TXB_SKIP = TXSET + 13 * 8,           // [2 plane types][13][3]
-    EOB = TXB_SKIP + 2 * 13 * 3,         // [2][12]: the row (context 0) of the plane type's size
-    EOB_EXTRA = EOB + 2 * 12,            // [2][9][3]
-    DC_SIGN = EOB_EXTRA + 2 * 9 * 3,     // [2][3][3] as in the full layout
-    COEFF_BASE_EOB = DC_SIGN + 18,       // [2][4][4]
-    USE_WIENER = COEFF_BASE_EOB + 2 * 16, RESTORE_SW = USE_WIENER + 3, CFL_SIGN = RESTORE_SW + 4, CFL_ALPHA = CFL_SIGN + 9,
-    DELTA_Q = CFL_ALPHA + 6 * 17,
-    TOTAL = DELTA_Q + 5
-  };
-};
-static_assert(CL::COEFF_BASE - CL::USE_WIENER == CC::TOTAL - CC::USE_WIENER, "the trailing tables are copied as one piece");
-__shared__ uint16_t g_cdfw_full[CL::COEFF_BASE + 18];   // wide rows; + 18: whole-row reads by 17 lanes may run past the last row
-__shared__ uint16_t g_cdfw_compact[CC::TOTAL + 18];
+// The layout and its image are av1mi_dev.h's (Av1miCdfCompact): built once by the host behind the CDF blob, copied here per tile (gathered
+// per wave from the blob - 2-byte loads at divided and remaindered indices, ten round trips one after the other - it was the same work
+// 30 600 times a chunk).
+typedef Av1miCdfCompact CC;
+alignas(16) __shared__ uint16_t g_cdfw_full[(CL::COEFF_BASE + 18 + 7) & ~7];   // wide rows; + 18: whole-row reads by 17 lanes may run past the last row
+alignas(16) __shared__ uint16_t g_cdfw_compact[CC::WORDS];
 struct SymLds {
   alignas(16) int16_t lv[32 * 32];
   uint8_t left_lvl[3][16], left_dc[3][16];   // per superblock row of the tile
@@ -79,7 +69,7 @@ __shared__ SymLds g_sym;
 // above contexts; only the two-superblock instantiations reference (and allocate) the larger object
 template <int TSB>
 struct TileLds {
-  Av1miBlkInfo info[64 * TSB * TSB];
+  alignas(16) Av1miBlkInfo info[64 * TSB * TSB];   // (copied in as 16-byte records)
   uint8_t above_lvl[3][16 * TSB], above_dc[3][16 * TSB];
 };
 __shared__ TileLds<1> g_tile1;
@@ -107,6 +97,16 @@ __device__ __forceinline__ int floor_log2(unsigned v) { return 31 - __builtin_cl
 __device__ __forceinline__ void emit1(Sym &y, int lane, uint32_t ent) {
   if (lane == 0 && y.pos < y.cap) y.out[y.pos] = ent;
   y.pos++;
+}
+// A run of `len` <= 64 literal bits, most significant first, with one store: lane i writes bit len - 1 - i at pos + i.  Entries at or
+// beyond the capacity are not written; pos keeps counting, so stream_len > stream_cap still reports the overflow.
+__device__ __forceinline__ void emit_bits(Sym &y, int lane, unsigned long long bits, int len) {
+  if (lane < len && y.pos + lane < y.cap) y.out[y.pos + lane] = ENT_LITERAL((int)((bits >> ((len - 1 - lane) & 63)) & 1));
+  y.pos += len;
+}
+__device__ __forceinline__ void emit_bits(Sym &y, int lane, unsigned bits, int len) {   // len <= 32
+  if (lane < len && y.pos + lane < y.cap) y.out[y.pos + lane] = ENT_LITERAL((int)((bits >> ((len - 1 - lane) & 31)) & 1));
+  y.pos += len;
 }
 
 // Wide-alphabet / rare symbol: adapt the n-symbol row at LDS offset `off` cooperatively (lane j =
@@ -230,7 +230,6 @@ __device__ __forceinline__ void sym_coeffs(Sym &y, const int lane, const int ada
   // the block's levels, 16 bytes (8 levels) per lane and step: requested here, needed only after the block's first symbols (by then
   // they have arrived - issued where they are copied to LDS the wave waited a memory round trip per transform block); unconditional,
   // index clamped (a load under a condition is waited for on the spot)
-  typedef unsigned int u4 __attribute__((ext_vector_type(4)));
   u4 lv_pre[2];
   {
     const u4 *g128 = reinterpret_cast<const u4 *>(lv_global);
@@ -284,7 +283,7 @@ __device__ __forceinline__ void sym_coeffs(Sym &y, const int lane, const int ada
       if (eob_pt >= 3) {
         const int nbits = eob_pt - 2;
         sym_wide(y, lane, adapt, (extra >> (nbits - 1)) & 1, FULL ? CL::EOB_EXTRA + ((txs * 2 + ptype) * 9 + (eob_pt - 3)) * 3 : CC::EOB_EXTRA + (ptype * 9 + (eob_pt - 3)) * 3, 2);
-        for (int i = 1; i < nbits; i++) emit1(y, lane, ENT_LITERAL((extra >> (nbits - 1 - i)) & 1));
+        emit_bits(y, lane, (unsigned)extra, nbits - 1);   // the bits behind the first are literals
       }
     }
 #define scan(i_) scan_pos((i_), bwl)
@@ -340,11 +339,18 @@ __device__ __forceinline__ void sym_coeffs(Sym &y, const int lane, const int ada
         if (c >= 0 && y.pos + off + cnt <= y.cap) {
           uint32_t *o = y.out + y.pos + off;
           if (c != eob - 1) *o++ = ENT_NARROW(slot0 + cb, imin(level, 3));
-          if (level > 2) {
-            for (int idx = 0; idx < 4; idx++) {
-              const int k3 = imin(level - 3 - idx * 3, 3);
-              *o++ = ENT_NARROW(slot0 + 42 + cbr, k3);
-              if (k3 < 3) break;
+          // the range symbols: nbr = cnt less the base symbol of them, known since the prefix sum - predicated stores, no loop (as a
+          // loop with a break it ran divergent, as often as the wave's largest level asked)
+          const int nbr = cnt - (c != eob - 1);
+          const uint32_t br = ENT_NARROW(slot0 + 42 + cbr, 0);
+          if (nbr > 0) {
+            o[0] = br | (uint32_t)imin(level - 3, 3);
+            if (nbr > 1) {
+              o[1] = br | (uint32_t)imin(level - 6, 3);
+              if (nbr > 2) {
+                o[2] = br | (uint32_t)imin(level - 9, 3);
+                if (nbr > 3) o[3] = br | (uint32_t)imin(level - 12, 3);
+              }
             }
           }
         }
@@ -427,8 +433,7 @@ __device__ __forceinline__ void sym_coeffs(Sym &y, const int lane, const int ada
           if (l0 > 14) {  // its golomb tail (rare) right behind it
             const unsigned g = (unsigned)(l0 - 15) + 1;
             const int len = floor_log2(g) + 1;
-            for (int k = 0; k < len - 1; k++) emit1(y, lane, ENT_LITERAL(0));
-            for (int k = len - 1; k >= 0; k--) emit1(y, lane, ENT_LITERAL((g >> k) & 1));
+            emit_bits(y, lane, g, 2 * len - 1);   // len - 1 zeros, then g's len bits
           }
         }
       }
@@ -639,26 +644,13 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
   // of a variant's tiles; this test decides)
   if (av1mi_tile_is_regular(P, f, tr, tc, TSB) == FULL) return;
   if constexpr (FULL) {
-    for (int i = lane; i < CL::COEFF_BASE; i += 64) g_cdfw_full[i] = cdf_init[i];
+    // whole 16-byte pieces, then the last entries one by one
+    for (int i = lane; i < CL::COEFF_BASE / 8; i += 64) reinterpret_cast<u4 *>(g_cdfw_full)[i] = reinterpret_cast<const u4 *>(cdf_init)[i];
+    if (lane < CL::COEFF_BASE % 8) g_cdfw_full[(CL::COEFF_BASE & ~7) + lane] = cdf_init[(CL::COEFF_BASE & ~7) + lane];
     if (lane < 18) g_cdfw_full[CL::COEFF_BASE + lane] = 0;
   } else {
-    // the compact layout (struct CC): the tile's leaves have one size, so one luma and one chroma transform size
-    const int l2y = P.max_bs_log2 > 6 ? 6 : P.max_bs_log2, l2c = l2y - 1 > 5 ? 5 : l2y - 1;
-    uint16_t *const w = g_cdfw_compact;
-    for (int i = lane; i < CC::LEAD; i += 64) w[i] = cdf_init[i];
-    for (int i = lane; i < 13 * 8; i += 64)
-      w[CC::TXSET + i] = l2y <= 3 ? cdf_init[CL::TX_SET1 + (l2y - 2) * 13 * 8 + i] : ((l2y == 4 && i < 13 * 6) ? cdf_init[CL::TX_SET2 + (l2y - 2) * 13 * 6 + i] : (uint16_t)0);
-    for (int i = lane; i < 2 * 39; i += 64) { const int p = i / 39, txs = (p ? l2c : l2y) - 2; w[CC::TXB_SKIP + i] = cdf_init[CL::TXB_SKIP + txs * 39 + i % 39]; }
-    if (lane < 24) {
-      const int p = lane / 12, k = lane % 12, bwl = (p ? l2c : l2y) > 5 ? 5 : (p ? l2c : l2y), msz = 2 * bwl - 4, nsy = 5 + msz;
-      const int eoff = CL::EOB16 + 4 * (msz * 6 + (msz * (msz - 1)) / 2) + (p * 2 + 0) * (nsy + 1);
-      w[CC::EOB + lane] = k <= nsy ? cdf_init[eoff + k] : (uint16_t)0;
-    }
-    if (lane < 2 * 27) { const int p = lane / 27, txs = (p ? l2c : l2y) - 2; w[CC::EOB_EXTRA + lane] = cdf_init[CL::EOB_EXTRA + (txs * 2 + p) * 27 + lane % 27]; }
-    if (lane < 18) w[CC::DC_SIGN + lane] = cdf_init[CL::DC_SIGN + lane];
-    if (lane < 2 * 16) { const int p = lane / 16, txs = (p ? l2c : l2y) - 2; w[CC::COEFF_BASE_EOB + lane] = cdf_init[CL::COEFF_BASE_EOB + (txs * 2 + p) * 16 + lane % 16]; }
-    for (int i = lane; i < CC::TOTAL - CC::USE_WIENER; i += 64) w[CC::USE_WIENER + i] = cdf_init[CL::USE_WIENER + i];
-    if (lane < 18) w[CC::TOTAL + lane] = 0;
+    // the compact layout's image for this leaf size lies behind the blob (the host built it with the blob: it depends on nothing else)
+    for (int i = lane; i < CC::WORDS / 8; i += 64) reinterpret_cast<u4 *>(g_cdfw_compact)[i] = reinterpret_cast<const u4 *>(cdf_init + CC::AT)[i];
   }
   if (FULL) {
     for (int i = lane; i < CL::INTRA_TOTAL - CL::COEFF_BASE; i += 64) g_cdf_narrow[i] = cdf_init[CL::COEFF_BASE + i];
@@ -673,9 +665,10 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
     const Av1miBlkInfo *finfo = blk + (size_t)f * P.b8_rows * P.b8_cols;
     for (int u = lane; u < 64 * TSB * TSB; u += 64) {
       const int r = tr * TW + u / TW, c = tc * TW + u % TW;
-      Av1miBlkInfo bi = {};
-      if (r < P.b8_rows && c < P.b8_cols) bi = finfo[(size_t)r * P.b8_cols + c];
-      TI.info[u] = bi;
+      // (one 16-byte record as one register quad: copied as a structure it went through scratch memory, the kernel's only use of it)
+      u4 bi = {0u, 0u, 0u, 0u};
+      if (r < P.b8_rows && c < P.b8_cols) bi = *reinterpret_cast<const u4 *>(&finfo[(size_t)r * P.b8_cols + c]);
+      *reinterpret_cast<u4 *>(&TI.info[u]) = bi;
       if (INTER) g_inter.newmv[u] = 0;
     }
     for (int i = lane; i < 3 * 16 * TSB; i += 64) { (&TI.above_lvl[0][0])[i] = 0; (&TI.above_dc[0][0])[i] = 0; }
@@ -741,7 +734,7 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
           const int rf = (sgr_prev >> sh) & 3;
           const int len = fc ? uni((int)fc[1]) : P.sgr_code_len[rf][ch - 4];
           const unsigned long long bits = fc ? (unsigned long long)(uint32_t)uni((int)fc[0]) : P.sgr_code_bits[rf][ch - 4];
-          for (int i = len - 1; i >= 0; i--) emit1(y, lane, ENT_LITERAL((int)((bits >> i) & 1)));
+          emit_bits(y, lane, bits, len);
           if (!fc) sgr_prev = (sgr_prev & ~(3 << sh)) | ((ch - 3) << sh);
         } else if (ch && P.lr_wfit_code) {
           // every Wiener unit's bits are its own, written against the carried RefLrWiener by lr_wfit_kernel.hip:
@@ -749,19 +742,23 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
           const uint32_t *wc = P.lr_wfit_code + (((size_t)f * 3 + pl) * urows * ucols + sbr * ucols + sbc) * 3;
           const int len = uni((int)wc[2]);
           const unsigned long long bits = (unsigned long long)(uint32_t)uni((int)wc[0]) | ((unsigned long long)(uint32_t)uni((int)wc[1]) << 32);
-          for (int i = len - 1; i >= 0; i--) emit1(y, lane, ENT_LITERAL((int)((bits >> i) & 1)));
+          emit_bits(y, lane, bits, len);
         } else if (ch) {
           const int rf = (lr_prev >> sh) & 3;
           const int len = pl ? P.lr_code_len_uv[rf][ch - 1] : P.lr_code_len[rf][ch - 1];
           const unsigned long long bits = pl ? P.lr_code_bits_uv[rf][ch - 1] : P.lr_code_bits[rf][ch - 1];
-          for (int i = len - 1; i >= 0; i--) emit1(y, lane, ENT_LITERAL((int)((bits >> i) & 1)));
+          emit_bits(y, lane, bits, len);
           lr_prev = (lr_prev & ~(3 << sh)) | (ch << sh);
         }
       }
     }
   }
 #pragma nounroll
-  for (int z = 0; z < 64; z++) {
+  // 8x8 units in Z (partition) order, from leaf origin to leaf origin: the 4^(leaf - 3) units of a leaf follow its origin in that
+  // order, so the walk steps over them (as a trip per unit, 60 of the 64 trips of a superblock of 32x32 leaves found nothing to do, at
+  // an LDS round trip each); a unit outside the frame advances by one
+  for (int z = 0, z_next; z < 64; z = z_next) {
+    z_next = z + 1;
     const int bx = (((z >> 0) & 1) | ((z >> 1) & 2) | ((z >> 2) & 4)) << 3;
     const int by = (((z >> 1) & 1) | ((z >> 2) & 2) | ((z >> 3) & 4)) << 3;
     if (tg.sb_y + by >= P.height || tg.sb_x + bx >= P.width) continue;
@@ -769,6 +766,7 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
     // leaf containing this 8x8 unit (written by the recon kernel); it is coded at its origin only
     const int leaf = uni(INFO(b8x, b8y).bsl);
     if ((bx | by) & ((1 << leaf) - 1)) continue;
+    z_next = z + (1 << (2 * (leaf - 3)));
     // nodes whose origin is (bx, by): every level above the leaf down to the leaf, largest first.
     // A node at level l > leaf with this origin contains a smaller leaf, so it is a SPLIT node.
     const int top = imin(6, __builtin_ctz((unsigned)(bx | by | 64)));
@@ -805,7 +803,7 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
         sym_wide(y, lane, adapt, skip, CL::SKIP + sctx * 3, 2);
         if (cdef_todo && !skip) {   // read_cdef (§5.11.56): cdef_bits literal bits, MSB first
           const int ci = uni(P.cdef_idx[(size_t)f * sbs_per_frame + sb]);
-          for (int i = P.cdef_bits - 1; i >= 0; i--) sym_bool(y, lane, (ci >> i) & 1, 16384);
+          emit_bits(y, lane, (unsigned)ci, P.cdef_bits);
           cdef_todo = 0;
         }
         if (dq_todo) {   // read_delta_qindex (§5.11.46): delta_q_present = 1, delta_q_res = 2, i.e. steps of 4
@@ -816,10 +814,9 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
             sym_wide(y, lane, adapt, imin(a, 3), FULL ? CL::DELTA_Q : CC::DELTA_Q, 4);   // delta_q_abs
             if (a >= 3) {   // delta_q_rem_bits L(3), delta_q_abs_bits L(rem_bits + 1)
               const int nb = floor_log2((unsigned)(a - 1)), rest = a - 1 - (1 << nb);
-              for (int i = 2; i >= 0; i--) sym_bool(y, lane, ((nb - 1) >> i) & 1, 16384);
-              for (int i = nb - 1; i >= 0; i--) sym_bool(y, lane, (rest >> i) & 1, 16384);
+              emit_bits(y, lane, (unsigned)(((nb - 1) << nb) | rest), 3 + nb);
             }
-            if (a) sym_bool(y, lane, r < 0, 16384);   // delta_q_sign_bit
+            if (a) emit_bits(y, lane, (unsigned)(r < 0), 1);   // delta_q_sign_bit
             cur_q = qsb;
           }
         }

@@ -1548,12 +1548,17 @@ __device__ __forceinline__ void encode_superblock(const SbCtx &cx, const PIX *fr
   constexpr int WL = SPLIT ? 1 : 0, WC = SPLIT ? 2 : 0;
   const int wv = SPLIT ? uniform_i((int)threadIdx.x >> 6) : 0;
 #pragma nounroll
-  for (int z = 0; z < 64; z++) {  // 8x8 units in Z (partition) order
+  // 8x8 units in Z (partition) order, from leaf origin to leaf origin: a leaf of size 2^bsl covers the 4^(bsl - 3) units that follow
+  // its origin in that order (the ones beyond the frame included), so the walk steps over them; a unit outside the frame that
+  // no leaf covers advances by one
+  for (int z = 0, z_next; z < 64; z = z_next) {
+    z_next = z + 1;
     const int bx = (((z >> 0) & 1) | ((z >> 1) & 2) | ((z >> 2) & 4)) << 3;
     const int by = (((z >> 1) & 1) | ((z >> 2) & 2) | ((z >> 3) & 4)) << 3;
     if (cx.sb_y + by >= P.height || cx.sb_x + bx >= P.width) continue;
     const int bsl = leaf_bsl_at(P, have_mask, mask, cx.sb_x, cx.sb_y, bx, by);
     if (bsl == 0) continue;
+    z_next = z + (1 << (2 * (bsl - 3)));
     const int n = 1 << bsl;
     const int qi = si * 64 + z;
     int mode = 3 << 4;   // (mode | (angle delta + 3) << 4)

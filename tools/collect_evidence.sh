@@ -18,6 +18,7 @@ export AV1MI_BENCH_CLIP_ON_CPU=1
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python3 $B --steps 1 --warmup 0 $common > $out/pmc_fetch.log 2>&1 &&
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- python3 $B --steps 1 --warmup 0 $common > $out/pmc_write.log 2>&1 &&
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --output-format csv -d $out/pmc_sq -- python3 $B --steps 1 --warmup 0 $common > $out/pmc_sq.log 2>&1 &&
+rocprofv3 --kernel-trace --pmc SQ_BUSY_CYCLES SQ_INSTS_SMEM SQ_INSTS_BRANCH SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_FLAT SQ_ACTIVE_INST_SCA SQ_INST_CYCLES_SALU --output-format csv -d $out/pmc_sq2 -- python3 $B --steps 1 --warmup 0 $common > $out/pmc_sq2.log 2>&1 &&
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch_ippp -- python3 $B --steps 1 --warmup 0 $common --keyint 240 --mode-mask 7 > $out/pmc_fetch_ippp.log 2>&1 &&
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/pmc_write_ippp -- python3 $B --steps 1 --warmup 0 $common --keyint 240 --mode-mask 7 > $out/pmc_write_ippp.log 2>&1 &&
 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --output-format csv -d $out/pmc_sq_ippp -- python3 $B --steps 1 --warmup 0 $common --keyint 240 --mode-mask 7 > $out/pmc_sq_ippp.log 2>&1

@@ -59,7 +59,8 @@ def main():
     for what in ("intra", "ippp", "prod"):
         print(stats(tag, what))
     traffic = {}
-    for what, dirs, wl in (("intra", ("pmc_fetch", "pmc_write", "pmc_sq"), "cfg2_1080p_intra"),
+    # (pmc_sq2: a further SQ pass where one was taken - SQ_BUSY_CYCLES, SQ_INSTS_SMEM, SQ_INSTS_BRANCH, the scalar-active counters)
+    for what, dirs, wl in (("intra", ("pmc_fetch", "pmc_write", "pmc_sq", "pmc_sq2"), "cfg2_1080p_intra"),
                            ("ippp", ("pmc_fetch_ippp", "pmc_write_ippp", "pmc_sq_ippp"), "cfg3_1080p_ippp")):
         acc, calls = counters(tag, dirs)
         if not acc:
