@@ -176,17 +176,33 @@ def lr_fit_field(lr, sets=0):
 
 
 LR_WIENER_FIT = 0x400   # include/av1mi.h: AV1MI_LR_WIENER_FIT
+LR_UNIT_128 = 0x1000    # include/av1mi.h: AV1MI_LR_UNIT_128 / AV1MI_LR_UNIT_256 - enable_lr bits 12-13, lr_unit_shift 1 / 2
+LR_UNIT_256 = 0x2000
 
 
-def default_params(width, height, bit_depth=8, aq_strength=None, lr_fit=None, lr_wiener_fit=False, **kw):
+def lr_unit_shift_of(enable_lr):
+    """include/av1mi.h: AV1MI_LR_UNIT_SHIFT - luma restoration units are 64 << shift samples"""
+    return (enable_lr >> 12) & 3
+
+
+def lr_unit_grid(width, height, shift=0):
+    """(unit rows, unit columns) of every plane of a width x height frame at a unit size: count_units_in_frame both ways"""
+    u = 64 << shift
+    return max((height + u // 2) // u, 1), max((width + u // 2) // u, 1)
+
+
+def default_params(width, height, bit_depth=8, aq_strength=None, lr_fit=None, lr_wiener_fit=False, lr_unit_shift=0, **kw):
     """aq_strength: packed into cq_level beside the CQ level (cq_aq); lr_fit: True or a mask of parameter sets, packed into enable_lr
-    (lr_fit_field); lr_wiener_fit: True sets enable_lr's bit 10 (LR_WIENER_FIT); every other keyword sets the structure field of its name"""
+    (lr_fit_field); lr_wiener_fit: True sets enable_lr's bit 10 (LR_WIENER_FIT); lr_unit_shift: 1 / 2 sets enable_lr's bits 12-13
+    (LR_UNIT_128 / LR_UNIT_256); every other keyword sets the structure field of its name"""
     p = Params()
     _lib.av1mi_default_params(C.byref(p), width, height, bit_depth)
     if lr_fit is not None and lr_fit is not False:
         kw["enable_lr"] = lr_fit_field(kw.get("enable_lr", p.enable_lr), 0 if lr_fit is True else int(lr_fit))
     if lr_wiener_fit:
         kw["enable_lr"] = kw.get("enable_lr", p.enable_lr) | LR_WIENER_FIT
+    if lr_unit_shift:
+        kw["enable_lr"] = kw.get("enable_lr", p.enable_lr) | ((int(lr_unit_shift) & 3) << 12)
     if aq_strength is not None:
         kw["cq_level"] = cq_aq(kw.get("cq_level", p.cq_level), aq_strength)
     for k, v in kw.items():
@@ -260,6 +276,7 @@ class Context:
         _raise_for(_lib.av1mi_ctx_create(device_id, C.byref(h)), "av1mi_ctx_create")
         self._h = h
         self._last_size = None   # (width, height) of the last encode_chunk call: lr_fit_result's unit grid
+        self._last_unit_shift = 0   # ... and its lr_unit_shift
 
     def close(self):
         if self._h:
@@ -325,12 +342,12 @@ class Context:
         units[frame][plane][unit row][unit column][4] (int8: choice, set, xqd0, xqd1) and err[frame][plane][unit row][unit column][23]
         (uint64); zeros for planes that are not restored and for a chunk without the fit.  The arrays are sized by the library's own
         unit count (av1mi_lr_fit_units); their shape follows the frame size of this object's last successful encode_chunk call, or
-        width and height, and a size whose unit grid is not the library's is refused."""
+        width and height, at that call's unit size, and a size whose unit grid is not the library's is refused."""
         import numpy as np
         n_units = int(_lib.av1mi_lr_fit_units(self._h))
         if width is None or height is None:
             width, height = self._last_size if self._last_size is not None else (0, 0)
-        ur, uc = max((height + 32) // 64, 1), max((width + 32) // 64, 1)
+        ur, uc = lr_unit_grid(width, height, self._last_unit_shift)
         if n_units == 0 or ur * uc != n_units:
             _raise_for(E_INVALID_ARG, "av1mi_lr_fit_result: the last chunk has %d units per plane, not the %d x %d of %d x %d frames" % (n_units, ur, uc, width, height))
         units = np.zeros((n_frames, 3, ur, uc, 4), dtype=np.int8)
@@ -348,7 +365,7 @@ class Context:
         n_units = int(_lib.av1mi_lr_wiener_fit_units(self._h))
         if width is None or height is None:
             width, height = self._last_size if self._last_size is not None else (0, 0)
-        ur, uc = max((height + 32) // 64, 1), max((width + 32) // 64, 1)
+        ur, uc = lr_unit_grid(width, height, self._last_unit_shift)
         if n_units == 0 or ur * uc != n_units:
             _raise_for(E_INVALID_ARG, "av1mi_lr_wiener_fit_result: the last chunk has %d units per plane, not the %d x %d of %d x %d frames" % (n_units, ur, uc, width, height))
         units = np.zeros((n_frames, 3, ur, uc, 8), dtype=np.int8)
@@ -387,6 +404,7 @@ class Context:
         if rc:
             _raise_for(rc, self.last_error())
         self._last_size = (params.width, params.height)   # of the last chunk that succeeded, as the library's own results are
+        self._last_unit_shift = lr_unit_shift_of(params.enable_lr)
         data = C.string_at(out.data, out.size) if copy_out else None
         _lib.av1mi_free(out.data)
         return data, list(sizes), rep, recon

@@ -4,6 +4,7 @@
 #define AV1MI_DEV_H
 #include <stdint.h>
 #include <stddef.h>
+#include "lr_geometry.h"
 #ifdef __HIPCC__
 #define AV1MI_HD __host__ __device__
 #else
@@ -113,6 +114,8 @@ struct Av1miDevParams {
   // (lr_uv_shift 1); unit choices and sums are then [frame][plane][unit], else [frame][unit].  A chroma Wiener unit codes taps 1
   // and 2 of each pass only (tap 0 is 0): its bit strings, against the plane's RefLrWiener; self-guided units share luma's.
   int lr_chroma;
+  // av1mi_params.enable_lr bits 12-13: luma units of 64 << lr_unit_shift samples, chroma units of half that
+  int lr_unit_shift;
   int lr_code_len_uv[4][3];
   unsigned long long lr_code_bits_uv[4][3];
   // the self-guided fit (av1mi_params.enable_lr bit 8): null, or per [frame][plane 0..2][unit] the bit string
@@ -180,11 +183,22 @@ AV1MI_HD inline void av1mi_me_key_decode(unsigned long long key, int R, int *dy,
 // frame f of a chunk is a key frame iff f % keyint == 0
 AV1MI_HD inline int av1mi_frame_is_inter(const Av1miDevParams &P, int f) { return P.keyint > 1 && (f % P.keyint) != 0; }
 
-// ---- loop restoration: a plane's grid of units, from the signalled size (64x64 luma samples each; the last row / column takes a remainder of
-// less than half a unit), and the units of one frame over its restored planes - the frame stride of the [frame][plane][unit] choices and sums
-AV1MI_HD inline int av1mi_lr_unit_rows(const Av1miDevParams &P) { return (P.true_h + 32) / 64 > 0 ? (P.true_h + 32) / 64 : 1; }
-AV1MI_HD inline int av1mi_lr_unit_cols(const Av1miDevParams &P) { return (P.true_w + 32) / 64 > 0 ? (P.true_w + 32) / 64 : 1; }
+// ---- loop restoration (lr_geometry.h): a plane's grid of units at the chunk's unit size, from the signalled size, and the units of one
+// frame over its restored planes - the frame stride of the [frame][plane][unit] choices and sums.  The cells - the units of shift 0 - are
+// the kernels' work items at every unit size
+AV1MI_HD inline int av1mi_lr_cell_rows(const Av1miDevParams &P) { return av1mi_lr_count(P.true_h, 0); }
+AV1MI_HD inline int av1mi_lr_cell_cols(const Av1miDevParams &P) { return av1mi_lr_count(P.true_w, 0); }
+AV1MI_HD inline int av1mi_lr_unit_rows(const Av1miDevParams &P) { return av1mi_lr_count(P.true_h, P.lr_unit_shift); }
+AV1MI_HD inline int av1mi_lr_unit_cols(const Av1miDevParams &P) { return av1mi_lr_count(P.true_w, P.lr_unit_shift); }
 AV1MI_HD inline int av1mi_lr_frame_units(const Av1miDevParams &P) { return (P.lr_chroma ? 3 : 1) * av1mi_lr_unit_rows(P) * av1mi_lr_unit_cols(P); }
+// the grid of the restoration kernels for `count` frames.  Luma: AV1MI_LR_SLICES waves per cell; chroma: per frame and plane, cell rows x
+// pairs of cell columns, AV1MI_LR_SLICES_C waves each (the signalled size is even, so the chroma grid is the luma one)
+#define AV1MI_LR_SLICES 7
+#define AV1MI_LR_SLICES_C 4
+AV1MI_HD inline int av1mi_lr_grid(const Av1miDevParams &P, int count) {
+  const int crows = av1mi_lr_cell_rows(P), ccols = av1mi_lr_cell_cols(P);
+  return count * crows * ccols * AV1MI_LR_SLICES + (P.lr_chroma ? count * 2 * crows * ((ccols + 1) / 2) * AV1MI_LR_SLICES_C : 0);
+}
 
 // the self-guided fit's buffers, all [frame][plane 0..2][unit] whichever planes are restored (lr_fit_kernel.hip)
 struct Av1miLrFit {

@@ -83,6 +83,7 @@ struct Resolved {
   int aq;                             // strength of the adaptive quantisation, 0 = off (p.cq_level then holds the CQ level alone)
   uint32_t lr_fit_mask;               // enable_lr bit 8: the parameter sets the self-guided fit searches, 0 = no fit (p.enable_lr holds the type)
   int lr_wfit;                        // enable_lr bit 10: the Wiener fit (p.enable_lr holds the type)
+  int lr_unit_shift;                  // enable_lr bits 12-13: luma restoration units of 64 << lr_unit_shift samples (0 .. 2)
 };
 
 // aom's quantizer_to_qindex[] (CQ level -> base_q_idx); 30 -> 120
@@ -115,7 +116,14 @@ int resolve(const av1mi_params *in, Resolved *r) {
   if (p.deblock > 2) return AV1MI_E_INVALID_ARG;
   r->qidx = kQuantizerToQindex[p.cq_level];
   r->q = quant_steps(r->qidx, (int)p.bit_depth);
-  // enable_lr bit 8 (AV1MI_LR_FIT): the self-guided fit on switchable units, bits 16-31 the sets searched (0 = all); nothing in bits 9-15
+  // enable_lr bits 12-13 (AV1MI_LR_UNIT_128 / _256): the unit size, with any low byte 1 .. 4 and either fit; 3 is no size
+  r->lr_unit_shift = (int)((p.enable_lr >> 12) & 3u);
+  if (r->lr_unit_shift) {
+    const uint32_t low = p.enable_lr & 0xFFu;
+    if (r->lr_unit_shift > AV1MI_LR_MAX_UNIT_SHIFT || low < 1 || low > 4) return AV1MI_E_INVALID_ARG;
+    p.enable_lr &= ~0x3000u;
+  }
+  // enable_lr bit 8 (AV1MI_LR_FIT): the self-guided fit on switchable units, bits 16-31 the sets searched (0 = all); nothing else in bits 9-15
   // bit 10 (AV1MI_LR_WIENER_FIT): the Wiener fit, with any low byte 1 .. 4, alone or with bit 8
   r->lr_fit_mask = 0;
   r->lr_wfit = 0;
@@ -312,11 +320,13 @@ std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint
       b.put(p.cdef_uv_pri, 4); b.put(p.cdef_uv_sec, 2);
     }
   }
-  if (p.enable_lr) {  // lr_params (§5.9.20): lr_type per plane, lr_unit_shift 0 = 64x64 luma units
+  if (p.enable_lr) {  // lr_params (§5.9.20): lr_type per plane, then the unit size: lr_unit_shift 0 = 64x64 luma units, 1 = 128x128 or,
+                      // with lr_unit_extra_shift, 256x256
     const uint32_t t = p.enable_lr == 2 ? 1 : 2;  // lr_type: 1 = RESTORE_SWITCHABLE, 2 = RESTORE_WIENER
     b.put(t, 2); b.put(r.lr_chroma ? t : 0, 2); b.put(r.lr_chroma ? t : 0, 2);  // Y, U, V: chroma the luma type with enable_lr 3 / 4
-    b.put(0, 1);
-    if (r.lr_chroma) b.put(1, 1);  // lr_uv_shift: 32x32 chroma units, the picture area of a luma unit
+    b.put(r.lr_unit_shift > 0 ? 1 : 0, 1);                          // lr_unit_shift (the superblocks are 64x64)
+    if (r.lr_unit_shift) b.put(r.lr_unit_shift == 2 ? 1 : 0, 1);    // lr_unit_extra_shift
+    if (r.lr_chroma) b.put(1, 1);  // lr_uv_shift: chroma units of half the luma size, the picture area of a luma unit
   }
   b.put(0, 1);  // tx_mode_select = 0: TX_MODE_LARGEST
   if (inter) b.put(0, 1);  // reference_select = 0
@@ -580,8 +590,7 @@ int tile_stream_cap(const Resolved &r, int scale) { return 8192 * scale * r.tile
 
 // the self-guided fit's units of a chunk - its frames' restoration units over three planes - and the bytes of their block
 size_t fit_chunk_units(const Resolved &r, size_t n_frames) {
-  const size_t ur = (r.p.height + 32) / 64 > 0 ? (r.p.height + 32) / 64 : 1, uc = (r.p.width + 32) / 64 > 0 ? (r.p.width + 32) / 64 : 1;
-  return n_frames * 3 * ur * uc;
+  return n_frames * 3 * (size_t)av1mi_lr_count((int)r.p.height, r.lr_unit_shift) * (size_t)av1mi_lr_count((int)r.p.width, r.lr_unit_shift);
 }
 size_t fit_bytes(size_t units) { return units * (AV1MI_LR_FIT_CANDS * 8 + 4 + AV1MI_LR_FIT_SETS * 5 * 8 + 8) + 8; }
 size_t wfit_bytes(size_t units) { return units * (8 + 8 + AV1MI_LR_WFIT_SUMS * 8 + 12); }   // error, record, sums, code
@@ -658,8 +667,8 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     w.d_lf_sel = reinterpret_cast<uint8_t *>(w.d_lf_err + nf * 3 * AV1MI_LF_CANDS);
     HIPCHK(c, ws_alloc(w, w.h_lf, nf * (3 * AV1MI_LF_CANDS * sizeof(unsigned long long) + 4), true));
   }
-  if (p.enable_lr && !w.d_cd) {   // unit choices and sums for three planes (enable_lr 3 / 4), whichever value this chunk has: the
-                                  // buffers stay with the geometry while enable_lr changes
+  if (p.enable_lr && !w.d_cd) {   // unit choices and sums for three planes (enable_lr 3 / 4) of 64x64 units, whichever value and unit size
+                                  // this chunk has: the buffers stay with the geometry while enable_lr changes
     HIPCHK(c, ws_alloc(w, w.d_cd, nf * frame_bytes));
     HIPCHK(c, ws_alloc(w, w.d_lrc, 3 * nf * nsb + 64));
     HIPCHK(c, ws_alloc(w, w.d_lrsse, (3 * nf * nsb + 64) * 8 * sizeof(unsigned long long)));
@@ -757,6 +766,7 @@ Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const
   }
   P.enable_lr = (int)p.enable_lr;
   P.lr_chroma = r.lr_chroma;
+  P.lr_unit_shift = r.lr_unit_shift;
   P.lr_fit_code = r.lr_fit_mask ? lr_fit_code : nullptr;
   P.lr_wfit_code = r.lr_wfit ? lr_wfit_code : nullptr;
   P.chunk_record = record; P.tile_symbols = tile_symbols;

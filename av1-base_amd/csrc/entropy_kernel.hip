@@ -711,18 +711,21 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
 
   if (P.enable_lr) {
     // read_lr (§5.11.57): the restoration units whose origin lies in this superblock, Y and (enable_lr 3 / 4) U, V.  Luma units are
-    // 64x64 offset by 8 rows, chroma units 32x32 offset by 4 (lr_uv_shift 1), so unit (r, c) of every plane starts in superblock
-    // (r, c), and the signalled size being even every plane has the same unit grid.  The coefficients are coded against the plane's
+    // 64 << lr_unit_shift samples offset by 8 rows, chroma units half that offset by 4 (lr_uv_shift 1), so unit (r, c) of every plane
+    // starts in superblock (r << lr_unit_shift, c << lr_unit_shift) - the other superblocks, and those past the last unit (264 rows:
+    // five superblock rows, two units of 128), read none - and the signalled size being even every plane has the same unit grid
+    // (lr_geometry.h).  The coefficients are coded against the plane's
     // RefLrWiener / RefSgrXqd, which start every tile at their mid values and follow the plane's units coded with a filter; the
     // three CDFs are shared by the planes
-    const int urows = imax((P.true_h + 32) / 64, 1), ucols = imax((P.true_w + 32) / 64, 1);  // from the signalled size
-    if (sbr < urows && sbc < ucols) {
+    const int urows = av1mi_lr_unit_rows(P), ucols = av1mi_lr_unit_cols(P);  // from the signalled size
+    const int ur = av1mi_lr_sb_unit(sbr, urows, P.lr_unit_shift), uc = av1mi_lr_sb_unit(sbc, ucols, P.lr_unit_shift);
+    if (ur >= 0 && uc >= 0) {
       const int nplanes = P.lr_chroma ? 3 : 1;
 #pragma nounroll
       for (int pl = 0; pl < nplanes; pl++) {
         // choice [frame][plane][unit]: 0 = off, 1..3 = Wiener candidate, 4..6 = self-guided candidate (RESTORE_SWITCHABLE frames only)
         // with the Wiener fit (P.lr_wfit_code) 23 = the unit's fitted Wiener filter
-        const int ch = uni(lr_choice[((size_t)f * nplanes + pl) * urows * ucols + sbr * ucols + sbc]);
+        const int ch = uni(lr_choice[((size_t)f * nplanes + pl) * urows * ucols + ur * ucols + uc]);
         const bool wiener = ch <= 3 || (P.lr_wfit_code && ch == 23);
         if (P.enable_lr == 2) sym_wide(y, lane, adapt, ch == 0 ? 0 : (wiener ? 1 : 2), FULL ? CL::RESTORE_SW : CC::RESTORE_SW, 3);
         else sym_wide(y, lane, adapt, ch != 0, FULL ? CL::USE_WIENER : CC::USE_WIENER, 2);
@@ -730,7 +733,7 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
         if (!wiener) {
           // with the self-guided fit (choices 4 .. 22) the unit's bits are its own, written against the carried RefSgrXqd by
           // lr_fit_kernel.hip: [frame][plane 0..2][unit] { bits, length }
-          const uint32_t *fc = P.lr_fit_code ? P.lr_fit_code + (((size_t)f * 3 + pl) * urows * ucols + sbr * ucols + sbc) * 2 : nullptr;
+          const uint32_t *fc = P.lr_fit_code ? P.lr_fit_code + (((size_t)f * 3 + pl) * urows * ucols + ur * ucols + uc) * 2 : nullptr;
           const int rf = (sgr_prev >> sh) & 3;
           const int len = fc ? uni((int)fc[1]) : P.sgr_code_len[rf][ch - 4];
           const unsigned long long bits = fc ? (unsigned long long)(uint32_t)uni((int)fc[0]) : P.sgr_code_bits[rf][ch - 4];
@@ -739,7 +742,7 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
         } else if (ch && P.lr_wfit_code) {
           // every Wiener unit's bits are its own, written against the carried RefLrWiener by lr_wfit_kernel.hip:
           // [frame][plane 0..2][unit] { bits 0-31, bits 32-63, length }
-          const uint32_t *wc = P.lr_wfit_code + (((size_t)f * 3 + pl) * urows * ucols + sbr * ucols + sbc) * 3;
+          const uint32_t *wc = P.lr_wfit_code + (((size_t)f * 3 + pl) * urows * ucols + ur * ucols + uc) * 3;
           const int len = uni((int)wc[2]);
           const unsigned long long bits = (unsigned long long)(uint32_t)uni((int)wc[0]) | ((unsigned long long)(uint32_t)uni((int)wc[1]) << 32);
           emit_bits(y, lane, bits, len);

@@ -9,6 +9,7 @@
 // same grid, window and grids in LDS (17 KB per wave + a 128-byte table of the units' weights).  Four launches after lr_kernel.hip's
 // phase 0 (the SSE of the seven fixed candidates):
 //   1 sums    per set the A / B grids with the set's strengths, the five sums per lane, reduced per unit, one 64-bit atomic per sum
+//             (14-bit terms; a unit of 256 luma samples has at most 383 x 391 of them: |sum| < 2^46)
 //   2 SSE     every slice solves its units' weights from the complete sums (32 lanes, one (unit, set) each), filters again and adds
 //             its exact SSE per set
 //   3 decide  first minimum over the 23 candidates, the unit's record, and the winner of any kind applied (with the padding and,
@@ -143,28 +144,31 @@ template <typename PIX, int PHASE>
 __global__ void __launch_bounds__(64) lr_fit_kernel(Av1miDevParams P, const PIX *__restrict__ pre, const PIX *__restrict__ cdef,
                                                    const PIX *__restrict__ src, PIX *__restrict__ out, uint8_t *__restrict__ choice,
                                                    const unsigned long long *__restrict__ unit_sse, Av1miLrFit F) {
-  const int urows = av1mi_lr_unit_rows(P), ucols = av1mi_lr_unit_cols(P), per = urows * ucols;
+  // the blocks are those of the cells (the units of lr_unit_shift 0); sums, weights, errors and records are those of the unit a cell lies in
+  const int crows = av1mi_lr_cell_rows(P), ccols = av1mi_lr_cell_cols(P), cells = crows * ccols;
+  const int ush = P.lr_unit_shift, urows = av1mi_lr_unit_rows(P), ucols = av1mi_lr_unit_cols(P), per = urows * ucols;
   const int lane = threadIdx.x;
-  const int luma_blocks = P.n_frames * per * LR_SLICES;
-  int f, pl, ur, slice, x0, x1, ucl, last_col;
+  const int luma_blocks = P.n_frames * cells * LR_SLICES;
+  int f, pl, cr, slice, x0, x1, ccl, last_col;
   if ((int)blockIdx.x < luma_blocks) {
-    const int item = blockIdx.x / LR_SLICES, u = item % per;
-    slice = blockIdx.x % LR_SLICES; f = item / per; pl = 0; ur = u / ucols; ucl = u % ucols;
-    x0 = ucl * 64; last_col = ucl == ucols - 1; x1 = last_col ? P.true_w : x0 + 64;
+    const int item = blockIdx.x / LR_SLICES, cell = item % cells;
+    slice = blockIdx.x % LR_SLICES; f = item / cells; pl = 0; cr = cell / ccols; ccl = cell % ccols;
+    x0 = ccl * 64; last_col = ccl == ccols - 1; x1 = last_col ? P.true_w : x0 + 64;
   } else {
     if (!P.lr_chroma) return;
-    const int item = (int)blockIdx.x - luma_blocks, pairs = (ucols + 1) >> 1, rest = item / LR_SLICES_C;
+    const int item = (int)blockIdx.x - luma_blocks, pairs = (ccols + 1) >> 1, rest = item / LR_SLICES_C;
     const int pc = rest % pairs;
-    slice = item % LR_SLICES_C; ur = rest / pairs % urows; pl = 1 + rest / (pairs * urows) % 2; f = rest / (pairs * urows * 2); ucl = -1;
+    slice = item % LR_SLICES_C; cr = rest / pairs % crows; pl = 1 + rest / (pairs * crows) % 2; f = rest / (pairs * crows * 2); ccl = -1;
     if (f >= P.n_frames) return;
     x0 = pc * 64; last_col = pc == pairs - 1; x1 = last_col ? (P.true_w + 1) >> 1 : x0 + 64;
   }
+  const int ur = av1mi_lr_unit_of_cell(cr, urows, ush);
   const int sub = pl > 0;
   const int W = sub ? (P.true_w + 1) >> 1 : P.true_w, H = sub ? (P.true_h + 1) >> 1 : P.true_h, stride = sub ? P.stride_c : P.stride_y;
-  const int sh = 64 >> sub, so = 8 >> sub;   // stripe height = unit size, and the row offset of both
+  const int sh = 64 >> sub, so = 8 >> sub;   // stripe height = cell size, and the row offset of both
   const size_t fo = (size_t)f * P.frame_samples + (pl == 0 ? 0 : (pl == 1 ? P.plane_off_u : P.plane_off_v));
   pre += fo; cdef += fo; src += fo; out += fo;
-  const int uy0 = ur ? ur * sh - so : 0, uy1 = ur == urows - 1 ? H : ur * sh + sh - so;
+  const int uy0 = av1mi_lr_row0(cr, 0, sub), uy1 = av1mi_lr_row1(cr, crows, 0, sub, H);   // the cell row's rows
   const int y0 = uy0 + slice * 16, y1 = y0 + 16 < uy1 ? y0 + 16 : uy1;
   if (y0 >= uy1) return;
   const int maxv = (1 << P.bit_depth) - 1, bd = P.bit_depth;
@@ -173,8 +177,10 @@ __global__ void __launch_bounds__(64) lr_fit_kernel(Av1miDevParams P, const PIX 
   for (int xs = x0; xs < x1; xs += 64) {
     const int x = xs + lane;
     const bool active = x < x1;
-    // the section's units: lanes 0-31 are in `lo`, lanes 32-63 in `hi` (luma, and a last chroma unit on its own: one unit)
-    const int lo = ucl >= 0 ? ucl : min(ucols - 1, xs >> 5), hi = ucl >= 0 ? ucl : min(ucols - 1, (xs >> 5) + 1);
+    // the section's units: lanes 0-31 are in `lo`, lanes 32-63 in `hi` (one unit: luma, a last chroma cell on its own, and two chroma
+    // cells of one larger unit)
+    const int lo = av1mi_lr_unit_of_cell(ccl >= 0 ? ccl : min(ccols - 1, xs >> 5), ucols, ush);
+    const int hi = av1mi_lr_unit_of_cell(ccl >= 0 ? ccl : min(ccols - 1, (xs >> 5) + 1), ucols, ush);
     const int hsel = lo != hi ? lane >> 5 : 0, unit = hsel ? hi : lo;
     if constexpr (PHASE >= 2) {
       // the weights of both units and every set from the complete sums
@@ -202,8 +208,8 @@ __global__ void __launch_bounds__(64) lr_fit_kernel(Av1miDevParams P, const PIX 
         if (best[h] >= 7) { const int w = g_fitw[h][best[h] - 7]; bset[h] = best[h] - 7; bw0[h] = (w & 255) - 128; bw1[h] = ((w >> 8) & 255) - 128; }
         else if (best[h] >= 4) { bset[h] = c_sgr_cand[best[h] - 4][0]; bw0[h] = c_sgr_cand[best[h] - 4][1]; bw1[h] = c_sgr_cand[best[h] - 4][2]; }
       }
-      // the unit's record, by the lane of its first column in the unit's first slice
-      if (slice == 0 && active && x == (ucl >= 0 ? ucl * 64 : unit * 32)) {
+      // the unit's record, by the lane of its first column in the first slice of the unit's first cell
+      if (slice == 0 && cr == av1mi_lr_first_cell(ur, ush) && active && x == av1mi_lr_first_cell(unit, ush) * sh) {
         const unsigned long long *usse = unit_sse + (sse_base + unit) * 8;
         unsigned long long *e = F.err + (fit_base + unit) * AV1MI_LR_FIT_CANDS;
         for (int k = 0; k < 7; k++) e[k] = usse[k];
@@ -299,8 +305,8 @@ __global__ void __launch_bounds__(64) lr_fit_kernel(Av1miDevParams P, const PIX 
     }
   }
   if constexpr (PHASE == 3) {
-    // padding between the signalled and the coded size: copied with the last unit of the row / column (its last slice)
-    const int py1 = (ur == urows - 1 && y1 == uy1) ? P.height >> sub : y1, px1 = last_col ? P.width >> sub : x1;
+    // padding between the signalled and the coded size: copied with the last cell of the row / column (its last slice)
+    const int py1 = (cr == crows - 1 && y1 == uy1) ? P.height >> sub : y1, px1 = last_col ? P.width >> sub : x1;
     for (int y = y0; y < py1; y++)
       for (int x = x0 + lane; x < px1; x += 64)
         if (y >= y1 || x >= x1) out[(size_t)y * stride + x] = cdef[(size_t)y * stride + x];
@@ -316,8 +322,9 @@ __global__ void __launch_bounds__(64) lr_fit_kernel(Av1miDevParams P, const PIX 
 }
 
 // PHASE 4: the bit strings of the self-guided units, fixed candidates included.  One thread per (frame, restored plane, tile) walks the
-// tile's units in coding order - unit (r, c) of every plane is read with superblock (r, c) - and carries the plane's RefSgrXqd, which
-// starts every tile at Sgrproj_Xqd_Mid and takes every self-guided unit's weights, implied ones included.
+// tile's units in coding order - unit (r, c) of every plane is read with superblock (r << lr_unit_shift, c << lr_unit_shift), so a tile
+// may start no unit - and carries the plane's RefSgrXqd, which starts every tile at Sgrproj_Xqd_Mid and takes every self-guided unit's
+// weights, implied ones included.
 __global__ void __launch_bounds__(64) lr_fit_code_kernel(Av1miDevParams P, Av1miLrFit F) {
   const int urows = av1mi_lr_unit_rows(P), ucols = av1mi_lr_unit_cols(P), per = urows * ucols;
   const int nplanes = P.lr_chroma ? 3 : 1, tiles = P.tile_rows * P.tile_cols;
@@ -328,8 +335,9 @@ __global__ void __launch_bounds__(64) lr_fit_code_kernel(Av1miDevParams P, Av1mi
   int ref0 = -32, ref1 = 31;
   for (int si = 0; si < tsb * tsb; si++) {
     const int sbr = tr * tsb + si / tsb, sbc = tc * tsb + si % tsb;
-    if (sbr >= P.sb_rows || sbc >= P.sb_cols || sbr >= urows || sbc >= ucols) continue;
-    const size_t u = ((size_t)f * 3 + pl) * per + (size_t)sbr * ucols + sbc;
+    const int ur = av1mi_lr_sb_unit(sbr, urows, P.lr_unit_shift), uc = av1mi_lr_sb_unit(sbc, ucols, P.lr_unit_shift);
+    if (sbr >= P.sb_rows || sbc >= P.sb_cols || ur < 0 || uc < 0) continue;
+    const size_t u = ((size_t)f * 3 + pl) * per + (size_t)ur * ucols + uc;
     const int8_t *r = F.rec + u * 4;
     if (r[0] < 4) continue;
     const Av1miBitString b = av1mi_lr_sgr_code(r[1], r[2], r[3], ref0, ref1);
@@ -353,13 +361,12 @@ void launch_fit_typed(const Av1miDevParams &R, int grid, const void *pre, const 
 extern "C" hipError_t av1mi_launch_lr_fit(const Av1miDevParams *P, const void *pre, const void *cdef, const void *src, void *out, uint8_t *choice,
                                           const unsigned long long *unit_sse, const Av1miLrFit *fit, int frame0, int count, hipStream_t stream) {
   const Av1miDevParams R = av1mi_frame_range(*P, frame0, count);
-  const int urows = av1mi_lr_unit_rows(R), ucols = av1mi_lr_unit_cols(R);
-  const size_t upf = (size_t)av1mi_lr_frame_units(R), fit_upf = (size_t)3 * urows * ucols;
+  const size_t upf = (size_t)av1mi_lr_frame_units(R), fit_upf = (size_t)3 * av1mi_lr_unit_rows(R) * av1mi_lr_unit_cols(R);
   pre = av1mi_frame_at(R, pre, frame0); cdef = av1mi_frame_at(R, cdef, frame0); src = av1mi_frame_at(R, src, frame0); out = av1mi_frame_at(R, out, frame0);
   choice += frame0 * upf; unit_sse += frame0 * upf * 8;
   Av1miLrFit F = *fit;
   F.sums += frame0 * fit_upf * AV1MI_LR_FIT_SETS * 5; F.err += frame0 * fit_upf * AV1MI_LR_FIT_CANDS; F.rec += frame0 * fit_upf * 4; F.code += frame0 * fit_upf * 2;
-  const int grid = count * urows * ucols * LR_SLICES + (R.lr_chroma ? count * 2 * urows * ((ucols + 1) / 2) * LR_SLICES_C : 0);   // == av1mi_launch_lr's
+  const int grid = av1mi_lr_grid(R, count);   // == av1mi_launch_lr's
   if (R.bit_depth == 8) launch_fit_typed<uint8_t>(R, grid, pre, cdef, src, out, choice, unit_sse, F, stream);
   else launch_fit_typed<uint16_t>(R, grid, pre, cdef, src, out, choice, unit_sse, F, stream);
   const int threads = count * (R.lr_chroma ? 3 : 1) * R.tile_rows * R.tile_cols;

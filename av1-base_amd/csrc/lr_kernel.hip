@@ -141,16 +141,19 @@ __device__ __forceinline__ int lr_decide(const unsigned long long *usse) {
 // 64 lanes = 2 x 32 columns, so the window, the Wiener tile and the self-guided grids keep the luma layout (no LDS beyond luma's), and
 // the sums and the decision stay per unit (lanes 0-31 / 32-63 of a pass).  The last unit of a row (up to 47 columns) is processed
 // alone, or after its neighbour in a second pass of the wave.  Choices and sums are [frame][plane][unit].
+// Larger units (lr_unit_shift, lr_geometry.h): the waves stay those of the 32x32 cells (crows x ccols of them); a cell's sums go to the unit it
+// lies in and its rows take that unit's decision.  The two halves of a wave may then be one unit: two atomics to one address.
 template <typename PIX, bool SGR, int PHASE>
 __device__ __forceinline__ void lr_chroma(const Av1miDevParams &P, int item, const PIX *pre, const PIX *cdef, const PIX *src, PIX *out,
-                                          uint8_t *choice, unsigned long long *unit_sse, int urows, int ucols) {
-  const int pairs = (ucols + 1) >> 1, slice = item % LR_SLICES_C, rest = item / LR_SLICES_C;
-  const int pc = rest % pairs, ur = rest / pairs % urows, pl = rest / (pairs * urows) % 2, f = rest / (pairs * urows * 2);
+                                          uint8_t *choice, unsigned long long *unit_sse, int crows, int ccols) {
+  const int pairs = (ccols + 1) >> 1, slice = item % LR_SLICES_C, rest = item / LR_SLICES_C;
+  const int pc = rest % pairs, cr = rest / pairs % crows, pl = rest / (pairs * crows) % 2, f = rest / (pairs * crows * 2);
+  const int ush = P.lr_unit_shift, urows = av1mi_lr_unit_rows(P), ucols = av1mi_lr_unit_cols(P), ur = av1mi_lr_unit_of_cell(cr, urows, ush);
   const int lane = threadIdx.x;
   const size_t fo = (size_t)f * P.frame_samples + (pl ? P.plane_off_v : P.plane_off_u);
   pre += fo; cdef += fo; src += fo; out += fo;
   const int W = (P.true_w + 1) >> 1, H = (P.true_h + 1) >> 1, stride = P.stride_c;
-  const int uy0 = ur ? ur * 32 - 4 : 0, uy1 = ur == urows - 1 ? H : ur * 32 + 28;   // the unit row's rows
+  const int uy0 = av1mi_lr_row0(cr, 0, 1), uy1 = av1mi_lr_row1(cr, crows, 0, 1, H);   // the cell row's rows
   const int y0 = uy0 + slice * 16, y1 = y0 + 16 < uy1 ? y0 + 16 : uy1;              // this wave's rows
   if (y0 >= uy1) return;
   const int x0 = pc * 64, x1 = pc == pairs - 1 ? W : x0 + 64;
@@ -159,7 +162,8 @@ __device__ __forceinline__ void lr_chroma(const Av1miDevParams &P, int item, con
   for (int xs = x0; xs < x1; xs += 64) {
     const int x = xs + lane;
     const bool active = x < x1;
-    const int uc_lo = min(ucols - 1, xs >> 5), uc_hi = min(ucols - 1, (xs >> 5) + 1), uc = lane < 32 ? uc_lo : uc_hi;
+    const int uc_lo = av1mi_lr_unit_of_cell(min(ccols - 1, xs >> 5), ucols, ush), uc_hi = av1mi_lr_unit_of_cell(min(ccols - 1, (xs >> 5) + 1), ucols, ush);
+    const int uc = lane < 32 ? uc_lo : uc_hi;
     if constexpr (PHASE == 0) {
       unsigned long long sse[7] = { 0, 0, 0, 0, 0, 0, 0 };
       for (int st = (y0 + 4) / 32; st * 32 - 4 < y1; st++) {
@@ -211,7 +215,7 @@ __device__ __forceinline__ void lr_chroma(const Av1miDevParams &P, int item, con
       // both units' decisions in every lane (the stripe loop below stays uniform); each lane applies its own unit's
       const int best_lo = lr_decide<SGR>(unit_sse + (ubase + uc_lo) * 8), best_hi = lr_decide<SGR>(unit_sse + (ubase + uc_hi) * 8);
       const int best = lane < 32 ? best_lo : best_hi;
-      if (slice == 0 && x == uc * 32) choice[ubase + uc] = (uint8_t)best;
+      if (slice == 0 && cr == av1mi_lr_first_cell(ur, ush) && x == av1mi_lr_first_cell(uc, ush) * 32) choice[ubase + uc] = (uint8_t)best;
       const bool any_wiener = (best_lo && best_lo <= 3) || (best_hi && best_hi <= 3), any_sgr = best_lo > 3 || best_hi > 3;
       int tf[7];
       taps_of_uv(best && best <= 3 ? best - 1 : 0, tf);
@@ -250,8 +254,8 @@ __device__ __forceinline__ void lr_chroma(const Av1miDevParams &P, int item, con
     }
   }
   if constexpr (PHASE == 1) {
-    // padding between the signalled and the coded size: copied with the last unit of the row / column (its last slice)
-    const int py1 = (ur == urows - 1 && y1 == uy1) ? P.height >> 1 : y1, px1 = pc == pairs - 1 ? P.width >> 1 : x1;
+    // padding between the signalled and the coded size: copied with the last cell of the row / column (its last slice)
+    const int py1 = (cr == crows - 1 && y1 == uy1) ? P.height >> 1 : y1, px1 = pc == pairs - 1 ? P.width >> 1 : x1;
     for (int y = y0; y < py1; y++)
       for (int x = x0 + lane; x < px1; x += 64)
         if (y >= y1 || x >= x1) out[(size_t)y * stride + x] = cdef[(size_t)y * stride + x];
@@ -261,6 +265,7 @@ __device__ __forceinline__ void lr_chroma(const Av1miDevParams &P, int item, con
 // A unit is LR_SLICES waves, one per 16 of its rows (the last unit of a column has up to 103), in two launches: PHASE 0 adds
 // the slice's SSE of every candidate to the unit's sums (atomics), PHASE 1 reads the sums, takes the same decision in every
 // slice and applies it to its rows.  (As one wave per unit the kernel took 221 us of an inter frame's serial chain.)
+// Larger units (lr_unit_shift): the blocks stay those of the 64x64 cells; the sums and the decision are those of the unit a cell lies in.
 // CHROMA (enable_lr = 3 / 4): the grid's luma blocks are followed by the chroma units' (lr_chroma), and choices and sums are
 // [frame][plane][unit]; without it they are [frame][unit] and the luma blocks copy the co-located chroma.
 template <typename PIX, bool SGR, bool CHROMA, int PHASE>
@@ -269,25 +274,26 @@ __global__ void __launch_bounds__(64) lr_unit_kernel(Av1miDevParams P, const PIX
                                                     unsigned long long *__restrict__ unit_sse /* [frame][(plane)][unit][8] */) {
   // units and stripes follow the signalled size; the last unit of a row/column also carries the padding up to the coded
   // size (copied, never filtered), so the whole frame buffer is defined
-  const int urows = (P.true_h + 32) / 64 > 0 ? (P.true_h + 32) / 64 : 1, ucols = (P.true_w + 32) / 64 > 0 ? (P.true_w + 32) / 64 : 1;
-  const int per_frame = urows * ucols;
+  const int crows = av1mi_lr_cell_rows(P), ccols = av1mi_lr_cell_cols(P), per_frame = crows * ccols;
+  const int ush = P.lr_unit_shift, urows = av1mi_lr_unit_rows(P), ucols = av1mi_lr_unit_cols(P);
   if constexpr (CHROMA) {
     const int luma_blocks = P.n_frames * per_frame * LR_SLICES;
     if ((int)blockIdx.x >= luma_blocks) {
-      lr_chroma<PIX, SGR, PHASE>(P, (int)blockIdx.x - luma_blocks, pre, cdef, src, out, choice, unit_sse, urows, ucols);
+      lr_chroma<PIX, SGR, PHASE>(P, (int)blockIdx.x - luma_blocks, pre, cdef, src, out, choice, unit_sse, crows, ccols);
       return;
     }
   }
   const int item = blockIdx.x / LR_SLICES, slice = blockIdx.x % LR_SLICES;
-  const int f = item / per_frame, u = item % per_frame, ur = u / ucols, uc = u % ucols;
-  const int uidx = CHROMA ? f * 3 * per_frame + u : item;   // the unit's choice and sums
+  const int f = item / per_frame, cell = item % per_frame, cr = cell / ccols, cc = cell % ccols;
+  const int ur = av1mi_lr_unit_of_cell(cr, urows, ush), uc = av1mi_lr_unit_of_cell(cc, ucols, ush);
+  const int uidx = f * (CHROMA ? 3 : 1) * urows * ucols + ur * ucols + uc;   // the unit's choice and sums
   const int lane = threadIdx.x;
   const size_t fo = (size_t)f * P.frame_samples;
   pre += fo; cdef += fo; src += fo; out += fo;
-  const int uy0 = ur ? ur * 64 - 8 : 0, uy1 = ur == urows - 1 ? P.true_h : ur * 64 + 56;   // the unit's rows
+  const int uy0 = av1mi_lr_row0(cr, 0, 0), uy1 = av1mi_lr_row1(cr, crows, 0, 0, P.true_h);   // the cell's rows
   const int y0 = uy0 + slice * 16, y1 = y0 + 16 < uy1 ? y0 + 16 : uy1;                      // this wave's rows
   if (y0 >= uy1) return;
-  const int x0 = uc * 64, x1 = uc == ucols - 1 ? P.true_w : x0 + 64;
+  const int x0 = cc * 64, x1 = cc == ccols - 1 ? P.true_w : x0 + 64;
   const int maxv = (1 << P.bit_depth) - 1;
   unsigned long long *usse = unit_sse + (size_t)uidx * 8;
   if constexpr (PHASE == 0) {
@@ -352,7 +358,7 @@ __global__ void __launch_bounds__(64) lr_unit_kernel(Av1miDevParams P, const PIX
       if (s < bs) { bs = s; best = k + 1; }
     }
   }
-  if (lane == 0 && slice == 0) choice[uidx] = (uint8_t)best;
+  if (lane == 0 && slice == 0 && cr == av1mi_lr_first_cell(ur, ush) && cc == av1mi_lr_first_cell(uc, ush)) choice[uidx] = (uint8_t)best;
   // ---- apply: luma of the slice, and (without CHROMA) the co-located chroma (copied)
   for (int xs = x0; xs < x1; xs += 64) {
     const int x = xs + lane;
@@ -390,8 +396,8 @@ __global__ void __launch_bounds__(64) lr_unit_kernel(Av1miDevParams P, const PIX
     }
   }
   {
-    // padding between the signalled and the coded size (< 8 samples): copied with the last unit of the row / column (its last slice)
-    const int py1 = (ur == urows - 1 && y1 == uy1) ? P.height : y1, px1 = uc == ucols - 1 ? P.width : x1;
+    // padding between the signalled and the coded size (< 8 samples): copied with the last cell of the row / column (its last slice)
+    const int py1 = (cr == crows - 1 && y1 == uy1) ? P.height : y1, px1 = cc == ccols - 1 ? P.width : x1;
     for (int y = y0; y < py1; y++)
       for (int x = x0 + lane; x < px1; x += 64)
         if (y >= y1 || x >= x1) out[(size_t)y * P.stride_y + x] = cdef[(size_t)y * P.stride_y + x];
@@ -435,13 +441,10 @@ void launch_lr_typed(const Av1miDevParams *P, int grid, const void *pre, const v
 extern "C" hipError_t av1mi_launch_lr(const Av1miDevParams *P, const void *pre, const void *cdef, const void *src, void *out, uint8_t *choice,
                                       unsigned long long *unit_sse, int clear, int decide, int frame0, int count, hipStream_t stream) {
   const Av1miDevParams R = av1mi_frame_range(*P, frame0, count);
-  const int urows = av1mi_lr_unit_rows(R), ucols = av1mi_lr_unit_cols(R);
   const size_t upf = (size_t)av1mi_lr_frame_units(R);
   pre = av1mi_frame_at(R, pre, frame0); cdef = av1mi_frame_at(R, cdef, frame0); src = av1mi_frame_at(R, src, frame0); out = av1mi_frame_at(R, out, frame0);
   choice += frame0 * upf; unit_sse += frame0 * upf * 8;
-  // luma: LR_SLICES waves per unit; chroma: per frame and plane, unit rows x pairs of unit columns, LR_SLICES_C waves each (the signalled
-  // size is even, so the chroma unit grid is the luma one)
-  const int grid = count * urows * ucols * LR_SLICES + (R.lr_chroma ? count * 2 * urows * ((ucols + 1) / 2) * LR_SLICES_C : 0);
+  const int grid = av1mi_lr_grid(R, count);
   if (clear) {
     hipError_t e = hipMemsetAsync(unit_sse, 0, count * upf * 8 * sizeof(unsigned long long), stream);
     if (e != hipSuccess) return e;

@@ -88,7 +88,7 @@ __device__ __forceinline__ void lr_stage(const PIX *cdef, const PIX *pre, int xs
   }
 }
 
-// A unit is LR_SLICES waves, one per 16 of its rows (the last unit of a column has up to 103); a pair of chroma units LR_SLICES_C
-// (up to 51 rows)
-#define LR_SLICES 7
-#define LR_SLICES_C 4
+// A cell (a unit of lr_unit_shift 0) is LR_SLICES waves, one per 16 of its rows (the last cell of a column has up to 103); a pair of
+// chroma cells LR_SLICES_C (up to 51 rows).  av1mi_dev.h's av1mi_lr_grid sizes the launches with them.
+#define LR_SLICES AV1MI_LR_SLICES
+#define LR_SLICES_C AV1MI_LR_SLICES_C

@@ -9,8 +9,8 @@
 // MI355X mapping: lr_kernel.hip's - one 64-lane wave per 16-row slice of a luma unit or of a pair of chroma units, lane = column, the
 // same grid, the window and the Wiener tile in LDS (6.2 KB per wave + 64 bytes of the units' taps).  It runs after the decision over
 // the other candidates has been taken and applied (lr_kernel.hip, or lr_fit_kernel.hip with the self-guided fit), in four launches:
-//   1 sums      the 27 sums per lane over the section's rows (32-bit: |D| <= 2046, 16 rows), reduced per half wave, one 64-bit atomic
-//               per sum and half
+//   1 sums      the 27 sums per lane over the section's rows (32-bit: |D| <= 2046, 16 rows: < 2^27), reduced per half wave, one 64-bit
+//               atomic per sum and half into the unit's sums (a unit of 256 has at most 383 x 391 samples: |sum| < 2^40)
 //   2 SSE       every slice solves its units' taps from the complete sums (lanes 0 and 1, one unit each), filters with the two tap
 //               arrays and adds its exact SSE; the unit's first lane records the taps
 //   3 override  a unit whose fitted error is strictly below its winner's is filtered again with the fitted taps (read-only on every
@@ -49,28 +49,31 @@ __device__ __forceinline__ unsigned long long base_err_of(const BaseErr &B, size
 template <typename PIX, int PHASE>
 __global__ void __launch_bounds__(64) lr_wfit_kernel(Av1miDevParams P, const PIX *__restrict__ pre, const PIX *__restrict__ cdef,
                                                     const PIX *__restrict__ src, PIX *__restrict__ out, BaseErr B, Av1miLrWfit F) {
-  const int urows = av1mi_lr_unit_rows(P), ucols = av1mi_lr_unit_cols(P), per = urows * ucols;
+  // the blocks are those of the cells (the units of lr_unit_shift 0); sums, taps, errors and records are those of the unit a cell lies in
+  const int crows = av1mi_lr_cell_rows(P), ccols = av1mi_lr_cell_cols(P), cells = crows * ccols;
+  const int ush = P.lr_unit_shift, urows = av1mi_lr_unit_rows(P), ucols = av1mi_lr_unit_cols(P), per = urows * ucols;
   const int lane = threadIdx.x;
-  const int luma_blocks = P.n_frames * per * LR_SLICES;
-  int f, pl, ur, slice, x0, x1, ucl;
+  const int luma_blocks = P.n_frames * cells * LR_SLICES;
+  int f, pl, cr, slice, x0, x1, ccl;
   if ((int)blockIdx.x < luma_blocks) {
-    const int item = blockIdx.x / LR_SLICES, u = item % per;
-    slice = blockIdx.x % LR_SLICES; f = item / per; pl = 0; ur = u / ucols; ucl = u % ucols;
-    x0 = ucl * 64; x1 = ucl == ucols - 1 ? P.true_w : x0 + 64;
+    const int item = blockIdx.x / LR_SLICES, cell = item % cells;
+    slice = blockIdx.x % LR_SLICES; f = item / cells; pl = 0; cr = cell / ccols; ccl = cell % ccols;
+    x0 = ccl * 64; x1 = ccl == ccols - 1 ? P.true_w : x0 + 64;
   } else {
     if (!P.lr_chroma) return;
-    const int item = (int)blockIdx.x - luma_blocks, pairs = (ucols + 1) >> 1, rest = item / LR_SLICES_C;
+    const int item = (int)blockIdx.x - luma_blocks, pairs = (ccols + 1) >> 1, rest = item / LR_SLICES_C;
     const int pc = rest % pairs;
-    slice = item % LR_SLICES_C; ur = rest / pairs % urows; pl = 1 + rest / (pairs * urows) % 2; f = rest / (pairs * urows * 2); ucl = -1;
+    slice = item % LR_SLICES_C; cr = rest / pairs % crows; pl = 1 + rest / (pairs * crows) % 2; f = rest / (pairs * crows * 2); ccl = -1;
     if (f >= P.n_frames) return;
     x0 = pc * 64; x1 = pc == pairs - 1 ? (P.true_w + 1) >> 1 : x0 + 64;
   }
+  const int ur = av1mi_lr_unit_of_cell(cr, urows, ush);
   const int sub = pl > 0;
   const int W = sub ? (P.true_w + 1) >> 1 : P.true_w, H = sub ? (P.true_h + 1) >> 1 : P.true_h, stride = sub ? P.stride_c : P.stride_y;
-  const int sh = 64 >> sub, so = 8 >> sub;   // stripe height = unit size, and the row offset of both
+  const int sh = 64 >> sub, so = 8 >> sub;   // stripe height = cell size, and the row offset of both
   const size_t fo = (size_t)f * P.frame_samples + (pl == 0 ? 0 : (pl == 1 ? P.plane_off_u : P.plane_off_v));
   pre += fo; cdef += fo; src += fo; out += fo;
-  const int uy0 = ur ? ur * sh - so : 0, uy1 = ur == urows - 1 ? H : ur * sh + sh - so;
+  const int uy0 = av1mi_lr_row0(cr, 0, sub), uy1 = av1mi_lr_row1(cr, crows, 0, sub, H);   // the cell row's rows
   const int y0 = uy0 + slice * 16, y1 = y0 + 16 < uy1 ? y0 + 16 : uy1;
   if (y0 >= uy1) return;
   const int maxv = (1 << P.bit_depth) - 1, bd = P.bit_depth;
@@ -79,8 +82,10 @@ __global__ void __launch_bounds__(64) lr_wfit_kernel(Av1miDevParams P, const PIX
   for (int xs = x0; xs < x1; xs += 64) {
     const int x = xs + lane;
     const bool active = x < x1;
-    // the section's units: lanes 0-31 are in `lo`, lanes 32-63 in `hi` (luma, and a last chroma unit on its own: one unit)
-    const int lo = ucl >= 0 ? ucl : min(ucols - 1, xs >> 5), hi = ucl >= 0 ? ucl : min(ucols - 1, (xs >> 5) + 1);
+    // the section's units: lanes 0-31 are in `lo`, lanes 32-63 in `hi` (one unit: luma, a last chroma cell on its own, and two chroma
+    // cells of one larger unit)
+    const int lo = av1mi_lr_unit_of_cell(ccl >= 0 ? ccl : min(ccols - 1, xs >> 5), ucols, ush);
+    const int hi = av1mi_lr_unit_of_cell(ccl >= 0 ? ccl : min(ccols - 1, (xs >> 5) + 1), ucols, ush);
     const int hsel = lo != hi ? lane >> 5 : 0, unit = hsel ? hi : lo;
     int fv[7], fh[7];
     bool mine = false, any = true;
@@ -96,8 +101,9 @@ __global__ void __launch_bounds__(64) lr_wfit_kernel(Av1miDevParams P, const PIX
       mine = active && g_wtap[hsel][0] != 0;
       any = g_wtap[0][0] != 0 || g_wtap[1][0] != 0;
       taps7(&g_wtap[hsel][1], fv); taps7(&g_wtap[hsel][4], fh);
-      // the unit's record (present, taps), by the lane of its first column in the unit's first slice; the choice follows in phase 4
-      if (slice == 0 && active && x == (ucl >= 0 ? ucl * 64 : unit * 32)) {
+      // the unit's record (present, taps), by the lane of its first column in the first slice of the unit's first cell; the choice
+      // follows in phase 4
+      if (slice == 0 && cr == av1mi_lr_first_cell(ur, ush) && active && x == av1mi_lr_first_cell(unit, ush) * sh) {
         int8_t *r = F.rec + (fit_base + unit) * 8;
         for (int j = 0; j < 7; j++) r[1 + j] = (int8_t)g_wtap[hsel][j];
       }
@@ -174,7 +180,7 @@ __global__ void __launch_bounds__(64) lr_wfit_kernel(Av1miDevParams P, const PIX
 }
 
 // PHASE 4.  One thread per (frame, restored plane, tile) walks the tile's units in coding order - unit (r, c) of every plane is read
-// with superblock (r, c) - and carries the plane's RefLrWiener, which starts every tile at Wiener_Taps_Mid in both passes and takes
+// with superblock (r << lr_unit_shift, c << lr_unit_shift), so a tile may start no unit - and carries the plane's RefLrWiener, which starts every tile at Wiener_Taps_Mid in both passes and takes
 // every Wiener unit's taps, fixed filters included.  With the self-guided fit its units' bits are written again as well: lr_fit_kernel.hip
 // carried RefSgrXqd through units that have since become Wiener units, which the decoder's reference never sees.
 __global__ void __launch_bounds__(64) lr_wfit_code_kernel(Av1miDevParams P, uint8_t *choice /* == B.choice */, BaseErr B, Av1miLrWfit F) {
@@ -189,8 +195,9 @@ __global__ void __launch_bounds__(64) lr_wfit_code_kernel(Av1miDevParams P, uint
   int sref0 = -32, sref1 = 31;   // Sgrproj_Xqd_Mid
   for (int si = 0; si < tsb * tsb; si++) {
     const int sbr = tr * tsb + si / tsb, sbc = tc * tsb + si % tsb;
-    if (sbr >= P.sb_rows || sbc >= P.sb_cols || sbr >= urows || sbc >= ucols) continue;
-    const size_t u = ((size_t)f * 3 + pl) * per + (size_t)sbr * ucols + sbc, cu = ((size_t)f * nplanes + pl) * per + (size_t)sbr * ucols + sbc;
+    const int ur = av1mi_lr_sb_unit(sbr, urows, P.lr_unit_shift), uc = av1mi_lr_sb_unit(sbc, ucols, P.lr_unit_shift);
+    if (sbr >= P.sb_rows || sbc >= P.sb_cols || ur < 0 || uc < 0) continue;
+    const size_t u = ((size_t)f * 3 + pl) * per + (size_t)ur * ucols + uc, cu = ((size_t)f * nplanes + pl) * per + (size_t)ur * ucols + uc;
     int8_t *r = F.rec + u * 8;
     int c = choice[cu];
     if (!r[1]) F.err[u] = ~0ull;
@@ -230,8 +237,7 @@ extern "C" hipError_t av1mi_launch_lr_wfit(const Av1miDevParams *P, const void *
                                            const unsigned long long *unit_sse, const Av1miLrFit *sgr_fit, const Av1miLrWfit *wfit, int frame0,
                                            int count, hipStream_t stream) {
   const Av1miDevParams R = av1mi_frame_range(*P, frame0, count);
-  const int urows = av1mi_lr_unit_rows(R), ucols = av1mi_lr_unit_cols(R);
-  const size_t upf = (size_t)av1mi_lr_frame_units(R), fit_upf = (size_t)3 * urows * ucols;
+  const size_t upf = (size_t)av1mi_lr_frame_units(R), fit_upf = (size_t)3 * av1mi_lr_unit_rows(R) * av1mi_lr_unit_cols(R);
   pre = av1mi_frame_at(R, pre, frame0); cdef = av1mi_frame_at(R, cdef, frame0); src = av1mi_frame_at(R, src, frame0); out = av1mi_frame_at(R, out, frame0);
   choice += frame0 * upf;
   BaseErr B;
@@ -241,7 +247,7 @@ extern "C" hipError_t av1mi_launch_lr_wfit(const Av1miDevParams *P, const void *
   B.fit_code = sgr_fit ? sgr_fit->code + frame0 * fit_upf * 2 : nullptr;
   Av1miLrWfit F = *wfit;
   F.err += frame0 * fit_upf; F.rec += frame0 * fit_upf * 8; F.sums += frame0 * fit_upf * AV1MI_LR_WFIT_SUMS; F.code += frame0 * fit_upf * 3;
-  const int grid = count * urows * ucols * LR_SLICES + (R.lr_chroma ? count * 2 * urows * ((ucols + 1) / 2) * LR_SLICES_C : 0);   // == av1mi_launch_lr's
+  const int grid = av1mi_lr_grid(R, count);   // == av1mi_launch_lr's
   if (R.bit_depth == 8) launch_wfit_typed<uint8_t>(R, grid, pre, cdef, src, out, B, F, stream);
   else launch_wfit_typed<uint16_t>(R, grid, pre, cdef, src, out, B, F, stream);
   const int threads = count * (R.lr_chroma ? 3 : 1) * R.tile_rows * R.tile_cols;

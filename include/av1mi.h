@@ -44,6 +44,11 @@ typedef struct av1mi_ctx av1mi_ctx;
 #define AV1MI_LR_FIT(lr, sets) ((uint32_t)(lr) | 0x100u | ((uint32_t)(sets) << 16))
 /* av1mi_params.enable_lr bit 10: the Wiener fit, or-ed into a value with a low byte of 1 .. 4 (with or without AV1MI_LR_FIT) */
 #define AV1MI_LR_WIENER_FIT 0x400u
+/* av1mi_params.enable_lr bits 12-13: lr_unit_shift, or-ed into a value with a low byte of 1 .. 4 (with or without either fit) -
+ * restoration units of 128x128 / 256x256 luma samples instead of 64x64 */
+#define AV1MI_LR_UNIT_128 0x1000u
+#define AV1MI_LR_UNIT_256 0x2000u
+#define AV1MI_LR_UNIT_SHIFT(v) (((uint32_t)(v) >> 12) & 3u)
 
 /* Operating point.  Replaces the reference's single constant
  *   SVT_PARAMS = "--crf 8 --preset 3 --film-grain 20 ... --keyint 240 --lookahead 40"
@@ -86,13 +91,20 @@ typedef struct {
                                self-guided filter is fitted per unit - beside the seven candidates above a unit may take any of
                                the 16 parameter sets (bits 16-31: a mask over the sets searched, 0 = all) with the two weights
                                that least squares gives for the unit, the smallest exact SSE winning as before.  Headers are
-                               those of 2 / 4.  Bit 8 with any other low byte, and bits 9 and 11-15, are refused with
+                               those of 2 / 4.  Bit 8 with any other low byte, and bits 9, 11, 14 and 15, are refused with
                                AV1MI_E_INVALID_ARG.  av1mi_lr_fit_result reports the units' choices;
                                bit 10 (AV1MI_LR_WIENER_FIT) with a low byte of 1 .. 4, alone or with
                                bit 8: after the decision above a unit's Wiener filter is fitted by least squares - three vertical
                                and three horizontal taps (chroma: two and two) - and replaces the unit's winner where its exact
                                SSE is strictly smaller.  Headers are those of the low byte.  Bit 10 with any other low byte is
                                refused with AV1MI_E_INVALID_ARG.  av1mi_lr_wiener_fit_result reports the units' final choices;
+                               bits 12-13 (AV1MI_LR_UNIT_128, AV1MI_LR_UNIT_256) with a low byte of
+                               1 .. 4, alone or with bit 8, bit 10 or both: lr_unit_shift 1 / 2 - luma units of 128x128 / 256x256
+                               samples, chroma units of half that (always the picture area of a luma unit), max(1, (size + U / 2) / U)
+                               units each way; every decision, fit and result above is then taken per unit of that size, and a unit
+                               signals a quarter / a sixteenth of the side information.  The frame header grows by one bit.  Both
+                               bits set, and either with a low byte of 0, are refused with AV1MI_E_INVALID_ARG.  A context may
+                               change the unit size from chunk to chunk;
                                default 0: the decision needs the CDEF output, which serialises CDEF before entropy coding */
   uint32_t tile_sb;         /* tile size in 64x64 superblocks, both ways: 0 = automatic (1; 2 when the frame has more than 64
                                superblock rows or columns, e.g. 8K - AV1 allows at most 64 x 64 tiles), or force 1 / 2 */
@@ -232,12 +244,13 @@ int av1mi_lf_search_result(const av1mi_ctx *ctx, uint32_t n_frames, uint8_t *lev
  * units[((f * 3 + plane) * n_units + u) * 4 + 0..3] = { choice, lr_sgr_set, xqd0, xqd1 } - choice 0 = off, 1..3 = Wiener filter,
  * 4..6 = fixed self-guided candidate, 7 + t = parameter set t with fitted weights (set and weights 0 unless choice >= 4) - and
  * (optional) err[((f * 3 + plane) * n_units + u) * 23 + choice] = the candidates' squared error against the source, UINT64_MAX for
- * an absent candidate (a set outside the mask, or a singular fit).  n_units = unit rows x unit columns of a plane,
- * max(1, (size + 32) / 64) each way from the signalled size; units in raster order.  Entries are zero for planes that are not restored
+ * an absent candidate (a set outside the mask, or a singular fit).  n_units = unit rows x unit columns of a plane at the chunk's unit
+ * size U = 64 << lr_unit_shift (enable_lr bits 12-13), max(1, (size + U / 2) / U) each way from the signalled size; units in raster
+ * order, the arrays dense at that count.  Entries are zero for planes that are not restored
  * and for a chunk without the fit.  The values arrive with the chunk's other small results: the call only copies them.
  * AV1MI_E_INVALID_ARG if n_frames is not the last chunk's frame count. */
 int av1mi_lr_fit_result(const av1mi_ctx *ctx, uint32_t n_frames, int8_t *units, uint64_t *err);
-/* n_units of the context's last successfully encoded chunk (0: none): what a caller sizes the two arrays above by -
+/* n_units of the context's last successfully encoded chunk, at that chunk's unit size (0: none): what a caller sizes the two arrays above by -
  * units holds n_frames * 3 * n_units * 4 entries, err n_frames * 3 * n_units * 23 */
 uint32_t av1mi_lr_fit_units(const av1mi_ctx *ctx);
 
@@ -251,7 +264,7 @@ uint32_t av1mi_lr_fit_units(const av1mi_ctx *ctx);
  * chunk without the fit.  The values arrive with the chunk's other small results: the call only copies them.
  * AV1MI_E_INVALID_ARG if n_frames is not the last chunk's frame count. */
 int av1mi_lr_wiener_fit_result(const av1mi_ctx *ctx, uint32_t n_frames, int8_t *units, uint64_t *err);
-/* n_units of the context's last successfully encoded chunk (0: none): units holds n_frames * 3 * n_units * 8 entries, err
+/* n_units of the context's last successfully encoded chunk, at that chunk's unit size (0: none): units holds n_frames * 3 * n_units * 8 entries, err
  * n_frames * 3 * n_units */
 uint32_t av1mi_lr_wiener_fit_units(const av1mi_ctx *ctx);
 

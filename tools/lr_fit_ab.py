@@ -3,7 +3,8 @@
 candidates), fit | 4 (the self-guided filter fitted per unit over all 16 parameter sets) and fit | 4 with
 the mask 1 << 9 (set 9 alone: the fixed candidates' set with fitted weights), and with the Wiener fit (bit 10, item 9e) on 3, on 4 and on
 fit | 4, at the headline point (all key frames, CQ 30), IPPP at
-CQ 30 and the production point (CQ 8).  One JSON line per point and value: frames/s (best of --steps after --warmup, the clip in HBM),
+CQ 30 and the production point (CQ 8), each at restoration units of 64, 128 and 256 luma samples (--unit-shifts; bits 12-13, item 9f).
+One JSON line per point, value and unit size: frames/s (best of --steps after --warmup, the clip in HBM),
 milliseconds per frame, bytes per frame, PSNR Y / U / V of the reconstruction, the report's stage times and, with the fit, the
 histogram of the units' choices (off / Wiener / fixed / fitted), of the fitted sets and of the fitted weights at their clamps
 (av1mi_lr_fit_result) and, with the Wiener fit, the units choosing the fitted filter, those of them with a tap at a clamp and with
@@ -61,6 +62,7 @@ def main():
     ap.add_argument("--frames", type=int, default=60)
     ap.add_argument("--points", default="", help="comma-separated subset of the point names")
     ap.add_argument("--values", default="0,4,fit4,fit4_set9,3,wfit3,wfit4,wfit_fit4")
+    ap.add_argument("--unit-shifts", default="0", help="comma-separated lr_unit_shift values: 0 = units of 64 luma samples, 1 = 128, 2 = 256")
     args = ap.parse_args()
     import torch
     import av1mi
@@ -73,8 +75,10 @@ def main():
         for name, kw in POINTS:
             if want and name not in want:
                 continue
-            for v in args.values.split(","):
-                p = av1mi.default_params(w, h, bd, enable_lr=VALUES[v], **kw)
+            for v, shift in ((v, int(s)) for v in args.values.split(",") for s in args.unit_shifts.split(",")):
+                if shift and not VALUES[v]:
+                    continue   # a unit size needs restoration
+                p = av1mi.default_params(w, h, bd, enable_lr=VALUES[v], lr_unit_shift=shift, **kw)
                 for _ in range(args.warmup):
                     ctx.encode_chunk(p, clip.data_ptr(), n, on_device=True, copy_out=False)
                 best, rep = None, None
@@ -84,7 +88,7 @@ def main():
                     dt = time.perf_counter() - t0
                     if best is None or dt < best:
                         best, rep = dt, r
-                line = {"point": name, "enable_lr": v, "fps": round(n / best, 1), "ms": round(best * 1e3, 2), "ms_per_frame": round(best * 1e3 / n, 3),
+                line = {"point": name, "enable_lr": v, "unit": 64 << shift, "fps": round(n / best, 1), "ms": round(best * 1e3, 2), "ms_per_frame": round(best * 1e3 / n, 3),
                         "bytes_per_frame": round(rep.bytes / n, 1), "psnr": [round(x, 3) for x in rep.psnr], "sse": [int(x) for x in rep.sse],
                         "ms_recon": round(rep.ms_recon, 3), "ms_entropy": round(rep.ms_entropy, 3)}
                 if VALUES[v] & 0x100:
