@@ -36,7 +36,7 @@ E_INVALID_ARG, E_NO_DEVICE, E_HIP, E_OOM, E_OVERFLOW, E_FORMAT, E_UNSUPPORTED = 
 
 # every symbol include/av1mi.h declares
 ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", "av1mi_last_error", "av1mi_encode_chunk",
-               "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units"]
+               "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units", "av1mi_sym_order_result", "av1mi_sym_order_tiles"]
 
 
 class Params(C.Structure):
@@ -120,6 +120,9 @@ _lib.av1mi_lr_fit_units.restype = C.c_uint32
 _lib.av1mi_lr_wiener_fit_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint64)]
 _lib.av1mi_lr_wiener_fit_units.argtypes = [C.c_void_p]
 _lib.av1mi_lr_wiener_fit_units.restype = C.c_uint32
+_lib.av1mi_sym_order_result.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_uint32]
+_lib.av1mi_sym_order_tiles.argtypes = [C.c_void_p]
+_lib.av1mi_sym_order_tiles.restype = C.c_uint32
 _lib.av1mi_write_headers.argtypes = [C.POINTER(Params), C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_size_t)]
 
 
@@ -373,6 +376,20 @@ class Context:
         rc = _lib.av1mi_lr_wiener_fit_result(self._h, n_frames, units.ctypes.data_as(C.POINTER(C.c_int8)), err.ctypes.data_as(C.POINTER(C.c_uint64)))
         _raise_for(rc, "av1mi_lr_wiener_fit_result: the context's last successfully encoded chunk does not have %d frames (or there is none)" % n_frames)
         return units, err
+
+    def sym_order_result(self):
+        """The order symbolize took the last encoded chunk's tiles in (include/av1mi.h: av1mi_sym_order_result): numpy arrays
+        order[n_tiles] (uint32: chunk-wide tile indices, heaviest class first) and classes[n_tiles] (uint8: each tile's weight class,
+        by tile index); None for a chunk that was symbolized in natural order."""
+        import numpy as np
+        n = int(_lib.av1mi_sym_order_tiles(self._h))
+        if n == 0:
+            return None
+        order = np.zeros(n, dtype=np.uint32)
+        classes = np.zeros(n, dtype=np.uint8)
+        rc = _lib.av1mi_sym_order_result(self._h, order.ctypes.data_as(C.POINTER(C.c_uint32)), classes.ctypes.data_as(C.POINTER(C.c_uint8)), n)
+        _raise_for(rc, "av1mi_sym_order_result")
+        return order, classes
 
     def encode_chunk(self, params, frames, n_frames, on_device=False, want_recon=False, recon_ptr=None, copy_out=True):
         """frames: bytes-like/numpy (host) or an int device pointer (on_device=True).

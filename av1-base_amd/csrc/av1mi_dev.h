@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "lr_geometry.h"
+#include "tile_weight_rule.h"
 #ifdef __HIPCC__
 #define AV1MI_HD __host__ __device__
 #else

@@ -475,6 +475,9 @@ struct Workspace {
   uint32_t *d_tile_bytes = nullptr, *d_tile_off = nullptr, *d_frame_size = nullptr, *d_payload = nullptr, *d_sym = nullptr;
   uint32_t *d_streams = nullptr, *d_combos = nullptr;
   unsigned long long *d_sse = nullptr;
+  // symbolize's tile order (tile_weight_rule.h): the classes' counters - the head of the block d_sse lies in, so that one fill clears
+  // both - and the rows [AV1MI_TILE_CLASSES][cap_frames x tiles] the reconstruction fills
+  uint32_t *d_sym_count = nullptr, *d_sym_order = nullptr;
   Av1miChunkRecord *d_record = nullptr;   // symbol counts, overflow flag, then frame_off[cap_frames + 1] (av1mi_launch_pack)
   unsigned long long *d_me = nullptr;  // motion search results per 8x8 unit per frame
   void *d_stage = nullptr;             // sizes that are not multiples of 8: frames in the caller's tight layout (input / reconstruction out)
@@ -553,6 +556,8 @@ struct av1mi_ctx {
   uint32_t fit_plane_units = 0;   // the units of one plane of one frame (av1mi_lr_fit_units)
   bool fit_on = false;
   bool wfit_on = false;           // ... and its Wiener fit (av1mi_lr_wiener_fit_result): the head of ws.h_wfit
+  bool sym_order = true;          // AV1MI_SYM_ORDER, read when the context is made: 0 = symbolize in natural tile order everywhere
+  uint32_t sym_tiles = 0;         // the tiles of the last chunk's weight-ordered table (av1mi_sym_order_result); 0: natural order
 };
 
 namespace {
@@ -625,7 +630,9 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     HIPCHK(c, ws_alloc(w, w.d_streams, nf * ntile * (size_t)tile_stream_cap(r, c->cap_scale) * 4));
     for (uint32_t **b : { &w.d_frame_size, &w.d_payload }) HIPCHK(c, ws_alloc(w, *b, nf * 4));
     HIPCHK(c, ws_alloc(w, w.d_record, sizeof(Av1miChunkRecord) + (nf + 1) * 8));
-    HIPCHK(c, ws_alloc(w, w.d_sse, nf * 3 * 8));
+    HIPCHK(c, ws_alloc(w, w.d_sym_count, AV1MI_TILE_CLASSES * 4 + nf * 3 * 8));
+    w.d_sse = reinterpret_cast<unsigned long long *>(w.d_sym_count + AV1MI_TILE_CLASSES);
+    HIPCHK(c, ws_alloc(w, w.d_sym_order, (size_t)AV1MI_TILE_CLASSES * nf * ntile * 4));
     {  // the five small host mirrors share one page-locked block: an allocation of page-locked memory costs far more than they hold
       auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
       const size_t b_hdr = up(256 + nf * 512), b_cdf = up(Av1miCdfCompact::BLOB_WORDS * sizeof(uint16_t)), b_par = up(AV1MI_AQ_SLOTS * sizeof(Av1miDevParams)),
@@ -846,6 +853,7 @@ int av1mi_ctx_create(int device_id, av1mi_ctx **out) {
   c->device = device_id;
   // test hook: start at a capacity multiplier content would otherwise have to provoke (tests/test_gpu_parity.py: slots beyond 4 GB)
   if (const char *e = getenv("AV1MI_CAP_SCALE")) { const int k = atoi(e); if (k >= 1 && k <= 64 && (k & (k - 1)) == 0) c->cap_scale = k; }
+  if (const char *e = getenv("AV1MI_SYM_ORDER")) c->sym_order = atoi(e) != 0;   // experiment knob: 0 = natural tile order in symbolize
   // the main stream carries the serial chain of a chunk (and the latency-bound range coder): highest priority, so that
   // the bulk work put beside it on the second stream (CDEF, SSE, the chunk-wide motion search) fills gaps instead of
   // taking its slots
@@ -1114,6 +1122,26 @@ int av1mi_lr_fit_result(const av1mi_ctx *c, uint32_t n_frames, int8_t *units, ui
   return AV1MI_OK;
 }
 
+// The order symbolize took the last chunk's tiles in: the classes' counters and rows as they still stand on the device (the next chunk's
+// prepare_chunk clears them), fetched here - not with the chunk's small results, it is a diagnostic.
+int av1mi_sym_order_result(const av1mi_ctx *c, uint32_t *order, uint8_t *classes, uint32_t n) {
+  if (!c || !order || !classes || c->lf_levels.empty() || n != c->sym_tiles || n == 0) return AV1MI_E_INVALID_ARG;
+  uint32_t count[AV1MI_TILE_CLASSES];
+  if (hipSetDevice(c->device) != hipSuccess || hipMemcpy(count, c->ws.d_sym_count, sizeof(count), hipMemcpyDeviceToHost) != hipSuccess) return AV1MI_E_HIP;
+  uint32_t at = 0;
+  for (int k = AV1MI_TILE_CLASSES - 1; k >= 0; k--) {
+    if (count[k] > n - at) return AV1MI_E_HIP;   // (the counters do not add up to the chunk's tiles)
+    if (count[k] && hipMemcpy(order + at, c->ws.d_sym_order + (size_t)k * n, (size_t)count[k] * 4, hipMemcpyDeviceToHost) != hipSuccess) return AV1MI_E_HIP;
+    for (uint32_t i = 0; i < count[k]; i++) {
+      if (order[at + i] >= n) return AV1MI_E_HIP;
+      classes[order[at + i]] = (uint8_t)k;
+    }
+    at += count[k];
+  }
+  return at == n ? AV1MI_OK : AV1MI_E_HIP;
+}
+uint32_t av1mi_sym_order_tiles(const av1mi_ctx *c) { return c && !c->lf_levels.empty() ? c->sym_tiles : 0; }
+
 uint32_t av1mi_lr_wiener_fit_units(const av1mi_ctx *c) { return c ? c->fit_plane_units : 0; }
 // The Wiener fit of the context's last chunk, likewise.
 int av1mi_lr_wiener_fit_result(const av1mi_ctx *c, uint32_t n_frames, int8_t *units, uint64_t *err) {
@@ -1192,7 +1220,7 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
     }
   }
   HIPCHK(c, hipMemsetAsync(w.d_record, 0, sizeof(Av1miChunkRecord), s));
-  HIPCHK(c, hipMemsetAsync(w.d_sse, 0, (size_t)n_frames * 24, s));
+  HIPCHK(c, hipMemsetAsync(w.d_sym_count, 0, AV1MI_TILE_CLASSES * 4 + (size_t)n_frames * 24, s));   // the classes' counters and d_sse behind them
   if (P.cdef_search) HIPCHK(c, hipMemsetAsync(w.d_cdef_err, 0, (size_t)n_frames * P.sb_rows * P.sb_cols * 24 * sizeof(unsigned long long), s));
   // the level search's sums, once per attempt at the chunk (not a fill per frame on a P chain)
   if (P.lf_search) HIPCHK(c, hipMemsetAsync(w.d_lf_err, 0, (size_t)n_frames * 3 * AV1MI_LF_CANDS * sizeof(unsigned long long), s));
@@ -1214,13 +1242,25 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   return AV1MI_OK;
 }
 
+// Whether symbolize takes this chunk's tiles heavy first: all-key-frame chunks with one-superblock tiles, adaptive CDFs and
+// leaves up to 32x32, unless AV1MI_SYM_ORDER = 0.  The reconstruction launch then fills the table and symbolize reads it; sym_tiles
+// remembers it for av1mi_sym_order_result.  (64x64 leaves: measured, the reconstruction wave's wait for its place in the table - it
+// has just stored a whole superblock - costs that launch 0.034 ms, more than symbolize gains: DESIGN 5h.)
+static bool sym_order_on(av1mi_ctx *c, uint32_t n_frames) {
+  const bool on = c->sym_order && c->P.tile_sb == 1 && !c->P.disable_cdf_update && c->P.max_bs_log2 <= 5;
+  c->sym_tiles = on ? n_frames * (uint32_t)(c->P.tile_rows * c->P.tile_cols) : 0;
+  return on;
+}
+
 // Entropy coding of frames [from, n_frames) on the main stream (the frame-edge tiles' symbolize variant on the fourth), then the join
 // with the groups of frames before `from` coded on the third (schedule_inter): packing needs the tile sizes and bytes of every frame.
-static int entropy_code(av1mi_ctx *c, uint32_t from, uint32_t n_frames) {
+// by_weight: symbolize takes the tiles in the order the chunk's reconstruction launch left (sym_order_on).
+static int entropy_code(av1mi_ctx *c, uint32_t from, uint32_t n_frames, bool by_weight = false) {
   Workspace &w = c->ws; hipStream_t s = c->stream;
   HIPCHK(c, hipEventRecord(c->ev[EV_RECON_DONE], s));
   HIPCHK(c, av1mi_launch_entropy(&c->P, w.d_cdf, w.d_levels, w.d_blk, w.d_streams, w.d_sym, w.d_combos, w.d_slots, w.d_tile_bytes, w.d_lrc,
-                                 w.d_tile_off /* scratch until the packing kernels fill it */, (int)from, (int)(n_frames - from),
+                                 w.d_tile_off /* scratch until the packing kernels fill it */, by_weight ? w.d_sym_count : nullptr,
+                                 by_weight ? w.d_sym_order : nullptr, (int)from, (int)(n_frames - from),
                                  s, c->ev[EV_SYM_DONE], c->stream4, c->ev[EV_EDGE_FORK], c->ev[EV_EDGE_JOIN]));
   if (from) HIPCHK(c, hipStreamWaitEvent(s, c->ev[EV_GROUPS_JOINED], 0));
   HIPCHK(c, hipEventRecord(c->ev[EV_ENTROPY_DONE], s));
@@ -1254,11 +1294,13 @@ static int schedule_all_key(av1mi_ctx *c, const void *src, uint32_t n_frames) {
   const bool sse_in_cdef = n_frames > 1;
   const bool deblock = av1mi_frame_lf_levels(P, 0)[0] != 0;
   const int n = (int)n_frames;
-  HIPCHK(c, av1mi_launch_recon(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, nullptr, nullptr, 0, n, s));
+  const bool by_weight = sym_order_on(c, n_frames);
+  HIPCHK(c, av1mi_launch_recon(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, nullptr, nullptr, 0, n, by_weight ? w.d_sym_count : nullptr,
+                               by_weight ? w.d_sym_order : nullptr, s));
   if (P.lf_search) HIPCHK(c, av1mi_launch_deblock_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, n, s));
   if (deblock && deblock_s == s) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, 0, n, s));
   if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, n, s));
-  if (const int rc = entropy_code(c, 0, n_frames)) return rc;
+  if (const int rc = entropy_code(c, 0, n_frames, by_weight)) return rc;
   HIPCHK(c, hipStreamWaitEvent(s2, c->ev[EV_RECON_DONE], 0));
   if (deblock && deblock_s == s2) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, 0, n, s2));
   // measured: starting CDEF right after the reconstruction, beside symbolize, costs 8 % overall
@@ -1275,7 +1317,9 @@ static int schedule_all_key(av1mi_ctx *c, const void *src, uint32_t n_frames) {
 static int schedule_all_key_lr(av1mi_ctx *c, const void *src, uint32_t n_frames) {
   const Av1miDevParams &P = c->P; Workspace &w = c->ws; hipStream_t s = c->stream;
   const int n = (int)n_frames;
-  HIPCHK(c, av1mi_launch_recon(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, nullptr, nullptr, 0, n, s));
+  const bool by_weight = sym_order_on(c, n_frames);
+  HIPCHK(c, av1mi_launch_recon(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, nullptr, nullptr, 0, n, by_weight ? w.d_sym_count : nullptr,
+                               by_weight ? w.d_sym_order : nullptr, s));
   if (P.lf_search) HIPCHK(c, av1mi_launch_deblock_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, n, s));
   if (av1mi_frame_lf_levels(P, 0)[0]) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, 0, n, s));
   if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, n, s));
@@ -1283,7 +1327,7 @@ static int schedule_all_key_lr(av1mi_ctx *c, const void *src, uint32_t n_frames)
   HIPCHK(c, av1mi_launch_lr(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, 1, P.lr_fit_code == nullptr, 0, n, s));
   if (P.lr_fit_code) HIPCHK(c, av1mi_launch_lr_fit(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, &w.fit, 0, n, s));
   if (P.lr_wfit_code) HIPCHK(c, av1mi_launch_lr_wfit(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, P.lr_fit_code ? &w.fit : nullptr, &w.wfit, 0, n, s));
-  const int rc = entropy_code(c, 0, n_frames);
+  const int rc = entropy_code(c, 0, n_frames, by_weight);
   return rc ? rc : sse_beside_range_coder(c, src);
 }
 
@@ -1328,7 +1372,7 @@ static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
   for (uint32_t f = 0; f < n_frames; f++) {
     const int fi = (int)f;
     if (av1mi_frame_is_inter(P, fi)) HIPCHK(c, hipStreamWaitEvent(s, c->me_ev[f], 0));
-    HIPCHK(c, av1mi_launch_recon(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, w.d_fin, me_best, fi, 1, s));
+    HIPCHK(c, av1mi_launch_recon(&P, w.d_params, src, w.d_rec, w.d_levels, w.d_blk, w.d_fin, me_best, fi, 1, nullptr, nullptr, s));
     // the frame's levels before its deblocking (its reconstruction does not depend on them; everything after sees the chosen levels)
     if (P.lf_search) HIPCHK(c, av1mi_launch_deblock_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, fi, 1, s));
     if (av1mi_frame_lf_levels(P, fi)[0]) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, fi, 1, s));
@@ -1351,7 +1395,7 @@ static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
       HIPCHK(c, hipEventRecord(c->grp_ev[n_grp], s));
       HIPCHK(c, hipStreamWaitEvent(c->stream3, c->grp_ev[n_grp], 0));
       HIPCHK(c, av1mi_launch_entropy(&P, w.d_cdf, w.d_levels, w.d_blk, w.d_streams, w.d_sym, w.d_combos, w.d_slots, w.d_tile_bytes, w.d_lrc,
-                                     w.d_tile_off, (int)(f + 1 - grp), (int)grp, c->stream3, nullptr, nullptr, nullptr, nullptr));
+                                     w.d_tile_off, nullptr, nullptr, (int)(f + 1 - grp), (int)grp, c->stream3, nullptr, nullptr, nullptr, nullptr));
       n_grp++;
     }
   }
@@ -1486,7 +1530,7 @@ static int encode_chunk_once(av1mi_ctx *c, const av1mi_params *params, const voi
 static int run_chunk(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
                      av1mi_buf *out, uint32_t *frame_sizes, void *recon, av1mi_report *report) {
   out->data = nullptr; out->size = 0;
-  c->lf_levels.clear(); c->lf_errs.clear(); c->fit_units = 0; c->fit_plane_units = 0; c->fit_on = false; c->wfit_on = false;
+  c->lf_levels.clear(); c->lf_errs.clear(); c->fit_units = 0; c->fit_plane_units = 0; c->fit_on = false; c->wfit_on = false; c->sym_tiles = 0;
   Resolved r;
   int rc = resolve(params, &r);
   if (rc) { set_err(c, "invalid parameters"); return rc; }

@@ -73,14 +73,16 @@ hipError_t av1mi_launch_subpel_refine(const Av1miDevParams *P, const void *frame
 // dP: the chunk's parameters in device memory (what the kernels read; n_frames and the loop-filter levels are not used by them),
 // followed with adaptive quantisation by the quantiser slots' copies.  The kernels get P's split masks and quantiser indices from the
 // launch's first frame on.
+// sym_order (key frames, frame0 = 0, with sym_count: 16 zeroed counters): every tile of the launch adds itself to its weight class's row
+// of sym_order[AV1MI_TILE_CLASSES][count x tiles per frame] (tile_weight_rule.h), for av1mi_launch_entropy over the same frames; or null.
 hipError_t av1mi_launch_recon_u16(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels, Av1miBlkInfo *blk,
-                                  const void *fin, const unsigned long long *me_best, int frame0, int count, hipStream_t stream);
+                                  const void *fin, const unsigned long long *me_best, int frame0, int count, uint32_t *sym_count, uint32_t *sym_order, hipStream_t stream);
 hipError_t av1mi_launch_recon_u8(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels, Av1miBlkInfo *blk,
-                                 const void *fin, const unsigned long long *me_best, int frame0, int count, hipStream_t stream);
+                                 const void *fin, const unsigned long long *me_best, int frame0, int count, uint32_t *sym_count, uint32_t *sym_order, hipStream_t stream);
 hipError_t av1mi_launch_recon64_u16(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels, Av1miBlkInfo *blk,
-                                    const void *fin, const unsigned long long *me_best, int frame0, int count, hipStream_t stream);
+                                    const void *fin, const unsigned long long *me_best, int frame0, int count, uint32_t *sym_count, uint32_t *sym_order, hipStream_t stream);
 hipError_t av1mi_launch_recon64_u8(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels, Av1miBlkInfo *blk,
-                                   const void *fin, const unsigned long long *me_best, int frame0, int count, hipStream_t stream);
+                                   const void *fin, const unsigned long long *me_best, int frame0, int count, uint32_t *sym_count, uint32_t *sym_order, hipStream_t stream);
 // both passes over the frames of `rec`, in place, with the levels of frame0's kind (av1mi_frame_lf_levels) or, with the level search
 // on, each frame's own (P->lf_sel: av1mi_launch_deblock_search on the same stream before)
 hipError_t av1mi_launch_deblock(const Av1miDevParams *P, void *rec, const Av1miBlkInfo *blk, int frame0, int count, hipStream_t stream);
@@ -116,17 +118,21 @@ hipError_t av1mi_launch_lr_wfit(const Av1miDevParams *P, const void *pre, const 
 // tile_order: n_tiles entries of scratch.  mid: recorded on `stream` after symbolize, or null.  aux != null: the frame-edge tiles'
 // symbolize variant runs there, beside the regular one, between `fork` and `join`.  cdf_init: Av1miCdfCompact::BLOB_WORDS entries, 16-byte
 // aligned - the blob (Av1miCdfLayout) and behind it its compact image for P->max_bs_log2 (av1mi_cdf_compact_build)
+// sym_count, sym_order: what av1mi_launch_recon filled for the same frames (frame0 = 0, key frames only, one-superblock tiles) - the
+// regular symbolize variant takes its tiles from the heaviest class down; null: natural order.  Every other variant keeps natural order.
 hipError_t av1mi_launch_entropy(const Av1miDevParams *P, const uint16_t *cdf_init, const int16_t *levels, const Av1miBlkInfo *blk,
                                 uint32_t *streams, uint32_t *stream_len, uint32_t *tile_combos, uint8_t *slots, uint32_t *tile_bytes,
-                                const uint8_t *lr_choice, uint32_t *tile_order, int frame0, int count,
-                                hipStream_t stream, hipEvent_t mid, hipStream_t aux, hipEvent_t fork, hipEvent_t join);
+                                const uint8_t *lr_choice, uint32_t *tile_order, const uint32_t *sym_count, const uint32_t *sym_order,
+                                int frame0, int count, hipStream_t stream, hipEvent_t mid, hipStream_t aux, hipEvent_t fork, hipEvent_t join);
 }
 
 // 64x64 leaf blocks run the kernels of recon64_kernel.hip (64-point transforms, larger LDS tiles)
 inline hipError_t av1mi_launch_recon(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels, Av1miBlkInfo *blk,
-                                     const void *fin, const unsigned long long *me_best, int frame0, int count, hipStream_t stream) {
+                                     const void *fin, const unsigned long long *me_best, int frame0, int count, uint32_t *sym_count,
+                                     uint32_t *sym_order, hipStream_t stream) {
   return (P->max_bs_log2 >= 6 ? (P->bit_depth == 8 ? av1mi_launch_recon64_u8 : av1mi_launch_recon64_u16)
-                              : (P->bit_depth == 8 ? av1mi_launch_recon_u8 : av1mi_launch_recon_u16))(P, dP, src, rec, levels, blk, fin, me_best, frame0, count, stream);
+                              : (P->bit_depth == 8 ? av1mi_launch_recon_u8 : av1mi_launch_recon_u16))(P, dP, src, rec, levels, blk, fin, me_best, frame0, count,
+                                                                                                      sym_count, sym_order, stream);
 }
 
 #endif

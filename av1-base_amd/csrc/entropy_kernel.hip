@@ -632,10 +632,28 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
                                                            uint32_t *__restrict__ streams, uint32_t *__restrict__ stream_len,
                                                            uint32_t *__restrict__ tile_combos, const uint8_t *__restrict__ lr_choice,
                                                            int tile0 /* chunk-wide index of this launch's first tile: launches cover whole frames */,
-                                                           int edge_grid /* 0: one workgroup per tile of the launch's frames; 1: per EDGE tile of them (av1mi_edge_tile) */) {
+                                                           int edge_grid /* 0: one workgroup per tile of the launch's frames; 1: per EDGE tile of them (av1mi_edge_tile) */,
+                                                           const uint32_t *__restrict__ sym_count, const uint32_t *__restrict__ sym_order /* the tiles by weight class, or null: natural order */) {
   // one wave per TILE of TSB x TSB superblocks (raster order inside the tile)
   const int tiles_per_frame = P.tile_rows * P.tile_cols, sbs_per_frame = P.sb_rows * P.sb_cols;
   int gt = (int)blockIdx.x + tile0;
+  if (sym_order) {
+    // Heavy tiles first (tile_weight_rule.h): workgroup i takes entry i of the reconstruction's rows sym_order[class][tiles of the launch]
+    // laid end to end from the top class down - the 16 counts and the entry are scalar loads.  A tile writes only its own slots, so
+    // the bytes do not depend on the order; the order inside a class is the order of the reconstruction waves' atomics and differs
+    // from run to run.  (tile0 = 0 and a grid of the launch's tiles: the launcher sees to both.)
+    uint32_t i = blockIdx.x;
+    int cls = 0;
+    bool found = false;
+#pragma unroll
+    for (int c = AV1MI_TILE_CLASSES - 1; c > 0; c--) {
+      const uint32_t n = sym_count[c];
+      if (!found && i < n) { cls = c; found = true; }
+      if (!found) i -= n;
+    }
+    gt = (int)sym_order[(size_t)cls * gridDim.x + i];
+    if ((uint32_t)gt >= gridDim.x) return;   // (never, with a table the reconstruction filled: the rows hold every tile once)
+  }
   if (edge_grid) { const int ne = av1mi_edge_tiles(P); gt = (tile0 / tiles_per_frame + (int)blockIdx.x / ne) * tiles_per_frame + av1mi_edge_tile(P, (int)blockIdx.x % ne); }
   const int f = gt / tiles_per_frame, tile = gt % tiles_per_frame;
   const int tr = tile / P.tile_cols, tc = tile % P.tile_cols;
@@ -1333,8 +1351,8 @@ __global__ void __launch_bounds__(128) rangecode2_tiles_kernel(Av1miDevParams P,
 
 extern "C" hipError_t av1mi_launch_entropy(const Av1miDevParams *P, const uint16_t *cdf_init, const int16_t *levels,
                                            const Av1miBlkInfo *blk, uint32_t *streams, uint32_t *stream_len, uint32_t *tile_combos,
-                                           uint8_t *slots, uint32_t *tile_bytes, const uint8_t *lr_choice, uint32_t *tile_order, int frame0, int count,
-                                           hipStream_t stream, hipEvent_t mid, hipStream_t aux, hipEvent_t fork, hipEvent_t join) {
+                                           uint8_t *slots, uint32_t *tile_bytes, const uint8_t *lr_choice, uint32_t *tile_order,
+                                           const uint32_t *sym_count, const uint32_t *sym_order, int frame0, int count, hipStream_t stream, hipEvent_t mid, hipStream_t aux, hipEvent_t fork, hipEvent_t join) {
   const int tpf = P->tile_rows * P->tile_cols;
   const int n_tiles = count * tpf, tile0 = frame0 * tpf;
   bool has_inter = false, has_key = false;
@@ -1373,11 +1391,16 @@ extern "C" hipError_t av1mi_launch_entropy(const Av1miDevParams *P, const uint16
     fs = aux;
   }
   const int full_grid = edge_grid ? count * av1mi_edge_tiles(*P) : n_tiles;
+  // Heavy tiles first: the regular key-frame variant over one-superblock tiles alone, and only over the launch the table was made for
+  // (the whole chunk, from frame 0).  The other variants keep natural order.
+  if (sym_order && (!sym_count || frame0 != 0 || has_inter || P->tile_sb != 1)) return hipErrorInvalidValue;
 #define SYM_LAUNCH(FULLV, INTERV, TSBV)                                                                                                   \
   do {                                                                                                                                    \
+    const bool by_weight = !(FULLV) && !(INTERV) && (TSBV) == 1 && sym_order;                                                            \
     if ((FULLV) ? full_any : regular_any)                                                                                                 \
       hipLaunchKernelGGL((symbolize_tile_kernel<FULLV, INTERV, TSBV>), dim3((FULLV) ? full_grid : n_tiles), dim3(64), 0, (FULLV) ? fs : stream, *P, cdf_init, \
-                         levels, blk, streams, stream_len, tile_combos, lr_choice, tile0, (FULLV) && edge_grid ? 1 : 0);                  \
+                         levels, blk, streams, stream_len, tile_combos, lr_choice, tile0, (FULLV) && edge_grid ? 1 : 0,                   \
+                         by_weight ? sym_count : (const uint32_t *)nullptr, by_weight ? sym_order : (const uint32_t *)nullptr);           \
   } while (0)
   if (P->tile_sb == 1) {
     if (has_key) { SYM_LAUNCH(false, false, 1); SYM_LAUNCH(true, false, 1); }

@@ -1539,7 +1539,7 @@ __device__ __forceinline__ int leaf_bsl_at(const Av1miDevParams &P, int have_mas
 }
 
 template <typename PIX, bool INTER, int TSB, bool QM, bool SPLIT, bool EXT>
-__device__ __forceinline__ void encode_superblock(const SbCtx &cx, const PIX *frame, PIX *rec_frame, int16_t *sb_levels,
+__device__ __forceinline__ int encode_superblock(const SbCtx &cx, const PIX *frame, PIX *rec_frame, int16_t *sb_levels,
                                                   Av1miBlkInfo *info, int b8_stride, const PIX *ref_frame,
                                                   const unsigned long long *me_best /* this superblock's first unit */, int si,
                                                   int have_mask, uint32_t mask /* the superblock's split mask (content-driven partition) */) {
@@ -1547,6 +1547,7 @@ __device__ __forceinline__ void encode_superblock(const SbCtx &cx, const PIX *fr
   // SPLIT: wave 0 of the workgroup walks the luma blocks (and takes the decisions), wave 1 the chroma blocks
   constexpr int WL = SPLIT ? 1 : 0, WC = SPLIT ? 2 : 0;
   const int wv = SPLIT ? uniform_i((int)threadIdx.x >> 6) : 0;
+  int weight = 0;   // key frames: the sum of the eobs of the blocks coded here (tile_weight_rule.h), wave-uniform; returned
 #pragma nounroll
   // 8x8 units in Z (partition) order, from leaf origin to leaf origin: a leaf of size 2^bsl covers the 4^(bsl - 3) units that follow
   // its origin in that order (the ones beyond the frame included), so the walk steps over them; a unit outside the frame that
@@ -1618,8 +1619,9 @@ __device__ __forceinline__ void encode_superblock(const SbCtx &cx, const PIX *fr
       const int n8 = n >> 3;
       int e0 = SPLIT ? q_wait(&g_q.e0[qi]) : eo[0];
       if (SPLIT) { idtx = (e0 >> 12) & 1; e0 &= 0xFFF; }
+      const int e1 = eo[1], e2 = eo[2];
+      if constexpr (!INTER) weight += uniform_i(e0 + e1 + e2);
       if (cx.lane < n8 * n8) {
-        const int e1 = eo[1], e2 = eo[2];
         const int i = cx.lane / n8, j = cx.lane - i * n8;
         Av1miBlkInfo bi;
         const bool unit_inside = cx.sb_y + by + 8 * i < P.height && cx.sb_x + bx + 8 * j < P.width;   // an overhanging block's units beyond the frame have no entry
@@ -1635,6 +1637,7 @@ __device__ __forceinline__ void encode_superblock(const SbCtx &cx, const PIX *fr
       }
     }
   }
+  return weight;
 }
 
 // The tile walk of an inter frame is SPLIT (two waves per tile, see encode_superblock): its duration is the chain of the tile with
@@ -1652,7 +1655,8 @@ __global__ void __launch_bounds__(WalkSplit<INTER>::value ? 128 : 64) __attribut
                                                      const PIX *__restrict__ ref /* inter frame: previous final reconstruction, one frame */,
                                                      const unsigned long long *__restrict__ me_best,
                                                      const uint32_t *__restrict__ part /* split masks of the launch's first frame on (null: partition by geometry) */,
-                                                     const uint8_t *__restrict__ aq /* adaptive quantisation: quantiser indices of the launch's first frame on (null: base_q_idx) */) {
+                                                     const uint8_t *__restrict__ aq /* adaptive quantisation: quantiser indices of the launch's first frame on (null: base_q_idx) */,
+                                                     uint32_t *__restrict__ sym_count, uint32_t *__restrict__ sym_order /* key frames: symbolize's tile order (below), or null */) {
   // The parameters come through a pointer to device memory, not by value: the transform items are `noinline` and take the
   // address of the block, and the address of a by-value kernel argument is a private copy - every lane wrote the whole
   // structure (0.6 KB) to scratch at the start of the kernel and read its fields back from there.  Loads through a
@@ -1684,6 +1688,7 @@ __global__ void __launch_bounds__(WalkSplit<INTER>::value ? 128 : 64) __attribut
         aq_slots |= (uint32_t)uniform_i(av1mi_aq_slot((int)aq[(size_t)f * sbs_per_frame + sbr * P.sb_cols + sbc], P.base_q_idx)) << (4 * si);
     }
   }
+  int weight = 0;
 #pragma nounroll
   for (int si = 0; si < TSB * TSB; si++) {
     const int sbr = tr * TSB + si / TSB, sbc = tc * TSB + si % TSB;
@@ -1764,9 +1769,19 @@ __global__ void __launch_bounds__(WalkSplit<INTER>::value ? 128 : 64) __attribut
     int16_t *sb_levels = levels + ((size_t)f * sbs_per_frame + sb) * AV1MI_SB_LEVELS;
     Av1miBlkInfo *info = blk + (size_t)f * P.b8_rows * P.b8_cols + (size_t)(sbr * 8) * P.b8_cols + sbc * 8;
     // (inter frames are launched one at a time: f == 0 then, and `ref` / `me_best` belong to that frame)
-    encode_superblock<PIX, INTER, TSB, QM, SPLIT, EXT>(cx, frame, rec + (size_t)f * P.frame_samples, sb_levels, info, P.b8_cols, ref,
+    weight += encode_superblock<PIX, INTER, TSB, QM, SPLIT, EXT>(cx, frame, rec + (size_t)f * P.frame_samples, sb_levels, info, P.b8_cols, ref,
                                                   me_best ? me_best + (size_t)(sbr * 8) * P.b8_cols + sbc * 8 : nullptr, si,
                                                   part != nullptr, part ? part[(size_t)f * sbs_per_frame + sb] : 0u);
+  }
+  if constexpr (!INTER) {
+    // Symbolize's order (tile_weight_rule.h): this tile joins its weight class's row of sym_order[class][tiles of the launch] at the
+    // position the class's counter hands out - no sort; symbolize walks the rows from the heaviest class down.  Which tile of a
+    // class comes first is decided by the atomics and differs from run to run.  (sym_count: 16 counters, zero before the launch.)
+    if (sym_order && threadIdx.x == (SPLIT ? 64 : 0)) {   // (a split walk's chroma wave is the one that sees all three eobs)
+      const int cls = av1mi_tile_weight_class((uint32_t)weight);
+      const uint32_t at = atomicAdd(&sym_count[cls], 1u);
+      if (at < gridDim.x) sym_order[(size_t)cls * gridDim.x + at] = blockIdx.x;   // (always, with the counters cleared: a row holds every tile)
+    }
   }
 #ifdef AV1MI_STAMPS
   __syncthreads();
@@ -1872,9 +1887,11 @@ typedef uint8_t ReconPix;
 typedef uint16_t ReconPix;
 #endif
 extern "C" hipError_t AV1MI_LAUNCH_RECON(const Av1miDevParams *P, const Av1miDevParams *dP, const void *src, void *rec, int16_t *levels,
-                                         Av1miBlkInfo *blk, const void *fin, const unsigned long long *me_best, int frame0, int count, hipStream_t stream) {
+                                         Av1miBlkInfo *blk, const void *fin, const unsigned long long *me_best, int frame0, int count,
+                                         uint32_t *sym_count, uint32_t *sym_order, hipStream_t stream) {
   const bool inter = av1mi_frame_is_inter(*P, frame0);
   if (inter && (count != 1 || !fin || !me_best)) return hipErrorInvalidValue;
+  if (sym_order && (inter || frame0 != 0 || !sym_count)) return hipErrorInvalidValue;   // the table is the chunk's: one launch fills it
   const Av1miDevParams R = av1mi_frame_range(*P, frame0, count);
   const size_t nb8 = (size_t)P->b8_rows * P->b8_cols;
   const void *ref = inter ? av1mi_frame_at(R, fin, frame0 - 1) : nullptr;
@@ -1902,9 +1919,9 @@ extern "C" hipError_t AV1MI_LAUNCH_RECON(const Av1miDevParams *P, const Av1miDev
 #define RECON_LAUNCH2(PIXT, INTERV, TSBV, EXTV)                                                                                             \
   do {                                                                                                                                      \
     if (P->qm_tab) hipLaunchKernelGGL((recon_sb_kernel<PIXT, INTERV, TSBV, true, EXTV>), dim3(grid), dim3(WalkSplit<INTERV>::value ? 128 : 64), 0, stream, dP, (const PIXT *)src,  \
-                                      (PIXT *)rec, levels, blk, (const PIXT *)ref, me_best, part, R.aq_map);                                           \
+                                      (PIXT *)rec, levels, blk, (const PIXT *)ref, me_best, part, R.aq_map, sym_count, sym_order);                     \
     else hipLaunchKernelGGL((recon_sb_kernel<PIXT, INTERV, TSBV, false, EXTV>), dim3(grid), dim3(WalkSplit<INTERV>::value ? 128 : 64), 0, stream, dP, (const PIXT *)src,           \
-                            (PIXT *)rec, levels, blk, (const PIXT *)ref, me_best, part, R.aq_map);                                                     \
+                            (PIXT *)rec, levels, blk, (const PIXT *)ref, me_best, part, R.aq_map, sym_count, sym_order);                               \
   } while (0)
   // the optional intra tools (edge filter, chroma from luma) live in instantiations of their own (EXT)
 #define RECON_LAUNCH(PIXT, INTERV, TSBV)                                                                                                    \

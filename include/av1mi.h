@@ -268,6 +268,17 @@ int av1mi_lr_wiener_fit_result(const av1mi_ctx *ctx, uint32_t n_frames, int8_t *
  * n_frames * 3 * n_units */
 uint32_t av1mi_lr_wiener_fit_units(const av1mi_ctx *ctx);
 
+/* ---- symbolize's tile order of the last chunk ------------------------------------------------
+ * An all-key-frame chunk with one-superblock tiles, adaptive CDFs and block_log2 <= 5 is symbolized heavy tiles first (the
+ * environment variable AV1MI_SYM_ORDER = 0, read when the context is created, keeps natural order).  A tile's weight is the sum of its
+ * transform blocks' eobs, its class 0 .. 15 a monotone step function of the weight (class 0: weight 0).  For the context's last
+ * successfully encoded chunk order[0 .. n) = the chunk-wide tile indices (frame * tiles per frame + tile) in the order symbolize took them,
+ * a permutation with non-increasing class - the order inside a class differs from run to run, the bytes do not depend on it - and
+ * classes[tile] = that tile's class.  n must be av1mi_sym_order_tiles; the call reads the table back from the device.
+ * AV1MI_E_INVALID_ARG if the last chunk was symbolized in natural order (av1mi_sym_order_tiles is 0 then) or n is not its tile count. */
+int av1mi_sym_order_result(const av1mi_ctx *ctx, uint32_t *order, uint8_t *classes, uint32_t n);
+uint32_t av1mi_sym_order_tiles(const av1mi_ctx *ctx);
+
 /* ---- the drop-in for `run_av1an` ---------------------------------------------------------
  * Replaces  pub fn run_av1an(params: &Av1anEncodeParams) -> Result<(), EncodeError>
  * (crates/daemon/src/encode/av1an.rs:126-139), called from JobExecutor::execute through
