@@ -36,7 +36,7 @@ E_INVALID_ARG, E_NO_DEVICE, E_HIP, E_OOM, E_OVERFLOW, E_FORMAT, E_UNSUPPORTED = 
 
 # every symbol include/av1mi.h declares
 ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", "av1mi_last_error", "av1mi_encode_chunk",
-               "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units", "av1mi_sym_order_result", "av1mi_sym_order_tiles"]
+               "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units", "av1mi_sym_order_result", "av1mi_sym_order_tiles", "av1mi_inter_partition_result", "av1mi_inter_partition_units"]
 
 
 class Params(C.Structure):
@@ -123,6 +123,9 @@ _lib.av1mi_lr_wiener_fit_units.restype = C.c_uint32
 _lib.av1mi_sym_order_result.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_uint32]
 _lib.av1mi_sym_order_tiles.argtypes = [C.c_void_p]
 _lib.av1mi_sym_order_tiles.restype = C.c_uint32
+_lib.av1mi_inter_partition_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+_lib.av1mi_inter_partition_units.argtypes = [C.c_void_p]
+_lib.av1mi_inter_partition_units.restype = C.c_uint32
 _lib.av1mi_write_headers.argtypes = [C.POINTER(Params), C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p, C.POINTER(C.c_size_t)]
 
 
@@ -376,6 +379,27 @@ class Context:
         rc = _lib.av1mi_lr_wiener_fit_result(self._h, n_frames, units.ctypes.data_as(C.POINTER(C.c_int8)), err.ctypes.data_as(C.POINTER(C.c_uint64)))
         _raise_for(rc, "av1mi_lr_wiener_fit_result: the context's last successfully encoded chunk does not have %d frames (or there is none)" % n_frames)
         return units, err
+
+    def inter_partition_result(self, n_frames, width=None, height=None):
+        """The partition of the last encoded chunk's frames under partition_search 1 / 2 (include/av1mi.h: av1mi_inter_partition_result):
+        numpy arrays masks[frame][superblock row][superblock column] (uint32 split masks) and keys[frame][8x8 unit row][unit column]
+        (uint64: under partition_search = 2, in a chunk with inter frames, the integer search's key at every leaf's origin unit of an inter frame, other entries
+        unspecified; zeros without that search); None for a chunk without a partition map.  Shaped by the frame size of this object's last successful encode_chunk call, or width and
+        height; a size whose unit grid is not the library's is refused."""
+        import numpy as np
+        n_units = int(_lib.av1mi_inter_partition_units(self._h))
+        if n_units == 0:
+            return None
+        if width is None or height is None:
+            width, height = self._last_size if self._last_size is not None else (0, 0)
+        ur, uc = (height + 7) // 8, (width + 7) // 8
+        if ur * uc != n_units:
+            _raise_for(E_INVALID_ARG, "av1mi_inter_partition_result: the last chunk has %d 8x8 units per frame, not the %d x %d of %d x %d frames" % (n_units, ur, uc, width, height))
+        masks = np.zeros((n_frames, (ur + 7) // 8, (uc + 7) // 8), dtype=np.uint32)
+        keys = np.zeros((n_frames, ur, uc), dtype=np.uint64)
+        rc = _lib.av1mi_inter_partition_result(self._h, n_frames, masks.ctypes.data_as(C.POINTER(C.c_uint32)), keys.ctypes.data_as(C.POINTER(C.c_uint64)))
+        _raise_for(rc, "av1mi_inter_partition_result: the context's last successfully encoded chunk does not have %d frames (or there is none)" % n_frames)
+        return masks, keys
 
     def sym_order_result(self):
         """The order symbolize took the last encoded chunk's tiles in (include/av1mi.h: av1mi_sym_order_result): numpy arrays

@@ -30,6 +30,7 @@
 #include "wiener_fit_rule.h"
 #include "deblock_pieces.h"
 #include "aq_rule.h"
+#include "part_inter_rule.h"
 
 namespace {
 
@@ -140,7 +141,7 @@ int resolve(const av1mi_params *in, Resolved *r) {
     p.enable_lr = low;
   }
   if (p.subpel > 1 || p.enable_lr > 4 || p.color_range > 1 || p.intra_angle_delta > 1 || p.intra_edge_filter > 1 || p.cfl > 1 || p.tx_search > 1) return AV1MI_E_INVALID_ARG;
-  if (p.partition_search > 1 || p.me_presearch > 1) return AV1MI_E_INVALID_ARG;
+  if (p.partition_search > 2 || p.me_presearch > 1) return AV1MI_E_INVALID_ARG;
   // enable_lr 3 / 4 = 1 / 2 on all three planes: the frames' restoration type plus the chroma flag
   r->lr_chroma = p.enable_lr >= 3;
   if (r->lr_chroma) p.enable_lr -= 2;
@@ -487,6 +488,7 @@ struct Workspace {
   uint32_t *d_centre = nullptr;            // me_presearch: centre code of the full search per [frame][superblock]
   uint32_t *d_part = nullptr;              // content-driven partition: split mask per [frame][superblock] (partition_kernel)
   uint32_t *d_me64 = nullptr;              // 64x64 leaves: the search's [frame][superblock][candidate] SAD table
+  uint32_t *d_nodes = nullptr;             // partition_search = 2: the node-mode search's [frame][level][node] keys (part_inter_rule.h)
   uint16_t *d_aq_act = nullptr;            // adaptive quantisation: E per [frame][superblock] (aq_activity_kernel)
   uint8_t *d_aq_map = nullptr;             // ... the quantiser index per [frame][superblock] (aq_map_kernel)
   Av1miQmEntry *d_qm = nullptr;        // quantiser-matrix steps (Av1miDevParams::qm_tab), one slice per quantiser slot, valid for qm_key = (slices, level, qidx, bit depth)
@@ -515,7 +517,7 @@ struct Workspace {
   int cdf_bs_log2 = -1;                // ... and the leaf size its compact image behind the blob was made for
   int params_on_device = 0;            // d_params holds the first so many blocks of h_params (1, or AV1MI_AQ_SLOTS with adaptive quantisation)
   Av1miChunkRecord *h_record = nullptr; unsigned long long *h_sse = nullptr;   // d_record and d_sse land here
-  size_t out_cap = 0, me64_bytes = 0, h_out_cap = 0;   // bytes of d_out, d_me64, h_out
+  size_t out_cap = 0, me64_bytes = 0, nodes_bytes = 0, h_out_cap = 0;   // bytes of d_out, d_me64, d_nodes, h_out
   std::vector<std::pair<void *, bool>> owned;   // every buffer above: (address, page-locked host memory)
 };
 
@@ -558,6 +560,9 @@ struct av1mi_ctx {
   bool wfit_on = false;           // ... and its Wiener fit (av1mi_lr_wiener_fit_result): the head of ws.h_wfit
   bool sym_order = true;          // AV1MI_SYM_ORDER, read when the context is made: 0 = symbolize in natural tile order everywhere
   uint32_t sym_tiles = 0;         // the tiles of the last chunk's weight-ordered table (av1mi_sym_order_result); 0: natural order
+  bool part_inter = false;        // this chunk's inter frames are partitioned from the search's node costs (partition_search = 2)
+  bool pi_keys = false;           // ... and it was coded in that mode: its search keys are reported too
+  uint32_t pi_frames = 0, pi_units = 0, pi_sbs = 0;   // the last chunk with a partition map: frames, 8x8 units and superblocks per frame (av1mi_inter_partition_result)
 };
 
 namespace {
@@ -659,6 +664,10 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   if (p.block_log2 >= 6 && p.keyint > 1) {   // candidate table of the 64x64 leaves' motion search
     const size_t nc = 2 * (size_t)(p.me_range ? p.me_range : 8) + 1, need = nf * nsb * nc * nc * sizeof(uint32_t);
     if (w.me64_bytes < need) { w.me64_bytes = 0; HIPCHK(c, ws_alloc(w, w.d_me64, need)); w.me64_bytes = need; }
+  }
+  if (p.partition_search == 2 && p.keyint > 1) {   // node tables of the inter frames' partition decision, on first use
+    const size_t need = nf * av1mi_pi_frame_nodes(r.ch / 8, r.cw / 8) * sizeof(uint32_t);
+    if (w.nodes_bytes < need) { w.nodes_bytes = 0; HIPCHK(c, ws_alloc(w, w.d_nodes, need)); w.nodes_bytes = need; }
   }
   if (r.aq && !w.d_aq_map) {
     HIPCHK(c, ws_alloc(w, w.d_aq_act, nf * nsb * sizeof(uint16_t)));
@@ -1142,6 +1151,19 @@ int av1mi_sym_order_result(const av1mi_ctx *c, uint32_t *order, uint8_t *classes
 }
 uint32_t av1mi_sym_order_tiles(const av1mi_ctx *c) { return c && !c->lf_levels.empty() ? c->sym_tiles : 0; }
 
+// The partition of the last chunk's frames and the integer search's keys, as they still stand on the device (the context's next chunk
+// overwrites them), fetched here - a diagnostic like av1mi_sym_order_result.
+uint32_t av1mi_inter_partition_units(const av1mi_ctx *c) { return c && c->pi_frames ? c->pi_units : 0; }
+int av1mi_inter_partition_result(const av1mi_ctx *c, uint32_t n_frames, uint32_t *masks, uint64_t *keys) {
+  if (!c || !masks || !keys || n_frames == 0 || c->pi_frames != n_frames || c->lf_levels.empty()) return AV1MI_E_INVALID_ARG;
+  if (hipSetDevice(c->device) != hipSuccess) return AV1MI_E_HIP;
+  if (hipMemcpy(masks, c->ws.d_part, (size_t)n_frames * c->pi_sbs * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) return AV1MI_E_HIP;
+  // (the keys are the node-mode search's: a chunk without it - partition_search = 1, or no inter frame - reports zeros)
+  if (!c->pi_keys) memset(keys, 0, (size_t)n_frames * c->pi_units * sizeof(uint64_t));
+  else if (hipMemcpy(keys, c->ws.d_me, (size_t)n_frames * c->pi_units * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess) return AV1MI_E_HIP;
+  return AV1MI_OK;
+}
+
 uint32_t av1mi_lr_wiener_fit_units(const av1mi_ctx *c) { return c ? c->fit_plane_units : 0; }
 // The Wiener fit of the context's last chunk, likewise.
 int av1mi_lr_wiener_fit_result(const av1mi_ctx *c, uint32_t n_frames, int8_t *units, uint64_t *err) {
@@ -1346,6 +1368,7 @@ static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
   HIPCHK(c, hipMemsetAsync(w.d_me, 0xFF, (size_t)n_frames * nb8 * 8, s2));
   uint32_t *acc64 = P.max_bs_log2 >= 6 ? w.d_me64 : nullptr;
   if (acc64) HIPCHK(c, hipMemsetAsync(acc64, 0, (size_t)n_frames * nsb * (2 * P.me_range + 1) * (2 * P.me_range + 1) * sizeof(uint32_t), s2));
+  if (c->part_inter) HIPCHK(c, hipMemsetAsync(w.d_nodes, 0xFF, (size_t)n_frames * av1mi_pi_frame_nodes(P.b8_rows, P.b8_cols) * sizeof(uint32_t), s2));
   // one launch + one event per frame, enqueued from inside the frame loop below, behind the first frame's chain kernels: the chain's first
   // kernel (the key frame's reconstruction needs no vectors) no longer waits on the host for 120 - 180 API calls (under
   // the profiler the chain started 6.4 ms after the chunk's first kernel; unprofiled the calls take ~ 8 us each and one chunk gains nothing).
@@ -1386,7 +1409,9 @@ static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
       for (uint32_t g = 1; g < n_frames; g++) {
         if (!av1mi_frame_is_inter(P, (int)g)) continue;
         if (centre) HIPCHK(c, av1mi_launch_presearch(&P, w.d_quarter, w.d_centre, (int)g, 1, s2));
-        HIPCHK(c, av1mi_launch_motion_search(&P, src, w.d_me, P.me_range, (int)g, 1, acc64, centre, s2));
+        // partition_search = 2: the search keeps every node's best candidate, the decision writes the frame's masks and leaf keys
+        if (c->part_inter) HIPCHK(c, av1mi_launch_inter_partition(&P, src, w.d_me, P.me_range, (int)g, 1, acc64, centre, w.d_nodes, w.d_part, s2));
+        else HIPCHK(c, av1mi_launch_motion_search(&P, src, w.d_me, P.me_range, (int)g, 1, acc64, centre, s2));
         if (P.subpel) HIPCHK(c, av1mi_launch_subpel_refine(&P, src, w.d_me, w.d_me_sub, P.me_range, (int)g, 1, s2));
         HIPCHK(c, hipEventRecord(c->me_ev[g], s2));
       }
@@ -1531,6 +1556,7 @@ static int run_chunk(av1mi_ctx *c, const av1mi_params *params, const void *frame
                      av1mi_buf *out, uint32_t *frame_sizes, void *recon, av1mi_report *report) {
   out->data = nullptr; out->size = 0;
   c->lf_levels.clear(); c->lf_errs.clear(); c->fit_units = 0; c->fit_plane_units = 0; c->fit_on = false; c->wfit_on = false; c->sym_tiles = 0;
+  c->pi_frames = 0;
   Resolved r;
   int rc = resolve(params, &r);
   if (rc) { set_err(c, "invalid parameters"); return rc; }
@@ -1540,6 +1566,7 @@ static int run_chunk(av1mi_ctx *c, const av1mi_params *params, const void *frame
   Workspace &w = c->ws;
   c->P = dev_params(r, n_frames, c->cap_scale, w.d_part, w.d_qm, w.d_aq_map, w.d_cdef_err, w.d_cdef_idx, w.d_cdef_sel, w.d_lf_err, w.d_lf_sel,
                      w.d_record, w.d_sym, w.fit.code, w.wfit.code);
+  c->part_inter = r.p.partition_search == 2 && c->P.keyint > 1 && n_frames > 1;   // (the chunk goes through schedule_inter)
   const void *d_src = nullptr;
   rc = prepare_chunk(c, r, frames, n_frames, frames_on_device, &d_src);
   if (rc) return rc;
@@ -1554,7 +1581,9 @@ static int run_chunk(av1mi_ctx *c, const av1mi_params *params, const void *frame
     HIPCHK(c, av1mi_launch_pack(&P, w.d_slots, w.d_tile_bytes, w.d_tile_off, w.d_frame_size, w.d_payload,
                                 reinterpret_cast<unsigned long long *>(w.d_record + 1), w.d_hdr, w.d_out, &w.d_record->overflow, stage, c->stream));
   HIPCHK(c, hipEventRecord(c->ev[EV_PACK_DONE], c->stream));
-  return download_chunk(c, r, n_frames, frames_on_device, out, frame_sizes, recon, report);
+  rc = download_chunk(c, r, n_frames, frames_on_device, out, frame_sizes, recon, report);
+  if (rc == AV1MI_OK && P.part_map) { c->pi_keys = c->part_inter; c->pi_frames = n_frames; c->pi_units = (uint32_t)(P.b8_rows * P.b8_cols); c->pi_sbs = (uint32_t)(P.sb_rows * P.sb_cols); }
+  return rc;
 }
 
 }  // extern "C"

@@ -62,6 +62,11 @@ hipError_t av1mi_launch_presearch(const Av1miDevParams *P, const uint16_t *quart
 // centre: pre-search centre codes [frame][superblock], or null.
 hipError_t av1mi_launch_motion_search(const Av1miDevParams *P, const void *frames, unsigned long long *best, int me_range, int frame0,
                                       int count, uint32_t *acc64, const uint32_t *centre, hipStream_t stream);
+// partition_search = 2, instead of av1mi_launch_motion_search: the search in node mode - every node of the partition tree keeps its best
+// candidate in `nodes`, the [frame][level][node] tables of part_inter_rule.h filled with 0xFF bytes - then the frames' partition decided
+// from those costs: the masks into `part` ([frame][superblock]), the leaves' keys into `best`.  acc64, centre as above.
+hipError_t av1mi_launch_inter_partition(const Av1miDevParams *P, const void *frames, unsigned long long *best, int me_range, int frame0, int count,
+                                        uint32_t *acc64, const uint32_t *centre, uint32_t *nodes, uint32_t *part, hipStream_t stream);
 // Refines the frames' vectors: `best` = the full search's keys (av1mi_launch_motion_search on the same stream before), `refined` = same
 // layout, what the reconstruction reads with subpel = 1.
 hipError_t av1mi_launch_subpel_refine(const Av1miDevParams *P, const void *frames, const unsigned long long *best, unsigned long long *refined,

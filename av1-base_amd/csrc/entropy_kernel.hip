@@ -192,6 +192,7 @@ struct TileGeo {
   int tox, toy;     // origin of the current superblock inside the tile, luma pixels (0 or 64)
   int sb_x, sb_y;   // luma pixel origin
   int max_x4_y, max_y4_y, max_x4_c, max_y4_c;  // frame limits in 4x4 units, superblock-local
+  int big;          // the chunk has 64x64 leaves (block_log2 = 6): 64-point luma transforms can occur
 };
 
 // exclusive prefix sum over the wave with DPP row shifts and broadcasts (seven additions; the shuffle form went through LDS six times)
@@ -291,7 +292,12 @@ __device__ __forceinline__ void sym_coeffs(Sym &y, const int lane, const int ada
     // adapt per lane in K4; any further combination is resolved here (cooperatively, slowly).
     const int combo = txs * 2 + ptype;
     int slot0 = -1;
-    if (adapt) {
+    // (A tile of several superblocks can hold 64-point AND 32-point luma transforms - a 64x64 leaf beside a split or edge superblock.
+    // Their base CDFs differ but they SHARE the range CDFs (size class min(txs, 3)): in two slots, or a slot and the resolved path, the
+    // shared rows would adapt in two copies.  Both go the resolved path there, whose one copy is the decoder's; a chunk without
+    // 64x64 leaves has no 64-point transform and keeps its slots.)
+    const bool shared_br = FULL && TSB > 1 && tg.big && ptype == 0 && txs >= 3;
+    if (adapt && !shared_br) {
       if (y.combo0 == combo) slot0 = 0;
       else if (y.combo0 < 0) { y.combo0 = combo; slot0 = 0; }
       else if (y.combo1 == combo) slot0 = SLOTS_PER_COMBO;
@@ -713,7 +719,7 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
   const int sb = sbr * P.sb_cols + sbc;
   TileGeo tg;
   tg.tox = (si % TSB) * 64; tg.toy = (si / TSB) * 64;
-  tg.sb_x = sbc * 64; tg.sb_y = sbr * 64;
+  tg.sb_x = sbc * 64; tg.sb_y = sbr * 64; tg.big = P.max_bs_log2 >= 6;
   tg.max_x4_y = P.mi_cols - sbc * 16; tg.max_y4_y = P.mi_rows - sbr * 16;
   tg.max_x4_c = (P.mi_cols >> 1) - sbc * 8; tg.max_y4_c = (P.mi_rows >> 1) - sbr * 8;
   const int tox = tg.tox, toy = tg.toy, tox8 = tox >> 3, toy8 = toy >> 3;

@@ -24,6 +24,7 @@
 #include "av1mi_dev.h"
 #include "av1mi_launch.h"
 #include "av1_tables.h"
+#include "part_inter_rule.h"
 
 namespace {
 
@@ -47,12 +48,87 @@ __device__ __forceinline__ bool cell_in_leaf64(const Av1miDevParams &P, int f, i
   return !av1mi_node_split(P.width, P.height, P.min_bs_log2, P.max_bs_log2, P.part_map != nullptr, sb_mask(P, f, cx, cy), cx & ~63, cy & ~63, 0, 0, 6);
 }
 
-template <typename PIX, int R>
+// ---- node mode (av1mi_params.partition_search = 2; part_inter_rule.h): the search keeps the best candidate of
+// every NODE of the partition tree, not of every leaf - the partition of the frame is decided from these costs afterwards
+// (inter_partition_kernel).  The (cell, dy) wave has the sixteen 8x8 sub-block SADs of every dx in LDS; lane = dx sums them to the 16 + 4
+// + 1 node SADs of the cell, adds each node's vector penalty and forms 32-bit keys (cost << 11) | index (cost < 2^21 up to 32x32, index
+// < 2^11 at R <= 16).  Each of the 21 keys is reduced over the lanes with DPP row rotations as operands of the minimum and one
+// v_readlane per row of 16 lanes that holds candidates (the 64-bit shuffles of the leaf search go through the LDS pipe); lane i keeps
+// minimum i, and one atomic instruction posts the 21 minima to the frame's node tables.  Nodes whose origin is outside the frame - the
+// cell overhangs the grid of 8x8 units at the right and bottom edges - post nothing and index nothing.
+__device__ __forceinline__ uint32_t row_min_u32(uint32_t v) {
+  uint32_t t;
+  t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x128, 0xF, 0xF, false); v = t < v ? t : v;   // row_ror 8, 4, 2, 1
+  t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x124, 0xF, 0xF, false); v = t < v ? t : v;
+  t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x122, 0xF, 0xF, false); v = t < v ? t : v;
+  t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x121, 0xF, 0xF, false); v = t < v ? t : v;
+  return v;
+}
+template <int ROWS>
+__device__ __forceinline__ uint32_t wave_min_rows(uint32_t v) {   // minimum over the first ROWS rows of 16 lanes, wave-uniform
+  v = row_min_u32(v);
+  uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)v, 0);
+  if (ROWS > 1) { const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)v, 16); m = t < m ? t : m; }
+  if (ROWS > 2) { const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)v, 32); m = t < m ? t : m; }
+  return m;
+}
+
+template <int R>
+__device__ __forceinline__ void post_node_costs(const Av1miDevParams &P, int f, int cx, int cy, int dy, int dyi, int ccx, const uint32_t (*sad8)[16],
+                                                uint32_t *__restrict__ acc64, uint32_t *__restrict__ nodes_all) {
+  constexpr int NC = 2 * R + 1, ROWS = (NC + 15) / 16;
+  static_assert(NC * NC <= 2048 && ROWS <= 3, "a node key holds an 11-bit candidate index");
+  const int lane = threadIdx.x, W = P.width, H = P.height;
+  const bool live = lane < NC;
+  const int dxi = live ? lane : 0, dx = dxi - R + ccx;
+  const uint32_t pen = (uint32_t)(iabs(dx) + iabs(dy)), idx = (uint32_t)(dyi * NC + dxi);
+  uint32_t s8[16], s16[4];
+#pragma unroll
+  for (int i = 0; i < 16; i++) s8[i] = sad8[dxi][i];
+#pragma unroll
+  for (int q = 0; q < 4; q++) { const int o = (q >> 1) * 8 + (q & 1) * 2; s16[q] = s8[o] + s8[o + 1] + s8[o + 4] + s8[o + 5]; }
+  const uint32_t s32 = s16[0] + s16[1] + s16[2] + s16[3];
+  // the displaced node stays within 16 samples of the frame: per node row (wave-uniform) and per node column (per lane)
+  auto y_ok = [&](int oy, int n) { return cy + oy + dy >= -16 && cy + oy + dy + n <= H + 16; };
+  auto x_ok = [&](int ox, int n) { return live && cx + ox + dx >= -16 && cx + ox + dx + n <= W + 16; };
+  uint32_t res = 0xFFFFFFFFu;   // lane i: minimum i - 0 .. 15 the 8x8 nodes (raster), 16 .. 19 the 16x16 nodes (raster), 20 the 32x32 node
+#pragma unroll
+  for (int i = 0; i < 16; i++) {
+    const uint32_t key = x_ok((i & 3) * 8, 8) && y_ok((i >> 2) * 8, 8) ? ((s8[i] + 8u * pen) << 11) | idx : 0xFFFFFFFFu;
+    const uint32_t m = wave_min_rows<ROWS>(key);
+    res = lane == i ? m : res;
+  }
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const uint32_t key = x_ok((q & 1) * 16, 16) && y_ok((q >> 1) * 16, 16) ? ((s16[q] + 16u * pen) << 11) | idx : 0xFFFFFFFFu;
+    const uint32_t m = wave_min_rows<ROWS>(key);
+    res = lane == 16 + q ? m : res;
+  }
+  {
+    const uint32_t key = x_ok(0, 32) && y_ok(0, 32) ? ((s32 + 32u * pen) << 11) | idx : 0xFFFFFFFFu;
+    const uint32_t m = wave_min_rows<ROWS>(key);
+    res = lane == 20 ? m : res;
+  }
+  if (lane < 21) {
+    const int bsl = lane < 16 ? 3 : (lane < 20 ? 4 : 5), j = lane < 16 ? lane : (lane < 20 ? lane - 16 : 0);
+    const int x = cx + (lane < 16 ? (j & 3) * 8 : (j & 1) * 16), y = cy + (lane < 16 ? (j >> 2) * 8 : (j >> 1) * 16);
+    if (x < W && y < H && res != 0xFFFFFFFFu)
+      atomicMin(&nodes_all[(size_t)f * av1mi_pi_frame_nodes(P.b8_rows, P.b8_cols) + av1mi_pi_node_slot(P.b8_rows, P.b8_cols, bsl, x, y)], res);
+  }
+  // block_log2 = 6: every cell adds its 32x32 sums to its superblock's candidate table (the 64x64 node's cost)
+  if (acc64 && live) {
+    const size_t sb = (size_t)f * P.sb_rows * P.sb_cols + (size_t)(cy >> 6) * P.sb_cols + (cx >> 6);
+    atomicAdd(&acc64[(sb * NC + dyi) * NC + lane], s32);
+  }
+}
+
+template <typename PIX, int R, bool NODES = false>
 __global__ void __launch_bounds__(64) motion_search_kernel(Av1miDevParams P, const PIX *__restrict__ frames,
                                                           unsigned long long *__restrict__ best_all /* [frame][8x8 unit] */, int frame0,
                                                           int vec_ok /* frames are 16-byte aligned */,
                                                           uint32_t *__restrict__ acc64 /* 64x64 leaves: [frame][superblock][candidate] SAD sums, zeroed */,
-                                                          const uint32_t *__restrict__ centre /* pre-search: [frame][superblock] centre codes, or null */) {
+                                                          const uint32_t *__restrict__ centre /* pre-search: [frame][superblock] centre codes, or null */,
+                                                          uint32_t *__restrict__ nodes /* NODES: [frame][level][node] keys, all-ones (best_all is not written) */) {
   constexpr int NC = 2 * R + 1;
   __shared__ uint32_t sad8[NC][16];  // [dx][8x8 sub-block of the cell, raster]
   const int f = frame0 + blockIdx.z;
@@ -126,6 +202,10 @@ __global__ void __launch_bounds__(64) motion_search_kernel(Av1miDevParams P, con
     }
   }
   __syncthreads();
+  if constexpr (NODES) {   // node mode: every node's best candidate of this dy; no mask is read, no leaf key written
+    post_node_costs<R>(P, f, cx, cy, dy, dyi, ccx, sad8, acc64, nodes);
+    return;
+  }
   // ---- a cell of a 64x64 leaf: the leaf's SAD of a candidate is the sum over its four cells - every (cell, dy) wave adds its
   // cell sums to the leaf's candidate table; me64_reduce_kernel takes the minimum afterwards
   if (cell_in_leaf64(P, f, cx, cy)) {
@@ -206,6 +286,74 @@ __global__ void __launch_bounds__(64) me64_reduce_kernel(Av1miDevParams P, const
   }
   for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(key, o, 64); key = t < key ? t : key; }
   if (lane == 0) best_all[(size_t)f * P.b8_rows * P.b8_cols + (size_t)(y >> 3) * P.b8_cols + (x >> 3)] = key;
+}
+
+// inter_partition_kernel (partition_search = 2): one wave per superblock of an inter frame decides the superblock's partition from the
+// node tables the node-mode search filled - the rule is part_inter_rule.h's, bottom up.  The 64x64 node's key comes from the candidate
+// table as in me64_reduce_kernel (not launched in this mode).  Lane l holds the 8x8 node 21 + l and, l < 21, the larger node l (heap
+// order: the node's mask bit); a level's J go through LDS to the level above, one pass per level.  Writes the superblock's mask (a ballot
+// over the nodes that were reached and decided to split) and, at every leaf's origin unit, the leaf's key as the leaf search writes it.
+__global__ void __launch_bounds__(64) inter_partition_kernel(Av1miDevParams P, const uint32_t *__restrict__ acc64, const uint32_t *__restrict__ nodes_all,
+                                                            uint32_t *__restrict__ part, unsigned long long *__restrict__ best_all, int frame0, int R,
+                                                            const uint32_t *__restrict__ centre) {
+  __shared__ uint32_t sJ[AV1MI_PI_NODES];
+  __shared__ uint8_t sState[AV1MI_PI_NODES];
+  const int f = frame0 + blockIdx.y;
+  if (!av1mi_frame_is_inter(P, f)) return;
+  const int sb = blockIdx.x, sb_x = (sb % P.sb_cols) * 64, sb_y = (sb / P.sb_cols) * 64;
+  const int NC = 2 * R + 1, lane = threadIdx.x, W = P.width, H = P.height;
+  const uint32_t ccode = centre ? centre[(size_t)f * P.sb_rows * P.sb_cols + sb] : 0u;
+  const int ccx = 8 * av1mi_sext12(ccode), ccy = 8 * av1mi_sext12(ccode >> 12);
+  const unsigned long long ctop = (unsigned long long)ccode << 40;
+  // the 64x64 node: cost and minimum over its candidate table
+  unsigned long long key64 = ~0ull;
+  if (acc64) {
+    const uint32_t *tab = acc64 + ((size_t)f * P.sb_rows * P.sb_cols + sb) * NC * NC;
+    for (int c = lane; c < NC * NC; c += 64) {
+      const int dy = c / NC - R + ccy, dx = c % NC - R + ccx;
+      if (sb_x + dx < -16 || sb_x + dx + 64 > W + 16 || sb_y + dy < -16 || sb_y + dy + 64 > H + 16) continue;
+      const unsigned long long cost = (unsigned long long)tab[c] + (unsigned long long)(64 * (iabs(dx) + iabs(dy)));
+      const unsigned long long k = (cost << 16) | (unsigned long long)c;
+      key64 = k < key64 ? k : key64;
+    }
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(key64, o, 64); key64 = t < key64 ? t : key64; }
+  }
+  // this lane's nodes, their positions and keys (cost, candidate index); a node outside the frame reads nothing
+  const uint32_t *nodes = nodes_all + (size_t)f * av1mi_pi_frame_nodes(P.b8_rows, P.b8_cols);
+  const int ia = 21 + lane, ib = lane < 21 ? lane : -1;
+  int xa, ya, la, xb = 0, yb = 0, lb = 3;
+  av1mi_pi_node_pos(ia, &xa, &ya, &la);
+  if (ib >= 0) av1mi_pi_node_pos(ib, &xb, &yb, &lb);
+  xa += sb_x; ya += sb_y; xb += sb_x; yb += sb_y;
+  uint32_t cLa = AV1MI_PI_INF, idxa = 0, cLb = AV1MI_PI_INF, idxb = 0;
+  if (xa < W && ya < H) {
+    const uint32_t k = nodes[av1mi_pi_node_slot(P.b8_rows, P.b8_cols, 3, xa, ya)];
+    if (k != 0xFFFFFFFFu) { cLa = k >> 11; idxa = k & 0x7FFu; }
+  }
+  if (ib > 0 && xb < W && yb < H) {
+    const uint32_t k = nodes[av1mi_pi_node_slot(P.b8_rows, P.b8_cols, lb, xb, yb)];
+    if (k != 0xFFFFFFFFu) { cLb = k >> 11; idxb = k & 0x7FFu; }
+  }
+  if (ib == 0 && key64 != ~0ull) { cLb = (uint32_t)(key64 >> 16); idxb = (uint32_t)(key64 & 0xFFFF); }
+  int sta, stb = AV1MI_PI_OUT;
+  sJ[ia] = av1mi_pi_node(W, H, P.min_bs_log2, P.max_bs_log2, P.ac_q, xa, ya, 3, cLa, nullptr, &sta);
+  sState[ia] = (uint8_t)sta;
+  __syncthreads();
+  for (int level = 4; level <= 6; level++) {
+    if (ib >= 0 && lb == level) {
+      sJ[ib] = av1mi_pi_node(W, H, P.min_bs_log2, P.max_bs_log2, P.ac_q, xb, yb, lb, cLb, &sJ[4 * ib + 1], &stb);
+      sState[ib] = (uint8_t)stb;
+    }
+    __syncthreads();
+  }
+  const bool ra = av1mi_pi_reached(sState, ia) != 0, rb = ib >= 0 && av1mi_pi_reached(sState, ib) != 0;
+  const unsigned long long split = __ballot(rb && stb == AV1MI_PI_SPLIT);
+  if (lane == 0) part[(size_t)f * P.sb_rows * P.sb_cols + sb] = (uint32_t)split & 0x1FFFFFu;
+  unsigned long long *best = best_all + (size_t)f * P.b8_rows * P.b8_cols;
+  if (ra && (sta == AV1MI_PI_LEAF || sta == AV1MI_PI_KEEP))
+    best[(size_t)(ya >> 3) * P.b8_cols + (xa >> 3)] = cLa == AV1MI_PI_INF ? ~0ull : ctop | ((unsigned long long)cLa << 16) | idxa;
+  if (rb && (stb == AV1MI_PI_LEAF || stb == AV1MI_PI_KEEP))
+    best[(size_t)(yb >> 3) * P.b8_cols + (xb >> 3)] = cLb == AV1MI_PI_INF ? ~0ull : ctop | ((unsigned long long)cLb << 16) | idxb;
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -646,13 +794,32 @@ extern "C" hipError_t av1mi_launch_motion_search(const Av1miDevParams *P, const 
   dim3 grid(cells, 2 * me_range + 1, count);
   const int vec_ok = ((uintptr_t)frames & 15) == 0;  // frame size in bytes is a multiple of 32
   if (P->bit_depth == 8) {
-    if (me_range == 8) hipLaunchKernelGGL((motion_search_kernel<uint8_t, 8>), grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, best, frame0, vec_ok, acc64, centre);
-    else hipLaunchKernelGGL((motion_search_kernel<uint8_t, 16>), grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, best, frame0, vec_ok, acc64, centre);
+    if (me_range == 8) hipLaunchKernelGGL((motion_search_kernel<uint8_t, 8>), grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, best, frame0, vec_ok, acc64, centre, (uint32_t *)nullptr);
+    else hipLaunchKernelGGL((motion_search_kernel<uint8_t, 16>), grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, best, frame0, vec_ok, acc64, centre, (uint32_t *)nullptr);
   } else {
-    if (me_range == 8) hipLaunchKernelGGL((motion_search_kernel<uint16_t, 8>), grid, dim3(64), 0, stream, *P, (const uint16_t *)frames, best, frame0, vec_ok, acc64, centre);
-    else hipLaunchKernelGGL((motion_search_kernel<uint16_t, 16>), grid, dim3(64), 0, stream, *P, (const uint16_t *)frames, best, frame0, vec_ok, acc64, centre);
+    if (me_range == 8) hipLaunchKernelGGL((motion_search_kernel<uint16_t, 8>), grid, dim3(64), 0, stream, *P, (const uint16_t *)frames, best, frame0, vec_ok, acc64, centre, (uint32_t *)nullptr);
+    else hipLaunchKernelGGL((motion_search_kernel<uint16_t, 16>), grid, dim3(64), 0, stream, *P, (const uint16_t *)frames, best, frame0, vec_ok, acc64, centre, (uint32_t *)nullptr);
   }
   if (P->max_bs_log2 >= 6)
     hipLaunchKernelGGL(me64_reduce_kernel, dim3(P->sb_rows * P->sb_cols, count), dim3(64), 0, stream, *P, acc64, best, frame0, me_range, centre);
+  return hipGetLastError();
+}
+
+// partition_search = 2: the node-mode search of `count` frames from frame0, then the decision of their partition - masks into `part`
+// ([frame][superblock]), the leaves' keys into `best`.  nodes: the [frame][level][node] tables, all-ones; acc64 as above.
+extern "C" hipError_t av1mi_launch_inter_partition(const Av1miDevParams *P, const void *frames, unsigned long long *best, int me_range, int frame0, int count,
+                                                   uint32_t *acc64, const uint32_t *centre, uint32_t *nodes, uint32_t *part, hipStream_t stream) {
+  const int cells = ((P->width + 31) >> 5) * ((P->height + 31) >> 5);
+  dim3 grid(cells, 2 * me_range + 1, count);
+  const int vec_ok = ((uintptr_t)frames & 15) == 0;
+  if (P->bit_depth == 8) {
+    if (me_range == 8) hipLaunchKernelGGL((motion_search_kernel<uint8_t, 8, true>), grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, best, frame0, vec_ok, acc64, centre, nodes);
+    else hipLaunchKernelGGL((motion_search_kernel<uint8_t, 16, true>), grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, best, frame0, vec_ok, acc64, centre, nodes);
+  } else {
+    if (me_range == 8) hipLaunchKernelGGL((motion_search_kernel<uint16_t, 8, true>), grid, dim3(64), 0, stream, *P, (const uint16_t *)frames, best, frame0, vec_ok, acc64, centre, nodes);
+    else hipLaunchKernelGGL((motion_search_kernel<uint16_t, 16, true>), grid, dim3(64), 0, stream, *P, (const uint16_t *)frames, best, frame0, vec_ok, acc64, centre, nodes);
+  }
+  hipLaunchKernelGGL(inter_partition_kernel, dim3(P->sb_rows * P->sb_cols, count), dim3(64), 0, stream, *P, (const uint32_t *)acc64, (const uint32_t *)nodes, part, best,
+                     frame0, me_range, centre);
   return hipGetLastError();
 }

@@ -145,7 +145,11 @@ typedef struct {
   uint32_t partition_search; /* 1: content-driven partition - a node of the partition tree larger than `min_block_log2` and not larger than `block_log2`
                                splits when its four quadrants differ in activity (largest quadrant variance of the source luma > 4 x the
                                smallest + (ac_q / 16)^2), so quiet areas keep large blocks and edges / small objects get small ones; decided
-                               for all frames of a chunk by one GPU pass over the source.  0 (default): every block is `block_log2` */
+                               for all frames of a chunk by one GPU pass over the source.  2: key frames as with 1; an inter frame's
+                               nodes are decided bottom up from the motion search's block costs instead - the search keeps the best
+                               candidate of every node of the tree, and a node splits iff its children's costs plus a penalty of
+                               (n^2 (ac_q / 16)) >> 3 undercut its own (av1mi_inter_partition_result reports
+                               the masks).  3 and above are refused.  0 (default): every block is `block_log2` */
   uint32_t min_block_log2;  /* smallest leaf under partition_search: 3 (8x8, default when 0) .. block_log2 */
   uint32_t me_presearch;    /* inter frames: 1 = hierarchical motion search - a quarter-resolution search of +-64 luma samples per 32x32 cell finds the
                                centre the full-resolution search of +-me_range then runs around (row a13's "1/4-res ... full"); 0 (default): the
@@ -278,6 +282,19 @@ uint32_t av1mi_lr_wiener_fit_units(const av1mi_ctx *ctx);
  * AV1MI_E_INVALID_ARG if the last chunk was symbolized in natural order (av1mi_sym_order_tiles is 0 then) or n is not its tile count. */
 int av1mi_sym_order_result(const av1mi_ctx *ctx, uint32_t *order, uint8_t *classes, uint32_t n);
 uint32_t av1mi_sym_order_tiles(const av1mi_ctx *ctx);
+
+/* ---- the inter frames' partition of the last chunk ------------------------------------------
+ * With partition_search 1 or 2: masks[f * n_sb + sb] = the split mask of superblock sb
+ * (raster order, n_sb = ceil(w / 64) * ceil(h / 64)) of frame f of the context's last successfully encoded chunk - bit 0 the 64x64 node,
+ * bits 1 .. 4 the 32x32 nodes, bits 5 .. 20 the 16x16 nodes, each level in Z order; the source rule's masks (key frames, and every
+ * frame under partition_search = 1) hold a bit for every node the rule would split, an inter frame's under partition_search = 2 only for a
+ * node that was reached and decided - and, with partition_search = 2 and inter frames in the chunk (zeros otherwise), keys[f * n_units + u] = the integer search's key at 8x8 unit u
+ * (raster order over the coded size): at a leaf's origin unit (centre code << 40) | (cost << 16) | candidate index, UINT64_MAX if the leaf
+ * has no valid candidate; other units and key frames are unspecified.  n_units = av1mi_inter_partition_units (0: the last chunk
+ * had no partition map).  The call reads both arrays back from the device, where they stand until the context's next chunk.
+ * AV1MI_E_INVALID_ARG if n_frames is not that chunk's frame count. */
+int av1mi_inter_partition_result(const av1mi_ctx *ctx, uint32_t n_frames, uint32_t *masks, uint64_t *keys);
+uint32_t av1mi_inter_partition_units(const av1mi_ctx *ctx);
 
 /* ---- the drop-in for `run_av1an` ---------------------------------------------------------
  * Replaces  pub fn run_av1an(params: &Av1anEncodeParams) -> Result<(), EncodeError>

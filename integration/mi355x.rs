@@ -30,7 +30,7 @@ pub struct Av1miParams {            // include/av1mi.h: av1mi_params
     pub cfl: u32,                   // 1 = chroma-from-luma prediction is a candidate (key frames, blocks up to 32x32)
     pub tx_search: u32,             // 1 = identity transform (IDTX) for sparse intra luma residuals
     pub color_primaries: u32, pub transfer_characteristics: u32, pub matrix_coefficients: u32,   // CICP colour description (0 / 0 / 0 = none; HDR10: 9 / 16 / 9)
-    pub partition_search: u32,      // 1 = content-driven partition between min_block_log2 and block_log2
+    pub partition_search: u32,      // 1 = content-driven partition between min_block_log2 and block_log2; 2 = key frames as 1, inter frames partitioned from the motion search's node costs
     pub min_block_log2: u32,        // smallest leaf under partition_search (0 = 3: 8x8)
     pub me_presearch: u32,          // 1 = quarter-resolution pre-search (+-64) before the full-resolution search
     pub cdef_search: u32,           // 0 = fixed CDEF strengths; k = 1..4 = per-frame / per-superblock search over 2^(k-1) strength pairs

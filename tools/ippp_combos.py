@@ -19,5 +19,7 @@ run("bs6 fixed", block_log2=6)
 run("bs5 partition 3..5", block_log2=5, partition_search=1, min_block_log2=3)
 run("bs6 partition 3..6", block_log2=6, partition_search=1, min_block_log2=3)
 run("bs6 partition 4..6", block_log2=6, partition_search=1, min_block_log2=4)
+run("bs6 inter partition 3..6", block_log2=6, partition_search=2, min_block_log2=3)
+run("bs6 inter partition 4..6", block_log2=6, partition_search=2, min_block_log2=4)
 run("bs5 presearch", block_log2=5, me_presearch=1)
 run("bs6 presearch", block_log2=6, me_presearch=1)
