@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include "lr_geometry.h"
 #include "tile_weight_rule.h"
+#include "wiener_fit_rule.h"   // and lr_fit_rule.h: the counts that size the fits' buffers below
 #ifdef __HIPCC__
 #define AV1MI_HD __host__ __device__
 #else
@@ -208,7 +209,25 @@ struct Av1miLrFit {
   int8_t *rec;                // [4]: choice, set, xqd0, xqd1
   uint32_t *code;             // [2]: bits, length of a self-guided unit's syntax
   uint32_t mask;              // the sets searched (never 0)
+  // the buffers from frame `frame0` on, a frame being `upf` units (three planes)
+  Av1miLrFit at_frame(int frame0, size_t upf) const {
+    const size_t u = (size_t)frame0 * upf;
+    return { sums + u * AV1MI_LR_FIT_SETS * 5, err + u * AV1MI_LR_FIT_CANDS, rec + u * 4, code + u * 2, mask };
+  }
 };
+// A chunk's `n` units are one block, contiguous from its head: errors, records - the part the host fetches for av1mi_lr_fit_result -
+// then, from a multiple of 8 bytes on, sums and codes
+inline size_t av1mi_lr_fit_result_bytes(size_t n) { return n * (AV1MI_LR_FIT_CANDS * 8 + 4); }
+inline size_t av1mi_lr_fit_bytes(size_t n) { return av1mi_lr_fit_result_bytes(n) + 8 + n * (AV1MI_LR_FIT_SETS * 5 * 8 + 2 * 4); }
+inline Av1miLrFit av1mi_lr_fit_split(void *block, size_t n, uint32_t mask) {
+  Av1miLrFit F;
+  F.err = reinterpret_cast<unsigned long long *>(block);
+  F.rec = reinterpret_cast<int8_t *>(F.err + n * AV1MI_LR_FIT_CANDS);
+  F.sums = reinterpret_cast<long long *>(F.rec + ((n * 4 + 7) & ~(size_t)7));
+  F.code = reinterpret_cast<uint32_t *>(F.sums + n * AV1MI_LR_FIT_SETS * 5);
+  F.mask = mask;
+  return F;
+}
 
 // the Wiener fit's buffers, likewise [frame][plane 0..2][unit] (lr_wfit_kernel.hip)
 struct Av1miLrWfit {
@@ -216,7 +235,22 @@ struct Av1miLrWfit {
   int8_t *rec;                // [8]: final choice 0 .. 23, candidate present, cv0, cv1, cv2, ch0, ch1, ch2
   long long *sums;            // [27] (wiener_fit_rule.h)
   uint32_t *code;             // [3]: bits 0-31, bits 32-63, length of a Wiener unit's syntax
+  Av1miLrWfit at_frame(int frame0, size_t upf) const {
+    const size_t u = (size_t)frame0 * upf;
+    return { err + u, rec + u * 8, sums + u * AV1MI_LR_WFIT_SUMS, code + u * 3 };
+  }
 };
+// likewise one block: errors, records - the part the host fetches for av1mi_lr_wiener_fit_result - sums, codes
+inline size_t av1mi_lr_wfit_result_bytes(size_t n) { return n * (8 + 8); }
+inline size_t av1mi_lr_wfit_bytes(size_t n) { return av1mi_lr_wfit_result_bytes(n) + n * (AV1MI_LR_WFIT_SUMS * 8 + 3 * 4); }
+inline Av1miLrWfit av1mi_lr_wfit_split(void *block, size_t n) {
+  Av1miLrWfit F;
+  F.err = reinterpret_cast<unsigned long long *>(block);
+  F.rec = reinterpret_cast<int8_t *>(F.err + n);
+  F.sums = reinterpret_cast<long long *>(F.rec + n * 8);
+  F.code = reinterpret_cast<uint32_t *>(F.sums + n * AV1MI_LR_WFIT_SUMS);
+  return F;
+}
 
 // ---- which symbolize variant owns a tile (entropy_kernel.hip: the kernels decide per tile, the launcher sizes its grids by it)
 // Under a content-driven partition (P.part_map, device memory: device code only): does the superblock keep one block size throughout -

@@ -361,23 +361,20 @@ std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint
 // reference).  The writers (lr_put_signed_ref and what it calls, av1mi_lr_sgr_code) are lr_fit_rule.h's: the self-guided
 // fit runs them on the device, and the fixed candidates' constant strings below come from the same functions.
 using BitString = Av1miBitString;
-const int8_t kWienerCand[3][3] = { { 0, 0, -4 }, { 1, -3, -6 }, { 3, -7, 15 } };  // == lr_pieces.h, oracle/av1o_lr.c
-// chroma (enable_lr 3 / 4; tap 0 is 0 and not coded, §5.11.58)
-const int8_t kWienerCandUV[3][3] = { { 0, 0, -4 }, { 0, 0, 16 }, { 0, 6, 20 } };  // == lr_pieces.h
-const int8_t kSgrCand[3][3] = { { 9, 31, 31 }, { 9, 0, 31 }, { 9, 31, 95 } };     // { lr_sgr_set, xqd0, xqd1 }: == lr_pieces.h, oracle/av1o_lr.c
+// (the fixed candidates - av1mi_wiener_cand, av1mi_wiener_cand_uv, av1mi_sgr_cand - are lr_fit_rule.h's, which the kernels read as well)
 // self-guided unit (§5.11.58): lr_sgr_set L(4), then the two weights against RefSgrXqd (ref 0 = Sgrproj_Xqd_Mid at the tile
 // start, r = candidate r-1: the previous self-guided unit of the tile).  Every candidate uses set 9, whose radii are both
 // non-zero, so both weights are always coded.
 BitString sgr_code_of(int ref, int cand) {
   static const int mid[2] = { -32, 31 };
-  return av1mi_lr_sgr_code(kSgrCand[cand][0], kSgrCand[cand][1], kSgrCand[cand][2], ref ? kSgrCand[ref - 1][1] : mid[0], ref ? kSgrCand[ref - 1][2] : mid[1]);
+  return av1mi_lr_sgr_code(av1mi_sgr_cand[cand][0], av1mi_sgr_cand[cand][1], av1mi_sgr_cand[cand][2], ref ? av1mi_sgr_cand[ref - 1][1] : mid[0], ref ? av1mi_sgr_cand[ref - 1][2] : mid[1]);
 }
 // ref: 0 = Wiener_Taps_Mid (tile start), r = candidate r-1 (the previous unit of the tile that was coded with a filter)
 BitString lr_code_of(int ref, int cand) {
   static const int tmin[3] = { -5, -23, -17 }, tmax[3] = { 10, 8, 46 }, tk[3] = { 1, 2, 3 }, mid[3] = { 3, -7, 15 };
   BitString b;
   for (int pass = 0; pass < 2; pass++)
-    for (int j = 0; j < 3; j++) lr_put_signed_ref(b, tmin[j], tmax[j] + 1, tk[j], ref ? kWienerCand[ref - 1][j] : mid[j], kWienerCand[cand][j]);
+    for (int j = 0; j < 3; j++) lr_put_signed_ref(b, tmin[j], tmax[j] + 1, tk[j], ref ? av1mi_wiener_cand[ref - 1][j] : mid[j], av1mi_wiener_cand[cand][j]);
   return b;
 }
 // the same for a chroma unit: taps 1 and 2 of each pass, against the plane's RefLrWiener
@@ -385,7 +382,7 @@ BitString lr_code_of_uv(int ref, int cand) {
   static const int tmin[3] = { -5, -23, -17 }, tmax[3] = { 10, 8, 46 }, tk[3] = { 1, 2, 3 }, mid[3] = { 3, -7, 15 };
   BitString b;
   for (int pass = 0; pass < 2; pass++)
-    for (int j = 1; j < 3; j++) lr_put_signed_ref(b, tmin[j], tmax[j] + 1, tk[j], ref ? kWienerCandUV[ref - 1][j] : mid[j], kWienerCandUV[cand][j]);
+    for (int j = 1; j < 3; j++) lr_put_signed_ref(b, tmin[j], tmax[j] + 1, tk[j], ref ? av1mi_wiener_cand_uv[ref - 1][j] : mid[j], av1mi_wiener_cand_uv[cand][j]);
   return b;
 }
 
@@ -602,8 +599,6 @@ int tile_stream_cap(const Resolved &r, int scale) { return 8192 * scale * r.tile
 size_t fit_chunk_units(const Resolved &r, size_t n_frames) {
   return n_frames * 3 * (size_t)av1mi_lr_count((int)r.p.height, r.lr_unit_shift) * (size_t)av1mi_lr_count((int)r.p.width, r.lr_unit_shift);
 }
-size_t fit_bytes(size_t units) { return units * (AV1MI_LR_FIT_CANDS * 8 + 4 + AV1MI_LR_FIT_SETS * 5 * 8 + 8) + 8; }
-size_t wfit_bytes(size_t units) { return units * (8 + 8 + AV1MI_LR_WFIT_SUMS * 8 + 12); }   // error, record, sums, code
 
 int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   const av1mi_params &p = r.p;
@@ -691,29 +686,17 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   }
   if (r.lr_fit_mask && (!w.d_fit || !w.h_fit)) {   // for three planes, like the unit sums: the buffers stay while enable_lr changes
     const size_t units = 3 * nf * nsb + 64;
-    HIPCHK(c, ws_alloc(w, w.d_fit, fit_bytes(units)));
-    HIPCHK(c, ws_alloc(w, w.h_fit, units * (AV1MI_LR_FIT_CANDS * 8 + 4), true));
+    HIPCHK(c, ws_alloc(w, w.d_fit, av1mi_lr_fit_bytes(units)));
+    HIPCHK(c, ws_alloc(w, w.h_fit, av1mi_lr_fit_result_bytes(units), true));
   }
-  if (r.lr_fit_mask) {   // this chunk's units, contiguous from the head of the block: errors, records (to a multiple of 8 bytes), sums, codes
-    const size_t n = fit_chunk_units(r, n_frames);
-    w.fit.err = reinterpret_cast<unsigned long long *>(w.d_fit);
-    w.fit.rec = reinterpret_cast<int8_t *>(w.fit.err + n * AV1MI_LR_FIT_CANDS);
-    w.fit.sums = reinterpret_cast<long long *>(w.fit.rec + ((n * 4 + 7) & ~(size_t)7));
-    w.fit.code = reinterpret_cast<uint32_t *>(w.fit.sums + n * AV1MI_LR_FIT_SETS * 5);
-  }
+  if (r.lr_fit_mask) w.fit = av1mi_lr_fit_split(w.d_fit, fit_chunk_units(r, n_frames), r.lr_fit_mask);   // this chunk's units, from the head of the block
   w.fit.mask = r.lr_fit_mask;
   if (r.lr_wfit && (!w.d_wfit || !w.h_wfit)) {
     const size_t units = 3 * nf * nsb + 64;
-    HIPCHK(c, ws_alloc(w, w.d_wfit, wfit_bytes(units)));
-    HIPCHK(c, ws_alloc(w, w.h_wfit, units * 16, true));
+    HIPCHK(c, ws_alloc(w, w.d_wfit, av1mi_lr_wfit_bytes(units)));
+    HIPCHK(c, ws_alloc(w, w.h_wfit, av1mi_lr_wfit_result_bytes(units), true));
   }
-  if (r.lr_wfit) {   // this chunk's units, contiguous from the head of the block
-    const size_t n = fit_chunk_units(r, n_frames);
-    w.wfit.err = reinterpret_cast<unsigned long long *>(w.d_wfit);
-    w.wfit.rec = reinterpret_cast<int8_t *>(w.wfit.err + n);
-    w.wfit.sums = reinterpret_cast<long long *>(w.wfit.rec + n * 8);
-    w.wfit.code = reinterpret_cast<uint32_t *>(w.wfit.sums + n * AV1MI_LR_WFIT_SUMS);
-  }
+  if (r.lr_wfit) w.wfit = av1mi_lr_wfit_split(w.d_wfit, fit_chunk_units(r, n_frames));
   w.res = r;
   if (p.enable_qm && r.qm_level < 15) {
     // dequantiser step per coefficient position (§7.12.3) and its reciprocal, for the square transform sizes 4..32
@@ -1122,8 +1105,9 @@ int av1mi_lr_fit_result(const av1mi_ctx *c, uint32_t n_frames, int8_t *units, ui
   if (!c || !units || n_frames == 0 || c->lf_levels.size() != (size_t)n_frames * 4) return AV1MI_E_INVALID_ARG;
   const size_t n = c->fit_units;
   if (c->fit_on) {
-    memcpy(units, c->ws.h_fit + n * AV1MI_LR_FIT_CANDS * 8, n * 4);
-    if (err) memcpy(err, c->ws.h_fit, n * AV1MI_LR_FIT_CANDS * 8);
+    const Av1miLrFit H = av1mi_lr_fit_split(c->ws.h_fit, n, 0);   // the fetched head of the block
+    memcpy(units, H.rec, n * 4);
+    if (err) memcpy(err, H.err, n * AV1MI_LR_FIT_CANDS * 8);
   } else {
     memset(units, 0, n * 4);
     if (err) memset(err, 0, n * AV1MI_LR_FIT_CANDS * 8);
@@ -1170,8 +1154,9 @@ int av1mi_lr_wiener_fit_result(const av1mi_ctx *c, uint32_t n_frames, int8_t *un
   if (!c || !units || n_frames == 0 || c->lf_levels.size() != (size_t)n_frames * 4) return AV1MI_E_INVALID_ARG;
   const size_t n = c->fit_units;
   if (c->wfit_on) {
-    memcpy(units, c->ws.h_wfit + n * 8, n * 8);
-    if (err) memcpy(err, c->ws.h_wfit, n * 8);
+    const Av1miLrWfit H = av1mi_lr_wfit_split(c->ws.h_wfit, n);   // the fetched head of the block
+    memcpy(units, H.rec, n * 8);
+    if (err) memcpy(err, H.err, n * 8);
   } else {
     memset(units, 0, n * 8);
     if (err) memset(err, 0, n * 8);
@@ -1247,8 +1232,8 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   // the level search's sums, once per attempt at the chunk (not a fill per frame on a P chain)
   if (P.lf_search) HIPCHK(c, hipMemsetAsync(w.d_lf_err, 0, (size_t)n_frames * 3 * AV1MI_LF_CANDS * sizeof(unsigned long long), s));
   // the self-guided fit's sums, errors, records and codes, once per attempt at the chunk
-  if (P.lr_fit_code) HIPCHK(c, hipMemsetAsync(w.d_fit, 0, fit_bytes(fit_chunk_units(r, n_frames)), s));
-  if (P.lr_wfit_code) HIPCHK(c, hipMemsetAsync(w.d_wfit, 0, wfit_bytes(fit_chunk_units(r, n_frames)), s));
+  if (P.lr_fit_code) HIPCHK(c, hipMemsetAsync(w.d_fit, 0, av1mi_lr_fit_bytes(fit_chunk_units(r, n_frames)), s));
+  if (P.lr_wfit_code) HIPCHK(c, hipMemsetAsync(w.d_wfit, 0, av1mi_lr_wfit_bytes(fit_chunk_units(r, n_frames)), s));
   HIPCHK(c, hipEventRecord(c->ev[EV_START], s));
   // the caller's frames are used in place if they are on the device at the coded size; a padded chunk arrives in the stage
   if (!frames_on_device) HIPCHK(c, hipMemcpyAsync(r.padded ? w.d_stage : w.d_src, frames, caller_bytes(r, n_frames), hipMemcpyHostToDevice, s));
@@ -1334,6 +1319,17 @@ static int schedule_all_key(av1mi_ctx *c, const void *src, uint32_t n_frames) {
   return AV1MI_OK;
 }
 
+// Restoration of frames [frame0, frame0 + count) from `cdef` into d_fin: the fixed candidates - which also decide and filter unless the
+// self-guided fit does - then the fits the chunk has.  clear: the launch clears its frames' unit sums (else the caller has)
+static int launch_restoration(av1mi_ctx *c, const void *src, const void *cdef, int clear, int frame0, int count) {
+  const Av1miDevParams &P = c->P; Workspace &w = c->ws; hipStream_t s = c->stream;
+  const Av1miLrFit *fit = P.lr_fit_code ? &w.fit : nullptr;
+  HIPCHK(c, av1mi_launch_lr(&P, w.d_rec, cdef, src, w.d_fin, w.d_lrc, w.d_lrsse, clear, fit == nullptr, frame0, count, s));
+  if (fit) HIPCHK(c, av1mi_launch_lr_fit(&P, w.d_rec, cdef, src, w.d_fin, w.d_lrc, w.d_lrsse, fit, frame0, count, s));
+  if (P.lr_wfit_code) HIPCHK(c, av1mi_launch_lr_wfit(&P, w.d_rec, cdef, src, w.d_fin, w.d_lrc, w.d_lrsse, fit, &w.wfit, frame0, count, s));
+  return AV1MI_OK;
+}
+
 // All-key-frame chunk with loop restoration: the unit decisions are part of the tile syntax, so deblocking, CDEF (into d_cd) and
 // restoration (into d_fin) precede entropy coding on the main stream.
 static int schedule_all_key_lr(av1mi_ctx *c, const void *src, uint32_t n_frames) {
@@ -1346,10 +1342,8 @@ static int schedule_all_key_lr(av1mi_ctx *c, const void *src, uint32_t n_frames)
   if (av1mi_frame_lf_levels(P, 0)[0]) HIPCHK(c, av1mi_launch_deblock(&P, w.d_rec, w.d_blk, 0, n, s));
   if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, 0, n, s));
   HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, w.d_cd, w.d_blk, nullptr, nullptr, 0, n, s));
-  HIPCHK(c, av1mi_launch_lr(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, 1, P.lr_fit_code == nullptr, 0, n, s));
-  if (P.lr_fit_code) HIPCHK(c, av1mi_launch_lr_fit(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, &w.fit, 0, n, s));
-  if (P.lr_wfit_code) HIPCHK(c, av1mi_launch_lr_wfit(&P, w.d_rec, w.d_cd, src, w.d_fin, w.d_lrc, w.d_lrsse, P.lr_fit_code ? &w.fit : nullptr, &w.wfit, 0, n, s));
-  const int rc = entropy_code(c, 0, n_frames, by_weight);
+  int rc = launch_restoration(c, src, w.d_cd, 1, 0, n);
+  if (!rc) rc = entropy_code(c, 0, n_frames, by_weight);
   return rc ? rc : sse_beside_range_coder(c, src);
 }
 
@@ -1402,9 +1396,7 @@ static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
     // the frame's strength set before its CDEF (the next frame's reference is the output of the chosen strengths)
     if (P.cdef_search) HIPCHK(c, av1mi_launch_cdef_search(&P, w.d_rec, src, w.d_blk, w.d_hdr, fi, 1, s));
     HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, cdef_out, w.d_blk, nullptr, nullptr, fi, 1, s));
-    if (lr) HIPCHK(c, av1mi_launch_lr(&P, w.d_rec, cdef_out, src, w.d_fin, w.d_lrc, w.d_lrsse, 0, P.lr_fit_code == nullptr, fi, 1, s));
-    if (lr && P.lr_fit_code) HIPCHK(c, av1mi_launch_lr_fit(&P, w.d_rec, cdef_out, src, w.d_fin, w.d_lrc, w.d_lrsse, &w.fit, fi, 1, s));
-    if (lr && P.lr_wfit_code) HIPCHK(c, av1mi_launch_lr_wfit(&P, w.d_rec, cdef_out, src, w.d_fin, w.d_lrc, w.d_lrsse, P.lr_fit_code ? &w.fit : nullptr, &w.wfit, fi, 1, s));
+    if (lr) { const int rc = launch_restoration(c, src, cdef_out, 0, fi, 1); if (rc) return rc; }
     if (f == 0)   // (frame 0 of a chunk is a key frame: its chain kernels are in the queue)
       for (uint32_t g = 1; g < n_frames; g++) {
         if (!av1mi_frame_is_inter(P, (int)g)) continue;
@@ -1486,8 +1478,8 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
   if (e1 == hipSuccess && P.lf_search) e1 = hipMemcpyAsync(w.h_lf + lf_err_bytes, w.d_lf_sel, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s);
   // the self-guided fit's errors and records (av1mi_lr_fit_result), likewise
   const size_t fit_n = (size_t)n_frames * 3 * av1mi_lr_unit_rows(P) * av1mi_lr_unit_cols(P);
-  if (e1 == hipSuccess && P.lr_fit_code) e1 = hipMemcpyAsync(w.h_fit, w.d_fit, fit_n * (AV1MI_LR_FIT_CANDS * 8 + 4), hipMemcpyDeviceToHost, s);
-  if (e1 == hipSuccess && P.lr_wfit_code) e1 = hipMemcpyAsync(w.h_wfit, w.d_wfit, fit_n * 16, hipMemcpyDeviceToHost, s);   // (av1mi_lr_wiener_fit_result)
+  if (e1 == hipSuccess && P.lr_fit_code) e1 = hipMemcpyAsync(w.h_fit, w.d_fit, av1mi_lr_fit_result_bytes(fit_n), hipMemcpyDeviceToHost, s);
+  if (e1 == hipSuccess && P.lr_wfit_code) e1 = hipMemcpyAsync(w.h_wfit, w.d_wfit, av1mi_lr_wfit_result_bytes(fit_n), hipMemcpyDeviceToHost, s);   // (av1mi_lr_wiener_fit_result)
   // the bitstream is on the host once EV_DOWNLOAD_DONE has passed: hand it over to the caller's buffer while the second stream finishes
   if (e1 == hipSuccess && e2 == hipSuccess && dst != host) {
     e1 = hipEventSynchronize(c->ev[EV_DOWNLOAD_DONE]);

@@ -1,6 +1,6 @@
 // lr_fit_rule.h - the self-guided restoration fit (av1mi_params.enable_lr bit 8, AV1MI_LR_FIT), all integers, for
 // host and device: lr_fit_kernel.hip runs it per restoration unit, av1mi_host.cpp builds the fixed candidates' bit strings with its
-// writers, tests/host/lr_fit_rule_host.cpp compiles it for the CPU against the numpy restatement (tests/sgr_fit_ref.py).
+// writers from its candidate tables (the restoration kernels' too, lr_pieces.h), tests/host/lr_fit_rule_host.cpp compiles it for the CPU against the numpy restatement (tests/sgr_fit_ref.py).
 // Non-normative except for the syntax: the decoder sees lr_sgr_set and the weights (§5.11.58).
 //
 //   set t        radii and strengths (r0, eps0, r1, eps1) = Sgr_Params[t] (§7.17.3); r0 is 2 or 0, r1 is 1 or 0
@@ -33,13 +33,21 @@
 //   {2,12,1,4} {2,15,1,6} {2,18,1,8} {2,21,1,9} {2,24,1,10} {2,29,1,11} {2,36,1,12} {2,45,1,13} {2,56,1,14} {2,68,1,15}
 //   {0,0,1,5} {0,0,1,8} {0,0,1,11} {0,0,1,14} {2,30,0,0} {2,75,0,0}
 // (packed, so that host and device read the same constants without a table in memory)
-AV1MI_FIT_HD inline int av1mi_sgr_r0(int t) { return t < 10 || t >= 14 ? 2 : 0; }
-AV1MI_FIT_HD inline int av1mi_sgr_r1(int t) { return t < 14 ? 1 : 0; }
-AV1MI_FIT_HD inline int av1mi_sgr_eps0(int t) {   // a byte per set
+AV1MI_FIT_HD constexpr int av1mi_sgr_r0(int t) { return t < 10 || t >= 14 ? 2 : 0; }
+AV1MI_FIT_HD constexpr int av1mi_sgr_r1(int t) { return t < 14 ? 1 : 0; }
+AV1MI_FIT_HD constexpr int av1mi_sgr_eps0(int t) {   // a byte per set
   const uint64_t lo = 0x2D241D1815120F0Cull /* sets 7 .. 0 */, hi = 0x4B1E000000004438ull /* sets 15 .. 8 */;
   return (int)(((t < 8 ? lo : hi) >> (8 * (t & 7))) & 255);
 }
-AV1MI_FIT_HD inline int av1mi_sgr_eps1(int t) { return (int)((0x00EB85FEDCBA9864ull >> (4 * t)) & 15); }   // a nibble per set
+AV1MI_FIT_HD constexpr int av1mi_sgr_eps1(int t) { return (int)((0x00EB85FEDCBA9864ull >> (4 * t)) & 15); }   // a nibble per set
+
+// ---- the fixed candidates (restated in oracle/av1o_lr.c av1o_wiener_candidates / av1o_sgr_candidates): initialisers,
+// for the kernels' __constant__ copies (lr_pieces.h) and the host's tables below (the fixed candidates' bit strings, av1mi_host.cpp)
+#define AV1MI_WIENER_CAND { { 0, 0, -4 }, { 1, -3, -6 }, { 3, -7, 15 } }       /* taps 0 .. 2 of both passes */
+#define AV1MI_WIENER_CAND_UV { { 0, 0, -4 }, { 0, 0, 16 }, { 0, 6, 20 } }      /* chroma (enable_lr 3 / 4): tap 0 is 0 and not coded, §5.11.58 */
+#define AV1MI_SGR_CAND { { 9, 31, 31 }, { 9, 0, 31 }, { 9, 31, 95 } }          /* { lr_sgr_set, xqd0, xqd1 } */
+#define AV1MI_SGR_CAND_SET 9   /* the set of every fixed self-guided candidate: both radii non-zero */
+const int8_t av1mi_wiener_cand[3][3] = AV1MI_WIENER_CAND, av1mi_wiener_cand_uv[3][3] = AV1MI_WIENER_CAND_UV, av1mi_sgr_cand[3][3] = AV1MI_SGR_CAND;
 
 AV1MI_FIT_HD inline int av1mi_fit_clamp(long long v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : (int)v); }
 AV1MI_FIT_HD inline long long av1mi_fit_rdiv(long long a, long long b) {

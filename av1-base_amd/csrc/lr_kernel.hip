@@ -10,129 +10,31 @@
 // MI355X mapping: waves of 16 rows of a 64x64 unit (lane = column), two phases (see lr_unit_kernel).  Per stripe of the unit the horizontal pass of 70 rows goes to
 // LDS as int16 (the spec's clamp keeps it in 16 bits for 8/10 bit), the vertical pass reads 7 LDS rows per sample.  The
 // three candidates are evaluated for their SSE only (with enable_lr = 2 also three self-guided candidates: the A/B grids of
-// both box-filter passes go to LDS per stripe section, see sgr_grid); the winner is applied in a last pass that writes the final
+// both box-filter passes go to LDS per stripe section, see lr_pieces.h's box_grid); the winner is applied in a last pass that writes the final
 // reconstruction (with enable_lr = 1 / 2 chroma is copied: FrameRestorationType = NONE; with 3 / 4 the chroma units are decided
 // and filtered in the same two launches, see lr_chroma).  Algorithmic HBM bytes: CDEF frame read + pre-CDEF rows at stripe edges
 // + source read + final write = ~3*L*b + N*b per frame (~3*N*b with the chroma units).
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "av1mi_dev.h"
 #include "av1mi_launch.h"
 
 namespace {
 
-#include "lr_pieces.h"   // candidate tables, LDS tiles, the staged window, the Wiener filter, reductions, LR_SLICES / LR_SLICES_C
+#include "lr_pieces.h"   // candidate tables, LDS tiles, the staged window, both filters, the decision, the tail, LR_SLICES / LR_SLICES_C
 
-// A and B from the box sums (sum of samples b, of squares a) of a (2r+1)^2 window
-// (sgr_ab and sgr_grid have twins with the strength as an argument, lr_fit_kernel.hip's fit_ab and fit_grid: a change to the
-// arithmetic, the window or the grid layout here is a change there)
-template <int R>
-__device__ __forceinline__ void sgr_ab(uint32_t a, uint32_t b, int bd, uint32_t &A, int32_t &B) {
-  constexpr uint32_t n = (2 * R + 1) * (2 * R + 1), eps = R == 2 ? 68 : 15, n2e = n * n * eps;
-  constexpr uint32_t s = ((1u << 20) + n2e / 2) / n2e, one_by_n = ((1u << 12) + n / 2) / n;
-  const uint32_t a8 = (a + ((1u << (2 * (bd - 8))) >> 1)) >> (2 * (bd - 8));
-  const uint32_t d = (b + ((1u << (bd - 8)) >> 1)) >> (bd - 8);
-  const uint32_t p = a8 * n > d * d ? a8 * n - d * d : 0;
-  const uint32_t z = (uint32_t)(((unsigned long long)p * s + (1u << 19)) >> 20);
-  const uint32_t a2 = z >= 255 ? 256 : (z == 0 ? 1 : ((z << 8) + z / 2) / (z + 1));
-  A = a2;
-  B = (int32_t)(((unsigned long long)(256 - a2) * b * one_by_n + (1u << 11)) >> 12);
+// the self-guided candidates: lr_pieces.h's box filter with the strengths of their set as compile-time constants
+constexpr int kSgrEps0 = av1mi_sgr_eps0(AV1MI_SGR_CAND_SET), kSgrEps1 = av1mi_sgr_eps1(AV1MI_SGR_CAND_SET);
+static_assert(av1mi_sgr_r0(AV1MI_SGR_CAND_SET) == 2 && av1mi_sgr_r1(AV1MI_SGR_CAND_SET) == 1, "the candidates' set has both radii");
+// both grids of a section, see box_grid (their readers wait at the caller's barrier)
+__device__ __forceinline__ void sgr_grids(int bd, int ya, int yb, int lane) {
+  box_grid<0>(bd, ya, yb, lane, kSgrEps0);
+  box_grid<1>(bd, ya, yb, lane, kSgrEps1);
 }
-
-// A/B of pass PASS (radius R) for the section rows ya - 1 .. yb and columns xs - 1 .. xs + 64 -> g_sgrA/B[PASS][row - (ya - 1)][col - (xs - 1)],
-// from the staged window.  Pass 0 is only read on odd rows.  Lane = column xs + lane with a sliding window of row sums; the
-// two edge columns are shared out over the lanes afterwards (direct sums).
-template <int PASS>
-__device__ __forceinline__ void sgr_grid(int bd, int ya, int yb, int lane) {
-  constexpr int R = PASS == 0 ? 2 : 1, WN = 2 * R + 1;
-  const uint16_t (*win)[72] = g_win;
-  uint32_t h1[WN], h2[WN];   // ring of the last WN row sums
-#pragma unroll
-  for (int t = 0; t < WN; t++) { h1[t] = 0; h2[t] = 0; }
-  for (int yy = ya - 1 - R; yy <= yb + R; yy++) {
-    const uint16_t *row = win[yy - (ya - 3)] + lane + 3 - R;
-    uint32_t r1 = 0, r2 = 0;
-#pragma unroll
-    for (int t = 0; t < WN; t++) { const uint32_t c = row[t]; r1 += c; r2 += c * c; }
-#pragma unroll
-    for (int t = 0; t < WN - 1; t++) { h1[t] = h1[t + 1]; h2[t] = h2[t + 1]; }
-    h1[WN - 1] = r1; h2[WN - 1] = r2;
-    const int yc = yy - R;   // centre row of the window that just became complete
-    if (yc >= ya - 1 && (PASS == 1 || (yc & 1))) {
-      uint32_t b = 0, a = 0;
-#pragma unroll
-      for (int t = 0; t < WN; t++) { b += h1[t]; a += h2[t]; }
-      uint32_t A; int32_t B;
-      sgr_ab<R>(a, b, bd, A, B);
-      if (PASS == 0) { g_sgrA0[(yc - (ya - 1)) >> 1][lane + 1] = (uint16_t)A; g_sgrB0[(yc - (ya - 1)) >> 1][lane + 1] = B; }
-      else { g_sgrA1[yc - (ya - 1)][lane + 1] = (uint16_t)A; g_sgrB1[yc - (ya - 1)][lane + 1] = B; }
-    }
-  }
-  const int rows = yb - ya + 2;
-  for (int task = lane; task < rows * 2; task += 64) {
-    const int ri = task >> 1, side = task & 1;
-    const int yc = ya - 1 + ri, j = side ? 67 : 2;   // window column of xs + 64 / xs - 1
-    if (PASS == 0 && !(yc & 1)) continue;
-    uint32_t a = 0, b = 0;
-    for (int dy = -R; dy <= R; dy++) {
-      const uint16_t *row = win[yc + dy - (ya - 3)] + j - R;
-#pragma unroll
-      for (int t = 0; t < WN; t++) { const uint32_t c = row[t]; b += c; a += c * c; }
-    }
-    uint32_t A; int32_t B;
-    sgr_ab<R>(a, b, bd, A, B);
-    if (PASS == 0) { g_sgrA0[ri >> 1][side ? 65 : 0] = (uint16_t)A; g_sgrB0[ri >> 1][side ? 65 : 0] = B; }
-    else { g_sgrA1[ri][side ? 65 : 0] = (uint16_t)A; g_sgrB1[ri][side ? 65 : 0] = B; }
-  }
-}
-
-// the two box-filter outputs (flt0: r = 2, flt1: r = 1) of sample (x = xs + lane, y) from the grids; cur = the CDEF sample
-__device__ __forceinline__ void sgr_flt(int lane, int y, int ya, int cur, int &flt0, int &flt1) {
-  const int ri = y - (ya - 1), c = lane + 1;
-  {
-    int a = 0, b = 0;
-#pragma unroll
-    for (int dy = -1; dy <= 1; dy++)
-#pragma unroll
-      for (int dx = -1; dx <= 1; dx++) {
-        const int w = (dx == 0 || dy == 0) ? 4 : 3;
-        a += w * (int)g_sgrA1[ri + dy][c + dx]; b += w * g_sgrB1[ri + dy][c + dx];
-      }
-    flt1 = (a * cur + b + (1 << 8)) >> 9;
-  }
-  {
-    int a = 0, b = 0;
-    if (y & 1) {  // odd row: the row itself, weights 5 6 5, shift 4
-      const int r0 = ri >> 1;
-      a = 5 * (int)g_sgrA0[r0][c - 1] + 6 * (int)g_sgrA0[r0][c] + 5 * (int)g_sgrA0[r0][c + 1];
-      b = 5 * g_sgrB0[r0][c - 1] + 6 * g_sgrB0[r0][c] + 5 * g_sgrB0[r0][c + 1];
-      flt0 = (a * cur + b + (1 << 7)) >> 8;
-    } else {      // even row: the rows above and below, shift 5
-#pragma unroll
-      for (int dy = -1; dy <= 1; dy += 2) {
-        const int r0 = (ri + dy) >> 1;
-        a += 5 * (int)g_sgrA0[r0][c - 1] + 6 * (int)g_sgrA0[r0][c] + 5 * (int)g_sgrA0[r0][c + 1];
-        b += 5 * g_sgrB0[r0][c - 1] + 6 * g_sgrB0[r0][c] + 5 * g_sgrB0[r0][c + 1];
-      }
-      flt0 = (a * cur + b + (1 << 8)) >> 9;
-    }
-  }
-}
-__device__ __forceinline__ int sgr_blend(int cur, int flt0, int flt1, int w0, int w1, int maxv) {
-  const int u = cur << 4, w2 = 128 - w0 - w1;
-  const int v = w1 * u + w0 * flt0 + w2 * flt1;   // set 9: both radii non-zero
-  return clampi((v + (1 << 10)) >> 11, 0, maxv);
-}
-
-// the decision of a unit from its sums: the first minimum in the order off, Wiener 1..3, self-guided 1..3
-template <bool SGR>
-__device__ __forceinline__ int lr_decide(const unsigned long long *usse) {
-  int best = 0;
-  unsigned long long bs = usse[0];
-  for (int k = 0; k < (SGR ? 6 : 3); k++) {
-    const unsigned long long s = usse[k + 1];
-    if (s < bs) { bs = s; best = k + 1; }
-  }
-  return best;
+// the two box-filter outputs of sample (xs + lane, y), and candidate k's blend of them: the candidates differ only in the blend
+__device__ __forceinline__ void box_flt01(int lane, int y, int ya, int cur, int &f0, int &f1) { f1 = box_flt1(lane, y, ya, cur); f0 = box_flt0(lane, y, ya, cur); }
+__device__ __forceinline__ int sgr_cand(int k, int cur, int f0, int f1, int maxv) {
+  return box_blend(cur, 1, 1, f0, f1, c_sgr_cand[k][1], c_sgr_cand[k][2], maxv);
 }
 
 // ---- chroma units (enable_lr = 3 / 4) ---------------------------------------------------------------------
@@ -191,17 +93,16 @@ __device__ __forceinline__ void lr_chroma(const Av1miDevParams &P, int item, con
             if (active && ya + i < yb) { const int d = wiener_v(i, lane, tf, maxv) - sv[i]; sse[k + 1] += (unsigned long long)(d * d); }
         }
         if constexpr (SGR) {
-          sgr_grid<0>(P.bit_depth, ya, yb, lane);
-          sgr_grid<1>(P.bit_depth, ya, yb, lane);
+          sgr_grids(P.bit_depth, ya, yb, lane);
           __syncthreads();
 #pragma unroll
           for (int i = 0; i < 16; i++)
             if (active && ya + i < yb) {
               int f0, f1;
-              sgr_flt(lane, ya + i, ya, cur[i], f0, f1);
+              box_flt01(lane, ya + i, ya, cur[i], f0, f1);
 #pragma unroll
               for (int k = 0; k < 3; k++) {
-                const int d = sgr_blend(cur[i], f0, f1, c_sgr_cand[k][1], c_sgr_cand[k][2], maxv) - sv[i];
+                const int d = sgr_cand(k, cur[i], f0, f1, maxv) - sv[i];
                 sse[4 + k] += (unsigned long long)(d * d);
               }
             }
@@ -213,7 +114,8 @@ __device__ __forceinline__ void lr_chroma(const Av1miDevParams &P, int item, con
       }
     } else {
       // both units' decisions in every lane (the stripe loop below stays uniform); each lane applies its own unit's
-      const int best_lo = lr_decide<SGR>(unit_sse + (ubase + uc_lo) * 8), best_hi = lr_decide<SGR>(unit_sse + (ubase + uc_hi) * 8);
+      unsigned long long bs;
+      const int best_lo = lr_decide(unit_sse + (ubase + uc_lo) * 8, SGR ? 6 : 3, bs), best_hi = lr_decide(unit_sse + (ubase + uc_hi) * 8, SGR ? 6 : 3, bs);
       const int best = lane < 32 ? best_lo : best_hi;
       if (slice == 0 && cr == av1mi_lr_first_cell(ur, ush) && x == av1mi_lr_first_cell(uc, ush) * 32) choice[ubase + uc] = (uint8_t)best;
       const bool any_wiener = (best_lo && best_lo <= 3) || (best_hi && best_hi <= 3), any_sgr = best_lo > 3 || best_hi > 3;
@@ -229,8 +131,7 @@ __device__ __forceinline__ void lr_chroma(const Av1miDevParams &P, int item, con
         }
         if constexpr (SGR) {
           if (any_sgr) {
-            sgr_grid<0>(P.bit_depth, ya, yb, lane);
-            sgr_grid<1>(P.bit_depth, ya, yb, lane);
+            sgr_grids(P.bit_depth, ya, yb, lane);
             __syncthreads();
           }
         }
@@ -241,8 +142,8 @@ __device__ __forceinline__ void lr_chroma(const Av1miDevParams &P, int item, con
             if (best > 3) {
               const int cur = (int)g_win[y - ya + 3][lane + 3];
               int f0, f1;
-              sgr_flt(lane, y, ya, cur, f0, f1);
-              v = sgr_blend(cur, f0, f1, c_sgr_cand[best - 4][1], c_sgr_cand[best - 4][2], maxv);
+              box_flt01(lane, y, ya, cur, f0, f1);
+              v = sgr_cand(best - 4, cur, f0, f1, maxv);
             } else if (best) {
               v = wiener_v(y - ya, lane, tf, maxv);
             } else {
@@ -253,13 +154,7 @@ __device__ __forceinline__ void lr_chroma(const Av1miDevParams &P, int item, con
       }
     }
   }
-  if constexpr (PHASE == 1) {
-    // padding between the signalled and the coded size: copied with the last cell of the row / column (its last slice)
-    const int py1 = (cr == crows - 1 && y1 == uy1) ? P.height >> 1 : y1, px1 = pc == pairs - 1 ? P.width >> 1 : x1;
-    for (int y = y0; y < py1; y++)
-      for (int x = x0 + lane; x < px1; x += 64)
-        if (y >= y1 || x >= x1) out[(size_t)y * stride + x] = cdef[(size_t)y * stride + x];
-  }
+  if constexpr (PHASE == 1) lr_tail<PIX>(P, cdef, out, 1, false, cr == crows - 1 && y1 == uy1, pc == pairs - 1, x0, x1, y0, y1, stride, lane);
 }
 
 // A unit is LR_SLICES waves, one per 16 of its rows (the last unit of a column has up to 103), in two launches: PHASE 0 adds
@@ -327,17 +222,16 @@ __global__ void __launch_bounds__(64) lr_unit_kernel(Av1miDevParams P, const PIX
           if (active && ya + i < yb) { const int d = wiener_v(i, lane, tf, maxv) - sv[i]; sse[k + 1] += (unsigned long long)(d * d); }
       }
       if constexpr (SGR) {
-        sgr_grid<0>(P.bit_depth, ya, yb, lane);
-        sgr_grid<1>(P.bit_depth, ya, yb, lane);
+        sgr_grids(P.bit_depth, ya, yb, lane);
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < 16; i++)
           if (active && ya + i < yb) {
             int f0, f1;
-            sgr_flt(lane, ya + i, ya, cur[i], f0, f1);
+            box_flt01(lane, ya + i, ya, cur[i], f0, f1);
 #pragma unroll
             for (int k = 0; k < 3; k++) {
-              const int d = sgr_blend(cur[i], f0, f1, c_sgr_cand[k][1], c_sgr_cand[k][2], maxv) - sv[i];
+              const int d = sgr_cand(k, cur[i], f0, f1, maxv) - sv[i];
               sse[4 + k] += (unsigned long long)(d * d);
             }
           }
@@ -349,15 +243,8 @@ __global__ void __launch_bounds__(64) lr_unit_kernel(Av1miDevParams P, const PIX
     if (lane == 0 && v) atomicAdd(&usse[k], v);
   }
   } else {
-  int best = 0;
-  {
-    unsigned long long bs = usse[0];
-    const int ncand = SGR ? 6 : 3;
-    for (int k = 0; k < ncand; k++) {
-      const unsigned long long s = usse[k + 1];
-      if (s < bs) { bs = s; best = k + 1; }
-    }
-  }
+  unsigned long long bs;
+  const int best = lr_decide(usse, SGR ? 6 : 3, bs);
   if (lane == 0 && slice == 0 && cr == av1mi_lr_first_cell(ur, ush) && cc == av1mi_lr_first_cell(uc, ush)) choice[uidx] = (uint8_t)best;
   // ---- apply: luma of the slice, and (without CHROMA) the co-located chroma (copied)
   for (int xs = x0; xs < x1; xs += 64) {
@@ -373,15 +260,14 @@ __global__ void __launch_bounds__(64) lr_unit_kernel(Av1miDevParams P, const PIX
       }
       if (best > 3) {
         if constexpr (SGR) {
-          sgr_grid<0>(P.bit_depth, ya, yb, lane);
-          sgr_grid<1>(P.bit_depth, ya, yb, lane);
+          sgr_grids(P.bit_depth, ya, yb, lane);
           __syncthreads();
           if (active)
             for (int y = ya; y < yb; y++) {
               const int cur = (int)g_win[y - ya + 3][lane + 3];
               int f0, f1;
-              sgr_flt(lane, y, ya, cur, f0, f1);
-              out[(size_t)y * P.stride_y + x] = (PIX)sgr_blend(cur, f0, f1, c_sgr_cand[best - 4][1], c_sgr_cand[best - 4][2], maxv);
+              box_flt01(lane, y, ya, cur, f0, f1);
+              out[(size_t)y * P.stride_y + x] = (PIX)sgr_cand(best - 4, cur, f0, f1, maxv);
             }
         }
       } else if (best) {
@@ -395,21 +281,7 @@ __global__ void __launch_bounds__(64) lr_unit_kernel(Av1miDevParams P, const PIX
       }
     }
   }
-  {
-    // padding between the signalled and the coded size (< 8 samples): copied with the last cell of the row / column (its last slice)
-    const int py1 = (cr == crows - 1 && y1 == uy1) ? P.height : y1, px1 = cc == ccols - 1 ? P.width : x1;
-    for (int y = y0; y < py1; y++)
-      for (int x = x0 + lane; x < px1; x += 64)
-        if (y >= y1 || x >= x1) out[(size_t)y * P.stride_y + x] = cdef[(size_t)y * P.stride_y + x];
-    if constexpr (!CHROMA) {
-      const int cy0 = y0 >> 1, cy1 = py1 >> 1, cx0 = x0 >> 1, cx1 = px1 >> 1;
-      for (int pl = 0; pl < 2; pl++) {
-        const size_t po = pl ? P.plane_off_v : P.plane_off_u;
-        for (int y = cy0; y < cy1; y++)
-          for (int x = cx0 + lane; x < cx1; x += 64) out[po + (size_t)y * P.stride_c + x] = cdef[po + (size_t)y * P.stride_c + x];
-      }
-    }
-  }
+  lr_tail<PIX>(P, cdef, out, 0, !CHROMA, cr == crows - 1 && y1 == uy1, cc == ccols - 1, x0, x1, y0, y1, P.stride_y, lane);
   }  // PHASE 1
 }
 
@@ -421,35 +293,26 @@ void launch_lr_phases(const Av1miDevParams *P, int grid, const PIX *pre, const P
   if (decide) hipLaunchKernelGGL((lr_unit_kernel<PIX, SGR, CHROMA, 1>), dim3(grid), dim3(64), 0, stream, *P, pre, cdef, src, out, choice, unit_sse);
 }
 
-// enable_lr = 2 (RESTORE_SWITCHABLE): the instantiations with the self-guided candidates (17 KB of LDS per wave, 6.2 KB without)
-template <typename PIX>
-void launch_lr_typed(const Av1miDevParams *P, int grid, const void *pre, const void *cdef, const void *src, void *out, uint8_t *choice,
-                     unsigned long long *unit_sse, int decide, hipStream_t stream) {
-  const PIX *a = (const PIX *)pre, *b = (const PIX *)cdef, *s = (const PIX *)src;
-  PIX *o = (PIX *)out;
-  if (P->enable_lr == 2) {
-    if (P->lr_chroma) launch_lr_phases<PIX, true, true>(P, grid, a, b, s, o, choice, unit_sse, decide, stream);
-    else launch_lr_phases<PIX, true, false>(P, grid, a, b, s, o, choice, unit_sse, decide, stream);
-  } else {
-    if (P->lr_chroma) launch_lr_phases<PIX, false, true>(P, grid, a, b, s, o, choice, unit_sse, decide, stream);
-    else launch_lr_phases<PIX, false, false>(P, grid, a, b, s, o, choice, unit_sse, decide, stream);
-  }
-}
-
 }  // namespace
 
 extern "C" hipError_t av1mi_launch_lr(const Av1miDevParams *P, const void *pre, const void *cdef, const void *src, void *out, uint8_t *choice,
                                       unsigned long long *unit_sse, int clear, int decide, int frame0, int count, hipStream_t stream) {
-  const Av1miDevParams R = av1mi_frame_range(*P, frame0, count);
-  const size_t upf = (size_t)av1mi_lr_frame_units(R);
-  pre = av1mi_frame_at(R, pre, frame0); cdef = av1mi_frame_at(R, cdef, frame0); src = av1mi_frame_at(R, src, frame0); out = av1mi_frame_at(R, out, frame0);
-  choice += frame0 * upf; unit_sse += frame0 * upf * 8;
-  const int grid = av1mi_lr_grid(R, count);
+  const LrLaunch L = lr_launch_head(P, pre, cdef, src, out, frame0, count);
+  choice += L.unit0; unit_sse += L.unit0 * 8;
   if (clear) {
-    hipError_t e = hipMemsetAsync(unit_sse, 0, count * upf * 8 * sizeof(unsigned long long), stream);
+    hipError_t e = hipMemsetAsync(unit_sse, 0, count * L.upf * 8 * sizeof(unsigned long long), stream);
     if (e != hipSuccess) return e;
   }
-  if (R.bit_depth == 8) launch_lr_typed<uint8_t>(&R, grid, pre, cdef, src, out, choice, unit_sse, decide, stream);
-  else launch_lr_typed<uint16_t>(&R, grid, pre, cdef, src, out, choice, unit_sse, decide, stream);
+  // enable_lr = 2 (RESTORE_SWITCHABLE): the instantiations with the self-guided candidates (17 KB of LDS per wave, 6.2 KB without)
+  lr_launch_typed(L, [&](auto *a, auto *b, auto *s, auto *o) {
+    using PIX = std::remove_pointer_t<decltype(o)>;
+    if (L.R.enable_lr == 2) {
+      if (L.R.lr_chroma) launch_lr_phases<PIX, true, true>(&L.R, L.grid, a, b, s, o, choice, unit_sse, decide, stream);
+      else launch_lr_phases<PIX, true, false>(&L.R, L.grid, a, b, s, o, choice, unit_sse, decide, stream);
+    } else {
+      if (L.R.lr_chroma) launch_lr_phases<PIX, false, true>(&L.R, L.grid, a, b, s, o, choice, unit_sse, decide, stream);
+      else launch_lr_phases<PIX, false, false>(&L.R, L.grid, a, b, s, o, choice, unit_sse, decide, stream);
+    }
+  });
   return hipGetLastError();
 }

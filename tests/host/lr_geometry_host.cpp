@@ -1,7 +1,8 @@
 // The restoration units' geometry header (av1-base_amd/csrc/lr_geometry.h) compiled for the host: tests/test_lr_unit_host.py checks the
 // counts, the bounds, the cell -> unit map and the coding superblock against the Python restatement (tests/lr_ref.py, tests/lr_unit_ref.py)
 // through the functions below, and runs the stand-alone program (-DLR_GEOMETRY_MAIN) plain and under the sanitizers: for every even size
-// 8 .. 1200 and every shift it proves, from the header alone, what the kernels rely on.
+// 8 .. 1200 and every shift it proves, from the header alone, what the kernels rely on - and, for the two fits' blocks of per-unit tables
+// (av1mi_dev.h: av1mi_lr_fit_split, av1mi_lr_wfit_split), that the parts fill a block of av1mi_lr_*fit_bytes without touching each other.
 #include "../../av1-base_amd/csrc/lr_geometry.h"
 
 extern "C" int geo_count(int size, int shift) { return av1mi_lr_count(size, shift); }
@@ -21,6 +22,9 @@ extern "C" int geo_sb_unit(int sb, int units, int shift) { return av1mi_lr_sb_un
 
 #ifdef LR_GEOMETRY_MAIN
 #include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include "../../av1-base_amd/csrc/av1mi_dev.h"
 
 static long g_checks = 0, g_fail = 0;
 static void check(bool ok, const char *what, int size, int shift, int a, int b) {
@@ -28,7 +32,43 @@ static void check(bool ok, const char *what, int size, int shift, int a, int b) 
   if (!ok && g_fail++ < 20) printf("FAIL %s: size %d shift %d (%d, %d)\n", what, size, shift, a, b);
 }
 
+// a block of exactly the stated size, every part written over its whole extent (the sanitizers see a write past the block), then read
+// back: the parts are disjoint, the 64-bit ones aligned, errors and records are the head the host fetches, at_frame strides every part
+static bool filled(const void *p, int v, size_t bytes) {
+  for (size_t i = 0; i < bytes; i++) if (((const unsigned char *)p)[i] != v) return false;
+  return true;
+}
+static void check_fit_blocks() {
+  for (size_t n = 1; n <= 2000; n += n < 24 ? 1 : 97) {
+    unsigned char *blk = (unsigned char *)malloc(av1mi_lr_fit_bytes(n));
+    const Av1miLrFit F = av1mi_lr_fit_split(blk, n, 0xFFFFu);
+    const size_t be = n * AV1MI_LR_FIT_CANDS * 8, br = n * 4, bs = n * AV1MI_LR_FIT_SETS * 5 * 8, bc = n * 2 * 4;
+    memset(F.err, 1, be); memset(F.rec, 2, br); memset(F.sums, 3, bs); memset(F.code, 4, bc);
+    check(filled(F.err, 1, be) && filled(F.rec, 2, br) && filled(F.sums, 3, bs) && filled(F.code, 4, bc), "self-guided fit: parts disjoint", (int)n, 0, 0, 0);
+    check((unsigned char *)F.err == blk && (unsigned char *)F.rec == blk + be && (unsigned char *)F.rec + br == blk + av1mi_lr_fit_result_bytes(n),
+          "self-guided fit: the fetched head", (int)n, 0, 0, 0);
+    check(((size_t)((unsigned char *)F.sums - blk) & 7) == 0 && (unsigned char *)F.code + bc <= blk + av1mi_lr_fit_bytes(n) && F.mask == 0xFFFFu,
+          "self-guided fit: alignment and end", (int)n, 0, 0, 0);
+    const Av1miLrFit G = F.at_frame(0, n).at_frame(1, n / 2);
+    check(G.err == F.err + n / 2 * AV1MI_LR_FIT_CANDS && G.rec == F.rec + n / 2 * 4 && G.sums == F.sums + n / 2 * AV1MI_LR_FIT_SETS * 5 &&
+          G.code == F.code + n / 2 * 2 && G.mask == F.mask, "self-guided fit: at_frame", (int)n, 0, 0, 0);
+    free(blk);
+    blk = (unsigned char *)malloc(av1mi_lr_wfit_bytes(n));
+    const Av1miLrWfit W = av1mi_lr_wfit_split(blk, n);
+    const size_t we = n * 8, wr = n * 8, ws = n * AV1MI_LR_WFIT_SUMS * 8, wc = n * 3 * 4;
+    memset(W.err, 1, we); memset(W.rec, 2, wr); memset(W.sums, 3, ws); memset(W.code, 4, wc);
+    check(filled(W.err, 1, we) && filled(W.rec, 2, wr) && filled(W.sums, 3, ws) && filled(W.code, 4, wc), "Wiener fit: parts disjoint", (int)n, 0, 0, 0);
+    check((unsigned char *)W.err == blk && (unsigned char *)W.rec + wr == blk + av1mi_lr_wfit_result_bytes(n) &&
+          (unsigned char *)W.code + wc == blk + av1mi_lr_wfit_bytes(n), "Wiener fit: head and end", (int)n, 0, 0, 0);
+    const Av1miLrWfit V = W.at_frame(1, n / 2);
+    check(V.err == W.err + n / 2 && V.rec == W.rec + n / 2 * 8 && V.sums == W.sums + n / 2 * AV1MI_LR_WFIT_SUMS && V.code == W.code + n / 2 * 3,
+          "Wiener fit: at_frame", (int)n, 0, 0, 0);
+    free(blk);
+  }
+}
+
 int main() {
+  check_fit_blocks();
   for (int size = 8; size <= 1200; size += 2)
     for (int shift = 0; shift <= AV1MI_LR_MAX_UNIT_SHIFT; shift++) {
       const int U = 64 << shift, units = av1mi_lr_count(size, shift), cells = av1mi_lr_count(size, 0);

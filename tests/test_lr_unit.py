@@ -232,3 +232,35 @@ def test_bits_clear_is_unchanged(av1mi, oracle, ctx, lr):
     digest = hashlib.sha256(data).hexdigest()
     print("enable_lr %#x: %s" % (lr, digest))
     assert digest == PARENT_BYTES[lr]
+
+
+# sha256 of the bitstreams of the clips below, recorded from a build of the commit before the restoration kernels took their box filter,
+# wave walk and tail from lr_pieces.h: with the seven above, every instantiation of the three kernels at both sample types, chroma
+# sections of one unit and of two, and units larger than a cell
+SHARED_CASES = [(202, 122, 8), (328, 248, 10)]   # signalled != coded size and a chroma pair with a lone last cell; 10-bit
+SHARED_LR = (0x1001, 0x2002, 0x1003, 0x2104, 0x1403, 0x2504)
+SHARED_BYTES = {
+    (202, 8, 0x1001): "0c5fec41bdfe81e371b4780487a1ee5e86db49d2affb1b884ebe0f8c1cf7dba5",
+    (328, 10, 0x1001): "2ea6f7992f218db91a56336580391e0c43a1ab9997321135515604570448e547",
+    (202, 8, 0x2002): "00badb92c61dcc57ef50075d3db870ecf6eff0ea9bf8bf1dca91d25287f753be",
+    (328, 10, 0x2002): "de954c3896726189a67b8475f76f38abf7da5440229cde9cf334fb33942291ca",
+    (202, 8, 0x1003): "5be5fca06a868a870250fb8b2fa1a16aef63cddf4edae796da304dd6103a1d25",
+    (328, 10, 0x1003): "fc21a2cb86cc18cb6562a3c102cfb70d7f51cac2bd288e0e756eff5bf1d13ba2",
+    (202, 8, 0x2104): "d1803718bdf6a13ac2bf13932128de5d1908e39b88c91156ed1b7f63823ce50a",
+    (328, 10, 0x2104): "7c899ac66a3a6796fa49d42a6408caa678da48cc5df2223ac96312cec52cd57d",
+    (202, 8, 0x1403): "a007e48a7bc1989a7ca2299b5eca89c4e88090a2b2fc7313b9b8fe2dc96d5d9e",
+    (328, 10, 0x1403): "1b3521c71ddc23c2d9b6132c5fcb25f7f2741f8b607806f3645bc568de677e02",
+    (202, 8, 0x2504): "980cf72cc740625655c5f12f8bd2d6f38bbebada75f9c94d8cc7a67202eaf2f4",
+    (328, 10, 0x2504): "2d01a2c471814edac92e44f9e9c89c7a9a2b54d08ca3b00669778d52aa306d65",
+}
+
+
+@pytest.mark.parametrize("w,h,bd", SHARED_CASES)
+@pytest.mark.parametrize("lr", SHARED_LR, ids=["%#x" % v for v in SHARED_LR])
+def test_shared_pieces_keep_the_bytes(av1mi, oracle, ctx, w, h, bd, lr):
+    """with the kernels' shared pieces the bytes are those of the commit before them"""
+    frames = wbase.clip(oracle, w, h, bd, 3, seed=123)
+    data, sizes, _, _ = base.encode(ctx, av1mi, frames, w, h, bd, enable_lr=lr, keyint=2, deblock=1)
+    digest = hashlib.sha256(data).hexdigest()
+    print("%dx%d-%d enable_lr %#x: %s" % (w, h, bd, lr, digest))
+    assert digest == SHARED_BYTES[(w, bd, lr)]
