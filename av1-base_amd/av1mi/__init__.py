@@ -36,7 +36,8 @@ E_INVALID_ARG, E_NO_DEVICE, E_HIP, E_OOM, E_OVERFLOW, E_FORMAT, E_UNSUPPORTED = 
 
 # every symbol include/av1mi.h declares
 ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", "av1mi_last_error", "av1mi_encode_chunk",
-               "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units", "av1mi_sym_order_result", "av1mi_sym_order_tiles", "av1mi_inter_partition_result", "av1mi_inter_partition_units"]
+               "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units", "av1mi_sym_order_result", "av1mi_sym_order_tiles", "av1mi_inter_partition_result", "av1mi_inter_partition_units",
+               "av1mi_lr_rd_result", "av1mi_lr_rd_units"]
 
 
 class Params(C.Structure):
@@ -120,6 +121,9 @@ _lib.av1mi_lr_fit_units.restype = C.c_uint32
 _lib.av1mi_lr_wiener_fit_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint64)]
 _lib.av1mi_lr_wiener_fit_units.argtypes = [C.c_void_p]
 _lib.av1mi_lr_wiener_fit_units.restype = C.c_uint32
+_lib.av1mi_lr_rd_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+_lib.av1mi_lr_rd_units.argtypes = [C.c_void_p]
+_lib.av1mi_lr_rd_units.restype = C.c_uint32
 _lib.av1mi_sym_order_result.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_uint32]
 _lib.av1mi_sym_order_tiles.argtypes = [C.c_void_p]
 _lib.av1mi_sym_order_tiles.restype = C.c_uint32
@@ -184,6 +188,17 @@ def lr_fit_field(lr, sets=0):
 LR_WIENER_FIT = 0x400   # include/av1mi.h: AV1MI_LR_WIENER_FIT
 LR_UNIT_128 = 0x1000    # include/av1mi.h: AV1MI_LR_UNIT_128 / AV1MI_LR_UNIT_256 - enable_lr bits 12-13, lr_unit_shift 1 / 2
 LR_UNIT_256 = 0x2000
+LR_RD = 0xC000          # include/av1mi.h: AV1MI_LR_RD(0) - enable_lr bits 14 and 15, both: the unit decisions weigh a rate term
+
+
+def lr_rd_field(s=0):
+    """include/av1mi.h: AV1MI_LR_RD - or-ed into enable_lr; s = 0 .. 3 scales lambda by 1, 1/2, 1/4, 2 (bit 0 of s in bit 9, bit 1 in bit 11)"""
+    return LR_RD | ((s & 1) << 9) | ((s & 2) << 10)
+
+
+def lr_rd_scale_of(enable_lr):
+    """include/av1mi.h: AV1MI_LR_RD_ON / AV1MI_LR_RD_SCALE - the scale s of the rate term, or None without it"""
+    return (((enable_lr >> 9) & 1) | ((enable_lr >> 10) & 2)) if (enable_lr & LR_RD) == LR_RD else None
 
 
 def lr_unit_shift_of(enable_lr):
@@ -197,10 +212,11 @@ def lr_unit_grid(width, height, shift=0):
     return max((height + u // 2) // u, 1), max((width + u // 2) // u, 1)
 
 
-def default_params(width, height, bit_depth=8, aq_strength=None, lr_fit=None, lr_wiener_fit=False, lr_unit_shift=0, **kw):
+def default_params(width, height, bit_depth=8, aq_strength=None, lr_fit=None, lr_wiener_fit=False, lr_unit_shift=0, lr_rd=None, **kw):
     """aq_strength: packed into cq_level beside the CQ level (cq_aq); lr_fit: True or a mask of parameter sets, packed into enable_lr
     (lr_fit_field); lr_wiener_fit: True sets enable_lr's bit 10 (LR_WIENER_FIT); lr_unit_shift: 1 / 2 sets enable_lr's bits 12-13
-    (LR_UNIT_128 / LR_UNIT_256); every other keyword sets the structure field of its name"""
+    (LR_UNIT_128 / LR_UNIT_256); lr_rd: a scale s = 0 .. 3 sets the rate term of the unit decisions (lr_rd_field); every other keyword
+    sets the structure field of its name"""
     p = Params()
     _lib.av1mi_default_params(C.byref(p), width, height, bit_depth)
     if lr_fit is not None and lr_fit is not False:
@@ -209,6 +225,8 @@ def default_params(width, height, bit_depth=8, aq_strength=None, lr_fit=None, lr
         kw["enable_lr"] = kw.get("enable_lr", p.enable_lr) | LR_WIENER_FIT
     if lr_unit_shift:
         kw["enable_lr"] = kw.get("enable_lr", p.enable_lr) | ((int(lr_unit_shift) & 3) << 12)
+    if lr_rd is not None and lr_rd is not False:
+        kw["enable_lr"] = kw.get("enable_lr", p.enable_lr) | lr_rd_field(int(lr_rd))
     if aq_strength is not None:
         kw["cq_level"] = cq_aq(kw.get("cq_level", p.cq_level), aq_strength)
     for k, v in kw.items():
@@ -379,6 +397,25 @@ class Context:
         rc = _lib.av1mi_lr_wiener_fit_result(self._h, n_frames, units.ctypes.data_as(C.POINTER(C.c_int8)), err.ctypes.data_as(C.POINTER(C.c_uint64)))
         _raise_for(rc, "av1mi_lr_wiener_fit_result: the context's last successfully encoded chunk does not have %d frames (or there is none)" % n_frames)
         return units, err
+
+    def lr_rd_result(self, n_frames, width=None, height=None):
+        """The final restoration decisions of the last encoded chunk (include/av1mi.h: av1mi_lr_rd_result), for every enable_lr value
+        with a low byte of 1 .. 4: numpy arrays choice[frame][plane][unit row][unit column] (int8, 0 .. 23) and bits16 likewise (uint32:
+        the choice's side information in sixteenths of a bit), and lambda (int; 0 without the rate term).  Sized and shaped as
+        lr_fit_result's."""
+        import numpy as np
+        n_units = int(_lib.av1mi_lr_rd_units(self._h))
+        if width is None or height is None:
+            width, height = self._last_size if self._last_size is not None else (0, 0)
+        ur, uc = lr_unit_grid(width, height, self._last_unit_shift)
+        if n_units == 0 or ur * uc != n_units:
+            _raise_for(E_INVALID_ARG, "av1mi_lr_rd_result: the last chunk has %d units per plane, not the %d x %d of %d x %d frames" % (n_units, ur, uc, width, height))
+        choice = np.zeros((n_frames, 3, ur, uc), dtype=np.int8)
+        bits16 = np.zeros((n_frames, 3, ur, uc), dtype=np.uint32)
+        lam = C.c_uint64(0)
+        rc = _lib.av1mi_lr_rd_result(self._h, n_frames, choice.ctypes.data_as(C.POINTER(C.c_int8)), bits16.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(lam))
+        _raise_for(rc, "av1mi_lr_rd_result: the context's last successfully encoded chunk does not have %d frames (or there is none)" % n_frames)
+        return choice, bits16, int(lam.value)
 
     def inter_partition_result(self, n_frames, width=None, height=None):
         """The partition of the last encoded chunk's frames under partition_search 1 / 2 (include/av1mi.h: av1mi_inter_partition_result):

@@ -22,7 +22,7 @@
 #define AV1MI_AQ_MAX_STRENGTH 4
 #define AV1MI_AQ_MAX_DELTA 6    /* |d|: the index moves by at most 24 either way */
 
-AV1MI_AQ_HD inline int av1mi_aq_log2_q4(uint32_t x) {
+AV1MI_AQ_HD constexpr int av1mi_aq_log2_q4(uint32_t x) {
   const int k = 31 - __builtin_clz(x);
   return 16 * k + (int)((((uint64_t)x << 4) >> k) & 15);
 }

@@ -108,6 +108,9 @@ struct Av1miDevParams {
   // reference RefLrWiener (both passes), MSB first in the low `lr_code_len[r][k]` bits
   int enable_lr;                         // the frames' restoration type: 1 = RESTORE_WIENER, 2 = RESTORE_SWITCHABLE (any plane)
   int lr_code_len[4][3];                 // [reference: 0 = Wiener_Taps_Mid, r = candidate r-1][candidate]
+  // av1mi_params.enable_lr bits 14 and 15: the unit decisions minimise 16 D + lr_lambda B16 (lr_rate_rule.h); 0 = by
+  // the error alone.  The fixed candidates' B16 come from the lengths against reference 0 here and below.  (In what was padding.)
+  uint32_t lr_lambda;
   unsigned long long lr_code_bits[4][3];
   // enable_lr = 2: the same for a self-guided unit (lr_sgr_set + both weights against RefSgrXqd; reference 0 = Sgrproj_Xqd_Mid)
   int sgr_code_len[4][3];
@@ -130,6 +133,7 @@ struct Av1miDevParams {
   Av1miChunkRecord *chunk_record;
   const uint32_t *tile_symbols;
 };
+static_assert(sizeof(Av1miDevParams) == 864, "lr_lambda took padding: the block, a kernel argument, keeps its size");
 
 // ---- adaptive quantisation: the parameter block in device memory is followed by one copy per quantiser slot, equal to it except for
 // dc_q, ac_q, their reciprocals and the quantiser-matrix slice.  Slot 0 is the block itself (base_q_idx); slot 1 + 6 + d holds

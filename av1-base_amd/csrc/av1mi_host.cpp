@@ -27,6 +27,7 @@
 #include "av1mi_dev.h"
 #include "av1mi_launch.h"
 #include "lr_fit_rule.h"
+#include "lr_rate_rule.h"
 #include "wiener_fit_rule.h"
 #include "deblock_pieces.h"
 #include "aq_rule.h"
@@ -85,6 +86,7 @@ struct Resolved {
   uint32_t lr_fit_mask;               // enable_lr bit 8: the parameter sets the self-guided fit searches, 0 = no fit (p.enable_lr holds the type)
   int lr_wfit;                        // enable_lr bit 10: the Wiener fit (p.enable_lr holds the type)
   int lr_unit_shift;                  // enable_lr bits 12-13: luma restoration units of 64 << lr_unit_shift samples (0 .. 2)
+  uint32_t lr_lambda;                 // enable_lr bits 14 and 15: the rate term's lambda (lr_rate_rule.h), 0 = the decisions go by the error alone
 };
 
 // aom's quantizer_to_qindex[] (CQ level -> base_q_idx); 30 -> 120
@@ -117,6 +119,16 @@ int resolve(const av1mi_params *in, Resolved *r) {
   if (p.deblock > 2) return AV1MI_E_INVALID_ARG;
   r->qidx = kQuantizerToQindex[p.cq_level];
   r->q = quant_steps(r->qidx, (int)p.bit_depth);
+  // enable_lr bits 14 and 15, both (AV1MI_LR_RD): the rate term, with any low byte 1 .. 4, either fit and a unit size; bits 9 and 11 are
+  // then its scale.  lambda stays with base_q_idx under adaptive quantisation, like the deblocking level.  (Without both bits the four
+  // stay in the field, which the checks below refuse.)
+  r->lr_lambda = 0;
+  if (AV1MI_LR_RD_ON(p.enable_lr)) {
+    const uint32_t low = p.enable_lr & 0xFFu;
+    if (low < 1 || low > 4) return AV1MI_E_INVALID_ARG;
+    r->lr_lambda = (uint32_t)av1mi_lr_lambda_of_step((unsigned long long)r->q.dc_q, (int)AV1MI_LR_RD_SCALE(p.enable_lr));
+    p.enable_lr &= ~0xCA00u;
+  }
   // enable_lr bits 12-13 (AV1MI_LR_UNIT_128 / _256): the unit size, with any low byte 1 .. 4 and either fit; 3 is no size
   r->lr_unit_shift = (int)((p.enable_lr >> 12) & 3u);
   if (r->lr_unit_shift) {
@@ -766,6 +778,7 @@ Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale, const
   P.enable_lr = (int)p.enable_lr;
   P.lr_chroma = r.lr_chroma;
   P.lr_unit_shift = r.lr_unit_shift;
+  P.lr_lambda = r.lr_lambda;
   P.lr_fit_code = r.lr_fit_mask ? lr_fit_code : nullptr;
   P.lr_wfit_code = r.lr_wfit ? lr_wfit_code : nullptr;
   P.chunk_record = record; P.tile_symbols = tile_symbols;
@@ -1161,6 +1174,46 @@ int av1mi_lr_wiener_fit_result(const av1mi_ctx *c, uint32_t n_frames, int8_t *un
     memset(units, 0, n * 8);
     if (err) memset(err, 0, n * 8);
   }
+  return AV1MI_OK;
+}
+
+uint32_t av1mi_lr_rd_units(const av1mi_ctx *c) { return c ? c->fit_plane_units : 0; }
+// The final restoration decisions of the context's last chunk: the choices as they still stand on the device (the context's next chunk
+// overwrites them), fetched here - a diagnostic like av1mi_sym_order_result - and their B16 from the fits' records, which arrived with
+// the chunk.
+int av1mi_lr_rd_result(const av1mi_ctx *c, uint32_t n_frames, int8_t *choice, uint32_t *bits16, uint64_t *lambda) {
+  if (!c || !choice || n_frames == 0 || c->lf_levels.size() != (size_t)n_frames * 4) return AV1MI_E_INVALID_ARG;
+  const Av1miDevParams &P = c->P;
+  const size_t n = c->fit_units, per = c->fit_plane_units;
+  memset(choice, 0, n);
+  if (bits16) memset(bits16, 0, n * sizeof(uint32_t));
+  if (lambda) *lambda = P.enable_lr ? P.lr_lambda : 0;
+  if (!P.enable_lr) return AV1MI_OK;
+  const int planes = P.lr_chroma ? 3 : 1, sw = P.enable_lr == 2;
+  std::vector<uint8_t> dev((size_t)n_frames * planes * per);   // [frame][restored plane][unit]
+  if (hipSetDevice(c->device) != hipSuccess || hipMemcpy(dev.data(), c->ws.d_lrc, dev.size(), hipMemcpyDeviceToHost) != hipSuccess) return AV1MI_E_HIP;
+  const Av1miLrFit G = c->fit_on ? av1mi_lr_fit_split(c->ws.h_fit, n, 0) : Av1miLrFit{};
+  const Av1miLrWfit W = c->wfit_on ? av1mi_lr_wfit_split(c->ws.h_wfit, n) : Av1miLrWfit{};
+  for (uint32_t f = 0; f < n_frames; f++)
+    for (int pl = 0; pl < planes; pl++)
+      for (size_t k = 0; k < per; k++) {
+        const size_t u = ((size_t)f * 3 + pl) * per + k;
+        const int ch = dev[((size_t)f * planes + pl) * per + k];
+        choice[u] = (int8_t)ch;
+        if (!bits16) continue;
+        int lc = 0;
+        if (ch == AV1MI_LR_WFIT_CHOICE) {
+          if (!W.rec) return AV1MI_E_HIP;
+          const int8_t *q = W.rec + u * 8;
+          lc = av1mi_lr_wiener_lc(pl > 0, q[2], q[3], q[4], q[5], q[6], q[7]);
+        } else if (ch >= 7) {
+          if (!G.rec) return AV1MI_E_HIP;
+          const int8_t *q = G.rec + u * 4;
+          lc = av1mi_lr_sgr_lc(q[1], q[2], q[3]);
+        } else if (ch >= 4) lc = P.sgr_code_len[0][ch - 4];
+        else if (ch) lc = pl ? P.lr_code_len_uv[0][ch - 1] : P.lr_code_len[0][ch - 1];
+        bits16[u] = (uint32_t)av1mi_lr_b16(lc, av1mi_lr_type_t16(sw, av1mi_lr_choice_type(ch)));
+      }
   return AV1MI_OK;
 }
 

@@ -12,7 +12,8 @@
 //             (14-bit terms; a unit of 256 luma samples has at most 383 x 391 of them: |sum| < 2^46)
 //   2 SSE     every slice solves its units' weights from the complete sums (32 lanes, one (unit, set) each), filters again and adds
 //             its exact SSE per set
-//   3 decide  first minimum over the 23 candidates, the unit's record, and the winner of any kind applied (with the padding and,
+//   3 decide  first minimum over the 23 candidates - of the error or, with the rate term (lr_rate_rule.h), of J, the fitted weights' bits
+//             counted beside the solve - the unit's record, and the winner of any kind applied (with the padding and,
 //             without chroma restoration, the chroma copy of lr_kernel.hip's phase 1)
 //   4 codes   one thread per (frame, plane, tile) carries RefSgrXqd over the tile's units in coding order
 // Sets 11, 12, 13 share their r = 1 strengths with sets 2, 5, 8: the sets run in an order that puts them behind those, and a pass whose
@@ -22,12 +23,14 @@
 #include "av1mi_dev.h"
 #include "av1mi_launch.h"
 #include "lr_fit_rule.h"
+#include "lr_rate_rule.h"
 
 namespace {
 
 #include "lr_pieces.h"
 
-__shared__ int g_fitw[2][AV1MI_LR_FIT_SETS];   // [unit of the wave's section][set]: -1 absent, else (xqd0 + 128) | (xqd1 + 128) << 8
+// [unit of the wave's section][set]: -1 absent, else (xqd0 + 128) | (xqd1 + 128) << 8 and, for a decision with the rate term, Lc << 16
+__shared__ int g_fitw[2][AV1MI_LR_FIT_SETS];
 
 // the sets in the order 0 1 2 11 3 4 5 12 6 7 8 13 9 10 14 15, a nibble each
 __device__ __forceinline__ int fit_order(int i) { return (int)((0xFEA9D876C543B210ull >> (4 * i)) & 15); }
@@ -66,21 +69,24 @@ __global__ void __launch_bounds__(64) lr_fit_kernel(Av1miDevParams P, const PIX 
         const int h = lane >> 4, t = lane & 15;
         int w0 = 0, w1 = 0, ok = 0;
         if ((F.mask >> t) & 1) ok = av1mi_lr_fit_solve(t, F.sums + ((fit_base + (h ? hi : lo)) * AV1MI_LR_FIT_SETS + t) * 5, &w0, &w1);
-        g_fitw[h][t] = ok ? ((w0 + 128) | ((w1 + 128) << 8)) : -1;
+        int lc = 0;
+        if constexpr (PHASE == 3) { if (ok && P.lr_lambda) lc = av1mi_lr_sgr_lc(t, w0, w1); }
+        g_fitw[h][t] = ok ? ((w0 + 128) | ((w1 + 128) << 8) | (lc << 16)) : -1;
       }
       __syncthreads();
     }
     [[maybe_unused]] int best[2] = { 0, 0 }, bset[2] = { 0, 0 }, bw0[2] = { 0, 0 }, bw1[2] = { 0, 0 };
     if constexpr (PHASE == 3) {
+      const LrRate rate = lr_rate(P, sub);
 #pragma unroll
       for (int h = 0; h < 2; h++) {
         const unsigned long long *e = F.err + (fit_base + (h ? hi : lo)) * AV1MI_LR_FIT_CANDS;
-        unsigned long long bs;
-        best[h] = lr_decide(unit_sse + (sse_base + (h ? hi : lo)) * 8, 6, bs);   // ... and on over the fitted sets
+        unsigned long long bj;
+        best[h] = lr_decide(unit_sse + (sse_base + (h ? hi : lo)) * 8, 6, rate, bj);   // ... and on over the fitted sets
         for (int t = 0; t < AV1MI_LR_FIT_SETS; t++) {
           if (g_fitw[h][t] < 0) continue;
-          const unsigned long long s = e[7 + t];
-          if (s < bs) { bs = s; best[h] = 7 + t; }
+          const unsigned long long j = av1mi_lr_j(e[7 + t], rate.lambda, av1mi_lr_b16(g_fitw[h][t] >> 16, rate.t16_sgr));
+          if (j < bj) { bj = j; best[h] = 7 + t; }
         }
         if (best[h] >= 7) { const int fw = g_fitw[h][best[h] - 7]; bset[h] = best[h] - 7; bw0[h] = (fw & 255) - 128; bw1[h] = ((fw >> 8) & 255) - 128; }
         else if (best[h] >= 4) { bset[h] = c_sgr_cand[best[h] - 4][0]; bw0[h] = c_sgr_cand[best[h] - 4][1]; bw1[h] = c_sgr_cand[best[h] - 4][2]; }
@@ -128,7 +134,7 @@ __global__ void __launch_bounds__(64) lr_fit_kernel(Av1miDevParams P, const PIX 
               if ((lane & 31) == 0 && v) atomicAdd(&dst[k], v);
             }
           } else {
-            const int fw = g_fitw[hsel][t], w0 = (fw & 255) - 128, w1 = ((fw >> 8) & 255) - 128;
+            const int fw = g_fitw[hsel][t], w0 = (fw & 255) - 128, w1 = ((fw >> 8) & 255) - 128;   // (PHASE 2: no Lc above)
             unsigned long long sse = 0;
 #pragma unroll
             for (int i = 0; i < 16; i++)

@@ -91,20 +91,27 @@ AV1MI_FIT_HD inline int av1mi_lr_fit_solve(int t, const long long *sums, int *xq
 }
 
 // ---- loop restoration unit syntax (§5.11.58): literal bits, MSB first in the low `len` bits.  Mirrors
-// decode_signed_subexp_with_ref_bool / decode_subexp_bool / NS / inverse_recenter.
+// decode_signed_subexp_with_ref_bool / decode_subexp_bool / NS / inverse_recenter.  The writers take any sink with put(value, bits):
+// the bit string, or the count alone (lr_rate_rule.h weighs a unit's length).
 struct Av1miBitString {
   unsigned long long bits = 0;
   int len = 0;
   AV1MI_FIT_HD void put(unsigned v, int n) { for (int i = n - 1; i >= 0; i--) { bits = (bits << 1) | ((v >> i) & 1); len++; } }
 };
-AV1MI_FIT_HD inline void lr_put_ns(Av1miBitString &b, int n, int v) {
+struct Av1miBitCount {
+  int len = 0;
+  AV1MI_FIT_HD void put(unsigned, int n) { len += n; }
+};
+template <typename SINK>
+AV1MI_FIT_HD inline void lr_put_ns(SINK &b, int n, int v) {
   int w = 0, x = n;
   while (x) { w++; x >>= 1; }
   const int m = (1 << w) - n;
   if (v < m) b.put((unsigned)v, w - 1);
   else { const int extra = v + m; b.put((unsigned)(extra >> 1), w - 1); b.put((unsigned)(extra & 1), 1); }
 }
-AV1MI_FIT_HD inline void lr_put_subexp(Av1miBitString &b, int num_syms, int k, int v) {
+template <typename SINK>
+AV1MI_FIT_HD inline void lr_put_subexp(SINK &b, int num_syms, int k, int v) {
   int i = 0, mk = 0;
   for (;;) {
     const int b2 = i ? k + i - 1 : k, a = 1 << b2;
@@ -114,7 +121,8 @@ AV1MI_FIT_HD inline void lr_put_subexp(Av1miBitString &b, int num_syms, int k, i
   }
 }
 AV1MI_FIT_HD inline int lr_recenter(int r, int v) { return v > 2 * r ? v : (v >= r ? (v - r) << 1 : ((r - v) << 1) - 1); }
-AV1MI_FIT_HD inline void lr_put_signed_ref(Av1miBitString &b, int low, int high, int k, int r, int v) {
+template <typename SINK>
+AV1MI_FIT_HD inline void lr_put_signed_ref(SINK &b, int low, int high, int k, int r, int v) {
   const int mx = high - low, x = v - low, rr = r - low;
   if ((rr << 1) <= mx) lr_put_subexp(b, mx, k, lr_recenter(rr, x));
   else lr_put_subexp(b, mx, k, lr_recenter(mx - 1 - rr, mx - 1 - x));
@@ -122,11 +130,15 @@ AV1MI_FIT_HD inline void lr_put_signed_ref(Av1miBitString &b, int low, int high,
 
 // A self-guided unit: lr_sgr_set L(4), then the weight(s) whose radius is non-zero against the plane's RefSgrXqd (ref0, ref1), k = 4:
 // at most 4 + 9 + 9 = 22 bits.  The caller carries the reference: after the unit it is (xqd0, xqd1), implied values included.
-AV1MI_FIT_HD inline Av1miBitString av1mi_lr_sgr_code(int set, int xqd0, int xqd1, int ref0, int ref1) {
-  Av1miBitString b;
+template <typename SINK>
+AV1MI_FIT_HD inline void av1mi_lr_sgr_put(SINK &b, int set, int xqd0, int xqd1, int ref0, int ref1) {
   b.put((unsigned)set, 4);
   if (av1mi_sgr_r0(set)) lr_put_signed_ref(b, AV1MI_SGR_XQD0_MIN, AV1MI_SGR_XQD0_MAX + 1, 4, ref0, xqd0);
   if (av1mi_sgr_r1(set)) lr_put_signed_ref(b, AV1MI_SGR_XQD1_MIN, AV1MI_SGR_XQD1_MAX + 1, 4, ref1, xqd1);
+}
+AV1MI_FIT_HD inline Av1miBitString av1mi_lr_sgr_code(int set, int xqd0, int xqd1, int ref0, int ref1) {
+  Av1miBitString b;
+  av1mi_lr_sgr_put(b, set, xqd0, xqd1, ref0, ref1);
   return b;
 }
 

@@ -5,7 +5,8 @@
 // (/root/reference/crates/daemon/src/encode/av1an.rs:126-139).  Normative part: AV1 spec §7.17.3 (units offset by 8 luma
 // rows), §7.17.4 (separable 7-tap Wiener filter, Round2 by 3 then 11, intermediate clamp) and §7.17.6 (rows outside the
 // 64-row stripe come from the pre-CDEF frame, at most 2 rows away).  Encoder part: a unit takes the
-// candidate filter with the smallest SSE against the source, or none; restated in oracle/av1o_lr.c.
+// candidate filter with the smallest SSE against the source, or none; restated in oracle/av1o_lr.c.  With av1mi_params.enable_lr bits 14
+// and 15 the smallest J = 16 SSE + lambda x side information instead (lr_rate_rule.h; no oracle).
 //
 // MI355X mapping: waves of 16 rows of a 64x64 unit (lane = column), two phases (see lr_unit_kernel).  Per stripe of the unit the horizontal pass of 70 rows goes to
 // LDS as int16 (the spec's clamp keeps it in 16 bits for 8/10 bit), the vertical pass reads 7 LDS rows per sample.  The
@@ -18,6 +19,7 @@
 #include <type_traits>
 #include "av1mi_dev.h"
 #include "av1mi_launch.h"
+#include "lr_rate_rule.h"
 
 namespace {
 
@@ -114,8 +116,9 @@ __device__ __forceinline__ void lr_chroma(const Av1miDevParams &P, int item, con
       }
     } else {
       // both units' decisions in every lane (the stripe loop below stays uniform); each lane applies its own unit's
-      unsigned long long bs;
-      const int best_lo = lr_decide(unit_sse + (ubase + uc_lo) * 8, SGR ? 6 : 3, bs), best_hi = lr_decide(unit_sse + (ubase + uc_hi) * 8, SGR ? 6 : 3, bs);
+      unsigned long long bj;
+      const LrRate rate = lr_rate(P, 1);
+      const int best_lo = lr_decide(unit_sse + (ubase + uc_lo) * 8, SGR ? 6 : 3, rate, bj), best_hi = lr_decide(unit_sse + (ubase + uc_hi) * 8, SGR ? 6 : 3, rate, bj);
       const int best = lane < 32 ? best_lo : best_hi;
       if (slice == 0 && cr == av1mi_lr_first_cell(ur, ush) && x == av1mi_lr_first_cell(uc, ush) * 32) choice[ubase + uc] = (uint8_t)best;
       const bool any_wiener = (best_lo && best_lo <= 3) || (best_hi && best_hi <= 3), any_sgr = best_lo > 3 || best_hi > 3;
@@ -243,8 +246,8 @@ __global__ void __launch_bounds__(64) lr_unit_kernel(Av1miDevParams P, const PIX
     if (lane == 0 && v) atomicAdd(&usse[k], v);
   }
   } else {
-  unsigned long long bs;
-  const int best = lr_decide(usse, SGR ? 6 : 3, bs);
+  unsigned long long bj;
+  const int best = lr_decide(usse, SGR ? 6 : 3, lr_rate(P, 0), bj);
   if (lane == 0 && slice == 0 && cr == av1mi_lr_first_cell(ur, ush) && cc == av1mi_lr_first_cell(uc, ush)) choice[uidx] = (uint8_t)best;
   // ---- apply: luma of the slice, and (without CHROMA) the co-located chroma (copied)
   for (int xs = x0; xs < x1; xs += 64) {

@@ -3,7 +3,8 @@
 // box filter with the strength as an argument, the decision over the fixed candidates, the tail of the applying phase, the reductions
 // and the launchers' head; for the two fit files also the stripes, the wave and its sections, and the code kernels' walk (lr_unit_kernel
 // and lr_chroma keep their own index arithmetic and stripe loops).  Included inside each translation unit's
-// unnamed namespace (after av1mi_dev.h and av1mi_launch.h), so each has its own LDS and constants.
+// unnamed namespace (after av1mi_dev.h, av1mi_launch.h and lr_rate_rule.h, whose rate term the decision weighs), so each has its own LDS
+// and constants.
 // LDS per wave: window 3.1 KB + Wiener tile 3.1 KB + self-guided grids 10.7 KB.
 
 // the fixed candidates (lr_fit_rule.h)
@@ -49,14 +50,34 @@ __device__ __forceinline__ unsigned long long half_sum64(unsigned long long v) {
   return v;
 }
 
-// the decision of a unit over the fixed candidates from its sums: the first minimum in the order off, Wiener 1..3 and (ncand = 6)
-// self-guided 1..3; bs: the minimum, for the self-guided fit to go on from
-__device__ __forceinline__ int lr_decide(const unsigned long long *usse, int ncand, unsigned long long &bs) {
+// the rate terms of a plane's fixed candidates (lr_rate_rule.h): B16 of off, Wiener 1..3 and self-guided 1..3 - the type symbol under the
+// frames' restoration type plus the length of the host's bit string against the tile-start reference - and of the two fitted kinds the
+// type symbol alone; lambda = 0: the decisions go by the error alone
+struct LrRate {
+  unsigned long long lambda;
+  int b16[7], t16_wiener, t16_sgr;
+};
+__device__ __forceinline__ LrRate lr_rate(const Av1miDevParams &P, int sub) {
+  const int sw = P.enable_lr == 2;
+  LrRate R;
+  R.lambda = P.lr_lambda;
+  R.t16_wiener = av1mi_lr_type_t16(sw, 1); R.t16_sgr = av1mi_lr_type_t16(sw, 2);
+  R.b16[0] = av1mi_lr_type_t16(sw, 0);
+  for (int k = 0; k < 3; k++) {
+    R.b16[1 + k] = av1mi_lr_b16(sub ? P.lr_code_len_uv[0][k] : P.lr_code_len[0][k], R.t16_wiener);
+    R.b16[4 + k] = av1mi_lr_b16(P.sgr_code_len[0][k], R.t16_sgr);
+  }
+  return R;
+}
+
+// the decision of a unit over the fixed candidates from its sums: the first minimum of J = 16 D + lambda B16 in the order off, Wiener 1..3
+// and (ncand = 6) self-guided 1..3; bj: the minimum, for the self-guided fit to go on from
+__device__ __forceinline__ int lr_decide(const unsigned long long *usse, int ncand, const LrRate &R, unsigned long long &bj) {
   int best = 0;
-  bs = usse[0];
+  bj = av1mi_lr_j(usse[0], R.lambda, R.b16[0]);
   for (int k = 0; k < ncand; k++) {
-    const unsigned long long s = usse[k + 1];
-    if (s < bs) { bs = s; best = k + 1; }
+    const unsigned long long j = av1mi_lr_j(usse[k + 1], R.lambda, R.b16[k + 1]);
+    if (j < bj) { bj = j; best = k + 1; }
   }
   return best;
 }

@@ -13,8 +13,8 @@
 //               atomic per sum and half into the unit's sums (a unit of 256 has at most 383 x 391 samples: |sum| < 2^40)
 //   2 SSE       every slice solves its units' taps from the complete sums (lanes 0 and 1, one unit each), filters with the two tap
 //               arrays and adds its exact SSE; the unit's first lane records the taps
-//   3 override  a unit whose fitted error is strictly below its winner's is filtered again with the fitted taps (read-only on every
-//               table: the slices of a unit take the same decision)
+//   3 override  a unit whose fitted error - with the rate term, its J - is strictly below its winner's is filtered again with the fitted
+//               taps (read-only on every table: the slices of a unit take the same decision)
 //   4 codes     one thread per (frame, plane, tile) walks the tile's units in coding order: the final choice (23 = fitted) into the
 //               record and the choice table, and the bits of every Wiener unit against the carried RefLrWiener
 #include <hip/hip_runtime.h>
@@ -22,6 +22,7 @@
 #include "av1mi_dev.h"
 #include "av1mi_launch.h"
 #include "wiener_fit_rule.h"
+#include "lr_rate_rule.h"
 
 namespace {
 
@@ -40,6 +41,22 @@ struct BaseErr {
 __device__ __forceinline__ unsigned long long base_err_of(const BaseErr &B, size_t sse_idx, size_t fit_idx) {
   const int c = B.choice[sse_idx];
   return B.fit_err ? B.fit_err[fit_idx * AV1MI_LR_FIT_CANDS + c] : B.unit_sse[sse_idx * 8 + c];
+}
+
+// Does the fitted filter of unit u (present; cu: the unit in the fixed candidates' tables; sub: a chroma plane) replace the unit's winner:
+// iff its error is strictly smaller or, with the rate term, its J = 16 D + lambda B16 is (lr_rate_rule.h).  The winner's coefficient
+// length is the host's against the tile-start reference for a fixed candidate, the syntax writer's for fitted weights and taps.
+__device__ __forceinline__ bool wfit_overrides(const Av1miDevParams &P, const BaseErr &B, const Av1miLrWfit &F, size_t cu, size_t u, int sub) {
+  const unsigned long long ef = F.err[u], eb = base_err_of(B, cu, u);
+  if (!P.lr_lambda) return ef < eb;
+  const int sw = P.enable_lr == 2, c = B.choice[cu];
+  int lc = 0;
+  if (c >= 7) { const int8_t *q = B.fit_rec + u * 4; lc = av1mi_lr_sgr_lc(q[1], q[2], q[3]); }
+  else if (c >= 4) lc = P.sgr_code_len[0][c - 4];
+  else if (c) lc = sub ? P.lr_code_len_uv[0][c - 1] : P.lr_code_len[0][c - 1];
+  const int8_t *r = F.rec + u * 8;
+  const int bf = av1mi_lr_b16(av1mi_lr_wiener_lc(sub, r[2], r[3], r[4], r[5], r[6], r[7]), av1mi_lr_type_t16(sw, 1));
+  return av1mi_lr_j(ef, P.lr_lambda, bf) < av1mi_lr_j(eb, P.lr_lambda, av1mi_lr_b16(lc, av1mi_lr_type_t16(sw, av1mi_lr_choice_type(c))));
 }
 
 // PHASE 1: sums; 2: solve and SSE; 3: override.  The grid is lr_unit_kernel's.
@@ -83,7 +100,7 @@ __global__ void __launch_bounds__(64) lr_wfit_kernel(Av1miDevParams P, const PIX
       bool ov[2];
       for (int h = 0; h < 2; h++) {
         const size_t fu = fit_base + (h ? hi : lo);
-        ov[h] = F.rec[fu * 8 + 1] != 0 && F.err[fu] < base_err_of(B, sse_base + (h ? hi : lo), fu);
+        ov[h] = F.rec[fu * 8 + 1] != 0 && wfit_overrides(P, B, F, sse_base + (h ? hi : lo), fu, sub);
       }
       const int8_t *r = F.rec + (fit_base + unit) * 8;
       taps7(r[2], r[3], r[4], fv); taps7(r[5], r[6], r[7], fh);
@@ -159,7 +176,7 @@ __global__ void __launch_bounds__(64) lr_wfit_code_kernel(Av1miDevParams P, uint
     int8_t *r = F.rec + u * 8;
     int c = choice[cu];
     if (!r[1]) F.err[u] = ~0ull;
-    else if (F.err[u] < base_err_of(B, cu, u)) { c = AV1MI_LR_WFIT_CHOICE; choice[cu] = (uint8_t)c; }
+    else if (wfit_overrides(P, B, F, cu, u, pl > 0)) { c = AV1MI_LR_WFIT_CHOICE; choice[cu] = (uint8_t)c; }
     r[0] = (int8_t)c;
     if (B.fit_code && c >= 4 && c != AV1MI_LR_WFIT_CHOICE) {
       const int8_t *q = B.fit_rec + u * 4;

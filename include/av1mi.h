@@ -49,6 +49,11 @@ typedef struct av1mi_ctx av1mi_ctx;
 #define AV1MI_LR_UNIT_128 0x1000u
 #define AV1MI_LR_UNIT_256 0x2000u
 #define AV1MI_LR_UNIT_SHIFT(v) (((uint32_t)(v) >> 12) & 3u)
+/* av1mi_params.enable_lr bits 14 and 15, both: the unit decisions weigh a rate term, or-ed into a value with a low byte of 1 .. 4 (with
+ * or without either fit and a unit size); s = 0 .. 3 scales lambda by 1, 1/2, 1/4, 2: bit 0 of s is bit 9 of the field, bit 1 is bit 11 */
+#define AV1MI_LR_RD(s) (0xC000u | (((uint32_t)(s) & 1u) << 9) | (((uint32_t)(s) & 2u) << 10))
+#define AV1MI_LR_RD_ON(v) (((uint32_t)(v) & 0xC000u) == 0xC000u)
+#define AV1MI_LR_RD_SCALE(v) ((((uint32_t)(v) >> 9) & 1u) | (((uint32_t)(v) >> 10) & 2u))
 
 /* Operating point.  Replaces the reference's single constant
  *   SVT_PARAMS = "--crf 8 --preset 3 --film-grain 20 ... --keyint 240 --lookahead 40"
@@ -91,7 +96,7 @@ typedef struct {
                                self-guided filter is fitted per unit - beside the seven candidates above a unit may take any of
                                the 16 parameter sets (bits 16-31: a mask over the sets searched, 0 = all) with the two weights
                                that least squares gives for the unit, the smallest exact SSE winning as before.  Headers are
-                               those of 2 / 4.  Bit 8 with any other low byte, and bits 9, 11, 14 and 15, are refused with
+                               those of 2 / 4.  Bit 8 with any other low byte, and bits 9, 11, 14 and 15 (but see AV1MI_LR_RD below), are refused with
                                AV1MI_E_INVALID_ARG.  av1mi_lr_fit_result reports the units' choices;
                                bit 10 (AV1MI_LR_WIENER_FIT) with a low byte of 1 .. 4, alone or with
                                bit 8: after the decision above a unit's Wiener filter is fitted by least squares - three vertical
@@ -105,6 +110,15 @@ typedef struct {
                                signals a quarter / a sixteenth of the side information.  The frame header grows by one bit.  Both
                                bits set, and either with a low byte of 0, are refused with AV1MI_E_INVALID_ARG.  A context may
                                change the unit size from chunk to chunk;
+                               bits 14 and 15, both (AV1MI_LR_RD(s)) with a low byte of 1 .. 4 and any of
+                               the bits above: every unit decision - fixed candidates, self-guided fit, Wiener override, all planes,
+                               all unit sizes - minimises J = 16 D + lambda B16 instead of the squared error D.  B16 is the unit's
+                               side information in sixteenths of a bit: its coefficients' length against the tile-start reference
+                               plus its type symbol under the default CDFs; lambda = (13 q^2) >> 9 from the dc step q of base_q_idx,
+                               scaled by s = 0 .. 3 (bits 9 and 11 of the field): x1, x1/2, x1/4, x2.  Filters, fits, candidate order,
+                               syntax and headers are unchanged.  Bits 9, 11, 14 or 15 without both of 14 and 15 stay refused with
+                               AV1MI_E_INVALID_ARG, as do both with a low byte of 0 or above 4.  A context may switch the mode from
+                               chunk to chunk.  av1mi_lr_rd_result reports the units' final choices and bits;
                                default 0: the decision needs the CDEF output, which serialises CDEF before entropy coding */
   uint32_t tile_sb;         /* tile size in 64x64 superblocks, both ways: 0 = automatic (1; 2 when the frame has more than 64
                                superblock rows or columns, e.g. 8K - AV1 allows at most 64 x 64 tiles), or force 1 / 2 */
@@ -271,6 +285,17 @@ int av1mi_lr_wiener_fit_result(const av1mi_ctx *ctx, uint32_t n_frames, int8_t *
 /* n_units of the context's last successfully encoded chunk, at that chunk's unit size (0: none): units holds n_frames * 3 * n_units * 8 entries, err
  * n_frames * 3 * n_units */
 uint32_t av1mi_lr_wiener_fit_units(const av1mi_ctx *ctx);
+
+/* ---- restoration decisions of the last chunk --------------------------------------------------
+ * For every enable_lr value with a low byte of 1 .. 4, with or without the rate term (AV1MI_LR_RD): per restoration unit of the context's
+ * last successfully encoded chunk choice[(f * 3 + plane) * n_units + u] = the unit's final choice 0 .. 23 in av1mi_lr_wiener_fit_result's
+ * numbering, (optional) bits16[...] = B16 of that choice - 16 x the length of its coefficients against the plane's tile-start references
+ * plus the cost of its type symbol under the default CDFs, in sixteenths of a bit; what the rate term weighs - and (optional)
+ * *lambda = the lambda the chunk's decisions used, 0 without the rate term.  n_units (av1mi_lr_rd_units) and the unit order are
+ * av1mi_lr_fit_result's.  Entries are zero for planes that are not restored and for a chunk without restoration.  The call reads the
+ * choices back from the device.  AV1MI_E_INVALID_ARG if n_frames is not the last chunk's frame count. */
+int av1mi_lr_rd_result(const av1mi_ctx *ctx, uint32_t n_frames, int8_t *choice, uint32_t *bits16, uint64_t *lambda);
+uint32_t av1mi_lr_rd_units(const av1mi_ctx *ctx);
 
 /* ---- symbolize's tile order of the last chunk ------------------------------------------------
  * An all-key-frame chunk with one-superblock tiles, adaptive CDFs and block_log2 <= 5 is symbolized heavy tiles first (the

@@ -8,7 +8,10 @@ One JSON line per point, value and unit size: frames/s (best of --steps after --
 milliseconds per frame, bytes per frame, PSNR Y / U / V of the reconstruction, the report's stage times and, with the fit, the
 histogram of the units' choices (off / Wiener / fixed / fitted), of the fitted sets and of the fitted weights at their clamps
 (av1mi_lr_fit_result) and, with the Wiener fit, the units choosing the fitted filter, those of them with a tap at a clamp and with
-different vertical and horizontal taps (av1mi_lr_wiener_fit_result).  It reports what it measures, nothing more."""
+different vertical and horizontal taps (av1mi_lr_wiener_fit_result).  With --rd 0,1,2,3 every row with restoration also runs with the
+rate term of the unit decisions (bits 14 and 15, item 9g) at those lambda scales; every row with restoration then reports the final
+choices - units off / Wiener (fixed or fitted) / fixed self-guided / fitted self-guided - and the units' side information per frame in
+bits, the sum of bits16 / 16 (av1mi_lr_rd_result), and the rate term's rows lambda.  It reports what it measures, nothing more."""
 import argparse
 import json
 import os
@@ -55,6 +58,14 @@ def wfit_hist(units):
             "cv_ne_ch": int((won[:, 2:5] != won[:, 5:8]).any(axis=1).sum())}
 
 
+def rd_hist(choice, bits16, n):
+    """final choices of choice[frame][plane][row][column] over all planes (a plane that is not restored counts as off) and the units'
+    side information per frame in bits"""
+    k = choice.reshape(-1)
+    return {"off": int((k == 0).sum()), "wiener": int((((k >= 1) & (k <= 3)) | (k == 23)).sum()), "fixed": int(((k >= 4) & (k <= 6)).sum()),
+            "fitted": int(((k >= 7) & (k < 23)).sum()), "unit_bits_per_frame": round(float(bits16.sum()) / 16 / n, 1)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=5)
@@ -63,6 +74,7 @@ def main():
     ap.add_argument("--points", default="", help="comma-separated subset of the point names")
     ap.add_argument("--values", default="0,4,fit4,fit4_set9,3,wfit3,wfit4,wfit_fit4")
     ap.add_argument("--unit-shifts", default="0", help="comma-separated lr_unit_shift values: 0 = units of 64 luma samples, 1 = 128, 2 = 256")
+    ap.add_argument("--rd", default="", help="comma-separated lambda scales 0 .. 3: every row with restoration also runs with the rate term at each")
     args = ap.parse_args()
     import torch
     import av1mi
@@ -75,10 +87,11 @@ def main():
         for name, kw in POINTS:
             if want and name not in want:
                 continue
-            for v, shift in ((v, int(s)) for v in args.values.split(",") for s in args.unit_shifts.split(",")):
-                if shift and not VALUES[v]:
-                    continue   # a unit size needs restoration
-                p = av1mi.default_params(w, h, bd, enable_lr=VALUES[v], lr_unit_shift=shift, **kw)
+            rds = [None] + [int(s) for s in args.rd.split(",") if s != ""]
+            for v, shift, rd in ((v, int(s), rd) for v in args.values.split(",") for s in args.unit_shifts.split(",") for rd in rds):
+                if (shift or rd is not None) and not VALUES[v]:
+                    continue   # a unit size and the rate term need restoration
+                p = av1mi.default_params(w, h, bd, enable_lr=VALUES[v], lr_unit_shift=shift, lr_rd=rd, **kw)
                 for _ in range(args.warmup):
                     ctx.encode_chunk(p, clip.data_ptr(), n, on_device=True, copy_out=False)
                 best, rep = None, None
@@ -88,13 +101,17 @@ def main():
                     dt = time.perf_counter() - t0
                     if best is None or dt < best:
                         best, rep = dt, r
-                line = {"point": name, "enable_lr": v, "unit": 64 << shift, "fps": round(n / best, 1), "ms": round(best * 1e3, 2), "ms_per_frame": round(best * 1e3 / n, 3),
+                line = {"point": name, "enable_lr": v, "unit": 64 << shift, "rd": rd, "fps": round(n / best, 1), "ms": round(best * 1e3, 2), "ms_per_frame": round(best * 1e3 / n, 3),
                         "bytes_per_frame": round(rep.bytes / n, 1), "psnr": [round(x, 3) for x in rep.psnr], "sse": [int(x) for x in rep.sse],
                         "ms_recon": round(rep.ms_recon, 3), "ms_entropy": round(rep.ms_entropy, 3)}
                 if VALUES[v] & 0x100:
                     line["fit"] = fit_hist(ctx.lr_fit_result(n)[0])
                 if VALUES[v] & 0x400:
                     line["wiener_fit"] = wfit_hist(ctx.lr_wiener_fit_result(n)[0])
+                if VALUES[v] and args.rd:
+                    choice, bits16, lam = ctx.lr_rd_result(n)
+                    line["lambda"] = lam
+                    line["choices"] = rd_hist(choice, bits16, n)
                 print(json.dumps(line), flush=True)
 
 
