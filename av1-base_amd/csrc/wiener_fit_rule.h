@@ -6,11 +6,15 @@
 //   sample       W = the filter's input (§7.17.6), X its centre, e = src - X; tap k = 0, 1, 2 has the offset o = 3 - k:
 //                Dv_k = W[y-o][x] + W[y+o][x] - 2 X,  Dh_k = W[y][x-o] + W[y][x+o] - 2 X
 //                (the taps sum to 128: the output is X + (sum a_k Dv_k + sum b_k Dh_k) / 128 + a second-order term the rule drops)
-//   unit         27 exact sums, |sum| < 2^36: Hvv[j][k] = sum Dv_j Dv_k (00 01 02 11 12 22), Hhh likewise, Hvh[j][k] = sum Dv_j Dh_k
-//                (row j), Cv[j] = sum Dv_j e, Ch[k] = sum Dh_k e
+//   unit         27 exact sums: Hvv[j][k] = sum Dv_j Dv_k (00 01 02 11 12 22), Hhh likewise, Hvh[j][k] = sum Dv_j Dh_k
+//                (row j), Cv[j] = sum Dv_j e, Ch[k] = sum Dh_k e.  |sum| < 2^40: at 10 bit |D| <= 2 * 1023 < 2^11 and |e| <= 1023, a
+//                product is below 2^22, and the largest unit, of 256, has at most 383 x 391 = 149753 < 2^17.2 samples: below 2^39.2
+//                (units of 64: at most 95 x 103 samples, below 2^35.3; the edge matrix of tests/lr_edge_cases.py reaches 2^37.06)
 //   solve_idx    over a subset of the taps: m = the largest |H[i][j]|, |R[i]| of the subset, s = max(0, bitlength(m) - 17), every
 //                entry >> s (arithmetic), Cramer's rule; absent if det <= 0, else x_q = rdiv(128 d_q, det)
-//                (six products of three 17-bit entries, times 128: below 2^62)
+//                (after the shift |entry| <= 2^17, a product of three is at most 2^51, a determinant's six at most 6 * 2^51 < 2^53.6,
+//                times 128: below 2^60.6, so below 2^62.  Before the shift the refit's and the second stage's sums of H t / Hvh cv
+//                hold at most three terms of 2^39.2 * 46: below 2^46.4)
 //   solve        x over the taps first .. 2 (first = 1 for chroma: tap 0 is 0 and not coded); t_i = clamp(x_i, Min_i, Max_i); if the
 //                clamp acted on some taps but not on all, the free ones are refitted once with the clamped ones held:
 //                R2_i = R_i - rdiv(sum_{j clamped} H[i][j] t_j, 128), y = solve_idx(H, R2, free), t_i = clamp(y_i) if y is present

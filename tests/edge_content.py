@@ -251,6 +251,22 @@ def with_gpu_only_tools(c):
 GPU_ONLY_CASES = [with_gpu_only_tools(c) for c in CASES if c["name"].startswith(("geom_", "c_"))]
 assert len({c["name"] for c in CASES + GPU_ONLY_CASES}) == len(CASES) + len(GPU_ONLY_CASES)
 
+# the encoder-side decisions together (no oracle for the combination): the AQ map, the deblocking level search, the CDEF search with four
+# pairs, and restoration on all planes in units of 256 with both fits and the rate term (include/av1mi.h: AV1MI_LR_RD(0) = 0xC000) -
+# every geometry case, and the moving content cases at the smallest and the largest leaf; a base case's own values of these give way
+DECISION_TOOLS = dict(aq_strength=4, deblock=2, cdef_search=3, enable_lr=0x2504 | 0xC000)
+
+
+def with_decision_tools(c):
+    c = dict(c, name=c["name"] + "_decisions", params=dict(c["params"], **DECISION_TOOLS))
+    c["params"].pop("enable_cdef", None)
+    return c
+
+
+DECISION_CASES = [with_decision_tools(c) for c in CASES
+                  if c["name"].startswith("geom_") or (c["name"].startswith("c_") and c["name"].endswith("_p") and c["params"]["block_log2"] in (3, 6))]
+assert len({c["name"] for c in CASES + GPU_ONLY_CASES + DECISION_CASES}) == len(CASES) + len(GPU_ONLY_CASES) + len(DECISION_CASES)
+
 
 # ------------------------------------------------------------------ a minimal sequence header reader (spec 5.5)
 def color_config(seq_obu):

@@ -1,7 +1,8 @@
 """GPU edge tests: tiny and thin frames, extreme quantisers and strengths, full-range patterned content (tests/edge_content.py), each
 checked three ways - (a) bitstream, reconstruction and the reported SSE equal the oracle's, (b) dav1d decodes the GPU's stream to the
 GPU's reconstruction, (c) with the GPU-only tools (cdef_search 4, enable_lr 4), which have no oracle: dav1d decodes the stream to the
-reconstruction and two runs give the same bytes.  Without libavif the dav1d checks are replaced by the committed edge fixtures."""
+reconstruction and two runs give the same bytes, (d) the same for the encoder-side decisions together (edge_content.DECISION_TOOLS).
+Without libavif the dav1d checks are replaced by the committed edge fixtures."""
 import hashlib
 import json
 import os
@@ -75,6 +76,18 @@ def test_edge_case_equals_oracle_and_decodes(av1mi, ctx, oracle, case):
 
 @pytest.mark.parametrize("case", E.GPU_ONLY_CASES, ids=[c["name"] for c in E.GPU_ONLY_CASES])
 def test_gpu_only_tools_decode_and_repeat(av1mi, ctx, oracle, case):
+    frames = E.source(oracle, case)
+    tus, recs, rep = encode(av1mi, ctx, case, frames)
+    tus2, recs2, rep2 = encode(av1mi, ctx, case, frames)
+    assert tus == tus2 and [int(x) for x in rep.sse] == [int(x) for x in rep2.sse]
+    assert all(np.array_equal(a[pl], b[pl]) for a, b in zip(recs, recs2) for pl in range(3))
+    check_dav1d(case, tus, recs)
+
+
+@pytest.mark.parametrize("case", E.DECISION_CASES, ids=[c["name"] for c in E.DECISION_CASES])
+def test_decision_tools_decode_and_repeat(av1mi, ctx, oracle, case):
+    """the AQ map, the deblocking level search, the CDEF search and restoration with both fits, the rate term and units of 256 together:
+    the only check of the syntax of their combination at tiny frames (each decision has its own restatement elsewhere)"""
     frames = E.source(oracle, case)
     tus, recs, rep = encode(av1mi, ctx, case, frames)
     tus2, recs2, rep2 = encode(av1mi, ctx, case, frames)
