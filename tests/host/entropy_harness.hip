@@ -1,5 +1,5 @@
 // Launch harness of the entropy back end for tests/test_entropy_kernels.py: the range coder's two forms and the tile order
-// (entropy_kernel.hip), the frame / chunk layout and the tile packing (cdef_pack_kernels.hip), each driven with buffers the
+// (entropy_kernel.hip), the frame / chunk layout and the tile packing (pack_kernels.hip), each driven with buffers the
 // test fills itself, so that every path can be checked against an exact reference.  Test infrastructure only.
 //
 // The kernels sit in anonymous namespaces, so only a translation unit that includes their source can launch them.  This file is
@@ -15,7 +15,7 @@
 #ifndef EH_PACK
 #include "../../av1-base_amd/csrc/entropy_kernel.hip"
 #else
-#include "../../av1-base_amd/csrc/cdef_pack_kernels.hip"
+#include "../../av1-base_amd/csrc/pack_kernels.hip"
 #endif
 
 namespace {
