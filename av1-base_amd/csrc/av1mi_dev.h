@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "lr_geometry.h"
+#include "me_rule.h"
 #include "tile_weight_rule.h"
 #include "wiener_fit_rule.h"   // and lr_fit_rule.h: the counts that size the fits' buffers below
 #ifdef __HIPCC__
@@ -173,18 +174,7 @@ AV1MI_HD inline int av1mi_leaf_bsl_at(int width, int height, int min_bs_log2, in
   return 0;
 }
 
-// ---- motion search keys (me_kernel.hip -> recon_kernel.hip): per leaf a 64-bit key, the minimum over its candidates of
-//   (centre code << 40) | (cost << 16) | candidate index,   cost = SAD + n (|dx| + |dy|) < 2^24,   index = (dy - Cy + R) (2 R + 1) + (dx - Cx + R)
-// centre code = (Cy / 8 & 0xFFF) << 12 | (Cx / 8 & 0xFFF): the centre (Cx, Cy) of the superblock's search in units of 8 luma samples, 12-bit two's
-// complement - zero without the quarter-resolution pre-search (av1mi_params.me_presearch), the same for every candidate of a leaf, so the
-// minimum is taken over (cost, index) as before.
-AV1MI_HD inline int av1mi_sext12(uint32_t v) { return (int)((v & 0xFFFu) ^ 0x800u) - 0x800; }
-AV1MI_HD inline void av1mi_me_key_decode(unsigned long long key, int R, int *dy, int *dx, int *cost) {
-  const int nc = 2 * R + 1, idx = (int)(key & 0xFFFF);
-  *dy = idx / nc - R + 8 * av1mi_sext12((uint32_t)(key >> 52));
-  *dx = idx % nc - R + 8 * av1mi_sext12((uint32_t)(key >> 40));
-  *cost = (int)((key >> 16) & 0xFFFFFF);
-}
+// ---- motion search keys (me_kernel.hip -> recon_kernel.hip): me_rule.h has the layouts, av1mi_me_key_decode and the centre code
 
 // frame f of a chunk is a key frame iff f % keyint == 0
 AV1MI_HD inline int av1mi_frame_is_inter(const Av1miDevParams &P, int f) { return P.keyint > 1 && (f % P.keyint) != 0; }

@@ -5,8 +5,9 @@
 // (/root/reference/crates/daemon/src/encode/av1an.rs:126-139).  Encoder-side, non-normative; the algorithm is the
 // one DESIGN.md §3.9 defines and oracle/av1o_enc.c (motion_search) restates: for every leaf block of the partition,
 // cost(dx, dy) = SAD(source block, previous SOURCE frame displaced by (dx, dy)) + n * (|dx| + |dy|) over
-// |dx|, |dy| <= R with the displaced block kept within 16 samples of the frame; minimum cost, ties to the first
-// candidate in (dy, dx) raster order.
+// |dx|, |dy| <= R with the displaced block kept within reach of the frame; minimum cost, ties to the first
+// candidate in (dy, dx) raster order.  The rules more than one kernel applies - reach, cost, candidate index, the centre code, the
+// leaf, node and refined keys, the refinement's candidates and cost - are me_rule.h's, which the host tests run too.
 //
 // MI355X mapping: the search is open loop (source against previous source), so it does not sit on the frame-by-frame
 // reconstruction chain of a chunk: the inter frames are searched up front, a launch and an event per frame, on a second
@@ -17,7 +18,7 @@
 // DPP row rotations turn them into the 16 8x8 sub-block SADs of the cell, and the leaf blocks of the
 // cell (one 32x32 - its dx candidates then reduced one per lane - or 16x16 / 8x8 blocks at frame edges or smaller block
 // sizes) sum their sub-blocks from LDS.
-// Each leaf's best candidate of this dy goes into a 64-bit atomicMin on (cost << 16 | candidate index).
+// Each leaf's best candidate of this dy goes into a 64-bit atomicMin on the leaf key (me_rule.h).
 // Algorithmic HBM bytes per frame: source luma read once + reference luma read once = 2*L*b (L luma samples);
 // the (2R+1)-fold re-reads of the reference by the dy waves of a cell are L2 hits.
 #include <hip/hip_runtime.h>
@@ -25,10 +26,38 @@
 #include "av1mi_launch.h"
 #include "av1_tables.h"
 #include "part_inter_rule.h"
+#include <type_traits>
 
 namespace {
 
-__device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
+// ---- device-only pieces the kernels below share.  Minimum over the wave, in every lane (a 64-bit shuffle goes through the LDS pipe) ...
+template <typename T>
+__device__ __forceinline__ T wave_min(T v) {
+  for (int o = 32; o > 0; o >>= 1) { const T t = __shfl_xor(v, o, 64); v = t < v ? t : v; }
+  return v;
+}
+// ... and the wave's sums of a pair, in every lane
+__device__ __forceinline__ void wave_sum2(int &a, int &b) {
+  for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); b += __shfl_xor(b, o, 64); }
+}
+// eight signed 16-bit values <-> one 16-byte word
+__device__ __forceinline__ uint4 pack8(const int *v) {
+  uint4 w;
+  w.x = (uint32_t)(uint16_t)v[0] | ((uint32_t)(uint16_t)v[1] << 16); w.y = (uint32_t)(uint16_t)v[2] | ((uint32_t)(uint16_t)v[3] << 16);
+  w.z = (uint32_t)(uint16_t)v[4] | ((uint32_t)(uint16_t)v[5] << 16); w.w = (uint32_t)(uint16_t)v[6] | ((uint32_t)(uint16_t)v[7] << 16);
+  return w;
+}
+__device__ __forceinline__ void unpack8(const uint4 &q, int *v) {
+  const uint32_t d[4] = { q.x, q.y, q.z, q.w };
+#pragma unroll
+  for (int i = 0; i < 4; i++) { v[2 * i] = (int16_t)(d[i] & 0xFFFF); v[2 * i + 1] = (int16_t)(d[i] >> 16); }
+}
+// the centre of a superblock's search (me_rule.h: the centre code; zero without a pre-search): the code and (ccx, ccy) in luma samples
+__device__ __forceinline__ uint32_t sb_centre(const Av1miDevParams &P, const uint32_t *__restrict__ centre, int f, int sb, int &ccx, int &ccy) {
+  const uint32_t ccode = centre ? centre[(size_t)f * P.sb_rows * P.sb_cols + sb] : 0u;
+  av1mi_me_centre_decode(ccode, &ccx, &ccy);
+  return ccode;
+}
 
 // the split mask of frame f's superblock that holds luma position (x, y) (content-driven partition; av1mi_dev.h has the rule)
 __device__ __forceinline__ uint32_t sb_mask(const Av1miDevParams &P, int f, int x, int y) {
@@ -51,7 +80,7 @@ __device__ __forceinline__ bool cell_in_leaf64(const Av1miDevParams &P, int f, i
 // ---- node mode (av1mi_params.partition_search = 2; part_inter_rule.h): the search keeps the best candidate of
 // every NODE of the partition tree, not of every leaf - the partition of the frame is decided from these costs afterwards
 // (inter_partition_kernel).  The (cell, dy) wave has the sixteen 8x8 sub-block SADs of every dx in LDS; lane = dx sums them to the 16 + 4
-// + 1 node SADs of the cell, adds each node's vector penalty and forms 32-bit keys (cost << 11) | index (cost < 2^21 up to 32x32, index
+// + 1 node SADs of the cell, adds each node's vector penalty and forms the 32-bit node keys of me_rule.h (cost < 2^21 up to 32x32, index
 // < 2^11 at R <= 16).  Each of the 21 keys is reduced over the lanes with DPP row rotations as operands of the minimum and one
 // v_readlane per row of 16 lanes that holds candidates (the 64-bit shuffles of the leaf search go through the LDS pipe); lane i keeps
 // minimum i, and one atomic instruction posts the 21 minima to the frame's node tables.  Nodes whose origin is outside the frame - the
@@ -77,42 +106,41 @@ template <int R>
 __device__ __forceinline__ void post_node_costs(const Av1miDevParams &P, int f, int cx, int cy, int dy, int dyi, int ccx, const uint32_t (*sad8)[16],
                                                 uint32_t *__restrict__ acc64, uint32_t *__restrict__ nodes_all) {
   constexpr int NC = 2 * R + 1, ROWS = (NC + 15) / 16;
-  static_assert(NC * NC <= 2048 && ROWS <= 3, "a node key holds an 11-bit candidate index");
+  static_assert(NC * NC <= (1 << AV1MI_ME_NODE_INDEX_BITS) && ROWS <= 3, "a node key holds an 11-bit candidate index");
   const int lane = threadIdx.x, W = P.width, H = P.height;
   const bool live = lane < NC;
   const int dxi = live ? lane : 0, dx = dxi - R + ccx;
-  const uint32_t pen = (uint32_t)(iabs(dx) + iabs(dy)), idx = (uint32_t)(dyi * NC + dxi);
+  const uint32_t idx = av1mi_me_index(dyi, dxi, R);
   uint32_t s8[16], s16[4];
 #pragma unroll
   for (int i = 0; i < 16; i++) s8[i] = sad8[dxi][i];
 #pragma unroll
   for (int q = 0; q < 4; q++) { const int o = (q >> 1) * 8 + (q & 1) * 2; s16[q] = s8[o] + s8[o + 1] + s8[o + 4] + s8[o + 5]; }
   const uint32_t s32 = s16[0] + s16[1] + s16[2] + s16[3];
-  // the displaced node stays within 16 samples of the frame: per node row (wave-uniform) and per node column (per lane)
-  auto y_ok = [&](int oy, int n) { return cy + oy + dy >= -16 && cy + oy + dy + n <= H + 16; };
-  auto x_ok = [&](int ox, int n) { return live && cx + ox + dx >= -16 && cx + ox + dx + n <= W + 16; };
-  uint32_t res = 0xFFFFFFFFu;   // lane i: minimum i - 0 .. 15 the 8x8 nodes (raster), 16 .. 19 the 16x16 nodes (raster), 20 the 32x32 node
+  // the displaced node stays within reach of the frame: per node row (wave-uniform) and per node column (per lane)
+  auto key_of = [&](uint32_t sad, int ox, int oy, int n) {
+    const bool ok = live && av1mi_me_reach(cx + ox, dx, n, W) && av1mi_me_reach(cy + oy, dy, n, H);
+    return ok ? av1mi_me_node_key(av1mi_me_cost(sad, n, dx, dy), idx) : AV1MI_ME_NODE_NONE;
+  };
+  uint32_t res = AV1MI_ME_NODE_NONE;   // lane i: minimum i - 0 .. 15 the 8x8 nodes (raster), 16 .. 19 the 16x16 nodes (raster), 20 the 32x32 node
 #pragma unroll
   for (int i = 0; i < 16; i++) {
-    const uint32_t key = x_ok((i & 3) * 8, 8) && y_ok((i >> 2) * 8, 8) ? ((s8[i] + 8u * pen) << 11) | idx : 0xFFFFFFFFu;
-    const uint32_t m = wave_min_rows<ROWS>(key);
+    const uint32_t m = wave_min_rows<ROWS>(key_of(s8[i], (i & 3) * 8, (i >> 2) * 8, 8));
     res = lane == i ? m : res;
   }
 #pragma unroll
   for (int q = 0; q < 4; q++) {
-    const uint32_t key = x_ok((q & 1) * 16, 16) && y_ok((q >> 1) * 16, 16) ? ((s16[q] + 16u * pen) << 11) | idx : 0xFFFFFFFFu;
-    const uint32_t m = wave_min_rows<ROWS>(key);
+    const uint32_t m = wave_min_rows<ROWS>(key_of(s16[q], (q & 1) * 16, (q >> 1) * 16, 16));
     res = lane == 16 + q ? m : res;
   }
   {
-    const uint32_t key = x_ok(0, 32) && y_ok(0, 32) ? ((s32 + 32u * pen) << 11) | idx : 0xFFFFFFFFu;
-    const uint32_t m = wave_min_rows<ROWS>(key);
+    const uint32_t m = wave_min_rows<ROWS>(key_of(s32, 0, 0, 32));
     res = lane == 20 ? m : res;
   }
   if (lane < 21) {
     const int bsl = lane < 16 ? 3 : (lane < 20 ? 4 : 5), j = lane < 16 ? lane : (lane < 20 ? lane - 16 : 0);
     const int x = cx + (lane < 16 ? (j & 3) * 8 : (j & 1) * 16), y = cy + (lane < 16 ? (j >> 2) * 8 : (j >> 1) * 16);
-    if (x < W && y < H && res != 0xFFFFFFFFu)
+    if (x < W && y < H && res != AV1MI_ME_NODE_NONE)
       atomicMin(&nodes_all[(size_t)f * av1mi_pi_frame_nodes(P.b8_rows, P.b8_cols) + av1mi_pi_node_slot(P.b8_rows, P.b8_cols, bsl, x, y)], res);
   }
   // block_log2 = 6: every cell adds its 32x32 sums to its superblock's candidate table (the 64x64 node's cost)
@@ -138,10 +166,8 @@ __global__ void __launch_bounds__(64) motion_search_kernel(Av1miDevParams P, con
   const int cells_x = (P.width + 31) >> 5;
   const int cell = blockIdx.x, dyi = blockIdx.y;
   const int cx = (cell % cells_x) * 32, cy = (cell / cells_x) * 32;
-  // centre of the superblock's search (av1mi_dev.h: motion search keys): whole multiples of 8 luma samples, zero without a pre-search
-  const uint32_t ccode = centre ? centre[((size_t)f * P.sb_rows + (cy >> 6)) * P.sb_cols + (cx >> 6)] : 0u;
-  const int ccx = 8 * av1mi_sext12(ccode), ccy = 8 * av1mi_sext12(ccode >> 12);
-  const unsigned long long ctop = (unsigned long long)ccode << 40;
+  int ccx, ccy;
+  const uint32_t ccode = sb_centre(P, centre, f, (cy >> 6) * P.sb_cols + (cx >> 6), ccx, ccy);
   const int dy = dyi - R + ccy;
   const int lane = threadIdx.x, r = lane >> 1, half = lane & 1;
   const int W = P.width, H = P.height;
@@ -221,20 +247,19 @@ __global__ void __launch_bounds__(64) motion_search_kernel(Av1miDevParams P, con
   // ---- the usual cell: one 32x32 leaf.  Lane = dx candidate: each sums the 16 sub-block SADs of its dx, a wave minimum
   // over (cost, candidate) picks the best of this dy (as one lane looping over the candidates it was a third of the kernel)
   if (leaf_bsl_cell(P, f, cx, cy, 0, 0) == 5) {
-    if (cy + dy >= -16 && cy + dy + 32 <= H + 16) {
-      unsigned long long key = ~0ull;
+    if (av1mi_me_reach(cy, dy, 32, H)) {
+      unsigned long long key = AV1MI_ME_KEY_NONE;
       if (lane < NC) {
         const int dx = lane - R + ccx;
-        if (!(cx + dx < -16 || cx + dx + 32 > W + 16)) {
+        if (av1mi_me_reach(cx, dx, 32, W)) {
           uint32_t sad = 0;
 #pragma unroll
           for (int i = 0; i < 16; i++) sad += sad8[lane][i];
-          const unsigned long long cost = (unsigned long long)sad + (unsigned long long)(32 * (iabs(dx) + iabs(dy)));
-          key = ctop | (cost << 16) | (unsigned long long)(dyi * NC + lane);
+          key = av1mi_me_key(ccode, av1mi_me_cost(sad, 32, dx, dy), av1mi_me_index(dyi, lane, R));
         }
       }
-      for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(key, o, 64); key = t < key ? t : key; }
-      if (lane == 0 && key != ~0ull) atomicMin(&best[(size_t)(cy >> 3) * P.b8_cols + (cx >> 3)], key);
+      key = wave_min(key);
+      if (lane == 0 && key != AV1MI_ME_KEY_NONE) atomicMin(&best[(size_t)(cy >> 3) * P.b8_cols + (cx >> 3)], key);
     }
     return;
   }
@@ -245,47 +270,50 @@ __global__ void __launch_bounds__(64) motion_search_kernel(Av1miDevParams P, con
     if (bsl) {
       const int n = 1 << bsl, n8 = n >> 3;
       const int x = cx + ux * 8, y = cy + uy * 8;
-      if (y + dy >= -16 && y + dy + n <= H + 16) {
-        unsigned long long bk = ~0ull;
+      if (av1mi_me_reach(y, dy, n, H)) {
+        unsigned long long bk = AV1MI_ME_KEY_NONE;
         for (int dxi = 0; dxi < NC; dxi++) {
           const int dx = dxi - R + ccx;
-          if (x + dx < -16 || x + dx + n > W + 16) continue;
+          if (!av1mi_me_reach(x, dx, n, W)) continue;
           uint32_t sad = 0;
           for (int i = 0; i < n8; i++)
             for (int j = 0; j < n8; j++) sad += sad8[dxi][(uy + i) * 4 + ux + j];
-          const unsigned long long cost = (unsigned long long)sad + (unsigned long long)(n * (iabs(dx) + iabs(dy)));
-          const unsigned long long key = ctop | (cost << 16) | (unsigned long long)(dyi * NC + dxi);
+          const unsigned long long key = av1mi_me_key(ccode, av1mi_me_cost(sad, n, dx, dy), av1mi_me_index(dyi, dxi, R));
           bk = key < bk ? key : bk;
         }
-        if (bk != ~0ull) atomicMin(&best[(size_t)((cy >> 3) + uy) * P.b8_cols + (cx >> 3) + ux], bk);
+        if (bk != AV1MI_ME_KEY_NONE) atomicMin(&best[(size_t)((cy >> 3) + uy) * P.b8_cols + (cx >> 3) + ux], bk);
       }
     }
   }
 }
 
-// One wave per superblock that is a 64x64 leaf: cost and minimum over the candidate table the search filled (same rule: cost =
-// SAD + 64 * (|dx| + |dy|), the displaced block within 16 samples of the frame, ties to the first candidate in raster order).
+// The 64x64 block at (x, y): cost and minimum over its candidate table `tab` that the search filled (same rule: cost = SAD + 64 * (|dx| +
+// |dy|), the displaced block within reach of the frame, ties to the first candidate in raster order - the table's position is the
+// candidate index).  The whole wave calls; every lane gets the key, with `code` in the centre's place.
+__device__ __forceinline__ unsigned long long best_of_table64(const uint32_t *__restrict__ tab, int x, int y, int W, int H, int R, int ccx, int ccy, uint32_t code) {
+  const int NC = 2 * R + 1;
+  unsigned long long key = AV1MI_ME_KEY_NONE;
+  for (int c = threadIdx.x; c < NC * NC; c += 64) {
+    const int dy = c / NC - R + ccy, dx = c % NC - R + ccx;
+    if (!av1mi_me_reach(x, dx, 64, W) || !av1mi_me_reach(y, dy, 64, H)) continue;
+    const unsigned long long k = av1mi_me_key(code, av1mi_me_cost(tab[c], 64, dx, dy), (uint32_t)c);
+    key = k < key ? k : key;
+  }
+  return wave_min(key);
+}
+
+// One wave per superblock that is a 64x64 leaf: the leaf's key from its candidate table.
 __global__ void __launch_bounds__(64) me64_reduce_kernel(Av1miDevParams P, const uint32_t *__restrict__ acc64,
                                                         unsigned long long *__restrict__ best_all, int frame0, int R, const uint32_t *__restrict__ centre) {
   const int f = frame0 + blockIdx.y;
   if (!av1mi_frame_is_inter(P, f)) return;
   const int sb = blockIdx.x, x = (sb % P.sb_cols) * 64, y = (sb / P.sb_cols) * 64;
   if (!cell_in_leaf64(P, f, x, y)) return;
-  const int NC = 2 * R + 1, lane = threadIdx.x;
-  const uint32_t ccode = centre ? centre[(size_t)f * P.sb_rows * P.sb_cols + sb] : 0u;
-  const int ccx = 8 * av1mi_sext12(ccode), ccy = 8 * av1mi_sext12(ccode >> 12);
-  const unsigned long long ctop = (unsigned long long)ccode << 40;
-  const uint32_t *tab = acc64 + ((size_t)f * P.sb_rows * P.sb_cols + sb) * NC * NC;
-  unsigned long long key = ~0ull;
-  for (int c = lane; c < NC * NC; c += 64) {
-    const int dy = c / NC - R + ccy, dx = c % NC - R + ccx;
-    if (x + dx < -16 || x + dx + 64 > P.width + 16 || y + dy < -16 || y + dy + 64 > P.height + 16) continue;
-    const unsigned long long cost = (unsigned long long)tab[c] + (unsigned long long)(64 * (iabs(dx) + iabs(dy)));
-    const unsigned long long k = ctop | (cost << 16) | (unsigned long long)c;
-    key = k < key ? k : key;
-  }
-  for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(key, o, 64); key = t < key ? t : key; }
-  if (lane == 0) best_all[(size_t)f * P.b8_rows * P.b8_cols + (size_t)(y >> 3) * P.b8_cols + (x >> 3)] = key;
+  const int NC = 2 * R + 1;
+  int ccx, ccy;
+  const uint32_t ccode = sb_centre(P, centre, f, sb, ccx, ccy);
+  const unsigned long long key = best_of_table64(acc64 + ((size_t)f * P.sb_rows * P.sb_cols + sb) * NC * NC, x, y, P.width, P.height, R, ccx, ccy, ccode);
+  if (threadIdx.x == 0) best_all[(size_t)f * P.b8_rows * P.b8_cols + (size_t)(y >> 3) * P.b8_cols + (x >> 3)] = key;
 }
 
 // inter_partition_kernel (partition_search = 2): one wave per superblock of an inter frame decides the superblock's partition from the
@@ -302,22 +330,11 @@ __global__ void __launch_bounds__(64) inter_partition_kernel(Av1miDevParams P, c
   if (!av1mi_frame_is_inter(P, f)) return;
   const int sb = blockIdx.x, sb_x = (sb % P.sb_cols) * 64, sb_y = (sb / P.sb_cols) * 64;
   const int NC = 2 * R + 1, lane = threadIdx.x, W = P.width, H = P.height;
-  const uint32_t ccode = centre ? centre[(size_t)f * P.sb_rows * P.sb_cols + sb] : 0u;
-  const int ccx = 8 * av1mi_sext12(ccode), ccy = 8 * av1mi_sext12(ccode >> 12);
-  const unsigned long long ctop = (unsigned long long)ccode << 40;
-  // the 64x64 node: cost and minimum over its candidate table
-  unsigned long long key64 = ~0ull;
-  if (acc64) {
-    const uint32_t *tab = acc64 + ((size_t)f * P.sb_rows * P.sb_cols + sb) * NC * NC;
-    for (int c = lane; c < NC * NC; c += 64) {
-      const int dy = c / NC - R + ccy, dx = c % NC - R + ccx;
-      if (sb_x + dx < -16 || sb_x + dx + 64 > W + 16 || sb_y + dy < -16 || sb_y + dy + 64 > H + 16) continue;
-      const unsigned long long cost = (unsigned long long)tab[c] + (unsigned long long)(64 * (iabs(dx) + iabs(dy)));
-      const unsigned long long k = (cost << 16) | (unsigned long long)c;
-      key64 = k < key64 ? k : key64;
-    }
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long t = __shfl_xor(key64, o, 64); key64 = t < key64 ? t : key64; }
-  }
+  int ccx, ccy;
+  const uint32_t ccode = sb_centre(P, centre, f, sb, ccx, ccy);
+  // the 64x64 node: cost and minimum over its candidate table (no centre in this key: a leaf's key gets it below)
+  unsigned long long key64 = AV1MI_ME_KEY_NONE;
+  if (acc64) key64 = best_of_table64(acc64 + ((size_t)f * P.sb_rows * P.sb_cols + sb) * NC * NC, sb_x, sb_y, W, H, R, ccx, ccy, 0u);
   // this lane's nodes, their positions and keys (cost, candidate index); a node outside the frame reads nothing
   const uint32_t *nodes = nodes_all + (size_t)f * av1mi_pi_frame_nodes(P.b8_rows, P.b8_cols);
   const int ia = 21 + lane, ib = lane < 21 ? lane : -1;
@@ -328,13 +345,13 @@ __global__ void __launch_bounds__(64) inter_partition_kernel(Av1miDevParams P, c
   uint32_t cLa = AV1MI_PI_INF, idxa = 0, cLb = AV1MI_PI_INF, idxb = 0;
   if (xa < W && ya < H) {
     const uint32_t k = nodes[av1mi_pi_node_slot(P.b8_rows, P.b8_cols, 3, xa, ya)];
-    if (k != 0xFFFFFFFFu) { cLa = k >> 11; idxa = k & 0x7FFu; }
+    if (k != AV1MI_ME_NODE_NONE) { cLa = av1mi_me_node_cost(k); idxa = av1mi_me_node_index(k); }
   }
   if (ib > 0 && xb < W && yb < H) {
     const uint32_t k = nodes[av1mi_pi_node_slot(P.b8_rows, P.b8_cols, lb, xb, yb)];
-    if (k != 0xFFFFFFFFu) { cLb = k >> 11; idxb = k & 0x7FFu; }
+    if (k != AV1MI_ME_NODE_NONE) { cLb = av1mi_me_node_cost(k); idxb = av1mi_me_node_index(k); }
   }
-  if (ib == 0 && key64 != ~0ull) { cLb = (uint32_t)(key64 >> 16); idxb = (uint32_t)(key64 & 0xFFFF); }
+  if (ib == 0 && key64 != AV1MI_ME_KEY_NONE) { cLb = av1mi_me_key_cost(key64); idxb = av1mi_me_key_index(key64); }
   int sta, stb = AV1MI_PI_OUT;
   sJ[ia] = av1mi_pi_node(W, H, P.min_bs_log2, P.max_bs_log2, P.ac_q, xa, ya, 3, cLa, nullptr, &sta);
   sState[ia] = (uint8_t)sta;
@@ -351,9 +368,9 @@ __global__ void __launch_bounds__(64) inter_partition_kernel(Av1miDevParams P, c
   if (lane == 0) part[(size_t)f * P.sb_rows * P.sb_cols + sb] = (uint32_t)split & 0x1FFFFFu;
   unsigned long long *best = best_all + (size_t)f * P.b8_rows * P.b8_cols;
   if (ra && (sta == AV1MI_PI_LEAF || sta == AV1MI_PI_KEEP))
-    best[(size_t)(ya >> 3) * P.b8_cols + (xa >> 3)] = cLa == AV1MI_PI_INF ? ~0ull : ctop | ((unsigned long long)cLa << 16) | idxa;
+    best[(size_t)(ya >> 3) * P.b8_cols + (xa >> 3)] = cLa == AV1MI_PI_INF ? AV1MI_ME_KEY_NONE : av1mi_me_key(ccode, cLa, idxa);
   if (rb && (stb == AV1MI_PI_LEAF || stb == AV1MI_PI_KEEP))
-    best[(size_t)(yb >> 3) * P.b8_cols + (xb >> 3)] = cLb == AV1MI_PI_INF ? ~0ull : ctop | ((unsigned long long)cLb << 16) | idxb;
+    best[(size_t)(yb >> 3) * P.b8_cols + (xb >> 3)] = cLb == AV1MI_PI_INF ? AV1MI_ME_KEY_NONE : av1mi_me_key(ccode, cLb, idxb);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -363,7 +380,7 @@ __global__ void __launch_bounds__(64) inter_partition_kernel(Av1miDevParams P, c
 // (EIGHTTAP, Round2 by 3 after the horizontal pass, by 11 and a clamp after the vertical one); cost = SATD (sum of the
 // absolute 8x8 Hadamard coefficients of the difference, >> 3) + (n * (|mv.row| + |mv.col|) >> 3), the integer winner
 // re-costed the same way first; a candidate replaces the best only when strictly cheaper, candidates in (row, col)
-// raster order; the displaced block stays within 16 samples of the frame.
+// raster order; the displaced block stays within reach of the frame (me_rule.h: the refinement).
 // One wave per cell of the largest block size (its leaf; the smaller leaves of a cell that straddles the frame edge in
 // turn).  The (n + 8)^2 reference window
 // around the integer winner - every candidate's taps lie inside it - and the source block are staged in LDS once, all
@@ -373,7 +390,7 @@ __global__ void __launch_bounds__(64) inter_partition_kernel(Av1miDevParams P, c
 // The Hadamard transform of 32x32 blocks (and of the quadrants of 64x64 ones) runs on the matrix cores straight from the vertical
 // pass's registers (refine_eval, measured against the butterflies with tools/mfma_satd_ab.hip); the smaller blocks' runs as
 // butterflies (24 additions per 8 values, rows through LDS, then columns).
-// Output: (SAD << 36) | (u16 mv.row << 16) | u16 mv.col per leaf, which is what the recon kernel reads.
+// Output: the refined key of me_rule.h per leaf, which is what the recon kernel reads (av1mi_me_leaf_motion).
 __constant__ int16_t c_subpel_me[2][16][8] = AV1_SUBPEL_FILTERS_INIT;
 
 typedef int v4i_t __attribute__((ext_vector_type(4)));
@@ -455,7 +472,7 @@ __device__ __forceinline__ void refine_eval(const Av1miDevParams &P, int x, int 
     const uint4 *wp = reinterpret_cast<const uint4 *>(win + (iy + r) * WS + 8 * sg);
     const uint4 q0 = wp[0], q1 = wp[1];
     const uint32_t d[8] = { q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w };
-    int a[16];
+    int a[16];   // (unsigned samples, unpacked here: through unpack8's form the kernel needed 7 registers more - DESIGN.md §4.5b)
 #pragma unroll
     for (int i = 0; i < 8; i++) { a[2 * i] = (int)(d[i] & 0xFFFF); a[2 * i + 1] = (int)(d[i] >> 16); }
     int o[8];
@@ -472,10 +489,7 @@ __device__ __forceinline__ void refine_eval(const Av1miDevParams &P, int x, int 
         for (int t = 0; t < 8; t++) sum += fh[t] * a[j + t];
         o[j] = (sum + 4) >> 3; }
     }
-    uint4 w;
-    w.x = (uint32_t)(uint16_t)o[0] | ((uint32_t)(uint16_t)o[1] << 16); w.y = (uint32_t)(uint16_t)o[2] | ((uint32_t)(uint16_t)o[3] << 16);
-    w.z = (uint32_t)(uint16_t)o[4] | ((uint32_t)(uint16_t)o[5] << 16); w.w = (uint32_t)(uint16_t)o[6] | ((uint32_t)(uint16_t)o[7] << 16);
-    *reinterpret_cast<uint4 *>(mid + r * n + 8 * sg) = w;
+    *reinterpret_cast<uint4 *>(mid + r * n + 8 * sg) = pack8(o);
   }
   __syncthreads();
   // vertical pass: lane = column c, rows r0 .. r0 + RPL - 1
@@ -494,7 +508,7 @@ __device__ __forceinline__ void refine_eval(const Av1miDevParams &P, int x, int 
       int v = (sum + 1024) >> 11;
       v = v < 0 ? 0 : (v > maxv ? maxv : v);
       const int d = (int)srcb[(r0 + j) * n + c] - v;
-      sad += iabs(d);
+      sad += av1mi_me_iabs(d);
       if constexpr (LOG2N == 5) dd[j] = d;
       else dif[(r0 + j) * n + c] = (int16_t)d;
     }
@@ -535,8 +549,8 @@ __device__ __forceinline__ void refine_eval(const Av1miDevParams &P, int x, int 
     acc2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(ha, lo, acc2, 0, 0, 0);
     int satd = 0;
 #pragma unroll
-    for (int r = 0; r < 16; r++) satd += iabs(acc2[r]);
-    for (int o = 32; o > 0; o >>= 1) { sad += __shfl_xor(sad, o, 64); satd += __shfl_xor(satd, o, 64); }
+    for (int r = 0; r < 16; r++) satd += av1mi_me_iabs(acc2[r]);
+    wave_sum2(sad, satd);
     __syncthreads();   // `mid` is rewritten by the next candidate's horizontal pass
     sad_out = sad; satd_out = satd;
     return;
@@ -548,14 +562,10 @@ __device__ __forceinline__ void refine_eval(const Av1miDevParams &P, int x, int 
   for (int task = lane; task < HT; task += 64) {
     const int b = task >> 3, i = task & 7;
     int16_t *rowp = dif + ((b / NB) * 8 + i) * n + (b % NB) * 8;
-    const uint4 q = *reinterpret_cast<const uint4 *>(rowp);
-    int v[8] = { (int16_t)(q.x & 0xFFFF), (int16_t)(q.x >> 16), (int16_t)(q.y & 0xFFFF), (int16_t)(q.y >> 16),
-                 (int16_t)(q.z & 0xFFFF), (int16_t)(q.z >> 16), (int16_t)(q.w & 0xFFFF), (int16_t)(q.w >> 16) };
+    int v[8];
+    unpack8(*reinterpret_cast<const uint4 *>(rowp), v);
     hadamard8(v);
-    uint4 w;
-    w.x = (uint32_t)(uint16_t)v[0] | ((uint32_t)(uint16_t)v[1] << 16); w.y = (uint32_t)(uint16_t)v[2] | ((uint32_t)(uint16_t)v[3] << 16);
-    w.z = (uint32_t)(uint16_t)v[4] | ((uint32_t)(uint16_t)v[5] << 16); w.w = (uint32_t)(uint16_t)v[6] | ((uint32_t)(uint16_t)v[7] << 16);
-    *reinterpret_cast<uint4 *>(rowp) = w;
+    *reinterpret_cast<uint4 *>(rowp) = pack8(v);
   }
   __syncthreads();
   int satd = 0;
@@ -567,13 +577,15 @@ __device__ __forceinline__ void refine_eval(const Av1miDevParams &P, int x, int 
     for (int i = 0; i < 8; i++) v[i] = colp[i * n];
     hadamard8(v);
 #pragma unroll
-    for (int i = 0; i < 8; i++) satd += iabs(v[i]);
+    for (int i = 0; i < 8; i++) satd += av1mi_me_iabs(v[i]);
   }
-  for (int o = 32; o > 0; o >>= 1) { sad += __shfl_xor(sad, o, 64); satd += __shfl_xor(satd, o, 64); }
+  wave_sum2(sad, satd);
   __syncthreads();
   sad_out = sad; satd_out = satd;
 }
 
+// The two functions below walk a stage's candidates the same way - me_rule.h's candidate test, vector and reach, then its cost.  (As one
+// function over "tiles per leaf" the decision has to wait for a stage's sums, which the one-tile leaves do not keep: DESIGN.md §4.5b.)
 template <typename PIX, int LOG2N>
 __device__ __forceinline__ void refine_leaf(const Av1miDevParams &P, const PIX *__restrict__ src, const PIX *__restrict__ ref, int x, int y,
                                             int &best_row, int &best_col, int &best_sad, uint16_t *win, int16_t *mid, uint16_t *srcb, int16_t *dif) {
@@ -586,12 +598,12 @@ __device__ __forceinline__ void refine_leaf(const Av1miDevParams &P, const PIX *
   for (int step = 8; step >= 2; step >>= 1) {
     const int base_row = best_row, base_col = best_col;
     for (int k = 0; k < 9; k++) {
-      if ((k == 4) != (step == 8)) continue;
-      const int mr = base_row + (step == 8 ? 0 : (k / 3 - 1) * step), mc = base_col + (step == 8 ? 0 : (k % 3 - 1) * step);
-      if (x * 8 + mc < -128 || (x + n) * 8 + mc > (W + 16) * 8 || y * 8 + mr < -128 || (y + n) * 8 + mr > (H + 16) * 8) continue;
+      if (!av1mi_me_refine_is_cand(step, k)) continue;
+      const int mr = av1mi_me_refine_row(step, k, base_row), mc = av1mi_me_refine_col(step, k, base_col);
+      if (av1mi_me_out_of_reach8(x, mc, n, W) || av1mi_me_out_of_reach8(y, mr, n, H)) continue;
       int sad, satd;
       refine_eval<PIX, LOG2N>(P, x, y, wx, wy, mr, mc, win, mid, srcb, dif, sad, satd);
-      const long cost = (long)(satd >> 3) + (((long)n * (iabs(mr) + iabs(mc))) >> 3);
+      const long cost = av1mi_me_refine_cost(satd, n, mr, mc);
       if (step == 8 || cost < best_cost) { best_cost = cost; best_sad = sad; best_row = mr; best_col = mc; }
     }
   }
@@ -618,9 +630,9 @@ __device__ __forceinline__ void refine_leaf64(const Av1miDevParams &P, const PIX
       refine_stage<PIX, 5>(P, src, ref, qx, qy, wx, wy, win, srcb);
 #pragma unroll
       for (int k = 0; k < 9; k++) {
-        if ((k == 4) != (step == 8)) continue;
-        const int mr = base_row + (step == 8 ? 0 : (k / 3 - 1) * step), mc = base_col + (step == 8 ? 0 : (k % 3 - 1) * step);
-        if (x * 8 + mc < -128 || (x + n) * 8 + mc > (W + 16) * 8 || y * 8 + mr < -128 || (y + n) * 8 + mr > (H + 16) * 8) continue;
+        if (!av1mi_me_refine_is_cand(step, k)) continue;
+        const int mr = av1mi_me_refine_row(step, k, base_row), mc = av1mi_me_refine_col(step, k, base_col);
+        if (av1mi_me_out_of_reach8(x, mc, n, W) || av1mi_me_out_of_reach8(y, mr, n, H)) continue;
         int sad, satd;
         refine_eval<PIX, 5>(P, qx, qy, wx, wy, mr, mc, win, mid, srcb, dif, sad, satd);
         sad_acc[k] += sad; satd_acc[k] += satd;
@@ -628,10 +640,10 @@ __device__ __forceinline__ void refine_leaf64(const Av1miDevParams &P, const PIX
     }
 #pragma unroll
     for (int k = 0; k < 9; k++) {
-      if ((k == 4) != (step == 8)) continue;
-      const int mr = base_row + (step == 8 ? 0 : (k / 3 - 1) * step), mc = base_col + (step == 8 ? 0 : (k % 3 - 1) * step);
-      if (x * 8 + mc < -128 || (x + n) * 8 + mc > (W + 16) * 8 || y * 8 + mr < -128 || (y + n) * 8 + mr > (H + 16) * 8) continue;
-      const long cost = (long)(satd_acc[k] >> 3) + (((long)n * (iabs(mr) + iabs(mc))) >> 3);
+      if (!av1mi_me_refine_is_cand(step, k)) continue;
+      const int mr = av1mi_me_refine_row(step, k, base_row), mc = av1mi_me_refine_col(step, k, base_col);
+      if (av1mi_me_out_of_reach8(x, mc, n, W) || av1mi_me_out_of_reach8(y, mr, n, H)) continue;
+      const long cost = av1mi_me_refine_cost(satd_acc[k], n, mr, mc);
       if (step == 8 || cost < best_cost) { best_cost = cost; best_sad = sad_acc[k]; best_row = mr; best_col = mc; }
     }
   }
@@ -648,7 +660,6 @@ __global__ void __launch_bounds__(64) subpel_refine_kernel(Av1miDevParams P, con
   const int f = frame0 + blockIdx.z;
   if (!av1mi_frame_is_inter(P, f)) return;
   const PIX *src = frames + (size_t)f * P.frame_samples, *ref = src - P.frame_samples;
-  const int NC = 2 * R + 1;
   // this wave's cell of the largest block size: one leaf inside the frame, a few smaller ones where it straddles the edge
   const int u = 1 << (cell_log2 - 3);
   if (cell_log2 == 6 && cell_in_leaf64(P, f, blockIdx.x * 64, blockIdx.y * 64)) {   // this wave's cell is one 64x64 leaf
@@ -658,7 +669,7 @@ __global__ void __launch_bounds__(64) subpel_refine_kernel(Av1miDevParams P, con
     int best_row = idy * 8, best_col = idx_ * 8, best_sad = 0;
     refine_leaf64<PIX>(P, src, ref, blockIdx.x * 64, blockIdx.y * 64, best_row, best_col, best_sad, win, mid, srcb, dif);
     if (threadIdx.x == 0)
-      out_all[slot] = ((unsigned long long)(uint32_t)best_sad << 36) | ((unsigned long long)(uint16_t)(int16_t)best_row << 16) | (uint16_t)(int16_t)best_col;
+      out_all[slot] = av1mi_me_refined_key(best_sad, best_row, best_col);
     return;
   }
   for (int uy = blockIdx.y * u; uy < (int)(blockIdx.y + 1) * u; uy++)
@@ -667,7 +678,7 @@ __global__ void __launch_bounds__(64) subpel_refine_kernel(Av1miDevParams P, con
       const int bsl = leaf_bsl_cell(P, f, (ux >> 2) * 32, (uy >> 2) * 32, ux & 3, uy & 3);
       if (!bsl) continue;
       const size_t slot = (size_t)f * P.b8_rows * P.b8_cols + (size_t)uy * P.b8_cols + ux;
-      const unsigned long long key = in_all[slot];   // the full search's key: (cost << 16) | candidate index
+      const unsigned long long key = in_all[slot];   // the full search's leaf key
       int idy, idx_, icost;
       av1mi_me_key_decode(key, R, &idy, &idx_, &icost);
       int best_row = idy * 8, best_col = idx_ * 8;
@@ -678,7 +689,7 @@ __global__ void __launch_bounds__(64) subpel_refine_kernel(Av1miDevParams P, con
         default: refine_leaf<PIX, 3>(P, src, ref, ux * 8, uy * 8, best_row, best_col, best_sad, win, mid, srcb, dif); break;
       }
       if (threadIdx.x == 0)
-        out_all[slot] = ((unsigned long long)(uint32_t)best_sad << 36) | ((unsigned long long)(uint16_t)(int16_t)best_row << 16) | (uint16_t)(int16_t)best_col;
+        out_all[slot] = av1mi_me_refined_key(best_sad, best_row, best_col);
     }
 }
 
@@ -706,9 +717,9 @@ __global__ void __launch_bounds__(256) quarter_luma_kernel(Av1miDevParams P, con
 // presearch_kernel: one workgroup of two waves per superblock of an inter frame.  The superblock's 16x16 quarter-resolution block and the
 // 48x48 window of the previous frame around it (coordinates clamped to the plane) are staged in LDS; lane = dqx + 16, each wave takes half
 // of the dqy range; a candidate's SAD two samples per instruction (the block's pair is a broadcast read, the window's pair an unaligned
-// 4-byte read), cost = SAD + 16 (|dqx| + |dqy|); a candidate whose centre would push the superblock more than 16 samples out of the frame is
-// skipped; minimum over (cost, raster index).  Writes the centre code of the winner rounded to whole multiples of 8 luma samples
-// (av1mi_dev.h: motion search keys).  (As one wave with one sample per instruction it took as long as a frame's chain step, and the chain
+// 4-byte read), cost = SAD + 16 (|dqx| + |dqy|); a candidate whose centre would push the superblock (its part inside the frame) out of reach of the
+// frame is skipped; minimum over a node key (cost, raster index).  Writes the centre code of the winner rounded to whole multiples of 8
+// luma samples (me_rule.h: the centre code).  (As one wave with one sample per instruction it took as long as a frame's chain step, and the chain
 // waited for it: 1080p IPPP 5.36 -> 4.89 k frames/s.)
 __global__ void __launch_bounds__(128) presearch_kernel(Av1miDevParams P, const uint16_t *__restrict__ quarter, uint32_t *__restrict__ centre, int frame0) {
   __shared__ __attribute__((aligned(16))) uint16_t cur[16][16];
@@ -734,14 +745,14 @@ __global__ void __launch_bounds__(128) presearch_kernel(Av1miDevParams P, const 
     win[r][c] = qp[(size_t)y * qw + x];
   }
   __syncthreads();
-  const int sbw = W - sx < 64 ? W - sx : 64, sbh = H - sy < 64 ? H - sy : 64;
-  uint32_t best = 0xFFFFFFFFu;
+  static_assert(33 * 33 <= (1 << AV1MI_ME_NODE_INDEX_BITS), "a node key holds an 11-bit candidate index");
+  const int sbw = av1mi_me_sb_extent(sx, W), sbh = av1mi_me_sb_extent(sy, H);
+  uint32_t best = AV1MI_ME_NODE_NONE;
   const int dqx = lane - 16;
   // wave 0: dqy -16 .. 0, wave 1: 1 .. 16
   for (int dqy = wave ? 1 : -16; dqy <= (wave ? 16 : 0); dqy++) {
     if (lane > 32) continue;
-    const int ccx = ((dqx + 1) >> 1) * 8, ccy = ((dqy + 1) >> 1) * 8;
-    if (sx + ccx < -16 || sx + ccx + sbw > W + 16 || sy + ccy < -16 || sy + ccy + sbh > H + 16) continue;
+    if (!av1mi_me_reach(sx, av1mi_me_centre_of_quarter(dqx), sbw, W) || !av1mi_me_reach(sy, av1mi_me_centre_of_quarter(dqy), sbh, H)) continue;
     uint32_t sad = 0;
     for (int i = 0; i < 16; i++) {
       const uint32_t *cr = reinterpret_cast<const uint32_t *>(&cur[i][0]);
@@ -749,18 +760,16 @@ __global__ void __launch_bounds__(128) presearch_kernel(Av1miDevParams P, const 
 #pragma unroll
       for (int k = 0; k < 8; k++) sad = __builtin_amdgcn_sad_u16(cr[k], *reinterpret_cast<const u32_any *>(wr + 2 * k), sad);
     }
-    const uint32_t cost = sad + 16u * (uint32_t)(iabs(dqx) + iabs(dqy));
-    const uint32_t key = (cost << 11) | (uint32_t)((dqy + 16) * 33 + lane);
+    const uint32_t key = av1mi_me_node_key(av1mi_me_cost(sad, 16, dqx, dqy), av1mi_me_index(dqy + 16, lane, 16));
     best = key < best ? key : best;
   }
-  for (int o = 32; o > 0; o >>= 1) { const uint32_t t = __shfl_xor(best, o, 64); best = t < best ? t : best; }
+  best = wave_min(best);
   if (lane == 0) wbest[wave] = best;
   __syncthreads();
   if (tid == 0) {
     const uint32_t bb = wbest[0] < wbest[1] ? wbest[0] : wbest[1];
-    const int idx = (int)(bb & 0x7FF), bqy = idx / 33 - 16, bqx = idx % 33 - 16;
-    const int c8y = (bqy + 1) >> 1, c8x = (bqx + 1) >> 1;   // centre / 8
-    centre[(size_t)f * P.sb_rows * P.sb_cols + sb] = ((uint32_t)(c8y & 0xFFF) << 12) | (uint32_t)(c8x & 0xFFF);
+    const int idx = (int)av1mi_me_node_index(bb), bqy = idx / 33 - 16, bqx = idx % 33 - 16;
+    centre[(size_t)f * P.sb_rows * P.sb_cols + sb] = av1mi_me_centre_encode(bqx, bqy);
   }
 }
 
@@ -788,18 +797,25 @@ extern "C" hipError_t av1mi_launch_subpel_refine(const Av1miDevParams *P, const 
   return hipGetLastError();
 }
 
+// The search of `count` frames from frame0, leaf mode or node mode: one instantiation per sample type and range
+template <bool NODES>
+static void launch_search(const Av1miDevParams *P, const void *frames, unsigned long long *best, int me_range, int frame0, int count, uint32_t *acc64,
+                          const uint32_t *centre, uint32_t *nodes, hipStream_t stream) {
+  const int cells = ((P->width + 31) >> 5) * ((P->height + 31) >> 5);
+  const dim3 grid(cells, 2 * me_range + 1, count);
+  const int vec_ok = ((uintptr_t)frames & 15) == 0;  // frames are 16-byte aligned (the frame size in bytes is a multiple of 32)
+  auto typed = [&](auto *luma) {
+    using PIX = std::remove_const_t<std::remove_pointer_t<decltype(luma)>>;
+    if (me_range == 8) hipLaunchKernelGGL((motion_search_kernel<PIX, 8, NODES>), grid, dim3(64), 0, stream, *P, luma, best, frame0, vec_ok, acc64, centre, nodes);
+    else hipLaunchKernelGGL((motion_search_kernel<PIX, 16, NODES>), grid, dim3(64), 0, stream, *P, luma, best, frame0, vec_ok, acc64, centre, nodes);
+  };
+  if (P->bit_depth == 8) typed((const uint8_t *)frames);
+  else typed((const uint16_t *)frames);
+}
+
 extern "C" hipError_t av1mi_launch_motion_search(const Av1miDevParams *P, const void *frames, unsigned long long *best, int me_range,
                                                  int frame0, int count, uint32_t *acc64, const uint32_t *centre, hipStream_t stream) {
-  const int cells = ((P->width + 31) >> 5) * ((P->height + 31) >> 5);
-  dim3 grid(cells, 2 * me_range + 1, count);
-  const int vec_ok = ((uintptr_t)frames & 15) == 0;  // frame size in bytes is a multiple of 32
-  if (P->bit_depth == 8) {
-    if (me_range == 8) hipLaunchKernelGGL((motion_search_kernel<uint8_t, 8>), grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, best, frame0, vec_ok, acc64, centre, (uint32_t *)nullptr);
-    else hipLaunchKernelGGL((motion_search_kernel<uint8_t, 16>), grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, best, frame0, vec_ok, acc64, centre, (uint32_t *)nullptr);
-  } else {
-    if (me_range == 8) hipLaunchKernelGGL((motion_search_kernel<uint16_t, 8>), grid, dim3(64), 0, stream, *P, (const uint16_t *)frames, best, frame0, vec_ok, acc64, centre, (uint32_t *)nullptr);
-    else hipLaunchKernelGGL((motion_search_kernel<uint16_t, 16>), grid, dim3(64), 0, stream, *P, (const uint16_t *)frames, best, frame0, vec_ok, acc64, centre, (uint32_t *)nullptr);
-  }
+  launch_search<false>(P, frames, best, me_range, frame0, count, acc64, centre, nullptr, stream);
   if (P->max_bs_log2 >= 6)
     hipLaunchKernelGGL(me64_reduce_kernel, dim3(P->sb_rows * P->sb_cols, count), dim3(64), 0, stream, *P, acc64, best, frame0, me_range, centre);
   return hipGetLastError();
@@ -809,16 +825,7 @@ extern "C" hipError_t av1mi_launch_motion_search(const Av1miDevParams *P, const 
 // ([frame][superblock]), the leaves' keys into `best`.  nodes: the [frame][level][node] tables, all-ones; acc64 as above.
 extern "C" hipError_t av1mi_launch_inter_partition(const Av1miDevParams *P, const void *frames, unsigned long long *best, int me_range, int frame0, int count,
                                                    uint32_t *acc64, const uint32_t *centre, uint32_t *nodes, uint32_t *part, hipStream_t stream) {
-  const int cells = ((P->width + 31) >> 5) * ((P->height + 31) >> 5);
-  dim3 grid(cells, 2 * me_range + 1, count);
-  const int vec_ok = ((uintptr_t)frames & 15) == 0;
-  if (P->bit_depth == 8) {
-    if (me_range == 8) hipLaunchKernelGGL((motion_search_kernel<uint8_t, 8, true>), grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, best, frame0, vec_ok, acc64, centre, nodes);
-    else hipLaunchKernelGGL((motion_search_kernel<uint8_t, 16, true>), grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, best, frame0, vec_ok, acc64, centre, nodes);
-  } else {
-    if (me_range == 8) hipLaunchKernelGGL((motion_search_kernel<uint16_t, 8, true>), grid, dim3(64), 0, stream, *P, (const uint16_t *)frames, best, frame0, vec_ok, acc64, centre, nodes);
-    else hipLaunchKernelGGL((motion_search_kernel<uint16_t, 16, true>), grid, dim3(64), 0, stream, *P, (const uint16_t *)frames, best, frame0, vec_ok, acc64, centre, nodes);
-  }
+  launch_search<true>(P, frames, best, me_range, frame0, count, acc64, centre, nodes, stream);
   hipLaunchKernelGGL(inter_partition_kernel, dim3(P->sb_rows * P->sb_cols, count), dim3(64), 0, stream, *P, (const uint32_t *)acc64, (const uint32_t *)nodes, part, best,
                      frame0, me_range, centre);
   return hipGetLastError();

@@ -42,7 +42,7 @@ enum { AV1MI_PI_OUT = 0, AV1MI_PI_LEAF = 1, AV1MI_PI_MUST = 2, AV1MI_PI_SPLIT = 
 AV1MI_HD inline uint32_t av1mi_pi_add(uint32_t a, uint32_t b) { return a == AV1MI_PI_INF || b == AV1MI_PI_INF ? AV1MI_PI_INF : a + b; }
 AV1MI_HD inline uint32_t av1mi_pi_penalty(int n, int ac_q) { return ((uint32_t)(n * n) * (uint32_t)(ac_q >> 4)) >> AV1MI_PI_K; }
 
-// The search's node tables (me_kernel.hip, node mode): per frame the 32-bit keys (cost << 11) | index of the 8x8 nodes [b8_rows][b8_cols],
+// The search's node tables (me_kernel.hip, node mode): per frame the 32-bit node keys (me_rule.h) of the 8x8 nodes [b8_rows][b8_cols],
 // then of the 16x16 and of the 32x32 nodes, a grid each that covers the 8x8 one; all-ones where no candidate was valid.
 AV1MI_HD inline int av1mi_pi_level_dim(int b8, int bsl) { return (b8 + (1 << (bsl - 3)) - 1) >> (bsl - 3); }
 AV1MI_HD inline size_t av1mi_pi_level_off(int b8_rows, int b8_cols, int bsl) {

@@ -1566,17 +1566,9 @@ __device__ __forceinline__ int encode_superblock(const SbCtx &cx, const PIX *fra
     InterInfo ii;
     ii.ref = ref_frame; ii.is_inter = 0; ii.mv_row = ii.mv_col = 0; ii.sad_inter = 0;
     if constexpr (INTER) {
-      // motion search result of this leaf: (cost << 16) | candidate index, cost = SAD + n * (|dx| + |dy|)
+      // motion search result of this leaf: the leaf key, or with subpel the refined key (me_rule.h has both layouts and the reader)
       const unsigned long long key = g_ws.key[(by >> 3) * 8 + (bx >> 3)];   // (staged per superblock: recon_sb_kernel)
-      if (P.subpel) {  // refined (me_kernel.hip): (SAD << 36) | (u16 mv.row << 16) | u16 mv.col, 1/8 samples
-        ii.mv_row = (int16_t)(key >> 16); ii.mv_col = (int16_t)key;
-        ii.sad_inter = (int)(key >> 36);
-      } else {
-        int dyv, dxv, cost;
-        av1mi_me_key_decode(key, P.me_range, &dyv, &dxv, &cost);
-        ii.mv_row = dyv * 8; ii.mv_col = dxv * 8;
-        ii.sad_inter = cost - n * ((dxv < 0 ? -dxv : dxv) + (dyv < 0 ? -dyv : dyv));
-      }
+      av1mi_me_leaf_motion(key, P.subpel, P.me_range, n, &ii.mv_row, &ii.mv_col, &ii.sad_inter);
       // the block's inter version is done (recon_inter_pre_kernel): its eobs, in case motion compensation wins
       const uint16_t *pre = g_ws.pre_eob[(by >> 3) * 8 + (bx >> 3)];
       ii.pre_eob[0] = pre[0]; ii.pre_eob[1] = pre[1]; ii.pre_eob[2] = pre[2];
@@ -1818,16 +1810,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AV1MI_R
       const int n = 1 << bsl;
       InterInfo ii;
       ii.ref = ref; ii.is_inter = 1; ii.pre_eob[0] = ii.pre_eob[1] = ii.pre_eob[2] = 0;
-      const unsigned long long key = me_best[(size_t)uy * P.b8_cols + ux];
-      if (P.subpel) {
-        ii.mv_row = (int16_t)(key >> 16); ii.mv_col = (int16_t)key;
-        ii.sad_inter = (int)(key >> 36);
-      } else {
-        int dyv, dxv, cost;
-        av1mi_me_key_decode(key, P.me_range, &dyv, &dxv, &cost);
-        ii.mv_row = dyv * 8; ii.mv_col = dxv * 8;
-        ii.sad_inter = cost - n * ((dxv < 0 ? -dxv : dxv) + (dyv < 0 ? -dyv : dyv));
-      }
+      const unsigned long long key = me_best[(size_t)uy * P.b8_cols + ux];   // leaf key or refined key (me_rule.h)
+      av1mi_me_leaf_motion(key, P.subpel, P.me_range, n, &ii.mv_row, &ii.mv_col, &ii.sad_inter);
       const int sb = (cx.sb_y >> 6) * P.sb_cols + (cx.sb_x >> 6);
       int16_t *sb_levels = levels + (size_t)sb * AV1MI_SB_LEVELS;
       int16_t *lv_y = sb_levels + av1mi_levels_off(0, bx, by);

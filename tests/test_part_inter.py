@@ -30,17 +30,12 @@ def centres_of(keys_f, sbr, sbc):
     return out
 
 
-@pytest.mark.parametrize("case", PR.CASES, ids=[c["name"] for c in PR.CASES])
-def test_masks_and_leaf_keys_equal_the_reference(av1mi, ctx, case):
-    frames = PR.make_frames(case)
-    n, w, h = len(frames), case["w"], case["h"]
-    _, _, _, (masks1, _) = encode(av1mi, ctx, case, frames, 1)
-    _, _, _, (masks2, keys2) = encode(av1mi, ctx, case, frames, 2)
-    assert np.array_equal(masks2[0], masks1[0])   # the key frame keeps the source rule
+def assert_inter_frames_equal_the_reference(case, frames, masks2, keys2):
+    """masks and leaf keys of every inter frame against part_inter_ref.reference_frame, the centres taken from the keys"""
     p = case["params"]
     sbr, sbc = masks2.shape[1:]
     acq = PR.case_ac_q(case)
-    for t in range(1, n):
+    for t in range(1, len(frames)):
         cen = centres_of(keys2[t], sbr, sbc)
         if not p.get("me_presearch"):
             assert not cen.any()
@@ -50,6 +45,27 @@ def test_masks_and_leaf_keys_equal_the_reference(av1mi, ctx, case):
         # every leaf's key, centre code included: all leaves of a superblock carry the superblock's code
         bad = [(u, hex(int(keys2[t][u])), hex(k)) for u, k in want_keys.items() if int(keys2[t][u]) != k]
         assert not bad, (t, bad[:8])
+
+
+@pytest.mark.parametrize("case", PR.CASES, ids=[c["name"] for c in PR.CASES])
+def test_masks_and_leaf_keys_equal_the_reference(av1mi, ctx, case):
+    frames = PR.make_frames(case)
+    _, _, _, (masks1, _) = encode(av1mi, ctx, case, frames, 1)
+    _, _, _, (masks2, keys2) = encode(av1mi, ctx, case, frames, 2)
+    assert np.array_equal(masks2[0], masks1[0])   # the key frame keeps the source rule
+    assert_inter_frames_equal_the_reference(case, frames, masks2, keys2)
+
+
+@pytest.mark.parametrize("me_range", [8, 16])
+@pytest.mark.parametrize("bd", [8, 10])
+def test_every_instantiation_of_the_node_search_equals_the_reference(av1mi, ctx, bd, me_range):
+    """the node-mode search is built per sample type and range; the cases above reach (8-bit, 8) and (10-bit, 16).  The 72x56 case - two
+    superblocks, four frames - at every combination; what its content ties on is the content test's matter, not this one's"""
+    base = next(c for c in PR.CASES if c["name"] == "72x56")
+    case = dict(base, bd=bd, params=dict(base["params"], me_range=me_range))
+    frames = PR.make_frames(case)
+    _, _, _, (masks2, keys2) = encode(av1mi, ctx, case, frames, 2)
+    assert_inter_frames_equal_the_reference(case, frames, masks2, keys2)
 
 
 @pytest.mark.parametrize("bs", [5, 6])

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Partition of inter frames A/B: 1080p x 60, 10-bit, IPPP (keyint 240), one chunk, the clip in HBM, coded with
-fixed 32x32 and fixed 64x64 leaves, partition_search = 1 with leaves 3..6 and partition_search = 2 with leaves 3..6 and 4..6 - on bench.py's
+fixed 32x32 and fixed 64x64 leaves, partition_search = 1 with leaves 3..6 and partition_search = 2 with leaves 3..6 and 4..6, and three points
+with the sub-sample refinement and the pre-search (so that a run launches every kernel of me_kernel.hip) - on bench.py's
 synthclip and on the same clip with, in every 128x128 region, a 48x48 patch that moves by (3, -2) per frame over a background that pans
 by (1, 0).  One JSON line per clip and mode: frames/s (best of --steps after --warmup), bytes per frame, PSNR Y / U / V, the report's
 chain time (source ready -> last reconstruction: ms_recon) and entropy time, and the histogram of the inter frames' leaf sizes.  With
@@ -24,6 +25,11 @@ MODES = [
     ("ps1_3..6", dict(block_log2=6, partition_search=1, min_block_log2=3)),
     ("ps2_3..6", dict(block_log2=6, partition_search=2, min_block_log2=3)),
     ("ps2_4..6", dict(block_log2=6, partition_search=2, min_block_log2=4)),
+    # the search's other kernels: the refinement, the pre-search (bench.py's cfg3_1080p_ippp_presearch_partition), and
+    # node mode with both at the wider range
+    ("fixed32_subpel", dict(block_log2=5, subpel=1)),
+    ("ps1_3..6_pre", dict(block_log2=6, partition_search=1, min_block_log2=3, me_presearch=1)),
+    ("ps2_3..6_pre_r16_subpel", dict(block_log2=6, partition_search=2, min_block_log2=3, me_presearch=1, me_range=16, subpel=1)),
 ]
 
 
