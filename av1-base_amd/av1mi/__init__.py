@@ -37,7 +37,7 @@ E_INVALID_ARG, E_NO_DEVICE, E_HIP, E_OOM, E_OVERFLOW, E_FORMAT, E_UNSUPPORTED = 
 # every symbol include/av1mi.h declares
 ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", "av1mi_last_error", "av1mi_encode_chunk",
                "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units", "av1mi_sym_order_result", "av1mi_sym_order_tiles", "av1mi_inter_partition_result", "av1mi_inter_partition_units",
-               "av1mi_lr_rd_result", "av1mi_lr_rd_units"]
+               "av1mi_lr_rd_result", "av1mi_lr_rd_units", "av1mi_temporal_filter"]
 
 
 class Params(C.Structure):
@@ -114,6 +114,7 @@ _lib.av1mi_struct_sizes.argtypes = [C.POINTER(C.c_uint32), C.c_uint32]
 _lib.av1mi_struct_sizes.restype = C.c_uint32
 ABI_VERSION = 8   # include/av1mi.h: AV1MI_ABI_VERSION this mirror was written against
 _lib.av1mi_aq_qindex.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8)]
+_lib.av1mi_temporal_filter.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_uint32)]
 _lib.av1mi_lf_search_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
 _lib.av1mi_lr_fit_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint64)]
 _lib.av1mi_lr_fit_units.argtypes = [C.c_void_p]
@@ -180,6 +181,30 @@ def aq_strength_of(v):
     return (v >> 8) & 7
 
 
+TF_MAX_FRAMES = 7
+TF_MAX_STRENGTH = 7
+
+
+def me_tf(presearch, frames, strength):
+    """include/av1mi.h: AV1MI_ME_TF - the me_presearch field with the temporal filter's frames in bits 8-10 and strength in bits 12-14"""
+    return (presearch & 1) | ((frames & 7) << 8) | ((strength & 7) << 12)
+
+
+def me_presearch_of(v):
+    """include/av1mi.h: AV1MI_ME_PRESEARCH"""
+    return v & 1
+
+
+def tf_frames_of(v):
+    """include/av1mi.h: AV1MI_TF_FRAMES"""
+    return (v >> 8) & 7
+
+
+def tf_strength_of(v):
+    """include/av1mi.h: AV1MI_TF_STRENGTH"""
+    return (v >> 12) & 7
+
+
 def lr_fit_field(lr, sets=0):
     """include/av1mi.h: AV1MI_LR_FIT - the enable_lr field (2 or 4) with the self-guided fit over the parameter sets of the mask (0: all 16)"""
     return (lr & 0xFF) | 0x100 | ((sets & 0xFFFF) << 16)
@@ -212,13 +237,17 @@ def lr_unit_grid(width, height, shift=0):
     return max((height + u // 2) // u, 1), max((width + u // 2) // u, 1)
 
 
-def default_params(width, height, bit_depth=8, aq_strength=None, lr_fit=None, lr_wiener_fit=False, lr_unit_shift=0, lr_rd=None, **kw):
+def default_params(width, height, bit_depth=8, aq_strength=None, lr_fit=None, lr_wiener_fit=False, lr_unit_shift=0, lr_rd=None, tf_frames=None,
+                   tf_strength=None, **kw):
     """aq_strength: packed into cq_level beside the CQ level (cq_aq); lr_fit: True or a mask of parameter sets, packed into enable_lr
     (lr_fit_field); lr_wiener_fit: True sets enable_lr's bit 10 (LR_WIENER_FIT); lr_unit_shift: 1 / 2 sets enable_lr's bits 12-13
-    (LR_UNIT_128 / LR_UNIT_256); lr_rd: a scale s = 0 .. 3 sets the rate term of the unit decisions (lr_rd_field); every other keyword
-    sets the structure field of its name"""
+    (LR_UNIT_128 / LR_UNIT_256); lr_rd: a scale s = 0 .. 3 sets the rate term of the unit decisions (lr_rd_field); tf_frames, tf_strength:
+    the key frames' temporal filter, packed into me_presearch beside the pre-search's switch (me_tf); every other keyword sets the
+    structure field of its name"""
     p = Params()
     _lib.av1mi_default_params(C.byref(p), width, height, bit_depth)
+    if tf_frames is not None or tf_strength is not None:
+        kw["me_presearch"] = me_tf(kw.get("me_presearch", p.me_presearch), int(tf_frames or 0), int(tf_strength or 0))
     if lr_fit is not None and lr_fit is not False:
         kw["enable_lr"] = lr_fit_field(kw.get("enable_lr", p.enable_lr), 0 if lr_fit is True else int(lr_fit))
     if lr_wiener_fit:
@@ -350,6 +379,33 @@ class Context:
         rc = _lib.av1mi_aq_qindex(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0, out.ctypes.data_as(C.POINTER(C.c_uint8)))
         _raise_for(rc, self.last_error())
         return out
+
+    def temporal_filter(self, params, frames, n_frames, on_device=False, out_ptr=None, want_mv=True):
+        """The key frames' temporal filter alone (include/av1mi.h: av1mi_temporal_filter).  Host frames (bytes-like / numpy): returns
+        (the chunk with its key frames filtered, as a numpy uint8 array of the input's bytes, mv).  on_device=True: `frames` and the
+        optional `out_ptr` are device pointers; returns (None, mv).  mv: numpy uint32 [key frame][tf_frames][16x16 block] of the coded
+        size, 0xFFFFFFFF where a follower does not exist; None with want_mv=False or the filter off."""
+        import numpy as np
+        bps = 2 if params.bit_depth > 8 else 1
+        nbytes = params.width * params.height * 3 // 2 * bps * n_frames
+        n_tf, keyint = tf_frames_of(params.me_presearch), max(int(params.keyint), 1)
+        cw, ch = (params.width + 7) & ~7, (params.height + 7) & ~7
+        mv = np.zeros(((n_frames + keyint - 1) // keyint, n_tf, ((cw + 15) // 16) * ((ch + 15) // 16)), dtype=np.uint32) if want_mv and n_tf else None
+        out = None
+        if on_device:
+            fptr = C.c_void_p(int(frames))
+            optr = C.c_void_p(int(out_ptr)) if out_ptr is not None else None
+        else:
+            arr = np.ascontiguousarray(np.frombuffer(frames, dtype=np.uint8) if not isinstance(frames, np.ndarray) else frames)
+            if arr.nbytes != nbytes:
+                raise ValueError("frames: expected %d bytes, got %d" % (nbytes, arr.nbytes))
+            fptr = arr.ctypes.data_as(C.c_void_p)
+            out = np.empty(nbytes, dtype=np.uint8)
+            optr = out.ctypes.data_as(C.c_void_p)
+        rc = _lib.av1mi_temporal_filter(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0, optr,
+                                        mv.ctypes.data_as(C.POINTER(C.c_uint32)) if mv is not None else None)
+        _raise_for(rc, self.last_error())
+        return out, mv
 
     def lf_search_result(self, n_frames):
         """The deblocking levels of the last encoded chunk and the level search's error table (include/av1mi.h:

@@ -32,6 +32,7 @@
 #include "deblock_pieces.h"
 #include "aq_rule.h"
 #include "part_inter_rule.h"
+#include "tf_rule.h"
 
 namespace {
 
@@ -87,6 +88,7 @@ struct Resolved {
   int lr_wfit;                        // enable_lr bit 10: the Wiener fit (p.enable_lr holds the type)
   int lr_unit_shift;                  // enable_lr bits 12-13: luma restoration units of 64 << lr_unit_shift samples (0 .. 2)
   uint32_t lr_lambda;                 // enable_lr bits 14 and 15: the rate term's lambda (lr_rate_rule.h), 0 = the decisions go by the error alone
+  int tf_frames, tf_strength;         // me_presearch bits 8-10 and 12-14: the key frames' temporal filter (tf_rule.h), 0 followers = off (p.me_presearch then holds bit 0 alone)
 };
 
 // aom's quantizer_to_qindex[] (CQ level -> base_q_idx); 30 -> 120
@@ -153,7 +155,10 @@ int resolve(const av1mi_params *in, Resolved *r) {
     p.enable_lr = low;
   }
   if (p.subpel > 1 || p.enable_lr > 4 || p.color_range > 1 || p.intra_angle_delta > 1 || p.intra_edge_filter > 1 || p.cfl > 1 || p.tx_search > 1) return AV1MI_E_INVALID_ARG;
-  if (p.partition_search > 2 || p.me_presearch > 1) return AV1MI_E_INVALID_ARG;
+  if (p.partition_search > 2 || !av1mi_tf_field_ok(p.me_presearch)) return AV1MI_E_INVALID_ARG;
+  // me_presearch bits 8-10 and 12-14 (AV1MI_ME_TF): the temporal filter's followers and strength; bit 0 stays as the pre-search's switch
+  r->tf_frames = av1mi_tf_field_frames(p.me_presearch); r->tf_strength = av1mi_tf_field_strength(p.me_presearch);
+  p.me_presearch = (uint32_t)av1mi_tf_field_presearch(p.me_presearch);
   // enable_lr 3 / 4 = 1 / 2 on all three planes: the frames' restoration type plus the chroma flag
   r->lr_chroma = p.enable_lr >= 3;
   if (r->lr_chroma) p.enable_lr -= 2;
@@ -500,6 +505,7 @@ struct Workspace {
   uint32_t *d_nodes = nullptr;             // partition_search = 2: the node-mode search's [frame][level][node] keys (part_inter_rule.h)
   uint16_t *d_aq_act = nullptr;            // adaptive quantisation: E per [frame][superblock] (aq_activity_kernel)
   uint8_t *d_aq_map = nullptr;             // ... the quantiser index per [frame][superblock] (aq_map_kernel)
+  uint32_t *d_tf_mv = nullptr;             // temporal filter: the search's keys per [key frame][follower][16x16 block] (tf_kernel.hip)
   Av1miQmEntry *d_qm = nullptr;        // quantiser-matrix steps (Av1miDevParams::qm_tab), one slice per quantiser slot, valid for qm_key = (slices, level, qidx, bit depth)
   std::vector<Av1miQmEntry> h_qm; int qm_key = -1;
   uint8_t *d_lrc = nullptr;            // per restoration unit: 0 = off, k = candidate k-1
@@ -526,7 +532,7 @@ struct Workspace {
   int cdf_bs_log2 = -1;                // ... and the leaf size its compact image behind the blob was made for
   int params_on_device = 0;            // d_params holds the first so many blocks of h_params (1, or AV1MI_AQ_SLOTS with adaptive quantisation)
   Av1miChunkRecord *h_record = nullptr; unsigned long long *h_sse = nullptr;   // d_record and d_sse land here
-  size_t out_cap = 0, me64_bytes = 0, nodes_bytes = 0, h_out_cap = 0;   // bytes of d_out, d_me64, d_nodes, h_out
+  size_t out_cap = 0, me64_bytes = 0, nodes_bytes = 0, h_out_cap = 0, tf_mv_bytes = 0;   // bytes of d_out, d_me64, d_nodes, h_out, d_tf_mv
   std::vector<std::pair<void *, bool>> owned;   // every buffer above: (address, page-locked host memory)
 };
 
@@ -612,6 +618,13 @@ size_t fit_chunk_units(const Resolved &r, size_t n_frames) {
   return n_frames * 3 * (size_t)av1mi_lr_count((int)r.p.height, r.lr_unit_shift) * (size_t)av1mi_lr_count((int)r.p.width, r.lr_unit_shift);
 }
 
+// the temporal filter's keys of a chunk: [key frame][follower 1 .. tf_frames][16x16 block of the coded size]
+size_t tf_mv_entries(const Resolved &r, size_t n_frames) {
+  return (size_t)av1mi_tf_key_frames((int)r.p.keyint, (int)n_frames) * (size_t)r.tf_frames * (size_t)av1mi_tf_blocks(r.cw) * (size_t)av1mi_tf_blocks(r.ch);
+}
+// whether the filter changes any frame of the chunk: some key frame has a follower (its first key frame then has)
+bool tf_runs(const Resolved &r, size_t n_frames) { return av1mi_tf_followers(r.tf_frames, (int)r.p.keyint, (int)n_frames, 0) > 0; }
+
 int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   const av1mi_params &p = r.p;
   Workspace &w = c->ws;
@@ -675,6 +688,10 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   if (p.partition_search == 2 && p.keyint > 1) {   // node tables of the inter frames' partition decision, on first use
     const size_t need = nf * av1mi_pi_frame_nodes(r.ch / 8, r.cw / 8) * sizeof(uint32_t);
     if (w.nodes_bytes < need) { w.nodes_bytes = 0; HIPCHK(c, ws_alloc(w, w.d_nodes, need)); w.nodes_bytes = need; }
+  }
+  if (r.tf_frames) {   // the temporal filter's keys, on first use (and when a chunk has more key frames or followers than any before)
+    const size_t need = tf_mv_entries(r, n_frames) * sizeof(uint32_t);
+    if (w.tf_mv_bytes < need) { w.tf_mv_bytes = 0; HIPCHK(c, ws_alloc(w, w.d_tf_mv, need)); w.tf_mv_bytes = need; }
   }
   if (r.aq && !w.d_aq_map) {
     HIPCHK(c, ws_alloc(w, w.d_aq_act, nf * nsb * sizeof(uint16_t)));
@@ -1091,6 +1108,50 @@ int av1mi_aq_qindex(av1mi_ctx *c, const av1mi_params *params, const void *frames
   return AV1MI_OK;
 }
 
+// The temporal filter alone: the launch the encoder runs on a chunk's source (av1mi_launch_temporal_filter), on buffers of the call's own.
+int av1mi_temporal_filter(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, void *out,
+                          uint32_t *mv) {
+  if (!c || !frames || n_frames == 0) return AV1MI_E_INVALID_ARG;
+  Resolved r;
+  int rc = resolve(params, &r);
+  if (rc) { set_err(c, "invalid parameters"); return rc; }
+  HIPCHK(c, hipSetDevice(c->device));
+  const int bps = r.p.bit_depth > 8 ? 2 : 1;
+  const size_t in_bytes = caller_bytes(r, n_frames), coded_bytes = (size_t)n_frames * r.cw * r.ch * 3 / 2 * bps;
+  const size_t n_mv = tf_mv_entries(r, n_frames);
+  const Av1miDevParams P = dev_params(r, n_frames, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+  hipStream_t s = c->stream;
+  const hipMemcpyKind in_kind = frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, out_kind = frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+  void *d_in = nullptr, *d_coded = nullptr;   // the frames as the caller has them (padded sizes: in, then the cropped result), and at the coded size
+  uint32_t *d_mv = nullptr;
+  auto cleanup = [&] { for (void *b : { d_in, d_coded, (void *)d_mv }) if (b) (void)hipFree(b); };
+  hipError_t e = hipMalloc(&d_coded, coded_bytes);
+  if (e == hipSuccess && n_mv) e = hipMalloc((void **)&d_mv, n_mv * sizeof(uint32_t));
+  if (e == hipSuccess && r.padded) {   // edge-extended as the encoder's source is
+    const void *src = frames;
+    e = hipMalloc(&d_in, in_bytes);
+    if (e == hipSuccess && !frames_on_device) { e = hipMemcpyAsync(d_in, frames, in_bytes, hipMemcpyHostToDevice, s); src = d_in; }
+    if (e == hipSuccess) e = av1mi_launch_pad(src, d_coded, (int)r.p.width, (int)r.p.height, r.cw, r.ch, (int)r.p.bit_depth, (int)n_frames, 0, s);
+  } else if (e == hipSuccess) {
+    e = hipMemcpyAsync(d_coded, frames, in_bytes, in_kind, s);
+  }
+  if (e == hipSuccess && n_mv) e = av1mi_launch_temporal_filter(&P, d_coded, d_mv, r.tf_frames, r.tf_strength, s);
+  if (e == hipSuccess && out) {
+    const void *res = d_coded;
+    if (r.padded) {
+      e = av1mi_launch_pad(d_coded, d_in, (int)r.p.width, (int)r.p.height, r.cw, r.ch, (int)r.p.bit_depth, (int)n_frames, 1, s);
+      res = d_in;
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, res, in_bytes, out_kind, s);
+  }
+  if (e == hipSuccess && mv && n_mv) e = hipMemcpyAsync(mv, d_mv, n_mv * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  const hipError_t e2 = hipStreamSynchronize(s);   // (also after a failure: nothing may still read the buffers freed below)
+  cleanup();
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) { set_err(c, "temporal-filter pass failed: %s", hipGetErrorString(e)); return e == hipErrorOutOfMemory ? AV1MI_E_OOM : AV1MI_E_HIP; }
+  return AV1MI_OK;
+}
+
 // The levels the context's last chunk was deblocked with and, with the level search, the candidates' errors: what download_chunk kept.
 int av1mi_lf_search_result(const av1mi_ctx *c, uint32_t n_frames, uint8_t *levels, uint64_t *err) {
   if (!c || !levels || n_frames == 0 || c->lf_levels.size() != (size_t)n_frames * 4) return AV1MI_E_INVALID_ARG;
@@ -1293,6 +1354,12 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   // not a multiple of 8: edge-extend every frame to the coded size (the signalled size stays exact)
   if (r.padded) HIPCHK(c, av1mi_launch_pad(frames_on_device ? frames : w.d_stage, w.d_src, (int)r.p.width, (int)r.p.height, r.cw, r.ch, P.bit_depth, (int)n_frames, 0, s));
   *d_src = frames_on_device && !r.padded ? frames : w.d_src;
+  // the key frames' temporal filter: in place in the chunk's source - a chunk that is used in place is copied first, the caller's
+  // memory is never written.  Everything below and after reads the filtered key frames.
+  if (tf_runs(r, n_frames)) {
+    if (*d_src != w.d_src) { HIPCHK(c, hipMemcpyAsync(w.d_src, frames, caller_bytes(r, n_frames), hipMemcpyDeviceToDevice, s)); *d_src = w.d_src; }
+    HIPCHK(c, av1mi_launch_temporal_filter(&P, w.d_src, w.d_tf_mv, r.tf_frames, r.tf_strength, s));
+  }
   // content-driven partition: the split masks of every superblock of the chunk, from the source, before anything walks blocks (the second
   // stream's motion search waits for EV_SRC_READY as well)
   if (P.part_map) HIPCHK(c, av1mi_launch_partition(&P, *d_src, w.d_part, s));

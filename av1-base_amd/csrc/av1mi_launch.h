@@ -41,6 +41,11 @@ extern "C" {
 hipError_t av1mi_launch_partition(const Av1miDevParams *P, const void *frames, uint32_t *part, hipStream_t stream);
 // quantiser index of every superblock (aq_activity_kernel, aq_map_kernel): act and qmap are [frame][superblock]
 hipError_t av1mi_launch_aq(const Av1miDevParams *P, const void *frames, uint16_t *act, uint8_t *qmap, int strength, hipStream_t stream);
+// the key frames' temporal filter (tf_kernel.hip, tf_rule.h), in place in `frames` at the coded size: every key frame of the chunk is
+// replaced by its filter over up to tf_frames followers at tf_strength, range P->me_range, and re-extended past the signalled size.
+// `frames` must be a 16-byte aligned device pointer (both callers pass an allocation of their own; anything else is refused).
+// mv: the search's node keys [key frame][tf_frames][16x16 block], all written (all-ones for a follower that does not exist)
+hipError_t av1mi_launch_temporal_filter(const Av1miDevParams *P, void *frames, uint32_t *mv, int tf_frames, int tf_strength, hipStream_t stream);
 // quarter-resolution luma of all frames
 hipError_t av1mi_launch_quarter_luma(const Av1miDevParams *P, const void *frames, uint16_t *quarter, hipStream_t stream);
 // `frames` / `prev0` must be 16-byte aligned device pointers (checked by the caller); sad[] zeroed by the caller

@@ -54,6 +54,12 @@ typedef struct av1mi_ctx av1mi_ctx;
 #define AV1MI_LR_RD(s) (0xC000u | (((uint32_t)(s) & 1u) << 9) | (((uint32_t)(s) & 2u) << 10))
 #define AV1MI_LR_RD_ON(v) (((uint32_t)(v) & 0xC000u) == 0xC000u)
 #define AV1MI_LR_RD_SCALE(v) ((((uint32_t)(v) >> 9) & 1u) | (((uint32_t)(v) >> 10) & 2u))
+/* av1mi_params.me_presearch carries three values: bit 0 the pre-search's switch, bits 8-10 the frames (0 = off, 1 .. 7) and bits 12-14
+ * the strength (0 .. 7) of the key frames' temporal filter */
+#define AV1MI_ME_TF(presearch, frames, strength) (((uint32_t)(presearch) & 1u) | (((uint32_t)(frames) & 7u) << 8) | (((uint32_t)(strength) & 7u) << 12))
+#define AV1MI_ME_PRESEARCH(v) ((uint32_t)(v) & 1u)
+#define AV1MI_TF_FRAMES(v) (((uint32_t)(v) >> 8) & 7u)
+#define AV1MI_TF_STRENGTH(v) (((uint32_t)(v) >> 12) & 7u)
 
 /* Operating point.  Replaces the reference's single constant
  *   SVT_PARAMS = "--crf 8 --preset 3 --film-grain 20 ... --keyint 240 --lookahead 40"
@@ -167,7 +173,13 @@ typedef struct {
   uint32_t min_block_log2;  /* smallest leaf under partition_search: 3 (8x8, default when 0) .. block_log2 */
   uint32_t me_presearch;    /* inter frames: 1 = hierarchical motion search - a quarter-resolution search of +-64 luma samples per 32x32 cell finds the
                                centre the full-resolution search of +-me_range then runs around (row a13's "1/4-res ... full"); 0 (default): the
-                               full-resolution search runs around the zero vector */
+                               full-resolution search runs around the zero vector.
+                               bits 8-10: tf_frames N = 1 .. 7, bits 12-14: tf_strength s = 0 .. 7 (AV1MI_ME_TF packs the field) - the key
+                               frames' temporal filter: every key frame f (f % keyint == 0) of a chunk is
+                               replaced, as the source of the whole encode, by its motion-compensated filter over the frames f + 1 ..
+                               f + min(N, keyint - 1, frames left in the chunk); the caller's frames are not written, followers are not
+                               changed, and the bitstream is the one the chunk with av1mi_temporal_filter's output gives with the filter
+                               off.  N = 0 (default): off.  Any other bit, or s without N, is refused */
   uint32_t cdef_search;     /* CDEF strengths chosen per frame and per 64x64 superblock by an exhaustive search on the device:
                                0 (default) = off, the fixed strengths above for every frame; k = 1..4 = on, cdef_bits = k - 1, i.e. 1, 2, 4 or 8
                                strength pairs per frame, each superblock picking one by the squared error of the filtered output against the
@@ -185,8 +197,9 @@ typedef struct {
 typedef struct {
   uint32_t frames;
   uint64_t bytes;
-  double sse[3];            /* sum of squared error of the reconstruction, per plane */
-  double psnr[3];
+  double sse[3];            /* sum of squared error of the reconstruction, per plane: against the coded source - with the temporal
+                               filter on, the filtered key frames (av1mi_temporal_filter returns them), not the caller's */
+  double psnr[3];           /* ... and the PSNR from it, likewise */
   /* device time per stage, milliseconds (HIP events on the encoder's stream) */
   float ms_h2d, ms_recon, ms_cdef, ms_entropy, ms_pack, ms_d2h, ms_total;
   float ms_symbolize;       /* part of ms_entropy spent in the symbolize kernel */
@@ -248,6 +261,19 @@ int av1mi_scene_cuts(av1mi_ctx *ctx, const av1mi_params *params, const void *fra
  * av1mi_scene_cuts (tight planar frames, host or 16-byte aligned device memory). */
 int av1mi_aq_qindex(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames,
                     int frames_on_device, uint8_t *qindex);
+
+/* ---- the key frames' temporal filter on its own --------------------------------------------
+ * What av1mi_encode_chunk codes instead of the key frames when av1mi_params.me_presearch carries the filter (AV1MI_ME_TF): the
+ * same launches on the same frames.  `out` (optional; layout and residency of `frames`, at the signalled size): the chunk with
+ * its key frames filtered and every other frame copied.  `mv` (optional, host memory): the filter's motion search,
+ * mv[((f / keyint) * N + (t - 1)) * nb + b] = the winner of block b of key frame f against frame f + t as (cost << 11) | index,
+ * cost = SAD + 16 (|dx| + |dy|), index = (dy + R) (2 R + 1) + dx + R, R = me_range; nb = the 16x16 blocks of the coded size
+ * (width and height rounded up to multiples of 8), b in raster order; 0xFFFFFFFF for a follower that does not exist.  With the
+ * filter off `out` is a copy and `mv` is not written.
+ * av1mi_aq_qindex and av1mi_scene_cuts look at the frames they are given, whatever the field says: a caller who wants what the
+ * encoder sees with the filter on passes them this call's output. */
+int av1mi_temporal_filter(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames,
+                          int frames_on_device, void *out, uint32_t *mv);
 
 /* ---- deblocking levels of the last chunk ---------------------------------------------------
  * loop_filter_level[0..3] (luma vertical edges, luma horizontal, U, V) every frame of the context's last successfully encoded

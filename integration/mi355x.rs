@@ -32,7 +32,7 @@ pub struct Av1miParams {            // include/av1mi.h: av1mi_params
     pub color_primaries: u32, pub transfer_characteristics: u32, pub matrix_coefficients: u32,   // CICP colour description (0 / 0 / 0 = none; HDR10: 9 / 16 / 9)
     pub partition_search: u32,      // 1 = content-driven partition between min_block_log2 and block_log2; 2 = key frames as 1, inter frames partitioned from the motion search's node costs
     pub min_block_log2: u32,        // smallest leaf under partition_search (0 = 3: 8x8)
-    pub me_presearch: u32,          // 1 = quarter-resolution pre-search (+-64) before the full-resolution search
+    pub me_presearch: u32,          // bit 0: 1 = quarter-resolution pre-search (+-64) before the full-resolution search; bits 8-10 / 12-14: the key frames' temporal filter (`me_tf` packs the field; 0 frames = off)
     pub cdef_search: u32,           // 0 = fixed CDEF strengths; k = 1..4 = per-frame / per-superblock search over 2^(k-1) strength pairs
 }
 #[repr(C)]
@@ -60,6 +60,12 @@ pub const AV1MI_LR_WIENER_FIT: u32 = 0x400;
 pub const fn cq_aq(cq: u32, strength: u32) -> u32 { (cq & 0xFF) | ((strength & 7) << 8) }
 pub const fn cq_level_of(v: u32) -> u32 { v & 0xFF }
 pub const fn aq_strength_of(v: u32) -> u32 { (v >> 8) & 7 }
+// include/av1mi.h: AV1MI_ME_TF / AV1MI_ME_PRESEARCH / AV1MI_TF_FRAMES / AV1MI_TF_STRENGTH - me_presearch carries the pre-search's switch and
+// the temporal filter's frames (0 = off, 1..7) and strength (0..7)
+pub const fn me_tf(presearch: u32, frames: u32, strength: u32) -> u32 { (presearch & 1) | ((frames & 7) << 8) | ((strength & 7) << 12) }
+pub const fn me_presearch_of(v: u32) -> u32 { v & 1 }
+pub const fn tf_frames_of(v: u32) -> u32 { (v >> 8) & 7 }
+pub const fn tf_strength_of(v: u32) -> u32 { (v >> 12) & 7 }
 type ProgressCb = Option<extern "C" fn(user: *mut c_void, done: u32, total: u32, fps: f64, bytes: u64)>;
 
 #[link(name = "av1mi")]

@@ -1,0 +1,59 @@
+// The temporal filter's rules (av1-base_amd/csrc/tf_rule.h: what the kernels of tf_kernel.hip and av1mi_host.cpp apply) compiled for the
+// host, for tests/test_tf_host.py: reads cases from a text file, one per line, and prints one line of results each.
+//   F v                          the me_presearch field: ok, pre-search, frames, strength
+//   N N keyint n_frames f        the followers of key frame f; the chunk's key frames
+//   I S B sh chroma              weight index and weight of a sample
+//   L num den                    the blend
+//   C a b c d dx dy p            the chroma prediction from its four taps at the luma vector, and the bases of position p on both axes
+//   K bd s key pred chroma n     a generated block - every key sample `key`, every follower's prediction `pred`, n followers alike: S
+//                                (the 3x3 sum with clamped positions, from an array of the block's errors), B, index, weight, den, output
+#include <inttypes.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <vector>
+#include "../../av1-base_amd/csrc/tf_rule.h"
+
+int main(int argc, char **argv) {
+  if (argc < 2) { fprintf(stderr, "usage: %s cases.txt\n", argv[0]); return 2; }
+  FILE *f = fopen(argv[1], "r");
+  if (!f) { perror(argv[1]); return 2; }
+  char t;
+  long lines = 0;
+  while (fscanf(f, " %c", &t) == 1) {
+    long long a[8] = {0};
+    const int want = t == 'F' ? 1 : t == 'N' ? 4 : t == 'I' ? 4 : t == 'L' ? 2 : t == 'C' ? 7 : t == 'K' ? 6 : -1;
+    if (want < 0) { fprintf(stderr, "line %ld: unknown case '%c'\n", lines, t); fclose(f); return 2; }
+    for (int i = 0; i < want; i++)
+      if (fscanf(f, "%lld", &a[i]) != 1) { fprintf(stderr, "short line %ld\n", lines); fclose(f); return 2; }
+    if (t == 'F') {
+      const uint32_t v = (uint32_t)a[0];
+      printf("%d %d %d %d\n", (int)av1mi_tf_field_ok(v), av1mi_tf_field_presearch(v), av1mi_tf_field_frames(v), av1mi_tf_field_strength(v));
+    } else if (t == 'N') {
+      printf("%d %d\n", av1mi_tf_followers((int)a[0], (int)a[1], (int)a[2], (int)a[3]), av1mi_tf_key_frames((int)a[1], (int)a[2]));
+    } else if (t == 'I') {
+      const int i = av1mi_tf_index((uint32_t)a[0], (uint32_t)a[1], (int)a[2], (int)a[3]);
+      printf("%d %d\n", i, av1mi_tf_weight(i));
+    } else if (t == 'L') {
+      printf("%d\n", av1mi_tf_blend((uint32_t)a[0], (uint32_t)a[1]));
+    } else if (t == 'C') {
+      printf("%d %d %d\n", av1mi_tf_chroma_pred((int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)a[4], (int)a[5]), av1mi_tf_chroma_base((int)a[6], (int)a[4]),
+             av1mi_tf_chroma_base((int)a[6], (int)a[5]));
+    } else {
+      const int bd = (int)a[0], s = (int)a[1], key = (int)a[2], pred = (int)a[3], chroma = (int)a[4], n = (int)a[5];
+      const int side = chroma ? AV1MI_TF_BLOCK / 2 : AV1MI_TF_BLOCK;
+      std::vector<uint32_t> e2((size_t)side * side);
+      uint32_t B = 0;
+      for (auto &v : e2) { v = (uint32_t)((key - pred) * (key - pred)); B += v; }
+      uint32_t S = 0;   // at the block's corner: every clamped position is inside the array
+      for (int v = -1; v <= 1; v++)
+        for (int u = -1; u <= 1; u++) S += e2[(size_t)(v < 0 ? 0 : v) * side + (u < 0 ? 0 : u)];
+      const int i = av1mi_tf_index(S, B, av1mi_tf_shift(s, bd), chroma), w = av1mi_tf_weight(i);
+      uint32_t num = 16u * (uint32_t)key, den = 16;
+      for (int k = 0; k < n; k++) { num += (uint32_t)w * (uint32_t)pred; den += (uint32_t)w; }
+      printf("%" PRIu32 " %" PRIu32 " %d %d %" PRIu32 " %d\n", S, B, i, w, den, av1mi_tf_blend(num, den));
+    }
+    lines++;
+  }
+  fclose(f);
+  return 0;
+}
