@@ -321,6 +321,14 @@ def write_headers(params):
     return seq.raw[:n.value], fh.raw[:(bits.value + 7) // 8], bits.value
 
 
+def _frames_ptr(frames, on_device):
+    """(pointer, what keeps it alive) of the frames a pass is given: an int device pointer with on_device, else host bytes-like / numpy"""
+    if on_device:
+        return C.c_void_p(int(frames)), None
+    keep = bytes(frames)
+    return C.cast(C.c_char_p(keep), C.c_void_p), keep
+
+
 class Context:
     """One GPU + one HIP stream = one chunk in flight (include/av1mi.h: av1mi_ctx)."""
 
@@ -351,14 +359,9 @@ class Context:
         state = state if state is not None else SceneState()
         sad = (C.c_uint64 * n_frames)()
         cut = (C.c_uint8 * n_frames)()
-        if on_device:
-            fptr = C.c_void_p(int(frames))
-            pptr = C.c_void_p(int(prev_frame)) if prev_frame else None
-        else:
-            keep = bytes(frames)
-            fptr = C.cast(C.c_char_p(keep), C.c_void_p)
-            keep2 = bytes(prev_frame) if prev_frame is not None else None
-            pptr = C.cast(C.c_char_p(keep2), C.c_void_p) if keep2 is not None else None
+        fptr, keep = _frames_ptr(frames, on_device)
+        has_prev = bool(prev_frame) if on_device else prev_frame is not None
+        pptr, keep2 = _frames_ptr(prev_frame, on_device) if has_prev else (None, None)
         rc = _lib.av1mi_scene_cuts(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0, pptr, C.byref(state),
                                    min_scene_len, sad, cut)
         _raise_for(rc, self.last_error())
@@ -371,11 +374,7 @@ class Context:
         cw, ch = (params.width + 7) & ~7, (params.height + 7) & ~7
         sbc, sbr = (cw + 63) // 64, (ch + 63) // 64
         out = np.zeros((n_frames, sbr, sbc), dtype=np.uint8)
-        if on_device:
-            fptr = C.c_void_p(int(frames))
-        else:
-            keep = bytes(frames)
-            fptr = C.cast(C.c_char_p(keep), C.c_void_p)
+        fptr, keep = _frames_ptr(frames, on_device)
         rc = _lib.av1mi_aq_qindex(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0, out.ctypes.data_as(C.POINTER(C.c_uint8)))
         _raise_for(rc, self.last_error())
         return out
@@ -392,20 +391,28 @@ class Context:
         cw, ch = (params.width + 7) & ~7, (params.height + 7) & ~7
         mv = np.zeros(((n_frames + keyint - 1) // keyint, n_tf, ((cw + 15) // 16) * ((ch + 15) // 16)), dtype=np.uint32) if want_mv and n_tf else None
         out = None
+        fptr, keep = _frames_ptr(frames, on_device)
         if on_device:
-            fptr = C.c_void_p(int(frames))
             optr = C.c_void_p(int(out_ptr)) if out_ptr is not None else None
         else:
-            arr = np.ascontiguousarray(np.frombuffer(frames, dtype=np.uint8) if not isinstance(frames, np.ndarray) else frames)
-            if arr.nbytes != nbytes:
-                raise ValueError("frames: expected %d bytes, got %d" % (nbytes, arr.nbytes))
-            fptr = arr.ctypes.data_as(C.c_void_p)
+            if len(keep) != nbytes:
+                raise ValueError("frames: expected %d bytes, got %d" % (nbytes, len(keep)))
             out = np.empty(nbytes, dtype=np.uint8)
             optr = out.ctypes.data_as(C.c_void_p)
         rc = _lib.av1mi_temporal_filter(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0, optr,
                                         mv.ctypes.data_as(C.POINTER(C.c_uint32)) if mv is not None else None)
         _raise_for(rc, self.last_error())
         return out, mv
+
+    def _unit_grid(self, what, n_units, width, height):
+        """(unit rows, unit columns) a restoration result is shaped by: of width x height - by default the frame size of the last
+        successful encode_chunk call - at that call's unit size; refused unless that grid has the library's n_units units"""
+        if width is None or height is None:
+            width, height = self._last_size if self._last_size is not None else (0, 0)
+        ur, uc = lr_unit_grid(width, height, self._last_unit_shift)
+        if n_units == 0 or ur * uc != n_units:
+            _raise_for(E_INVALID_ARG, "%s: the last chunk has %d units per plane, not the %d x %d of %d x %d frames" % (what, n_units, ur, uc, width, height))
+        return ur, uc
 
     def lf_search_result(self, n_frames):
         """The deblocking levels of the last encoded chunk and the level search's error table (include/av1mi.h:
@@ -424,12 +431,7 @@ class Context:
         unit count (av1mi_lr_fit_units); their shape follows the frame size of this object's last successful encode_chunk call, or
         width and height, at that call's unit size, and a size whose unit grid is not the library's is refused."""
         import numpy as np
-        n_units = int(_lib.av1mi_lr_fit_units(self._h))
-        if width is None or height is None:
-            width, height = self._last_size if self._last_size is not None else (0, 0)
-        ur, uc = lr_unit_grid(width, height, self._last_unit_shift)
-        if n_units == 0 or ur * uc != n_units:
-            _raise_for(E_INVALID_ARG, "av1mi_lr_fit_result: the last chunk has %d units per plane, not the %d x %d of %d x %d frames" % (n_units, ur, uc, width, height))
+        ur, uc = self._unit_grid("av1mi_lr_fit_result", int(_lib.av1mi_lr_fit_units(self._h)), width, height)
         units = np.zeros((n_frames, 3, ur, uc, 4), dtype=np.int8)
         err = np.zeros((n_frames, 3, ur, uc, 23), dtype=np.uint64)
         rc = _lib.av1mi_lr_fit_result(self._h, n_frames, units.ctypes.data_as(C.POINTER(C.c_int8)), err.ctypes.data_as(C.POINTER(C.c_uint64)))
@@ -442,12 +444,7 @@ class Context:
         err[frame][plane][unit row][unit column] (uint64); zeros for planes that are not restored and for a chunk without the fit.
         Sized and shaped as lr_fit_result's."""
         import numpy as np
-        n_units = int(_lib.av1mi_lr_wiener_fit_units(self._h))
-        if width is None or height is None:
-            width, height = self._last_size if self._last_size is not None else (0, 0)
-        ur, uc = lr_unit_grid(width, height, self._last_unit_shift)
-        if n_units == 0 or ur * uc != n_units:
-            _raise_for(E_INVALID_ARG, "av1mi_lr_wiener_fit_result: the last chunk has %d units per plane, not the %d x %d of %d x %d frames" % (n_units, ur, uc, width, height))
+        ur, uc = self._unit_grid("av1mi_lr_wiener_fit_result", int(_lib.av1mi_lr_wiener_fit_units(self._h)), width, height)
         units = np.zeros((n_frames, 3, ur, uc, 8), dtype=np.int8)
         err = np.zeros((n_frames, 3, ur, uc), dtype=np.uint64)
         rc = _lib.av1mi_lr_wiener_fit_result(self._h, n_frames, units.ctypes.data_as(C.POINTER(C.c_int8)), err.ctypes.data_as(C.POINTER(C.c_uint64)))
@@ -460,12 +457,7 @@ class Context:
         the choice's side information in sixteenths of a bit), and lambda (int; 0 without the rate term).  Sized and shaped as
         lr_fit_result's."""
         import numpy as np
-        n_units = int(_lib.av1mi_lr_rd_units(self._h))
-        if width is None or height is None:
-            width, height = self._last_size if self._last_size is not None else (0, 0)
-        ur, uc = lr_unit_grid(width, height, self._last_unit_shift)
-        if n_units == 0 or ur * uc != n_units:
-            _raise_for(E_INVALID_ARG, "av1mi_lr_rd_result: the last chunk has %d units per plane, not the %d x %d of %d x %d frames" % (n_units, ur, uc, width, height))
+        ur, uc = self._unit_grid("av1mi_lr_rd_result", int(_lib.av1mi_lr_rd_units(self._h)), width, height)
         choice = np.zeros((n_frames, 3, ur, uc), dtype=np.int8)
         bits16 = np.zeros((n_frames, 3, ur, uc), dtype=np.uint32)
         lam = C.c_uint64(0)

@@ -1,0 +1,153 @@
+// av1mi_ctx.h - the encoder context and what it owns: the device workspace, the streams and events, the error text and the record
+// of its last chunk.  av1mi_ctx.cpp keeps them (and runs the stand-alone passes); av1mi_host.cpp encodes one chunk on them.
+#ifndef AV1MI_CTX_H
+#define AV1MI_CTX_H
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "av1mi_syntax.h"
+#include "av1mi_launch.h"
+
+namespace av1mi {
+
+// Points of one chunk on the context's streams; the report's stage times are the intervals between them.  Main stream: start, source
+// on the device, reconstruction (and the rest of the kind's work before entropy coding), symbolize, entropy coding (groups joined), packing
+// and download done.  Second stream: its work beside the range coder.  Third: an inter chunk's groups.  Fourth: the edge tiles' fork, join.
+enum ChunkEvent { EV_START, EV_SRC_READY, EV_RECON_DONE, EV_SYM_DONE, EV_ENTROPY_DONE, EV_PACK_DONE, EV_DOWNLOAD_DONE,
+                  EV_CDEF_START, EV_CDEF_DONE, EV_GROUPS_JOINED, EV_EDGE_FORK, EV_EDGE_JOIN, EV_COUNT };
+
+// A context's device workspace and host staging buffer.  Every buffer comes from ws_alloc, which records it; free_workspace frees
+// what was recorded and resets all of it to these defaults.
+struct Workspace {
+  size_t cap_frames = 0;
+  int scale = 0;       // the capacity multiplier the workspace was allocated with
+  Resolved res = {};   // ... and the parameters of its last chunk
+  void *d_src = nullptr, *d_rec = nullptr, *d_fin = nullptr;
+  int16_t *d_levels = nullptr; Av1miBlkInfo *d_blk = nullptr;
+  uint8_t *d_slots = nullptr, *d_out = nullptr, *d_hdr = nullptr;
+  uint16_t *d_cdf = nullptr;
+  Av1miDevParams *d_params = nullptr;  // copy of P for the kernels that read their parameters through a pointer (recon)
+  uint32_t *d_tile_bytes = nullptr, *d_tile_off = nullptr, *d_frame_size = nullptr, *d_payload = nullptr, *d_sym = nullptr;
+  uint32_t *d_streams = nullptr, *d_combos = nullptr;
+  unsigned long long *d_sse = nullptr;
+  // symbolize's tile order (tile_weight_rule.h): the classes' counters - the head of the block d_sse lies in, so that one fill clears
+  // both - and the rows [AV1MI_TILE_CLASSES][cap_frames x tiles] the reconstruction fills
+  uint32_t *d_sym_count = nullptr, *d_sym_order = nullptr;
+  Av1miChunkRecord *d_record = nullptr;   // symbol counts, overflow flag, then frame_off[cap_frames + 1] (av1mi_launch_pack)
+  unsigned long long *d_me = nullptr;  // motion search results per 8x8 unit per frame
+  void *d_stage = nullptr;             // sizes that are not multiples of 8: frames in the caller's tight layout (input / reconstruction out)
+  void *d_cd = nullptr;                // loop restoration on: CDEF output (d_fin then holds the restored frames)
+  unsigned long long *d_me_sub = nullptr;  // sub-sample refinement: refined [frame][8x8 unit] keys (me_kernel.hip)
+  uint16_t *d_quarter = nullptr;           // me_presearch: quarter-resolution luma of every frame of the chunk
+  uint32_t *d_centre = nullptr;            // me_presearch: centre code of the full search per [frame][superblock]
+  uint32_t *d_part = nullptr;              // content-driven partition: split mask per [frame][superblock] (partition_kernel)
+  uint32_t *d_me64 = nullptr;              // 64x64 leaves: the search's [frame][superblock][candidate] SAD table
+  uint32_t *d_nodes = nullptr;             // partition_search = 2: the node-mode search's [frame][level][node] keys (part_inter_rule.h)
+  uint16_t *d_aq_act = nullptr;            // adaptive quantisation: E per [frame][superblock] (aq_activity_kernel)
+  uint8_t *d_aq_map = nullptr;             // ... the quantiser index per [frame][superblock] (aq_map_kernel)
+  uint32_t *d_tf_mv = nullptr;             // temporal filter: the search's keys per [key frame][follower][16x16 block] (tf_kernel.hip)
+  Av1miQmEntry *d_qm = nullptr;        // quantiser-matrix steps (Av1miDevParams::qm_tab), one slice per quantiser slot, valid for qm_key = (slices, level, qidx, bit depth)
+  std::vector<Av1miQmEntry> h_qm; int qm_key = -1;
+  uint8_t *d_lrc = nullptr;            // per restoration unit: 0 = off, k = candidate k-1
+  unsigned long long *d_lrsse = nullptr;  // per restoration unit: the candidates' SSE sums (scratch of lr_kernel.hip's two phases)
+  // the self-guided fit: one block, laid out for the chunk's units (ensure_workspace) - errors and records, which the host fetches
+  // into h_fit with one copy, then sums and codes - so that one fill clears a chunk's part
+  Av1miLrFit fit = {};
+  uint8_t *d_fit = nullptr, *h_fit = nullptr;
+  // the Wiener fit, likewise: errors and records at the head (h_wfit), then sums and codes
+  Av1miLrWfit wfit = {};
+  uint8_t *d_wfit = nullptr, *h_wfit = nullptr;
+  unsigned long long *d_cdef_err = nullptr;  // CDEF strength search: per [frame][superblock] the 24 candidates' squared errors
+  int8_t *d_cdef_idx = nullptr;              // ... per [frame][superblock] the index into the frame's set (-1: not coded)
+  uint8_t *d_cdef_sel = nullptr;             // ... per frame the set: 8 slots of pair indices
+  unsigned long long *d_lf_err = nullptr;    // deblocking level search: per [frame][plane] the 16 candidates' squared errors, and behind
+  uint8_t *d_lf_sel = nullptr;               // them, in the same block, per frame the four levels; h_lf: where one copy lands both
+  uint8_t *h_lf = nullptr;
+  uint8_t *h_out = nullptr;            // host staging (pinned), for when the caller's buffer cannot be page-locked
+  // Page-locked host side of the small transfers.  The chunk constants - header blob, default CDFs, parameters - are the same for
+  // every chunk of a job: h_hdr / h_cdf / h_params hold what d_hdr / d_cdf / d_params hold, and prepare_chunk uploads only what differs.
+  uint8_t *h_hdr = nullptr; uint16_t *h_cdf = nullptr; Av1miDevParams *h_params = nullptr;
+  size_t hdr_bytes = 0;                // bytes of h_hdr that d_hdr is known to hold; 0: unknown (the strength search writes into d_hdr)
+  int cdf_qidx = -1;                   // the quantiser index d_cdf was made for (the blob depends on nothing else); -1: none
+  int cdf_bs_log2 = -1;                // ... and the leaf size its compact image behind the blob was made for
+  int params_on_device = 0;            // d_params holds the first so many blocks of h_params (1, or AV1MI_AQ_SLOTS with adaptive quantisation)
+  Av1miChunkRecord *h_record = nullptr; unsigned long long *h_sse = nullptr;   // d_record and d_sse land here
+  size_t out_cap = 0, me64_bytes = 0, nodes_bytes = 0, h_out_cap = 0, tf_mv_bytes = 0;   // bytes of d_out, d_me64, d_nodes, h_out, d_tf_mv
+  std::vector<std::pair<void *, bool>> owned;   // every buffer above: (address, page-locked host memory)
+};
+
+// (Re)allocates one buffer of the workspace - device memory, or page-locked host memory with `host` - and records it for free_workspace
+template <class T>
+hipError_t ws_alloc(Workspace &w, T *&p, size_t bytes, bool host = false) {
+  for (auto b = w.owned.begin(); p && b != w.owned.end(); ++b)   // a buffer that grows: the old one goes
+    if (b->first == (void *)p) { (void)(b->second ? hipHostFree(p) : hipFree(p)); w.owned.erase(b); break; }
+  void *v = nullptr;
+  const hipError_t e = host ? hipHostMalloc(&v, bytes, hipHostMallocDefault) : hipMalloc(&v, bytes);
+  if (e == hipSuccess) w.owned.emplace_back(v, host);
+  p = (T *)v;
+  return e;
+}
+
+// What a context remembers of its last chunk for the *_result, *_units and *_tiles entry points: filled once the chunk has succeeded
+// (run_chunk), reset when the next one starts.
+struct LastChunk {
+  uint32_t n_frames = 0;   // 0: no chunk yet, or the last one failed
+  // its deblocking levels (4 per frame) and level-search errors (48 per frame; zeros without the search): av1mi_lf_search_result
+  std::vector<uint8_t> lf_levels;
+  std::vector<unsigned long long> lf_errs;
+  // its self-guided fit (av1mi_lr_fit_result): the units of its frames over three planes, and whether the fit ran - the errors and
+  // records are then the head of ws.h_fit
+  size_t fit_units = 0;
+  uint32_t fit_plane_units = 0;   // the units of one plane of one frame (av1mi_lr_fit_units)
+  bool fit_on = false;
+  bool wfit_on = false;           // ... and its Wiener fit (av1mi_lr_wiener_fit_result): the head of ws.h_wfit
+  uint32_t sym_tiles = 0;         // the tiles of its weight-ordered table (av1mi_sym_order_result); 0: natural order
+  bool pi_keys = false;           // it was partitioned from the search's node costs: its search keys are reported too
+  uint32_t pi_frames = 0, pi_units = 0, pi_sbs = 0;   // with a partition map: frames (else 0), 8x8 units and superblocks per frame (av1mi_inter_partition_result)
+};
+
+}  // namespace av1mi
+
+struct av1mi_ctx {
+  int device = -1;
+  hipStream_t stream = nullptr;   // the four streams come from and go back to a process-wide pool (av1mi_ctx_create)
+  hipStream_t stream2 = nullptr;  // CDEF + SSE run here, beside the entropy kernels on `stream`
+  hipStream_t stream3 = nullptr;  // inter chunks: entropy coding of finished groups of frames, beside the frame-by-frame chain
+  hipStream_t stream4 = nullptr;  // the frame-edge tiles' symbolize variant, beside the regular one on `stream` (av1mi_launch_entropy)
+  hipEvent_t ev[av1mi::EV_COUNT] = {};
+  std::vector<hipEvent_t> me_ev;       // per frame: its motion search has finished (second stream -> main stream)
+  std::vector<hipEvent_t> grp_ev;      // per group of frames of an inter chunk: reconstructed (main stream -> third stream)
+  std::string err;
+  int cap_scale = 1;   // per-tile symbol-stream / bitstream-slot capacity multiplier (1, 2, 4, ... 64)
+  av1mi::Workspace ws;
+  Av1miDevParams P = {};
+  bool sym_order = true;          // AV1MI_SYM_ORDER, read when the context is made: 0 = symbolize in natural tile order everywhere
+  bool part_inter = false;        // this chunk's inter frames are partitioned from the search's node costs (partition_search = 2)
+  av1mi::LastChunk last;
+};
+
+#define HIPCHK(c, call)                                                                          \
+  do {                                                                                           \
+    hipError_t e__ = (call);                                                                     \
+    if (e__ != hipSuccess) {                                                                     \
+      set_err((c), "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__), __FILE__, __LINE__);   \
+      return e__ == hipErrorOutOfMemory ? AV1MI_E_OOM : AV1MI_E_HIP;                             \
+    }                                                                                            \
+  } while (0)
+
+namespace av1mi {
+
+void set_err(av1mi_ctx *c, const char *fmt, ...);
+void free_workspace(av1mi_ctx *c);
+int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames);
+// the workspace's buffers bound into a chunk's parameters, each under the condition its kernels run under
+void bind_workspace(Av1miDevParams &P, const Resolved &r, const Workspace &w);
+// a page-locked block of the process-wide pool for a chunk's bitstream (av1mi_free puts it back); null: none to be had
+void *pin_acquire(size_t bytes);
+
+}  // namespace av1mi
+
+#endif

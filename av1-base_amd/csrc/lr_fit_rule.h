@@ -1,5 +1,5 @@
 // lr_fit_rule.h - the self-guided restoration fit (av1mi_params.enable_lr bit 8, AV1MI_LR_FIT), all integers, for
-// host and device: lr_fit_kernel.hip runs it per restoration unit, av1mi_host.cpp builds the fixed candidates' bit strings with its
+// host and device: lr_fit_kernel.hip runs it per restoration unit, av1mi_syntax.cpp builds the fixed candidates' bit strings with its
 // writers from its candidate tables (the restoration kernels' too, lr_pieces.h), tests/host/lr_fit_rule_host.cpp compiles it for the CPU against the numpy restatement (tests/sgr_fit_ref.py).
 // Non-normative except for the syntax: the decoder sees lr_sgr_set and the weights (§5.11.58).
 //
@@ -42,7 +42,7 @@ AV1MI_FIT_HD constexpr int av1mi_sgr_eps0(int t) {   // a byte per set
 AV1MI_FIT_HD constexpr int av1mi_sgr_eps1(int t) { return (int)((0x00EB85FEDCBA9864ull >> (4 * t)) & 15); }   // a nibble per set
 
 // ---- the fixed candidates (restated in oracle/av1o_lr.c av1o_wiener_candidates / av1o_sgr_candidates): initialisers,
-// for the kernels' __constant__ copies (lr_pieces.h) and the host's tables below (the fixed candidates' bit strings, av1mi_host.cpp)
+// for the kernels' __constant__ copies (lr_pieces.h) and the host's tables below (the fixed candidates' bit strings, av1mi_syntax.cpp)
 #define AV1MI_WIENER_CAND { { 0, 0, -4 }, { 1, -3, -6 }, { 3, -7, 15 } }       /* taps 0 .. 2 of both passes */
 #define AV1MI_WIENER_CAND_UV { { 0, 0, -4 }, { 0, 0, 16 }, { 0, 6, 20 } }      /* chroma (enable_lr 3 / 4): tap 0 is 0 and not coded, §5.11.58 */
 #define AV1MI_SGR_CAND { { 9, 31, 31 }, { 9, 0, 31 }, { 9, 31, 95 } }          /* { lr_sgr_set, xqd0, xqd1 } */

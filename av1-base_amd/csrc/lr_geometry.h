@@ -1,5 +1,5 @@
 // lr_geometry.h - the grid of loop restoration units at a unit size (av1mi_params.enable_lr bits 12-13, lr_unit_shift; DESIGN.md §3 item
-// 9f), for host and device: the restoration kernels, symbolize's read_lr and av1mi_host.cpp take their counts, bounds and maps from here,
+// 9f), for host and device: the restoration kernels, symbolize's read_lr and the host code take their counts, bounds and maps from here,
 // tests/host/lr_geometry_host.cpp compiles it for the CPU against tests/lr_ref.py.  Normative: §5.9.20 (unit sizes), §5.11.57 (which
 // superblock reads which unit), §7.17 (count_units_in_frame, the units' bounds, the row offset of 8 luma rows).
 //

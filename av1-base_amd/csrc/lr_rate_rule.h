@@ -1,6 +1,6 @@
 // lr_rate_rule.h - the rate term of the loop-restoration unit decisions (av1mi_params.enable_lr bits 14 and 15, AV1MI_LR_RD; DESIGN.md
 // §3 item 9g), all integers, for host and device: the three restoration kernels weigh a candidate's side information against its error
-// with it, av1mi_host.cpp derives lambda and reports the bits (av1mi_lr_rd_result), tests/host/lr_rate_rule_host.cpp compiles it for the
+// with it, av1mi_syntax.cpp derives lambda and av1mi_ctx.cpp reports the bits (av1mi_lr_rd_result), tests/host/lr_rate_rule_host.cpp compiles it for the
 // CPU against the numpy restatement (tests/lr_rd_ref.py).  Non-normative: the decoder sees the units' types and coefficients as ever.
 //
 //   lambda       q = the dc step of base_q_idx at the stream's bit depth, lambda0 = (13 q^2) >> 9 (libaom's RDCOST weighs D << 7 against

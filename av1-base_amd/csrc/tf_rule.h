@@ -1,7 +1,7 @@
 // tf_rule.h - the rules of the key frames' temporal filter that more than one place applies, compiled for
 // the device and for the host: how the switch packs into av1mi_params.me_presearch, how many followers a key frame has, the weight of a
 // follower's sample from its errors, the blend, and the chroma predictor's taps at a luma vector.  The kernels of tf_kernel.hip and
-// av1mi_host.cpp go through these; tests/host/tf_rule_host.cpp runs them on the CPU against the restatement in tests/tf_ref.py.
+// the host code (av1mi_syntax.cpp, av1mi_host.cpp) go through these; tests/host/tf_rule_host.cpp runs them on the CPU against the restatement in tests/tf_ref.py.
 // The search's own rules - reach, cost, index, the node key - are me_rule.h's, with blocks of AV1MI_TF_BLOCK and a zero centre.
 #ifndef AV1MI_TF_RULE_H
 #define AV1MI_TF_RULE_H

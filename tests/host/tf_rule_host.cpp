@@ -1,4 +1,4 @@
-// The temporal filter's rules (av1-base_amd/csrc/tf_rule.h: what the kernels of tf_kernel.hip and av1mi_host.cpp apply) compiled for the
+// The temporal filter's rules (av1-base_amd/csrc/tf_rule.h: what the kernels of tf_kernel.hip and the host code apply) compiled for the
 // host, for tests/test_tf_host.py: reads cases from a text file, one per line, and prints one line of results each.
 //   F v                          the me_presearch field: ok, pre-search, frames, strength
 //   N N keyint n_frames f        the followers of key frame f; the chunk's key frames

@@ -8,20 +8,14 @@ import re
 import numpy as np
 import pytest
 
+import host_build
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def av1mi():
-    lib = os.path.join(ROOT, "av1-base_amd", "libav1mi.so")
-    if not os.path.exists(lib):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("av1mi_build", os.path.join(ROOT, "av1-base_amd", "build.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    import av1mi as m
-    return m
+    return host_build.library()
 
 
 def test_exports_every_declared_symbol(av1mi):

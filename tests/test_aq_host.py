@@ -4,12 +4,11 @@ staying what it was, and the rule header (av1-base_amd/csrc/aq_rule.h) compiled 
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_build
 import aq_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,15 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def av1mi():
-    lib = os.path.join(ROOT, "av1-base_amd", "libav1mi.so")
-    if not os.path.exists(lib):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("av1mi_build", os.path.join(ROOT, "av1-base_amd", "build.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    import av1mi as m
-    return m
+    return host_build.library()
 
 
 def _bits(data, n):
@@ -110,12 +101,7 @@ def test_header_layout(av1mi, kw, cq):
 # ---------------------------------------------------------------- the rule header, compiled for the host
 @pytest.fixture(scope="module")
 def rule(tmp_path_factory):
-    cxx = next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++") or "") if c and os.path.exists(c)), None)
-    if not cxx:
-        pytest.skip("no clang++")
-    so = str(tmp_path_factory.mktemp("aq") / "libaqrule.so")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", os.path.join(ROOT, "tests", "host", "aq_rule_host.cpp"), "-o", so])
-    lib = C.CDLL(so)
+    lib = C.CDLL(host_build.build_shared(host_build.host_cxx(), os.path.join(ROOT, "tests", "host", "aq_rule_host.cpp"), tmp_path_factory.mktemp("aq") / "libaqrule.so"))
     lib.aq_log2_q4.argtypes = [C.c_uint]
     lib.aq_unit_energy.argtypes = [C.c_uint, C.c_uint, C.c_int]
     lib.aq_sb_energy.argtypes = [C.c_void_p, C.c_int]

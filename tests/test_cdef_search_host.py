@@ -4,11 +4,11 @@ frame header it implies (cdef_bits = k - 1 and 2^(k-1) strength pairs) and the A
 search's 24 errors per superblock against 16 oracle runs at fixed strengths, the candidate pool against P8.  All comparisons are exact."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
+
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "host", "cdef_pieces_host.cpp")
@@ -18,15 +18,7 @@ P8 = [0, 1, 2, 3, 4, 6, 8, 11]   # the pool's primary strengths (tests/test_cdef
 
 @pytest.fixture(scope="module")
 def av1mi():
-    lib = os.path.join(ROOT, "av1-base_amd", "libav1mi.so")
-    if not os.path.exists(lib):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("av1mi_build", os.path.join(ROOT, "av1-base_amd", "build.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    import av1mi as m
-    return m
+    return host_build.library()
 
 
 def _bits(data, n):
@@ -92,17 +84,12 @@ def test_cdef_search_layout(av1mi):
 # ---------------------------------------------------------------- the pieces on the host
 @pytest.fixture(scope="module")
 def cxx():
-    c = next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++") or "") if c and os.path.exists(c)), None)
-    if not c:
-        pytest.skip("no clang++")
-    return c
+    return host_build.host_cxx()
 
 
 @pytest.fixture(scope="module")
 def pieces(cxx, tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("cdef") / "libcdefpieces.so")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", SRC, "-o", so])
-    lib = C.CDLL(so)
+    lib = C.CDLL(host_build.build_shared(cxx, SRC, tmp_path_factory.mktemp("cdef") / "libcdefpieces.so"))
     lib.cdef_frame.argtypes = [U16P] * 6 + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]
     lib.cdef_frame.restype = None
     lib.cdef_search_errors.argtypes = [U16P] * 6 + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -247,31 +234,15 @@ def test_pool(pieces):
     assert len(seen) == 128
 
 
-def _build_main(cxx, exe, extra):
-    return subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-DCDEF_PIECES_MAIN"] + extra + [SRC, "-o", exe], capture_output=True, text=True)
-
-
 def test_standalone_program(cxx, tmp_path):
     """the same source as a program with its own main: the search's errors are the filter's at every candidate's strengths"""
-    exe = str(tmp_path / "cdef_main")
-    r = _build_main(cxx, exe, [])
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.run_program(cxx, SRC, tmp_path / "cdef_main", defines=["CDEF_PIECES_MAIN"])
     assert out.returncode == 0 and " 0 mismatches" in out.stdout, out.stdout + out.stderr
 
 
 def test_standalone_program_under_sanitizers(cxx, tmp_path):
     """... and under AddressSanitizer and UndefinedBehaviorSanitizer (host code only).  Skipped only where an empty program does not
     build and run under the sanitizers - their runtimes are not installed; a failure of the project's source is a failure"""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    probe_src, probe = str(tmp_path / "probe.cpp"), str(tmp_path / "probe")
-    open(probe_src, "w").write("int main() { return 0; }\n")
-    p = subprocess.run([cxx] + san + [probe_src, "-o", probe], capture_output=True, text=True)
-    if p.returncode or subprocess.run([probe], capture_output=True).returncode:
-        pytest.skip("the sanitizer runtimes are not installed")
-    exe = str(tmp_path / "cdef_main_san")
-    r = _build_main(cxx, exe, san)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.run_program(cxx, SRC, tmp_path / "cdef_main_san", defines=["CDEF_PIECES_MAIN"], sanitized=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert " 0 mismatches" in out.stdout

@@ -5,12 +5,11 @@ headers, parameter checks and ABI."""
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_build
 import deblock_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,30 +19,17 @@ U16P = C.POINTER(C.c_uint16)
 
 @pytest.fixture(scope="module")
 def av1mi():
-    lib = os.path.join(ROOT, "av1-base_amd", "libav1mi.so")
-    if not os.path.exists(lib):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("av1mi_build", os.path.join(ROOT, "av1-base_amd", "build.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    import av1mi as m
-    return m
+    return host_build.library()
 
 
 @pytest.fixture(scope="module")
 def cxx():
-    c = next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++") or "") if c and os.path.exists(c)), None)
-    if not c:
-        pytest.skip("no clang++")
-    return c
+    return host_build.host_cxx()
 
 
 @pytest.fixture(scope="module")
 def pieces(cxx, tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("lf") / "liblfpieces.so")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", SRC, "-o", so])
-    lib = C.CDLL(so)
+    lib = C.CDLL(host_build.build_shared(cxx, SRC, tmp_path_factory.mktemp("lf") / "liblfpieces.so"))
     lib.lf_frame.argtypes = [U16P, U16P, U16P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
     lib.lf_frame.restype = None
     lib.lf_tiles_against_frame.argtypes = [U16P, U16P, U16P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
@@ -138,32 +124,16 @@ def test_pieces_equal_the_oracle_and_tiles_equal_the_frame(pieces, oracle, tw, t
         assert pieces.lf_tiles_against_frame(*ptrs, w, h, tw, th, bd, bsl8.ctypes.data, lvl) == 0, "level %d" % lvl
 
 
-def _build_main(cxx, exe, extra):
-    return subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-DDEBLOCK_PIECES_MAIN"] + extra + [SRC, "-o", exe], capture_output=True, text=True)
-
-
 def test_standalone_program(cxx, tmp_path):
     """test 2, the same source as a program with its own main: it builds and finds no mismatch"""
-    exe = str(tmp_path / "lf_main")
-    r = _build_main(cxx, exe, [])
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.run_program(cxx, SRC, tmp_path / "lf_main", defines=["DEBLOCK_PIECES_MAIN"])
     assert out.returncode == 0 and " 0 mismatches" in out.stdout, out.stdout + out.stderr
 
 
 def test_standalone_program_under_sanitizers(cxx, tmp_path):
     """... and under AddressSanitizer and UndefinedBehaviorSanitizer (host code only).  Skipped only where an empty program does not
     build and run under the sanitizers - their runtimes are not installed; a failure of the project's source is a failure"""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    probe_src, probe = str(tmp_path / "probe.cpp"), str(tmp_path / "probe")
-    open(probe_src, "w").write("int main() { return 0; }\n")
-    p = subprocess.run([cxx] + san + [probe_src, "-o", probe], capture_output=True, text=True)
-    if p.returncode or subprocess.run([probe], capture_output=True).returncode:
-        pytest.skip("the sanitizer runtimes are not installed")
-    exe = str(tmp_path / "lf_main_san")
-    r = _build_main(cxx, exe, san)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.run_program(cxx, SRC, tmp_path / "lf_main_san", defines=["DEBLOCK_PIECES_MAIN"], sanitized=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert " 0 mismatches" in out.stdout
 

@@ -4,11 +4,11 @@ restatement of AV1 spec 7.11.2 that dav1d pins through tests/golden/): every mod
 a whole wave per block (luma) and half a wave (one plane of a chroma pair) - the prediction itself and the SAD against a source block."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
+
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "host", "intra_pieces_host.cpp")
@@ -21,12 +21,7 @@ SM_WEIGHTS = {64: [255, 248, 240, 233, 225, 218, 210, 203, 196, 189, 182, 176, 1
 
 @pytest.fixture(scope="module")
 def pieces(tmp_path_factory):
-    cxx = next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++") or "") if c and os.path.exists(c)), None)
-    if not cxx:
-        pytest.skip("no clang++ (the header uses ext_vector_type)")
-    so = str(tmp_path_factory.mktemp("pieces") / "libpieces.so")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", SRC, "-o", so])
-    lib = C.CDLL(so)
+    lib = C.CDLL(host_build.build_shared(host_build.host_cxx(), SRC, tmp_path_factory.mktemp("pieces") / "libpieces.so"))
     lib.pieces_run.restype = C.c_long
     lib.pieces_run.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     lib.pieces_magic.restype = C.c_uint

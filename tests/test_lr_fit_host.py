@@ -4,12 +4,11 @@ Python restatement - parameter table, solve, unit-code writer round trip - and t
 import ctypes as C
 import os
 import random
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_build
 import sgr_fit_ref as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,25 +16,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def av1mi():
-    lib = os.path.join(ROOT, "av1-base_amd", "libav1mi.so")
-    if not os.path.exists(lib):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("av1mi_build", os.path.join(ROOT, "av1-base_amd", "build.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    import av1mi as m
-    return m
+    return host_build.library()
 
 
 @pytest.fixture(scope="module")
 def rule(tmp_path_factory):
-    cxx = next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++") or "", shutil.which("g++") or "") if c and os.path.exists(c)), None)
-    if not cxx:
-        pytest.skip("no C++ compiler")
-    so = str(tmp_path_factory.mktemp("fit") / "libfitrule.so")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", os.path.join(ROOT, "tests", "host", "lr_fit_rule_host.cpp"), "-o", so])
-    lib = C.CDLL(so)
+    lib = C.CDLL(host_build.build_shared(host_build.host_cxx(gcc=True), os.path.join(ROOT, "tests", "host", "lr_fit_rule_host.cpp"), tmp_path_factory.mktemp("fit") / "libfitrule.so"))
     lib.fit_params.argtypes = [C.c_int, C.c_void_p]
     lib.fit_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     lib.fit_code.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_uint64)]

@@ -4,11 +4,10 @@ restatement (tests/lr_rd_ref.py); the restated writers through the repo's decode
 behaviour without a device."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import pytest
 
+import host_build
 import lr_rd_ref as ref
 import sgr_fit_ref
 import wiener_fit_ref
@@ -19,23 +18,12 @@ SRC = os.path.join(ROOT, "tests", "host", "lr_rate_rule_host.cpp")
 
 @pytest.fixture(scope="module")
 def av1mi():
-    lib = os.path.join(ROOT, "av1-base_amd", "libav1mi.so")
-    if not os.path.exists(lib):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("av1mi_build", os.path.join(ROOT, "av1-base_amd", "build.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    import av1mi as m
-    return m
+    return host_build.library()
 
 
 @pytest.fixture(scope="module")
 def cxx():
-    c = next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++") or "", shutil.which("g++") or "") if c and os.path.exists(c)), None)
-    if not c:
-        pytest.skip("no C++ compiler")
-    return c
+    return host_build.host_cxx(gcc=True)
 
 
 def _grid(lo, hi):
@@ -59,10 +47,6 @@ def _expected():
             lines.append("LAM %d %d :" % (bd, s) + "".join(" %d" % ref.lam(q, bd, s) for q in range(1, 256)))
     lines.append("BOUND %d" % (ref.lam(255, 10, 3) * ref.b16(42, 30)))
     return lines
-
-
-def _build(cxx, exe, extra):
-    return subprocess.run([cxx, "-O1", "-g", "-std=c++17"] + extra + [SRC, "-o", exe], capture_output=True, text=True)
 
 
 def test_type_costs_are_pinned():
@@ -128,10 +112,7 @@ def test_decide_rule():
 
 
 def test_standalone_program(cxx, tmp_path):
-    exe = str(tmp_path / "lr_rate_main")
-    r = _build(cxx, exe, [])
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.run_program(cxx, SRC, tmp_path / "lr_rate_main")
     assert out.returncode == 0, out.stdout[-500:] + out.stderr
     got, want = out.stdout.splitlines(), _expected()
     assert len(got) == len(want)
@@ -143,16 +124,7 @@ def test_standalone_program(cxx, tmp_path):
 def test_standalone_program_under_sanitizers(cxx, tmp_path):
     """... and under AddressSanitizer and UndefinedBehaviorSanitizer (host code only).  Skipped only where an empty program does not
     build and run under the sanitizers - their runtimes are not installed"""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    probe_src, probe = str(tmp_path / "probe.cpp"), str(tmp_path / "probe")
-    open(probe_src, "w").write("int main() { return 0; }\n")
-    p = subprocess.run([cxx] + san + [probe_src, "-o", probe], capture_output=True, text=True)
-    if p.returncode or subprocess.run([probe], capture_output=True).returncode:
-        pytest.skip("the sanitizer runtimes are not installed")
-    exe = str(tmp_path / "lr_rate_main_san")
-    r = _build(cxx, exe, san)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.run_program(cxx, SRC, tmp_path / "lr_rate_main_san", sanitized=True)
     assert out.returncode == 0, out.stdout[-500:] + out.stderr
     assert out.stdout.splitlines() == _expected()
 

@@ -4,11 +4,11 @@ centre code: reach, cost and key of every candidate of blocks at the frame's edg
 and of the reader of a leaf's motion, the pre-search's centre and reach, and the refinement's candidate sequence and cost.  The same
 program runs once more under AddressSanitizer and UndefinedBehaviorSanitizer."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_build
 import part_inter_ref as PR
 from test_part_inter_host import cxx  # noqa: F401  (the same compiler lookup)
 
@@ -164,10 +164,6 @@ def cases(tmp_path_factory):
     return path, want
 
 
-def _build(cxx, exe, extra):
-    return subprocess.run([cxx, "-O1", "-g", "-std=c++17"] + extra + [SRC, "-o", exe], capture_output=True, text=True)
-
-
 def _check(got, want):
     assert len(got) == len(want)
     for i, (g, w) in enumerate(zip(got, want)):
@@ -179,10 +175,7 @@ def _check(got, want):
 
 
 def test_standalone_program_equals_the_restatement(cxx, cases, tmp_path):  # noqa: F811
-    exe = str(tmp_path / "me_rule_host")
-    r = _build(cxx, exe, [])
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = subprocess.run([exe, cases[0]], capture_output=True, text=True)
+    out = host_build.run_program(cxx, SRC, tmp_path / "me_rule_host", args=[cases[0]])
     assert out.returncode == 0, out.stderr[-2000:]
     _check(out.stdout.split("\n")[:-1], cases[1])
 
@@ -190,15 +183,6 @@ def test_standalone_program_equals_the_restatement(cxx, cases, tmp_path):  # noq
 def test_standalone_program_under_sanitizers(cxx, cases, tmp_path):  # noqa: F811
     """... and under AddressSanitizer and UndefinedBehaviorSanitizer (host code only, run on its own).  Skipped only where an empty
     program does not build and run under the sanitizers - their runtimes are not installed"""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    probe_src, probe = str(tmp_path / "probe.cpp"), str(tmp_path / "probe")
-    open(probe_src, "w").write("int main() { return 0; }\n")
-    p = subprocess.run([cxx] + san + [probe_src, "-o", probe], capture_output=True, text=True)
-    if p.returncode or subprocess.run([probe], capture_output=True).returncode:
-        pytest.skip("the sanitizer runtimes are not installed")
-    exe = str(tmp_path / "me_rule_host_san")
-    r = _build(cxx, exe, san)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = subprocess.run([exe, cases[0]], capture_output=True, text=True)
+    out = host_build.run_program(cxx, SRC, tmp_path / "me_rule_host_san", args=[cases[0]], sanitized=True)
     assert out.returncode == 0, out.stdout[-500:] + out.stderr[-2000:]
     _check(out.stdout.split("\n")[:-1], cases[1])

@@ -4,12 +4,11 @@ remainder against 64, one to three superblocks each way - and every min_block_lo
 costs that tie exactly (S == cL), costs one off either way, and nodes without a valid candidate.  The same program runs once more under
 AddressSanitizer and UndefinedBehaviorSanitizer."""
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_build
 import part_inter_ref as PR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -63,10 +62,7 @@ def make_costs(rng, W, H, lo, hi, acq, sb_x, sb_y):
 
 @pytest.fixture(scope="module")
 def cxx():
-    c = next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++") or "", shutil.which("g++") or "") if c and os.path.exists(c)), None)
-    if not c:
-        pytest.skip("no C++ compiler")
-    return c
+    return host_build.host_cxx(gcc=True)
 
 
 @pytest.fixture(scope="module")
@@ -98,15 +94,8 @@ def cases(tmp_path_factory):
     return path, want
 
 
-def _build(cxx, exe, extra):
-    return subprocess.run([cxx, "-O1", "-g", "-std=c++17"] + extra + [SRC, "-o", exe], capture_output=True, text=True)
-
-
 def test_standalone_program_equals_the_numpy_rule(cxx, cases, tmp_path):
-    exe = str(tmp_path / "part_inter_host")
-    r = _build(cxx, exe, [])
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = subprocess.run([exe, cases[0]], capture_output=True, text=True)
+    out = host_build.run_program(cxx, SRC, tmp_path / "part_inter_host", args=[cases[0]])
     assert out.returncode == 0, out.stderr[-2000:]
     got = out.stdout.split("\n")[:-1]
     assert len(got) == len(cases[1])
@@ -117,15 +106,6 @@ def test_standalone_program_equals_the_numpy_rule(cxx, cases, tmp_path):
 def test_standalone_program_under_sanitizers(cxx, cases, tmp_path):
     """... and under AddressSanitizer and UndefinedBehaviorSanitizer (host code only, run on its own).  Skipped only where an empty
     program does not build and run under the sanitizers - their runtimes are not installed"""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    probe_src, probe = str(tmp_path / "probe.cpp"), str(tmp_path / "probe")
-    open(probe_src, "w").write("int main() { return 0; }\n")
-    p = subprocess.run([cxx] + san + [probe_src, "-o", probe], capture_output=True, text=True)
-    if p.returncode or subprocess.run([probe], capture_output=True).returncode:
-        pytest.skip("the sanitizer runtimes are not installed")
-    exe = str(tmp_path / "part_inter_host_san")
-    r = _build(cxx, exe, san)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = subprocess.run([exe, cases[0]], capture_output=True, text=True)
+    out = host_build.run_program(cxx, SRC, tmp_path / "part_inter_host_san", args=[cases[0]], sanitized=True)
     assert out.returncode == 0, out.stdout[-500:] + out.stderr[-2000:]
     assert out.stdout.split("\n")[:-1] == cases[1]

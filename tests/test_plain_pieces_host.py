@@ -4,12 +4,11 @@ tests/test_intra_pieces.py covers: N = 8, 16, 32, 64 at 8 and 10 bit, a whole wa
 all zero and all maximum, and a corner above and below both neighbours - Paeth's three branches - the prediction itself and the SAD."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_build
 from test_intra_pieces import SM_WEIGHTS
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,12 +18,7 @@ SMOOTH, SMOOTH_V, SMOOTH_H, PAETH = 9, 10, 11, 12
 
 @pytest.fixture(scope="module")
 def pieces(tmp_path_factory):
-    cxx = next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++") or "") if c and os.path.exists(c)), None)
-    if not cxx:
-        pytest.skip("no clang++ (the header uses ext_vector_type)")
-    so = str(tmp_path_factory.mktemp("plain") / "libpieces.so")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", SRC, "-o", so])
-    lib = C.CDLL(so)
+    lib = C.CDLL(host_build.build_shared(host_build.host_cxx(), SRC, tmp_path_factory.mktemp("plain") / "libpieces.so"))
     lib.pieces_run.restype = C.c_long
     lib.pieces_run.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     return lib

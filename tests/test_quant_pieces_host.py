@@ -5,11 +5,11 @@ extent - transform sizes 4 .. 64, 8 and 10 bit, the lowest quantiser index, 120 
 +-2^16 plus the extremes that reach the 0x7FFF cap, every (row, column) at every coded width."""
 import ctypes as C
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
+
+import host_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "host", "quant_pieces_host.cpp")
@@ -18,17 +18,12 @@ QIDX = (1, 120, 255)
 
 @pytest.fixture(scope="module")
 def cxx():
-    c = next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++") or "") if c and os.path.exists(c)), None)
-    if not c:
-        pytest.skip("no clang++")
-    return c
+    return host_build.host_cxx()
 
 
 @pytest.fixture(scope="module")
 def quant(cxx, tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("quant") / "libquantpieces.so")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", SRC, "-o", so])
-    lib = C.CDLL(so)
+    lib = C.CDLL(host_build.build_shared(cxx, SRC, tmp_path_factory.mktemp("quant") / "libquantpieces.so"))
     lib.qp_sweep.restype = C.c_long
     lib.qp_sweep.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_long)]
     lib.qp_positions.restype = C.c_long
@@ -62,30 +57,14 @@ def test_scan_key_orders_positions_as_the_oracle_scan(quant, oracle, cw):
     assert np.array_equal(np.argsort(keys, kind="stable"), scan)
 
 
-def _build_main(cxx, exe, extra):
-    return subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-DQUANT_PIECES_MAIN"] + extra + [SRC, "-o", exe], capture_output=True, text=True)
-
-
 def test_standalone_program(cxx, tmp_path):
-    exe = str(tmp_path / "quant_main")
-    r = _build_main(cxx, exe, [])
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.run_program(cxx, SRC, tmp_path / "quant_main", defines=["QUANT_PIECES_MAIN"])
     assert out.returncode == 0 and " 0 mismatches" in out.stdout, out.stdout + out.stderr
 
 
 def test_standalone_program_under_sanitizers(cxx, tmp_path):
     """... and under AddressSanitizer and UndefinedBehaviorSanitizer (host code only).  Skipped only where an empty program does not
     build and run under the sanitizers - their runtimes are not installed; a failure of the project's source is a failure"""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    probe_src, probe = str(tmp_path / "probe.cpp"), str(tmp_path / "probe")
-    open(probe_src, "w").write("int main() { return 0; }\n")
-    p = subprocess.run([cxx] + san + [probe_src, "-o", probe], capture_output=True, text=True)
-    if p.returncode or subprocess.run([probe], capture_output=True).returncode:
-        pytest.skip("the sanitizer runtimes are not installed")
-    exe = str(tmp_path / "quant_main_san")
-    r = _build_main(cxx, exe, san)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.run_program(cxx, SRC, tmp_path / "quant_main_san", defines=["QUANT_PIECES_MAIN"], sanitized=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert " 0 mismatches" in out.stdout

@@ -6,12 +6,11 @@ import ctypes as C
 import itertools
 import os
 import random
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_build
 import lr_ref
 import wiener_fit_ref as ref
 
@@ -22,30 +21,17 @@ CODE_BITS = 64   # the container of a unit's code: two 32-bit words (Av1miLrWfit
 
 @pytest.fixture(scope="module")
 def av1mi():
-    lib = os.path.join(ROOT, "av1-base_amd", "libav1mi.so")
-    if not os.path.exists(lib):
-        import importlib.util
-        spec = importlib.util.spec_from_file_location("av1mi_build", os.path.join(ROOT, "av1-base_amd", "build.py"))
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)
-        mod.build()
-    import av1mi as m
-    return m
+    return host_build.library()
 
 
 @pytest.fixture(scope="module")
 def cxx():
-    c = next((c for c in ("/opt/rocm/lib/llvm/bin/clang++", shutil.which("clang++") or "", shutil.which("g++") or "") if c and os.path.exists(c)), None)
-    if not c:
-        pytest.skip("no C++ compiler")
-    return c
+    return host_build.host_cxx(gcc=True)
 
 
 @pytest.fixture(scope="module")
 def rule(cxx, tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("wfit") / "libwfitrule.so")
-    subprocess.check_call([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", SRC, "-o", so])
-    lib = C.CDLL(so)
+    lib = C.CDLL(host_build.build_shared(cxx, SRC, tmp_path_factory.mktemp("wfit") / "libwfitrule.so"))
     lib.wf_fit.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.wf_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.wf_code.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
@@ -223,31 +209,15 @@ def test_code_writer_round_trip(rule):
 
 
 # ---------------------------------------------------------------- the stand-alone program
-def _build_main(cxx, exe, extra):
-    return subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-DWIENER_FIT_RULE_MAIN"] + extra + [SRC, "-o", exe], capture_output=True, text=True)
-
-
 def test_standalone_program(cxx, tmp_path):
-    exe = str(tmp_path / "wfit_main")
-    r = _build_main(cxx, exe, [])
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.run_program(cxx, SRC, tmp_path / "wfit_main", defines=["WIENER_FIT_RULE_MAIN"])
     assert out.returncode == 0 and " 0 failures" in out.stdout, out.stdout + out.stderr
 
 
 def test_standalone_program_under_sanitizers(cxx, tmp_path):
     """... and under AddressSanitizer and UndefinedBehaviorSanitizer (host code only; a signed overflow in the rule would stop it).
     Skipped only where an empty program does not build and run under the sanitizers - their runtimes are not installed"""
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
-    probe_src, probe = str(tmp_path / "probe.cpp"), str(tmp_path / "probe")
-    open(probe_src, "w").write("int main() { return 0; }\n")
-    p = subprocess.run([cxx] + san + [probe_src, "-o", probe], capture_output=True, text=True)
-    if p.returncode or subprocess.run([probe], capture_output=True).returncode:
-        pytest.skip("the sanitizer runtimes are not installed")
-    exe = str(tmp_path / "wfit_main_san")
-    r = _build_main(cxx, exe, san)
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True)
+    out = host_build.run_program(cxx, SRC, tmp_path / "wfit_main_san", defines=["WIENER_FIT_RULE_MAIN"], sanitized=True)
     assert out.returncode == 0, out.stdout + out.stderr
     assert " 0 failures" in out.stdout
 
