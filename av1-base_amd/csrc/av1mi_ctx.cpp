@@ -179,8 +179,6 @@ void bind_workspace(Av1miDevParams &P, const Resolved &r, const Workspace &w) {
 
 using namespace av1mi;
 
-extern "C" {
-
 // The four streams of a context come from a process-wide pool and go back to it when the context is destroyed.  The runtime maps
 // streams onto a few hardware queues in creation order, and after contexts had been created and destroyed a number of times a new
 // context's chain stream could share a queue with its own search stream, whose launches for the whole chunk are queued up front: a
@@ -191,7 +189,7 @@ struct StreamSet { hipStream_t s[4]; };
 std::mutex g_stream_mu;
 std::vector<std::pair<int, StreamSet>> g_stream_pool;   // (device, set)
 }  // namespace
-void av1mi_host_release_streams(void) {
+void av1mi::release_streams() {
   std::vector<std::pair<int, StreamSet>> all;
   { std::lock_guard<std::mutex> lk(g_stream_mu); all.swap(g_stream_pool); }
   for (auto &e : all) {
@@ -199,6 +197,12 @@ void av1mi_host_release_streams(void) {
     for (auto st : e.second.s) if (st) (void)hipStreamDestroy(st);
   }
 }
+
+// A context that goes back to av1mi_encode_file's cache forgets the capacity multiplier its last job's content raised (it would
+// otherwise size - or, at the limit, refuse - an unrelated job's workspace by it); the next chunk reallocates at scale 1.
+void av1mi::recycle_ctx(av1mi_ctx *c) { if (c) c->cap_scale = 1; }
+
+extern "C" {
 
 int av1mi_ctx_create(int device_id, av1mi_ctx **out) {
   if (!out) return AV1MI_E_INVALID_ARG;
@@ -263,10 +267,6 @@ void av1mi_ctx_destroy(av1mi_ctx *c) {
   delete c;
 }
 
-// A context that goes back to av1mi_encode_file's cache forgets the capacity multiplier its last job's content raised (it would
-// otherwise size - or, at the limit, refuse - an unrelated job's workspace by it); the next chunk reallocates at scale 1.
-void av1mi_host_ctx_recycle(av1mi_ctx *c) { if (c) c->cap_scale = 1; }
-
 const char *av1mi_last_error(const av1mi_ctx *c) { return c ? c->err.c_str() : "no context"; }
 
 // Bitstream buffers handed to the caller (av1mi_buf.data) are page-locked blocks from a process-wide pool: the packed chunk is
@@ -279,7 +279,7 @@ std::vector<std::pair<void *, size_t>> g_pin_out;    // handed out: (block, capa
 std::vector<std::pair<void *, size_t>> g_pin_free;   // waiting for the next chunk
 constexpr size_t PIN_FREE_MAX_BYTES = (size_t)1 << 30;
 // parked blocks: a job with w workers has up to 2 w finished chunks waiting for the writer, so the bound follows the largest worker
-// count seen (av1mi_host_expect_blocks) - freeing a block is hipHostFree, which synchronises the whole device
+// count seen (expect_blocks) - freeing a block is hipHostFree, which synchronises the whole device
 std::atomic<size_t> g_pin_free_max_blocks{16};
 }  // namespace
 }  // extern "C"
@@ -305,18 +305,18 @@ void *av1mi::pin_acquire(size_t bytes) {
   return p;
 }
 
-extern "C" {
-
-void av1mi_host_expect_blocks(unsigned n) {
+void av1mi::expect_blocks(unsigned n) {
   size_t cur = g_pin_free_max_blocks.load();
   while (n > cur && n <= 256 && !g_pin_free_max_blocks.compare_exchange_weak(cur, n)) { }
 }
 
-void av1mi_host_release_buffers(void) {
+void av1mi::release_buffers() {
   std::vector<std::pair<void *, size_t>> all;
   { std::lock_guard<std::mutex> lk(g_pin_mu); all.swap(g_pin_free); }
   for (auto &b : all) (void)hipHostFree(b.first);
 }
+
+extern "C" {
 
 void av1mi_free(void *p) {
   if (!p) return;

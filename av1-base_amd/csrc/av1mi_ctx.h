@@ -147,6 +147,11 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames);
 void bind_workspace(Av1miDevParams &P, const Resolved &r, const Workspace &w);
 // a page-locked block of the process-wide pool for a chunk's bitstream (av1mi_free puts it back); null: none to be had
 void *pin_acquire(size_t bytes);
+// What av1mi_file.cpp's job and caches need of the context and the two pools:
+void recycle_ctx(av1mi_ctx *c);   // a context on its way into the cache of idle contexts
+void expect_blocks(unsigned n);   // so many page-locked blocks may wait for a job's writer at once: park that many
+void release_streams();           // destroys the stream sets destroyed contexts left in the pool
+void release_buffers();           // frees the page-locked blocks av1mi_free() put back
 
 }  // namespace av1mi
 

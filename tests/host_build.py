@@ -10,6 +10,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "tests", "host")
 SANITIZE = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+THREAD_SANITIZE = ["-fsanitize=thread"]
 
 
 def host_cxx(gcc=False):
@@ -34,23 +35,28 @@ def build_program(cxx, sources, exe, defines=(), extra=()):
                           capture_output=True, text=True)
 
 
-def sanitizers_work(cxx, tmp_path):
+def sanitizers_work(cxx, tmp_path, flags=SANITIZE):
     """whether an empty program builds and runs under the sanitizers here, i.e. their runtimes are installed"""
     probe_src, probe = str(tmp_path / "probe.cpp"), str(tmp_path / "probe")
     open(probe_src, "w").write("int main() { return 0; }\n")
-    p = subprocess.run([cxx] + SANITIZE + [probe_src, "-o", probe], capture_output=True, text=True)
+    p = subprocess.run([cxx] + list(flags) + [probe_src, "-o", probe], capture_output=True, text=True)
     return not p.returncode and not subprocess.run([probe], capture_output=True).returncode
 
 
-def run_program(cxx, sources, exe, args=(), defines=(), sanitized=False):
+def run_program(cxx, sources, exe, args=(), defines=(), sanitized=False, extra=(), timeout=None):
     """Builds the stand-alone program `exe` (a path under the test's tmp_path) and runs it; returns the run's CompletedProcess.  The
-    build failing is a failure.  sanitized: under the sanitizers - skipped only where an empty program does not build and run under
-    them; a failure of the project's source is a failure."""
-    if sanitized and not sanitizers_work(cxx, exe.parent):
+    build failing is a failure.  sanitized: under the sanitizers - True for SANITIZE, or a set of flags of the caller's such as
+    THREAD_SANITIZE - skipped only where an empty program does not build and run under them; a failure of the project's source is a
+    failure.  extra: further compiler flags.  timeout: seconds the run may take; running out of them is a failure."""
+    flags = SANITIZE if sanitized is True else list(sanitized or ())
+    if flags and not sanitizers_work(cxx, exe.parent, flags):
         pytest.skip("the sanitizer runtimes are not installed")
-    r = build_program(cxx, sources, exe, defines, SANITIZE if sanitized else ())
+    r = build_program(cxx, sources, exe, defines, list(flags) + list(extra))
     assert r.returncode == 0, r.stderr[-2000:]
-    return subprocess.run([str(exe)] + [str(a) for a in args], capture_output=True, text=True)
+    try:
+        return subprocess.run([str(exe)] + [str(a) for a in args], capture_output=True, text=True, timeout=timeout)
+    except subprocess.TimeoutExpired:
+        pytest.fail("%s did not finish within %s s" % (os.path.basename(str(exe)), timeout))
 
 
 def _list(sources):

@@ -6,6 +6,8 @@ import os
 import numpy as np
 import pytest
 
+from mkv_ref import _ebml
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -753,21 +755,6 @@ def test_4k_every_optional_tool_equals_oracle(av1mi, ctx, oracle):
     assert recon.tobytes() == b"".join(raw_of(r, bd) for r in recs)
 
 
-def _ebml(buf, pos, end):
-    """yield (id, payload_start, payload_end) of the EBML elements in buf[pos:end]"""
-    while pos < end:
-        b = buf[pos]
-        n = 1 + (8 - b.bit_length())
-        eid = int.from_bytes(buf[pos:pos + n], "big")
-        pos += n
-        b = buf[pos]
-        n = 1 + (8 - b.bit_length())
-        size = int.from_bytes(buf[pos:pos + n], "big") & ((1 << (7 * n)) - 1)
-        pos += n
-        yield eid, pos, pos + size
-        pos += size
-
-
 def test_encode_file_matroska_and_obu_outputs(av1mi, oracle, tmp_path):
     """output_path ending in .mkv (the reference's job output, jobs.rs:187-188): EBML header, Segment with Info,
     one V_AV1 track whose CodecPrivate is the av1C record + sequence header, one Cluster per key frame with a
@@ -966,6 +953,32 @@ def test_encode_file_many_chunks_few_workers(av1mi, oracle, tmp_path):
         assert rep.frames == n and rep.chunks == n
         outs.append(out.read_bytes())
     assert outs[0] == outs[1]
+
+
+def test_encode_file_failure_mid_job_leaves_the_process_sound(av1mi, oracle, tmp_path):
+    """A job that fails with chunks in flight - a host-side format error: 100 bytes of a seventh frame behind six whole ones, one frame per
+    chunk, two workers - leaves neither an output nor a temporary file, and the process encodes the good clip afterwards to the bytes it
+    gave before (the failed job's contexts are destroyed, not recycled); the caches are released at the end."""
+    w, h, n = 72, 56, 6
+    fr = [raw_of(oracle.synthclip_frame(w, h, 8, seed=85, t=t), 8) for t in range(n + 1)]
+    good = b"YUV4MPEG2 W%d H%d F30:1 Ip A1:1 C420jpeg\n" % (w, h) + b"".join(b"FRAME\n" + f for f in fr[:n])
+    (tmp_path / "good.y4m").write_bytes(good)
+    (tmp_path / "bad.y4m").write_bytes(good + b"FRAME\n" + fr[n][:94])   # marker and 94 bytes: 100 trailing bytes
+    plan = av1mi.derive_plan(8, workers_override=2)
+
+    def encode(name):
+        out = tmp_path / (name + ".obu")
+        rep = av1mi.run_mi355x(av1mi.EncodeParams(tmp_path / "good.y4m", out, tmp_path, plan, chunk_frames=1))
+        assert rep.frames == n and rep.chunks == n
+        return out.read_bytes()
+
+    first = encode("first")
+    with pytest.raises(av1mi.EncodeFailed) as ei:
+        av1mi.run_mi355x(av1mi.EncodeParams(tmp_path / "bad.y4m", tmp_path / "bad.obu", tmp_path, plan, chunk_frames=1))
+    assert ei.value.code == av1mi.E_FORMAT
+    assert not (tmp_path / "bad.obu").exists() and not list(tmp_path.glob("*.tmp.*"))
+    assert encode("again") == first
+    av1mi.release_caches()
 
 
 @pytest.mark.parametrize("w,h,bd,n,bs,keyint", [(200, 120, 8, 2, 5, 1), (328, 248, 10, 2, 4, 1), (72, 104, 8, 2, 5, 1), (648, 360, 8, 3, 5, 240),
