@@ -37,7 +37,7 @@ E_INVALID_ARG, E_NO_DEVICE, E_HIP, E_OOM, E_OVERFLOW, E_FORMAT, E_UNSUPPORTED = 
 # every symbol include/av1mi.h declares
 ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", "av1mi_last_error", "av1mi_encode_chunk",
                "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units", "av1mi_sym_order_result", "av1mi_sym_order_tiles", "av1mi_inter_partition_result", "av1mi_inter_partition_units",
-               "av1mi_lr_rd_result", "av1mi_lr_rd_units", "av1mi_temporal_filter"]
+               "av1mi_lr_rd_result", "av1mi_lr_rd_units", "av1mi_temporal_filter", "av1mi_tpl_analysis"]
 
 
 class Params(C.Structure):
@@ -115,6 +115,8 @@ _lib.av1mi_struct_sizes.restype = C.c_uint32
 ABI_VERSION = 8   # include/av1mi.h: AV1MI_ABI_VERSION this mirror was written against
 _lib.av1mi_aq_qindex.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8)]
 _lib.av1mi_temporal_filter.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_uint32)]
+_lib.av1mi_tpl_analysis.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint16), C.POINTER(C.c_uint32)]
 _lib.av1mi_lf_search_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
 _lib.av1mi_lr_fit_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint64)]
 _lib.av1mi_lr_fit_units.argtypes = [C.c_void_p]
@@ -169,6 +171,20 @@ AQ_MAX_STRENGTH = 4
 def cq_aq(cq, strength):
     """include/av1mi.h: AV1MI_CQ_AQ - the cq_level field with the strength of the adaptive quantisation in bits 8-10"""
     return (cq & 0xFF) | ((strength & 7) << 8)
+
+
+TPL_MAX_STRENGTH = 4
+
+
+def cq_aq_tpl(cq, aq, tpl):
+    """include/av1mi.h: AV1MI_CQ_AQ_TPL - the cq_level field with the strengths of the adaptive quantisation's spatial term in bits 8-10
+    and of its temporal term in bits 12-14"""
+    return cq_aq(cq, aq) | ((tpl & 7) << 12)
+
+
+def tpl_strength_of(v):
+    """include/av1mi.h: AV1MI_TPL_STRENGTH"""
+    return (v >> 12) & 7
 
 
 def cq_level_of(v):
@@ -237,9 +253,9 @@ def lr_unit_grid(width, height, shift=0):
     return max((height + u // 2) // u, 1), max((width + u // 2) // u, 1)
 
 
-def default_params(width, height, bit_depth=8, aq_strength=None, lr_fit=None, lr_wiener_fit=False, lr_unit_shift=0, lr_rd=None, tf_frames=None,
+def default_params(width, height, bit_depth=8, aq_strength=None, tpl_strength=None, lr_fit=None, lr_wiener_fit=False, lr_unit_shift=0, lr_rd=None, tf_frames=None,
                    tf_strength=None, **kw):
-    """aq_strength: packed into cq_level beside the CQ level (cq_aq); lr_fit: True or a mask of parameter sets, packed into enable_lr
+    """aq_strength, tpl_strength: packed into cq_level beside the CQ level (cq_aq_tpl); lr_fit: True or a mask of parameter sets, packed into enable_lr
     (lr_fit_field); lr_wiener_fit: True sets enable_lr's bit 10 (LR_WIENER_FIT); lr_unit_shift: 1 / 2 sets enable_lr's bits 12-13
     (LR_UNIT_128 / LR_UNIT_256); lr_rd: a scale s = 0 .. 3 sets the rate term of the unit decisions (lr_rd_field); tf_frames, tf_strength:
     the key frames' temporal filter, packed into me_presearch beside the pre-search's switch (me_tf); every other keyword sets the
@@ -256,8 +272,9 @@ def default_params(width, height, bit_depth=8, aq_strength=None, lr_fit=None, lr
         kw["enable_lr"] = kw.get("enable_lr", p.enable_lr) | ((int(lr_unit_shift) & 3) << 12)
     if lr_rd is not None and lr_rd is not False:
         kw["enable_lr"] = kw.get("enable_lr", p.enable_lr) | lr_rd_field(int(lr_rd))
-    if aq_strength is not None:
-        kw["cq_level"] = cq_aq(kw.get("cq_level", p.cq_level), aq_strength)
+    if aq_strength is not None or tpl_strength is not None:
+        cq = kw.get("cq_level", p.cq_level)
+        kw["cq_level"] = cq_aq_tpl(cq, aq_strength_of(cq) if aq_strength is None else aq_strength, tpl_strength_of(cq) if tpl_strength is None else tpl_strength)
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)
@@ -377,6 +394,26 @@ class Context:
         fptr, keep = _frames_ptr(frames, on_device)
         rc = _lib.av1mi_aq_qindex(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0, out.ctypes.data_as(C.POINTER(C.c_uint8)))
         _raise_for(rc, self.last_error())
+        return out
+
+    def tpl_analysis(self, params, frames, n_frames, on_device=False):
+        """The temporal-dependency analysis alone (include/av1mi.h: av1mi_tpl_analysis); frames as for scene_cuts.  Returns a dict of
+        numpy arrays: intra, inter, key (uint32) and flow (uint64) as [frame][block row][block column] over the 16x16 blocks of the coded
+        size, beta (uint16) as [frame][superblock row][superblock column], and mean_beta (int)."""
+        import numpy as np
+        cw, ch = (params.width + 7) & ~7, (params.height + 7) & ~7
+        nbx, nby, sbc, sbr = (cw + 15) // 16, (ch + 15) // 16, (cw + 63) // 64, (ch + 63) // 64
+        out = {k: np.zeros((n_frames, nby, nbx), dtype=np.uint32) for k in ("intra", "inter", "key")}
+        out["flow"] = np.zeros((n_frames, nby, nbx), dtype=np.uint64)
+        out["beta"] = np.zeros((n_frames, sbr, sbc), dtype=np.uint16)
+        mean = C.c_uint32(0)
+        fptr, keep = _frames_ptr(frames, on_device)
+        u32 = C.POINTER(C.c_uint32)
+        rc = _lib.av1mi_tpl_analysis(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0, out["intra"].ctypes.data_as(u32),
+                                     out["inter"].ctypes.data_as(u32), out["key"].ctypes.data_as(u32), out["flow"].ctypes.data_as(C.POINTER(C.c_uint64)),
+                                     out["beta"].ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(mean))
+        _raise_for(rc, self.last_error())
+        out["mean_beta"] = int(mean.value)
         return out
 
     def temporal_filter(self, params, frames, n_frames, on_device=False, out_ptr=None, want_mv=True):

@@ -33,9 +33,9 @@ AV1MI_AQ_HD inline int av1mi_aq_unit_energy(uint32_t S, uint32_t Q, int bit_dept
 }
 // rounded mean: E of a superblock from the sum over its n units, M of a frame from the sum over its N superblocks
 AV1MI_AQ_HD inline int av1mi_aq_mean(uint32_t sum, uint32_t n) { return (int)((sum + n / 2) / n); }
-// d of a superblock, clamped so that base + 4 d stays inside 1 .. 255
-AV1MI_AQ_HD inline int av1mi_aq_delta(int strength, int E, int M, int base) {
-  const int t = strength * (E - M), a = ((t < 0 ? -t : t) + 16) >> 5;
+// d of a superblock from its t, clamped so that base + 4 d stays inside 1 .. 255 (tpl_rule.h adds its term to t and comes here too)
+AV1MI_AQ_HD inline int av1mi_aq_delta_of(int t, int base) {
+  const int a = ((t < 0 ? -t : t) + 16) >> 5;
   int d = t < 0 ? -a : a;
   int lo = -((base - 1) / 4), hi = (255 - base) / 4;
   lo = lo < -AV1MI_AQ_MAX_DELTA ? -AV1MI_AQ_MAX_DELTA : lo;
@@ -43,6 +43,7 @@ AV1MI_AQ_HD inline int av1mi_aq_delta(int strength, int E, int M, int base) {
   d = d < lo ? lo : (d > hi ? hi : d);
   return d;
 }
+AV1MI_AQ_HD inline int av1mi_aq_delta(int strength, int E, int M, int base) { return av1mi_aq_delta_of(strength * (E - M), base); }
 AV1MI_AQ_HD inline int av1mi_aq_qindex_of(int strength, int E, int M, int base) { return base + 4 * av1mi_aq_delta(strength, E, M, base); }
 
 #endif

@@ -17,6 +17,7 @@
 #include "wiener_fit_rule.h"
 #include "deblock_pieces.h"
 #include "aq_rule.h"
+#include "tpl_rule.h"
 #include "part_inter_rule.h"
 
 namespace av1mi {
@@ -115,9 +116,15 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   }
   // the temporal filter's keys, on first use (and when a chunk has more key frames or followers than any before)
   if (r.tf_frames) HIPCHK(c, ws_grow(w, w.d_tf_mv, w.tf_mv_bytes, tf_mv_entries(r, n_frames) * sizeof(uint32_t)));
-  if (r.aq && !w.d_aq_map) {
+  if (dq_on(r) && !w.d_aq_map) {
     HIPCHK(c, ws_alloc(w, w.d_aq_act, nf * nsb * sizeof(uint16_t)));
     HIPCHK(c, ws_alloc(w, w.d_aq_map, nf * nsb));
+  }
+  if (r.tpl && !w.d_tpl_beta) {   // (beta last: every one of the five stands once it does)
+    const size_t nb = (size_t)av1mi_tpl_blocks(r.cw) * av1mi_tpl_blocks(r.ch);
+    for (uint32_t **b : { &w.d_tpl_intra, &w.d_tpl_inter, &w.d_tpl_key }) HIPCHK(c, ws_alloc(w, *b, nf * nb * sizeof(uint32_t)));
+    HIPCHK(c, ws_alloc(w, w.d_tpl_flow, av1mi_tpl_flow_entries(r.cw, r.ch, (int)nf) * sizeof(unsigned long long)));
+    HIPCHK(c, ws_alloc(w, w.d_tpl_beta, nf * nsb * sizeof(uint16_t)));
   }
   if (p.cdef_search && (!w.d_cdef_err || !w.d_cdef_idx || !w.d_cdef_sel)) {
     HIPCHK(c, ws_alloc(w, w.d_cdef_err, nf * nsb * 24 * sizeof(unsigned long long)));
@@ -150,7 +157,7 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   if (p.enable_qm && r.qm_level < 15) {
     // one slice of steps, or with adaptive quantisation one per quantiser slot (make_qm_table)
     if (!w.d_qm) HIPCHK(c, ws_alloc(w, w.d_qm, AV1MI_AQ_SLOTS * 2 * AV1MI_QM_PLANE * sizeof(Av1miQmEntry)));
-    const int slices = r.aq ? AV1MI_AQ_SLOTS : 1;
+    const int slices = dq_on(r) ? AV1MI_AQ_SLOTS : 1;
     const int key = (slices << 24) | (r.qm_level << 16) | (r.qidx << 4) | (int)p.bit_depth;
     if (w.qm_key != key) {
       w.h_qm = make_qm_table(r);
@@ -167,7 +174,7 @@ void bind_workspace(Av1miDevParams &P, const Resolved &r, const Workspace &w) {
   const av1mi_params &p = r.p;
   if (p.enable_qm && r.qm_level < 15) P.qm_tab = w.d_qm;
   if (p.partition_search) P.part_map = w.d_part;
-  if (r.aq) P.aq_map = w.d_aq_map;
+  if (dq_on(r)) P.aq_map = w.d_aq_map;
   if (p.cdef_search) { P.cdef_err = w.d_cdef_err; P.cdef_idx = w.d_cdef_idx; P.cdef_sel = w.d_cdef_sel; }
   if (p.deblock == 2) { P.lf_err = w.d_lf_err; P.lf_sel = w.d_lf_sel; }
   if (r.lr_fit_mask) P.lr_fit_code = w.fit.code;
@@ -453,15 +460,42 @@ int av1mi_scene_cuts(av1mi_ctx *c, const av1mi_params *params, const void *frame
   return AV1MI_OK;
 }
 
-// The adaptive quantisation's decision alone: the same two launches the encoder runs on a chunk's source (av1mi_launch_aq), on buffers of
-// the call's own.
+}  // extern "C"
+
+namespace {
+// The temporal-dependency analysis of a stand-alone pass: its five buffers, the flow cleared, and the launches (av1mi_launch_tpl) on
+// `src`, n frames at the coded size taken as one chunk.  What failed is in t.e.
+struct TplBuffers {
+  uint32_t *intra = nullptr, *inter = nullptr, *key = nullptr;
+  unsigned long long *flow = nullptr;
+  uint16_t *beta = nullptr;
+  size_t n_blk = 0, n_flow = 0;
+  const unsigned long long *beta_sum() const { return flow + n_flow - 1; }
+};
+void run_tpl(PassBuffers &t, const Resolved &r, const Av1miDevParams &P, const void *src, uint32_t n_frames, TplBuffers &b) {
+  b.n_flow = av1mi_tpl_flow_entries(r.cw, r.ch, (int)n_frames);
+  b.n_blk = b.n_flow - 1;
+  t.alloc(b.intra, b.n_blk * sizeof(uint32_t));
+  t.alloc(b.inter, b.n_blk * sizeof(uint32_t));
+  t.alloc(b.key, b.n_blk * sizeof(uint32_t));
+  t.alloc(b.flow, b.n_flow * sizeof(unsigned long long));
+  t.alloc(b.beta, (size_t)n_frames * r.sb_cols * r.sb_rows * sizeof(uint16_t));
+  if (t.ok()) t.e = hipMemsetAsync(b.flow, 0, b.n_flow * sizeof(unsigned long long), t.stream);
+  if (t.ok()) t.e = av1mi_launch_tpl(&P, src, b.intra, b.inter, b.key, b.flow, b.beta, t.stream);
+}
+}  // namespace
+
+extern "C" {
+
+// The adaptive quantisation's decision alone: the same launches the encoder runs on a chunk's source (av1mi_launch_tpl with a temporal
+// strength, av1mi_launch_aq), on buffers of the call's own.
 int av1mi_aq_qindex(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, uint8_t *qindex) {
   if (!c || !frames || !qindex || n_frames == 0) return AV1MI_E_INVALID_ARG;
   Resolved r;
   int rc = resolve(params, &r);
   if (rc) { set_err(c, "invalid parameters"); return rc; }
   const size_t nsb = (size_t)r.sb_cols * r.sb_rows, n_map = (size_t)n_frames * nsb;
-  if (!r.aq) { memset(qindex, r.qidx, n_map); return AV1MI_OK; }
+  if (!dq_on(r)) { memset(qindex, r.qidx, n_map); return AV1MI_OK; }
   if (frames_on_device && ((uintptr_t)frames & 15)) { set_err(c, "device frames must be 16-byte aligned"); return AV1MI_E_INVALID_ARG; }
   HIPCHK(c, hipSetDevice(c->device));
   const Av1miDevParams P = dev_params(r, n_frames, 1);
@@ -469,12 +503,42 @@ int av1mi_aq_qindex(av1mi_ctx *c, const av1mi_params *params, const void *frames
   PassBuffers t(s);
   uint16_t *d_act = nullptr;
   uint8_t *d_map = nullptr;
+  TplBuffers tpl;
   t.alloc(d_act, n_map * sizeof(uint16_t));
   t.alloc(d_map, n_map);
   const void *src = coded_frames(t, r, frames, n_frames, frames_on_device);   // the rule reads the coded size
-  if (t.ok()) t.e = av1mi_launch_aq(&P, src, d_act, d_map, r.aq, s);
+  if (r.tpl) run_tpl(t, r, P, src, n_frames, tpl);
+  if (t.ok()) t.e = av1mi_launch_aq(&P, src, d_act, d_map, r.aq, tpl.beta, r.tpl ? tpl.beta_sum() : nullptr, r.tpl, s);
   if (t.ok()) t.e = hipMemcpyAsync(qindex, d_map, n_map, hipMemcpyDeviceToHost, s);
   return t.finish(c, "adaptive-quantisation");
+}
+
+// The temporal-dependency analysis alone: the launches the encoder runs on a chunk's source (av1mi_launch_tpl), on buffers of the call's own.
+int av1mi_tpl_analysis(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, uint32_t *intra,
+                       uint32_t *inter, uint32_t *key, uint64_t *flow, uint16_t *beta, uint32_t *mean_beta) {
+  if (!c || !frames || n_frames == 0) return AV1MI_E_INVALID_ARG;
+  Resolved r;
+  int rc = resolve(params, &r);
+  if (rc || !r.tpl) { set_err(c, rc ? "invalid parameters" : "the temporal strength is 0"); return rc ? rc : AV1MI_E_INVALID_ARG; }
+  if (frames_on_device && ((uintptr_t)frames & 15)) { set_err(c, "device frames must be 16-byte aligned"); return AV1MI_E_INVALID_ARG; }
+  HIPCHK(c, hipSetDevice(c->device));
+  const Av1miDevParams P = dev_params(r, n_frames, 1);
+  hipStream_t s = c->stream;
+  PassBuffers t(s);
+  TplBuffers b;
+  const void *src = coded_frames(t, r, frames, n_frames, frames_on_device);
+  if (t.ok()) run_tpl(t, r, P, src, n_frames, b);
+  unsigned long long sum = 0;
+  const size_t n_sb = (size_t)n_frames * r.sb_cols * r.sb_rows;
+  if (t.ok() && intra) t.e = hipMemcpyAsync(intra, b.intra, b.n_blk * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  if (t.ok() && inter) t.e = hipMemcpyAsync(inter, b.inter, b.n_blk * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  if (t.ok() && key) t.e = hipMemcpyAsync(key, b.key, b.n_blk * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  if (t.ok() && flow) t.e = hipMemcpyAsync(flow, b.flow, b.n_blk * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+  if (t.ok() && beta) t.e = hipMemcpyAsync(beta, b.beta, n_sb * sizeof(uint16_t), hipMemcpyDeviceToHost, s);
+  if (t.ok() && mean_beta) t.e = hipMemcpyAsync(&sum, b.beta_sum(), sizeof(sum), hipMemcpyDeviceToHost, s);
+  rc = t.finish(c, "temporal-dependency");   // (drains the stream: `sum` has arrived)
+  if (rc == AV1MI_OK && mean_beta) *mean_beta = (uint32_t)av1mi_tpl_mean_beta(sum, n_sb);
+  return rc;
 }
 
 // The temporal filter alone: the launch the encoder runs on a chunk's source (av1mi_launch_temporal_filter), on buffers of the call's own.

@@ -48,6 +48,11 @@ struct Workspace {
   uint32_t *d_nodes = nullptr;             // partition_search = 2: the node-mode search's [frame][level][node] keys (part_inter_rule.h)
   uint16_t *d_aq_act = nullptr;            // adaptive quantisation: E per [frame][superblock] (aq_activity_kernel)
   uint8_t *d_aq_map = nullptr;             // ... the quantiser index per [frame][superblock] (aq_map_kernel)
+  // the temporal-dependency analysis (tpl_kernel.hip), on first use: per [frame][16x16 block] I, C and the search's key, the flow A with
+  // the chunk's sum of beta behind it (av1mi_tpl_flow_entries: one fill clears both), and beta per [frame][superblock]
+  uint32_t *d_tpl_intra = nullptr, *d_tpl_inter = nullptr, *d_tpl_key = nullptr;
+  unsigned long long *d_tpl_flow = nullptr;
+  uint16_t *d_tpl_beta = nullptr;
   uint32_t *d_tf_mv = nullptr;             // temporal filter: the search's keys per [key frame][follower][16x16 block] (tf_kernel.hip)
   Av1miQmEntry *d_qm = nullptr;        // quantiser-matrix steps (Av1miDevParams::qm_tab), one slice per quantiser slot, valid for qm_key = (slices, level, qidx, bit depth)
   std::vector<Av1miQmEntry> h_qm; int qm_key = -1;

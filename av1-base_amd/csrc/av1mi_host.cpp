@@ -18,6 +18,7 @@
 #include "wiener_fit_rule.h"
 #include "deblock_pieces.h"
 #include "part_inter_rule.h"
+#include "tpl_rule.h"
 
 using namespace av1mi;
 
@@ -102,7 +103,16 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   // stream's motion search waits for EV_SRC_READY as well)
   if (P.part_map) HIPCHK(c, av1mi_launch_partition(&P, *d_src, w.d_part, s));
   // adaptive quantisation: every superblock's quantiser index, likewise from the source and on the device - the walks and symbolize read the map
-  if (P.aq_map) HIPCHK(c, av1mi_launch_aq(&P, *d_src, w.d_aq_act, w.d_aq_map, r.aq, s));
+  // ... with a temporal strength behind the chunk's temporal-dependency analysis (it sees the filtered key frames): beta of every
+  // superblock and the chunk's sum of it, the flow cleared once per attempt at the chunk
+  const unsigned long long *beta_sum = nullptr;
+  if (r.tpl) {
+    const size_t n_flow = av1mi_tpl_flow_entries(r.cw, r.ch, (int)n_frames);
+    HIPCHK(c, hipMemsetAsync(w.d_tpl_flow, 0, n_flow * sizeof(unsigned long long), s));
+    HIPCHK(c, av1mi_launch_tpl(&P, *d_src, w.d_tpl_intra, w.d_tpl_inter, w.d_tpl_key, w.d_tpl_flow, w.d_tpl_beta, s));
+    beta_sum = w.d_tpl_flow + n_flow - 1;
+  }
+  if (P.aq_map) HIPCHK(c, av1mi_launch_aq(&P, *d_src, w.d_aq_act, w.d_aq_map, r.aq, w.d_tpl_beta, beta_sum, r.tpl, s));
   HIPCHK(c, hipEventRecord(c->ev[EV_SRC_READY], s));
   return AV1MI_OK;
 }

@@ -39,8 +39,17 @@ extern "C" {
 // ---- whole chunk (or call): all P->n_frames frames
 // split masks of every superblock (partition_kernel)
 hipError_t av1mi_launch_partition(const Av1miDevParams *P, const void *frames, uint32_t *part, hipStream_t stream);
-// quantiser index of every superblock (aq_activity_kernel, aq_map_kernel): act and qmap are [frame][superblock]
-hipError_t av1mi_launch_aq(const Av1miDevParams *P, const void *frames, uint16_t *act, uint8_t *qmap, int strength, hipStream_t stream);
+// quantiser index of every superblock (aq_activity_kernel, aq_map_kernel): act and qmap are [frame][superblock].  tpl_strength != 0: the
+// temporal term on top (tpl_rule.h) - beta [frame][superblock] and beta_sum, the chunk's sum of it, as av1mi_launch_tpl on the same
+// stream before has left them; either strength may be 0, not both
+hipError_t av1mi_launch_aq(const Av1miDevParams *P, const void *frames, uint16_t *act, uint8_t *qmap, int strength, const uint16_t *beta,
+                           const unsigned long long *beta_sum, int tpl_strength, hipStream_t stream);
+// the temporal-dependency analysis (tpl_kernel.hip, tpl_rule.h) of the chunk's source at the coded size, range P->me_range: per
+// [frame][16x16 block] the intra cost, the inter cost, the search's node key (all-ones on key frames) - all written - and the flow, added
+// into `flow`; per [frame][superblock] beta.  flow: av1mi_tpl_flow_entries entries, zeroed by the caller - the last one receives the
+// chunk's sum of beta.  `frames` must be a 16-byte aligned device pointer (anything else is refused); it is only read
+hipError_t av1mi_launch_tpl(const Av1miDevParams *P, const void *frames, uint32_t *intra, uint32_t *inter, uint32_t *key, unsigned long long *flow,
+                            uint16_t *beta, hipStream_t stream);
 // the key frames' temporal filter (tf_kernel.hip, tf_rule.h), in place in `frames` at the coded size: every key frame of the chunk is
 // replaced by its filter over up to tf_frames followers at tf_strength, range P->me_range, and re-extended past the signalled size.
 // `frames` must be a 16-byte aligned device pointer (both callers pass an allocation of their own; anything else is refused).

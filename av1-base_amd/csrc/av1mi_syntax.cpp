@@ -16,6 +16,7 @@
 #include "lr_rate_rule.h"
 #include "deblock_pieces.h"
 #include "aq_rule.h"
+#include "tpl_rule.h"
 #include "tf_rule.h"
 
 namespace av1mi {
@@ -69,9 +70,11 @@ int resolve(const av1mi_params *in, Resolved *r) {
   r->padded = r->cw != (int)p.width || r->ch != (int)p.height;
   if (p.bit_depth != 8 && p.bit_depth != 10) return AV1MI_E_INVALID_ARG;
   // cq_level 0 is base_q_idx 0: CodedLossless frames (spec 5.9.2), whose syntax this encoder does not write (no WHT, no lossless header)
-  // ... and bits 8-10 of the field are the strength of the adaptive quantisation, 0 .. 4; nothing above them
+  // ... and bits 8-10 of the field are the strength of the adaptive quantisation, 0 .. 4, bits 12-14 that of its temporal term, 0 .. 4;
+  // nothing in bit 11 or above them
   r->aq = (int)AV1MI_AQ_STRENGTH(p.cq_level);
-  if ((p.cq_level >> 11) || r->aq > AV1MI_AQ_MAX_STRENGTH) return AV1MI_E_INVALID_ARG;
+  r->tpl = (int)AV1MI_TPL_STRENGTH(p.cq_level);
+  if ((p.cq_level & ~0x77FFu) || r->aq > AV1MI_AQ_MAX_STRENGTH || r->tpl > AV1MI_TPL_MAX_STRENGTH) return AV1MI_E_INVALID_ARG;
   p.cq_level = AV1MI_CQ_LEVEL(p.cq_level);
   if (p.cq_level == 0 || p.cq_level > 63 || p.film_grain > 50) return AV1MI_E_INVALID_ARG;
   if (p.keyint == 0) p.keyint = 1;
@@ -278,8 +281,8 @@ std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint
   b.put(r.p.enable_qm ? 1 : 0, 1);  // using_qmatrix
   if (r.p.enable_qm) { b.put((uint32_t)r.qm_level, 4); b.put((uint32_t)r.qm_level, 4); }  // qm_y, qm_u (= qm_v: separate_uv_delta_q = 0)
   b.put(0, 1);  // segmentation_enabled
-  if (r.qidx > 0) b.put(r.aq ? 1 : 0, 1);  // delta_q_present
-  if (r.aq) {
+  if (r.qidx > 0) b.put(dq_on(r) ? 1 : 0, 1);  // delta_q_present
+  if (dq_on(r)) {
     b.put(2, 2);  // delta_q_res: deltas in steps of 4
     b.put(0, 1);  // delta_lf_present
   }
@@ -518,7 +521,7 @@ std::vector<Av1miDevParams> slot_params(const Av1miDevParams &P) {
 // with adaptive quantisation one slice per quantiser slot (av1mi_aq_slot): the superblock's steps through the frame's matrix
 std::vector<Av1miQmEntry> make_qm_table(const Resolved &r) {
   static const int off[4] = { AV1MI_QM_4X4, AV1MI_QM_8X8, AV1MI_QM_16X16, AV1MI_QM_32X32 };
-  const int slices = r.aq ? AV1MI_AQ_SLOTS : 1;
+  const int slices = dq_on(r) ? AV1MI_AQ_SLOTS : 1;
   std::vector<Av1miQmEntry> tab((size_t)slices * 2 * AV1MI_QM_PLANE);
   for (int sl = 0; sl < slices; sl++) {
     const QuantSteps qs = quant_steps(av1mi_aq_slot_qindex(sl, r.qidx), (int)r.p.bit_depth);

@@ -28,6 +28,7 @@ struct Resolved {
   int qm_level;                       // quantiser-matrix level of all planes (15 = flat); only meaningful with p.enable_qm
   int lr_chroma;                      // enable_lr 3 / 4: U and V restored as well (p.enable_lr then holds the type: 1 / 2)
   int aq;                             // strength of the adaptive quantisation, 0 = off (p.cq_level then holds the CQ level alone)
+  int tpl;                            // cq_level bits 12-14: strength of its temporal term (tpl_rule.h), 0 = off; delta_q is coded when either is set (dq_on)
   uint32_t lr_fit_mask;               // enable_lr bit 8: the parameter sets the self-guided fit searches, 0 = no fit (p.enable_lr holds the type)
   int lr_wfit;                        // enable_lr bit 10: the Wiener fit (p.enable_lr holds the type)
   int lr_unit_shift;                  // enable_lr bits 12-13: luma restoration units of 64 << lr_unit_shift samples (0 .. 2)
@@ -36,6 +37,8 @@ struct Resolved {
 };
 
 int resolve(const av1mi_params *in, Resolved *r);
+// superblocks carry a quantiser index of their own: the spatial or the temporal term of the adaptive quantisation is on
+inline bool dq_on(const Resolved &r) { return r.aq || r.tpl; }
 // bytes of n frames in the caller's layout: tight at the signalled size
 size_t caller_bytes(const Resolved &r, size_t n);
 

@@ -11,6 +11,7 @@
 #include "av1mi_dev.h"
 #include "av1mi_launch.h"
 #include "aq_rule.h"
+#include "tpl_rule.h"
 
 namespace {
 
@@ -184,17 +185,27 @@ __global__ void __launch_bounds__(64) aq_activity_kernel(Av1miDevParams P, const
   if (lane == 0) act[(size_t)f * P.sb_rows * P.sb_cols + sb] = (uint16_t)av1mi_aq_mean(e, n);
 }
 
-__global__ void __launch_bounds__(256) aq_map_kernel(Av1miDevParams P, const uint16_t *__restrict__ act, uint8_t *__restrict__ qmap, int strength) {
+// beta, beta_sum, tpl_strength: the temporal term (tpl_rule.h) - beta per [frame][superblock] and the chunk's sum of it, from
+// av1mi_launch_tpl on the same stream before; strength 0: neither is read and the map is the spatial rule's.  A spatial strength of 0
+// does not read act.
+__global__ void __launch_bounds__(256) aq_map_kernel(Av1miDevParams P, const uint16_t *__restrict__ act, uint8_t *__restrict__ qmap, int strength,
+                                                     const uint16_t *__restrict__ beta, const unsigned long long *__restrict__ beta_sum, int tpl_strength) {
   __shared__ uint32_t part[4];
   const int f = blockIdx.x, t = threadIdx.x, nsb = P.sb_rows * P.sb_cols;
   const uint16_t *E = act + (size_t)f * nsb;
   uint32_t sum = 0;
-  for (int i = t; i < nsb; i += 256) sum += E[i];
+  if (strength) for (int i = t; i < nsb; i += 256) sum += E[i];
   for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
   if ((t & 63) == 0) part[t >> 6] = sum;
   __syncthreads();
   const int M = av1mi_aq_mean(part[0] + part[1] + part[2] + part[3], (uint32_t)nsb);
-  for (int i = t; i < nsb; i += 256) qmap[(size_t)f * nsb + i] = (uint8_t)av1mi_aq_qindex_of(strength, (int)E[i], M, P.base_q_idx);
+  if (!tpl_strength) {
+    for (int i = t; i < nsb; i += 256) qmap[(size_t)f * nsb + i] = (uint8_t)av1mi_aq_qindex_of(strength, (int)E[i], M, P.base_q_idx);
+    return;
+  }
+  const int Mb = av1mi_tpl_mean_beta(*beta_sum, (uint64_t)P.n_frames * (uint64_t)nsb);
+  for (int i = t; i < nsb; i += 256)
+    qmap[(size_t)f * nsb + i] = (uint8_t)av1mi_tpl_qindex_of(strength, strength ? (int)E[i] : 0, M, tpl_strength, (int)beta[(size_t)f * nsb + i], Mb, P.base_q_idx);
 }
 
 }  // namespace
@@ -206,11 +217,13 @@ extern "C" hipError_t av1mi_launch_partition(const Av1miDevParams *P, const void
   return hipGetLastError();
 }
 
-extern "C" hipError_t av1mi_launch_aq(const Av1miDevParams *P, const void *frames, uint16_t *act, uint8_t *qmap, int strength, hipStream_t stream) {
+extern "C" hipError_t av1mi_launch_aq(const Av1miDevParams *P, const void *frames, uint16_t *act, uint8_t *qmap, int strength, const uint16_t *beta,
+                                      const unsigned long long *beta_sum, int tpl_strength, hipStream_t stream) {
   dim3 grid(P->sb_rows * P->sb_cols, P->n_frames);
-  if (P->bit_depth == 8) hipLaunchKernelGGL(aq_activity_kernel<uint8_t>, grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, act);
+  if (!strength) { }   // the spatial term is 0: no activity pass
+  else if (P->bit_depth == 8) hipLaunchKernelGGL(aq_activity_kernel<uint8_t>, grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, act);
   else hipLaunchKernelGGL(aq_activity_kernel<uint16_t>, grid, dim3(64), 0, stream, *P, (const uint16_t *)frames, act);
-  hipLaunchKernelGGL(aq_map_kernel, dim3(P->n_frames), dim3(256), 0, stream, *P, (const uint16_t *)act, qmap, strength);
+  hipLaunchKernelGGL(aq_map_kernel, dim3(P->n_frames), dim3(256), 0, stream, *P, (const uint16_t *)act, qmap, strength, beta, beta_sum, tpl_strength);
   return hipGetLastError();
 }
 

@@ -5,11 +5,8 @@
 // quantisation, the in-loop decisions, the report's SSE - then reads the filtered frame.  Followers are read only.
 //
 // Two launches.  tf_search_kernel: per (16x16 block, follower, key frame) one wave runs the full search of +-R whole samples around zero
-// with me_rule.h's reach, cost, index and node key - the scheme of motion_search_kernel (packed sample pairs, v_sad_u16, DPP row
-// rotations as operands of the additions) laid out for one block: lane = (row of the block, one of four dy) so that a pass over the 2R+1 dx
-// covers four dy, the 16 lanes of a DPP row are the block's 16 rows, and the row's sum is the candidate's SAD.  Interior blocks load
-// their rows in whole words (with one-sample loads everywhere the launch took 4.7 times as long: DESIGN.md §5l).  One 32-bit key per
-// (key frame, follower, block).  tf_blend_kernel: one wave per block reads the key block into registers (4 luma + 2 chroma samples per
+// with me_rule.h's reach, cost, index and node key - tf_search.h's body, which the temporal-dependency analysis (tpl_kernel.hip) runs
+// too.  One 32-bit key per (key frame, follower, block).  tf_blend_kernel: one wave per block reads the key block into registers (4 luma + 2 chroma samples per
 // lane), and per follower the displaced prediction, forms the errors' 3x3 sums through LDS and the block sums with shuffles, weighs and
 // accumulates; then blends, re-extends past the signalled size and writes the block in place - blocks are disjoint, and a block reads
 // the key frame inside itself only (an overhanging block's clamped coordinates stay in the block).
@@ -19,66 +16,15 @@
 #include "av1mi_dev.h"
 #include "av1mi_launch.h"
 #include "tf_rule.h"
+#include "tf_search.h"
 
 namespace {
-
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// sum over the 16 lanes of a DPP row, in every lane of the row: rotations within the row as operands of the additions
-__device__ __forceinline__ uint32_t row_sum_u32(uint32_t v) {
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, false);   // row_ror 8, 4, 2, 1
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x124, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x122, 0xF, 0xF, false);
-  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x121, 0xF, 0xF, false);
-  return v;
-}
-// minimum over the wave, wave-uniform: over each row with rotations, then one v_readlane per row
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-  uint32_t t;
-  t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x128, 0xF, 0xF, false); v = t < v ? t : v;
-  t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x124, 0xF, 0xF, false); v = t < v ? t : v;
-  t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x122, 0xF, 0xF, false); v = t < v ? t : v;
-  t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x121, 0xF, 0xF, false); v = t < v ? t : v;
-  uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)v, 0);
-  t = (uint32_t)__builtin_amdgcn_readlane((int)v, 16); m = t < m ? t : m;
-  t = (uint32_t)__builtin_amdgcn_readlane((int)v, 32); m = t < m ? t : m;
-  t = (uint32_t)__builtin_amdgcn_readlane((int)v, 48); m = t < m ? t : m;
-  return m;
-}
 
 // where the search's key of (key frame index k, follower t = 1 .. N, block b) lives
 __device__ __forceinline__ size_t key_slot(int k, int N, int t, int nb, int b) { return ((size_t)k * N + (t - 1)) * nb + b; }
 
-// 2 NP consecutive samples of a row from x0 on, two per register: pair[i] = samples (x0 + 2i, x0 + 2i + 1).  `inside`: all of them lie
-// in the row and x0 is a multiple of 8 samples (8 bytes for 8-bit samples, 16 for 16-bit ones: the loads are that wide; NP is a
-// multiple of 4) - else one sample at a time with clamped coordinates.
-template <typename PIX, int NP>
-__device__ __forceinline__ void load_pairs(const PIX *__restrict__ row, int x0, int W, bool inside, uint32_t *pair) {
-  static_assert(NP % 4 == 0, "whole 8-sample loads");
-  if (inside) {
-    if constexpr (sizeof(PIX) == 2) {
-      const uint4 *v = reinterpret_cast<const uint4 *>(row + x0);
-#pragma unroll
-      for (int j = 0; j < NP / 4; j++) { const uint4 d = v[j]; pair[4 * j] = d.x; pair[4 * j + 1] = d.y; pair[4 * j + 2] = d.z; pair[4 * j + 3] = d.w; }
-    } else {
-      const uint2 *v = reinterpret_cast<const uint2 *>(row + x0);
-#pragma unroll
-      for (int j = 0; j < NP / 4; j++) {
-        const uint2 d = v[j];
-        pair[4 * j] = (d.x & 0xFFu) | ((d.x << 8) & 0xFF0000u); pair[4 * j + 1] = ((d.x >> 16) & 0xFFu) | ((d.x >> 8) & 0xFF0000u);
-        pair[4 * j + 2] = (d.y & 0xFFu) | ((d.y << 8) & 0xFF0000u); pair[4 * j + 3] = ((d.y >> 16) & 0xFFu) | ((d.y >> 8) & 0xFF0000u);
-      }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < NP; i++) pair[i] = (uint32_t)row[clampi(x0 + 2 * i, W - 1)] | ((uint32_t)row[clampi(x0 + 2 * i + 1, W - 1)] << 16);
-  }
-}
-
 template <typename PIX, int R>
 __global__ void __launch_bounds__(64) tf_search_kernel(Av1miDevParams P, const PIX *__restrict__ frames, uint32_t *__restrict__ mv, int N) {
-  constexpr int NC = 2 * R + 1, PASSES = (NC + 3) / 4;
-  static_assert(NC * NC <= (1 << AV1MI_ME_NODE_INDEX_BITS), "a node key holds an 11-bit candidate index");
   const int W = P.width, H = P.height, nbx = av1mi_tf_blocks(W), nb = nbx * av1mi_tf_blocks(H);
   const int b = blockIdx.x, t = blockIdx.y + 1, k = blockIdx.z, f = k * P.keyint, lane = threadIdx.x;
   uint32_t *slot = mv + key_slot(k, N, t, nb, b);
@@ -87,50 +33,16 @@ __global__ void __launch_bounds__(64) tf_search_kernel(Av1miDevParams P, const P
     return;
   }
   const PIX *key = frames + (size_t)f * P.frame_samples, *ref = key + (size_t)t * P.frame_samples;   // luma of the two frames
-  const int x = (b % nbx) * AV1MI_TF_BLOCK, y = (b / nbx) * AV1MI_TF_BLOCK;
-  const int r = lane & 15, q = lane >> 4;
-  // the key block's row r, coordinates clamped to the frame (an overhanging block), two samples per register
-  // (interior blocks - the window of every candidate inside the row - load whole words: `frames` is 16-byte aligned, x and R are
-  // multiples of 8, and so are the rows' strides and the frames' sizes)
-  const bool in_key = x + AV1MI_TF_BLOCK <= W, in_ref = x - R >= 0 && x + AV1MI_TF_BLOCK + R <= W;
+  // (`frames` is 16-byte aligned, and the rows' strides and the frames' sizes are multiples of 8: tf_search.h loads whole words)
   uint32_t s2[8];
-  load_pairs<PIX, 8>(key + (size_t)clampi(y + r, H - 1) * P.stride_y, x, W, in_key, s2);
-  // the dxi within reach of the frame, one bit each (wave-uniform; one mask instead of a flag per dxi kept across the passes)
-  unsigned long long x_ok = 0;
-  for (int dxi = 0; dxi < NC; dxi++) x_ok |= (unsigned long long)av1mi_me_reach(x, dxi - R, AV1MI_TF_BLOCK, W) << dxi;
-  uint32_t best = AV1MI_ME_NODE_NONE;   // this lane's candidates: dx = its row position (mod 16), dy = 4 pass + q
-  for (int pass = 0; pass < PASSES; pass++) {
-    const int dyi = pass * 4 + q;
-    const bool live = dyi < NC;
-    const int dy = (live ? dyi : NC - 1) - R;
-    // the follower's samples x - R .. x + 15 + R of row y + r + dy, coordinates clamped: rE[i] = samples (2i, 2i + 1), rO[i] = (2i + 1,
-    // 2i + 2) - the key pair i meets rE[i + dx / 2] for even dxi and rO[i + (dxi - 1) / 2] for odd
-    uint32_t rE[8 + R], rO[8 + R];
-    load_pairs<PIX, 8 + R>(ref + (size_t)clampi(y + r + dy, H - 1) * P.stride_y, x - R, W, in_ref, rE);
-#pragma unroll
-    for (int i = 0; i < 8 + R; i++) rO[i] = i < 8 + R - 1 ? (rE[i] >> 16) | (rE[i + 1] << 16) : 0u;
-    const bool y_ok = live && av1mi_me_reach(y, dy, AV1MI_TF_BLOCK, H);
-#pragma unroll
-    for (int dxi = 0; dxi < NC; dxi++) {
-      const int h = dxi >> 1;
-      uint32_t a = 0;
-#pragma unroll
-      for (int i = 0; i < 8; i++) a = __builtin_amdgcn_sad_u16(s2[i], (dxi & 1) ? rO[i + h] : rE[i + h], a);
-      a = row_sum_u32(a);   // over the block's 16 rows: the candidate's SAD, in every lane of the row
-      const int dx = dxi - R;
-      const bool ok = y_ok && r == (dxi & 15) && ((x_ok >> dxi) & 1);
-      const uint32_t c = av1mi_me_node_key(av1mi_me_cost(a, AV1MI_TF_BLOCK, dx, dy), av1mi_me_index(dyi, dxi, R));
-      best = ok && c < best ? c : best;
-    }
-  }
-  best = wave_min_u32(best);   // (0, 0) is always within reach: never all-ones
+  const uint32_t best = tf_search_block<PIX, R>(key, ref, (b % nbx) * AV1MI_TF_BLOCK, (b / nbx) * AV1MI_TF_BLOCK, W, H, P.stride_y, lane, s2);
   if (lane == 0) *slot = best;
 }
 
 // One plane's sample of frame `fr` at clamped coordinates
 template <typename PIX>
 __device__ __forceinline__ int at(const PIX *__restrict__ plane, int stride, int px, int py, int w, int h) {
-  return (int)plane[(size_t)clampi(py, h - 1) * stride + clampi(px, w - 1)];
+  return (int)plane[(size_t)tf_clampi(py, h - 1) * stride + tf_clampi(px, w - 1)];
 }
 
 template <typename PIX>
@@ -186,7 +98,7 @@ __global__ void __launch_bounds__(64) tf_blend_kernel(Av1miDevParams P, PIX *__r
 #pragma unroll
       for (int v = -1; v <= 1; v++)
 #pragma unroll
-        for (int u = -1; u <= 1; u++) S += sE[clampi(ly + v, 15) * 16 + clampi(lx + i + u, 15)];
+        for (int u = -1; u <= 1; u++) S += sE[tf_clampi(ly + v, 15) * 16 + tf_clampi(lx + i + u, 15)];
       const uint32_t w = (uint32_t)av1mi_tf_weight(av1mi_tf_index(S, bY, sh, 0));
       numY[i] += w * (uint32_t)pY[i]; denY[i] += w;
     }
@@ -196,7 +108,7 @@ __global__ void __launch_bounds__(64) tf_blend_kernel(Av1miDevParams P, PIX *__r
 #pragma unroll
       for (int v = -1; v <= 1; v++)
 #pragma unroll
-        for (int u = -1; u <= 1; u++) S += sE[256 + pl * 64 + clampi(cy + v, 7) * 8 + clampi(cx + i + u, 7)];
+        for (int u = -1; u <= 1; u++) S += sE[256 + pl * 64 + tf_clampi(cy + v, 7) * 8 + tf_clampi(cx + i + u, 7)];
       const uint32_t w = (uint32_t)av1mi_tf_weight(av1mi_tf_index(S, bC, sh, 1));
       numC[i] += w * (uint32_t)pC[i]; denC[i] += w;
     }
@@ -211,21 +123,21 @@ __global__ void __launch_bounds__(64) tf_blend_kernel(Av1miDevParams P, PIX *__r
   __syncthreads();
   const int tw = P.true_w, th = P.true_h, twc = tw >> 1, thc = th >> 1;
   {
-    const int yy = y + ly, sy = clampi((yy < th ? yy : th - 1) - y, 15);
+    const int yy = y + ly, sy = tf_clampi((yy < th ? yy : th - 1) - y, 15);
     if (yy < H) {
 #pragma unroll
       for (int i = 0; i < 4; i++) {
-        const int xx = x + lx + i, sx = clampi((xx < tw ? xx : tw - 1) - x, 15);
+        const int xx = x + lx + i, sx = tf_clampi((xx < tw ? xx : tw - 1) - x, 15);
         if (xx < W) key[(size_t)yy * P.stride_y + xx] = (PIX)sE[sy * 16 + sx];
       }
     }
   }
   {
-    const int yy = yc + cy, sy = clampi((yy < thc ? yy : thc - 1) - yc, 7);
+    const int yy = yc + cy, sy = tf_clampi((yy < thc ? yy : thc - 1) - yc, 7);
     if (yy < Hc) {
 #pragma unroll
       for (int i = 0; i < 2; i++) {
-        const int xx = xc + cx + i, sx = clampi((xx < twc ? xx : twc - 1) - xc, 7);
+        const int xx = xc + cx + i, sx = tf_clampi((xx < twc ? xx : twc - 1) - xc, 7);
         if (xx < Wc) key[coff + (size_t)yy * P.stride_c + xx] = (PIX)sE[256 + pl * 64 + sy * 8 + sx];
       }
     }

@@ -36,10 +36,13 @@ enum {
 
 typedef struct av1mi_ctx av1mi_ctx;
 
-/* av1mi_params.cq_level carries two values: the CQ level and the strength of the adaptive quantisation */
+/* av1mi_params.cq_level carries three values: the CQ level, the strength of the adaptive quantisation's spatial term and the strength
+ * of its temporal term */
 #define AV1MI_CQ_AQ(cq, strength) (((uint32_t)(cq) & 0xFFu) | (((uint32_t)(strength) & 7u) << 8))
+#define AV1MI_CQ_AQ_TPL(cq, aq, tpl) (AV1MI_CQ_AQ(cq, aq) | (((uint32_t)(tpl) & 7u) << 12))
 #define AV1MI_CQ_LEVEL(v) ((uint32_t)(v) & 0xFFu)
 #define AV1MI_AQ_STRENGTH(v) (((uint32_t)(v) >> 8) & 7u)
+#define AV1MI_TPL_STRENGTH(v) (((uint32_t)(v) >> 12) & 7u)
 /* av1mi_params.enable_lr with the self-guided fit: lr = 2 or 4, sets = a mask over the 16 parameter sets searched (0 = all) */
 #define AV1MI_LR_FIT(lr, sets) ((uint32_t)(lr) | 0x100u | ((uint32_t)(sets) << 16))
 /* av1mi_params.enable_lr bit 10: the Wiener fit, or-ed into a value with a low byte of 1 .. 4 (with or without AV1MI_LR_FIT) */
@@ -63,7 +66,10 @@ typedef struct av1mi_ctx av1mi_ctx;
 
 /* Operating point.  Replaces the reference's single constant
  *   SVT_PARAMS = "--crf 8 --preset 3 --film-grain 20 ... --keyint 240 --lookahead 40"
- * (crates/daemon/src/encode/av1an.rs:14) and `--pix-format yuv420p10le` (av1an.rs:90). */
+ * (crates/daemon/src/encode/av1an.rs:14) and `--pix-format yuv420p10le` (av1an.rs:90).  What `--lookahead` buys there has two
+ * switches here, both off by default and both over the whole chunk rather than 40 frames: the key frames' temporal filter
+ * (me_presearch, AV1MI_ME_TF) and the temporal-dependency term of the adaptive quantisation (cq_level, AV1MI_CQ_AQ_TPL).  There is
+ * no per-frame base_q_idx and no B pyramid. */
 typedef struct {
   uint32_t width, height;   /* luma size, even, >= 8, yuv 4:2:0.  Sizes that are not multiples of 8 are coded at the next
                                multiple of 8 (source edge-extended on the device) and signalled exactly, as any AV1 encoder does */
@@ -75,8 +81,16 @@ typedef struct {
                                base_q_idx + 4 d, d in -6..6 from s times the difference between the log2 variance of its source luma
                                (mean over its 8x8 units) and the frame's mean, s = 2 being one step per doubling - flat superblocks a
                                finer quantiser, busy ones a coarser (delta_q_present = 1, delta_q_res = 2; deblocking level, partition
-                               threshold and quantiser-matrix level stay with base_q_idx).  Strengths 5..7 and any higher bit are
-                               refused with AV1MI_E_INVALID_ARG */
+                               threshold and quantiser-matrix level stay with base_q_idx).
+                               bits 12-14: tpl_strength 0..4, the temporal term of the same map (AV1MI_CQ_AQ_TPL packs the field;
+                               DESIGN.md §3 item 1d): 0 (default) = off; s = 1..4: a look-ahead over the whole chunk follows the
+                               motion of 16x16 source blocks (whole samples, +-me_range, frame against the frame before) backwards
+                               from the chunk's last frame and measures, per superblock, beta = the log2 of how much of the later
+                               frames it is going to predict; s (beta - the chunk's mean beta) is subtracted from the spatial term
+                               before d is formed - superblocks the rest of the chunk depends on a finer quantiser, superblocks
+                               nothing depends on a coarser.  Either strength alone turns delta_q_present on; with keyint = 1
+                               nothing is predicted and the term is 0.  Strengths 5..7 of either, bit 11 and bits 15-31 are refused
+                               with AV1MI_E_INVALID_ARG */
   uint32_t keyint;          /* "--keyint": 1 = every frame a key frame; N > 1 = a key frame every N frames of a chunk, the
                                frames between are INTER frames predicted from the previous reconstruction (one
                                reference, integer-pel full search; chunks always start with a key frame) */
@@ -257,10 +271,23 @@ int av1mi_scene_cuts(av1mi_ctx *ctx, const av1mi_params *params, const void *fra
 
 /* ---- adaptive quantisation: the decision on its own (what an analysis tool wants) ------------
  * The quantiser index every 64x64 superblock of every frame is coded with: qindex[(f * sb_rows + r) * sb_cols + c],
- * sb_cols = (ceil8(width) + 63) / 64, likewise rows; all base_q_idx when the strength is 0.  Same frame arguments as
+ * sb_cols = (ceil8(width) + 63) / 64, likewise rows; all base_q_idx when both strengths are 0; with a tpl_strength the map of both
+ * terms, the frames taken as one chunk (keyint and me_range as the parameters say).  Same frame arguments as
  * av1mi_scene_cuts (tight planar frames, host or 16-byte aligned device memory). */
 int av1mi_aq_qindex(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames,
                     int frames_on_device, uint8_t *qindex);
+
+/* ---- the temporal-dependency analysis on its own ----------------------------------------------
+ * What av1mi_encode_chunk runs on a chunk's source when av1mi_params.cq_level carries a tpl_strength (AV1MI_CQ_AQ_TPL): the same
+ * launches on the same frames, taken as one chunk.  Every output is optional, host memory.  Per frame f and 16x16 block b of the
+ * coded size (nb = ceil(ceil8(width) / 16) * ceil(ceil8(height) / 16) blocks in raster order), at [f * nb + b]: intra = I, the block's
+ * sum of absolute differences from its mean (at least 1); inter = C, min(I, the SAD of the best whole-sample vector within +-me_range
+ * against frame f - 1), I on key frames; key = that vector's (cost << 11) | index as av1mi_temporal_filter reports its own,
+ * 0xFFFFFFFF on key frames; flow = A, what the frames after f inside its key-frame interval hand back to the block.  beta: per frame
+ * and superblock, layout of av1mi_aq_qindex: 16 log2 ((sum I + A) / sum I) over the superblock's blocks; *mean_beta: its rounded mean
+ * over the chunk.  AV1MI_E_INVALID_ARG when the strength is 0.  Like av1mi_aq_qindex it looks at the frames it is given. */
+int av1mi_tpl_analysis(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
+                       uint32_t *intra, uint32_t *inter, uint32_t *key, uint64_t *flow, uint16_t *beta, uint32_t *mean_beta);
 
 /* ---- the key frames' temporal filter on its own --------------------------------------------
  * What av1mi_encode_chunk codes instead of the key frames when av1mi_params.me_presearch carries the filter (AV1MI_ME_TF): the

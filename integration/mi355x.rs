@@ -9,7 +9,8 @@ use std::os::raw::{c_char, c_int, c_void};
 #[derive(Default, Clone, Copy)]
 pub struct Av1miParams {            // include/av1mi.h: av1mi_params
     pub width: u32, pub height: u32, pub bit_depth: u32,
-    /// Bits 0-7: the CQ level 1..63; bits 8-10: aq_strength 0..4, activity-adaptive quantisation (`cq_aq` packs the field; 0 = off).
+    /// Bits 0-7: the CQ level 1..63; bits 8-10: aq_strength 0..4, activity-adaptive quantisation (`cq_aq` packs the field; 0 = off);
+    /// bits 12-14: tpl_strength 0..4, its temporal-dependency term from a look-ahead over the chunk (`cq_aq_tpl` packs all three; 0 = off).
     pub cq_level: u32,
     pub keyint: u32, pub block_log2: u32, pub cdf_update: u32, pub enable_cdef: u32,
     pub cdef_y_pri: u32, pub cdef_y_sec: u32, pub cdef_uv_pri: u32, pub cdef_uv_sec: u32, pub cdef_damping: u32,
@@ -58,6 +59,10 @@ pub const AV1MI_AQ_MAX_STRENGTH: u32 = 4;
 // include/av1mi.h: AV1MI_LR_WIENER_FIT - or-ed into enable_lr
 pub const AV1MI_LR_WIENER_FIT: u32 = 0x400;
 pub const fn cq_aq(cq: u32, strength: u32) -> u32 { (cq & 0xFF) | ((strength & 7) << 8) }
+// include/av1mi.h: AV1MI_CQ_AQ_TPL / AV1MI_TPL_STRENGTH - the temporal term's strength beside the two
+pub const AV1MI_TPL_MAX_STRENGTH: u32 = 4;
+pub const fn cq_aq_tpl(cq: u32, aq: u32, tpl: u32) -> u32 { cq_aq(cq, aq) | ((tpl & 7) << 12) }
+pub const fn tpl_strength_of(v: u32) -> u32 { (v >> 12) & 7 }
 pub const fn cq_level_of(v: u32) -> u32 { v & 0xFF }
 pub const fn aq_strength_of(v: u32) -> u32 { (v >> 8) & 7 }
 // include/av1mi.h: AV1MI_ME_TF / AV1MI_ME_PRESEARCH / AV1MI_TF_FRAMES / AV1MI_TF_STRENGTH - me_presearch carries the pre-search's switch and
