@@ -37,7 +37,8 @@ E_INVALID_ARG, E_NO_DEVICE, E_HIP, E_OOM, E_OVERFLOW, E_FORMAT, E_UNSUPPORTED = 
 # every symbol include/av1mi.h declares
 ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", "av1mi_last_error", "av1mi_encode_chunk",
                "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units", "av1mi_sym_order_result", "av1mi_sym_order_tiles", "av1mi_inter_partition_result", "av1mi_inter_partition_units",
-               "av1mi_lr_rd_result", "av1mi_lr_rd_units", "av1mi_temporal_filter", "av1mi_tpl_analysis"]
+               "av1mi_lr_rd_result", "av1mi_lr_rd_units", "av1mi_temporal_filter", "av1mi_tpl_analysis", "av1mi_film_grain_estimate",
+               "av1mi_film_grain_result"]
 
 
 class Params(C.Structure):
@@ -117,6 +118,9 @@ _lib.av1mi_aq_qindex.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_
 _lib.av1mi_temporal_filter.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_uint32)]
 _lib.av1mi_tpl_analysis.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint16), C.POINTER(C.c_uint32)]
+_lib.av1mi_film_grain_estimate.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint8)]
+_lib.av1mi_film_grain_result.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
 _lib.av1mi_lf_search_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
 _lib.av1mi_lr_fit_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint64)]
 _lib.av1mi_lr_fit_units.argtypes = [C.c_void_p]
@@ -197,6 +201,25 @@ def aq_strength_of(v):
     return (v >> 8) & 7
 
 
+FILM_GRAIN_MAX = 50
+FILM_GRAIN_ESTIMATE = 0x100   # include/av1mi.h: bit 8 of film_grain - the table is estimated from the chunk's source
+
+
+def film_grain_estimate(n):
+    """include/av1mi.h: AV1MI_FILM_GRAIN_ESTIMATE - the film_grain field with the estimate on and N = 1 .. 50 as the ceiling"""
+    return n | FILM_GRAIN_ESTIMATE
+
+
+def film_grain_estimated(v):
+    """include/av1mi.h: AV1MI_FILM_GRAIN_ESTIMATED"""
+    return (v >> 8) & 1
+
+
+def film_grain_level_of(v):
+    """include/av1mi.h: AV1MI_FILM_GRAIN_LEVEL"""
+    return v & 0xFF
+
+
 TF_MAX_FRAMES = 7
 TF_MAX_STRENGTH = 7
 
@@ -254,14 +277,17 @@ def lr_unit_grid(width, height, shift=0):
 
 
 def default_params(width, height, bit_depth=8, aq_strength=None, tpl_strength=None, lr_fit=None, lr_wiener_fit=False, lr_unit_shift=0, lr_rd=None, tf_frames=None,
-                   tf_strength=None, **kw):
-    """aq_strength, tpl_strength: packed into cq_level beside the CQ level (cq_aq_tpl); lr_fit: True or a mask of parameter sets, packed into enable_lr
+                   tf_strength=None, film_grain_estimate=None, **kw):
+    """film_grain_estimate: N = 1 .. 50 sets film_grain to the estimated table with the ceiling N (the function of that name), True turns
+    the estimate on for the film_grain keyword's N; aq_strength, tpl_strength: packed into cq_level beside the CQ level (cq_aq_tpl); lr_fit: True or a mask of parameter sets, packed into enable_lr
     (lr_fit_field); lr_wiener_fit: True sets enable_lr's bit 10 (LR_WIENER_FIT); lr_unit_shift: 1 / 2 sets enable_lr's bits 12-13
     (LR_UNIT_128 / LR_UNIT_256); lr_rd: a scale s = 0 .. 3 sets the rate term of the unit decisions (lr_rd_field); tf_frames, tf_strength:
     the key frames' temporal filter, packed into me_presearch beside the pre-search's switch (me_tf); every other keyword sets the
     structure field of its name"""
     p = Params()
     _lib.av1mi_default_params(C.byref(p), width, height, bit_depth)
+    if film_grain_estimate is not None and film_grain_estimate is not False:
+        kw["film_grain"] = FILM_GRAIN_ESTIMATE | (kw.get("film_grain", p.film_grain) if film_grain_estimate is True else int(film_grain_estimate))
     if tf_frames is not None or tf_strength is not None:
         kw["me_presearch"] = me_tf(kw.get("me_presearch", p.me_presearch), int(tf_frames or 0), int(tf_strength or 0))
     if lr_fit is not None and lr_fit is not False:
@@ -415,6 +441,29 @@ class Context:
         _raise_for(rc, self.last_error())
         out["mean_beta"] = int(mean.value)
         return out
+
+    def film_grain_estimate(self, params, frames, n_frames, on_device=False, want_blocks=True):
+        """The film-grain estimate alone (include/av1mi.h: av1mi_film_grain_estimate); frames as for scene_cuts.  Returns numpy arrays
+        (table uint8 [plane][8], counts uint32 [plane][8], blocks uint8 [frame][block row][block column][4] = bin, v_y, v_u, v_v over the
+        whole 16x16 blocks of the signalled size - None with want_blocks=False)."""
+        import numpy as np
+        table = np.zeros((3, 8), dtype=np.uint8)
+        counts = np.zeros((3, 8), dtype=np.uint32)
+        blocks = np.zeros((n_frames, params.height // 16, params.width // 16, 4), dtype=np.uint8) if want_blocks else None
+        fptr, keep = _frames_ptr(frames, on_device)
+        rc = _lib.av1mi_film_grain_estimate(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0, table.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                            counts.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                            blocks.ctypes.data_as(C.POINTER(C.c_uint8)) if want_blocks and blocks.size else None)
+        _raise_for(rc, self.last_error())
+        return table, counts, blocks
+
+    def film_grain_result(self):
+        """The film-grain table of the last encoded chunk (include/av1mi.h: av1mi_film_grain_result): numpy uint8 [plane][8], zeros for
+        a chunk without the estimate."""
+        import numpy as np
+        table = np.zeros((3, 8), dtype=np.uint8)
+        _raise_for(_lib.av1mi_film_grain_result(self._h, table.ctypes.data_as(C.POINTER(C.c_uint8))), self.last_error())
+        return table
 
     def temporal_filter(self, params, frames, n_frames, on_device=False, out_ptr=None, want_mv=True):
         """The key frames' temporal filter alone (include/av1mi.h: av1mi_temporal_filter).  Host frames (bytes-like / numpy): returns

@@ -18,6 +18,7 @@
 #include "deblock_pieces.h"
 #include "aq_rule.h"
 #include "tpl_rule.h"
+#include "fg_rule.h"
 #include "part_inter_rule.h"
 
 namespace av1mi {
@@ -125,6 +126,10 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     for (uint32_t **b : { &w.d_tpl_intra, &w.d_tpl_inter, &w.d_tpl_key }) HIPCHK(c, ws_alloc(w, *b, nf * nb * sizeof(uint32_t)));
     HIPCHK(c, ws_alloc(w, w.d_tpl_flow, av1mi_tpl_flow_entries(r.cw, r.ch, (int)nf) * sizeof(unsigned long long)));
     HIPCHK(c, ws_alloc(w, w.d_tpl_beta, nf * nsb * sizeof(uint16_t)));
+  }
+  if (r.fg_estimate && (!w.d_fg || !w.h_fg)) {
+    HIPCHK(c, ws_alloc(w, w.d_fg, fg_bytes(nf * (size_t)av1mi_fg_blocks((int)p.width) * av1mi_fg_blocks((int)p.height))));
+    HIPCHK(c, ws_alloc(w, w.h_fg, FG_RESULT_BYTES, true));
   }
   if (p.cdef_search && (!w.d_cdef_err || !w.d_cdef_idx || !w.d_cdef_sel)) {
     HIPCHK(c, ws_alloc(w, w.d_cdef_err, nf * nsb * 24 * sizeof(unsigned long long)));
@@ -539,6 +544,37 @@ int av1mi_tpl_analysis(av1mi_ctx *c, const av1mi_params *params, const void *fra
   rc = t.finish(c, "temporal-dependency");   // (drains the stream: `sum` has arrived)
   if (rc == AV1MI_OK && mean_beta) *mean_beta = (uint32_t)av1mi_tpl_mean_beta(sum, n_sb);
   return rc;
+}
+
+// The film-grain estimate alone: the launches the encoder runs on a chunk's source (av1mi_launch_film_grain), on a block of the call's own
+// and without a header to write into.
+int av1mi_film_grain_estimate(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, uint8_t *table,
+                              uint32_t *counts, uint8_t *blocks) {
+  if (!c || !frames || n_frames == 0) return AV1MI_E_INVALID_ARG;
+  Resolved r;
+  int rc = resolve(params, &r);
+  if (rc || !r.fg_estimate) { set_err(c, rc ? "invalid parameters" : "film_grain does not ask for the estimate"); return rc ? rc : AV1MI_E_INVALID_ARG; }
+  if (frames_on_device && ((uintptr_t)frames & 15)) { set_err(c, "device frames must be 16-byte aligned"); return AV1MI_E_INVALID_ARG; }
+  HIPCHK(c, hipSetDevice(c->device));
+  const Av1miDevParams P = dev_params(r, n_frames, 1);
+  hipStream_t s = c->stream;
+  PassBuffers t(s);
+  const size_t n_blk = (size_t)n_frames * av1mi_fg_blocks((int)r.p.width) * av1mi_fg_blocks((int)r.p.height);
+  uint8_t *d_fg = nullptr;
+  t.alloc(d_fg, fg_bytes(n_blk));
+  const void *src = coded_frames(t, r, frames, n_frames, frames_on_device);
+  if (t.ok()) t.e = launch_film_grain(P, r, src, d_fg, nullptr, 0, 0, s);
+  if (t.ok() && table) t.e = hipMemcpyAsync(table, d_fg, AV1MI_FG_TABLE, hipMemcpyDeviceToHost, s);
+  if (t.ok() && counts) t.e = hipMemcpyAsync(counts, d_fg + FG_COUNTS_AT, AV1MI_FG_TABLE * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  if (t.ok() && blocks && n_blk) t.e = hipMemcpyAsync(blocks, d_fg + FG_BLOCKS_AT, n_blk * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  return t.finish(c, "film-grain");
+}
+
+// The film-grain table of the context's last chunk: what download_chunk kept, zeros for a chunk without the estimate.
+int av1mi_film_grain_result(const av1mi_ctx *c, uint8_t *table) {
+  if (!c || !table || !c->last.n_frames) return AV1MI_E_INVALID_ARG;
+  memcpy(table, c->last.fg_table, sizeof(c->last.fg_table));
+  return AV1MI_OK;
 }
 
 // The temporal filter alone: the launch the encoder runs on a chunk's source (av1mi_launch_temporal_filter), on buffers of the call's own.

@@ -19,6 +19,7 @@
 #include "deblock_pieces.h"
 #include "part_inter_rule.h"
 #include "tpl_rule.h"
+#include "fg_rule.h"
 
 using namespace av1mi;
 
@@ -33,8 +34,9 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   // frames have different lengths; frames of one kind differ only in grain_seed)
   size_t str_key = 0, str_inter = 0;   // CDEF strength search: where cdef_select_kernel writes each frame's set
   size_t lf_key = 0, lf_inter = 0;     // deblocking level search: where deblock_decide_kernel writes each frame's levels
-  std::vector<uint8_t> seq = make_sequence_header(r), fh = make_frame_header(r, nullptr, 0, false, &str_key, &lf_key),
-                       fhi = make_frame_header(r, nullptr, 0, true, &str_inter, &lf_inter);
+  size_t fg_key = 0, fg_inter = 0;     // film-grain estimate: where fg_table_kernel writes each frame's table
+  std::vector<uint8_t> seq = make_sequence_header(r), fh = make_frame_header(r, nullptr, 0, false, &str_key, &lf_key, &fg_key),
+                       fhi = make_frame_header(r, nullptr, 0, true, &str_inter, &lf_inter, &fg_inter);
   P.cdef_str_bit[0] = (int)str_key; P.cdef_str_bit[1] = (int)str_inter;
   P.lf_bit[0] = (int)lf_key; P.lf_bit[1] = (int)lf_inter;
   P.seq_hdr_bytes = (int)seq.size(); P.frame_hdr_bytes = (int)fh.size(); P.inter_hdr_bytes = (int)fhi.size();
@@ -50,13 +52,13 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   // Upload what the device does not hold already (consecutive chunks of a job: nothing), from page-locked memory - the copies are
   // asynchronous, and the previous chunk's have completed (download_chunk waits for the main stream).  With the strength search on,
   // cdef_select_kernel writes the strengths into the frame headers on the device: the blob goes up every chunk.  Likewise with the
-  // deblocking level search (deblock_decide_kernel writes the levels).
+  // deblocking level search (deblock_decide_kernel writes the levels) and the film-grain estimate (fg_table_kernel writes the table).
   if (w.hdr_bytes != blob.size() || memcmp(w.h_hdr, blob.data(), blob.size())) {
     w.hdr_bytes = 0;
     memcpy(w.h_hdr, blob.data(), blob.size());
     HIPCHK(c, hipMemcpyAsync(w.d_hdr, w.h_hdr, blob.size(), hipMemcpyHostToDevice, s));
   }
-  w.hdr_bytes = P.cdef_search || P.lf_search ? 0 : blob.size();
+  w.hdr_bytes = P.cdef_search || P.lf_search || r.fg_estimate ? 0 : blob.size();
   if (w.cdf_qidx != r.qidx || w.cdf_bs_log2 != P.max_bs_log2) {
     w.cdf_qidx = -1;
     // the blob, and behind it the regular symbolize variants' compact image of it for this leaf size (av1mi_dev.h: Av1miCdfCompact)
@@ -93,6 +95,9 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   // not a multiple of 8: edge-extend every frame to the coded size (the signalled size stays exact)
   if (r.padded) HIPCHK(c, av1mi_launch_pad(frames_on_device ? frames : w.d_stage, w.d_src, (int)r.p.width, (int)r.p.height, r.cw, r.ch, P.bit_depth, (int)n_frames, 0, s));
   *d_src = frames_on_device && !r.padded ? frames : w.d_src;
+  // the film-grain estimate: the table from the frames as the caller gave them - before the temporal filter - into every frame header,
+  // in front of every other kernel that patches a header (neighbouring fields can share a byte)
+  if (r.fg_estimate) HIPCHK(c, launch_film_grain(P, r, *d_src, w.d_fg, w.d_hdr, fg_key, fg_inter, s));
   // the key frames' temporal filter: in place in the chunk's source - a chunk that is used in place is copied first, the caller's
   // memory is never written.  Everything below and after reads the filtered key frames.
   if (tf_runs(r, n_frames)) {
@@ -340,6 +345,8 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
   const size_t lf_err_bytes = (size_t)n_frames * 3 * AV1MI_LF_CANDS * sizeof(unsigned long long);
   if (e1 == hipSuccess && P.lf_search) e1 = hipMemcpyAsync(w.h_lf, w.d_lf_err, lf_err_bytes, hipMemcpyDeviceToHost, s);
   if (e1 == hipSuccess && P.lf_search) e1 = hipMemcpyAsync(w.h_lf + lf_err_bytes, w.d_lf_sel, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s);
+  // the film-grain estimate's table and counts, likewise
+  if (e1 == hipSuccess && r.fg_estimate) e1 = hipMemcpyAsync(w.h_fg, w.d_fg, FG_RESULT_BYTES, hipMemcpyDeviceToHost, s);
   // the self-guided fit's errors and records, likewise
   const size_t fit_n = (size_t)n_frames * 3 * av1mi_lr_unit_rows(P) * av1mi_lr_unit_cols(P);
   if (e1 == hipSuccess && P.lr_fit_code) e1 = hipMemcpyAsync(w.h_fit, w.d_fit, av1mi_lr_fit_result_bytes(fit_n), hipMemcpyDeviceToHost, s);
@@ -385,7 +392,7 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
 
 // What the context reports of the chunk it has just encoded (av1mi_ctx.cpp's *_result, *_units and *_tiles entry points): the small
 // results download_chunk brought to the host, and what tells where the larger ones still stand on the device.
-static LastChunk record_last_chunk(const av1mi_ctx *c, uint32_t n_frames, bool inter) {
+static LastChunk record_last_chunk(const av1mi_ctx *c, const Resolved &r, uint32_t n_frames, bool inter) {
   const Av1miDevParams &P = c->P; const Workspace &w = c->ws;
   LastChunk L;
   L.n_frames = n_frames;
@@ -403,6 +410,7 @@ static LastChunk record_last_chunk(const av1mi_ctx *c, uint32_t n_frames, bool i
   L.fit_on = P.lr_fit_code != nullptr;   // (the values stay in h_fit until the context's next chunk)
   L.wfit_on = P.lr_wfit_code != nullptr;
   if (!inter && sym_order_on(c)) L.sym_tiles = n_frames * (uint32_t)(P.tile_rows * P.tile_cols);   // (the all-key schedules' table)
+  if (r.fg_estimate) memcpy(L.fg_table, w.h_fg, sizeof(L.fg_table));
   if (P.part_map) { L.pi_keys = c->part_inter; L.pi_frames = n_frames; L.pi_units = (uint32_t)(P.b8_rows * P.b8_cols); L.pi_sbs = (uint32_t)(P.sb_rows * P.sb_cols); }
   return L;
 }
@@ -437,7 +445,7 @@ static int run_chunk(av1mi_ctx *c, const av1mi_params *params, const void *frame
                                 reinterpret_cast<unsigned long long *>(w.d_record + 1), w.d_hdr, w.d_out, &w.d_record->overflow, stage, c->stream));
   HIPCHK(c, hipEventRecord(c->ev[EV_PACK_DONE], c->stream));
   rc = download_chunk(c, r, n_frames, frames_on_device, out, frame_sizes, recon, report);
-  if (rc == AV1MI_OK) c->last = record_last_chunk(c, n_frames, inter);
+  if (rc == AV1MI_OK) c->last = record_last_chunk(c, r, n_frames, inter);
   return rc;
 }
 

@@ -50,6 +50,15 @@ hipError_t av1mi_launch_aq(const Av1miDevParams *P, const void *frames, uint16_t
 // chunk's sum of beta.  `frames` must be a 16-byte aligned device pointer (anything else is refused); it is only read
 hipError_t av1mi_launch_tpl(const Av1miDevParams *P, const void *frames, uint32_t *intra, uint32_t *inter, uint32_t *key, unsigned long long *flow,
                             uint16_t *beta, hipStream_t stream);
+// the film-grain estimate (fg_kernel.hip, fg_rule.h) of the chunk's source: `frames` at the coded size, of which the whole 16x16 blocks of
+// the signalled size are read.  blocks: per [frame][block] the record { bin, v_y, v_u, v_v }, all written (16-byte aligned); parts: scratch
+// for the histograms' parts, AV1MI_FG_PARTS x 24 x 256 counters (16-byte aligned); table, counts: the 24 values [plane][bin], clamped to
+// ceil_y / ceil_c, and the bins' block counts.  hdr_blob: null, or the chunk's header blob, whose
+// frame headers receive the values at bit_key / bit_inter (make_frame_header's fg_bit of the two frame kinds).  `frames` must be a
+// 16-byte aligned device pointer; it is only read
+#define AV1MI_FG_PARTS 64
+hipError_t av1mi_launch_film_grain(const Av1miDevParams *P, const void *frames, uint32_t *blocks, uint32_t *parts, uint8_t *table, uint32_t *counts,
+                                   int ceil_y, int ceil_c, uint8_t *hdr_blob, int bit_key, int bit_inter, hipStream_t stream);
 // the key frames' temporal filter (tf_kernel.hip, tf_rule.h), in place in `frames` at the coded size: every key frame of the chunk is
 // replaced by its filter over up to tf_frames followers at tf_strength, range P->me_range, and re-extended past the signalled size.
 // `frames` must be a 16-byte aligned device pointer (both callers pass an allocation of their own; anything else is refused).

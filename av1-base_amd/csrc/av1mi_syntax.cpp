@@ -18,6 +18,7 @@
 #include "aq_rule.h"
 #include "tpl_rule.h"
 #include "tf_rule.h"
+#include "fg_rule.h"
 
 namespace av1mi {
 
@@ -76,7 +77,15 @@ int resolve(const av1mi_params *in, Resolved *r) {
   r->tpl = (int)AV1MI_TPL_STRENGTH(p.cq_level);
   if ((p.cq_level & ~0x77FFu) || r->aq > AV1MI_AQ_MAX_STRENGTH || r->tpl > AV1MI_TPL_MAX_STRENGTH) return AV1MI_E_INVALID_ARG;
   p.cq_level = AV1MI_CQ_LEVEL(p.cq_level);
-  if (p.cq_level == 0 || p.cq_level > 63 || p.film_grain > 50) return AV1MI_E_INVALID_ARG;
+  if (p.cq_level == 0 || p.cq_level > 63) return AV1MI_E_INVALID_ARG;
+  // film_grain bit 8 (AV1MI_FILM_GRAIN_ESTIMATE): the table is estimated from the chunk's source, the low byte N = 1 .. 50 its ceiling;
+  // nothing above bit 8, and without it 0 .. 50 as ever
+  r->fg_estimate = (p.film_grain & 0x100u) ? 1 : 0;
+  if (r->fg_estimate) {
+    if ((p.film_grain >> 9) || (p.film_grain & 0xFFu) < 1 || (p.film_grain & 0xFFu) > AV1MI_FG_MAX_N) return AV1MI_E_INVALID_ARG;
+    p.film_grain &= 0xFFu;
+  }
+  if (p.film_grain > AV1MI_FG_MAX_N) return AV1MI_E_INVALID_ARG;
   if (p.keyint == 0) p.keyint = 1;
   if (p.me_range == 0) p.me_range = 8;
   if (p.me_range != 8 && p.me_range != 16) return AV1MI_E_INVALID_ARG;
@@ -222,7 +231,11 @@ std::vector<uint8_t> make_sequence_header(const Resolved &r) {
 // lf_bit (optional): bit offset of loop_filter_level[0] - with the level search on (deblock = 2) the header carries the pool's D = 0
 // entries as placeholders, max(g, 1), max(g, 1), g, g, and deblock_decide_kernel overwrites those 24 bits in the frame's slot (luma
 // never picks 0, so all four fields are coded whatever is chosen)
-std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint32_t frame_number, bool inter, size_t *cdef_str_bit, size_t *lf_bit) {
+// fg_bit (optional): bit offset of the first luma point of film_grain_params - with the estimate on (film_grain bit 8) the table has eight
+// points per plane at x = 16 + 32 k (fg_rule.h) whose values the header carries at the ceiling, 2 N luma / N chroma, as placeholders, and
+// fg_table_kernel overwrites those 24 values in every frame's slot
+std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint32_t frame_number, bool inter, size_t *cdef_str_bit, size_t *lf_bit,
+                                       size_t *fg_bit) {
   const av1mi_params &p = r.p;
   BitWriter b;
   b.put(0, 1);  // show_existing_frame
@@ -321,9 +334,20 @@ std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint
     b.put(1, 1);                                              // apply_grain
     b.put((7391u + 173u * (p.first_frame + frame_number)) & 0xFFFFu, 16);  // grain_seed
     if (inter) b.put(1, 1);                                   // update_grain (implied on key frames)
-    b.put(2, 4); b.put(0, 8); b.put(sy, 8); b.put(255, 8); b.put(sy, 8);  // num_y_points + points
-    b.put(0, 1);                                              // chroma_scaling_from_luma
-    for (int pl = 0; pl < 2; pl++) { b.put(2, 4); b.put(0, 8); b.put(sc, 8); b.put(255, 8); b.put(sc, 8); }
+    if (r.fg_estimate) {                                      // eight points per plane, the ceiling as placeholders
+      b.put(AV1MI_FG_BINS, 4);                                // num_y_points
+      if (fg_bit) *fg_bit = b.bits;
+      for (int k = 0; k < AV1MI_FG_BINS; k++) { b.put((uint32_t)av1mi_fg_point_x(k), 8); b.put(sy, 8); }
+      b.put(0, 1);                                            // chroma_scaling_from_luma
+      for (int pl = 0; pl < 2; pl++) {
+        b.put(AV1MI_FG_BINS, 4);                              // num_cb_points, num_cr_points
+        for (int k = 0; k < AV1MI_FG_BINS; k++) { b.put((uint32_t)av1mi_fg_point_x(k), 8); b.put(sc, 8); }
+      }
+    } else {
+      b.put(2, 4); b.put(0, 8); b.put(sy, 8); b.put(255, 8); b.put(sy, 8);  // num_y_points + points
+      b.put(0, 1);                                              // chroma_scaling_from_luma
+      for (int pl = 0; pl < 2; pl++) { b.put(2, 4); b.put(0, 8); b.put(sc, 8); b.put(255, 8); b.put(sc, 8); }
+    }
     b.put(3, 2);                                              // grain_scaling_minus_8
     b.put(0, 2);                                              // ar_coeff_lag
     b.put(128, 8); b.put(128, 8);                             // ar_coeffs_cb/cr_plus_128[0]

@@ -63,6 +63,10 @@ typedef struct av1mi_ctx av1mi_ctx;
 #define AV1MI_ME_PRESEARCH(v) ((uint32_t)(v) & 1u)
 #define AV1MI_TF_FRAMES(v) (((uint32_t)(v) >> 8) & 7u)
 #define AV1MI_TF_STRENGTH(v) (((uint32_t)(v) >> 12) & 7u)
+/* av1mi_params.film_grain with the table estimated from the chunk's source: N = 1 .. 50 stays the ceiling of its values */
+#define AV1MI_FILM_GRAIN_ESTIMATE(n) ((uint32_t)(n) | 0x100u)
+#define AV1MI_FILM_GRAIN_ESTIMATED(v) ((((uint32_t)(v)) >> 8) & 1u)
+#define AV1MI_FILM_GRAIN_LEVEL(v) ((uint32_t)(v) & 0xFFu)
 
 /* Operating point.  Replaces the reference's single constant
  *   SVT_PARAMS = "--crf 8 --preset 3 --film-grain 20 ... --keyint 240 --lookahead 40"
@@ -102,7 +106,19 @@ typedef struct {
   uint32_t intra_mode_mask; /* bit m = luma intra mode m is a candidate (AV1 mode numbering); 0 = default {DC, V, H} */
   uint32_t film_grain;      /* "--film-grain N" (av1an.rs:14): 0 = off; N = 1..50 writes a film-grain table into every
                                frame header (2-point scaling functions, value 2N luma / N chroma, AR lag 0);
-                               synthesis is decoder-side */
+                               synthesis is decoder-side.
+                               bit 8 with a low byte N = 1..50 (AV1MI_FILM_GRAIN_ESTIMATE(N)): the table is
+                               estimated per chunk from the chunk's own source, on the GPU, as SVT-AV1's "--film-grain N" measures
+                               its source - per plane eight points at x = 16 + 32 k whose values are, per luma intensity bin, the
+                               lower quartile over the chunk's whole 16x16 blocks (with their 8x8 chroma blocks) of a noise estimate
+                               that is blind to planes and ramps, scaled to the table's units (fg_rule.h).  N stays the ceiling: no
+                               luma value exceeds 2N and no chroma value N, the fixed table's values, so the estimate never adds
+                               more grain than film_grain = N - on a clean source it adds less, down to none.  The same table goes
+                               into every frame of the chunk; the frame header is 288 bits longer than the fixed mode's, whatever
+                               the content; tile data and reconstruction are those of the fixed mode.  av1mi_write_headers returns
+                               the header with the ceiling's values, av1mi_film_grain_result the chunk's table.  Bit 8 with a low
+                               byte of 0 or above 50, any bit above 8, and 51..255 are refused with AV1MI_E_INVALID_ARG.  A context
+                               may switch the mode from chunk to chunk */
   uint32_t first_frame;     /* number of the chunk's first frame inside the clip (seeds grain_seed per frame) */
   uint32_t me_range;        /* inter frames: motion search range in luma samples, 8 or 16 (0 = 8) */
   uint32_t enable_lr;       /* 1 = loop restoration on luma (Wiener, 64x64 units, each unit off or one of 3 filters by SSE);
@@ -301,6 +317,20 @@ int av1mi_tpl_analysis(av1mi_ctx *ctx, const av1mi_params *params, const void *f
  * encoder sees with the filter on passes them this call's output. */
 int av1mi_temporal_filter(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames,
                           int frames_on_device, void *out, uint32_t *mv);
+
+/* ---- the film-grain estimate on its own ---------------------------------------------------------
+ * What av1mi_encode_chunk runs on a chunk's source when av1mi_params.film_grain carries bit 8 (AV1MI_FILM_GRAIN_ESTIMATE): the same
+ * launches on the same frames, taken as one chunk.  Every output is optional, host memory.  table[plane * 8 + k]: the value of point k
+ * (x = 16 + 32 k) of plane 0 .. 2 (Y, U, V), what the chunk's frame headers carry.  counts[plane * 8 + k]: the blocks of luma bin k
+ * (equal for the three planes); a bin below 16 blocks took its value from the nearest bin that has them.  blocks: per frame f and whole
+ * 16x16 block b of the signalled size (nb = (width / 16) * (height / 16) blocks in raster order), at [(f * nb + b) * 4 + 0..3]:
+ * { bin, v_y, v_u, v_v }, the block's luma bin and its three noise values before the quartile and the ceiling.  AV1MI_E_INVALID_ARG
+ * without bit 8; the arguments are checked before a device is touched.  Like av1mi_aq_qindex it looks at the frames it is given. */
+int av1mi_film_grain_estimate(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
+                              uint8_t *table, uint32_t *counts, uint8_t *blocks);
+/* The table the frame headers of the context's last successfully encoded chunk carry, layout as above; zeros for a chunk without the
+ * estimate.  The values arrive with the chunk's other small results: the call only copies them.  AV1MI_E_INVALID_ARG without such a chunk. */
+int av1mi_film_grain_result(const av1mi_ctx *ctx, uint8_t *table);
 
 /* ---- deblocking levels of the last chunk ---------------------------------------------------
  * loop_filter_level[0..3] (luma vertical edges, luma horizontal, U, V) every frame of the context's last successfully encoded

@@ -71,7 +71,15 @@ pub const fn me_tf(presearch: u32, frames: u32, strength: u32) -> u32 { (presear
 pub const fn me_presearch_of(v: u32) -> u32 { v & 1 }
 pub const fn tf_frames_of(v: u32) -> u32 { (v >> 8) & 7 }
 pub const fn tf_strength_of(v: u32) -> u32 { (v >> 12) & 7 }
-type ProgressCb = Option<extern "C" fn(user: *mut c_void, done: u32, total: u32, fps: f64, bytes: u64)>;
+// include/av1mi.h: AV1MI_FILM_GRAIN_ESTIMATE / AV1MI_FILM_GRAIN_ESTIMATED / AV1MI_FILM_GRAIN_LEVEL - film_grain bit 8: the film-grain table is
+// estimated per chunk from the chunk's source, N = 1..50 stays the ceiling of its values (run_mi355x keeps the fixed table: the default)
+pub const AV1MI_FILM_GRAIN_MAX: u32 = 50;
+pub const fn film_grain_estimate(n: u32) -> u32 { n | 0x100 }
+pub const fn film_grain_estimated(v: u32) -> u32 { (v >> 8) & 1 }
+pub const fn film_grain_level_of(v: u32) -> u32 { v & 0xFF }
+#[repr(C)]
+pub struct Av1miCtx { _opaque: [u8; 0] }   // include/av1mi.h: av1mi_ctx
+type ProgressCb =Option<extern "C" fn(user: *mut c_void, done: u32, total: u32, fps: f64, bytes: u64)>;
 
 #[link(name = "av1mi")]
 extern "C" {
@@ -79,6 +87,11 @@ extern "C" {
     fn av1mi_struct_sizes(sizes: *mut u32, cap: u32) -> u32;
     fn av1mi_default_params(p: *mut Av1miParams, w: u32, h: u32, bit_depth: u32);
     fn av1mi_encode_file(job: *const Av1miJob, cb: ProgressCb, user: *mut c_void, total: *mut Av1miReport) -> c_int;
+    // the film-grain estimate of `n_frames` frames taken as one chunk: table[24] and counts[24] as [plane][bin], blocks 4 bytes per whole
+    // 16x16 block and frame { bin, v_y, v_u, v_v }, every output optional (null); and the table of a context's last chunk
+    pub fn av1mi_film_grain_estimate(ctx: *mut Av1miCtx, params: *const Av1miParams, frames: *const c_void, n_frames: u32, frames_on_device: c_int,
+                                     table: *mut u8, counts: *mut u32, blocks: *mut u8) -> c_int;
+    pub fn av1mi_film_grain_result(ctx: *const Av1miCtx, table: *mut u8) -> c_int;
 }
 
 // Layout pin (include/av1mi.h: av1mi_struct_sizes).  Compile time: the sizes this file was written against (ABI version 8, LP64);
