@@ -38,7 +38,7 @@ E_INVALID_ARG, E_NO_DEVICE, E_HIP, E_OOM, E_OVERFLOW, E_FORMAT, E_UNSUPPORTED = 
 ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", "av1mi_last_error", "av1mi_encode_chunk",
                "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units", "av1mi_sym_order_result", "av1mi_sym_order_tiles", "av1mi_inter_partition_result", "av1mi_inter_partition_units",
                "av1mi_lr_rd_result", "av1mi_lr_rd_units", "av1mi_temporal_filter", "av1mi_tpl_analysis", "av1mi_film_grain_estimate",
-               "av1mi_film_grain_result"]
+               "av1mi_film_grain_result", "av1mi_film_grain_denoise"]
 
 
 class Params(C.Structure):
@@ -121,6 +121,7 @@ _lib.av1mi_tpl_analysis.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C
 _lib.av1mi_film_grain_estimate.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32),
                                             C.POINTER(C.c_uint8)]
 _lib.av1mi_film_grain_result.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
+_lib.av1mi_film_grain_denoise.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8), C.c_void_p, C.POINTER(C.c_uint8)]
 _lib.av1mi_lf_search_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
 _lib.av1mi_lr_fit_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint64)]
 _lib.av1mi_lr_fit_units.argtypes = [C.c_void_p]
@@ -215,6 +216,19 @@ def film_grain_estimated(v):
     return (v >> 8) & 1
 
 
+FILM_GRAIN_DENOISE = 0x400    # include/av1mi.h: bit 10 of film_grain, with bit 8 - the source is denoised by the estimated table
+
+
+def film_grain_denoise(n):
+    """include/av1mi.h: AV1MI_FILM_GRAIN_DENOISE - the film_grain field with the estimate and the denoiser on and N = 1 .. 50 as the ceiling"""
+    return n | FILM_GRAIN_ESTIMATE | FILM_GRAIN_DENOISE
+
+
+def film_grain_denoised(v):
+    """include/av1mi.h: AV1MI_FILM_GRAIN_DENOISED"""
+    return (v >> 10) & 1
+
+
 def film_grain_level_of(v):
     """include/av1mi.h: AV1MI_FILM_GRAIN_LEVEL"""
     return v & 0xFF
@@ -277,9 +291,10 @@ def lr_unit_grid(width, height, shift=0):
 
 
 def default_params(width, height, bit_depth=8, aq_strength=None, tpl_strength=None, lr_fit=None, lr_wiener_fit=False, lr_unit_shift=0, lr_rd=None, tf_frames=None,
-                   tf_strength=None, film_grain_estimate=None, **kw):
+                   tf_strength=None, film_grain_estimate=None, film_grain_denoise=None, **kw):
     """film_grain_estimate: N = 1 .. 50 sets film_grain to the estimated table with the ceiling N (the function of that name), True turns
-    the estimate on for the film_grain keyword's N; aq_strength, tpl_strength: packed into cq_level beside the CQ level (cq_aq_tpl); lr_fit: True or a mask of parameter sets, packed into enable_lr
+    the estimate on for the film_grain keyword's N; film_grain_denoise: likewise, with the source denoised by that table (the function of
+    that name); aq_strength, tpl_strength: packed into cq_level beside the CQ level (cq_aq_tpl); lr_fit: True or a mask of parameter sets, packed into enable_lr
     (lr_fit_field); lr_wiener_fit: True sets enable_lr's bit 10 (LR_WIENER_FIT); lr_unit_shift: 1 / 2 sets enable_lr's bits 12-13
     (LR_UNIT_128 / LR_UNIT_256); lr_rd: a scale s = 0 .. 3 sets the rate term of the unit decisions (lr_rd_field); tf_frames, tf_strength:
     the key frames' temporal filter, packed into me_presearch beside the pre-search's switch (me_tf); every other keyword sets the
@@ -288,6 +303,8 @@ def default_params(width, height, bit_depth=8, aq_strength=None, tpl_strength=No
     _lib.av1mi_default_params(C.byref(p), width, height, bit_depth)
     if film_grain_estimate is not None and film_grain_estimate is not False:
         kw["film_grain"] = FILM_GRAIN_ESTIMATE | (kw.get("film_grain", p.film_grain) if film_grain_estimate is True else int(film_grain_estimate))
+    if film_grain_denoise is not None and film_grain_denoise is not False:
+        kw["film_grain"] = FILM_GRAIN_ESTIMATE | FILM_GRAIN_DENOISE | (kw.get("film_grain", p.film_grain) if film_grain_denoise is True else int(film_grain_denoise))
     if tf_frames is not None or tf_strength is not None:
         kw["me_presearch"] = me_tf(kw.get("me_presearch", p.me_presearch), int(tf_frames or 0), int(tf_strength or 0))
     if lr_fit is not None and lr_fit is not False:
@@ -456,6 +473,33 @@ class Context:
                                             blocks.ctypes.data_as(C.POINTER(C.c_uint8)) if want_blocks and blocks.size else None)
         _raise_for(rc, self.last_error())
         return table, counts, blocks
+
+    def film_grain_denoise(self, params, frames, n_frames, on_device=False, out_ptr=None, use_table=None):
+        """The film-grain denoiser alone (include/av1mi.h: av1mi_film_grain_denoise).  Host frames (bytes-like / numpy): returns (the
+        denoised chunk as a numpy uint8 array of the input's bytes, table).  on_device=True: `frames` and `out_ptr` are device pointers;
+        returns (None, table).  table: numpy uint8 [plane][8], the values the filter ran with; use_table: 24 values ([plane][8]) it takes
+        instead of the chunk's estimate."""
+        import numpy as np
+        bps = 2 if params.bit_depth > 8 else 1
+        nbytes = params.width * params.height * 3 // 2 * bps * n_frames
+        table = np.zeros((3, 8), dtype=np.uint8)
+        given = None
+        if use_table is not None:
+            given = np.ascontiguousarray(np.asarray(use_table, dtype=np.uint8).reshape(24))
+        out = None
+        fptr, keep = _frames_ptr(frames, on_device)
+        if on_device:
+            optr = C.c_void_p(int(out_ptr)) if out_ptr is not None else None
+        else:
+            if len(keep) != nbytes:
+                raise ValueError("frames: expected %d bytes, got %d" % (nbytes, len(keep)))
+            out = np.empty(nbytes, dtype=np.uint8)
+            optr = out.ctypes.data_as(C.c_void_p)
+        rc = _lib.av1mi_film_grain_denoise(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0,
+                                           given.ctypes.data_as(C.POINTER(C.c_uint8)) if given is not None else None, optr,
+                                           table.ctypes.data_as(C.POINTER(C.c_uint8)))
+        _raise_for(rc, self.last_error())
+        return out, table
 
     def film_grain_result(self):
         """The film-grain table of the last encoded chunk (include/av1mi.h: av1mi_film_grain_result): numpy uint8 [plane][8], zeros for

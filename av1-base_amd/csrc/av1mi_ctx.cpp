@@ -100,7 +100,8 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   }
   const size_t nf = w.cap_frames;
   const size_t unit_cap = 3 * nf * nsb + 64;   // restoration units the choices, sums and fits have room for: three planes of 64x64 units
-  if (r.padded && !w.d_stage) HIPCHK(c, ws_alloc(w, w.d_stage, caller_bytes(r, nf)));
+  // the caller's frames in front of a pass that writes d_src from them: the edge extension, and the film-grain denoiser at any size
+  if ((r.padded || r.fg_denoise) && !w.d_stage) HIPCHK(c, ws_alloc(w, w.d_stage, caller_bytes(r, nf)));
   if (p.partition_search && !w.d_part) HIPCHK(c, ws_alloc(w, w.d_part, nf * nsb * sizeof(uint32_t)));
   if (p.me_presearch && !w.d_quarter) {
     HIPCHK(c, ws_alloc(w, w.d_quarter, nf * (size_t)(r.cw / 4) * (r.ch / 4) * sizeof(uint16_t)));
@@ -568,6 +569,51 @@ int av1mi_film_grain_estimate(av1mi_ctx *c, const av1mi_params *params, const vo
   if (t.ok() && counts) t.e = hipMemcpyAsync(counts, d_fg + FG_COUNTS_AT, AV1MI_FG_TABLE * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
   if (t.ok() && blocks && n_blk) t.e = hipMemcpyAsync(blocks, d_fg + FG_BLOCKS_AT, n_blk * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
   return t.finish(c, "film-grain");
+}
+
+// The film-grain denoiser alone: the launches the encoder runs on a chunk's source (av1mi_launch_film_grain unless the caller gives the
+// table, av1mi_launch_fg_denoise), on buffers of the call's own; the result cropped to the caller's layout.
+int av1mi_film_grain_denoise(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, const uint8_t *use_table,
+                             void *out, uint8_t *table) {
+  if (!c || !frames || !out || n_frames == 0) return AV1MI_E_INVALID_ARG;
+  Resolved r;
+  int rc = resolve(params, &r);
+  if (rc || !r.fg_denoise) { set_err(c, rc ? "invalid parameters" : "film_grain does not ask for the denoiser"); return rc ? rc : AV1MI_E_INVALID_ARG; }
+  if (frames_on_device && (((uintptr_t)frames | (uintptr_t)out) & 15)) { set_err(c, "device frames must be 16-byte aligned"); return AV1MI_E_INVALID_ARG; }
+  HIPCHK(c, hipSetDevice(c->device));
+  const Av1miDevParams P = dev_params(r, n_frames, 1);
+  hipStream_t s = c->stream;
+  PassBuffers t(s);
+  const size_t in_bytes = caller_bytes(r, n_frames), coded_bytes = (size_t)n_frames * r.cw * r.ch * 3 / 2 * (r.p.bit_depth > 8 ? 2 : 1);
+  const size_t n_blk = (size_t)n_frames * av1mi_fg_blocks((int)r.p.width) * av1mi_fg_blocks((int)r.p.height);
+  uint8_t *d_fg = nullptr;
+  void *d_in = nullptr, *d_pad = nullptr, *d_den = nullptr, *d_crop = nullptr;
+  t.alloc(d_fg, fg_bytes(n_blk));
+  t.alloc(d_den, coded_bytes);
+  const void *tight = frames;   // the frames as the caller gave them, on the device: what the denoiser reads
+  if (!frames_on_device) {
+    if (t.alloc(d_in, in_bytes)) t.e = hipMemcpyAsync(d_in, frames, in_bytes, hipMemcpyHostToDevice, s);
+    tight = d_in;
+  }
+  if (use_table) {
+    if (t.ok()) t.e = hipMemcpyAsync(d_fg, use_table, AV1MI_FG_TABLE, hipMemcpyHostToDevice, s);
+  } else {   // the estimate reads the coded size
+    const void *coded = tight;
+    if (r.padded) {
+      t.alloc(d_pad, coded_bytes);
+      if (t.ok()) t.e = av1mi_launch_pad(tight, d_pad, (int)r.p.width, (int)r.p.height, r.cw, r.ch, (int)r.p.bit_depth, (int)n_frames, 0, s);
+      coded = d_pad;
+    }
+    if (t.ok()) t.e = launch_film_grain(P, r, coded, d_fg, nullptr, 0, 0, s);
+  }
+  if (t.ok()) t.e = av1mi_launch_fg_denoise(&P, tight, d_den, d_fg, s);
+  if (r.padded) {
+    t.alloc(d_crop, in_bytes);
+    if (t.ok()) t.e = av1mi_launch_pad(d_den, d_crop, (int)r.p.width, (int)r.p.height, r.cw, r.ch, (int)r.p.bit_depth, (int)n_frames, 1, s);
+  }
+  if (t.ok()) t.e = hipMemcpyAsync(out, r.padded ? d_crop : d_den, in_bytes, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s);
+  if (t.ok() && table) t.e = hipMemcpyAsync(table, d_fg, AV1MI_FG_TABLE, hipMemcpyDeviceToHost, s);
+  return t.finish(c, "film-grain denoise");
 }
 
 // The film-grain table of the context's last chunk: what download_chunk kept, zeros for a chunk without the estimate.

@@ -90,18 +90,28 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   if (P.lr_fit_code) HIPCHK(c, hipMemsetAsync(w.d_fit, 0, av1mi_lr_fit_bytes(fit_chunk_units(r, n_frames)), s));
   if (P.lr_wfit_code) HIPCHK(c, hipMemsetAsync(w.d_wfit, 0, av1mi_lr_wfit_bytes(fit_chunk_units(r, n_frames)), s));
   HIPCHK(c, hipEventRecord(c->ev[EV_START], s));
-  // the caller's frames are used in place if they are on the device at the coded size; a padded chunk arrives in the stage
-  if (!frames_on_device) HIPCHK(c, hipMemcpyAsync(r.padded ? w.d_stage : w.d_src, frames, caller_bytes(r, n_frames), hipMemcpyHostToDevice, s));
+  // the caller's frames are used in place if they are on the device at the coded size; a padded chunk arrives in the stage, and so does
+  // a chunk the film-grain denoiser will write d_src from
+  const bool staged = r.padded || r.fg_denoise;
+  if (!frames_on_device) HIPCHK(c, hipMemcpyAsync(staged ? w.d_stage : w.d_src, frames, caller_bytes(r, n_frames), hipMemcpyHostToDevice, s));
+  const void *tight = frames_on_device ? frames : w.d_stage;   // (with `staged`) the frames as the caller gave them, on the device
   // not a multiple of 8: edge-extend every frame to the coded size (the signalled size stays exact)
-  if (r.padded) HIPCHK(c, av1mi_launch_pad(frames_on_device ? frames : w.d_stage, w.d_src, (int)r.p.width, (int)r.p.height, r.cw, r.ch, P.bit_depth, (int)n_frames, 0, s));
-  *d_src = frames_on_device && !r.padded ? frames : w.d_src;
-  // the film-grain estimate: the table from the frames as the caller gave them - before the temporal filter - into every frame header,
-  // in front of every other kernel that patches a header (neighbouring fields can share a byte)
+  if (r.padded) HIPCHK(c, av1mi_launch_pad(tight, w.d_src, (int)r.p.width, (int)r.p.height, r.cw, r.ch, P.bit_depth, (int)n_frames, 0, s));
+  *d_src = r.padded ? w.d_src : (staged ? tight : (frames_on_device ? frames : w.d_src));
+  // the film-grain estimate: the table from the frames as the caller gave them - before the denoiser and the temporal filter - into every
+  // frame header, in front of every other kernel that patches a header (neighbouring fields can share a byte)
   if (r.fg_estimate) HIPCHK(c, launch_film_grain(P, r, *d_src, w.d_fg, w.d_hdr, fg_key, fg_inter, s));
+  // the denoiser: the caller's frames filtered by that table, where fg_table_kernel left it, into d_src at the coded size - out of place, the
+  // edge extension in its store (a padded chunk's extension above served the estimate alone).  Everything below and after reads the
+  // denoised chunk
+  if (r.fg_denoise) {
+    HIPCHK(c, av1mi_launch_fg_denoise(&P, tight, w.d_src, w.d_fg, s));
+    *d_src = w.d_src;
+  }
   // the key frames' temporal filter: in place in the chunk's source - a chunk that is used in place is copied first, the caller's
   // memory is never written.  Everything below and after reads the filtered key frames.
   if (tf_runs(r, n_frames)) {
-    if (*d_src != w.d_src) { HIPCHK(c, hipMemcpyAsync(w.d_src, frames, caller_bytes(r, n_frames), hipMemcpyDeviceToDevice, s)); *d_src = w.d_src; }
+    if (*d_src != w.d_src) { HIPCHK(c, hipMemcpyAsync(w.d_src, *d_src, caller_bytes(r, n_frames), hipMemcpyDeviceToDevice, s)); *d_src = w.d_src; }
     HIPCHK(c, av1mi_launch_temporal_filter(&P, w.d_src, w.d_tf_mv, r.tf_frames, r.tf_strength, s));
   }
   // content-driven partition: the split masks of every superblock of the chunk, from the source, before anything walks blocks (the second

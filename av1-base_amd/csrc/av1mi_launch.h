@@ -59,6 +59,11 @@ hipError_t av1mi_launch_tpl(const Av1miDevParams *P, const void *frames, uint32_
 #define AV1MI_FG_PARTS 64
 hipError_t av1mi_launch_film_grain(const Av1miDevParams *P, const void *frames, uint32_t *blocks, uint32_t *parts, uint8_t *table, uint32_t *counts,
                                    int ceil_y, int ceil_c, uint8_t *hdr_blob, int bit_key, int bit_inter, hipStream_t stream);
+// the source denoised by the film-grain table (fg_denoise_kernel.hip, fg_denoise_rule.h), out of place: `frames` as the caller gave them,
+// tight at the signalled size P->true_w x P->true_h, only read; `out` the same frames filtered, at the coded size, samples outside the
+// signalled picture replicating the denoised edge; table: the 24 values [plane][bin] in device memory (av1mi_launch_film_grain's, on the
+// same stream before).  Both frame pointers must be 16-byte aligned device pointers and different blocks
+hipError_t av1mi_launch_fg_denoise(const Av1miDevParams *P, const void *frames, void *out, const uint8_t *table, hipStream_t stream);
 // the key frames' temporal filter (tf_kernel.hip, tf_rule.h), in place in `frames` at the coded size: every key frame of the chunk is
 // replaced by its filter over up to tf_frames followers at tf_strength, range P->me_range, and re-extended past the signalled size.
 // `frames` must be a 16-byte aligned device pointer (both callers pass an allocation of their own; anything else is refused).

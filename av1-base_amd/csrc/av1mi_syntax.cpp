@@ -79,10 +79,13 @@ int resolve(const av1mi_params *in, Resolved *r) {
   p.cq_level = AV1MI_CQ_LEVEL(p.cq_level);
   if (p.cq_level == 0 || p.cq_level > 63) return AV1MI_E_INVALID_ARG;
   // film_grain bit 8 (AV1MI_FILM_GRAIN_ESTIMATE): the table is estimated from the chunk's source, the low byte N = 1 .. 50 its ceiling;
-  // nothing above bit 8, and without it 0 .. 50 as ever
+  // without it 0 .. 50 as ever.  Bit 10 with bit 8 (AV1MI_FILM_GRAIN_DENOISE): the source is denoised by that table before it is coded
+  // (fg_denoise_rule.h).  Nothing in bit 9 or above bit 10, and bit 10 not alone
   r->fg_estimate = (p.film_grain & 0x100u) ? 1 : 0;
+  r->fg_denoise = (p.film_grain & 0x400u) ? 1 : 0;
+  if (r->fg_denoise && !r->fg_estimate) return AV1MI_E_INVALID_ARG;
   if (r->fg_estimate) {
-    if ((p.film_grain >> 9) || (p.film_grain & 0xFFu) < 1 || (p.film_grain & 0xFFu) > AV1MI_FG_MAX_N) return AV1MI_E_INVALID_ARG;
+    if ((p.film_grain & ~0x5FFu) || (p.film_grain & 0xFFu) < 1 || (p.film_grain & 0xFFu) > AV1MI_FG_MAX_N) return AV1MI_E_INVALID_ARG;
     p.film_grain &= 0xFFu;
   }
   if (p.film_grain > AV1MI_FG_MAX_N) return AV1MI_E_INVALID_ARG;

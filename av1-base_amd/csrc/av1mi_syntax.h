@@ -34,7 +34,8 @@ struct Resolved {
   int lr_unit_shift;                  // enable_lr bits 12-13: luma restoration units of 64 << lr_unit_shift samples (0 .. 2)
   uint32_t lr_lambda;                 // enable_lr bits 14 and 15: the rate term's lambda (lr_rate_rule.h), 0 = the decisions go by the error alone
   int fg_estimate;                    // film_grain bit 8: the film-grain table is estimated per chunk (fg_rule.h); p.film_grain then holds the ceiling N alone
-  int tf_frames, tf_strength;         // me_presearch bits 8-10 and 12-14: the key frames' temporal filter (tf_rule.h), 0 followers = off (p.me_presearch then holds bit 0 alone)
+  int fg_denoise;                     // film_grain bit 10 (with bit 8): the chunk's source is denoised by the estimated table before it is coded (fg_denoise_rule.h)
+  int tf_frames, tf_strength;        // me_presearch bits 8-10 and 12-14: the key frames' temporal filter (tf_rule.h), 0 followers = off (p.me_presearch then holds bit 0 alone)
 };
 
 int resolve(const av1mi_params *in, Resolved *r);

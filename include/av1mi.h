@@ -67,6 +67,9 @@ typedef struct av1mi_ctx av1mi_ctx;
 #define AV1MI_FILM_GRAIN_ESTIMATE(n) ((uint32_t)(n) | 0x100u)
 #define AV1MI_FILM_GRAIN_ESTIMATED(v) ((((uint32_t)(v)) >> 8) & 1u)
 #define AV1MI_FILM_GRAIN_LEVEL(v) ((uint32_t)(v) & 0xFFu)
+/* ... and with the source denoised by that table before it is coded (bit 10, only together with bit 8) */
+#define AV1MI_FILM_GRAIN_DENOISE(n) ((uint32_t)(n) | 0x100u | 0x400u)
+#define AV1MI_FILM_GRAIN_DENOISED(v) ((((uint32_t)(v)) >> 10) & 1u)
 
 /* Operating point.  Replaces the reference's single constant
  *   SVT_PARAMS = "--crf 8 --preset 3 --film-grain 20 ... --keyint 240 --lookahead 40"
@@ -116,9 +119,19 @@ typedef struct {
                                more grain than film_grain = N - on a clean source it adds less, down to none.  The same table goes
                                into every frame of the chunk; the frame header is 288 bits longer than the fixed mode's, whatever
                                the content; tile data and reconstruction are those of the fixed mode.  av1mi_write_headers returns
-                               the header with the ceiling's values, av1mi_film_grain_result the chunk's table.  Bit 8 with a low
-                               byte of 0 or above 50, any bit above 8, and 51..255 are refused with AV1MI_E_INVALID_ARG.  A context
-                               may switch the mode from chunk to chunk */
+                               the header with the ceiling's values, av1mi_film_grain_result the chunk's table.
+                               bit 10 together with bit 8 (AV1MI_FILM_GRAIN_DENOISE(N)): the second half
+                               of "--film-grain N" - the chunk is coded from a source with the measured grain taken out, and the
+                               decoder puts it back by synthesis.  After the estimate, which still reads the frames as the caller
+                               gave them, every sample of the three planes is replaced by a weighted mean over its 5x5 window
+                               whose weights fall linearly with the difference from the sample and reach 0 at T = 4 sigma of the
+                               grain the table signals at the sample's luma (fg_denoise_rule.h) - a zero table changes nothing,
+                               no sample moves by T or more.  The key frames' temporal filter, the partition, the adaptive
+                               quantisation and the encoder proper see the denoised chunk; av1mi_report.sse and psnr are against
+                               it (the coded source, as with the temporal filter).  Headers and av1mi_film_grain_result are the
+                               estimate mode's; the caller's frames are never written.
+                               Bit 8 with a low byte of 0 or above 50, bit 10 without bit 8, bit 9, any bit above 10, and 51..255 are
+                               refused with AV1MI_E_INVALID_ARG.  A context may switch the mode from chunk to chunk */
   uint32_t first_frame;     /* number of the chunk's first frame inside the clip (seeds grain_seed per frame) */
   uint32_t me_range;        /* inter frames: motion search range in luma samples, 8 or 16 (0 = 8) */
   uint32_t enable_lr;       /* 1 = loop restoration on luma (Wiener, 64x64 units, each unit off or one of 3 filters by SSE);
@@ -228,7 +241,8 @@ typedef struct {
   uint32_t frames;
   uint64_t bytes;
   double sse[3];            /* sum of squared error of the reconstruction, per plane: against the coded source - with the temporal
-                               filter on, the filtered key frames (av1mi_temporal_filter returns them), not the caller's */
+                               filter on, the filtered key frames (av1mi_temporal_filter returns them), with the film-grain denoiser
+                               on, the denoised frames (av1mi_film_grain_denoise returns them), not the caller's */
   double psnr[3];           /* ... and the PSNR from it, likewise */
   /* device time per stage, milliseconds (HIP events on the encoder's stream) */
   float ms_h2d, ms_recon, ms_cdef, ms_entropy, ms_pack, ms_d2h, ms_total;
@@ -331,6 +345,16 @@ int av1mi_film_grain_estimate(av1mi_ctx *ctx, const av1mi_params *params, const 
 /* The table the frame headers of the context's last successfully encoded chunk carry, layout as above; zeros for a chunk without the
  * estimate.  The values arrive with the chunk's other small results: the call only copies them.  AV1MI_E_INVALID_ARG without such a chunk. */
 int av1mi_film_grain_result(const av1mi_ctx *ctx, uint8_t *table);
+
+/* ---- the film-grain denoiser on its own ------------------------------------------------------------
+ * What av1mi_encode_chunk runs on a chunk's source when av1mi_params.film_grain carries bits 8 and 10 (AV1MI_FILM_GRAIN_DENOISE): the
+ * same launches on the same frames, taken as one chunk.  out: the denoised chunk at the signalled size, in the layout and residency of
+ * `frames` (device pointers 16-byte aligned, a block other than `frames`).  table (optional, host): the 24 values [plane * 8 + k] the
+ * filter ran with.  use_table (optional, host): 24 values the filter takes as they are instead of the chunk's estimate - no ceiling is
+ * applied and the estimate is skipped.  AV1MI_E_INVALID_ARG without bits 8 and 10; the arguments are checked before a device is touched.
+ * Like av1mi_film_grain_estimate it looks at the frames it is given. */
+int av1mi_film_grain_denoise(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
+                             const uint8_t *use_table, void *out, uint8_t *table);
 
 /* ---- deblocking levels of the last chunk ---------------------------------------------------
  * loop_filter_level[0..3] (luma vertical edges, luma horizontal, U, V) every frame of the context's last successfully encoded

@@ -77,6 +77,9 @@ pub const AV1MI_FILM_GRAIN_MAX: u32 = 50;
 pub const fn film_grain_estimate(n: u32) -> u32 { n | 0x100 }
 pub const fn film_grain_estimated(v: u32) -> u32 { (v >> 8) & 1 }
 pub const fn film_grain_level_of(v: u32) -> u32 { v & 0xFF }
+// AV1MI_FILM_GRAIN_DENOISE / AV1MI_FILM_GRAIN_DENOISED - film_grain bit 10, with bit 8: the source is denoised by the estimated table before it is coded
+pub const fn film_grain_denoise(n: u32) -> u32 { n | 0x100 | 0x400 }
+pub const fn film_grain_denoised(v: u32) -> u32 { (v >> 10) & 1 }
 #[repr(C)]
 pub struct Av1miCtx { _opaque: [u8; 0] }   // include/av1mi.h: av1mi_ctx
 type ProgressCb =Option<extern "C" fn(user: *mut c_void, done: u32, total: u32, fps: f64, bytes: u64)>;
@@ -92,6 +95,10 @@ extern "C" {
     pub fn av1mi_film_grain_estimate(ctx: *mut Av1miCtx, params: *const Av1miParams, frames: *const c_void, n_frames: u32, frames_on_device: c_int,
                                      table: *mut u8, counts: *mut u32, blocks: *mut u8) -> c_int;
     pub fn av1mi_film_grain_result(ctx: *const Av1miCtx, table: *mut u8) -> c_int;
+    // the film-grain denoiser of `n_frames` frames taken as one chunk: `out` the denoised frames in the layout and residency of `frames`,
+    // table[24] (optional) the values the filter ran with, use_table[24] (optional) values it takes instead of the chunk's estimate
+    pub fn av1mi_film_grain_denoise(ctx: *mut Av1miCtx, params: *const Av1miParams, frames: *const c_void, n_frames: u32, frames_on_device: c_int,
+                                    use_table: *const u8, out: *mut c_void, table: *mut u8) -> c_int;
 }
 
 // Layout pin (include/av1mi.h: av1mi_struct_sizes).  Compile time: the sizes this file was written against (ABI version 8, LP64);
