@@ -38,7 +38,7 @@ E_INVALID_ARG, E_NO_DEVICE, E_HIP, E_OOM, E_OVERFLOW, E_FORMAT, E_UNSUPPORTED = 
 ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", "av1mi_last_error", "av1mi_encode_chunk",
                "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units", "av1mi_sym_order_result", "av1mi_sym_order_tiles", "av1mi_inter_partition_result", "av1mi_inter_partition_units",
                "av1mi_lr_rd_result", "av1mi_lr_rd_units", "av1mi_temporal_filter", "av1mi_tpl_analysis", "av1mi_film_grain_estimate",
-               "av1mi_film_grain_result", "av1mi_film_grain_denoise"]
+               "av1mi_film_grain_result", "av1mi_film_grain_denoise", "av1mi_film_grain_ar_estimate", "av1mi_film_grain_ar_result"]
 
 
 class Params(C.Structure):
@@ -121,6 +121,9 @@ _lib.av1mi_tpl_analysis.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C
 _lib.av1mi_film_grain_estimate.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32),
                                             C.POINTER(C.c_uint8)]
 _lib.av1mi_film_grain_result.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
+_lib.av1mi_film_grain_ar_estimate.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_int8), C.POINTER(C.c_uint8),
+                                              C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int64)]
+_lib.av1mi_film_grain_ar_result.argtypes = [C.c_void_p, C.POINTER(C.c_int8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
 _lib.av1mi_film_grain_denoise.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8), C.c_void_p, C.POINTER(C.c_uint8)]
 _lib.av1mi_lf_search_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
 _lib.av1mi_lr_fit_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint64)]
@@ -229,6 +232,19 @@ def film_grain_denoised(v):
     return (v >> 10) & 1
 
 
+FILM_GRAIN_AR = 0x3000        # include/av1mi.h: bits 12-13 of film_grain, with bit 8 - the lag of the fitted autoregressive coefficients
+
+
+def film_grain_ar(lag):
+    """include/av1mi.h: AV1MI_FILM_GRAIN_AR - the lag 1 .. 3, to be or-ed into film_grain_estimate(n) or film_grain_denoise(n)"""
+    return (lag & 3) << 12
+
+
+def film_grain_ar_lag(v):
+    """include/av1mi.h: AV1MI_FILM_GRAIN_AR_LAG"""
+    return (v >> 12) & 3
+
+
 def film_grain_level_of(v):
     """include/av1mi.h: AV1MI_FILM_GRAIN_LEVEL"""
     return v & 0xFF
@@ -291,8 +307,8 @@ def lr_unit_grid(width, height, shift=0):
 
 
 def default_params(width, height, bit_depth=8, aq_strength=None, tpl_strength=None, lr_fit=None, lr_wiener_fit=False, lr_unit_shift=0, lr_rd=None, tf_frames=None,
-                   tf_strength=None, film_grain_estimate=None, film_grain_denoise=None, **kw):
-    """film_grain_estimate: N = 1 .. 50 sets film_grain to the estimated table with the ceiling N (the function of that name), True turns
+                   tf_strength=None, film_grain_estimate=None, film_grain_denoise=None, film_grain_ar=None, **kw):
+    """film_grain_ar: a lag 1 .. 3 or-ed into the film_grain field the other keywords give (film_grain_ar); film_grain_estimate: N = 1 .. 50 sets film_grain to the estimated table with the ceiling N (the function of that name), True turns
     the estimate on for the film_grain keyword's N; film_grain_denoise: likewise, with the source denoised by that table (the function of
     that name); aq_strength, tpl_strength: packed into cq_level beside the CQ level (cq_aq_tpl); lr_fit: True or a mask of parameter sets, packed into enable_lr
     (lr_fit_field); lr_wiener_fit: True sets enable_lr's bit 10 (LR_WIENER_FIT); lr_unit_shift: 1 / 2 sets enable_lr's bits 12-13
@@ -305,6 +321,8 @@ def default_params(width, height, bit_depth=8, aq_strength=None, tpl_strength=No
         kw["film_grain"] = FILM_GRAIN_ESTIMATE | (kw.get("film_grain", p.film_grain) if film_grain_estimate is True else int(film_grain_estimate))
     if film_grain_denoise is not None and film_grain_denoise is not False:
         kw["film_grain"] = FILM_GRAIN_ESTIMATE | FILM_GRAIN_DENOISE | (kw.get("film_grain", p.film_grain) if film_grain_denoise is True else int(film_grain_denoise))
+    if film_grain_ar:
+        kw["film_grain"] = kw.get("film_grain", p.film_grain) | ((int(film_grain_ar) & 3) << 12)
     if tf_frames is not None or tf_strength is not None:
         kw["me_presearch"] = me_tf(kw.get("me_presearch", p.me_presearch), int(tf_frames or 0), int(tf_strength or 0))
     if lr_fit is not None and lr_fit is not False:
@@ -500,6 +518,30 @@ class Context:
                                            table.ctypes.data_as(C.POINTER(C.c_uint8)))
         _raise_for(rc, self.last_error())
         return out, table
+
+    def film_grain_ar_estimate(self, params, frames, n_frames, on_device=False):
+        """The film grain's autoregressive fit alone (include/av1mi.h: av1mi_film_grain_ar_estimate); frames as for scene_cuts.  Returns a
+        dict of numpy arrays: coeffs int8 [plane][25], table and sigma_table uint8 [plane][8], gain and flat uint32 [plane], sums int64
+        [plane][46]."""
+        import numpy as np
+        out = dict(coeffs=np.zeros((3, 25), dtype=np.int8), table=np.zeros((3, 8), dtype=np.uint8), sigma_table=np.zeros((3, 8), dtype=np.uint8),
+                   gain=np.zeros(3, dtype=np.uint32), flat=np.zeros(3, dtype=np.uint32), sums=np.zeros((3, 46), dtype=np.int64))
+        fptr, keep = _frames_ptr(frames, on_device)
+        u8, u32 = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+        rc = _lib.av1mi_film_grain_ar_estimate(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0, out["coeffs"].ctypes.data_as(C.POINTER(C.c_int8)),
+                                               out["table"].ctypes.data_as(u8), out["sigma_table"].ctypes.data_as(u8), out["gain"].ctypes.data_as(u32),
+                                               out["flat"].ctypes.data_as(u32), out["sums"].ctypes.data_as(C.POINTER(C.c_int64)))
+        _raise_for(rc, self.last_error())
+        return out
+
+    def film_grain_ar_result(self):
+        """The autoregressive fit of the last encoded chunk (include/av1mi.h: av1mi_film_grain_ar_result): (coeffs int8 [plane][25],
+        sigma_table uint8 [plane][8], gain uint32 [plane]); zeros and gains of 256 for a chunk without a lag."""
+        import numpy as np
+        coeffs, sigma, gain = np.zeros((3, 25), dtype=np.int8), np.zeros((3, 8), dtype=np.uint8), np.zeros(3, dtype=np.uint32)
+        _raise_for(_lib.av1mi_film_grain_ar_result(self._h, coeffs.ctypes.data_as(C.POINTER(C.c_int8)), sigma.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                   gain.ctypes.data_as(C.POINTER(C.c_uint32))), self.last_error())
+        return coeffs, sigma, gain
 
     def film_grain_result(self):
         """The film-grain table of the last encoded chunk (include/av1mi.h: av1mi_film_grain_result): numpy uint8 [plane][8], zeros for

@@ -19,6 +19,7 @@
 #include "aq_rule.h"
 #include "tpl_rule.h"
 #include "fg_rule.h"
+#include "fg_ar_rule.h"
 #include "part_inter_rule.h"
 
 namespace av1mi {
@@ -131,6 +132,10 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   if (r.fg_estimate && (!w.d_fg || !w.h_fg)) {
     HIPCHK(c, ws_alloc(w, w.d_fg, fg_bytes(nf * (size_t)av1mi_fg_blocks((int)p.width) * av1mi_fg_blocks((int)p.height))));
     HIPCHK(c, ws_alloc(w, w.h_fg, FG_RESULT_BYTES, true));
+  }
+  if (r.fg_ar_lag && (!w.d_fg_ar || !w.h_fg_ar)) {
+    HIPCHK(c, ws_alloc(w, w.d_fg_ar, AV1MI_FGAR_BYTES));
+    HIPCHK(c, ws_alloc(w, w.h_fg_ar, AV1MI_FGAR_RESULT_BYTES, true));
   }
   if (p.cdef_search && (!w.d_cdef_err || !w.d_cdef_idx || !w.d_cdef_sel)) {
     HIPCHK(c, ws_alloc(w, w.d_cdef_err, nf * nsb * 24 * sizeof(unsigned long long)));
@@ -614,6 +619,46 @@ int av1mi_film_grain_denoise(av1mi_ctx *c, const av1mi_params *params, const voi
   if (t.ok()) t.e = hipMemcpyAsync(out, r.padded ? d_crop : d_den, in_bytes, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s);
   if (t.ok() && table) t.e = hipMemcpyAsync(table, d_fg, AV1MI_FG_TABLE, hipMemcpyDeviceToHost, s);
   return t.finish(c, "film-grain denoise");
+}
+
+// The autoregressive fit alone: the launches the encoder runs on a chunk's source (av1mi_launch_film_grain, av1mi_launch_fg_ar), on blocks
+// of the call's own and without a header to write into.
+int av1mi_film_grain_ar_estimate(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, int8_t *coeffs,
+                                 uint8_t *table, uint8_t *sigma_table, uint32_t *gain, uint32_t *flat_blocks, int64_t *sums) {
+  if (!c || !frames || n_frames == 0) return AV1MI_E_INVALID_ARG;
+  Resolved r;
+  int rc = resolve(params, &r);
+  if (rc || !r.fg_ar_lag) { set_err(c, rc ? "invalid parameters" : "film_grain does not ask for the autoregressive fit"); return rc ? rc : AV1MI_E_INVALID_ARG; }
+  if (frames_on_device && ((uintptr_t)frames & 15)) { set_err(c, "device frames must be 16-byte aligned"); return AV1MI_E_INVALID_ARG; }
+  HIPCHK(c, hipSetDevice(c->device));
+  const Av1miDevParams P = dev_params(r, n_frames, 1);
+  hipStream_t s = c->stream;
+  PassBuffers t(s);
+  const size_t n_blk = (size_t)n_frames * av1mi_fg_blocks((int)r.p.width) * av1mi_fg_blocks((int)r.p.height);
+  uint8_t *d_fg = nullptr, *d_ar = nullptr;
+  t.alloc(d_fg, fg_bytes(n_blk));
+  t.alloc(d_ar, AV1MI_FGAR_BYTES);
+  const void *src = coded_frames(t, r, frames, n_frames, frames_on_device);
+  const size_t none[2] = { 0, 0 };
+  if (t.ok()) t.e = launch_film_grain(P, r, src, d_fg, nullptr, 0, 0, s);
+  if (t.ok()) t.e = launch_fg_ar(P, r, src, d_fg, d_ar, nullptr, none, none, s);
+  auto fetch = [&](void *dst, size_t at, size_t bytes) { if (t.ok() && dst) t.e = hipMemcpyAsync(dst, d_ar + at, bytes, hipMemcpyDeviceToHost, s); };
+  fetch(coeffs, AV1MI_FGAR_COEFF_AT, 3 * AV1MI_FGAR_COEFFS);
+  fetch(table, AV1MI_FGAR_TABLE_AT, AV1MI_FG_TABLE);
+  fetch(sigma_table, AV1MI_FGAR_SIGMA_AT, AV1MI_FG_TABLE);
+  fetch(gain, AV1MI_FGAR_GAIN_AT, 3 * sizeof(uint32_t));
+  fetch(flat_blocks, AV1MI_FGAR_FLAT_AT, 3 * sizeof(uint32_t));
+  fetch(sums, AV1MI_FGAR_SUMS_AT, 3 * AV1MI_FGAR_SUMS * sizeof(int64_t));
+  return t.finish(c, "film-grain autoregressive fit");
+}
+
+// The autoregressive fit of the context's last chunk: what download_chunk kept, zeros and gains of 256 for a chunk without a lag.
+int av1mi_film_grain_ar_result(const av1mi_ctx *c, int8_t *coeffs, uint8_t *sigma_table, uint32_t *gain) {
+  if (!c || !c->last.n_frames) return AV1MI_E_INVALID_ARG;
+  if (coeffs) memcpy(coeffs, c->last.fg_ar_coeffs, sizeof(c->last.fg_ar_coeffs));
+  if (sigma_table) memcpy(sigma_table, c->last.fg_sigma_table, sizeof(c->last.fg_sigma_table));
+  if (gain) memcpy(gain, c->last.fg_ar_gain, sizeof(c->last.fg_ar_gain));
+  return AV1MI_OK;
 }
 
 // The film-grain table of the context's last chunk: what download_chunk kept, zeros for a chunk without the estimate.

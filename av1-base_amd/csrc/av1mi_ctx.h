@@ -54,10 +54,12 @@ struct Workspace {
   uint32_t *d_tpl_intra = nullptr, *d_tpl_inter = nullptr, *d_tpl_key = nullptr;
   unsigned long long *d_tpl_flow = nullptr;
   uint16_t *d_tpl_beta = nullptr;
-  // the film-grain estimate (fg_kernel.hip), on first use: one block - the table's 24 bytes, at byte 32 the 24 counts, at byte 128 the
-  // histograms' parts and behind them the records per [frame][16x16 block of the signalled size]; h_fg: where one copy lands the table
-  // and the counts
+  // the film-grain estimate (fg_kernel.hip), on first use: one block - the table's 24 bytes, at byte 32 the 24 counts, at byte 128 the 24
+  // quartiles, at byte 160 the histograms' parts and behind them the records per [frame][16x16 block of the signalled size]; h_fg: where
+  // one copy lands the table and the counts
   uint8_t *d_fg = nullptr, *h_fg = nullptr;
+  // the grain's autoregressive fit (fg_ar_kernel.hip), on first use: its block (av1mi_launch_fg_ar), and where one copy lands its result
+  uint8_t *d_fg_ar = nullptr, *h_fg_ar = nullptr;
   uint32_t *d_tf_mv = nullptr;             // temporal filter: the search's keys per [key frame][follower][16x16 block] (tf_kernel.hip)
   Av1miQmEntry *d_qm = nullptr;        // quantiser-matrix steps (Av1miDevParams::qm_tab), one slice per quantiser slot, valid for qm_key = (slices, level, qidx, bit depth)
   std::vector<Av1miQmEntry> h_qm; int qm_key = -1;
@@ -117,18 +119,29 @@ struct LastChunk {
   uint32_t sym_tiles = 0;         // the tiles of its weight-ordered table (av1mi_sym_order_result); 0: natural order
   bool pi_keys = false;           // it was partitioned from the search's node costs: its search keys are reported too
   uint32_t pi_frames = 0, pi_units = 0, pi_sbs = 0;   // with a partition map: frames (else 0), 8x8 units and superblocks per frame (av1mi_inter_partition_result)
-  uint8_t fg_table[24] = {};      // its estimated film-grain table (av1mi_film_grain_result); zeros without the estimate
+  uint8_t fg_table[24] = {};      // the film-grain table its headers carry (av1mi_film_grain_result); zeros without the estimate
+  // its autoregressive fit (av1mi_film_grain_ar_result): coefficients, the table before the gains, the gains; zeros and 256 without a lag
+  int8_t fg_ar_coeffs[3 * 25] = {};
+  uint8_t fg_sigma_table[24] = {};
+  uint32_t fg_ar_gain[3] = { 256, 256, 256 };
 };
-// the film-grain estimate's block (Workspace::d_fg, and a stand-alone pass's): where the counts, the histograms' parts and the records
-// start, its bytes, and the head the host fetches (table and counts)
-constexpr size_t FG_COUNTS_AT = 32, FG_PARTS_AT = 128, FG_BLOCKS_AT = FG_PARTS_AT + (size_t)AV1MI_FG_PARTS * 24 * 256 * sizeof(uint32_t), FG_RESULT_BYTES = 128;
+// the film-grain estimate's block (Workspace::d_fg, and a stand-alone pass's): where the counts, the quartiles, the histograms' parts and
+// the records start, its bytes, and the head the host fetches (table and counts)
+constexpr size_t FG_COUNTS_AT = 32, FG_QUART_AT = 128, FG_PARTS_AT = 160, FG_BLOCKS_AT = FG_PARTS_AT + (size_t)AV1MI_FG_PARTS * 24 * 256 * sizeof(uint32_t), FG_RESULT_BYTES = 128;
 inline size_t fg_bytes(size_t n_blocks) { return FG_BLOCKS_AT + (n_blocks ? n_blocks : 1) * sizeof(uint32_t); }
 // the launch on such a block
 inline hipError_t launch_film_grain(const Av1miDevParams &P, const Resolved &r, const void *src, uint8_t *d_fg, uint8_t *hdr_blob, size_t bit_key, size_t bit_inter,
                                     hipStream_t s) {
   return av1mi_launch_film_grain(&P, src, reinterpret_cast<uint32_t *>(d_fg + FG_BLOCKS_AT), reinterpret_cast<uint32_t *>(d_fg + FG_PARTS_AT), d_fg,
-                                 reinterpret_cast<uint32_t *>(d_fg + FG_COUNTS_AT), av1mi_fg_ceiling((int)r.p.film_grain, 0), av1mi_fg_ceiling((int)r.p.film_grain, 1),
+                                 reinterpret_cast<uint32_t *>(d_fg + FG_COUNTS_AT), d_fg + FG_QUART_AT, av1mi_fg_ceiling((int)r.p.film_grain, 0), av1mi_fg_ceiling((int)r.p.film_grain, 1),
                                  hdr_blob, (int)bit_key, (int)bit_inter, s);
+}
+// ... and the autoregressive fit's behind it, on the estimate's block as that launch left it and a block of AV1MI_FGAR_BYTES
+inline hipError_t launch_fg_ar(const Av1miDevParams &P, const Resolved &r, const void *src, const uint8_t *d_fg, uint8_t *d_fg_ar, uint8_t *hdr_blob,
+                               const size_t fg_bit[2], const size_t ar_bit[2], hipStream_t s) {
+  return av1mi_launch_fg_ar(&P, src, reinterpret_cast<const uint32_t *>(d_fg + FG_BLOCKS_AT), d_fg + FG_QUART_AT,
+                            reinterpret_cast<const uint32_t *>(d_fg + FG_COUNTS_AT), d_fg, r.fg_ar_lag, d_fg_ar, hdr_blob, (int)fg_bit[0], (int)fg_bit[1],
+                            (int)ar_bit[0], (int)ar_bit[1], s);
 }
 
 }  // namespace av1mi

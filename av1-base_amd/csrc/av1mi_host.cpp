@@ -34,9 +34,10 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   // frames have different lengths; frames of one kind differ only in grain_seed)
   size_t str_key = 0, str_inter = 0;   // CDEF strength search: where cdef_select_kernel writes each frame's set
   size_t lf_key = 0, lf_inter = 0;     // deblocking level search: where deblock_decide_kernel writes each frame's levels
-  size_t fg_key = 0, fg_inter = 0;     // film-grain estimate: where fg_table_kernel writes each frame's table
-  std::vector<uint8_t> seq = make_sequence_header(r), fh = make_frame_header(r, nullptr, 0, false, &str_key, &lf_key, &fg_key),
-                       fhi = make_frame_header(r, nullptr, 0, true, &str_inter, &lf_inter, &fg_inter);
+  size_t fg_bit[2] = { 0, 0 };         // film-grain estimate: where fg_table_kernel writes each frame's table (key, inter)
+  size_t ar_bit[2] = { 0, 0 };         // ... and fg_ar_solve_kernel the autoregressive coefficients
+  std::vector<uint8_t> seq = make_sequence_header(r), fh = make_frame_header(r, nullptr, 0, false, &str_key, &lf_key, &fg_bit[0], &ar_bit[0]),
+                       fhi = make_frame_header(r, nullptr, 0, true, &str_inter, &lf_inter, &fg_bit[1], &ar_bit[1]);
   P.cdef_str_bit[0] = (int)str_key; P.cdef_str_bit[1] = (int)str_inter;
   P.lf_bit[0] = (int)lf_key; P.lf_bit[1] = (int)lf_inter;
   P.seq_hdr_bytes = (int)seq.size(); P.frame_hdr_bytes = (int)fh.size(); P.inter_hdr_bytes = (int)fhi.size();
@@ -100,7 +101,10 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   *d_src = r.padded ? w.d_src : (staged ? tight : (frames_on_device ? frames : w.d_src));
   // the film-grain estimate: the table from the frames as the caller gave them - before the denoiser and the temporal filter - into every
   // frame header, in front of every other kernel that patches a header (neighbouring fields can share a byte)
-  if (r.fg_estimate) HIPCHK(c, launch_film_grain(P, r, *d_src, w.d_fg, w.d_hdr, fg_key, fg_inter, s));
+  if (r.fg_estimate) HIPCHK(c, launch_film_grain(P, r, *d_src, w.d_fg, w.d_hdr, fg_bit[0], fg_bit[1], s));
+  // the grain's autoregressive fit on the same frames: the coefficients, and the table scaled by the fit's gains over fg_table_kernel's
+  // values, into every frame header.  The table in d_fg stays as it is: the denoiser filters by the grain's whole sigma
+  if (r.fg_ar_lag) HIPCHK(c, launch_fg_ar(P, r, *d_src, w.d_fg, w.d_fg_ar, w.d_hdr, fg_bit, ar_bit, s));
   // the denoiser: the caller's frames filtered by that table, where fg_table_kernel left it, into d_src at the coded size - out of place, the
   // edge extension in its store (a padded chunk's extension above served the estimate alone).  Everything below and after reads the
   // denoised chunk
@@ -357,6 +361,7 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
   if (e1 == hipSuccess && P.lf_search) e1 = hipMemcpyAsync(w.h_lf + lf_err_bytes, w.d_lf_sel, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s);
   // the film-grain estimate's table and counts, likewise
   if (e1 == hipSuccess && r.fg_estimate) e1 = hipMemcpyAsync(w.h_fg, w.d_fg, FG_RESULT_BYTES, hipMemcpyDeviceToHost, s);
+  if (e1 == hipSuccess && r.fg_ar_lag) e1 = hipMemcpyAsync(w.h_fg_ar, w.d_fg_ar, AV1MI_FGAR_RESULT_BYTES, hipMemcpyDeviceToHost, s);
   // the self-guided fit's errors and records, likewise
   const size_t fit_n = (size_t)n_frames * 3 * av1mi_lr_unit_rows(P) * av1mi_lr_unit_cols(P);
   if (e1 == hipSuccess && P.lr_fit_code) e1 = hipMemcpyAsync(w.h_fit, w.d_fit, av1mi_lr_fit_result_bytes(fit_n), hipMemcpyDeviceToHost, s);
@@ -421,6 +426,12 @@ static LastChunk record_last_chunk(const av1mi_ctx *c, const Resolved &r, uint32
   L.wfit_on = P.lr_wfit_code != nullptr;
   if (!inter && sym_order_on(c)) L.sym_tiles = n_frames * (uint32_t)(P.tile_rows * P.tile_cols);   // (the all-key schedules' table)
   if (r.fg_estimate) memcpy(L.fg_table, w.h_fg, sizeof(L.fg_table));
+  if (r.fg_ar_lag) {   // the headers carry the scaled table
+    memcpy(L.fg_table, w.h_fg_ar + AV1MI_FGAR_TABLE_AT, sizeof(L.fg_table));
+    memcpy(L.fg_ar_coeffs, w.h_fg_ar + AV1MI_FGAR_COEFF_AT, sizeof(L.fg_ar_coeffs));
+    memcpy(L.fg_sigma_table, w.h_fg_ar + AV1MI_FGAR_SIGMA_AT, sizeof(L.fg_sigma_table));
+    memcpy(L.fg_ar_gain, w.h_fg_ar + AV1MI_FGAR_GAIN_AT, sizeof(L.fg_ar_gain));
+  }
   if (P.part_map) { L.pi_keys = c->part_inter; L.pi_frames = n_frames; L.pi_units = (uint32_t)(P.b8_rows * P.b8_cols); L.pi_sbs = (uint32_t)(P.sb_rows * P.sb_cols); }
   return L;
 }

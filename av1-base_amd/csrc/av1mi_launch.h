@@ -53,12 +53,30 @@ hipError_t av1mi_launch_tpl(const Av1miDevParams *P, const void *frames, uint32_
 // the film-grain estimate (fg_kernel.hip, fg_rule.h) of the chunk's source: `frames` at the coded size, of which the whole 16x16 blocks of
 // the signalled size are read.  blocks: per [frame][block] the record { bin, v_y, v_u, v_v }, all written (16-byte aligned); parts: scratch
 // for the histograms' parts, AV1MI_FG_PARTS x 24 x 256 counters (16-byte aligned); table, counts: the 24 values [plane][bin], clamped to
-// ceil_y / ceil_c, and the bins' block counts.  hdr_blob: null, or the chunk's header blob, whose
+// ceil_y / ceil_c, and the bins' block counts; quart (optional): the 24 quartiles before the fill and the clamp, 0 for a bin without
+// blocks.  hdr_blob: null, or the chunk's header blob, whose
 // frame headers receive the values at bit_key / bit_inter (make_frame_header's fg_bit of the two frame kinds).  `frames` must be a
 // 16-byte aligned device pointer; it is only read
 #define AV1MI_FG_PARTS 64
 hipError_t av1mi_launch_film_grain(const Av1miDevParams *P, const void *frames, uint32_t *blocks, uint32_t *parts, uint8_t *table, uint32_t *counts,
-                                   int ceil_y, int ceil_c, uint8_t *hdr_blob, int bit_key, int bit_inter, hipStream_t stream);
+                                   uint8_t *quart, int ceil_y, int ceil_c, uint8_t *hdr_blob, int bit_key, int bit_inter, hipStream_t stream);
+// the grain's autoregressive fit at lag 1 .. 3 (fg_ar_kernel.hip, fg_ar_rule.h) on the same frames, behind av1mi_launch_film_grain on the
+// same stream: blocks, quart, counts and table as that launch left them.  ar: a 16-byte aligned block of AV1MI_FGAR_BYTES - the result at
+// its head (int8 coefficients [plane][25], the 24 scaled values, the 24 unscaled, gains and flat blocks [plane], the sums [plane][46]; what
+// the host fetches in one copy), the workgroups' parts behind it.  hdr_blob: null, or the chunk's header blob, whose frame headers receive
+// the scaled values at fg_bit_* and the coefficient bytes at ar_bit_* (make_frame_header's fg_bit and fg_ar_bit of the two frame kinds)
+#define AV1MI_FGAR_COEFF_AT 0
+#define AV1MI_FGAR_TABLE_AT 80
+#define AV1MI_FGAR_SIGMA_AT 104
+#define AV1MI_FGAR_GAIN_AT 128
+#define AV1MI_FGAR_FLAT_AT 140
+#define AV1MI_FGAR_SUMS_AT 152
+#define AV1MI_FGAR_RESULT_BYTES 1280
+#define AV1MI_FGAR_MAX_GROUPS 1024
+#define AV1MI_FGAR_BYTES (AV1MI_FGAR_RESULT_BYTES + (size_t)AV1MI_FGAR_MAX_GROUPS * 3 * 47 * 8)
+hipError_t av1mi_launch_fg_ar(const Av1miDevParams *P, const void *frames, const uint32_t *blocks, const uint8_t *quart, const uint32_t *counts,
+                              const uint8_t *table, int lag, uint8_t *ar, uint8_t *hdr_blob, int fg_bit_key, int fg_bit_inter, int ar_bit_key,
+                              int ar_bit_inter, hipStream_t stream);
 // the source denoised by the film-grain table (fg_denoise_kernel.hip, fg_denoise_rule.h), out of place: `frames` as the caller gave them,
 // tight at the signalled size P->true_w x P->true_h, only read; `out` the same frames filtered, at the coded size, samples outside the
 // signalled picture replicating the denoised edge; table: the 24 values [plane][bin] in device memory (av1mi_launch_film_grain's, on the

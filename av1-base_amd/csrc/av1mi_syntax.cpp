@@ -80,12 +80,14 @@ int resolve(const av1mi_params *in, Resolved *r) {
   if (p.cq_level == 0 || p.cq_level > 63) return AV1MI_E_INVALID_ARG;
   // film_grain bit 8 (AV1MI_FILM_GRAIN_ESTIMATE): the table is estimated from the chunk's source, the low byte N = 1 .. 50 its ceiling;
   // without it 0 .. 50 as ever.  Bit 10 with bit 8 (AV1MI_FILM_GRAIN_DENOISE): the source is denoised by that table before it is coded
-  // (fg_denoise_rule.h).  Nothing in bit 9 or above bit 10, and bit 10 not alone
+  // (fg_denoise_rule.h).  Bits 12-13 with bit 8 (AV1MI_FILM_GRAIN_AR): the lag 1 .. 3 at which the grain's autoregressive coefficients are
+  // fitted (fg_ar_rule.h).  Nothing in bit 9, bit 11 or above bit 13, and neither bit 10 nor bits 12-13 without bit 8
   r->fg_estimate = (p.film_grain & 0x100u) ? 1 : 0;
   r->fg_denoise = (p.film_grain & 0x400u) ? 1 : 0;
+  r->fg_ar_lag = r->fg_estimate ? (int)AV1MI_FILM_GRAIN_AR_LAG(p.film_grain) : 0;
   if (r->fg_denoise && !r->fg_estimate) return AV1MI_E_INVALID_ARG;
   if (r->fg_estimate) {
-    if ((p.film_grain & ~0x5FFu) || (p.film_grain & 0xFFu) < 1 || (p.film_grain & 0xFFu) > AV1MI_FG_MAX_N) return AV1MI_E_INVALID_ARG;
+    if ((p.film_grain & ~0x35FFu) || (p.film_grain & 0xFFu) < 1 || (p.film_grain & 0xFFu) > AV1MI_FG_MAX_N) return AV1MI_E_INVALID_ARG;
     p.film_grain &= 0xFFu;
   }
   if (p.film_grain > AV1MI_FG_MAX_N) return AV1MI_E_INVALID_ARG;
@@ -237,8 +239,11 @@ std::vector<uint8_t> make_sequence_header(const Resolved &r) {
 // fg_bit (optional): bit offset of the first luma point of film_grain_params - with the estimate on (film_grain bit 8) the table has eight
 // points per plane at x = 16 + 32 k (fg_rule.h) whose values the header carries at the ceiling, 2 N luma / N chroma, as placeholders, and
 // fg_table_kernel overwrites those 24 values in every frame's slot
+// fg_ar_bit (optional): bit offset of the first luma coefficient - with a lag L (film_grain bits 12-13) the header carries ar_coeff_lag = L
+// and 2 L (L + 1) luma, then 2 L (L + 1) + 1 cb and as many cr coefficients as 128 (zero) placeholders, 6 L (L + 1) + 2 bytes in a row
+// which fg_ar_solve_kernel overwrites in every frame's slot, with the points scaled by the fit's gain; ar_coeff_shift_minus_6 is then 1
 std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint32_t frame_number, bool inter, size_t *cdef_str_bit, size_t *lf_bit,
-                                       size_t *fg_bit) {
+                                       size_t *fg_bit, size_t *fg_ar_bit) {
   const av1mi_params &p = r.p;
   BitWriter b;
   b.put(0, 1);  // show_existing_frame
@@ -352,9 +357,12 @@ std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint
       for (int pl = 0; pl < 2; pl++) { b.put(2, 4); b.put(0, 8); b.put(sc, 8); b.put(255, 8); b.put(sc, 8); }
     }
     b.put(3, 2);                                              // grain_scaling_minus_8
-    b.put(0, 2);                                              // ar_coeff_lag
-    b.put(128, 8); b.put(128, 8);                             // ar_coeffs_cb/cr_plus_128[0]
-    b.put(0, 2);                                              // ar_coeff_shift_minus_6
+    const int lag = r.fg_ar_lag, n_pos = 2 * lag * (lag + 1);
+    b.put((uint32_t)lag, 2);                                  // ar_coeff_lag
+    if (fg_ar_bit) *fg_ar_bit = lag ? b.bits : 0;
+    for (int i = 0; i < n_pos; i++) b.put(128, 8);            // ar_coeffs_y_plus_128 (there are luma points whenever there is a lag)
+    for (int i = 0; i < 2 * (n_pos + 1); i++) b.put(128, 8);  // ar_coeffs_cb/cr_plus_128: the positions and the luma tap
+    b.put(lag ? 1 : 0, 2);                                    // ar_coeff_shift_minus_6: Q7 coefficients with a lag
     b.put(0, 2);                                              // grain_scale_shift
     for (int pl = 0; pl < 2; pl++) { b.put(128, 8); b.put(192, 8); b.put(256, 9); }  // mult, luma_mult, offset
     b.put(1, 1);                                              // overlap_flag

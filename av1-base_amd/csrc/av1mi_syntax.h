@@ -35,6 +35,7 @@ struct Resolved {
   uint32_t lr_lambda;                 // enable_lr bits 14 and 15: the rate term's lambda (lr_rate_rule.h), 0 = the decisions go by the error alone
   int fg_estimate;                    // film_grain bit 8: the film-grain table is estimated per chunk (fg_rule.h); p.film_grain then holds the ceiling N alone
   int fg_denoise;                     // film_grain bit 10 (with bit 8): the chunk's source is denoised by the estimated table before it is coded (fg_denoise_rule.h)
+  int fg_ar_lag;                      // film_grain bits 12-13 (with bit 8): the grain's autoregressive coefficients are fitted per chunk at this lag (fg_ar_rule.h), 0 = white grain
   int tf_frames, tf_strength;        // me_presearch bits 8-10 and 12-14: the key frames' temporal filter (tf_rule.h), 0 followers = off (p.me_presearch then holds bit 0 alone)
 };
 
@@ -47,7 +48,7 @@ size_t caller_bytes(const Resolved &r, size_t n);
 // sequence_header_obu, complete OBU; and the OBU_FRAME payload up to the first tile, with the bit offsets of its placeholders
 std::vector<uint8_t> make_sequence_header(const Resolved &r);
 std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint32_t frame_number = 0, bool inter = false, size_t *cdef_str_bit = nullptr,
-                                       size_t *lf_bit = nullptr, size_t *fg_bit = nullptr);
+                                       size_t *lf_bit = nullptr, size_t *fg_bit = nullptr, size_t *fg_ar_bit = nullptr);
 // default CDF blob for one q context in the layout of Av1miCdfLayout
 std::vector<uint16_t> make_cdf_blob(int qidx);
 

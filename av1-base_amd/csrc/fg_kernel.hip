@@ -14,36 +14,14 @@
 // all records was measured first: on content whose blocks share few values the adds queue up at a few LDS counters, 0.45 ms of a
 // 1080p x 60 chunk's 0.58.)
 // fg_table_kernel: one workgroup.  The parts' sum into LDS, the quartiles, the fill and the clamp; the table and the counts to memory, and
-// the 24 values into every frame's header slot at fg_bit, one lane per header.
+// the 24 values into every frame's header slot at fg_bit, one lane per header; the quartiles before fill and clamp for fg_ar_kernel.hip.
 #include <hip/hip_runtime.h>
 #include "av1mi_dev.h"
 #include "av1mi_launch.h"
 #include "fg_rule.h"
+#include "fg_pieces.h"
 
 namespace {
-
-// 16 / 8 bytes in one load from an address that is only known to be 4-byte aligned (8-bit chroma rows of a coded width that is not a
-// multiple of 32)
-struct __attribute__((aligned(4))) FgLoad16 { uint32_t w[4]; };
-struct __attribute__((aligned(4))) FgLoad8 { uint32_t w[2]; };
-
-// 16 samples from p into x; `full` = 0: only the first 8 exist, the rest read as 0
-template <typename PIX>
-__device__ __forceinline__ void fg_load_row(const PIX *p, bool full, int (&x)[16]) {
-  if (sizeof(PIX) == 1) {
-    uint32_t w[4] = { 0, 0, 0, 0 };
-    if (full) { const FgLoad16 v = *reinterpret_cast<const FgLoad16 *>(p); w[0] = v.w[0]; w[1] = v.w[1]; w[2] = v.w[2]; w[3] = v.w[3]; }
-    else { const FgLoad8 v = *reinterpret_cast<const FgLoad8 *>(p); w[0] = v.w[0]; w[1] = v.w[1]; }
-#pragma unroll
-    for (int i = 0; i < 16; i++) x[i] = (int)((w[i >> 2] >> (8 * (i & 3))) & 0xFFu);
-  } else {
-    uint32_t w[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    { const FgLoad16 v = *reinterpret_cast<const FgLoad16 *>(p); w[0] = v.w[0]; w[1] = v.w[1]; w[2] = v.w[2]; w[3] = v.w[3]; }
-    if (full) { const FgLoad16 v = *reinterpret_cast<const FgLoad16 *>(p + 8); w[4] = v.w[0]; w[5] = v.w[1]; w[6] = v.w[2]; w[7] = v.w[3]; }
-#pragma unroll
-    for (int i = 0; i < 16; i++) x[i] = (int)((w[i >> 1] >> (16 * (i & 1))) & 0xFFFFu);
-  }
-}
 
 // sum |M * x| of this lane's row over the columns 1 .. 6, 7 .. 8 and 9 .. 14 (zeros unless `interior`: the row has both neighbours inside its
 // block, which are the lanes before and after this one)
@@ -123,13 +101,6 @@ __global__ void __launch_bounds__(FG_THREADS) fg_block_kernel(Av1miDevParams P, 
   }
 }
 
-// writes the 8 bits of v at bit offset `bit` of h (MSB first, like the header's writer)
-__device__ __forceinline__ void fg_put8(uint8_t *h, int bit, uint32_t v) {
-  const int i = bit >> 3, sh = bit & 7;
-  h[i] = (uint8_t)((h[i] & ~(0xFFu >> sh)) | (v >> sh));
-  if (sh) h[i + 1] = (uint8_t)((h[i + 1] & (0xFFu >> sh)) | ((v << (8 - sh)) & 0xFFu));
-}
-
 constexpr int FG_TABLE_THREADS = 1024, FG_HIST_STRIDE = 257;   // (the stride: the 24 lanes that scan the histograms start on 24 banks)
 constexpr int FG_HIST_WORDS = AV1MI_FG_TABLE * 256;            // counters of one part
 constexpr size_t FG_PART_RECORDS = 8192;                       // records a part holds at least, while there are parts left
@@ -158,7 +129,7 @@ __global__ void __launch_bounds__(FG_TABLE_THREADS) fg_hist_kernel(const uint32_
 }
 
 __global__ void __launch_bounds__(FG_TABLE_THREADS) fg_table_kernel(Av1miDevParams P, const uint32_t *__restrict__ parts, int n_parts, int ceil_y, int ceil_c,
-                                                                    uint8_t *__restrict__ table, uint32_t *__restrict__ counts, uint8_t *__restrict__ hdr_blob,
+                                                                    uint8_t *__restrict__ table, uint32_t *__restrict__ counts, uint8_t *__restrict__ quart, uint8_t *__restrict__ hdr_blob,
                                                                     int bit_key, int bit_inter) {
   __shared__ uint32_t hist[AV1MI_FG_TABLE * FG_HIST_STRIDE];
   __shared__ uint32_t count[AV1MI_FG_TABLE];
@@ -184,6 +155,7 @@ __global__ void __launch_bounds__(FG_TABLE_THREADS) fg_table_kernel(Av1miDevPara
     final_v[t] = v;
     table[t] = (uint8_t)v;
     counts[t] = count[t];
+    if (quart) quart[t] = (uint8_t)value[t];   // before the fill and the ceiling: what fg_ar_kernel.hip calls a block flat by
   }
   __syncthreads();
   if (!hdr_blob) return;
@@ -192,14 +164,14 @@ __global__ void __launch_bounds__(FG_TABLE_THREADS) fg_table_kernel(Av1miDevPara
     const int bit = av1mi_frame_is_inter(P, f) ? bit_inter : bit_key;
     for (int pl = 0; pl < 3; pl++)
       for (int k = 0; k < AV1MI_FG_BINS; k++)
-        fg_put8(h, bit + (pl == 0 ? 0 : (pl == 1 ? AV1MI_FG_CB_BIT : AV1MI_FG_CR_BIT)) + 16 * k + 8, (uint32_t)final_v[pl * AV1MI_FG_BINS + k]);
+        av1mi_fg_put8(h, bit + (pl == 0 ? 0 : (pl == 1 ? AV1MI_FG_CB_BIT : AV1MI_FG_CR_BIT)) + 16 * k + 8, (uint32_t)final_v[pl * AV1MI_FG_BINS + k]);
   }
 }
 
 }  // namespace
 
 extern "C" hipError_t av1mi_launch_film_grain(const Av1miDevParams *P, const void *frames, uint32_t *blocks, uint32_t *parts, uint8_t *table, uint32_t *counts,
-                                              int ceil_y, int ceil_c, uint8_t *hdr_blob, int bit_key, int bit_inter, hipStream_t stream) {
+                                              uint8_t *quart, int ceil_y, int ceil_c, uint8_t *hdr_blob, int bit_key, int bit_inter, hipStream_t stream) {
   if (P->n_frames < 1 || ((uintptr_t)frames & 15) || ((uintptr_t)blocks & 15) || ((uintptr_t)parts & 15) || (hdr_blob && (bit_key <= 0 || bit_inter <= 0))) return hipErrorInvalidValue;
   const int nbx = av1mi_fg_blocks(P->true_w), nby = av1mi_fg_blocks(P->true_h);
   const size_t n = (size_t)P->n_frames * nbx * nby;
@@ -218,6 +190,6 @@ extern "C" hipError_t av1mi_launch_film_grain(const Av1miDevParams *P, const voi
     hipLaunchKernelGGL(fg_hist_kernel, dim3((unsigned)n_parts), dim3(FG_TABLE_THREADS), 0, stream, (const uint32_t *)blocks, n, per, parts);
   }
   hipLaunchKernelGGL(fg_table_kernel, dim3(1), dim3(FG_TABLE_THREADS), 0, stream, *P, (const uint32_t *)parts, (int)n_parts, ceil_y, ceil_c, table, counts,
-                     hdr_blob, bit_key, bit_inter);
+                     quart, hdr_blob, bit_key, bit_inter);
   return hipGetLastError();
 }

@@ -94,5 +94,11 @@ AV1MI_FG_HD inline int av1mi_fg_fill(const uint32_t *count, const int *value, in
   }
   return v > ceiling ? ceiling : v;
 }
+// writes the 8 bits of v at bit offset `bit` of h (MSB first, like the header's writer)
+AV1MI_FG_HD inline void av1mi_fg_put8(uint8_t *h, int bit, uint32_t v) {
+  const int i = bit >> 3, sh = bit & 7;
+  h[i] = (uint8_t)((h[i] & ~(0xFFu >> sh)) | (v >> sh));
+  if (sh) h[i + 1] = (uint8_t)((h[i + 1] & (0xFFu >> sh)) | ((v << (8 - sh)) & 0xFFu));
+}
 
 #endif

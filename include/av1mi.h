@@ -70,6 +70,10 @@ typedef struct av1mi_ctx av1mi_ctx;
 /* ... and with the source denoised by that table before it is coded (bit 10, only together with bit 8) */
 #define AV1MI_FILM_GRAIN_DENOISE(n) ((uint32_t)(n) | 0x100u | 0x400u)
 #define AV1MI_FILM_GRAIN_DENOISED(v) ((((uint32_t)(v)) >> 10) & 1u)
+/* ... and with the grain's autoregressive coefficients fitted at lag 1 .. 3 (bits 12-13, only together with bit 8): or-ed into either of
+ * the two values above */
+#define AV1MI_FILM_GRAIN_AR(lag) (((uint32_t)(lag) & 3u) << 12)
+#define AV1MI_FILM_GRAIN_AR_LAG(v) ((((uint32_t)(v)) >> 12) & 3u)
 
 /* Operating point.  Replaces the reference's single constant
  *   SVT_PARAMS = "--crf 8 --preset 3 --film-grain 20 ... --keyint 240 --lookahead 40"
@@ -130,8 +134,23 @@ typedef struct {
                                quantisation and the encoder proper see the denoised chunk; av1mi_report.sse and psnr are against
                                it (the coded source, as with the temporal filter).  Headers and av1mi_film_grain_result are the
                                estimate mode's; the caller's frames are never written.
-                               Bit 8 with a low byte of 0 or above 50, bit 10 without bit 8, bit 9, any bit above 10, and 51..255 are
-                               refused with AV1MI_E_INVALID_ARG.  A context may switch the mode from chunk to chunk */
+                               bits 12-13 = L = 1..3 together with bit 8, with or without bit 10 (| AV1MI_FILM_GRAIN_AR(L); DESIGN.md
+                               section 3 item 7d): the third piece - the grain the decoder synthesises gets the source grain's
+                               size instead of being white.  After the estimate, and on the same frames, the blocks the table calls
+                               flat (value at most their bin's quartile, detrended energy at most 16 sigma^2 of it) are detrended
+                               by their least-squares plane, the products of their residuals at the offsets a lag-L filter sees
+                               are summed over the chunk per plane, and the 2 L (L + 1) coefficients per plane are fitted to the
+                               resulting correlations and quantised to Q7, ar_coeff_shift_minus_6 = 1 (fg_ar_rule.h, all integers).
+                               The points of a plane are scaled by the square root of the innovation's share of the variance, so
+                               the synthesised grain keeps the sigma the estimate measured; a plane without 16 flat blocks or
+                               with an ill-conditioned or amplifying fit keeps zero coefficients and its points.  The chroma
+                               planes' luma tap stays 0.  The frame header is 48 L (L + 1) bits longer than the estimate mode's,
+                               whatever the content; tile data and reconstruction are those of the same mode with L = 0; the
+                               denoiser keeps the unscaled table.  av1mi_write_headers returns ceiling values and zero coefficients,
+                               av1mi_film_grain_result the scaled table, av1mi_film_grain_ar_result the rest.
+                               Bit 8 with a low byte of 0 or above 50, bit 10 or bits 12-13 without bit 8, bit 9, bit 11, any bit
+                               above 13, and 51..255 are refused with AV1MI_E_INVALID_ARG.  A context may switch the mode and the
+                               lag from chunk to chunk */
   uint32_t first_frame;     /* number of the chunk's first frame inside the clip (seeds grain_seed per frame) */
   uint32_t me_range;        /* inter frames: motion search range in luma samples, 8 or 16 (0 = 8) */
   uint32_t enable_lr;       /* 1 = loop restoration on luma (Wiener, 64x64 units, each unit off or one of 3 filters by SSE);
@@ -355,6 +374,23 @@ int av1mi_film_grain_result(const av1mi_ctx *ctx, uint8_t *table);
  * Like av1mi_film_grain_estimate it looks at the frames it is given. */
 int av1mi_film_grain_denoise(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
                              const uint8_t *use_table, void *out, uint8_t *table);
+
+/* ---- the film grain's autoregressive fit on its own --------------------------------------------------
+ * What av1mi_encode_chunk runs on a chunk's source when av1mi_params.film_grain carries bit 8 and a lag in bits 12-13
+ * (AV1MI_FILM_GRAIN_AR): the estimate's launches and the fit's, on the same frames, taken as one chunk.  Every output is optional, host
+ * memory.  coeffs[plane * 25 + i]: the Q7 coefficients in the order the header codes them (rows -L .. 0, columns -L .. L, up to the
+ * sample itself), for U and V the luma tap behind them; entries the lag does not use are 0.  table[plane * 8 + k]: what the headers carry,
+ * the estimate's value scaled by the plane's gain.  sigma_table: the same before the scaling - what av1mi_film_grain_estimate returns
+ * and the denoiser uses.  gain[plane]: Q8, 64 .. 256 (256: no fit).  flat_blocks[plane]: the blocks the sums ran over.
+ * sums[plane * 46 + k]: R[dy][dx], the sum of e[r][c] e[r + dy][c + dx] in sixteenths of a sample squared, at k = dx for dy = 0
+ * (dx = 0 .. 6) and k = 7 + 13 (dy - 1) + dx + 6 for dy = 1 .. 3 (dx = -6 .. 6); zeros where dy > L or |dx| > 2 L.
+ * AV1MI_E_INVALID_ARG without bits 12-13; the arguments are checked before a device is touched.  (av1mi_film_grain_estimate and
+ * av1mi_film_grain_denoise accept a field with bits 12-13 and behave as without them: they report the sigma table.) */
+int av1mi_film_grain_ar_estimate(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
+                                 int8_t *coeffs, uint8_t *table, uint8_t *sigma_table, uint32_t *gain, uint32_t *flat_blocks, int64_t *sums);
+/* The fit of the context's last successfully encoded chunk, layouts as above, every output optional; zeros, with gains of 256, for a
+ * chunk without a lag.  The values arrive with the chunk's other small results.  AV1MI_E_INVALID_ARG without such a chunk. */
+int av1mi_film_grain_ar_result(const av1mi_ctx *ctx, int8_t *coeffs, uint8_t *sigma_table, uint32_t *gain);
 
 /* ---- deblocking levels of the last chunk ---------------------------------------------------
  * loop_filter_level[0..3] (luma vertical edges, luma horizontal, U, V) every frame of the context's last successfully encoded

@@ -80,6 +80,11 @@ pub const fn film_grain_level_of(v: u32) -> u32 { v & 0xFF }
 // AV1MI_FILM_GRAIN_DENOISE / AV1MI_FILM_GRAIN_DENOISED - film_grain bit 10, with bit 8: the source is denoised by the estimated table before it is coded
 pub const fn film_grain_denoise(n: u32) -> u32 { n | 0x100 | 0x400 }
 pub const fn film_grain_denoised(v: u32) -> u32 { (v >> 10) & 1 }
+// AV1MI_FILM_GRAIN_AR / AV1MI_FILM_GRAIN_AR_LAG - film_grain bits 12-13, with bit 8: the lag 1..3 of the grain's fitted autoregressive
+// coefficients, or-ed into film_grain_estimate(n) or film_grain_denoise(n)
+pub const AV1MI_FILM_GRAIN_AR_MAX_LAG: u32 = 3;
+pub const fn film_grain_ar(lag: u32) -> u32 { (lag & 3) << 12 }
+pub const fn film_grain_ar_lag(v: u32) -> u32 { (v >> 12) & 3 }
 #[repr(C)]
 pub struct Av1miCtx { _opaque: [u8; 0] }   // include/av1mi.h: av1mi_ctx
 type ProgressCb =Option<extern "C" fn(user: *mut c_void, done: u32, total: u32, fps: f64, bytes: u64)>;
@@ -99,6 +104,12 @@ extern "C" {
     // table[24] (optional) the values the filter ran with, use_table[24] (optional) values it takes instead of the chunk's estimate
     pub fn av1mi_film_grain_denoise(ctx: *mut Av1miCtx, params: *const Av1miParams, frames: *const c_void, n_frames: u32, frames_on_device: c_int,
                                     use_table: *const u8, out: *mut c_void, table: *mut u8) -> c_int;
+    // the grain's autoregressive fit of `n_frames` frames taken as one chunk: coeffs[3 * 25] in Q7, table[24] as the headers carry it,
+    // sigma_table[24] before the gains, gain[3] in Q8, flat_blocks[3], sums[3 * 46], every output optional (null); and the fit of a
+    // context's last chunk
+    pub fn av1mi_film_grain_ar_estimate(ctx: *mut Av1miCtx, params: *const Av1miParams, frames: *const c_void, n_frames: u32, frames_on_device: c_int,
+                                        coeffs: *mut i8, table: *mut u8, sigma_table: *mut u8, gain: *mut u32, flat_blocks: *mut u32, sums: *mut i64) -> c_int;
+    pub fn av1mi_film_grain_ar_result(ctx: *const Av1miCtx, coeffs: *mut i8, sigma_table: *mut u8, gain: *mut u32) -> c_int;
 }
 
 // Layout pin (include/av1mi.h: av1mi_struct_sizes).  Compile time: the sizes this file was written against (ABI version 8, LP64);

@@ -7,8 +7,12 @@ film_grain = AV1MI_FILM_GRAIN_ESTIMATE(N), and with the source denoised by that 
 and of the denoise runs (best of --steps after --warmup) and of the fixed runs alternated with them, bytes per frame of the three, "start ->
 source ready" of the three (ms_h2d: the passes run there) and their differences - the estimate's milliseconds and the denoiser's -, the time
 of the estimate's call alone (av1mi_film_grain_estimate, with its allocation), and on the noise clip, whose clean ramps the tool keeps, the
-PSNR of the coded source against them before and after the denoiser (the caller's frames, and av1mi_film_grain_denoise's output).  It
-reports what it measures, nothing more."""
+PSNR of the coded source against them before and after the denoiser (the caller's frames, and av1mi_film_grain_denoise's output).
+A third clip, "arnoise", is the ramps with the same noise passed through a known autoregressive filter (AR_TRUTH, lag 1) first; on it the
+tool also runs the fourth mode, estimated + denoised + the grain's autoregressive fit at lag 1, 2 and 3,
+alternated with the denoise mode, and adds per lag the fitted Q7 coefficients beside the injected ones, the gains, the flat blocks and
+their share of all blocks, the milliseconds of the new pass (the difference of "start -> source ready" against the denoise mode's)
+beside the estimate's, and bytes per frame.  It reports what it measures, nothing more."""
 import argparse
 import json
 import os
@@ -22,9 +26,25 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import bench  # noqa: E402
 
 
-def noisy_ramp_clip(torch, w, h, bd, n, dev, seed=7):
+AR_TRUTH = [0.05, 0.20, -0.05, 0.45]   # lag 1: above left, above, above right, left
+
+
+def ar_noise(torch, shape, g, dev, coeffs):
+    """unit-variance noise through g[y][x] = sum c_i g[y + r_i][x + d_i] + white[y][x] (lag 1; the periodic plane, in the frequency domain)"""
+    white = torch.randn(shape, generator=g, device=dev)
+    if coeffs is None:
+        return white
+    wy = 2 * torch.pi * torch.fft.fftfreq(shape[0], device=dev)[:, None]
+    wx = 2 * torch.pi * torch.fft.fftfreq(shape[1], device=dev)[None, :]
+    H = 1 - sum(c * torch.exp(1j * (wy * r + wx * d)) for c, (r, d) in zip(coeffs, ((-1, -1), (-1, 0), (-1, 1), (0, -1))))
+    out = torch.fft.ifft2(torch.fft.fft2(white) / H).real
+    return out / out.std()
+
+
+def noisy_ramp_clip(torch, w, h, bd, n, dev, seed=7, coeffs=None):
     """n frames of a horizontal luma ramp (black to white, a slow vertical tilt; the operator is blind to both) with Gaussian noise of
-    sigma 0.5 + 1.5 luma / white at 8-bit scale, U and V flat with sigma 0.75; a new noise field every frame.  Returns (the clip, the
+    sigma 0.5 + 1.5 luma / white at 8-bit scale, U and V flat with sigma 0.75; a new noise field every frame, white or (coeffs) through
+    ar_noise.  Returns (the clip, the
     clean ramps in the same layout)"""
     g = torch.Generator(device=dev)
     g.manual_seed(seed)
@@ -38,8 +58,8 @@ def noisy_ramp_clip(torch, w, h, bd, n, dev, seed=7):
     clean_planes = [level.round().clamp(0, mx)] + [torch.full((h // 2, w // 2), 128.0 * sc, device=dev) for _ in range(2)]
     clean = torch.cat([p.to(dt).reshape(-1) for p in clean_planes]).repeat(n)
     for _ in range(n):
-        luma = (level + sigma * torch.randn((h, w), generator=g, device=dev)).round().clamp(0, mx)
-        planes = [luma] + [(128.0 * sc + 0.75 * sc * torch.randn((h // 2, w // 2), generator=g, device=dev)).round().clamp(0, mx) for _ in range(2)]
+        luma = (level + sigma * ar_noise(torch, (h, w), g, dev, coeffs)).round().clamp(0, mx)
+        planes = [luma] + [(128.0 * sc + 0.75 * sc * ar_noise(torch, (h // 2, w // 2), g, dev, coeffs)).round().clamp(0, mx) for _ in range(2)]
         frames.append(torch.cat([p.to(dt).reshape(-1) for p in planes]))
     return torch.cat(frames).view(torch.uint8), clean.view(torch.uint8)
 
@@ -57,7 +77,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--frames", type=int, default=60)
-    ap.add_argument("--clips", default="synth,noise")
+    ap.add_argument("--clips", default="synth,noise,arnoise")
     ap.add_argument("--level", type=int, default=20, help="N: the fixed table's level and the estimate's ceiling")
     ap.add_argument("--keyints", default="1,240")
     ap.add_argument("--extra", default="", help="further parameters for every run, name=value,...")
@@ -69,7 +89,8 @@ def main():
     extra = {k: int(v) for k, v in (kv.split("=") for kv in args.extra.split(",") if kv)}
     with av1mi.Context(0) as ctx:
         for name in args.clips.split(","):
-            clip, clean = (bench.make_clip_torch(w, h, bd, n, 1080, dev), None) if name == "synth" else noisy_ramp_clip(torch, w, h, bd, n, dev)
+            clip, clean = (bench.make_clip_torch(w, h, bd, n, 1080, dev), None) if name == "synth" else noisy_ramp_clip(
+                torch, w, h, bd, n, dev, coeffs=AR_TRUTH if name == "arnoise" else None)
             torch.cuda.synchronize(dev)
             for keyint in (int(k) for k in args.keyints.split(",")):
                 kw = dict(keyint=keyint, intra_mode_mask=0x7, **extra)
@@ -113,6 +134,27 @@ def main():
                     line["psnr_source_against_clean_before"] = round(psnr(torch, clip, clean, bd), 3)
                     line["psnr_source_against_clean_after"] = round(psnr(torch, out, clean, bd), 3)
                     del out
+                if name == "arnoise":   # the fourth mode, alternated with the denoise mode
+                    lags = {lag: av1mi.default_params(w, h, bd, film_grain_denoise=args.level, film_grain_ar=lag, **kw) for lag in (1, 2, 3)}
+                    for p in lags.values():
+                        ctx.encode_chunk(p, clip.data_ptr(), n, on_device=True, copy_out=False)
+                    ms, nbytes = {lag: None for lag in lags}, {}
+                    for _ in range(args.steps):
+                        for lag, p in lags.items():
+                            _, _, r0, _ = ctx.encode_chunk(den, clip.data_ptr(), n, on_device=True, copy_out=False)
+                            _, _, r1, _ = ctx.encode_chunk(p, clip.data_ptr(), n, on_device=True, copy_out=False)
+                            d = r1.ms_h2d - r0.ms_h2d
+                            if ms[lag] is None or d < ms[lag]:
+                                ms[lag], nbytes[lag] = d, r1.bytes
+                    line["ar_injected_q7"] = [round(128 * c) for c in AR_TRUTH]
+                    for lag, p in lags.items():
+                        fit = ctx.film_grain_ar_estimate(p, clip.data_ptr(), n, on_device=True)
+                        used = 2 * lag * (lag + 1)
+                        line["ar_lag%d" % lag] = {"coeffs_y": fit["coeffs"][0][:used].tolist(), "coeffs_u": fit["coeffs"][1][:used].tolist(),
+                                                  "coeffs_v": fit["coeffs"][2][:used].tolist(), "gain": fit["gain"].tolist(), "flat_blocks": fit["flat"].tolist(),
+                                                  "flat_share": round(float(fit["flat"][0]) / (n * (w // 16) * (h // 16)), 4),
+                                                  "table_y": fit["table"][0].tolist(), "ms_pass_ar": round(ms[lag], 3), "ms_pass_estimate": line["ms_pass"],
+                                                  "bytes_per_frame": round(nbytes[lag] / n, 1)}
                 print(json.dumps(line), flush=True)
 
 
