@@ -130,12 +130,12 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     HIPCHK(c, ws_alloc(w, w.d_tpl_beta, nf * nsb * sizeof(uint16_t)));
   }
   if (r.fg_estimate && (!w.d_fg || !w.h_fg)) {
-    HIPCHK(c, ws_alloc(w, w.d_fg, fg_bytes(nf * (size_t)av1mi_fg_blocks((int)p.width) * av1mi_fg_blocks((int)p.height))));
-    HIPCHK(c, ws_alloc(w, w.h_fg, FG_RESULT_BYTES, true));
+    HIPCHK(c, ws_alloc(w, w.d_fg, av1mi_fg_bytes(fg_records(r, nf))));
+    HIPCHK(c, ws_alloc(w, w.h_fg, av1mi_fg_result_bytes(), true));
   }
   if (r.fg_ar_lag && (!w.d_fg_ar || !w.h_fg_ar)) {
-    HIPCHK(c, ws_alloc(w, w.d_fg_ar, AV1MI_FGAR_BYTES));
-    HIPCHK(c, ws_alloc(w, w.h_fg_ar, AV1MI_FGAR_RESULT_BYTES, true));
+    HIPCHK(c, ws_alloc(w, w.d_fg_ar, av1mi_fgar_bytes()));
+    HIPCHK(c, ws_alloc(w, w.h_fg_ar, av1mi_fgar_result_bytes(), true));
   }
   if (p.cdef_search && (!w.d_cdef_err || !w.d_cdef_idx || !w.d_cdef_sel)) {
     HIPCHK(c, ws_alloc(w, w.d_cdef_err, nf * nsb * 24 * sizeof(unsigned long long)));
@@ -191,6 +191,18 @@ void bind_workspace(Av1miDevParams &P, const Resolved &r, const Workspace &w) {
   if (r.lr_fit_mask) P.lr_fit_code = w.fit.code;
   if (r.lr_wfit) P.lr_wfit_code = w.wfit.code;
   P.chunk_record = w.d_record; P.tile_symbols = w.d_sym;
+}
+
+hipError_t launch_grain_passes(const Av1miDevParams &P, const Resolved &r, const void *tight, const void *coded, uint8_t *d_fg, uint8_t *d_fg_ar, void *out,
+                               uint8_t *hdr_blob, Av1miFgBits bits, hipStream_t s) {
+  const Av1miFgBlock fg = av1mi_fg_split(d_fg);
+  const int N = (int)r.p.film_grain;
+  hipError_t e = hipSuccess;
+  if (r.fg_estimate && coded) e = av1mi_launch_film_grain(&P, coded, fg, av1mi_fg_ceiling(N, 0), av1mi_fg_ceiling(N, 1), hdr_blob, bits, s);
+  // (the table in d_fg stays as the estimate left it: the headers carry the fit's scaled one, the denoiser filters by the grain's whole sigma)
+  if (e == hipSuccess && r.fg_ar_lag && coded && d_fg_ar) e = av1mi_launch_fg_ar(&P, coded, fg, r.fg_ar_lag, av1mi_fgar_split(d_fg_ar), hdr_blob, bits, s);
+  if (e == hipSuccess && r.fg_denoise && out) e = av1mi_launch_fg_denoise(&P, tight, out, fg.table, s);
+  return e;
 }
 
 }  // namespace av1mi
@@ -397,26 +409,58 @@ struct PassBuffers {
   }
 };
 
-// n caller frames at the coded size on the device, as the encoder's source is: uploaded if they are on the host, edge-extended if the
-// coded size is not the signalled one.  own_copy: the result is always a buffer of the pass's, which it may write - *own_copy -
-// never the caller's memory.  Null after a failure (t.e).
-const void *coded_frames(PassBuffers &t, const Resolved &r, const void *frames, uint32_t n_frames, int frames_on_device, void **own_copy = nullptr) {
-  hipStream_t s = t.stream;
-  const size_t in_bytes = caller_bytes(r, n_frames), coded_bytes = (size_t)n_frames * r.cw * r.ch * 3 / 2 * (r.p.bit_depth > 8 ? 2 : 1);
-  const void *src = frames;
+// What the stand-alone passes on frames at the coded size open with, after the null checks of their own arguments: the parameters
+// resolved; then open() - the mode the pass needs (mode_on, of `r`, with what to say when it is off), the 16-byte alignment of the device
+// pointers the caller gave (all of them or'ed, 0 for none), the context's device, and the kernels' parameters of the n frames as one
+// chunk.  Until open() has succeeded the pass owns nothing and leaving it drains nothing.
+struct Pass : PassBuffers {
+  Resolved r = {};
+  Av1miDevParams P;
+  int rc;
+  Pass(av1mi_ctx *c, const av1mi_params *params) : PassBuffers(c->stream), rc(resolve(params, &r)) { left = true; }
+  int open(av1mi_ctx *c, uint32_t n_frames, bool mode_on, const char *mode_off, uintptr_t device_ptrs) {
+    if (rc) { set_err(c, "invalid parameters"); return rc; }
+    if (!mode_on) { set_err(c, "%s", mode_off); return AV1MI_E_INVALID_ARG; }
+    if (device_ptrs & 15) { set_err(c, "device frames must be 16-byte aligned"); return AV1MI_E_INVALID_ARG; }
+    HIPCHK(c, hipSetDevice(c->device));
+    P = dev_params(r, n_frames, 1);
+    left = false;
+    return AV1MI_OK;
+  }
+};
+
+// n caller frames on the device, as the encoder's source is.  tight: in the caller's layout - uploaded if they are on the host.  coded:
+// at the coded size - edge-extended into a buffer of the pass's if that is not the signalled size, else `tight` - unless want_coded is
+// off.  own_copy: `coded` is always a buffer of the pass's, which it may write - `own` - never the caller's memory.  All null after a
+// failure (t.e).
+struct PassFrames { const void *tight = nullptr, *coded = nullptr; void *own = nullptr; };
+size_t coded_bytes(const Resolved &r, size_t n_frames) { return n_frames * r.cw * r.ch * 3 / 2 * (r.p.bit_depth > 8 ? 2 : 1); }
+PassFrames coded_frames(PassBuffers &t, const Resolved &r, const void *frames, uint32_t n_frames, int on_device, bool own_copy = false, bool want_coded = true) {
+  const size_t in_bytes = caller_bytes(r, n_frames);
+  const bool make = want_coded && (r.padded || own_copy), direct = make && !r.padded;   // direct: the copy is made from the caller's memory
+  PassFrames F;
   void *d_in = nullptr, *d_coded = nullptr;
-  if (!frames_on_device && (r.padded || !own_copy)) {
-    if (t.alloc(d_in, in_bytes)) t.e = hipMemcpyAsync(d_in, frames, in_bytes, hipMemcpyHostToDevice, s);
-    src = d_in;
-  }
-  if (r.padded || own_copy) {
-    t.alloc(d_coded, coded_bytes);
-    if (t.ok() && r.padded) t.e = av1mi_launch_pad(src, d_coded, (int)r.p.width, (int)r.p.height, r.cw, r.ch, (int)r.p.bit_depth, (int)n_frames, 0, s);
-    else if (t.ok()) t.e = hipMemcpyAsync(d_coded, frames, in_bytes, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
-    src = d_coded;
-  }
-  if (own_copy) *own_copy = t.ok() ? d_coded : nullptr;
-  return t.ok() ? src : nullptr;
+  if (!on_device && !direct && t.alloc(d_in, in_bytes)) t.e = hipMemcpyAsync(d_in, frames, in_bytes, hipMemcpyHostToDevice, t.stream);
+  if (make) t.alloc(d_coded, coded_bytes(r, n_frames));
+  F.tight = direct ? d_coded : (on_device ? frames : d_in);
+  if (t.ok() && direct) t.e = hipMemcpyAsync(d_coded, frames, in_bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, t.stream);
+  else if (t.ok() && make) t.e = av1mi_launch_pad(F.tight, d_coded, (int)r.p.width, (int)r.p.height, r.cw, r.ch, (int)r.p.bit_depth, (int)n_frames, 0, t.stream);
+  if (want_coded) F.coded = make ? d_coded : F.tight;
+  if (own_copy) F.own = d_coded;
+  return t.ok() ? F : PassFrames();
+}
+
+// a result of the pass to host memory, where the caller asks for it
+void to_host(PassBuffers &t, void *dst, const void *d_src, size_t bytes) {
+  if (t.ok() && dst && bytes) t.e = hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, t.stream);
+}
+
+// a pass's result at the coded size, cropped to the caller's layout and copied to `out` - where the caller's frames are, host or device
+void return_frames(PassBuffers &t, const Resolved &r, const void *d_coded, void *out, uint32_t n_frames, int frames_on_device) {
+  const size_t in_bytes = caller_bytes(r, n_frames);
+  void *d_crop = nullptr;
+  if (r.padded && t.alloc(d_crop, in_bytes)) t.e = av1mi_launch_pad(d_coded, d_crop, (int)r.p.width, (int)r.p.height, r.cw, r.ch, (int)r.p.bit_depth, (int)n_frames, 1, t.stream);
+  if (t.ok()) t.e = hipMemcpyAsync(out, r.padded ? d_crop : d_coded, in_bytes, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, t.stream);
 }
 
 }  // namespace
@@ -502,22 +546,17 @@ extern "C" {
 // strength, av1mi_launch_aq), on buffers of the call's own.
 int av1mi_aq_qindex(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, uint8_t *qindex) {
   if (!c || !frames || !qindex || n_frames == 0) return AV1MI_E_INVALID_ARG;
-  Resolved r;
-  int rc = resolve(params, &r);
-  if (rc) { set_err(c, "invalid parameters"); return rc; }
-  const size_t nsb = (size_t)r.sb_cols * r.sb_rows, n_map = (size_t)n_frames * nsb;
-  if (!dq_on(r)) { memset(qindex, r.qidx, n_map); return AV1MI_OK; }
-  if (frames_on_device && ((uintptr_t)frames & 15)) { set_err(c, "device frames must be 16-byte aligned"); return AV1MI_E_INVALID_ARG; }
-  HIPCHK(c, hipSetDevice(c->device));
-  const Av1miDevParams P = dev_params(r, n_frames, 1);
-  hipStream_t s = c->stream;
-  PassBuffers t(s);
+  Pass t(c, params);
+  const Resolved &r = t.r; const Av1miDevParams &P = t.P; hipStream_t s = t.stream;
+  const size_t n_map = (size_t)n_frames * r.sb_cols * r.sb_rows;
+  if (!t.rc && !dq_on(r)) { memset(qindex, r.qidx, n_map); return AV1MI_OK; }   // delta-q is off: nothing looks at the frames or their alignment
+  if (const int rc = t.open(c, n_frames, true, nullptr, frames_on_device ? (uintptr_t)frames : 0)) return rc;
   uint16_t *d_act = nullptr;
   uint8_t *d_map = nullptr;
   TplBuffers tpl;
   t.alloc(d_act, n_map * sizeof(uint16_t));
   t.alloc(d_map, n_map);
-  const void *src = coded_frames(t, r, frames, n_frames, frames_on_device);   // the rule reads the coded size
+  const void *src = coded_frames(t, r, frames, n_frames, frames_on_device).coded;   // the rule reads the coded size
   if (r.tpl) run_tpl(t, r, P, src, n_frames, tpl);
   if (t.ok()) t.e = av1mi_launch_aq(&P, src, d_act, d_map, r.aq, tpl.beta, r.tpl ? tpl.beta_sum() : nullptr, r.tpl, s);
   if (t.ok()) t.e = hipMemcpyAsync(qindex, d_map, n_map, hipMemcpyDeviceToHost, s);
@@ -528,127 +567,80 @@ int av1mi_aq_qindex(av1mi_ctx *c, const av1mi_params *params, const void *frames
 int av1mi_tpl_analysis(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, uint32_t *intra,
                        uint32_t *inter, uint32_t *key, uint64_t *flow, uint16_t *beta, uint32_t *mean_beta) {
   if (!c || !frames || n_frames == 0) return AV1MI_E_INVALID_ARG;
-  Resolved r;
-  int rc = resolve(params, &r);
-  if (rc || !r.tpl) { set_err(c, rc ? "invalid parameters" : "the temporal strength is 0"); return rc ? rc : AV1MI_E_INVALID_ARG; }
-  if (frames_on_device && ((uintptr_t)frames & 15)) { set_err(c, "device frames must be 16-byte aligned"); return AV1MI_E_INVALID_ARG; }
-  HIPCHK(c, hipSetDevice(c->device));
-  const Av1miDevParams P = dev_params(r, n_frames, 1);
-  hipStream_t s = c->stream;
-  PassBuffers t(s);
+  Pass t(c, params);
+  if (const int rc = t.open(c, n_frames, t.r.tpl, "the temporal strength is 0", frames_on_device ? (uintptr_t)frames : 0)) return rc;
   TplBuffers b;
-  const void *src = coded_frames(t, r, frames, n_frames, frames_on_device);
-  if (t.ok()) run_tpl(t, r, P, src, n_frames, b);
+  const void *src = coded_frames(t, t.r, frames, n_frames, frames_on_device).coded;
+  if (t.ok()) run_tpl(t, t.r, t.P, src, n_frames, b);
   unsigned long long sum = 0;
-  const size_t n_sb = (size_t)n_frames * r.sb_cols * r.sb_rows;
-  if (t.ok() && intra) t.e = hipMemcpyAsync(intra, b.intra, b.n_blk * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-  if (t.ok() && inter) t.e = hipMemcpyAsync(inter, b.inter, b.n_blk * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-  if (t.ok() && key) t.e = hipMemcpyAsync(key, b.key, b.n_blk * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-  if (t.ok() && flow) t.e = hipMemcpyAsync(flow, b.flow, b.n_blk * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
-  if (t.ok() && beta) t.e = hipMemcpyAsync(beta, b.beta, n_sb * sizeof(uint16_t), hipMemcpyDeviceToHost, s);
-  if (t.ok() && mean_beta) t.e = hipMemcpyAsync(&sum, b.beta_sum(), sizeof(sum), hipMemcpyDeviceToHost, s);
-  rc = t.finish(c, "temporal-dependency");   // (drains the stream: `sum` has arrived)
+  const size_t n_sb = (size_t)n_frames * t.r.sb_cols * t.r.sb_rows;
+  to_host(t, intra, b.intra, b.n_blk * sizeof(uint32_t));
+  to_host(t, inter, b.inter, b.n_blk * sizeof(uint32_t));
+  to_host(t, key, b.key, b.n_blk * sizeof(uint32_t));
+  to_host(t, flow, b.flow, b.n_blk * sizeof(unsigned long long));
+  to_host(t, beta, b.beta, n_sb * sizeof(uint16_t));
+  if (t.ok() && mean_beta) to_host(t, &sum, b.beta_sum(), sizeof(sum));
+  const int rc = t.finish(c, "temporal-dependency");   // (drains the stream: `sum` has arrived)
   if (rc == AV1MI_OK && mean_beta) *mean_beta = (uint32_t)av1mi_tpl_mean_beta(sum, n_sb);
   return rc;
 }
 
-// The film-grain estimate alone: the launches the encoder runs on a chunk's source (av1mi_launch_film_grain), on a block of the call's own
-// and without a header to write into.
+// The three film-grain passes alone run launch_grain_passes, as prepare_chunk does, on blocks and buffers of the call's own and without
+// a header to write into.
 int av1mi_film_grain_estimate(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, uint8_t *table,
                               uint32_t *counts, uint8_t *blocks) {
   if (!c || !frames || n_frames == 0) return AV1MI_E_INVALID_ARG;
-  Resolved r;
-  int rc = resolve(params, &r);
-  if (rc || !r.fg_estimate) { set_err(c, rc ? "invalid parameters" : "film_grain does not ask for the estimate"); return rc ? rc : AV1MI_E_INVALID_ARG; }
-  if (frames_on_device && ((uintptr_t)frames & 15)) { set_err(c, "device frames must be 16-byte aligned"); return AV1MI_E_INVALID_ARG; }
-  HIPCHK(c, hipSetDevice(c->device));
-  const Av1miDevParams P = dev_params(r, n_frames, 1);
-  hipStream_t s = c->stream;
-  PassBuffers t(s);
-  const size_t n_blk = (size_t)n_frames * av1mi_fg_blocks((int)r.p.width) * av1mi_fg_blocks((int)r.p.height);
+  Pass t(c, params);
+  if (const int rc = t.open(c, n_frames, t.r.fg_estimate, "film_grain does not ask for the estimate", frames_on_device ? (uintptr_t)frames : 0)) return rc;
+  const size_t n_blk = fg_records(t.r, n_frames);
   uint8_t *d_fg = nullptr;
-  t.alloc(d_fg, fg_bytes(n_blk));
-  const void *src = coded_frames(t, r, frames, n_frames, frames_on_device);
-  if (t.ok()) t.e = launch_film_grain(P, r, src, d_fg, nullptr, 0, 0, s);
-  if (t.ok() && table) t.e = hipMemcpyAsync(table, d_fg, AV1MI_FG_TABLE, hipMemcpyDeviceToHost, s);
-  if (t.ok() && counts) t.e = hipMemcpyAsync(counts, d_fg + FG_COUNTS_AT, AV1MI_FG_TABLE * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
-  if (t.ok() && blocks && n_blk) t.e = hipMemcpyAsync(blocks, d_fg + FG_BLOCKS_AT, n_blk * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  t.alloc(d_fg, av1mi_fg_bytes(n_blk));
+  const PassFrames F = coded_frames(t, t.r, frames, n_frames, frames_on_device);
+  if (t.ok()) t.e = launch_grain_passes(t.P, t.r, nullptr, F.coded, d_fg, nullptr, nullptr, nullptr, Av1miFgBits{}, t.stream);
+  const Av1miFgBlock fg = av1mi_fg_split(d_fg);
+  to_host(t, table, fg.table, AV1MI_FG_TABLE);
+  to_host(t, counts, fg.counts, AV1MI_FG_TABLE * sizeof(uint32_t));
+  to_host(t, blocks, fg.blocks, n_blk * sizeof(uint32_t));
   return t.finish(c, "film-grain");
 }
 
-// The film-grain denoiser alone: the launches the encoder runs on a chunk's source (av1mi_launch_film_grain unless the caller gives the
-// table, av1mi_launch_fg_denoise), on buffers of the call's own; the result cropped to the caller's layout.
+// ... the denoiser: the estimate unless the caller gives the table; the result cropped to the caller's layout
 int av1mi_film_grain_denoise(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, const uint8_t *use_table,
                              void *out, uint8_t *table) {
   if (!c || !frames || !out || n_frames == 0) return AV1MI_E_INVALID_ARG;
-  Resolved r;
-  int rc = resolve(params, &r);
-  if (rc || !r.fg_denoise) { set_err(c, rc ? "invalid parameters" : "film_grain does not ask for the denoiser"); return rc ? rc : AV1MI_E_INVALID_ARG; }
-  if (frames_on_device && (((uintptr_t)frames | (uintptr_t)out) & 15)) { set_err(c, "device frames must be 16-byte aligned"); return AV1MI_E_INVALID_ARG; }
-  HIPCHK(c, hipSetDevice(c->device));
-  const Av1miDevParams P = dev_params(r, n_frames, 1);
-  hipStream_t s = c->stream;
-  PassBuffers t(s);
-  const size_t in_bytes = caller_bytes(r, n_frames), coded_bytes = (size_t)n_frames * r.cw * r.ch * 3 / 2 * (r.p.bit_depth > 8 ? 2 : 1);
-  const size_t n_blk = (size_t)n_frames * av1mi_fg_blocks((int)r.p.width) * av1mi_fg_blocks((int)r.p.height);
+  Pass t(c, params);
+  const uintptr_t device_ptrs = frames_on_device ? (uintptr_t)frames | (uintptr_t)out : 0;
+  if (const int rc = t.open(c, n_frames, t.r.fg_denoise, "film_grain does not ask for the denoiser", device_ptrs)) return rc;
   uint8_t *d_fg = nullptr;
-  void *d_in = nullptr, *d_pad = nullptr, *d_den = nullptr, *d_crop = nullptr;
-  t.alloc(d_fg, fg_bytes(n_blk));
-  t.alloc(d_den, coded_bytes);
-  const void *tight = frames;   // the frames as the caller gave them, on the device: what the denoiser reads
-  if (!frames_on_device) {
-    if (t.alloc(d_in, in_bytes)) t.e = hipMemcpyAsync(d_in, frames, in_bytes, hipMemcpyHostToDevice, s);
-    tight = d_in;
-  }
-  if (use_table) {
-    if (t.ok()) t.e = hipMemcpyAsync(d_fg, use_table, AV1MI_FG_TABLE, hipMemcpyHostToDevice, s);
-  } else {   // the estimate reads the coded size
-    const void *coded = tight;
-    if (r.padded) {
-      t.alloc(d_pad, coded_bytes);
-      if (t.ok()) t.e = av1mi_launch_pad(tight, d_pad, (int)r.p.width, (int)r.p.height, r.cw, r.ch, (int)r.p.bit_depth, (int)n_frames, 0, s);
-      coded = d_pad;
-    }
-    if (t.ok()) t.e = launch_film_grain(P, r, coded, d_fg, nullptr, 0, 0, s);
-  }
-  if (t.ok()) t.e = av1mi_launch_fg_denoise(&P, tight, d_den, d_fg, s);
-  if (r.padded) {
-    t.alloc(d_crop, in_bytes);
-    if (t.ok()) t.e = av1mi_launch_pad(d_den, d_crop, (int)r.p.width, (int)r.p.height, r.cw, r.ch, (int)r.p.bit_depth, (int)n_frames, 1, s);
-  }
-  if (t.ok()) t.e = hipMemcpyAsync(out, r.padded ? d_crop : d_den, in_bytes, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s);
-  if (t.ok() && table) t.e = hipMemcpyAsync(table, d_fg, AV1MI_FG_TABLE, hipMemcpyDeviceToHost, s);
+  void *d_den = nullptr;
+  t.alloc(d_fg, av1mi_fg_bytes(fg_records(t.r, n_frames)));
+  t.alloc(d_den, coded_bytes(t.r, n_frames));
+  const PassFrames F = coded_frames(t, t.r, frames, n_frames, frames_on_device, false, !use_table);   // (the estimate reads the coded size)
+  if (t.ok() && use_table) t.e = hipMemcpyAsync(d_fg, use_table, AV1MI_FG_TABLE, hipMemcpyHostToDevice, t.stream);
+  if (t.ok()) t.e = launch_grain_passes(t.P, t.r, F.tight, F.coded, d_fg, nullptr, d_den, nullptr, Av1miFgBits{}, t.stream);
+  if (t.ok()) return_frames(t, t.r, d_den, out, n_frames, frames_on_device);
+  to_host(t, table, d_fg, AV1MI_FG_TABLE);
   return t.finish(c, "film-grain denoise");
 }
 
-// The autoregressive fit alone: the launches the encoder runs on a chunk's source (av1mi_launch_film_grain, av1mi_launch_fg_ar), on blocks
-// of the call's own and without a header to write into.
+// ... the autoregressive fit, behind the estimate
 int av1mi_film_grain_ar_estimate(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, int8_t *coeffs,
                                  uint8_t *table, uint8_t *sigma_table, uint32_t *gain, uint32_t *flat_blocks, int64_t *sums) {
   if (!c || !frames || n_frames == 0) return AV1MI_E_INVALID_ARG;
-  Resolved r;
-  int rc = resolve(params, &r);
-  if (rc || !r.fg_ar_lag) { set_err(c, rc ? "invalid parameters" : "film_grain does not ask for the autoregressive fit"); return rc ? rc : AV1MI_E_INVALID_ARG; }
-  if (frames_on_device && ((uintptr_t)frames & 15)) { set_err(c, "device frames must be 16-byte aligned"); return AV1MI_E_INVALID_ARG; }
-  HIPCHK(c, hipSetDevice(c->device));
-  const Av1miDevParams P = dev_params(r, n_frames, 1);
-  hipStream_t s = c->stream;
-  PassBuffers t(s);
-  const size_t n_blk = (size_t)n_frames * av1mi_fg_blocks((int)r.p.width) * av1mi_fg_blocks((int)r.p.height);
+  Pass t(c, params);
+  if (const int rc = t.open(c, n_frames, t.r.fg_ar_lag, "film_grain does not ask for the autoregressive fit", frames_on_device ? (uintptr_t)frames : 0)) return rc;
   uint8_t *d_fg = nullptr, *d_ar = nullptr;
-  t.alloc(d_fg, fg_bytes(n_blk));
-  t.alloc(d_ar, AV1MI_FGAR_BYTES);
-  const void *src = coded_frames(t, r, frames, n_frames, frames_on_device);
-  const size_t none[2] = { 0, 0 };
-  if (t.ok()) t.e = launch_film_grain(P, r, src, d_fg, nullptr, 0, 0, s);
-  if (t.ok()) t.e = launch_fg_ar(P, r, src, d_fg, d_ar, nullptr, none, none, s);
-  auto fetch = [&](void *dst, size_t at, size_t bytes) { if (t.ok() && dst) t.e = hipMemcpyAsync(dst, d_ar + at, bytes, hipMemcpyDeviceToHost, s); };
-  fetch(coeffs, AV1MI_FGAR_COEFF_AT, 3 * AV1MI_FGAR_COEFFS);
-  fetch(table, AV1MI_FGAR_TABLE_AT, AV1MI_FG_TABLE);
-  fetch(sigma_table, AV1MI_FGAR_SIGMA_AT, AV1MI_FG_TABLE);
-  fetch(gain, AV1MI_FGAR_GAIN_AT, 3 * sizeof(uint32_t));
-  fetch(flat_blocks, AV1MI_FGAR_FLAT_AT, 3 * sizeof(uint32_t));
-  fetch(sums, AV1MI_FGAR_SUMS_AT, 3 * AV1MI_FGAR_SUMS * sizeof(int64_t));
+  t.alloc(d_fg, av1mi_fg_bytes(fg_records(t.r, n_frames)));
+  t.alloc(d_ar, av1mi_fgar_bytes());
+  const PassFrames F = coded_frames(t, t.r, frames, n_frames, frames_on_device);
+  if (t.ok()) t.e = launch_grain_passes(t.P, t.r, nullptr, F.coded, d_fg, d_ar, nullptr, nullptr, Av1miFgBits{}, t.stream);
+  const Av1miFgArBlock ar = av1mi_fgar_split(d_ar);
+  to_host(t, coeffs, ar.coeffs, 3 * AV1MI_FGAR_COEFFS);
+  to_host(t, table, ar.table, AV1MI_FG_TABLE);
+  to_host(t, sigma_table, ar.sigma, AV1MI_FG_TABLE);
+  to_host(t, gain, ar.gain, 3 * sizeof(uint32_t));
+  to_host(t, flat_blocks, ar.flat, 3 * sizeof(uint32_t));
+  to_host(t, sums, ar.sums, 3 * AV1MI_FGAR_SUMS * sizeof(int64_t));
   return t.finish(c, "film-grain autoregressive fit");
 }
 
@@ -672,25 +664,15 @@ int av1mi_film_grain_result(const av1mi_ctx *c, uint8_t *table) {
 int av1mi_temporal_filter(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, void *out,
                           uint32_t *mv) {
   if (!c || !frames || n_frames == 0) return AV1MI_E_INVALID_ARG;
-  Resolved r;
-  int rc = resolve(params, &r);
-  if (rc) { set_err(c, "invalid parameters"); return rc; }
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t in_bytes = caller_bytes(r, n_frames), n_mv = tf_mv_entries(r, n_frames);
-  const Av1miDevParams P = dev_params(r, n_frames, 1);
-  hipStream_t s = c->stream;
-  PassBuffers t(s);
+  Pass t(c, params);
+  if (const int rc = t.open(c, n_frames, true, nullptr, 0)) return rc;   // (no mode, and no alignment to ask for: the filter works on a copy of the pass's)
+  const size_t n_mv = tf_mv_entries(t.r, n_frames);
   uint32_t *d_mv = nullptr;
-  void *d_coded = nullptr, *d_crop = nullptr;   // the filter works in place at the coded size; padded sizes: the result cropped to the caller's layout
   if (n_mv) t.alloc(d_mv, n_mv * sizeof(uint32_t));
-  if (out && r.padded) t.alloc(d_crop, in_bytes);
-  coded_frames(t, r, frames, n_frames, frames_on_device, &d_coded);
-  if (t.ok() && n_mv) t.e = av1mi_launch_temporal_filter(&P, d_coded, d_mv, r.tf_frames, r.tf_strength, s);
-  if (t.ok() && out) {
-    if (r.padded) t.e = av1mi_launch_pad(d_coded, d_crop, (int)r.p.width, (int)r.p.height, r.cw, r.ch, (int)r.p.bit_depth, (int)n_frames, 1, s);
-    if (t.ok()) t.e = hipMemcpyAsync(out, r.padded ? d_crop : d_coded, in_bytes, frames_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s);
-  }
-  if (t.ok() && mv && n_mv) t.e = hipMemcpyAsync(mv, d_mv, n_mv * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  void *d_coded = coded_frames(t, t.r, frames, n_frames, frames_on_device, true).own;   // the filter works in place at the coded size
+  if (t.ok() && n_mv) t.e = av1mi_launch_temporal_filter(&t.P, d_coded, d_mv, t.r.tf_frames, t.r.tf_strength, t.stream);
+  if (t.ok() && out) return_frames(t, t.r, d_coded, out, n_frames, frames_on_device);
+  to_host(t, mv, d_mv, n_mv * sizeof(uint32_t));
   return t.finish(c, "temporal-filter");
 }
 

@@ -54,11 +54,9 @@ struct Workspace {
   uint32_t *d_tpl_intra = nullptr, *d_tpl_inter = nullptr, *d_tpl_key = nullptr;
   unsigned long long *d_tpl_flow = nullptr;
   uint16_t *d_tpl_beta = nullptr;
-  // the film-grain estimate (fg_kernel.hip), on first use: one block - the table's 24 bytes, at byte 32 the 24 counts, at byte 128 the 24
-  // quartiles, at byte 160 the histograms' parts and behind them the records per [frame][16x16 block of the signalled size]; h_fg: where
-  // one copy lands the table and the counts
+  // the film-grain estimate (fg_kernel.hip), on first use: its block (av1mi_fg_split); h_fg: where one copy lands its head
   uint8_t *d_fg = nullptr, *h_fg = nullptr;
-  // the grain's autoregressive fit (fg_ar_kernel.hip), on first use: its block (av1mi_launch_fg_ar), and where one copy lands its result
+  // the grain's autoregressive fit (fg_ar_kernel.hip), on first use: its block (av1mi_fgar_split), and where one copy lands its head
   uint8_t *d_fg_ar = nullptr, *h_fg_ar = nullptr;
   uint32_t *d_tf_mv = nullptr;             // temporal filter: the search's keys per [key frame][follower][16x16 block] (tf_kernel.hip)
   Av1miQmEntry *d_qm = nullptr;        // quantiser-matrix steps (Av1miDevParams::qm_tab), one slice per quantiser slot, valid for qm_key = (slices, level, qidx, bit depth)
@@ -125,24 +123,14 @@ struct LastChunk {
   uint8_t fg_sigma_table[24] = {};
   uint32_t fg_ar_gain[3] = { 256, 256, 256 };
 };
-// the film-grain estimate's block (Workspace::d_fg, and a stand-alone pass's): where the counts, the quartiles, the histograms' parts and
-// the records start, its bytes, and the head the host fetches (table and counts)
-constexpr size_t FG_COUNTS_AT = 32, FG_QUART_AT = 128, FG_PARTS_AT = 160, FG_BLOCKS_AT = FG_PARTS_AT + (size_t)AV1MI_FG_PARTS * 24 * 256 * sizeof(uint32_t), FG_RESULT_BYTES = 128;
-inline size_t fg_bytes(size_t n_blocks) { return FG_BLOCKS_AT + (n_blocks ? n_blocks : 1) * sizeof(uint32_t); }
-// the launch on such a block
-inline hipError_t launch_film_grain(const Av1miDevParams &P, const Resolved &r, const void *src, uint8_t *d_fg, uint8_t *hdr_blob, size_t bit_key, size_t bit_inter,
-                                    hipStream_t s) {
-  return av1mi_launch_film_grain(&P, src, reinterpret_cast<uint32_t *>(d_fg + FG_BLOCKS_AT), reinterpret_cast<uint32_t *>(d_fg + FG_PARTS_AT), d_fg,
-                                 reinterpret_cast<uint32_t *>(d_fg + FG_COUNTS_AT), d_fg + FG_QUART_AT, av1mi_fg_ceiling((int)r.p.film_grain, 0), av1mi_fg_ceiling((int)r.p.film_grain, 1),
-                                 hdr_blob, (int)bit_key, (int)bit_inter, s);
-}
-// ... and the autoregressive fit's behind it, on the estimate's block as that launch left it and a block of AV1MI_FGAR_BYTES
-inline hipError_t launch_fg_ar(const Av1miDevParams &P, const Resolved &r, const void *src, const uint8_t *d_fg, uint8_t *d_fg_ar, uint8_t *hdr_blob,
-                               const size_t fg_bit[2], const size_t ar_bit[2], hipStream_t s) {
-  return av1mi_launch_fg_ar(&P, src, reinterpret_cast<const uint32_t *>(d_fg + FG_BLOCKS_AT), d_fg + FG_QUART_AT,
-                            reinterpret_cast<const uint32_t *>(d_fg + FG_COUNTS_AT), d_fg, r.fg_ar_lag, d_fg_ar, hdr_blob, (int)fg_bit[0], (int)fg_bit[1],
-                            (int)ar_bit[0], (int)ar_bit[1], s);
-}
+// the records of the film-grain estimate over n_frames frames: the whole 16x16 blocks of the signalled size
+inline size_t fg_records(const Resolved &r, size_t n_frames) { return n_frames * av1mi_fg_blocks((int)r.p.width) * av1mi_fg_blocks((int)r.p.height); }
+// The grain passes `r` asks for, in the encoder's order on stream s: the estimate on `coded` - the caller's frames on the device at the
+// coded size - into the estimate's block d_fg; the autoregressive fit on the same frames into the fit's block d_fg_ar; the denoiser from
+// `tight`, the same frames in the caller's layout, by d_fg's table into `out` at the coded size.  A pass whose frames or block are null is
+// left out (the stand-alone passes run their part).  hdr_blob: the chunk's header blob, which estimate and fit patch at `bits`, or null
+hipError_t launch_grain_passes(const Av1miDevParams &P, const Resolved &r, const void *tight, const void *coded, uint8_t *d_fg, uint8_t *d_fg_ar, void *out,
+                               uint8_t *hdr_blob, Av1miFgBits bits, hipStream_t s);
 
 }  // namespace av1mi
 

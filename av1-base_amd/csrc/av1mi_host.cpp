@@ -99,18 +99,15 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   // not a multiple of 8: edge-extend every frame to the coded size (the signalled size stays exact)
   if (r.padded) HIPCHK(c, av1mi_launch_pad(tight, w.d_src, (int)r.p.width, (int)r.p.height, r.cw, r.ch, P.bit_depth, (int)n_frames, 0, s));
   *d_src = r.padded ? w.d_src : (staged ? tight : (frames_on_device ? frames : w.d_src));
-  // the film-grain estimate: the table from the frames as the caller gave them - before the denoiser and the temporal filter - into every
-  // frame header, in front of every other kernel that patches a header (neighbouring fields can share a byte)
-  if (r.fg_estimate) HIPCHK(c, launch_film_grain(P, r, *d_src, w.d_fg, w.d_hdr, fg_bit[0], fg_bit[1], s));
-  // the grain's autoregressive fit on the same frames: the coefficients, and the table scaled by the fit's gains over fg_table_kernel's
-  // values, into every frame header.  The table in d_fg stays as it is: the denoiser filters by the grain's whole sigma
-  if (r.fg_ar_lag) HIPCHK(c, launch_fg_ar(P, r, *d_src, w.d_fg, w.d_fg_ar, w.d_hdr, fg_bit, ar_bit, s));
-  // the denoiser: the caller's frames filtered by that table, where fg_table_kernel left it, into d_src at the coded size - out of place, the
-  // edge extension in its store (a padded chunk's extension above served the estimate alone).  Everything below and after reads the
-  // denoised chunk
-  if (r.fg_denoise) {
-    HIPCHK(c, av1mi_launch_fg_denoise(&P, tight, w.d_src, w.d_fg, s));
-    *d_src = w.d_src;
+  // the grain passes.  The film-grain estimate: the table from the frames as the caller gave them - before the denoiser and the temporal
+  // filter - into every frame header, in front of every other kernel that patches a header (neighbouring fields can share a byte).  The
+  // grain's autoregressive fit on the same frames: the coefficients, and the table scaled by the fit's gains over fg_table_kernel's values,
+  // into every frame header.  The denoiser: the caller's frames filtered by the estimate's table into d_src at the coded size - out of place,
+  // the edge extension in its store (a padded chunk's extension above served the estimate alone).  Everything below reads the denoised chunk
+  if (r.fg_estimate) {
+    const Av1miFgBits bits = { (int)fg_bit[0], (int)fg_bit[1], (int)ar_bit[0], (int)ar_bit[1] };
+    HIPCHK(c, launch_grain_passes(P, r, tight, *d_src, w.d_fg, w.d_fg_ar, w.d_src, w.d_hdr, bits, s));
+    if (r.fg_denoise) *d_src = w.d_src;
   }
   // the key frames' temporal filter: in place in the chunk's source - a chunk that is used in place is copied first, the caller's
   // memory is never written.  Everything below and after reads the filtered key frames.
@@ -360,8 +357,8 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
   if (e1 == hipSuccess && P.lf_search) e1 = hipMemcpyAsync(w.h_lf, w.d_lf_err, lf_err_bytes, hipMemcpyDeviceToHost, s);
   if (e1 == hipSuccess && P.lf_search) e1 = hipMemcpyAsync(w.h_lf + lf_err_bytes, w.d_lf_sel, (size_t)n_frames * 4, hipMemcpyDeviceToHost, s);
   // the film-grain estimate's table and counts, likewise
-  if (e1 == hipSuccess && r.fg_estimate) e1 = hipMemcpyAsync(w.h_fg, w.d_fg, FG_RESULT_BYTES, hipMemcpyDeviceToHost, s);
-  if (e1 == hipSuccess && r.fg_ar_lag) e1 = hipMemcpyAsync(w.h_fg_ar, w.d_fg_ar, AV1MI_FGAR_RESULT_BYTES, hipMemcpyDeviceToHost, s);
+  if (e1 == hipSuccess && r.fg_estimate) e1 = hipMemcpyAsync(w.h_fg, w.d_fg, av1mi_fg_result_bytes(), hipMemcpyDeviceToHost, s);
+  if (e1 == hipSuccess && r.fg_ar_lag) e1 = hipMemcpyAsync(w.h_fg_ar, w.d_fg_ar, av1mi_fgar_result_bytes(), hipMemcpyDeviceToHost, s);
   // the self-guided fit's errors and records, likewise
   const size_t fit_n = (size_t)n_frames * 3 * av1mi_lr_unit_rows(P) * av1mi_lr_unit_cols(P);
   if (e1 == hipSuccess && P.lr_fit_code) e1 = hipMemcpyAsync(w.h_fit, w.d_fit, av1mi_lr_fit_result_bytes(fit_n), hipMemcpyDeviceToHost, s);
@@ -425,12 +422,13 @@ static LastChunk record_last_chunk(const av1mi_ctx *c, const Resolved &r, uint32
   L.fit_on = P.lr_fit_code != nullptr;   // (the values stay in h_fit until the context's next chunk)
   L.wfit_on = P.lr_wfit_code != nullptr;
   if (!inter && sym_order_on(c)) L.sym_tiles = n_frames * (uint32_t)(P.tile_rows * P.tile_cols);   // (the all-key schedules' table)
-  if (r.fg_estimate) memcpy(L.fg_table, w.h_fg, sizeof(L.fg_table));
+  if (r.fg_estimate) memcpy(L.fg_table, av1mi_fg_split(w.h_fg).table, sizeof(L.fg_table));   // (the fetched heads of the two blocks)
   if (r.fg_ar_lag) {   // the headers carry the scaled table
-    memcpy(L.fg_table, w.h_fg_ar + AV1MI_FGAR_TABLE_AT, sizeof(L.fg_table));
-    memcpy(L.fg_ar_coeffs, w.h_fg_ar + AV1MI_FGAR_COEFF_AT, sizeof(L.fg_ar_coeffs));
-    memcpy(L.fg_sigma_table, w.h_fg_ar + AV1MI_FGAR_SIGMA_AT, sizeof(L.fg_sigma_table));
-    memcpy(L.fg_ar_gain, w.h_fg_ar + AV1MI_FGAR_GAIN_AT, sizeof(L.fg_ar_gain));
+    const Av1miFgArBlock H = av1mi_fgar_split(w.h_fg_ar);
+    memcpy(L.fg_table, H.table, sizeof(L.fg_table));
+    memcpy(L.fg_ar_coeffs, H.coeffs, sizeof(L.fg_ar_coeffs));
+    memcpy(L.fg_sigma_table, H.sigma, sizeof(L.fg_sigma_table));
+    memcpy(L.fg_ar_gain, H.gain, sizeof(L.fg_ar_gain));
   }
   if (P.part_map) { L.pi_keys = c->part_inter; L.pi_frames = n_frames; L.pi_units = (uint32_t)(P.b8_rows * P.b8_cols); L.pi_sbs = (uint32_t)(P.sb_rows * P.sb_cols); }
   return L;

@@ -7,6 +7,8 @@
 // [frame0, frame0 + count) of the chunk P describes.  The search kernels and the entropy coder index the chunk themselves; reconstruction,
 // deblocking, CDEF and restoration kernels see a launch's frames only: their launchers (and no one else) advance the arrays to frame0 and
 // hand the kernels av1mi_frame_range's parameters.  Every other launcher runs on all P->n_frames frames.
+// Blocks.  A pass whose buffers are one allocation takes a struct of pointers into it: the restoration fits' (av1mi_dev.h) and the
+// film-grain passes' below, with their split functions, byte sizes and fetched heads.
 #ifndef AV1MI_LAUNCH_H
 #define AV1MI_LAUNCH_H
 #include <hip/hip_runtime.h>
@@ -35,6 +37,48 @@ inline void *av1mi_frame_at(const Av1miDevParams &P, void *frames, int f) { retu
 // deblocking levels of frame f, by its kind (level [0] zero: the frame is not deblocked - the launcher's and its caller's one rule)
 inline const int *av1mi_frame_lf_levels(const Av1miDevParams &P, int f) { return av1mi_frame_is_inter(P, f) ? P.lf_level_inter : P.lf_level; }
 
+// The two blocks of the film-grain passes, described as the restoration fits' are (av1mi_lr_fit_split): one allocation each, a struct of
+// pointers into it, its bytes, and the head the host fetches in one copy - a split of the page-locked mirror reads that.
+// The estimate's block (fg_kernel.hip), for n records - the pointers at bytes 0, 32, 128, 160 and behind the parts:
+#define AV1MI_FG_PARTS 64
+struct Av1miFgBlock {
+  uint8_t *table;     // the 24 values [plane][bin], clamped to the ceilings
+  uint32_t *counts;   // the bins' 24 block counts
+  uint8_t *quart;     // the 24 quartiles before the fill and the clamp, 0 for a bin without blocks (fg_ar_kernel.hip's flatness)
+  uint32_t *parts;    // scratch: the histograms' parts, AV1MI_FG_PARTS x 24 x 256 counters (16-byte aligned)
+  uint32_t *blocks;   // per [frame][16x16 block of the signalled size] the record { bin, v_y, v_u, v_v }, all written (16-byte aligned)
+};
+inline size_t av1mi_fg_result_bytes() { return 128; }   // table and counts
+inline size_t av1mi_fg_bytes(size_t n) { return 160 + ((size_t)AV1MI_FG_PARTS * 24 * 256 + (n ? n : 1)) * sizeof(uint32_t); }
+inline Av1miFgBlock av1mi_fg_split(void *block) {
+  uint8_t *b = reinterpret_cast<uint8_t *>(block);
+  uint32_t *parts = reinterpret_cast<uint32_t *>(b + 160);
+  return { b, reinterpret_cast<uint32_t *>(b + 32), b + 128, parts, parts + (size_t)AV1MI_FG_PARTS * 24 * 256 };
+}
+// The fit's block (fg_ar_kernel.hip), 16-byte aligned: the result at its head - the pointers at bytes 0, 80, 104, 128, 140 and 152 - and
+// the workgroups' parts behind it
+#define AV1MI_FGAR_MAX_GROUPS 1024
+struct Av1miFgArBlock {
+  int8_t *coeffs;       // [plane][25]
+  uint8_t *table;       // the 24 values scaled by the gains: what the headers carry
+  uint8_t *sigma;       // the 24 values unscaled: the estimate's table
+  uint32_t *gain;       // [plane], 256 = 1
+  uint32_t *flat;       // [plane]: the flat blocks
+  long long *sums;      // [plane][46]
+  long long *parts;     // [workgroup][plane][47]: the sums and the flat blocks of up to AV1MI_FGAR_MAX_GROUPS workgroups
+};
+inline size_t av1mi_fgar_result_bytes() { return 1280; }
+inline size_t av1mi_fgar_bytes() { return av1mi_fgar_result_bytes() + (size_t)AV1MI_FGAR_MAX_GROUPS * 3 * 47 * 8; }
+inline Av1miFgArBlock av1mi_fgar_split(void *block) {
+  uint8_t *b = reinterpret_cast<uint8_t *>(block);
+  uint32_t *gain = reinterpret_cast<uint32_t *>(b + 128);
+  return { reinterpret_cast<int8_t *>(b), b + 80, b + 104, gain, gain + 3, reinterpret_cast<long long *>(b + 152),
+           reinterpret_cast<long long *>(b + av1mi_fgar_result_bytes()) };
+}
+// where make_frame_header left the placeholders the passes overwrite in every frame's header slot: the first luma point (fg_bit) and the
+// first luma coefficient (fg_ar_bit) of a key and of an inter frame's header; all 0 without a header blob
+struct Av1miFgBits { int fg_key, fg_inter, ar_key, ar_inter; };
+
 extern "C" {
 // ---- whole chunk (or call): all P->n_frames frames
 // split masks of every superblock (partition_kernel)
@@ -51,32 +95,15 @@ hipError_t av1mi_launch_aq(const Av1miDevParams *P, const void *frames, uint16_t
 hipError_t av1mi_launch_tpl(const Av1miDevParams *P, const void *frames, uint32_t *intra, uint32_t *inter, uint32_t *key, unsigned long long *flow,
                             uint16_t *beta, hipStream_t stream);
 // the film-grain estimate (fg_kernel.hip, fg_rule.h) of the chunk's source: `frames` at the coded size, of which the whole 16x16 blocks of
-// the signalled size are read.  blocks: per [frame][block] the record { bin, v_y, v_u, v_v }, all written (16-byte aligned); parts: scratch
-// for the histograms' parts, AV1MI_FG_PARTS x 24 x 256 counters (16-byte aligned); table, counts: the 24 values [plane][bin], clamped to
-// ceil_y / ceil_c, and the bins' block counts; quart (optional): the 24 quartiles before the fill and the clamp, 0 for a bin without
-// blocks.  hdr_blob: null, or the chunk's header blob, whose
-// frame headers receive the values at bit_key / bit_inter (make_frame_header's fg_bit of the two frame kinds).  `frames` must be a
-// 16-byte aligned device pointer; it is only read
-#define AV1MI_FG_PARTS 64
-hipError_t av1mi_launch_film_grain(const Av1miDevParams *P, const void *frames, uint32_t *blocks, uint32_t *parts, uint8_t *table, uint32_t *counts,
-                                   uint8_t *quart, int ceil_y, int ceil_c, uint8_t *hdr_blob, int bit_key, int bit_inter, hipStream_t stream);
+// the signalled size are read; a 16-byte aligned device pointer, only read.  fg: the estimate's block, split.  The table is clamped to
+// ceil_y / ceil_c.  hdr_blob: null, or the chunk's header blob, whose frame headers receive the values at bits.fg_key / bits.fg_inter
+hipError_t av1mi_launch_film_grain(const Av1miDevParams *P, const void *frames, Av1miFgBlock fg, int ceil_y, int ceil_c, uint8_t *hdr_blob,
+                                   Av1miFgBits bits, hipStream_t stream);
 // the grain's autoregressive fit at lag 1 .. 3 (fg_ar_kernel.hip, fg_ar_rule.h) on the same frames, behind av1mi_launch_film_grain on the
-// same stream: blocks, quart, counts and table as that launch left them.  ar: a 16-byte aligned block of AV1MI_FGAR_BYTES - the result at
-// its head (int8 coefficients [plane][25], the 24 scaled values, the 24 unscaled, gains and flat blocks [plane], the sums [plane][46]; what
-// the host fetches in one copy), the workgroups' parts behind it.  hdr_blob: null, or the chunk's header blob, whose frame headers receive
-// the scaled values at fg_bit_* and the coefficient bytes at ar_bit_* (make_frame_header's fg_bit and fg_ar_bit of the two frame kinds)
-#define AV1MI_FGAR_COEFF_AT 0
-#define AV1MI_FGAR_TABLE_AT 80
-#define AV1MI_FGAR_SIGMA_AT 104
-#define AV1MI_FGAR_GAIN_AT 128
-#define AV1MI_FGAR_FLAT_AT 140
-#define AV1MI_FGAR_SUMS_AT 152
-#define AV1MI_FGAR_RESULT_BYTES 1280
-#define AV1MI_FGAR_MAX_GROUPS 1024
-#define AV1MI_FGAR_BYTES (AV1MI_FGAR_RESULT_BYTES + (size_t)AV1MI_FGAR_MAX_GROUPS * 3 * 47 * 8)
-hipError_t av1mi_launch_fg_ar(const Av1miDevParams *P, const void *frames, const uint32_t *blocks, const uint8_t *quart, const uint32_t *counts,
-                              const uint8_t *table, int lag, uint8_t *ar, uint8_t *hdr_blob, int fg_bit_key, int fg_bit_inter, int ar_bit_key,
-                              int ar_bit_inter, hipStream_t stream);
+// same stream: fg as that launch left it.  ar: the fit's block, split.  hdr_blob: null, or the chunk's header blob, whose frame headers
+// receive the scaled values at bits.fg_* and the coefficient bytes at bits.ar_*
+hipError_t av1mi_launch_fg_ar(const Av1miDevParams *P, const void *frames, Av1miFgBlock fg, int lag, Av1miFgArBlock ar, uint8_t *hdr_blob,
+                              Av1miFgBits bits, hipStream_t stream);
 // the source denoised by the film-grain table (fg_denoise_kernel.hip, fg_denoise_rule.h), out of place: `frames` as the caller gave them,
 // tight at the signalled size P->true_w x P->true_h, only read; `out` the same frames filtered, at the coded size, samples outside the
 // signalled picture replicating the denoised edge; table: the 24 values [plane][bin] in device memory (av1mi_launch_film_grain's, on the

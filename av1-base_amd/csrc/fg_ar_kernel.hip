@@ -1,11 +1,12 @@
 // fg_ar_kernel.hip - the film grain's autoregressive coefficients fitted to a chunk's source (av1mi_params.film_grain bits 12-13; DESIGN.md
 // §3 item 7d; fg_ar_rule.h is the rule).  Two kernels on the main stream, behind fg_table_kernel and in front of the denoiser:
 //
-// fg_ar_sums_kernel: walks the estimate's block records in fg_block_kernel's order - a workgroup of three waves takes four pairs of
-// blocks a step, waves 0 and 1 their eight luma blocks, wave 2 the four U and four V pair-rows - and skips a step's blocks that are no
-// candidates by their record (a wave none of whose blocks is one does nothing).  LANES ARE POSITIONS, the offsets are registers: a
-// lane holds one row of 16 samples, loaded with 16 bytes a load as fg_block_kernel does (a luma block's row, or the U (V) row of a pair of
-// blocks), so a block's rows sit in consecutive lanes.  S, A and B meet by exchanges over the block's 16 (8) lanes, e stays in the lane's
+// fg_ar_sums_kernel: walks the estimate's block records by fg_rule.h's block walk, the code fg_block_kernel wrote them by - a workgroup of
+// three waves takes four pairs of blocks a step, waves 0 and 1 their eight luma blocks, wave 2 the four U and four V pair-rows - and skips
+// a step's blocks that are no candidates by their record (a wave none of whose blocks is one does nothing).  One body, fgar_step<N>, for
+// the luma waves (N = 16, one block per lane row) and the chroma wave (N = 8, two).  LANES ARE POSITIONS, the offsets are registers: a
+// lane holds one row of 16 samples, addressed, loaded, packed and summed with fg_pieces.h's pieces as fg_block_kernel does, so a block's
+// rows sit in consecutive lanes.  S, A and B meet by exchanges over the block's 16 (8) lanes, e stays in the lane's
 // registers, the energy condition is tested the same way, and a block that fails it has its e zeroed rather than its lanes branched
 // away.  The products of a row with the rows 1 .. L below it come from those lanes, two 16-bit residuals per 32-bit exchange; per offset
 // the row's up to 16 products are summed in 32 bits with 24-bit multiply-adds (|e| < 2^14 and any sum of a flat block's products is at
@@ -13,7 +14,7 @@
 // workgroup's blocks.  Why not lanes as offsets: 46 of 64 lanes would work, every one of them would read the whole block - from LDS,
 // where the 46 lanes of an offset row read addresses one word apart at best and the same words over and over - and the products of a lane
 // would need 64-bit adds each.  With lanes as rows the block is read once into registers, LDS is not used in the loop at all and the
-// inner loop is one full-rate instruction per product; the price is 92 accumulator registers - 202 VGPRs in all, two waves a SIMD,
+// inner loop is one full-rate instruction per product; the price is 92 accumulator registers - 198 VGPRs in all, two waves a SIMD,
 // no scratch - in a loop with one load per step and otherwise arithmetic.  At the end the accumulators are reduced
 // over the lanes of a plane and the workgroup stores its part: store and sum, no atomics; integer sums, so any grid gives the same.
 // Algorithmic HBM bytes: the candidate blocks' samples once (at most n L b 3 / 2, L luma samples of the counted blocks, b bytes each)
@@ -29,13 +30,7 @@
 
 namespace {
 
-constexpr int FGAR_THREADS = 192;
 constexpr int FGAR_GROUP_WORDS = 3 * AV1MI_FGAR_PART;   // what a workgroup stores
-
-__device__ __forceinline__ unsigned long long fgar_sum_lanes(unsigned long long v, int lanes) {
-  for (int o = lanes >> 1; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // the products of this lane's row e[] - 16 / N blocks' rows of N residuals - with itself and with the rows 1 .. lag below it (the lanes
 // behind this one, while they are rows of the same blocks), added to acc[]; every lane of the wave comes here
@@ -52,7 +47,7 @@ __device__ __forceinline__ void fgar_accumulate(const int (&e)[16], int row, int
     }
   uint32_t pk[8];
 #pragma unroll
-  for (int j = 0; j < 8; j++) pk[j] = ((uint32_t)e[2 * j] & 0xFFFFu) | ((uint32_t)e[2 * j + 1] << 16);
+  for (int j = 0; j < 8; j++) pk[j] = fg_pack2(e[2 * j], e[2 * j + 1]);
 #pragma unroll
   for (int dy = 1; dy <= AV1MI_FGAR_MAX_LAG; dy++)
     if (dy <= lag) {
@@ -62,8 +57,8 @@ __device__ __forceinline__ void fgar_accumulate(const int (&e)[16], int row, int
       for (int j = 0; j < 8; j++) {
         uint32_t v = __shfl_down(pk[j], dy, 64);
         v = in ? v : 0u;
-        nb[2 * j] = (int)(int16_t)(v & 0xFFFFu);
-        nb[2 * j + 1] = (int)v >> 16;
+        nb[2 * j] = fg_lo16(v);
+        nb[2 * j + 1] = fg_hi16(v);
       }
 #pragma unroll
       for (int dx = -2 * AV1MI_FGAR_MAX_LAG; dx <= 2 * AV1MI_FGAR_MAX_LAG; dx++)
@@ -77,115 +72,88 @@ __device__ __forceinline__ void fgar_accumulate(const int (&e)[16], int row, int
     }
 }
 
+// One step of a wave's lanes, all 64 of which come here: a lane's row holds H blocks' rows of N samples, spot b's block and (chroma) the one
+// right of it.  A block that is no candidate by its record, or is not there, stays all zero: nothing of it is loaded (`both` guards the
+// right record and the right 8 samples) and its e[] adds nothing.  Returns early only when no lane of the wave has a candidate (a
+// ballot: wave-uniform), so every exchange below is reached by all lanes; no barrier in here.
+template <int N, typename PIX>
+__device__ __forceinline__ void fgar_step(const Av1miDevParams &P, const PIX *frames, const uint32_t *blocks, size_t at, const Av1miFgSpot &b, int plane, int row,
+                                          const int *q_of, const uint32_t *n_of, int lag, long long (&acc)[AV1MI_FGAR_SUMS], long long &n_flat) {
+  constexpr int H = 16 / N;
+  bool cand[H], flat[H], any = false;
+  int q[H], S[H], A[H], B[H];
+  unsigned long long en[H];
+#pragma unroll
+  for (int h = 0; h < H; h++) {
+    cand[h] = false; q[h] = S[h] = A[h] = 0; en[h] = 0;
+    if (h ? b.both : b.here) {
+      const uint32_t rec = blocks[at + h];
+      cand[h] = av1mi_fgar_candidate(rec, plane, q_of + plane * AV1MI_FG_BINS, n_of + plane * AV1MI_FG_BINS);
+      q[h] = q_of[plane * AV1MI_FG_BINS + (rec & 7u)];
+    }
+    any = any || cand[h];
+  }
+  if (!__ballot(any)) return;
+  int x[16], e[16];
+#pragma unroll
+  for (int c = 0; c < 16; c++) x[c] = 0;
+  if (any) fg_load_row<PIX>(fg_row_at(P, frames, plane, b.f, b.by, b.bx, row), N == 16 || b.both, x);
+#pragma unroll
+  for (int c = 0; c < 16; c++) { S[c / N] += x[c]; A[c / N] += (2 * (c & (N - 1)) - (N - 1)) * x[c]; }
+#pragma unroll
+  for (int h = 0; h < H; h++) {
+    B[h] = (2 * row - (N - 1)) * S[h];
+    S[h] = fg_sum_lanes(S[h], N); A[h] = fg_sum_lanes(A[h], N); B[h] = fg_sum_lanes(B[h], N);
+  }
+#pragma unroll
+  for (int c = 0; c < 16; c++) {
+    e[c] = cand[c / N] ? av1mi_fgar_residual(N, x[c], row, c & (N - 1), S[c / N], A[c / N], B[c / N]) : 0;
+    const uint32_t a = (uint32_t)(e[c] < 0 ? -e[c] : e[c]);   // (below 2^16: fg_ar_rule.h)
+    en[c / N] += a * a;
+  }
+  any = false;
+#pragma unroll
+  for (int h = 0; h < H; h++) {
+    en[h] = fg_sum_lanes(en[h], N);
+    flat[h] = cand[h] && av1mi_fgar_energy_ok(en[h], N, q[h], P.bit_depth);
+    if (flat[h] && row == 0) n_flat++;
+    any = any || flat[h];
+  }
+#pragma unroll
+  for (int c = 0; c < 16; c++) e[c] = flat[c / N] ? e[c] : 0;
+  if (__ballot(any)) fgar_accumulate<N>(e, row, lag, acc);
+}
+
 template <typename PIX>
-__global__ void __launch_bounds__(FGAR_THREADS) fg_ar_sums_kernel(Av1miDevParams P, const PIX *__restrict__ frames, const uint32_t *__restrict__ blocks,
-                                                                  const uint8_t *__restrict__ quart, const uint32_t *__restrict__ counts, int lag,
-                                                                  long long *__restrict__ parts) {
+__global__ void __launch_bounds__(AV1MI_FG_WALK_THREADS) fg_ar_sums_kernel(Av1miDevParams P, const PIX *__restrict__ frames, const uint32_t *__restrict__ blocks,
+                                                                           const uint8_t *__restrict__ quart, const uint32_t *__restrict__ counts, int lag,
+                                                                           long long *__restrict__ parts) {
   __shared__ int q_of[AV1MI_FG_TABLE];
   __shared__ uint32_t n_of[AV1MI_FG_TABLE];
   __shared__ long long red[6][AV1MI_FGAR_PART];   // the half-waves' sums: four of luma, U, V
   const int t = threadIdx.x;
   if (t < AV1MI_FG_TABLE) { q_of[t] = quart[t]; n_of[t] = counts[t]; }
   __syncthreads();
-  const int nbx = av1mi_fg_blocks(P.true_w), nby = av1mi_fg_blocks(P.true_h), npx = (nbx + 1) / 2;
-  const long n_pairs = (long)P.n_frames * nby * npx, n_steps = (n_pairs + 3) / 4;
-  const bool luma = t < 128;   // wave-uniform
-  const int slot = luma ? t >> 4 : ((t >> 3) & 3) * 2, row = luma ? t & 15 : t & 7, plane = luma ? 0 : 1 + ((t - 128) >> 5);
+  const int nbx = av1mi_fg_blocks(P.true_w), nby = av1mi_fg_blocks(P.true_h);
+  const long n_steps = av1mi_fg_walk_steps(P.n_frames, nbx, nby);
+  const Av1miFgLane L = av1mi_fg_walk_lane(t);
   long long acc[AV1MI_FGAR_SUMS];
 #pragma unroll
   for (int k = 0; k < AV1MI_FGAR_SUMS; k++) acc[k] = 0;
   long long n_flat = 0;
-  for (long step = blockIdx.x; step < n_steps; step += gridDim.x) {
-    // this lane's block (chroma: the left block of its pair), as fg_block_kernel places them
-    const long gp = step * 4 + (slot >> 1);
-    const int f = (int)(gp / ((long)nby * npx)), in_frame = (int)(gp % ((long)nby * npx));
-    const int by = in_frame / npx, bx = (in_frame % npx) * 2 + (slot & 1);
-    const bool here = gp < n_pairs && bx < nbx;
-    const size_t at = ((size_t)f * nby + by) * nbx + bx;
-    if (luma) {
-      bool cand = false;
-      int q = 0;
-      if (here) {
-        const uint32_t rec = blocks[at];
-        cand = av1mi_fgar_candidate(rec, 0, q_of, n_of);
-        q = q_of[rec & 7u];
-      }
-      if (!__ballot(cand)) continue;
-      int x[16], S = 0, A = 0;
-#pragma unroll
-      for (int c = 0; c < 16; c++) x[c] = 0;
-      if (cand) fg_load_row<PIX>(frames + (size_t)f * P.frame_samples + (size_t)(by * 16 + row) * P.stride_y + bx * 16, true, x);
-#pragma unroll
-      for (int c = 0; c < 16; c++) { S += x[c]; A += (2 * c - 15) * x[c]; }
-      int B = (2 * row - 15) * S;
-      for (int o = 8; o > 0; o >>= 1) { S += __shfl_xor(S, o, 64); A += __shfl_xor(A, o, 64); B += __shfl_xor(B, o, 64); }
-      int e[16];
-      unsigned long long en = 0;
-#pragma unroll
-      for (int c = 0; c < 16; c++) {
-        e[c] = cand ? av1mi_fgar_residual(16, x[c], row, c, S, A, B) : 0;
-        const uint32_t a = (uint32_t)(e[c] < 0 ? -e[c] : e[c]);   // (below 2^16: fg_ar_rule.h)
-        en += a * a;
-      }
-      en = fgar_sum_lanes(en, 16);
-      const bool flat = cand && av1mi_fgar_energy_ok(en, 16, q, P.bit_depth);
-#pragma unroll
-      for (int c = 0; c < 16; c++) e[c] = flat ? e[c] : 0;
-      if (flat && row == 0) n_flat++;
-      if (__ballot(flat)) fgar_accumulate<16>(e, row, lag, acc);
-    } else {
-      bool cand[2] = { false, false };
-      int q[2] = { 0, 0 };
-      const bool both = here && bx + 1 < nbx;
-      if (here) {
-        const uint32_t rec = blocks[at];
-        cand[0] = av1mi_fgar_candidate(rec, plane, q_of + plane * AV1MI_FG_BINS, n_of + plane * AV1MI_FG_BINS);
-        q[0] = q_of[plane * AV1MI_FG_BINS + (rec & 7u)];
-      }
-      if (both) {
-        const uint32_t rec = blocks[at + 1];
-        cand[1] = av1mi_fgar_candidate(rec, plane, q_of + plane * AV1MI_FG_BINS, n_of + plane * AV1MI_FG_BINS);
-        q[1] = q_of[plane * AV1MI_FG_BINS + (rec & 7u)];
-      }
-      if (!__ballot(cand[0] || cand[1])) continue;
-      int x[16], S[2] = { 0, 0 }, A[2] = { 0, 0 }, B[2];
-#pragma unroll
-      for (int c = 0; c < 16; c++) x[c] = 0;
-      if (cand[0] || cand[1])
-        fg_load_row<PIX>(frames + (size_t)f * P.frame_samples + (plane == 1 ? P.plane_off_u : P.plane_off_v) + (size_t)(by * 8 + row) * P.stride_c + bx * 8, both, x);
-#pragma unroll
-      for (int c = 0; c < 16; c++) { S[c >> 3] += x[c]; A[c >> 3] += (2 * (c & 7) - 7) * x[c]; }
-      B[0] = (2 * row - 7) * S[0]; B[1] = (2 * row - 7) * S[1];
-      for (int o = 4; o > 0; o >>= 1)
-#pragma unroll
-        for (int h = 0; h < 2; h++) { S[h] += __shfl_xor(S[h], o, 64); A[h] += __shfl_xor(A[h], o, 64); B[h] += __shfl_xor(B[h], o, 64); }
-      int e[16];
-      unsigned long long en[2] = { 0, 0 };
-#pragma unroll
-      for (int c = 0; c < 16; c++) {
-        e[c] = cand[c >> 3] ? av1mi_fgar_residual(8, x[c], row, c & 7, S[c >> 3], A[c >> 3], B[c >> 3]) : 0;
-        const uint32_t a = (uint32_t)(e[c] < 0 ? -e[c] : e[c]);
-        en[c >> 3] += a * a;
-      }
-      bool flat[2];
-#pragma unroll
-      for (int h = 0; h < 2; h++) {
-        en[h] = fgar_sum_lanes(en[h], 8);
-        flat[h] = cand[h] && av1mi_fgar_energy_ok(en[h], 8, q[h], P.bit_depth);
-        if (flat[h] && row == 0) n_flat++;
-      }
-#pragma unroll
-      for (int c = 0; c < 16; c++) e[c] = flat[c >> 3] ? e[c] : 0;
-      if (__ballot(flat[0] || flat[1])) fgar_accumulate<8>(e, row, lag, acc);
-    }
+  for (long step = blockIdx.x; step < n_steps; step += gridDim.x) {   // (no barrier in the loop: a wave without candidates goes on alone)
+    const Av1miFgSpot b = av1mi_fg_walk_spot(step, L.slot, P.n_frames, nbx, nby);   // this lane's block (chroma: the left block of its pair)
+    const size_t at = ((size_t)b.f * nby + b.by) * nbx + b.bx;
+    if (L.luma) fgar_step<16, PIX>(P, frames, blocks, at, b, 0, L.row, q_of, n_of, lag, acc, n_flat);   // (wave-uniform)
+    else fgar_step<8, PIX>(P, frames, blocks, at, b, L.plane, L.row, q_of, n_of, lag, acc, n_flat);
   }
   // the lanes' sums over each half-wave (a plane's lanes fill whole half-waves), then over the workgroup per plane
 #pragma unroll
   for (int k = 0; k < AV1MI_FGAR_SUMS; k++) {
-    const long long v = (long long)fgar_sum_lanes((unsigned long long)acc[k], 32);
+    const long long v = fg_sum_lanes(acc[k], 32);
     if ((t & 31) == 0) red[t >> 5][k] = v;
   }
-  n_flat = (long long)fgar_sum_lanes((unsigned long long)n_flat, 32);
+  n_flat = fg_sum_lanes(n_flat, 32);
   if ((t & 31) == 0) red[t >> 5][AV1MI_FGAR_SUMS] = n_flat;
   __syncthreads();
   if (t < FGAR_GROUP_WORDS) {
@@ -197,9 +165,8 @@ __global__ void __launch_bounds__(FGAR_THREADS) fg_ar_sums_kernel(Av1miDevParams
 constexpr int FGAR_SOLVE_THREADS = 1024, FGAR_SLICES = 7, FGAR_SLICE_STRIDE = 144;   // 7 x 144 lanes sum the parts
 
 __global__ void __launch_bounds__(FGAR_SOLVE_THREADS) fg_ar_solve_kernel(Av1miDevParams P, const long long *__restrict__ parts, int n_groups, int lag,
-                                                                         const uint8_t *__restrict__ table, uint8_t *__restrict__ out,
-                                                                         uint8_t *__restrict__ hdr_blob, int fg_bit_key, int fg_bit_inter, int ar_bit_key,
-                                                                         int ar_bit_inter) {
+                                                                         const uint8_t *__restrict__ table, Av1miFgArBlock out,
+                                                                         uint8_t *__restrict__ hdr_blob, Av1miFgBits bits) {
   __shared__ long long slice[FGAR_SLICES][FGAR_SLICE_STRIDE];
   __shared__ long long sums[FGAR_GROUP_WORDS];
   __shared__ int rho[3 * AV1MI_FGAR_SUMS];
@@ -239,26 +206,23 @@ __global__ void __launch_bounds__(FGAR_SOLVE_THREADS) fg_ar_solve_kernel(Av1miDe
   if (t < AV1MI_FG_TABLE) {
     const int v = av1mi_fgar_compensate(table[t], gain[t / AV1MI_FG_BINS]);
     final_v[t] = v;
-    out[AV1MI_FGAR_TABLE_AT + t] = (uint8_t)v;
-    out[AV1MI_FGAR_SIGMA_AT + t] = table[t];
+    out.table[t] = (uint8_t)v;
+    out.sigma[t] = table[t];
   }
-  if (t < 3 * AV1MI_FGAR_COEFFS) out[AV1MI_FGAR_COEFF_AT + t] = (uint8_t)coef[t / AV1MI_FGAR_COEFFS][t % AV1MI_FGAR_COEFFS];
+  if (t < 3 * AV1MI_FGAR_COEFFS) out.coeffs[t] = coef[t / AV1MI_FGAR_COEFFS][t % AV1MI_FGAR_COEFFS];
   if (t < 3) {
-    reinterpret_cast<uint32_t *>(out + AV1MI_FGAR_GAIN_AT)[t] = gain[t];
-    reinterpret_cast<uint32_t *>(out + AV1MI_FGAR_FLAT_AT)[t] = (uint32_t)sums[t * AV1MI_FGAR_PART + AV1MI_FGAR_SUMS];
+    out.gain[t] = gain[t];
+    out.flat[t] = (uint32_t)sums[t * AV1MI_FGAR_PART + AV1MI_FGAR_SUMS];
   }
-  if (t < 3 * AV1MI_FGAR_SUMS) reinterpret_cast<long long *>(out + AV1MI_FGAR_SUMS_AT)[t] = sums[(t / AV1MI_FGAR_SUMS) * AV1MI_FGAR_PART + t % AV1MI_FGAR_SUMS];
+  if (t < 3 * AV1MI_FGAR_SUMS) out.sums[t] = sums[(t / AV1MI_FGAR_SUMS) * AV1MI_FGAR_PART + t % AV1MI_FGAR_SUMS];
   __syncthreads();
   if (!hdr_blob) return;
   const int n_pos = av1mi_fgar_positions(lag);
   for (int f = t; f < P.n_frames; f += FGAR_SOLVE_THREADS) {   // one writer per header
     uint8_t *h = hdr_blob + P.seq_hdr_bytes + (size_t)f * P.hdr_slot_bytes;
     const bool inter = av1mi_frame_is_inter(P, f);
-    const int bit = inter ? fg_bit_inter : fg_bit_key;
-    for (int pl = 0; pl < 3; pl++)
-      for (int k = 0; k < AV1MI_FG_BINS; k++)
-        av1mi_fg_put8(h, bit + (pl == 0 ? 0 : (pl == 1 ? AV1MI_FG_CB_BIT : AV1MI_FG_CR_BIT)) + 16 * k + 8, (uint32_t)final_v[pl * AV1MI_FG_BINS + k]);
-    int ar = inter ? ar_bit_inter : ar_bit_key;
+    fg_put_points(h, inter ? bits.fg_inter : bits.fg_key, final_v);
+    int ar = inter ? bits.ar_inter : bits.ar_key;
     for (int pl = 0; pl < 3; pl++)   // luma's positions, then cb's and cr's with their luma tap (0) behind them
       for (int i = 0; i < n_pos + (pl ? 1 : 0); i++, ar += 8) av1mi_fg_put8(h, ar, (uint32_t)(128 + (i < n_pos ? coef[pl][i] : 0)));
   }
@@ -266,21 +230,18 @@ __global__ void __launch_bounds__(FGAR_SOLVE_THREADS) fg_ar_solve_kernel(Av1miDe
 
 }  // namespace
 
-extern "C" hipError_t av1mi_launch_fg_ar(const Av1miDevParams *P, const void *frames, const uint32_t *blocks, const uint8_t *quart, const uint32_t *counts,
-                                         const uint8_t *table, int lag, uint8_t *ar, uint8_t *hdr_blob, int fg_bit_key, int fg_bit_inter, int ar_bit_key,
-                                         int ar_bit_inter, hipStream_t stream) {
-  if (P->n_frames < 1 || lag < 1 || lag > AV1MI_FGAR_MAX_LAG || ((uintptr_t)frames & 15) || ((uintptr_t)ar & 15) ||
-      (hdr_blob && (fg_bit_key <= 0 || fg_bit_inter <= 0 || ar_bit_key <= 0 || ar_bit_inter <= 0)))
+extern "C" hipError_t av1mi_launch_fg_ar(const Av1miDevParams *P, const void *frames, Av1miFgBlock fg, int lag, Av1miFgArBlock ar, uint8_t *hdr_blob,
+                                         Av1miFgBits bits, hipStream_t stream) {
+  if (P->n_frames < 1 || lag < 1 || lag > AV1MI_FGAR_MAX_LAG || ((uintptr_t)frames & 15) || ((uintptr_t)ar.coeffs & 15) ||
+      (hdr_blob && (bits.fg_key <= 0 || bits.fg_inter <= 0 || bits.ar_key <= 0 || bits.ar_inter <= 0)))
     return hipErrorInvalidValue;
-  const int nbx = av1mi_fg_blocks(P->true_w), nby = av1mi_fg_blocks(P->true_h);
-  const long n_steps = ((long)P->n_frames * nby * ((nbx + 1) / 2) + 3) / 4;
+  const long n_steps = av1mi_fg_walk_steps(P->n_frames, av1mi_fg_blocks(P->true_w), av1mi_fg_blocks(P->true_h));
   const int n_groups = (int)(n_steps < AV1MI_FGAR_MAX_GROUPS ? n_steps : AV1MI_FGAR_MAX_GROUPS);
-  long long *parts = reinterpret_cast<long long *>(ar + AV1MI_FGAR_RESULT_BYTES);
+  const dim3 grid((unsigned)n_groups), threads(AV1MI_FG_WALK_THREADS);
   if (n_groups) {   // (a picture smaller than a block has none: no fit)
-    if (P->bit_depth == 8) hipLaunchKernelGGL((fg_ar_sums_kernel<uint8_t>), dim3((unsigned)n_groups), dim3(FGAR_THREADS), 0, stream, *P, (const uint8_t *)frames, blocks, quart, counts, lag, parts);
-    else hipLaunchKernelGGL((fg_ar_sums_kernel<uint16_t>), dim3((unsigned)n_groups), dim3(FGAR_THREADS), 0, stream, *P, (const uint16_t *)frames, blocks, quart, counts, lag, parts);
+    if (P->bit_depth == 8) hipLaunchKernelGGL((fg_ar_sums_kernel<uint8_t>), grid, threads, 0, stream, *P, (const uint8_t *)frames, fg.blocks, fg.quart, fg.counts, lag, ar.parts);
+    else hipLaunchKernelGGL((fg_ar_sums_kernel<uint16_t>), grid, threads, 0, stream, *P, (const uint16_t *)frames, fg.blocks, fg.quart, fg.counts, lag, ar.parts);
   }
-  hipLaunchKernelGGL(fg_ar_solve_kernel, dim3(1), dim3(FGAR_SOLVE_THREADS), 0, stream, *P, (const long long *)parts, n_groups, lag, table, ar, hdr_blob,
-                     fg_bit_key, fg_bit_inter, ar_bit_key, ar_bit_inter);
+  hipLaunchKernelGGL(fg_ar_solve_kernel, dim3(1), dim3(FGAR_SOLVE_THREADS), 0, stream, *P, (const long long *)ar.parts, n_groups, lag, fg.table, ar, hdr_blob, bits);
   return hipGetLastError();
 }

@@ -1,6 +1,7 @@
 // fg_denoise_kernel.hip - the chunk's source denoised by its film-grain table before anything codes it (av1mi_params.film_grain bits 8 and
 // 10; fg_denoise_rule.h is the rule).  One kernel on the main stream, behind fg_table_kernel, whose 24 values it
-// reads where that kernel left them.
+// reads where that kernel left them (Av1miFgBlock::table; launch_grain_passes runs the three film-grain passes in their order).  It works
+// on tiles of the coded size, not on the estimate's 16x16 blocks: it shares nothing with the block walk of fg_rule.h and fg_pieces.h.
 //
 // Out of place: it reads the frames as the caller gave them - tight, at the signalled size - and writes the chunk's source at the coded
 // size, so that chroma's index and every window see undenoised samples and the caller's memory is never written.  A workgroup takes a

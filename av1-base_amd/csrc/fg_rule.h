@@ -94,6 +94,30 @@ AV1MI_FG_HD inline int av1mi_fg_fill(const uint32_t *count, const int *value, in
   }
   return v > ceiling ? ceiling : v;
 }
+// ---- the block walk of fg_block_kernel and fg_ar_sums_kernel: both place their lanes and blocks by these functions alone, so the fit
+// visits the estimate's records where the estimate put them (tests/host/fg_rule_host.cpp runs the walk on the CPU).  A workgroup of three
+// waves takes four PAIRS of horizontally adjacent blocks a step, eight block slots: waves 0 and 1 are 128 luma lanes, 16 rows of each slot's
+// block; wave 2 is 2 x 32 chroma lanes, 8 U (V) rows of each pair - a lane sits at the pair's left slot and holds 2 x 8 samples.
+#define AV1MI_FG_WALK_THREADS 192
+#define AV1MI_FG_WALK_SLOTS 8
+struct Av1miFgLane { bool luma; int slot, row, plane; };   // (luma is wave-uniform)
+AV1MI_FG_HD inline Av1miFgLane av1mi_fg_walk_lane(int t) {
+  const bool luma = t < 128;
+  return { luma, luma ? t >> 4 : ((t >> 3) & 3) * 2, luma ? t & 15 : t & 7, luma ? 0 : 1 + ((t - 128) >> 5) };
+}
+// the steps of a chunk of n_frames frames of nbx x nby blocks
+AV1MI_FG_HD inline long av1mi_fg_walk_steps(int n_frames, int nbx, int nby) { return ((long)n_frames * nby * ((nbx + 1) / 2) + 3) / 4; }
+// the block of a slot at a step < av1mi_fg_walk_steps: pair (step * 4 + slot / 2) in frame, row, column order, side slot & 1.  here:
+// the block exists (f, by, bx are then inside the chunk); both: so does the block right of it - for a chroma lane, its pair's right half
+struct Av1miFgSpot { int f, by, bx; bool here, both; };
+AV1MI_FG_HD inline Av1miFgSpot av1mi_fg_walk_spot(long step, int slot, int n_frames, int nbx, int nby) {
+  const int npx = (nbx + 1) / 2;
+  const long per_frame = (long)nby * npx, gp = step * 4 + (slot >> 1);
+  const int in_frame = (int)(gp % per_frame), bx = (in_frame % npx) * 2 + (slot & 1);
+  const bool here = gp < n_frames * per_frame && bx < nbx;
+  return { (int)(gp / per_frame), in_frame / npx, bx, here, here && bx + 1 < nbx };
+}
+
 // writes the 8 bits of v at bit offset `bit` of h (MSB first, like the header's writer)
 AV1MI_FG_HD inline void av1mi_fg_put8(uint8_t *h, int bit, uint32_t v) {
   const int i = bit >> 3, sh = bit & 7;

@@ -19,7 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 # w, h, bit depth, frames: no block at all; 4 x 3 blocks; 10 bits; a size that is no multiple of 8 (the coded size is padded, the
-# padding must not count) with an odd number of blocks per row (a pair with one block); more than one step of a workgroup
+# padding must not count) with an odd number of blocks per row (a pair with one block); more than one workgroup at 10 bits (75 steps,
+# one each)
 SIZES = [(8, 8, 8, 1), (72, 56, 8, 3), (136, 72, 10, 2), (202, 122, 8, 2), (328, 248, 10, 2)]
 N = 50   # the ceiling: 100 luma, 50 chroma - above the left half's 64 sigma = 32, below the right half's 80 for chroma
 
@@ -32,6 +33,8 @@ def the_clip(kind, w, h, bd, n):
     if key not in _clips:
         if kind == "two_level":
             raw = fg_ref.two_level_clip(w, h, bd, n)
+        elif kind == "two_level_x4":   # a quarter of the frames, four times over: the records are per block
+            raw = fg_ref.two_level_clip(w, h, bd, n // 4) * 4
         elif kind == "checker":
             raw = fg_ref.checker_clip(w, h, bd, n)
         else:
@@ -65,7 +68,10 @@ def ctx(av1mi):
     c.close()
 
 
-CONTENT = [("two_level",) + s for s in SIZES] + [("synth", 202, 122, 8, 2), ("synth", 136, 72, 10, 2), ("checker", 72, 56, 8, 3), ("checker", 136, 72, 10, 2)]
+# ... and more than one step of a workgroup: 35 x 58 blocks of 16 frames are 4176 steps for the grid's 4096 workgroups (every row's last
+# pair lacks its right block)
+CONTENT = [("two_level",) + s for s in SIZES] + [("synth", 202, 122, 8, 2), ("synth", 136, 72, 10, 2), ("checker", 72, 56, 8, 3), ("checker", 136, 72, 10, 2),
+                                                 ("two_level_x4", 568, 928, 8, 16)]
 
 
 @pytest.mark.gpu

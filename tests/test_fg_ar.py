@@ -51,9 +51,11 @@ def ctx(av1mi):
 
 
 # one block (the fit is absent); no block; two blocks a frame; 10 bits; a width that is no multiple of 16 with an odd count of block pairs;
-# more than one step of a workgroup at 10 bits; a plane without noise; blocks only the energy condition keeps out
+# more than one workgroup at 10 bits (75 steps, one each); more than one step of a workgroup - 35 x 58 blocks of 4 frames are 1044 steps for
+# the grid's 1024 workgroups, and every row's last pair lacks its right block; a plane without noise; blocks only the energy condition
+# keeps out
 CONTENT = [("ar", 16, 16, 8, 1), ("ar", 8, 8, 8, 1), ("ar", 40, 24, 8, 2), ("ar", 72, 56, 10, 3), ("ar", 202, 122, 8, 2), ("ar", 328, 248, 10, 2),
-           ("const_u", 202, 122, 8, 2), ("vstep", 202, 122, 8, 2), ("hstep", 136, 120, 10, 2), ("checker", 72, 56, 8, 3), ("checker", 136, 72, 10, 2)]
+           ("ar", 568, 928, 8, 4), ("const_u", 202, 122, 8, 2), ("vstep", 202, 122, 8, 2), ("hstep", 136, 120, 10, 2), ("checker", 72, 56, 8, 3), ("checker", 136, 72, 10, 2)]
 FIELDS = ("sums", "flat", "coeffs", "gain", "table", "sigma_table")
 
 

@@ -1,7 +1,8 @@
 """CPU tests of the film-grain estimate's interface (include/av1mi.h: av1mi_params.film_grain bit 8, av1mi_film_grain_estimate,
 av1mi_film_grain_result): how the field packs and what is refused, the frame header of both frame kinds against the fixed mode's and
 against tests/fg_ref.py's bit string, the ABI staying what it was, and the rule header (av1-base_amd/csrc/fg_rule.h) compiled for the host
-- a stand-alone program, run plain and under the sanitizers - against the restatement on synthetic inputs no clip reaches."""
+- a stand-alone program, run plain and under the sanitizers - against the restatement on synthetic inputs no clip reaches, and its block
+walk, which the estimate's and the fit's kernels place their lanes by, against a plain enumeration."""
 import ctypes as C
 import os
 import re
@@ -112,6 +113,27 @@ def _table_cases():
     ]
 
 
+# (blocks per row, block rows, frames, workgroups): one block; no block; an odd count of blocks per row on one workgroup and on two; more
+# workgroups than steps; the GPU tests' multi-step clips - 1044 steps on the fit's 1024 workgroups, 4176 on the estimate's 4096
+WALKS = [(1, 1, 1, 1), (0, 3, 2, 1), (3, 2, 2, 1), (3, 2, 2, 2), (5, 1, 3, 4), (4, 3, 5, 3), (35, 58, 4, 1024), (35, 58, 16, 4096)]
+
+
+def _walk_plain(nbx, nby, nf, grid):
+    """what the program prints for a W line, from a plain enumeration: the pairs in frame, row, column order, four a step, the steps dealt
+    round the workgroups; slot 2 k + side of a step holds side `side` of its k-th pair"""
+    pairs = [(f, by, px) for f in range(nf) for by in range(nby) for px in range((nbx + 1) // 2)]
+    steps = (len(pairs) + 3) // 4
+    order = both = 0
+    for gp, (f, by, px) in enumerate(pairs):
+        for side in (0, 1):
+            if 2 * px + side < nbx:
+                order += 16 * ((gp // 4) * 8 + (gp % 4) * 2 + side + 1) * ((f * nby + by) * nbx + 2 * px + side + 1)   # 16 rows
+        both += 16 * (2 * px + 1 < nbx)   # 2 planes of 8 rows
+    wg_sum = sum((g + 1) * len(range(g, steps, grid)) for g in range(grid))
+    blocks = nf * nby * nbx
+    return [steps, 16 * blocks, 16 * blocks, 16 * len(pairs), 16 * len(pairs), both, 0, 0, wg_sum, order % (1 << 64)]
+
+
 @pytest.fixture(scope="module")
 def program(av1mi, tmp_path_factory):
     """(the case lines, the lines the plain program prints for them, the path of the case file)"""
@@ -124,6 +146,7 @@ def program(av1mi, tmp_path_factory):
             lines.append("Q %d %s" % (n, " ".join(str(int(v)) for v in rng.integers(0, 256 if n > 4 else 4, n))))
     for cy, cc, recs in _table_cases():
         lines.append("T %d %d %d %s" % (cy, cc, len(recs), " ".join("%x" % r for r in recs)))
+    lines += ["W %d %d %d %d" % w for w in WALKS]
     for kw in MIXES:
         kw = dict(kw)
         geom = (kw.pop("width", 1920), kw.pop("height", 1080), kw.pop("bit_depth", 10))
@@ -188,6 +211,19 @@ def test_rule_table_equals_the_restatement(program):
     assert t(5)[0][0].max() <= 100 and t(5)[0][1:].max() <= 50 and t(5)[0][0, 0] == 100 and t(5)[0][1, 0] == 50
     assert t(6)[0][0].max() <= 2 and t(6)[0][1:].max() <= 1
     assert [int(x) for x in t(7)[0][0]] == [min(16 * b, 100) for b in range(8)]
+
+
+def test_walk_takes_every_block_once(program):
+    """fg_rule.h's block walk, every lane of every workgroup over its steps: every block of every frame by exactly 16 luma lanes with the
+    rows 0 .. 15, every pair by exactly 8 lanes per chroma plane with the rows 0 .. 7, the right block flagged exactly when it exists,
+    nothing outside the picture, every lane of a workgroup as many steps as its index gives it, and the slots in the enumeration's order"""
+    lines, got, _ = program
+    outs = [[int(v) for v in g.split()] for ln, g in zip(lines, got) if ln[0] == "W"]
+    assert len(outs) == len(WALKS)
+    for w, g in zip(WALKS, outs):
+        assert g == _walk_plain(*w), w
+    steps = {w: g[0] for w, g in zip(WALKS, outs)}
+    assert steps[(0, 3, 2, 1)] == 0 and steps[(35, 58, 4, 1024)] == 1044 and steps[(35, 58, 16, 4096)] == 4176   # more steps than workgroups
 
 
 def test_standalone_program_under_sanitizers(program, tmp_path):
