@@ -38,7 +38,8 @@ E_INVALID_ARG, E_NO_DEVICE, E_HIP, E_OOM, E_OVERFLOW, E_FORMAT, E_UNSUPPORTED = 
 ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", "av1mi_last_error", "av1mi_encode_chunk",
                "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units", "av1mi_sym_order_result", "av1mi_sym_order_tiles", "av1mi_inter_partition_result", "av1mi_inter_partition_units",
                "av1mi_lr_rd_result", "av1mi_lr_rd_units", "av1mi_temporal_filter", "av1mi_tpl_analysis", "av1mi_film_grain_estimate",
-               "av1mi_film_grain_result", "av1mi_film_grain_denoise", "av1mi_film_grain_ar_estimate", "av1mi_film_grain_ar_result"]
+               "av1mi_film_grain_result", "av1mi_film_grain_denoise", "av1mi_film_grain_ar_estimate", "av1mi_film_grain_ar_result",
+               "av1mi_film_grain_denoise_temporal"]
 
 
 class Params(C.Structure):
@@ -125,6 +126,9 @@ _lib.av1mi_film_grain_ar_estimate.argtypes = [C.c_void_p, C.POINTER(Params), C.c
                                               C.POINTER(C.c_uint8), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_int64)]
 _lib.av1mi_film_grain_ar_result.argtypes = [C.c_void_p, C.POINTER(C.c_int8), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
 _lib.av1mi_film_grain_denoise.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8), C.c_void_p, C.POINTER(C.c_uint8)]
+_lib.av1mi_film_grain_denoise_temporal.restype = C.c_int
+_lib.av1mi_film_grain_denoise_temporal.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32),
+                                                   C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
 _lib.av1mi_lf_search_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)]
 _lib.av1mi_lr_fit_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_uint64)]
 _lib.av1mi_lr_fit_units.argtypes = [C.c_void_p]
@@ -232,6 +236,27 @@ def film_grain_denoised(v):
     return (v >> 10) & 1
 
 
+FILM_GRAIN_DENOISE_TEMPORAL = 0xC000   # include/av1mi.h: bits 14 and 15 of film_grain, both, with bits 8 and 10 - the denoiser's temporal term
+FILM_GRAIN_DENOISE_SPAN2 = 0x200       # ... bit 9, only with them: two neighbour frames each way instead of one
+FILM_GRAIN_DENOISE_SLOTS = 4           # the neighbours' slots of a frame in the keys' layout: g - f = -2, -1, +1, +2
+FILM_GRAIN_NO_NEIGHBOUR = 0xFFFFFFFF
+
+
+def film_grain_denoise_temporal(n, span=1):
+    """include/av1mi.h: AV1MI_FILM_GRAIN_DENOISE_TEMPORAL - film_grain_denoise(n) with the temporal term over span = 1 or 2 neighbours each way"""
+    return n | FILM_GRAIN_ESTIMATE | FILM_GRAIN_DENOISE | FILM_GRAIN_DENOISE_TEMPORAL | (FILM_GRAIN_DENOISE_SPAN2 if span == 2 else 0)
+
+
+def film_grain_denoise_span(v):
+    """include/av1mi.h: AV1MI_FILM_GRAIN_DENOISE_SPAN: 0, 1 or 2"""
+    return (2 if v & FILM_GRAIN_DENOISE_SPAN2 else 1) if v & FILM_GRAIN_DENOISE_TEMPORAL == FILM_GRAIN_DENOISE_TEMPORAL else 0
+
+
+def film_grain_mv_blocks(width, height):
+    """the 16x16 blocks of the coded size: what one (frame, slot) of the temporal term's keys holds"""
+    return ((((width + 7) & ~7) + 15) // 16) * ((((height + 7) & ~7) + 15) // 16)
+
+
 FILM_GRAIN_AR = 0x3000        # include/av1mi.h: bits 12-13 of film_grain, with bit 8 - the lag of the fitted autoregressive coefficients
 
 
@@ -307,8 +332,9 @@ def lr_unit_grid(width, height, shift=0):
 
 
 def default_params(width, height, bit_depth=8, aq_strength=None, tpl_strength=None, lr_fit=None, lr_wiener_fit=False, lr_unit_shift=0, lr_rd=None, tf_frames=None,
-                   tf_strength=None, film_grain_estimate=None, film_grain_denoise=None, film_grain_ar=None, **kw):
-    """film_grain_ar: a lag 1 .. 3 or-ed into the film_grain field the other keywords give (film_grain_ar); film_grain_estimate: N = 1 .. 50 sets film_grain to the estimated table with the ceiling N (the function of that name), True turns
+                   tf_strength=None, film_grain_estimate=None, film_grain_denoise=None, film_grain_ar=None, film_grain_temporal=None, **kw):
+    """film_grain_temporal: a span 1 or 2 - the denoiser's temporal term or-ed into the film_grain field the other keywords give
+    (film_grain_denoise_temporal); film_grain_ar: a lag 1 .. 3 or-ed into the film_grain field the other keywords give (film_grain_ar); film_grain_estimate: N = 1 .. 50 sets film_grain to the estimated table with the ceiling N (the function of that name), True turns
     the estimate on for the film_grain keyword's N; film_grain_denoise: likewise, with the source denoised by that table (the function of
     that name); aq_strength, tpl_strength: packed into cq_level beside the CQ level (cq_aq_tpl); lr_fit: True or a mask of parameter sets, packed into enable_lr
     (lr_fit_field); lr_wiener_fit: True sets enable_lr's bit 10 (LR_WIENER_FIT); lr_unit_shift: 1 / 2 sets enable_lr's bits 12-13
@@ -323,6 +349,8 @@ def default_params(width, height, bit_depth=8, aq_strength=None, tpl_strength=No
         kw["film_grain"] = FILM_GRAIN_ESTIMATE | FILM_GRAIN_DENOISE | (kw.get("film_grain", p.film_grain) if film_grain_denoise is True else int(film_grain_denoise))
     if film_grain_ar:
         kw["film_grain"] = kw.get("film_grain", p.film_grain) | ((int(film_grain_ar) & 3) << 12)
+    if film_grain_temporal:
+        kw["film_grain"] = kw.get("film_grain", p.film_grain) | FILM_GRAIN_DENOISE_TEMPORAL | (FILM_GRAIN_DENOISE_SPAN2 if int(film_grain_temporal) == 2 else 0)
     if tf_frames is not None or tf_strength is not None:
         kw["me_presearch"] = me_tf(kw.get("me_presearch", p.me_presearch), int(tf_frames or 0), int(tf_strength or 0))
     if lr_fit is not None and lr_fit is not False:
@@ -518,6 +546,38 @@ class Context:
                                            table.ctypes.data_as(C.POINTER(C.c_uint8)))
         _raise_for(rc, self.last_error())
         return out, table
+
+    def film_grain_denoise_temporal(self, params, frames, n_frames, on_device=False, out_ptr=None, use_table=None, use_mv=None, want_out=True):
+        """The film-grain denoiser with its temporal term (include/av1mi.h: av1mi_film_grain_denoise_temporal); frames, out_ptr, use_table
+        and the first two results as for film_grain_denoise.  Returns (denoised or None, table, mv): mv numpy uint32
+        [frame][slot g - f = -2, -1, +1, +2][16x16 block of the coded size], the keys the filter ran with; use_mv: keys in that layout it
+        takes instead of searching; want_out=False: only table and mv."""
+        import numpy as np
+        bps = 2 if params.bit_depth > 8 else 1
+        nbytes = params.width * params.height * 3 // 2 * bps * n_frames
+        nb = film_grain_mv_blocks(params.width, params.height)
+        table = np.zeros((3, 8), dtype=np.uint8)
+        mv = np.zeros((n_frames, FILM_GRAIN_DENOISE_SLOTS, nb), dtype=np.uint32)
+        given = given_mv = out = optr = None
+        if use_table is not None:
+            given = np.ascontiguousarray(np.asarray(use_table, dtype=np.uint8).reshape(24))
+        if use_mv is not None:
+            given_mv = np.ascontiguousarray(np.asarray(use_mv, dtype=np.uint32).reshape(mv.size))
+        fptr, keep = _frames_ptr(frames, on_device)
+        if on_device:
+            optr = C.c_void_p(int(out_ptr)) if out_ptr is not None else None
+        else:
+            if len(keep) != nbytes:
+                raise ValueError("frames: expected %d bytes, got %d" % (nbytes, len(keep)))
+            if want_out:
+                out = np.empty(nbytes, dtype=np.uint8)
+                optr = out.ctypes.data_as(C.c_void_p)
+        rc = _lib.av1mi_film_grain_denoise_temporal(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0,
+                                                    given.ctypes.data_as(C.POINTER(C.c_uint8)) if given is not None else None,
+                                                    given_mv.ctypes.data_as(C.POINTER(C.c_uint32)) if given_mv is not None else None, optr,
+                                                    table.ctypes.data_as(C.POINTER(C.c_uint8)), mv.ctypes.data_as(C.POINTER(C.c_uint32)))
+        _raise_for(rc, self.last_error())
+        return out, table, mv
 
     def film_grain_ar_estimate(self, params, frames, n_frames, on_device=False):
         """The film grain's autoregressive fit alone (include/av1mi.h: av1mi_film_grain_ar_estimate); frames as for scene_cuts.  Returns a

@@ -20,6 +20,7 @@
 #include "tpl_rule.h"
 #include "fg_rule.h"
 #include "fg_ar_rule.h"
+#include "fg_denoise_rule.h"
 #include "part_inter_rule.h"
 
 namespace av1mi {
@@ -117,6 +118,8 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     const size_t need = nf * av1mi_pi_frame_nodes(r.ch / 8, r.cw / 8) * sizeof(uint32_t);
     HIPCHK(c, ws_grow(w, w.d_nodes, w.nodes_bytes, need));
   }
+  // the keys of the film-grain denoiser's temporal term, on first use (and when a chunk has more frames than any before)
+  if (r.fg_denoise_span) HIPCHK(c, ws_grow(w, w.d_fgd_mv, w.fgd_mv_bytes, fgd_mv_entries(r, n_frames) * sizeof(uint32_t)));
   // the temporal filter's keys, on first use (and when a chunk has more key frames or followers than any before)
   if (r.tf_frames) HIPCHK(c, ws_grow(w, w.d_tf_mv, w.tf_mv_bytes, tf_mv_entries(r, n_frames) * sizeof(uint32_t)));
   if (dq_on(r) && !w.d_aq_map) {
@@ -194,14 +197,16 @@ void bind_workspace(Av1miDevParams &P, const Resolved &r, const Workspace &w) {
 }
 
 hipError_t launch_grain_passes(const Av1miDevParams &P, const Resolved &r, const void *tight, const void *coded, uint8_t *d_fg, uint8_t *d_fg_ar, void *out,
-                               uint8_t *hdr_blob, Av1miFgBits bits, hipStream_t s) {
+                               uint8_t *hdr_blob, Av1miFgBits bits, hipStream_t s, uint32_t *d_mv, bool have_mv, bool estimate) {
   const Av1miFgBlock fg = av1mi_fg_split(d_fg);
   const int N = (int)r.p.film_grain;
   hipError_t e = hipSuccess;
-  if (r.fg_estimate && coded) e = av1mi_launch_film_grain(&P, coded, fg, av1mi_fg_ceiling(N, 0), av1mi_fg_ceiling(N, 1), hdr_blob, bits, s);
+  if (r.fg_estimate && coded && estimate) e = av1mi_launch_film_grain(&P, coded, fg, av1mi_fg_ceiling(N, 0), av1mi_fg_ceiling(N, 1), hdr_blob, bits, s);
   // (the table in d_fg stays as the estimate left it: the headers carry the fit's scaled one, the denoiser filters by the grain's whole sigma)
-  if (e == hipSuccess && r.fg_ar_lag && coded && d_fg_ar) e = av1mi_launch_fg_ar(&P, coded, fg, r.fg_ar_lag, av1mi_fgar_split(d_fg_ar), hdr_blob, bits, s);
-  if (e == hipSuccess && r.fg_denoise && out) e = av1mi_launch_fg_denoise(&P, tight, out, fg.table, s);
+  if (e == hipSuccess && r.fg_ar_lag && coded && estimate && d_fg_ar) e = av1mi_launch_fg_ar(&P, coded, fg, r.fg_ar_lag, av1mi_fgar_split(d_fg_ar), hdr_blob, bits, s);
+  const int span = r.fg_denoise ? r.fg_denoise_span : 0;
+  if (e == hipSuccess && span && d_mv && !have_mv && coded) e = av1mi_launch_fg_denoise_search(&P, coded, d_mv, span, s);
+  if (e == hipSuccess && r.fg_denoise && out) e = av1mi_launch_fg_denoise(&P, tight, out, fg.table, d_mv, span, s);
   return e;
 }
 
@@ -604,23 +609,65 @@ int av1mi_film_grain_estimate(av1mi_ctx *c, const av1mi_params *params, const vo
   return t.finish(c, "film-grain");
 }
 
-// ... the denoiser: the estimate unless the caller gives the table; the result cropped to the caller's layout
+}  // extern "C"
+
+namespace {
+// ... the denoiser: the estimate unless the caller gives the table; the result cropped to the caller's layout.  With the temporal term
+// (the field's bits 14 and 15) the search's keys as well, unless the caller gives them - use_mv, n_frames * 4 * blocks entries on the host:
+// the indexes as they are, all-ones for "no neighbour", an index no vector of the range has refused, and the entries of neighbours frame f
+// cannot have at the span made all-ones; mv: the keys the filter ran with.  need_temporal: the field must carry the term
+int denoise_pass(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, const uint8_t *use_table,
+                 const uint32_t *use_mv, void *out, uint8_t *table, uint32_t *mv, bool need_temporal) {
+  Pass t(c, params);
+  const uintptr_t device_ptrs = frames_on_device ? (uintptr_t)frames | (uintptr_t)out : 0;
+  const bool mode = !t.rc && t.r.fg_denoise && (!need_temporal || t.r.fg_denoise_span);
+  const int span = mode ? t.r.fg_denoise_span : 0;
+  const size_t n_mv = span ? fgd_mv_entries(t.r, n_frames) : 0, nb = n_mv / n_frames / AV1MI_FGD_SLOTS;
+  std::vector<uint32_t> given;
+  if (span && use_mv) {   // (checked like the other arguments, before a device is touched)
+    const uint32_t nc = 2 * t.r.p.me_range + 1;
+    given.assign(use_mv, use_mv + n_mv);
+    for (size_t i = 0; i < n_mv; i++) {
+      if (!av1mi_fgd_slot_exists((int)(i / (AV1MI_FGD_SLOTS * nb)), (int)(i / nb % AV1MI_FGD_SLOTS), span, (int)n_frames)) given[i] = AV1MI_FGD_NONE;
+      else if (given[i] != AV1MI_FGD_NONE && (given[i] & 0x7FFu) >= nc * nc) {
+        set_err(c, "use_mv[%zu]: index %u is no vector of the range", i, given[i] & 0x7FFu);
+        return AV1MI_E_INVALID_ARG;
+      }
+    }
+  }
+  if (const int rc = t.open(c, n_frames, mode, need_temporal ? "film_grain does not ask for the denoiser's temporal term" : "film_grain does not ask for the denoiser", device_ptrs))
+    return rc;
+  uint8_t *d_fg = nullptr;
+  void *d_den = nullptr;
+  uint32_t *d_mv = nullptr;
+  t.alloc(d_fg, av1mi_fg_bytes(fg_records(t.r, n_frames)));
+  if (out) t.alloc(d_den, coded_bytes(t.r, n_frames));
+  if (span) t.alloc(d_mv, n_mv * sizeof(uint32_t));
+  if (t.ok() && span && use_mv) t.e = hipMemcpyAsync(d_mv, given.data(), n_mv * sizeof(uint32_t), hipMemcpyHostToDevice, t.stream);   // (`given` outlives the pass: finish() drains)
+  // (the estimate and the search read the coded size)
+  const PassFrames F = coded_frames(t, t.r, frames, n_frames, frames_on_device, false, !use_table || (span && !use_mv));
+  if (t.ok() && use_table) t.e = hipMemcpyAsync(d_fg, use_table, AV1MI_FG_TABLE, hipMemcpyHostToDevice, t.stream);
+  if (t.ok()) t.e = launch_grain_passes(t.P, t.r, F.tight, F.coded, d_fg, nullptr, d_den, nullptr, Av1miFgBits{}, t.stream, d_mv, use_mv != nullptr, !use_table);
+  if (t.ok() && out) return_frames(t, t.r, d_den, out, n_frames, frames_on_device);
+  to_host(t, table, d_fg, AV1MI_FG_TABLE);
+  to_host(t, mv, d_mv, n_mv * sizeof(uint32_t));
+  return t.finish(c, "film-grain denoise");
+}
+}  // namespace
+
+extern "C" {
+
 int av1mi_film_grain_denoise(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, const uint8_t *use_table,
                              void *out, uint8_t *table) {
   if (!c || !frames || !out || n_frames == 0) return AV1MI_E_INVALID_ARG;
-  Pass t(c, params);
-  const uintptr_t device_ptrs = frames_on_device ? (uintptr_t)frames | (uintptr_t)out : 0;
-  if (const int rc = t.open(c, n_frames, t.r.fg_denoise, "film_grain does not ask for the denoiser", device_ptrs)) return rc;
-  uint8_t *d_fg = nullptr;
-  void *d_den = nullptr;
-  t.alloc(d_fg, av1mi_fg_bytes(fg_records(t.r, n_frames)));
-  t.alloc(d_den, coded_bytes(t.r, n_frames));
-  const PassFrames F = coded_frames(t, t.r, frames, n_frames, frames_on_device, false, !use_table);   // (the estimate reads the coded size)
-  if (t.ok() && use_table) t.e = hipMemcpyAsync(d_fg, use_table, AV1MI_FG_TABLE, hipMemcpyHostToDevice, t.stream);
-  if (t.ok()) t.e = launch_grain_passes(t.P, t.r, F.tight, F.coded, d_fg, nullptr, d_den, nullptr, Av1miFgBits{}, t.stream);
-  if (t.ok()) return_frames(t, t.r, d_den, out, n_frames, frames_on_device);
-  to_host(t, table, d_fg, AV1MI_FG_TABLE);
-  return t.finish(c, "film-grain denoise");
+  return denoise_pass(c, params, frames, n_frames, frames_on_device, use_table, nullptr, out, table, nullptr, false);
+}
+
+// ... with the temporal term, its keys reported or given
+int av1mi_film_grain_denoise_temporal(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
+                                      const uint8_t *use_table, const uint32_t *use_mv, void *out, uint8_t *table, uint32_t *mv) {
+  if (!c || !frames || (!out && !mv) || n_frames == 0) return AV1MI_E_INVALID_ARG;
+  return denoise_pass(c, params, frames, n_frames, frames_on_device, use_table, use_mv, out, table, mv, true);
 }
 
 // ... the autoregressive fit, behind the estimate

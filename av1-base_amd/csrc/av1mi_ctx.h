@@ -58,6 +58,7 @@ struct Workspace {
   uint8_t *d_fg = nullptr, *h_fg = nullptr;
   // the grain's autoregressive fit (fg_ar_kernel.hip), on first use: its block (av1mi_fgar_split), and where one copy lands its head
   uint8_t *d_fg_ar = nullptr, *h_fg_ar = nullptr;
+  uint32_t *d_fgd_mv = nullptr;            // the film-grain denoiser's temporal term: the search's keys per [frame][slot][16x16 block] (fg_denoise_rule.h)
   uint32_t *d_tf_mv = nullptr;             // temporal filter: the search's keys per [key frame][follower][16x16 block] (tf_kernel.hip)
   Av1miQmEntry *d_qm = nullptr;        // quantiser-matrix steps (Av1miDevParams::qm_tab), one slice per quantiser slot, valid for qm_key = (slices, level, qidx, bit depth)
   std::vector<Av1miQmEntry> h_qm; int qm_key = -1;
@@ -85,7 +86,7 @@ struct Workspace {
   int cdf_bs_log2 = -1;                // ... and the leaf size its compact image behind the blob was made for
   int params_on_device = 0;            // d_params holds the first so many blocks of h_params (1, or AV1MI_AQ_SLOTS with adaptive quantisation)
   Av1miChunkRecord *h_record = nullptr; unsigned long long *h_sse = nullptr;   // d_record and d_sse land here
-  size_t out_cap = 0, me64_bytes = 0, nodes_bytes = 0, h_out_cap = 0, tf_mv_bytes = 0;   // bytes of d_out, d_me64, d_nodes, h_out, d_tf_mv
+  size_t out_cap = 0, me64_bytes = 0, nodes_bytes = 0, h_out_cap = 0, tf_mv_bytes = 0, fgd_mv_bytes = 0;   // bytes of d_out, d_me64, d_nodes, h_out, d_tf_mv, d_fgd_mv
   std::vector<std::pair<void *, bool>> owned;   // every buffer above: (address, page-locked host memory)
 };
 
@@ -128,9 +129,12 @@ inline size_t fg_records(const Resolved &r, size_t n_frames) { return n_frames *
 // The grain passes `r` asks for, in the encoder's order on stream s: the estimate on `coded` - the caller's frames on the device at the
 // coded size - into the estimate's block d_fg; the autoregressive fit on the same frames into the fit's block d_fg_ar; the denoiser from
 // `tight`, the same frames in the caller's layout, by d_fg's table into `out` at the coded size.  A pass whose frames or block are null is
-// left out (the stand-alone passes run their part).  hdr_blob: the chunk's header blob, which estimate and fit patch at `bits`, or null
+// left out (the stand-alone passes run their part).  hdr_blob: the chunk's header blob, which estimate and fit patch at `bits`, or null.
+// With the temporal term (r.fg_denoise_span) the denoiser is two launches: the search of every frame in its neighbours on `coded` into
+// d_mv (fgd_mv_entries) - in front of the filter, which on a padded chunk writes the block `coded` is - unless have_mv: d_mv holds the keys.
+// estimate: off for a table the caller has put into d_fg
 hipError_t launch_grain_passes(const Av1miDevParams &P, const Resolved &r, const void *tight, const void *coded, uint8_t *d_fg, uint8_t *d_fg_ar, void *out,
-                               uint8_t *hdr_blob, Av1miFgBits bits, hipStream_t s);
+                               uint8_t *hdr_blob, Av1miFgBits bits, hipStream_t s, uint32_t *d_mv = nullptr, bool have_mv = false, bool estimate = true);
 
 }  // namespace av1mi
 

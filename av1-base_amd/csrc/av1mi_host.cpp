@@ -103,10 +103,11 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   // filter - into every frame header, in front of every other kernel that patches a header (neighbouring fields can share a byte).  The
   // grain's autoregressive fit on the same frames: the coefficients, and the table scaled by the fit's gains over fg_table_kernel's values,
   // into every frame header.  The denoiser: the caller's frames filtered by the estimate's table into d_src at the coded size - out of place,
-  // the edge extension in its store (a padded chunk's extension above served the estimate alone).  Everything below reads the denoised chunk
+  // the edge extension in its store (a padded chunk's extension above served the estimate alone) - with the temporal term behind the search
+  // of every frame in its neighbours, which reads the undenoised *d_src first.  Everything below reads the denoised chunk
   if (r.fg_estimate) {
     const Av1miFgBits bits = { (int)fg_bit[0], (int)fg_bit[1], (int)ar_bit[0], (int)ar_bit[1] };
-    HIPCHK(c, launch_grain_passes(P, r, tight, *d_src, w.d_fg, w.d_fg_ar, w.d_src, w.d_hdr, bits, s));
+    HIPCHK(c, launch_grain_passes(P, r, tight, *d_src, w.d_fg, w.d_fg_ar, w.d_src, w.d_hdr, bits, s, w.d_fgd_mv));
     if (r.fg_denoise) *d_src = w.d_src;
   }
   // the key frames' temporal filter: in place in the chunk's source - a chunk that is used in place is copied first, the caller's

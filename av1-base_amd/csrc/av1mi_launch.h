@@ -107,8 +107,15 @@ hipError_t av1mi_launch_fg_ar(const Av1miDevParams *P, const void *frames, Av1mi
 // the source denoised by the film-grain table (fg_denoise_kernel.hip, fg_denoise_rule.h), out of place: `frames` as the caller gave them,
 // tight at the signalled size P->true_w x P->true_h, only read; `out` the same frames filtered, at the coded size, samples outside the
 // signalled picture replicating the denoised edge; table: the 24 values [plane][bin] in device memory (av1mi_launch_film_grain's, on the
-// same stream before).  Both frame pointers must be 16-byte aligned device pointers and different blocks
-hipError_t av1mi_launch_fg_denoise(const Av1miDevParams *P, const void *frames, void *out, const uint8_t *table, hipStream_t stream);
+// same stream before).  Both frame pointers must be 16-byte aligned device pointers and different blocks.  span = 1 or 2: with the
+// temporal term over so many neighbours each way, by the keys mv[(frame * 4 + slot) * blocks + block] (fg_denoise_rule.h) at range
+// P->me_range - av1mi_launch_fg_denoise_search's on the same stream before, or the caller's; span = 0: the spatial filter, mv is not read
+hipError_t av1mi_launch_fg_denoise(const Av1miDevParams *P, const void *frames, void *out, const uint8_t *table, const uint32_t *mv, int span,
+                                   hipStream_t stream);
+// the temporal term's search: `coded`, the undenoised frames at the coded size (a 16-byte aligned device pointer, only read; it may be the
+// block the filter launch behind it writes), every frame against its neighbours within `span` at range P->me_range; mv: all its
+// P->n_frames * 4 * blocks keys written, all-ones for a neighbour that does not exist
+hipError_t av1mi_launch_fg_denoise_search(const Av1miDevParams *P, const void *coded, uint32_t *mv, int span, hipStream_t stream);
 // the key frames' temporal filter (tf_kernel.hip, tf_rule.h), in place in `frames` at the coded size: every key frame of the chunk is
 // replaced by its filter over up to tf_frames followers at tf_strength, range P->me_range, and re-extended past the signalled size.
 // `frames` must be a 16-byte aligned device pointer (both callers pass an allocation of their own; anything else is refused).

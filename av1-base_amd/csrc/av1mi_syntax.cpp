@@ -19,6 +19,7 @@
 #include "tpl_rule.h"
 #include "tf_rule.h"
 #include "fg_rule.h"
+#include "fg_denoise_rule.h"
 
 namespace av1mi {
 
@@ -81,13 +82,17 @@ int resolve(const av1mi_params *in, Resolved *r) {
   // film_grain bit 8 (AV1MI_FILM_GRAIN_ESTIMATE): the table is estimated from the chunk's source, the low byte N = 1 .. 50 its ceiling;
   // without it 0 .. 50 as ever.  Bit 10 with bit 8 (AV1MI_FILM_GRAIN_DENOISE): the source is denoised by that table before it is coded
   // (fg_denoise_rule.h).  Bits 12-13 with bit 8 (AV1MI_FILM_GRAIN_AR): the lag 1 .. 3 at which the grain's autoregressive coefficients are
-  // fitted (fg_ar_rule.h).  Nothing in bit 9, bit 11 or above bit 13, and neither bit 10 nor bits 12-13 without bit 8
+  // fitted (fg_ar_rule.h).  Bits 14 and 15, both, with bits 8 and 10 (AV1MI_FILM_GRAIN_DENOISE_TEMPORAL): the denoiser's temporal term over
+  // one neighbour each way, with bit 9 over two (fg_denoise_rule.h: av1mi_fgd_field_span).  Nothing in bit 11 or above bit 15, neither bit
+  // 14 nor bit 15 alone, no bit 9 without them, and neither bit 10 nor bits 12-13 without bit 8
   r->fg_estimate = (p.film_grain & 0x100u) ? 1 : 0;
   r->fg_denoise = (p.film_grain & 0x400u) ? 1 : 0;
   r->fg_ar_lag = r->fg_estimate ? (int)AV1MI_FILM_GRAIN_AR_LAG(p.film_grain) : 0;
+  r->fg_denoise_span = av1mi_fgd_field_span(p.film_grain);
   if (r->fg_denoise && !r->fg_estimate) return AV1MI_E_INVALID_ARG;
+  if (((p.film_grain & 0xC000u) || (p.film_grain & 0x200u)) && !(r->fg_denoise_span && r->fg_denoise)) return AV1MI_E_INVALID_ARG;
   if (r->fg_estimate) {
-    if ((p.film_grain & ~0x35FFu) || (p.film_grain & 0xFFu) < 1 || (p.film_grain & 0xFFu) > AV1MI_FG_MAX_N) return AV1MI_E_INVALID_ARG;
+    if ((p.film_grain & ~0xF7FFu) || (p.film_grain & 0xFFu) < 1 || (p.film_grain & 0xFFu) > AV1MI_FG_MAX_N) return AV1MI_E_INVALID_ARG;
     p.film_grain &= 0xFFu;
   }
   if (p.film_grain > AV1MI_FG_MAX_N) return AV1MI_E_INVALID_ARG;
@@ -486,6 +491,10 @@ size_t fit_chunk_units(const Resolved &r, size_t n_frames) {
 // the temporal filter's keys of a chunk: [key frame][follower 1 .. tf_frames][16x16 block of the coded size]
 size_t tf_mv_entries(const Resolved &r, size_t n_frames) {
   return (size_t)av1mi_tf_key_frames((int)r.p.keyint, (int)n_frames) * (size_t)r.tf_frames * (size_t)av1mi_tf_blocks(r.cw) * (size_t)av1mi_tf_blocks(r.ch);
+}
+// the film-grain denoiser's temporal keys of a chunk: [frame][slot g - f = -2, -1, +1, +2][16x16 block of the coded size]
+size_t fgd_mv_entries(const Resolved &r, size_t n_frames) {
+  return n_frames * AV1MI_FGD_SLOTS * (size_t)av1mi_tf_blocks(r.cw) * (size_t)av1mi_tf_blocks(r.ch);
 }
 // whether the filter changes any frame of the chunk: some key frame has a follower (its first key frame then has)
 bool tf_runs(const Resolved &r, size_t n_frames) { return av1mi_tf_followers(r.tf_frames, (int)r.p.keyint, (int)n_frames, 0) > 0; }

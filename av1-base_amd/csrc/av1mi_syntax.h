@@ -35,6 +35,7 @@ struct Resolved {
   uint32_t lr_lambda;                 // enable_lr bits 14 and 15: the rate term's lambda (lr_rate_rule.h), 0 = the decisions go by the error alone
   int fg_estimate;                    // film_grain bit 8: the film-grain table is estimated per chunk (fg_rule.h); p.film_grain then holds the ceiling N alone
   int fg_denoise;                     // film_grain bit 10 (with bit 8): the chunk's source is denoised by the estimated table before it is coded (fg_denoise_rule.h)
+  int fg_denoise_span;                // film_grain bits 14 and 15 (with bits 8 and 10): the denoiser's temporal term over so many neighbours each way, 1 or with bit 9 2; 0 = the spatial filter alone
   int fg_ar_lag;                      // film_grain bits 12-13 (with bit 8): the grain's autoregressive coefficients are fitted per chunk at this lag (fg_ar_rule.h), 0 = white grain
   int tf_frames, tf_strength;        // me_presearch bits 8-10 and 12-14: the key frames' temporal filter (tf_rule.h), 0 followers = off (p.me_presearch then holds bit 0 alone)
 };
@@ -57,6 +58,7 @@ int tile_slot_bytes(const Resolved &r, int scale);
 int tile_stream_cap(const Resolved &r, int scale);
 size_t fit_chunk_units(const Resolved &r, size_t n_frames);
 size_t tf_mv_entries(const Resolved &r, size_t n_frames);
+size_t fgd_mv_entries(const Resolved &r, size_t n_frames);
 bool tf_runs(const Resolved &r, size_t n_frames);
 
 // The kernels' parameters of a chunk of `n_frames` frames, as far as they follow from `r` and the capacity multiplier: every buffer

@@ -74,6 +74,10 @@ typedef struct av1mi_ctx av1mi_ctx;
  * the two values above */
 #define AV1MI_FILM_GRAIN_AR(lag) (((uint32_t)(lag) & 3u) << 12)
 #define AV1MI_FILM_GRAIN_AR_LAG(v) ((((uint32_t)(v)) >> 12) & 3u)
+/* ... and the denoiser with its motion-compensated temporal term over span = 1 or 2 neighbour frames each way (bits 14 and 15, both, only
+ * together with bits 8 and 10; bit 9, only together with them, selects span 2); AV1MI_FILM_GRAIN_AR(L) may be or-ed in.  _SPAN: 0, 1 or 2 */
+#define AV1MI_FILM_GRAIN_DENOISE_TEMPORAL(n, span) ((uint32_t)(n) | 0x100u | 0x400u | 0xC000u | ((span) == 2 ? 0x200u : 0u))
+#define AV1MI_FILM_GRAIN_DENOISE_SPAN(v) ((((uint32_t)(v)) & 0xC000u) == 0xC000u ? ((((uint32_t)(v)) & 0x200u) ? 2u : 1u) : 0u)
 
 /* Operating point.  Replaces the reference's single constant
  *   SVT_PARAMS = "--crf 8 --preset 3 --film-grain 20 ... --keyint 240 --lookahead 40"
@@ -148,9 +152,19 @@ typedef struct {
                                whatever the content; tile data and reconstruction are those of the same mode with L = 0; the
                                denoiser keeps the unscaled table.  av1mi_write_headers returns ceiling values and zero coefficients,
                                av1mi_film_grain_result the scaled table, av1mi_film_grain_ar_result the rest.
-                               Bit 8 with a low byte of 0 or above 50, bit 10 or bits 12-13 without bit 8, bit 9, bit 11, any bit
-                               above 13, and 51..255 are refused with AV1MI_E_INVALID_ARG.  A context may switch the mode and the
-                               lag from chunk to chunk */
+                               bits 14 and 15, both, together with bits 8 and 10 (AV1MI_FILM_GRAIN_DENOISE_TEMPORAL(N, span);
+                               DESIGN.md section 3 item 7e): the denoiser's temporal term.  Grain is independent from frame to
+                               frame, the picture is not: per 16x16 luma block every frame f is searched (whole samples, +-me_range
+                               around zero, the undenoised frames at the coded size) in each neighbour g = f - S .. f + S of the
+                               chunk, S = 1, or 2 with bit 9, across key frames; on top of its 5x5 window every sample takes the
+                               3x3 window of the caller's undenoised frame g around the displaced position (chroma: the vector
+                               halved, whole samples), with the same weights by the same T - the centre counting four times - so
+                               a wrong match weighs nothing.  A zero table still changes nothing, no sample moves by T or more,
+                               and a one-frame chunk is the spatial filter's.  Headers and av1mi_film_grain_result stay the
+                               estimate mode's.
+                               Bit 8 with a low byte of 0 or above 50, bit 10 or bits 12-13 without bit 8, bit 14 or bit 15 alone or
+                               without bit 10, bit 9 without bits 14 and 15, bit 11, any bit above 15, and 51..255 are refused with
+                               AV1MI_E_INVALID_ARG.  A context may switch the mode, the span and the lag from chunk to chunk */
   uint32_t first_frame;     /* number of the chunk's first frame inside the clip (seeds grain_seed per frame) */
   uint32_t me_range;        /* inter frames: motion search range in luma samples, 8 or 16 (0 = 8) */
   uint32_t enable_lr;       /* 1 = loop restoration on luma (Wiener, 64x64 units, each unit off or one of 3 filters by SSE);
@@ -371,9 +385,20 @@ int av1mi_film_grain_result(const av1mi_ctx *ctx, uint8_t *table);
  * `frames` (device pointers 16-byte aligned, a block other than `frames`).  table (optional, host): the 24 values [plane * 8 + k] the
  * filter ran with.  use_table (optional, host): 24 values the filter takes as they are instead of the chunk's estimate - no ceiling is
  * applied and the estimate is skipped.  AV1MI_E_INVALID_ARG without bits 8 and 10; the arguments are checked before a device is touched.
- * Like av1mi_film_grain_estimate it looks at the frames it is given. */
+ * Like av1mi_film_grain_estimate it looks at the frames it is given.  A field with bits 14 and 15 runs the temporal term as well, the
+ * encoder's launches.  (av1mi_film_grain_estimate and av1mi_film_grain_ar_estimate accept those bits and behave as without them.) */
 int av1mi_film_grain_denoise(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
                              const uint8_t *use_table, void *out, uint8_t *table);
+/* The same with the temporal term's vectors in the open (AV1MI_FILM_GRAIN_DENOISE_TEMPORAL; AV1MI_E_INVALID_ARG without bits 14 and 15).
+ * use_table, out and table as above; out may be NULL when only mv is wanted.  mv (optional, host): n_frames * 4 * nb entries,
+ * nb = ceil(coded width / 16) * ceil(coded height / 16) blocks in raster order, at [(f * 4 + slot) * nb + b] the key the filter ran with
+ * for frame f, its neighbour g = f - 2, f - 1, f + 1, f + 2 (slot 0 .. 3) and block b: (cost << 11) | index as av1mi_temporal_filter
+ * reports its own - index = (dy + R) * (2 R + 1) + (dx + R), R = me_range -, 0xFFFFFFFF where g is no frame of the chunk or beyond the
+ * span.  use_mv (optional, host, same layout): the search is skipped and the entries' indexes are taken as they are; 0xFFFFFFFF: the
+ * block has no such neighbour; an index of (2 R + 1)^2 or more is AV1MI_E_INVALID_ARG; entries of slots beyond the span or outside
+ * the chunk are ignored.  The arguments are checked before a device is touched. */
+int av1mi_film_grain_denoise_temporal(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
+                                      const uint8_t *use_table, const uint32_t *use_mv, void *out, uint8_t *table, uint32_t *mv);
 
 /* ---- the film grain's autoregressive fit on its own --------------------------------------------------
  * What av1mi_encode_chunk runs on a chunk's source when av1mi_params.film_grain carries bit 8 and a lag in bits 12-13

@@ -85,6 +85,10 @@ pub const fn film_grain_denoised(v: u32) -> u32 { (v >> 10) & 1 }
 pub const AV1MI_FILM_GRAIN_AR_MAX_LAG: u32 = 3;
 pub const fn film_grain_ar(lag: u32) -> u32 { (lag & 3) << 12 }
 pub const fn film_grain_ar_lag(v: u32) -> u32 { (v >> 12) & 3 }
+// AV1MI_FILM_GRAIN_DENOISE_TEMPORAL / AV1MI_FILM_GRAIN_DENOISE_SPAN - film_grain bits 14 and 15, with bits 8 and 10: the denoiser's
+// motion-compensated temporal term over span = 1 or (bit 9) 2 neighbour frames each way
+pub const fn film_grain_denoise_temporal(n: u32, span: u32) -> u32 { n | 0x100 | 0x400 | 0xC000 | if span == 2 { 0x200 } else { 0 } }
+pub const fn film_grain_denoise_span(v: u32) -> u32 { if v & 0xC000 == 0xC000 { if v & 0x200 != 0 { 2 } else { 1 } } else { 0 } }
 #[repr(C)]
 pub struct Av1miCtx { _opaque: [u8; 0] }   // include/av1mi.h: av1mi_ctx
 type ProgressCb =Option<extern "C" fn(user: *mut c_void, done: u32, total: u32, fps: f64, bytes: u64)>;
@@ -104,6 +108,10 @@ extern "C" {
     // table[24] (optional) the values the filter ran with, use_table[24] (optional) values it takes instead of the chunk's estimate
     pub fn av1mi_film_grain_denoise(ctx: *mut Av1miCtx, params: *const Av1miParams, frames: *const c_void, n_frames: u32, frames_on_device: c_int,
                                     use_table: *const u8, out: *mut c_void, table: *mut u8) -> c_int;
+    // ... with the temporal term (film_grain_denoise_temporal): mv[n_frames * 4 * blocks] (optional) the search's keys the filter ran with,
+    // use_mv (optional, same layout) keys it takes instead of searching; `out` may be null when only mv is wanted
+    pub fn av1mi_film_grain_denoise_temporal(ctx: *mut Av1miCtx, params: *const Av1miParams, frames: *const c_void, n_frames: u32, frames_on_device: c_int,
+                                             use_table: *const u8, use_mv: *const u32, out: *mut c_void, table: *mut u8, mv: *mut u32) -> c_int;
     // the grain's autoregressive fit of `n_frames` frames taken as one chunk: coeffs[3 * 25] in Q7, table[24] as the headers carry it,
     // sigma_table[24] before the gains, gain[3] in Q8, flat_blocks[3], sums[3 * 46], every output optional (null); and the fit of a
     // context's last chunk

@@ -12,7 +12,13 @@ A third clip, "arnoise", is the ramps with the same noise passed through a known
 tool also runs the fourth mode, estimated + denoised + the grain's autoregressive fit at lag 1, 2 and 3,
 alternated with the denoise mode, and adds per lag the fitted Q7 coefficients beside the injected ones, the gains, the flat blocks and
 their share of all blocks, the milliseconds of the new pass (the difference of "start -> source ready" against the denoise mode's)
-beside the estimate's, and bytes per frame.  It reports what it measures, nothing more."""
+beside the estimate's, and bytes per frame.
+A fourth clip, "texture", is a field of independent random samples that moves two samples right and down per frame under Gaussian noise of
+sigma 1 (8-bit scale) - what the spatial window finds no honest neighbour in.  On the clips whose clean original the tool keeps it also
+runs the denoiser's temporal term at S = 1 and S = 2, film_grain = AV1MI_FILM_GRAIN_DENOISE_TEMPORAL(N, S),
+alternated with the spatial mode (--spans; empty: none): per span the milliseconds of the denoiser's launches (the difference of "start ->
+source ready" against the estimate mode's, as ms_pass_denoise is the spatial mode's), bytes per frame, and the PSNR of the coded source
+against the clean clip.  It reports what it measures, nothing more."""
 import argparse
 import json
 import os
@@ -64,6 +70,31 @@ def noisy_ramp_clip(torch, w, h, bd, n, dev, seed=7, coeffs=None):
     return torch.cat(frames).view(torch.uint8), clean.view(torch.uint8)
 
 
+def noisy_texture_clip(torch, w, h, bd, n, dev, seed=9, motion=(2, 2), sigma=1.0):
+    """n frames of a random texture - luma independent uniform samples 60 .. 200 (8-bit scale), U and V 100 .. 156 - that moves `motion`
+    luma samples right and down per frame (chroma half as far), with Gaussian noise of `sigma`, a new field every frame.  Returns (the clip,
+    the clean frames in the same layout)"""
+    g = torch.Generator(device=dev)
+    g.manual_seed(seed)
+    sc, mx = 1 << (bd - 8), float((1 << bd) - 1)
+    dt = torch.int16 if bd > 8 else torch.uint8
+    mxs, mys = motion[0] * (n - 1), motion[1] * (n - 1)
+    fields = [torch.randint(60 * sc, 200 * sc + 1, (h + mys, w + mxs), generator=g, device=dev).float()] + [
+        torch.randint(100 * sc, 156 * sc + 1, (h // 2 + mys // 2, w // 2 + mxs // 2), generator=g, device=dev).float() for _ in range(2)]
+    frames, clean = [], []
+    for t in range(n):
+        fc, fn = [], []
+        for pl, fld in enumerate(fields):
+            d, ph, pw = (1, h, w) if pl == 0 else (2, h // 2, w // 2)
+            oy, ox = (n - 1 - t) * motion[1] // d, (n - 1 - t) * motion[0] // d
+            c = fld[oy:oy + ph, ox:ox + pw]
+            fc.append(c.to(dt).reshape(-1))
+            fn.append((c + sigma * sc * torch.randn(c.shape, generator=g, device=dev)).round().clamp(0, mx).to(dt).reshape(-1))
+        clean.append(torch.cat(fc))
+        frames.append(torch.cat(fn))
+    return torch.cat(frames).view(torch.uint8), torch.cat(clean).view(torch.uint8)
+
+
 def psnr(torch, a, b, bd):
     """of two clips in one layout, over every sample"""
     dt = torch.int16 if bd > 8 else torch.uint8
@@ -77,7 +108,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--frames", type=int, default=60)
-    ap.add_argument("--clips", default="synth,noise,arnoise")
+    ap.add_argument("--clips", default="synth,noise,arnoise,texture")
+    ap.add_argument("--spans", default="1,2", help="the temporal term's spans to run on the clips with a clean original; empty: none")
     ap.add_argument("--level", type=int, default=20, help="N: the fixed table's level and the estimate's ceiling")
     ap.add_argument("--keyints", default="1,240")
     ap.add_argument("--extra", default="", help="further parameters for every run, name=value,...")
@@ -89,8 +121,12 @@ def main():
     extra = {k: int(v) for k, v in (kv.split("=") for kv in args.extra.split(",") if kv)}
     with av1mi.Context(0) as ctx:
         for name in args.clips.split(","):
-            clip, clean = (bench.make_clip_torch(w, h, bd, n, 1080, dev), None) if name == "synth" else noisy_ramp_clip(
-                torch, w, h, bd, n, dev, coeffs=AR_TRUTH if name == "arnoise" else None)
+            if name == "synth":
+                clip, clean = bench.make_clip_torch(w, h, bd, n, 1080, dev), None
+            elif name == "texture":
+                clip, clean = noisy_texture_clip(torch, w, h, bd, n, dev)
+            else:
+                clip, clean = noisy_ramp_clip(torch, w, h, bd, n, dev, coeffs=AR_TRUTH if name == "arnoise" else None)
             torch.cuda.synchronize(dev)
             for keyint in (int(k) for k in args.keyints.split(",")):
                 kw = dict(keyint=keyint, intra_mode_mask=0x7, **extra)
@@ -133,6 +169,24 @@ def main():
                     assert (ran_with == table).all()
                     line["psnr_source_against_clean_before"] = round(psnr(torch, clip, clean, bd), 3)
                     line["psnr_source_against_clean_after"] = round(psnr(torch, out, clean, bd), 3)
+                    # the temporal term, alternated with the spatial mode
+                    spans = {int(v): av1mi.default_params(w, h, bd, film_grain_denoise=args.level, film_grain_temporal=int(v), **kw) for v in args.spans.split(",") if v}
+                    for p in spans.values():
+                        ctx.encode_chunk(p, clip.data_ptr(), n, on_device=True, copy_out=False)
+                    ms, ms_spatial, nbytes = {v: None for v in spans}, None, {}
+                    for _ in range(args.steps):
+                        for v, p in spans.items():
+                            _, _, r0, _ = ctx.encode_chunk(den, clip.data_ptr(), n, on_device=True, copy_out=False)
+                            _, _, r1, _ = ctx.encode_chunk(p, clip.data_ptr(), n, on_device=True, copy_out=False)
+                            d0, d1 = r0.ms_h2d - rep["estimate"].ms_h2d, r1.ms_h2d - rep["estimate"].ms_h2d
+                            ms_spatial = d0 if ms_spatial is None or d0 < ms_spatial else ms_spatial
+                            if ms[v] is None or d1 < ms[v]:
+                                ms[v], nbytes[v] = d1, r1.bytes
+                    for v, p in spans.items():
+                        ctx.film_grain_denoise(p, clip.data_ptr(), n, on_device=True, out_ptr=out.data_ptr())
+                        line["temporal_s%d" % v] = {"ms_pass_denoise": round(ms[v], 3), "ms_pass_denoise_spatial_alternated": round(ms_spatial, 3),
+                                                    "bytes_per_frame": round(nbytes[v] / n, 1),
+                                                    "psnr_source_against_clean_after": round(psnr(torch, out, clean, bd), 3)}
                     del out
                 if name == "arnoise":   # the fourth mode, alternated with the denoise mode
                     lags = {lag: av1mi.default_params(w, h, bd, film_grain_denoise=args.level, film_grain_ar=lag, **kw) for lag in (1, 2, 3)}
