@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include "av1mi_dev.h"
 #include "av1mi_launch.h"
+#include "quant_pieces.h"
 
 namespace {
 
@@ -64,7 +65,6 @@ struct SymLds {
   uint8_t left_lvl[3][16], left_dc[3][16];   // per superblock row of the tile
 };
 __shared__ SymLds g_sym;
-#define S (&g_sym)
 // per-tile state whose size depends on the tile size (TSB x TSB superblocks): block info of the tile's 8x8 units and the
 // above contexts; only the two-superblock instantiations reference (and allocate) the larger object
 template <int TSB>
@@ -74,13 +74,37 @@ struct TileLds {
 };
 __shared__ TileLds<1> g_tile1;
 __shared__ TileLds<2> g_tile2;
-template <int TSB> struct TileSel;
-template <> struct TileSel<1> { static __device__ __forceinline__ TileLds<1> &get() { return g_tile1; } };
-template <> struct TileSel<2> { static __device__ __forceinline__ TileLds<2> &get() { return g_tile2; } };
-#define TI (TileSel<TSB>::get())
-#define TW (8 * TSB)   // tile width in 8x8 units
+template <int TSB>
+__device__ __forceinline__ TileLds<TSB> &tile_lds() {
+  if constexpr (TSB == 1) return g_tile1; else return g_tile2;
+}
+
+// The offsets of the wide rows whose place depends on the variant: the full layout (Av1miCdfLayout) keeps them per transform size, the
+// compact one (Av1miCdfCompact) per plane type.  PARTITION .. SKIP, KF_Y_MODE, ANGLE_DELTA, UV_MODE and the inter rows are CL's in both.
+template <bool FULL>
+struct Rows {
+  static __device__ __forceinline__ uint16_t *lds() { if constexpr (FULL) return g_cdfw_full; else return g_cdfw_compact; }
+  static __device__ __forceinline__ int txb_skip(int txs, int ptype, int zctx) { return FULL ? CL::TXB_SKIP + (txs * 13 + zctx) * 3 : CC::TXB_SKIP + (ptype * 13 + zctx) * 3; }
+  // msz = 2 bwl - 4: the eob class row of the coded area's size (5 + msz symbols), context 0
+  static __device__ __forceinline__ int eob(int msz, int ptype) { return FULL ? CL::EOB16 + 4 * (msz * 6 + (msz * (msz - 1)) / 2) + ptype * 2 * (6 + msz) : CC::EOB + ptype * 12; }
+  static __device__ __forceinline__ int eob_extra(int txs, int ptype, int k) { return FULL ? CL::EOB_EXTRA + ((txs * 2 + ptype) * 9 + k) * 3 : CC::EOB_EXTRA + (ptype * 9 + k) * 3; }
+  static __device__ __forceinline__ int coeff_base_eob(int txs, int ptype, int cctx) { return FULL ? CL::COEFF_BASE_EOB + ((txs * 2 + ptype) * 4 + cctx) * 4 : CC::COEFF_BASE_EOB + (ptype * 4 + cctx) * 4; }
+  static __device__ __forceinline__ int dc_sign(int ptype, int dctx) { return (FULL ? CL::DC_SIGN : CC::DC_SIGN) + (ptype * 3 + dctx) * 3; }
+  // intra set 1 (transforms of 4 and 8 points, rows of 8) or set 2 (16 points, rows of 6)
+  static __device__ __forceinline__ int tx_set(int log2n, int ymode) {
+    if (log2n <= 3) return FULL ? CL::TX_SET1 + ((log2n - 2) * 13 + ymode) * 8 : CC::TXSET + ymode * 8;
+    return FULL ? CL::TX_SET2 + ((log2n - 2) * 13 + ymode) * 6 : CC::TXSET + ymode * 6;
+  }
+  static __device__ __forceinline__ int restore_switchable() { return FULL ? CL::RESTORE_SW : CC::RESTORE_SW; }
+  static __device__ __forceinline__ int use_wiener() { return FULL ? CL::USE_WIENER : CC::USE_WIENER; }
+  static __device__ __forceinline__ int delta_q() { return FULL ? CL::DELTA_Q : CC::DELTA_Q; }
+  static __device__ __forceinline__ int cfl_sign() { return FULL ? CL::CFL_SIGN : CC::CFL_SIGN; }
+  static __device__ __forceinline__ int cfl_alpha(int sign_own, int sign_other) { return (FULL ? CL::CFL_ALPHA : CC::CFL_ALPHA) + ((sign_own - 1) * 3 + sign_other) * 17; }
+};
 
 struct Sym {
+  int lane;          // of the tile's wave
+  int adapt;         // the CDFs adapt (disable_cdf_update = 0)
   uint16_t *cdf;     // the variant's wide rows (LDS)
   uint32_t *out;     // this tile's stream (global)
   int pos;           // entries written (uniform)
@@ -94,67 +118,56 @@ __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
 __device__ __forceinline__ int floor_log2(unsigned v) { return 31 - __builtin_clz(v); }
 
-__device__ __forceinline__ void emit1(Sym &y, int lane, uint32_t ent) {
-  if (lane == 0 && y.pos < y.cap) y.out[y.pos] = ent;
+__device__ __forceinline__ void emit1(Sym &y, uint32_t ent) {
+  if (y.lane == 0 && y.pos < y.cap) y.out[y.pos] = ent;
   y.pos++;
 }
-// A run of `len` <= 64 literal bits, most significant first, with one store: lane i writes bit len - 1 - i at pos + i.  Entries at or
-// beyond the capacity are not written; pos keeps counting, so stream_len > stream_cap still reports the overflow.
-__device__ __forceinline__ void emit_bits(Sym &y, int lane, unsigned long long bits, int len) {
-  if (lane < len && y.pos + lane < y.cap) y.out[y.pos + lane] = ENT_LITERAL((int)((bits >> ((len - 1 - lane) & 63)) & 1));
-  y.pos += len;
-}
-__device__ __forceinline__ void emit_bits(Sym &y, int lane, unsigned bits, int len) {   // len <= 32
-  if (lane < len && y.pos + lane < y.cap) y.out[y.pos + lane] = ENT_LITERAL((int)((bits >> ((len - 1 - lane) & 31)) & 1));
+// A run of `len` literal bits (at most 64, and at most the width of W), most significant first, with one store: lane i writes bit
+// len - 1 - i at pos + i.  Entries at or beyond the capacity are not written; pos keeps counting, so stream_len > stream_cap still
+// reports the overflow.  (W = unsigned: 32-bit shifts - the 64-bit form is scalar work twice over.)
+template <typename W>
+__device__ __forceinline__ void emit_bits(Sym &y, W bits, int len) {
+  if (y.lane < len && y.pos + y.lane < y.cap) y.out[y.pos + y.lane] = ENT_LITERAL((int)((bits >> ((len - 1 - y.lane) & (8 * (int)sizeof(W) - 1))) & 1));
   y.pos += len;
 }
 
+// One symbol against one CDF row, cooperatively: the lane holds entry `lane` of an n-symbol row (v; the lanes past entry n whatever
+// they read).  fl / fh of symbol s, and the lane's entry after the adaptation at rate rate0 + (counter > 15) + (counter > 31) - the
+// entry as it was when the CDFs are static.
+struct CdfStep { uint32_t fl, fh; int nv; };
+__device__ __forceinline__ CdfStep cdf_step(const Sym &y, int v, int s, int n, int rate0) {
+  CdfStep st;
+  st.fl = s > 0 ? (uint32_t)__builtin_amdgcn_readlane(v, s - 1) : 32768u;
+  st.fh = (uint32_t)__builtin_amdgcn_readlane(v, s);
+  st.nv = v;
+  if (y.adapt) {
+    const int cntr = __builtin_amdgcn_readlane(v, n);
+    const int rate = rate0 + (cntr > 15) + (cntr > 31);
+    const int nv = y.lane < s ? v + ((32768 - v) >> rate) : v - (v >> rate);
+    st.nv = y.lane == n ? cntr + (cntr < 32) : nv;
+  }
+  return st;
+}
 // Wide-alphabet / rare symbol: adapt the n-symbol row at LDS offset `off` cooperatively (lane j =
 // entry j) and emit the RESOLVED entry.
 template <int ARR = 0>  // 0: y.cdf (key-frame syntax), 1: g_cdf_inter (offsets relative to CL::INTER_BASE)
-__device__ __forceinline__ void sym_wide(Sym &y, int lane, int adapt, int s, int off, int n) {
-  s = uni(s); off = uni(off) - (ARR ? CL::INTER_BASE : 0); n = uni(n);
-  const int v = ARR ? g_cdf_inter[off + (lane < 17 ? lane : 16)] : y.cdf[off + (lane < 17 ? lane : 16)];
-  const uint32_t fl = s > 0 ? (uint32_t)__builtin_amdgcn_readlane(v, s - 1) : 32768u;
-  const uint32_t fh = (uint32_t)__builtin_amdgcn_readlane(v, s);
-  if (adapt) {
-    const int cntr = __builtin_amdgcn_readlane(v, n);
-    const int rate = 3 + (cntr > 15) + (cntr > 31) + (n > 3 ? 2 : 1);
-    int nv = lane < s ? v + ((32768 - v) >> rate) : v - (v >> rate);
-    nv = lane == n ? cntr + (cntr < 32) : nv;
-    if (lane <= n) { if (ARR) g_cdf_inter[off + lane] = (uint16_t)nv; else y.cdf[off + lane] = (uint16_t)nv; }
-  }
-  emit1(y, lane, ENT_RESOLVED(fl >> 6, fh >> 6, n - 1 - s));
+__device__ __forceinline__ void sym_wide(Sym &y, int s, int off, int n) {
+  s = uni(s); off = uni(off); n = uni(n);
+  uint16_t *row;
+  if constexpr (ARR) row = g_cdf_inter + (off - CL::INTER_BASE); else row = y.cdf + off;
+  const CdfStep st = cdf_step(y, row[y.lane < 17 ? y.lane : 16], s, n, 3 + (n > 3 ? 2 : 1));
+  if (y.adapt && y.lane <= n) row[y.lane] = (uint16_t)st.nv;
+  emit1(y, ENT_RESOLVED(st.fl >> 6, st.fh >> 6, n - 1 - s));
 }
-// same for a 4-symbol coefficient row kept in the narrow LDS array (FULL variant only)
-__device__ __forceinline__ void sym_narrow_resolved(Sym &y, int lane, int adapt, int s, int off) {
-  s = uni(s); off = uni(off) - CL::COEFF_BASE;
-  const int v = g_cdf_narrow[off + (lane < 5 ? lane : 4)];
-  const uint32_t fl = s > 0 ? (uint32_t)__builtin_amdgcn_readlane(v, s - 1) : 32768u;
-  const uint32_t fh = (uint32_t)__builtin_amdgcn_readlane(v, s);
-  if (adapt) {
-    const int cntr = __builtin_amdgcn_readlane(v, 4);
-    const int rate = 5 + (cntr > 15) + (cntr > 31);
-    int nv = lane < s ? v + ((32768 - v) >> rate) : v - (v >> rate);
-    nv = lane == 4 ? cntr + (cntr < 32) : nv;
-    if (lane <= 4) g_cdf_narrow[off + lane] = (uint16_t)nv;
-  }
-  emit1(y, lane, ENT_RESOLVED(fl >> 6, fh >> 6, 3 - s));
-}
-__device__ __forceinline__ void sym_bool(Sym &y, int lane, int val, uint32_t f) {
+__device__ __forceinline__ void sym_bool(Sym &y, int val, uint32_t f) {
   // P(val == 1) = f / 32768, no adaptation
-  emit1(y, lane, val ? ENT_RESOLVED(f >> 6, 0, 0) : ENT_RESOLVED(512, f >> 6, 1));
+  emit1(y, val ? ENT_RESOLVED(f >> 6, 0, 0) : ENT_RESOLVED(512, f >> 6, 1));
 }
+__device__ __forceinline__ int icdf_prob(const Sym &y, int off, int el) { return (el > 0 ? y.cdf[off + el - 1] : 32768) - y.cdf[off + el]; }
 
-__device__ __forceinline__ int scan_index(int row, int col, int n) {
-  int d = row + col;
-  int before = d < n ? (d * (d + 1)) >> 1 : n * n - (((2 * n - 1 - d) * (2 * n - d)) >> 1);
-  int lo = d - (n - 1) > 0 ? d - (n - 1) : 0;
-  return before + ((d & 1) ? row - lo : col - lo);
-}
-// position (row << log2n | col) of scan index c in the default zig-zag of an n x n block: the inverse of scan_index, from a table
-// in device memory built at compile time (2.7 KB for 4x4 .. 32x32; L1 / L2 resident).  In LDS the table cost a quarter of the
-// kernel's occupancy, computed (anti-diagonal by a float square root + integer fix-up) it was 30 instructions per lane and pass
+// position (row << log2n | col) of scan index c in the default zig-zag of an n x n block: the inverse of quant_pieces.h's scan_index,
+// from a table in device memory built at compile time (2.7 KB for 4x4 .. 32x32; L1 / L2 resident).  In LDS the table cost a quarter of
+// the kernel's occupancy, computed (anti-diagonal by a float square root + integer fix-up) it was 30 instructions per lane and pass
 // of a kernel that is bound by instruction issue.
 struct ScanTab { uint16_t v[16 + 64 + 256 + 1024]; };
 constexpr ScanTab make_scan_tab() {
@@ -163,12 +176,7 @@ constexpr ScanTab make_scan_tab() {
   for (int l = 2; l <= 5; l++) {
     const int n = 1 << l;
     for (int row = 0; row < n; row++)
-      for (int col = 0; col < n; col++) {
-        const int d = row + col;
-        const int before = d < n ? (d * (d + 1)) >> 1 : n * n - (((2 * n - 1 - d) * (2 * n - d)) >> 1);
-        const int lo = d - (n - 1) > 0 ? d - (n - 1) : 0;
-        t.v[off + before + ((d & 1) ? row - lo : col - lo)] = (uint16_t)((row << l) | col);
-      }
+      for (int col = 0; col < n; col++) t.v[off + av1mi_quant::scan_index(row, col, n)] = (uint16_t)((row << l) | col);
     off += n * n;
   }
   return t;
@@ -188,15 +196,33 @@ __device__ __forceinline__ int mode_txfm(int mode) { return (int)((0x39da724u >>
 __device__ __forceinline__ int txsym_set1(int tt) { return (0x4651 >> (4 * tt)) & 15; }   // { 1, 5, 6, 4 }
 __device__ __forceinline__ int txsym_set2(int tt) { return (0x2431 >> (4 * tt)) & 15; }   // { 1, 3, 4, 2 }
 
-struct TileGeo {
+// The tile under the wave as its current superblock addresses it: where the superblock lies, the frame's limits inside it, the tile's
+// block info and the above / left coefficient contexts.
+struct CoefCtx { uint8_t *lvl, *dc; };   // per 4x4 column (above) or row (left) of a plane: cumulative level, DC sign category
+template <int TSB>
+struct TileCtx {
+  static constexpr int TW = 8 * TSB;   // tile width in 8x8 units
   int tox, toy;     // origin of the current superblock inside the tile, luma pixels (0 or 64)
   int sb_x, sb_y;   // luma pixel origin
   int max_x4_y, max_y4_y, max_x4_c, max_y4_c;  // frame limits in 4x4 units, superblock-local
   int big;          // the chunk has 64x64 leaves (block_log2 = 6): 64-point luma transforms can occur
+  // block info of tile-local unit u / of the unit at tile-local 4x4 position (r4, c4) / of the superblock's unit (ux, uy)
+  static __device__ __forceinline__ Av1miBlkInfo &unit(int u) { return tile_lds<TSB>().info[u]; }
+  static __device__ __forceinline__ int unit_at4(int r4, int c4) { return (r4 >> 1) * TW + (c4 >> 1); }
+  __device__ __forceinline__ int unit_of(int ux, int uy) const { return (uy + (toy >> 3)) * TW + ux + (tox >> 3); }
+  __device__ __forceinline__ Av1miBlkInfo &info(int ux, int uy) const { return unit(unit_of(ux, uy)); }
+  // coefficient contexts of a plane, indexed by the superblock's 4x4 column / row (above contexts are kept per tile-local column)
+  __device__ __forceinline__ CoefCtx above(int plane) const {
+    const int o = plane ? tox >> 3 : tox >> 2;
+    return { tile_lds<TSB>().above_lvl[plane] + o, tile_lds<TSB>().above_dc[plane] + o };
+  }
+  static __device__ __forceinline__ CoefCtx left(int plane) { return { g_sym.left_lvl[plane], g_sym.left_dc[plane] }; }
+  __device__ __forceinline__ int max_x4(int plane) const { return plane ? max_x4_c : max_x4_y; }
+  __device__ __forceinline__ int max_y4(int plane) const { return plane ? max_y4_c : max_y4_y; }
 };
 
 // exclusive prefix sum over the wave with DPP row shifts and broadcasts (seven additions; the shuffle form went through LDS six times)
-__device__ __forceinline__ int wave_excl_scan(int v, int lane, int *total) {
+__device__ __forceinline__ int wave_excl_scan(int v, int *total) {
   int x = v;
   x += __builtin_amdgcn_update_dpp(0, x, 0x111, 0xF, 0xF, false);   // row_shr:1
   x += __builtin_amdgcn_update_dpp(0, x, 0x112, 0xF, 0xF, false);   // row_shr:2
@@ -205,29 +231,258 @@ __device__ __forceinline__ int wave_excl_scan(int v, int lane, int *total) {
   x += __builtin_amdgcn_update_dpp(0, x, 0x142, 0xA, 0xF, false);   // row_bcast:15 into rows 1 and 3
   x += __builtin_amdgcn_update_dpp(0, x, 0x143, 0xC, 0xF, false);   // row_bcast:31 into rows 2 and 3
   *total = __builtin_amdgcn_readlane(x, 63);
-  (void)lane;
   return x - v;
 }
+// OR of `o` and sum of `s` over the first row of 16 lanes, in each of them: an all-reduce by DPP rotations (row_ror 8, 4, 2, 1)
+template <int ROR>
+__device__ __forceinline__ void row16_or_sum_step(int &o, int &s) {
+  o |= __builtin_amdgcn_update_dpp(0, o, 0x120 + ROR, 0xF, 0xF, false);
+  s += __builtin_amdgcn_update_dpp(0, s, 0x120 + ROR, 0xF, 0xF, false);
+}
+__device__ __forceinline__ void row16_or_sum(int &o, int &s) {
+  row16_or_sum_step<8>(o, s); row16_or_sum_step<4>(o, s); row16_or_sum_step<2>(o, s); row16_or_sum_step<1>(o, s);
+}
 
-// coefficients of one transform block (spec §5.11.39); x4/y4 in plane 4x4 units local to the SB.
+// ---- coefficients of one transform block (spec §5.11.39) in four stages: header, levels, signs, contexts ---------------------------
+
+// Stage 1, the header: all_zero, then for a coded block the transform type (§5.11.47), the eob class and its extra bits.
+// txs = log2n - 2 is the size class (TX_64X64 = 4), bwl the coded area's log2 width.
+template <bool FULL>
+__device__ __forceinline__ void txb_header(Sym &y, int plane, int log2n, int bwl, int eob, int zctx, int ymode, int idtx, int is_inter) {
+  typedef Rows<FULL> R;
+  const int ptype = plane > 0, txs = log2n - 2;
+  sym_wide(y, eob == 0, R::txb_skip(txs, ptype, zctx), 2);
+  if (eob == 0) return;
+  if (plane == 0 && is_inter) {
+    // inter_tx_type: every inter block is DCT_DCT = symbol 7 / 3 / 1 of TX_SET_INTER_1 / _2 / _3 (§5.11.47)
+    if (log2n <= 3) sym_wide<1>(y, 7, CL::INTER_TX1 + (log2n - 2) * 17, 16);
+    else if (log2n == 4) sym_wide<1>(y, 3, CL::INTER_TX2, 12);
+    else if (log2n == 5) sym_wide<1>(y, 1, CL::INTER_TX3 + 3 * 3, 2);
+    // (TX_64X64: the transform set is DCT only, nothing is coded)
+  } else if (plane == 0 && log2n <= 4) {
+    // intra_tx_type: the mode's default type, or IDTX (symbol 0 of both intra sets) when the reconstruction chose it
+    const int tt = mode_txfm(ymode);
+    if (log2n <= 3) sym_wide(y, idtx ? 0 : txsym_set1(tt), R::tx_set(log2n, ymode), 7);
+    else sym_wide(y, idtx ? 0 : txsym_set2(tt), R::tx_set(log2n, ymode), 5);
+  }
+  const int eob_pt = eob <= 2 ? eob : floor_log2((unsigned)(eob - 1)) + 2;
+  const int base = eob_pt < 2 ? eob_pt : ((1 << (eob_pt - 2)) + 1);
+  const int extra = eob - base;
+  const int msz = 2 * bwl - 4;
+  sym_wide(y, eob_pt - 1, R::eob(msz, ptype), 5 + msz);
+  if (eob_pt >= 3) {
+    const int nbits = eob_pt - 2;
+    sym_wide(y, (extra >> (nbits - 1)) & 1, R::eob_extra(txs, ptype, eob_pt - 3), 2);
+    emit_bits(y, (unsigned)extra, nbits - 1);   // the bits behind the first are literals
+  }
+}
+
+// Stage 2, the levels.  What the lane's coefficient (scan index c at position pos, none if c < 0) codes: its magnitude, the rows of
+// its coeff_base and coeff_br contexts inside the (tx size, plane type) combination, and its number of symbols.
+struct CoefSyms { int level, cb, cbr, cnt; };
+__device__ __forceinline__ int lv_abs_clipped(int r, int c, int bwl) {
+  return (r < (1 << bwl) && c < (1 << bwl)) ? iabs((int)g_sym.lv[(r << bwl) + c]) : 0;
+}
+__device__ __forceinline__ CoefSyms coeff_syms(int c, int pos, int eob, int bwl) {
+  CoefSyms k = { 0, 0, 0, 0 };
+  if (c < 0) return k;
+  const int row = pos >> bwl, col = pos & ((1 << bwl) - 1);
+  const int a01 = lv_abs_clipped(row, col + 1, bwl), a10 = lv_abs_clipped(row + 1, col, bwl), a11 = lv_abs_clipped(row + 1, col + 1, bwl);
+  const int a02 = lv_abs_clipped(row, col + 2, bwl), a20 = lv_abs_clipped(row + 2, col, bwl);
+  const int mag = imin(a01, 3) + imin(a10, 3) + imin(a11, 3) + imin(a02, 3) + imin(a20, 3);
+  // Coeff_Base_Ctx_Offset of a square block depends on row + col only: 0, 1, 6, 6, 21, 21 ... (a table load per lane otherwise)
+  const int rc = row + col;
+  k.cb = pos == 0 ? 0 : imin((mag + 1) >> 1, 4) + (rc < 2 ? rc : (rc < 4 ? 6 : 21));
+  int mb = imin(a01, 15) + imin(a10, 15) + imin(a11, 15);
+  mb = imin((mb + 1) >> 1, 6);
+  k.cbr = pos == 0 ? mb : ((row < 2 && col < 2) ? mb + 7 : mb + 14);
+  k.level = iabs((int)g_sym.lv[pos]);
+  // symbols of this coefficient: base (except the last coefficient) + 0..4 range symbols
+  const int nbr = k.level > 2 ? imin((k.level - 3) / 3 + 1, 4) : 0;
+  k.cnt = (c != eob - 1) + nbr;
+  return k;
+}
+// 64 coefficients whose rows adapt per lane in K4: NARROW entries (slot, symbol), every lane its own at the prefix sum of the counts
+__device__ __forceinline__ void levels_to_slots(Sym &y, const CoefSyms &k, int c, int eob, int slot0) {
+  int total;
+  const int off = wave_excl_scan(k.cnt, &total);
+  if (c >= 0 && y.pos + off + k.cnt <= y.cap) {
+    uint32_t *o = y.out + y.pos + off;
+    if (c != eob - 1) *o++ = ENT_NARROW(slot0 + k.cb, imin(k.level, 3));
+    // the range symbols: nbr = cnt less the base symbol of them, known since the prefix sum - predicated stores, no loop (as a
+    // loop with a break it ran divergent, as often as the wave's largest level asked)
+    const int nbr = k.cnt - (c != eob - 1);
+    const uint32_t br = ENT_NARROW(slot0 + 42 + k.cbr, 0);
+    if (nbr > 0) {
+      o[0] = br | (uint32_t)imin(k.level - 3, 3);
+      if (nbr > 1) {
+        o[1] = br | (uint32_t)imin(k.level - 6, 3);
+        if (nbr > 2) {
+          o[2] = br | (uint32_t)imin(k.level - 9, 3);
+          if (nbr > 3) o[3] = br | (uint32_t)imin(k.level - 12, 3);
+        }
+      }
+    }
+  }
+  y.pos += total;
+}
+// Resolved path (static CDFs, or a third size class in an edge tile): the symbols adapt here, one after the other - a few
+// waves with a long serial chain, which last as long as the regular variant's thousands beside them.  So the chain is kept short:
+// the batch's (row, symbol) pairs go to an LDS list in coding order, lane-parallel like the slot path above; the serial loop
+// then takes 64 of them into a register, reads the NEXT pair's CDF row before it writes the current one back (forwarded when both
+// name the same row), builds the entries in a register and stores the 64 with one instruction.
+// g_cdf_narrow offset of the combination's row r: r < 42 ? row0 + 5 r : row1 + 5 r
+__device__ __forceinline__ void levels_resolved(Sym &y, const CoefSyms &k, int c, int eob, int row0, int row1) {
+  int total;
+  const int off = wave_excl_scan(k.cnt, &total);
+  if (c >= 0) {
+    uint16_t *o = g_full_list + off;
+    if (c != eob - 1) *o++ = (uint16_t)((k.cb << 2) | imin(k.level, 3));
+    if (k.level > 2) {
+      for (int idx = 0; idx < 4; idx++) {
+        const int k3 = imin(k.level - 3 - idx * 3, 3);
+        *o++ = (uint16_t)(((42 + k.cbr) << 2) | k3);
+        if (k3 < 3) break;
+      }
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+  const int l5 = y.lane < 5 ? y.lane : 4;
+  for (int k0 = 0; k0 < total; k0 += 64) {
+    const int n_k = imin(64, total - k0);
+    const int ents = k0 + y.lane < total ? (int)g_full_list[k0 + y.lane] : 0;
+    int e = __builtin_amdgcn_readlane(ents, 0);
+    int roff = ((e >> 2) < 42 ? row0 : row1) + (e >> 2) * 5;
+    int v = g_cdf_narrow[roff + l5];
+    uint32_t outv = 0;
+    for (int i = 0; i < n_k; i++) {
+      const int sy = e & 3;
+      // the next pair and its row (i + 1 == n_k: lane 63's or a stale pair - a valid row either way, and unused)
+      const int e_nx = __builtin_amdgcn_readlane(ents, (i + 1) & 63);
+      const int roff_nx = ((e_nx >> 2) < 42 ? row0 : row1) + (e_nx >> 2) * 5;
+      const int v_nx = g_cdf_narrow[roff_nx + l5];
+      const CdfStep st = cdf_step(y, v, sy, 4, 5);
+      if (y.adapt && y.lane <= 4) g_cdf_narrow[roff + y.lane] = (uint16_t)st.nv;
+      outv = y.lane == i ? ENT_RESOLVED(st.fl >> 6, st.fh >> 6, 3 - sy) : outv;
+      v = roff_nx == roff ? st.nv : v_nx;
+      roff = roff_nx; e = e_nx;
+    }
+    if (y.lane < n_k && y.pos + y.lane < y.cap) y.out[y.pos + y.lane] = outv;
+    y.pos += n_k;
+  }
+}
+// coeff_base_eob of the last coefficient, then all coefficients in reverse scan order (the levels are in g_sym.lv)
 template <bool FULL, int TSB>
-__device__ __forceinline__ void sym_coeffs(Sym &y, const int lane, const int adapt, const TileGeo &tg, int plane, int log2n, int x4,
-                                           int y4, int eob, int ymode, int is_inter, const int16_t *lv_global) {
-  const int idtx = ymode >> 8;   // bit 8 of the mode argument: the luma block uses the identity transform
-  ymode &= 255;
-  const int ptype = plane > 0;
-  const int txs = log2n - 2;
+__device__ __forceinline__ void level_pass(Sym &y, int big, int ptype, int txs, int bwl, int eob) {
+  const int n = 1 << bwl;
+  // slot range of this (tx size, plane type): the first MAX_COMBOS combinations met in a tile
+  // adapt per lane in K4; any further combination is resolved here (cooperatively, slowly).
+  const int combo = txs * 2 + ptype;
+  int slot0 = -1;
+  // (A tile of several superblocks can hold 64-point AND 32-point luma transforms - a 64x64 leaf beside a split or edge superblock.
+  // Their base CDFs differ but they SHARE the range CDFs (size class min(txs, 3)): in two slots, or a slot and the resolved path, the
+  // shared rows would adapt in two copies.  Both go the resolved path there, whose one copy is the decoder's; a chunk without
+  // 64x64 leaves has no 64-point transform and keeps its slots.)
+  const bool shared_br = FULL && TSB > 1 && big && ptype == 0 && txs >= 3;
+  if (y.adapt && !shared_br) {
+    if (y.combo0 == combo) slot0 = 0;
+    else if (y.combo0 < 0) { y.combo0 = combo; slot0 = 0; }
+    else if (y.combo1 == combo) slot0 = SLOTS_PER_COMBO;
+    else if (y.combo1 < 0) { y.combo1 = combo; slot0 = SLOTS_PER_COMBO; }
+  }
+  const int row0 = combo * 42 * 5, row1 = CL::COEFF_BR - CL::COEFF_BASE + ((txs > 3 ? 3 : txs) * 2 + ptype) * 21 * 5 - 42 * 5;
+  // Scan positions come from a table in device memory: the load for the NEXT 64 coefficients is issued before the current ones are
+  // worked on, with a clamped index instead of a condition (a load under `if (c >= 0)` is waited for on the spot, and on this serial
+  // chain that was a cache round trip per 64 coefficients and pass).
+  int pos_nx = scan_pos(imax(eob - 1 - y.lane, 0), bwl);
+  // ---- last coefficient: coeff_base_eob (3 symbols, resolved here)
+  {
+    const int cc = eob - 1;
+    const int lvl_last = uni(iabs((int)g_sym.lv[__builtin_amdgcn_readfirstlane(pos_nx)]));   // (lane 0 holds scan index eob - 1)
+    const int cctx = cc == 0 ? 0 : (cc <= (n * n) / 8 ? 1 : (cc <= (n * n) / 4 ? 2 : 3));
+    sym_wide(y, imin(lvl_last, 3) - 1, Rows<FULL>::coeff_base_eob(txs, ptype, cctx), 3);
+  }
+  // ---- all coefficients in reverse scan order, 64 at a time: lane i owns scan index c_hi - i
+  for (int c_hi = eob - 1; c_hi >= 0; c_hi -= 64) {
+    const int c = c_hi - y.lane;
+    const int pos = pos_nx;
+    pos_nx = scan_pos(imax(c - 64, 0), bwl);
+    const CoefSyms k = coeff_syms(c, pos, eob, bwl);
+    if (slot0 >= 0) levels_to_slots(y, k, c, eob, slot0);
+    else if constexpr (FULL) levels_resolved(y, k, c, eob, row0, row1);
+  }
+}
+
+// Stage 3, signs / golomb in forward scan order (all literals except the DC sign).  Returns the block's cumulative level (capped at
+// 63) and leaves the DC sign category in dc_cat.
+template <bool FULL>
+__device__ __forceinline__ int sign_pass(Sym &y, int ptype, int bwl, int eob, int dsum, int &dc_cat) {
+  int cul = 0;
+  int fpos_nx = scan_pos(imin(y.lane, eob - 1), bwl);
+  for (int c0 = 0; c0 < eob; c0 += 64) {
+    const int c = c0 + y.lane;
+    int v = 0;
+    const int fpos = fpos_nx;
+    fpos_nx = scan_pos(imin(c + 64, eob - 1), bwl);
+    if (c < eob) v = g_sym.lv[fpos];
+    const int level = iabs(v);
+    { int lsum; (void)wave_excl_scan(level, &lsum); cul += lsum; }   // (the DPP prefix sum's total)
+    if (c0 == 0) {
+      const int v0 = __builtin_amdgcn_readlane(v, 0);
+      if (v0 != 0) {
+        const int dctx = dsum < 0 ? 1 : (dsum > 0 ? 2 : 0);
+        sym_wide(y, v0 < 0, Rows<FULL>::dc_sign(ptype, dctx), 2);
+        dc_cat = v0 < 0 ? 1 : 2;
+        const int l0 = iabs(v0);
+        if (l0 > 14) {  // its golomb tail (rare) right behind it
+          const unsigned g = (unsigned)(l0 - 15) + 1;
+          const int len = floor_log2(g) + 1;
+          emit_bits(y, g, 2 * len - 1);   // len - 1 zeros, then g's len bits
+        }
+      }
+    }
+    const bool mine = level != 0 && c != 0;
+    const unsigned g = level > 14 ? (unsigned)(level - 15) + 1 : 0;
+    const int glen = g ? floor_log2(g) + 1 : 0;
+    const int cnt = mine ? 1 + (g ? 2 * glen - 1 : 0) : 0;
+    int total;
+    const int off = wave_excl_scan(cnt, &total);
+    if (mine && y.pos + off + cnt <= y.cap) {
+      uint32_t *o = y.out + y.pos + off;
+      *o++ = ENT_LITERAL(v < 0);
+      if (g) {
+        for (int i = 0; i < glen - 1; i++) *o++ = ENT_LITERAL(0);
+        for (int i = glen - 1; i >= 0; i--) *o++ = ENT_LITERAL((g >> i) & 1);
+      }
+    }
+    y.pos += total;
+  }
+  return imin(cul, 63);
+}
+
+// Stage 4, and the contexts of a skipped block: the above and left contexts of a block of w4 4x4 units at (x4, y4) of the plane
+// (superblock-local), clipped to the frame - every read checks the same limits.  The caller keeps the wave's earlier reads and later
+// reads apart from these writes (__syncthreads).
+template <int TSB>
+__device__ __forceinline__ void write_coef_ctx(const TileCtx<TSB> &t, int lane, int plane, int x4, int y4, int w4, int cul, int dc_cat) {
+  const CoefCtx above = t.above(plane), left = t.left(plane);
+  if (lane < w4) {
+    if (x4 + lane < t.max_x4(plane)) { above.lvl[x4 + lane] = (uint8_t)cul; above.dc[x4 + lane] = (uint8_t)dc_cat; }
+    if (y4 + lane < t.max_y4(plane)) { left.lvl[y4 + lane] = (uint8_t)cul; left.dc[y4 + lane] = (uint8_t)dc_cat; }
+  }
+}
+
+// the transform block; x4/y4 in plane 4x4 units local to the SB; idtx: the luma block uses the identity transform
+template <bool FULL, int TSB>
+__device__ __forceinline__ void sym_coeffs(Sym &y, const TileCtx<TSB> &t, int plane, int log2n, int x4, int y4, int eob, int ymode, int idtx,
+                                           int is_inter, const int16_t *lv_global) {
   const int w4 = (1 << log2n) >> 2;
   // a 64-point transform codes only its 32x32 low-frequency corner: contexts of the size class TX_64X64 (txs 4), scan, eob and
   // neighbourhoods of a 32x32 area
   const int bwl = log2n > 5 ? 5 : log2n;
   const int n = 1 << bwl;
-  const int max_x4 = plane ? tg.max_x4_c : tg.max_x4_y, max_y4 = plane ? tg.max_y4_c : tg.max_y4_y;
-  const int aoff = (plane ? tg.tox >> 3 : tg.tox >> 2);  // above contexts are indexed by tile-local 4x4 column
-#define a_lvl (TI.above_lvl[plane] + aoff)
-#define a_dc (TI.above_dc[plane] + aoff)
-#define l_lvl S->left_lvl[plane]
-#define l_dc S->left_dc[plane]
   // the block's levels, 16 bytes (8 levels) per lane and step: requested here, needed only after the block's first symbols (by then
   // they have arrived - issued where they are copied to LDS the wave waited a memory round trip per transform block); unconditional,
   // index clamped (a load under a condition is waited for on the spot)
@@ -235,243 +490,36 @@ __device__ __forceinline__ void sym_coeffs(Sym &y, const int lane, const int ada
   {
     const u4 *g128 = reinterpret_cast<const u4 *>(lv_global);
     const int last = n * n / 8 - 1;
-    lv_pre[0] = g128[imin(lane, last)];
-    lv_pre[1] = g128[imin(lane + 64, last)];
+    lv_pre[0] = g128[imin(y.lane, last)];
+    lv_pre[1] = g128[imin(y.lane + 64, last)];
   }
+  // the neighbours' contexts: any level or DC above (bit 0) / left (bit 1), and the sum of the DC signs
   int nb_or = 0, dsum = 0;
-  if (lane < w4) {
-    if (x4 + lane < max_x4) { nb_or |= (a_lvl[x4 + lane] | a_dc[x4 + lane]) ? 1 : 0; int sg = a_dc[x4 + lane]; dsum += sg == 1 ? -1 : (sg == 2 ? 1 : 0); }
-    if (y4 + lane < max_y4) { nb_or |= (l_lvl[y4 + lane] | l_dc[y4 + lane]) ? 2 : 0; int sg = l_dc[y4 + lane]; dsum += sg == 1 ? -1 : (sg == 2 ? 1 : 0); }
+  {
+    const CoefCtx above = t.above(plane), left = t.left(plane);
+    if (y.lane < w4) {
+      if (x4 + y.lane < t.max_x4(plane)) { nb_or |= (above.lvl[x4 + y.lane] | above.dc[x4 + y.lane]) ? 1 : 0; int sg = above.dc[x4 + y.lane]; dsum += sg == 1 ? -1 : (sg == 2 ? 1 : 0); }
+      if (y4 + y.lane < t.max_y4(plane)) { nb_or |= (left.lvl[y4 + y.lane] | left.dc[y4 + y.lane]) ? 2 : 0; int sg = left.dc[y4 + y.lane]; dsum += sg == 1 ? -1 : (sg == 2 ? 1 : 0); }
+    }
+    row16_or_sum(nb_or, dsum);   // (w4 <= 16 lanes hold values)
+    nb_or = uni(nb_or); dsum = uni(dsum);
   }
-  // w4 <= 16 lanes hold values: an all-reduce inside the first row of 16 lanes by DPP rotations (row_ror 8, 4, 2, 1)
-  nb_or |= __builtin_amdgcn_update_dpp(0, nb_or, 0x128, 0xF, 0xF, false); dsum += __builtin_amdgcn_update_dpp(0, dsum, 0x128, 0xF, 0xF, false);
-  nb_or |= __builtin_amdgcn_update_dpp(0, nb_or, 0x124, 0xF, 0xF, false); dsum += __builtin_amdgcn_update_dpp(0, dsum, 0x124, 0xF, 0xF, false);
-  nb_or |= __builtin_amdgcn_update_dpp(0, nb_or, 0x122, 0xF, 0xF, false); dsum += __builtin_amdgcn_update_dpp(0, dsum, 0x122, 0xF, 0xF, false);
-  nb_or |= __builtin_amdgcn_update_dpp(0, nb_or, 0x121, 0xF, 0xF, false); dsum += __builtin_amdgcn_update_dpp(0, dsum, 0x121, 0xF, 0xF, false);
-  nb_or = uni(nb_or); dsum = uni(dsum);
   // luma: TX_MODE_LARGEST with square blocks => transform == block => ctx 0
   const int zctx = plane == 0 ? 0 : 7 + (nb_or & 1) + (nb_or >> 1);
-  sym_wide(y, lane, adapt, eob == 0, FULL ? CL::TXB_SKIP + (txs * 13 + zctx) * 3 : CC::TXB_SKIP + (ptype * 13 + zctx) * 3, 2);
+  txb_header<FULL>(y, plane, log2n, bwl, eob, zctx, ymode, idtx, is_inter);
   int cul = 0, dc_cat = 0;
   if (eob != 0) {
-    {
-      // ... into the LDS copy (same row-major layout)
-      u4 *l128 = reinterpret_cast<u4 *>(S->lv);
-      if (lane < n * n / 8) l128[lane] = lv_pre[0];
-      if (lane + 64 < n * n / 8) l128[lane + 64] = lv_pre[1];
-      __syncthreads();
-    }
-    if (plane == 0 && is_inter) {
-      // inter_tx_type: every inter block is DCT_DCT = symbol 7 / 3 / 1 of TX_SET_INTER_1 / _2 / _3 (§5.11.47)
-      if (log2n <= 3) sym_wide<1>(y, lane, adapt, 7, CL::INTER_TX1 + (log2n - 2) * 17, 16);
-      else if (log2n == 4) sym_wide<1>(y, lane, adapt, 3, CL::INTER_TX2, 12);
-      else if (log2n == 5) sym_wide<1>(y, lane, adapt, 1, CL::INTER_TX3 + 3 * 3, 2);
-      // (TX_64X64: the transform set is DCT only, nothing is coded)
-    } else if (plane == 0 && log2n <= 4) {
-      // intra_tx_type: the mode's default type, or IDTX (symbol 0 of both intra sets) when the reconstruction chose it
-      const int tt = mode_txfm(ymode);
-      if (log2n <= 3) sym_wide(y, lane, adapt, idtx ? 0 : txsym_set1(tt), FULL ? CL::TX_SET1 + ((log2n - 2) * 13 + ymode) * 8 : CC::TXSET + ymode * 8, 7);
-      else sym_wide(y, lane, adapt, idtx ? 0 : txsym_set2(tt), FULL ? CL::TX_SET2 + ((log2n - 2) * 13 + ymode) * 6 : CC::TXSET + ymode * 6, 5);
-    }
-    {
-      const int eob_pt = eob <= 2 ? eob : floor_log2((unsigned)(eob - 1)) + 2;
-      const int base = eob_pt < 2 ? eob_pt : ((1 << (eob_pt - 2)) + 1);
-      const int extra = eob - base;
-      const int msz = 2 * bwl - 4;
-      const int nsy = 5 + msz;
-      const int eoff = CL::EOB16 + 4 * (msz * 6 + (msz * (msz - 1)) / 2);
-      sym_wide(y, lane, adapt, eob_pt - 1, FULL ? eoff + (ptype * 2 + 0) * (nsy + 1) : CC::EOB + ptype * 12, nsy);
-      if (eob_pt >= 3) {
-        const int nbits = eob_pt - 2;
-        sym_wide(y, lane, adapt, (extra >> (nbits - 1)) & 1, FULL ? CL::EOB_EXTRA + ((txs * 2 + ptype) * 9 + (eob_pt - 3)) * 3 : CC::EOB_EXTRA + (ptype * 9 + (eob_pt - 3)) * 3, 2);
-        emit_bits(y, lane, (unsigned)extra, nbits - 1);   // the bits behind the first are literals
-      }
-    }
-#define scan(i_) scan_pos((i_), bwl)
-    // slot range of this (tx size, plane type): the first MAX_COMBOS combinations met in a tile
-    // adapt per lane in K4; any further combination is resolved here (cooperatively, slowly).
-    const int combo = txs * 2 + ptype;
-    int slot0 = -1;
-    // (A tile of several superblocks can hold 64-point AND 32-point luma transforms - a 64x64 leaf beside a split or edge superblock.
-    // Their base CDFs differ but they SHARE the range CDFs (size class min(txs, 3)): in two slots, or a slot and the resolved path, the
-    // shared rows would adapt in two copies.  Both go the resolved path there, whose one copy is the decoder's; a chunk without
-    // 64x64 leaves has no 64-point transform and keeps its slots.)
-    const bool shared_br = FULL && TSB > 1 && tg.big && ptype == 0 && txs >= 3;
-    if (adapt && !shared_br) {
-      if (y.combo0 == combo) slot0 = 0;
-      else if (y.combo0 < 0) { y.combo0 = combo; slot0 = 0; }
-      else if (y.combo1 == combo) slot0 = SLOTS_PER_COMBO;
-      else if (y.combo1 < 0) { y.combo1 = combo; slot0 = SLOTS_PER_COMBO; }
-    }
-    const int base_off0 = CL::COEFF_BASE + (txs * 2 + ptype) * 42 * 5;
-    const int br_off0 = CL::COEFF_BR + ((txs > 3 ? 3 : txs) * 2 + ptype) * 21 * 5;
-    // Scan positions come from a table in device memory: the load for the NEXT 64 coefficients is issued before the current ones are
-    // worked on, with a clamped index instead of a condition (a load under `if (c >= 0)` is waited for on the spot, and on this serial
-    // chain that was a cache round trip per 64 coefficients and pass).
-    int pos_nx = scan(imax(eob - 1 - lane, 0));
-    // ---- last coefficient: coeff_base_eob (3 symbols, resolved here)
-    {
-      const int cc = eob - 1;
-      const int lvl_last = uni(iabs((int)S->lv[__builtin_amdgcn_readfirstlane(pos_nx)]));   // (lane 0 holds scan index eob - 1)
-      const int cctx = cc == 0 ? 0 : (cc <= (n * n) / 8 ? 1 : (cc <= (n * n) / 4 ? 2 : 3));
-      sym_wide(y, lane, adapt, imin(lvl_last, 3) - 1, FULL ? CL::COEFF_BASE_EOB + ((txs * 2 + ptype) * 4 + cctx) * 4 : CC::COEFF_BASE_EOB + (ptype * 4 + cctx) * 4, 3);
-    }
-    // ---- all coefficients in reverse scan order, 64 at a time: lane i owns scan index c_hi - i
-    for (int c_hi = eob - 1; c_hi >= 0; c_hi -= 64) {
-      const int c = c_hi - lane;
-      int level = 0, cb = 0, cbr = 0, cnt = 0;
-      const int pos = pos_nx;
-      pos_nx = scan(imax(c - 64, 0));
-      if (c >= 0) {
-        const int row = pos >> bwl, col = pos & (n - 1);
-#define LVA(r_, c_) (((r_) < n && (c_) < n) ? iabs((int)S->lv[((r_) << bwl) + (c_)]) : 0)
-        const int a01 = LVA(row, col + 1), a10 = LVA(row + 1, col), a11 = LVA(row + 1, col + 1), a02 = LVA(row, col + 2), a20 = LVA(row + 2, col);
-#undef LVA
-        const int mag = imin(a01, 3) + imin(a10, 3) + imin(a11, 3) + imin(a02, 3) + imin(a20, 3);
-        // Coeff_Base_Ctx_Offset of a square block depends on row + col only: 0, 1, 6, 6, 21, 21 ... (a table load per lane otherwise)
-        const int rc = row + col;
-        cb = pos == 0 ? 0 : imin((mag + 1) >> 1, 4) + (rc < 2 ? rc : (rc < 4 ? 6 : 21));
-        int mb = imin(a01, 15) + imin(a10, 15) + imin(a11, 15);
-        mb = imin((mb + 1) >> 1, 6);
-        cbr = pos == 0 ? mb : ((row < 2 && col < 2) ? mb + 7 : mb + 14);
-        level = iabs((int)S->lv[pos]);
-        // symbols of this coefficient: base (except the last coefficient) + 0..4 range symbols
-        const int nbr = level > 2 ? imin((level - 3) / 3 + 1, 4) : 0;
-        cnt = (c != eob - 1) + nbr;
-      }
-      if (slot0 >= 0) {
-        int total;
-        const int off = wave_excl_scan(cnt, lane, &total);
-        if (c >= 0 && y.pos + off + cnt <= y.cap) {
-          uint32_t *o = y.out + y.pos + off;
-          if (c != eob - 1) *o++ = ENT_NARROW(slot0 + cb, imin(level, 3));
-          // the range symbols: nbr = cnt less the base symbol of them, known since the prefix sum - predicated stores, no loop (as a
-          // loop with a break it ran divergent, as often as the wave's largest level asked)
-          const int nbr = cnt - (c != eob - 1);
-          const uint32_t br = ENT_NARROW(slot0 + 42 + cbr, 0);
-          if (nbr > 0) {
-            o[0] = br | (uint32_t)imin(level - 3, 3);
-            if (nbr > 1) {
-              o[1] = br | (uint32_t)imin(level - 6, 3);
-              if (nbr > 2) {
-                o[2] = br | (uint32_t)imin(level - 9, 3);
-                if (nbr > 3) o[3] = br | (uint32_t)imin(level - 12, 3);
-              }
-            }
-          }
-        }
-        y.pos += total;
-      } else if (FULL) {
-        // Resolved path (static CDFs, or a third size class in an edge tile): the symbols adapt here, one after the other - a few
-        // waves with a long serial chain, which last as long as the regular variant's thousands beside them.  So the chain is kept short:
-        // the batch's (row, symbol) pairs go to an LDS list in coding order, lane-parallel like the slot path above; the serial loop
-        // then takes 64 of them into a register, reads the NEXT pair's CDF row before it writes the current one back (forwarded when both
-        // name the same row), builds the entries in a register and stores the 64 with one instruction.
-        if constexpr (FULL) {
-          int total;
-          const int off = wave_excl_scan(cnt, lane, &total);
-          if (c >= 0) {
-            uint16_t *o = g_full_list + off;
-            if (c != eob - 1) *o++ = (uint16_t)((cb << 2) | imin(level, 3));
-            if (level > 2) {
-              for (int idx = 0; idx < 4; idx++) {
-                const int k3 = imin(level - 3 - idx * 3, 3);
-                *o++ = (uint16_t)(((42 + cbr) << 2) | k3);
-                if (k3 < 3) break;
-              }
-            }
-          }
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-          const int row0 = base_off0 - CL::COEFF_BASE, row1 = br_off0 - CL::COEFF_BASE - 42 * 5;   // g_cdf_narrow offset of row r: r < 42 ? row0 + 5 r : row1 + 5 r
-          const int l5 = lane < 5 ? lane : 4;
-          for (int k0 = 0; k0 < total; k0 += 64) {
-            const int n_k = imin(64, total - k0);
-            const int ents = k0 + lane < total ? (int)g_full_list[k0 + lane] : 0;
-            int e = __builtin_amdgcn_readlane(ents, 0);
-            int roff = ((e >> 2) < 42 ? row0 : row1) + (e >> 2) * 5;
-            int v = g_cdf_narrow[roff + l5];
-            uint32_t outv = 0;
-            for (int k = 0; k < n_k; k++) {
-              const int sy = e & 3;
-              // the next pair and its row (k + 1 == n_k: lane 63's or a stale pair - a valid row either way, and unused)
-              const int e_nx = __builtin_amdgcn_readlane(ents, (k + 1) & 63);
-              const int roff_nx = ((e_nx >> 2) < 42 ? row0 : row1) + (e_nx >> 2) * 5;
-              const int v_nx = g_cdf_narrow[roff_nx + l5];
-              const uint32_t fl = sy > 0 ? (uint32_t)__builtin_amdgcn_readlane(v, sy - 1) : 32768u;
-              const uint32_t fh = (uint32_t)__builtin_amdgcn_readlane(v, sy);
-              int nv = v;
-              if (adapt) {
-                const int cntr = __builtin_amdgcn_readlane(v, 4);
-                const int rate = 5 + (cntr > 15) + (cntr > 31);
-                nv = lane < sy ? v + ((32768 - v) >> rate) : v - (v >> rate);
-                nv = lane == 4 ? cntr + (cntr < 32) : nv;
-                if (lane <= 4) g_cdf_narrow[roff + lane] = (uint16_t)nv;
-              }
-              outv = lane == k ? ENT_RESOLVED(fl >> 6, fh >> 6, 3 - sy) : outv;
-              v = roff_nx == roff ? nv : v_nx;
-              roff = roff_nx; e = e_nx;
-            }
-            if (lane < n_k && y.pos + lane < y.cap) y.out[y.pos + lane] = outv;
-            y.pos += n_k;
-          }
-        }
-      }
-    }
-    // ---- signs / golomb in forward scan order (all literals except the DC sign)
-    int fpos_nx = scan(imin(lane, eob - 1));
-    for (int c0 = 0; c0 < eob; c0 += 64) {
-      const int c = c0 + lane;
-      int v = 0;
-      const int fpos = fpos_nx;
-      fpos_nx = scan(imin(c + 64, eob - 1));
-      if (c < eob) v = S->lv[fpos];
-      const int level = iabs(v);
-      { int lsum; (void)wave_excl_scan(level, lane, &lsum); cul += lsum; }   // (the DPP prefix sum's total)
-      if (c0 == 0) {
-        const int v0 = __builtin_amdgcn_readlane(v, 0);
-        if (v0 != 0) {
-          const int dctx = dsum < 0 ? 1 : (dsum > 0 ? 2 : 0);
-          sym_wide(y, lane, adapt, v0 < 0, (FULL ? CL::DC_SIGN : CC::DC_SIGN) + (ptype * 3 + dctx) * 3, 2);
-          dc_cat = v0 < 0 ? 1 : 2;
-          const int l0 = iabs(v0);
-          if (l0 > 14) {  // its golomb tail (rare) right behind it
-            const unsigned g = (unsigned)(l0 - 15) + 1;
-            const int len = floor_log2(g) + 1;
-            emit_bits(y, lane, g, 2 * len - 1);   // len - 1 zeros, then g's len bits
-          }
-        }
-      }
-      const bool mine = level != 0 && c != 0;
-      const unsigned g = level > 14 ? (unsigned)(level - 15) + 1 : 0;
-      const int glen = g ? floor_log2(g) + 1 : 0;
-      const int cnt = mine ? 1 + (g ? 2 * glen - 1 : 0) : 0;
-      int total;
-      const int off = wave_excl_scan(cnt, lane, &total);
-      if (mine && y.pos + off + cnt <= y.cap) {
-        uint32_t *o = y.out + y.pos + off;
-        *o++ = ENT_LITERAL(v < 0);
-        if (g) {
-          for (int k = 0; k < glen - 1; k++) *o++ = ENT_LITERAL(0);
-          for (int k = glen - 1; k >= 0; k--) *o++ = ENT_LITERAL((g >> k) & 1);
-        }
-      }
-      y.pos += total;
-    }
-    cul = imin(cul, 63);
-#undef scan
+    // ... into the LDS copy (same row-major layout)
+    u4 *l128 = reinterpret_cast<u4 *>(g_sym.lv);
+    if (y.lane < n * n / 8) l128[y.lane] = lv_pre[0];
+    if (y.lane + 64 < n * n / 8) l128[y.lane + 64] = lv_pre[1];
+    __syncthreads();
+    level_pass<FULL, TSB>(y, t.big, plane > 0, log2n - 2, bwl, eob);
+    cul = sign_pass<FULL>(y, plane > 0, bwl, eob, dsum, dc_cat);
   }
   __syncthreads();
-  if (lane < w4) {
-    if (x4 + lane < max_x4) { a_lvl[x4 + lane] = (uint8_t)cul; a_dc[x4 + lane] = (uint8_t)dc_cat; }
-    if (y4 + lane < max_y4) { l_lvl[y4 + lane] = (uint8_t)cul; l_dc[y4 + lane] = (uint8_t)dc_cat; }
-  }
+  write_coef_ctx(t, y.lane, plane, x4, y4, w4, cul, dc_cat);
   __syncthreads();
-#undef a_lvl
-#undef a_dc
-#undef l_lvl
-#undef l_dc
 }
 
 // ---- motion vector prediction (spec §7.10.2) inside a one-superblock tile ----------------------
@@ -492,9 +540,10 @@ __device__ __forceinline__ int unit_order(int ux, int uy) { return (((uy >> 3) *
 __device__ __forceinline__ bool mv_inside(const MvScan &m, int r4, int c4) { return r4 >= 0 && c4 >= 0 && r4 < m.max_r4 && c4 < m.max_c4; }
 template <int TSB>
 __device__ __forceinline__ void stack_add(MvScan &m, int r4, int c4, int weight) {
-  const int u = (r4 >> 1) * TW + (c4 >> 1);
-  if (!uni(TI.info[u].is_inter)) return;
-  const int mr = uni(TI.info[u].mv_row), mc = uni(TI.info[u].mv_col);  // multiples of 8: lower_mv_precision is a no-op
+  const int u = TileCtx<TSB>::unit_at4(r4, c4);
+  const Av1miBlkInfo &bi = TileCtx<TSB>::unit(u);
+  if (!uni(bi.is_inter)) return;
+  const int mr = uni(bi.mv_row), mc = uni(bi.mv_col);  // multiples of 8: lower_mv_precision is a no-op
   if (uni(g_inter.newmv[u])) m.new_count++;
   m.found = 1;
   int i = 0;
@@ -504,33 +553,22 @@ __device__ __forceinline__ void stack_add(MvScan &m, int r4, int c4, int weight)
   else if (m.num < 8) { g_inter.stk_row[m.num] = mr; g_inter.stk_col[m.num] = mc; g_inter.stk_w[m.num] = weight; m.num++; }
 }
 template <int TSB>
-__device__ __forceinline__ int cand_n4(int r4, int c4) { return (1 << uni(TI.info[(r4 >> 1) * TW + (c4 >> 1)].bsl)) >> 2; }
-template <int TSB>
-__device__ __forceinline__ void scan_row(MvScan &m, int r4, int c4, int bw4, int delta_row) {
-  int delta_col = 0, i = 0;
-  const int end4 = imin(imin(bw4, m.max_c4 - c4), 16);
-  if (iabs(delta_row) > 1) { delta_row += r4 & 1; delta_col = 1 - (c4 & 1); }
+__device__ __forceinline__ int cand_n4(int r4, int c4) { return (1 << uni(TileCtx<TSB>::unit(TileCtx<TSB>::unit_at4(r4, c4)).bsl)) >> 2; }
+// the row (ROW) above or the column left of the block of n4 units at (r4, c4), `delta` units away (-1, -3, -5)
+template <int TSB, bool ROW>
+__device__ __forceinline__ void scan_line(MvScan &m, int r4, int c4, int n4, int delta) {
+  const int along0 = ROW ? c4 : r4, across0 = ROW ? r4 : c4;   // the coordinate the scan runs along / the one `delta` is applied to
+  const int end4 = imin(imin(n4, (ROW ? m.max_c4 : m.max_r4) - along0), 16);
+  int d_along = 0, i = 0;
+  if (iabs(delta) > 1) { delta += across0 & 1; d_along = 1 - (along0 & 1); }
+  const bool far = iabs(delta) > 1;
   while (i < end4) {
-    const int r = r4 + delta_row, c = c4 + delta_col + i;
+    const int across = across0 + delta, along = along0 + d_along + i;
+    const int r = ROW ? across : along, c = ROW ? along : across;
     if (!mv_inside(m, r, c)) break;
-    int len = imin(cand_n4<TSB>(r, c), bw4);
-    if (iabs(delta_row) > 1) len = imax(len, 2);
-    if (bw4 >= 16) len = imax(len, 4);
-    stack_add<TSB>(m, r, c, len * 2);
-    i += len;
-  }
-}
-template <int TSB>
-__device__ __forceinline__ void scan_col(MvScan &m, int r4, int c4, int bh4, int delta_col) {
-  int delta_row = 0, i = 0;
-  const int end4 = imin(imin(bh4, m.max_r4 - r4), 16);
-  if (iabs(delta_col) > 1) { delta_row = 1 - (r4 & 1); delta_col += c4 & 1; }
-  while (i < end4) {
-    const int r = r4 + delta_row + i, c = c4 + delta_col;
-    if (!mv_inside(m, r, c)) break;
-    int len = imin(cand_n4<TSB>(r, c), bh4);
-    if (iabs(delta_col) > 1) len = imax(len, 2);
-    if (bh4 >= 16) len = imax(len, 4);
+    int len = imin(cand_n4<TSB>(r, c), n4);
+    if (far) len = imax(len, 2);
+    if (n4 >= 16) len = imax(len, 4);
     stack_add<TSB>(m, r, c, len * 2);
     i += len;
   }
@@ -557,35 +595,25 @@ __device__ __forceinline__ void sort_stack(int start, int end) {
 }
 // returns NumMvFound; contexts through the references.  (r4, c4): block origin, n4: block size, all in 4x4 units
 template <int TSB>
-__device__ __forceinline__ int build_mv_stack(const Av1miDevParams &P, const TileGeo &tg, int r4, int c4, int n4, int &new_ctx, int &ref_ctx) {
+__device__ __forceinline__ int build_mv_stack(const TileCtx<TSB> &t, int r4, int c4, int n4, int &new_ctx, int &ref_ctx) {
   MvScan m;
   m.num = 0; m.new_count = 0; m.found = 0;
   // limits: the tile (TSB superblocks) clipped to the frame, in tile-local 4x4 units
-  m.max_r4 = imin(16 * TSB, tg.max_y4_y + (tg.toy >> 2)); m.max_c4 = imin(16 * TSB, tg.max_x4_y + (tg.tox >> 2));
+  m.max_r4 = imin(16 * TSB, t.max_y4_y + (t.toy >> 2)); m.max_c4 = imin(16 * TSB, t.max_x4_y + (t.tox >> 2));
   m.cur_z = unit_order<TSB>(c4 >> 1, r4 >> 1);
-  scan_row<TSB>(m, r4, c4, n4, -1);
-  int found_above = m.found; m.found = 0;
-  scan_col<TSB>(m, r4, c4, n4, -1);
-  int found_left = m.found; m.found = 0;
+  int found_above = 0, found_left = 0;
+  auto found_into = [&m](int &side) { side |= m.found; m.found = 0; };   // what the scan just done met counts for its side
+  scan_line<TSB, true>(m, r4, c4, n4, -1); found_into(found_above);
+  scan_line<TSB, false>(m, r4, c4, n4, -1); found_into(found_left);
   if (n4 <= 16) scan_point<TSB>(m, r4, c4, -1, n4);
-  if (m.found) found_above = 1;
-  m.found = 0;
+  found_into(found_above);
   const int close_matches = found_above + found_left, num_nearest = m.num, num_new = m.new_count;
   for (int i = 0; i < num_nearest; i++) g_inter.stk_w[i] = uni(g_inter.stk_w[i]) + 640;  // REF_CAT_LEVEL
-  scan_point<TSB>(m, r4, c4, -1, -1);
-  if (m.found) found_above = 1;
-  m.found = 0;
-  scan_row<TSB>(m, r4, c4, n4, -3);
-  if (m.found) found_above = 1;
-  m.found = 0;
-  scan_col<TSB>(m, r4, c4, n4, -3);
-  if (m.found) found_left = 1;
-  m.found = 0;
-  scan_row<TSB>(m, r4, c4, n4, -5);
-  if (m.found) found_above = 1;
-  m.found = 0;
-  scan_col<TSB>(m, r4, c4, n4, -5);
-  if (m.found) found_left = 1;
+  scan_point<TSB>(m, r4, c4, -1, -1); found_into(found_above);
+  scan_line<TSB, true>(m, r4, c4, n4, -3); found_into(found_above);
+  scan_line<TSB, false>(m, r4, c4, n4, -3); found_into(found_left);
+  scan_line<TSB, true>(m, r4, c4, n4, -5); found_into(found_above);
+  scan_line<TSB, false>(m, r4, c4, n4, -5); found_into(found_left);
   const int total_matches = found_above + found_left;
   sort_stack(0, num_nearest);
   sort_stack(num_nearest, m.num);
@@ -597,7 +625,6 @@ __device__ __forceinline__ int build_mv_stack(const Av1miDevParams &P, const Til
   else { new_ctx = 5 - imin(num_new, 1); ref_ctx = 5; }
   // clamping (§7.10.2.14): the motion search keeps every coded vector within 16 samples of the frame, which is
   // inside the clamp range of every later block - nothing to do
-  (void)P;
   return m.num;
 }
 __device__ __forceinline__ int drl_ctx(int idx) {
@@ -608,25 +635,204 @@ __device__ __forceinline__ int drl_ctx(int idx) {
   return 0;
 }
 // read_mv_component mirrored (§5.11.32), v != 0 in 1/8 samples (always a multiple of 8 here)
-__device__ __forceinline__ void sym_mv_component(Sym &y, int lane, int adapt, int comp, int v) {
+__device__ __forceinline__ void sym_mv_component(Sym &y, int comp, int v) {
   const int base = CL::MV_COMP + comp * CL::MVC_SIZE;
   const int z = iabs(v) - 1;
   int cls = 0;
   while (cls < 10 && z >= (2 << (cls + 3))) cls++;
   const int o = z - (cls ? (2 << (cls + 2)) : 0);
   const int d = o >> 3, fr = (o >> 1) & 3;
-  sym_wide<1>(y, lane, adapt, v < 0, base + CL::MVC_SIGN, 2);
-  sym_wide<1>(y, lane, adapt, cls, base + CL::MVC_CLASS, 11);
+  sym_wide<1>(y, v < 0, base + CL::MVC_SIGN, 2);
+  sym_wide<1>(y, cls, base + CL::MVC_CLASS, 11);
   if (cls == 0) {
-    sym_wide<1>(y, lane, adapt, d, base + CL::MVC_CLASS0, 2);
-    sym_wide<1>(y, lane, adapt, fr, base + CL::MVC_CLASS0_FP + d * 5, 4);
+    sym_wide<1>(y, d, base + CL::MVC_CLASS0, 2);
+    sym_wide<1>(y, fr, base + CL::MVC_CLASS0_FP + d * 5, 4);
   } else {
-    for (int i = 0; i < cls; i++) sym_wide<1>(y, lane, adapt, (d >> i) & 1, base + CL::MVC_BITS + i * 3, 2);
-    sym_wide<1>(y, lane, adapt, fr, base + CL::MVC_FP, 4);
+    for (int i = 0; i < cls; i++) sym_wide<1>(y, (d >> i) & 1, base + CL::MVC_BITS + i * 3, 2);
+    sym_wide<1>(y, fr, base + CL::MVC_FP, 4);
   }
 }
 
-__device__ __forceinline__ int icdf_prob(const Sym &y, int off, int el) { return (el > 0 ? y.cdf[off + el - 1] : 32768) - y.cdf[off + el]; }
+// ---- the syntax elements of a tile, named as in the spec ---------------------------------------------------------------------------
+
+// What a block's contexts read of the units above and left of its origin (inside the tile: `avail`; all zero where not), wave-uniform.
+struct Neighbour { int avail, skip, is_inter, ymode, bsl; };
+struct Neighbours { Neighbour u, l; };
+template <int TSB>
+__device__ __forceinline__ Neighbour read_neighbour(const TileCtx<TSB> &t, int avail, int ux, int uy) {
+  Neighbour nb = { avail, 0, 0, 0, 0 };
+  if (avail) {
+    const Av1miBlkInfo &bi = t.info(ux, uy);
+    nb.skip = uni(bi.skip); nb.is_inter = uni(bi.is_inter); nb.ymode = uni(bi.ymode); nb.bsl = uni(bi.bsl);
+  }
+  return nb;
+}
+
+// read_lr (§5.11.57): the restoration units whose origin lies in superblock (sbr, sbc) of frame f, Y and (enable_lr 3 / 4) U, V.  Luma
+// units are 64 << lr_unit_shift samples offset by 8 rows, chroma units half that offset by 4 (lr_uv_shift 1), so unit (r, c) of every
+// plane starts in superblock (r << lr_unit_shift, c << lr_unit_shift) - the other superblocks, and those past the last unit (264 rows:
+// five superblock rows, two units of 128), read none - and the signalled size being even every plane has the same unit grid
+// (lr_geometry.h).  The coefficients are coded against the plane's RefLrWiener / RefSgrXqd, which start every tile at their mid values
+// and follow the plane's units coded with a filter (lr_prev / sgr_prev, 2 bits per plane); the three CDFs are shared by the planes
+template <bool FULL>
+__device__ __forceinline__ void read_lr(Sym &y, const Av1miDevParams &P, const uint8_t *__restrict__ lr_choice, int f, int sbr, int sbc, int &lr_prev, int &sgr_prev) {
+  const int urows = av1mi_lr_unit_rows(P), ucols = av1mi_lr_unit_cols(P);  // from the signalled size
+  const int ur = av1mi_lr_sb_unit(sbr, urows, P.lr_unit_shift), uc = av1mi_lr_sb_unit(sbc, ucols, P.lr_unit_shift);
+  if (ur < 0 || uc < 0) return;
+  const int nplanes = P.lr_chroma ? 3 : 1;
+#pragma nounroll
+  for (int pl = 0; pl < nplanes; pl++) {
+    // choice [frame][plane][unit]: 0 = off, 1..3 = Wiener candidate, 4..6 = self-guided candidate (RESTORE_SWITCHABLE frames only)
+    // with the Wiener fit (P.lr_wfit_code) 23 = the unit's fitted Wiener filter
+    const int ch = uni(lr_choice[((size_t)f * nplanes + pl) * urows * ucols + ur * ucols + uc]);
+    const bool wiener = ch <= 3 || (P.lr_wfit_code && ch == 23);
+    if (P.enable_lr == 2) sym_wide(y, ch == 0 ? 0 : (wiener ? 1 : 2), Rows<FULL>::restore_switchable(), 3);
+    else sym_wide(y, ch != 0, Rows<FULL>::use_wiener(), 2);
+    const int sh = 2 * pl;
+    const size_t rec = ((size_t)f * 3 + pl) * urows * ucols + ur * ucols + uc;   // the unit's record of a fit: [frame][plane 0..2][unit]
+    if (!wiener) {
+      // with the self-guided fit (choices 4 .. 22) the unit's bits are its own, written against the carried RefSgrXqd by
+      // lr_fit_kernel.hip: { bits, length }
+      const uint32_t *fc = P.lr_fit_code ? P.lr_fit_code + rec * 2 : nullptr;
+      const int rf = (sgr_prev >> sh) & 3;
+      const int len = fc ? uni((int)fc[1]) : P.sgr_code_len[rf][ch - 4];
+      const unsigned long long bits = fc ? (unsigned long long)(uint32_t)uni((int)fc[0]) : P.sgr_code_bits[rf][ch - 4];
+      emit_bits(y, bits, len);
+      if (!fc) sgr_prev = (sgr_prev & ~(3 << sh)) | ((ch - 3) << sh);
+    } else if (ch && P.lr_wfit_code) {
+      // every Wiener unit's bits are its own, written against the carried RefLrWiener by lr_wfit_kernel.hip:
+      // { bits 0-31, bits 32-63, length }
+      const uint32_t *wc = P.lr_wfit_code + rec * 3;
+      const int len = uni((int)wc[2]);
+      const unsigned long long bits = (unsigned long long)(uint32_t)uni((int)wc[0]) | ((unsigned long long)(uint32_t)uni((int)wc[1]) << 32);
+      emit_bits(y, bits, len);
+    } else if (ch) {
+      const int rf = (lr_prev >> sh) & 3;
+      const int len = pl ? P.lr_code_len_uv[rf][ch - 1] : P.lr_code_len[rf][ch - 1];
+      const unsigned long long bits = pl ? P.lr_code_bits_uv[rf][ch - 1] : P.lr_code_bits[rf][ch - 1];
+      emit_bits(y, bits, len);
+      lr_prev = (lr_prev & ~(3 << sh)) | (ch << sh);
+    }
+  }
+}
+
+// partition (§5.11.4) of one node of 2^bsl samples, a split or a leaf (PARTITION_SPLIT / PARTITION_NONE), with rows_left x cols_left
+// samples of the frame from its origin on; the context from the blocks above and left of that origin
+__device__ __forceinline__ void sym_partition(Sym &y, const Neighbours &nb, int bsl, bool split, int rows_left, int cols_left) {
+  const int half = (1 << bsl) >> 1;
+  const bool has_rows = half < rows_left, has_cols = half < cols_left;
+  const int above = nb.u.avail && nb.u.bsl < bsl, left = nb.l.avail && nb.l.bsl < bsl;
+  const int off = CL::PARTITION + ((bsl - 3) * 4 + left * 2 + above) * 11;
+  if (has_rows && has_cols) {
+    sym_wide(y, split ? 3 : 0, off, bsl == 3 ? 4 : 10);
+  } else if (has_cols) {
+    int p = icdf_prob(y, off, 2) + icdf_prob(y, off, 3);
+    if (bsl != 3) p += icdf_prob(y, off, 4) + icdf_prob(y, off, 6) + icdf_prob(y, off, 7) + icdf_prob(y, off, 9);
+    sym_bool(y, 1, (uint32_t)uni(p));
+  } else if (has_rows) {
+    int p = icdf_prob(y, off, 1) + icdf_prob(y, off, 3);
+    if (bsl != 3) p += icdf_prob(y, off, 4) + icdf_prob(y, off, 5) + icdf_prob(y, off, 6) + icdf_prob(y, off, 8);
+    sym_bool(y, 1, (uint32_t)uni(p));
+  }
+}
+
+// read_cdef (§5.11.56): the superblock's cdef_idx, cdef_bits literal bits, MSB first
+__device__ __forceinline__ void read_cdef(Sym &y, const Av1miDevParams &P, size_t sb_of_chunk) {
+  emit_bits(y, (unsigned)uni(P.cdef_idx[sb_of_chunk]), P.cdef_bits);
+}
+
+// read_delta_qindex (§5.11.46): delta_q_present = 1, delta_q_res = 2, i.e. steps of 4, from CurrentQIndex to the superblock's index
+template <bool FULL>
+__device__ __forceinline__ void read_delta_qindex(Sym &y, int qsb, int &cur_q) {
+  const int r = (qsb - cur_q) / 4, a = iabs(r);
+  sym_wide(y, imin(a, 3), Rows<FULL>::delta_q(), 4);   // delta_q_abs
+  if (a >= 3) {   // delta_q_rem_bits L(3), delta_q_abs_bits L(rem_bits + 1)
+    const int nb = floor_log2((unsigned)(a - 1)), rest = a - 1 - (1 << nb);
+    emit_bits(y, (unsigned)(((nb - 1) << nb) | rest), 3 + nb);
+  }
+  if (a) emit_bits(y, (unsigned)(r < 0), 1);   // delta_q_sign_bit
+  cur_q = qsb;
+}
+
+// is_inter of inter_frame_mode_info (§5.11.18), context from the neighbours' intra-ness
+__device__ __forceinline__ void sym_is_inter(Sym &y, const Neighbours &nb, int is_inter) {
+  const int a_intra = nb.u.avail && !nb.u.is_inter, l_intra = nb.l.avail && !nb.l.is_inter;
+  int ictx;
+  if (nb.u.avail && nb.l.avail) ictx = (l_intra && a_intra) ? 3 : ((l_intra || a_intra) ? 1 : 0);
+  else ictx = 2 * (a_intra | l_intra);   // (one neighbour or none)
+  sym_wide<1>(y, is_inter, CL::IS_INTER + ictx * 3, 2);
+}
+
+// inter_block_mode_info (§5.11.23) of the block of n samples at (bx, by) of the superblock: LAST_FRAME = single_ref_p1 0, p3 0, p4 0;
+// then the cheapest name of the vector the recon kernel used: NEARESTMV, NEARMV, GLOBALMV, else NEWMV against the list's head.
+// Leaves the block's NEWMV flag in g_inter.newmv for the lists of the blocks after it.
+template <int TSB>
+__device__ __forceinline__ void inter_block_mode_info(Sym &y, const TileCtx<TSB> &t, const Neighbours &nb, int bx, int by, int n) {
+  const int rctx = nb.u.is_inter + nb.l.is_inter > 0 ? 2 : 1;
+  sym_wide<1>(y, 0, CL::SINGLE_REF + (0 * 3 + rctx) * 3, 2);
+  sym_wide<1>(y, 0, CL::SINGLE_REF + (2 * 3 + rctx) * 3, 2);
+  sym_wide<1>(y, 0, CL::SINGLE_REF + (3 * 3 + rctx) * 3, 2);
+  int new_ctx, ref_ctx;
+  const int num = build_mv_stack<TSB>(t, (by + t.toy) >> 2, (bx + t.tox) >> 2, n >> 2, new_ctx, ref_ctx);
+  const Av1miBlkInfo &bi = t.info(bx >> 3, by >> 3);
+  const int mvr = uni(bi.mv_row), mvc = uni(bi.mv_col);
+  const int s0r = uni(g_inter.stk_row[0]), s0c = uni(g_inter.stk_col[0]), s1r = uni(g_inter.stk_row[1]), s1c = uni(g_inter.stk_col[1]);
+  int mode;  // 0 NEARESTMV 1 NEARMV 2 GLOBALMV 3 NEWMV
+  if (num >= 1 && mvr == s0r && mvc == s0c) mode = 0;
+  else if (num >= 2 && mvr == s1r && mvc == s1c) mode = 1;
+  else if ((mvr | mvc) == 0) mode = 2;
+  else mode = 3;
+  sym_wide<1>(y, mode != 3, CL::NEWMV + new_ctx * 3, 2);
+  if (mode != 3) {
+    sym_wide<1>(y, mode != 2, CL::GLOBALMV + 0 * 3, 2);
+    if (mode != 2) sym_wide<1>(y, mode == 1, CL::REFMV + ref_ctx * 3, 2);
+  }
+  if (mode == 3) { if (num > 1) sym_wide<1>(y, 0, CL::DRL + drl_ctx(0) * 3, 2); }
+  else if (mode == 1) { if (num > 2) sym_wide<1>(y, 0, CL::DRL + drl_ctx(1) * 3, 2); }
+  if (mode == 3) {
+    const int dr = mvr - s0r, dc = mvc - s0c;  // list head, or the zero global vector when the list is empty
+    sym_wide<1>(y, (dr != 0 ? 2 : 0) | (dc != 0 ? 1 : 0), CL::MV_JOINT, 4);
+    if (dr) sym_mv_component(y, 0, dr);
+    if (dc) sym_mv_component(y, 1, dc);
+  }
+  const int n8 = n >> 3;
+  if (y.lane < n8 * n8) g_inter.newmv[t.unit_of((bx >> 3) + y.lane % n8, (by >> 3) + y.lane / n8)] = (uint8_t)(mode == 3);
+}
+
+// read_cfl_alphas (§5.11.45); `ainfo` bits 4-9 / 10-15: the alphas of U / V, 6-bit two's complement, not both zero
+template <bool FULL>
+__device__ __forceinline__ void read_cfl_alphas(Sym &y, int ainfo) {
+  const int au = ((ainfo >> 4) & 63) - 2 * ((ainfo >> 4) & 32), av = ((ainfo >> 10) & 63) - 2 * ((ainfo >> 10) & 32);
+  const int su = au == 0 ? 0 : (au < 0 ? 1 : 2), sv = av == 0 ? 0 : (av < 0 ? 1 : 2);
+  sym_wide(y, su * 3 + sv - 1, Rows<FULL>::cfl_sign(), 8);
+  if (su) sym_wide(y, iabs(au) - 1, Rows<FULL>::cfl_alpha(su, sv), 16);
+  if (sv) sym_wide(y, iabs(av) - 1, Rows<FULL>::cfl_alpha(sv, su), 16);
+}
+
+// The intra modes of a block of 2^bsl samples: y_mode of intra_frame_mode_info (§5.11.7, key frames: context from the neighbours'
+// modes) or of intra_block_mode_info (§5.11.22, inter frames: by block-size group), the angle deltas, and chroma: the luma mode at
+// luma's angle delta, or chroma from luma.  `ainfo` is the block's `angle` field: bits 0-2 the angle delta, from bit 4 the CfL alphas.
+template <bool FULL, bool INTER>
+__device__ __forceinline__ void intra_mode_info(Sym &y, const Neighbours &nb, int bsl, int ymode, int ainfo) {
+  if constexpr (INTER) sym_wide<1>(y, ymode, CL::IF_Y_MODE + (bsl <= 3 ? 1 : (bsl == 4 ? 2 : 3)) * 14, 13);
+  else sym_wide(y, ymode, CL::KF_Y_MODE + (intra_mode_ctx(nb.u.ymode) * 5 + intra_mode_ctx(nb.l.ymode)) * 14, 13);
+  const int adelta = ainfo & 7, cfl = (ainfo >> 4) != 0;
+  if (ymode >= 1 && ymode <= 8) sym_wide(y, adelta, CL::ANGLE_DELTA + (ymode - 1) * 8, 7);
+  const int uvmode = cfl ? 13 : ymode;
+  const int cfl_allowed = bsl <= 5;
+  sym_wide(y, uvmode, CL::UV_MODE + (cfl_allowed * 13 + ymode) * 15, cfl_allowed ? 14 : 13);
+  if (cfl) read_cfl_alphas<FULL>(y, ainfo);
+  if (uvmode >= 1 && uvmode <= 8) sym_wide(y, adelta, CL::ANGLE_DELTA + (uvmode - 1) * 8, 7);
+}
+
+// reset_block_context (§5.11.5) of a skipped block of n samples at (bx, by) of the superblock: its coefficient contexts are zero
+template <int TSB>
+__device__ __forceinline__ void reset_block_context(const TileCtx<TSB> &t, int lane, int bx, int by, int n) {
+  __syncthreads();
+  write_coef_ctx(t, lane, 0, bx >> 2, by >> 2, n >> 2, 0, 0);
+  for (int pl = 1; pl < 3; pl++) write_coef_ctx(t, lane, pl, bx >> 3, by >> 3, imax(n >> 3, 1), 0, 0);
+  __syncthreads();
+}
 
 // FULL = false: regular tiles in adaptive mode - every leaf of the tile has one size, i.e. exactly two (tx size, plane type)
 // classes, no narrow rows in LDS (10.4 KB -> ~4 waves per SIMD).
@@ -640,7 +846,8 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
                                                            int tile0 /* chunk-wide index of this launch's first tile: launches cover whole frames */,
                                                            int edge_grid /* 0: one workgroup per tile of the launch's frames; 1: per EDGE tile of them (av1mi_edge_tile) */,
                                                            const uint32_t *__restrict__ sym_count, const uint32_t *__restrict__ sym_order /* the tiles by weight class, or null: natural order */) {
-  // one wave per TILE of TSB x TSB superblocks (raster order inside the tile)
+  typedef TileCtx<TSB> Tile;
+  // ---- the tile: one wave per TILE of TSB x TSB superblocks (raster order inside the tile)
   const int tiles_per_frame = P.tile_rows * P.tile_cols, sbs_per_frame = P.sb_rows * P.sb_cols;
   int gt = (int)blockIdx.x + tile0;
   if (sym_order) {
@@ -667,282 +874,125 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
   // (a tile whose superblocks mix block sizes holds more than two classes: the full variant's.  The launcher's grids are supersets
   // of a variant's tiles; this test decides)
   if (av1mi_tile_is_regular(P, f, tr, tc, TSB) == FULL) return;
+  // ---- the tile's state: the CDF rows of the variant ...
   if constexpr (FULL) {
     // whole 16-byte pieces, then the last entries one by one
     for (int i = lane; i < CL::COEFF_BASE / 8; i += 64) reinterpret_cast<u4 *>(g_cdfw_full)[i] = reinterpret_cast<const u4 *>(cdf_init)[i];
     if (lane < CL::COEFF_BASE % 8) g_cdfw_full[(CL::COEFF_BASE & ~7) + lane] = cdf_init[(CL::COEFF_BASE & ~7) + lane];
     if (lane < 18) g_cdfw_full[CL::COEFF_BASE + lane] = 0;
+    for (int i = lane; i < CL::INTRA_TOTAL - CL::COEFF_BASE; i += 64) g_cdf_narrow[i] = cdf_init[CL::COEFF_BASE + i];
+    g_cdf_narrow[CL::INTRA_TOTAL - CL::COEFF_BASE + lane] = 0;
   } else {
     // the compact layout's image for this leaf size lies behind the blob (the host built it with the blob: it depends on nothing else)
     for (int i = lane; i < CC::WORDS / 8; i += 64) reinterpret_cast<u4 *>(g_cdfw_compact)[i] = reinterpret_cast<const u4 *>(cdf_init + CC::AT)[i];
   }
-  if (FULL) {
-    for (int i = lane; i < CL::INTRA_TOTAL - CL::COEFF_BASE; i += 64) g_cdf_narrow[i] = cdf_init[CL::COEFF_BASE + i];
-    g_cdf_narrow[CL::INTRA_TOTAL - CL::COEFF_BASE + lane] = 0;
-  }
-  if (INTER) {
+  if constexpr (INTER) {
     for (int i = lane; i < CL::TOTAL - CL::INTER_BASE; i += 64) g_cdf_inter[i] = cdf_init[CL::INTER_BASE + i];
     g_cdf_inter[CL::TOTAL - CL::INTER_BASE + lane] = 0;
   }
   {
-    // block info of the whole tile (zero outside the frame), above contexts cleared (clear_above_context)
+    // ... block info of the whole tile (zero outside the frame), above contexts cleared (clear_above_context)
     const Av1miBlkInfo *finfo = blk + (size_t)f * P.b8_rows * P.b8_cols;
     for (int u = lane; u < 64 * TSB * TSB; u += 64) {
-      const int r = tr * TW + u / TW, c = tc * TW + u % TW;
+      const int r = tr * Tile::TW + u / Tile::TW, c = tc * Tile::TW + u % Tile::TW;
       // (one 16-byte record as one register quad: copied as a structure it went through scratch memory, the kernel's only use of it)
       u4 bi = {0u, 0u, 0u, 0u};
       if (r < P.b8_rows && c < P.b8_cols) bi = *reinterpret_cast<const u4 *>(&finfo[(size_t)r * P.b8_cols + c]);
-      *reinterpret_cast<u4 *>(&TI.info[u]) = bi;
-      if (INTER) g_inter.newmv[u] = 0;
+      *reinterpret_cast<u4 *>(&Tile::unit(u)) = bi;
+      if constexpr (INTER) g_inter.newmv[u] = 0;
     }
-    for (int i = lane; i < 3 * 16 * TSB; i += 64) { (&TI.above_lvl[0][0])[i] = 0; (&TI.above_dc[0][0])[i] = 0; }
+    TileLds<TSB> &tl = tile_lds<TSB>();
+    for (int i = lane; i < 3 * 16 * TSB; i += 64) { (&tl.above_lvl[0][0])[i] = 0; (&tl.above_dc[0][0])[i] = 0; }
   }
   __syncthreads();
   Sym y;
-  y.cdf = FULL ? g_cdfw_full : g_cdfw_compact;
+  y.lane = lane;
+  y.adapt = !P.disable_cdf_update;
+  y.cdf = Rows<FULL>::lds();
   y.out = streams + (size_t)gt * P.stream_cap;
   y.pos = 0; y.cap = P.stream_cap;
   y.combo0 = -1; y.combo1 = -1;
-  const int adapt = !P.disable_cdf_update;
   // INTER = false: key frames only (no inter syntax compiled in); INTER = true: the chunk's inter frames.  Each
   // instantiation skips the other's frames.
-  const int inter_frame = INTER;
   if (av1mi_frame_is_inter(P, f) != (int)INTER) return;
   // 2 bits per plane (bits 2 p .. 2 p + 1: plane p):
   int lr_prev = 0;  // RefLrWiener of the tile: 0 = Wiener_Taps_Mid, k = candidate k-1 (the plane's last unit coded with a Wiener filter)
   int sgr_prev = 0; // RefSgrXqd of the tile: 0 = Sgrproj_Xqd_Mid, k = self-guided candidate k-1 (the plane's last self-guided unit)
   int cur_q = P.base_q_idx;   // CurrentQIndex (adaptive quantisation): base_q_idx at the tile start, then the last index a delta was coded for
+  // ---- the tile's superblocks
 #pragma nounroll
   for (int si = 0; si < TSB * TSB; si++) {
-  const int sbr = tr * TSB + si / TSB, sbc = tc * TSB + si % TSB;
-  if (sbr >= P.sb_rows || sbc >= P.sb_cols) continue;
-  const int sb = sbr * P.sb_cols + sbc;
-  TileGeo tg;
-  tg.tox = (si % TSB) * 64; tg.toy = (si / TSB) * 64;
-  tg.sb_x = sbc * 64; tg.sb_y = sbr * 64; tg.big = P.max_bs_log2 >= 6;
-  tg.max_x4_y = P.mi_cols - sbc * 16; tg.max_y4_y = P.mi_rows - sbr * 16;
-  tg.max_x4_c = (P.mi_cols >> 1) - sbc * 8; tg.max_y4_c = (P.mi_rows >> 1) - sbr * 8;
-  const int tox = tg.tox, toy = tg.toy, tox8 = tox >> 3, toy8 = toy >> 3;
-#define INFO(ux_, uy_) TI.info[((uy_) + toy8) * TW + (ux_) + tox8]
-  const int16_t *sb_levels = levels + ((size_t)f * sbs_per_frame + sb) * AV1MI_SB_LEVELS;
-  int cdef_todo = P.cdef_bits > 0;   // read_cdef: the superblock's cdef_idx is coded at its first block that is not skipped
-  int dq_todo = P.aq_map != nullptr;   // read_delta_qindex: at the superblock's first block
-  if (si % TSB == 0) {  // clear_left_context at the start of every superblock row of the tile
-    __syncthreads();
-    if (lane < 48) { (&S->left_lvl[0][0])[lane] = 0; (&S->left_dc[0][0])[lane] = 0; }
-    __syncthreads();
-  }
-
-  if (P.enable_lr) {
-    // read_lr (§5.11.57): the restoration units whose origin lies in this superblock, Y and (enable_lr 3 / 4) U, V.  Luma units are
-    // 64 << lr_unit_shift samples offset by 8 rows, chroma units half that offset by 4 (lr_uv_shift 1), so unit (r, c) of every plane
-    // starts in superblock (r << lr_unit_shift, c << lr_unit_shift) - the other superblocks, and those past the last unit (264 rows:
-    // five superblock rows, two units of 128), read none - and the signalled size being even every plane has the same unit grid
-    // (lr_geometry.h).  The coefficients are coded against the plane's
-    // RefLrWiener / RefSgrXqd, which start every tile at their mid values and follow the plane's units coded with a filter; the
-    // three CDFs are shared by the planes
-    const int urows = av1mi_lr_unit_rows(P), ucols = av1mi_lr_unit_cols(P);  // from the signalled size
-    const int ur = av1mi_lr_sb_unit(sbr, urows, P.lr_unit_shift), uc = av1mi_lr_sb_unit(sbc, ucols, P.lr_unit_shift);
-    if (ur >= 0 && uc >= 0) {
-      const int nplanes = P.lr_chroma ? 3 : 1;
+    const int sbr = tr * TSB + si / TSB, sbc = tc * TSB + si % TSB;
+    if (sbr >= P.sb_rows || sbc >= P.sb_cols) continue;
+    const int sb = sbr * P.sb_cols + sbc;
+    const size_t sb_of_chunk = (size_t)f * sbs_per_frame + sb;
+    Tile t;
+    t.tox = (si % TSB) * 64; t.toy = (si / TSB) * 64;
+    t.sb_x = sbc * 64; t.sb_y = sbr * 64; t.big = P.max_bs_log2 >= 6;
+    t.max_x4_y = P.mi_cols - sbc * 16; t.max_y4_y = P.mi_rows - sbr * 16;
+    t.max_x4_c = (P.mi_cols >> 1) - sbc * 8; t.max_y4_c = (P.mi_rows >> 1) - sbr * 8;
+    const int16_t *sb_levels = levels + sb_of_chunk * AV1MI_SB_LEVELS;
+    int cdef_todo = P.cdef_bits > 0;   // read_cdef: the superblock's cdef_idx is coded at its first block that is not skipped
+    int dq_todo = P.aq_map != nullptr;   // read_delta_qindex: at the superblock's first block
+    if (si % TSB == 0) {  // clear_left_context at the start of every superblock row of the tile
+      __syncthreads();
+      if (lane < 48) { (&g_sym.left_lvl[0][0])[lane] = 0; (&g_sym.left_dc[0][0])[lane] = 0; }
+      __syncthreads();
+    }
+    if (P.enable_lr) read_lr<FULL>(y, P, lr_choice, f, sbr, sbc, lr_prev, sgr_prev);
+    // ---- the superblock's leaves.
+    // 8x8 units in Z (partition) order, from leaf origin to leaf origin: the 4^(leaf - 3) units of a leaf follow its origin in that
+    // order, so the walk steps over them (as a trip per unit, 60 of the 64 trips of a superblock of 32x32 leaves found nothing to do, at
+    // an LDS round trip each); a unit outside the frame advances by one
 #pragma nounroll
-      for (int pl = 0; pl < nplanes; pl++) {
-        // choice [frame][plane][unit]: 0 = off, 1..3 = Wiener candidate, 4..6 = self-guided candidate (RESTORE_SWITCHABLE frames only)
-        // with the Wiener fit (P.lr_wfit_code) 23 = the unit's fitted Wiener filter
-        const int ch = uni(lr_choice[((size_t)f * nplanes + pl) * urows * ucols + ur * ucols + uc]);
-        const bool wiener = ch <= 3 || (P.lr_wfit_code && ch == 23);
-        if (P.enable_lr == 2) sym_wide(y, lane, adapt, ch == 0 ? 0 : (wiener ? 1 : 2), FULL ? CL::RESTORE_SW : CC::RESTORE_SW, 3);
-        else sym_wide(y, lane, adapt, ch != 0, FULL ? CL::USE_WIENER : CC::USE_WIENER, 2);
-        const int sh = 2 * pl;
-        if (!wiener) {
-          // with the self-guided fit (choices 4 .. 22) the unit's bits are its own, written against the carried RefSgrXqd by
-          // lr_fit_kernel.hip: [frame][plane 0..2][unit] { bits, length }
-          const uint32_t *fc = P.lr_fit_code ? P.lr_fit_code + (((size_t)f * 3 + pl) * urows * ucols + ur * ucols + uc) * 2 : nullptr;
-          const int rf = (sgr_prev >> sh) & 3;
-          const int len = fc ? uni((int)fc[1]) : P.sgr_code_len[rf][ch - 4];
-          const unsigned long long bits = fc ? (unsigned long long)(uint32_t)uni((int)fc[0]) : P.sgr_code_bits[rf][ch - 4];
-          emit_bits(y, lane, bits, len);
-          if (!fc) sgr_prev = (sgr_prev & ~(3 << sh)) | ((ch - 3) << sh);
-        } else if (ch && P.lr_wfit_code) {
-          // every Wiener unit's bits are its own, written against the carried RefLrWiener by lr_wfit_kernel.hip:
-          // [frame][plane 0..2][unit] { bits 0-31, bits 32-63, length }
-          const uint32_t *wc = P.lr_wfit_code + (((size_t)f * 3 + pl) * urows * ucols + ur * ucols + uc) * 3;
-          const int len = uni((int)wc[2]);
-          const unsigned long long bits = (unsigned long long)(uint32_t)uni((int)wc[0]) | ((unsigned long long)(uint32_t)uni((int)wc[1]) << 32);
-          emit_bits(y, lane, bits, len);
-        } else if (ch) {
-          const int rf = (lr_prev >> sh) & 3;
-          const int len = pl ? P.lr_code_len_uv[rf][ch - 1] : P.lr_code_len[rf][ch - 1];
-          const unsigned long long bits = pl ? P.lr_code_bits_uv[rf][ch - 1] : P.lr_code_bits[rf][ch - 1];
-          emit_bits(y, lane, bits, len);
-          lr_prev = (lr_prev & ~(3 << sh)) | (ch << sh);
-        }
+    for (int z = 0, z_next; z < 64; z = z_next) {
+      z_next = z + 1;
+      const int bx = (((z >> 0) & 1) | ((z >> 1) & 2) | ((z >> 2) & 4)) << 3;
+      const int by = (((z >> 1) & 1) | ((z >> 2) & 2) | ((z >> 3) & 4)) << 3;
+      if (t.sb_y + by >= P.height || t.sb_x + bx >= P.width) continue;
+      const int b8x = bx >> 3, b8y = by >> 3;
+      // leaf containing this 8x8 unit (written by the recon kernel); it is coded at its origin only
+      const Av1miBlkInfo &bi = t.info(b8x, b8y);
+      const int leaf = uni(bi.bsl);
+      if ((bx | by) & ((1 << leaf) - 1)) continue;
+      z_next = z + (1 << (2 * (leaf - 3)));
+      const Neighbours nb = { read_neighbour(t, by + t.toy > 0, b8x, b8y - 1), read_neighbour(t, bx + t.tox > 0, b8x - 1, b8y) };
+      // nodes whose origin is (bx, by): every level above the leaf down to the leaf, largest first.
+      // A node at level l > leaf with this origin contains a smaller leaf, so it is a SPLIT node.
+      const int top = imin(6, __builtin_ctz((unsigned)(bx | by | 64)));
+#pragma nounroll
+      for (int bsl = top; bsl >= leaf; bsl--) sym_partition(y, nb, bsl, bsl > leaf, P.height - (t.sb_y + by), P.width - (t.sb_x + bx));
+      // the leaf's block (intra_frame_mode_info §5.11.7 / inter_frame_mode_info §5.11.18, then residual)
+      const int n = 1 << leaf;
+      const int ymode = uni(bi.ymode), skip = uni(bi.skip), ainfo = uni(bi.angle);
+      sym_wide(y, skip, CL::SKIP + (nb.u.skip + nb.l.skip) * 3, 2);
+      if (cdef_todo && !skip) { read_cdef(y, P, sb_of_chunk); cdef_todo = 0; }
+      if (dq_todo) {
+        dq_todo = 0;
+        // a skipped 64x64 block codes none: CurrentQIndex stays (its levels are all zero - no step is used)
+        if (!(leaf == 6 && skip)) read_delta_qindex<FULL>(y, uni(P.aq_map[sb_of_chunk]), cur_q);
+      }
+      int is_inter = 0;
+      if constexpr (INTER) {
+        is_inter = uni(bi.is_inter);
+        sym_is_inter(y, nb, is_inter);
+        if (is_inter) inter_block_mode_info(y, t, nb, bx, by, n);
+      }
+      if (!is_inter) intra_mode_info<FULL, INTER>(y, nb, leaf, ymode, ainfo);
+      if (skip) {
+        reset_block_context(t, lane, bx, by, n);
+      } else {
+        for (int pl = 0; pl < 3; pl++)
+          sym_coeffs<FULL>(y, t, pl, pl ? leaf - 1 : leaf, pl ? bx >> 3 : bx >> 2, pl ? by >> 3 : by >> 2, uni(bi.eob[pl]), ymode, pl == 0 && ((ainfo >> 3) & 1),
+                           is_inter, sb_levels + av1mi_levels_off(pl, bx, by));
       }
     }
-  }
-#pragma nounroll
-  // 8x8 units in Z (partition) order, from leaf origin to leaf origin: the 4^(leaf - 3) units of a leaf follow its origin in that
-  // order, so the walk steps over them (as a trip per unit, 60 of the 64 trips of a superblock of 32x32 leaves found nothing to do, at
-  // an LDS round trip each); a unit outside the frame advances by one
-  for (int z = 0, z_next; z < 64; z = z_next) {
-    z_next = z + 1;
-    const int bx = (((z >> 0) & 1) | ((z >> 1) & 2) | ((z >> 2) & 4)) << 3;
-    const int by = (((z >> 1) & 1) | ((z >> 2) & 2) | ((z >> 3) & 4)) << 3;
-    if (tg.sb_y + by >= P.height || tg.sb_x + bx >= P.width) continue;
-    const int b8x = bx >> 3, b8y = by >> 3;
-    // leaf containing this 8x8 unit (written by the recon kernel); it is coded at its origin only
-    const int leaf = uni(INFO(b8x, b8y).bsl);
-    if ((bx | by) & ((1 << leaf) - 1)) continue;
-    z_next = z + (1 << (2 * (leaf - 3)));
-    // nodes whose origin is (bx, by): every level above the leaf down to the leaf, largest first.
-    // A node at level l > leaf with this origin contains a smaller leaf, so it is a SPLIT node.
-    const int top = imin(6, __builtin_ctz((unsigned)(bx | by | 64)));
-#pragma nounroll
-    for (int bsl = top; bsl >= leaf; bsl--) {
-      const int n = 1 << bsl;
-      const bool split = bsl > leaf;
-      {
-        const int half = n >> 1;
-        const bool has_rows = tg.sb_y + by + half < P.height, has_cols = tg.sb_x + bx + half < P.width;
-        const int above = by + toy > 0 && uni(INFO(b8x, b8y - 1).bsl) < bsl;
-        const int left = bx + tox > 0 && uni(INFO(b8x - 1, b8y).bsl) < bsl;
-        const int off = CL::PARTITION + ((bsl - 3) * 4 + left * 2 + above) * 11;
-        if (has_rows && has_cols) {
-          sym_wide(y, lane, adapt, split ? 3 : 0, off, bsl == 3 ? 4 : 10);
-        } else if (has_cols) {
-          int p = icdf_prob(y, off, 2) + icdf_prob(y, off, 3);
-          if (bsl != 3) p += icdf_prob(y, off, 4) + icdf_prob(y, off, 6) + icdf_prob(y, off, 7) + icdf_prob(y, off, 9);
-          sym_bool(y, lane, 1, (uint32_t)uni(p));
-        } else if (has_rows) {
-          int p = icdf_prob(y, off, 1) + icdf_prob(y, off, 3);
-          if (bsl != 3) p += icdf_prob(y, off, 4) + icdf_prob(y, off, 5) + icdf_prob(y, off, 6) + icdf_prob(y, off, 8);
-          sym_bool(y, lane, 1, (uint32_t)uni(p));
-        }
-      }
-      if (split) continue;
-      {
-        const int ymode = uni(INFO(b8x, b8y).ymode), skip = uni(INFO(b8x, b8y).skip);
-        const int eob0 = uni(INFO(b8x, b8y).eob[0]), eob1 = uni(INFO(b8x, b8y).eob[1]), eob2 = uni(INFO(b8x, b8y).eob[2]);
-        const int avail_u = by + toy > 0, avail_l = bx + tox > 0;  // inside the tile
-        int sctx = 0;
-        if (avail_u) sctx += uni(INFO(b8x, b8y - 1).skip);
-        if (avail_l) sctx += uni(INFO(b8x - 1, b8y).skip);
-        sym_wide(y, lane, adapt, skip, CL::SKIP + sctx * 3, 2);
-        if (cdef_todo && !skip) {   // read_cdef (§5.11.56): cdef_bits literal bits, MSB first
-          const int ci = uni(P.cdef_idx[(size_t)f * sbs_per_frame + sb]);
-          emit_bits(y, lane, (unsigned)ci, P.cdef_bits);
-          cdef_todo = 0;
-        }
-        if (dq_todo) {   // read_delta_qindex (§5.11.46): delta_q_present = 1, delta_q_res = 2, i.e. steps of 4
-          dq_todo = 0;
-          if (!(bsl == 6 && skip)) {   // a skipped 64x64 block codes none: CurrentQIndex stays (its levels are all zero - no step is used)
-            const int qsb = uni(P.aq_map[(size_t)f * sbs_per_frame + sb]);
-            const int r = (qsb - cur_q) / 4, a = iabs(r);
-            sym_wide(y, lane, adapt, imin(a, 3), FULL ? CL::DELTA_Q : CC::DELTA_Q, 4);   // delta_q_abs
-            if (a >= 3) {   // delta_q_rem_bits L(3), delta_q_abs_bits L(rem_bits + 1)
-              const int nb = floor_log2((unsigned)(a - 1)), rest = a - 1 - (1 << nb);
-              emit_bits(y, lane, (unsigned)(((nb - 1) << nb) | rest), 3 + nb);
-            }
-            if (a) emit_bits(y, lane, (unsigned)(r < 0), 1);   // delta_q_sign_bit
-            cur_q = qsb;
-          }
-        }
-        const int is_inter = inter_frame ? uni(INFO(b8x, b8y).is_inter) : 0;
-        if (inter_frame) {
-          // inter_frame_mode_info (§5.11.18): is_inter, context from the neighbours' intra-ness
-          const int a_intra = avail_u ? !uni(INFO(b8x, b8y - 1).is_inter) : 0;
-          const int l_intra = avail_l ? !uni(INFO(b8x - 1, b8y).is_inter) : 0;
-          int ictx;
-          if (avail_u && avail_l) ictx = (l_intra && a_intra) ? 3 : ((l_intra || a_intra) ? 1 : 0);
-          else if (avail_u || avail_l) ictx = 2 * (avail_u ? a_intra : l_intra);
-          else ictx = 0;
-          sym_wide<1>(y, lane, adapt, is_inter, CL::IS_INTER + ictx * 3, 2);
-        }
-        if (is_inter) {
-          // inter_block_mode_info (§5.11.23): LAST_FRAME = single_ref_p1 0, p3 0, p4 0; then the cheapest name of
-          // the vector the recon kernel used: NEARESTMV, NEARMV, GLOBALMV, else NEWMV against the list's head
-          const int n_last = (avail_u ? uni(INFO(b8x, b8y - 1).is_inter) : 0) + (avail_l ? uni(INFO(b8x - 1, b8y).is_inter) : 0);
-          const int rctx = n_last > 0 ? 2 : 1;
-          sym_wide<1>(y, lane, adapt, 0, CL::SINGLE_REF + (0 * 3 + rctx) * 3, 2);
-          sym_wide<1>(y, lane, adapt, 0, CL::SINGLE_REF + (2 * 3 + rctx) * 3, 2);
-          sym_wide<1>(y, lane, adapt, 0, CL::SINGLE_REF + (3 * 3 + rctx) * 3, 2);
-          int new_ctx, ref_ctx;
-          const int num = build_mv_stack<TSB>(P, tg, (by + toy) >> 2, (bx + tox) >> 2, n >> 2, new_ctx, ref_ctx);
-          const int mvr = uni(INFO(b8x, b8y).mv_row), mvc = uni(INFO(b8x, b8y).mv_col);
-          const int s0r = uni(g_inter.stk_row[0]), s0c = uni(g_inter.stk_col[0]), s1r = uni(g_inter.stk_row[1]), s1c = uni(g_inter.stk_col[1]);
-          int mode;  // 0 NEARESTMV 1 NEARMV 2 GLOBALMV 3 NEWMV
-          if (num >= 1 && mvr == s0r && mvc == s0c) mode = 0;
-          else if (num >= 2 && mvr == s1r && mvc == s1c) mode = 1;
-          else if ((mvr | mvc) == 0) mode = 2;
-          else mode = 3;
-          sym_wide<1>(y, lane, adapt, mode != 3, CL::NEWMV + new_ctx * 3, 2);
-          if (mode != 3) {
-            sym_wide<1>(y, lane, adapt, mode != 2, CL::GLOBALMV + 0 * 3, 2);
-            if (mode != 2) sym_wide<1>(y, lane, adapt, mode == 1, CL::REFMV + ref_ctx * 3, 2);
-          }
-          if (mode == 3) { if (num > 1) sym_wide<1>(y, lane, adapt, 0, CL::DRL + drl_ctx(0) * 3, 2); }
-          else if (mode == 1) { if (num > 2) sym_wide<1>(y, lane, adapt, 0, CL::DRL + drl_ctx(1) * 3, 2); }
-          if (mode == 3) {
-            const int dr = mvr - s0r, dc = mvc - s0c;  // list head, or the zero global vector when the list is empty
-            sym_wide<1>(y, lane, adapt, (dr != 0 ? 2 : 0) | (dc != 0 ? 1 : 0), CL::MV_JOINT, 4);
-            if (dr) sym_mv_component(y, lane, adapt, 0, dr);
-            if (dc) sym_mv_component(y, lane, adapt, 1, dc);
-          }
-          {
-            const int n8 = n >> 3;
-            if (lane < n8 * n8) g_inter.newmv[(b8y + toy8 + lane / n8) * TW + b8x + tox8 + lane % n8] = (uint8_t)(mode == 3);
-          }
-        } else {
-          if (inter_frame) {
-            // intra_block_mode_info (§5.11.22): y_mode by block-size group
-            sym_wide<1>(y, lane, adapt, ymode, CL::IF_Y_MODE + (bsl <= 3 ? 1 : (bsl == 4 ? 2 : 3)) * 14, 13);
-          } else {
-            const int am = intra_mode_ctx(uni(avail_u ? INFO(b8x, b8y - 1).ymode : 0));
-            const int lm = intra_mode_ctx(uni(avail_l ? INFO(b8x - 1, b8y).ymode : 0));
-            sym_wide(y, lane, adapt, ymode, CL::KF_Y_MODE + (am * 5 + lm) * 14, 13);
-          }
-          // chroma: the luma mode at luma's angle delta, or chroma from luma (`angle` bits 4-9 / 10-15: the alphas, not both zero)
-          const int ainfo = uni(INFO(b8x, b8y).angle), adelta = ainfo & 7, cfl = (ainfo >> 4) != 0;
-          if (ymode >= 1 && ymode <= 8) sym_wide(y, lane, adapt, adelta, CL::ANGLE_DELTA + (ymode - 1) * 8, 7);
-          const int uvmode = cfl ? 13 : ymode;
-          const int cfl_allowed = n <= 32;
-          sym_wide(y, lane, adapt, uvmode, CL::UV_MODE + (cfl_allowed * 13 + ymode) * 15, cfl_allowed ? 14 : 13);
-          if (cfl) {   // read_cfl_alphas (spec 5.11.45)
-            const int au = ((ainfo >> 4) & 63) - 2 * ((ainfo >> 4) & 32), av = ((ainfo >> 10) & 63) - 2 * ((ainfo >> 10) & 32);   // 6-bit two's complement
-            const int su = au == 0 ? 0 : (au < 0 ? 1 : 2), sv = av == 0 ? 0 : (av < 0 ? 1 : 2);
-            sym_wide(y, lane, adapt, su * 3 + sv - 1, FULL ? CL::CFL_SIGN : CC::CFL_SIGN, 8);
-            if (su) sym_wide(y, lane, adapt, iabs(au) - 1, (FULL ? CL::CFL_ALPHA : CC::CFL_ALPHA) + ((su - 1) * 3 + sv) * 17, 16);
-            if (sv) sym_wide(y, lane, adapt, iabs(av) - 1, (FULL ? CL::CFL_ALPHA : CC::CFL_ALPHA) + ((sv - 1) * 3 + su) * 17, 16);
-          }
-          if (uvmode >= 1 && uvmode <= 8) sym_wide(y, lane, adapt, adelta, CL::ANGLE_DELTA + (uvmode - 1) * 8, 7);
-        }
-        const int w4 = n >> 2, w4c = imax(w4 >> 1, 1);
-        const int log2c = bsl - 1;
-        if (skip) {
-          __syncthreads();
-          if (lane < w4) { TI.above_lvl[0][((bx + tox) >> 2) + lane] = 0; TI.above_dc[0][((bx + tox) >> 2) + lane] = 0; S->left_lvl[0][(by >> 2) + lane] = 0; S->left_dc[0][(by >> 2) + lane] = 0; }
-          if (lane < w4c) {
-            for (int pl = 1; pl < 3; pl++) { TI.above_lvl[pl][((bx + tox) >> 3) + lane] = 0; TI.above_dc[pl][((bx + tox) >> 3) + lane] = 0; S->left_lvl[pl][(by >> 3) + lane] = 0; S->left_dc[pl][(by >> 3) + lane] = 0; }
-          }
-          __syncthreads();
-        } else {
-          for (int pl = 0; pl < 3; pl++) {
-            const int l2 = pl ? log2c : bsl;
-            const int16_t *lvp = sb_levels + av1mi_levels_off(pl, bx, by);
-            sym_coeffs<FULL, TSB>(y, lane, adapt, tg, pl, l2, pl ? bx >> 3 : bx >> 2, pl ? by >> 3 : by >> 2, pl == 0 ? eob0 : (pl == 1 ? eob1 : eob2), ymode | (pl == 0 ? ((uni(INFO(b8x, b8y).angle) >> 3) & 1) << 8 : 0), is_inter, lvp);
-          }
-        }
-      }
-    }
-  }
-#undef INFO
   }  // superblocks of the tile
   if (lane == 0) {
     stream_len[gt] = (uint32_t)y.pos;
     tile_combos[gt] = (uint32_t)((y.combo0 & 0xFF) | ((y.combo1 & 0xFF) << 8));
   }
 }
-#undef S
 
 // Tiles in the order of decreasing symbol-stream length: a counting sort in one workgroup (histogram over the length in LDS,
 // exclusive scan, scatter).  Which tile of a bucket comes first does not matter -

@@ -91,6 +91,14 @@ AV1MI_QUANT_FN int dequant(uint32_t lv, uint32_t q, int sgn, int lim) {
 // scan key of the position (the larger, the later in scan order) and its extent {row + 1, column + 1} as packed 16-bit values
 AV1MI_QUANT_FN int scan_key(int row, int col) { const int d = row + col; return (d << 6) | ((d & 1) ? row : col); }
 AV1MI_QUANT_FN uint32_t extent(int row, int col) { return ((uint32_t)(row + 1) << 16) | (uint32_t)(col + 1); }
+// index of the position in the default zig-zag scan of an n x n block: the positions on the anti-diagonals before its
+// own, then its place on that one (odd anti-diagonals run with increasing row, even ones with increasing column)
+AV1MI_QUANT_FN constexpr int scan_index(int row, int col, int n) {
+  const int d = row + col;
+  const int before = d < n ? (d * (d + 1)) >> 1 : n * n - (((2 * n - 1 - d) * (2 * n - d)) >> 1);
+  const int lo = d - (n - 1) > 0 ? d - (n - 1) : 0;
+  return before + ((d & 1) ? row - lo : col - lo);
+}
 
 }  // namespace av1mi_quant
 #endif

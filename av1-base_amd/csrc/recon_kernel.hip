@@ -319,15 +319,6 @@ template <> struct Tx1d<6> {
 };
 #endif
 
-// position of (row, col) in the default zig-zag scan of an n x n block:
-// odd anti-diagonals run with increasing row, even ones with increasing column.
-__device__ __forceinline__ int scan_index(int row, int col, int n) {
-  int d = row + col;
-  int before = d < n ? (d * (d + 1)) >> 1 : n * n - (((2 * n - 1 - d) * (2 * n - d)) >> 1);
-  int lo = d - (n - 1) > 0 ? d - (n - 1) : 0;
-  return before + ((d & 1) ? row - lo : col - lo);
-}
-
 // ---- intra edge filter helpers (spec 7.11.2.9 strength selection, 7.11.2.10 upsample selection; w = h = n)
 __device__ __forceinline__ int ef_strength(int wh, int type, int delta) {
   const int d = delta < 0 ? -delta : delta;
@@ -1348,7 +1339,7 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
   int eob = 0;
   if (my_key >= 0) {
     const int d0 = my_key >> 6, w = my_key & 63;
-    eob = scan_index((d0 & 1) ? w : d0 - w, (d0 & 1) ? d0 - w : w, CW) + 1;
+    eob = qp::scan_index((d0 & 1) ? w : d0 - w, (d0 & 1) ? d0 - w : w, CW) + 1;
   }
   // ---- the block's nonzero extent: rows / columns beyond it hold no level, so the inverse passes run the networks pruned for that many
   // inputs (txfm_gen.h: a rotation with a zero input is one multiply, sums with a zero are copies) and, in the matrix-core path, only

@@ -118,6 +118,13 @@ extern "C" void qp_keys(int cw, int *out) {
     for (int c = 0; c < cw; c++) out[r * cw + c] = qp::scan_key(r, c);
 }
 
+// scan indices of a cw x cw block, row-major; the formula is a constant expression too (the symbolizer builds its table from it)
+static_assert(qp::scan_index(0, 0, 4) == 0 && qp::scan_index(0, 1, 4) == 1 && qp::scan_index(1, 0, 4) == 2 && qp::scan_index(3, 3, 4) == 15, "zig-zag");
+extern "C" void qp_scan_indices(int cw, int *out) {
+  for (int r = 0; r < cw; r++)
+    for (int c = 0; c < cw; c++) out[r * cw + c] = qp::scan_index(r, c, cw);
+}
+
 #ifdef QUANT_PIECES_MAIN
 int main() {
   long bad = qp_positions(), capped_all = 0;

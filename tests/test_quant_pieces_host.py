@@ -28,6 +28,7 @@ def quant(cxx, tmp_path_factory):
     lib.qp_sweep.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_long)]
     lib.qp_positions.restype = C.c_long
     lib.qp_keys.argtypes = [C.c_int, C.c_void_p]
+    lib.qp_scan_indices.argtypes = [C.c_int, C.c_void_p]
     return lib
 
 
@@ -55,6 +56,10 @@ def test_scan_key_orders_positions_as_the_oracle_scan(quant, oracle, cw):
     scan = np.ctypeslib.as_array(L.av1o_default_scan({4: 2, 8: 3, 16: 4, 32: 5}[cw]), shape=(cw * cw,)).astype(np.int64)
     assert len(set(keys.tolist())) == cw * cw
     assert np.array_equal(np.argsort(keys, kind="stable"), scan)
+    # ... and scan_index names each position's place in that scan outright
+    idx = np.full(cw * cw, -1, np.int32)
+    quant.qp_scan_indices(cw, idx.ctypes.data)
+    assert np.array_equal(scan[idx], np.arange(cw * cw))
 
 
 def test_standalone_program(cxx, tmp_path):

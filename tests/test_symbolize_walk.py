@@ -4,8 +4,8 @@ reconstruction kernel (§4.2): bitstream, reconstruction and SSE equal the oracl
 
 Walk: fixed leaves of 8, 16, 32 and 64 samples (a step of 1, 4, 16 and 64 units) and the content-driven partition with leaves 8 .. 64
 on `mixed` - superblocks that are flat (one 64x64 leaf), and superblocks cut into 32x32, 16x16 and 8x8 leaves - at 64x64, 128x128, 72x88 and
-200x136 (superblocks with units outside the frame and leaves forced smaller at the edge), key-frame and IPPP chunks, 8 and 10 bit, one
-case with tiles of 2 x 2 superblocks.  Literal runs: noise at the lowest quantiser index (DC levels above 14: the Golomb tail) and
+200x136 (superblocks with units outside the frame and leaves forced smaller at the edge), key-frame and IPPP chunks, 8 and 10 bit, and
+tiles of 2 x 2 superblocks (the partition there with adaptive and with static CDFs).  Literal runs: noise at the lowest quantiser index (DC levels above 14: the Golomb tail) and
 `eob_ladder`, blocks whose spectrum ends at a chosen scan position (every eob_extra length); a flat frame at the highest (no run at all).
 tests/test_symbolize_walk_content.py asserts on the CPU that these inputs do what they are for.
 
@@ -113,7 +113,7 @@ def test_walk_equals_the_oracle(av1mi, ctx, oracle, w, h, tag, params, bd, keyin
     check(av1mi, ctx, oracle, case, walk_frames(case))
 
 
-@pytest.mark.parametrize("params", [dict(block_log2=4), dict(PART)], ids=["bs4", "part"])
+@pytest.mark.parametrize("params", [dict(block_log2=4), dict(PART), dict(PART, cdf_update=0)], ids=["bs4", "part", "part_static"])
 def test_walk_in_tiles_of_two_by_two_superblocks(av1mi, ctx, oracle, params):
     case = walk_case(200, 136, 10, 3, dict(params, tile_sb=2), "tile2")
     check(av1mi, ctx, oracle, case, walk_frames(case))
