@@ -9,8 +9,8 @@
 //   dequantiser ((level * q) & 0xFFFFFF) >> TSH with the sign, clamped to [-2^(7 + bd), 2^(7 + bd) - 1]   (normative)
 //   scan        by anti-diagonal d = row + col, odd ones by increasing row, even ones by increasing column: key = d << 6 | position.
 //               A lane that holds one row (one column) of the block has its largest key at its last nonzero column (row): with the
-//               other coordinate fixed the anti-diagonal grows with it.  So the loops track that one index and derive key and extent
-//               once from it.
+//               other coordinate fixed the anti-diagonal grows with it.  So the loops - flat or with quantiser matrices: the argument
+//               does not involve the step - track that one index and derive key and extent once from it.
 #ifndef AV1MI_QUANT_PIECES_H
 #define AV1MI_QUANT_PIECES_H
 #include <stdint.h>
@@ -69,9 +69,11 @@ AV1MI_QUANT_FN uint32_t level_abs(uint32_t av, uint32_t rnd, uint32_t recip) {
   return lv > LEVEL_CAP ? (uint32_t)LEVEL_CAP : lv;
 }
 
-// level * step for the dequantiser: both are below 2^24 (level <= 0x7FFF, step < 2^15 up to 10 bit).  The device form is the one the
-// loops had before this header; the device library's __umul24 is plain C, and with the step's range unknown to the compiler it ends in
-// v_mul_lo_u32 here (8 per chroma pair, behind `if (lv)`), not in the 24-bit multiply its name promises
+// level * step for the dequantiser: both are below 2^24, which is all the two forms need to agree.  level <= 0x7FFF; the step of the
+// flat quantiser is below 2^13 (ac_q at most 1828 at 8 bit, 7312 at 10), and a quantiser-matrix step Round2(q * Quantizer_Matrix, 5) with
+// matrix entries of 30 .. 242 is at most 13 824 at 8 bit and 55 297 at 10 - below 2^16 (tests/host/quant_pieces_host.cpp derives the bound
+// from the tables).  The device library's __umul24 is plain C, and with the step's range unknown to the compiler it ends in v_mul_lo_u32
+// here (8 per chroma pair, behind `if (lv)`), not in the 24-bit multiply its name promises
 AV1MI_QUANT_FN uint32_t q_mul24(uint32_t lv, uint32_t q) {
 #if defined(__HIP_DEVICE_COMPILE__)
   return __umul24(lv, q);
@@ -87,6 +89,29 @@ AV1MI_QUANT_FN int dequant(uint32_t lv, uint32_t q, int sgn, int lim) {
   d = with_sign((uint32_t)d, sgn);
   return d < -lim ? -lim : (d > lim - 1 ? lim - 1 : d);
 }
+
+// ---- the quantiser step of one coefficient: what every quantiser loop of the kernel calls.  mag = the level's magnitude (nonzero: the
+// position counts for the scan key and the extent), level = it with the coefficient's sign (what goes to the level buffer), deq = the
+// dequantised value the inverse transform takes
+struct Quantised { uint32_t mag; int level, deq; };
+// coefficient -> level, given the position's rounding term and reciprocal
+template <int TSH>
+AV1MI_QUANT_FN Quantised quantise(int v, uint32_t rnd, uint32_t recip) {
+  const int sgn = sign_mask(v);
+  const uint32_t lv = level_abs<TSH>(magnitude(v, sgn), rnd, recip);
+  return Quantised{ lv, with_sign(lv, sgn), 0 };
+}
+// coefficient -> level and dequantised value, given the position's (q, recip, rnd).  The dequantiser stays behind `if (mag)`: a column
+// with no level in any row costs the wave nothing
+template <int TSH>
+AV1MI_QUANT_FN Quantised quantise_dequantise(int v, uint32_t q, uint32_t recip, uint32_t rnd, int lim) {
+  Quantised z = quantise<TSH>(v, rnd, recip);
+  if (z.mag) z.deq = dequant<TSH>(z.mag, q, sign_mask(v), lim);
+  return z;
+}
+// a stored level -> dequantised value
+template <int TSH>
+AV1MI_QUANT_FN int dequant_level(int level, uint32_t q, int lim) { const int sgn = sign_mask(level); return dequant<TSH>(magnitude(level, sgn), q, sgn, lim); }
 
 // scan key of the position (the larger, the later in scan order) and its extent {row + 1, column + 1} as packed 16-bit values
 AV1MI_QUANT_FN int scan_key(int row, int col) { const int d = row + col; return (d << 6) | ((d & 1) ? row : col); }

@@ -56,6 +56,7 @@ static __device__ __forceinline__ int32_t av1_half_btf1(int32_t w, int32_t a) { 
 #include "fdct32_matrix.h"
 #include "intra_pieces.h"
 #include "quant_pieces.h"
+#include "recon_pieces.h"
 #ifndef AV1MI_CHROMA_HANDOVER
 #define AV1MI_CHROMA_HANDOVER 1
 #endif
@@ -247,6 +248,14 @@ __device__ __forceinline__ uint32_t pk_max(uint32_t a, uint32_t b) {
   typedef unsigned short pm2 __attribute__((ext_vector_type(2)));
   return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(pm2, a), __builtin_bit_cast(pm2, b)));
 }
+__device__ __forceinline__ int dpp_pk_max(int a, int b) { return (int)pk_max((uint32_t)a, (uint32_t)b); }
+// ... of every lane's pair along the wave
+__device__ __forceinline__ uint32_t wave_pk_max(uint32_t v) {
+  int x = (int)v;
+  AV1MI_DPP_SCAN(x, dpp_pk_max);
+  x = dpp_pk_max(x, __builtin_amdgcn_update_dpp(x, x, 0x143, 0xC, 0xF, false));
+  return (uint32_t)__builtin_amdgcn_readlane(x, 63);
+}
 __device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
 __device__ __forceinline__ int rshift_round(int v, int s) { return s ? (v + (1 << (s - 1))) >> s : v; }
 __device__ __forceinline__ int clamp_bits(int v, int bits) {
@@ -262,7 +271,6 @@ __device__ __forceinline__ void ident1d(int32_t *x) {
   for (int i = 0; i < (1 << LOG2N); i++) x[i] = LOG2N == 2 ? (x[i] * 5793 + 2048) >> 12 : (LOG2N == 3 ? x[i] * 2 : (x[i] * 11586 + 2048) >> 12);
 }
 template <int LOG2N> struct Tx1d;
-template <int V> struct NzTag { static constexpr int value = V; };
 template <> struct Tx1d<2> {
   template <int NZ> static __device__ __forceinline__ void inv_nz(int32_t *x, int t) { inv(x, t); }
   static __device__ __forceinline__ void iadst(int32_t *x) {
@@ -551,23 +559,13 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
     ii.ref = uniform_p(ii.ref); ii.mv_row = uniform_i(ii.mv_row); ii.mv_col = uniform_i(ii.mv_col); ii.sad_inter = uniform_i(ii.sad_inter);
     ii.is_inter = uniform_i(ii.is_inter); ii.pre_eob[0] = uniform_i(ii.pre_eob[0]); ii.pre_eob[1] = uniform_i(ii.pre_eob[1]); ii.pre_eob[2] = uniform_i(ii.pre_eob[2]);
   }
-  constexpr int N = 1 << LOG2N;
-  constexpr int ST = N + 1;
-  // MM: luma 32x32 blocks run the forward transform as a matrix product on the matrix cores: the residual rows are
-  // then read with 128-bit loads, so they lie 32 apart (16-byte aligned) instead of 33
-  constexpr bool MM = LOG2N == 5 && NPL == 1;
-  // VEC: block classes whose DC / V / H prediction and residual are written eight samples per lane and step (128-bit LDS accesses):
-  // luma 32x32 and the chroma 16x16 pair; their residual rows lie 32 / 24 apart (16-byte aligned)
-  constexpr bool VEC = MM || (LOG2N == 4 && NPL == 2);
-  constexpr int STR = MM ? 32 : (VEC ? 24 : ST);
-  constexpr int G = 64 / NPL;              // lanes per group
-  constexpr int PIXO = NPL == 1 ? 0 : (N > 16 ? 1024 : 512); // per-group offset inside srcblk / blkpix (NPL == 2: N <= 16, or 32 in the 64x64 build)
-  constexpr int SCRO = NPL == 1 ? 0 : (N > 16 ? 32 * 33 : 16 * 24);   // (16 rows of stride 24: see STR)
-  constexpr int EDGO = NPL == 1 ? 0 : AV1MI_EDGS;
+  namespace rp = av1mi_recon;
+  typedef rp::ItemGeom<LOG2N, NPL> GE;   // (recon_pieces.h has what the names stand for)
+  constexpr int N = GE::N, ST = GE::ST, STR = GE::STR, G = GE::G, PIXO = GE::PIXO, SCRO = GE::SCRO, EB = GE::EB, CW = GE::CW;
+  constexpr int SH0 = GE::SH0, SH1 = GE::SH1, SH2 = GE::SH2, RS = GE::RS, TSH = GE::TSH;
+  constexpr bool MM = GE::MM, VEC = GE::VEC, PVOK = GE::PVOK;
+  constexpr int EDGO = NPL == 1 ? 0 : AV1MI_EDGS;   // per-group offset inside the edge arrays
   static_assert(NPL == 1 ? 8 + 3 * N + 9 <= 2 * AV1MI_EDGS + 8 : 8 + 3 * N + 9 <= AV1MI_EDGS, "padded edge does not fit its array");
-  constexpr int EB = 8;   // index of element 0 inside a group's edge array
-  // PVOK: block classes with the piece-wise intra predictors (eight samples of a row per lane and step; below)
-  constexpr bool PVOK = N >= 8;
   const Av1miDevParams *P = cx.P;
   const int lane = cx.lane;
   const int grp = NPL == 1 ? 0 : lane >> 5, sl = NPL == 1 ? lane : lane & 31;
@@ -591,28 +589,41 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
   // row replicated, the reconstruction is stored only inside the plane
   const int pw_lim = (plane0 ? P->width >> 1 : P->width) - gx, ph_lim = (plane0 ? P->height >> 1 : P->height) - gy;   // samples of the block inside
   const bool overhang = pw_lim < N || ph_lim < N;
-  // PH == 2, motion compensation won: the block is already reconstructed in HBM - bottom row, right column and corners go to
-  // the line buffers, the decoded-block map and the eob are set, nothing else happens
-  auto inter_done = [&]() {
-    if constexpr (PH == 2) {
-      // the block's bottom row and right column come from the superblock's staged rows / columns (g_ws; the row index of a leaf's last
-      // row inside the frame is 7 mod 8 - 3 mod 4 in chroma - whatever its size, block sizes and coded frame sizes being multiples of 8)
-      const int rb = N - 1 < ph_lim ? N - 1 : ph_lim - 1, cb = N - 1 < pw_lim ? N - 1 : pw_lim - 1;   // last row / column inside
-      const uint16_t *srow = plane == 0 ? g_ws.row_y[(y0 + rb) >> 3] + x0 : g_ws.row_c[plane - 1][(y0 + rb) >> 2] + x0;
-      const uint16_t *scol = plane == 0 ? g_ws.col_y[(x0 + cb) >> 3] + y0 : g_ws.col_c[plane - 1][(x0 + cb) >> 2] + y0;
+  // the 16-byte pieces of the block's rows in the frame: 8 samples of 16 bits, 16 of 8 - where the block has that many and they are aligned
+  // (asked where the rows move, at the item's head and at its tail: held from one to the other the answer cost the kernels a register)
+  constexpr bool WIDE_OK = rp::RowPieces<PIX, N>::OK;
+  auto rows_wide = [&]() -> bool { return WIDE_OK && uniform_i(rp::rows_aligned<PIX>(overhang, gs, gx)); };
+  // ---- the finished block's hand-over to the neighbours to come: bottom row and right column (bottom(c) / right(r): the sample at that
+  // column / row) into the line buffers, the corners at every 8-aligned (chroma: 4-aligned) position of the two, the decoded-block map,
+  // the smooth-mode flag of the edge filter, the eob
+  auto hand_over = [&](auto bottom, auto right, int smooth, int eob_v) {
+    if constexpr (PH != 1) {
       if (sl < N) {
-        LN.above(plane)[lx + sl] = srow[sl < pw_lim ? sl : pw_lim - 1];
-        LN.left(plane)[ly + sl] = scol[sl < ph_lim ? sl : ph_lim - 1];
+        LN.above(plane)[lx + sl] = bottom(sl);
+        LN.left(plane)[ly + sl] = right(sl);
       }
       if (sl < (N >> cgs)) {
         const int j = sl + 1, q = (j << cgs) - 1;
-        LN.corner[plane][(ly + N) >> cgs][(lx >> cgs) + j] = srow[q < pw_lim ? q : pw_lim - 1];
-        LN.corner[plane][(ly >> cgs) + j][(lx + N) >> cgs] = scol[q < ph_lim ? q : ph_lim - 1];
+        LN.corner[plane][(ly + N) >> cgs][(lx >> cgs) + j] = bottom(q);
+        LN.corner[plane][(ly >> cgs) + j][(lx + N) >> cgs] = right(q);
       }
       if (lane < step) S->blkdec[pc][r4 + lane + 1] |= ((1u << step) - 1u) << (c4 + 1);   // (a lane per row of the block)
-      if (EXT && lane < (plane0 ? N >> 2 : N >> 3)) { LN.sm_above[pc][(lx >> (plane0 ? 2 : 3)) + lane] = 0; LN.sm_left[pc][(ly >> (plane0 ? 2 : 3)) + lane] = 0; }
-      if (sl == 0) eob_out[grp] = plane == 0 ? ii.pre_eob[0] : (plane == 1 ? ii.pre_eob[1] : ii.pre_eob[2]);   // (no dynamic index: the array stays in registers)
-      wave_sync();
+      if (EXT && lane < (plane0 ? N >> 2 : N >> 3)) { LN.sm_above[pc][(lx >> (plane0 ? 2 : 3)) + lane] = (uint8_t)smooth; LN.sm_left[pc][(ly >> (plane0 ? 2 : 3)) + lane] = (uint8_t)smooth; }
+    }
+    if (sl == 0) eob_out[grp] = eob_v;
+    wave_sync();
+  };
+  // PH == 2, motion compensation won: the block is already reconstructed in HBM - only the hand-over happens
+  auto inter_done = [&]() {
+    if constexpr (PH == 2) {
+      // the block's bottom row and right column come from the superblock's staged rows / columns (g_ws; the row index of a leaf's last
+      // row inside the frame is 7 mod 8 - 3 mod 4 in chroma - whatever its size, block sizes and coded frame sizes being multiples of 8);
+      // a block that overhangs the frame repeats its last sample inside
+      const int rb = N - 1 < ph_lim ? N - 1 : ph_lim - 1, cb = N - 1 < pw_lim ? N - 1 : pw_lim - 1;   // last row / column inside
+      const uint16_t *srow = plane == 0 ? g_ws.row_y[(y0 + rb) >> 3] + x0 : g_ws.row_c[plane - 1][(y0 + rb) >> 2] + x0;
+      const uint16_t *scol = plane == 0 ? g_ws.col_y[(x0 + cb) >> 3] + y0 : g_ws.col_c[plane - 1][(x0 + cb) >> 2] + y0;
+      hand_over([&](int c) { return srow[c < pw_lim ? c : pw_lim - 1]; }, [&](int r) { return scol[r < ph_lim ? r : ph_lim - 1]; }, 0,
+                plane == 0 ? ii.pre_eob[0] : (plane == 1 ? ii.pre_eob[1] : ii.pre_eob[2]));   // (no dynamic index: the array stays in registers)
     }
   };
   if constexpr (PH == 2) {
@@ -637,85 +648,26 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
       // (any 2-byte alignment: the vector points anywhere) instead of one clamped 2-byte load per sample
       const int ix = px0 >> 4, iy = py0 >> 4;
       if (!mc_in_lds && uniform_i(((px0 | py0) & 15) == 0 && ix >= 0 && iy >= 0 && ix + N - 1 <= last_x && iy + N - 1 <= last_y)) {
-        constexpr int CPR = N / 8;
-        typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-        typedef u4 u4_any __attribute__((aligned(2)));
-        const PIX *rp = static_cast<const PIX *>(ii.ref) + poff;
-        // (every load of the copy before its first LDS store - in one loop the compiler keeps source order, load -> wait -> store ->
-        // load ...: a memory round trip per piece; unconditional, the index clamped: a load under a condition is waited for on the spot)
-        constexpr int CNT = (N * CPR + G - 1) / G;
-        u4 pv[CNT];
-#pragma unroll
-        for (int k = 0; k < CNT; k++) {
-          const int q = sl + k * G < N * CPR ? sl + k * G : 0, r = q / CPR, c8 = q - r * CPR;
-          pv[k] = *reinterpret_cast<const u4_any *>(rp + (size_t)(iy + r) * gs + ix + 8 * c8);
-        }
-#pragma unroll
-        for (int k = 0; k < CNT; k++) {
-          const int q = sl + k * G, r = q / CPR, c8 = q - r * CPR;
-          if (q < N * CPR) *reinterpret_cast<u4 *>(&S->blkpix[po + r * N + 8 * c8]) = pv[k];
-        }
+        rp::rows_to_tile<N, G, false>(sl, static_cast<const PIX *>(ii.ref) + poff + (size_t)iy * gs + ix, gs, S->blkpix + po);
         mc_in_lds = true;
       }
     }
   }
-  // ---- source block -> LDS.  16-bit samples of a block inside the frame go as 16-byte pieces of a row (8 samples: two loads per
+  // ---- source block -> LDS.  A block inside the frame goes as 16-byte pieces of a row (8 samples of 16 bits: two loads per
   // lane for a 32x32 block instead of sixteen 2-byte ones, full cache lines; the stamps build had the sixteen at 25 - 30 % of a
-  // block pass); 8-bit samples, 4-wide blocks and blocks that overhang the frame edge (clamped coordinates) sample by sample.
+  // block pass); blocks narrower than a piece and blocks that overhang the frame edge (clamped coordinates) sample by sample.
   bool staged_src = false;
   if constexpr (PH == 2 && NPL == 1 && N >= 8) {
     if (plane0 == 0) {   // the walk's luma item: the superblock's source is staged (g_ws), edge samples already replicated
-      typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-      constexpr int CPR = N / 8;
-#pragma unroll
-      for (int q = sl; q < N * CPR; q += G) {
-        const int r = q / CPR, c8 = q - r * CPR;
-        *reinterpret_cast<u4 *>(&S->srcblk[r * N + 8 * c8]) = *reinterpret_cast<const u4 *>(&g_ws.src_y[(y0 + r) * 64 + x0 + 8 * c8]);
-      }
+      rp::rows_copy<N, G>(sl, &g_ws.src_y[y0 * 64 + x0], 64, S->srcblk, N);
       staged_src = true;
     }
   }
   if (!staged_src) {
     const PIX *pl = frame + poff;
-    bool wide = false;
-    if constexpr (sizeof(PIX) == 2 && N >= 8) {
-      wide = uniform_i(!overhang && ((gs | gx) & 7) == 0);
-      if (wide) {
-        constexpr int CPR = N / 8;   // 16-byte pieces per row
-        typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-        constexpr int CNT = (N * CPR + G - 1) / G;   // (all loads first: see the motion-compensated copy above)
-        u4 sv[CNT];
-#pragma unroll
-        for (int k = 0; k < CNT; k++) {
-          const int q = sl + k * G < N * CPR ? sl + k * G : 0, r = q / CPR, c8 = q - r * CPR;
-          sv[k] = *reinterpret_cast<const u4 *>(pl + (size_t)(gy + r) * gs + gx + 8 * c8);
-        }
-#pragma unroll
-        for (int k = 0; k < CNT; k++) {
-          const int q = sl + k * G, r = q / CPR, c8 = q - r * CPR;
-          if (q < N * CPR) *reinterpret_cast<u4 *>(&S->srcblk[po + r * N + 8 * c8]) = sv[k];
-        }
-      }
-    }
-    if constexpr (sizeof(PIX) == 1 && N >= 16) {   // 8-bit samples: 16 of them per 16-byte load, widened to the tile's 16-bit layout
-      wide = uniform_i(!overhang && ((gs | gx) & 15) == 0);
-      if (wide) {
-        constexpr int CPR = N / 16;
-        typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int q = sl; q < N * CPR; q += G) {
-          const int r = q / CPR, c16 = q - r * CPR;
-          const u4 v = *reinterpret_cast<const u4 *>(pl + (size_t)(gy + r) * gs + gx + 16 * c16);
-          u4 lo, hi;
-#pragma unroll
-          for (int k = 0; k < 2; k++) {
-            lo[2 * k] = __builtin_amdgcn_perm(0u, v[k], 0x0c010c00u); lo[2 * k + 1] = __builtin_amdgcn_perm(0u, v[k], 0x0c030c02u);
-            hi[2 * k] = __builtin_amdgcn_perm(0u, v[2 + k], 0x0c010c00u); hi[2 * k + 1] = __builtin_amdgcn_perm(0u, v[2 + k], 0x0c030c02u);
-          }
-          *reinterpret_cast<u4 *>(&S->srcblk[po + r * N + 16 * c16]) = lo;
-          *reinterpret_cast<u4 *>(&S->srcblk[po + r * N + 16 * c16 + 8]) = hi;
-        }
-      }
+    const bool wide = rows_wide();
+    if constexpr (WIDE_OK) {
+      if (wide) rp::rows_to_tile<N, G>(sl, pl + (size_t)gy * gs + gx, gs, S->srcblk + po);
     }
     if (!wide) {
 #pragma unroll   // all of the block's loads in flight together (N*N/G <= 16 per lane)
@@ -990,7 +942,8 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
           dir_edges(ang, EA, EL, up_a, up_l);
           int sad = 0;
           if (PVOK && !(up_a | up_l)) sad = pv_run(best_mode, ang, dx, dy, EA, EL, false);
-          else
+          else   // (the plain sample-by-sample SAD, as the candidate loop below has it: said twice on purpose - the two as one lambda cost the
+                 // P-frame chunk 1.0 % of its reconstruction stage, beyond the parent's spread, and the kernels of the optional tools two VGPRs)
 #pragma unroll 4
           for (int p = sl; p < N * N; p += G)
             sad += iabs((int)S->srcblk[po + p] - pred_pixel<LOG2N, WV>(best_mode, p >> LOG2N, p & (N - 1), dcv, ang, dx, dy, EA, EL, up_a, up_l));
@@ -1020,6 +973,8 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
     if constexpr (VEC) {
       // final trip of a luma 32x32 block / a chroma 16x16 pair predicted DC, V or H from the raw edges: prediction and residual eight
       // samples per lane and step (128-bit LDS accesses, packed 16-bit subtraction) instead of one
+      // (the packed residual is written out here and in the pass of its own below: as a shared piece of recon_pieces.h it took the walk's
+      // chroma item into the VGPRs that recon_sb_kernel keeps its own values in, and the P-frame kernels' register count rose by one)
       if (final_trip && !(INTER && ii.is_inter) && !fe && !use_cfl && (mode == DC_PRED || ang == 90 || ang == 180)) {
         typedef unsigned int u4 __attribute__((ext_vector_type(4)));
         typedef short s8 __attribute__((ext_vector_type(8)));
@@ -1057,9 +1012,9 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
         pv = S->blkpix[po + p];
       } else if (INTER && final_trip && ii.is_inter) {
         const int ss = plane0 > 0;
-        const PIX *rp = static_cast<const PIX *>(ii.ref) + poff;
+        const PIX *refp = static_cast<const PIX *>(ii.ref) + poff;
         // lastX / lastY of §7.11.3.3: the reference is clamped to the SIGNALLED frame size
-        pv = mc_sample<PIX>(rp, gs, ((P->true_w + ss) >> ss) - 1, ((P->true_h + ss) >> ss) - 1,
+        pv = mc_sample<PIX>(refp, gs, ((P->true_w + ss) >> ss) - 1, ((P->true_h + ss) >> ss) - 1,
                             ((gx + c) << 4) + ((2 * ii.mv_col) >> ss), ((gy + r) << 4) + ((2 * ii.mv_row) >> ss), (1 << bd) - 1);
       } else if (use_cfl) {
         pv = cfl_px(cfl_alpha, S->scratch[CFL_ACO + p]);
@@ -1113,12 +1068,6 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
     }
   }
   const int vt = idtx ? 3 : (txt & 1), ht = idtx ? 3 : ((txt >> 1) & 1);  // ADST_DCT(1): vertical ADST; DCT_ADST(2): horizontal ADST
-  // 64-point transforms (64x64 build): only the 32x32 low-frequency corner is coded (CW = 32) - the column pass keeps its first
-  // 32 outputs, the row pass runs on 32 lanes and keeps 32, the inverse passes take 32 inputs (zeros beyond) and give 64 outputs
-  constexpr int CW = N > 32 ? 32 : N;
-  constexpr int SH0 = LOG2N == 6 ? 0 : 2, SH1 = LOG2N == 2 ? 0 : (LOG2N == 3 ? 1 : (LOG2N == 4 ? 2 : (LOG2N == 5 ? 4 : 2))), SH2 = LOG2N == 6 ? 2 : 0;
-  constexpr int RS = LOG2N == 2 ? 0 : (LOG2N == 3 ? 1 : 2);
-  constexpr int TSH = LOG2N == 6 ? 2 : (LOG2N == 5 ? 1 : 0);  // dequant shift of the size class (§7.12.3)
   int32_t x[N];
   const bool tx_lane = sl < N, row_lane = sl < CW;
   int my_key = -1;  // (anti-diagonal << 6 | position inside it) of the last nonzero level in scan order
@@ -1196,10 +1145,9 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
             rnd = dc ? qp::dz_round(q, 0) : rnd;
           }
         }
-        const int sgn = qp::sign_mask(v);
-        const uint32_t lv = qp::level_abs<TSH>(qp::magnitude(v, sgn), rnd, recip);
-        lvl[row * 32 + col] = (int16_t)qp::with_sign(lv, sgn);
-        last = lv ? reg : last;
+        const qp::Quantised z = qp::quantise<TSH>(v, rnd, recip);
+        lvl[row * 32 + col] = (int16_t)z.level;
+        last = z.mag ? reg : last;
       }
       if (last >= 0) { const int row = qp::mm_row(last, mh); my_key = qp::scan_key(row, col); my_ext = qp::extent(row, col); }
     }
@@ -1247,6 +1195,7 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
           q = dc ? (uint32_t)P->dc_q : acq; recip = dc ? P->dc_recip : acr;
           rnd = qp::dz_pick(0, ta, tb, qp::dz_round(q, 0), qp::dz_round(q, 1), qp::dz_round(q, 2));
         }
+        // (here and in the flat loop the step is spelled out from its parts: through qp::quantise_dequantise the P-frame chunk lost 1.5 %)
         const int sgn = qp::sign_mask(v);
         const uint32_t lv = qp::level_abs<TSH>(qp::magnitude(v, sgn), rnd, recip);
         lvl[row * CW + jb + j] = (int16_t)qp::with_sign(lv, sgn);
@@ -1265,17 +1214,14 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
   #pragma unroll
       for (int j = 0; j < N; j++) x[j] = S->scratch[so + sl * ST + j];
       Tx1d<LOG2N>::fwd(x, ht);
-      const int row = sl;
+      const int row = sl, lim = 1 << (7 + bd);
+      int lastj = -1;   // (of the scan key only the last nonzero column is tracked: the key grows with the column inside a row)
       if constexpr (!QM) {
         // One step for every AC coefficient, another for DC: the dead-zone class of a coefficient is two compares against per-lane
-        // thresholds (no divergent three-way branch), signs go through the sign mask, the dequantiser's product fits a 24-bit
-        // multiply (level < 2^15, step < 2^15), and of the scan key only the last nonzero column is tracked (the key grows with the
-        // column inside a row).  The dequantiser stays behind `if (lv)`: a column with no level in any row costs the wave nothing.
+        // thresholds (no divergent three-way branch); the step itself is quant_pieces.h's.
         const uint32_t acq = (uint32_t)P->ac_q, acr = P->ac_recip;
         const uint32_t r0 = qp::dz_round(acq, 0), r1 = qp::dz_round(acq, 1), r2 = qp::dz_round(acq, 2);
         const int ta = qp::dz_ta(row, CW), tb = qp::dz_tb(row, CW);   // column j is in dead-zone class 0 below ta, 1 below tb, else 2
-        const int lim = 1 << (7 + bd);
-        int lastj = -1;
   #pragma unroll
         for (int j = 0; j < CW; j++) {
           const int v = rshift_round(x[j], SH2);
@@ -1295,42 +1241,28 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
           }
           x[j] = d;
         }
-        if (lastj >= 0) { my_key = qp::scan_key(row, lastj); my_ext = qp::extent(row, lastj); }
       } else {
-      constexpr int QM_OFF = LOG2N == 2 ? AV1MI_QM_4X4 : (LOG2N == 3 ? AV1MI_QM_8X8 : (LOG2N == 4 ? AV1MI_QM_16X16 : AV1MI_QM_32X32));
-      const QmTab tab = qm_table(P) + (pc ? AV1MI_QM_PLANE : 0) + QM_OFF + row;
-      // (the flat quantiser's four values as scalars first: selecting between a field of the parameter block and a table entry made the
-      // compiler select between two ADDRESSES in different address spaces - FLAT loads)
-      const uint32_t dcq = (uint32_t)P->dc_q, acq = (uint32_t)P->ac_q, dcr = P->dc_recip, acr = P->ac_recip;
-  #pragma unroll
-      for (int j = 0; j < CW; j++) {
-        const int v = rshift_round(x[j], SH2);
-        uint32_t q = tab[j * CW].q, recip = tab[j * CW].recip;
-        if (idtx) {   // the matrices apply to the 2-D DCT / ADST types only (spec 7.12.3: PlaneTxType < IDTX)
-          const bool dc = (row | j) == 0;
-          q = dc ? dcq : acq; recip = dc ? dcr : acr;
+        constexpr int QM_OFF = LOG2N == 2 ? AV1MI_QM_4X4 : (LOG2N == 3 ? AV1MI_QM_8X8 : (LOG2N == 4 ? AV1MI_QM_16X16 : AV1MI_QM_32X32));
+        const QmTab tab = qm_table(P) + (pc ? AV1MI_QM_PLANE : 0) + QM_OFF + row;
+        // (the flat quantiser's four values as scalars first: selecting between a field of the parameter block and a table entry made the
+        // compiler select between two ADDRESSES in different address spaces - FLAT loads)
+        const uint32_t dcq = (uint32_t)P->dc_q, acq = (uint32_t)P->ac_q, dcr = P->dc_recip, acr = P->ac_recip;
+    #pragma unroll
+        for (int j = 0; j < CW; j++) {
+          const int v = rshift_round(x[j], SH2);
+          uint32_t q = tab[j * CW].q, recip = tab[j * CW].recip;
+          if (idtx) {   // the matrices apply to the 2-D DCT / ADST types only (spec 7.12.3: PlaneTxType < IDTX)
+            const bool dc = (row | j) == 0;
+            q = dc ? dcq : acq; recip = dc ? dcr : acr;
+          }
+          // frequency-dependent dead zone: 3q/8 for row+col < n/4, q/4 below n/2, q/8 above (n = the coded width)
+          const qp::Quantised z = qp::quantise_dequantise<TSH>(v, q, recip, qp::dz_round(q, qp::dz_class(row, j, CW)), lim);
+          lvl[row * CW + j] = (int16_t)z.level;
+          if (z.mag) lastj = j;
+          x[j] = z.deq;
         }
-        // frequency-dependent dead zone: 3q/8 for row+col < n/4, q/4 below n/2, q/8 above (n = the coded width)
-        const int d0 = row + j;
-        const uint32_t rnd = d0 < (CW >> 2) ? (3 * q) >> 3 : (d0 < (CW >> 1) ? (q >> 2) : (q >> 3));
-        const uint32_t a = ((uint32_t)iabs(v) << TSH) + rnd;
-        uint32_t lv = __umulhi(a, recip);
-        if (lv > 0x7FFF) lv = 0x7FFF;
-        lvl[row * CW + j] = (int16_t)(v < 0 ? -(int)lv : (int)lv);
-        int d = 0;
-        if (lv) {
-          // scan order: by anti-diagonal, odd ones by increasing row, even ones by increasing column
-          const int key = (d0 << 6) | ((d0 & 1) ? row : j);
-          my_key = key > my_key ? key : my_key;
-          my_ext = ((uint32_t)(row + 1) << 16) | (uint32_t)(j + 1);   // (columns grow with j)
-          d = (int)(((uint32_t)lv * q) & 0xFFFFFF) >> TSH;
-          const int lim = 1 << (7 + bd);
-          d = v < 0 ? -d : d;
-          d = d < -lim ? -lim : (d > lim - 1 ? lim - 1 : d);
-        }
-        x[j] = d;
       }
-      }
+      if (lastj >= 0) { my_key = qp::scan_key(row, lastj); my_ext = qp::extent(row, lastj); }
   #pragma unroll
       for (int j = CW; j < N; j++) x[j] = 0;
     }
@@ -1347,21 +1279,9 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
   // (both planes of a chroma pair): ext = {columns, rows} as packed 16-bit maxima.
   int nzc, nzr;
   {
-    uint32_t ext = my_ext;
-    ext = pk_max(ext, (uint32_t)__builtin_amdgcn_update_dpp((int)ext, (int)ext, 0x111, 0xF, 0xF, false));
-    ext = pk_max(ext, (uint32_t)__builtin_amdgcn_update_dpp((int)ext, (int)ext, 0x112, 0xF, 0xF, false));
-    ext = pk_max(ext, (uint32_t)__builtin_amdgcn_update_dpp((int)ext, (int)ext, 0x114, 0xF, 0xF, false));
-    ext = pk_max(ext, (uint32_t)__builtin_amdgcn_update_dpp((int)ext, (int)ext, 0x118, 0xF, 0xF, false));
-    ext = pk_max(ext, (uint32_t)__builtin_amdgcn_update_dpp((int)ext, (int)ext, 0x142, 0xA, 0xF, false));
-    ext = pk_max(ext, (uint32_t)__builtin_amdgcn_update_dpp((int)ext, (int)ext, 0x143, 0xC, 0xF, false));
-    ext = (uint32_t)__builtin_amdgcn_readlane((int)ext, 63);
+    const uint32_t ext = wave_pk_max(my_ext);
     const int ec = (int)(ext & 0xFFFF), er = (int)(ext >> 16);
-    // the classes this size has pruned networks for (64 = the full network)
-    auto cls = [](int v) { return LOG2N >= 5 ? (v <= 8 ? 8 : (v <= 16 ? 16 : 64)) : (LOG2N == 4 ? (v <= 4 ? 4 : (v <= 8 ? 8 : 64)) : (LOG2N == 3 && v <= 4 ? 4 : 64)); };
-    nzc = cls(ec); nzr = cls(er);
-#ifdef AV1MI_NO_PRUNE
-    nzc = nzr = 64;
-#endif
+    nzc = rp::nz_class<LOG2N>(ec); nzr = rp::nz_class<LOG2N>(er);
   }
   // row pass of one class: [matrix-core path: the row's levels back from LDS through the normative dequantiser (spec 7.12.3),] inverse rows
   auto row_pass = [&](auto tag) {
@@ -1380,10 +1300,7 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
           uint32_t q;
           if constexpr (QM) q = tab[j * 32].q;
           else q = (row | j) == 0 ? (uint32_t)P->dc_q : (uint32_t)P->ac_q;
-          const int sgn = lvs >> 31;
-          int d = (int)((__umul24((uint32_t)((lvs ^ sgn) - sgn), q) & 0xFFFFFF) >> TSH);
-          d = (d ^ sgn) - sgn;
-          x[j] = d < -lim ? -lim : (d > lim - 1 ? lim - 1 : d);
+          x[j] = qp::dequant_level<TSH>(lvs, q, lim);
         }
       }
     }
@@ -1394,13 +1311,7 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
     for (int j = 0; j < N; j++) S->scratch[so + sl * ST + j] = (int16_t)clamp_bits(rshift_round(x[j], RS), bd + 6 > 16 ? bd + 6 : 16);
   };
   if (row_lane && eob && sl < nzr) {   // (rows beyond the extent are all zero: the column pass does not read them)
-#ifndef AV1MI_NO_PRUNE   /* (A/B switch: the build without the pruned networks) */
-    if (LOG2N >= 4 && nzc == 8) row_pass(NzTag<8>{});
-    else if (LOG2N >= 5 && nzc == 16) row_pass(NzTag<16>{});
-    else if ((LOG2N == 3 || LOG2N == 4) && nzc == 4) row_pass(NzTag<4>{});
-    else
-#endif
-    row_pass(NzTag<64>{});
+    rp::dispatch_nz<LOG2N>(nzc, row_pass);
   }
   wave_sync();
   STAMP(4);   // forward rows, quantiser, dequantiser, eob, inverse rows
@@ -1416,15 +1327,7 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
       S->blkpix[po + i * N + sl] = (uint16_t)(v < 0 ? 0 : (v > maxv ? maxv : v));
     }
   };
-  if (tx_lane && eob) {
-#ifndef AV1MI_NO_PRUNE
-    if (LOG2N >= 4 && nzr == 8) col_pass(NzTag<8>{});
-    else if (LOG2N >= 5 && nzr == 16) col_pass(NzTag<16>{});
-    else if ((LOG2N == 3 || LOG2N == 4) && nzr == 4) col_pass(NzTag<4>{});
-    else
-#endif
-    col_pass(NzTag<64>{});
-  }
+  if (tx_lane && eob) rp::dispatch_nz<LOG2N>(nzr, col_pass);
   if (eob) {  // levels out (32-bit words, coalesced inside the group)
     // (16 bytes = 8 levels per store: the block's area of the level buffer is 32-byte aligned, av1mi_levels_off)
     constexpr int PIECES = CW * CW / 8;
@@ -1438,61 +1341,20 @@ __device__ __attribute__((noinline)) int tx_item(SbCtx cx, const PIX *frame, PIX
   // ---- reconstruction -> HBM (coalesced rows) and -> line buffers for the neighbours to come
   {
     PIX *pl = rec_frame + poff;
-    bool wide_out = false;
-    if constexpr (sizeof(PIX) == 2 && N >= 8) {   // 16-byte pieces of the rows, as the source came in
-      wide_out = uniform_i(!overhang && ((gs | gx) & 7) == 0);
-      if (wide_out) {
-        constexpr int CPR = N / 8;
-        typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int q = sl; q < N * CPR; q += G) {
-          const int r = q / CPR, c8 = q - r * CPR;
-          *reinterpret_cast<u4 *>(pl + (size_t)(gy + r) * gs + gx + 8 * c8) = *reinterpret_cast<const u4 *>(&S->blkpix[po + r * N + 8 * c8]);
-        }
-      }
+    const bool wide = rows_wide();
+    if constexpr (WIDE_OK) {   // 16-byte pieces of the rows, as the source came in
+      if (wide) rp::tile_to_rows<N, G>(sl, S->blkpix + po, pl + (size_t)gy * gs + gx, gs);
     }
-    if constexpr (sizeof(PIX) == 1 && N >= 16) {   // 8-bit samples: 16 per 16-byte store
-      wide_out = uniform_i(!overhang && ((gs | gx) & 15) == 0);
-      if (wide_out) {
-        constexpr int CPR = N / 16;
-        typedef unsigned int u4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int q = sl; q < N * CPR; q += G) {
-          const int r = q / CPR, c16 = q - r * CPR;
-          const u4 lo = *reinterpret_cast<const u4 *>(&S->blkpix[po + r * N + 16 * c16]), hi = *reinterpret_cast<const u4 *>(&S->blkpix[po + r * N + 16 * c16 + 8]);
-          u4 v;
-          v[0] = __builtin_amdgcn_perm(lo[1], lo[0], 0x06040200u); v[1] = __builtin_amdgcn_perm(lo[3], lo[2], 0x06040200u);
-          v[2] = __builtin_amdgcn_perm(hi[1], hi[0], 0x06040200u); v[3] = __builtin_amdgcn_perm(hi[3], hi[2], 0x06040200u);
-          *reinterpret_cast<u4 *>(pl + (size_t)(gy + r) * gs + gx + 16 * c16) = v;
-        }
-      }
-    }
-    if (!wide_out) {
+    if (!wide) {
 #pragma unroll 4
       for (int p = sl; p < N * N; p += G) {
         const int r = p >> LOG2N, c = p & (N - 1);
         if (!overhang || (r < ph_lim && c < pw_lim)) pl[(size_t)(gy + r) * gs + gx + c] = (PIX)S->blkpix[po + p];
       }
     }
-    if constexpr (PH != 1) {
-      if (sl < N) {
-        LN.above(plane)[lx + sl] = S->blkpix[po + (N - 1) * N + sl];
-        LN.left(plane)[ly + sl] = S->blkpix[po + sl * N + (N - 1)];
-      }
-      if (sl < (N >> cgs)) {  // corners at every 8-aligned (chroma: 4-aligned) position of the bottom row and right column
-        const int j = sl + 1, q = (j << cgs) - 1;
-        LN.corner[plane][(ly + N) >> cgs][(lx >> cgs) + j] = S->blkpix[po + (N - 1) * N + q];
-        LN.corner[plane][(ly >> cgs) + j][(lx + N) >> cgs] = S->blkpix[po + q * N + (N - 1)];
-      }
-      if (lane < step) S->blkdec[pc][r4 + lane + 1] |= ((1u << step) - 1u) << (c4 + 1);   // (a lane per row of the block)
-      if (EXT && lane < (plane0 ? N >> 2 : N >> 3)) {
-        const uint8_t smf = (uint8_t)(!(INTER && ii.is_inter) && best_mode >= SMOOTH_PRED && best_mode <= SMOOTH_H_PRED);
-        LN.sm_above[pc][(lx >> (plane0 ? 2 : 3)) + lane] = smf; LN.sm_left[pc][(ly >> (plane0 ? 2 : 3)) + lane] = smf;
-      }
-    }
   }
-  if (sl == 0) eob_out[grp] = eob;
-  wave_sync();
+  hand_over([&](int c) { return S->blkpix[po + (N - 1) * N + c]; }, [&](int r) { return S->blkpix[po + r * N + (N - 1)]; },
+            !(INTER && ii.is_inter) && best_mode >= SMOOTH_PRED && best_mode <= SMOOTH_H_PRED, eob);
   STAMP(6);   // reconstruction -> HBM, line buffers, decoded-block map
   if constexpr (EXT && NPL == 1 && !INTER && PH == 0 && N >= 8 && N <= 32) {
     // chroma from luma: the block's reconstructed luma, subsampled 2x2 (sum of four << 1 = Q3) and centred on its rounded

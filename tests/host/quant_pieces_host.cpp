@@ -44,14 +44,22 @@ static long sweep_t(int bd, uint32_t q, int cls, long *capped) {
   for (long k = -65536 - 2 * NE; k <= 65536; k++) {
     int32_t v = (int32_t)k;
     if (k < -65536) { const long e = -65537 - k; v = (e & 1) ? -extremes[e >> 1] : extremes[e >> 1]; }
-    const int sgn = qp::sign_mask(v);
-    const uint32_t lv = qp::level_abs<TSH>(qp::magnitude(v, sgn), rnd, recip);
-    const int32_t level = qp::with_sign(lv, sgn), want = ref_level(v, q, rnd, TSH);
-    bad += level != want || (int16_t)level != want;
-    bad += (lv ? qp::dequant<TSH>(lv, q, sgn, lim) : 0) != ref_dequant(want, q, TSH, bd);
-    *capped += lv == qp::LEVEL_CAP;
+    // the unified step - what every quantiser loop of the kernel calls - and its two halves on their own: the level alone (the matrix-core
+    // loop) and the stored level through the dequantiser (the row pass that follows it)
+    const qp::Quantised z = qp::quantise_dequantise<TSH>(v, q, recip, rnd, lim), z0 = qp::quantise<TSH>(v, rnd, recip);
+    const int32_t want = ref_level(v, q, rnd, TSH), want_d = ref_dequant(want, q, TSH, bd);
+    bad += z.level != want || (int16_t)z.level != want || z.mag != (uint32_t)llabs((long long)want);
+    bad += z.deq != want_d;
+    bad += z0.level != want || z0.mag != z.mag || z0.deq != 0;
+    bad += qp::dequant_level<TSH>((int16_t)z.level, q, lim) != want_d;
+    *capped += z.mag == qp::LEVEL_CAP;
   }
   return bad;
+}
+
+static long sweep(int log2n, int bd, uint32_t q, int cls, long *capped) {
+  const int sh = ref_tsh(log2n);
+  return sh == 0 ? sweep_t<0>(bd, q, cls, capped) : (sh == 1 ? sweep_t<1>(bd, q, cls, capped) : sweep_t<2>(bd, q, cls, capped));
 }
 
 // every coefficient value in +-2^16 and the extremes, both steps of the quantiser index, the three dead-zone classes: mismatches
@@ -60,10 +68,47 @@ extern "C" long qp_sweep(int log2n, int bd, int qidx, long *capped) {
   long bad = 0;
   *capped = 0;
   for (int s = 0; s < 2; s++)
-    for (int cls = 0; cls < 3; cls++) {
-      const int sh = ref_tsh(log2n);
-      bad += sh == 0 ? sweep_t<0>(bd, qs[s], cls, capped) : (sh == 1 ? sweep_t<1>(bd, qs[s], cls, capped) : sweep_t<2>(bd, qs[s], cls, capped));
-    }
+    for (int cls = 0; cls < 3; cls++) bad += sweep(log2n, bd, qs[s], cls, capped);
+  return bad;
+}
+
+// ---- quantiser-matrix steps: Round2(q * Quantizer_Matrix, 5) as the context's table holds them (av1mi_syntax.cpp, make_qm_table)
+static uint32_t qm_step(uint32_t q, uint32_t entry) { return (q * entry + 16) >> 5; }
+static void qm_entry_range(uint32_t *lo, uint32_t *hi) {
+  *lo = 255; *hi = 0;
+  for (int l = 0; l < 15; l++)
+    for (int pt = 0; pt < 2; pt++)
+      for (int i = 0; i < 1360; i++) {
+        const uint32_t e = av1_qm_iwt[l][pt][i];
+        *lo = e < *lo ? e : *lo; *hi = e > *hi ? e : *hi;
+      }
+}
+// the largest step a table can hold at the bit depth (any matrix level, plane type and position, the highest quantiser index), and the
+// range of the matrix entries: what q_mul24's "both operands below 2^24" rests on
+extern "C" uint32_t qp_qm_max_step(int bd, uint32_t *entry_lo, uint32_t *entry_hi) {
+  qm_entry_range(entry_lo, entry_hi);
+  uint32_t top = 0;
+  for (int qidx = 0; qidx < 256; qidx++)
+    for (int l = 0; l < 15; l++)
+      for (int pt = 0; pt < 2; pt++)
+        for (int i = 0; i < 1360; i++) {
+          const bool dc = i == 0 || i == 16 || i == 80 || i == 336;   // the first position of each size
+          const uint32_t q = (uint32_t)(bd == 8 ? (dc ? av1_dc_q8 : av1_ac_q8)[qidx] : (dc ? av1_dc_q10 : av1_ac_q10)[qidx]);
+          const uint32_t st = qm_step(q, av1_qm_iwt[l][pt][i]);
+          top = st > top ? st : top;
+        }
+  return top;
+}
+// the sweep of qp_sweep at the extreme steps of the quantiser-matrix tables: smallest and largest matrix entry on both steps of the index
+extern "C" long qp_sweep_qm(int log2n, int bd, int qidx, long *capped) {
+  const uint32_t qs[2] = { (uint32_t)(bd == 8 ? av1_dc_q8[qidx] : av1_dc_q10[qidx]), (uint32_t)(bd == 8 ? av1_ac_q8[qidx] : av1_ac_q10[qidx]) };
+  uint32_t e[2];
+  qm_entry_range(&e[0], &e[1]);
+  long bad = 0;
+  *capped = 0;
+  for (int s = 0; s < 2; s++)
+    for (int k = 0; k < 2; k++)
+      for (int cls = 0; cls < 3; cls++) bad += sweep(log2n, bd, qm_step(qs[s], e[k]), cls, capped);
   return bad;
 }
 
@@ -135,8 +180,11 @@ int main() {
         long capped = 0;
         bad += qp_sweep(log2n, bd, qidx[k], &capped);
         capped_all += capped;
+        if (log2n <= 5) { bad += qp_sweep_qm(log2n, bd, qidx[k], &capped); capped_all += capped; }   // (the matrices stop at 32x32)
       }
   if (!capped_all) bad++;
+  uint32_t lo, hi;
+  bad += qp_qm_max_step(8, &lo, &hi) >= (1u << 16) || qp_qm_max_step(10, &lo, &hi) >= (1u << 16);
   printf("quant_pieces: %ld mismatches\n", bad);
   return bad != 0;
 }

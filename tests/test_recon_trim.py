@@ -11,7 +11,11 @@ one vertical cosine of frequency k - an impulse at coefficient row k, k stepping
 so that the last nonzero coefficient falls in each of the 16 register rows of both wave halves - and per 16x16 chroma block a horizontal
 one, so that a chroma row's last level falls in every column of both lanes that share the row (tests/test_recon_trim_content.py
 asserts on the CPU where the levels fall); and `synthclip v1`.  One case with
-quantiser matrices (that instantiation keeps its table reads) and one with 64x64 leaf blocks."""
+quantiser matrices (that instantiation keeps its table reads) and one with 64x64 leaf blocks.
+
+The item's shared pieces (recon_pieces.h, the one quantiser step of quant_pieces.h) run in every case here; two of their branches no
+other case reached have cases of their own below: the hand-over of a motion-compensated block that overhangs the frame (the staged
+rows' clamps), and the quantiser-matrix row loop on blocks that took the identity transform."""
 import numpy as np
 import pytest
 
@@ -101,3 +105,44 @@ def test_untouched_instantiations_equal_the_oracle(av1mi, ctx, oracle, params):
     for w, h, bd in ((96, 80, 10), (128, 64, 8)):
         case = dict(name="synth_%dx%d_%db_%s" % (w, h, bd, sorted(params)[0]), w=w, h=h, bd=bd, n=N, params=dict(params))
         check(av1mi, ctx, oracle, case, E.synth(oracle, w, h, bd, N, 1080))
+
+
+def leaves32_overhanging(w, h):
+    """the 32x32 leaves that cross the frame's edge: a node is split where half of it or more lies outside (av1mi_dev.h, av1mi_node_split)"""
+    return [(x, y) for y in range(0, h, 32) for x in range(0, w, 32) if x + 16 < w and y + 16 < h and (x + 32 > w or y + 32 > h)]
+
+
+@pytest.mark.parametrize("bd", [10, 8])
+@pytest.mark.parametrize("w,h", [(88, 88), (96, 80)])
+def test_inter_hand_over_of_overhanging_blocks_equals_the_oracle(av1mi, ctx, oracle, w, h, bd):
+    """two identical frames, the second a P frame of 32x32 leaves: motion compensation wins everywhere, so at 88x88 the blocks that
+    overhang the right edge, the bottom edge and - the corner block - both hand their bottom row and right column over from the staged
+    rows of the inter version, clamped to the last sample inside, in luma and, following it, in both chroma planes.  (88 is no multiple
+    of 16 either: the 8-bit rows take the sample-by-sample copies.)  96x80 is the counterpart without a clamp: exactly half of its
+    bottom 32x32 nodes lies inside, so they are split and nothing overhangs."""
+    f = E.synth(oracle, w, h, bd, 1, 1080)[0]
+    frames = [f, [pl.copy() for pl in f]]
+    case = dict(name="static_%dx%d_%db" % (w, h, bd), w=w, h=h, bd=bd, n=N, params=dict(keyint=240, block_log2=5))
+    # on the CPU first: the oracle codes EVERY block of the P frame as an inter block, the overhanging ones of each plane among them
+    # (a chroma block follows its luma block) - otherwise the case proves nothing
+    over = leaves32_overhanging(w, h)
+    assert len(over) == (5 if (w, h) == (88, 88) else 0) and ((64, 64) in over) == ((w, h) == (88, 88))
+    _, rec0, _ = oracle.encode_frame(E.oracle_config(oracle, case, 0), frames[0], with_seq_hdr=True, ref=None, prev_src=None)
+    _, _, st = oracle.encode_frame(E.oracle_config(oracle, case, 1), frames[1], with_seq_hdr=False, ref=rec0, prev_src=frames[0])
+    assert st.n_inter_blocks == st.n_blocks == (9 if (w, h) == (88, 88) else 12)
+    check(av1mi, ctx, oracle, case, frames)
+
+
+@pytest.mark.parametrize("bd", [10, 8])
+@pytest.mark.parametrize("bs", [4, 3])
+def test_quantiser_matrices_with_identity_transform_search_equal_the_oracle(av1mi, ctx, oracle, bs, bd):
+    """posterised content (flat areas, sharp edges: sparse residuals) with tx_search under quantiser matrices: the blocks that take the
+    identity transform are quantised with the flat steps inside the quantiser-matrix row loop (spec 7.12.3: PlaneTxType < IDTX)"""
+    w = h = 64
+    shift = bd - 3
+    frames = [[(pl >> shift) << shift for pl in f] for f in E.synth(oracle, w, h, bd, N, {4: 4504, 3: 4500}[bs])]
+    params = dict(block_log2=bs, tx_search=1, enable_qm=1, qm_min=1, qm_max=15)
+    case = dict(name="idtx_qm_bs%d_%db" % (bs, bd), w=w, h=h, bd=bd, n=N, params=params)
+    # on the CPU first: the identity transform is chosen somewhere - without the search the oracle's stream is another
+    assert E.oracle_encode(oracle, case, frames)[0] != E.oracle_encode(oracle, dict(case, params=dict(params, tx_search=0)), frames)[0]
+    check(av1mi, ctx, oracle, case, frames)
