@@ -39,7 +39,7 @@ ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", 
                "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units", "av1mi_sym_order_result", "av1mi_sym_order_tiles", "av1mi_inter_partition_result", "av1mi_inter_partition_units",
                "av1mi_lr_rd_result", "av1mi_lr_rd_units", "av1mi_temporal_filter", "av1mi_tpl_analysis", "av1mi_film_grain_estimate",
                "av1mi_film_grain_result", "av1mi_film_grain_denoise", "av1mi_film_grain_ar_estimate", "av1mi_film_grain_ar_result",
-               "av1mi_film_grain_denoise_temporal"]
+               "av1mi_film_grain_denoise_temporal", "av1mi_tpl_frame_q", "av1mi_frame_q_result"]
 
 
 class Params(C.Structure):
@@ -119,6 +119,9 @@ _lib.av1mi_aq_qindex.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_
 _lib.av1mi_temporal_filter.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_uint32)]
 _lib.av1mi_tpl_analysis.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint16), C.POINTER(C.c_uint32)]
+_lib.av1mi_tpl_frame_q.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                    C.POINTER(C.c_uint16), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
+_lib.av1mi_frame_q_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)]
 _lib.av1mi_film_grain_estimate.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32),
                                             C.POINTER(C.c_uint8)]
 _lib.av1mi_film_grain_result.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
@@ -197,6 +200,20 @@ def cq_aq_tpl(cq, aq, tpl):
 def tpl_strength_of(v):
     """include/av1mi.h: AV1MI_TPL_STRENGTH"""
     return (v >> 12) & 7
+
+
+FQ_MAX_STRENGTH = 4
+
+
+def cq_aq_tpl_fq(cq, aq, tpl, fq):
+    """include/av1mi.h: AV1MI_CQ_AQ_TPL_FQ - the cq_level field with the strength of the frame term (every frame its own base_q_idx) in
+    bits 20-22 beside the other three"""
+    return cq_aq_tpl(cq, aq, tpl) | ((fq & 7) << 20)
+
+
+def frame_q_strength_of(v):
+    """include/av1mi.h: AV1MI_FQ_STRENGTH"""
+    return (v >> 20) & 7
 
 
 def cq_level_of(v):
@@ -332,8 +349,8 @@ def lr_unit_grid(width, height, shift=0):
 
 
 def default_params(width, height, bit_depth=8, aq_strength=None, tpl_strength=None, lr_fit=None, lr_wiener_fit=False, lr_unit_shift=0, lr_rd=None, tf_frames=None,
-                   tf_strength=None, film_grain_estimate=None, film_grain_denoise=None, film_grain_ar=None, film_grain_temporal=None, **kw):
-    """film_grain_temporal: a span 1 or 2 - the denoiser's temporal term or-ed into the film_grain field the other keywords give
+                   tf_strength=None, film_grain_estimate=None, film_grain_denoise=None, film_grain_ar=None, film_grain_temporal=None, frame_q_strength=None, **kw):
+    """frame_q_strength: packed into cq_level's bits 20-22 beside the other three (cq_aq_tpl_fq); film_grain_temporal: a span 1 or 2 - the denoiser's temporal term or-ed into the film_grain field the other keywords give
     (film_grain_denoise_temporal); film_grain_ar: a lag 1 .. 3 or-ed into the film_grain field the other keywords give (film_grain_ar); film_grain_estimate: N = 1 .. 50 sets film_grain to the estimated table with the ceiling N (the function of that name), True turns
     the estimate on for the film_grain keyword's N; film_grain_denoise: likewise, with the source denoised by that table (the function of
     that name); aq_strength, tpl_strength: packed into cq_level beside the CQ level (cq_aq_tpl); lr_fit: True or a mask of parameter sets, packed into enable_lr
@@ -361,9 +378,10 @@ def default_params(width, height, bit_depth=8, aq_strength=None, tpl_strength=No
         kw["enable_lr"] = kw.get("enable_lr", p.enable_lr) | ((int(lr_unit_shift) & 3) << 12)
     if lr_rd is not None and lr_rd is not False:
         kw["enable_lr"] = kw.get("enable_lr", p.enable_lr) | lr_rd_field(int(lr_rd))
-    if aq_strength is not None or tpl_strength is not None:
+    if aq_strength is not None or tpl_strength is not None or frame_q_strength is not None:
         cq = kw.get("cq_level", p.cq_level)
-        kw["cq_level"] = cq_aq_tpl(cq, aq_strength_of(cq) if aq_strength is None else aq_strength, tpl_strength_of(cq) if tpl_strength is None else tpl_strength)
+        kw["cq_level"] = cq_aq_tpl_fq(cq, aq_strength_of(cq) if aq_strength is None else aq_strength, tpl_strength_of(cq) if tpl_strength is None else tpl_strength,
+                                      frame_q_strength_of(cq) if frame_q_strength is None else frame_q_strength)
     for k, v in kw.items():
         if not hasattr(p, k):
             raise AttributeError(k)
@@ -504,6 +522,30 @@ class Context:
         _raise_for(rc, self.last_error())
         out["mean_beta"] = int(mean.value)
         return out
+
+    def tpl_frame_q(self, params, frames, n_frames, on_device=False):
+        """The frame term's decision alone (include/av1mi.h: av1mi_tpl_frame_q); frames as for scene_cuts.  Returns a dict of numpy
+        arrays with one entry per frame - intra_sum, dep_sum (uint64), beta (uint16), frame_q (uint8) - and mean_beta (int)."""
+        import numpy as np
+        out = dict(intra_sum=np.zeros(n_frames, dtype=np.uint64), dep_sum=np.zeros(n_frames, dtype=np.uint64),
+                   beta=np.zeros(n_frames, dtype=np.uint16), frame_q=np.zeros(n_frames, dtype=np.uint8))
+        mean = C.c_uint32(0)
+        fptr, keep = _frames_ptr(frames, on_device)
+        u64 = C.POINTER(C.c_uint64)
+        rc = _lib.av1mi_tpl_frame_q(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0, out["intra_sum"].ctypes.data_as(u64),
+                                    out["dep_sum"].ctypes.data_as(u64), out["beta"].ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(mean),
+                                    out["frame_q"].ctypes.data_as(C.POINTER(C.c_uint8)))
+        _raise_for(rc, self.last_error())
+        out["mean_beta"] = int(mean.value)
+        return out
+
+    def frame_q_result(self, n_frames):
+        """(frame_q uint8 [frame], beta uint16 [frame]) of the chunk this context encoded last (include/av1mi.h: av1mi_frame_q_result)"""
+        import numpy as np
+        q, beta = np.zeros(n_frames, dtype=np.uint8), np.zeros(n_frames, dtype=np.uint16)
+        rc = _lib.av1mi_frame_q_result(self._h, n_frames, q.ctypes.data_as(C.POINTER(C.c_uint8)), beta.ctypes.data_as(C.POINTER(C.c_uint16)))
+        _raise_for(rc, self.last_error())
+        return q, beta
 
     def film_grain_estimate(self, params, frames, n_frames, on_device=False, want_blocks=True):
         """The film-grain estimate alone (include/av1mi.h: av1mi_film_grain_estimate); frames as for scene_cuts.  Returns numpy arrays

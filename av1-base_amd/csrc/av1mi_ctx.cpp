@@ -65,7 +65,8 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     const size_t nf = n_frames, slot = (size_t)tile_slot_bytes(r, c->cap_scale);
     // the small blocks that have a page-locked mirror on the host: header blob, default CDFs with their compact image, parameters,
     // chunk record with frame_off[nf + 1], squared errors
-    const size_t hdr_bytes = 256 + nf * 512, cdf_bytes = Av1miCdfCompact::BLOB_WORDS * sizeof(uint16_t), par_bytes = AV1MI_AQ_SLOTS * sizeof(Av1miDevParams),
+    // (CDFs and parameters at what the frame term needs - four q contexts, 28 quantiser slots: 50 KB; a chunk uploads what it uses)
+    const size_t hdr_bytes = 256 + nf * 512, cdf_bytes = 4 * Av1miCdfCompact::BLOB_WORDS * sizeof(uint16_t), par_bytes = AV1MI_FQ_SLOTS * sizeof(Av1miDevParams),
                  rec_bytes = sizeof(Av1miChunkRecord) + (nf + 1) * 8, sse_bytes = nf * 3 * 8;
     for (void **b : { &w.d_src, &w.d_rec, &w.d_fin }) HIPCHK(c, ws_alloc(w, *b, nf * frame_bytes));
     HIPCHK(c, ws_alloc(w, w.d_levels, nf * nsb * AV1MI_SB_LEVELS * sizeof(int16_t)));
@@ -122,11 +123,15 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   if (r.fg_denoise_span) HIPCHK(c, ws_grow(w, w.d_fgd_mv, w.fgd_mv_bytes, fgd_mv_entries(r, n_frames) * sizeof(uint32_t)));
   // the temporal filter's keys, on first use (and when a chunk has more key frames or followers than any before)
   if (r.tf_frames) HIPCHK(c, ws_grow(w, w.d_tf_mv, w.tf_mv_bytes, tf_mv_entries(r, n_frames) * sizeof(uint32_t)));
-  if (dq_on(r) && !w.d_aq_map) {
+  if (qmap_on(r) && !w.d_aq_map) {
     HIPCHK(c, ws_alloc(w, w.d_aq_act, nf * nsb * sizeof(uint16_t)));
     HIPCHK(c, ws_alloc(w, w.d_aq_map, nf * nsb));
   }
-  if (r.tpl && !w.d_tpl_beta) {   // (beta last: every one of the five stands once it does)
+  if (r.fq && (!w.d_fq || !w.h_fq)) {
+    HIPCHK(c, ws_alloc(w, w.d_fq, av1mi_fq_bytes(nf)));
+    HIPCHK(c, ws_alloc(w, w.h_fq, av1mi_fq_bytes(nf), true));
+  }
+  if ((r.tpl || r.fq) && !w.d_tpl_beta) {   // (beta last: every one of the five stands once it does)
     const size_t nb = (size_t)av1mi_tpl_blocks(r.cw) * av1mi_tpl_blocks(r.ch);
     for (uint32_t **b : { &w.d_tpl_intra, &w.d_tpl_inter, &w.d_tpl_key }) HIPCHK(c, ws_alloc(w, *b, nf * nb * sizeof(uint32_t)));
     HIPCHK(c, ws_alloc(w, w.d_tpl_flow, av1mi_tpl_flow_entries(r.cw, r.ch, (int)nf) * sizeof(unsigned long long)));
@@ -170,8 +175,8 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   w.res = r;
   if (p.enable_qm && r.qm_level < 15) {
     // one slice of steps, or with adaptive quantisation one per quantiser slot (make_qm_table)
-    if (!w.d_qm) HIPCHK(c, ws_alloc(w, w.d_qm, AV1MI_AQ_SLOTS * 2 * AV1MI_QM_PLANE * sizeof(Av1miQmEntry)));
-    const int slices = dq_on(r) ? AV1MI_AQ_SLOTS : 1;
+    if (!w.d_qm) HIPCHK(c, ws_alloc(w, w.d_qm, AV1MI_FQ_SLOTS * 2 * AV1MI_QM_PLANE * sizeof(Av1miQmEntry)));
+    const int slices = quant_slots(r);
     const int key = (slices << 24) | (r.qm_level << 16) | (r.qidx << 4) | (int)p.bit_depth;
     if (w.qm_key != key) {
       w.h_qm = make_qm_table(r);
@@ -188,7 +193,8 @@ void bind_workspace(Av1miDevParams &P, const Resolved &r, const Workspace &w) {
   const av1mi_params &p = r.p;
   if (p.enable_qm && r.qm_level < 15) P.qm_tab = w.d_qm;
   if (p.partition_search) P.part_map = w.d_part;
-  if (dq_on(r)) P.aq_map = w.d_aq_map;
+  if (qmap_on(r)) P.aq_map = w.d_aq_map;
+  if (r.fq) P.frame_q = av1mi_fq_split(w.d_fq, (size_t)P.n_frames).frame_q;
   if (p.cdef_search) { P.cdef_err = w.d_cdef_err; P.cdef_idx = w.d_cdef_idx; P.cdef_sel = w.d_cdef_sel; }
   if (p.deblock == 2) { P.lf_err = w.d_lf_err; P.lf_sel = w.d_lf_sel; }
   if (r.lr_fit_mask) P.lr_fit_code = w.fit.code;
@@ -543,6 +549,14 @@ void run_tpl(PassBuffers &t, const Resolved &r, const Av1miDevParams &P, const v
   if (t.ok()) t.e = hipMemsetAsync(b.flow, 0, b.n_flow * sizeof(unsigned long long), t.stream);
   if (t.ok()) t.e = av1mi_launch_tpl(&P, src, b.intra, b.inter, b.key, b.flow, b.beta, t.stream);
 }
+// ... and the frame term's sums behind it (av1mi_launch_tpl_frames), in a block of the pass's
+Av1miFqBlock run_fq(PassBuffers &t, const Av1miDevParams &P, uint32_t n_frames, const TplBuffers &b) {
+  uint8_t *d = nullptr;
+  t.alloc(d, av1mi_fq_bytes(n_frames));
+  const Av1miFqBlock fq = av1mi_fq_split(d, n_frames);
+  if (t.ok()) t.e = av1mi_launch_tpl_frames(&P, b.intra, b.flow, b.beta, fq, t.stream);
+  return fq;
+}
 }  // namespace
 
 extern "C" {
@@ -554,18 +568,58 @@ int av1mi_aq_qindex(av1mi_ctx *c, const av1mi_params *params, const void *frames
   Pass t(c, params);
   const Resolved &r = t.r; const Av1miDevParams &P = t.P; hipStream_t s = t.stream;
   const size_t n_map = (size_t)n_frames * r.sb_cols * r.sb_rows;
-  if (!t.rc && !dq_on(r)) { memset(qindex, r.qidx, n_map); return AV1MI_OK; }   // delta-q is off: nothing looks at the frames or their alignment
+  if (!t.rc && !qmap_on(r)) { memset(qindex, r.qidx, n_map); return AV1MI_OK; }   // every superblock at the chunk's index: nothing looks at the frames or their alignment
   if (const int rc = t.open(c, n_frames, true, nullptr, frames_on_device ? (uintptr_t)frames : 0)) return rc;
   uint16_t *d_act = nullptr;
   uint8_t *d_map = nullptr;
   TplBuffers tpl;
+  Av1miFqMap fq = {};
   t.alloc(d_act, n_map * sizeof(uint16_t));
   t.alloc(d_map, n_map);
   const void *src = coded_frames(t, r, frames, n_frames, frames_on_device).coded;   // the rule reads the coded size
-  if (r.tpl) run_tpl(t, r, P, src, n_frames, tpl);
-  if (t.ok()) t.e = av1mi_launch_aq(&P, src, d_act, d_map, r.aq, tpl.beta, r.tpl ? tpl.beta_sum() : nullptr, r.tpl, s);
+  if (r.tpl || r.fq) run_tpl(t, r, P, src, n_frames, tpl);
+  if (r.fq) { fq.strength = r.fq; fq.fq = run_fq(t, P, n_frames, tpl); }   // the combined map: the frames' steps included
+  if (t.ok()) t.e = av1mi_launch_aq(&P, src, d_act, d_map, r.aq, tpl.beta, r.tpl ? tpl.beta_sum() : nullptr, r.tpl, &fq, s);
   if (t.ok()) t.e = hipMemcpyAsync(qindex, d_map, n_map, hipMemcpyDeviceToHost, s);
   return t.finish(c, "adaptive-quantisation");
+}
+
+// The frame term's decision alone: the encoder's launches (av1mi_launch_tpl, av1mi_launch_tpl_frames, aq_map_kernel's frame step) on the
+// frames it is given, on buffers of the call's own and without a header to write into.
+int av1mi_tpl_frame_q(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device, uint64_t *intra_sum,
+                      uint64_t *dep_sum, uint16_t *beta, uint32_t *mean_beta, uint8_t *frame_q) {
+  if (!c || !frames || n_frames == 0) return AV1MI_E_INVALID_ARG;
+  Pass t(c, params);
+  if (const int rc = t.open(c, n_frames, t.r.fq, "the frame strength is 0", frames_on_device ? (uintptr_t)frames : 0)) return rc;
+  TplBuffers b;
+  Av1miFqMap fq = {};
+  uint8_t *d_map = nullptr;
+  t.alloc(d_map, (size_t)n_frames * t.r.sb_cols * t.r.sb_rows);
+  const void *src = coded_frames(t, t.r, frames, n_frames, frames_on_device).coded;
+  if (t.ok()) run_tpl(t, t.r, t.P, src, n_frames, b);
+  fq.strength = t.r.fq;
+  fq.fq = run_fq(t, t.P, n_frames, b);
+  if (t.ok()) t.e = av1mi_launch_aq(&t.P, src, nullptr, d_map, 0, b.beta, nullptr, 0, &fq, t.stream);   // (the map, all q_f, is not reported)
+  std::vector<uint16_t> bf(n_frames, 0);
+  to_host(t, intra_sum, fq.fq.intra_sum, (size_t)n_frames * 8);
+  to_host(t, dep_sum, fq.fq.dep_sum, (size_t)n_frames * 8);
+  to_host(t, bf.data(), fq.fq.beta, (size_t)n_frames * 2);
+  to_host(t, frame_q, fq.fq.frame_q, n_frames);
+  const int rc = t.finish(c, "frame-quantiser");   // (drains the stream: `bf` has arrived)
+  if (rc != AV1MI_OK) return rc;
+  uint64_t sum = 0;
+  for (uint32_t f = 0; f < n_frames; f++) sum += bf[f];
+  if (beta) memcpy(beta, bf.data(), (size_t)n_frames * 2);
+  if (mean_beta) *mean_beta = (uint32_t)av1mi_fq_mean(sum, n_frames);
+  return AV1MI_OK;
+}
+
+// The frames' base_q_idx and betaF of the context's last chunk: what download_chunk kept.
+int av1mi_frame_q_result(const av1mi_ctx *c, uint32_t n_frames, uint8_t *frame_q, uint16_t *beta) {
+  if (!c || !c->last.n_frames || n_frames != c->last.n_frames) return AV1MI_E_INVALID_ARG;
+  if (frame_q) memcpy(frame_q, c->last.frame_q.data(), n_frames);
+  if (beta) memcpy(beta, c->last.frame_beta.data(), (size_t)n_frames * sizeof(uint16_t));
+  return AV1MI_OK;
 }
 
 // The temporal-dependency analysis alone: the launches the encoder runs on a chunk's source (av1mi_launch_tpl), on buffers of the call's own.

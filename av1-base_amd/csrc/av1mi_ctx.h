@@ -54,6 +54,9 @@ struct Workspace {
   uint32_t *d_tpl_intra = nullptr, *d_tpl_inter = nullptr, *d_tpl_key = nullptr;
   unsigned long long *d_tpl_flow = nullptr;
   uint16_t *d_tpl_beta = nullptr;
+  // the frame term (cq_level bits 20-22), on first use: its block (av1mi_fq_split) - per frame OF, PF, the sum of beta, betaF and q_f - and
+  // where one copy lands it
+  uint8_t *d_fq = nullptr, *h_fq = nullptr;
   // the film-grain estimate (fg_kernel.hip), on first use: its block (av1mi_fg_split); h_fg: where one copy lands its head
   uint8_t *d_fg = nullptr, *h_fg = nullptr;
   // the grain's autoregressive fit (fg_ar_kernel.hip), on first use: its block (av1mi_fgar_split), and where one copy lands its head
@@ -82,9 +85,10 @@ struct Workspace {
   // every chunk of a job: h_hdr / h_cdf / h_params hold what d_hdr / d_cdf / d_params hold, and prepare_chunk uploads only what differs.
   uint8_t *h_hdr = nullptr; uint16_t *h_cdf = nullptr; Av1miDevParams *h_params = nullptr;
   size_t hdr_bytes = 0;                // bytes of h_hdr that d_hdr is known to hold; 0: unknown (the strength search writes into d_hdr)
-  int cdf_qidx = -1;                   // the quantiser index d_cdf was made for (the blob depends on nothing else); -1: none
+  int cdf_qidx = -1;                   // the quantiser index d_cdf was made for (the blob depends on nothing else); -1: none; AV1MI_CDF_ALL: the
+                                       // four q contexts' blobs one after the other (the frame term)
   int cdf_bs_log2 = -1;                // ... and the leaf size its compact image behind the blob was made for
-  int params_on_device = 0;            // d_params holds the first so many blocks of h_params (1, or AV1MI_AQ_SLOTS with adaptive quantisation)
+  int params_on_device = 0;            // d_params holds the first so many blocks of h_params (1, AV1MI_AQ_SLOTS with adaptive quantisation, AV1MI_FQ_SLOTS with the frame term)
   Av1miChunkRecord *h_record = nullptr; unsigned long long *h_sse = nullptr;   // d_record and d_sse land here
   size_t out_cap = 0, me64_bytes = 0, nodes_bytes = 0, h_out_cap = 0, tf_mv_bytes = 0, fgd_mv_bytes = 0;   // bytes of d_out, d_me64, d_nodes, h_out, d_tf_mv, d_fgd_mv
   std::vector<std::pair<void *, bool>> owned;   // every buffer above: (address, page-locked host memory)
@@ -123,7 +127,11 @@ struct LastChunk {
   int8_t fg_ar_coeffs[3 * 25] = {};
   uint8_t fg_sigma_table[24] = {};
   uint32_t fg_ar_gain[3] = { 256, 256, 256 };
+  // its frames' base_q_idx and betaF (av1mi_frame_q_result): the chunk's index and zeros without the frame term
+  std::vector<uint8_t> frame_q;
+  std::vector<uint16_t> frame_beta;
 };
+#define AV1MI_CDF_ALL 256
 // the records of the film-grain estimate over n_frames frames: the whole 16x16 blocks of the signalled size
 inline size_t fg_records(const Resolved &r, size_t n_frames) { return n_frames * av1mi_fg_blocks((int)r.p.width) * av1mi_fg_blocks((int)r.p.height); }
 // The grain passes `r` asks for, in the encoder's order on stream s: the estimate on `coded` - the caller's frames on the device at the

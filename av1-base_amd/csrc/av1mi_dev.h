@@ -48,9 +48,11 @@ struct Av1miDevParams {
   uint32_t dc_recip, ac_recip;  // ceil(2^32 / q)
   // quantiser matrices (using_qmatrix): null, or per plane type (luma | chroma) and square transform size the dequantiser
   // step of every coefficient position, {q2 = Round2(q * Quantizer_Matrix[level][plane > 0][pos], 5), ceil(2^32 / q2)};
-  // a plane whose level is 15 (flat) holds q itself.  Offsets AV1MI_QM_*; header fields using_qm, qm_y, qm_uv.
+  // a plane whose level is 15 (flat) holds q itself.  Offsets AV1MI_QM_*; header fields using_qm, qm_y, qm_uv.  (using_qm in front of
+  // the pointer, where padding was: the eight bytes went to frame_q below and every other field keeps its offset.)
+  int using_qm;
   const Av1miQmEntry *qm_tab;
-  int using_qm, qm_y, qm_uv;
+  int qm_y, qm_uv;
   int min_bs_log2, max_bs_log2;
   // content-driven partition (av1mi_params.partition_search): null, or per frame of the chunk and superblock the split mask
   // partition_kernel wrote (av1mi_node_split below); a node larger than min_bs_log2 and not larger than max_bs_log2 follows it
@@ -61,6 +63,14 @@ struct Av1miDevParams {
   // everything else a kernel derives from the quantiser - deblocking level, partition threshold, quantiser-matrix level, coefficient
   // q context, range-coder stages - stays with base_q_idx
   const uint8_t *aq_map;
+  // the frame term (av1mi_params.cq_level bits 20-22, tpl_rule.h): null, or per frame of the chunk its own base_q_idx q_f
+  // (aq_map_kernel, which writes it into the frame's header as well).  aq_map is then always there - q_f + 4 d, or all q_f when no
+  // superblock term is on - and its slots are the wide set (av1mi_aq_slot).  What follows q_f: the header's base_q_idx, the coefficient
+  // CDFs' q context (normative) and CurrentQIndex at every tile start (symbolize and the range coder), and through the slot the steps,
+  // reciprocals, dead zone, dequantiser and quantiser-matrix slice.  What stays with the chunk's base_q_idx, each an encoder's choice
+  // and legal in the stream: the deblocking level and the level search's centre, both partition thresholds, the quantiser-matrix
+  // level, lr_lambda, the inter-partition penalty and the range coder's stage choice
+  const uint8_t *frame_q;
   uint32_t mode_mask;
   int angle_delta;          // 1: directional winners of the luma mode decision are refined over the angle deltas -3 .. +3
   int edge_filter;          // enable_intra_edge_filter
@@ -139,12 +149,17 @@ static_assert(sizeof(Av1miDevParams) == 864, "lr_lambda took padding: the block,
 // ---- adaptive quantisation: the parameter block in device memory is followed by one copy per quantiser slot, equal to it except for
 // dc_q, ac_q, their reciprocals and the quantiser-matrix slice.  Slot 0 is the block itself (base_q_idx); slot 1 + 6 + d holds
 // base_q_idx + 4 d, d = -6 .. 6 (an index outside 1 .. 255 never occurs in a map: its slot repeats the base).
+// With the frame term (frame_q) the set is wide: slot 1 + 16 + j holds base_q_idx + 4 j, j = k_f + d = -16 .. 10 - 28 blocks, five bits.
 #define AV1MI_AQ_SLOTS 14
-AV1MI_HD inline int av1mi_aq_slot(int qindex, int base_q_idx) { return 7 + (qindex - base_q_idx) / 4; }
-AV1MI_HD inline int av1mi_aq_slot_qindex(int slot, int base_q_idx) {
-  const int q = slot ? base_q_idx + 4 * (slot - 7) : base_q_idx;
+#define AV1MI_FQ_SLOTS 28
+AV1MI_HD inline int av1mi_aq_slots(bool wide) { return wide ? AV1MI_FQ_SLOTS : AV1MI_AQ_SLOTS; }
+AV1MI_HD inline int av1mi_aq_slot(int qindex, int base_q_idx, bool wide = false) { return (wide ? 17 : 7) + (qindex - base_q_idx) / 4; }
+AV1MI_HD inline int av1mi_aq_slot_qindex(int slot, int base_q_idx, bool wide = false) {
+  const int q = slot ? base_q_idx + 4 * (slot - (wide ? 17 : 7)) : base_q_idx;
   return q >= 1 && q <= 255 ? q : base_q_idx;
 }
+// coefficient q context (spec 8.3.2 init_coeff_cdfs): which of the four sets of default coefficient CDFs a frame of this base_q_idx starts from
+AV1MI_HD inline int av1mi_q_context(int qidx) { return qidx <= 20 ? 0 : (qidx <= 60 ? 1 : (qidx <= 120 ? 2 : 3)); }
 
 // ---- partition: does the node of size 2^bsl at superblock-local (ox, oy) split?  One rule for every kernel that
 // walks blocks (reconstruction, motion search, symbolize).  The syntax forces a split where the node's half point is outside the

@@ -36,8 +36,9 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   size_t lf_key = 0, lf_inter = 0;     // deblocking level search: where deblock_decide_kernel writes each frame's levels
   size_t fg_bit[2] = { 0, 0 };         // film-grain estimate: where fg_table_kernel writes each frame's table (key, inter)
   size_t ar_bit[2] = { 0, 0 };         // ... and fg_ar_solve_kernel the autoregressive coefficients
-  std::vector<uint8_t> seq = make_sequence_header(r), fh = make_frame_header(r, nullptr, 0, false, &str_key, &lf_key, &fg_bit[0], &ar_bit[0]),
-                       fhi = make_frame_header(r, nullptr, 0, true, &str_inter, &lf_inter, &fg_bit[1], &ar_bit[1]);
+  size_t q_bit[2] = { 0, 0 };          // the frame term: where aq_map_kernel writes each frame's base_q_idx
+  std::vector<uint8_t> seq = make_sequence_header(r), fh = make_frame_header(r, nullptr, 0, false, &str_key, &lf_key, &fg_bit[0], &ar_bit[0], &q_bit[0]),
+                       fhi = make_frame_header(r, nullptr, 0, true, &str_inter, &lf_inter, &fg_bit[1], &ar_bit[1], &q_bit[1]);
   P.cdef_str_bit[0] = (int)str_key; P.cdef_str_bit[1] = (int)str_inter;
   P.lf_bit[0] = (int)lf_key; P.lf_bit[1] = (int)lf_inter;
   P.seq_hdr_bytes = (int)seq.size(); P.frame_hdr_bytes = (int)fh.size(); P.inter_hdr_bytes = (int)fhi.size();
@@ -53,22 +54,30 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   // Upload what the device does not hold already (consecutive chunks of a job: nothing), from page-locked memory - the copies are
   // asynchronous, and the previous chunk's have completed (download_chunk waits for the main stream).  With the strength search on,
   // cdef_select_kernel writes the strengths into the frame headers on the device: the blob goes up every chunk.  Likewise with the
-  // deblocking level search (deblock_decide_kernel writes the levels) and the film-grain estimate (fg_table_kernel writes the table).
+  // deblocking level search (deblock_decide_kernel writes the levels), the film-grain estimate (fg_table_kernel writes the table) and
+  // the frame term (aq_map_kernel writes the frames' base_q_idx).
   if (w.hdr_bytes != blob.size() || memcmp(w.h_hdr, blob.data(), blob.size())) {
     w.hdr_bytes = 0;
     memcpy(w.h_hdr, blob.data(), blob.size());
     HIPCHK(c, hipMemcpyAsync(w.d_hdr, w.h_hdr, blob.size(), hipMemcpyHostToDevice, s));
   }
-  w.hdr_bytes = P.cdef_search || P.lf_search || r.fg_estimate ? 0 : blob.size();
-  if (w.cdf_qidx != r.qidx || w.cdf_bs_log2 != P.max_bs_log2) {
+  w.hdr_bytes = P.cdef_search || P.lf_search || r.fg_estimate || r.fq ? 0 : blob.size();
+  // the default CDFs of the chunk's q context - or, with the frame term, of all four one after the other: a frame's tiles take the
+  // blob of its own q_f (entropy_kernel.hip: frame_cdf) - once per context and leaf size
+  const int cdf_key = r.fq ? AV1MI_CDF_ALL : r.qidx;
+  if (w.cdf_qidx != cdf_key || w.cdf_bs_log2 != P.max_bs_log2) {
     w.cdf_qidx = -1;
-    // the blob, and behind it the regular symbolize variants' compact image of it for this leaf size (av1mi_dev.h: Av1miCdfCompact)
-    std::vector<uint16_t> cdf = make_cdf_blob(r.qidx);
-    cdf.resize(Av1miCdfCompact::BLOB_WORDS, 0);
-    av1mi_cdf_compact_build(cdf.data(), P.max_bs_log2, cdf.data() + Av1miCdfCompact::AT);
-    memcpy(w.h_cdf, cdf.data(), cdf.size() * 2);
-    HIPCHK(c, hipMemcpyAsync(w.d_cdf, w.h_cdf, cdf.size() * 2, hipMemcpyHostToDevice, s));
-    w.cdf_qidx = r.qidx; w.cdf_bs_log2 = P.max_bs_log2;
+    static const int context_qidx[4] = { 20, 60, 120, 255 };   // an index of each q context (av1mi_q_context)
+    const int n_blobs = r.fq ? 4 : 1;
+    for (int k = 0; k < n_blobs; k++) {
+      // the blob, and behind it the regular symbolize variants' compact image of it for this leaf size (av1mi_dev.h: Av1miCdfCompact)
+      std::vector<uint16_t> cdf = make_cdf_blob(r.fq ? context_qidx[k] : r.qidx);
+      cdf.resize(Av1miCdfCompact::BLOB_WORDS, 0);
+      av1mi_cdf_compact_build(cdf.data(), P.max_bs_log2, cdf.data() + Av1miCdfCompact::AT);
+      memcpy(w.h_cdf + (size_t)k * Av1miCdfCompact::BLOB_WORDS, cdf.data(), cdf.size() * 2);
+    }
+    HIPCHK(c, hipMemcpyAsync(w.d_cdf, w.h_cdf, (size_t)n_blobs * Av1miCdfCompact::BLOB_WORDS * 2, hipMemcpyHostToDevice, s));
+    w.cdf_qidx = cdf_key; w.cdf_bs_log2 = P.max_bs_log2;
   }
   {
     // The recon kernel reads its parameters from device memory: P, and with adaptive quantisation the quantiser slots' copies behind it
@@ -122,14 +131,23 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   // adaptive quantisation: every superblock's quantiser index, likewise from the source and on the device - the walks and symbolize read the map
   // ... with a temporal strength behind the chunk's temporal-dependency analysis (it sees the filtered key frames): beta of every
   // superblock and the chunk's sum of it, the flow cleared once per attempt at the chunk
+  // ... and with a frame strength behind the frames' sums of the same analysis (which it runs whatever the temporal strength): every
+  // frame's base_q_idx, into the map, into P.frame_q and into the frame's header - all on the device, no host round trip in front of
+  // "source ready"
   const unsigned long long *beta_sum = nullptr;
-  if (r.tpl) {
+  Av1miFqMap fq = {};
+  if (r.tpl || r.fq) {
     const size_t n_flow = av1mi_tpl_flow_entries(r.cw, r.ch, (int)n_frames);
     HIPCHK(c, hipMemsetAsync(w.d_tpl_flow, 0, n_flow * sizeof(unsigned long long), s));
     HIPCHK(c, av1mi_launch_tpl(&P, *d_src, w.d_tpl_intra, w.d_tpl_inter, w.d_tpl_key, w.d_tpl_flow, w.d_tpl_beta, s));
     beta_sum = w.d_tpl_flow + n_flow - 1;
   }
-  if (P.aq_map) HIPCHK(c, av1mi_launch_aq(&P, *d_src, w.d_aq_act, w.d_aq_map, r.aq, w.d_tpl_beta, beta_sum, r.tpl, s));
+  if (r.fq) {
+    fq.strength = r.fq; fq.q_bit[0] = (int)q_bit[0]; fq.q_bit[1] = (int)q_bit[1];
+    fq.fq = av1mi_fq_split(w.d_fq, n_frames); fq.hdr_blob = w.d_hdr;
+    HIPCHK(c, av1mi_launch_tpl_frames(&P, w.d_tpl_intra, w.d_tpl_flow, w.d_tpl_beta, fq.fq, s));
+  }
+  if (P.aq_map) HIPCHK(c, av1mi_launch_aq(&P, *d_src, w.d_aq_act, w.d_aq_map, r.aq, w.d_tpl_beta, r.tpl ? beta_sum : nullptr, r.tpl, &fq, s));
   HIPCHK(c, hipEventRecord(c->ev[EV_SRC_READY], s));
   return AV1MI_OK;
 }
@@ -140,13 +158,22 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
 // has just stored a whole superblock - costs that launch 0.034 ms, more than symbolize gains: DESIGN 5h.)
 static bool sym_order_on(const av1mi_ctx *c) { return c->sym_order && c->P.tile_sb == 1 && !c->P.disable_cdf_update && c->P.max_bs_log2 <= 5; }
 
+// The entropy coder's parameters: the chunk's - without the map where the stream carries no deltas: with the frame term alone the map
+// holds the frames' q_f for the reconstruction's slots, delta_q_present is 0 and symbolize codes none.
+static Av1miDevParams entropy_params(const av1mi_ctx *c) {
+  Av1miDevParams E = c->P;
+  if (!dq_on(c->ws.res)) E.aq_map = nullptr;
+  return E;
+}
+
 // Entropy coding of frames [from, n_frames) on the main stream (the frame-edge tiles' symbolize variant on the fourth), then the join
 // with the groups of frames before `from` coded on the third (schedule_inter): packing needs the tile sizes and bytes of every frame.
 // by_weight: symbolize takes the tiles in the order the chunk's reconstruction launch left (sym_order_on).
 static int entropy_code(av1mi_ctx *c, uint32_t from, uint32_t n_frames, bool by_weight = false) {
   Workspace &w = c->ws; hipStream_t s = c->stream;
+  const Av1miDevParams E = entropy_params(c);
   HIPCHK(c, hipEventRecord(c->ev[EV_RECON_DONE], s));
-  HIPCHK(c, av1mi_launch_entropy(&c->P, w.d_cdf, w.d_levels, w.d_blk, w.d_streams, w.d_sym, w.d_combos, w.d_slots, w.d_tile_bytes, w.d_lrc,
+  HIPCHK(c, av1mi_launch_entropy(&E, w.d_cdf, w.d_levels, w.d_blk, w.d_streams, w.d_sym, w.d_combos, w.d_slots, w.d_tile_bytes, w.d_lrc,
                                  w.d_tile_off /* scratch until the packing kernels fill it */, by_weight ? w.d_sym_count : nullptr,
                                  by_weight ? w.d_sym_order : nullptr, (int)from, (int)(n_frames - from),
                                  s, c->ev[EV_SYM_DONE], c->stream4, c->ev[EV_EDGE_FORK], c->ev[EV_EDGE_JOIN]));
@@ -292,7 +319,8 @@ static int schedule_inter(av1mi_ctx *c, const void *src, uint32_t n_frames) {
       if (c->grp_ev.size() <= n_grp) { hipEvent_t e; HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->grp_ev.push_back(e); }
       HIPCHK(c, hipEventRecord(c->grp_ev[n_grp], s));
       HIPCHK(c, hipStreamWaitEvent(c->stream3, c->grp_ev[n_grp], 0));
-      HIPCHK(c, av1mi_launch_entropy(&P, w.d_cdf, w.d_levels, w.d_blk, w.d_streams, w.d_sym, w.d_combos, w.d_slots, w.d_tile_bytes, w.d_lrc,
+      const Av1miDevParams E = entropy_params(c);
+      HIPCHK(c, av1mi_launch_entropy(&E, w.d_cdf, w.d_levels, w.d_blk, w.d_streams, w.d_sym, w.d_combos, w.d_slots, w.d_tile_bytes, w.d_lrc,
                                      w.d_tile_off, nullptr, nullptr, (int)(f + 1 - grp), (int)grp, c->stream3, nullptr, nullptr, nullptr, nullptr));
       n_grp++;
     }
@@ -360,6 +388,8 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
   // the film-grain estimate's table and counts, likewise
   if (e1 == hipSuccess && r.fg_estimate) e1 = hipMemcpyAsync(w.h_fg, w.d_fg, av1mi_fg_result_bytes(), hipMemcpyDeviceToHost, s);
   if (e1 == hipSuccess && r.fg_ar_lag) e1 = hipMemcpyAsync(w.h_fg_ar, w.d_fg_ar, av1mi_fgar_result_bytes(), hipMemcpyDeviceToHost, s);
+  // the frame term's block, likewise
+  if (e1 == hipSuccess && r.fq) e1 = hipMemcpyAsync(w.h_fq, w.d_fq, av1mi_fq_bytes(n_frames), hipMemcpyDeviceToHost, s);
   // the self-guided fit's errors and records, likewise
   const size_t fit_n = (size_t)n_frames * 3 * av1mi_lr_unit_rows(P) * av1mi_lr_unit_cols(P);
   if (e1 == hipSuccess && P.lr_fit_code) e1 = hipMemcpyAsync(w.h_fit, w.d_fit, av1mi_lr_fit_result_bytes(fit_n), hipMemcpyDeviceToHost, s);
@@ -430,6 +460,13 @@ static LastChunk record_last_chunk(const av1mi_ctx *c, const Resolved &r, uint32
     memcpy(L.fg_ar_coeffs, H.coeffs, sizeof(L.fg_ar_coeffs));
     memcpy(L.fg_sigma_table, H.sigma, sizeof(L.fg_sigma_table));
     memcpy(L.fg_ar_gain, H.gain, sizeof(L.fg_ar_gain));
+  }
+  L.frame_q.assign(n_frames, (uint8_t)r.qidx);
+  L.frame_beta.assign(n_frames, 0);
+  if (r.fq) {
+    const Av1miFqBlock H = av1mi_fq_split(w.h_fq, n_frames);
+    memcpy(L.frame_q.data(), H.frame_q, n_frames);
+    memcpy(L.frame_beta.data(), H.beta, (size_t)n_frames * sizeof(uint16_t));
   }
   if (P.part_map) { L.pi_keys = c->part_inter; L.pi_frames = n_frames; L.pi_units = (uint32_t)(P.b8_rows * P.b8_cols); L.pi_sbs = (uint32_t)(P.sb_rows * P.sb_cols); }
   return L;

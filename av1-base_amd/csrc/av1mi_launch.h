@@ -23,6 +23,7 @@ inline Av1miDevParams av1mi_frame_range(const Av1miDevParams &P, int frame0, int
   R.n_frames = count;
   if (R.part_map) R.part_map += sb0;
   if (R.aq_map) R.aq_map += sb0;
+  if (R.frame_q) R.frame_q += frame0;
   if (R.cdef_idx) R.cdef_idx += sb0;
   if (R.cdef_sel) R.cdef_sel += (size_t)frame0 * 8;
   if (R.lf_err) R.lf_err += (size_t)frame0 * 48;
@@ -79,15 +80,44 @@ inline Av1miFgArBlock av1mi_fgar_split(void *block) {
 // first luma coefficient (fg_ar_bit) of a key and of an inter frame's header; all 0 without a header blob
 struct Av1miFgBits { int fg_key, fg_inter, ar_key, ar_inter; };
 
+// The frame term's block (tpl_rule.h "frame"; tpl_frame_kernel, aq_map_kernel), for n frames, 8-byte aligned: the small results per
+// frame in one allocation, which the host fetches in one copy
+struct Av1miFqBlock {
+  unsigned long long *intra_sum;     // OF = sum I over the frame's blocks
+  unsigned long long *dep_sum;       // PF = sum (I + A)
+  unsigned long long *sb_beta_sum;   // the sum of beta over the frame's superblocks (Mb_f comes from it)
+  uint16_t *beta;                    // betaF
+  uint8_t *frame_q;                  // q_f, the frame's base_q_idx (aq_map_kernel)
+};
+inline size_t av1mi_fq_bytes(size_t n) { return n * 27; }
+inline Av1miFqBlock av1mi_fq_split(void *block, size_t n) {
+  unsigned long long *q = reinterpret_cast<unsigned long long *>(block);
+  uint16_t *b = reinterpret_cast<uint16_t *>(q + 3 * n);
+  return { q, q + n, q + 2 * n, b, reinterpret_cast<uint8_t *>(b + n) };
+}
+// What aq_map_kernel takes of the frame term: strength 0 = off, nothing else is read.  hdr_blob: null, or the chunk's header blob, whose
+// frame headers receive q_f in the eight bits of base_q_idx at q_bit[key / inter] (make_frame_header's offsets; not byte-aligned)
+struct Av1miFqMap {
+  int strength;
+  int q_bit[2];
+  Av1miFqBlock fq;
+  uint8_t *hdr_blob;
+};
+
 extern "C" {
 // ---- whole chunk (or call): all P->n_frames frames
 // split masks of every superblock (partition_kernel)
 hipError_t av1mi_launch_partition(const Av1miDevParams *P, const void *frames, uint32_t *part, hipStream_t stream);
 // quantiser index of every superblock (aq_activity_kernel, aq_map_kernel): act and qmap are [frame][superblock].  tpl_strength != 0: the
 // temporal term on top (tpl_rule.h) - beta [frame][superblock] and beta_sum, the chunk's sum of it, as av1mi_launch_tpl on the same
-// stream before has left them; either strength may be 0, not both
+// stream before has left them; either strength may be 0, not both - unless the frame term is on.  fq: null, or the frame term
+// (fq->strength != 0, behind av1mi_launch_tpl_frames on the same stream): every frame's q_f into fq->fq.frame_q and into its header, the
+// map q_f + 4 d with the temporal term against the frame's own mean, or all q_f when both superblock strengths are 0
 hipError_t av1mi_launch_aq(const Av1miDevParams *P, const void *frames, uint16_t *act, uint8_t *qmap, int strength, const uint16_t *beta,
-                           const unsigned long long *beta_sum, int tpl_strength, hipStream_t stream);
+                           const unsigned long long *beta_sum, int tpl_strength, const Av1miFqMap *fq, hipStream_t stream);
+// the frame term's sums (tpl_frame_kernel), behind av1mi_launch_tpl on the same stream: OF, PF, betaF and the sum of beta of every frame
+hipError_t av1mi_launch_tpl_frames(const Av1miDevParams *P, const uint32_t *intra, const unsigned long long *flow, const uint16_t *beta,
+                                   Av1miFqBlock fq, hipStream_t stream);
 // the temporal-dependency analysis (tpl_kernel.hip, tpl_rule.h) of the chunk's source at the coded size, range P->me_range: per
 // [frame][16x16 block] the intra cost, the inter cost, the search's node key (all-ones on key frames) - all written - and the flow, added
 // into `flow`; per [frame][superblock] beta.  flow: av1mi_tpl_flow_entries entries, zeroed by the caller - the last one receives the

@@ -55,8 +55,6 @@ QuantSteps quant_steps(int qindex, int bit_depth) {
   return { dc, ac, recip32((uint32_t)dc), recip32((uint32_t)ac) };
 }
 static void set_quant_steps(Av1miDevParams &P, const QuantSteps &q) { P.dc_q = q.dc_q; P.ac_q = q.ac_q; P.dc_recip = q.dc_recip; P.ac_recip = q.ac_recip; }
-// coefficient q context: which of the four sets of default coefficient CDFs the frames start from
-static int q_context(int qidx) { return qidx <= 20 ? 0 : (qidx <= 60 ? 1 : (qidx <= 120 ? 2 : 3)); }
 
 // aom's quantizer_to_qindex[] (CQ level -> base_q_idx); 30 -> 120
 const uint8_t kQuantizerToQindex[64] = {
@@ -73,10 +71,11 @@ int resolve(const av1mi_params *in, Resolved *r) {
   if (p.bit_depth != 8 && p.bit_depth != 10) return AV1MI_E_INVALID_ARG;
   // cq_level 0 is base_q_idx 0: CodedLossless frames (spec 5.9.2), whose syntax this encoder does not write (no WHT, no lossless header)
   // ... and bits 8-10 of the field are the strength of the adaptive quantisation, 0 .. 4, bits 12-14 that of its temporal term, 0 .. 4;
-  // nothing in bit 11 or above them
+  // bits 20-22 that of the frame term, 0 .. 4 (tpl_rule.h: every frame its own base_q_idx); nothing in bits 11, 15-19 or 23-31
   r->aq = (int)AV1MI_AQ_STRENGTH(p.cq_level);
   r->tpl = (int)AV1MI_TPL_STRENGTH(p.cq_level);
-  if ((p.cq_level & ~0x77FFu) || r->aq > AV1MI_AQ_MAX_STRENGTH || r->tpl > AV1MI_TPL_MAX_STRENGTH) return AV1MI_E_INVALID_ARG;
+  r->fq = (int)AV1MI_FQ_STRENGTH(p.cq_level);
+  if ((p.cq_level & ~0x7077FFu) || r->aq > AV1MI_AQ_MAX_STRENGTH || r->tpl > AV1MI_TPL_MAX_STRENGTH || r->fq > AV1MI_FQ_MAX_STRENGTH) return AV1MI_E_INVALID_ARG;
   p.cq_level = AV1MI_CQ_LEVEL(p.cq_level);
   if (p.cq_level == 0 || p.cq_level > 63) return AV1MI_E_INVALID_ARG;
   // film_grain bit 8 (AV1MI_FILM_GRAIN_ESTIMATE): the table is estimated from the chunk's source, the low byte N = 1 .. 50 its ceiling;
@@ -247,8 +246,10 @@ std::vector<uint8_t> make_sequence_header(const Resolved &r) {
 // fg_ar_bit (optional): bit offset of the first luma coefficient - with a lag L (film_grain bits 12-13) the header carries ar_coeff_lag = L
 // and 2 L (L + 1) luma, then 2 L (L + 1) + 1 cb and as many cr coefficients as 128 (zero) placeholders, 6 L (L + 1) + 2 bytes in a row
 // which fg_ar_solve_kernel overwrites in every frame's slot, with the points scaled by the fit's gain; ar_coeff_shift_minus_6 is then 1
+// q_bit (optional): bit offset of base_q_idx - with the frame term on (cq_level bits 20-22) the header carries the chunk's index as the
+// placeholder and aq_map_kernel overwrites those 8 bits with the frame's q_f in its slot (the field is not byte-aligned)
 std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint32_t frame_number, bool inter, size_t *cdef_str_bit, size_t *lf_bit,
-                                       size_t *fg_bit, size_t *fg_ar_bit) {
+                                       size_t *fg_bit, size_t *fg_ar_bit, size_t *q_bit) {
   const av1mi_params &p = r.p;
   BitWriter b;
   b.put(0, 1);  // show_existing_frame
@@ -300,7 +301,8 @@ std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint
       b.put(3, 2);        // tile_size_bytes_minus_1
     }
   }
-  b.put((uint32_t)r.qidx, 8);
+  if (q_bit) *q_bit = b.bits;
+  b.put((uint32_t)r.qidx, 8);  // base_q_idx
   b.put(0, 1);  // DeltaQYDc
   b.put(0, 1);  // DeltaQUDc
   b.put(0, 1);  // DeltaQUAc
@@ -419,7 +421,7 @@ static void emit_rows(std::vector<uint16_t> &v, size_t off, const uint16_t (*row
 }
 std::vector<uint16_t> make_cdf_blob(int qidx) {
   typedef Av1miCdfLayout CL;
-  const int q = q_context(qidx);
+  const int q = av1mi_q_context(qidx);
   std::vector<uint16_t> v(CL::TOTAL, 0);
   int pn[20];
   for (int i = 0; i < 20; i++) pn[i] = i < 4 ? 4 : (i < 16 ? 10 : 8);
@@ -511,7 +513,7 @@ Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale) {
   P.tile_sb = r.tile_sb; P.tile_rows = r.tile_rows; P.tile_cols = r.tile_cols;
   P.n_frames = (int)n_frames;
   P.base_q_idx = r.qidx;
-  P.qctx = q_context(r.qidx);
+  P.qctx = av1mi_q_context(r.qidx);
   set_quant_steps(P, r.q);
   P.using_qm = p.enable_qm ? 1 : 0; P.qm_y = P.qm_uv = r.qm_level;
   P.max_bs_log2 = (int)p.block_log2;
@@ -551,11 +553,12 @@ Av1miDevParams dev_params(const Resolved &r, uint32_t n_frames, int scale) {
 // quantiser slot (av1mi_aq_slot) that differs in the quantiser steps, their reciprocals and the quantiser-matrix slice alone: the
 // walk takes its superblock's copy, and everything else it reads there is what the first block holds.
 std::vector<Av1miDevParams> slot_params(const Av1miDevParams &P) {
-  const int n_par = P.aq_map ? AV1MI_AQ_SLOTS : 1;
+  const bool wide = P.frame_q != nullptr;   // the frame term: 28 blocks
+  const int n_par = P.aq_map ? av1mi_aq_slots(wide) : 1;
   std::vector<Av1miDevParams> par((size_t)n_par, P);
   for (int sl = 1; sl < n_par; sl++) {
     Av1miDevParams &Q = par[(size_t)sl];
-    set_quant_steps(Q, quant_steps(av1mi_aq_slot_qindex(sl, P.base_q_idx), P.bit_depth));
+    set_quant_steps(Q, quant_steps(av1mi_aq_slot_qindex(sl, P.base_q_idx, wide), P.bit_depth));
     if (P.qm_tab) Q.qm_tab = P.qm_tab + (size_t)sl * 2 * AV1MI_QM_PLANE;
   }
   return par;
@@ -565,10 +568,10 @@ std::vector<Av1miDevParams> slot_params(const Av1miDevParams &P) {
 // with adaptive quantisation one slice per quantiser slot (av1mi_aq_slot): the superblock's steps through the frame's matrix
 std::vector<Av1miQmEntry> make_qm_table(const Resolved &r) {
   static const int off[4] = { AV1MI_QM_4X4, AV1MI_QM_8X8, AV1MI_QM_16X16, AV1MI_QM_32X32 };
-  const int slices = dq_on(r) ? AV1MI_AQ_SLOTS : 1;
+  const int slices = quant_slots(r);
   std::vector<Av1miQmEntry> tab((size_t)slices * 2 * AV1MI_QM_PLANE);
   for (int sl = 0; sl < slices; sl++) {
-    const QuantSteps qs = quant_steps(av1mi_aq_slot_qindex(sl, r.qidx), (int)r.p.bit_depth);
+    const QuantSteps qs = quant_steps(av1mi_aq_slot_qindex(sl, r.qidx, r.fq != 0), (int)r.p.bit_depth);
     for (int pt = 0; pt < 2; pt++)
       for (int l2 = 2; l2 <= 5; l2++)
         for (int i = 0; i < (1 << (2 * l2)); i++) {

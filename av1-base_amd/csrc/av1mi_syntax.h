@@ -29,6 +29,7 @@ struct Resolved {
   int lr_chroma;                      // enable_lr 3 / 4: U and V restored as well (p.enable_lr then holds the type: 1 / 2)
   int aq;                             // strength of the adaptive quantisation, 0 = off (p.cq_level then holds the CQ level alone)
   int tpl;                            // cq_level bits 12-14: strength of its temporal term (tpl_rule.h), 0 = off; delta_q is coded when either is set (dq_on)
+  int fq;                             // cq_level bits 20-22: strength of the frame term (tpl_rule.h), 0 = off: every frame its own base_q_idx; it runs the look-ahead whatever tpl is
   uint32_t lr_fit_mask;               // enable_lr bit 8: the parameter sets the self-guided fit searches, 0 = no fit (p.enable_lr holds the type)
   int lr_wfit;                        // enable_lr bit 10: the Wiener fit (p.enable_lr holds the type)
   int lr_unit_shift;                  // enable_lr bits 12-13: luma restoration units of 64 << lr_unit_shift samples (0 .. 2)
@@ -43,13 +44,18 @@ struct Resolved {
 int resolve(const av1mi_params *in, Resolved *r);
 // superblocks carry a quantiser index of their own: the spatial or the temporal term of the adaptive quantisation is on
 inline bool dq_on(const Resolved &r) { return r.aq || r.tpl; }
+// the reconstruction reads a map of quantiser indices: superblocks or frames carry an index of their own
+inline bool qmap_on(const Resolved &r) { return dq_on(r) || r.fq; }
+// the quantiser slots behind the parameter block and the slices of the quantiser-matrix table: 1, the 14 of the superblock terms, or the
+// frame term's 28
+inline int quant_slots(const Resolved &r) { return r.fq ? AV1MI_FQ_SLOTS : (dq_on(r) ? AV1MI_AQ_SLOTS : 1); }
 // bytes of n frames in the caller's layout: tight at the signalled size
 size_t caller_bytes(const Resolved &r, size_t n);
 
 // sequence_header_obu, complete OBU; and the OBU_FRAME payload up to the first tile, with the bit offsets of its placeholders
 std::vector<uint8_t> make_sequence_header(const Resolved &r);
 std::vector<uint8_t> make_frame_header(const Resolved &r, size_t *hdr_bits, uint32_t frame_number = 0, bool inter = false, size_t *cdef_str_bit = nullptr,
-                                       size_t *lf_bit = nullptr, size_t *fg_bit = nullptr, size_t *fg_ar_bit = nullptr);
+                                       size_t *lf_bit = nullptr, size_t *fg_bit = nullptr, size_t *fg_ar_bit = nullptr, size_t *q_bit = nullptr);
 // default CDF blob for one q context in the layout of Av1miCdfLayout
 std::vector<uint16_t> make_cdf_blob(int qidx);
 

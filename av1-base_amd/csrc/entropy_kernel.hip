@@ -834,6 +834,12 @@ __device__ __forceinline__ void reset_block_context(const TileCtx<TSB> &t, int l
   __syncthreads();
 }
 
+// the blob a frame's tiles start from: with the frame term (P.frame_q) the four q contexts' blobs follow one another, each with its
+// compact image, and the frame's q_f picks - the coefficient CDFs' q context is normative
+static __device__ __forceinline__ const uint16_t *frame_cdf(const Av1miDevParams &P, const uint16_t *cdf_init, int f) {
+  return P.frame_q ? cdf_init + (size_t)av1mi_q_context((int)P.frame_q[f]) * CC::BLOB_WORDS : cdf_init;
+}
+
 // FULL = false: regular tiles in adaptive mode - every leaf of the tile has one size, i.e. exactly two (tx size, plane type)
 // classes, no narrow rows in LDS (10.4 KB -> ~4 waves per SIMD).
 // FULL = true: tiles that mix sizes (content-driven partition, forced splits at the frame edge) and static-CDF mode.  Each variant
@@ -874,6 +880,7 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
   // (a tile whose superblocks mix block sizes holds more than two classes: the full variant's.  The launcher's grids are supersets
   // of a variant's tiles; this test decides)
   if (av1mi_tile_is_regular(P, f, tr, tc, TSB) == FULL) return;
+  cdf_init = frame_cdf(P, cdf_init, f);
   // ---- the tile's state: the CDF rows of the variant ...
   if constexpr (FULL) {
     // whole 16-byte pieces, then the last entries one by one
@@ -918,7 +925,9 @@ __global__ void __launch_bounds__(64) symbolize_tile_kernel(Av1miDevParams P, co
   // 2 bits per plane (bits 2 p .. 2 p + 1: plane p):
   int lr_prev = 0;  // RefLrWiener of the tile: 0 = Wiener_Taps_Mid, k = candidate k-1 (the plane's last unit coded with a Wiener filter)
   int sgr_prev = 0; // RefSgrXqd of the tile: 0 = Sgrproj_Xqd_Mid, k = self-guided candidate k-1 (the plane's last self-guided unit)
-  int cur_q = P.base_q_idx;   // CurrentQIndex (adaptive quantisation): base_q_idx at the tile start, then the last index a delta was coded for
+  // CurrentQIndex (adaptive quantisation): the frame's base_q_idx at the tile start - its own q_f with the frame term - then the last
+  // index a delta was coded for
+  int cur_q = P.frame_q ? (int)P.frame_q[f] : P.base_q_idx;
   // ---- the tile's superblocks
 #pragma nounroll
   for (int si = 0; si < TSB * TSB; si++) {
@@ -1089,7 +1098,8 @@ static __device__ __forceinline__ RcTile rc_tile(const Av1miDevParams &P, int n_
 }
 
 // per-lane CDF rows from the defaults of the tile's two (tx size, plane type) classes (one byte each in `combos`, 0xFF: none)
-static __device__ __forceinline__ void rc_init_rows(RcRows &row, const uint16_t *cdf_init, uint32_t combos, int lane) {
+static __device__ __forceinline__ void rc_init_rows(RcRows &row, const Av1miDevParams &P, const RcTile &T, const uint16_t *cdf_init, uint32_t combos, int lane) {
+  cdf_init = frame_cdf(P, cdf_init, T.tile / (P.tile_rows * P.tile_cols));   // (a lane without a tile has tile 0 and no combos)
   for (int k = 0; k < MAX_COMBOS; k++) {
     const int combo = (combos >> (8 * k)) & 0xFF;
     if (combo == 0xFF) continue;
@@ -1284,7 +1294,7 @@ __global__ void __launch_bounds__(256) rangecode4_tiles_kernel(Av1miDevParams P,
                                                              int tile0 /* chunk-wide index of the launch's first tile; n_tiles and `order` are launch-local */) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const RcTile T = rc_tile(P, n_tiles, streams, stream_len, order, tile0, lane);
-  if (wave == 0) rc_init_rows(g_rc.row, cdf_init, T.live ? tile_combos[T.tile] : 0xFFFFu, lane);
+  if (wave == 0) rc_init_rows(g_rc.row, P, T, cdf_init, T.live ? tile_combos[T.tile] : 0xFFFFu, lane);
   uint32_t rng = 0x8000;    // range stage
   RcOut out(P, slots, T);   // output stage
   __syncthreads();
@@ -1367,7 +1377,7 @@ __global__ void __launch_bounds__(128) rangecode2_tiles_kernel(Av1miDevParams P,
                                                              int tile0 /* chunk-wide index of the launch's first tile; n_tiles and `order` are launch-local */) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const RcTile T = rc_tile(P, n_tiles, streams, stream_len, order, tile0, lane);
-  if (wave == 0) rc_init_rows(g_rc2.row, cdf_init, T.live ? tile_combos[T.tile] : 0xFFFFu, lane);
+  if (wave == 0) rc_init_rows(g_rc2.row, P, T, cdf_init, T.live ? tile_combos[T.tile] : 0xFFFFu, lane);
   uint32_t rng = 0x8000;    // coder
   RcOut out(P, slots, T);
   __syncthreads();

@@ -1524,13 +1524,14 @@ __global__ void __launch_bounds__(WalkSplit<INTER>::value ? 128 : 64) __attribut
   const int tile_mi_r1 = (tile_mi_r0 + TSB * 16 < P.mi_rows) ? tile_mi_r0 + TSB * 16 : P.mi_rows;
   const int tile_mi_c1 = (tile_mi_c0 + TSB * 16 < P.mi_cols) ? tile_mi_c0 + TSB * 16 : P.mi_cols;
   const PIX *frame = src + (size_t)f * P.frame_samples;
-  // adaptive quantisation: the quantiser slots (av1mi_aq_slot) of the tile's superblocks, four bits each - one scalar across the walk
+  // adaptive quantisation: the quantiser slots (av1mi_aq_slot) of the tile's superblocks, five bits each (the frame term's wide set has
+  // 28) - one scalar across the walk
   uint32_t aq_slots = 0;
   if (aq) {
     for (int si = 0; si < TSB * TSB; si++) {
       const int sbr = tr * TSB + si / TSB, sbc = tc * TSB + si % TSB;
       if (sbr < P.sb_rows && sbc < P.sb_cols)
-        aq_slots |= (uint32_t)uniform_i(av1mi_aq_slot((int)aq[(size_t)f * sbs_per_frame + sbr * P.sb_cols + sbc], P.base_q_idx)) << (4 * si);
+        aq_slots |= (uint32_t)uniform_i(av1mi_aq_slot((int)aq[(size_t)f * sbs_per_frame + sbr * P.sb_cols + sbc], P.base_q_idx, P.frame_q != nullptr)) << (5 * si);
     }
   }
   int weight = 0;
@@ -1542,7 +1543,7 @@ __global__ void __launch_bounds__(WalkSplit<INTER>::value ? 128 : 64) __attribut
     SbCtx cx;
     // adaptive quantisation: the superblock's steps, reciprocals and matrix slice - its slot's copy of the parameters (slot 0, the
     // block itself, without; a wave-uniform pointer: the fields stay scalar loads)
-    cx.P = Pd + ((aq_slots >> (4 * si)) & 15u);
+    cx.P = Pd + ((aq_slots >> (5 * si)) & 31u);
     cx.lane = threadIdx.x & 63; cx.sb_x = sbc * 64; cx.sb_y = sbr * 64;
     cx.tox = (si % TSB) * 64; cx.toy = (si / TSB) * 64;
     SbLds *const sbl = (SPLIT && threadIdx.x >= 64) ? SbSel<2>::get() : SbSel<0>::get();   // each wave of a split walk keeps a map of its own
@@ -1656,7 +1657,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(AV1MI_R
       if (x >= P.width || y >= P.height) continue;
       SbCtx cx;
       cx.lane = threadIdx.x; cx.sb_x = x & ~63; cx.sb_y = y & ~63; cx.tox = 0; cx.toy = 0;
-      cx.P = aq ? Pd + uniform_i(av1mi_aq_slot((int)aq[(cx.sb_y >> 6) * P.sb_cols + (cx.sb_x >> 6)], P.base_q_idx)) : Pd;
+      cx.P = aq ? Pd + uniform_i(av1mi_aq_slot((int)aq[(cx.sb_y >> 6) * P.sb_cols + (cx.sb_x >> 6)], P.base_q_idx, P.frame_q != nullptr)) : Pd;
       const int bx = x - cx.sb_x, by = y - cx.sb_y;
       const int bsl = leaf_bsl_at(P, part != nullptr, part ? part[(cx.sb_y >> 6) * P.sb_cols + (cx.sb_x >> 6)] : 0u, cx.sb_x, cx.sb_y, bx, by);
       if (bsl == 0) continue;

@@ -188,9 +188,14 @@ __global__ void __launch_bounds__(64) aq_activity_kernel(Av1miDevParams P, const
 // beta, beta_sum, tpl_strength: the temporal term (tpl_rule.h) - beta per [frame][superblock] and the chunk's sum of it, from
 // av1mi_launch_tpl on the same stream before; strength 0: neither is read and the map is the spatial rule's.  A spatial strength of 0
 // does not read act.
+// F: the frame term (tpl_rule.h "frame"), F.strength 0 = off.  On: the workgroup forms MF from the chunk's n values of betaF
+// (tpl_frame_kernel on the same stream before), then its frame's k_f and q_f - into F.fq.frame_q and into the eight bits of base_q_idx
+// in the frame's header slot - and writes the map q_f + 4 d, the temporal term against the frame's own mean and the clamp against q_f;
+// all q_f when both superblock strengths are 0.
 __global__ void __launch_bounds__(256) aq_map_kernel(Av1miDevParams P, const uint16_t *__restrict__ act, uint8_t *__restrict__ qmap, int strength,
-                                                     const uint16_t *__restrict__ beta, const unsigned long long *__restrict__ beta_sum, int tpl_strength) {
-  __shared__ uint32_t part[4];
+                                                     const uint16_t *__restrict__ beta, const unsigned long long *__restrict__ beta_sum, int tpl_strength,
+                                                     Av1miFqMap F) {
+  __shared__ uint32_t part[4], fpart[4];
   const int f = blockIdx.x, t = threadIdx.x, nsb = P.sb_rows * P.sb_cols;
   const uint16_t *E = act + (size_t)f * nsb;
   uint32_t sum = 0;
@@ -199,6 +204,32 @@ __global__ void __launch_bounds__(256) aq_map_kernel(Av1miDevParams P, const uin
   if ((t & 63) == 0) part[t >> 6] = sum;
   __syncthreads();
   const int M = av1mi_aq_mean(part[0] + part[1] + part[2] + part[3], (uint32_t)nsb);
+  if (F.strength) {
+    uint32_t bf = 0;
+    for (int i = t; i < P.n_frames; i += 256) bf += F.fq.beta[i];
+    for (int o = 32; o > 0; o >>= 1) bf += __shfl_xor(bf, o, 64);
+    if ((t & 63) == 0) fpart[t >> 6] = bf;
+    __syncthreads();
+    const int MF = av1mi_fq_mean((uint64_t)fpart[0] + fpart[1] + fpart[2] + fpart[3], (uint64_t)P.n_frames);
+    const int qf = av1mi_fq_qindex(F.strength, (int)F.fq.beta[f], MF, P.base_q_idx);
+    const int Mbf = tpl_strength ? av1mi_tpl_mean_beta(F.fq.sb_beta_sum[f], (uint64_t)nsb) : 0;
+    for (int i = t; i < nsb; i += 256)
+      qmap[(size_t)f * nsb + i] = (uint8_t)(strength || tpl_strength ? av1mi_fq_sb_qindex(strength, strength ? (int)E[i] : 0, M, tpl_strength,
+                                                                                        tpl_strength ? (int)beta[(size_t)f * nsb + i] : 0, Mbf, qf)
+                                                                    : qf);
+    if (t == 0) {
+      F.fq.frame_q[f] = (uint8_t)qf;
+      if (F.hdr_blob) {
+        uint8_t *h = F.hdr_blob + P.seq_hdr_bytes + (size_t)f * P.hdr_slot_bytes;
+        int bit = F.q_bit[av1mi_frame_is_inter(P, f)];
+        for (int k = 7; k >= 0; k--, bit++) {
+          const uint8_t m = (uint8_t)(0x80 >> (bit & 7));
+          h[bit >> 3] = ((qf >> k) & 1) ? (uint8_t)(h[bit >> 3] | m) : (uint8_t)(h[bit >> 3] & ~m);
+        }
+      }
+    }
+    return;
+  }
   if (!tpl_strength) {
     for (int i = t; i < nsb; i += 256) qmap[(size_t)f * nsb + i] = (uint8_t)av1mi_aq_qindex_of(strength, (int)E[i], M, P.base_q_idx);
     return;
@@ -218,12 +249,17 @@ extern "C" hipError_t av1mi_launch_partition(const Av1miDevParams *P, const void
 }
 
 extern "C" hipError_t av1mi_launch_aq(const Av1miDevParams *P, const void *frames, uint16_t *act, uint8_t *qmap, int strength, const uint16_t *beta,
-                                      const unsigned long long *beta_sum, int tpl_strength, hipStream_t stream) {
+                                      const unsigned long long *beta_sum, int tpl_strength, const Av1miFqMap *fq, hipStream_t stream) {
+  Av1miFqMap F = {};
+  if (fq && fq->strength) {
+    if (!fq->fq.beta || !fq->fq.sb_beta_sum || !fq->fq.frame_q) return hipErrorInvalidValue;
+    F = *fq;
+  }
   dim3 grid(P->sb_rows * P->sb_cols, P->n_frames);
   if (!strength) { }   // the spatial term is 0: no activity pass
   else if (P->bit_depth == 8) hipLaunchKernelGGL(aq_activity_kernel<uint8_t>, grid, dim3(64), 0, stream, *P, (const uint8_t *)frames, act);
   else hipLaunchKernelGGL(aq_activity_kernel<uint16_t>, grid, dim3(64), 0, stream, *P, (const uint16_t *)frames, act);
-  hipLaunchKernelGGL(aq_map_kernel, dim3(P->n_frames), dim3(256), 0, stream, *P, (const uint16_t *)act, qmap, strength, beta, beta_sum, tpl_strength);
+  hipLaunchKernelGGL(aq_map_kernel, dim3(P->n_frames), dim3(256), 0, stream, *P, (const uint16_t *)act, qmap, strength, beta, beta_sum, tpl_strength, F);
   return hipGetLastError();
 }
 

@@ -8,6 +8,9 @@
 // takes one block of frame f and adds its up to four shares into A[f - 1] with 64-bit integer atomics (any order gives the same sums).
 // Stream order is the only dependency between the frames' launches.  tpl_beta_kernel: one wave per (superblock, frame), lane = 16x16
 // block of the superblock: O, P, beta, and beta added into the chunk's sum, from which aq_map_kernel (scene_kernels.hip) takes Mb.
+// tpl_frame_kernel (the frame term, cq_level bits 20-22): one workgroup per frame sums I and I + A over the frame's blocks and beta over
+// its superblocks - 64 bits per lane, a wave reduction, one LDS step, no atomics - and leaves OF, PF, betaF and the sum of beta per frame,
+// from which aq_map_kernel takes the frames' indices.
 // Algorithmic HBM bytes per chunk of n frames: 2 n L b read by the search (L luma samples, b bytes each; the 2R+1-fold re-reads are L1 /
 // L2 hits), 12 n L / 256 written by it, and about 56 n L / 256 moved by the flow and the superblock pass.
 #include <hip/hip_runtime.h>
@@ -87,6 +90,31 @@ __global__ void __launch_bounds__(64) tpl_beta_kernel(Av1miDevParams P, const ui
   }
 }
 
+// the frame's sums (tpl_rule.h "frame"): OF, PF, betaF and the sum of beta over the frame's superblocks, behind tpl_beta_kernel
+__global__ void __launch_bounds__(256) tpl_frame_kernel(Av1miDevParams P, const uint32_t *__restrict__ intra, const unsigned long long *__restrict__ flow,
+                                                        const uint16_t *__restrict__ beta, Av1miFqBlock out) {
+  __shared__ unsigned long long part[3][4];
+  const int nb = av1mi_tpl_blocks(P.width) * av1mi_tpl_blocks(P.height), nsb = P.sb_rows * P.sb_cols;
+  const int f = blockIdx.x, t = threadIdx.x;
+  unsigned long long O = 0, Pv = 0, B = 0;
+  for (int i = t; i < nb; i += 256) {
+    const size_t at = (size_t)f * nb + i;
+    const unsigned long long I = intra[at];
+    O += I; Pv += I + flow[at];
+  }
+  for (int i = t; i < nsb; i += 256) B += beta[(size_t)f * nsb + i];
+  for (int o = 32; o > 0; o >>= 1) { O += __shfl_xor(O, o, 64); Pv += __shfl_xor(Pv, o, 64); B += __shfl_xor(B, o, 64); }
+  if ((t & 63) == 0) { part[0][t >> 6] = O; part[1][t >> 6] = Pv; part[2][t >> 6] = B; }
+  __syncthreads();
+  if (t == 0) {   // (every block has I >= 1: OF >= 1)
+    O = part[0][0] + part[0][1] + part[0][2] + part[0][3];
+    Pv = part[1][0] + part[1][1] + part[1][2] + part[1][3];
+    out.intra_sum[f] = O; out.dep_sum[f] = Pv;
+    out.sb_beta_sum[f] = part[2][0] + part[2][1] + part[2][2] + part[2][3];
+    out.beta[f] = (uint16_t)av1mi_fq_beta(O, Pv);
+  }
+}
+
 template <typename PIX>
 hipError_t launch_tpl(const Av1miDevParams &P, const void *frames, uint32_t *intra, uint32_t *inter, uint32_t *key, unsigned long long *flow,
                       uint16_t *beta, hipStream_t stream) {
@@ -110,4 +138,11 @@ extern "C" hipError_t av1mi_launch_tpl(const Av1miDevParams *P, const void *fram
   if ((P->me_range != 8 && P->me_range != 16) || P->keyint < 1 || P->n_frames < 1 || ((uintptr_t)frames & 15)) return hipErrorInvalidValue;
   return P->bit_depth == 8 ? launch_tpl<uint8_t>(*P, frames, intra, inter, key, flow, beta, stream)
                            : launch_tpl<uint16_t>(*P, frames, intra, inter, key, flow, beta, stream);
+}
+
+extern "C" hipError_t av1mi_launch_tpl_frames(const Av1miDevParams *P, const uint32_t *intra, const unsigned long long *flow, const uint16_t *beta,
+                                              Av1miFqBlock fq, hipStream_t stream) {
+  if (P->n_frames < 1 || !intra || !flow || !beta || !fq.intra_sum) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(tpl_frame_kernel, dim3(P->n_frames), dim3(256), 0, stream, *P, intra, flow, beta, fq);
+  return hipGetLastError();
 }

@@ -1,7 +1,8 @@
 // tpl_rule.h - the temporal-dependency rule of the adaptive quantisation (av1mi_params.cq_level bits 12-14: tpl_strength; DESIGN.md §3
 // item 1d), all integers, for host and device: tpl_kernel.hip runs it per 16x16 block, per superblock and per chunk,
 // tests/host/tpl_rule_host.cpp compiles it for the CPU against the numpy restatement (tests/tpl_ref.py).  Non-normative, like aq_rule.h:
-// the decoder only sees the per-superblock quantiser index.
+// the decoder only sees the per-superblock quantiser index.  The frame term (bits 20-22: fq_strength; §3 item 1e) is at the end of the
+// file, with tests/host/fq_rule_host.cpp and tests/fq_ref.py.
 //
 //   block        16x16 luma samples of the coded size, nbx = ceil(cw / 16) by nby = ceil(ch / 16), coordinates clamped to the frame
 //   intra cost   S = the sum of the block's 256 samples, m = (S + 128) >> 8, I = max(1, sum |x - m|)
@@ -70,6 +71,38 @@ AV1MI_AQ_HD inline int av1mi_tpl_delta(int aq_strength, int E, int M, int tpl_st
 }
 AV1MI_AQ_HD inline int av1mi_tpl_qindex_of(int aq_strength, int E, int M, int tpl_strength, int beta, int Mb, int base) {
   return base + 4 * av1mi_tpl_delta(aq_strength, E, M, tpl_strength, beta, Mb, base);
+}
+
+// ---- the frame term (av1mi_params.cq_level bits 20-22: fq_strength): every frame of the chunk gets a base_q_idx
+// of its own from the same analysis.  Non-normative like the rest: the decoder reads the index from the frame's header.
+//   frame        OF = sum I, PF = sum (I + A) over all nbx nby blocks of the frame, 64 bits; betaF = L(PF) - L(OF) >= 0
+//   chunk        MF = (sum betaF + n / 2) / n over its n frames
+//   step         t = fq_strength (betaF - MF), a = (|t| + 8) >> 4, k = -a for t > 0, else +a; clamped to [AV1MI_FQ_MIN_STEP,
+//                AV1MI_FQ_MAX_STEP], then to [-((base - 1) / 4), (255 - base) / 4]; q_f = base + 4 k - strength 1 is one step of 4 per
+//                doubling of PF / OF against the chunk's mean
+//   superblock   with a spatial or temporal strength as well: the temporal term against the FRAME's mean Mb_f = (sum beta + N / 2) / N
+//                over the frame's N superblocks (the frame term moves the frame, the superblock term redistributes inside it);
+//                d clamped against q_f, index q_f + 4 d
+#define AV1MI_FQ_MAX_STRENGTH 4
+#define AV1MI_FQ_MIN_STEP (-10)
+#define AV1MI_FQ_MAX_STEP 4
+
+// betaF of a frame from OF = sum I and PF = sum (I + A), OF >= 1
+AV1MI_AQ_HD inline int av1mi_fq_beta(uint64_t OF, uint64_t PF) { return av1mi_tpl_log2_q4(PF) - av1mi_tpl_log2_q4(OF); }
+// MF of a chunk from the sum over its n frames
+AV1MI_AQ_HD inline int av1mi_fq_mean(uint64_t sum, uint64_t n) { return (int)((sum + n / 2) / n); }
+// k_f and q_f of a frame
+AV1MI_AQ_HD inline int av1mi_fq_step(int fq_strength, int betaF, int MF, int base) {
+  const int t = fq_strength * (betaF - MF), a = ((t < 0 ? -t : t) + 8) >> 4;
+  int k = t > 0 ? -a : a;
+  k = k < AV1MI_FQ_MIN_STEP ? AV1MI_FQ_MIN_STEP : (k > AV1MI_FQ_MAX_STEP ? AV1MI_FQ_MAX_STEP : k);
+  const int lo = -((base - 1) / 4), hi = (255 - base) / 4;
+  return k < lo ? lo : (k > hi ? hi : k);
+}
+AV1MI_AQ_HD inline int av1mi_fq_qindex(int fq_strength, int betaF, int MF, int base) { return base + 4 * av1mi_fq_step(fq_strength, betaF, MF, base); }
+// the index of a superblock of a frame coded at q_f: av1mi_tpl_qindex_of with the frame's mean and the frame's index
+AV1MI_AQ_HD inline int av1mi_fq_sb_qindex(int aq_strength, int E, int M, int tpl_strength, int beta, int Mb_f, int q_f) {
+  return av1mi_tpl_qindex_of(aq_strength, E, M, tpl_strength, beta, Mb_f, q_f);
 }
 
 #endif

@@ -36,13 +36,15 @@ enum {
 
 typedef struct av1mi_ctx av1mi_ctx;
 
-/* av1mi_params.cq_level carries three values: the CQ level, the strength of the adaptive quantisation's spatial term and the strength
- * of its temporal term */
+/* av1mi_params.cq_level carries four values: the CQ level, the strength of the adaptive quantisation's spatial term, the strength
+ * of its temporal term and the strength of the frame term (every frame its own base_q_idx) */
 #define AV1MI_CQ_AQ(cq, strength) (((uint32_t)(cq) & 0xFFu) | (((uint32_t)(strength) & 7u) << 8))
 #define AV1MI_CQ_AQ_TPL(cq, aq, tpl) (AV1MI_CQ_AQ(cq, aq) | (((uint32_t)(tpl) & 7u) << 12))
+#define AV1MI_CQ_AQ_TPL_FQ(cq, aq, tpl, fq) (AV1MI_CQ_AQ_TPL(cq, aq, tpl) | (((uint32_t)(fq) & 7u) << 20))
 #define AV1MI_CQ_LEVEL(v) ((uint32_t)(v) & 0xFFu)
 #define AV1MI_AQ_STRENGTH(v) (((uint32_t)(v) >> 8) & 7u)
 #define AV1MI_TPL_STRENGTH(v) (((uint32_t)(v) >> 12) & 7u)
+#define AV1MI_FQ_STRENGTH(v) (((uint32_t)(v) >> 20) & 7u)
 /* av1mi_params.enable_lr with the self-guided fit: lr = 2 or 4, sets = a mask over the 16 parameter sets searched (0 = all) */
 #define AV1MI_LR_FIT(lr, sets) ((uint32_t)(lr) | 0x100u | ((uint32_t)(sets) << 16))
 /* av1mi_params.enable_lr bit 10: the Wiener fit, or-ed into a value with a low byte of 1 .. 4 (with or without AV1MI_LR_FIT) */
@@ -81,10 +83,11 @@ typedef struct av1mi_ctx av1mi_ctx;
 
 /* Operating point.  Replaces the reference's single constant
  *   SVT_PARAMS = "--crf 8 --preset 3 --film-grain 20 ... --keyint 240 --lookahead 40"
- * (crates/daemon/src/encode/av1an.rs:14) and `--pix-format yuv420p10le` (av1an.rs:90).  What `--lookahead` buys there has two
- * switches here, both off by default and both over the whole chunk rather than 40 frames: the key frames' temporal filter
- * (me_presearch, AV1MI_ME_TF) and the temporal-dependency term of the adaptive quantisation (cq_level, AV1MI_CQ_AQ_TPL).  There is
- * no per-frame base_q_idx and no B pyramid. */
+ * (crates/daemon/src/encode/av1an.rs:14) and `--pix-format yuv420p10le` (av1an.rs:90).  What `--lookahead` buys there has three
+ * switches here, all off by default and all over the whole chunk rather than 40 frames: the key frames' temporal filter
+ * (me_presearch, AV1MI_ME_TF), the temporal-dependency term of the adaptive quantisation (cq_level, AV1MI_CQ_AQ_TPL) and every
+ * frame's own base_q_idx from the same analysis (cq_level, AV1MI_CQ_AQ_TPL_FQ).  The deblocking level and the quantiser-matrix level do
+ * not follow the frame's index, and there is no B pyramid. */
 typedef struct {
   uint32_t width, height;   /* luma size, even, >= 8, yuv 4:2:0.  Sizes that are not multiples of 8 are coded at the next
                                multiple of 8 (source edge-extended on the device) and signalled exactly, as any AV1 encoder does */
@@ -104,8 +107,21 @@ typedef struct {
                                frames it is going to predict; s (beta - the chunk's mean beta) is subtracted from the spatial term
                                before d is formed - superblocks the rest of the chunk depends on a finer quantiser, superblocks
                                nothing depends on a coarser.  Either strength alone turns delta_q_present on; with keyint = 1
-                               nothing is predicted and the term is 0.  Strengths 5..7 of either, bit 11 and bits 15-31 are refused
-                               with AV1MI_E_INVALID_ARG */
+                               nothing is predicted and the term is 0.
+                               bits 20-22: fq_strength 0..4, the frame term (AV1MI_CQ_AQ_TPL_FQ packs the field):
+                               0 (default) = every frame of the chunk at the index the CQ level maps to; s = 1..4: the same look-ahead
+                               (it runs whatever tpl_strength is) gives every frame betaF = the log2 of (its own cost + what the later
+                               frames take from it) / its own cost, and the frame is coded at base_q_idx + 4 k, k in -10..+4 from
+                               s (betaF - the chunk's mean betaF), s = 1 being one step per doubling - the first frame of a long
+                               interval a finer quantiser, the last frame in front of a key frame, which nothing depends on, a
+                               coarser.  The frame's header carries its index; the coefficient CDFs' q context, CurrentQIndex at the
+                               tile starts and the quantiser follow it.  With a superblock strength as well the temporal term is taken
+                               against the frame's own mean beta and d is clamped against the frame's index.  What stays with the
+                               chunk's index, each an encoder's choice and legal in the stream: the deblocking level and the level
+                               search's centre, both partition thresholds, the quantiser-matrix level, the restoration's lambda, the
+                               inter-partition penalty and the range coder's stage choice.  delta_q_present stays "aq_strength or
+                               tpl_strength".  Strengths 5..7 of any of the three, bits 11, 15-19 and 23-31 are refused with
+                               AV1MI_E_INVALID_ARG */
   uint32_t keyint;          /* "--keyint": 1 = every frame a key frame; N > 1 = a key frame every N frames of a chunk, the
                                frames between are INTER frames predicted from the previous reconstruction (one
                                reference, integer-pel full search; chunks always start with a key frame) */
@@ -351,6 +367,19 @@ int av1mi_aq_qindex(av1mi_ctx *ctx, const av1mi_params *params, const void *fram
  * over the chunk.  AV1MI_E_INVALID_ARG when the strength is 0.  Like av1mi_aq_qindex it looks at the frames it is given. */
 int av1mi_tpl_analysis(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
                        uint32_t *intra, uint32_t *inter, uint32_t *key, uint64_t *flow, uint16_t *beta, uint32_t *mean_beta);
+
+/* ---- the frame term on its own ------------------------------------------------------------------
+ * What av1mi_encode_chunk runs on a chunk's source when av1mi_params.cq_level carries an fq_strength (AV1MI_CQ_AQ_TPL_FQ): the same
+ * launches on the frames it is given, taken as one chunk.  Every output is optional, host memory, one entry per frame: intra_sum =
+ * OF, the sum of I over the frame's 16x16 blocks; dep_sum = PF, the sum of I + A; beta = betaF = 16 log2 (PF / OF) as the analysis
+ * forms it; *mean_beta = MF, its rounded mean over the frames; frame_q = the frame's base_q_idx.  AV1MI_E_INVALID_ARG when the
+ * strength is 0; arguments are checked before a device is touched.  With an fq_strength av1mi_aq_qindex returns the combined map,
+ * the frames' steps included, and av1mi_write_headers the header with the chunk's index as the placeholder the device overwrites. */
+int av1mi_tpl_frame_q(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
+                      uint64_t *intra_sum, uint64_t *dep_sum, uint16_t *beta, uint32_t *mean_beta, uint8_t *frame_q);
+/* The same of the chunk the context encoded last: frame_q[n_frames] and beta[n_frames] (each optional) - all base_q_idx and zeros for
+ * a chunk without the term.  AV1MI_E_INVALID_ARG without a successfully encoded chunk or with another frame count. */
+int av1mi_frame_q_result(const av1mi_ctx *ctx, uint32_t n_frames, uint8_t *frame_q, uint16_t *beta);
 
 /* ---- the key frames' temporal filter on its own --------------------------------------------
  * What av1mi_encode_chunk codes instead of the key frames when av1mi_params.me_presearch carries the filter (AV1MI_ME_TF): the

@@ -10,7 +10,8 @@ use std::os::raw::{c_char, c_int, c_void};
 pub struct Av1miParams {            // include/av1mi.h: av1mi_params
     pub width: u32, pub height: u32, pub bit_depth: u32,
     /// Bits 0-7: the CQ level 1..63; bits 8-10: aq_strength 0..4, activity-adaptive quantisation (`cq_aq` packs the field; 0 = off);
-    /// bits 12-14: tpl_strength 0..4, its temporal-dependency term from a look-ahead over the chunk (`cq_aq_tpl` packs all three; 0 = off).
+    /// bits 12-14: tpl_strength 0..4, its temporal-dependency term from a look-ahead over the chunk (`cq_aq_tpl` packs all three; 0 = off);
+    /// bits 20-22: fq_strength 0..4, every frame its own base_q_idx from the same look-ahead (`cq_aq_tpl_fq` packs all four; 0 = off).
     pub cq_level: u32,
     pub keyint: u32, pub block_log2: u32, pub cdf_update: u32, pub enable_cdef: u32,
     pub cdef_y_pri: u32, pub cdef_y_sec: u32, pub cdef_uv_pri: u32, pub cdef_uv_sec: u32, pub cdef_damping: u32,
@@ -63,6 +64,10 @@ pub const fn cq_aq(cq: u32, strength: u32) -> u32 { (cq & 0xFF) | ((strength & 7
 pub const AV1MI_TPL_MAX_STRENGTH: u32 = 4;
 pub const fn cq_aq_tpl(cq: u32, aq: u32, tpl: u32) -> u32 { cq_aq(cq, aq) | ((tpl & 7) << 12) }
 pub const fn tpl_strength_of(v: u32) -> u32 { (v >> 12) & 7 }
+// include/av1mi.h: AV1MI_CQ_AQ_TPL_FQ / AV1MI_FQ_STRENGTH - the frame term's strength (every frame its own base_q_idx) beside the three
+pub const AV1MI_FQ_MAX_STRENGTH: u32 = 4;
+pub const fn cq_aq_tpl_fq(cq: u32, aq: u32, tpl: u32, fq: u32) -> u32 { cq_aq_tpl(cq, aq, tpl) | ((fq & 7) << 20) }
+pub const fn frame_q_strength_of(v: u32) -> u32 { (v >> 20) & 7 }
 pub const fn cq_level_of(v: u32) -> u32 { v & 0xFF }
 pub const fn aq_strength_of(v: u32) -> u32 { (v >> 8) & 7 }
 // include/av1mi.h: AV1MI_ME_TF / AV1MI_ME_PRESEARCH / AV1MI_TF_FRAMES / AV1MI_TF_STRENGTH - me_presearch carries the pre-search's switch and
@@ -118,6 +123,12 @@ extern "C" {
     pub fn av1mi_film_grain_ar_estimate(ctx: *mut Av1miCtx, params: *const Av1miParams, frames: *const c_void, n_frames: u32, frames_on_device: c_int,
                                         coeffs: *mut i8, table: *mut u8, sigma_table: *mut u8, gain: *mut u32, flat_blocks: *mut u32, sums: *mut i64) -> c_int;
     pub fn av1mi_film_grain_ar_result(ctx: *const Av1miCtx, coeffs: *mut i8, sigma_table: *mut u8, gain: *mut u32) -> c_int;
+    // the frame term (cq_aq_tpl_fq) of `n_frames` frames taken as one chunk: per frame intra_sum, dep_sum, beta and frame_q, the frame's
+    // base_q_idx, and *mean_beta, every output optional (null); and the frame_q[n_frames] / beta[n_frames] of the chunk the context
+    // encoded last
+    pub fn av1mi_tpl_frame_q(ctx: *mut Av1miCtx, params: *const Av1miParams, frames: *const c_void, n_frames: u32, frames_on_device: c_int,
+                             intra_sum: *mut u64, dep_sum: *mut u64, beta: *mut u16, mean_beta: *mut u32, frame_q: *mut u8) -> c_int;
+    pub fn av1mi_frame_q_result(ctx: *const Av1miCtx, n_frames: u32, frame_q: *mut u8, beta: *mut u16) -> c_int;
 }
 
 // Layout pin (include/av1mi.h: av1mi_struct_sizes).  Compile time: the sizes this file was written against (ABI version 8, LP64);
