@@ -39,7 +39,8 @@ ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", 
                "av1mi_free", "av1mi_encode_file", "av1mi_cq_to_qindex", "av1mi_abi_version", "av1mi_write_headers", "av1mi_scene_cuts", "av1mi_job_execute", "av1mi_probe_y4m", "av1mi_chunk_owner", "av1mi_plan_workers", "av1mi_release_caches", "av1mi_struct_sizes", "av1mi_aq_qindex", "av1mi_lf_search_result", "av1mi_lr_fit_result", "av1mi_lr_fit_units", "av1mi_lr_wiener_fit_result", "av1mi_lr_wiener_fit_units", "av1mi_sym_order_result", "av1mi_sym_order_tiles", "av1mi_inter_partition_result", "av1mi_inter_partition_units",
                "av1mi_lr_rd_result", "av1mi_lr_rd_units", "av1mi_temporal_filter", "av1mi_tpl_analysis", "av1mi_film_grain_estimate",
                "av1mi_film_grain_result", "av1mi_film_grain_denoise", "av1mi_film_grain_ar_estimate", "av1mi_film_grain_ar_result",
-               "av1mi_film_grain_denoise_temporal", "av1mi_tpl_frame_q", "av1mi_frame_q_result"]
+               "av1mi_film_grain_denoise_temporal", "av1mi_tpl_frame_q", "av1mi_frame_q_result", "av1mi_quality", "av1mi_ctx_set_quality",
+               "av1mi_quality_result", "av1mi_encode_file_quality"]
 
 
 class Params(C.Structure):
@@ -90,6 +91,11 @@ class ClipInfo(C.Structure):
                 ("color_range", C.c_uint32), ("frames", C.c_uint64)]
 
 
+class PlaneQuality(C.Structure):
+    """include/av1mi.h: av1mi_plane_quality (24 bytes)"""
+    _fields_ = [("sse", C.c_uint64), ("ssim_sum", C.c_int64), ("windows", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 STATE_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p, C.POINTER(JobMetrics))
 PROGRESS_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64)
 
@@ -122,6 +128,10 @@ _lib.av1mi_tpl_analysis.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C
 _lib.av1mi_tpl_frame_q.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                     C.POINTER(C.c_uint16), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)]
 _lib.av1mi_frame_q_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16)]
+_lib.av1mi_quality.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(PlaneQuality), C.POINTER(C.c_int32)]
+_lib.av1mi_ctx_set_quality.argtypes = [C.c_void_p, C.c_uint32]
+_lib.av1mi_quality_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PlaneQuality)]
+_lib.av1mi_encode_file_quality.argtypes = [C.POINTER(Job), PROGRESS_CB, C.c_void_p, C.POINTER(Report), C.POINTER(PlaneQuality)]
 _lib.av1mi_film_grain_estimate.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32),
                                             C.POINTER(C.c_uint8)]
 _lib.av1mi_film_grain_result.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
@@ -445,6 +455,61 @@ def write_headers(params):
     return seq.raw[:n.value], fh.raw[:(bits.value + 7) // 8], bits.value
 
 
+# ------------------------------------------------------------------ quality (include/av1mi.h: av1mi_plane_quality; csrc/ssim_rule.h)
+SSIM_Q = 24                       # a window's value is a Q24 number
+SSIM_WEIGHTS = (0.8, 0.1, 0.1)    # libaom's "all planes" figure: 0.8 Y + 0.1 U + 0.1 V
+
+
+def ssim_windows(n):
+    """the windows along a dimension of n samples"""
+    return (n - 8) // 4 + 1 if n >= 8 else 0
+
+
+def quality_window_grid(width, height):
+    """[(ny, nx)] of the planes Y, U, V of a width x height frame: the window map holds them in this order, each in raster order, dense"""
+    cw, ch = (width + 1) // 2, (height + 1) // 2
+    return [(ssim_windows(height), ssim_windows(width))] + [(ssim_windows(ch), ssim_windows(cw))] * 2
+
+
+def _quality_array(q):
+    """PlaneQuality entries as a numpy structured array with the fields sse (uint64), ssim_sum (int64), windows (uint64: `reserved`
+    carries the high half of a file's sum)"""
+    import numpy as np
+    out = np.zeros(len(q), dtype=[("sse", np.uint64), ("ssim_sum", np.int64), ("windows", np.uint64)])
+    for i, e in enumerate(q):
+        out[i] = (e.sse, e.ssim_sum, e.windows | e.reserved << 32)
+    return out
+
+
+def ssim_of(planes):
+    """Plane sums -> the figures a person reads.  planes: three (sse, ssim_sum, windows) of Y, U, V - rows of the arrays quality() and
+    quality_result() return, a sum of such rows over frames, or encode_file_quality()'s sums.  Returns a dict: y, u, v = ssim_sum /
+    (windows * 2^24), None for a plane without windows; all = 0.8 Y + 0.1 U + 0.1 V over the planes that have windows, the weights
+    renormalised (None without any); db = -10 log10(1 - all), 99.0 at all == 1."""
+    import math
+    vals = [int(p[1]) / (int(p[2]) * float(1 << SSIM_Q)) if int(p[2]) else None for p in planes]
+    wsum = sum(w for w, v in zip(SSIM_WEIGHTS, vals) if v is not None)
+    allp = sum(w * v for w, v in zip(SSIM_WEIGHTS, vals) if v is not None) / wsum if wsum else None
+    db = None if allp is None else (99.0 if allp >= 1.0 else -10.0 * math.log10(1.0 - allp))
+    return dict(y=vals[0], u=vals[1], v=vals[2], all=allp, db=db)
+
+
+def quality_sum(q):
+    """[frame][plane] rows of Context.quality / quality_result -> the three planes' sums over the frames, as ssim_of and psnr_of take them"""
+    return [(int(q["sse"][:, pl].sum()), int(q["ssim_sum"][:, pl].sum()), int(q["windows"][:, pl].sum())) for pl in range(3)]
+
+
+def psnr_of(planes, width, height, bit_depth, n_frames):
+    """Plane sums (as for ssim_of) of n_frames frames -> PSNR in dB: y, u, v per plane and `all` over every sample; 99.0 without error"""
+    import math
+    mx = float((1 << bit_depth) - 1)
+    npx = [width * height, ((width + 1) // 2) * ((height + 1) // 2)]
+    db = lambda sse, n: 99.0 if sse == 0 else 10.0 * math.log10(mx * mx * n / sse)   # noqa: E731
+    sse = [int(p[0]) for p in planes]
+    return dict(y=db(sse[0], n_frames * npx[0]), u=db(sse[1], n_frames * npx[1]), v=db(sse[2], n_frames * npx[1]),
+                all=db(sum(sse), n_frames * (npx[0] + 2 * npx[1])))
+
+
 def _frames_ptr(frames, on_device):
     """(pointer, what keeps it alive) of the frames a pass is given: an int device pointer with on_device, else host bytes-like / numpy"""
     if on_device:
@@ -538,6 +603,43 @@ class Context:
         _raise_for(rc, self.last_error())
         out["mean_beta"] = int(mean.value)
         return out
+
+    def quality(self, params, ref, test, n_frames, on_device=False, want_map=False):
+        """`test` against `ref` on the device (include/av1mi.h: av1mi_quality); both as the frames of scene_cuts.  Returns a numpy
+        structured array [frame][plane] with the fields sse, ssim_sum, windows - and with want_map the window map as well: a list per
+        frame of the three planes' int32 arrays [ny][nx] (quality_window_grid)."""
+        import numpy as np
+        out = (PlaneQuality * (n_frames * 3))()
+        grid = quality_window_grid(params.width, params.height)
+        per_frame = sum(ny * nx for ny, nx in grid)
+        wmap = np.zeros(n_frames * per_frame, dtype=np.int32) if want_map else None
+        aptr, keep_a = _frames_ptr(ref, on_device)
+        bptr, keep_b = _frames_ptr(test, on_device)
+        rc = _lib.av1mi_quality(self._h, C.byref(params), aptr, bptr, n_frames, 1 if on_device else 0, out,
+                                wmap.ctypes.data_as(C.POINTER(C.c_int32)) if want_map else None)
+        _raise_for(rc, self.last_error())
+        q = _quality_array(out).reshape(n_frames, 3)
+        if not want_map:
+            return q
+        maps, at = [], 0
+        for f in range(n_frames):
+            planes = []
+            for ny, nx in grid:
+                planes.append(wmap[at:at + ny * nx].reshape(ny, nx))
+                at += ny * nx
+            maps.append(planes)
+        return q, maps
+
+    def set_quality(self, on):
+        """the encoder's quality switch (include/av1mi.h: av1mi_ctx_set_quality): every later chunk of this context ends with the pass"""
+        _raise_for(_lib.av1mi_ctx_set_quality(self._h, 1 if on else 0), "av1mi_ctx_set_quality")
+
+    def quality_result(self, n_frames):
+        """[frame][plane] sse, ssim_sum, windows of the chunk this context encoded last (include/av1mi.h: av1mi_quality_result): the final
+        reconstruction against the coded source; zeros for a chunk encoded with the switch off"""
+        out = (PlaneQuality * (n_frames * 3))()
+        _raise_for(_lib.av1mi_quality_result(self._h, n_frames, out), "av1mi_quality_result")
+        return _quality_array(out).reshape(n_frames, 3)
 
     def frame_q_result(self, n_frames):
         """(frame_q uint8 [frame], beta uint16 [frame]) of the chunk this context encoded last (include/av1mi.h: av1mi_frame_q_result)"""
@@ -845,7 +947,13 @@ class EncodeParams:
         self.enc = enc
 
 
-def run_mi355x(params, progress=None):
+def encode_file_quality(params, progress=None):
+    """run_mi355x with the quality pass on every chunk (include/av1mi.h: av1mi_encode_file_quality).  Returns (Report, the three planes'
+    sums over all frames of all chunks as the structured array of Context.quality - ssim_of() turns it into figures)."""
+    return run_mi355x(params, progress, _quality=True)
+
+
+def run_mi355x(params, progress=None, _quality=False):
     """Drop-in for `run_av1an(&params)`: blocks until the output file is complete; returns the
     Report on success, raises EncodeFailed / EncodeIo otherwise (never leaves a partial output)."""
     job = Job()
@@ -859,6 +967,10 @@ def run_mi355x(params, progress=None):
     job.params = p
     rep = Report()
     cb = PROGRESS_CB(lambda u, d, t, fps, b: progress(d, t, fps, b)) if progress else C.cast(None, PROGRESS_CB)
+    if _quality:
+        q = (PlaneQuality * 3)()
+        _raise_for(_lib.av1mi_encode_file_quality(C.byref(job), cb, None, C.byref(rep), q))
+        return rep, _quality_array(q)
     rc = _lib.av1mi_encode_file(C.byref(job), cb, None, C.byref(rep))
     _raise_for(rc)
     return rep

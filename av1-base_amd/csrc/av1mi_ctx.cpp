@@ -155,6 +155,10 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
     w.d_lf_sel = reinterpret_cast<uint8_t *>(w.d_lf_err + nf * 3 * AV1MI_LF_CANDS);
     HIPCHK(c, ws_alloc(w, w.h_lf, nf * (3 * AV1MI_LF_CANDS * sizeof(unsigned long long) + 4), true));
   }
+  if (c->quality && (!w.d_quality || !w.h_quality)) {
+    HIPCHK(c, ws_alloc(w, w.d_quality, nf * 3 * 2 * sizeof(unsigned long long)));
+    HIPCHK(c, ws_alloc(w, w.h_quality, nf * 3 * 2 * sizeof(unsigned long long), true));
+  }
   if (p.enable_lr && !w.d_cd) {   // unit choices and sums for three planes (enable_lr 3 / 4) of 64x64 units, whichever value and unit size
                                   // this chunk has: the buffers stay with the geometry while enable_lr changes
     HIPCHK(c, ws_alloc(w, w.d_cd, nf * frame_bytes));
@@ -241,7 +245,12 @@ void av1mi::release_streams() {
 
 // A context that goes back to av1mi_encode_file's cache forgets the capacity multiplier its last job's content raised (it would
 // otherwise size - or, at the limit, refuse - an unrelated job's workspace by it); the next chunk reallocates at scale 1.
-void av1mi::recycle_ctx(av1mi_ctx *c) { if (c) c->cap_scale = 1; }
+// ... and the quality switch a job set on it.
+void av1mi::recycle_ctx(av1mi_ctx *c) { if (c) { c->cap_scale = 1; c->quality = false; } }
+
+av1mi_plane_quality av1mi::plane_quality(const unsigned long long *q, const Av1miQualityGeom &G, int plane) {
+  return { q[0], (int64_t)q[1], av1mi_quality_windows(G, plane), 0 };
+}
 
 extern "C" {
 
@@ -611,6 +620,46 @@ int av1mi_tpl_frame_q(av1mi_ctx *c, const av1mi_params *params, const void *fram
   for (uint32_t f = 0; f < n_frames; f++) sum += bf[f];
   if (beta) memcpy(beta, bf.data(), (size_t)n_frames * 2);
   if (mean_beta) *mean_beta = (uint32_t)av1mi_fq_mean(sum, n_frames);
+  return AV1MI_OK;
+}
+
+// One chunk against another on the device (quality_kernel.hip), both in the callers' tight layout as the scene-cut pass takes its frames.
+int av1mi_quality(av1mi_ctx *c, const av1mi_params *params, const void *ref, const void *test, uint32_t n_frames, int frames_on_device,
+                  av1mi_plane_quality *out, int32_t *window_map) {
+  if (!c || !params || !ref || !test || !out || n_frames == 0) return AV1MI_E_INVALID_ARG;
+  av1mi_params size;   // only the size and the depth matter: whatever else the caller's parameters say is not looked at
+  av1mi_default_params(&size, params->width, params->height, params->bit_depth);
+  Pass t(c, &size);
+  if (const int rc = t.open(c, n_frames, true, nullptr, frames_on_device ? (uintptr_t)ref | (uintptr_t)test : 0)) return rc;
+  const Resolved &r = t.r;
+  const Av1miQualityGeom G = av1mi_quality_geom((int)r.p.width, (int)r.p.height, (int)r.p.width, (int)r.p.height, (int)r.p.bit_depth);
+  const size_t n_sums = (size_t)n_frames * 3 * 2, n_map = (size_t)n_frames * G.map_frame;
+  unsigned long long *d_sums = nullptr;
+  int32_t *d_map = nullptr;
+  if (t.alloc(d_sums, n_sums * sizeof(unsigned long long))) t.e = hipMemsetAsync(d_sums, 0, n_sums * sizeof(unsigned long long), t.stream);
+  if (window_map) t.alloc(d_map, n_map * sizeof(int32_t));
+  const void *a = coded_frames(t, r, ref, n_frames, frames_on_device, false, false).tight;
+  const void *b = coded_frames(t, r, test, n_frames, frames_on_device, false, false).tight;
+  if (t.ok()) t.e = av1mi_launch_quality(&G, a, b, (int)n_frames, d_sums, d_map, t.stream);
+  std::vector<unsigned long long> sums(n_sums, 0);
+  to_host(t, sums.data(), d_sums, n_sums * sizeof(unsigned long long));
+  to_host(t, window_map, d_map, n_map * sizeof(int32_t));
+  const int rc = t.finish(c, "quality");   // (drains the stream: `sums` has arrived)
+  if (rc != AV1MI_OK) return rc;
+  for (size_t i = 0; i < (size_t)n_frames * 3; i++) out[i] = plane_quality(&sums[i * 2], G, (int)(i % 3));
+  return AV1MI_OK;
+}
+
+int av1mi_ctx_set_quality(av1mi_ctx *c, uint32_t on) {
+  if (!c) return AV1MI_E_INVALID_ARG;
+  c->quality = on != 0;
+  return AV1MI_OK;
+}
+
+// The quality of the context's last chunk: what download_chunk kept, zeros for a chunk encoded with the switch off.
+int av1mi_quality_result(const av1mi_ctx *c, uint32_t n_frames, av1mi_plane_quality *out) {
+  if (!c || !out || !c->last.n_frames || n_frames != c->last.n_frames) return AV1MI_E_INVALID_ARG;
+  memcpy(out, c->last.quality.data(), (size_t)n_frames * 3 * sizeof(av1mi_plane_quality));
   return AV1MI_OK;
 }
 

@@ -80,6 +80,9 @@ struct Workspace {
   unsigned long long *d_lf_err = nullptr;    // deblocking level search: per [frame][plane] the 16 candidates' squared errors, and behind
   uint8_t *d_lf_sel = nullptr;               // them, in the same block, per frame the four levels; h_lf: where one copy lands both
   uint8_t *h_lf = nullptr;
+  // the quality pass inside the encoder (av1mi_ctx_set_quality), on first use: per [frame][plane] the squared error and the sum of
+  // window values (av1mi_launch_quality), and where one copy lands them
+  unsigned long long *d_quality = nullptr, *h_quality = nullptr;
   uint8_t *h_out = nullptr;            // host staging (pinned), for when the caller's buffer cannot be page-locked
   // Page-locked host side of the small transfers.  The chunk constants - header blob, default CDFs, parameters - are the same for
   // every chunk of a job: h_hdr / h_cdf / h_params hold what d_hdr / d_cdf / d_params hold, and prepare_chunk uploads only what differs.
@@ -130,6 +133,8 @@ struct LastChunk {
   // its frames' base_q_idx and betaF (av1mi_frame_q_result): the chunk's index and zeros without the frame term
   std::vector<uint8_t> frame_q;
   std::vector<uint16_t> frame_beta;
+  // its quality per [frame][plane] (av1mi_quality_result): zeros for a chunk encoded with the switch off
+  std::vector<av1mi_plane_quality> quality;
 };
 #define AV1MI_CDF_ALL 256
 // the records of the film-grain estimate over n_frames frames: the whole 16x16 blocks of the signalled size
@@ -161,6 +166,7 @@ struct av1mi_ctx {
   Av1miDevParams P = {};
   bool sym_order = true;          // AV1MI_SYM_ORDER, read when the context is made: 0 = symbolize in natural tile order everywhere
   bool part_inter = false;        // this chunk's inter frames are partitioned from the search's node costs (partition_search = 2)
+  bool quality = false;           // av1mi_ctx_set_quality: every chunk ends with the quality pass on its final frames
   av1mi::LastChunk last;
 };
 
@@ -184,6 +190,8 @@ void bind_workspace(Av1miDevParams &P, const Resolved &r, const Workspace &w);
 void *pin_acquire(size_t bytes);
 // What av1mi_file.cpp's job and caches need of the context and the two pools:
 void recycle_ctx(av1mi_ctx *c);   // a context on its way into the cache of idle contexts
+// the host's part of a plane's quality: the sums as av1mi_launch_quality left them at q[0 .. 1], and the plane's windows
+av1mi_plane_quality plane_quality(const unsigned long long *q, const Av1miQualityGeom &G, int plane);
 void expect_blocks(unsigned n);   // so many page-locked blocks may wait for a job's writer at once: park that many
 void release_streams();           // destroys the stream sets destroyed contexts left in the pool
 void release_buffers();           // frees the page-locked blocks av1mi_free() put back

@@ -157,6 +157,7 @@ struct Chunk {
   av1mi_buf out = { nullptr, 0 };
   std::vector<uint32_t> sizes;
   av1mi_report rep = {};
+  std::vector<av1mi_plane_quality> quality;   // per [frame][plane], where the job asks for it (av1mi_encode_file_quality)
   int rc = 0;
   Chunk(PinnedPool &pl, size_t bytes) : pool(pl), slot(pl.acquire(bytes)) {}
   void release_slot() { if (slot) pool.release(slot); slot = nullptr; }
@@ -268,8 +269,15 @@ void read_scene_chunks(FileJob &j, ChunkPipeline &pipe, av1mi_ctx *det_ctx, cons
   if (cur->n_frames > 0 && !j.first_err) j.submit(pipe, std::move(cur));
 }
 
-void add_report(av1mi_report &tot, const Chunk &ck) {
+// ... and the planes' quality sums, where the job has them: the windows of a long clip outgrow 32 bits, `reserved` carries the high half
+void add_report(av1mi_report &tot, av1mi_plane_quality *sum, const Chunk &ck) {
   const av1mi_report &r = ck.rep;
+  for (size_t i = 0; sum && i < ck.quality.size(); i++) {
+    av1mi_plane_quality &s = sum[i % 3];
+    const uint64_t n = ((uint64_t)s.reserved << 32 | s.windows) + ck.quality[i].windows;
+    s.sse += ck.quality[i].sse; s.ssim_sum += ck.quality[i].ssim_sum;
+    s.windows = (uint32_t)n; s.reserved = (uint32_t)(n >> 32);
+  }
   tot.frames += ck.n_frames; tot.bytes += r.bytes; tot.n_symbols += r.n_symbols;
   tot.gpus_used |= r.gpus_used;
   for (int p = 0; p < 3; p++) tot.sse[p] += r.sse[p];
@@ -330,6 +338,11 @@ extern "C" void av1mi_release_caches(void) {
 }
 
 extern "C" int av1mi_encode_file(const av1mi_job *job, av1mi_progress_cb cb, void *user, av1mi_report *total) {
+  return av1mi_encode_file_quality(job, cb, user, total, nullptr);
+}
+
+// sum: null, or the job's quality sums - its workers' contexts then run the quality pass on every chunk (give_ctx switches it off again)
+extern "C" int av1mi_encode_file_quality(const av1mi_job *job, av1mi_progress_cb cb, void *user, av1mi_report *total, av1mi_plane_quality sum[3]) {
   if (!job || !job->input_path || !job->output_path) return AV1MI_E_INVALID_ARG;
   FileJob j;   // every return below releases what the job holds by then
   const Laps &laps = j.laps;
@@ -350,6 +363,7 @@ extern "C" int av1mi_encode_file(const av1mi_job *job, av1mi_progress_cb cb, voi
   const uint32_t workers = (uint32_t)planned;
   for (uint32_t i = 0; i < workers; i++)
     if ((rc = j.take(dev_of[i]))) return rc;
+  if (sum) for (auto &e : j.ctxs) (void)av1mi_ctx_set_quality(e.second, 1);
   laps.lap("contexts created");
   if (scene_mode && (rc = j.take(dev_of[0]))) return rc;   // the reader thread's own context for the scene-cut pass; gets no worker thread
   av1mi_ctx *det_ctx = scene_mode ? j.ctxs.back().second : nullptr;
@@ -373,11 +387,16 @@ extern "C" int av1mi_encode_file(const av1mi_job *job, av1mi_progress_cb cb, voi
   uint32_t frames_done = 0;
   const uint32_t keyint = prm.keyint ? prm.keyint : 1;
   av1mi_report tot = {};
+  av1mi_plane_quality qtot[3] = {};
   auto encode = [&](ChunkPtr &ck, unsigned worker) {
     ck->sizes.resize(ck->n_frames);
     av1mi_params cp = prm;
     cp.first_frame = prm.first_frame + ck->first_frame;
     ck->rc = av1mi_encode_chunk(j.ctxs[worker].second, &cp, ck->slot->p, ck->n_frames, 0, &ck->out, ck->sizes.data(), nullptr, &ck->rep);
+    if (sum && !ck->rc) {
+      ck->quality.resize((size_t)ck->n_frames * 3);
+      ck->rc = av1mi_quality_result(j.ctxs[worker].second, ck->n_frames, ck->quality.data());
+    }
     if (laps.on) fprintf(stderr, "[av1mi_encode_file] %8.2f ms  chunk %u encoded (h2d %.2f total %.2f ms on the device)\n", laps.ms(), ck->index, ck->rep.ms_h2d, ck->rep.ms_total);
     ck->release_slot();   // (av1mi_encode_chunk returns after its upload has completed)
   };
@@ -391,7 +410,7 @@ extern "C" int av1mi_encode_file(const av1mi_job *job, av1mi_progress_cb cb, voi
       off += ck->sizes[f];
     }
     frames_done += ck->n_frames;
-    add_report(tot, *ck);
+    add_report(tot, sum ? qtot : nullptr, *ck);
     if (cb) {
       const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
       // total: the clip's length when the input is a regular file, else the frames read so far
@@ -423,5 +442,6 @@ extern "C" int av1mi_encode_file(const av1mi_job *job, av1mi_progress_cb cb, voi
     tot.chunks = j.n_chunks;
     *total = tot;
   }
+  if (sum) memcpy(sum, qtot, sizeof(qtot));
   return AV1MI_OK;
 }

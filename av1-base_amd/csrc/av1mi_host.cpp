@@ -99,6 +99,7 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   // the self-guided fit's sums, errors, records and codes, once per attempt at the chunk
   if (P.lr_fit_code) HIPCHK(c, hipMemsetAsync(w.d_fit, 0, av1mi_lr_fit_bytes(fit_chunk_units(r, n_frames)), s));
   if (P.lr_wfit_code) HIPCHK(c, hipMemsetAsync(w.d_wfit, 0, av1mi_lr_wfit_bytes(fit_chunk_units(r, n_frames)), s));
+  if (c->quality) HIPCHK(c, hipMemsetAsync(w.d_quality, 0, (size_t)n_frames * 3 * 2 * sizeof(unsigned long long), s));   // the quality pass adds
   HIPCHK(c, hipEventRecord(c->ev[EV_START], s));
   // the caller's frames are used in place if they are on the device at the coded size; a padded chunk arrives in the stage, and so does
   // a chunk the film-grain denoiser will write d_src from
@@ -182,11 +183,24 @@ static int entropy_code(av1mi_ctx *c, uint32_t from, uint32_t n_frames, bool by_
   return AV1MI_OK;
 }
 
+// The chunk's planes as the quality pass sees them: stored at the coded size, compared over the signalled one
+static Av1miQualityGeom quality_geom(const Av1miDevParams &P) { return av1mi_quality_geom(P.true_w, P.true_h, P.width, P.height, P.bit_depth); }
+
+// With the context's quality switch on: the final frames against the coded source, one launch over the chunk on the second stream behind
+// the squared error's (off: nothing)
+static int quality_beside_sse(av1mi_ctx *c, const void *src) {
+  if (!c->quality) return AV1MI_OK;
+  const Av1miQualityGeom G = quality_geom(c->P);
+  HIPCHK(c, av1mi_launch_quality(&G, src, c->ws.d_fin, c->P.n_frames, c->ws.d_quality, nullptr, c->stream2));
+  return AV1MI_OK;
+}
+
 // The second stream beside the range coder, once symbolize is done: the squared error of the final frames
 static int sse_beside_range_coder(av1mi_ctx *c, const void *src) {
   HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev[EV_SYM_DONE], 0));
   HIPCHK(c, hipEventRecord(c->ev[EV_CDEF_START], c->stream2));
   HIPCHK(c, av1mi_launch_sse(&c->P, src, c->ws.d_fin, c->ws.d_sse, c->stream2));
+  if (const int rc = quality_beside_sse(c, src)) return rc;
   HIPCHK(c, hipEventRecord(c->ev[EV_CDEF_DONE], c->stream2));
   return AV1MI_OK;
 }
@@ -223,6 +237,7 @@ static int schedule_all_key(av1mi_ctx *c, const void *src, uint32_t n_frames) {
   HIPCHK(c, hipEventRecord(c->ev[EV_CDEF_START], s2));
   HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, w.d_fin, w.d_blk, sse_in_cdef ? src : nullptr, sse_in_cdef ? w.d_sse : nullptr, 0, n, s2));
   if (!sse_in_cdef) HIPCHK(c, av1mi_launch_sse(&P, src, w.d_fin, w.d_sse, s2));
+  if (const int rc = quality_beside_sse(c, src)) return rc;
   HIPCHK(c, hipEventRecord(c->ev[EV_CDEF_DONE], s2));
   return AV1MI_OK;
 }
@@ -380,6 +395,7 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
   }
   const unsigned long long *sse = w.h_sse;
   if (e1 == hipSuccess) e1 = hipMemcpyAsync(w.h_sse, w.d_sse, (size_t)n_frames * 24, hipMemcpyDeviceToHost, s);
+  if (e1 == hipSuccess && c->quality) e1 = hipMemcpyAsync(w.h_quality, w.d_quality, (size_t)n_frames * 3 * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
   // the level search's tables and levels (record_last_chunk keeps them): one more small copy before the wait below.  The levels sit behind the
   // whole workspace's tables, not behind this chunk's: two copies when the chunk is shorter
   const size_t lf_err_bytes = (size_t)n_frames * 3 * AV1MI_LF_CANDS * sizeof(unsigned long long);
@@ -467,6 +483,11 @@ static LastChunk record_last_chunk(const av1mi_ctx *c, const Resolved &r, uint32
     const Av1miFqBlock H = av1mi_fq_split(w.h_fq, n_frames);
     memcpy(L.frame_q.data(), H.frame_q, n_frames);
     memcpy(L.frame_beta.data(), H.beta, (size_t)n_frames * sizeof(uint16_t));
+  }
+  L.quality.assign((size_t)n_frames * 3, av1mi_plane_quality{});
+  if (c->quality) {
+    const Av1miQualityGeom G = quality_geom(P);
+    for (size_t i = 0; i < L.quality.size(); i++) L.quality[i] = plane_quality(w.h_quality + i * 2, G, (int)(i % 3));
   }
   if (P.part_map) { L.pi_keys = c->part_inter; L.pi_frames = n_frames; L.pi_units = (uint32_t)(P.b8_rows * P.b8_cols); L.pi_sbs = (uint32_t)(P.sb_rows * P.sb_cols); }
   return L;

@@ -104,6 +104,38 @@ struct Av1miFqMap {
   uint8_t *hdr_blob;
 };
 
+// What the quality pass (quality_kernel.hip, ssim_rule.h) compares: two chunks of one layout, given explicitly - a frame every
+// frame_samples samples, and per plane where it starts in the frame, its row stride (all in samples) and its h x w at the signalled size.
+// The callers' tight layout and the encoder's buffers at the coded size are the two uses.  map_at: where a plane's windows start in a
+// frame's part of the window map, map_frame the windows of a frame over its three planes
+struct Av1miQualityGeom {
+  size_t frame_samples;
+  size_t off[3];
+  int stride[3], w[3], h[3];
+  uint32_t map_at[3], map_frame;
+  int bit_depth;
+};
+// a plane's windows (ssim_rule.h: av1mi_ssim_windows both ways)
+inline uint32_t av1mi_quality_windows(const Av1miQualityGeom &G, int pl) {
+  const int ny = G.h[pl] >= 8 ? (G.h[pl] - 8) / 4 + 1 : 0, nx = G.w[pl] >= 8 ? (G.w[pl] - 8) / 4 + 1 : 0;
+  return (uint32_t)ny * (uint32_t)nx;
+}
+// planar 4:2:0 frames stored at cw x ch with the signalled w x h inside them: cw x ch = w x h is the callers' tight layout
+inline Av1miQualityGeom av1mi_quality_geom(int w, int h, int cw, int ch, int bit_depth) {
+  Av1miQualityGeom G = {};
+  G.frame_samples = (size_t)cw * ch * 3 / 2;
+  G.bit_depth = bit_depth;
+  for (int pl = 0; pl < 3; pl++) {
+    G.off[pl] = pl == 0 ? 0 : (size_t)cw * ch + (pl == 2 ? (size_t)(cw / 2) * (ch / 2) : 0);
+    G.stride[pl] = pl ? cw / 2 : cw;
+    G.w[pl] = pl ? (w + 1) / 2 : w;
+    G.h[pl] = pl ? (h + 1) / 2 : h;
+    G.map_at[pl] = G.map_frame;
+    G.map_frame += av1mi_quality_windows(G, pl);
+  }
+  return G;
+}
+
 extern "C" {
 // ---- whole chunk (or call): all P->n_frames frames
 // split masks of every superblock (partition_kernel)
@@ -159,6 +191,11 @@ hipError_t av1mi_launch_luma_sad(const Av1miDevParams *P, const void *frames, co
 hipError_t av1mi_launch_pad(const void *in, void *out, int w, int h, int cw, int ch, int bit_depth, int n_frames, int crop, hipStream_t stream);
 // squared error of a against b into sse[frame][plane] (added)
 hipError_t av1mi_launch_sse(const Av1miDevParams *P, const void *a, const void *b, unsigned long long *sse, hipStream_t stream);
+// the quality pass (quality_kernel.hip, ssim_rule.h): n_frames frames of `a`, the reference, against `b`, both laid out as G says.
+// sums[(frame * 3 + plane) * 2 + 0 / 1]: the plane's squared error and its sum of window values (a two's-complement int64), both ADDED -
+// zeroed by the caller.  map: null, or per frame G->map_frame window values, every one written
+hipError_t av1mi_launch_quality(const Av1miQualityGeom *G, const void *a, const void *b, int n_frames, unsigned long long *sums, int32_t *map,
+                                hipStream_t stream);
 // stage 0: the frames' layout, sizes and the chunk record; stage 1: headers and tiles into `out`
 hipError_t av1mi_launch_pack(const Av1miDevParams *P, const uint8_t *slots, const uint32_t *tile_bytes, uint32_t *tile_off,
                              uint32_t *frame_size, uint32_t *payload_size, unsigned long long *frame_off, const uint8_t *hdr_blob,

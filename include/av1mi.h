@@ -518,6 +518,30 @@ uint32_t av1mi_sym_order_tiles(const av1mi_ctx *ctx);
 int av1mi_inter_partition_result(const av1mi_ctx *ctx, uint32_t n_frames, uint32_t *masks, uint64_t *keys);
 uint32_t av1mi_inter_partition_units(const av1mi_ctx *ctx);
 
+/* ---- quality: SSIM and exact squared error of one chunk against another, on the device ---------------------------------------
+ * The measure is libaom's aom_ssim2 in integers (av1-base_amd/csrc/ssim_rule.h): 8x8 windows at every (4 i, 4 j) of a plane at the
+ * signalled size - ny = (h - 8) / 4 + 1 rows of them for h >= 8, else none; nx likewise - each window's value truncated to Q24, so that
+ * every implementation agrees bit for bit.  Per frame and plane (chroma (h + 1) / 2 x (w + 1) / 2): sse = sum (a - b)^2 over the whole
+ * plane, exact; ssim_sum = the sum of the window values; windows = ny * nx (0 for a plane under 8 samples either way: the chroma of
+ * an 8x8 frame).  The SSIM a person reads is ssim_sum / (windows * 2^24), formed by the caller. */
+typedef struct { uint64_t sse; int64_t ssim_sum; uint32_t windows; uint32_t reserved; } av1mi_plane_quality;   /* 24 bytes */
+
+/* `test` against `ref`: two chunks of n_frames frames in the callers' layout (tight planar frames as for av1mi_scene_cuts, both host
+ * memory or both 16-byte aligned device memory).  Of the parameters only width, height and bit_depth matter.  out[f * 3 + plane]: frame
+ * f's plane.  window_map (optional, host memory): per frame, Y then U then V, each plane's ny * nx window values in raster order, dense -
+ * n_frames * (the three planes' windows) entries.  Null arguments, n_frames == 0 and misaligned device pointers are
+ * AV1MI_E_INVALID_ARG before a device is touched. */
+int av1mi_quality(av1mi_ctx *ctx, const av1mi_params *params, const void *ref, const void *test, uint32_t n_frames, int frames_on_device,
+                  av1mi_plane_quality *out, int32_t *window_map);
+/* The same inside the encoder, default off: with `on` != 0 every chunk the context encodes from then on ends with one more launch, the
+ * final reconstruction against the coded source (what av1mi_report.sse is taken against), beside the squared-error launch; the
+ * bitstream does not depend on the switch. */
+int av1mi_ctx_set_quality(av1mi_ctx *ctx, uint32_t on);
+/* out[f * 3 + plane] of the context's last successfully encoded chunk; zeros (windows = 0) for a chunk encoded with the switch off.  The
+ * values arrive with the chunk's other small results: the call only copies them.  AV1MI_E_INVALID_ARG without such a chunk or if
+ * n_frames is not its frame count. */
+int av1mi_quality_result(const av1mi_ctx *ctx, uint32_t n_frames, av1mi_plane_quality *out);
+
 /* ---- the drop-in for `run_av1an` ---------------------------------------------------------
  * Replaces  pub fn run_av1an(params: &Av1anEncodeParams) -> Result<(), EncodeError>
  * (crates/daemon/src/encode/av1an.rs:126-139), called from JobExecutor::execute through
@@ -550,6 +574,10 @@ typedef struct {
 int av1mi_probe_y4m(const char *path, av1mi_clip_info *info);
 
 int av1mi_encode_file(const av1mi_job *job, av1mi_progress_cb cb, void *user, av1mi_report *total);
+/* av1mi_encode_file with the quality switch on in its workers' contexts (they go back to the cache with it off): sum[plane] = the three
+ * planes' sse, ssim_sum and windows added up over all frames of all chunks; the output file is the one av1mi_encode_file writes.
+ * sum == NULL is av1mi_encode_file. */
+int av1mi_encode_file_quality(const av1mi_job *job, av1mi_progress_cb cb, void *user, av1mi_report *total, av1mi_plane_quality sum[3]);
 
 /* av1mi_encode_file keeps its idle contexts (streams + HBM workspace) and pinned host buffers for the next job of the process -
  * the daemon encodes job after job (job_executor.rs:266-437), and setting them up costs more than a short clip's encode.

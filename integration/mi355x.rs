@@ -55,6 +55,22 @@ pub struct Av1miReport {            // fills JobMetrics.{fps, frames_encoded, ps
     pub ms_d2h: f32, pub ms_total: f32, pub ms_symbolize: f32, pub n_symbols: u64,
     pub max_tile_symbols: u32, pub cap_scale: u32, pub chunks: u32, pub gpus_used: u32,
 }
+#[repr(C)]
+#[derive(Default, Clone, Copy)]
+pub struct Av1miPlaneQuality {      // include/av1mi.h: av1mi_plane_quality - fills JobMetrics.ssim (metrics.rs:12-30)
+    pub sse: u64, pub ssim_sum: i64,
+    pub windows: u32, pub reserved: u32,   // in av1mi_encode_file_quality's sums `reserved` is the high half of the window count
+}
+/// Plane sums (Y, U, V) -> libaom's "all planes" SSIM, 0.8 Y + 0.1 U + 0.1 V: a window's value is a Q24 number; a plane without windows
+/// drops out and the weights are renormalised; None without any window.
+pub fn ssim_all(sum: &[Av1miPlaneQuality; 3]) -> Option<f64> {
+    let (mut v, mut wsum) = (0.0f64, 0.0f64);
+    for (q, wt) in sum.iter().zip([0.8f64, 0.1, 0.1]) {
+        let n = ((q.reserved as u64) << 32) | q.windows as u64;
+        if n > 0 { v += wt * q.ssim_sum as f64 / (n as f64 * (1u64 << 24) as f64); wsum += wt; }
+    }
+    if wsum > 0.0 { Some(v / wsum) } else { None }
+}
 // include/av1mi.h: AV1MI_CQ_AQ / AV1MI_CQ_LEVEL / AV1MI_AQ_STRENGTH - cq_level carries the CQ level and the adaptive quantisation's strength
 pub const AV1MI_AQ_MAX_STRENGTH: u32 = 4;
 // include/av1mi.h: AV1MI_LR_WIENER_FIT - or-ed into enable_lr
@@ -104,6 +120,14 @@ extern "C" {
     fn av1mi_struct_sizes(sizes: *mut u32, cap: u32) -> u32;
     fn av1mi_default_params(p: *mut Av1miParams, w: u32, h: u32, bit_depth: u32);
     fn av1mi_encode_file(job: *const Av1miJob, cb: ProgressCb, user: *mut c_void, total: *mut Av1miReport) -> c_int;
+    // av1mi_encode_file with the quality pass on every chunk: sum[3] = the planes' sse, ssim_sum and windows over the whole file
+    fn av1mi_encode_file_quality(job: *const Av1miJob, cb: ProgressCb, user: *mut c_void, total: *mut Av1miReport, sum: *mut Av1miPlaneQuality) -> c_int;
+    // `test` against `reference`, two chunks of `n_frames` tight planar frames: out[n_frames * 3] per frame and plane, window_map (optional,
+    // null) every window's Q24 value; the encoder's switch for the same pass at the end of every chunk, and its result for the last chunk
+    pub fn av1mi_quality(ctx: *mut Av1miCtx, params: *const Av1miParams, reference: *const c_void, test: *const c_void, n_frames: u32,
+                         frames_on_device: c_int, out: *mut Av1miPlaneQuality, window_map: *mut i32) -> c_int;
+    pub fn av1mi_ctx_set_quality(ctx: *mut Av1miCtx, on: u32) -> c_int;
+    pub fn av1mi_quality_result(ctx: *const Av1miCtx, n_frames: u32, out: *mut Av1miPlaneQuality) -> c_int;
     // the film-grain estimate of `n_frames` frames taken as one chunk: table[24] and counts[24] as [plane][bin], blocks 4 bytes per whole
     // 16x16 block and frame { bin, v_y, v_u, v_v }, every output optional (null); and the table of a context's last chunk
     pub fn av1mi_film_grain_estimate(ctx: *mut Av1miCtx, params: *const Av1miParams, frames: *const c_void, n_frames: u32, frames_on_device: c_int,
@@ -138,6 +162,7 @@ pub const AV1MI_ABI_VERSION: u32 = 8;
 const _: () = assert!(std::mem::size_of::<Av1miParams>() == 36 * 4);
 const _: () = assert!(std::mem::size_of::<Av1miJob>() == 3 * 8 + 3 * 4 + 36 * 4);
 const _: () = assert!(std::mem::size_of::<Av1miReport>() == 120);
+const _: () = assert!(std::mem::size_of::<Av1miPlaneQuality>() == 24);
 pub fn check_layout() -> Result<(), EncodeError> {
     static ONCE: std::sync::OnceLock<bool> = std::sync::OnceLock::new();
     let ok = *ONCE.get_or_init(|| unsafe {
@@ -152,6 +177,18 @@ pub fn check_layout() -> Result<(), EncodeError> {
 
 /// Same contract as `run_av1an` (av1an.rs:126-139): blocks until `output_path` is complete.
 pub fn run_mi355x(params: &Av1anEncodeParams, cq_level: u32) -> Result<(), EncodeError> {
+    encode(params, cq_level, None)
+}
+
+/// The same encode - the output file is byte for byte the same - with the quality pass on every chunk: returns the file's all-planes
+/// SSIM of the reconstruction against the coded source, which the caller stores in `JobMetrics.ssim` beside `psnr`.
+pub fn run_mi355x_with_ssim(params: &Av1anEncodeParams, cq_level: u32) -> Result<Option<f32>, EncodeError> {
+    let mut sum = [Av1miPlaneQuality::default(); 3];
+    encode(params, cq_level, Some(&mut sum))?;
+    Ok(ssim_all(&sum).map(|v| v as f32))
+}
+
+fn encode(params: &Av1anEncodeParams, cq_level: u32, sum: Option<&mut [Av1miPlaneQuality; 3]>) -> Result<(), EncodeError> {
     let c = |p: &std::path::Path| CString::new(p.as_os_str().as_encoded_bytes()).map_err(|e| EncodeError::Io(std::io::Error::other(e)));
     check_layout()?;
     let (i, o, t) = (c(&params.input_path)?, c(&params.output_path)?, c(&params.temp_chunks_dir)?);
@@ -167,7 +204,11 @@ pub fn run_mi355x(params: &Av1anEncodeParams, cq_level: u32) -> Result<(), Encod
     let job = Av1miJob { input_path: i.as_ptr(), output_path: o.as_ptr(), temp_dir: t.as_ptr(),
                          workers: params.concurrency.av1an_workers, chunk_frames: 0 /* scene-cut chunks */, gpu_mask: 0, params: p };
     let mut rep = Av1miReport::default();
-    match unsafe { av1mi_encode_file(&job, None, std::ptr::null_mut(), &mut rep) } {
+    let rc = match sum {
+        Some(q) => unsafe { av1mi_encode_file_quality(&job, None, std::ptr::null_mut(), &mut rep, q.as_mut_ptr()) },
+        None => unsafe { av1mi_encode_file(&job, None, std::ptr::null_mut(), &mut rep) },
+    };
+    match rc {
         0 => Ok(()),
         rc if rc > 0 => Err(EncodeError::Av1anFailed(rc)),                                   // av1an.rs:21
         rc => Err(EncodeError::Io(std::io::Error::from_raw_os_error(-rc))),                   // av1an.rs:29

@@ -4,7 +4,8 @@ all 13 intra candidates, CQ 30), cfg3_1080p_ippp and the production point.  One 
 --steps after --warmup, the clip in HBM), bytes per frame, PSNR Y / U / V of the reconstruction, the report's stage times (the activity
 pass runs between the chunk's start and "source ready": ms_h2d), the time of the decision alone (av1mi_aq_qindex, with its
 allocations) and the histogram of the superblocks' quantiser indices.  The rule trades PSNR for flat-area quality: at equal bytes PSNR
-is expected to fall, and this tool reports what it measures, nothing more."""
+is expected to fall - which is why every line also carries SSIM Y and all-planes of the reconstruction against the coded source
+(av1mi_quality_result), the structural measure the rule is meant to move - and this tool reports what it measures, nothing more."""
 import argparse
 import json
 import os
@@ -23,6 +24,18 @@ POINTS = [
     ("production_1080p", dict(keyint=240, cq_level=8, intra_mode_mask=0x7, film_grain=20, subpel=1, deblock=1, enable_lr=2,
                               enable_qm=1, qm_min=1, qm_max=15)),
 ]
+
+
+def ssim_columns(av1mi, ctx, p, clip_ptr, n):
+    """SSIM Y and all-planes of the chunk's reconstruction against its coded source: one more encode with the context's quality switch on
+    (the timed runs have it off)"""
+    ctx.set_quality(True)
+    try:
+        ctx.encode_chunk(p, clip_ptr, n, on_device=True, copy_out=False)
+        s = av1mi.ssim_of(av1mi.quality_sum(ctx.quality_result(n)))
+    finally:
+        ctx.set_quality(False)
+    return {"ssim_y": round(s["y"], 5), "ssim_all": round(s["all"], 5), "ssim_all_db": round(s["db"], 3)}
 
 
 def main():
@@ -65,7 +78,7 @@ def main():
                                   "bytes_per_frame": round(rep.bytes / n, 1), "psnr": [round(x, 3) for x in rep.psnr],
                                   "ms_h2d": round(rep.ms_h2d, 3), "ms_recon": round(rep.ms_recon, 3), "ms_entropy": round(rep.ms_entropy, 3),
                                   "ms_symbolize": round(rep.ms_symbolize, 3), "ms_aq_qindex_call": round(ms_map, 3),
-                                  "qindex_hist": {int(a): int(b) for a, b in zip(q, cnt)}}), flush=True)
+                                  "qindex_hist": {int(a): int(b) for a, b in zip(q, cnt)}, **ssim_columns(av1mi, ctx, p, clip.data_ptr(), n)}), flush=True)
 
 
 if __name__ == "__main__":

@@ -95,12 +95,10 @@ def noisy_texture_clip(torch, w, h, bd, n, dev, seed=9, motion=(2, 2), sigma=1.0
     return torch.cat(frames).view(torch.uint8), torch.cat(clean).view(torch.uint8)
 
 
-def psnr(torch, a, b, bd):
-    """of two clips in one layout, over every sample"""
-    dt = torch.int16 if bd > 8 else torch.uint8
-    d = a.view(dt).to(torch.float64) - b.view(dt).to(torch.float64)
-    mse = float((d * d).mean())
-    return 99.0 if mse == 0 else 10.0 * float(torch.log10(torch.tensor(((1 << bd) - 1) ** 2 / mse)))
+def psnr(av1mi, ctx, p, a, b, n):
+    """of clip a against clip b, two device tensors in one tight layout, over every sample: compared on the device (av1mi_quality)"""
+    s = av1mi.quality_sum(ctx.quality(p, b.data_ptr(), a.data_ptr(), n, on_device=True))
+    return av1mi.psnr_of(s, p.width, p.height, p.bit_depth, n)["all"]
 
 
 def main():
@@ -167,8 +165,8 @@ def main():
                     out = torch.empty_like(clip)
                     _, ran_with = ctx.film_grain_denoise(den, clip.data_ptr(), n, on_device=True, out_ptr=out.data_ptr())
                     assert (ran_with == table).all()
-                    line["psnr_source_against_clean_before"] = round(psnr(torch, clip, clean, bd), 3)
-                    line["psnr_source_against_clean_after"] = round(psnr(torch, out, clean, bd), 3)
+                    line["psnr_source_against_clean_before"] = round(psnr(av1mi, ctx, den, clip, clean, n), 3)
+                    line["psnr_source_against_clean_after"] = round(psnr(av1mi, ctx, den, out, clean, n), 3)
                     # the temporal term, alternated with the spatial mode
                     spans = {int(v): av1mi.default_params(w, h, bd, film_grain_denoise=args.level, film_grain_temporal=int(v), **kw) for v in args.spans.split(",") if v}
                     for p in spans.values():
@@ -186,7 +184,7 @@ def main():
                         ctx.film_grain_denoise(p, clip.data_ptr(), n, on_device=True, out_ptr=out.data_ptr())
                         line["temporal_s%d" % v] = {"ms_pass_denoise": round(ms[v], 3), "ms_pass_denoise_spatial_alternated": round(ms_spatial, 3),
                                                     "bytes_per_frame": round(nbytes[v] / n, 1),
-                                                    "psnr_source_against_clean_after": round(psnr(torch, out, clean, bd), 3)}
+                                                    "psnr_source_against_clean_after": round(psnr(av1mi, ctx, den, out, clean, n), 3)}
                     del out
                 if name == "arnoise":   # the fourth mode, alternated with the denoise mode
                     lags = {lag: av1mi.default_params(w, h, bd, film_grain_denoise=args.level, film_grain_ar=lag, **kw) for lag in (1, 2, 3)}

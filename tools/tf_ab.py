@@ -5,8 +5,9 @@ tests/tf_ref.py's generator).  One JSON line per clip and setting:
   fps / fps_off       frames/s of the chunk with the setting and of the filter off, timed alternately (off, on, off, on ...) in this
                       process after --warmup, best of --steps each; off_spread: lowest and highest of that row's off timings, and the
                       first line of a clip has the spread of all its off timings - what a difference has to exceed to mean anything
-  bytes_per_frame, psnr   PSNR Y / U / V of the returned reconstruction against the ORIGINAL source (and against the clean pattern
-                      where there is one), computed here in numpy - the report's own PSNR is against the filtered key frames
+  bytes_per_frame, psnr, ssim   PSNR Y / U / V and SSIM Y / all-planes of the returned reconstruction against the ORIGINAL source (and
+                      against the clean pattern where there is one), compared on the device (av1mi_quality) - the report's own PSNR is
+                      against the filtered key frames
   ms_filter_call      av1mi_temporal_filter alone, with its allocations and copies; ms_copy: a device copy of the chunk, what the
                       filter costs a device-resident chunk before its kernels run
   index_hist, rejected_share   histogram of the weight indices over the samples of all block-followers, and the share of
@@ -28,19 +29,11 @@ import tf_ref  # noqa: E402
 SETTINGS = [(n, s) for n in (1, 3, 7) for s in (1, 3, 5)]
 
 
-def psnr_planes(a, b, w, h, bd, n):
-    """PSNR per plane of two tight I420 byte strings over n frames"""
-    import numpy as np
-    dt = np.uint16 if bd > 8 else np.uint8
-    x = np.frombuffer(a, dtype=dt).reshape(n, -1).astype(np.int32)
-    y = np.frombuffer(b, dtype=dt).reshape(n, -1).astype(np.int32)
-    cuts = [0, w * h, w * h + w * h // 4, w * h * 3 // 2]
-    out = []
-    for pl in range(3):
-        d = (x[:, cuts[pl]:cuts[pl + 1]] - y[:, cuts[pl]:cuts[pl + 1]]).astype(np.int64)
-        mse = float((d * d).mean())
-        out.append(round(10 * np.log10(((1 << bd) - 1) ** 2 / mse), 3) if mse else float("inf"))
-    return out
+def against(av1mi, ctx, p, ref, test, w, h, bd, n):
+    """(PSNR per plane, [SSIM Y, SSIM all planes]) of chunk `test` against chunk `ref`, two device tensors in the tight layout"""
+    s = av1mi.quality_sum(ctx.quality(p, ref.data_ptr(), test.data_ptr(), n, on_device=True))
+    ps, ss = av1mi.psnr_of(s, w, h, bd, n), av1mi.ssim_of(s)
+    return [round(ps[k], 3) for k in "yuv"], [round(ss["y"], 5), round(ss["all"], 5)]
 
 
 def main():
@@ -51,7 +44,6 @@ def main():
     ap.add_argument("--pattern-frames", type=int, default=16)
     ap.add_argument("--clips", default="synthclip,pattern")
     args = ap.parse_args()
-    import numpy as np
     import torch
     import av1mi
     dev = torch.device("cuda:0")
@@ -63,7 +55,8 @@ def main():
     if "pattern" in args.clips.split(","):
         noisy, clean = tf_ref.pattern_clip(w, h, 8, args.pattern_frames, seed=7, sigma=2.0)
         t = torch.frombuffer(bytearray(noisy), dtype=torch.uint8).to(dev)
-        clips.append(("pattern_noise_1080p", 8, args.pattern_frames, t, clean, dict(cq_level=30, intra_mode_mask=0x7)))
+        clips.append(("pattern_noise_1080p", 8, args.pattern_frames, t, torch.frombuffer(bytearray(clean), dtype=torch.uint8).to(dev),
+                      dict(cq_level=30, intra_mode_mask=0x7)))
     with av1mi.Context(0) as ctx:
         for name, bd, n, clip, clean, kw in clips:
             clip = clip.reshape(-1)
@@ -80,12 +73,12 @@ def main():
             def line(p, t_on, t_offs, rep, extra):
                 run(p, want_recon=True)
                 torch.cuda.synchronize(dev)
-                rec = recon.cpu().numpy().tobytes()
+                psnr, ssim = against(av1mi, ctx, p, clip, recon, w, h, bd, n)
                 d = {"clip": name, "fps": round(n / t_on, 1), "fps_off": round(n / min(t_offs), 1),
                      "off_spread_fps": [round(n / max(t_offs), 1), round(n / min(t_offs), 1)], "bytes_per_frame": round(rep.bytes / n, 1),
-                     "psnr": psnr_planes(rec, src, w, h, bd, n), "psnr_report": [round(x, 3) for x in rep.psnr], "ms_h2d": round(rep.ms_h2d, 3)}
+                     "psnr": psnr, "ssim": ssim, "psnr_report": [round(x, 3) for x in rep.psnr], "ms_h2d": round(rep.ms_h2d, 3)}
                 if clean is not None:
-                    d["psnr_clean"] = psnr_planes(rec, clean, w, h, bd, n)
+                    d["psnr_clean"], d["ssim_clean"] = against(av1mi, ctx, p, clean, recon, w, h, bd, n)
                 d.update(extra)
                 print(json.dumps(d), flush=True)
                 return d

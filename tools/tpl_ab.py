@@ -19,6 +19,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "av1-base_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import bench  # noqa: E402
+from aq_ab import ssim_columns  # noqa: E402
 
 
 def bytes_at_psnr(points, psnr):
@@ -86,7 +87,7 @@ def main():
                     print(json.dumps({"clip": name, "cq": cq, "tpl_strength": s, "fps": round(n / best, 1), "fps_off_alternated": round(n / best_off, 1),
                                       "bytes_per_frame": round(rep.bytes / n, 1), "psnr": [round(x, 3) for x in rep.psnr],
                                       "ms_start_to_source_ready": round(rep.ms_h2d, 3), "ms_aq_qindex_call": round(ms_map, 3),
-                                      "d_hist_by_frame": hist}), flush=True)
+                                      "d_hist_by_frame": hist, **ssim_columns(av1mi, ctx, p, clip.data_ptr(), n)}), flush=True)
             if 0 in curve:
                 for s in strengths:
                     if s == 0:
