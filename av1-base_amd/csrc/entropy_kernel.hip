@@ -1062,7 +1062,6 @@ struct RcTile {
   bool live, overflow;
   int tile, count, nb;   // count: 0 on overflow; nb: batches of the wave's longest tile
   const uint32_t *st;    // the tile's stream
-  int adapt;
 
   // The stream reads are one 16-byte request per lane into 64 different streams (an HBM / L2 round trip each): the next batch is
   // loaded while the current one is worked on.  Three register buffers (batch mod 3): a buffer is refilled with batch + 3 at the END
@@ -1093,7 +1092,6 @@ static __device__ __forceinline__ RcTile rc_tile(const Av1miDevParams &P, int n_
   for (int o = 32; o > 0; o >>= 1) { const int m = __shfl_xor(maxcount, o, 64); maxcount = m > maxcount ? m : maxcount; }
   t.nb = (maxcount + RC_BATCH - 1) / RC_BATCH;
   t.st = streams + (size_t)(t.live ? t.tile : 0) * P.stream_cap;
-  t.adapt = !P.disable_cdf_update;
   return t;
 }
 
@@ -1150,9 +1148,9 @@ static __device__ __forceinline__ uint64_t rc_adapt(uint64_t rw, int s) {
 // lies beyond a tile's count inside the last batch is whatever an earlier chunk left there: it may adapt rows (the tile is over) and
 // is replaced before it is coded.  The row of entry i + 1 is read BEFORE entry i's row is written back, and replaced by that new row
 // if both entries name the same slot - otherwise every entry waited for an LDS round trip behind the previous entry's write (read ->
-// adapt -> write -> read ...).
-template <class F>
-static __device__ __forceinline__ void rc_walk(RcRows &row, const QBuf &q, int lane, int adapt, F &&f) {
+// adapt -> write -> read ...).  ADAPT is a compile-time parameter: as a run-time value it cost a scalar test and a branch per entry.
+template <bool ADAPT, class F>
+static __device__ __forceinline__ void rc_walk(RcRows &row, const QBuf &q, int lane, F &&f) {
   uint32_t ev[RC_BATCH];
   rc_entries(q, ev);
   auto slot_of = [&](uint32_t e) { const uint32_t t = e >> 2; return (int)(t < (uint32_t)RC_DUMMY ? t : (uint32_t)RC_DUMMY); };
@@ -1166,7 +1164,7 @@ static __device__ __forceinline__ void rc_walk(RcRows &row, const QBuf &q, int l
     if (jj + 1 < RC_BATCH) { slot_nx = slot_of(ev[jj + 1]); rw_nx = row[slot_nx][lane]; }
     f(jj, ev[jj], rw);
     uint64_t nrow = rw;
-    if (adapt) {
+    if (ADAPT) {
       nrow = rc_adapt(rw, s);
       row[slot][lane] = nrow;
     }
@@ -1176,13 +1174,16 @@ static __device__ __forceinline__ void rc_walk(RcRows &row, const QBuf &q, int l
 
 // a narrow entry resolved against its row: {fl, fh, N - s}; a resolved one as it is
 static __device__ __forceinline__ uint32_t rc_resolve(uint64_t rw, uint32_t ent) {
-  const int s = ent & 3;
-  const uint32_t c01 = (uint32_t)rw, c2 = (uint32_t)(rw >> 32) & 0xFFFFu;
-  // fl = icdf[s-1] (32768 for s == 0), fh = icdf[s] (0 for s == 3): one 64-bit shift each of {32768, c0, c1, c2} / {c0, c1, c2, 0}
-  const uint64_t vals = ((uint64_t)c2 << 32) | c01;
-  const uint32_t fh = (uint32_t)(vals >> (16 * s)) & 0xFFFFu;
-  const uint32_t fl = (uint32_t)(((vals << 16) | 0x8000u) >> (16 * s)) & 0xFFFFu;
-  return (ent & 0x80000000u) ? ent : ENT_RESOLVED(fl >> 6, fh >> 6, 3 - s);
+  const uint32_t s = ent & 3;
+  // fl = icdf[s-1] (32768 for s == 0) and fh = icdf[s] (0 for s == 3) are neighbours in the halfwords {32768, c0, c1, c2, 0}: ONE
+  // 64-bit shift of {32768, c0, c1, c2} brings both down, fl into the low half and fh into the high one (the counter leaves at the
+  // top), and each goes from there straight to its place in the entry: fl6 << 14 = (fl & 0xFFC0) << 8, fh6 << 4 = (fh & 0xFFC0) >> 2
+  const uint64_t vals = ((uint64_t)(uint32_t)(rw >> 16) << 32) | ((uint32_t)rw << 16) | 0x8000u;
+  const uint32_t x = (uint32_t)(vals >> (16 * s));
+  const uint32_t res = ((x << 8) & 0x00FFC000u) | (((x >> 18) & 0x3FF0u) | (0x80000003u ^ s));
+  static_assert(ENT_RESOLVED(0x3FF, 0, 0) == 0x80FFC000u && ENT_RESOLVED(0, 0x3FF, 3) == 0x80003FF3u, "the masks above are the entry's fields");
+  // a select, not a branch: both values are there for every lane (the resolved entry went through the dummy row)
+  return (int32_t)ent < 0 ? ent : res;
 }
 
 // entry i of the tile, or beyond its count "the whole range" (fl = 32768, fh = 0 of a one-symbol alphabet): changes nothing, emits
@@ -1230,17 +1231,22 @@ struct RcOut {
   __device__ __forceinline__ void code(uint32_t add, int d) {
     uint32_t l = low + add;
     int s2 = cnt + d;
-    if (s2 >= 0) {   // one byte, or two when at least 8 bits are ready
-      int c = cnt + 16;
-      const bool two = s2 >= 8;
-      // no inner branch: the first byte is stored in any case and, if it was not due, overwritten by the second at the same position
-      put(pos, l >> c);
-      pos += two;
-      l = two ? l & ((1u << c) - 1) : l;
-      c = two ? c - 8 : c;
+    int c = cnt + 16;
+    // Two bytes at once take a shift of nine or more - a symbol coded at a probability below 2^-9 - which is rare even over the wave's
+    // 64 tiles, while SOME lane has one byte due at more than half of the entries: the wave asks once whether any has two, and
+    // only then do those lanes emit their first byte; what is left is the common case, one byte or none.
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(s2 >= 8) != 0, 0)) {
+      if (s2 >= 8) {
+        emit(l >> c);
+        l &= (1u << c) - 1;
+        c -= 8;
+        s2 -= 8;
+      }
+    }
+    if (s2 >= 0) {
       emit(l >> c);
       l &= (1u << c) - 1;
-      s2 = c + d - 24;
+      s2 -= 8;
     }
     low = l << d;
     cnt = s2;
@@ -1277,8 +1283,8 @@ static __device__ __forceinline__ void rc_finish(const RcTile &t, RcOut &o, uint
 //   wave 2 (range):   the range recurrence alone: rng -> (what the entry adds to `low`, the normalisation shift);
 //   wave 3 (output):  accumulates `low` and writes the tile's bytes.
 // The kernel's duration is the serial chain of its longest tile (~4.8 k symbols at 1080p) times the instructions per entry of the
-// slowest stage: a wave alone on its SIMD issues one vector instruction per ~4.4 cycles, so the two-wave form (resolver 61, coder 45
-// instructions per entry) was bound at 61; the stages here are 34 / 25 / 20 / 34.
+// slowest stage: a wave alone on its SIMD issues one vector instruction per ~4.4 cycles, so the two-wave form (resolver 46, coder 39
+// instructions per entry) is bound at 46; the stages here are 35 / 19 / 21 / 20 ("The chain, from the listing").
 struct RcLds {
   RcRows row;
   uint64_t ring_row[2][RC_BATCH][64];
@@ -1287,11 +1293,12 @@ struct RcLds {
 };
 __shared__ RcLds g_rc;
 
-__global__ void __launch_bounds__(256) rangecode4_tiles_kernel(Av1miDevParams P, int n_tiles, const uint16_t *__restrict__ cdf_init,
-                                                             const uint32_t *__restrict__ streams, const uint32_t *__restrict__ stream_len,
-                                                             const uint32_t *__restrict__ tile_combos, uint8_t *__restrict__ slots,
-                                                             uint32_t *__restrict__ tile_bytes, const uint32_t *__restrict__ order,
-                                                             int tile0 /* chunk-wide index of the launch's first tile; n_tiles and `order` are launch-local */) {
+// (ADAPT = !disable_cdf_update: the kernels below choose the body once)
+template <bool ADAPT>
+static __device__ __forceinline__ void rangecode4_body(const Av1miDevParams &P, int n_tiles, const uint16_t *__restrict__ cdf_init,
+                                                       const uint32_t *__restrict__ streams, const uint32_t *__restrict__ stream_len,
+                                                       const uint32_t *__restrict__ tile_combos, uint8_t *__restrict__ slots,
+                                                       uint32_t *__restrict__ tile_bytes, const uint32_t *__restrict__ order, int tile0) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const RcTile T = rc_tile(P, n_tiles, streams, stream_len, order, tile0, lane);
   if (wave == 0) rc_init_rows(g_rc.row, P, T, cdf_init, T.live ? tile_combos[T.tile] : 0xFFFFu, lane);
@@ -1303,7 +1310,7 @@ __global__ void __launch_bounds__(256) rangecode4_tiles_kernel(Av1miDevParams P,
   if (wave <= 1) { T.load_batch(qa, 0); T.load_batch(qb, 1); T.load_batch(qc, 2); }
   const int n_trips = (T.nb + 3 + 2) / 3 * 3;   // (a multiple of 3: the loops of waves 0 and 1 are unrolled by the three buffers)
   auto stage0 = [&](const int k, QBuf &q0) __attribute__((always_inline)) {
-    if (k < T.nb) rc_walk(g_rc.row, q0, lane, T.adapt, [&](int jj, uint32_t, uint64_t rw) { g_rc.ring_row[k & 1][jj][lane] = rw; });
+    if (k < T.nb) rc_walk<ADAPT>(g_rc.row, q0, lane, [&](int jj, uint32_t, uint64_t rw) { g_rc.ring_row[k & 1][jj][lane] = rw; });
     T.load_batch(q0, k + 3);
     rc_trip_end();
   };
@@ -1358,6 +1365,15 @@ __global__ void __launch_bounds__(256) rangecode4_tiles_kernel(Av1miDevParams P,
   if (wave == 3) rc_finish(T, out, tile_bytes);
 }
 
+__global__ void __launch_bounds__(256) rangecode4_tiles_kernel(Av1miDevParams P, int n_tiles, const uint16_t *__restrict__ cdf_init,
+                                                             const uint32_t *__restrict__ streams, const uint32_t *__restrict__ stream_len,
+                                                             const uint32_t *__restrict__ tile_combos, uint8_t *__restrict__ slots,
+                                                             uint32_t *__restrict__ tile_bytes, const uint32_t *__restrict__ order,
+                                                             int tile0 /* chunk-wide index of the launch's first tile; n_tiles and `order` are launch-local */) {
+  if (P.disable_cdf_update) rangecode4_body<false>(P, n_tiles, cdf_init, streams, stream_len, tile_combos, slots, tile_bytes, order, tile0);
+  else rangecode4_body<true>(P, n_tiles, cdf_init, streams, stream_len, tile_combos, slots, tile_bytes, order, tile0);
+}
+
 // ---- K4, two-stage form (more than 256 workgroups: see the launcher)
 // TWO waves per workgroup working as a pipeline:
 //   wave 0 (resolver): walks the tile's stream, adapts the tile's rows and turns every entry into a RESOLVED one in an LDS ring;
@@ -1370,11 +1386,11 @@ struct Rc2Lds {
 };
 __shared__ Rc2Lds g_rc2;
 
-__global__ void __launch_bounds__(128) rangecode2_tiles_kernel(Av1miDevParams P, int n_tiles, const uint16_t *__restrict__ cdf_init,
-                                                             const uint32_t *__restrict__ streams, const uint32_t *__restrict__ stream_len,
-                                                             const uint32_t *__restrict__ tile_combos, uint8_t *__restrict__ slots,
-                                                             uint32_t *__restrict__ tile_bytes, const uint32_t *__restrict__ order,
-                                                             int tile0 /* chunk-wide index of the launch's first tile; n_tiles and `order` are launch-local */) {
+template <bool ADAPT>
+static __device__ __forceinline__ void rangecode2_body(const Av1miDevParams &P, int n_tiles, const uint16_t *__restrict__ cdf_init,
+                                                       const uint32_t *__restrict__ streams, const uint32_t *__restrict__ stream_len,
+                                                       const uint32_t *__restrict__ tile_combos, uint8_t *__restrict__ slots,
+                                                       uint32_t *__restrict__ tile_bytes, const uint32_t *__restrict__ order, int tile0) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const RcTile T = rc_tile(P, n_tiles, streams, stream_len, order, tile0, lane);
   if (wave == 0) rc_init_rows(g_rc2.row, P, T, cdf_init, T.live ? tile_combos[T.tile] : 0xFFFFu, lane);
@@ -1386,7 +1402,7 @@ __global__ void __launch_bounds__(128) rangecode2_tiles_kernel(Av1miDevParams P,
   if (wave == 0) { T.load_batch(qa, 0); T.load_batch(qb, 1); T.load_batch(qd, 2); }
   const int n_trips = (T.nb + 1 + 2) / 3 * 3;
   auto resolve_trip = [&](const int k, QBuf &q0) __attribute__((always_inline)) {
-    if (k < T.nb) rc_walk(g_rc2.row, q0, lane, T.adapt, [&](int jj, uint32_t ent, uint64_t rw) { g_rc2.ring[k & 1][jj][lane] = rc_resolve(rw, ent); });
+    if (k < T.nb) rc_walk<ADAPT>(g_rc2.row, q0, lane, [&](int jj, uint32_t ent, uint64_t rw) { g_rc2.ring[k & 1][jj][lane] = rc_resolve(rw, ent); });
     T.load_batch(q0, k + 3);
     rc_trip_end();
   };
@@ -1411,6 +1427,15 @@ __global__ void __launch_bounds__(128) rangecode2_tiles_kernel(Av1miDevParams P,
     for (int k = 0; k < n_trips; k++) code_trip(k);
   }
   if (wave == 1) rc_finish(T, out, tile_bytes);
+}
+
+__global__ void __launch_bounds__(128) rangecode2_tiles_kernel(Av1miDevParams P, int n_tiles, const uint16_t *__restrict__ cdf_init,
+                                                             const uint32_t *__restrict__ streams, const uint32_t *__restrict__ stream_len,
+                                                             const uint32_t *__restrict__ tile_combos, uint8_t *__restrict__ slots,
+                                                             uint32_t *__restrict__ tile_bytes, const uint32_t *__restrict__ order,
+                                                             int tile0 /* chunk-wide index of the launch's first tile; n_tiles and `order` are launch-local */) {
+  if (P.disable_cdf_update) rangecode2_body<false>(P, n_tiles, cdf_init, streams, stream_len, tile_combos, slots, tile_bytes, order, tile0);
+  else rangecode2_body<true>(P, n_tiles, cdf_init, streams, stream_len, tile_combos, slots, tile_bytes, order, tile0);
 }
 
 }  // namespace
@@ -1482,10 +1507,11 @@ extern "C" hipError_t av1mi_launch_entropy(const Av1miDevParams *P, const uint16
   }
   if (mid) (void)hipEventRecord(mid, stream);
   // Two forms of the range coder.  A wave of either wants a SIMD to itself (two workgroups' waves on one SIMD: twice as long,
-  // measured), so a CU runs four waves at full speed: ONE workgroup of the four-stage form (~100 ns per entry of the longest tile) or
-  // TWO of the two-stage form (~140 ns).  Measured range-coder times, two-stage / four-stage form, ms (tools/rc_probe.sh):
-  //   1080p all-key x 30 (239 workgroups) 0.79 / 0.55     x 60 (478) 0.75 / 1.04     x 120 (956) 1.78 / 1.64     x 60 at CQ 8 2.57 / 2.88
-  //   1080p IPPP x 60 (470)  0.68 / 0.53    at CQ 8  1.76 / 2.27    production point (CQ 8)  1.26 / 1.46    8K IPPP x 16 (510)  2.0 / 1.6
+  // measured), so a CU runs four waves at full speed: ONE workgroup of the four-stage form (~90 ns per entry of the longest tile) or
+  // TWO of the two-stage form (~110 ns).  Measured range-coder times, two-stage / four-stage form, ms (tools/rc_probe.sh):
+  //   1080p all-key x 30 (239 workgroups) 0.56 / 0.44     x 60 (478) 0.54 / 0.92     x 120 (956) 1.51 / 1.45     1080p IPPP x 60 (470)  0.56 / 0.50
+  // and, from before the per-entry chain was shortened (the four rows above were 0.79 / 0.55, 0.75 / 1.04, 1.78 / 1.64, 0.68 / 0.53):
+  //   1080p all-key x 60 at CQ 8 2.57 / 2.88    IPPP x 60 at CQ 8  1.76 / 2.27    production point (CQ 8)  1.26 / 1.46    8K IPPP x 16 (510)  2.0 / 1.6
   //   4K x 30 (957) all-key  1.68 / 1.58    IPPP  0.84 / 0.74
   // Up to 256 workgroups the four-stage form runs them all at once and wins; beyond 512 both run in rounds and the faster workgroup
   // wins again.  Between the two the two-stage form still has everything resident while the four-stage form runs two rounds of
