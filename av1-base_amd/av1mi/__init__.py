@@ -40,7 +40,8 @@ ABI_SYMBOLS = ["av1mi_default_params", "av1mi_ctx_create", "av1mi_ctx_destroy", 
                "av1mi_lr_rd_result", "av1mi_lr_rd_units", "av1mi_temporal_filter", "av1mi_tpl_analysis", "av1mi_film_grain_estimate",
                "av1mi_film_grain_result", "av1mi_film_grain_denoise", "av1mi_film_grain_ar_estimate", "av1mi_film_grain_ar_result",
                "av1mi_film_grain_denoise_temporal", "av1mi_tpl_frame_q", "av1mi_frame_q_result", "av1mi_quality", "av1mi_ctx_set_quality",
-               "av1mi_quality_result", "av1mi_encode_file_quality"]
+               "av1mi_quality_result", "av1mi_encode_file_quality", "av1mi_grain_params_size", "av1mi_film_grain_synth",
+               "av1mi_film_grain_params_result", "av1mi_ctx_set_displayed_quality", "av1mi_displayed_quality_result"]
 
 
 class Params(C.Structure):
@@ -96,6 +97,17 @@ class PlaneQuality(C.Structure):
     _fields_ = [("sse", C.c_uint64), ("ssim_sum", C.c_int64), ("windows", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class GrainParams(C.Structure):
+    """include/av1mi.h: av1mi_grain_params (164 bytes): film_grain_params without the seed, points as { x, y }, coefficients signed"""
+    _fields_ = [("num_y_points", C.c_uint8), ("num_cb_points", C.c_uint8), ("num_cr_points", C.c_uint8), ("chroma_scaling_from_luma", C.c_uint8),
+                ("point_y", C.c_uint8 * 2 * 14), ("point_cb", C.c_uint8 * 2 * 10), ("point_cr", C.c_uint8 * 2 * 10),
+                ("grain_scaling_minus_8", C.c_uint8), ("ar_coeff_lag", C.c_uint8), ("ar_coeff_shift_minus_6", C.c_uint8), ("grain_scale_shift", C.c_uint8),
+                ("ar_coeffs_y", C.c_int8 * 24), ("ar_coeffs_cb", C.c_int8 * 25), ("ar_coeffs_cr", C.c_int8 * 25),
+                ("overlap_flag", C.c_uint8), ("clip_to_restricted_range", C.c_uint8),
+                ("cb_mult", C.c_uint8), ("cb_luma_mult", C.c_uint8), ("cr_mult", C.c_uint8), ("cr_luma_mult", C.c_uint8),
+                ("cb_offset", C.c_uint16), ("cr_offset", C.c_uint16), ("mc_identity", C.c_uint8), ("reserved", C.c_uint8 * 3)]
+
+
 STATE_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p, C.POINTER(JobMetrics))
 PROGRESS_CB = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_uint64)
 
@@ -132,6 +144,13 @@ _lib.av1mi_quality.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_vo
 _lib.av1mi_ctx_set_quality.argtypes = [C.c_void_p, C.c_uint32]
 _lib.av1mi_quality_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PlaneQuality)]
 _lib.av1mi_encode_file_quality.argtypes = [C.POINTER(Job), PROGRESS_CB, C.c_void_p, C.POINTER(Report), C.POINTER(PlaneQuality)]
+_lib.av1mi_grain_params_size.restype = C.c_uint32
+if C.sizeof(GrainParams) != int(_lib.av1mi_grain_params_size()):   # the mirror against the library it loaded
+    raise ImportError("av1mi_grain_params: the library's struct has %d bytes, this mirror %d" % (int(_lib.av1mi_grain_params_size()), C.sizeof(GrainParams)))
+_lib.av1mi_film_grain_synth.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(GrainParams), C.POINTER(C.c_uint16), C.c_void_p]
+_lib.av1mi_film_grain_params_result.argtypes = [C.c_void_p, C.POINTER(GrainParams)]
+_lib.av1mi_ctx_set_displayed_quality.argtypes = [C.c_void_p, C.c_uint32]
+_lib.av1mi_displayed_quality_result.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(PlaneQuality)]
 _lib.av1mi_film_grain_estimate.argtypes = [C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_uint8), C.POINTER(C.c_uint32),
                                             C.POINTER(C.c_uint8)]
 _lib.av1mi_film_grain_result.argtypes = [C.c_void_p, C.POINTER(C.c_uint8)]
@@ -639,6 +658,46 @@ class Context:
         reconstruction against the coded source; zeros for a chunk encoded with the switch off"""
         out = (PlaneQuality * (n_frames * 3))()
         _raise_for(_lib.av1mi_quality_result(self._h, n_frames, out), "av1mi_quality_result")
+        return _quality_array(out).reshape(n_frames, 3)
+
+    def film_grain_synth(self, params, frames, n_frames, grain, seeds=None, on_device=False, out_ptr=None):
+        """The frames with the grain a decoder adds (include/av1mi.h: av1mi_film_grain_synth).  grain: a GrainParams, or its 164 bytes;
+        seeds: one grain_seed per frame, None for the encoder's rule from params.first_frame.  Host frames (bytes-like / numpy): returns
+        the chunk as a numpy uint8 array of the input's bytes.  on_device=True: `frames` and `out_ptr` are device pointers; returns None."""
+        import numpy as np
+        g = grain if isinstance(grain, GrainParams) else GrainParams.from_buffer_copy(bytes(grain))
+        sd = None if seeds is None else np.ascontiguousarray(np.asarray(seeds, dtype=np.uint16).reshape(n_frames))
+        nbytes = params.width * params.height * 3 // 2 * (2 if params.bit_depth > 8 else 1) * n_frames
+        fptr, keep = _frames_ptr(frames, on_device)
+        out = None
+        if on_device:
+            optr = C.c_void_p(int(out_ptr)) if out_ptr is not None else None
+        else:
+            if len(keep) != nbytes:
+                raise ValueError("frames: expected %d bytes, got %d" % (nbytes, len(keep)))
+            out = np.empty(nbytes, dtype=np.uint8)
+            optr = out.ctypes.data_as(C.c_void_p)
+        rc = _lib.av1mi_film_grain_synth(self._h, C.byref(params), fptr, n_frames, 1 if on_device else 0, C.byref(g),
+                                         sd.ctypes.data_as(C.POINTER(C.c_uint16)) if sd is not None else None, optr)
+        _raise_for(rc, self.last_error())
+        return out
+
+    def film_grain_params_result(self):
+        """the GrainParams the frame headers of the chunk this context encoded last carry (include/av1mi.h: av1mi_film_grain_params_result)"""
+        g = GrainParams()
+        _raise_for(_lib.av1mi_film_grain_params_result(self._h, C.byref(g)), "av1mi_film_grain_params_result")
+        return g
+
+    def set_displayed_quality(self, on):
+        """the displayed-picture switch (include/av1mi.h: av1mi_ctx_set_displayed_quality): every later chunk of this context with film grain
+        ends with the synthesis of its reconstruction and the quality pass of that against the caller's frames"""
+        _raise_for(_lib.av1mi_ctx_set_displayed_quality(self._h, 1 if on else 0), "av1mi_ctx_set_displayed_quality")
+
+    def displayed_quality_result(self, n_frames):
+        """[frame][plane] sse, ssim_sum, windows of the displayed picture of the chunk this context encoded last (include/av1mi.h:
+        av1mi_displayed_quality_result); zeros with the switch off or without film grain"""
+        out = (PlaneQuality * (n_frames * 3))()
+        _raise_for(_lib.av1mi_displayed_quality_result(self._h, n_frames, out), "av1mi_displayed_quality_result")
         return _quality_array(out).reshape(n_frames, 3)
 
     def frame_q_result(self, n_frames):

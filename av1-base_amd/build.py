@@ -15,7 +15,7 @@ CSRC = os.path.join(HERE, "csrc")
 _VARIANT = os.environ.get("AV1MI_BUILD_VARIANT", "")
 OUT = os.path.join(HERE, "ab", "libav1mi_%s.so" % _VARIANT) if _VARIANT else os.path.join(HERE, "libav1mi.so")
 OBJDIR = os.path.join(HERE, "build_" + _VARIANT if _VARIANT else "build")
-SOURCES = ["recon64_kernel.hip", "recon64_8_kernel.hip", "recon_kernel.hip", "recon8_kernel.hip", "entropy_kernel.hip", "cdef_kernel.hip", "pack_kernels.hip", "scene_kernels.hip", "quality_kernel.hip", "me_kernel.hip", "tf_kernel.hip", "tpl_kernel.hip", "fg_kernel.hip", "fg_denoise_kernel.hip", "fg_ar_kernel.hip", "lr_kernel.hip", "lr_fit_kernel.hip", "lr_wfit_kernel.hip", "deblock_kernel.hip", "av1mi_syntax.cpp", "av1mi_ctx.cpp", "av1mi_host.cpp", "av1mi_container.cpp", "av1mi_file.cpp", "av1mi_exec.cpp"]
+SOURCES = ["recon64_kernel.hip", "recon64_8_kernel.hip", "recon_kernel.hip", "recon8_kernel.hip", "entropy_kernel.hip", "cdef_kernel.hip", "pack_kernels.hip", "scene_kernels.hip", "quality_kernel.hip", "me_kernel.hip", "tf_kernel.hip", "tpl_kernel.hip", "fg_kernel.hip", "fg_denoise_kernel.hip", "fg_ar_kernel.hip", "fg_synth_kernel.hip", "lr_kernel.hip", "lr_fit_kernel.hip", "lr_wfit_kernel.hip", "deblock_kernel.hip", "av1mi_syntax.cpp", "av1mi_ctx.cpp", "av1mi_host.cpp", "av1mi_container.cpp", "av1mi_file.cpp", "av1mi_exec.cpp"]
 # -fno-optimize-sibling-calls: keeps LLVM from marking the calls of the `noinline` transform items `tail`.  With the marker the
 # backend's interprocedural register allocation treats the items as ordinary ABI functions that save and restore every
 # callee-saved VGPR they touch - 33 stores + 29 loads of 256 B per call, 60 % of the reconstruction kernel's HBM traffic

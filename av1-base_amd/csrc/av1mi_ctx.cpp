@@ -21,6 +21,7 @@
 #include "fg_rule.h"
 #include "fg_ar_rule.h"
 #include "fg_denoise_rule.h"
+#include "fg_synth_rule.h"
 #include "part_inter_rule.h"
 
 namespace av1mi {
@@ -104,7 +105,8 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   const size_t nf = w.cap_frames;
   const size_t unit_cap = 3 * nf * nsb + 64;   // restoration units the choices, sums and fits have room for: three planes of 64x64 units
   // the caller's frames in front of a pass that writes d_src from them: the edge extension, and the film-grain denoiser at any size
-  if ((r.padded || r.fg_denoise) && !w.d_stage) HIPCHK(c, ws_alloc(w, w.d_stage, caller_bytes(r, nf)));
+  // ... and with the displayed picture's quality a chunk whose key frames the temporal filter rewrites in d_src
+  if ((r.padded || r.fg_denoise || (displayed_on(c, r) && r.tf_frames)) && !w.d_stage) HIPCHK(c, ws_alloc(w, w.d_stage, caller_bytes(r, nf)));
   if (p.partition_search && !w.d_part) HIPCHK(c, ws_alloc(w, w.d_part, nf * nsb * sizeof(uint32_t)));
   if (p.me_presearch && !w.d_quarter) {
     HIPCHK(c, ws_alloc(w, w.d_quarter, nf * (size_t)(r.cw / 4) * (r.ch / 4) * sizeof(uint16_t)));
@@ -158,6 +160,12 @@ int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames) {
   if (c->quality && (!w.d_quality || !w.h_quality)) {
     HIPCHK(c, ws_alloc(w, w.d_quality, nf * 3 * 2 * sizeof(unsigned long long)));
     HIPCHK(c, ws_alloc(w, w.h_quality, nf * 3 * 2 * sizeof(unsigned long long), true));
+  }
+  if (displayed_on(c, r) && (!w.d_fgs || !w.d_disp || !w.d_disp_quality || !w.h_disp_quality)) {
+    HIPCHK(c, ws_alloc(w, w.d_fgs, av1mi_fgs_bytes(nf, (size_t)av1mi_fgs_stripes((int)p.height) * av1mi_fgs_blocks((int)p.width))));
+    HIPCHK(c, ws_alloc(w, w.d_disp, caller_bytes(r, nf)));
+    HIPCHK(c, ws_alloc(w, w.d_disp_quality, nf * 3 * 2 * sizeof(unsigned long long)));
+    HIPCHK(c, ws_alloc(w, w.h_disp_quality, nf * 3 * 2 * sizeof(unsigned long long), true));
   }
   if (p.enable_lr && !w.d_cd) {   // unit choices and sums for three planes (enable_lr 3 / 4) of 64x64 units, whichever value and unit size
                                   // this chunk has: the buffers stay with the geometry while enable_lr changes
@@ -245,8 +253,8 @@ void av1mi::release_streams() {
 
 // A context that goes back to av1mi_encode_file's cache forgets the capacity multiplier its last job's content raised (it would
 // otherwise size - or, at the limit, refuse - an unrelated job's workspace by it); the next chunk reallocates at scale 1.
-// ... and the quality switch a job set on it.
-void av1mi::recycle_ctx(av1mi_ctx *c) { if (c) { c->cap_scale = 1; c->quality = false; } }
+// ... and the quality switches a job set on it.
+void av1mi::recycle_ctx(av1mi_ctx *c) { if (c) { c->cap_scale = 1; c->quality = false; c->displayed = false; } }
 
 av1mi_plane_quality av1mi::plane_quality(const unsigned long long *q, const Av1miQualityGeom &G, int plane) {
   return { q[0], (int64_t)q[1], av1mi_quality_windows(G, plane), 0 };
@@ -661,6 +669,62 @@ int av1mi_quality_result(const av1mi_ctx *c, uint32_t n_frames, av1mi_plane_qual
   if (!c || !out || !c->last.n_frames || n_frames != c->last.n_frames) return AV1MI_E_INVALID_ARG;
   memcpy(out, c->last.quality.data(), (size_t)n_frames * 3 * sizeof(av1mi_plane_quality));
   return AV1MI_OK;
+}
+
+// What the last chunk's frame headers carry: the rule's parameter set of its mode, table and coefficients.
+int av1mi_film_grain_params_result(const av1mi_ctx *c, av1mi_grain_params *g) {
+  if (!c || !g || !c->last.n_frames || !c->last.film_grain) return AV1MI_E_INVALID_ARG;
+  av1mi_fgs_header_params((int)c->last.film_grain, c->last.fg_estimate, c->last.fg_ar_lag, c->last.fg_table, c->last.fg_ar_coeffs, g);
+  return AV1MI_OK;
+}
+
+int av1mi_ctx_set_displayed_quality(av1mi_ctx *c, uint32_t on) {
+  if (!c) return AV1MI_E_INVALID_ARG;
+  c->displayed = on != 0;
+  return AV1MI_OK;
+}
+
+// The displayed picture's quality of the context's last chunk: what download_chunk kept, zeros with the switch off or without film grain.
+int av1mi_displayed_quality_result(const av1mi_ctx *c, uint32_t n_frames, av1mi_plane_quality *out) {
+  if (!c || !out || !c->last.n_frames || n_frames != c->last.n_frames) return AV1MI_E_INVALID_ARG;
+  memcpy(out, c->last.displayed.data(), (size_t)n_frames * 3 * sizeof(av1mi_plane_quality));
+  return AV1MI_OK;
+}
+
+uint32_t av1mi_grain_params_size(void) { return (uint32_t)sizeof(av1mi_grain_params); }
+
+// What a decoder adds to the frames (fg_synth_kernel.hip), in the callers' tight layout as the quality pass takes its frames: the
+// templates' launch and the frames' on buffers of the call's own.
+int av1mi_film_grain_synth(av1mi_ctx *c, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
+                           const av1mi_grain_params *g, const uint16_t *seeds, void *out) {
+  if (!c || !params || !frames || !g || !out || out == frames || n_frames == 0 || n_frames > 65535) return AV1MI_E_INVALID_ARG;
+  if (!av1mi_fgs_params_valid(*g)) { set_err(c, "invalid film-grain parameters"); return AV1MI_E_INVALID_ARG; }
+  av1mi_params size;   // only the size and the depth matter, and the first frame's number for the seeds
+  av1mi_default_params(&size, params->width, params->height, params->bit_depth);
+  Pass t(c, &size);
+  if (const int rc = t.open(c, n_frames, true, nullptr, frames_on_device ? (uintptr_t)frames | (uintptr_t)out : 0)) return rc;
+  const Resolved &r = t.r;
+  const size_t bytes = caller_bytes(r, n_frames);
+  if (!av1mi_fgs_any_plane_on(*g)) {   // no scaling function: the frames as they are
+    if (frames_on_device) t.e = hipMemcpyAsync(out, frames, bytes, hipMemcpyDeviceToDevice, t.stream);
+    else memcpy(out, frames, bytes);
+    return t.finish(c, "film-grain synthesis");
+  }
+  const int w = (int)r.p.width, h = (int)r.p.height;
+  const Av1miQualityGeom G = av1mi_quality_geom(w, h, w, h, (int)r.p.bit_depth);
+  uint8_t *d_block = nullptr;
+  uint16_t *d_seeds = nullptr;
+  void *d_out = frames_on_device ? out : nullptr;
+  t.alloc(d_block, av1mi_fgs_bytes(n_frames, (size_t)av1mi_fgs_stripes(h) * av1mi_fgs_blocks(w)));
+  if (seeds && t.alloc(d_seeds, (size_t)n_frames * sizeof(uint16_t))) t.e = hipMemcpyAsync(d_seeds, seeds, (size_t)n_frames * sizeof(uint16_t), hipMemcpyHostToDevice, t.stream);
+  if (!frames_on_device) t.alloc(d_out, bytes);
+  const void *in = coded_frames(t, r, frames, n_frames, frames_on_device, false, false).tight;
+  const Av1miFgsBlock B = av1mi_fgs_split(d_block, n_frames);
+  if (t.ok()) t.e = hipMemcpyAsync(B.g, g, sizeof(*g), hipMemcpyHostToDevice, t.stream);
+  if (t.ok()) t.e = av1mi_launch_fg_synth_templates((int)r.p.bit_depth, w, h, (int)n_frames, d_seeds, params->first_frame, B, t.stream);
+  if (t.ok()) t.e = av1mi_launch_fg_synth_apply(&G, &G, in, d_out, (int)n_frames, B, t.stream);
+  if (!frames_on_device) to_host(t, out, d_out, bytes);
+  return t.finish(c, "film-grain synthesis");
 }
 
 // The frames' base_q_idx and betaF of the context's last chunk: what download_chunk kept.

@@ -83,6 +83,12 @@ struct Workspace {
   // the quality pass inside the encoder (av1mi_ctx_set_quality), on first use: per [frame][plane] the squared error and the sum of
   // window values (av1mi_launch_quality), and where one copy lands them
   unsigned long long *d_quality = nullptr, *h_quality = nullptr;
+  // the displayed picture's quality (av1mi_ctx_set_displayed_quality), on first use with film grain: the synthesis' block
+  // (av1mi_fgs_split), the final frames with their grain in the caller's tight layout, the quality pass's sums of those against the
+  // caller's frames, and where one copy lands them
+  uint8_t *d_fgs = nullptr;
+  void *d_disp = nullptr;
+  unsigned long long *d_disp_quality = nullptr, *h_disp_quality = nullptr;
   uint8_t *h_out = nullptr;            // host staging (pinned), for when the caller's buffer cannot be page-locked
   // Page-locked host side of the small transfers.  The chunk constants - header blob, default CDFs, parameters - are the same for
   // every chunk of a job: h_hdr / h_cdf / h_params hold what d_hdr / d_cdf / d_params hold, and prepare_chunk uploads only what differs.
@@ -135,6 +141,12 @@ struct LastChunk {
   std::vector<uint16_t> frame_beta;
   // its quality per [frame][plane] (av1mi_quality_result): zeros for a chunk encoded with the switch off
   std::vector<av1mi_plane_quality> quality;
+  // the displayed picture's per [frame][plane] (av1mi_displayed_quality_result): zeros with the switch off or without film grain
+  std::vector<av1mi_plane_quality> displayed;
+  // what its headers' film_grain_params were made of (av1mi_film_grain_params_result): N (0: none), estimated, the lag
+  uint32_t film_grain = 0;
+  bool fg_estimate = false;
+  int fg_ar_lag = 0;
 };
 #define AV1MI_CDF_ALL 256
 // the records of the film-grain estimate over n_frames frames: the whole 16x16 blocks of the signalled size
@@ -167,6 +179,8 @@ struct av1mi_ctx {
   bool sym_order = true;          // AV1MI_SYM_ORDER, read when the context is made: 0 = symbolize in natural tile order everywhere
   bool part_inter = false;        // this chunk's inter frames are partitioned from the search's node costs (partition_search = 2)
   bool quality = false;           // av1mi_ctx_set_quality: every chunk ends with the quality pass on its final frames
+  bool displayed = false;         // av1mi_ctx_set_displayed_quality: every chunk with film grain ends with the synthesis and its quality pass
+  const void *d_orig = nullptr;   // this chunk's frames as the caller gave them, tight, on the device: the caller's memory, d_stage or d_src
   av1mi::LastChunk last;
 };
 
@@ -184,6 +198,8 @@ namespace av1mi {
 void set_err(av1mi_ctx *c, const char *fmt, ...);
 void free_workspace(av1mi_ctx *c);
 int ensure_workspace(av1mi_ctx *c, const Resolved &r, uint32_t n_frames);
+// whether a chunk of `r` ends with the displayed picture's quality
+inline bool displayed_on(const av1mi_ctx *c, const Resolved &r) { return c->displayed && r.p.film_grain != 0; }
 // the workspace's buffers bound into a chunk's parameters, each under the condition its kernels run under
 void bind_workspace(Av1miDevParams &P, const Resolved &r, const Workspace &w);
 // a page-locked block of the process-wide pool for a chunk's bitstream (av1mi_free puts it back); null: none to be had

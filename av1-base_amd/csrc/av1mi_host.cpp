@@ -20,6 +20,7 @@
 #include "part_inter_rule.h"
 #include "tpl_rule.h"
 #include "fg_rule.h"
+#include "fg_synth_rule.h"
 
 using namespace av1mi;
 
@@ -100,15 +101,18 @@ static int prepare_chunk(av1mi_ctx *c, const Resolved &r, const void *frames, ui
   if (P.lr_fit_code) HIPCHK(c, hipMemsetAsync(w.d_fit, 0, av1mi_lr_fit_bytes(fit_chunk_units(r, n_frames)), s));
   if (P.lr_wfit_code) HIPCHK(c, hipMemsetAsync(w.d_wfit, 0, av1mi_lr_wfit_bytes(fit_chunk_units(r, n_frames)), s));
   if (c->quality) HIPCHK(c, hipMemsetAsync(w.d_quality, 0, (size_t)n_frames * 3 * 2 * sizeof(unsigned long long), s));   // the quality pass adds
+  if (displayed_on(c, r)) HIPCHK(c, hipMemsetAsync(w.d_disp_quality, 0, (size_t)n_frames * 3 * 2 * sizeof(unsigned long long), s));
   HIPCHK(c, hipEventRecord(c->ev[EV_START], s));
   // the caller's frames are used in place if they are on the device at the coded size; a padded chunk arrives in the stage, and so does
-  // a chunk the film-grain denoiser will write d_src from
-  const bool staged = r.padded || r.fg_denoise;
+  // a chunk the film-grain denoiser will write d_src from - and, for the displayed picture's quality, one whose key frames the temporal
+  // filter will rewrite in d_src: the pass compares against the frames as the caller gave them
+  const bool staged = r.padded || r.fg_denoise || (displayed_on(c, r) && tf_runs(r, n_frames));
   if (!frames_on_device) HIPCHK(c, hipMemcpyAsync(staged ? w.d_stage : w.d_src, frames, caller_bytes(r, n_frames), hipMemcpyHostToDevice, s));
   const void *tight = frames_on_device ? frames : w.d_stage;   // (with `staged`) the frames as the caller gave them, on the device
   // not a multiple of 8: edge-extend every frame to the coded size (the signalled size stays exact)
   if (r.padded) HIPCHK(c, av1mi_launch_pad(tight, w.d_src, (int)r.p.width, (int)r.p.height, r.cw, r.ch, P.bit_depth, (int)n_frames, 0, s));
   *d_src = r.padded ? w.d_src : (staged ? tight : (frames_on_device ? frames : w.d_src));
+  c->d_orig = frames_on_device || staged ? tight : w.d_src;   // (nothing writes the stage before the chunk's last kernels have read it)
   // the grain passes.  The film-grain estimate: the table from the frames as the caller gave them - before the denoiser and the temporal
   // filter - into every frame header, in front of every other kernel that patches a header (neighbouring fields can share a byte).  The
   // grain's autoregressive fit on the same frames: the coefficients, and the table scaled by the fit's gains over fg_table_kernel's values,
@@ -195,12 +199,30 @@ static int quality_beside_sse(av1mi_ctx *c, const void *src) {
   return AV1MI_OK;
 }
 
+// With the displayed-quality switch on and film grain in the headers: what a decoder shows - the final frames with the grain of the
+// headers' parameters and seeds, which fgs_params_kernel reads where the estimate and the fit left them - into d_disp in the caller's
+// layout, then the quality pass of that against the frames as the caller gave them; on the second stream behind the squared error's
+static int displayed_beside_sse(av1mi_ctx *c) {
+  const Resolved &r = c->ws.res;
+  if (!displayed_on(c, r)) return AV1MI_OK;
+  const Av1miDevParams &P = c->P; Workspace &w = c->ws; hipStream_t s2 = c->stream2;
+  const Av1miFgsBlock B = av1mi_fgs_split(w.d_fgs, (size_t)P.n_frames);
+  const uint8_t *table = !r.fg_estimate ? nullptr : (r.fg_ar_lag ? av1mi_fgar_split(w.d_fg_ar).table : av1mi_fg_split(w.d_fg).table);
+  const Av1miQualityGeom coded = quality_geom(P), tight = av1mi_quality_geom(P.true_w, P.true_h, P.true_w, P.true_h, P.bit_depth);
+  HIPCHK(c, av1mi_launch_fg_synth_params((int)r.p.film_grain, r.fg_estimate, r.fg_ar_lag, table, r.fg_ar_lag ? av1mi_fgar_split(w.d_fg_ar).coeffs : nullptr, B, s2));
+  HIPCHK(c, av1mi_launch_fg_synth_templates(P.bit_depth, P.true_w, P.true_h, P.n_frames, nullptr, r.p.first_frame, B, s2));
+  HIPCHK(c, av1mi_launch_fg_synth_apply(&coded, &tight, w.d_fin, w.d_disp, P.n_frames, B, s2));
+  HIPCHK(c, av1mi_launch_quality(&tight, c->d_orig, w.d_disp, P.n_frames, w.d_disp_quality, nullptr, s2));
+  return AV1MI_OK;
+}
+
 // The second stream beside the range coder, once symbolize is done: the squared error of the final frames
 static int sse_beside_range_coder(av1mi_ctx *c, const void *src) {
   HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev[EV_SYM_DONE], 0));
   HIPCHK(c, hipEventRecord(c->ev[EV_CDEF_START], c->stream2));
   HIPCHK(c, av1mi_launch_sse(&c->P, src, c->ws.d_fin, c->ws.d_sse, c->stream2));
   if (const int rc = quality_beside_sse(c, src)) return rc;
+  if (const int rc = displayed_beside_sse(c)) return rc;
   HIPCHK(c, hipEventRecord(c->ev[EV_CDEF_DONE], c->stream2));
   return AV1MI_OK;
 }
@@ -238,6 +260,7 @@ static int schedule_all_key(av1mi_ctx *c, const void *src, uint32_t n_frames) {
   HIPCHK(c, av1mi_launch_cdef(&P, w.d_rec, w.d_fin, w.d_blk, sse_in_cdef ? src : nullptr, sse_in_cdef ? w.d_sse : nullptr, 0, n, s2));
   if (!sse_in_cdef) HIPCHK(c, av1mi_launch_sse(&P, src, w.d_fin, w.d_sse, s2));
   if (const int rc = quality_beside_sse(c, src)) return rc;
+  if (const int rc = displayed_beside_sse(c)) return rc;
   HIPCHK(c, hipEventRecord(c->ev[EV_CDEF_DONE], s2));
   return AV1MI_OK;
 }
@@ -396,6 +419,7 @@ static int download_chunk(av1mi_ctx *c, const Resolved &r, uint32_t n_frames, in
   const unsigned long long *sse = w.h_sse;
   if (e1 == hipSuccess) e1 = hipMemcpyAsync(w.h_sse, w.d_sse, (size_t)n_frames * 24, hipMemcpyDeviceToHost, s);
   if (e1 == hipSuccess && c->quality) e1 = hipMemcpyAsync(w.h_quality, w.d_quality, (size_t)n_frames * 3 * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
+  if (e1 == hipSuccess && displayed_on(c, r)) e1 = hipMemcpyAsync(w.h_disp_quality, w.d_disp_quality, (size_t)n_frames * 3 * 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
   // the level search's tables and levels (record_last_chunk keeps them): one more small copy before the wait below.  The levels sit behind the
   // whole workspace's tables, not behind this chunk's: two copies when the chunk is shorter
   const size_t lf_err_bytes = (size_t)n_frames * 3 * AV1MI_LF_CANDS * sizeof(unsigned long long);
@@ -489,6 +513,12 @@ static LastChunk record_last_chunk(const av1mi_ctx *c, const Resolved &r, uint32
     const Av1miQualityGeom G = quality_geom(P);
     for (size_t i = 0; i < L.quality.size(); i++) L.quality[i] = plane_quality(w.h_quality + i * 2, G, (int)(i % 3));
   }
+  L.displayed.assign((size_t)n_frames * 3, av1mi_plane_quality{});
+  if (displayed_on(c, r)) {
+    const Av1miQualityGeom G = av1mi_quality_geom(P.true_w, P.true_h, P.true_w, P.true_h, P.bit_depth);
+    for (size_t i = 0; i < L.displayed.size(); i++) L.displayed[i] = plane_quality(w.h_disp_quality + i * 2, G, (int)(i % 3));
+  }
+  L.film_grain = r.p.film_grain; L.fg_estimate = r.fg_estimate != 0; L.fg_ar_lag = r.fg_ar_lag;
   if (P.part_map) { L.pi_keys = c->part_inter; L.pi_frames = n_frames; L.pi_units = (uint32_t)(P.b8_rows * P.b8_cols); L.pi_sbs = (uint32_t)(P.sb_rows * P.sb_cols); }
   return L;
 }

@@ -13,6 +13,7 @@
 #define AV1MI_LAUNCH_H
 #include <hip/hip_runtime.h>
 #include "av1mi_dev.h"
+#include "../../include/av1mi.h"
 
 // The parameters of a launch over frames [frame0, frame0 + count): n_frames is the launch's, and every per-frame map the kernels index
 // from the launch's first frame on starts there - a kernel that is given a range indexes these maps relative to the launch, whether
@@ -136,8 +137,37 @@ inline Av1miQualityGeom av1mi_quality_geom(int w, int h, int cw, int ch, int bit
   return G;
 }
 
+// The film-grain synthesis' block (fg_synth_kernel.hip, fg_synth_rule.h), for n frames of frame_blocks = stripes x blocks 32x32 luma
+// blocks each, 16-byte aligned: the parameter set at its head (byte 0) and the three scaling functions (byte 256), then from byte 1024 the
+// frames' templates (AV1MI_FGS_TEMPLATE_N = 9330 samples each) and their blocks' values
+struct Av1miFgsBlock {
+  av1mi_grain_params *g;   // what both kernels read: the caller's, uploaded, or av1mi_launch_fg_synth_params'
+  uint8_t *lut;            // [plane][256]
+  int16_t *templates;      // [frame][9330]: LumaGrain, CbGrain, CrGrain
+  uint8_t *offs;           // [frame][stripe][block]
+};
+inline size_t av1mi_fgs_bytes(size_t n, size_t frame_blocks) { return 1024 + n * (9330 * sizeof(int16_t) + frame_blocks); }
+inline Av1miFgsBlock av1mi_fgs_split(void *block, size_t n) {
+  uint8_t *b = reinterpret_cast<uint8_t *>(block);
+  return { reinterpret_cast<av1mi_grain_params *>(b), b + 256, reinterpret_cast<int16_t *>(b + 1024), b + 1024 + n * 9330 * sizeof(int16_t) };
+}
+
 extern "C" {
 // ---- whole chunk (or call): all P->n_frames frames
+// the film-grain synthesis (fg_synth_kernel.hip, fg_synth_rule.h), launches on one stream, all reading the parameter set at B.g.
+// _params: B.g = what the encoder's frame headers carry with film_grain = N (fg_synth_rule.h: av1mi_fgs_header_params) - table: null for
+// the fixed table, else the 24 values in device memory (av1mi_launch_film_grain's, or with a lag av1mi_launch_fg_ar's scaled ones);
+// coeffs: null without a lag, else the fit's [plane][25].  A caller with a set of its own copies it to B.g instead.
+// _templates: the templates, block values and scaling functions of n_frames frames of w x h luma (both even) into B: seeds null - frame
+// f's grain_seed by the encoder's rule from first_frame - or n_frames seeds in device memory.
+// _apply: `in`, laid out as Gin says, with its grain into `out`, another block, laid out as Gout says - each the callers' tight layout
+// or the encoder's coded size, as the quality pass, of one signalled size; every sample of that size is written, a plane without a scaling
+// function copied
+hipError_t av1mi_launch_fg_synth_params(int N, int estimate, int lag, const uint8_t *table, const int8_t *coeffs, Av1miFgsBlock B, hipStream_t stream);
+hipError_t av1mi_launch_fg_synth_templates(int bit_depth, int w, int h, int n_frames, const uint16_t *seeds, uint32_t first_frame, Av1miFgsBlock B,
+                                           hipStream_t stream);
+hipError_t av1mi_launch_fg_synth_apply(const Av1miQualityGeom *Gin, const Av1miQualityGeom *Gout, const void *in, void *out, int n_frames,
+                                       Av1miFgsBlock B, hipStream_t stream);
 // split masks of every superblock (partition_kernel)
 hipError_t av1mi_launch_partition(const Av1miDevParams *P, const void *frames, uint32_t *part, hipStream_t stream);
 // quantiser index of every superblock (aq_activity_kernel, aq_map_kernel): act and qmap are [frame][superblock].  tpl_strength != 0: the

@@ -542,6 +542,45 @@ int av1mi_ctx_set_quality(av1mi_ctx *ctx, uint32_t on);
  * n_frames is not its frame count. */
 int av1mi_quality_result(const av1mi_ctx *ctx, uint32_t n_frames, av1mi_plane_quality *out);
 
+/* ---- film-grain synthesis: what a decoder makes of film_grain_params, on the device ------------------------------------------
+ * AV1 spec 7.18.3 for 4:2:0, bit-exact with dav1d (av1-base_amd/csrc/fg_synth_rule.h).  The parameter set
+ * is every field of film_grain_params (spec 5.9.30) except grain_seed, coefficients and points as the spec's variables hold them
+ * (ar_coeffs_* without the + 128): point_*[k] = { x, y }, x strictly increasing; ar_coeffs_y holds 2 L (L + 1) values at lag L,
+ * ar_coeffs_cb / _cr one more, the luma tap.  mc_identity: the sequence's matrix_coefficients is MC_IDENTITY (the chroma maximum of
+ * clip_to_restricted_range). */
+typedef struct {
+  uint8_t num_y_points, num_cb_points, num_cr_points, chroma_scaling_from_luma;   /* at most 14, 10, 10 */
+  uint8_t point_y[14][2], point_cb[10][2], point_cr[10][2];
+  uint8_t grain_scaling_minus_8, ar_coeff_lag, ar_coeff_shift_minus_6, grain_scale_shift;   /* each 0 .. 3 */
+  int8_t ar_coeffs_y[24], ar_coeffs_cb[25], ar_coeffs_cr[25];
+  uint8_t overlap_flag, clip_to_restricted_range;
+  uint8_t cb_mult, cb_luma_mult, cr_mult, cr_luma_mult;
+  uint16_t cb_offset, cr_offset;   /* 0 .. 511 */
+  uint8_t mc_identity, reserved[3];
+} av1mi_grain_params;   /* 164 bytes */
+uint32_t av1mi_grain_params_size(void);   /* sizeof(av1mi_grain_params), for a binding to check its mirror */
+
+/* out = frames with the grain of `g` added: n_frames frames in the layout and residency of av1mi_quality (tight planar frames, both host
+ * memory or both 16-byte aligned device memory), of the parameters only width, height and bit_depth - and first_frame where seeds is
+ * null - matter.  seeds[f]: frame f's grain_seed; null: the encoder's rule, 7391 + 173 (first_frame + f) mod 65536.  A table with no
+ * points and chroma_scaling_from_luma = 0 copies the input.  Null arguments, n_frames == 0, out == frames, more points than a plane
+ * may have or points out of order, a lag or shift above 3, an offset above 511 and misaligned device pointers are
+ * AV1MI_E_INVALID_ARG before a device is touched. */
+int av1mi_film_grain_synth(av1mi_ctx *ctx, const av1mi_params *params, const void *frames, uint32_t n_frames, int frames_on_device,
+                           const av1mi_grain_params *g, const uint16_t *seeds, void *out);
+/* What the frame headers of the context's last successfully encoded chunk carry, without the seed: the fixed two-point table, or the
+ * estimate's eight points (scaled by the fit's gain with a lag), the coefficients, shifts and multipliers - what a decoder of that
+ * chunk synthesises with.  AV1MI_E_INVALID_ARG without such a chunk or if it was encoded with film_grain = 0. */
+int av1mi_film_grain_params_result(const av1mi_ctx *ctx, av1mi_grain_params *g);
+/* The displayed picture's quality inside the encoder, default off: with `on` != 0 every chunk encoded with film_grain != 0 ends with
+ * the synthesis of its final reconstruction (the headers' parameters and seeds) into a buffer of the context's, and the quality pass of
+ * that against the frames as the caller gave them - not the denoised or temporally filtered ones.  The bitstream, the reconstruction
+ * and av1mi_report do not depend on the switch. */
+int av1mi_ctx_set_displayed_quality(av1mi_ctx *ctx, uint32_t on);
+/* out[f * 3 + plane] of the context's last successfully encoded chunk: zeros for a chunk encoded with the switch off or without film
+ * grain.  AV1MI_E_INVALID_ARG without such a chunk or if n_frames is not its frame count. */
+int av1mi_displayed_quality_result(const av1mi_ctx *ctx, uint32_t n_frames, av1mi_plane_quality *out);
+
 /* ---- the drop-in for `run_av1an` ---------------------------------------------------------
  * Replaces  pub fn run_av1an(params: &Av1anEncodeParams) -> Result<(), EncodeError>
  * (crates/daemon/src/encode/av1an.rs:126-139), called from JobExecutor::execute through

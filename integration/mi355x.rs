@@ -61,6 +61,18 @@ pub struct Av1miPlaneQuality {      // include/av1mi.h: av1mi_plane_quality - fi
     pub sse: u64, pub ssim_sum: i64,
     pub windows: u32, pub reserved: u32,   // in av1mi_encode_file_quality's sums `reserved` is the high half of the window count
 }
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct Av1miGrainParams {       // include/av1mi.h: av1mi_grain_params - film_grain_params without the seed
+    pub num_y_points: u8, pub num_cb_points: u8, pub num_cr_points: u8, pub chroma_scaling_from_luma: u8,
+    pub point_y: [[u8; 2]; 14], pub point_cb: [[u8; 2]; 10], pub point_cr: [[u8; 2]; 10],   // { x, y }
+    pub grain_scaling_minus_8: u8, pub ar_coeff_lag: u8, pub ar_coeff_shift_minus_6: u8, pub grain_scale_shift: u8,
+    pub ar_coeffs_y: [i8; 24], pub ar_coeffs_cb: [i8; 25], pub ar_coeffs_cr: [i8; 25],
+    pub overlap_flag: u8, pub clip_to_restricted_range: u8,
+    pub cb_mult: u8, pub cb_luma_mult: u8, pub cr_mult: u8, pub cr_luma_mult: u8,
+    pub cb_offset: u16, pub cr_offset: u16,
+    pub mc_identity: u8, pub reserved: [u8; 3],
+}
 /// Plane sums (Y, U, V) -> libaom's "all planes" SSIM, 0.8 Y + 0.1 U + 0.1 V: a window's value is a Q24 number; a plane without windows
 /// drops out and the weights are renormalised; None without any window.
 pub fn ssim_all(sum: &[Av1miPlaneQuality; 3]) -> Option<f64> {
@@ -128,6 +140,16 @@ extern "C" {
                          frames_on_device: c_int, out: *mut Av1miPlaneQuality, window_map: *mut i32) -> c_int;
     pub fn av1mi_ctx_set_quality(ctx: *mut Av1miCtx, on: u32) -> c_int;
     pub fn av1mi_quality_result(ctx: *const Av1miCtx, n_frames: u32, out: *mut Av1miPlaneQuality) -> c_int;
+    // the film-grain synthesis (AV1 spec 7.18.3, bit-exact with dav1d): `out` = `frames` with the grain of `g`, both in the layout and
+    // residency of av1mi_quality; seeds[n_frames] or null for the encoder's rule from params.first_frame.  What the last chunk's frame
+    // headers carry; the switch for the displayed picture's quality - the synthesis of every chunk's reconstruction against the caller's
+    // frames - and its result for the last chunk
+    pub fn av1mi_grain_params_size() -> u32;
+    pub fn av1mi_film_grain_synth(ctx: *mut Av1miCtx, params: *const Av1miParams, frames: *const c_void, n_frames: u32, frames_on_device: c_int,
+                                  g: *const Av1miGrainParams, seeds: *const u16, out: *mut c_void) -> c_int;
+    pub fn av1mi_film_grain_params_result(ctx: *const Av1miCtx, g: *mut Av1miGrainParams) -> c_int;
+    pub fn av1mi_ctx_set_displayed_quality(ctx: *mut Av1miCtx, on: u32) -> c_int;
+    pub fn av1mi_displayed_quality_result(ctx: *const Av1miCtx, n_frames: u32, out: *mut Av1miPlaneQuality) -> c_int;
     // the film-grain estimate of `n_frames` frames taken as one chunk: table[24] and counts[24] as [plane][bin], blocks 4 bytes per whole
     // 16x16 block and frame { bin, v_y, v_u, v_v }, every output optional (null); and the table of a context's last chunk
     pub fn av1mi_film_grain_estimate(ctx: *mut Av1miCtx, params: *const Av1miParams, frames: *const c_void, n_frames: u32, frames_on_device: c_int,
@@ -163,6 +185,7 @@ const _: () = assert!(std::mem::size_of::<Av1miParams>() == 36 * 4);
 const _: () = assert!(std::mem::size_of::<Av1miJob>() == 3 * 8 + 3 * 4 + 36 * 4);
 const _: () = assert!(std::mem::size_of::<Av1miReport>() == 120);
 const _: () = assert!(std::mem::size_of::<Av1miPlaneQuality>() == 24);
+const _: () = assert!(std::mem::size_of::<Av1miGrainParams>() == 164);
 pub fn check_layout() -> Result<(), EncodeError> {
     static ONCE: std::sync::OnceLock<bool> = std::sync::OnceLock::new();
     let ok = *ONCE.get_or_init(|| unsafe {
@@ -171,6 +194,7 @@ pub fn check_layout() -> Result<(), EncodeError> {
             && v[0] as usize == std::mem::size_of::<Av1miParams>() && v[1] as usize == std::mem::size_of::<Av1miJob>()
             && v[2] as usize == std::mem::size_of::<Av1miReport>() && v[8] as usize == std::mem::offset_of!(Av1miJob, params)
             && v[9] as usize == std::mem::offset_of!(Av1miReport, ms_h2d)
+            && av1mi_grain_params_size() as usize == std::mem::size_of::<Av1miGrainParams>()
     });
     if ok { Ok(()) } else { Err(EncodeError::Av1anFailed(7 /* AV1MI_E_UNSUPPORTED: ABI mismatch */)) }
 }

@@ -18,7 +18,13 @@ sigma 1 (8-bit scale) - what the spatial window finds no honest neighbour in.  O
 runs the denoiser's temporal term at S = 1 and S = 2, film_grain = AV1MI_FILM_GRAIN_DENOISE_TEMPORAL(N, S),
 alternated with the spatial mode (--spans; empty: none): per span the milliseconds of the denoiser's launches (the difference of "start ->
 source ready" against the estimate mode's, as ms_pass_denoise is the spatial mode's), bytes per frame, and the PSNR of the coded source
-against the clean clip.  It reports what it measures, nothing more."""
+against the clean clip.
+On the two ramp clips it also measures the picture as displayed (--no-displayed leaves it out): per mode - fixed,
+estimated, denoised, denoised + temporal, the last three also with the autoregressive fit at lag 1 - the chunk is coded with the
+displayed-quality switch on, and the line carries the PSNR and SSIM of reconstruction + synthesised grain against the frames the tool
+handed in (av1mi_displayed_quality_result) beside those of the reconstruction against the coded source, and the film-grain estimate of the
+synthesised output (av1mi_film_grain_synth, then av1mi_film_grain_estimate on it) beside the source's: the displayed picture's noise per
+luma bin.  It reports what it measures, nothing more."""
 import argparse
 import json
 import os
@@ -101,6 +107,27 @@ def psnr(av1mi, ctx, p, a, b, n):
     return av1mi.psnr_of(s, p.width, p.height, p.bit_depth, n)["all"]
 
 
+def displayed(torch, av1mi, ctx, p, est, clip, n):
+    """one chunk with the displayed-quality switch on: the displayed picture's figures against the caller's frames, the reconstruction's
+    against the coded source, and the estimate's luma table of reconstruction + synthesised grain (est: the parameters the estimate runs with)"""
+    rec, shown = torch.empty_like(clip), torch.empty_like(clip)
+    try:
+        ctx.set_displayed_quality(True)
+        ctx.set_quality(True)
+        ctx.encode_chunk(p, clip.data_ptr(), n, on_device=True, want_recon=True, recon_ptr=rec.data_ptr(), copy_out=False)
+        shown_q, coded_q = av1mi.quality_sum(ctx.displayed_quality_result(n)), av1mi.quality_sum(ctx.quality_result(n))
+        g = ctx.film_grain_params_result()
+    finally:
+        ctx.set_displayed_quality(False)
+        ctx.set_quality(False)
+    ctx.film_grain_synth(p, rec.data_ptr(), n, g, on_device=True, out_ptr=shown.data_ptr())
+    table, _, _ = ctx.film_grain_estimate(est, shown.data_ptr(), n, on_device=True, want_blocks=False)
+    size = (p.width, p.height, p.bit_depth, n)
+    return {"psnr_displayed_against_original": round(av1mi.psnr_of(shown_q, *size)["all"], 3), "ssim_displayed_against_original": round(av1mi.ssim_of(shown_q)["all"], 5),
+            "psnr_recon_against_coded_source": round(av1mi.psnr_of(coded_q, *size)["all"], 3), "ssim_recon_against_coded_source": round(av1mi.ssim_of(coded_q)["all"], 5),
+            "header_table_y": [int(g.point_y[k][1]) for k in range(g.num_y_points)], "displayed_estimate_table_y": table[0].tolist()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=5)
@@ -110,6 +137,7 @@ def main():
     ap.add_argument("--spans", default="1,2", help="the temporal term's spans to run on the clips with a clean original; empty: none")
     ap.add_argument("--level", type=int, default=20, help="N: the fixed table's level and the estimate's ceiling")
     ap.add_argument("--keyints", default="1,240")
+    ap.add_argument("--no-displayed", action="store_true", help="leave out the displayed picture's figures on the ramp clips")
     ap.add_argument("--extra", default="", help="further parameters for every run, name=value,...")
     args = ap.parse_args()
     import torch
@@ -207,6 +235,15 @@ def main():
                                                   "flat_share": round(float(fit["flat"][0]) / (n * (w // 16) * (h // 16)), 4),
                                                   "table_y": fit["table"][0].tolist(), "ms_pass_ar": round(ms[lag], 3), "ms_pass_estimate": line["ms_pass"],
                                                   "bytes_per_frame": round(nbytes[lag] / n, 1)}
+                if name in ("noise", "arnoise") and not args.no_displayed:   # the picture as displayed, per mode; the source's own estimate beside it
+                    modes = {"fixed": dict(film_grain=args.level), "estimate": dict(film_grain_estimate=args.level), "denoise": dict(film_grain_denoise=args.level),
+                             "denoise_temporal": dict(film_grain_denoise=args.level, film_grain_temporal=1)}
+                    line["source_estimate_table_y"] = table[0].tolist()
+                    line["displayed"] = {}
+                    for tag, mode in modes.items():
+                        for lag in (0,) if tag == "fixed" else (0, 1):
+                            p = av1mi.default_params(w, h, bd, film_grain_ar=lag or None, **mode, **kw)
+                            line["displayed"][tag + ("_ar1" if lag else "")] = displayed(torch, av1mi, ctx, p, est, clip, n)
                 print(json.dumps(line), flush=True)
 
 
